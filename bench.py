@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/sec of the batched Tetris-piclim board step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the line: the headline and what follows from its own numbers.
+Everything else -- CPU baseline, side figures, scaling model, the detail record -- runs only with `--full`.
+`--dump-outputs DIR` writes what the last timed step left a caller holding (dump_outputs()) for comparing two builds.
 
 A "step" is one lockstep pass of the hot path (tpl_step: one Tetris.move per board, auto-reset of finished boards from the device
 pool) over one batch of synthetic actions.  Workload = BASELINE.json configs[2] at N = 1 and configs[3] at N > 1: 1,048,576 boards
@@ -27,11 +31,12 @@ launch ("excluding one warm-up"): a launch into a queue that has run 
 not a property of a step (`timing.launch_after_synchronize_ms`).
 
 Output.  stdout carries ONE JSON line, the contract's: the headline keys first, `roofline` (the step kernel against HBM at the
-canonical 96 B/board-step of SURVEY 8(d); `frac` = this run, `frac_hbm_resident` = the same kernel where nothing fits the 256 MiB
-Infinity Cache), `cpu_baseline` (the C oracle on this box's host cores; `limited_by` says what bounds them), `scaling_model` (N = 1:
-the periods of a 2-, 4- and 8-GPU run's shards measured on this GPU, and the value and efficiency they imply) and one number per
-side figure.  The full record -- every side figure with its own roofline, bench_side.py -- goes to `--detail` (default
-gpurun_out/bench_detail_n<N>.json) and, as one line prefixed BENCH_DETAIL, to stderr; the headline alone goes there once already
+canonical 96 B/board-step of SURVEY 8(d); `frac` = this run; with --full also `frac_hbm_resident` = the same kernel where nothing
+fits the 256 MiB Infinity Cache), and with --full `cpu_baseline` (the C oracle on this box's host cores; `limited_by` says what
+bounds them), `scaling_model` (N = 1: the periods of a 2-, 4- and 8-GPU run's shards measured on this GPU, and the value and
+efficiency they imply) and one number per side figure.  The full record -- every side figure with its own roofline, bench_side.py
+-- goes to `--detail` (with --full the default is bench_out/bench_detail_n<N>.json; a plain run writes it only where --detail
+says) and, as one line prefixed BENCH_DETAIL, to stderr; with --full the headline alone goes there once already
 right behind the timed region (BENCH_HEADLINE), before any side figure runs.  Side figures never enter `value`; each
 runs under a guard (bench_side.SideFigures): an exception costs its own key, figures past --side-budget are skipped, and if one
 hangs past --side-timeout the line is printed with what there is and the process exits with status 3.  A failure INSIDE the timed
@@ -81,7 +86,7 @@ def self_launch(args):
     return subprocess.call(cmd, env=env)
 
 
-def parse_args():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
@@ -109,13 +114,22 @@ def parse_args():
                     help="seconds of side figures after which the remaining ones are skipped (the headline is never skipped)")
     ap.add_argument("--side-timeout", type=float, default=300.0,
                     help="seconds after which a side figure that is STILL running is abandoned: the line is printed, exit status 3")
-    ap.add_argument("--detail", default=None, help="where the full record goes (default gpurun_out/bench_detail_n<N>.json; '-' = nowhere)")
-    args = ap.parse_args()
+    ap.add_argument("--detail", default=None,
+                    help="where the full record goes (--full: default bench_out/bench_detail_n<N>.json; plain run: none unless given; '-' = nowhere)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline, the side figures, the scaling model and the detail record (a plain run times the headline only; "
+                         "the side-figure options above take effect only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0's boards; see dump_outputs())")
+    args = ap.parse_args(argv)
     if args.gpus < 1 or args.steps < 1 or args.warmup < 0:
         ap.error("--gpus and --steps must be positive, --warmup non-negative")
-    if args.no_side_figures:
+    if args.no_side_figures or not args.full:
         args.actor_boards = args.carved_pool = args.chunk = args.sustained = args.shard_ranks = 0
         args.no_config1 = args.no_weak_job = args.no_out_of_cache = True
+    if not args.full:
+        args.no_cpu_baseline = True
+        args.detail = args.detail or "-"
     return args
 
 
@@ -134,6 +148,42 @@ def traffic_of(n):
                                   f"{tj.get('commit')}, source digest {str(tj.get('source_digest'))[:12]}), scaled to {n} boards"}
     except Exception:                 # noqa: BLE001
         return {"traffic": None, "traffic_decomposed": None, "traffic_stale": None, "traffic_source": None}
+
+
+DUMP_BOARDS = 1 << 20                   # --dump-outputs: per-board arrays of at most this many boards, a seeded sample beyond
+DUMP_ROWS_BOARDS = 1 << 16              # ... and the 20 rows of at most this many boards (46 MiB in all at the most)
+DUMP_SAMPLE_SEED = 20251016             # the sample is fixed: the same boards in every run of the same arguments
+
+
+def dump_outputs(out_dir, env, reward, done, mean_return):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as out_dir/<name>.npy -- that step's `reward`
+    and `done`, the boards as packed_state() returns them (`rows`, `cur`, `nxt`, `lines`, `moves`, `state`, `pieces_left`), the
+    handle's episode counters (`stats`: episodes, lines, wins, topouts) and the job's `mean_episodic_return` (NaN before the first
+    episode ends).  Float32, float64 where float32 could round.  Per-board arrays cover at most DUMP_BOARDS boards and `rows` at
+    most DUMP_ROWS_BOARDS; past that they hold a seeded sample, whose board indices go along (`board_index`, `rows_index`)."""
+    import numpy as np
+    n = reward.numel()
+    state = {k: v.cpu().numpy() for k, v in env.packed_state().items()}
+    stats = env.stats()
+
+    def sample(k):
+        return None if n <= k else np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, k, replace=False))
+    arrays = {"reward": reward.cpu().numpy(), "done": done.cpu().numpy()}
+    arrays.update((k, state[k]) for k in ("cur", "nxt", "lines", "moves", "state", "pieces_left"))
+    idx = sample(DUMP_BOARDS)
+    arrays = {k: (v if idx is None else v[idx]).astype(np.float32) for k, v in arrays.items()}
+    ridx = sample(DUMP_ROWS_BOARDS)
+    rows = state["rows"].view(np.uint16)
+    arrays["rows"] = (rows if ridx is None else rows[ridx]).astype(np.float32)
+    for name, ix in (("board_index", idx), ("rows_index", ridx)):
+        if ix is not None:
+            arrays[name] = ix.astype(np.float64)
+    arrays["stats"] = np.array([stats[k] for k in ("episodes", "lines", "wins", "topouts")], dtype=np.float64)
+    arrays["mean_episodic_return"] = np.array([np.nan if mean_return is None else mean_return], dtype=np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def compact(d):
@@ -250,13 +300,15 @@ def main():
         else:
             dist.init_process_group(backend)
         # the ranks' agreements around the side figures travel over a gloo group of HOST tensors (SideFigures); if that group
-        # cannot be made, they fall back to the job's own group and device tensors -- the headline must not depend on it
-        try:
-            ctl = dist.new_group(backend="gloo", timeout=datetime.timedelta(seconds=max(600.0, 2 * args.side_timeout)))
-            dist.all_reduce(torch.zeros(1, dtype=torch.float64), group=ctl)
-            ctl_note = "gloo group of host tensors"
-        except Exception as e:        # noqa: BLE001
-            ctl, ctl_note = None, f"the job's own group, device tensors (no gloo control group: {type(e).__name__}: {e})"[:300]
+        # cannot be made, they fall back to the job's own group and device tensors -- the headline must not depend on it.
+        # A plain run has no side figures and makes no such group.
+        if args.full:
+            try:
+                ctl = dist.new_group(backend="gloo", timeout=datetime.timedelta(seconds=max(600.0, 2 * args.side_timeout)))
+                dist.all_reduce(torch.zeros(1, dtype=torch.float64), group=ctl)
+                ctl_note = "gloo group of host tensors"
+            except Exception as e:        # noqa: BLE001
+                ctl, ctl_note = None, f"the job's own group, device tensors (no gloo control group: {type(e).__name__}: {e})"[:300]
     assert torch.cuda.is_available(), "bench.py needs a GPU (there is no CPU path)"
     dev = torch.device("cuda", local)
     torch.cuda.set_device(dev)
@@ -354,20 +406,27 @@ def main():
     barrier()
     torch.cuda.synchronize(dev)
     t3 = time.perf_counter()
+    if args.dump_outputs and rank == 0:                           # before anything else moves the boards
+        last = replays[-1].steps - 1 if mode == "graph" else None  # a replayed graph wrote step k of its chunk into rs[k], ds[k]
+        dump_outputs(args.dump_outputs, env, reward if last is None else rs[last], done if last is None else ds[last],
+                     mean_return if episodes else None)
     host_issue_us = (h1 - h0) / K * 1e6
     host_call_us = host_issue_us
-    if mode == "graph":                                           # what a tpl_step() call costs the host, measured apart
-        torch.cuda.synchronize(dev)
-        h0 = time.perf_counter()
-        for t in range(64):
-            env.step_into(rows_of[t % S], reward, done)
-        host_call_us = (time.perf_counter() - h0) / 64 * 1e6
-        torch.cuda.synchronize(dev)
+    if mode == "graph":                                           # what a tpl_step() call costs the host, measured apart (--full)
+        host_call_us = None
+        if args.full:
+            torch.cuda.synchronize(dev)
+            h0 = time.perf_counter()
+            for t in range(64):
+                env.step_into(rows_of[t % S], reward, done)
+            host_call_us = (time.perf_counter() - h0) / 64 * 1e6
+            torch.cuda.synchronize(dev)
     per_rank_ms = every_rank(ev_a.elapsed_time(ev_c) / K)
     steady_ms = max(per_rank_ms)                                  # max over ranks
     wake_ms = max(every_rank(ev_w.elapsed_time(ev_a))) if W >= 1 else None
     wall_ms, collective_ms = max(every_rank((t3 - t0) * 1e3)), max(every_rank((t2 - t1) * 1e3))
-    host_call_us, host_issue_us = max(every_rank(host_call_us)), max(every_rank(host_issue_us))
+    host_issue_us = max(every_rank(host_issue_us))
+    host_call_us = max(every_rank(host_call_us)) if host_call_us is not None else None
     value = float(total) / (steady_ms * 1e-3)
 
     per_rank_roofline = []                                        # each rank's kernel priced on the boards of ITS shard
@@ -383,7 +442,7 @@ def main():
                                     "out_of_cache": None, "cpu_baseline": None},
                               figures={"actor_loop": None, "config_supply": None, "config1_run": None, "weak_scaling_job": None,
                                        "shard_run": None, "scaling_model": None})
-    detail_path = args.detail or os.path.join(ROOT, "gpurun_out", f"bench_detail_n{world}.json")
+    detail_path = args.detail or os.path.join(ROOT, "bench_out", f"bench_detail_n{world}.json")
 
     def record(abandoned=None):
         """The full record, from what has been measured so far."""
@@ -413,7 +472,7 @@ def main():
                        "per_rank_ms_per_step": per_rank_ms, "wall_ms_per_step": wall_ms / K, "collective_ms": collective_ms,
                        "launch_after_synchronize_ms": wake_ms, "host_call_us": host_call_us, "host_issue_us_per_step": host_issue_us,
                        "host_call_is": "what one tpl_step() call costs the host thread (max over ranks)"
-                                       + ("" if mode == "eager" else ", measured over 64 eager calls behind the region"),
+                                       + ("" if mode == "eager" else ", measured over 64 eager calls behind the region (--full only)"),
                        "host_bound": bool(host_issue_us > 0.9 * steady_ms * 1e3)},
             "ranks_seen": dist.get_world_size() if dist_on else 1, "backend": dist.get_backend() if dist_on else None,
             "per_rank_roofline": per_rank_roofline,
@@ -464,6 +523,12 @@ def main():
         print("BENCH_DETAIL " + json.dumps(full), file=sys.stderr, flush=True)
         write_line(json.dumps(compact(full)))
 
+    if not args.full:                                             # a plain run: the headline is all there is
+        env.terminate()
+        emit()
+        if dist_on:
+            dist.destroy_process_group()
+        return
     if rank == 0:
         # the headline on record BEFORE any side figure runs (stderr and the detail file; stdout keeps its one line for the end):
         # should a side figure take the process down instead of raising, the measurement is not lost with it

@@ -72,7 +72,7 @@ def _bench(gpus, extra=(), boards=65536, inject=None, base=("--sustained", "100"
     with tempfile.TemporaryDirectory() as tmp:
         detail = os.path.join(tmp, "detail.json")
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", str(steps), "--warmup", "5", "--boards", str(boards),
-               "--detail", detail, *base, *extra]
+               "--detail", detail, "--full", *base, *extra]
         res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
         assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-3000:]
         full = json.load(open(detail))

@@ -5,10 +5,13 @@
 # sustained step figure and fused rollout.  The rule since round 5: no change to tpl_device.h, step_kernel,
 # rollout_kernel or carve_kernel without >= 5 % here and a green `pytest -m gpu`.
 ARGS=${AB_ARGS:-"--no-cpu-baseline --actor-boards 0 --carved-pool 0 --no-config1 --no-out-of-cache --shard-ranks 0 --steps 500 --warmup 50"}
+BASE_ARGS=$ARGS
 for round in 1 2 3; do
   for v in "$@"; do
     tree=.; def=$v
     if [ "$v" = "old" ]; then tree=_ab/old; def=""; fi
+    # the sustained pass and the fused rollout run under --full; a tree from before that option runs them by default
+    ARGS="$(grep -q '"--full"' $tree/bench.py && echo --full) $BASE_ARGS"
     (cd $tree && TPL_EXTRA_DEFINE=$def python bench.py $ARGS --detail /tmp/ab_detail.json 2>/dev/null | python -c "
 import json,os,sys
 for l in sys.stdin:
