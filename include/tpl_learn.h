@@ -1,0 +1,75 @@
+/*
+ * tpl_learn.h -- C ABI of the learner library (libtpl_learn.so): a packed replay ring on the device and device-side
+ * packing of a PolicyMLP's parameters into the three policy images of libtetris_piclim.so.
+ *
+ * Conventions (as include/tetris_piclim.h)
+ *   - every function returns 0 on success or a negative tpl_status (TPL_ERR_ARG, TPL_ERR_HIP, ...);
+ *     tpl_learn_last_error() gives the message of the calling thread's last failure.
+ *   - every data pointer is a DEVICE pointer; `stream` is a hipStream_t passed as void* (NULL = the default stream).
+ *     Calls only enqueue work; argument errors come back before any HIP call is made.
+ *
+ * Replay record (TPL_REPLAY_RECORD_BYTES = 80, 16-byte aligned), one per transition (s, a, r, done, s'):
+ *   bytes  0..15  s  plane A      16..31  s  plane B         (the 32-byte state of tpl_actor_rollout's states_a / states_b)
+ *         32..47  s' plane A      48..63  s' plane B
+ *         64..67  reward f32      68 action u8   69 done u8   70..79 zero
+ * Ring indexing: a push of a [T][n] chunk at host-side head h writes transition (t, board i) to slot (h + t*n + i) mod capacity.
+ */
+#ifndef TPL_LEARN_H
+#define TPL_LEARN_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "tetris_piclim.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define TPL_REPLAY_RECORD_BYTES 80
+
+typedef enum { TPL_IMAGE_BF16 = 0, TPL_IMAGE_F32 = 1, TPL_IMAGE_SPLIT = 2 } tpl_image_kind;
+
+/* Message of the last failure of this library on this thread ("" if none). */
+const char* tpl_learn_last_error(void);
+
+/* Bytes of one replay record (80). */
+size_t tpl_replay_record_bytes(void);
+
+/* Appends one tpl_actor_rollout chunk of `num_steps` x `n` transitions to `ring` ([capacity] records).
+ * actions u8 / rewards f32 / dones u8 [num_steps][n]; states_a / states_b [num_steps][n] 16-byte words (the state BEFORE
+ * each step); plane_a / plane_b: the environment's resident planes after the chunk (tpl_state_ptrs), i.e. s' of the last
+ * step.  s' of step t < num_steps - 1 is the recorded state of step t + 1 -- so the environment must auto-reset: the s' of
+ * a done transition is then the freshly reset board, which the done flag masks.  Transition (t, i) lands in slot
+ * (head + t*n + i) mod capacity; num_steps * n must not exceed capacity (no slot is written twice in one push). */
+int tpl_replay_push(void* ring, int64_t capacity, int64_t head, int32_t num_steps, int64_t n, const uint8_t* actions,
+                    const float* rewards, const uint8_t* dones, const void* states_a, const void* states_b,
+                    const void* plane_a, const void* plane_b, void* stream);
+
+/* One minibatch of `batch` transitions drawn uniformly with replacement from slots [0, size) of the ring: draw i takes
+ * slot tpl_replay_index(seed, update, i, size).  Writes, for every draw i:
+ *   obs [batch][217] of `dtype` (TPL_F32 / TPL_BF16): the observation of s, bit-identical to tpl_expand_states (L, M);
+ *   next_a / next_b [batch] 16-byte words: the planes of s' (e.g. the resident planes of a `batch`-board environment);
+ *   action u8, reward f32, done u8 [batch]; index i64 [batch] the slot drawn (optional, may be NULL).
+ * `obs` must be 16-byte aligned. */
+int tpl_replay_sample(const void* ring, int64_t capacity, int64_t size, int64_t batch, uint64_t seed, uint64_t update,
+                      int32_t L, int32_t M, void* obs, int32_t dtype, void* next_a, void* next_b, uint8_t* action,
+                      float* reward, uint8_t* done, int64_t* index, void* stream);
+
+/* The sampling hash on the host (for tests and callers that want to know the draws): splitmix64 of the stream keyed by
+ * (seed, update) at position i, mapped to [0, size) by the high half of a 64 x 64-bit product.  size < 2^32. */
+int64_t tpl_replay_index(uint64_t seed, uint64_t update, int64_t i, int64_t size);
+
+/* Device-side tpl_policy_pack / tpl_policy_pack_f32 / tpl_policy_pack_split: the ten float32 parameter arrays of
+ * Model(217, 14) (device pointers, torch layout) -> the image of that kind (device, 16-byte aligned), byte-identical to the
+ * host packer's.  tpl_learn_image_bytes(kind) equals tpl_policy_image_bytes[_f32|_split](). */
+size_t tpl_learn_image_bytes(int32_t kind);
+int tpl_learn_pack(int32_t kind, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
+                   const float* b3, const float* w4, const float* b4, const float* w5, const float* b5, void* image,
+                   void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* TPL_LEARN_H */

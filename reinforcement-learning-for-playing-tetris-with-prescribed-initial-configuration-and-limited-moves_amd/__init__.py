@@ -11,7 +11,8 @@ from ._lib import (LIB_PATH, SYMBOLS, TplError, build_library, carve, forward_ge
                    shape_info)
 
 __all__ = ["BatchedTetris", "Tetris", "Snapshot", "OBS_DIM", "NUM_ACTIONS", "RUNNING", "WON", "LOST", "TplError",
-           "RandomPieceGenerator", "get_tetromino", "piece_translations", "translate", "carve", "build_library", "shape_info", "generate_configs", "forward_generate", "pack_policy", "LIB_PATH", "SYMBOLS"]
+           "RandomPieceGenerator", "get_tetromino", "piece_translations", "translate", "carve", "build_library", "shape_info", "generate_configs", "forward_generate", "pack_policy", "LIB_PATH", "SYMBOLS", "DQNLearner",
+           "ReplayRing"]
 
 
 def __getattr__(name):
@@ -28,4 +29,9 @@ def __getattr__(name):
         return getattr(importlib.import_module(__name__ + ".pieces"), name)
     if name in ("Actor", "PolicyMLP"):
         return getattr(importlib.import_module(__name__ + ".actor"), name)
+    if name in ("DQNLearner", "ReplayRing"):
+        # the learner library (libtpl_learn.so) is built and loaded only here, on first use
+        return getattr(importlib.import_module(__name__ + ".learn"), name)
+    if name in ("learn", "_learn_lib"):
+        return importlib.import_module(__name__ + "." + name)
     raise AttributeError(name)

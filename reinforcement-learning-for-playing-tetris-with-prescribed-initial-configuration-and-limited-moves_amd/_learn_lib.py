@@ -1,0 +1,180 @@
+"""Build and bind the learner's C-ABI library (include/tpl_learn.h) with ctypes: the packed replay ring and the device-side
+policy packers (csrc/learn/).
+
+A library of its own (<repo>/lib/libtpl_learn.so), so that the environment library and its measured sources stay as they
+are: it includes the environment's device headers read-only and links nothing of libtetris_piclim.so.  Built, stamped and
+locked as _lib.build_library builds the environment library; its digest covers its units and every header they include.
+Nothing here is loaded by `import tetris_piclim` or by any environment entry point.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+
+from . import _lib
+from ._lib import TplError, _hipcc
+
+_LEARN_CSRC = os.path.join(_lib._CSRC, "learn")
+LEARN_LIB_PATH = os.path.join(_lib._LIBDIR, "libtpl_learn.so")
+_UNITS = [os.path.join(_LEARN_CSRC, f) for f in ("replay.hip", "pack.hip")]
+
+# entry points declared in include/tpl_learn.h (tests check that the .so exports every one of them)
+LEARN_SYMBOLS = [
+    "tpl_learn_last_error", "tpl_replay_record_bytes", "tpl_replay_push", "tpl_replay_sample", "tpl_replay_index",
+    "tpl_learn_image_bytes", "tpl_learn_pack",
+]
+
+IMAGE_KINDS = {"bf16": 0, "f32": 1, "split": 2}
+RECORD_BYTES = 80
+
+
+def _sources() -> list:
+    """The units and, transitively, every quoted #include of theirs (the environment headers among them)."""
+    seen, todo = [], list(_UNITS)
+    while todo:
+        path = os.path.normpath(todo.pop(0))
+        if path in seen:
+            continue
+        seen.append(path)
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(path).read(), flags=re.M):
+            todo.append(os.path.join(os.path.dirname(path), inc))
+    return sorted(seen)
+
+
+def _source_digest() -> str:
+    import hashlib
+    h = hashlib.sha256()
+    for path in _sources():
+        with open(path, "rb") as f:
+            h.update(os.path.relpath(path, _lib._ROOT).encode() + b"\0" + f.read())
+    return h.hexdigest()
+
+
+def build_library(force: bool = False, verbose: bool = False) -> str:
+    """hipcc --offload-arch=gfx950 -> <repo>/lib/libtpl_learn.so; stale by digest, concurrent builders serialise on a lock."""
+    stamp = LEARN_LIB_PATH + ".sha256"
+    digest = _source_digest()
+
+    def fresh():
+        return os.path.exists(LEARN_LIB_PATH) and os.path.exists(stamp) and open(stamp).read().strip() == digest
+
+    if not force and fresh():
+        return LEARN_LIB_PATH
+    import fcntl
+    os.makedirs(_lib._LIBDIR, exist_ok=True)
+    with open(LEARN_LIB_PATH + ".lock", "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        try:
+            if force or not fresh():
+                tmp = f"{LEARN_LIB_PATH}.{os.getpid()}.tmp"
+                cmd = [_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-o", tmp] + _UNITS
+                res = subprocess.run(cmd, capture_output=True, text=True)
+                if res.returncode != 0:
+                    raise RuntimeError("hipcc failed:\n" + res.stdout + res.stderr)
+                os.replace(tmp, LEARN_LIB_PATH)
+                with open(stamp + ".tmp", "w") as f:
+                    f.write(digest)
+                os.replace(stamp + ".tmp", stamp)
+                if verbose:
+                    print("built", LEARN_LIB_PATH)
+        finally:
+            fcntl.flock(lock, fcntl.LOCK_UN)
+    return LEARN_LIB_PATH
+
+
+_handle = None
+
+
+def lib() -> C.CDLL:
+    global _handle
+    if _handle is not None:
+        return _handle
+    import torch  # noqa: F401  -- torch's HIP runtime first (_lib.lib() says why)
+    L = C.CDLL(build_library())
+    vp, i32, i64, u64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_size_t
+    L.tpl_learn_last_error.restype = C.c_char_p
+    L.tpl_learn_last_error.argtypes = []
+    L.tpl_replay_record_bytes.restype = sz
+    L.tpl_replay_record_bytes.argtypes = []
+    L.tpl_replay_push.argtypes = [vp, i64, i64, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.tpl_replay_sample.argtypes = [vp, i64, i64, i64, u64, u64, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.tpl_replay_index.restype = i64
+    L.tpl_replay_index.argtypes = [u64, u64, i64, i64]
+    L.tpl_learn_image_bytes.restype = sz
+    L.tpl_learn_image_bytes.argtypes = [i32]
+    L.tpl_learn_pack.argtypes = [i32] + [vp] * 12
+    for name in ("tpl_replay_push", "tpl_replay_sample", "tpl_learn_pack"):
+        getattr(L, name).restype = i32
+    _handle = L
+    return L
+
+
+def check(status: int) -> None:
+    if status != 0:
+        raise TplError(f"tpl_learn status {status}: {lib().tpl_learn_last_error().decode()}")
+
+
+# ------------------------------------------------------------------------------------------------ the sampling hash
+_GOLDEN = np.uint64(0x9E3779B97F4A7C15)
+_M32 = np.uint64(0xFFFFFFFF)
+
+
+def _mix64(z):
+    z = np.asarray(z, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def replay_indices(seed: int, update: int, batch: int, size: int) -> np.ndarray:
+    """The slots tpl_replay_sample draws (int64 [batch]): draw i is position i + 1 of the splitmix64 stream keyed by
+    (seed, update), h, mapped to floor(h * size / 2^64) -- computed from 32-bit halves, exact for size < 2^32."""
+    if not 1 <= size < (1 << 32):
+        raise ValueError("size must be in [1, 2^32)")
+    with np.errstate(over="ignore"):
+        key = _mix64(np.uint64(seed % (1 << 64)) + _GOLDEN * np.uint64((update + 1) % (1 << 64)))
+        h = _mix64(key + _GOLDEN * (np.arange(batch, dtype=np.uint64) + np.uint64(1)))
+        s = np.uint64(size)
+        hi, lo = h >> np.uint64(32), h & _M32
+        return ((hi * s + ((lo * s) >> np.uint64(32))) >> np.uint64(32)).astype(np.int64)
+
+
+# ------------------------------------------------------------------------------------------------ device packing
+def policy_tensors(model) -> list:
+    """The ten float32 parameter tensors of a PolicyMLP, contiguous, in tpl_learn_pack's argument order."""
+    return [t.detach().contiguous() for layer in (model.layer1, model.layer2, model.layer3, model.layer4, model.layer5)
+            for t in (layer.weight, layer.bias)]
+
+
+_SHAPES = [(128, 217), (128,), (128, 128), (128,), (128, 128), (128,), (128, 128), (128,), (14, 128), (14,)]
+
+
+def pack_policy_device(params, kind: str = "split", out=None):
+    """tpl_learn_pack: ten float32 device tensors (w1, b1, ..., w5, b5; torch layout) -> the policy image of `kind`
+    ("bf16", "f32" or "split") as a uint8 device tensor, byte-identical to _lib.pack_policy's.  Enqueued on the current
+    stream; no host sync."""
+    import torch
+    if kind not in IMAGE_KINDS:
+        raise ValueError(f"kind must be one of {sorted(IMAGE_KINDS)}")
+    params = list(params)
+    if len(params) != 10:
+        raise ValueError("pack_policy_device takes the ten parameter tensors of Model(217, 14)")
+    dev = params[0].device
+    for t, shape in zip(params, _SHAPES):
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != shape or t.device != dev
+                or dev.type != "cuda" or not t.is_contiguous()):
+            raise ValueError(f"policy parameters must be contiguous float32 {_SHAPES} on one GPU")
+    L = lib()
+    nbytes = L.tpl_learn_image_bytes(IMAGE_KINDS[kind])
+    if out is None:
+        out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    if out.dtype != torch.uint8 or tuple(out.shape) != (nbytes,) or out.device != dev or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous uint8 tensor of {nbytes} bytes on {dev}")
+    stream = torch._C._cuda_getCurrentRawStream(dev.index)
+    check(L.tpl_learn_pack(IMAGE_KINDS[kind], *[t.data_ptr() for t in params], out.data_ptr(), stream))
+    return out

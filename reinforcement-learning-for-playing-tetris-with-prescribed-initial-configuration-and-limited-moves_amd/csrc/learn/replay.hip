@@ -1,0 +1,177 @@
+// replay.hip -- the packed replay ring: push one actor_rollout chunk, sample one minibatch.
+//
+// A transition is an 80-byte record (include/tpl_learn.h): s and s' as the environment's 32-byte resident state, then the
+// reward, action and done.  Against the 868-byte float32 observation that is 2 x 32 B for both states: a ring of 2^24
+// transitions is 1.3 GB.  The observation of s is made only when a minibatch is drawn, with the environment's own two
+// stages (tpl_observe.h), so it is bit-identical to tpl_expand_states of the same planes; s' leaves as planes, to be
+// read by the target network's policy kernel in place.
+//
+//   push    one lane per transition (t, i): three 16-byte loads of the chunk (s, and s' = the state recorded at t + 1,
+//           or the resident planes after the chunk for the last step), the three scalars, five 16-byte stores.
+//           Consecutive lanes write consecutive records, so every wave store covers 1,280 contiguous bytes.
+//   sample  one lane per draw: the slot is a hash of (seed, update, i), the record comes in as five 16-byte loads
+//           (random slots: the 80 B are the whole traffic of the read side), s is turned into 217 feature bytes in LDS
+//           and leaves as the wave's contiguous span of the observation with 16-byte non-temporal stores -- observe.hip's
+//           scheme, so a draw costs 80 B read and 868 B (f32) / 434 B (bf16) + 32 B + 6 B written.
+#include "tpl_learn_internal.h"
+#include "../tpl_observe.h"
+
+#include <cstdarg>
+#include <cstdio>
+
+namespace tpl_learn {
+
+static thread_local char g_err[512] = "";
+
+int fail_msg(int code, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+    return code;
+}
+
+namespace {
+
+using tpl::obs::kObsWaves;
+using tpl::obs::kWaveLds;
+
+constexpr int kPushBlock = 256;
+constexpr int64_t kMaxSize = (int64_t)1 << 32;     // the slot map takes size below 2^32 (343 GB of records: beyond HBM)
+
+struct PushArgs {
+    uint4* ring;                 // [capacity][5]
+    int64_t capacity, head, total, n;
+    const uint8_t* actions;
+    const float* rewards;
+    const uint8_t* dones;
+    const uint4* states_a;
+    const uint4* states_b;
+    const uint4* plane_a;
+    const uint4* plane_b;
+};
+
+__global__ __launch_bounds__(kPushBlock) void replay_push_kernel(const PushArgs p) {
+    const int64_t j = (int64_t)blockIdx.x * kPushBlock + threadIdx.x;     // transition t * n + i of the chunk
+    if (j >= p.total) return;
+    const uint4 sa = p.states_a[j], sb = p.states_b[j];
+    const int64_t nx = j + p.n;
+    uint4 na, nb;
+    if (nx < p.total) {
+        na = p.states_a[nx]; nb = p.states_b[nx];
+    } else {                                                              // the last step: s' is the resident state
+        const int64_t i = j - (p.total - p.n);
+        na = p.plane_a[i]; nb = p.plane_b[i];
+    }
+    const uint4 tail = make_uint4(__float_as_uint(p.rewards[j]), (uint32_t)p.actions[j] | ((uint32_t)p.dones[j] << 8), 0u, 0u);
+    int64_t slot = p.head + j;                                            // head < capacity and j < capacity
+    if (slot >= p.capacity) slot -= p.capacity;
+    uint4* const rec = p.ring + slot * 5;
+    rec[0] = sa; rec[1] = sb; rec[2] = na; rec[3] = nb; rec[4] = tail;
+}
+
+struct SampleArgs {
+    const uint4* ring;
+    int64_t size, batch;
+    uint64_t key;
+    uint32_t L, M;
+    void* obs;
+    uint4* next_a;
+    uint4* next_b;
+    uint8_t* action;
+    float* reward;
+    uint8_t* done;
+    int64_t* index;
+};
+
+template <typename T>
+__global__ __launch_bounds__(64 * kObsWaves) void replay_sample_kernel(const SampleArgs p) {
+    __shared__ __attribute__((aligned(16))) uint8_t s_rows[kObsWaves][kWaveLds];
+    const int lane = threadIdx.x & 63;
+    const int64_t base = ((int64_t)blockIdx.x * kObsWaves + (threadIdx.x >> 6)) * 64;     // the wave's first draw
+    if (base >= p.batch) return;                                                          // wave-uniform
+    const int count = (int)((p.batch - base) < 64 ? (p.batch - base) : 64);
+    uint8_t* const rows = s_rows[threadIdx.x >> 6];
+    int lines_left = 0;
+    if (lane < count) {
+        const int64_t i = base + lane;
+        const int64_t slot = replay_slot(p.key, (uint64_t)i, (uint64_t)p.size);
+        const uint4* const rec = p.ring + slot * 5;
+        const uint4 sa = rec[0], sb = rec[1], na = rec[2], nb = rec[3], tail = rec[4];
+        tpl::Board s;
+        tpl::unpack_board(sa, sb, s);
+        lines_left = tpl::obs::board_to_bytes(s, p.L, p.M, rows, lane);
+        p.next_a[i] = na;
+        p.next_b[i] = nb;
+        p.reward[i] = __uint_as_float(tail.x);
+        p.action[i] = (uint8_t)(tail.y & 0xFFu);
+        p.done[i] = (uint8_t)((tail.y >> 8) & 0xFFu);
+        if (p.index) p.index[i] = slot;
+    }
+    tpl::obs::store_span<T>(rows, lane, count, base, lines_left, (T*)p.obs);
+}
+
+}  // namespace
+}  // namespace tpl_learn
+
+using namespace tpl_learn;
+
+extern "C" const char* tpl_learn_last_error(void) { return g_err; }
+
+extern "C" size_t tpl_replay_record_bytes(void) { return (size_t)TPL_REPLAY_RECORD_BYTES; }
+
+extern "C" int64_t tpl_replay_index(uint64_t seed, uint64_t update, int64_t i, int64_t size) {
+    if (size < 1 || size >= kMaxSize || i < 0) return -1;
+    return replay_slot(replay_key(seed, update), (uint64_t)i, (uint64_t)size);
+}
+
+extern "C" int tpl_replay_push(void* ring, int64_t capacity, int64_t head, int32_t num_steps, int64_t n, const uint8_t* actions,
+                               const float* rewards, const uint8_t* dones, const void* states_a, const void* states_b,
+                               const void* plane_a, const void* plane_b, void* stream) {
+    if (!ring || !actions || !rewards || !dones || !states_a || !states_b || !plane_a || !plane_b)
+        return fail_msg(TPL_ERR_ARG, "tpl_replay_push: null pointer");
+    if (capacity < 1 || capacity >= kMaxSize) return fail_msg(TPL_ERR_ARG, "tpl_replay_push: capacity must be in [1, 2^32)");
+    if (num_steps < 1 || n < 1) return fail_msg(TPL_ERR_ARG, "tpl_replay_push: num_steps and n must be positive");
+    if ((int64_t)num_steps * n > capacity)
+        return fail_msg(TPL_ERR_ARG, "tpl_replay_push: a chunk of %d x %lld transitions exceeds the capacity %lld", num_steps,
+                        (long long)n, (long long)capacity);
+    if (head < 0 || head >= capacity) return fail_msg(TPL_ERR_ARG, "tpl_replay_push: head must be in [0, capacity)");
+    if (((uintptr_t)ring & 15u) || ((uintptr_t)states_a & 15u) || ((uintptr_t)states_b & 15u) || ((uintptr_t)plane_a & 15u) ||
+        ((uintptr_t)plane_b & 15u))
+        return fail_msg(TPL_ERR_ARG, "tpl_replay_push: ring, states and planes must be 16-byte aligned");
+    PushArgs p{};
+    p.ring = (uint4*)ring; p.capacity = capacity; p.head = head; p.total = (int64_t)num_steps * n; p.n = n;
+    p.actions = actions; p.rewards = rewards; p.dones = dones;
+    p.states_a = (const uint4*)states_a; p.states_b = (const uint4*)states_b;
+    p.plane_a = (const uint4*)plane_a; p.plane_b = (const uint4*)plane_b;
+    const dim3 grid((unsigned)((p.total + kPushBlock - 1) / kPushBlock)), block(kPushBlock);
+    hipLaunchKernelGGL(replay_push_kernel, grid, block, 0, (hipStream_t)stream, p);
+    TPL_LEARN_HIP(hipGetLastError());
+    return TPL_OK;
+}
+
+extern "C" int tpl_replay_sample(const void* ring, int64_t capacity, int64_t size, int64_t batch, uint64_t seed, uint64_t update,
+                                 int32_t L, int32_t M, void* obs, int32_t dtype, void* next_a, void* next_b, uint8_t* action,
+                                 float* reward, uint8_t* done, int64_t* index, void* stream) {
+    if (!ring || !obs || !next_a || !next_b || !action || !reward || !done)
+        return fail_msg(TPL_ERR_ARG, "tpl_replay_sample: null pointer");
+    if (capacity < 1 || capacity >= kMaxSize) return fail_msg(TPL_ERR_ARG, "tpl_replay_sample: capacity must be in [1, 2^32)");
+    if (size < 1 || size > capacity) return fail_msg(TPL_ERR_ARG, "tpl_replay_sample: size must be in [1, capacity] (an empty ring has nothing to draw)");
+    if (batch < 1) return fail_msg(TPL_ERR_ARG, "tpl_replay_sample: batch must be positive");
+    if (batch > ((int64_t)1 << 31) / TPL_OBS_DIM) return fail_msg(TPL_ERR_ARG, "tpl_replay_sample: batch too large");
+    if (L < 1 || L > 255 || M < 1 || M > 255) return fail_msg(TPL_ERR_ARG, "tpl_replay_sample: L and M must be in [1, 255]");
+    if (dtype != TPL_F32 && dtype != TPL_BF16) return fail_msg(TPL_ERR_ARG, "tpl_replay_sample: unknown observation dtype %d", dtype);
+    if (((uintptr_t)ring & 15u) || ((uintptr_t)obs & 15u) || ((uintptr_t)next_a & 15u) || ((uintptr_t)next_b & 15u))
+        return fail_msg(TPL_ERR_ARG, "tpl_replay_sample: ring, obs and planes must be 16-byte aligned");
+    SampleArgs p{};
+    p.ring = (const uint4*)ring; p.size = size; p.batch = batch; p.key = replay_key(seed, update);
+    p.L = (uint32_t)L; p.M = (uint32_t)M; p.obs = obs; p.next_a = (uint4*)next_a; p.next_b = (uint4*)next_b;
+    p.action = action; p.reward = reward; p.done = done; p.index = index;
+    const dim3 grid((unsigned)((batch + 64 * kObsWaves - 1) / (64 * kObsWaves))), block(64 * kObsWaves);
+    if (dtype == TPL_F32)
+        hipLaunchKernelGGL(replay_sample_kernel<float>, grid, block, 0, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL(replay_sample_kernel<__hip_bfloat16>, grid, block, 0, (hipStream_t)stream, p);
+    TPL_LEARN_HIP(hipGetLastError());
+    return TPL_OK;
+}

@@ -1,0 +1,253 @@
+"""DQN on the batched environment: the algorithm of the upstream model/train.py (the PyTorch DQN tutorial's
+`optimize_model`, with its constants as defaults), over a packed replay ring that lives on the device.
+
+Data path of one round (collect + update):
+
+    actor_rollout(split image of the online net, epsilon)      one launch, T steps x N boards, records the 32-B states
+    tpl_replay_push                                             the chunk -> 80-B records (s, a, r, done, s') in the ring
+    tpl_replay_sample                                           B draws -> obs(s) [B, 217], s' as planes of a B-board env, a, r, done
+    tpl_policy_act_split(scratch env, target image)             Q'(s') [B, 14] at float32 accuracy on the bf16 matrix pipe
+    torch autograd                                              Q(s) of the online net, Huber loss, AdamW(amsgrad) step
+    soft update + tpl_learn_pack (split)                        the target image repacked on the device, no host copy
+
+Factored Q over the 40 actions.  Model(217, 14) has 14 outputs for 40 actions (rotation r in 0..3, location l in 0..9,
+action = 10 r + l); the environment's decode (tpl_decode_actions, and pick_action inside the policy kernels) takes
+argmax(out[0:4]) as the rotation and argmax(out[4:14]) as the location.  The learner scores an action as the sum of its two
+heads,
+
+    Q(s, a) = out[a // 10] + out[4 + a % 10],      so      max_a Q(s, a) = max(out[0:4]) + max(out[4:14]),
+
+whose arg-max is exactly the decoded action: the actor's greedy choice is the learner's greedy choice.  The 14 outputs cannot
+score 40 actions any other way that agrees with that decode (a score that is not monotone in both heads separately would
+have an arg-max the decode does not return).
+
+TD target  y = r + gamma * (1 - done) * (max Q'_rot(s') + max Q'_loc(s')), in float32; loss SmoothL1 (Huber, delta 1)
+between Q(s, a) and y; gradients clipped to +-100 by value; AdamW(lr, amsgrad=True); after every update the soft update
+theta' <- tau * theta + (1 - tau) * theta' and a repack of the target image.
+
+Epsilon schedule  eps_end + (eps_start - eps_end) * exp(-steps_done / eps_decay), where steps_done counts LOCKSTEP
+ITERATIONS of the batch: the batched reading of the reference's per-action counter (each iteration is one action on every
+board).  Epsilon is held constant within one collect() -- one actor_rollout launch.
+"""
+from __future__ import annotations
+
+import copy
+import ctypes as C
+import math
+from typing import Optional
+
+import torch
+from torch import nn
+
+from . import _learn_lib
+from ._learn_lib import check, pack_policy_device
+from .actor import PolicyMLP
+from .env import OBS_DIM, BatchedTetris, _OBS_CODES
+
+RECORD_BYTES = _learn_lib.RECORD_BYTES
+
+
+class ReplayRing:
+    """`capacity` transitions of 80 bytes on the device (include/tpl_learn.h).  A push of a [T, N] chunk at head h writes
+    transition (t, board i) to slot (h + t * N + i) mod capacity; the oldest transitions are overwritten.  Draws are uniform
+    with replacement over the filled slots [0, size)."""
+
+    def __init__(self, capacity: int, device):
+        capacity = int(capacity)
+        if not 1 <= capacity < (1 << 32):
+            raise ValueError("capacity must be in [1, 2^32)")
+        self.capacity, self.device = capacity, torch.device(device)
+        self.data = torch.zeros(capacity * RECORD_BYTES, dtype=torch.uint8, device=self.device)
+        self.head = 0
+        self.size = 0
+
+    def _stream(self):
+        return torch._C._cuda_getCurrentRawStream(self.device.index)
+
+    def push(self, env: BatchedTetris, traj: dict) -> None:
+        """Append the trajectory of env.actor_rollout(..., record=True, record_states=True), called just before: s' of the
+        last step is read from the environment's resident planes."""
+        if not env.auto_reset:
+            raise ValueError("the replay ring takes transitions of an auto-reset environment (the state before a step must be a "
+                             "running board)")
+        actions, rewards, dones = traj["actions"], traj["rewards"], traj["dones"]
+        sa, sb = traj["states_a"], traj["states_b"]
+        steps, n = actions.shape
+        if n != env.num_envs or tuple(sa.shape) != (steps, n, 4) or tuple(sb.shape) != (steps, n, 4):
+            raise ValueError("the trajectory does not belong to this environment")
+        if steps * n > self.capacity:
+            raise ValueError(f"a chunk of {steps} x {n} transitions does not fit a ring of {self.capacity}")
+        pa, pb = C.c_void_p(), C.c_void_p()
+        from ._lib import check as env_check
+        env_check(env._lib.tpl_state_ptrs(env._h, C.byref(pa), C.byref(pb)))
+        dev = lambda t, dt: t.device == self.device and t.is_contiguous() and t.dtype in dt
+        if not (dev(actions, (torch.uint8,)) and dev(rewards, (torch.float32,)) and dev(dones, (torch.uint8, torch.bool))
+                and dev(sa, (torch.int32,)) and dev(sb, (torch.int32,))):
+            raise ValueError("trajectory tensors must be contiguous device tensors as actor_rollout returns them")
+        check(_learn_lib.lib().tpl_replay_push(self.data.data_ptr(), self.capacity, self.head, steps, n, actions.data_ptr(),
+                                               rewards.data_ptr(), dones.data_ptr(), sa.data_ptr(), sb.data_ptr(), pa.value,
+                                               pb.value, self._stream()))
+        self.head = (self.head + steps * n) % self.capacity
+        self.size = min(self.size + steps * n, self.capacity)
+
+    def sample(self, batch: int, seed: int, update: int, next_env: BatchedTetris, obs_dtype=torch.float32,
+               with_index: bool = False) -> dict:
+        """One minibatch: draw i takes slot _learn_lib.replay_indices(seed, update, batch, size)[i].  Returns obs [batch, 217]
+        (the observation of s, as env.expand_states makes it), action u8, reward f32, done u8 (and index i64); the s' planes
+        are written into the resident state of `next_env`, an environment of exactly `batch` boards."""
+        if self.size < 1:
+            raise ValueError("the replay ring is empty")
+        if next_env.num_envs != batch or next_env.device != self.device:
+            raise ValueError(f"next_env must hold exactly {batch} boards on {self.device}")
+        if obs_dtype not in _OBS_CODES:
+            raise ValueError("obs_dtype must be torch.float32 or torch.bfloat16")
+        d = self.device
+        out = dict(obs=torch.empty((batch, OBS_DIM), dtype=obs_dtype, device=d),
+                   action=torch.empty(batch, dtype=torch.uint8, device=d),
+                   reward=torch.empty(batch, dtype=torch.float32, device=d),
+                   done=torch.empty(batch, dtype=torch.uint8, device=d))
+        if with_index:
+            out["index"] = torch.empty(batch, dtype=torch.int64, device=d)
+        pa, pb = C.c_void_p(), C.c_void_p()
+        from ._lib import check as env_check
+        env_check(next_env._lib.tpl_state_ptrs(next_env._h, C.byref(pa), C.byref(pb)))
+        idx = out.get("index")
+        check(_learn_lib.lib().tpl_replay_sample(
+            self.data.data_ptr(), self.capacity, self.size, batch, int(seed) % (1 << 64), int(update) % (1 << 64),
+            next_env.L, next_env.M, out["obs"].data_ptr(), _OBS_CODES[obs_dtype], pa.value, pb.value,
+            out["action"].data_ptr(), out["reward"].data_ptr(), out["done"].data_ptr(),
+            None if idx is None else idx.data_ptr(), self._stream()))
+        return out
+
+
+def factored_q(out: torch.Tensor, action: torch.Tensor) -> torch.Tensor:
+    """Q(s, a) = out[a // 10] + out[4 + a % 10] for [B, 14] outputs and [B] actions."""
+    a = action.long().unsqueeze(1)
+    return (out.gather(1, a // 10) + out.gather(1, 4 + a % 10)).squeeze(1)
+
+
+def factored_max(out: torch.Tensor) -> torch.Tensor:
+    """max over the 40 actions of the factored Q: max(out[0:4]) + max(out[4:14])."""
+    return out[:, :4].max(dim=1).values + out[:, 4:14].max(dim=1).values
+
+
+class DQNLearner:
+    """DQN for Model(217, 14) on a BatchedTetris (defaults: the constants of the upstream model/train.py).
+
+    collect(steps)   one actor_rollout of the online net's split image at the scheduled epsilon, pushed into the ring
+    update(n=1)      n minibatch updates (sample -> Q(s) in torch, Q'(s') on the split kernel -> Huber -> AdamW -> soft update)
+    evaluate(steps)  the greedy policy (epsilon 0) on a separate environment over the same pool: episodes, wins, win rate
+    """
+
+    def __init__(self, env: BatchedTetris, model: Optional[nn.Module] = None, capacity: int = 1 << 20, batch_size: int = 128,
+                 gamma: float = 0.99, eps_start: float = 0.9, eps_end: float = 0.05, eps_decay: float = 1000,
+                 tau: float = 0.005, lr: float = 1e-4, seed: int = 0):
+        if not env.auto_reset:
+            raise ValueError("DQNLearner needs an environment with auto_reset=True (the replay ring's s' of a finished "
+                             "episode is the freshly reset board, masked by done)")
+        if batch_size < 1:
+            raise ValueError("batch_size must be positive")
+        self.env, self.device = env, env.device
+        self.batch_size, self.gamma, self.tau, self.lr = int(batch_size), float(gamma), float(tau), float(lr)
+        self.eps_start, self.eps_end, self.eps_decay = float(eps_start), float(eps_end), float(eps_decay)
+        self.seed = int(seed)
+        self.model = (model if model is not None else PolicyMLP()).to(device=self.device, dtype=torch.float32)
+        self.target = copy.deepcopy(self.model)                   # target_net.load_state_dict(policy_net.state_dict())
+        for p in self.target.parameters():
+            p.requires_grad_(False)
+        self.optimizer = torch.optim.AdamW(self.model.parameters(), lr=self.lr, amsgrad=True)
+        self.loss_fn = nn.SmoothL1Loss()
+        self.ring = ReplayRing(capacity, self.device)
+        # the target network's boards: s' of each draw is written into this environment's resident planes
+        self.next_env = BatchedTetris(env.L, env.M, self.batch_size, device=self.device, seed=self.seed)
+        self.actor_image = pack_policy_device(_learn_lib.policy_tensors(self.model), "split")
+        self.target_image = pack_policy_device(_learn_lib.policy_tensors(self.target), "split")
+        self._next_action = torch.empty(self.batch_size, dtype=torch.uint8, device=self.device)
+        self._next_q = torch.empty((self.batch_size, 14), dtype=torch.float32, device=self.device)
+        self.steps_done = 0
+        self.updates = 0
+        self.last = None                                         # the last update's minibatch, Q'(s') and y
+        self.eval_env = None
+
+    # ------------------------------------------------------------------------------------------ acting
+    def epsilon(self) -> float:
+        return self.eps_end + (self.eps_start - self.eps_end) * math.exp(-self.steps_done / self.eps_decay)
+
+    def collect(self, steps: int) -> dict:
+        """`steps` lockstep iterations of the whole batch under the online net at the scheduled epsilon, appended to the
+        ring (steps * N transitions).  Returns the recorded trajectory (device tensors) and the epsilon used."""
+        steps = int(steps)
+        if steps < 1:
+            raise ValueError("steps must be positive")
+        if steps * self.env.num_envs > self.ring.capacity:
+            raise ValueError(f"collect({steps}) adds {steps * self.env.num_envs} transitions, more than the ring's capacity "
+                             f"{self.ring.capacity}")
+        eps = self.epsilon()
+        pack_policy_device(_learn_lib.policy_tensors(self.model), "split", out=self.actor_image)
+        traj = self.env.actor_rollout(self.actor_image, steps, epsilon=eps, seed=self.seed, step0=self.steps_done,
+                                      record=True, record_states=True)
+        self.ring.push(self.env, traj)
+        self.steps_done += steps
+        traj["epsilon"] = eps
+        return traj
+
+    # ------------------------------------------------------------------------------------------ learning
+    def update(self, n: int = 1) -> float:
+        """n optimisation steps of the tutorial's optimize_model; returns the last loss."""
+        if self.ring.size < self.batch_size:
+            raise ValueError(f"the ring holds {self.ring.size} transitions, fewer than batch_size={self.batch_size}: collect first")
+        loss = None
+        for _ in range(int(n)):
+            loss = self._update_once()
+        return float(loss)
+
+    @torch.no_grad()
+    def minibatch(self) -> dict:
+        """The next update's minibatch (draws keyed by (seed, updates)) with Q'(s') of the target image and the TD target y;
+        s' stays in next_env's resident planes."""
+        batch = self.ring.sample(self.batch_size, self.seed, self.updates, self.next_env, with_index=True)
+        self.next_env.policy_act(self.target_image, out=self._next_action, logits=self._next_q)
+        next_q = self._next_q.clone()
+        y = batch["reward"] + self.gamma * (1.0 - batch["done"].float()) * factored_max(next_q)
+        return dict(batch, next_q=next_q, y=y)
+
+    def _update_once(self) -> torch.Tensor:
+        batch = self.minibatch()
+        y = batch["y"]
+        q = factored_q(self.model(batch["obs"]), batch["action"])
+        loss = self.loss_fn(q, y)
+        self.optimizer.zero_grad()
+        loss.backward()
+        torch.nn.utils.clip_grad_value_(self.model.parameters(), 100)
+        self.optimizer.step()
+        self.soft_update()
+        self.updates += 1
+        self.last = batch
+        return loss.detach()
+
+    @torch.no_grad()
+    def soft_update(self) -> None:
+        """theta' <- tau * theta + (1 - tau) * theta', then the target image repacked on the device."""
+        for pt, p in zip(self.target.parameters(), self.model.parameters()):
+            pt.copy_(p * self.tau + pt * (1 - self.tau))
+        pack_policy_device(_learn_lib.policy_tensors(self.target), "split", out=self.target_image)
+
+    # ------------------------------------------------------------------------------------------ evaluation
+    def evaluate(self, steps: int, epsilon: float = 0.0) -> dict:
+        """`steps` iterations of the online net's policy (greedy by default) on a separate auto-reset environment with the
+        learner env's size, L, M and configuration pool, from a full reset.  Returns episodes finished, wins, win rate."""
+        env = self.env
+        if env._pool is None:
+            raise ValueError("the learner's environment has no configuration pool to evaluate on")
+        if self.eval_env is None:
+            self.eval_env = BatchedTetris(env.L, env.M, env.num_envs, device=self.device, seed=env.seed + 1, auto_reset=True,
+                                          assign=env.assign, reward=env.reward_params)
+        ev = self.eval_env
+        if getattr(self, "_eval_pool", None) is not env._pool:
+            ev.load_configs(*env._pool, validate=False)
+            self._eval_pool = env._pool
+        ev.reset()
+        image = pack_policy_device(_learn_lib.policy_tensors(self.model), "split")
+        ev.actor_rollout(image, int(steps), epsilon=float(epsilon), seed=self.seed + 1, record=False)
+        st = ev.stats()
+        return dict(episodes=st["episodes"], wins=st["wins"], win_rate=st["wins"] / max(st["episodes"], 1))

@@ -1,0 +1,161 @@
+"""Timings of the DQN learner on one GPU (profiles/learner/README.md).
+
+    python3 tools/learner_probe.py                 runs every part below as a child process under `timeout -k 10 <s>`, stops at the
+                                                   first failure, prints one JSON line per part
+    python3 tools/learner_probe.py --part NAME     one part
+
+Parts:
+    sample    tpl_replay_sample at B = 65,536 and 2^20 (float32 and bf16 obs), as bytes/s against 6.3 TB/s achievable HBM
+    push      tpl_replay_push against the actor_rollout launch that recorded the same chunk
+    update    DQNLearner.update() per second at B = 128 and 65,536
+    loop      collect(1) + update(4) rounds at N = 262,144 on an L=2 / M=2 pool (win-only reward): transitions/s end to end and
+              the greedy win rate before and after
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+HBM_ACHIEVABLE = 6.3e12
+PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600}
+
+
+def _timed(fn, reps, warmup=3):
+    import torch
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    for _ in range(reps):
+        fn()
+    stop.record()
+    torch.cuda.synchronize()
+    return start.elapsed_time(stop) / 1e3 / reps
+
+
+def _filled_ring(n=1 << 18, steps=16):
+    import torch
+    import tetris_piclim as T
+    env = T.BatchedTetris(10, 40, n, device="cuda:0", seed=1, auto_reset=True)
+    env.load_configs(*env.synthetic_configs(4096))
+    env.reset()
+    torch.manual_seed(0)
+    image = T.actor.policy_image(T.PolicyMLP(), env.device, f32="split")
+    ring = T.ReplayRing(n * steps, env.device)
+    traj = env.actor_rollout(image, steps, epsilon=0.5, seed=3, record=True, record_states=True)
+    ring.push(env, traj)
+    return env, image, ring, traj
+
+
+def part_sample():
+    import torch
+    import tetris_piclim as T
+    env, _, ring, _ = _filled_ring()
+    out = []
+    for batch in (65536, 1 << 20):
+        next_env = T.BatchedTetris(10, 40, batch, device="cuda:0", seed=2)
+        for dtype, obs_bytes in ((torch.float32, 868), (torch.bfloat16, 434)):
+            k = [0]
+
+            def draw():
+                k[0] += 1
+                ring.sample(batch, 7, k[0], next_env, obs_dtype=dtype)
+            t = _timed(draw, 20)
+            moved = batch * (80 + obs_bytes + 32 + 6)          # record read; obs, s' planes, action / reward / done written
+            out.append(dict(batch=batch, obs=str(dtype).split(".")[-1], us=round(t * 1e6, 2), bytes_per_draw=80 + obs_bytes + 38,
+                            tb_per_s=round(moved / t / 1e12, 3), of_achievable=round(moved / t / HBM_ACHIEVABLE, 3)))
+        next_env.terminate()
+    return dict(part="sample", ring=ring.capacity, rows=out)
+
+
+def part_push():
+    import torch
+    env, image, ring, traj = _filled_ring()
+    n, steps = env.num_envs, traj["actions"].shape[0]
+    t_push = _timed(lambda: ring.push(env, traj), 20)
+    t_roll = _timed(lambda: env.actor_rollout(image, steps, epsilon=0.5, seed=3, record=True, record_states=True), 5, warmup=1)
+    moved = n * steps * (80 + 32 + 32 + 6)
+    return dict(part="push", boards=n, steps=steps, push_us=round(t_push * 1e6, 1), rollout_us=round(t_roll * 1e6, 1),
+                push_over_rollout=round(t_push / t_roll, 4), push_tb_per_s=round(moved / t_push / 1e12, 3))
+
+
+def part_update():
+    import torch
+    import tetris_piclim as T
+    rows = []
+    for batch in (128, 65536):
+        env = T.BatchedTetris(10, 40, 1 << 16, device="cuda:0", seed=1, auto_reset=True)
+        env.load_configs(*env.synthetic_configs(4096))
+        env.reset()
+        torch.manual_seed(0)
+        learner = T.DQNLearner(env, capacity=1 << 20, batch_size=batch, seed=1)
+        learner.collect(8)
+        learner.update(5)
+        torch.cuda.synchronize()
+        reps = 200 if batch == 128 else 50
+        t0 = time.perf_counter()
+        learner.update(reps)
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t0) / reps
+        rows.append(dict(batch=batch, updates_per_s=round(1 / dt, 1), ms_per_update=round(dt * 1e3, 3)))
+        env.terminate()
+    return dict(part="update", rows=rows)
+
+
+def part_loop():
+    import torch
+    import tetris_piclim as T
+    n, rounds, per = 262144, 300, 4
+    rows, pieces = T.generate_configs(2, 2, 64, seed=100)
+    env = T.BatchedTetris(2, 2, n, device="cuda:0", seed=0, auto_reset=True, reward=(0.0, 1.0, 0.0))
+    env.load_configs(rows, pieces)
+    env.reset()
+    torch.manual_seed(0)
+    learner = T.DQNLearner(env, capacity=1 << 22, batch_size=1024, eps_start=1.0, eps_end=0.05, eps_decay=10, tau=0.05,
+                           lr=1e-3, seed=0)
+    before = learner.evaluate(8)["win_rate"]
+    random_rate = learner.evaluate(8, epsilon=1.0)["win_rate"]
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    curve = []
+    for r in range(rounds):
+        learner.collect(1)
+        learner.update(per)
+        if (r + 1) % 100 == 0:
+            torch.cuda.synchronize()
+            curve.append((r + 1, round(time.perf_counter() - t0, 2)))
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    after = learner.evaluate(8)
+    return dict(part="loop", boards=n, rounds=rounds, updates_per_round=per, batch=1024, seconds=round(dt, 2),
+                transitions_per_s=round(rounds * n / dt), updates_per_s=round(rounds * per / dt, 1), elapsed_at=curve,
+                win_rate_random=round(random_rate, 4), win_rate_greedy_before=round(before, 4),
+                win_rate_greedy_after=round(after["win_rate"], 4), eval_episodes=after["episodes"])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--part", choices=sorted(PARTS))
+    args = ap.parse_args()
+    if args.part:
+        print(json.dumps(globals()["part_" + args.part]()), flush=True)
+        return 0
+    for name, limit in PARTS.items():
+        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--part", name]
+        res = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT)
+        lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
+        if res.returncode != 0 or not lines:
+            print(json.dumps(dict(part=name, failed=res.returncode, stderr=res.stderr[-2000:])), flush=True)
+            return res.returncode or 1               # nothing more is started on the GPU after a failed step
+        print(lines[-1], flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
