@@ -68,6 +68,51 @@ int tpl_learn_pack(int32_t kind, const float* w1, const float* b1, const float* 
                    const float* b3, const float* w4, const float* b4, const float* w5, const float* b5, void* image,
                    void* stream);
 
+/* Prioritized replay (proportional, Schaul et al. 2016): a 16-ary float64 sum tree over the ring's slots, on the device.
+ *
+ * Tree image, tpl_priority_tree_bytes(capacity) bytes, 128-byte aligned; every word is a little-endian f64 / i64:
+ *   bytes 0..127   header: word 0 the running maximum priority (f64, 1.0 after init), word 1 the capacity (i64),
+ *                  word 2 the number of levels (i64), words 3..15 zero
+ *   level 0        the `capacity` leaf priorities, one per ring slot (f64; an unfilled slot holds 0)
+ *   level k >= 1   n_k = ceil(n_{k-1} / 16) nodes: node j is children 16j .. 16j+15 of level k-1 added left to right in
+ *                  float64, one rounding per add; a missing child counts as 0.  The top level has one node, the root: the total.
+ *   Level 0 starts at byte 128, level k + 1 at the start of level k plus 8 * n_k rounded up to 128 bytes, so the 16 children
+ *   of a node are one 128-byte line; the padding is zero.  A draw reads ceil(log16 capacity) lines.
+ *
+ * Push: every slot of [head, head + count) mod capacity gets the running maximum.  Update: the priorities are clamped to
+ * fmin(fmax(p, 1e-12), 1e30) (NaN -> 1e-12); a slot named more than once in one batch takes the largest of its new
+ * priorities; the running maximum becomes max(old, max of the batch).  Indices outside [0, capacity) are ignored.
+ * Draw i of a prioritized minibatch (stratified): u_i = ((i + U_i) * total) / batch in float64, U_i = (h_i >> 11) * 2^-53 with
+ * h_i the splitmix64 value tpl_replay_index maps; from the root, take the first child k with u < c_k, else u -= c_k; if no
+ * child is taken (rounding), the last child with c_k > 0.  Zero-priority slots are never drawn. */
+#define TPL_PRIORITY_HEADER_BYTES 128
+#define TPL_PRIORITY_FANOUT 16
+#define TPL_PRIORITY_MIN 1e-12
+#define TPL_PRIORITY_MAX 1e30
+
+/* Bytes of the tree of a ring of `capacity` slots (0 unless capacity is in [1, 2^32)). */
+size_t tpl_priority_tree_bytes(int64_t capacity);
+
+/* Zeroes the tree and writes its header (running maximum 1.0). */
+int tpl_priority_init(void* tree, int64_t capacity, void* stream);
+
+/* The slots of one tpl_replay_push at `head` of `count` transitions get the running maximum; their ancestors are re-summed. */
+int tpl_priority_push(void* tree, int64_t capacity, int64_t head, int64_t count, void* stream);
+
+/* Priority write-back of one minibatch: index i64 [batch], priority f64 [batch] (already (|delta| + eps)^alpha). */
+int tpl_priority_update(void* tree, int64_t capacity, int64_t batch, const int64_t* index, const double* priority,
+                        void* stream);
+
+/* tpl_replay_sample with the draws taken from the tree instead of uniformly: the same outputs, `index` required, and
+ * prob f32 [batch] = (float)(leaf / total) of each draw. */
+int tpl_replay_sample_prioritized(const void* ring, const void* tree, int64_t capacity, int64_t size, int64_t batch,
+                                  uint64_t seed, uint64_t update, int32_t L, int32_t M, void* obs, int32_t dtype, void* next_a,
+                                  void* next_b, uint8_t* action, float* reward, uint8_t* done, int64_t* index, float* prob,
+                                  void* stream);
+
+/* u_i of draw i on the host (for tests): ((i + U_i) * total) / batch; -1 if batch < 1, i < 0 or i >= batch. */
+double tpl_priority_target(uint64_t seed, uint64_t update, int64_t i, int64_t batch, double total);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,7 @@ from ._lib import (LIB_PATH, SYMBOLS, TplError, build_library, carve, forward_ge
 
 __all__ = ["BatchedTetris", "Tetris", "Snapshot", "OBS_DIM", "NUM_ACTIONS", "RUNNING", "WON", "LOST", "TplError",
            "RandomPieceGenerator", "get_tetromino", "piece_translations", "translate", "carve", "build_library", "shape_info", "generate_configs", "forward_generate", "pack_policy", "LIB_PATH", "SYMBOLS", "DQNLearner",
-           "ReplayRing"]
+           "ReplayRing", "PrioritizedReplayRing"]
 
 
 def __getattr__(name):
@@ -29,7 +29,7 @@ def __getattr__(name):
         return getattr(importlib.import_module(__name__ + ".pieces"), name)
     if name in ("Actor", "PolicyMLP"):
         return getattr(importlib.import_module(__name__ + ".actor"), name)
-    if name in ("DQNLearner", "ReplayRing"):
+    if name in ("DQNLearner", "ReplayRing", "PrioritizedReplayRing"):
         # the learner library (libtpl_learn.so) is built and loaded only here, on first use
         return getattr(importlib.import_module(__name__ + ".learn"), name)
     if name in ("learn", "_learn_lib"):

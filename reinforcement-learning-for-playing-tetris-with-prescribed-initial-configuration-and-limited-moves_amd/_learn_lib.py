@@ -20,12 +20,13 @@ from ._lib import TplError, _hipcc
 
 _LEARN_CSRC = os.path.join(_lib._CSRC, "learn")
 LEARN_LIB_PATH = os.path.join(_lib._LIBDIR, "libtpl_learn.so")
-_UNITS = [os.path.join(_LEARN_CSRC, f) for f in ("replay.hip", "pack.hip")]
+_UNITS = [os.path.join(_LEARN_CSRC, f) for f in ("replay.hip", "pack.hip", "priority.hip")]
 
 # entry points declared in include/tpl_learn.h (tests check that the .so exports every one of them)
 LEARN_SYMBOLS = [
     "tpl_learn_last_error", "tpl_replay_record_bytes", "tpl_replay_push", "tpl_replay_sample", "tpl_replay_index",
-    "tpl_learn_image_bytes", "tpl_learn_pack",
+    "tpl_learn_image_bytes", "tpl_learn_pack", "tpl_priority_tree_bytes", "tpl_priority_init", "tpl_priority_push",
+    "tpl_priority_update", "tpl_replay_sample_prioritized", "tpl_priority_target",
 ]
 
 IMAGE_KINDS = {"bf16": 0, "f32": 1, "split": 2}
@@ -107,7 +108,18 @@ def lib() -> C.CDLL:
     L.tpl_learn_image_bytes.restype = sz
     L.tpl_learn_image_bytes.argtypes = [i32]
     L.tpl_learn_pack.argtypes = [i32] + [vp] * 12
-    for name in ("tpl_replay_push", "tpl_replay_sample", "tpl_learn_pack"):
+    f64 = C.c_double
+    L.tpl_priority_tree_bytes.restype = sz
+    L.tpl_priority_tree_bytes.argtypes = [i64]
+    L.tpl_priority_init.argtypes = [vp, i64, vp]
+    L.tpl_priority_push.argtypes = [vp, i64, i64, i64, vp]
+    L.tpl_priority_update.argtypes = [vp, i64, i64, vp, vp, vp]
+    L.tpl_replay_sample_prioritized.argtypes = [vp, vp, i64, i64, i64, u64, u64, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp,
+                                                vp]
+    L.tpl_priority_target.restype = f64
+    L.tpl_priority_target.argtypes = [u64, u64, i64, i64, f64]
+    for name in ("tpl_replay_push", "tpl_replay_sample", "tpl_learn_pack", "tpl_priority_init", "tpl_priority_push",
+                 "tpl_priority_update", "tpl_replay_sample_prioritized"):
         getattr(L, name).restype = i32
     _handle = L
     return L
@@ -131,17 +143,132 @@ def _mix64(z):
     return z ^ (z >> np.uint64(31))
 
 
+def _draw_hashes(seed: int, update: int, batch: int) -> np.ndarray:
+    """h_i, i < batch: position i + 1 of the splitmix64 stream keyed by (seed, update) (uint64 [batch])."""
+    with np.errstate(over="ignore"):
+        key = _mix64(np.uint64(seed % (1 << 64)) + _GOLDEN * np.uint64((update + 1) % (1 << 64)))
+        return _mix64(key + _GOLDEN * (np.arange(batch, dtype=np.uint64) + np.uint64(1)))
+
+
 def replay_indices(seed: int, update: int, batch: int, size: int) -> np.ndarray:
     """The slots tpl_replay_sample draws (int64 [batch]): draw i is position i + 1 of the splitmix64 stream keyed by
     (seed, update), h, mapped to floor(h * size / 2^64) -- computed from 32-bit halves, exact for size < 2^32."""
     if not 1 <= size < (1 << 32):
         raise ValueError("size must be in [1, 2^32)")
+    h = _draw_hashes(seed, update, batch)
     with np.errstate(over="ignore"):
-        key = _mix64(np.uint64(seed % (1 << 64)) + _GOLDEN * np.uint64((update + 1) % (1 << 64)))
-        h = _mix64(key + _GOLDEN * (np.arange(batch, dtype=np.uint64) + np.uint64(1)))
         s = np.uint64(size)
         hi, lo = h >> np.uint64(32), h & _M32
         return ((hi * s + ((lo * s) >> np.uint64(32))) >> np.uint64(32)).astype(np.int64)
+
+
+# ------------------------------------------------------------------------------------------------ the priority tree
+# A numpy mirror of csrc/learn/priority.hip (layout and rules: include/tpl_learn.h).  A tree is a float64 array of
+# tpl_priority_tree_bytes(capacity) / 8 words, the device image word for word; the header's integer words are viewed as int64.
+PRIORITY_HEADER_WORDS = 16
+PRIORITY_FANOUT = 16
+PRIORITY_MIN, PRIORITY_MAX = 1e-12, 1e30
+
+
+def priority_layout(capacity: int):
+    """(offsets, counts, words): where each level starts (in float64 words from the base), its node count, the image size."""
+    if not 1 <= capacity < (1 << 32):
+        raise ValueError("capacity must be in [1, 2^32)")
+    offsets, counts, n, at = [], [], int(capacity), PRIORITY_HEADER_WORDS
+    while True:
+        offsets.append(at)
+        counts.append(n)
+        at += -(-n // PRIORITY_FANOUT) * PRIORITY_FANOUT
+        if n == 1:
+            return offsets, counts, at
+        n = -(-n // PRIORITY_FANOUT)
+
+
+def priority_tree_init(capacity: int) -> np.ndarray:
+    """tpl_priority_init: all zero, running maximum 1.0, the capacity and the number of levels in the header."""
+    offsets, _, words = priority_layout(capacity)
+    tree = np.zeros(words, dtype=np.float64)
+    tree[0] = 1.0
+    tree.view(np.int64)[1:3] = (capacity, len(offsets))
+    return tree
+
+
+def _leaves(tree):
+    capacity = int(tree.view(np.int64)[1])
+    return tree[PRIORITY_HEADER_WORDS:PRIORITY_HEADER_WORDS + capacity], capacity
+
+
+def priority_tree_resum(tree) -> None:
+    """Every node := its 16 children added left to right, one rounding per add (the padding children are 0)."""
+    offsets, counts, _ = priority_layout(int(tree.view(np.int64)[1]))
+    for k in range(1, len(offsets)):
+        child = tree[offsets[k - 1]:offsets[k - 1] + PRIORITY_FANOUT * counts[k]].reshape(counts[k], PRIORITY_FANOUT)
+        s = child[:, 0].copy()
+        for c in range(1, PRIORITY_FANOUT):
+            s = s + child[:, c]
+        tree[offsets[k]:offsets[k] + counts[k]] = s
+
+
+def priority_tree_push(tree: np.ndarray, head: int, count: int) -> np.ndarray:
+    """tpl_priority_push, in place: slots [head, head + count) mod capacity get the running maximum."""
+    leaves, capacity = _leaves(tree)
+    if not (0 <= head < capacity and 1 <= count <= capacity):
+        raise ValueError("head must be in [0, capacity) and count in [1, capacity]")
+    leaves[(head + np.arange(count)) % capacity] = tree[0]
+    priority_tree_resum(tree)
+    return tree
+
+
+def clamp_priorities(priority) -> np.ndarray:
+    """fmin(fmax(p, 1e-12), 1e30): NaN and everything below 1e-12 -> 1e-12, +inf -> 1e30."""
+    return np.fmin(np.fmax(np.asarray(priority, dtype=np.float64), PRIORITY_MIN), PRIORITY_MAX)
+
+
+def priority_tree_update(tree: np.ndarray, index, priority) -> np.ndarray:
+    """tpl_priority_update, in place: the drawn leaves are zeroed, then each takes the largest clamped priority given for it;
+    the running maximum takes the batch's.  Indices outside [0, capacity) are ignored."""
+    leaves, capacity = _leaves(tree)
+    index, priority = np.asarray(index, dtype=np.int64), np.asarray(priority, dtype=np.float64)
+    keep = (index >= 0) & (index < capacity)
+    index, p = index[keep], clamp_priorities(priority[keep])
+    leaves[index] = 0.0
+    np.maximum.at(leaves, index, p)
+    if p.size:
+        tree[0] = max(tree[0], p.max())
+    priority_tree_resum(tree)
+    return tree
+
+
+def priority_targets(seed: int, update: int, batch: int, total: float) -> np.ndarray:
+    """u_i = ((i + U_i) * total) / batch in float64, U_i = (h_i >> 11) * 2^-53 (tpl_priority_target)."""
+    U = (_draw_hashes(seed, update, batch) >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+    return ((np.arange(batch, dtype=np.float64) + U) * np.float64(total)) / np.float64(batch)
+
+
+def prioritized_draws(tree: np.ndarray, seed: int, update: int, batch: int):
+    """The slots tpl_replay_sample_prioritized draws and their prob = float32(leaf / total): (int64 [batch], float32 [batch])."""
+    capacity = int(tree.view(np.int64)[1])
+    offsets, _, _ = priority_layout(capacity)
+    total = tree[offsets[-1]]
+    u = priority_targets(seed, update, batch, total)
+    j = np.zeros(batch, dtype=np.int64)
+    leaf = np.full(batch, tree[offsets[0]])
+    lanes = np.arange(PRIORITY_FANOUT)
+    for k in range(len(offsets) - 1, 0, -1):
+        line = tree[offsets[k - 1] + PRIORITY_FANOUT * j[:, None] + lanes]
+        pick, picked = np.full(batch, -1), np.zeros(batch)
+        last, last_v = np.zeros(batch, dtype=np.int64), np.zeros(batch)
+        for c in range(PRIORITY_FANOUT):
+            x = line[:, c]
+            open_ = pick < 0
+            take = open_ & (u < x)
+            pick, picked = np.where(take, c, pick), np.where(take, x, picked)
+            u = np.where(open_ & ~take, u - x, u)
+            last, last_v = np.where(x > 0, c, last), np.where(x > 0, x, last_v)
+        none = pick < 0
+        pick, picked = np.where(none, last, pick), np.where(none, last_v, picked)
+        j, leaf = j * PRIORITY_FANOUT + pick, picked
+    return np.minimum(j, capacity - 1), (leaf / total).astype(np.float32)
 
 
 # ------------------------------------------------------------------------------------------------ device packing

@@ -13,8 +13,7 @@
 //           (random slots: the 80 B are the whole traffic of the read side), s is turned into 217 feature bytes in LDS
 //           and leaves as the wave's contiguous span of the observation with 16-byte non-temporal stores -- observe.hip's
 //           scheme, so a draw costs 80 B read and 868 B (f32) / 434 B (bf16) + 32 B + 6 B written.
-#include "tpl_learn_internal.h"
-#include "../tpl_observe.h"
+#include "tpl_replay_draw.h"
 
 #include <cstdarg>
 #include <cstdio>
@@ -70,20 +69,6 @@ __global__ __launch_bounds__(kPushBlock) void replay_push_kernel(const PushArgs 
     rec[0] = sa; rec[1] = sb; rec[2] = na; rec[3] = nb; rec[4] = tail;
 }
 
-struct SampleArgs {
-    const uint4* ring;
-    int64_t size, batch;
-    uint64_t key;
-    uint32_t L, M;
-    void* obs;
-    uint4* next_a;
-    uint4* next_b;
-    uint8_t* action;
-    float* reward;
-    uint8_t* done;
-    int64_t* index;
-};
-
 template <typename T>
 __global__ __launch_bounds__(64 * kObsWaves) void replay_sample_kernel(const SampleArgs p) {
     __shared__ __attribute__((aligned(16))) uint8_t s_rows[kObsWaves][kWaveLds];
@@ -91,24 +76,8 @@ __global__ __launch_bounds__(64 * kObsWaves) void replay_sample_kernel(const Sam
     const int64_t base = ((int64_t)blockIdx.x * kObsWaves + (threadIdx.x >> 6)) * 64;     // the wave's first draw
     if (base >= p.batch) return;                                                          // wave-uniform
     const int count = (int)((p.batch - base) < 64 ? (p.batch - base) : 64);
-    uint8_t* const rows = s_rows[threadIdx.x >> 6];
-    int lines_left = 0;
-    if (lane < count) {
-        const int64_t i = base + lane;
-        const int64_t slot = replay_slot(p.key, (uint64_t)i, (uint64_t)p.size);
-        const uint4* const rec = p.ring + slot * 5;
-        const uint4 sa = rec[0], sb = rec[1], na = rec[2], nb = rec[3], tail = rec[4];
-        tpl::Board s;
-        tpl::unpack_board(sa, sb, s);
-        lines_left = tpl::obs::board_to_bytes(s, p.L, p.M, rows, lane);
-        p.next_a[i] = na;
-        p.next_b[i] = nb;
-        p.reward[i] = __uint_as_float(tail.x);
-        p.action[i] = (uint8_t)(tail.y & 0xFFu);
-        p.done[i] = (uint8_t)((tail.y >> 8) & 0xFFu);
-        if (p.index) p.index[i] = slot;
-    }
-    tpl::obs::store_span<T>(rows, lane, count, base, lines_left, (T*)p.obs);
+    const int64_t slot = lane < count ? replay_slot(p.key, (uint64_t)(base + lane), (uint64_t)p.size) : 0;
+    emit_draw<T>(p, s_rows[threadIdx.x >> 6], lane, count, base, slot);
 }
 
 }  // namespace

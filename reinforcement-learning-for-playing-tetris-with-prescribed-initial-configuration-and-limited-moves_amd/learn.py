@@ -120,6 +120,98 @@ class ReplayRing:
         return out
 
 
+class PrioritizedReplayRing(ReplayRing):
+    """A ReplayRing with proportional prioritized draws (Schaul et al., 2016) from a 16-ary float64 sum tree that lives on the
+    device next to the ring (layout and rules: include/tpl_learn.h; numpy mirror: _learn_lib.prioritized_draws and friends).
+
+    push()               the ring push, then every pushed slot gets the running maximum priority (same stream)
+    sample()             stratified proportional draws: as ReplayRing.sample, plus index i64 and prob f32 = p_slot / total
+    update_priorities()  writes back priorities already shaped as (|delta| + eps)^alpha; refused after a push since the sample
+    priorities(), total(), max_priority()   device views of the leaves, the root and the running maximum (no sync)"""
+
+    def __init__(self, capacity: int, device):
+        super().__init__(capacity, device)
+        L = _learn_lib.lib()
+        nbytes = L.tpl_priority_tree_bytes(self.capacity)
+        self.tree = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        if self.tree.data_ptr() % 128:
+            raise RuntimeError("the priority tree must be 128-byte aligned")
+        offsets, _, _ = _learn_lib.priority_layout(self.capacity)
+        self._root = offsets[-1]
+        check(L.tpl_priority_init(self.tree.data_ptr(), self.capacity, self._stream()))
+        self.pushes = 0
+        self._sampled_at = None                                  # self.pushes when the last minibatch was drawn
+
+    def push(self, env: BatchedTetris, traj: dict) -> None:
+        head = self.head
+        super().push(env, traj)
+        count = int(traj["actions"].numel())
+        check(_learn_lib.lib().tpl_priority_push(self.tree.data_ptr(), self.capacity, head, count, self._stream()))
+        self.pushes += 1
+
+    def sample(self, batch: int, seed: int, update: int, next_env: BatchedTetris, obs_dtype=torch.float32) -> dict:
+        """One minibatch of proportional draws: draw i takes the slot _learn_lib.prioritized_draws(tree, seed, update, batch)
+        names.  Returns what ReplayRing.sample returns, with index i64 [batch] and prob f32 [batch]."""
+        if self.size < 1:
+            raise ValueError("the replay ring is empty")
+        if next_env.num_envs != batch or next_env.device != self.device:
+            raise ValueError(f"next_env must hold exactly {batch} boards on {self.device}")
+        if obs_dtype not in _OBS_CODES:
+            raise ValueError("obs_dtype must be torch.float32 or torch.bfloat16")
+        d = self.device
+        out = dict(obs=torch.empty((batch, OBS_DIM), dtype=obs_dtype, device=d),
+                   action=torch.empty(batch, dtype=torch.uint8, device=d),
+                   reward=torch.empty(batch, dtype=torch.float32, device=d),
+                   done=torch.empty(batch, dtype=torch.uint8, device=d),
+                   index=torch.empty(batch, dtype=torch.int64, device=d),
+                   prob=torch.empty(batch, dtype=torch.float32, device=d))
+        pa, pb = C.c_void_p(), C.c_void_p()
+        from ._lib import check as env_check
+        env_check(next_env._lib.tpl_state_ptrs(next_env._h, C.byref(pa), C.byref(pb)))
+        check(_learn_lib.lib().tpl_replay_sample_prioritized(
+            self.data.data_ptr(), self.tree.data_ptr(), self.capacity, self.size, batch, int(seed) % (1 << 64),
+            int(update) % (1 << 64), next_env.L, next_env.M, out["obs"].data_ptr(), _OBS_CODES[obs_dtype], pa.value, pb.value,
+            out["action"].data_ptr(), out["reward"].data_ptr(), out["done"].data_ptr(), out["index"].data_ptr(),
+            out["prob"].data_ptr(), self._stream()))
+        self._sampled_at = self.pushes
+        return out
+
+    def update_priorities(self, index: torch.Tensor, priority: torch.Tensor) -> None:
+        """Write back the priorities of the last minibatch's draws: index i64 [B] as sample() returned it, priority [B] (cast to
+        float64) = (|delta| + eps)^alpha.  Each is clamped to [1e-12, 1e30] (NaN -> 1e-12); a slot drawn twice takes the
+        larger; an index outside [0, capacity) is ignored.  Raises ValueError if the ring was pushed since that sample: its slots may hold other transitions now."""
+        if self._sampled_at is None:
+            raise ValueError("update_priorities needs a sample() first")
+        if self._sampled_at != self.pushes:
+            raise ValueError("the ring was pushed since the minibatch was drawn: its priorities would land on overwritten slots")
+        if index.dim() != 1 or priority.shape != index.shape or index.dtype != torch.int64:
+            raise ValueError("index must be int64 [B] and priority [B]")
+        if index.device != self.device or priority.device != self.device:
+            raise ValueError(f"index and priority must be on {self.device}")
+        if index.numel() < 1:
+            raise ValueError("an empty write-back")
+        index = index.contiguous()
+        priority = priority.to(torch.float64).contiguous()
+        check(_learn_lib.lib().tpl_priority_update(self.tree.data_ptr(), self.capacity, index.numel(), index.data_ptr(),
+                                                   priority.data_ptr(), self._stream()))
+
+    def _words(self) -> torch.Tensor:
+        return self.tree.view(torch.float64)
+
+    def priorities(self) -> torch.Tensor:
+        """The leaf priorities, float64 [capacity] (a view of the tree: 0 for an unfilled slot)."""
+        h = _learn_lib.PRIORITY_HEADER_WORDS
+        return self._words()[h:h + self.capacity]
+
+    def total(self) -> torch.Tensor:
+        """The root: the sum of every priority, float64 [1] (a view of the tree)."""
+        return self._words()[self._root:self._root + 1]
+
+    def max_priority(self) -> torch.Tensor:
+        """The running maximum priority that a push gives, float64 [1] (a view of the tree)."""
+        return self._words()[0:1]
+
+
 def factored_q(out: torch.Tensor, action: torch.Tensor) -> torch.Tensor:
     """Q(s, a) = out[a // 10] + out[4 + a % 10] for [B, 14] outputs and [B] actions."""
     a = action.long().unsqueeze(1)
@@ -134,6 +226,10 @@ def factored_max(out: torch.Tensor) -> torch.Tensor:
 class DQNLearner:
     """DQN for Model(217, 14) on a BatchedTetris (defaults: the constants of the upstream model/train.py).
 
+    prioritized=True draws minibatches from a PrioritizedReplayRing (proportional, exponent alpha), weights the Huber loss
+    per sample by importance-sampling weights (exponent beta, annealed to beta_final over beta_updates updates) and writes
+    back (|q - y| + priority_eps)^alpha after each optimizer step.
+
     collect(steps)   one actor_rollout of the online net's split image at the scheduled epsilon, pushed into the ring
     update(n=1)      n minibatch updates (sample -> Q(s) in torch, Q'(s') on the split kernel -> Huber -> AdamW -> soft update)
     evaluate(steps)  the greedy policy (epsilon 0) on a separate environment over the same pool: episodes, wins, win rate
@@ -141,12 +237,15 @@ class DQNLearner:
 
     def __init__(self, env: BatchedTetris, model: Optional[nn.Module] = None, capacity: int = 1 << 20, batch_size: int = 128,
                  gamma: float = 0.99, eps_start: float = 0.9, eps_end: float = 0.05, eps_decay: float = 1000,
-                 tau: float = 0.005, lr: float = 1e-4, seed: int = 0):
+                 tau: float = 0.005, lr: float = 1e-4, seed: int = 0, prioritized: bool = False, alpha: float = 0.6,
+                 beta: float = 0.4, beta_final: float = 1.0, beta_updates: int = 100_000, priority_eps: float = 1e-6):
         if not env.auto_reset:
             raise ValueError("DQNLearner needs an environment with auto_reset=True (the replay ring's s' of a finished "
                              "episode is the freshly reset board, masked by done)")
         if batch_size < 1:
             raise ValueError("batch_size must be positive")
+        if prioritized and (alpha < 0 or beta_updates < 1 or priority_eps < 0):
+            raise ValueError("prioritized replay needs alpha >= 0, beta_updates >= 1 and priority_eps >= 0")
         self.env, self.device = env, env.device
         self.batch_size, self.gamma, self.tau, self.lr = int(batch_size), float(gamma), float(tau), float(lr)
         self.eps_start, self.eps_end, self.eps_decay = float(eps_start), float(eps_end), float(eps_decay)
@@ -157,7 +256,10 @@ class DQNLearner:
             p.requires_grad_(False)
         self.optimizer = torch.optim.AdamW(self.model.parameters(), lr=self.lr, amsgrad=True)
         self.loss_fn = nn.SmoothL1Loss()
-        self.ring = ReplayRing(capacity, self.device)
+        self.prioritized = bool(prioritized)
+        self.alpha, self.beta0, self.beta_final = float(alpha), float(beta), float(beta_final)
+        self.beta_updates, self.priority_eps = int(beta_updates), float(priority_eps)
+        self.ring = (PrioritizedReplayRing if self.prioritized else ReplayRing)(capacity, self.device)
         # the target network's boards: s' of each draw is written into this environment's resident planes
         self.next_env = BatchedTetris(env.L, env.M, self.batch_size, device=self.device, seed=self.seed)
         self.actor_image = pack_policy_device(_learn_lib.policy_tensors(self.model), "split")
@@ -166,7 +268,7 @@ class DQNLearner:
         self._next_q = torch.empty((self.batch_size, 14), dtype=torch.float32, device=self.device)
         self.steps_done = 0
         self.updates = 0
-        self.last = None                                         # the last update's minibatch, Q'(s') and y
+        self.last = None                                         # the last update's minibatch, Q'(s'), y and Q(s, a)
         self.eval_env = None
 
     # ------------------------------------------------------------------------------------------ acting
@@ -201,11 +303,24 @@ class DQNLearner:
             loss = self._update_once()
         return float(loss)
 
+    def beta(self) -> float:
+        """The importance-sampling exponent of the next update: beta annealed linearly to beta_final over beta_updates."""
+        return self.beta0 + (self.beta_final - self.beta0) * min(1.0, self.updates / self.beta_updates)
+
     @torch.no_grad()
     def minibatch(self) -> dict:
         """The next update's minibatch (draws keyed by (seed, updates)) with Q'(s') of the target image and the TD target y;
-        s' stays in next_env's resident planes."""
-        batch = self.ring.sample(self.batch_size, self.seed, self.updates, self.next_env, with_index=True)
+        s' stays in next_env's resident planes.
+
+        Prioritized: also prob (of each draw) and weight, the importance-sampling weight (size * prob)^-beta divided by the
+        largest weight IN THE MINIBATCH (Dopamine's convention, chosen over Schaul et al.'s division by the weight of the
+        globally smallest priority so that no min-tree is needed), float32."""
+        if self.prioritized:
+            batch = self.ring.sample(self.batch_size, self.seed, self.updates, self.next_env)
+            w = (self.ring.size * batch["prob"].double()).pow(-self.beta())
+            batch["weight"] = (w / w.max()).float()
+        else:
+            batch = self.ring.sample(self.batch_size, self.seed, self.updates, self.next_env, with_index=True)
         self.next_env.policy_act(self.target_image, out=self._next_action, logits=self._next_q)
         next_q = self._next_q.clone()
         y = batch["reward"] + self.gamma * (1.0 - batch["done"].float()) * factored_max(next_q)
@@ -215,14 +330,19 @@ class DQNLearner:
         batch = self.minibatch()
         y = batch["y"]
         q = factored_q(self.model(batch["obs"]), batch["action"])
-        loss = self.loss_fn(q, y)
+        if self.prioritized:
+            loss = (batch["weight"] * nn.functional.smooth_l1_loss(q, y, reduction="none")).mean()
+        else:
+            loss = self.loss_fn(q, y)
         self.optimizer.zero_grad()
         loss.backward()
         torch.nn.utils.clip_grad_value_(self.model.parameters(), 100)
         self.optimizer.step()
+        if self.prioritized:                                    # (|delta| + eps)^alpha of this update's forward pass
+            self.ring.update_priorities(batch["index"], ((q - y).detach().double().abs() + self.priority_eps).pow(self.alpha))
         self.soft_update()
         self.updates += 1
-        self.last = batch
+        self.last = dict(batch, q=q.detach())
         return loss.detach()
 
     @torch.no_grad()

@@ -10,6 +10,9 @@ Parts:
     update    DQNLearner.update() per second at B = 128 and 65,536
     loop      collect(1) + update(4) rounds at N = 262,144 on an L=2 / M=2 pool (win-only reward): transitions/s end to end and
               the greedy win rate before and after
+    priority  prioritized replay: tpl_replay_sample_prioritized against tpl_replay_sample (B = 65,536 and 2^20, float32 obs, a
+              2^22 ring), tpl_priority_push against tpl_replay_push (16 x 262,144), tpl_priority_update (B = 128 and 65,536),
+              DQNLearner.update() per second with and without prioritized=True (B = 128), and the loop's win rate with PER on
 """
 import argparse
 import json
@@ -22,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 HBM_ACHIEVABLE = 6.3e12
-PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600}
+PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600, "priority": 600}
 
 
 def _timed(fn, reps, warmup=3):
@@ -39,7 +42,7 @@ def _timed(fn, reps, warmup=3):
     return start.elapsed_time(stop) / 1e3 / reps
 
 
-def _filled_ring(n=1 << 18, steps=16):
+def _filled_ring(n=1 << 18, steps=16, prioritized=False):
     import torch
     import tetris_piclim as T
     env = T.BatchedTetris(10, 40, n, device="cuda:0", seed=1, auto_reset=True)
@@ -47,7 +50,7 @@ def _filled_ring(n=1 << 18, steps=16):
     env.reset()
     torch.manual_seed(0)
     image = T.actor.policy_image(T.PolicyMLP(), env.device, f32="split")
-    ring = T.ReplayRing(n * steps, env.device)
+    ring = (T.PrioritizedReplayRing if prioritized else T.ReplayRing)(n * steps, env.device)
     traj = env.actor_rollout(image, steps, epsilon=0.5, seed=3, record=True, record_states=True)
     ring.push(env, traj)
     return env, image, ring, traj
@@ -108,7 +111,7 @@ def part_update():
     return dict(part="update", rows=rows)
 
 
-def part_loop():
+def part_loop(prioritized=False):
     import torch
     import tetris_piclim as T
     n, rounds, per = 262144, 300, 4
@@ -118,7 +121,7 @@ def part_loop():
     env.reset()
     torch.manual_seed(0)
     learner = T.DQNLearner(env, capacity=1 << 22, batch_size=1024, eps_start=1.0, eps_end=0.05, eps_decay=10, tau=0.05,
-                           lr=1e-3, seed=0)
+                           lr=1e-3, seed=0, prioritized=prioritized)
     before = learner.evaluate(8)["win_rate"]
     random_rate = learner.evaluate(8, epsilon=1.0)["win_rate"]
     torch.cuda.synchronize()
@@ -137,6 +140,83 @@ def part_loop():
                 transitions_per_s=round(rounds * n / dt), updates_per_s=round(rounds * per / dt, 1), elapsed_at=curve,
                 win_rate_random=round(random_rate, 4), win_rate_greedy_before=round(before, 4),
                 win_rate_greedy_after=round(after["win_rate"], 4), eval_episodes=after["episodes"])
+
+
+def _update_rate(batch, prioritized, reps=200):
+    import torch
+    import tetris_piclim as T
+    env = T.BatchedTetris(10, 40, 1 << 16, device="cuda:0", seed=1, auto_reset=True)
+    env.load_configs(*env.synthetic_configs(4096))
+    env.reset()
+    torch.manual_seed(0)
+    learner = T.DQNLearner(env, capacity=1 << 20, batch_size=batch, seed=1, prioritized=prioritized)
+    learner.collect(8)
+    learner.update(5)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    learner.update(reps)
+    torch.cuda.synchronize()
+    dt = (time.perf_counter() - t0) / reps
+    env.terminate()
+    return dt
+
+
+def part_priority():
+    import torch
+    import tetris_piclim as T
+    L = T._learn_lib.lib()
+    out = dict(part="priority")
+    env, _, ring, traj = _filled_ring(prioritized=True)
+    stream = torch._C._cuda_getCurrentRawStream(0)
+    # sample: prioritized against uniform on the same 2^22 ring (every slot at the running maximum)
+    rows = []
+    for batch in (65536, 1 << 20):
+        next_env = T.BatchedTetris(10, 40, batch, device="cuda:0", seed=2)
+        k = [0]
+
+        def uniform():
+            k[0] += 1
+            T.ReplayRing.sample(ring, batch, 7, k[0], next_env)
+
+        def prioritized():
+            k[0] += 1
+            ring.sample(batch, 7, k[0], next_env)
+        tu, tp = _timed(uniform, 20), _timed(prioritized, 20)
+        rows.append(dict(batch=batch, uniform_us=round(tu * 1e6, 2), prioritized_us=round(tp * 1e6, 2),
+                         ratio=round(tp / tu, 3)))
+        next_env.terminate()
+    out["sample"] = dict(ring=ring.capacity, obs="float32", rows=rows)
+    # push: the tree's share of a 16 x 262,144 push
+    n, steps = env.num_envs, traj["actions"].shape[0]
+    t_ring = _timed(lambda: T.ReplayRing.push(ring, env, traj), 20)
+    t_tree = _timed(lambda: T._learn_lib.check(L.tpl_priority_push(ring.tree.data_ptr(), ring.capacity, 0, n * steps, stream)), 20)
+    out["push"] = dict(transitions=n * steps, replay_push_us=round(t_ring * 1e6, 1), priority_push_us=round(t_tree * 1e6, 1),
+                       ratio=round(t_tree / t_ring, 3))
+    # write-back
+    rows = []
+    for batch in (128, 65536):
+        index = torch.randint(0, ring.capacity, (batch,), device="cuda:0", dtype=torch.int64)
+        prio = torch.rand(batch, device="cuda:0", dtype=torch.float64) + 0.5
+        t = _timed(lambda: T._learn_lib.check(L.tpl_priority_update(ring.tree.data_ptr(), ring.capacity, batch, index.data_ptr(),
+                                                                     prio.data_ptr(), stream)), 20)
+        rows.append(dict(batch=batch, us=round(t * 1e6, 2)))
+    out["update_priorities"] = rows
+    env.terminate()
+    del ring, traj
+    torch.cuda.empty_cache()
+    # DQNLearner.update(): both modes, same box, same run, alternated
+    uni, per = [], []
+    for _ in range(2):
+        uni.append(_update_rate(128, False))
+        per.append(_update_rate(128, True))
+    tu, tp = min(uni), min(per)
+    out["learner_update"] = dict(batch=128, uniform_updates_per_s=round(1 / tu, 1), prioritized_updates_per_s=round(1 / tp, 1),
+                                 prioritized_overhead=round(tp / tu - 1, 4))
+    torch.cuda.empty_cache()
+    loop = part_loop(prioritized=True)
+    loop["part"] = "loop_prioritized"
+    out["loop"] = loop
+    return out
 
 
 def main():
