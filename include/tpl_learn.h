@@ -113,6 +113,29 @@ int tpl_replay_sample_prioritized(const void* ring, const void* tree, int64_t ca
 /* u_i of draw i on the host (for tests): ((i + U_i) * total) / batch; -1 if batch < 1, i < 0 or i >= batch. */
 double tpl_priority_target(uint64_t seed, uint64_t update, int64_t i, int64_t batch, double total);
 
+/* n-step returns.  Every push of a [T][stride] chunk advances the head by T * stride, so global transition g = tau * stride + i
+ * (step tau, board i) lives in slot g mod capacity and the same board's next transition is `stride` slots later.  For a drawn
+ * slot j of a ring with host-side `head` and filled `size` (size < capacity only with head == size):
+ *   age(j) = (head - 1 - j) mod capacity               transitions pushed after slot j
+ *   successor k of j = slot (j + k * stride) mod capacity, which exists iff k * stride <= age(j)
+ *   K: go k = 0, 1, ... while k < n_step and successor k exists; stop AFTER the first record with done != 0 (it is included),
+ *      so 1 <= K <= n_step
+ *   R (float32, no fused multiply-add): g_0 = 1, R = r_0; for k = 1 .. K-1: g_k = g_{k-1} * gamma, R = R + g_k * r_k, each
+ *      product and each sum rounded once
+ *   done = the done byte of record K-1;  discount = 0 if done, else g_{K-1} * gamma (float32: gamma^K as an iterated product)
+ *   s' = the s' planes of successor K-1;  obs (of s), action, index and prob: those of slot j;  steps = K.
+ * At n_step = 1 the outputs are tpl_replay_sample's / tpl_replay_sample_prioritized's bit for bit, with discount gamma or 0. */
+#define TPL_NSTEP_MAX 16
+
+/* One minibatch with n-step returns.  tree == NULL: draw i takes tpl_replay_sample's slot (index optional, prob must be NULL);
+ * otherwise tpl_replay_sample_prioritized's (index and prob required).  ret, discount f32 and done, steps u8 [batch] are
+ * required.  Refused besides the two samplers' own checks: n_step outside [1, TPL_NSTEP_MAX], gamma outside [0, 1] or NaN,
+ * stride outside [1, capacity], head outside [0, capacity), size < capacity with head != size. */
+int tpl_replay_sample_nstep(const void* ring, const void* tree, int64_t capacity, int64_t size, int64_t head, int64_t stride,
+                            int32_t n_step, float gamma, int64_t batch, uint64_t seed, uint64_t update, int32_t L, int32_t M,
+                            void* obs, int32_t dtype, void* next_a, void* next_b, uint8_t* action, float* ret, float* discount,
+                            uint8_t* done, uint8_t* steps, int64_t* index, float* prob, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

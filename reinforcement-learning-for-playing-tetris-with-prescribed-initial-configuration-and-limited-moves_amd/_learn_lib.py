@@ -26,8 +26,9 @@ _UNITS = [os.path.join(_LEARN_CSRC, f) for f in ("replay.hip", "pack.hip", "prio
 LEARN_SYMBOLS = [
     "tpl_learn_last_error", "tpl_replay_record_bytes", "tpl_replay_push", "tpl_replay_sample", "tpl_replay_index",
     "tpl_learn_image_bytes", "tpl_learn_pack", "tpl_priority_tree_bytes", "tpl_priority_init", "tpl_priority_push",
-    "tpl_priority_update", "tpl_replay_sample_prioritized", "tpl_priority_target",
+    "tpl_priority_update", "tpl_replay_sample_prioritized", "tpl_priority_target", "tpl_replay_sample_nstep",
 ]
+NSTEP_MAX = 16
 
 IMAGE_KINDS = {"bf16": 0, "f32": 1, "split": 2}
 RECORD_BYTES = 80
@@ -118,8 +119,10 @@ def lib() -> C.CDLL:
                                                 vp]
     L.tpl_priority_target.restype = f64
     L.tpl_priority_target.argtypes = [u64, u64, i64, i64, f64]
+    L.tpl_replay_sample_nstep.argtypes = [vp, vp, i64, i64, i64, i64, i32, C.c_float, i64, u64, u64, i32, i32, vp, i32, vp, vp,
+                                          vp, vp, vp, vp, vp, vp, vp, vp]
     for name in ("tpl_replay_push", "tpl_replay_sample", "tpl_learn_pack", "tpl_priority_init", "tpl_priority_push",
-                 "tpl_priority_update", "tpl_replay_sample_prioritized"):
+                 "tpl_priority_update", "tpl_replay_sample_prioritized", "tpl_replay_sample_nstep"):
         getattr(L, name).restype = i32
     _handle = L
     return L
@@ -269,6 +272,38 @@ def prioritized_draws(tree: np.ndarray, seed: int, update: int, batch: int):
         pick, picked = np.where(none, last, pick), np.where(none, last_v, picked)
         j, leaf = j * PRIORITY_FANOUT + pick, picked
     return np.minimum(j, capacity - 1), (leaf / total).astype(np.float32)
+
+
+# ------------------------------------------------------------------------------------------------ n-step returns
+def nstep_targets(records, capacity: int, size: int, head: int, stride: int, slots, n_step: int, gamma: float):
+    """The n-step rule of include/tpl_learn.h for drawn `slots` (i64 [B]) of a ring of [capacity, 80] record bytes:
+    (R f32, discount f32, done u8, steps u8, s'-source slot i64), each [B], as tpl_replay_sample_nstep writes them.  Float32
+    numpy operations, each product and each sum rounded once."""
+    capacity, size, head, stride, n_step = int(capacity), int(size), int(head), int(stride), int(n_step)
+    if not (1 <= capacity < (1 << 32) and 1 <= size <= capacity and 0 <= head < capacity and 1 <= stride <= capacity
+            and 1 <= n_step <= NSTEP_MAX and 0.0 <= gamma <= 1.0 and (size == capacity or head == size)):
+        raise ValueError("nstep_targets: arguments outside what tpl_replay_sample_nstep takes")
+    rec = np.ascontiguousarray(records, dtype=np.uint8).reshape(capacity, RECORD_BYTES)
+    reward = rec[:, 64:68].copy().view(np.float32).reshape(-1)
+    dones = rec[:, 69]
+    j = np.asarray(slots, dtype=np.int64)
+    g32 = np.float32(gamma)
+    age = (head - 1 - j) % capacity
+    ret, g = reward[j].copy(), np.ones(j.shape, np.float32)
+    last = np.zeros(j.shape, np.int64)
+    open_ = dones[j] == 0
+    for k in range(1, n_step):
+        take = open_ & (k * stride <= age)
+        sk = (j + k * stride) % capacity
+        gk = g * g32
+        ret = np.where(take, ret + gk * reward[sk], ret)
+        g = np.where(take, gk, g)
+        last = np.where(take, k, last)
+        open_ = take & (dones[sk] == 0)
+    src = (j + last * stride) % capacity
+    done = dones[src].copy()
+    discount = np.where(done != 0, np.float32(0.0), g * g32).astype(np.float32)
+    return ret.astype(np.float32), discount, done, (last + 1).astype(np.uint8), src
 
 
 # ------------------------------------------------------------------------------------------------ device packing

@@ -13,6 +13,8 @@
 //           (random slots: the 80 B are the whole traffic of the read side), s is turned into 217 feature bytes in LDS
 //           and leaves as the wave's contiguous span of the observation with 16-byte non-temporal stores -- observe.hip's
 //           scheme, so a draw costs 80 B read and 868 B (f32) / 434 B (bf16) + 32 B + 6 B written.
+//   n-step  tpl_replay_sample_nstep: the same kernels in emit_draw's n-step form (tpl_replay_draw.h), which adds up to
+//           n_step - 1 successor tail words and one s' read per draw, and writes the return, discount and step count.
 #include "tpl_replay_draw.h"
 
 #include <cstdarg>
@@ -69,7 +71,7 @@ __global__ __launch_bounds__(kPushBlock) void replay_push_kernel(const PushArgs 
     rec[0] = sa; rec[1] = sb; rec[2] = na; rec[3] = nb; rec[4] = tail;
 }
 
-template <typename T>
+template <typename T, int kN = 0>                      // kN: emit_draw's form (0: 1-step)
 __global__ __launch_bounds__(64 * kObsWaves) void replay_sample_kernel(const SampleArgs p) {
     __shared__ __attribute__((aligned(16))) uint8_t s_rows[kObsWaves][kWaveLds];
     const int lane = threadIdx.x & 63;
@@ -77,10 +79,22 @@ __global__ __launch_bounds__(64 * kObsWaves) void replay_sample_kernel(const Sam
     if (base >= p.batch) return;                                                          // wave-uniform
     const int count = (int)((p.batch - base) < 64 ? (p.batch - base) : 64);
     const int64_t slot = lane < count ? replay_slot(p.key, (uint64_t)(base + lane), (uint64_t)p.size) : 0;
-    emit_draw<T>(p, s_rows[threadIdx.x >> 6], lane, count, base, slot);
+    emit_draw<T, kN>(p, s_rows[threadIdx.x >> 6], lane, count, base, slot);
 }
 
 }  // namespace
+
+int launch_nstep_uniform(const SampleArgs& p, int32_t dtype, hipStream_t stream) {
+    const dim3 grid((unsigned)((p.batch + 64 * kObsWaves - 1) / (64 * kObsWaves))), block(64 * kObsWaves);
+    dispatch_nstep(p.n_step, [&](auto n) {
+        if (dtype == TPL_F32)
+            hipLaunchKernelGGL((replay_sample_kernel<float, decltype(n)::value>), grid, block, 0, stream, p);
+        else
+            hipLaunchKernelGGL((replay_sample_kernel<__hip_bfloat16, decltype(n)::value>), grid, block, 0, stream, p);
+    });
+    TPL_LEARN_HIP(hipGetLastError());
+    return TPL_OK;
+}
 }  // namespace tpl_learn
 
 using namespace tpl_learn;
@@ -143,4 +157,41 @@ extern "C" int tpl_replay_sample(const void* ring, int64_t capacity, int64_t siz
         hipLaunchKernelGGL(replay_sample_kernel<__hip_bfloat16>, grid, block, 0, (hipStream_t)stream, p);
     TPL_LEARN_HIP(hipGetLastError());
     return TPL_OK;
+}
+
+extern "C" int tpl_replay_sample_nstep(const void* ring, const void* tree, int64_t capacity, int64_t size, int64_t head,
+                                       int64_t stride, int32_t n_step, float gamma, int64_t batch, uint64_t seed, uint64_t update,
+                                       int32_t L, int32_t M, void* obs, int32_t dtype, void* next_a, void* next_b, uint8_t* action,
+                                       float* ret, float* discount, uint8_t* done, uint8_t* steps, int64_t* index, float* prob,
+                                       void* stream) {
+    if (!ring || !obs || !next_a || !next_b || !action || !ret || !discount || !done || !steps)
+        return fail_msg(TPL_ERR_ARG, "tpl_replay_sample_nstep: null pointer");
+    if (tree && (!index || !prob))
+        return fail_msg(TPL_ERR_ARG, "tpl_replay_sample_nstep: null pointer (a tree needs index and prob)");
+    if (!tree && prob) return fail_msg(TPL_ERR_ARG, "tpl_replay_sample_nstep: prob must be NULL without a tree");
+    if (capacity < 1 || capacity >= kMaxSize) return fail_msg(TPL_ERR_ARG, "tpl_replay_sample_nstep: capacity must be in [1, 2^32)");
+    if (size < 1 || size > capacity)
+        return fail_msg(TPL_ERR_ARG, "tpl_replay_sample_nstep: size must be in [1, capacity] (an empty ring has nothing to draw)");
+    if (batch < 1) return fail_msg(TPL_ERR_ARG, "tpl_replay_sample_nstep: batch must be positive");
+    if (batch > ((int64_t)1 << 31) / TPL_OBS_DIM) return fail_msg(TPL_ERR_ARG, "tpl_replay_sample_nstep: batch too large");
+    if (L < 1 || L > 255 || M < 1 || M > 255) return fail_msg(TPL_ERR_ARG, "tpl_replay_sample_nstep: L and M must be in [1, 255]");
+    if (dtype != TPL_F32 && dtype != TPL_BF16)
+        return fail_msg(TPL_ERR_ARG, "tpl_replay_sample_nstep: unknown observation dtype %d", dtype);
+    if (((uintptr_t)ring & 15u) || ((uintptr_t)obs & 15u) || ((uintptr_t)next_a & 15u) || ((uintptr_t)next_b & 15u))
+        return fail_msg(TPL_ERR_ARG, "tpl_replay_sample_nstep: ring, obs and planes must be 16-byte aligned");
+    if (n_step < 1 || n_step > TPL_NSTEP_MAX)
+        return fail_msg(TPL_ERR_ARG, "tpl_replay_sample_nstep: n_step must be in [1, %d]", TPL_NSTEP_MAX);
+    if (!(gamma >= 0.0f && gamma <= 1.0f)) return fail_msg(TPL_ERR_ARG, "tpl_replay_sample_nstep: gamma must be in [0, 1]");
+    if (stride < 1 || stride > capacity) return fail_msg(TPL_ERR_ARG, "tpl_replay_sample_nstep: stride must be in [1, capacity]");
+    if (head < 0 || head >= capacity) return fail_msg(TPL_ERR_ARG, "tpl_replay_sample_nstep: head must be in [0, capacity)");
+    if (size < capacity && head != size)
+        return fail_msg(TPL_ERR_ARG, "tpl_replay_sample_nstep: head must equal size until the ring is full");
+    SampleArgs p{};
+    p.ring = (const uint4*)ring; p.size = size; p.batch = batch; p.key = replay_key(seed, update);
+    p.L = (uint32_t)L; p.M = (uint32_t)M; p.obs = obs; p.next_a = (uint4*)next_a; p.next_b = (uint4*)next_b;
+    p.action = action; p.reward = ret; p.done = done; p.index = index;
+    p.capacity = capacity; p.head = head; p.stride = stride; p.n_step = n_step; p.gamma = gamma;
+    p.discount = discount; p.steps = steps;
+    if (tree) return launch_nstep_prioritized(p, tree, capacity, prob, dtype, (hipStream_t)stream);
+    return launch_nstep_uniform(p, dtype, (hipStream_t)stream);
 }

@@ -23,7 +23,8 @@ have an arg-max the decode does not return).
 
 TD target  y = r + gamma * (1 - done) * (max Q'_rot(s') + max Q'_loc(s')), in float32; loss SmoothL1 (Huber, delta 1)
 between Q(s, a) and y; gradients clipped to +-100 by value; AdamW(lr, amsgrad=True); after every update the soft update
-theta' <- tau * theta + (1 - tau) * theta' and a repack of the target image.
+theta' <- tau * theta + (1 - tau) * theta' and a repack of the target image.  With n_step > 1 the sampler returns the n-step
+return R and discount gamma^K (0 after a done) instead, and y = R + discount * (max Q'_rot(s') + max Q'_loc(s')).
 
 Epsilon schedule  eps_end + (eps_start - eps_end) * exp(-steps_done / eps_decay), where steps_done counts LOCKSTEP
 ITERATIONS of the batch: the batched reading of the reference's per-action counter (each iteration is one action on every
@@ -34,6 +35,7 @@ from __future__ import annotations
 import copy
 import ctypes as C
 import math
+import weakref
 from typing import Optional
 
 import torch
@@ -50,7 +52,11 @@ RECORD_BYTES = _learn_lib.RECORD_BYTES
 class ReplayRing:
     """`capacity` transitions of 80 bytes on the device (include/tpl_learn.h).  A push of a [T, N] chunk at head h writes
     transition (t, board i) to slot (h + t * N + i) mod capacity; the oldest transitions are overwritten.  Draws are uniform
-    with replacement over the filled slots [0, size)."""
+    with replacement over the filled slots [0, size).
+
+    n-step returns (sample(..., n_step > 1)) follow a board from slot to slot `stride` = N apart, so they need every push
+    since construction to have come from one environment object with one N; a push that breaks this is still taken, but
+    n-step sampling raises ValueError afterwards."""
 
     def __init__(self, capacity: int, device):
         capacity = int(capacity)
@@ -60,9 +66,59 @@ class ReplayRing:
         self.data = torch.zeros(capacity * RECORD_BYTES, dtype=torch.uint8, device=self.device)
         self.head = 0
         self.size = 0
+        self.stride = None                                       # N of the first push
+        self._source = None                                      # weak reference to the environment of the first push
+        self._one_source = True                                  # every push since: that environment, that N
 
     def _stream(self):
         return torch._C._cuda_getCurrentRawStream(self.device.index)
+
+    def _track_push(self, env, n: int) -> None:
+        """Bookkeeping of the n-step rule: the first push fixes the environment and the stride, any other breaks it."""
+        if self.stride is None:
+            self.stride, self._source = int(n), weakref.ref(env)
+        elif int(n) != self.stride or self._source() is not env:
+            self._one_source = False
+
+    def _nstep_args(self, n_step, gamma):
+        """Validated (n_step, gamma) of a sample() call; gamma is None at n_step = 1."""
+        if isinstance(n_step, bool) or int(n_step) != n_step or not 1 <= int(n_step) <= _learn_lib.NSTEP_MAX:
+            raise ValueError(f"n_step must be an integer in [1, {_learn_lib.NSTEP_MAX}]")
+        n_step = int(n_step)
+        if n_step == 1:
+            return 1, None
+        if gamma is None:
+            raise ValueError("n_step > 1 needs gamma")
+        gamma = float(gamma)
+        if not 0.0 <= gamma <= 1.0:
+            raise ValueError("gamma must be in [0, 1]")
+        if not self._one_source:
+            raise ValueError("n-step sampling needs every push from one environment with one N: this ring was pushed from "
+                             "more than one environment or with more than one N")
+        return n_step, gamma
+
+    def _sample_nstep(self, tree, batch, seed, update, next_env, obs_dtype, with_index, n_step, gamma) -> dict:
+        d = self.device
+        out = dict(obs=torch.empty((batch, OBS_DIM), dtype=obs_dtype, device=d),
+                   action=torch.empty(batch, dtype=torch.uint8, device=d),
+                   reward=torch.empty(batch, dtype=torch.float32, device=d),
+                   done=torch.empty(batch, dtype=torch.uint8, device=d),
+                   discount=torch.empty(batch, dtype=torch.float32, device=d),
+                   steps=torch.empty(batch, dtype=torch.uint8, device=d))
+        if with_index or tree is not None:
+            out["index"] = torch.empty(batch, dtype=torch.int64, device=d)
+        if tree is not None:
+            out["prob"] = torch.empty(batch, dtype=torch.float32, device=d)
+        pa, pb = C.c_void_p(), C.c_void_p()
+        from ._lib import check as env_check
+        env_check(next_env._lib.tpl_state_ptrs(next_env._h, C.byref(pa), C.byref(pb)))
+        ptr = lambda k: out[k].data_ptr() if k in out else None
+        check(_learn_lib.lib().tpl_replay_sample_nstep(
+            self.data.data_ptr(), None if tree is None else tree.data_ptr(), self.capacity, self.size, self.head, self.stride,
+            n_step, gamma, batch, int(seed) % (1 << 64), int(update) % (1 << 64), next_env.L, next_env.M, out["obs"].data_ptr(),
+            _OBS_CODES[obs_dtype], pa.value, pb.value, ptr("action"), ptr("reward"), ptr("discount"), ptr("done"), ptr("steps"),
+            ptr("index"), ptr("prob"), self._stream()))
+        return out
 
     def push(self, env: BatchedTetris, traj: dict) -> None:
         """Append the trajectory of env.actor_rollout(..., record=True, record_states=True), called just before: s' of the
@@ -89,18 +145,26 @@ class ReplayRing:
                                                pb.value, self._stream()))
         self.head = (self.head + steps * n) % self.capacity
         self.size = min(self.size + steps * n, self.capacity)
+        self._track_push(env, n)
 
     def sample(self, batch: int, seed: int, update: int, next_env: BatchedTetris, obs_dtype=torch.float32,
-               with_index: bool = False) -> dict:
+               with_index: bool = False, n_step: int = 1, gamma: Optional[float] = None) -> dict:
         """One minibatch: draw i takes slot _learn_lib.replay_indices(seed, update, batch, size)[i].  Returns obs [batch, 217]
         (the observation of s, as env.expand_states makes it), action u8, reward f32, done u8 (and index i64); the s' planes
-        are written into the resident state of `next_env`, an environment of exactly `batch` boards."""
+        are written into the resident state of `next_env`, an environment of exactly `batch` boards.
+
+        n_step > 1 (gamma required): the n-step rule of include/tpl_learn.h (_learn_lib.nstep_targets restates it).  reward
+        is then the return R, done and s' are those of the last record taken, and discount f32 (gamma^K, or 0 if done) and
+        steps u8 (K) are added."""
+        n_step, gamma = self._nstep_args(n_step, gamma)
         if self.size < 1:
             raise ValueError("the replay ring is empty")
         if next_env.num_envs != batch or next_env.device != self.device:
             raise ValueError(f"next_env must hold exactly {batch} boards on {self.device}")
         if obs_dtype not in _OBS_CODES:
             raise ValueError("obs_dtype must be torch.float32 or torch.bfloat16")
+        if n_step > 1:
+            return self._sample_nstep(None, batch, seed, update, next_env, obs_dtype, with_index, n_step, gamma)
         d = self.device
         out = dict(obs=torch.empty((batch, OBS_DIM), dtype=obs_dtype, device=d),
                    action=torch.empty(batch, dtype=torch.uint8, device=d),
@@ -149,15 +213,22 @@ class PrioritizedReplayRing(ReplayRing):
         check(_learn_lib.lib().tpl_priority_push(self.tree.data_ptr(), self.capacity, head, count, self._stream()))
         self.pushes += 1
 
-    def sample(self, batch: int, seed: int, update: int, next_env: BatchedTetris, obs_dtype=torch.float32) -> dict:
+    def sample(self, batch: int, seed: int, update: int, next_env: BatchedTetris, obs_dtype=torch.float32, n_step: int = 1,
+               gamma: Optional[float] = None) -> dict:
         """One minibatch of proportional draws: draw i takes the slot _learn_lib.prioritized_draws(tree, seed, update, batch)
-        names.  Returns what ReplayRing.sample returns, with index i64 [batch] and prob f32 [batch]."""
+        names.  Returns what ReplayRing.sample returns, with index i64 [batch] and prob f32 [batch]; n_step and gamma as
+        there (the return, done, s', discount and steps of the n-step rule; index and prob stay the drawn slot's)."""
+        n_step, gamma = self._nstep_args(n_step, gamma)
         if self.size < 1:
             raise ValueError("the replay ring is empty")
         if next_env.num_envs != batch or next_env.device != self.device:
             raise ValueError(f"next_env must hold exactly {batch} boards on {self.device}")
         if obs_dtype not in _OBS_CODES:
             raise ValueError("obs_dtype must be torch.float32 or torch.bfloat16")
+        if n_step > 1:
+            out = self._sample_nstep(self.tree, batch, seed, update, next_env, obs_dtype, True, n_step, gamma)
+            self._sampled_at = self.pushes
+            return out
         d = self.device
         out = dict(obs=torch.empty((batch, OBS_DIM), dtype=obs_dtype, device=d),
                    action=torch.empty(batch, dtype=torch.uint8, device=d),
@@ -223,12 +294,30 @@ def factored_max(out: torch.Tensor) -> torch.Tensor:
     return out[:, :4].max(dim=1).values + out[:, 4:14].max(dim=1).values
 
 
-class DQNLearner:
+class _TakesNStep(type):
+    """DQNLearner(..., n_step=1): the class call takes n_step and checks it before __init__ runs, so that __init__'s
+    parameter list (its positional order, the prioritized options last) stays as it is."""
+
+    def __call__(cls, *args, n_step: int = 1, **kwargs):
+        if isinstance(n_step, bool) or int(n_step) != n_step or not 1 <= int(n_step) <= _learn_lib.NSTEP_MAX:
+            raise ValueError(f"n_step must be an integer in [1, {_learn_lib.NSTEP_MAX}]")
+        self = cls.__new__(cls)
+        self.n_step = int(n_step)
+        self.__init__(*args, **kwargs)
+        return self
+
+
+class DQNLearner(metaclass=_TakesNStep):
     """DQN for Model(217, 14) on a BatchedTetris (defaults: the constants of the upstream model/train.py).
 
     prioritized=True draws minibatches from a PrioritizedReplayRing (proportional, exponent alpha), weights the Huber loss
     per sample by importance-sampling weights (exponent beta, annealed to beta_final over beta_updates updates) and writes
     back (|q - y| + priority_eps)^alpha after each optimizer step.
+
+    n_step=n in [1, 16] bootstraps from n-step returns drawn on the device (include/tpl_learn.h):
+    y = R + discount * max Q'(s'), where R sums up to n rewards of one board discounted by gamma, the sum stops after a done,
+    discount is gamma^K (0 after a done) and s' is the state K moves on.  As in Rainbow (Hessel et al., 2018) the return of
+    epsilon-greedy data is not corrected for being off-policy.  n_step=1 is the 1-step target above, computed as before.
 
     collect(steps)   one actor_rollout of the online net's split image at the scheduled epsilon, pushed into the ring
     update(n=1)      n minibatch updates (sample -> Q(s) in torch, Q'(s') on the split kernel -> Huber -> AdamW -> soft update)
@@ -239,6 +328,9 @@ class DQNLearner:
                  gamma: float = 0.99, eps_start: float = 0.9, eps_end: float = 0.05, eps_decay: float = 1000,
                  tau: float = 0.005, lr: float = 1e-4, seed: int = 0, prioritized: bool = False, alpha: float = 0.6,
                  beta: float = 0.4, beta_final: float = 1.0, beta_updates: int = 100_000, priority_eps: float = 1e-6):
+        # self.n_step: set and checked by the class call (_TakesNStep)
+        if self.n_step > 1 and not 0.0 <= gamma <= 1.0:
+            raise ValueError("n-step returns need gamma in [0, 1]")
         if not env.auto_reset:
             raise ValueError("DQNLearner needs an environment with auto_reset=True (the replay ring's s' of a finished "
                              "episode is the freshly reset board, masked by done)")
@@ -315,15 +407,19 @@ class DQNLearner:
         Prioritized: also prob (of each draw) and weight, the importance-sampling weight (size * prob)^-beta divided by the
         largest weight IN THE MINIBATCH (Dopamine's convention, chosen over Schaul et al.'s division by the weight of the
         globally smallest priority so that no min-tree is needed), float32."""
+        nstep = dict(n_step=self.n_step, gamma=self.gamma) if self.n_step > 1 else {}
         if self.prioritized:
-            batch = self.ring.sample(self.batch_size, self.seed, self.updates, self.next_env)
+            batch = self.ring.sample(self.batch_size, self.seed, self.updates, self.next_env, **nstep)
             w = (self.ring.size * batch["prob"].double()).pow(-self.beta())
             batch["weight"] = (w / w.max()).float()
         else:
-            batch = self.ring.sample(self.batch_size, self.seed, self.updates, self.next_env, with_index=True)
+            batch = self.ring.sample(self.batch_size, self.seed, self.updates, self.next_env, with_index=True, **nstep)
         self.next_env.policy_act(self.target_image, out=self._next_action, logits=self._next_q)
         next_q = self._next_q.clone()
-        y = batch["reward"] + self.gamma * (1.0 - batch["done"].float()) * factored_max(next_q)
+        if self.n_step > 1:                                      # reward: the n-step return; discount: gamma^K, 0 after a done
+            y = batch["reward"] + batch["discount"] * factored_max(next_q)
+        else:
+            y = batch["reward"] + self.gamma * (1.0 - batch["done"].float()) * factored_max(next_q)
         return dict(batch, next_q=next_q, y=y)
 
     def _update_once(self) -> torch.Tensor:

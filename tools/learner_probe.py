@@ -13,6 +13,10 @@ Parts:
     priority  prioritized replay: tpl_replay_sample_prioritized against tpl_replay_sample (B = 65,536 and 2^20, float32 obs, a
               2^22 ring), tpl_priority_push against tpl_replay_push (16 x 262,144), tpl_priority_update (B = 128 and 65,536),
               DQNLearner.update() per second with and without prioritized=True (B = 128), and the loop's win rate with PER on
+    nstep     n-step returns: tpl_replay_sample_nstep at n = 1, 3 and 5 against tpl_replay_sample (and, with the tree, against
+              tpl_replay_sample_prioritized) at B = 65,536 and 2^20, float32 obs, a 2^22 ring, every variant timed in each of
+              five alternating rounds; DQNLearner.update() at B = 128 with n_step = 1 and 3, alternated three times; the loop's
+              win rate with n_step = 3
 """
 import argparse
 import json
@@ -25,7 +29,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 HBM_ACHIEVABLE = 6.3e12
-PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600, "priority": 600}
+PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600, "priority": 600, "nstep": 600}
 
 
 def _timed(fn, reps, warmup=3):
@@ -111,7 +115,7 @@ def part_update():
     return dict(part="update", rows=rows)
 
 
-def part_loop(prioritized=False):
+def part_loop(prioritized=False, n_step=1):
     import torch
     import tetris_piclim as T
     n, rounds, per = 262144, 300, 4
@@ -121,7 +125,7 @@ def part_loop(prioritized=False):
     env.reset()
     torch.manual_seed(0)
     learner = T.DQNLearner(env, capacity=1 << 22, batch_size=1024, eps_start=1.0, eps_end=0.05, eps_decay=10, tau=0.05,
-                           lr=1e-3, seed=0, prioritized=prioritized)
+                           lr=1e-3, seed=0, prioritized=prioritized, n_step=n_step)
     before = learner.evaluate(8)["win_rate"]
     random_rate = learner.evaluate(8, epsilon=1.0)["win_rate"]
     torch.cuda.synchronize()
@@ -142,14 +146,14 @@ def part_loop(prioritized=False):
                 win_rate_greedy_after=round(after["win_rate"], 4), eval_episodes=after["episodes"])
 
 
-def _update_rate(batch, prioritized, reps=200):
+def _update_rate(batch, prioritized, reps=200, n_step=1):
     import torch
     import tetris_piclim as T
     env = T.BatchedTetris(10, 40, 1 << 16, device="cuda:0", seed=1, auto_reset=True)
     env.load_configs(*env.synthetic_configs(4096))
     env.reset()
     torch.manual_seed(0)
-    learner = T.DQNLearner(env, capacity=1 << 20, batch_size=batch, seed=1, prioritized=prioritized)
+    learner = T.DQNLearner(env, capacity=1 << 20, batch_size=batch, seed=1, prioritized=prioritized, n_step=n_step)
     learner.collect(8)
     learner.update(5)
     torch.cuda.synchronize()
@@ -215,6 +219,81 @@ def part_priority():
     torch.cuda.empty_cache()
     loop = part_loop(prioritized=True)
     loop["part"] = "loop_prioritized"
+    out["loop"] = loop
+    return out
+
+
+def _spread(ts):
+    """min / median / max of a list of seconds, in µs."""
+    s = sorted(ts)
+    return dict(min=round(s[0] * 1e6, 2), median=round(s[len(s) // 2] * 1e6, 2), max=round(s[-1] * 1e6, 2))
+
+
+def part_nstep(rounds=5):
+    import ctypes as C
+    import torch
+    import tetris_piclim as T
+    L = T._learn_lib.lib()
+    check = T._learn_lib.check
+    out = dict(part="nstep")
+    env, _, ring, _ = _filled_ring(prioritized=True)
+    stream = torch._C._cuda_getCurrentRawStream(0)
+    cap, size, head, stride = ring.capacity, ring.size, ring.head, ring.stride
+    gamma, seed = 0.99, 7
+    rows = []
+    for batch in (65536, 1 << 20):
+        next_env = T.BatchedTetris(10, 40, batch, device="cuda:0", seed=2)
+        pa, pb = C.c_void_p(), C.c_void_p()
+        T._lib.check(next_env._lib.tpl_state_ptrs(next_env._h, C.byref(pa), C.byref(pb)))
+        e = lambda dt: torch.empty(batch, dtype=dt, device="cuda:0")
+        obs = torch.empty((batch, 217), dtype=torch.float32, device="cuda:0")
+        action, reward, done, steps = e(torch.uint8), e(torch.float32), e(torch.uint8), e(torch.uint8)
+        discount, index, prob = e(torch.float32), e(torch.int64), e(torch.float32)
+        f32 = T.learn._OBS_CODES[torch.float32]
+        k = [0]
+
+        def ref(tree):
+            k[0] += 1
+            if tree is None:
+                check(L.tpl_replay_sample(ring.data.data_ptr(), cap, size, batch, seed, k[0], 10, 40, obs.data_ptr(), f32, pa.value,
+                                          pb.value, action.data_ptr(), reward.data_ptr(), done.data_ptr(), index.data_ptr(),
+                                          stream))
+            else:
+                check(L.tpl_replay_sample_prioritized(ring.data.data_ptr(), tree, cap, size, batch, seed, k[0], 10, 40,
+                                                      obs.data_ptr(), f32, pa.value, pb.value, action.data_ptr(),
+                                                      reward.data_ptr(), done.data_ptr(), index.data_ptr(), prob.data_ptr(),
+                                                      stream))
+
+        def nstep(tree, n):
+            k[0] += 1
+            check(L.tpl_replay_sample_nstep(ring.data.data_ptr(), tree, cap, size, head, stride, n, gamma, batch, seed, k[0], 10,
+                                            40, obs.data_ptr(), f32, pa.value, pb.value, action.data_ptr(), reward.data_ptr(),
+                                            discount.data_ptr(), done.data_ptr(), steps.data_ptr(), index.data_ptr(),
+                                            None if tree is None else prob.data_ptr(), stream))
+        for mode, tree in (("uniform", None), ("prioritized", ring.tree.data_ptr())):
+            variants = [("ref", lambda: ref(tree))] + [(f"n{n}", (lambda n=n: nstep(tree, n))) for n in (1, 3, 5)]
+            times = {name: [] for name, _ in variants}
+            for _ in range(rounds):                              # alternate the variants round by round
+                for name, fn in variants:
+                    times[name].append(_timed(fn, 20))
+            med = {name: sorted(ts)[len(ts) // 2] for name, ts in times.items()}
+            rows.append(dict(batch=batch, mode=mode, us={name: _spread(ts) for name, ts in times.items()},
+                             ratio_of_medians={name: round(med[name] / med["ref"], 3) for name in med if name != "ref"}))
+        next_env.terminate()
+    out["sample"] = dict(ring=cap, obs="float32", rounds=rounds, launches_per_timing=20, rows=rows)
+    env.terminate()
+    del ring
+    torch.cuda.empty_cache()
+    one, three = [], []
+    for _ in range(3):
+        one.append(_update_rate(128, False))
+        three.append(_update_rate(128, False, n_step=3))
+    out["learner_update"] = dict(batch=128, n1_ms=[round(t * 1e3, 4) for t in one], n3_ms=[round(t * 1e3, 4) for t in three],
+                                 n1_spread=round(max(one) / min(one) - 1, 4),
+                                 n3_over_n1_median=round(sorted(three)[1] / sorted(one)[1] - 1, 4))
+    torch.cuda.empty_cache()
+    loop = part_loop(n_step=3)
+    loop["part"] = "loop_nstep3"
     out["loop"] = loop
     return out
 
