@@ -1,6 +1,7 @@
 /*
- * tpl_learn.h -- C ABI of the learner library (libtpl_learn.so): a packed replay ring on the device and device-side
- * packing of a PolicyMLP's parameters into the three policy images of libtetris_piclim.so.
+ * tpl_learn.h -- C ABI of the learner library (libtpl_learn.so): a packed replay ring on the device, its samplers (uniform,
+ * prioritized, n-step, each optionally mirrored) and device-side packing of a PolicyMLP's parameters into the three policy
+ * images of libtetris_piclim.so.
  *
  * Conventions (as include/tetris_piclim.h)
  *   - every function returns 0 on success or a negative tpl_status (TPL_ERR_ARG, TPL_ERR_HIP, ...);
@@ -135,6 +136,44 @@ int tpl_replay_sample_nstep(const void* ring, const void* tree, int64_t capacity
                             int32_t n_step, float gamma, int64_t batch, uint64_t seed, uint64_t update, int32_t L, int32_t M,
                             void* obs, int32_t dtype, void* next_a, void* next_b, uint8_t* action, float* ret, float* discount,
                             uint8_t* done, uint8_t* steps, int64_t* index, float* prob, void* stream);
+
+/* Mirror symmetry.  The game is exactly symmetric under the left-right reflection: reflect the board, swap L <-> J and S <-> Z in
+ * the piece list, reflect the action, and the move gives the reflected board with the same lines cleared, reward and ending.
+ *
+ * Mirror of a 32-byte state (planes A, B): column word x <-> column word 9 - x; each of the twelve 3-bit window entries p
+ * (the four bits kept in B.z included) becomes pi(p), pi = TPL_PIECE_MIRROR = [0, 2, 1, 3, 5, 4, 6, 7] (ids I0 L1 J2 T3 S4 Z5
+ * O6, 7 = none); lines, moves, state, slot and the unused bit 31 of B.y stay.  An involution on all 256 bits.
+ * Mirror of an action a (u8) taken in state s: r = (a / 10) & 3, l = a % 10, w = the width of shape table entry [cur(s)][r]
+ * with cur(s) = window entry 0 of s (for cur = 7 the table's entry as it stands: O's), l_eff = min(l, 10 - w),
+ *   a' = 10 * ((4 - r) & 3) + (10 - w - l_eff)            always below 40; mirroring twice gives 10 * r + l_eff.
+ * Mirror of the observation: cell 10 y + x <-> cell 10 y + 9 - x, 200 + p -> 200 + pi(p), 207 + p -> 207 + pi(p) (p < 7),
+ * features 214..216 fixed -- the observation of the mirrored state is this permutation of the observation of the state, bit
+ * for bit in float32 and bf16.
+ * A mirrored draw: obs is that of the mirrored s, next_a / next_b the mirrored s' (n-step: the s' of the last record taken),
+ * action the drawn record's, mirrored with the drawn record's cur.  The return, done, discount, steps, index and prob are
+ * those of the plain draw: priorities belong to the slot, mirrored or not.
+ * `mirror`: TPL_MIRROR_NEVER; TPL_MIRROR_COIN: draw i is mirrored iff bit 0 of h_i, the splitmix64 word at position i + 1 of the
+ * stream keyed by (seed, update) that tpl_replay_index maps and tpl_priority_target takes its U_i from (which use its top bits);
+ * TPL_MIRROR_ALWAYS. */
+typedef enum { TPL_MIRROR_NEVER = 0, TPL_MIRROR_COIN = 1, TPL_MIRROR_ALWAYS = 2 } tpl_mirror_mode;
+#define TPL_PIECE_MIRROR {0, 2, 1, 3, 5, 4, 6, 7}
+
+/* One minibatch in any of the four draw forms, mirrored as `mirror` says.  n_step >= 1: tpl_replay_sample_nstep's arguments,
+ * checks and outputs.  n_step = 0: the 1-step form of tpl_replay_sample (tree == NULL) / tpl_replay_sample_prioritized, whose
+ * outputs it writes (`ret` is their reward); head, stride and gamma are not read and discount and steps must be NULL.
+ * mirrored u8 [batch] (optional, may be NULL): 1 where draw i was reflected, else 0 (all 0 at TPL_MIRROR_NEVER).
+ * At TPL_MIRROR_NEVER every output is the corresponding existing entry's byte for byte (the same kernels). */
+int tpl_replay_sample_mirror(const void* ring, const void* tree, int64_t capacity, int64_t size, int64_t head, int64_t stride,
+                             int32_t n_step, float gamma, int64_t batch, uint64_t seed, uint64_t update, int32_t L, int32_t M,
+                             void* obs, int32_t dtype, void* next_a, void* next_b, uint8_t* action, float* ret, float* discount,
+                             uint8_t* done, uint8_t* steps, int64_t* index, float* prob, int32_t mirror, uint8_t* mirrored,
+                             void* stream);
+
+/* The mirror of `count` states: planes a / b [count] 16-byte words -> out_a / out_b (which may be a / b themselves).  With
+ * action and out_action u8 [count] (both or neither; out_action may be action): out_action[i] = the mirror of action[i] taken
+ * in state i as given.  The device function is the samplers'. */
+int tpl_mirror_states(int64_t count, const void* a, const void* b, void* out_a, void* out_b, const uint8_t* action,
+                      uint8_t* out_action, void* stream);
 
 #ifdef __cplusplus
 }

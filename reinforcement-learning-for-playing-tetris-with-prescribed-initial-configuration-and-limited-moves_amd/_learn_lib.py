@@ -27,8 +27,10 @@ LEARN_SYMBOLS = [
     "tpl_learn_last_error", "tpl_replay_record_bytes", "tpl_replay_push", "tpl_replay_sample", "tpl_replay_index",
     "tpl_learn_image_bytes", "tpl_learn_pack", "tpl_priority_tree_bytes", "tpl_priority_init", "tpl_priority_push",
     "tpl_priority_update", "tpl_replay_sample_prioritized", "tpl_priority_target", "tpl_replay_sample_nstep",
+    "tpl_replay_sample_mirror", "tpl_mirror_states",
 ]
 NSTEP_MAX = 16
+MIRROR_MODES = {False: 0, True: 1, "always": 2}          # sample(mirror=...) -> tpl_mirror_mode
 
 IMAGE_KINDS = {"bf16": 0, "f32": 1, "split": 2}
 RECORD_BYTES = 80
@@ -121,8 +123,11 @@ def lib() -> C.CDLL:
     L.tpl_priority_target.argtypes = [u64, u64, i64, i64, f64]
     L.tpl_replay_sample_nstep.argtypes = [vp, vp, i64, i64, i64, i64, i32, C.c_float, i64, u64, u64, i32, i32, vp, i32, vp, vp,
                                           vp, vp, vp, vp, vp, vp, vp, vp]
+    L.tpl_replay_sample_mirror.argtypes = L.tpl_replay_sample_nstep.argtypes[:-1] + [i32, vp, vp]
+    L.tpl_mirror_states.argtypes = [i64, vp, vp, vp, vp, vp, vp, vp]
     for name in ("tpl_replay_push", "tpl_replay_sample", "tpl_learn_pack", "tpl_priority_init", "tpl_priority_push",
-                 "tpl_priority_update", "tpl_replay_sample_prioritized", "tpl_replay_sample_nstep"):
+                 "tpl_priority_update", "tpl_replay_sample_prioritized", "tpl_replay_sample_nstep", "tpl_replay_sample_mirror",
+                 "tpl_mirror_states"):
         getattr(L, name).restype = i32
     _handle = L
     return L
@@ -304,6 +309,73 @@ def nstep_targets(records, capacity: int, size: int, head: int, stride: int, slo
     done = dones[src].copy()
     discount = np.where(done != 0, np.float32(0.0), g * g32).astype(np.float32)
     return ret.astype(np.float32), discount, done, (last + 1).astype(np.uint8), src
+
+
+# ------------------------------------------------------------------------------------------------ mirror symmetry
+# A numpy mirror of csrc/learn/tpl_mirror.h (the rule: include/tpl_learn.h).
+PIECE_MIRROR = (0, 2, 1, 3, 5, 4, 6, 7)                  # pi: L <-> J, S <-> Z
+# the observation of the mirrored state is obs[:, MIRROR_OBS_PERM] of the state's (an involution)
+MIRROR_OBS_PERM = np.array([10 * y + 9 - x for y in range(20) for x in range(10)] + [200 + p for p in PIECE_MIRROR[:7]]
+                           + [207 + p for p in PIECE_MIRROR[:7]] + [214, 215, 216], dtype=np.int64)
+
+
+def mirror_mode(mirror) -> int:
+    """sample(mirror=...) -> 0 (False), 1 (True: the coin) or 2 ("always"); ValueError for anything else, 0 and 1 included."""
+    if isinstance(mirror, (bool, str)) and mirror in MIRROR_MODES:
+        return MIRROR_MODES[mirror]
+    raise ValueError('mirror must be False, True (each draw mirrored on its coin) or "always"')
+
+
+def mirror_states(a, b):
+    """The mirror of states given as plane pairs (uint32 / int32 [K, 4] each) -> (A, B) uint32 [K, 4]: column x <-> column
+    9 - x, every window entry p -> PIECE_MIRROR[p]; lines, moves, state, slot and the unused bit 31 of B.y stay."""
+    A = np.ascontiguousarray(a).view(np.uint32).reshape(-1, 4).astype(np.uint64)
+    B = np.ascontiguousarray(b).view(np.uint32).reshape(-1, 4).astype(np.uint64)
+    u = np.uint64
+    c20, top4 = u(0xFFFFF), u(60)
+    # three 20-bit columns and a 4-bit field per 64 bits: (A.x, A.y), (A.z, A.w), (B.x, B.y); then col9 | lines | window[35:32]
+    w64 = [A[:, 0] | (A[:, 1] << u(32)), A[:, 2] | (A[:, 3] << u(32)), B[:, 0] | (B[:, 1] << u(32))]
+    cols = [(w >> u(20 * k)) & c20 for w in w64 for k in range(3)] + [B[:, 2] & c20]
+    cols = cols[::-1]
+    out = [cols[3 * j] | (cols[3 * j + 1] << u(20)) | (cols[3 * j + 2] << u(40)) | ((w64[j] >> top4) << top4) for j in range(3)]
+    window = B[:, 3] | ((B[:, 2] >> u(28)) << u(32))
+    mirrored = np.zeros_like(window)
+    pi = np.array(PIECE_MIRROR, dtype=np.uint64)
+    for e in range(12):
+        mirrored |= pi[((window >> u(3 * e)) & u(7)).astype(np.int64)] << u(3 * e)
+    lo, m32 = u(0xFFFFFFFF), u(32)
+    bz = cols[9] | (B[:, 2] & u(0x0FF00000)) | ((mirrored >> m32) << u(28))
+    A2 = np.stack([out[0] & lo, out[0] >> m32, out[1] & lo, out[1] >> m32], axis=1).astype(np.uint32)
+    B2 = np.stack([out[2] & lo, out[2] >> m32, bz, mirrored & lo], axis=1).astype(np.uint32)
+    return A2, B2
+
+
+_widths = None
+
+
+def shape_widths() -> np.ndarray:
+    """int64 [8, 4]: the width of shape table entry [piece][rotations & 3], through the environment library's host shape
+    query; row 7 ("none") is the table's own entry for it, O's."""
+    global _widths
+    if _widths is None:
+        w = [[_lib.shape_info(p, r)[1] for r in range(4)] for p in range(7)]
+        _widths = np.array(w + [w[6]], dtype=np.int64)
+    return _widths
+
+
+def mirror_actions(action, a, b) -> np.ndarray:
+    """The mirror of actions (u8 [K]) taken in the states (a, b) as given: r = (a // 10) & 3, l = a % 10, w the width of
+    [cur][r], a' = 10 ((4 - r) & 3) + (10 - w - min(l, 10 - w)) (uint8 [K], always below 40)."""
+    act = np.asarray(action, dtype=np.uint8).astype(np.int64).reshape(-1)
+    cur = (np.ascontiguousarray(b).view(np.uint32).reshape(-1, 4)[:, 3] & np.uint32(7)).astype(np.int64)
+    r, l = (act // 10) & 3, act % 10
+    w = shape_widths()[cur, r]
+    return (10 * ((4 - r) & 3) + (10 - w - np.minimum(l, 10 - w))).astype(np.uint8)
+
+
+def mirror_coins(seed: int, update: int, batch: int) -> np.ndarray:
+    """Which draws of a minibatch mode 1 mirrors (uint8 [batch]): bit 0 of h_i, the hash word replay_indices maps."""
+    return (_draw_hashes(seed, update, batch) & np.uint64(1)).astype(np.uint8)
 
 
 # ------------------------------------------------------------------------------------------------ device packing

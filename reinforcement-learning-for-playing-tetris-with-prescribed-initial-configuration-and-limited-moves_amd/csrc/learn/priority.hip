@@ -52,7 +52,7 @@ Layout layout(int64_t capacity) {
 
 __host__ __device__ inline double draw_target(uint64_t key, int64_t i, int64_t batch, double total) {
 #pragma clang fp contract(off)
-    const uint64_t h = mix64(key + kGolden * ((uint64_t)i + 1));
+    const uint64_t h = draw_hash(key, (uint64_t)i);
     const double U = (double)(h >> 11) * 0x1.0p-53;
     return (((double)i + U) * total) / (double)batch;
 }
@@ -181,7 +181,7 @@ __device__ __forceinline__ int64_t descend(const DescentArgs& d, double u, doubl
     return j < d.capacity ? j : d.capacity - 1;      // a consistent tree never reaches a padding child; stay in the ring
 }
 
-template <typename T, int kN = 0>                      // kN: emit_draw's form (0: 1-step)
+template <typename T, int kN = 0, bool kMirror = false>      // emit_draw's form (kN = 0: 1-step)
 __global__ __launch_bounds__(64 * kObsWaves) void replay_sample_prioritized_kernel(const SampleArgs p, const DescentArgs d) {
     __shared__ __attribute__((aligned(16))) uint8_t s_rows[kObsWaves][kWaveLds];
     const int lane = threadIdx.x & 63;
@@ -195,7 +195,7 @@ __global__ __launch_bounds__(64 * kObsWaves) void replay_sample_prioritized_kern
         slot = descend(d, draw_target(p.key, base + lane, p.batch, total), leaf);
         d.prob[base + lane] = (float)(leaf / total);
     }
-    emit_draw<T, kN>(p, s_rows[threadIdx.x >> 6], lane, count, base, slot);
+    emit_draw<T, kN, kMirror>(p, s_rows[threadIdx.x >> 6], lane, count, base, slot);
 }
 
 unsigned blocks(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
@@ -209,18 +209,20 @@ int check_tree(const char* fn, const void* tree, int64_t capacity) {
 
 }  // namespace
 
-int launch_nstep_prioritized(const SampleArgs& p, const void* tree, int64_t capacity, float* prob, int32_t dtype,
-                             hipStream_t stream) {
-    if (int e = check_tree("tpl_replay_sample_nstep", tree, capacity)) return e;
+int launch_prioritized(const char* fn, const SampleArgs& p, const void* tree, int64_t capacity, float* prob, int32_t dtype,
+                       hipStream_t stream) {
+    if (int e = check_tree(fn, tree, capacity)) return e;
     DescentArgs d{};
     d.tree = (const double*)tree; d.lay = layout(capacity); d.root = d.lay.offset[d.lay.levels - 1]; d.capacity = capacity;
     d.prob = prob;
     const dim3 grid((unsigned)((p.batch + 64 * kObsWaves - 1) / (64 * kObsWaves))), block(64 * kObsWaves);
-    dispatch_nstep(p.n_step, [&](auto n) {
+    dispatch_form(p, [&](auto n, auto m) {
+        constexpr int kN = decltype(n)::value;
+        constexpr bool kMirror = decltype(m)::value;
         if (dtype == TPL_F32)
-            hipLaunchKernelGGL((replay_sample_prioritized_kernel<float, decltype(n)::value>), grid, block, 0, stream, p, d);
+            hipLaunchKernelGGL((replay_sample_prioritized_kernel<float, kN, kMirror>), grid, block, 0, stream, p, d);
         else
-            hipLaunchKernelGGL((replay_sample_prioritized_kernel<__hip_bfloat16, decltype(n)::value>), grid, block, 0, stream, p, d);
+            hipLaunchKernelGGL((replay_sample_prioritized_kernel<__hip_bfloat16, kN, kMirror>), grid, block, 0, stream, p, d);
     });
     TPL_LEARN_HIP(hipGetLastError());
     return TPL_OK;

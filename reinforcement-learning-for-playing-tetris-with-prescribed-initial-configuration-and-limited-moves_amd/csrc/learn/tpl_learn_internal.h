@@ -31,8 +31,12 @@ __host__ __device__ inline uint64_t mix64(uint64_t z) {            // the splitm
 // half of the 64 x 64-bit product (size < 2^32).  _learn_lib.replay_indices restates it in numpy.
 __host__ __device__ inline uint64_t replay_key(uint64_t seed, uint64_t update) { return mix64(seed + kGolden * (update + 1)); }
 
+// h_i: the one 64-bit word of draw i.  The uniform slot is its product's high half, the prioritized target takes h_i >> 11 and
+// the mirror coin (include/tpl_learn.h) is its bit 0.
+__host__ __device__ inline uint64_t draw_hash(uint64_t key, uint64_t i) { return mix64(key + kGolden * (i + 1)); }
+
 __host__ __device__ inline int64_t replay_slot(uint64_t key, uint64_t i, uint64_t size) {
-    const uint64_t h = mix64(key + kGolden * (i + 1));
+    const uint64_t h = draw_hash(key, i);
 #ifdef __HIP_DEVICE_COMPILE__
     return (int64_t)__umul64hi(h, size);
 #else

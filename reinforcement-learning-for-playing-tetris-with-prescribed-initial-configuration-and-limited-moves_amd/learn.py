@@ -97,14 +97,19 @@ class ReplayRing:
                              "more than one environment or with more than one N")
         return n_step, gamma
 
-    def _sample_nstep(self, tree, batch, seed, update, next_env, obs_dtype, with_index, n_step, gamma) -> dict:
+    def _sample_nstep(self, tree, batch, seed, update, next_env, obs_dtype, with_index, n_step, gamma, mirror=0) -> dict:
+        """The n-step draw (mirror = 0: tpl_replay_sample_nstep) or, with a mirror mode, any draw form through
+        tpl_replay_sample_mirror (n_step = 1 is then the 1-step form: no discount, no steps)."""
         d = self.device
         out = dict(obs=torch.empty((batch, OBS_DIM), dtype=obs_dtype, device=d),
                    action=torch.empty(batch, dtype=torch.uint8, device=d),
                    reward=torch.empty(batch, dtype=torch.float32, device=d),
-                   done=torch.empty(batch, dtype=torch.uint8, device=d),
-                   discount=torch.empty(batch, dtype=torch.float32, device=d),
-                   steps=torch.empty(batch, dtype=torch.uint8, device=d))
+                   done=torch.empty(batch, dtype=torch.uint8, device=d))
+        if n_step > 1 or not mirror:
+            out.update(discount=torch.empty(batch, dtype=torch.float32, device=d),
+                       steps=torch.empty(batch, dtype=torch.uint8, device=d))
+        if mirror:
+            out["mirrored"] = torch.empty(batch, dtype=torch.uint8, device=d)
         if with_index or tree is not None:
             out["index"] = torch.empty(batch, dtype=torch.int64, device=d)
         if tree is not None:
@@ -113,11 +118,14 @@ class ReplayRing:
         from ._lib import check as env_check
         env_check(next_env._lib.tpl_state_ptrs(next_env._h, C.byref(pa), C.byref(pb)))
         ptr = lambda k: out[k].data_ptr() if k in out else None
-        check(_learn_lib.lib().tpl_replay_sample_nstep(
-            self.data.data_ptr(), None if tree is None else tree.data_ptr(), self.capacity, self.size, self.head, self.stride,
-            n_step, gamma, batch, int(seed) % (1 << 64), int(update) % (1 << 64), next_env.L, next_env.M, out["obs"].data_ptr(),
-            _OBS_CODES[obs_dtype], pa.value, pb.value, ptr("action"), ptr("reward"), ptr("discount"), ptr("done"), ptr("steps"),
-            ptr("index"), ptr("prob"), self._stream()))
+        args = [self.data.data_ptr(), None if tree is None else tree.data_ptr(), self.capacity, self.size, self.head,
+                self.stride or 1, n_step if "steps" in out else 0, gamma or 0.0, batch, int(seed) % (1 << 64),
+                int(update) % (1 << 64), next_env.L, next_env.M, out["obs"].data_ptr(), _OBS_CODES[obs_dtype], pa.value, pb.value,
+                ptr("action"), ptr("reward"), ptr("discount"), ptr("done"), ptr("steps"), ptr("index"), ptr("prob")]
+        if mirror:
+            check(_learn_lib.lib().tpl_replay_sample_mirror(*args, mirror, ptr("mirrored"), self._stream()))
+        else:
+            check(_learn_lib.lib().tpl_replay_sample_nstep(*args, self._stream()))
         return out
 
     def push(self, env: BatchedTetris, traj: dict) -> None:
@@ -148,14 +156,19 @@ class ReplayRing:
         self._track_push(env, n)
 
     def sample(self, batch: int, seed: int, update: int, next_env: BatchedTetris, obs_dtype=torch.float32,
-               with_index: bool = False, n_step: int = 1, gamma: Optional[float] = None) -> dict:
+               with_index: bool = False, n_step: int = 1, gamma: Optional[float] = None, mirror=False) -> dict:
         """One minibatch: draw i takes slot _learn_lib.replay_indices(seed, update, batch, size)[i].  Returns obs [batch, 217]
         (the observation of s, as env.expand_states makes it), action u8, reward f32, done u8 (and index i64); the s' planes
         are written into the resident state of `next_env`, an environment of exactly `batch` boards.
 
         n_step > 1 (gamma required): the n-step rule of include/tpl_learn.h (_learn_lib.nstep_targets restates it).  reward
         is then the return R, done and s' are those of the last record taken, and discount f32 (gamma^K, or 0 if done) and
-        steps u8 (K) are added."""
+        steps u8 (K) are added.
+
+        mirror=True reflects each draw left to right on its coin (_learn_lib.mirror_coins), mirror="always" every draw: obs,
+        the s' planes and action are those of the reflected transition (include/tpl_learn.h; _learn_lib.mirror_states,
+        mirror_actions and MIRROR_OBS_PERM restate it), everything else is the plain draw's, and mirrored u8 [batch] is added."""
+        mirror = _learn_lib.mirror_mode(mirror)
         n_step, gamma = self._nstep_args(n_step, gamma)
         if self.size < 1:
             raise ValueError("the replay ring is empty")
@@ -163,8 +176,8 @@ class ReplayRing:
             raise ValueError(f"next_env must hold exactly {batch} boards on {self.device}")
         if obs_dtype not in _OBS_CODES:
             raise ValueError("obs_dtype must be torch.float32 or torch.bfloat16")
-        if n_step > 1:
-            return self._sample_nstep(None, batch, seed, update, next_env, obs_dtype, with_index, n_step, gamma)
+        if n_step > 1 or mirror:
+            return self._sample_nstep(None, batch, seed, update, next_env, obs_dtype, with_index, n_step, gamma, mirror)
         d = self.device
         out = dict(obs=torch.empty((batch, OBS_DIM), dtype=obs_dtype, device=d),
                    action=torch.empty(batch, dtype=torch.uint8, device=d),
@@ -214,10 +227,12 @@ class PrioritizedReplayRing(ReplayRing):
         self.pushes += 1
 
     def sample(self, batch: int, seed: int, update: int, next_env: BatchedTetris, obs_dtype=torch.float32, n_step: int = 1,
-               gamma: Optional[float] = None) -> dict:
+               gamma: Optional[float] = None, mirror=False) -> dict:
         """One minibatch of proportional draws: draw i takes the slot _learn_lib.prioritized_draws(tree, seed, update, batch)
         names.  Returns what ReplayRing.sample returns, with index i64 [batch] and prob f32 [batch]; n_step and gamma as
-        there (the return, done, s', discount and steps of the n-step rule; index and prob stay the drawn slot's)."""
+        there (the return, done, s', discount and steps of the n-step rule; index and prob stay the drawn slot's), and mirror
+        as there (index and prob are the slot's, mirrored or not)."""
+        mirror = _learn_lib.mirror_mode(mirror)
         n_step, gamma = self._nstep_args(n_step, gamma)
         if self.size < 1:
             raise ValueError("the replay ring is empty")
@@ -225,8 +240,8 @@ class PrioritizedReplayRing(ReplayRing):
             raise ValueError(f"next_env must hold exactly {batch} boards on {self.device}")
         if obs_dtype not in _OBS_CODES:
             raise ValueError("obs_dtype must be torch.float32 or torch.bfloat16")
-        if n_step > 1:
-            out = self._sample_nstep(self.tree, batch, seed, update, next_env, obs_dtype, True, n_step, gamma)
+        if n_step > 1 or mirror:
+            out = self._sample_nstep(self.tree, batch, seed, update, next_env, obs_dtype, True, n_step, gamma, mirror)
             self._sampled_at = self.pushes
             return out
         d = self.device
@@ -295,14 +310,17 @@ def factored_max(out: torch.Tensor) -> torch.Tensor:
 
 
 class _TakesNStep(type):
-    """DQNLearner(..., n_step=1): the class call takes n_step and checks it before __init__ runs, so that __init__'s
-    parameter list (its positional order, the prioritized options last) stays as it is."""
+    """DQNLearner(..., n_step=1, mirror=False): the class call takes the keyword-only options and checks them before __init__
+    runs, so that __init__'s parameter list (its positional order, the prioritized options last) stays as it is."""
 
-    def __call__(cls, *args, n_step: int = 1, **kwargs):
+    def __call__(cls, *args, n_step: int = 1, mirror: bool = False, **kwargs):
         if isinstance(n_step, bool) or int(n_step) != n_step or not 1 <= int(n_step) <= _learn_lib.NSTEP_MAX:
             raise ValueError(f"n_step must be an integer in [1, {_learn_lib.NSTEP_MAX}]")
+        if not isinstance(mirror, bool):
+            raise ValueError("mirror must be False or True")
         self = cls.__new__(cls)
         self.n_step = int(n_step)
+        self.mirror = mirror
         self.__init__(*args, **kwargs)
         return self
 
@@ -319,6 +337,10 @@ class DQNLearner(metaclass=_TakesNStep):
     discount is gamma^K (0 after a done) and s' is the state K moves on.  As in Rainbow (Hessel et al., 2018) the return of
     epsilon-greedy data is not corrected for being off-policy.  n_step=1 is the 1-step target above, computed as before.
 
+    mirror=True draws every minibatch with the mirror coin: about half of its transitions come reflected left to right (s, a
+    and s'; the game is symmetric under it), so y and Q(s, a) are those of the reflected transition, and the minibatch gains
+    `mirrored`.  Priorities are written back to the slot whichever way it was drawn.  mirror=False is every path as before.
+
     collect(steps)   one actor_rollout of the online net's split image at the scheduled epsilon, pushed into the ring
     update(n=1)      n minibatch updates (sample -> Q(s) in torch, Q'(s') on the split kernel -> Huber -> AdamW -> soft update)
     evaluate(steps)  the greedy policy (epsilon 0) on a separate environment over the same pool: episodes, wins, win rate
@@ -328,7 +350,7 @@ class DQNLearner(metaclass=_TakesNStep):
                  gamma: float = 0.99, eps_start: float = 0.9, eps_end: float = 0.05, eps_decay: float = 1000,
                  tau: float = 0.005, lr: float = 1e-4, seed: int = 0, prioritized: bool = False, alpha: float = 0.6,
                  beta: float = 0.4, beta_final: float = 1.0, beta_updates: int = 100_000, priority_eps: float = 1e-6):
-        # self.n_step: set and checked by the class call (_TakesNStep)
+        # self.n_step, self.mirror: set and checked by the class call (_TakesNStep)
         if self.n_step > 1 and not 0.0 <= gamma <= 1.0:
             raise ValueError("n-step returns need gamma in [0, 1]")
         if not env.auto_reset:
@@ -408,6 +430,8 @@ class DQNLearner(metaclass=_TakesNStep):
         largest weight IN THE MINIBATCH (Dopamine's convention, chosen over Schaul et al.'s division by the weight of the
         globally smallest priority so that no min-tree is needed), float32."""
         nstep = dict(n_step=self.n_step, gamma=self.gamma) if self.n_step > 1 else {}
+        if self.mirror:
+            nstep["mirror"] = True
         if self.prioritized:
             batch = self.ring.sample(self.batch_size, self.seed, self.updates, self.next_env, **nstep)
             w = (self.ring.size * batch["prob"].double()).pow(-self.beta())

@@ -17,6 +17,9 @@ Parts:
               tpl_replay_sample_prioritized) at B = 65,536 and 2^20, float32 obs, a 2^22 ring, every variant timed in each of
               five alternating rounds; DQNLearner.update() at B = 128 with n_step = 1 and 3, alternated three times; the loop's
               win rate with n_step = 3
+    mirror    mirror symmetry: tpl_replay_sample_mirror in modes 0 (never), 1 (the coin) and 2 (always) against the existing entry
+              of each form -- uniform, prioritized and uniform n = 3 -- at 2^20 draws, float32 obs, a 2^22 ring, every variant
+              timed in each of five alternating rounds; the loop's win rate and wall time with mirror=False and mirror=True
 """
 import argparse
 import json
@@ -29,7 +32,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 HBM_ACHIEVABLE = 6.3e12
-PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600, "priority": 600, "nstep": 600}
+PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600, "priority": 600, "nstep": 600, "mirror": 600}
 
 
 def _timed(fn, reps, warmup=3):
@@ -115,7 +118,7 @@ def part_update():
     return dict(part="update", rows=rows)
 
 
-def part_loop(prioritized=False, n_step=1):
+def part_loop(prioritized=False, n_step=1, mirror=False):
     import torch
     import tetris_piclim as T
     n, rounds, per = 262144, 300, 4
@@ -125,7 +128,7 @@ def part_loop(prioritized=False, n_step=1):
     env.reset()
     torch.manual_seed(0)
     learner = T.DQNLearner(env, capacity=1 << 22, batch_size=1024, eps_start=1.0, eps_end=0.05, eps_decay=10, tau=0.05,
-                           lr=1e-3, seed=0, prioritized=prioritized, n_step=n_step)
+                           lr=1e-3, seed=0, prioritized=prioritized, n_step=n_step, mirror=mirror)
     before = learner.evaluate(8)["win_rate"]
     random_rate = learner.evaluate(8, epsilon=1.0)["win_rate"]
     torch.cuda.synchronize()
@@ -295,6 +298,77 @@ def part_nstep(rounds=5):
     loop = part_loop(n_step=3)
     loop["part"] = "loop_nstep3"
     out["loop"] = loop
+    return out
+
+
+def part_mirror(rounds=5):
+    import ctypes as C
+    import torch
+    import tetris_piclim as T
+    L = T._learn_lib.lib()
+    check = T._learn_lib.check
+    out = dict(part="mirror")
+    env, _, ring, _ = _filled_ring(prioritized=True)
+    stream = torch._C._cuda_getCurrentRawStream(0)
+    cap, size, head, stride = ring.capacity, ring.size, ring.head, ring.stride
+    gamma, seed, batch = 0.99, 7, 1 << 20
+    next_env = T.BatchedTetris(10, 40, batch, device="cuda:0", seed=2)
+    pa, pb = C.c_void_p(), C.c_void_p()
+    T._lib.check(next_env._lib.tpl_state_ptrs(next_env._h, C.byref(pa), C.byref(pb)))
+    e = lambda dt: torch.empty(batch, dtype=dt, device="cuda:0")
+    obs = torch.empty((batch, 217), dtype=torch.float32, device="cuda:0")
+    action, reward, done, steps, mirrored = e(torch.uint8), e(torch.float32), e(torch.uint8), e(torch.uint8), e(torch.uint8)
+    discount, index, prob = e(torch.float32), e(torch.int64), e(torch.float32)
+    f32 = T.learn._OBS_CODES[torch.float32]
+    tree = ring.tree.data_ptr()
+    k = [0]
+    front = (obs.data_ptr(), f32, pa.value, pb.value, action.data_ptr(), reward.data_ptr())
+
+    def existing(form):
+        k[0] += 1
+        if form == "uniform":
+            check(L.tpl_replay_sample(ring.data.data_ptr(), cap, size, batch, seed, k[0], 10, 40, *front, done.data_ptr(),
+                                      index.data_ptr(), stream))
+        elif form == "prioritized":
+            check(L.tpl_replay_sample_prioritized(ring.data.data_ptr(), tree, cap, size, batch, seed, k[0], 10, 40, *front,
+                                                  done.data_ptr(), index.data_ptr(), prob.data_ptr(), stream))
+        else:
+            check(L.tpl_replay_sample_nstep(ring.data.data_ptr(), None, cap, size, head, stride, 3, gamma, batch, seed, k[0], 10, 40,
+                                            *front, discount.data_ptr(), done.data_ptr(), steps.data_ptr(), index.data_ptr(), None,
+                                            stream))
+
+    def mirror(form, mode):
+        k[0] += 1
+        n = 3 if form == "nstep3" else 0
+        check(L.tpl_replay_sample_mirror(ring.data.data_ptr(), tree if form == "prioritized" else None, cap, size, head, stride, n,
+                                         gamma, batch, seed, k[0], 10, 40, *front, discount.data_ptr() if n else None,
+                                         done.data_ptr(), steps.data_ptr() if n else None, index.data_ptr(),
+                                         prob.data_ptr() if form == "prioritized" else None, mode, mirrored.data_ptr(), stream))
+    rows = []
+    for form in ("uniform", "prioritized", "nstep3"):
+        variants = [("existing", lambda: existing(form))] + [(f"mode{m}", (lambda m=m: mirror(form, m))) for m in (0, 1, 2)]
+        times = {name: [] for name, _ in variants}
+        for _ in range(rounds):                                  # alternate the variants round by round
+            for name, fn in variants:
+                times[name].append(_timed(fn, 20))
+        med = {name: sorted(ts)[len(ts) // 2] for name, ts in times.items()}
+        rows.append(dict(batch=batch, form=form, us={name: _spread(ts) for name, ts in times.items()},
+                         ratio_to_mode0={name: round(med[name] / med["mode0"], 3) for name in med if name != "mode0"}))
+    mirror("uniform", 1)
+    torch.cuda.synchronize()
+    out["sample"] = dict(ring=cap, obs="float32", rounds=rounds, launches_per_timing=20, rows=rows,
+                         mirrored_fraction_of_last_coin_draw=round(float(mirrored.float().mean()), 4))
+    next_env.terminate()
+    env.terminate()
+    del ring
+    torch.cuda.empty_cache()
+    loops = []
+    for flag in (False, True, False, True):                      # alternated: the wall time's own spread shows
+        loop = part_loop(mirror=flag)
+        loop["part"] = "loop_mirror" if flag else "loop_plain"
+        loops.append(loop)
+        torch.cuda.empty_cache()
+    out["loops"] = loops
     return out
 
 
