@@ -1,7 +1,7 @@
 /*
  * tpl_learn.h -- C ABI of the learner library (libtpl_learn.so): a packed replay ring on the device, its samplers (uniform,
- * prioritized, n-step, each optionally mirrored) and device-side packing of a PolicyMLP's parameters into the three policy
- * images of libtetris_piclim.so.
+ * prioritized, n-step, each optionally mirrored), device-side packing of a PolicyMLP's parameters into the three policy
+ * images of libtetris_piclim.so, and the enumeration of a board's 40 afterstates.
  *
  * Conventions (as include/tetris_piclim.h)
  *   - every function returns 0 on success or a negative tpl_status (TPL_ERR_ARG, TPL_ERR_HIP, ...);
@@ -174,6 +174,40 @@ int tpl_replay_sample_mirror(const void* ring, const void* tree, int64_t capacit
  * in state i as given.  The device function is the samplers'. */
 int tpl_mirror_states(int64_t count, const void* a, const void* b, void* out_a, void* out_b, const uint8_t* action,
                       uint8_t* out_action, void* stream);
+
+/* Afterstates.  For a 32-byte state s (planes A, B) and each of the 40 actions a = 10 r + l (r = a / 10 in 0..3, l = a % 10), what
+ * playing a from s leaves -- without touching s.  Outputs are laid out [n][40]: pair (i, a) at index 40 i + a.
+ *
+ * Finished board (state(s) != running): the afterstate is s bit for bit, reward 0, done 1, cleared 0 -- a frozen board of tpl_step.
+ * Running board: the move of the environment's device code as it stands (move_board(s, shape, r, l, L, M, topout) of
+ * csrc/tpl_device.h: on a top-out the board and moves stay, the state becomes lost), then the piece window popped by one entry
+ * WITHOUT a refill (next_window(s, false, 0): a 36-bit shift, zeros enter at the top).  cleared = the rows cleared (0..4),
+ * done = (state' != running), reward = r_line * cleared (+ r_win when the move wins) (+ r_lose when it loses) in float32: one
+ * rounded multiply and at most one rounded add, never fused (0.1f * 3 + x differs in the last bit when fused) -- step_reward's
+ * rule.  The slot bit and the unused bit 31 of B.y are carried over.
+ * canonical[a] = 10 * (r mod nrot(cur)) + min(l, 10 - w(cur, r)): cur = window entry 0 of s, nrot = TPL_PIECE_ROTATIONS,
+ * w = the width of shape table entry [cur][r] as the table stands (so cur = 7 reads O's).  Two actions with one canonical value
+ * are the same placement -- the right clamp and `rotations % len` alias 6 to 31 of the 40 -- and a == canonical[a] marks the
+ * distinct ones: 17 for I, 34 for L, J and T, 17 for S and Z, 9 for O.  canonical is computed for finished boards too.
+ *
+ * Relation to the step: for a running board the afterstate is what a non-auto-reset tpl_step with the same reward parameters
+ * leaves in the planes, and reward and done are the step's -- with ONE exception: on the move at which the environment refills
+ * the window ((moves + 1) % 10 == 0 with a pool loaded) window entries 2..11 (bits 6..31 of B.w, bits 28..31 of B.z) are the
+ * pool's next piece word there and the shifted-down rest here.  Entries 0 and 1 -- all that the observation reads -- are equal
+ * by construction of the piece words.  So AN AFTERSTATE'S WINDOW IS GOOD FOR `cur` AND `next` ONLY: a search deeper than one
+ * ply must start from environment states. */
+#define TPL_PIECE_ROTATIONS {2, 4, 4, 4, 2, 2, 1, 1}
+
+/* The 40 afterstates of each of `n` states: plane_a / plane_b [n] 16-byte words (read only) -> out_a / out_b [n][40] 16-byte
+ * words (both or neither; e.g. the resident planes of a 40 n-board environment, tpl_state_ptrs), reward f32, done u8, cleared u8,
+ * canonical u8 [n][40], each optional; at least one output.  Refused before any HIP call: n < 1, 40 n >= 2^31, a NULL or
+ * misaligned (16 bytes) plane pointer, only one of out_a / out_b, no output at all, L or M outside [1, 255]. */
+int tpl_afterstates(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line, float r_win,
+                    float r_lose, void* out_a, void* out_b, float* reward, uint8_t* done, uint8_t* cleared, uint8_t* canonical,
+                    void* stream);
+
+/* canonical[action] for current piece `cur` (0..7) on the host, for tests; -1 if cur or action (0..39) is out of range. */
+int32_t tpl_canonical_action(int32_t cur, int32_t action);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,7 @@ from ._lib import (LIB_PATH, SYMBOLS, TplError, build_library, carve, forward_ge
 
 __all__ = ["BatchedTetris", "Tetris", "Snapshot", "OBS_DIM", "NUM_ACTIONS", "RUNNING", "WON", "LOST", "TplError",
            "RandomPieceGenerator", "get_tetromino", "piece_translations", "translate", "carve", "build_library", "shape_info", "generate_configs", "forward_generate", "pack_policy", "LIB_PATH", "SYMBOLS", "DQNLearner",
-           "ReplayRing", "PrioritizedReplayRing"]
+           "ReplayRing", "PrioritizedReplayRing", "LookaheadPolicy", "afterstates"]
 
 
 def __getattr__(name):
@@ -32,6 +32,8 @@ def __getattr__(name):
     if name in ("DQNLearner", "ReplayRing", "PrioritizedReplayRing"):
         # the learner library (libtpl_learn.so) is built and loaded only here, on first use
         return getattr(importlib.import_module(__name__ + ".learn"), name)
-    if name in ("learn", "_learn_lib"):
+    if name in ("LookaheadPolicy", "afterstates"):
+        return getattr(importlib.import_module(__name__ + ".lookahead"), name)
+    if name in ("learn", "_learn_lib", "lookahead"):
         return importlib.import_module(__name__ + "." + name)
     raise AttributeError(name)

@@ -20,14 +20,14 @@ from ._lib import TplError, _hipcc
 
 _LEARN_CSRC = os.path.join(_lib._CSRC, "learn")
 LEARN_LIB_PATH = os.path.join(_lib._LIBDIR, "libtpl_learn.so")
-_UNITS = [os.path.join(_LEARN_CSRC, f) for f in ("replay.hip", "pack.hip", "priority.hip")]
+_UNITS = [os.path.join(_LEARN_CSRC, f) for f in ("replay.hip", "pack.hip", "priority.hip", "afterstates.hip")]
 
 # entry points declared in include/tpl_learn.h (tests check that the .so exports every one of them)
 LEARN_SYMBOLS = [
     "tpl_learn_last_error", "tpl_replay_record_bytes", "tpl_replay_push", "tpl_replay_sample", "tpl_replay_index",
     "tpl_learn_image_bytes", "tpl_learn_pack", "tpl_priority_tree_bytes", "tpl_priority_init", "tpl_priority_push",
     "tpl_priority_update", "tpl_replay_sample_prioritized", "tpl_priority_target", "tpl_replay_sample_nstep",
-    "tpl_replay_sample_mirror", "tpl_mirror_states",
+    "tpl_replay_sample_mirror", "tpl_mirror_states", "tpl_afterstates", "tpl_canonical_action",
 ]
 NSTEP_MAX = 16
 MIRROR_MODES = {False: 0, True: 1, "always": 2}          # sample(mirror=...) -> tpl_mirror_mode
@@ -125,9 +125,12 @@ def lib() -> C.CDLL:
                                           vp, vp, vp, vp, vp, vp, vp, vp]
     L.tpl_replay_sample_mirror.argtypes = L.tpl_replay_sample_nstep.argtypes[:-1] + [i32, vp, vp]
     L.tpl_mirror_states.argtypes = [i64, vp, vp, vp, vp, vp, vp, vp]
+    L.tpl_afterstates.argtypes = [vp, vp, i64, i32, i32, C.c_float, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, vp]
+    L.tpl_canonical_action.restype = i32
+    L.tpl_canonical_action.argtypes = [i32, i32]
     for name in ("tpl_replay_push", "tpl_replay_sample", "tpl_learn_pack", "tpl_priority_init", "tpl_priority_push",
                  "tpl_priority_update", "tpl_replay_sample_prioritized", "tpl_replay_sample_nstep", "tpl_replay_sample_mirror",
-                 "tpl_mirror_states"):
+                 "tpl_mirror_states", "tpl_afterstates"):
         getattr(L, name).restype = i32
     _handle = L
     return L
@@ -376,6 +379,23 @@ def mirror_actions(action, a, b) -> np.ndarray:
 def mirror_coins(seed: int, update: int, batch: int) -> np.ndarray:
     """Which draws of a minibatch mode 1 mirrors (uint8 [batch]): bit 0 of h_i, the hash word replay_indices maps."""
     return (_draw_hashes(seed, update, batch) & np.uint64(1)).astype(np.uint8)
+
+
+# ------------------------------------------------------------------------------------------------ afterstates
+# The canonical-action rule of include/tpl_learn.h in numpy (the device's: csrc/learn/afterstates.hip).
+NUM_ACTIONS = 40
+PIECE_ROTATIONS = (2, 4, 4, 4, 2, 2, 1, 1)               # nrot: `rotations % len` of each piece id; 7 ("none") reads O's entry
+
+
+def canonical_actions(cur, action) -> np.ndarray:
+    """canonical[a] = 10 (r mod nrot(cur)) + min(l, 10 - w(cur, r)) for a = 10 r + l in 0..39 and current piece cur in 0..7
+    (broadcast against each other; uint8).  Two actions with one canonical value are the same placement."""
+    cur, act = np.broadcast_arrays(np.asarray(cur, dtype=np.int64), np.asarray(action, dtype=np.int64))
+    if cur.size and (cur.min() < 0 or cur.max() > 7 or act.min() < 0 or act.max() >= NUM_ACTIONS):
+        raise ValueError("cur must be in 0..7 and action in 0..39")
+    r, l = act // 10, act % 10
+    w = shape_widths()[cur, r]
+    return (10 * (r % np.array(PIECE_ROTATIONS)[cur]) + np.minimum(l, 10 - w)).astype(np.uint8)
 
 
 # ------------------------------------------------------------------------------------------------ device packing

@@ -1,0 +1,142 @@
+// afterstates.hip -- the 40 successors of a board: tpl_afterstates, tpl_canonical_action (include/tpl_learn.h states the rule).
+//
+// The environment answers "what if every board plays action a" by stepping its resident state; a learner that scores the
+// placements of the current piece wants all 40 answers for one position.  This unit produces them without touching the
+// position: for board i and action a = 10 r + l, pair (i, a) at index 40 i + a gets the 32-byte afterstate, the reward, done,
+// the rows cleared and the canonical alias of a -- tpl_device.h's own unpack_board / move_board / next_window / pack_board, so
+// an afterstate is what a non-auto-reset step leaves, up to window entries 2..11 on the refill move.
+//
+// Lane mapping: one lane per PAIR, lane j of the grid = pair j.  Every output is then one contiguous stream: a wave writes 1 KiB
+// of each state plane with 16-byte stores, 256 B of rewards and 64 B of each byte array, all consecutive.  The read side is 32 B
+// per board, taken by all 40 lanes of the board: a wave holds 1.6 boards, so its two 16-byte loads touch at most three boards
+// (one or two 128-byte lines per plane) and the 40-fold reuse is served by the load unit, not by memory.  The other mapping,
+// a lane per board looping over 40 actions, would take the ten column tops once per board instead of once per pair, but its
+// stores are 640 B apart per lane (16 B per lane per row, 64 rows per wave store): the write side is 98 % of the traffic
+// (1,560 B out against 32 B in), so it decides.  Per board: 32 B read, 40 x (32 + 4 + 1 + 1 + 1) = 1,560 B written.
+#include "tpl_learn_internal.h"
+#include "tpl_mirror.h"
+
+namespace tpl_learn {
+namespace {
+
+constexpr int kAfterBlock = 256;
+constexpr int kActions = TPL_NUM_ACTIONS;
+
+// rotations % len of get_tetromino as r & (len - 1): len - 1 of piece p at bits 2p, 2p + 1 (len = [2, 4, 4, 4, 2, 2, 1, 1])
+constexpr int kRotations[8] = TPL_PIECE_ROTATIONS;
+constexpr uint32_t packed_rotation_masks() {
+    uint32_t v = 0;
+    for (int p = 0; p < 8; ++p) v |= (uint32_t)(kRotations[p] - 1) << (2 * p);
+    return v;
+}
+constexpr uint32_t kRotationMasks = packed_rotation_masks();
+
+// the shape table holds entry [p][r % len] at [p][r] for every r: the canonical rotation names the same entry
+constexpr bool table_repeats_with_the_rotation_count() {
+    for (int p = 0; p < 8; ++p)
+        for (int r = 0; r < 4; ++r) {
+            const tpl::ShapeWord a = tpl::kShapeTableHost[p * 4 + r], b = tpl::kShapeTableHost[p * 4 + (r & (kRotations[p] - 1))];
+            if (a.x != b.x || a.y != b.y) return false;
+        }
+    return true;
+}
+static_assert(table_repeats_with_the_rotation_count(), "kRotations does not match the shape table");
+
+// canonical[a] = 10 (r mod nrot(cur)) + min(l, 10 - w(cur, r)) for a = 10 r + l, r < 4, l < 10
+__host__ __device__ __forceinline__ uint32_t canonical_action(uint32_t cur, uint32_t r, uint32_t l) {
+    const uint32_t right = 9u - ((uint32_t)(kWidthsLess1 >> (2u * (cur * 4u + r))) & 3u);      // 10 - w
+    const uint32_t rc = r & ((kRotationMasks >> (2u * cur)) & 3u);
+    return 10u * rc + (l < right ? l : right);
+}
+
+struct AfterArgs {
+    const uint4* a;              // [n]
+    const uint4* b;
+    uint32_t total;              // 40 n, below 2^31
+    uint32_t L, M;
+    float r_line, r_win, r_lose;
+    uint4* out_a;                // [n][40], with out_b or not at all
+    uint4* out_b;
+    float* reward;               // [n][40], each optional
+    uint8_t* done;
+    uint8_t* cleared;
+    uint8_t* canonical;
+};
+
+// step_reward's rule (csrc/tpl_step.h): one rounded multiply, then at most one rounded add; contraction off, or the pair
+// becomes an FMA whose single rounding differs where r_line * n is not exact
+__device__ __forceinline__ float afterstate_reward(const AfterArgs& p, uint32_t n_clear, uint32_t state) {
+#pragma clang fp contract(off)
+    float reward = p.r_line * (float)n_clear;
+    if (state == tpl::ST_WON) reward = reward + p.r_win;
+    if (state >= tpl::ST_LOST_LIMIT) reward = reward + p.r_lose;
+    return reward;
+}
+
+__global__ __launch_bounds__(kAfterBlock) void afterstates_kernel(const AfterArgs p) {
+    __shared__ tpl::ShapeWord s_shape[32];
+    if (threadIdx.x < 32) s_shape[threadIdx.x] = tpl::kShapeTable[threadIdx.x];
+    __syncthreads();
+    const uint32_t j = blockIdx.x * kAfterBlock + threadIdx.x;          // pair 40 i + a
+    if (j >= p.total) return;
+    const uint32_t i = j / kActions, a = j - i * kActions;
+    const uint32_t r = a / 10u, l = a - r * 10u;                        // values, never indices: move_board selects on them
+    const uint4 A = p.a[i], B = p.b[i];
+    tpl::Board s;
+    tpl::unpack_board(A, B, s);
+    const uint32_t cur = s.window & 7u;
+    const bool running = s.state == tpl::ST_RUNNING;
+
+    bool topout;
+    const uint32_t n_clear = tpl::move_board(s, s_shape, r, l, p.L, p.M, topout);
+    tpl::next_window(s, false, 0);                                      // pieces.pop(0) without a refill: zeros enter
+    const float reward = afterstate_reward(p, n_clear, s.state);
+
+    // a finished board stays as it is, bit for bit, with reward 0, done 1, cleared 0 (a frozen board of tpl_step): selects
+    if (p.out_a) {
+        uint4 A2, B2;
+        tpl::pack_board(s, A2, B2);
+        B2.y |= B.y & 0x80000000u;                                      // the spare bit (the slot travels in the Board)
+        p.out_a[j] = make_uint4(running ? A2.x : A.x, running ? A2.y : A.y, running ? A2.z : A.z, running ? A2.w : A.w);
+        p.out_b[j] = make_uint4(running ? B2.x : B.x, running ? B2.y : B.y, running ? B2.z : B.z, running ? B2.w : B.w);
+    }
+    if (p.reward) p.reward[j] = running ? reward : 0.0f;
+    if (p.done) p.done[j] = (uint8_t)(running ? (s.state != tpl::ST_RUNNING ? 1u : 0u) : 1u);
+    if (p.cleared) p.cleared[j] = (uint8_t)(running ? n_clear : 0u);
+    if (p.canonical) p.canonical[j] = (uint8_t)canonical_action(cur, r, l);
+}
+
+}  // namespace
+}  // namespace tpl_learn
+
+using namespace tpl_learn;
+
+extern "C" int32_t tpl_canonical_action(int32_t cur, int32_t action) {
+    if (cur < 0 || cur > 7 || action < 0 || action >= kActions) return -1;
+    return (int32_t)canonical_action((uint32_t)cur, (uint32_t)action / 10u, (uint32_t)action % 10u);
+}
+
+extern "C" int tpl_afterstates(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line,
+                               float r_win, float r_lose, void* out_a, void* out_b, float* reward, uint8_t* done,
+                               uint8_t* cleared, uint8_t* canonical, void* stream) {
+    if (!plane_a || !plane_b) return fail_msg(TPL_ERR_ARG, "tpl_afterstates: null pointer");
+    if ((out_a == nullptr) != (out_b == nullptr)) return fail_msg(TPL_ERR_ARG, "tpl_afterstates: out_a and out_b go together");
+    if (!out_a && !reward && !done && !cleared && !canonical)
+        return fail_msg(TPL_ERR_ARG, "tpl_afterstates: at least one output must be given");
+    if (n < 1) return fail_msg(TPL_ERR_ARG, "tpl_afterstates: n must be positive");
+    if (n >= (((int64_t)1 << 31) + kActions - 1) / kActions)
+        return fail_msg(TPL_ERR_ARG, "tpl_afterstates: n too large (40 n must stay below 2^31)");
+    if (L < 1 || L > 255 || M < 1 || M > 255) return fail_msg(TPL_ERR_ARG, "tpl_afterstates: L and M must be in [1, 255]");
+    if (((uintptr_t)plane_a & 15u) || ((uintptr_t)plane_b & 15u) || ((uintptr_t)out_a & 15u) || ((uintptr_t)out_b & 15u))
+        return fail_msg(TPL_ERR_ARG, "tpl_afterstates: planes must be 16-byte aligned");
+    if ((uintptr_t)reward & 3u) return fail_msg(TPL_ERR_ARG, "tpl_afterstates: reward must be 4-byte aligned");
+    AfterArgs p{};
+    p.a = (const uint4*)plane_a; p.b = (const uint4*)plane_b; p.total = (uint32_t)(n * kActions);
+    p.L = (uint32_t)L; p.M = (uint32_t)M; p.r_line = r_line; p.r_win = r_win; p.r_lose = r_lose;
+    p.out_a = (uint4*)out_a; p.out_b = (uint4*)out_b;
+    p.reward = reward; p.done = done; p.cleared = cleared; p.canonical = canonical;
+    const dim3 grid((p.total + kAfterBlock - 1) / kAfterBlock), block(kAfterBlock);
+    hipLaunchKernelGGL(afterstates_kernel, grid, block, 0, (hipStream_t)stream, p);
+    TPL_LEARN_HIP(hipGetLastError());
+    return TPL_OK;
+}

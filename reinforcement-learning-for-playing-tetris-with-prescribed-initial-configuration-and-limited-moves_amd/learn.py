@@ -343,7 +343,8 @@ class DQNLearner(metaclass=_TakesNStep):
 
     collect(steps)   one actor_rollout of the online net's split image at the scheduled epsilon, pushed into the ring
     update(n=1)      n minibatch updates (sample -> Q(s) in torch, Q'(s') on the split kernel -> Huber -> AdamW -> soft update)
-    evaluate(steps)  the greedy policy (epsilon 0) on a separate environment over the same pool: episodes, wins, win rate
+    evaluate(steps)  the greedy policy (epsilon 0) on a separate environment over the same pool: episodes, wins, win rate;
+                     lookahead=True plays the one-ply lookahead on the online net instead
     """
 
     def __init__(self, env: BatchedTetris, model: Optional[nn.Module] = None, capacity: int = 1 << 20, batch_size: int = 128,
@@ -473,9 +474,15 @@ class DQNLearner(metaclass=_TakesNStep):
         pack_policy_device(_learn_lib.policy_tensors(self.target), "split", out=self.target_image)
 
     # ------------------------------------------------------------------------------------------ evaluation
-    def evaluate(self, steps: int, epsilon: float = 0.0) -> dict:
+    def evaluate(self, steps: int, epsilon: float = 0.0, lookahead: bool = False) -> dict:
         """`steps` iterations of the online net's policy (greedy by default) on a separate auto-reset environment with the
-        learner env's size, L, M and configuration pool, from a full reset.  Returns episodes finished, wins, win rate."""
+        learner env's size, L, M and configuration pool, from a full reset.  Returns episodes finished, wins, win rate.
+
+        lookahead=True plays the one-ply lookahead on the online net instead of its factored arg-max (lookahead.LookaheadPolicy
+        at the learner's gamma: every distinct placement scored as reward + gamma * (1 - done) * max Q(afterstate)), one step
+        per iteration; it is deterministic, so it takes no epsilon."""
+        if lookahead and epsilon != 0:
+            raise ValueError("evaluate(lookahead=True) is greedy: epsilon must be 0")
         env = self.env
         if env._pool is None:
             raise ValueError("the learner's environment has no configuration pool to evaluate on")
@@ -488,6 +495,18 @@ class DQNLearner(metaclass=_TakesNStep):
             self._eval_pool = env._pool
         ev.reset()
         image = pack_policy_device(_learn_lib.policy_tensors(self.model), "split")
-        ev.actor_rollout(image, int(steps), epsilon=float(epsilon), seed=self.seed + 1, record=False)
+        if lookahead:
+            from .lookahead import LookaheadPolicy
+            policy = getattr(self, "_lookahead", None)
+            if policy is None:
+                policy = self._lookahead = LookaheadPolicy(ev, image, gamma=self.gamma)
+            policy.image = image
+            action = torch.empty(ev.num_envs, dtype=torch.uint8, device=self.device)
+            reward = torch.empty(ev.num_envs, dtype=torch.float32, device=self.device)
+            done = torch.empty(ev.num_envs, dtype=torch.uint8, device=self.device)
+            for _ in range(int(steps)):
+                ev.step_into(policy.act(out=action), reward, done)
+        else:
+            ev.actor_rollout(image, int(steps), epsilon=float(epsilon), seed=self.seed + 1, record=False)
         st = ev.stats()
         return dict(episodes=st["episodes"], wins=st["wins"], win_rate=st["wins"] / max(st["episodes"], 1))

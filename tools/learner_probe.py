@@ -20,6 +20,11 @@ Parts:
     mirror    mirror symmetry: tpl_replay_sample_mirror in modes 0 (never), 1 (the coin) and 2 (always) against the existing entry
               of each form -- uniform, prioritized and uniform n = 3 -- at 2^20 draws, float32 obs, a 2^22 ring, every variant
               timed in each of five alternating rounds; the loop's win rate and wall time with mirror=False and mirror=True
+    afterstates  tpl_afterstates at 2^16, 2^18 and 2^20 boards (L=10 / M=40, mid-game), the full form and the form without state
+              planes, alternated over five rounds: each time as a fraction of 6.3 TB/s over its bytes (32 in, 1,560 or 280 out per
+              board) and against the VALU-issue yardstick (the kernel's static vector instructions per wave at 3.3 cycles each on
+              1,024 SIMDs at 2.4 GHz); the loop's win rate under evaluate(lookahead=True) next to the greedy one, and one
+              LookaheadPolicy.act() at 262,144 boards
 """
 import argparse
 import json
@@ -32,7 +37,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 HBM_ACHIEVABLE = 6.3e12
-PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600, "priority": 600, "nstep": 600, "mirror": 600}
+PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600, "priority": 600, "nstep": 600, "mirror": 600, "afterstates": 600}
+VALU_CYCLES, SIMDS, CLOCK_HZ = 3.3, 1024, 2.4e9           # the move's instruction mix, 256 CUs x 4, the clock
 
 
 def _timed(fn, reps, warmup=3):
@@ -118,7 +124,7 @@ def part_update():
     return dict(part="update", rows=rows)
 
 
-def part_loop(prioritized=False, n_step=1, mirror=False):
+def part_loop(prioritized=False, n_step=1, mirror=False, lookahead=False):
     import torch
     import tetris_piclim as T
     n, rounds, per = 262144, 300, 4
@@ -143,10 +149,21 @@ def part_loop(prioritized=False, n_step=1, mirror=False):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     after = learner.evaluate(8)
-    return dict(part="loop", boards=n, rounds=rounds, updates_per_round=per, batch=1024, seconds=round(dt, 2),
-                transitions_per_s=round(rounds * n / dt), updates_per_s=round(rounds * per / dt, 1), elapsed_at=curve,
-                win_rate_random=round(random_rate, 4), win_rate_greedy_before=round(before, 4),
-                win_rate_greedy_after=round(after["win_rate"], 4), eval_episodes=after["episodes"])
+    out = dict(part="loop", boards=n, rounds=rounds, updates_per_round=per, batch=1024, seconds=round(dt, 2),
+               transitions_per_s=round(rounds * n / dt), updates_per_s=round(rounds * per / dt, 1), elapsed_at=curve,
+               win_rate_random=round(random_rate, 4), win_rate_greedy_before=round(before, 4),
+               win_rate_greedy_after=round(after["win_rate"], 4), eval_episodes=after["episodes"])
+    if lookahead:
+        look = learner.evaluate(8, lookahead=True)
+        policy = learner._lookahead
+        action = torch.empty(n, dtype=torch.uint8, device="cuda:0")
+        t_act = _timed(lambda: policy.act(out=action), 5, warmup=1)
+        bare = T.LookaheadPolicy(learner.eval_env, image=None)
+        t_bare = _timed(lambda: bare.act(out=action), 5, warmup=1)
+        out.update(win_rate_lookahead_after=round(look["win_rate"], 4), lookahead_eval_episodes=look["episodes"],
+                   lookahead_act_ms=round(t_act * 1e3, 3), lookahead_act_without_network_ms=round(t_bare * 1e3, 3),
+                   lookahead_chunk=policy.chunk)
+    return out
 
 
 def _update_rate(batch, prioritized, reps=200, n_step=1):
@@ -369,6 +386,64 @@ def part_mirror(rounds=5):
         loops.append(loop)
         torch.cuda.empty_cache()
     out["loops"] = loops
+    return out
+
+
+def _static_valu(kernel, lib_path):
+    """Vector ALU instructions in the kernel's code as built (tools/dump_isa.sh): every path once, loop bodies included."""
+    res = subprocess.run(["bash", os.path.join(ROOT, "tools", "dump_isa.sh"), kernel, lib_path], capture_output=True, text=True,
+                         cwd=ROOT, timeout=120)
+    return sum(1 for l in res.stdout.splitlines() if l.split()[:1] and l.split()[0].startswith("v_"))
+
+
+def part_afterstates(rounds=5):
+    import ctypes as C
+    import torch
+    import tetris_piclim as T
+    L = T._learn_lib.lib()
+    check = T._learn_lib.check
+    stream = torch._C._cuda_getCurrentRawStream(0)
+    valu = _static_valu("afterstates_kernel", T._learn_lib.build_library())
+    out = dict(part="afterstates", static_valu_per_wave=valu, valu_cycles=VALU_CYCLES, streaming_tb_per_s=HBM_ACHIEVABLE / 1e12)
+    rows = []
+    for n in (1 << 16, 1 << 18, 1 << 20):
+        env = T.BatchedTetris(10, 40, n, device="cuda:0", seed=1, auto_reset=True)
+        env.load_configs(*env.synthetic_configs(4096))
+        env.reset()
+        for t in range(6):                                       # mid-game boards
+            env.step(env.synthetic_actions(t), observe=False)
+        pa, pb = C.c_void_p(), C.c_void_p()
+        T._lib.check(env._lib.tpl_state_ptrs(env._h, C.byref(pa), C.byref(pb)))
+        sa = torch.empty((n, 40, 4), dtype=torch.int32, device="cuda:0")
+        sb = torch.empty((n, 40, 4), dtype=torch.int32, device="cuda:0")
+        reward = torch.empty((n, 40), dtype=torch.float32, device="cuda:0")
+        done, cleared, canonical = (torch.empty((n, 40), dtype=torch.uint8, device="cuda:0") for _ in range(3))
+
+        def launch(planes):
+            check(L.tpl_afterstates(pa.value, pb.value, n, 10, 40, 1.0, 0.0, 0.0, sa.data_ptr() if planes else None,
+                                    sb.data_ptr() if planes else None, reward.data_ptr(), done.data_ptr(), cleared.data_ptr(),
+                                    canonical.data_ptr(), stream))
+        variants = [("full", lambda: launch(True), 32 + 40 * 39), ("no_planes", lambda: launch(False), 32 + 40 * 7)]
+        times = {name: [] for name, _, _ in variants}
+        for _ in range(rounds):                                  # alternate the two forms round by round
+            for name, fn, _ in variants:
+                times[name].append(_timed(fn, 20))
+        t_valu = (n * 40 / 64) * valu * VALU_CYCLES / SIMDS / CLOCK_HZ
+        row = dict(boards=n, valu_yardstick_us=round(t_valu * 1e6, 2))
+        for name, _, nbytes in variants:
+            t = sorted(times[name])[rounds // 2]
+            t_mem = n * nbytes / HBM_ACHIEVABLE
+            row[name] = dict(us=_spread(times[name]), bytes_per_board=nbytes, tb_per_s=round(n * nbytes / t / 1e12, 3),
+                             of_streaming=round(t_mem / t, 3), of_valu_yardstick=round(t_valu / t, 3),
+                             bound="memory" if t_mem >= t_valu else "valu-issue")
+        rows.append(row)
+        env.terminate()
+        del sa, sb
+        torch.cuda.empty_cache()
+    out["kernel"] = dict(rounds=rounds, launches_per_timing=20, rows=rows)
+    loop = part_loop(lookahead=True)
+    loop["part"] = "loop_lookahead"
+    out["loop"] = loop
     return out
 
 
