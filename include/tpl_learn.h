@@ -1,7 +1,8 @@
 /*
  * tpl_learn.h -- C ABI of the learner library (libtpl_learn.so): a packed replay ring on the device, its samplers (uniform,
  * prioritized, n-step, each optionally mirrored), device-side packing of a PolicyMLP's parameters into the three policy
- * images of libtetris_piclim.so, and the enumeration of a board's 40 afterstates.
+ * images of libtetris_piclim.so, the enumeration of a board's 40 afterstates, and board features of every placement with a
+ * linear placement policy on them.
  *
  * Conventions (as include/tetris_piclim.h)
  *   - every function returns 0 on success or a negative tpl_status (TPL_ERR_ARG, TPL_ERR_HIP, ...);
@@ -208,6 +209,56 @@ int tpl_afterstates(const void* plane_a, const void* plane_b, int64_t n, int32_t
 
 /* canonical[action] for current piece `cur` (0..7) on the host, for tests; -1 if cur or action (0..39) is out of range. */
 int32_t tpl_canonical_action(int32_t cur, int32_t action);
+
+/* Placement features and a linear placement policy on them (csrc/learn/heuristic.hip).
+ *
+ * phi(s, a), for a 32-byte state s and action a = 10 r + l, is TPL_NUM_FEATURES = 12 small non-negative integers.  Finished board
+ * (state(s) != running): all twelve are 0.  Running board: move_board(s, shape, r, l, L, M, topout) exactly as tpl_afterstates
+ * makes it (a top-out leaves the board as it was); n = the rows cleared, state' the new state, c_x the column words afterwards
+ * (bit r = row r, row 0 = top).  "Filled" and "empty" speak of this board after the clear;
+ * h_x = 20 - (row of the top-most filled cell of column x), 0 for an empty column.
+ *    0 cleared             n (0..4)
+ *    1 won                 1 if state' = won
+ *    2 lost                1 if state' = lost at the limit or topped out
+ *    3 holes               empty cells with at least one filled cell above them in their column
+ *    4 aggregate_height    sum_x h_x
+ *    5 max_height          max_x h_x
+ *    6 bumpiness           sum_{x = 0..8} |h_x - h_{x+1}|
+ *    7 row_transitions     each of the 20 rows read wall, x = 0..9, wall with the walls filled: adjacent pairs of different
+ *                          occupancy (an empty row gives 2)
+ *    8 column_transitions  per column the adjacent pairs (row r, row r + 1), r = 0..18, of different occupancy, plus 1 if row 19
+ *                          is empty (the floor is filled; nothing is counted above row 0)
+ *    9 wells               sum_x d_x (d_x + 1) / 2, d_x = max(0, min(h_{x-1}, h_{x+1}) - h_x) with h_{-1} = h_10 = 20
+ *   10 rows_with_holes     rows that contain at least one hole
+ *   11 hole_depth          over the columns that have a hole: the filled cells of the column above its top-most hole
+ * Every value fits an int16.  Landing height and eroded cells are left out on purpose: both need the drop distance, which
+ * move_board keeps to itself.
+ *
+ * Score: with weights w[12] (float32), score = w_0 phi_0 + w_1 phi_1 + ... + w_11 phi_11 from left to right in float32: every
+ * phi_f converts exactly, every product and every sum is rounded once, never fused (afterstate_reward's discipline).
+ * Choice: the arg-max of the score over the distinct placements (a == canonical[a]), the lowest a on ties (-0 and +0 tie).  A
+ * finished board so gets action 0 and the score of twelve zeros.  THE WEIGHTS MUST BE FINITE (device memory cannot be checked
+ * here), and of a size that no score overflows: the choice among scores that are not numbers is unspecified, though it is still
+ * one distinct placement per board.
+ * Population: board i uses weight row i / boards_per_member of a [P][12] array, P = ceil(n / boards_per_member); the last member
+ * may be short; boards_per_member >= n is the single-policy case.
+ * With w = (r_line, r_win, r_lose, 0, ..., 0) the score is tpl_afterstates' reward (adding a zero changes no value, and at most
+ * one of won / lost is set), bit for bit wherever that reward is not -0: the choice is the best immediate reward's. */
+#define TPL_NUM_FEATURES 12
+
+/* phi of all 40 actions of each of `n` states: plane_a / plane_b [n] 16-byte words (read only) -> features i16 [n][40][12], one
+ * contiguous 24-byte record per pair (8-byte aligned, written with 8-byte stores), and canonical u8 [n][40] (optional, as
+ * tpl_afterstates').  Refused before any HIP call: n < 1, 40 n >= 2^31, a NULL or misaligned (16 bytes) plane pointer, features
+ * NULL or not 8-byte aligned, L or M outside [1, 255]. */
+int tpl_placement_features(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, int16_t* features,
+                           uint8_t* canonical, void* stream);
+
+/* The chosen action of each of `n` states in one kernel (features, score and arg-max stay in registers and LDS: 32 bytes read
+ * and 1 or 5 written per board): weights f32 [P][12] (16-byte aligned), action u8 [n], score f32 [n] (optional: the chosen
+ * action's score).  Refused before any HIP call: tpl_placement_features' plane, n, L and M checks, weights or action NULL,
+ * boards_per_member < 1, weights not 16-byte or score not 4-byte aligned. */
+int tpl_placement_act(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const float* weights,
+                      int64_t boards_per_member, uint8_t* action, float* score, void* stream);
 
 #ifdef __cplusplus
 }

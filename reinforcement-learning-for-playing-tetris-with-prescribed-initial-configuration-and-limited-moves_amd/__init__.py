@@ -12,7 +12,8 @@ from ._lib import (LIB_PATH, SYMBOLS, TplError, build_library, carve, forward_ge
 
 __all__ = ["BatchedTetris", "Tetris", "Snapshot", "OBS_DIM", "NUM_ACTIONS", "RUNNING", "WON", "LOST", "TplError",
            "RandomPieceGenerator", "get_tetromino", "piece_translations", "translate", "carve", "build_library", "shape_info", "generate_configs", "forward_generate", "pack_policy", "LIB_PATH", "SYMBOLS", "DQNLearner",
-           "ReplayRing", "PrioritizedReplayRing", "LookaheadPolicy", "afterstates"]
+           "ReplayRing", "PrioritizedReplayRing", "LookaheadPolicy", "afterstates", "HeuristicPolicy", "placement_features",
+           "evaluate_heuristic", "tune_heuristic"]
 
 
 def __getattr__(name):
@@ -34,6 +35,8 @@ def __getattr__(name):
         return getattr(importlib.import_module(__name__ + ".learn"), name)
     if name in ("LookaheadPolicy", "afterstates"):
         return getattr(importlib.import_module(__name__ + ".lookahead"), name)
-    if name in ("learn", "_learn_lib", "lookahead"):
+    if name in ("HeuristicPolicy", "placement_features", "evaluate_heuristic", "tune_heuristic"):
+        return getattr(importlib.import_module(__name__ + ".heuristic"), name)
+    if name in ("learn", "_learn_lib", "lookahead", "heuristic"):
         return importlib.import_module(__name__ + "." + name)
     raise AttributeError(name)

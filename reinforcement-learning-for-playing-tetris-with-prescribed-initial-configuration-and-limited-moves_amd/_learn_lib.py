@@ -20,14 +20,16 @@ from ._lib import TplError, _hipcc
 
 _LEARN_CSRC = os.path.join(_lib._CSRC, "learn")
 LEARN_LIB_PATH = os.path.join(_lib._LIBDIR, "libtpl_learn.so")
-_UNITS = [os.path.join(_LEARN_CSRC, f) for f in ("replay.hip", "pack.hip", "priority.hip", "afterstates.hip")]
+_UNITS = [os.path.join(_LEARN_CSRC, f) for f in ("replay.hip", "pack.hip", "priority.hip", "afterstates.hip",
+                                                      "heuristic.hip")]
 
 # entry points declared in include/tpl_learn.h (tests check that the .so exports every one of them)
 LEARN_SYMBOLS = [
     "tpl_learn_last_error", "tpl_replay_record_bytes", "tpl_replay_push", "tpl_replay_sample", "tpl_replay_index",
     "tpl_learn_image_bytes", "tpl_learn_pack", "tpl_priority_tree_bytes", "tpl_priority_init", "tpl_priority_push",
     "tpl_priority_update", "tpl_replay_sample_prioritized", "tpl_priority_target", "tpl_replay_sample_nstep",
-    "tpl_replay_sample_mirror", "tpl_mirror_states", "tpl_afterstates", "tpl_canonical_action",
+    "tpl_replay_sample_mirror", "tpl_mirror_states", "tpl_afterstates", "tpl_canonical_action", "tpl_placement_features",
+    "tpl_placement_act",
 ]
 NSTEP_MAX = 16
 MIRROR_MODES = {False: 0, True: 1, "always": 2}          # sample(mirror=...) -> tpl_mirror_mode
@@ -128,9 +130,11 @@ def lib() -> C.CDLL:
     L.tpl_afterstates.argtypes = [vp, vp, i64, i32, i32, C.c_float, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, vp]
     L.tpl_canonical_action.restype = i32
     L.tpl_canonical_action.argtypes = [i32, i32]
+    L.tpl_placement_features.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp]
+    L.tpl_placement_act.argtypes = [vp, vp, i64, i32, i32, vp, i64, vp, vp, vp]
     for name in ("tpl_replay_push", "tpl_replay_sample", "tpl_learn_pack", "tpl_priority_init", "tpl_priority_push",
                  "tpl_priority_update", "tpl_replay_sample_prioritized", "tpl_replay_sample_nstep", "tpl_replay_sample_mirror",
-                 "tpl_mirror_states", "tpl_afterstates"):
+                 "tpl_mirror_states", "tpl_afterstates", "tpl_placement_features", "tpl_placement_act"):
         getattr(L, name).restype = i32
     _handle = L
     return L
@@ -396,6 +400,58 @@ def canonical_actions(cur, action) -> np.ndarray:
     r, l = act // 10, act % 10
     w = shape_widths()[cur, r]
     return (10 * (r % np.array(PIECE_ROTATIONS)[cur]) + np.minimum(l, 10 - w)).astype(np.uint8)
+
+
+# ------------------------------------------------------------------------------------------------ placement features
+# The feature table of include/tpl_learn.h on the host, counted on the 20 x 10 array of 0 / 1 cells (the device works on column
+# words with ctz / popcount: csrc/learn/heuristic.hip -- the two share nothing), and the score rule.
+NUM_FEATURES = 12
+FEATURE_NAMES = ("cleared", "won", "lost", "holes", "aggregate_height", "max_height", "bumpiness", "row_transitions",
+                 "column_transitions", "wells", "rows_with_holes", "hole_depth")
+
+
+def board_features(rows) -> np.ndarray:
+    """Features 3..11 of boards given as row masks (uint16 [K, 20] or [20], bit x = column x, row 0 = top) -> int64 [K, 9]:
+    holes, aggregate_height, max_height, bumpiness, row_transitions, column_transitions, wells, rows_with_holes, hole_depth.
+    Every feature is counted on the 20 x 10 array of 0 / 1 cells as the table words it."""
+    rows = np.asarray(rows)
+    if rows.ndim == 1:
+        rows = rows[None]
+    if rows.ndim != 2 or rows.shape[1] != 20:
+        raise ValueError("rows must be [K, 20] row masks")
+    k = rows.shape[0]
+    cell = (rows.astype(np.int64)[:, :, None] // (2 ** np.arange(10))[None, None, :]) % 2          # [K, 20, 10], 1 = filled
+    above = np.cumsum(cell, axis=1) - cell                     # filled cells of the column strictly above each cell
+    hole = (cell == 0) & (above > 0)
+    occupied = cell.any(axis=1)
+    height = np.where(occupied, 20 - cell.argmax(axis=1), 0)   # argmax: the first (top-most) filled row
+    bump = np.abs(height[:, 1:] - height[:, :-1]).sum(axis=1)
+    wall = np.ones((k, 20, 1), dtype=np.int64)
+    line = np.concatenate([wall, cell, wall], axis=2)          # wall, x = 0..9, wall
+    row_trans = (line[:, :, 1:] != line[:, :, :-1]).sum(axis=(1, 2))
+    col_trans = (cell[:, 1:, :] != cell[:, :-1, :]).sum(axis=(1, 2)) + (cell[:, 19, :] == 0).sum(axis=1)
+    beside = np.concatenate([np.full((k, 1), 20), height, np.full((k, 1), 20)], axis=1)           # h_{-1} = h_10 = 20
+    d = np.maximum(0, np.minimum(beside[:, :-2], beside[:, 2:]) - height)
+    wells = (d * (d + 1) // 2).sum(axis=1)
+    first_hole = hole.argmax(axis=1)                           # the top-most hole of each column, where it has one
+    above_it = np.take_along_axis(above, first_hole[:, None, :], axis=1)[:, 0, :]
+    depth = np.where(hole.any(axis=1), above_it, 0).sum(axis=1)
+    return np.stack([hole.sum(axis=(1, 2)), height.sum(axis=1), height.max(axis=1), bump, row_trans, col_trans, wells,
+                     hole.any(axis=2).sum(axis=1), depth], axis=1).astype(np.int64)
+
+
+def placement_score(features, weights) -> np.ndarray:
+    """score = w_0 phi_0 + w_1 phi_1 + ... + w_11 phi_11 from left to right in float32, every product and every sum rounded
+    once (numpy float32 operations; nothing fused): features [..., 12] integers, weights [12] or broadcastable [..., 12]."""
+    f = np.asarray(features)
+    w = np.asarray(weights, dtype=np.float32)
+    if f.shape[-1] != NUM_FEATURES or w.shape[-1] != NUM_FEATURES:
+        raise ValueError("features and weights must end in 12")
+    f = f.astype(np.float32)                                  # exact: every feature is a small integer
+    s = w[..., 0] * f[..., 0]
+    for k in range(1, NUM_FEATURES):
+        s = s + w[..., k] * f[..., k]
+    return np.asarray(s, dtype=np.float32)
 
 
 # ------------------------------------------------------------------------------------------------ device packing

@@ -22,33 +22,6 @@ namespace {
 constexpr int kAfterBlock = 256;
 constexpr int kActions = TPL_NUM_ACTIONS;
 
-// rotations % len of get_tetromino as r & (len - 1): len - 1 of piece p at bits 2p, 2p + 1 (len = [2, 4, 4, 4, 2, 2, 1, 1])
-constexpr int kRotations[8] = TPL_PIECE_ROTATIONS;
-constexpr uint32_t packed_rotation_masks() {
-    uint32_t v = 0;
-    for (int p = 0; p < 8; ++p) v |= (uint32_t)(kRotations[p] - 1) << (2 * p);
-    return v;
-}
-constexpr uint32_t kRotationMasks = packed_rotation_masks();
-
-// the shape table holds entry [p][r % len] at [p][r] for every r: the canonical rotation names the same entry
-constexpr bool table_repeats_with_the_rotation_count() {
-    for (int p = 0; p < 8; ++p)
-        for (int r = 0; r < 4; ++r) {
-            const tpl::ShapeWord a = tpl::kShapeTableHost[p * 4 + r], b = tpl::kShapeTableHost[p * 4 + (r & (kRotations[p] - 1))];
-            if (a.x != b.x || a.y != b.y) return false;
-        }
-    return true;
-}
-static_assert(table_repeats_with_the_rotation_count(), "kRotations does not match the shape table");
-
-// canonical[a] = 10 (r mod nrot(cur)) + min(l, 10 - w(cur, r)) for a = 10 r + l, r < 4, l < 10
-__host__ __device__ __forceinline__ uint32_t canonical_action(uint32_t cur, uint32_t r, uint32_t l) {
-    const uint32_t right = 9u - ((uint32_t)(kWidthsLess1 >> (2u * (cur * 4u + r))) & 3u);      // 10 - w
-    const uint32_t rc = r & ((kRotationMasks >> (2u * cur)) & 3u);
-    return 10u * rc + (l < right ? l : right);
-}
-
 struct AfterArgs {
     const uint4* a;              // [n]
     const uint4* b;

@@ -1,0 +1,259 @@
+// heuristic.hip -- board features of every placement and a linear placement policy on them: tpl_placement_features,
+// tpl_placement_act (include/tpl_learn.h states the rule).
+//
+// The classical Tetris controller scores the board a placement leaves by a linear function of a few hand-made features and
+// plays the best one.  In the column layout every such feature is a few ctz / popcount / xor operations on the ten column
+// words that move_board leaves in registers, so features, score and arg-max are one kernel: 32 B read per board, one byte
+// (five with the best score) written, nothing in between goes to memory.
+//
+// Lane mapping: one lane per (board, action) PAIR, as afterstates.hip, in blocks of 320 threads = 8 boards x 40 actions (five
+// waves), so no board straddles a block and a board's arg-max is one LDS word.  The arg-max is a 64-bit LDS atomic maximum per
+// board on  key = order-preserving image of the float32 score << 32 | (39 - a) : the largest score wins, among equal scores
+// the lowest action; alias lanes (a != canonical[a]) do not take part.  The lane whose key comes back writes the board's
+// outputs.  A maximum is order independent, so the result is deterministic.  Thread t < 8 of a block fetches the weight row of
+// the block's board t into LDS (the one division by boards_per_member happens there, in eight lanes of 320); the pair lanes
+// read their board's row back with three 16-byte LDS reads, the 40 lanes of a board from one address.
+// The other mapping -- a lane per board looping over the 40 actions -- unpacks once per board and has no cross-lane step, but
+// the move and the features, which are nine tenths of a pair's instructions, are per pair either way; it diverges on
+// nrot(cur), and has a fortieth of the lanes (DESIGN.md section 9 has the instruction counts).
+// r and l are values, never register indices (move_board's comment says why).
+#include "tpl_learn_internal.h"
+#include "tpl_mirror.h"
+
+namespace tpl_learn {
+namespace {
+
+constexpr int kActions = TPL_NUM_ACTIONS;
+constexpr int kFeatures = TPL_NUM_FEATURES;
+constexpr int kBoardsPerBlock = 8;
+constexpr int kActBlock = kBoardsPerBlock * kActions;        // 320 threads: five waves, eight whole boards
+constexpr int kFeatureBlock = 256;
+static_assert(kActBlock % 64 == 0, "a block is whole waves");
+
+struct Features { uint32_t f[kFeatures]; };
+
+// popcount(x) + acc: v_bcnt_u32_b32 adds its second operand
+__device__ __forceinline__ uint32_t bcnt(uint32_t x, uint32_t acc) { return (uint32_t)__builtin_popcount(x) + acc; }
+__device__ __forceinline__ uint32_t absdiff(uint32_t a, uint32_t b) { return max(a, b) - min(a, b); }
+
+// features 3..11 of a board given as its ten column words (bit r = row r, row 0 = top; bits 20.. clear)
+__device__ __forceinline__ void board_features(const uint32_t (&c)[tpl::kCols], Features& out) {
+    constexpr uint32_t kFloor = tpl::kSentinelBit;            // row 20: the floor, filled
+    uint32_t t[tpl::kCols];                                   // top of column x: row of its top-most filled cell, 20 if empty
+#pragma unroll
+    for (int x = 0; x < tpl::kCols; ++x) t[x] = (uint32_t)__builtin_ctz(c[x] | kFloor);
+
+    uint32_t top_sum = 0, top_min = tpl::kRows, filled = 0;
+    uint32_t col_trans = 0, hole_rows = 0, depth = 0;
+#pragma unroll
+    for (int x = 0; x < tpl::kCols; ++x) {
+        top_sum += t[x];
+        top_min = min(top_min, t[x]);
+        filled = bcnt(c[x], filled);
+        // rows r = 0..19 against r + 1 with the floor as row 20: pairs (r, r + 1), r < 19, and the floor term
+        const uint32_t cf = c[x] | kFloor;
+        col_trans = bcnt((cf ^ (cf >> 1)) & tpl::kColMask, col_trans);
+        // holes of the column: the empty cells below its top
+        hole_rows |= ~c[x] & (tpl::kColMask >> t[x] << t[x]);
+        // the run of filled cells from the top down; it ends at the column's top-most hole unless it reaches the floor
+        const uint32_t run = (uint32_t)__builtin_ctz(~(c[x] >> t[x]));
+        depth += t[x] + run < (uint32_t)tpl::kRows ? run : 0u;
+    }
+    const uint32_t height_sum = tpl::kRows * tpl::kCols - top_sum;
+
+    uint32_t bump = 0;
+#pragma unroll
+    for (int x = 0; x + 1 < tpl::kCols; ++x) bump += absdiff(t[x], t[x + 1]);
+
+    // per row: wall | x = 0..9 | wall, the walls filled
+    uint32_t row_trans = bcnt(~c[0] & tpl::kColMask, 0);
+#pragma unroll
+    for (int x = 0; x + 1 < tpl::kCols; ++x) row_trans = bcnt(c[x] ^ c[x + 1], row_trans);
+    row_trans = bcnt(~c[tpl::kCols - 1] & tpl::kColMask, row_trans);
+
+    // d_x = max(0, min(h_{x-1}, h_{x+1}) - h_x) = max(0, t_x - max(t_{x-1}, t_{x+1})), t = 0 beyond the walls (h = 20)
+    uint32_t wells = 0;
+#pragma unroll
+    for (int x = 0; x < tpl::kCols; ++x) {
+        const uint32_t left = x > 0 ? t[x - 1] : 0u, right = x + 1 < tpl::kCols ? t[x + 1] : 0u;
+        const uint32_t side = max(left, right);
+        const uint32_t d = t[x] > side ? t[x] - side : 0u;
+        wells += __umul24(d, d + 1u) >> 1;
+    }
+
+    out.f[3] = height_sum - filled;                            // holes: the cells below the tops that are not filled
+    out.f[4] = height_sum;
+    out.f[5] = tpl::kRows - top_min;
+    out.f[6] = bump;
+    out.f[7] = row_trans;
+    out.f[8] = col_trans;
+    out.f[9] = wells;
+    out.f[10] = (uint32_t)__builtin_popcount(hole_rows);
+    out.f[11] = depth;
+}
+
+// phi(s, a) of pair (i, a): the twelve features of what action a = 10 r + l leaves of state (A, B); all zero for a finished board
+__device__ __forceinline__ void pair_features(const uint4& A, const uint4& B, const tpl::ShapeWord* shape, uint32_t r, uint32_t l,
+                                              uint32_t L, uint32_t M, Features& out, uint32_t& cur) {
+    tpl::Board s;
+    tpl::unpack_board(A, B, s);
+    cur = s.window & 7u;
+    const bool running = s.state == tpl::ST_RUNNING;
+    bool topout;
+    const uint32_t n_clear = tpl::move_board(s, shape, r, l, L, M, topout);
+    board_features(s.c, out);
+    out.f[0] = n_clear;
+    out.f[1] = s.state == tpl::ST_WON ? 1u : 0u;
+    out.f[2] = s.state >= tpl::ST_LOST_LIMIT ? 1u : 0u;
+#pragma unroll
+    for (int k = 0; k < kFeatures; ++k) out.f[k] = running ? out.f[k] : 0u;
+}
+
+struct FeatureArgs {
+    const uint4* a;              // [n]
+    const uint4* b;
+    uint32_t total;              // 40 n, below 2^31
+    uint32_t L, M;
+    uint2* features;             // [n][40] records of 24 bytes = three 8-byte words
+    uint8_t* canonical;          // [n][40], optional
+};
+
+__global__ __launch_bounds__(kFeatureBlock) void placement_features_kernel(const FeatureArgs p) {
+    __shared__ tpl::ShapeWord s_shape[32];
+    if (threadIdx.x < 32) s_shape[threadIdx.x] = tpl::kShapeTable[threadIdx.x];
+    __syncthreads();
+    const uint32_t j = blockIdx.x * kFeatureBlock + threadIdx.x;        // pair 40 i + a
+    if (j >= p.total) return;
+    const uint32_t i = j / kActions, a = j - i * kActions;
+    const uint32_t r = a / 10u, l = a - r * 10u;
+    Features phi;
+    uint32_t cur;
+    pair_features(p.a[i], p.b[i], s_shape, r, l, p.L, p.M, phi, cur);
+    uint2* rec = p.features + 3u * (size_t)j;
+    rec[0] = make_uint2(phi.f[0] | (phi.f[1] << 16), phi.f[2] | (phi.f[3] << 16));
+    rec[1] = make_uint2(phi.f[4] | (phi.f[5] << 16), phi.f[6] | (phi.f[7] << 16));
+    rec[2] = make_uint2(phi.f[8] | (phi.f[9] << 16), phi.f[10] | (phi.f[11] << 16));
+    if (p.canonical) p.canonical[j] = (uint8_t)canonical_action(cur, r, l);
+}
+
+struct ActArgs {
+    const uint4* a;              // [n]
+    const uint4* b;
+    uint32_t n;                  // boards; 40 n below 2^31
+    uint32_t L, M;
+    const float* weights;        // [P][12], P = ceil(n / per_member)
+    uint32_t per_member;         // boards per weight row, in [1, n]
+    uint8_t* action;             // [n]
+    float* score;                // [n], optional
+};
+
+// w . phi left to right in float32: every product and every sum rounded once -- contraction off, as afterstate_reward
+__device__ __forceinline__ float placement_score(const float (&w)[kFeatures], const Features& phi) {
+#pragma clang fp contract(off)
+    float s = w[0] * (float)phi.f[0];
+#pragma unroll
+    for (int k = 1; k < kFeatures; ++k) s = s + w[k] * (float)phi.f[k];
+    return s;
+}
+
+// float32 -> uint32 with the order of the floats; -0 and +0 get one image, as they compare equal
+__device__ __forceinline__ uint32_t ordered_bits(float x) {
+    uint32_t u = __float_as_uint(x);
+    u = u == 0x80000000u ? 0u : u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__global__ __launch_bounds__(kActBlock) void placement_act_kernel(const ActArgs p) {
+    __shared__ tpl::ShapeWord s_shape[32];
+    __shared__ __attribute__((aligned(16))) float s_w[kBoardsPerBlock][kFeatures];
+    __shared__ unsigned long long s_best[kBoardsPerBlock];
+    const uint32_t first = blockIdx.x * kBoardsPerBlock;                // the block's boards: first .. first + 7
+    if (threadIdx.x < 32) s_shape[threadIdx.x] = tpl::kShapeTable[threadIdx.x];
+    if (threadIdx.x < kBoardsPerBlock) {
+        s_best[threadIdx.x] = 0ull;                                     // below every key: a key's high word has a bit set
+        const uint32_t board = min(first + threadIdx.x, p.n - 1u);
+        const float4* row = (const float4*)(p.weights + (size_t)(board / p.per_member) * kFeatures);
+        float4* dst = (float4*)s_w[threadIdx.x];
+        dst[0] = row[0]; dst[1] = row[1]; dst[2] = row[2];
+    }
+    __syncthreads();
+    const uint32_t slot = threadIdx.x / kActions, a = threadIdx.x - slot * kActions;
+    const uint32_t r = a / 10u, l = a - r * 10u;
+    const uint32_t i = first + slot;
+    const bool valid = i < p.n;                                         // whole boards: all 40 lanes of a board agree
+    const uint32_t src = valid ? i : p.n - 1u;                          // past the end: the last board again, never written
+    Features phi;
+    uint32_t cur;
+    pair_features(p.a[src], p.b[src], s_shape, r, l, p.L, p.M, phi, cur);
+    float w[kFeatures];
+    const float4* row = (const float4*)s_w[slot];
+#pragma unroll
+    for (int q = 0; q < kFeatures / 4; ++q) {
+        const float4 v = row[q];
+        w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
+    }
+    const float score = placement_score(w, phi);
+    const bool contends = valid && canonical_action(cur, r, l) == a;
+    const unsigned long long key = ((unsigned long long)ordered_bits(score) << 32) | (uint32_t)(kActions - 1 - a);
+    if (contends) atomicMax(&s_best[slot], key);
+    __syncthreads();
+    if (contends && s_best[slot] == key) {                              // one lane per board: the keys of a board are distinct
+        p.action[i] = (uint8_t)a;
+        if (p.score) p.score[i] = score;
+    }
+}
+
+}  // namespace
+}  // namespace tpl_learn
+
+using namespace tpl_learn;
+
+namespace {
+
+// the checks the two entry points share; `name` leads the message
+int check_planes(const char* name, const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M) {
+    if (!plane_a || !plane_b) return fail_msg(TPL_ERR_ARG, "%s: null pointer", name);
+    if (n < 1) return fail_msg(TPL_ERR_ARG, "%s: n must be positive", name);
+    if (n >= (((int64_t)1 << 31) + kActions - 1) / kActions)
+        return fail_msg(TPL_ERR_ARG, "%s: n too large (40 n must stay below 2^31)", name);
+    if (L < 1 || L > 255 || M < 1 || M > 255) return fail_msg(TPL_ERR_ARG, "%s: L and M must be in [1, 255]", name);
+    if (((uintptr_t)plane_a & 15u) || ((uintptr_t)plane_b & 15u))
+        return fail_msg(TPL_ERR_ARG, "%s: planes must be 16-byte aligned", name);
+    return TPL_OK;
+}
+
+}  // namespace
+
+extern "C" int tpl_placement_features(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M,
+                                      int16_t* features, uint8_t* canonical, void* stream) {
+    const char* name = "tpl_placement_features";
+    if (const int rc = check_planes(name, plane_a, plane_b, n, L, M)) return rc;
+    if (!features) return fail_msg(TPL_ERR_ARG, "%s: null pointer (features is required)", name);
+    if ((uintptr_t)features & 7u) return fail_msg(TPL_ERR_ARG, "%s: features must be 8-byte aligned", name);
+    FeatureArgs p{};
+    p.a = (const uint4*)plane_a; p.b = (const uint4*)plane_b; p.total = (uint32_t)(n * kActions);
+    p.L = (uint32_t)L; p.M = (uint32_t)M; p.features = (uint2*)features; p.canonical = canonical;
+    const dim3 grid((p.total + kFeatureBlock - 1) / kFeatureBlock), block(kFeatureBlock);
+    hipLaunchKernelGGL(placement_features_kernel, grid, block, 0, (hipStream_t)stream, p);
+    TPL_LEARN_HIP(hipGetLastError());
+    return TPL_OK;
+}
+
+extern "C" int tpl_placement_act(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const float* weights,
+                                 int64_t boards_per_member, uint8_t* action, float* score, void* stream) {
+    const char* name = "tpl_placement_act";
+    if (const int rc = check_planes(name, plane_a, plane_b, n, L, M)) return rc;
+    if (!weights || !action) return fail_msg(TPL_ERR_ARG, "%s: null pointer (weights and action are required)", name);
+    if (boards_per_member < 1) return fail_msg(TPL_ERR_ARG, "%s: boards_per_member must be positive", name);
+    if ((uintptr_t)weights & 15u) return fail_msg(TPL_ERR_ARG, "%s: weights must be 16-byte aligned", name);
+    if ((uintptr_t)score & 3u) return fail_msg(TPL_ERR_ARG, "%s: score must be 4-byte aligned", name);
+    ActArgs p{};
+    p.a = (const uint4*)plane_a; p.b = (const uint4*)plane_b; p.n = (uint32_t)n;
+    p.L = (uint32_t)L; p.M = (uint32_t)M; p.weights = weights;
+    p.per_member = (uint32_t)(boards_per_member < n ? boards_per_member : n);     // anything above n is the single-policy case
+    p.action = action; p.score = score;
+    const dim3 grid((p.n + kBoardsPerBlock - 1) / kBoardsPerBlock), block(kActBlock);
+    hipLaunchKernelGGL(placement_act_kernel, grid, block, 0, (hipStream_t)stream, p);
+    TPL_LEARN_HIP(hipGetLastError());
+    return TPL_OK;
+}

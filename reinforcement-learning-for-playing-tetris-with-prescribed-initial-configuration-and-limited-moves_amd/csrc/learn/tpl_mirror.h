@@ -7,6 +7,9 @@
 // comes out of a 64-bit literal (32 widths, two bits each) instead of a dependent load of the shape table.
 //
 // Every function takes `flip` and applies it with selects: a wave whose lanes disagree runs one straight-line path.
+//
+// canonical_action -- which of the 40 actions are one placement -- reads the same packed widths and lives here, shared by the
+// afterstate enumeration and the placement policy (afterstates.hip, heuristic.hip).
 #pragma once
 
 #include "../tpl_device.h"
@@ -21,6 +24,33 @@ constexpr uint64_t packed_widths() {
     return v;
 }
 constexpr uint64_t kWidthsLess1 = packed_widths();
+
+// rotations % len of get_tetromino as r & (len - 1): len - 1 of piece p at bits 2p, 2p + 1 (len = [2, 4, 4, 4, 2, 2, 1, 1])
+constexpr int kRotations[8] = TPL_PIECE_ROTATIONS;
+constexpr uint32_t packed_rotation_masks() {
+    uint32_t v = 0;
+    for (int p = 0; p < 8; ++p) v |= (uint32_t)(kRotations[p] - 1) << (2 * p);
+    return v;
+}
+constexpr uint32_t kRotationMasks = packed_rotation_masks();
+
+// the shape table holds entry [p][r % len] at [p][r] for every r: the canonical rotation names the same entry
+constexpr bool table_repeats_with_the_rotation_count() {
+    for (int p = 0; p < 8; ++p)
+        for (int r = 0; r < 4; ++r) {
+            const tpl::ShapeWord a = tpl::kShapeTableHost[p * 4 + r], b = tpl::kShapeTableHost[p * 4 + (r & (kRotations[p] - 1))];
+            if (a.x != b.x || a.y != b.y) return false;
+        }
+    return true;
+}
+static_assert(table_repeats_with_the_rotation_count(), "kRotations does not match the shape table");
+
+// canonical[a] = 10 (r mod nrot(cur)) + min(l, 10 - w(cur, r)) for a = 10 r + l, r < 4, l < 10
+__host__ __device__ __forceinline__ uint32_t canonical_action(uint32_t cur, uint32_t r, uint32_t l) {
+    const uint32_t right = 9u - ((uint32_t)(kWidthsLess1 >> (2u * (cur * 4u + r))) & 3u);      // 10 - w
+    const uint32_t rc = r & ((kRotationMasks >> (2u * cur)) & 3u);
+    return 10u * rc + (l < right ? l : right);
+}
 
 // a' = 10 ((4 - r) & 3) + (10 - w - min(l, 10 - w)) for a = 10 r' + l, r = r' & 3, w the width of entry [cur][r]; below 40
 __device__ __forceinline__ uint32_t mirror_action(uint32_t a, uint32_t cur, bool flip) {

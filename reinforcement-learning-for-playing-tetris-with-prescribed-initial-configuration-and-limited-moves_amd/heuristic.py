@@ -1,0 +1,227 @@
+"""Board features of every placement, a linear placement policy on them, and its tuning by the noisy cross-entropy method
+(the rule: include/tpl_learn.h; the kernels: csrc/learn/heuristic.hip).
+
+    placement_features(env)       phi(s, a) of all 40 actions of every board: int16 [K, 40, 12] (FEATURE_NAMES) and canonical
+    HeuristicPolicy(env, weights).act()
+                                  arg-max over the distinct placements of  w . phi(s, a)  in ONE launch: 32 bytes read and one
+                                  written per board; `weights` [P, 12] plays a population, `boards_per_member` boards each
+    evaluate_heuristic(env, weights, boards_per_member, steps)
+                                  episodes and wins of every member of a population on an auto-reset environment
+    tune_heuristic(L, M, config_pool, ...)
+                                  the weights by the noisy cross-entropy method (Szita & Lorincz 2006), fitness = win rate
+
+With weights (r_line, r_win, r_lose, 0, ..., 0) the policy is LookaheadPolicy(env, image=None): the best immediate reward.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _learn_lib
+from ._learn_lib import FEATURE_NAMES, NUM_ACTIONS, NUM_FEATURES, check
+from .lookahead import _MAX_BOARDS, _state_ptrs
+
+__all__ = ["FEATURE_NAMES", "placement_features", "HeuristicPolicy", "evaluate_heuristic", "tune_heuristic"]
+
+
+def placement_features(env, states_a: Optional[torch.Tensor] = None, states_b: Optional[torch.Tensor] = None):
+    """phi(s, a) for K states and all 40 actions: the resident boards of `env` (K = env.num_envs, read in place), or int32
+    [K, 4] plane pairs as env.expand_states takes them, under env.L and env.M.  Returns (features int16 [K, 40, 12], canonical
+    uint8 [K, 40]); entry [i, a] belongs to action a = 10 r + l played from state i, a == canonical[i, a] marks the distinct
+    placements, and a finished board's features are all zero."""
+    if (states_a is None) != (states_b is None):
+        raise ValueError("states_a and states_b go together")
+    if states_a is not None:
+        for t in (states_a, states_b):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != 4:
+                raise ValueError("states_a / states_b must be int32 [K, 4] tensors")
+        if states_a.shape != states_b.shape:
+            raise ValueError("states_a / states_b must be int32 [K, 4] tensors of equal shape")
+        k = int(states_a.shape[0])
+    else:
+        k = int(env.num_envs)
+    if not 1 <= k <= _MAX_BOARDS:
+        raise ValueError(f"placement_features takes 1 .. {_MAX_BOARDS} states (40 K must stay below 2^31)")
+    d = env.device
+    if states_a is not None:
+        states_a, states_b = states_a.to(d).contiguous(), states_b.to(d).contiguous()
+        src = (states_a.data_ptr(), states_b.data_ptr())
+    else:
+        src = _state_ptrs(env)
+    features = torch.empty((k, NUM_ACTIONS, NUM_FEATURES), dtype=torch.int16, device=d)
+    canonical = torch.empty((k, NUM_ACTIONS), dtype=torch.uint8, device=d)
+    stream = torch._C._cuda_getCurrentRawStream(d.index)
+    check(_learn_lib.lib().tpl_placement_features(src[0], src[1], k, env.L, env.M, features.data_ptr(), canonical.data_ptr(), stream))
+    return features, canonical
+
+
+def _weights(weights) -> np.ndarray:
+    """Anything array-like of shape [12] or [P, 12] -> finite float32 [P, 12]."""
+    if isinstance(weights, torch.Tensor):
+        weights = weights.detach().cpu().numpy()
+    w = np.asarray(weights)
+    if w.dtype == object or not (np.issubdtype(w.dtype, np.floating) or np.issubdtype(w.dtype, np.integer)):
+        raise ValueError(f"weights must be numbers of shape [{NUM_FEATURES}] or [P, {NUM_FEATURES}]")
+    if w.ndim == 1:
+        w = w[None]
+    if w.ndim != 2 or w.shape[1] != NUM_FEATURES or w.shape[0] < 1:
+        raise ValueError(f"weights must have shape [{NUM_FEATURES}] or [P, {NUM_FEATURES}], got {tuple(np.shape(weights))}")
+    with np.errstate(over="ignore"):
+        w = np.ascontiguousarray(w, dtype=np.float32)
+    if not np.isfinite(w).all():
+        raise ValueError("weights must be finite (in float32)")
+    return w
+
+
+def _members(n: int, rows: int, boards_per_member) -> int:
+    """The validated boards_per_member of `rows` weight rows on n boards (None: n for one row, else an even split)."""
+    if boards_per_member is None:
+        if n % rows:
+            raise ValueError(f"{n} boards do not split evenly among {rows} weight rows: give boards_per_member")
+        boards_per_member = n // rows
+    if isinstance(boards_per_member, bool) or int(boards_per_member) != boards_per_member or int(boards_per_member) < 1:
+        raise ValueError("boards_per_member must be a positive integer")
+    per = int(boards_per_member)
+    if -(-n // per) != rows:
+        raise ValueError(f"{n} boards at {per} per member are {-(-n // per)} members, but weights has {rows} rows")
+    return per
+
+
+class HeuristicPolicy:
+    """The linear placement policy on the resident boards of `env`: act() gives every board the arg-max over the distinct
+    placements of w . phi(s, a) (left to right in float32; the lowest action on ties; action 0 for a finished board), in one
+    launch that leaves the environment as it is.
+
+    weights: [12], or [P, 12] for a population -- board i plays row i // boards_per_member (the last member may be short;
+    None: the boards split evenly).  They are checked finite and uploaded once; set_weights() replaces them in place, so a
+    captured graph of act() plays the new ones."""
+
+    def __init__(self, env, weights, boards_per_member: Optional[int] = None):
+        w = _weights(weights)
+        n = int(env.num_envs)
+        if not 1 <= n <= _MAX_BOARDS:
+            raise ValueError(f"HeuristicPolicy takes an environment of 1 .. {_MAX_BOARDS} boards (40 N must stay below 2^31)")
+        self.boards_per_member = _members(n, w.shape[0], boards_per_member)
+        self.env, self.members = env, int(w.shape[0])
+        self.weights = torch.from_numpy(w).to(env.device)
+        self._planes = None
+
+    def set_weights(self, weights) -> None:
+        """Replace the weights (same shape) in the device buffer act() reads."""
+        w = _weights(weights)
+        if w.shape != tuple(self.weights.shape):
+            raise ValueError(f"weights must keep their shape {tuple(self.weights.shape)}")
+        self.weights.copy_(torch.from_numpy(w), non_blocking=False)
+
+    @torch.no_grad()
+    def act(self, out: Optional[torch.Tensor] = None, score: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """uint8 [N]: the action of every resident board; `score` (float32 [N], optional) receives the chosen action's score.
+        No host sync, and no allocation when `out` is given: capturable into a HIP graph."""
+        env = self.env
+        if out is None:
+            out = torch.empty(env.num_envs, dtype=torch.uint8, device=env.device)
+        env._own(out, torch.uint8, "out")
+        if score is not None:
+            env._own(score, torch.float32, "score")
+        if self._planes is None:
+            self._planes = _state_ptrs(env)                   # the resident planes live as long as the environment
+        stream = torch._C._cuda_getCurrentRawStream(env.device.index)
+        check(_learn_lib.lib().tpl_placement_act(self._planes[0], self._planes[1], env.num_envs, env.L, env.M,
+                                                 self.weights.data_ptr(), self.boards_per_member, out.data_ptr(),
+                                                 None if score is None else score.data_ptr(), stream))
+        return out
+
+
+def _win_count_reward(env) -> None:
+    if tuple(env.reward_params) != (0.0, 1.0, 0.0):
+        raise ValueError("evaluate_heuristic counts wins as summed reward: the environment's reward must be (0, 1, 0), "
+                         f"not {tuple(env.reward_params)}")
+
+
+@torch.no_grad()
+def evaluate_heuristic(env, weights, boards_per_member: Optional[int], steps: int, policy: Optional[HeuristicPolicy] = None) -> dict:
+    """Play `steps` steps of the population `weights` ([P, 12] or [12]) on `env` from a full reset: an auto-reset environment
+    with a configuration pool and reward parameters (0, 1, 0), so that the summed reward is the number of wins.  Member p plays
+    boards [p * boards_per_member, (p + 1) * boards_per_member).  Returns episodes and wins as int64 numpy arrays [P] and
+    win_rate = wins / max(episodes, 1); the tallies are kept on the device, with one sync at the end.  `policy`: a
+    HeuristicPolicy of this environment to reuse (its weights are replaced)."""
+    _win_count_reward(env)
+    if not env.auto_reset:
+        raise ValueError("evaluate_heuristic needs an auto-reset environment")
+    if isinstance(steps, bool) or int(steps) != steps or int(steps) < 1:
+        raise ValueError("steps must be a positive integer")
+    if policy is None:
+        policy = HeuristicPolicy(env, weights, boards_per_member)
+    else:
+        if policy.env is not env:
+            raise ValueError("policy belongs to another environment")
+        policy.set_weights(weights)
+        if boards_per_member is not None and int(boards_per_member) != policy.boards_per_member:
+            raise ValueError("policy was built with another boards_per_member")
+    n, d = env.num_envs, env.device
+    action = torch.empty(n, dtype=torch.uint8, device=d)
+    reward = torch.empty(n, dtype=torch.float32, device=d)
+    done = torch.empty(n, dtype=torch.uint8, device=d)
+    episodes = torch.zeros(n, dtype=torch.int32, device=d)
+    wins = torch.zeros(n, dtype=torch.float32, device=d)     # a board wins fewer than 2^24 times: the float sum is exact
+    env.reset()
+    for _ in range(int(steps)):
+        env.step_into(policy.act(out=action), reward, done)
+        episodes += done
+        wins += reward
+    member = torch.arange(n, device=d) // policy.boards_per_member
+    zeros = torch.zeros(policy.members, dtype=torch.int64, device=d)
+    ep = zeros.index_add(0, member, episodes.to(torch.int64)).cpu().numpy()
+    wn = zeros.index_add(0, member, wins.to(torch.int64)).cpu().numpy()
+    return dict(episodes=ep, wins=wn, win_rate=wn / np.maximum(ep, 1))
+
+
+def tune_heuristic(L: int, M: int, config_pool, population: int = 64, boards_per_member: int = 4096, steps: Optional[int] = None,
+                   generations: int = 20, elite_frac: float = 0.125, init_mean=None, init_std: float = 10.0, noise: float = 0.5,
+                   seed: int = 0, device="cuda:0") -> dict:
+    """The noisy cross-entropy method on the twelve weights.  Each generation samples `population` weight rows from
+    N(mean, diag std^2) with a CPU torch.Generator seeded by `seed`, plays them side by side (`boards_per_member` boards each,
+    `steps` steps from a full reset, default 4 M: some four episodes a board) on ONE evaluation environment of
+    population * boards_per_member boards over `config_pool` = (rows, pieces) with reward (0, 1, 0), takes fitness = wins /
+    max(episodes, 1), and refits mean and std to the best ceil(elite_frac * population) rows, std^2 = var(elite) + noise (the
+    constant noise term that keeps the search from freezing early).
+
+    Returns mean (float32 [12], the final one), best (float32 [12], the best member seen) with best_fitness, and history: one
+    dict of host floats per generation (population_mean, elite_mean, best).  Deterministic for a given seed."""
+    from .env import BatchedTetris
+    for name, v in (("population", population), ("boards_per_member", boards_per_member), ("generations", generations)):
+        if isinstance(v, bool) or int(v) != v or int(v) < 1:
+            raise ValueError(f"{name} must be a positive integer")
+    if not 0.0 < float(elite_frac) <= 1.0:
+        raise ValueError("elite_frac must be in (0, 1]")
+    if not (np.isfinite(init_std) and init_std > 0 and np.isfinite(noise) and noise >= 0):
+        raise ValueError("init_std must be positive and noise non-negative")
+    P, per = int(population), int(boards_per_member)
+    steps = 4 * int(M) if steps is None else int(steps)
+    mean = np.zeros(NUM_FEATURES, np.float64) if init_mean is None else _weights(init_mean)[0].astype(np.float64)
+    std = np.full(NUM_FEATURES, float(init_std), np.float64)
+    elite = max(1, int(np.ceil(float(elite_frac) * P)))
+    env = BatchedTetris(L, M, P * per, device=device, seed=int(seed), auto_reset=True, reward=(0.0, 1.0, 0.0),
+                        config_pool=config_pool)
+    gen = torch.Generator(device="cpu")
+    gen.manual_seed(int(seed))
+    policy, best, best_fitness, history = None, mean.astype(np.float32), -1.0, []
+    try:
+        for _ in range(int(generations)):
+            z = torch.randn((P, NUM_FEATURES), generator=gen, dtype=torch.float64).numpy()
+            rows = (mean[None, :] + std[None, :] * z).astype(np.float32)
+            if policy is None:
+                policy = HeuristicPolicy(env, rows, per)
+            fitness = evaluate_heuristic(env, rows, per, steps, policy=policy)["win_rate"]
+            order = np.argsort(-fitness, kind="stable")        # ties: the lower member first
+            top = rows[order[:elite]].astype(np.float64)
+            if fitness[order[0]] > best_fitness:
+                best, best_fitness = rows[order[0]].copy(), float(fitness[order[0]])
+            mean, std = top.mean(axis=0), np.sqrt(top.var(axis=0) + float(noise))
+            history.append(dict(population_mean=float(fitness.mean()), elite_mean=float(fitness[order[:elite]].mean()),
+                                best=float(fitness[order[0]])))
+    finally:
+        env.terminate()
+    return dict(mean=mean.astype(np.float32), best=best, best_fitness=best_fitness, history=history)

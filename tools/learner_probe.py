@@ -25,6 +25,11 @@ Parts:
               board) and against the VALU-issue yardstick (the kernel's static vector instructions per wave at 3.3 cycles each on
               1,024 SIMDs at 2.4 GHz); the loop's win rate under evaluate(lookahead=True) next to the greedy one, and one
               LookaheadPolicy.act() at 262,144 boards
+    heuristic    the placement policy: tpl_placement_act and tpl_placement_features at 2^16, 2^18 and 2^20 boards (L=10 / M=40,
+              mid-game), alternated over five rounds, each against 6.3 TB/s over its bytes and against the VALU-issue yardstick;
+              HeuristicPolicy.act() against LookaheadPolicy(env, image=None).act() at 262,144 boards, alternated in one process;
+              act() + step() env-steps/s at 2^20 boards; win rates of the uniform random policy, the reward weights and
+              tune_heuristic's weights on the loop's L=2 / M=2 pool and on an L=10 / M=40 carved pool (>= 10^6 episodes each)
 """
 import argparse
 import json
@@ -37,7 +42,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 HBM_ACHIEVABLE = 6.3e12
-PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600, "priority": 600, "nstep": 600, "mirror": 600, "afterstates": 600}
+PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600, "priority": 600, "nstep": 600, "mirror": 600, "afterstates": 600,
+         "heuristic": 600}
 VALU_CYCLES, SIMDS, CLOCK_HZ = 3.3, 1024, 2.4e9           # the move's instruction mix, 256 CUs x 4, the clock
 
 
@@ -444,6 +450,123 @@ def part_afterstates(rounds=5):
     loop = part_loop(lookahead=True)
     loop["part"] = "loop_lookahead"
     out["loop"] = loop
+    return out
+
+
+def _win_rates(L_, M_, pool, n, steps, tuned, seed):
+    """Win rates over `steps` steps of n auto-reset boards from a full reset: uniform random, the reward weights (0, 1, 0: the
+    best immediate win), `tuned`."""
+    import torch
+    import tetris_piclim as T
+    env = T.BatchedTetris(L_, M_, n, device="cuda:0", seed=seed, auto_reset=True, reward=(0.0, 1.0, 0.0), config_pool=pool)
+    env.reset()
+    reward_sum, finished = env.rollout_random(steps, seed=seed + 1)
+    out = dict(boards=n, steps=steps, seed=seed)
+    out["random"] = dict(episodes=int(finished.sum()), wins=int(round(float(reward_sum.sum()))))
+    for name, w in (("reward_weights", [0.0, 1.0, 0.0] + [0.0] * 9), ("tuned", tuned)):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        got = T.evaluate_heuristic(env, w, None, steps)
+        out[name] = dict(episodes=int(got["episodes"][0]), wins=int(got["wins"][0]), seconds=round(time.perf_counter() - t0, 3))
+    for name in ("random", "reward_weights", "tuned"):
+        out[name]["win_rate"] = round(out[name]["wins"] / max(out[name]["episodes"], 1), 5)
+    env.terminate()
+    return out
+
+
+def part_heuristic(rounds=5):
+    import ctypes as C
+    import numpy as np
+    import torch
+    import tetris_piclim as T
+    L = T._learn_lib.lib()
+    check = T._learn_lib.check
+    stream = torch._C._cuda_getCurrentRawStream(0)
+    lib_path = T._learn_lib.build_library()
+    valu = dict(act=_static_valu("placement_act_kernel", lib_path), features=_static_valu("placement_features_kernel", lib_path),
+                afterstates=_static_valu("afterstates_kernel", lib_path))
+    out = dict(part="heuristic", static_valu_per_wave=valu, valu_cycles=VALU_CYCLES, streaming_tb_per_s=HBM_ACHIEVABLE / 1e12)
+    classical = np.array([4, 100, -100, -8, -1, 0, -2, -3, -6, -3, -2, -1], np.float32) * np.float32(0.1)
+    weights = torch.from_numpy(classical).to("cuda:0")
+    rows = []
+    for n in (1 << 16, 1 << 18, 1 << 20):
+        env = T.BatchedTetris(10, 40, n, device="cuda:0", seed=1, auto_reset=True)
+        env.load_configs(*env.synthetic_configs(4096))
+        env.reset()
+        for t in range(6):                                       # mid-game boards
+            env.step(env.synthetic_actions(t), observe=False)
+        pa, pb = C.c_void_p(), C.c_void_p()
+        T._lib.check(env._lib.tpl_state_ptrs(env._h, C.byref(pa), C.byref(pb)))
+        feats = torch.empty((n, 40, 12), dtype=torch.int16, device="cuda:0")
+        canonical = torch.empty((n, 40), dtype=torch.uint8, device="cuda:0")
+        action = torch.empty(n, dtype=torch.uint8, device="cuda:0")
+        score = torch.empty(n, dtype=torch.float32, device="cuda:0")
+
+        def act(with_score):
+            check(L.tpl_placement_act(pa.value, pb.value, n, 10, 40, weights.data_ptr(), n, action.data_ptr(),
+                                      score.data_ptr() if with_score else None, stream))
+
+        def features():
+            check(L.tpl_placement_features(pa.value, pb.value, n, 10, 40, feats.data_ptr(), canonical.data_ptr(), stream))
+        variants = [("act", lambda: act(False), 32 + 1, "act"), ("act_with_score", lambda: act(True), 32 + 5, "act"),
+                    ("features", features, 32 + 40 * 25, "features")]
+        times = {name: [] for name, _, _, _ in variants}
+        for _ in range(rounds):                                  # alternate the forms round by round
+            for name, fn, _, _ in variants:
+                times[name].append(_timed(fn, 20))
+        row = dict(boards=n)
+        for name, _, nbytes, kernel in variants:
+            t = sorted(times[name])[rounds // 2]
+            t_mem = n * nbytes / HBM_ACHIEVABLE
+            t_valu = (n * 40 / 64) * valu[kernel] * VALU_CYCLES / SIMDS / CLOCK_HZ
+            row[name] = dict(us=_spread(times[name]), bytes_per_board=nbytes, of_streaming=round(t_mem / t, 4),
+                             valu_yardstick_us=round(t_valu * 1e6, 2), of_valu_yardstick=round(t_valu / t, 3),
+                             bound="memory" if t_mem >= t_valu else "valu-issue")
+        if n == 1 << 18:                                         # against the best-immediate-reward path that was there before
+            fused = T.HeuristicPolicy(env, [1.0, 0.0, 0.0] + [0.0] * 9)
+            parent = T.LookaheadPolicy(env, image=None)
+            assert torch.equal(fused.act(), parent.act())
+            ts = dict(fused=[], lookahead_without_network=[])
+            for _ in range(rounds):
+                ts["fused"].append(_timed(lambda: fused.act(out=action), 20))
+                ts["lookahead_without_network"].append(_timed(lambda: parent.act(out=action), 20))
+            row["policy_act"] = {k: _spread(v) for k, v in ts.items()}
+            row["policy_act"]["lookahead_chunks"] = -(-n // parent.chunk)
+        if n == 1 << 20:                                         # the host-driven loop: one act() and one step() per iteration
+            policy = T.HeuristicPolicy(env, classical)
+            reward = torch.empty(n, dtype=torch.float32, device="cuda:0")
+            done = torch.empty(n, dtype=torch.uint8, device="cuda:0")
+
+            def both():
+                env.step_into(policy.act(out=action), reward, done)
+            ts = [_timed(both, 20) for _ in range(rounds)]
+            step_only = [_timed(lambda: env.step_into(action, reward, done), 20) for _ in range(rounds)]
+            row["act_and_step"] = dict(us=_spread(ts), env_steps_per_s=round(n / sorted(ts)[rounds // 2]),
+                                       step_alone_us=_spread(step_only))
+        rows.append(row)
+        env.terminate()
+        del feats
+        torch.cuda.empty_cache()
+    out["kernel"] = dict(rounds=rounds, launches_per_timing=20, rows=rows)
+    # win rates: the loop's L=2 / M=2 pool (yardsticks: random 0.027, greedy 0.94, lookahead 0.97) ...
+    small = T.generate_configs(2, 2, 64, seed=100)
+    t0 = time.perf_counter()
+    tuned = T.tune_heuristic(2, 2, small, population=64, boards_per_member=4096, steps=8, generations=10, seed=0)
+    budget = dict(population=64, boards_per_member=4096, steps=8, generations=10, seed=0, seconds=round(time.perf_counter() - t0, 2))
+    out["l2_m2"] = dict(tune=dict(budget, best_fitness=round(tuned["best_fitness"], 5), best=[round(float(x), 4) for x in tuned["best"]],
+                                  history=tuned["history"]), rates=_win_rates(2, 2, small, 1 << 18, 8, tuned["best"], seed=0))
+    # ... and an L=10 / M=40 carved pool: one seed, >= 10^6 episodes per policy
+    gen_env = T.BatchedTetris(10, 40, 64, device="cuda:0", seed=7)
+    big = gen_env.carved_configs(1 << 16, seed=7)
+    gen_env.terminate()
+    t0 = time.perf_counter()
+    tuned = T.tune_heuristic(10, 40, big, population=64, boards_per_member=4096, steps=160, generations=40, seed=0)
+    budget = dict(population=64, boards_per_member=4096, steps=160, generations=40, seed=0, pool=1 << 16, pool_seed=7,
+                  seconds=round(time.perf_counter() - t0, 2))
+    out["l10_m40"] = dict(tune=dict(budget, best_fitness=round(tuned["best_fitness"], 5),
+                                    best=[round(float(x), 4) for x in tuned["best"]], mean=[round(float(x), 4) for x in tuned["mean"]],
+                                    history=tuned["history"]),
+                          rates=_win_rates(10, 40, big, 1 << 18, 200, tuned["best"], seed=11))
     return out
 
 
