@@ -260,6 +260,29 @@ int tpl_placement_features(const void* plane_a, const void* plane_b, int64_t n, 
 int tpl_placement_act(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const float* weights,
                       int64_t boards_per_member, uint8_t* action, float* score, void* stream);
 
+/* Two plies with the known next piece.  Window entry 1 of a state is the piece after the current one, and an afterstate's window is
+ * good for exactly these two entries (above), so two plies is the deepest search this library makes exactly without a pool.
+ * For a state s with weight row w[12], cur = window entry 0 of s, nxt = window entry 1:
+ *   Finished board (state(s) != running): action 0, second 255, score = the score of twelve zeros -- the one-ply rule.
+ *   Running board: for every distinct first placement a (a == canonical(cur, a)), move_board(s, a) exactly as tpl_afterstates makes
+ *   it gives n1 rows cleared, state1 and the board s1, whose window is popped by one entry, so that its current piece is nxt.
+ *     state1 != running (the first move ends the game): psi(a) = phi(s, a), the twelve one-ply features; V(a) = score(w, psi(a));
+ *       second(a) = 255.
+ *     otherwise, for every distinct second placement b (b == canonical(nxt, b)), move_board(s1, b) gives n2, state2 and the board s2:
+ *       psi(a, b) = (n1 + n2, won2, lost2, features 3..11 of s2) -- feature 0 is 0..8 and converts exactly;
+ *       score(a, b) = the score rule above on psi(a, b): left to right in float32, every product and sum rounded once, never fused;
+ *       V(a) = max over b of score(a, b); second(a) = the lowest b at that maximum (-0 and +0 tie; V(a) is that b's score).
+ *   Choice: action = the lowest a at the maximum of V, second = second(action), score = V(action).
+ * nxt = 7 ("none": the piece list ends after cur) is what move_board and the shape table make of it: O's entry, nine placements.
+ * The weight rows of a population and THE FINITENESS CAVEAT are tpl_placement_act's.
+ * After a non-auto-reset step with `action`, a board that still runs has a one-ply choice (tpl_placement_act, w_0 = 0) of `second`
+ * with the same score: the second ply is the one-ply rule on the board the step leaves.
+ *
+ * One kernel: 32 bytes read per board, action u8 [n], second u8 [n] (optional), score f32 [n] (optional) written; an output that is
+ * not given is not written.  Refused before any HIP call: everything tpl_placement_act refuses. */
+int tpl_placement_search(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const float* weights,
+                         int64_t boards_per_member, uint8_t* action, uint8_t* second, float* score, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

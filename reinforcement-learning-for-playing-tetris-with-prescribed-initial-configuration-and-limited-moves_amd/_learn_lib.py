@@ -29,7 +29,7 @@ LEARN_SYMBOLS = [
     "tpl_learn_image_bytes", "tpl_learn_pack", "tpl_priority_tree_bytes", "tpl_priority_init", "tpl_priority_push",
     "tpl_priority_update", "tpl_replay_sample_prioritized", "tpl_priority_target", "tpl_replay_sample_nstep",
     "tpl_replay_sample_mirror", "tpl_mirror_states", "tpl_afterstates", "tpl_canonical_action", "tpl_placement_features",
-    "tpl_placement_act",
+    "tpl_placement_act", "tpl_placement_search",
 ]
 NSTEP_MAX = 16
 MIRROR_MODES = {False: 0, True: 1, "always": 2}          # sample(mirror=...) -> tpl_mirror_mode
@@ -132,9 +132,11 @@ def lib() -> C.CDLL:
     L.tpl_canonical_action.argtypes = [i32, i32]
     L.tpl_placement_features.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp]
     L.tpl_placement_act.argtypes = [vp, vp, i64, i32, i32, vp, i64, vp, vp, vp]
+    L.tpl_placement_search.argtypes = [vp, vp, i64, i32, i32, vp, i64, vp, vp, vp, vp]
     for name in ("tpl_replay_push", "tpl_replay_sample", "tpl_learn_pack", "tpl_priority_init", "tpl_priority_push",
                  "tpl_priority_update", "tpl_replay_sample_prioritized", "tpl_replay_sample_nstep", "tpl_replay_sample_mirror",
-                 "tpl_mirror_states", "tpl_afterstates", "tpl_placement_features", "tpl_placement_act"):
+                 "tpl_mirror_states", "tpl_afterstates", "tpl_placement_features", "tpl_placement_act",
+                 "tpl_placement_search"):
         getattr(L, name).restype = i32
     _handle = L
     return L
@@ -452,6 +454,41 @@ def placement_score(features, weights) -> np.ndarray:
     for k in range(1, NUM_FEATURES):
         s = s + w[..., k] * f[..., k]
     return np.asarray(s, dtype=np.float32)
+
+
+NO_SECOND = 255
+
+
+def search_choice(phi1, done1, distinct1, phi2, distinct2, weights):
+    """The two-ply rule of include/tpl_learn.h (tpl_placement_search) on features that are given: phi1 [K, 40, 12] the one-ply
+    features of every first placement a, done1 [K, 40] where the first move ends the game (every a of a finished board),
+    distinct1 [K, 40] where a is a distinct placement of the current piece, phi2 [K, 40, 40, 12] = psi(a, b) (read only where
+    done1 is not set), distinct2 [K, 40] or [K, 40, 40] where b is a distinct placement of the next piece; weights [12], or one
+    row per board [K, 12].  Returns (action u8 [K], second u8 [K] -- 255 where the chosen first move ends the game --, score
+    f32 [K]): V(a) = the one-ply score where done1, else the maximum over the distinct b of placement_score, the lowest index
+    at each maximum (-0 and +0 tie)."""
+    phi1, phi2 = np.asarray(phi1), np.asarray(phi2)
+    k = phi1.shape[0]
+    if phi1.shape != (k, NUM_ACTIONS, NUM_FEATURES) or phi2.shape != (k, NUM_ACTIONS, NUM_ACTIONS, NUM_FEATURES):
+        raise ValueError("phi1 must be [K, 40, 12] and phi2 [K, 40, 40, 12]")
+    done1, distinct1, distinct2 = (np.asarray(x).astype(bool) for x in (done1, distinct1, distinct2))
+    if distinct2.ndim == 2:
+        distinct2 = distinct2[:, None, :]
+    if done1.shape != (k, NUM_ACTIONS) or distinct1.shape != (k, NUM_ACTIONS) or distinct2.shape[::2] != (k, NUM_ACTIONS):
+        raise ValueError("done1 and distinct1 must be [K, 40] and distinct2 [K, 40] or [K, 40, 40]")
+    w = np.asarray(weights, dtype=np.float32).reshape(-1, NUM_FEATURES)
+    if w.shape[0] not in (1, k):
+        raise ValueError("weights must be [12] or one row per board")
+    rows = np.arange(k)[:, None]
+    first = np.arange(NUM_ACTIONS)[None, :]
+    score2 = np.where(distinct2, placement_score(phi2, w[:, None, None, :]), -np.inf)
+    second = np.argmax(score2 == score2.max(axis=2, keepdims=True), axis=2)       # the lowest b at the maximum
+    value = np.where(done1, placement_score(phi1, w[:, None, :]), score2[rows, first, second]).astype(np.float32)
+    second = np.where(done1, NO_SECOND, second)
+    masked = np.where(distinct1, value, -np.inf)
+    action = np.argmax(masked == masked.max(axis=1, keepdims=True), axis=1)
+    at = np.arange(k)
+    return action.astype(np.uint8), second[at, action].astype(np.uint8), value[at, action]
 
 
 # ------------------------------------------------------------------------------------------------ device packing

@@ -1,5 +1,5 @@
-// heuristic.hip -- board features of every placement and a linear placement policy on them: tpl_placement_features,
-// tpl_placement_act (include/tpl_learn.h states the rule).
+// heuristic.hip -- board features of every placement and a linear placement policy on them, one ply or two: tpl_placement_features,
+// tpl_placement_act, tpl_placement_search (include/tpl_learn.h states the rules).
 //
 // The classical Tetris controller scores the board a placement leaves by a linear function of a few hand-made features and
 // plays the best one.  In the column layout every such feature is a few ctz / popcount / xor operations on the ten column
@@ -203,6 +203,110 @@ __global__ __launch_bounds__(kActBlock) void placement_act_kernel(const ActArgs 
     }
 }
 
+struct SearchArgs {
+    const uint4* a;              // [n]
+    const uint4* b;
+    uint32_t n;                  // boards; 40 n below 2^31
+    uint32_t L, M;
+    const float* weights;        // [P][12], P = ceil(n / per_member)
+    uint32_t per_member;         // boards per weight row, in [1, n]
+    uint8_t* action;             // [n]
+    uint8_t* second;             // [n], optional
+    float* score;                // [n], optional
+};
+
+constexpr uint32_t kNoSecond = 255u;
+
+// Two plies with the known next piece: placement_act_kernel's block, lane mapping and arg-max, but a lane's value is the best
+// of the distinct placements of `nxt` on the board its own first move leaves.  The lane makes its first move once and keeps
+// s1 in registers; the loop below copies it, moves and scores once per distinct second placement (9, 17 or 34 trips, the same
+// for the 40 lanes of a board) and keeps a running best under a strict > on the ordered key, so the lowest b survives.  Alias
+// lanes and lanes whose first move ended the game (or whose board is finished) skip the loop: their value is the one-ply score.
+__global__ __launch_bounds__(kActBlock) void placement_search_kernel(const SearchArgs p) {
+    __shared__ tpl::ShapeWord s_shape[32];
+    __shared__ __attribute__((aligned(16))) float s_w[kBoardsPerBlock][kFeatures];
+    __shared__ unsigned long long s_best[kBoardsPerBlock];
+    const uint32_t first = blockIdx.x * kBoardsPerBlock;                // the block's boards: first .. first + 7
+    if (threadIdx.x < 32) s_shape[threadIdx.x] = tpl::kShapeTable[threadIdx.x];
+    if (threadIdx.x < kBoardsPerBlock) {
+        s_best[threadIdx.x] = 0ull;                                     // below every key: a key's high word has a bit set
+        const uint32_t board = min(first + threadIdx.x, p.n - 1u);
+        const float4* row = (const float4*)(p.weights + (size_t)(board / p.per_member) * kFeatures);
+        float4* dst = (float4*)s_w[threadIdx.x];
+        dst[0] = row[0]; dst[1] = row[1]; dst[2] = row[2];
+    }
+    __syncthreads();
+    const uint32_t slot = threadIdx.x / kActions, a = threadIdx.x - slot * kActions;
+    const uint32_t r = a / 10u, l = a - r * 10u;
+    const uint32_t i = first + slot;
+    const bool valid = i < p.n;                                         // whole boards: all 40 lanes of a board agree
+    const uint32_t src = valid ? i : p.n - 1u;                          // past the end: the last board again, never written
+    float w[kFeatures];
+    const float4* row = (const float4*)s_w[slot];
+#pragma unroll
+    for (int q = 0; q < kFeatures / 4; ++q) {
+        const float4 v = row[q];
+        w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
+    }
+
+    // the first ply: tpl_afterstates' move and pop
+    tpl::Board s1;
+    tpl::unpack_board(p.a[src], p.b[src], s1);
+    const uint32_t cur = s1.window & 7u;
+    const bool running = s1.state == tpl::ST_RUNNING;
+    bool topout;
+    const uint32_t n1 = tpl::move_board(s1, s_shape, r, l, p.L, p.M, topout);
+    tpl::next_window(s1, false, 0);
+    const uint32_t nxt = s1.window & 7u;
+    const bool contends = valid && canonical_action(cur, r, l) == a;
+    const bool goes_on = running && s1.state == tpl::ST_RUNNING;
+
+    float value;
+    uint32_t second = kNoSecond;
+    if (contends && goes_on) {
+        // the distinct placements of nxt in ascending b = 10 r2 + l2: r2 below nrot(nxt), l2 up to 10 - w(nxt, r2)
+        const uint32_t last_rot = (kRotationMasks >> (2u * nxt)) & 3u;
+        uint32_t best_key = 0u, r2 = 0u, l2 = 0u;
+        value = 0.0f;
+#pragma unroll 1
+        while (r2 <= last_rot) {
+            tpl::Board s2 = s1;
+            bool topout2;
+            const uint32_t n2 = tpl::move_board(s2, s_shape, r2, l2, p.L, p.M, topout2);
+            Features psi;
+            board_features(s2.c, psi);
+            psi.f[0] = n1 + n2;
+            psi.f[1] = s2.state == tpl::ST_WON ? 1u : 0u;
+            psi.f[2] = s2.state >= tpl::ST_LOST_LIMIT ? 1u : 0u;
+            const float sc = placement_score(w, psi);
+            const uint32_t key = ordered_bits(sc);                      // never 0, so the first trip is taken
+            if (key > best_key) { best_key = key; value = sc; second = 10u * r2 + l2; }
+            const uint32_t right = 9u - ((uint32_t)(kWidthsLess1 >> (2u * (nxt * 4u + r2))) & 3u);      // 10 - w
+            const bool wrap = l2 >= right;
+            l2 = wrap ? 0u : l2 + 1u;
+            r2 += wrap ? 1u : 0u;
+        }
+    } else {
+        // the one-ply features of (s, a): the first move ended the game, or the board was finished before it (all zero)
+        Features phi;
+        board_features(s1.c, phi);
+        phi.f[0] = n1;
+        phi.f[1] = s1.state == tpl::ST_WON ? 1u : 0u;
+        phi.f[2] = s1.state >= tpl::ST_LOST_LIMIT ? 1u : 0u;
+#pragma unroll
+        for (int k = 0; k < kFeatures; ++k) phi.f[k] = running ? phi.f[k] : 0u;
+        value = placement_score(w, phi);
+    }
+    const unsigned long long key = ((unsigned long long)ordered_bits(value) << 32) | (uint32_t)(kActions - 1 - a);
+    if (contends) atomicMax(&s_best[slot], key);
+    __syncthreads();
+    if (contends && s_best[slot] == key) {                              // one lane per board: the keys of a board are distinct
+        p.action[i] = (uint8_t)a;
+        if (p.second) p.second[i] = (uint8_t)second;
+        if (p.score) p.score[i] = value;
+    }
+}
+
 }  // namespace
 }  // namespace tpl_learn
 
@@ -210,7 +314,7 @@ using namespace tpl_learn;
 
 namespace {
 
-// the checks the two entry points share; `name` leads the message
+// the checks the entry points share; `name` leads the message
 int check_planes(const char* name, const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M) {
     if (!plane_a || !plane_b) return fail_msg(TPL_ERR_ARG, "%s: null pointer", name);
     if (n < 1) return fail_msg(TPL_ERR_ARG, "%s: n must be positive", name);
@@ -254,6 +358,25 @@ extern "C" int tpl_placement_act(const void* plane_a, const void* plane_b, int64
     p.action = action; p.score = score;
     const dim3 grid((p.n + kBoardsPerBlock - 1) / kBoardsPerBlock), block(kActBlock);
     hipLaunchKernelGGL(placement_act_kernel, grid, block, 0, (hipStream_t)stream, p);
+    TPL_LEARN_HIP(hipGetLastError());
+    return TPL_OK;
+}
+
+extern "C" int tpl_placement_search(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const float* weights,
+                                    int64_t boards_per_member, uint8_t* action, uint8_t* second, float* score, void* stream) {
+    const char* name = "tpl_placement_search";
+    if (const int rc = check_planes(name, plane_a, plane_b, n, L, M)) return rc;
+    if (!weights || !action) return fail_msg(TPL_ERR_ARG, "%s: null pointer (weights and action are required)", name);
+    if (boards_per_member < 1) return fail_msg(TPL_ERR_ARG, "%s: boards_per_member must be positive", name);
+    if ((uintptr_t)weights & 15u) return fail_msg(TPL_ERR_ARG, "%s: weights must be 16-byte aligned", name);
+    if ((uintptr_t)score & 3u) return fail_msg(TPL_ERR_ARG, "%s: score must be 4-byte aligned", name);
+    SearchArgs p{};
+    p.a = (const uint4*)plane_a; p.b = (const uint4*)plane_b; p.n = (uint32_t)n;
+    p.L = (uint32_t)L; p.M = (uint32_t)M; p.weights = weights;
+    p.per_member = (uint32_t)(boards_per_member < n ? boards_per_member : n);     // anything above n is the single-policy case
+    p.action = action; p.second = second; p.score = score;
+    const dim3 grid((p.n + kBoardsPerBlock - 1) / kBoardsPerBlock), block(kActBlock);
+    hipLaunchKernelGGL(placement_search_kernel, grid, block, 0, (hipStream_t)stream, p);
     TPL_LEARN_HIP(hipGetLastError());
     return TPL_OK;
 }

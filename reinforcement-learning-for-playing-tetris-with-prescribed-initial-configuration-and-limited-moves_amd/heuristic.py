@@ -5,6 +5,9 @@
     HeuristicPolicy(env, weights).act()
                                   arg-max over the distinct placements of  w . phi(s, a)  in ONE launch: 32 bytes read and one
                                   written per board; `weights` [P, 12] plays a population, `boards_per_member` boards each
+    HeuristicPolicy(env, weights, depth=2).act()
+                                  two plies with the known next piece (window entry 1), still one launch: a first placement is
+                                  worth the best placement of the next piece on the board it leaves
     evaluate_heuristic(env, weights, boards_per_member, steps)
                                   episodes and wins of every member of a population on an auto-reset environment
     tune_heuristic(L, M, config_pool, ...)
@@ -75,6 +78,12 @@ def _weights(weights) -> np.ndarray:
     return w
 
 
+def _depth(depth) -> int:
+    if isinstance(depth, bool) or depth not in (1, 2):
+        raise ValueError("depth must be 1 (the current piece) or 2 (the current and the known next piece)")
+    return int(depth)
+
+
 def _members(n: int, rows: int, boards_per_member) -> int:
     """The validated boards_per_member of `rows` weight rows on n boards (None: n for one row, else an even split)."""
     if boards_per_member is None:
@@ -96,9 +105,15 @@ class HeuristicPolicy:
 
     weights: [12], or [P, 12] for a population -- board i plays row i // boards_per_member (the last member may be short;
     None: the boards split evenly).  They are checked finite and uploaded once; set_weights() replaces them in place, so a
-    captured graph of act() plays the new ones."""
+    captured graph of act() plays the new ones.
 
-    def __init__(self, env, weights, boards_per_member: Optional[int] = None):
+    depth=2 searches two plies (tpl_placement_search): a first placement that does not end the game is worth the best score
+    among the distinct placements of the next piece -- window entry 1, which every state carries -- on the board it leaves,
+    scored on (rows cleared by both moves, won, lost, the nine features of the final board); one that ends the game is worth
+    its one-ply score.  Still one launch and nothing written but the outputs."""
+
+    def __init__(self, env, weights, boards_per_member: Optional[int] = None, depth: int = 1):
+        self.depth = _depth(depth)
         w = _weights(weights)
         n = int(env.num_envs)
         if not 1 <= n <= _MAX_BOARDS:
@@ -116,10 +131,15 @@ class HeuristicPolicy:
         self.weights.copy_(torch.from_numpy(w), non_blocking=False)
 
     @torch.no_grad()
-    def act(self, out: Optional[torch.Tensor] = None, score: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def act(self, out: Optional[torch.Tensor] = None, score: Optional[torch.Tensor] = None,
+            second: Optional[torch.Tensor] = None) -> torch.Tensor:
         """uint8 [N]: the action of every resident board; `score` (float32 [N], optional) receives the chosen action's score.
-        No host sync, and no allocation when `out` is given: capturable into a HIP graph."""
+        At depth 2 `second` (uint8 [N], optional) receives the placement of the next piece that the score belongs to, 255 where
+        the chosen move ends the game or the board is finished.  No host sync, and no allocation when `out` is given:
+        capturable into a HIP graph."""
         env = self.env
+        if second is not None and self.depth == 1:
+            raise ValueError("second is the second ply's placement: this policy has depth 1")
         if out is None:
             out = torch.empty(env.num_envs, dtype=torch.uint8, device=env.device)
         env._own(out, torch.uint8, "out")
@@ -127,7 +147,15 @@ class HeuristicPolicy:
             env._own(score, torch.float32, "score")
         if self._planes is None:
             self._planes = _state_ptrs(env)                   # the resident planes live as long as the environment
+        if second is not None:
+            env._own(second, torch.uint8, "second")
         stream = torch._C._cuda_getCurrentRawStream(env.device.index)
+        if self.depth == 2:
+            check(_learn_lib.lib().tpl_placement_search(self._planes[0], self._planes[1], env.num_envs, env.L, env.M,
+                                                        self.weights.data_ptr(), self.boards_per_member, out.data_ptr(),
+                                                        None if second is None else second.data_ptr(),
+                                                        None if score is None else score.data_ptr(), stream))
+            return out
         check(_learn_lib.lib().tpl_placement_act(self._planes[0], self._planes[1], env.num_envs, env.L, env.M,
                                                  self.weights.data_ptr(), self.boards_per_member, out.data_ptr(),
                                                  None if score is None else score.data_ptr(), stream))
@@ -141,19 +169,24 @@ def _win_count_reward(env) -> None:
 
 
 @torch.no_grad()
-def evaluate_heuristic(env, weights, boards_per_member: Optional[int], steps: int, policy: Optional[HeuristicPolicy] = None) -> dict:
+def evaluate_heuristic(env, weights, boards_per_member: Optional[int], steps: int, policy: Optional[HeuristicPolicy] = None,
+                       depth: int = 1) -> dict:
     """Play `steps` steps of the population `weights` ([P, 12] or [12]) on `env` from a full reset: an auto-reset environment
     with a configuration pool and reward parameters (0, 1, 0), so that the summed reward is the number of wins.  Member p plays
     boards [p * boards_per_member, (p + 1) * boards_per_member).  Returns episodes and wins as int64 numpy arrays [P] and
     win_rate = wins / max(episodes, 1); the tallies are kept on the device, with one sync at the end.  `policy`: a
-    HeuristicPolicy of this environment to reuse (its weights are replaced)."""
+    HeuristicPolicy of this environment to reuse (its weights are replaced).  `depth`: 1 or 2 plies (HeuristicPolicy's); a
+    `policy` that is passed must have been built with it."""
+    depth = _depth(depth)
+    if policy is not None and policy.depth != depth:
+        raise ValueError(f"policy was built with depth {policy.depth}, not {depth}")
     _win_count_reward(env)
     if not env.auto_reset:
         raise ValueError("evaluate_heuristic needs an auto-reset environment")
     if isinstance(steps, bool) or int(steps) != steps or int(steps) < 1:
         raise ValueError("steps must be a positive integer")
     if policy is None:
-        policy = HeuristicPolicy(env, weights, boards_per_member)
+        policy = HeuristicPolicy(env, weights, boards_per_member, depth=depth)
     else:
         if policy.env is not env:
             raise ValueError("policy belongs to another environment")
@@ -180,17 +213,18 @@ def evaluate_heuristic(env, weights, boards_per_member: Optional[int], steps: in
 
 def tune_heuristic(L: int, M: int, config_pool, population: int = 64, boards_per_member: int = 4096, steps: Optional[int] = None,
                    generations: int = 20, elite_frac: float = 0.125, init_mean=None, init_std: float = 10.0, noise: float = 0.5,
-                   seed: int = 0, device="cuda:0") -> dict:
+                   seed: int = 0, device="cuda:0", depth: int = 1) -> dict:
     """The noisy cross-entropy method on the twelve weights.  Each generation samples `population` weight rows from
     N(mean, diag std^2) with a CPU torch.Generator seeded by `seed`, plays them side by side (`boards_per_member` boards each,
     `steps` steps from a full reset, default 4 M: some four episodes a board) on ONE evaluation environment of
     population * boards_per_member boards over `config_pool` = (rows, pieces) with reward (0, 1, 0), takes fitness = wins /
     max(episodes, 1), and refits mean and std to the best ceil(elite_frac * population) rows, std^2 = var(elite) + noise (the
-    constant noise term that keeps the search from freezing early).
+    constant noise term that keeps the search from freezing early).  `depth`: the plies the members search (1 or 2).
 
     Returns mean (float32 [12], the final one), best (float32 [12], the best member seen) with best_fitness, and history: one
     dict of host floats per generation (population_mean, elite_mean, best).  Deterministic for a given seed."""
     from .env import BatchedTetris
+    depth = _depth(depth)
     for name, v in (("population", population), ("boards_per_member", boards_per_member), ("generations", generations)):
         if isinstance(v, bool) or int(v) != v or int(v) < 1:
             raise ValueError(f"{name} must be a positive integer")
@@ -213,8 +247,8 @@ def tune_heuristic(L: int, M: int, config_pool, population: int = 64, boards_per
             z = torch.randn((P, NUM_FEATURES), generator=gen, dtype=torch.float64).numpy()
             rows = (mean[None, :] + std[None, :] * z).astype(np.float32)
             if policy is None:
-                policy = HeuristicPolicy(env, rows, per)
-            fitness = evaluate_heuristic(env, rows, per, steps, policy=policy)["win_rate"]
+                policy = HeuristicPolicy(env, rows, per, depth=depth)
+            fitness = evaluate_heuristic(env, rows, per, steps, policy=policy, depth=depth)["win_rate"]
             order = np.argsort(-fitness, kind="stable")        # ties: the lower member first
             top = rows[order[:elite]].astype(np.float64)
             if fitness[order[0]] > best_fitness:

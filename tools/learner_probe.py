@@ -30,6 +30,13 @@ Parts:
               HeuristicPolicy.act() against LookaheadPolicy(env, image=None).act() at 262,144 boards, alternated in one process;
               act() + step() env-steps/s at 2^20 boards; win rates of the uniform random policy, the reward weights and
               tune_heuristic's weights on the loop's L=2 / M=2 pool and on an L=10 / M=40 carved pool (>= 10^6 episodes each)
+    search       the two-ply placement search: tpl_placement_search at 2^16, 2^18 and 2^20 boards (L=10 / M=40, mid-game) against its
+              instruction price (per wave: the static vector instructions outside the second-ply loop once, the loop's as often as
+              the wave's slowest board has distinct placements of its next piece); HeuristicPolicy(depth=2).act() against the
+              composition it replaces at 262,144 boards (per 16,384-board chunk: afterstates into a scratch environment,
+              tpl_placement_act over its 40 x 16,384 boards, a torch max), alternated in one process; win rates at depth 1 and 2
+              of the classical signs and of a tuned row on the L=2 / M=2 pool and an L=10 / M=40 carved pool (>= 10^6 episodes
+              each, with standard errors)
 """
 import argparse
 import json
@@ -43,7 +50,7 @@ sys.path.insert(0, ROOT)
 
 HBM_ACHIEVABLE = 6.3e12
 PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600, "priority": 600, "nstep": 600, "mirror": 600, "afterstates": 600,
-         "heuristic": 600}
+         "heuristic": 600, "search": 900}
 VALU_CYCLES, SIMDS, CLOCK_HZ = 3.3, 1024, 2.4e9           # the move's instruction mix, 256 CUs x 4, the clock
 
 
@@ -567,6 +574,150 @@ def part_heuristic(rounds=5):
                                     best=[round(float(x), 4) for x in tuned["best"]], mean=[round(float(x), 4) for x in tuned["mean"]],
                                     history=tuned["history"]),
                           rates=_win_rates(10, 40, big, 1 << 18, 200, tuned["best"], seed=11))
+    return out
+
+
+def _loop_valu(kernel, lib_path):
+    """(vector ALU instructions of the kernel, those of its outermost loop): the loop is the backward branch with the longest
+    span in the code as built (tools/dump_isa.sh); an inner loop's body counts once."""
+    import re
+    res = subprocess.run(["bash", os.path.join(ROOT, "tools", "dump_isa.sh"), kernel, lib_path], capture_output=True, text=True,
+                         cwd=ROOT, timeout=120)
+    code = []                                                    # (address, mnemonic, branch offset in dwords or None)
+    for l in res.stdout.splitlines():
+        m = re.match(r"\s+(\S+)\s+(.*?)//\s*([0-9A-Fa-f]+):", l)
+        if m:
+            off = int(m.group(2).split()[0]) if m.group(1).startswith("s_cbranch") or m.group(1) == "s_branch" else None
+            code.append((int(m.group(3), 16), m.group(1), off))
+    total = sum(1 for _, op, _ in code if op.startswith("v_"))
+    span = (0, 0)
+    for addr, op, off in code:
+        if off is not None and off >= 32768:                     # a 16-bit offset in dwords from the next instruction: backward
+            target = addr + 4 + 4 * (off - 65536)
+            if addr - target > span[1] - span[0]:
+                span = (target, addr)
+    return total, sum(1 for addr, op, _ in code if op.startswith("v_") and span[0] <= addr <= span[1])
+
+
+def _search_rates(L_, M_, pool, n, steps, rows, seed):
+    """Episodes, wins, win rate and its standard error of each named weight row at depth 1 and at depth 2, `steps` steps of n
+    auto-reset boards from a full reset."""
+    import torch
+    import tetris_piclim as T
+    env = T.BatchedTetris(L_, M_, n, device="cuda:0", seed=seed, auto_reset=True, reward=(0.0, 1.0, 0.0), config_pool=pool)
+    out = dict(boards=n, steps=steps, seed=seed)
+    for name, w in rows:
+        for depth in (1, 2):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            got = T.evaluate_heuristic(env, w, None, steps, depth=depth)
+            e, wins = int(got["episodes"][0]), int(got["wins"][0])
+            p = wins / max(e, 1)
+            out[f"{name}_depth{depth}"] = dict(episodes=e, wins=wins, win_rate=round(p, 5),
+                                               standard_error=round((p * (1 - p) / max(e, 1)) ** 0.5, 6),
+                                               seconds=round(time.perf_counter() - t0, 3))
+    env.terminate()
+    return out
+
+
+def part_search(rounds=5):
+    import ctypes as C
+    import numpy as np
+    import torch
+    import tetris_piclim as T
+    L = T._learn_lib.lib()
+    check = T._learn_lib.check
+    stream = torch._C._cuda_getCurrentRawStream(0)
+    lib_path = T._learn_lib.build_library()
+    total, loop = _loop_valu("placement_search_kernel", lib_path)
+    out = dict(part="search", static_valu=dict(kernel=total, second_ply_loop=loop, placement_act_kernel=_static_valu("placement_act_kernel", lib_path)),
+               valu_cycles=VALU_CYCLES, streaming_tb_per_s=HBM_ACHIEVABLE / 1e12)
+    classical = np.array([4, 100, -100, -8, -1, 0, -2, -3, -6, -3, -2, -1], np.float32) * np.float32(0.1)
+    weights = torch.from_numpy(classical).to("cuda:0")
+    trips_of = np.array([17, 34, 34, 34, 17, 17, 9, 9])          # the distinct placements of each piece id
+    rows = []
+    for n in (1 << 16, 1 << 18, 1 << 20):
+        env = T.BatchedTetris(10, 40, n, device="cuda:0", seed=1, auto_reset=True)
+        env.load_configs(*env.synthetic_configs(4096))
+        env.reset()
+        for t in range(6):                                       # mid-game boards
+            env.step(env.synthetic_actions(t), observe=False)
+        pa, pb = C.c_void_p(), C.c_void_p()
+        T._lib.check(env._lib.tpl_state_ptrs(env._h, C.byref(pa), C.byref(pb)))
+        action = torch.empty(n, dtype=torch.uint8, device="cuda:0")
+        second = torch.empty(n, dtype=torch.uint8, device="cuda:0")
+        score = torch.empty(n, dtype=torch.float32, device="cuda:0")
+        # the trips of every wave: a block is 8 boards on 5 waves, wave v holds threads 64 v .. 64 v + 63 = boards 64 v / 40 ..
+        # (64 v + 63) / 40 of the block, and runs as long as its slowest board
+        b = env.raw_planes()[1].cpu().numpy().view(np.uint32)
+        running = ((b[:, 1] >> 28) & 3) == 0
+        trips = np.where(running, trips_of[(b[:, 3] >> 3) & 7], 0).reshape(-1, 8)
+        wave_trips = np.stack([trips[:, (64 * v) // 40:(64 * v + 63) // 40 + 1].max(axis=1) for v in range(5)], axis=1)
+        valu_per_wave = (total - loop) + loop * float(wave_trips.mean())
+
+        def search(full):
+            check(L.tpl_placement_search(pa.value, pb.value, n, 10, 40, weights.data_ptr(), n, action.data_ptr(),
+                                         second.data_ptr() if full else None, score.data_ptr() if full else None, stream))
+        variants = [("search", lambda: search(False), 32 + 1), ("search_with_second_and_score", lambda: search(True), 32 + 6)]
+        times = {name: [] for name, _, _ in variants}
+        for _ in range(rounds):                                  # alternate the forms round by round
+            for name, fn, _ in variants:
+                times[name].append(_timed(fn, 20))
+        t_valu = (n * 40 / 64) * valu_per_wave * VALU_CYCLES / SIMDS / CLOCK_HZ
+        row = dict(boards=n, running=int(running.sum()), mean_trips_per_board=round(float(trips.mean()), 2),
+                   mean_trips_per_wave=round(float(wave_trips.mean()), 2), valu_per_wave=round(valu_per_wave),
+                   valu_yardstick_us=round(t_valu * 1e6, 1))
+        for name, _, nbytes in variants:
+            t = sorted(times[name])[rounds // 2]
+            row[name] = dict(us=_spread(times[name]), bytes_per_board=nbytes, of_streaming=round(n * nbytes / HBM_ACHIEVABLE / t, 5),
+                             of_valu_yardstick=round(t_valu / t, 3))
+        if n == 1 << 18:                                         # against the composition of the one-ply pieces it replaces
+            chunk = 16384
+            fused = T.HeuristicPolicy(env, classical, depth=2)
+            scratch = T.BatchedTetris(10, 40, 40 * chunk, device="cuda:0", seed=1)
+            inner = T.HeuristicPolicy(scratch, classical)
+            inner_action = torch.empty(40 * chunk, dtype=torch.uint8, device="cuda:0")
+            inner_score = torch.empty(40 * chunk, dtype=torch.float32, device="cuda:0")
+            reward = torch.empty((chunk, 40), dtype=torch.float32, device="cuda:0")
+            done, cleared, canonical = (torch.empty((chunk, 40), dtype=torch.uint8, device="cuda:0") for _ in range(3))
+            ids = torch.arange(40, dtype=torch.int64, device="cuda:0")
+            sa, sb = T.lookahead._state_ptrs(scratch)
+
+            def composed():
+                for first in range(0, n, chunk):
+                    T.lookahead._enumerate(env, pa.value + 16 * first, pb.value + 16 * first, chunk, sa, sb, reward, done, cleared,
+                                           canonical)
+                    inner.act(out=inner_action, score=inner_score)
+                    v = torch.where(canonical == ids, inner_score.view(chunk, 40), float("-inf"))
+                    action[first:first + chunk] = v.max(dim=1).indices.to(torch.uint8)
+            ts = dict(fused=[], composed=[])
+            for _ in range(rounds):
+                ts["fused"].append(_timed(lambda: fused.act(out=action), 20))
+                ts["composed"].append(_timed(composed, 20))
+            med = {k: sorted(v)[rounds // 2] for k, v in ts.items()}
+            row["policy_act"] = dict(fused_us=_spread(ts["fused"]), composed_us=_spread(ts["composed"]), chunks=n // chunk,
+                                     composed_over_fused=round(med["composed"] / med["fused"], 3))
+            scratch.terminate()
+        rows.append(row)
+        env.terminate()
+        torch.cuda.empty_cache()
+    out["kernel"] = dict(rounds=rounds, launches_per_timing=20, rows=rows)
+    # win rates at depth 1 and 2: the classical signs and a row tuned at depth 2, >= 10^6 episodes per figure
+    small = T.generate_configs(2, 2, 64, seed=100)
+    t0 = time.perf_counter()
+    tuned = T.tune_heuristic(2, 2, small, population=64, boards_per_member=4096, steps=8, generations=10, seed=0, depth=2)
+    budget = dict(population=64, boards_per_member=4096, steps=8, generations=10, seed=0, depth=2, seconds=round(time.perf_counter() - t0, 2))
+    out["l2_m2"] = dict(tune=dict(budget, best_fitness=round(tuned["best_fitness"], 5), best=[round(float(x), 4) for x in tuned["best"]]),
+                        rates=_search_rates(2, 2, small, 1 << 18, 8, (("classical", classical), ("tuned", tuned["best"])), seed=0))
+    gen_env = T.BatchedTetris(10, 40, 64, device="cuda:0", seed=7)
+    big = gen_env.carved_configs(1 << 16, seed=7)
+    gen_env.terminate()
+    t0 = time.perf_counter()
+    tuned = T.tune_heuristic(10, 40, big, population=32, boards_per_member=2048, steps=80, generations=10, seed=0, depth=2)
+    budget = dict(population=32, boards_per_member=2048, steps=80, generations=10, seed=0, depth=2, pool=1 << 16, pool_seed=7,
+                  seconds=round(time.perf_counter() - t0, 2))
+    out["l10_m40"] = dict(tune=dict(budget, best_fitness=round(tuned["best_fitness"], 5), best=[round(float(x), 4) for x in tuned["best"]]),
+                          rates=_search_rates(10, 40, big, 1 << 18, 160, (("classical", classical), ("tuned", tuned["best"])), seed=11))
     return out
 
 
