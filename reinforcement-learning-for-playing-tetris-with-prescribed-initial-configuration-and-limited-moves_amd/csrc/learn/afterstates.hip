@@ -13,14 +13,12 @@
 // a lane per board looping over 40 actions, would take the ten column tops once per board instead of once per pair, but its
 // stores are 640 B apart per lane (16 B per lane per row, 64 rows per wave store): the write side is 98 % of the traffic
 // (1,560 B out against 32 B in), so it decides.  Per board: 32 B read, 40 x (32 + 4 + 1 + 1 + 1) = 1,560 B written.
-#include "tpl_learn_internal.h"
-#include "tpl_mirror.h"
+#include "tpl_placement.h"
 
 namespace tpl_learn {
 namespace {
 
 constexpr int kAfterBlock = 256;
-constexpr int kActions = TPL_NUM_ACTIONS;
 
 struct AfterArgs {
     const uint4* a;              // [n]
@@ -53,15 +51,12 @@ __global__ __launch_bounds__(kAfterBlock) void afterstates_kernel(const AfterArg
     const uint32_t j = blockIdx.x * kAfterBlock + threadIdx.x;          // pair 40 i + a
     if (j >= p.total) return;
     const uint32_t i = j / kActions, a = j - i * kActions;
-    const uint32_t r = a / 10u, l = a - r * 10u;                        // values, never indices: move_board selects on them
+    const uint32_t r = a / 10u, l = a - r * 10u;
     const uint4 A = p.a[i], B = p.b[i];
     tpl::Board s;
-    tpl::unpack_board(A, B, s);
-    const uint32_t cur = s.window & 7u;
-    const bool running = s.state == tpl::ST_RUNNING;
-
-    bool topout;
-    const uint32_t n_clear = tpl::move_board(s, s_shape, r, l, p.L, p.M, topout);
+    uint32_t cur;
+    bool running;
+    const uint32_t n_clear = first_move(A, B, s_shape, r, l, p.L, p.M, s, cur, running);
     tpl::next_window(s, false, 0);                                      // pieces.pop(0) without a refill: zeros enter
     const float reward = afterstate_reward(p, n_clear, s.state);
 
@@ -92,16 +87,12 @@ extern "C" int32_t tpl_canonical_action(int32_t cur, int32_t action) {
 extern "C" int tpl_afterstates(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line,
                                float r_win, float r_lose, void* out_a, void* out_b, float* reward, uint8_t* done,
                                uint8_t* cleared, uint8_t* canonical, void* stream) {
-    if (!plane_a || !plane_b) return fail_msg(TPL_ERR_ARG, "tpl_afterstates: null pointer");
+    if (const int rc = check_planes("tpl_afterstates", plane_a, plane_b, n, L, M)) return rc;
     if ((out_a == nullptr) != (out_b == nullptr)) return fail_msg(TPL_ERR_ARG, "tpl_afterstates: out_a and out_b go together");
     if (!out_a && !reward && !done && !cleared && !canonical)
         return fail_msg(TPL_ERR_ARG, "tpl_afterstates: at least one output must be given");
-    if (n < 1) return fail_msg(TPL_ERR_ARG, "tpl_afterstates: n must be positive");
-    if (n >= (((int64_t)1 << 31) + kActions - 1) / kActions)
-        return fail_msg(TPL_ERR_ARG, "tpl_afterstates: n too large (40 n must stay below 2^31)");
-    if (L < 1 || L > 255 || M < 1 || M > 255) return fail_msg(TPL_ERR_ARG, "tpl_afterstates: L and M must be in [1, 255]");
-    if (((uintptr_t)plane_a & 15u) || ((uintptr_t)plane_b & 15u) || ((uintptr_t)out_a & 15u) || ((uintptr_t)out_b & 15u))
-        return fail_msg(TPL_ERR_ARG, "tpl_afterstates: planes must be 16-byte aligned");
+    if (((uintptr_t)out_a & 15u) || ((uintptr_t)out_b & 15u))
+        return fail_msg(TPL_ERR_ARG, "tpl_afterstates: out_a and out_b must be 16-byte aligned");
     if ((uintptr_t)reward & 3u) return fail_msg(TPL_ERR_ARG, "tpl_afterstates: reward must be 4-byte aligned");
     AfterArgs p{};
     p.a = (const uint4*)plane_a; p.b = (const uint4*)plane_b; p.total = (uint32_t)(n * kActions);

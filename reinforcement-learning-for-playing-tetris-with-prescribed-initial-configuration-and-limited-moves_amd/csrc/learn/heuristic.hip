@@ -16,14 +16,15 @@
 // The other mapping -- a lane per board looping over the 40 actions -- unpacks once per board and has no cross-lane step, but
 // the move and the features, which are nine tenths of a pair's instructions, are per pair either way; it diverges on
 // nrot(cur), and has a fortieth of the lanes (DESIGN.md section 9 has the instruction counts).
-// r and l are values, never register indices (move_board's comment says why).
-#include "tpl_learn_internal.h"
-#include "tpl_mirror.h"
+//
+// That frame -- block prologue, lane decode, first move, arg-max and the winner's stores -- is written once, in
+// placement_policy<kPlies>; placement_act_kernel and placement_search_kernel are its two instances.  What a lane's first move
+// is worth is the one thing that differs: its own score at one ply, the best second placement's (second_ply) at two.
+#include "tpl_placement.h"
 
 namespace tpl_learn {
 namespace {
 
-constexpr int kActions = TPL_NUM_ACTIONS;
 constexpr int kFeatures = TPL_NUM_FEATURES;
 constexpr int kBoardsPerBlock = 8;
 constexpr int kActBlock = kBoardsPerBlock * kActions;        // 320 threads: five waves, eight whole boards
@@ -92,21 +93,14 @@ __device__ __forceinline__ void board_features(const uint32_t (&c)[tpl::kCols], 
     out.f[11] = depth;
 }
 
-// phi(s, a) of pair (i, a): the twelve features of what action a = 10 r + l leaves of state (A, B); all zero for a finished board
-__device__ __forceinline__ void pair_features(const uint4& A, const uint4& B, const tpl::ShapeWord* shape, uint32_t r, uint32_t l,
-                                              uint32_t L, uint32_t M, Features& out, uint32_t& cur) {
-    tpl::Board s;
-    tpl::unpack_board(A, B, s);
-    cur = s.window & 7u;
-    const bool running = s.state == tpl::ST_RUNNING;
-    bool topout;
-    const uint32_t n_clear = tpl::move_board(s, shape, r, l, L, M, topout);
+// phi of the board `s` that a move (or two) left: rows cleared, won, lost and board_features; all zero where `live` is false
+__device__ __forceinline__ void moved_features(const tpl::Board& s, uint32_t n_clear, bool live, Features& out) {
     board_features(s.c, out);
     out.f[0] = n_clear;
     out.f[1] = s.state == tpl::ST_WON ? 1u : 0u;
     out.f[2] = s.state >= tpl::ST_LOST_LIMIT ? 1u : 0u;
 #pragma unroll
-    for (int k = 0; k < kFeatures; ++k) out.f[k] = running ? out.f[k] : 0u;
+    for (int k = 0; k < kFeatures; ++k) out.f[k] = live ? out.f[k] : 0u;
 }
 
 struct FeatureArgs {
@@ -118,6 +112,7 @@ struct FeatureArgs {
     uint8_t* canonical;          // [n][40], optional
 };
 
+// phi(s, a) of every pair: the twelve features of what action a = 10 r + l leaves of state i; all zero for a finished board
 __global__ __launch_bounds__(kFeatureBlock) void placement_features_kernel(const FeatureArgs p) {
     __shared__ tpl::ShapeWord s_shape[32];
     if (threadIdx.x < 32) s_shape[threadIdx.x] = tpl::kShapeTable[threadIdx.x];
@@ -126,26 +121,18 @@ __global__ __launch_bounds__(kFeatureBlock) void placement_features_kernel(const
     if (j >= p.total) return;
     const uint32_t i = j / kActions, a = j - i * kActions;
     const uint32_t r = a / 10u, l = a - r * 10u;
-    Features phi;
+    tpl::Board s;
     uint32_t cur;
-    pair_features(p.a[i], p.b[i], s_shape, r, l, p.L, p.M, phi, cur);
+    bool running;
+    const uint32_t n_clear = first_move(p.a[i], p.b[i], s_shape, r, l, p.L, p.M, s, cur, running);
+    Features phi;
+    moved_features(s, n_clear, running, phi);
     uint2* rec = p.features + 3u * (size_t)j;
     rec[0] = make_uint2(phi.f[0] | (phi.f[1] << 16), phi.f[2] | (phi.f[3] << 16));
     rec[1] = make_uint2(phi.f[4] | (phi.f[5] << 16), phi.f[6] | (phi.f[7] << 16));
     rec[2] = make_uint2(phi.f[8] | (phi.f[9] << 16), phi.f[10] | (phi.f[11] << 16));
     if (p.canonical) p.canonical[j] = (uint8_t)canonical_action(cur, r, l);
 }
-
-struct ActArgs {
-    const uint4* a;              // [n]
-    const uint4* b;
-    uint32_t n;                  // boards; 40 n below 2^31
-    uint32_t L, M;
-    const float* weights;        // [P][12], P = ceil(n / per_member)
-    uint32_t per_member;         // boards per weight row, in [1, n]
-    uint8_t* action;             // [n]
-    float* score;                // [n], optional
-};
 
 // w . phi left to right in float32: every product and every sum rounded once -- contraction off, as afterstate_reward
 __device__ __forceinline__ float placement_score(const float (&w)[kFeatures], const Features& phi) {
@@ -163,47 +150,37 @@ __device__ __forceinline__ uint32_t ordered_bits(float x) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-__global__ __launch_bounds__(kActBlock) void placement_act_kernel(const ActArgs p) {
-    __shared__ tpl::ShapeWord s_shape[32];
-    __shared__ __attribute__((aligned(16))) float s_w[kBoardsPerBlock][kFeatures];
-    __shared__ unsigned long long s_best[kBoardsPerBlock];
-    const uint32_t first = blockIdx.x * kBoardsPerBlock;                // the block's boards: first .. first + 7
-    if (threadIdx.x < 32) s_shape[threadIdx.x] = tpl::kShapeTable[threadIdx.x];
-    if (threadIdx.x < kBoardsPerBlock) {
-        s_best[threadIdx.x] = 0ull;                                     // below every key: a key's high word has a bit set
-        const uint32_t board = min(first + threadIdx.x, p.n - 1u);
-        const float4* row = (const float4*)(p.weights + (size_t)(board / p.per_member) * kFeatures);
-        float4* dst = (float4*)s_w[threadIdx.x];
-        dst[0] = row[0]; dst[1] = row[1]; dst[2] = row[2];
+constexpr uint32_t kNoSecond = 255u;
+
+// The second ply with the known next piece: the best score among the distinct placements of s1's current piece on s1, the
+// board a first move that cleared n1 rows left (popped, still running), and the placement it belongs to.  Copies s1, moves and
+// scores once per distinct placement in ascending b = 10 r2 + l2 -- r2 below nrot, l2 up to 10 - w: 9, 17 or 34 trips, the
+// same for the 40 lanes of a board -- and keeps a running best under a strict > on the ordered key, so the lowest b survives.
+__device__ __forceinline__ float second_ply(const tpl::Board& s1, uint32_t n1, const tpl::ShapeWord* shape, uint32_t L, uint32_t M,
+                                            const float (&w)[kFeatures], uint32_t& second) {
+    const uint32_t nxt = s1.window & 7u;
+    const uint32_t last_rot = (kRotationMasks >> (2u * nxt)) & 3u;
+    uint32_t best_key = 0u, r2 = 0u, l2 = 0u;
+    float value = 0.0f;
+#pragma unroll 1
+    while (r2 <= last_rot) {
+        tpl::Board s2 = s1;
+        bool topout;
+        const uint32_t n2 = tpl::move_board(s2, shape, r2, l2, L, M, topout);
+        Features psi;
+        moved_features(s2, n1 + n2, true, psi);
+        const float sc = placement_score(w, psi);
+        const uint32_t key = ordered_bits(sc);                          // never 0, so the first trip is taken
+        if (key > best_key) { best_key = key; value = sc; second = 10u * r2 + l2; }
+        const uint32_t right = 9u - ((uint32_t)(kWidthsLess1 >> (2u * (nxt * 4u + r2))) & 3u);      // 10 - w
+        const bool wrap = l2 >= right;
+        l2 = wrap ? 0u : l2 + 1u;
+        r2 += wrap ? 1u : 0u;
     }
-    __syncthreads();
-    const uint32_t slot = threadIdx.x / kActions, a = threadIdx.x - slot * kActions;
-    const uint32_t r = a / 10u, l = a - r * 10u;
-    const uint32_t i = first + slot;
-    const bool valid = i < p.n;                                         // whole boards: all 40 lanes of a board agree
-    const uint32_t src = valid ? i : p.n - 1u;                          // past the end: the last board again, never written
-    Features phi;
-    uint32_t cur;
-    pair_features(p.a[src], p.b[src], s_shape, r, l, p.L, p.M, phi, cur);
-    float w[kFeatures];
-    const float4* row = (const float4*)s_w[slot];
-#pragma unroll
-    for (int q = 0; q < kFeatures / 4; ++q) {
-        const float4 v = row[q];
-        w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
-    }
-    const float score = placement_score(w, phi);
-    const bool contends = valid && canonical_action(cur, r, l) == a;
-    const unsigned long long key = ((unsigned long long)ordered_bits(score) << 32) | (uint32_t)(kActions - 1 - a);
-    if (contends) atomicMax(&s_best[slot], key);
-    __syncthreads();
-    if (contends && s_best[slot] == key) {                              // one lane per board: the keys of a board are distinct
-        p.action[i] = (uint8_t)a;
-        if (p.score) p.score[i] = score;
-    }
+    return value;
 }
 
-struct SearchArgs {
+struct PolicyArgs {
     const uint4* a;              // [n]
     const uint4* b;
     uint32_t n;                  // boards; 40 n below 2^31
@@ -211,18 +188,15 @@ struct SearchArgs {
     const float* weights;        // [P][12], P = ceil(n / per_member)
     uint32_t per_member;         // boards per weight row, in [1, n]
     uint8_t* action;             // [n]
-    uint8_t* second;             // [n], optional
+    uint8_t* second;             // [n], optional; null at one ply
     float* score;                // [n], optional
 };
 
-constexpr uint32_t kNoSecond = 255u;
-
-// Two plies with the known next piece: placement_act_kernel's block, lane mapping and arg-max, but a lane's value is the best
-// of the distinct placements of `nxt` on the board its own first move leaves.  The lane makes its first move once and keeps
-// s1 in registers; the loop below copies it, moves and scores once per distinct second placement (9, 17 or 34 trips, the same
-// for the 40 lanes of a board) and keeps a running best under a strict > on the ordered key, so the lowest b survives.  Alias
-// lanes and lanes whose first move ended the game (or whose board is finished) skip the loop: their value is the one-ply score.
-__global__ __launch_bounds__(kActBlock) void placement_search_kernel(const SearchArgs p) {
+// The policy of kPlies plies on the block's eight boards (the header comment has the frame).  A lane's value is the score of
+// what its first move leaves; at two plies, where that move leaves the game running, it is second_ply's instead.  Alias lanes
+// and lanes whose first move ended the game (or whose board is finished: all-zero features) keep the one-ply score.
+template <int kPlies>
+__device__ __forceinline__ void placement_policy(const PolicyArgs& p) {
     __shared__ tpl::ShapeWord s_shape[32];
     __shared__ __attribute__((aligned(16))) float s_w[kBoardsPerBlock][kFeatures];
     __shared__ unsigned long long s_best[kBoardsPerBlock];
@@ -241,6 +215,14 @@ __global__ __launch_bounds__(kActBlock) void placement_search_kernel(const Searc
     const uint32_t i = first + slot;
     const bool valid = i < p.n;                                         // whole boards: all 40 lanes of a board agree
     const uint32_t src = valid ? i : p.n - 1u;                          // past the end: the last board again, never written
+
+    tpl::Board s1;
+    uint32_t cur;
+    bool running;
+    const uint32_t n1 = first_move(p.a[src], p.b[src], s_shape, r, l, p.L, p.M, s1, cur, running);
+    const bool contends = valid && canonical_action(cur, r, l) == a;
+    // the weight row, read back here and not ahead of the first move: there both kernels measured 2 % slower on an MI355X
+    // at the same instruction counts (profiles/learner/README.md)
     float w[kFeatures];
     const float4* row = (const float4*)s_w[slot];
 #pragma unroll
@@ -248,53 +230,19 @@ __global__ __launch_bounds__(kActBlock) void placement_search_kernel(const Searc
         const float4 v = row[q];
         w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
     }
-
-    // the first ply: tpl_afterstates' move and pop
-    tpl::Board s1;
-    tpl::unpack_board(p.a[src], p.b[src], s1);
-    const uint32_t cur = s1.window & 7u;
-    const bool running = s1.state == tpl::ST_RUNNING;
-    bool topout;
-    const uint32_t n1 = tpl::move_board(s1, s_shape, r, l, p.L, p.M, topout);
-    tpl::next_window(s1, false, 0);
-    const uint32_t nxt = s1.window & 7u;
-    const bool contends = valid && canonical_action(cur, r, l) == a;
-    const bool goes_on = running && s1.state == tpl::ST_RUNNING;
+    bool goes_on = false;
+    if constexpr (kPlies == 2) {
+        tpl::next_window(s1, false, 0);                                 // tpl_afterstates' pop: the next piece becomes current
+        goes_on = contends && running && s1.state == tpl::ST_RUNNING;
+    }
 
     float value;
     uint32_t second = kNoSecond;
-    if (contends && goes_on) {
-        // the distinct placements of nxt in ascending b = 10 r2 + l2: r2 below nrot(nxt), l2 up to 10 - w(nxt, r2)
-        const uint32_t last_rot = (kRotationMasks >> (2u * nxt)) & 3u;
-        uint32_t best_key = 0u, r2 = 0u, l2 = 0u;
-        value = 0.0f;
-#pragma unroll 1
-        while (r2 <= last_rot) {
-            tpl::Board s2 = s1;
-            bool topout2;
-            const uint32_t n2 = tpl::move_board(s2, s_shape, r2, l2, p.L, p.M, topout2);
-            Features psi;
-            board_features(s2.c, psi);
-            psi.f[0] = n1 + n2;
-            psi.f[1] = s2.state == tpl::ST_WON ? 1u : 0u;
-            psi.f[2] = s2.state >= tpl::ST_LOST_LIMIT ? 1u : 0u;
-            const float sc = placement_score(w, psi);
-            const uint32_t key = ordered_bits(sc);                      // never 0, so the first trip is taken
-            if (key > best_key) { best_key = key; value = sc; second = 10u * r2 + l2; }
-            const uint32_t right = 9u - ((uint32_t)(kWidthsLess1 >> (2u * (nxt * 4u + r2))) & 3u);      // 10 - w
-            const bool wrap = l2 >= right;
-            l2 = wrap ? 0u : l2 + 1u;
-            r2 += wrap ? 1u : 0u;
-        }
+    if (goes_on) {
+        value = second_ply(s1, n1, s_shape, p.L, p.M, w, second);
     } else {
-        // the one-ply features of (s, a): the first move ended the game, or the board was finished before it (all zero)
         Features phi;
-        board_features(s1.c, phi);
-        phi.f[0] = n1;
-        phi.f[1] = s1.state == tpl::ST_WON ? 1u : 0u;
-        phi.f[2] = s1.state >= tpl::ST_LOST_LIMIT ? 1u : 0u;
-#pragma unroll
-        for (int k = 0; k < kFeatures; ++k) phi.f[k] = running ? phi.f[k] : 0u;
+        moved_features(s1, n1, running, phi);
         value = placement_score(w, phi);
     }
     const unsigned long long key = ((unsigned long long)ordered_bits(value) << 32) | (uint32_t)(kActions - 1 - a);
@@ -302,10 +250,13 @@ __global__ __launch_bounds__(kActBlock) void placement_search_kernel(const Searc
     __syncthreads();
     if (contends && s_best[slot] == key) {                              // one lane per board: the keys of a board are distinct
         p.action[i] = (uint8_t)a;
-        if (p.second) p.second[i] = (uint8_t)second;
+        if (kPlies == 2 && p.second) p.second[i] = (uint8_t)second;
         if (p.score) p.score[i] = value;
     }
 }
+
+__global__ __launch_bounds__(kActBlock) void placement_act_kernel(const PolicyArgs p) { placement_policy<1>(p); }
+__global__ __launch_bounds__(kActBlock) void placement_search_kernel(const PolicyArgs p) { placement_policy<2>(p); }
 
 }  // namespace
 }  // namespace tpl_learn
@@ -314,15 +265,22 @@ using namespace tpl_learn;
 
 namespace {
 
-// the checks the entry points share; `name` leads the message
-int check_planes(const char* name, const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M) {
-    if (!plane_a || !plane_b) return fail_msg(TPL_ERR_ARG, "%s: null pointer", name);
-    if (n < 1) return fail_msg(TPL_ERR_ARG, "%s: n must be positive", name);
-    if (n >= (((int64_t)1 << 31) + kActions - 1) / kActions)
-        return fail_msg(TPL_ERR_ARG, "%s: n too large (40 n must stay below 2^31)", name);
-    if (L < 1 || L > 255 || M < 1 || M > 255) return fail_msg(TPL_ERR_ARG, "%s: L and M must be in [1, 255]", name);
-    if (((uintptr_t)plane_a & 15u) || ((uintptr_t)plane_b & 15u))
-        return fail_msg(TPL_ERR_ARG, "%s: planes must be 16-byte aligned", name);
+// what tpl_placement_act (plies = 1, second = null) and tpl_placement_search (plies = 2) share: the checks and the launch
+int launch_policy(const char* name, int plies, const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M,
+                  const float* weights, int64_t boards_per_member, uint8_t* action, uint8_t* second, float* score, void* stream) {
+    if (const int rc = check_planes(name, plane_a, plane_b, n, L, M)) return rc;
+    if (!weights || !action) return fail_msg(TPL_ERR_ARG, "%s: null pointer (weights and action are required)", name);
+    if (boards_per_member < 1) return fail_msg(TPL_ERR_ARG, "%s: boards_per_member must be positive", name);
+    if ((uintptr_t)weights & 15u) return fail_msg(TPL_ERR_ARG, "%s: weights must be 16-byte aligned", name);
+    if ((uintptr_t)score & 3u) return fail_msg(TPL_ERR_ARG, "%s: score must be 4-byte aligned", name);
+    PolicyArgs p{};
+    p.a = (const uint4*)plane_a; p.b = (const uint4*)plane_b; p.n = (uint32_t)n;
+    p.L = (uint32_t)L; p.M = (uint32_t)M; p.weights = weights;
+    p.per_member = (uint32_t)(boards_per_member < n ? boards_per_member : n);     // anything above n is the single-policy case
+    p.action = action; p.second = second; p.score = score;
+    const dim3 grid((p.n + kBoardsPerBlock - 1) / kBoardsPerBlock), block(kActBlock);
+    hipLaunchKernelGGL(plies == 2 ? placement_search_kernel : placement_act_kernel, grid, block, 0, (hipStream_t)stream, p);
+    TPL_LEARN_HIP(hipGetLastError());
     return TPL_OK;
 }
 
@@ -345,38 +303,11 @@ extern "C" int tpl_placement_features(const void* plane_a, const void* plane_b, 
 
 extern "C" int tpl_placement_act(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const float* weights,
                                  int64_t boards_per_member, uint8_t* action, float* score, void* stream) {
-    const char* name = "tpl_placement_act";
-    if (const int rc = check_planes(name, plane_a, plane_b, n, L, M)) return rc;
-    if (!weights || !action) return fail_msg(TPL_ERR_ARG, "%s: null pointer (weights and action are required)", name);
-    if (boards_per_member < 1) return fail_msg(TPL_ERR_ARG, "%s: boards_per_member must be positive", name);
-    if ((uintptr_t)weights & 15u) return fail_msg(TPL_ERR_ARG, "%s: weights must be 16-byte aligned", name);
-    if ((uintptr_t)score & 3u) return fail_msg(TPL_ERR_ARG, "%s: score must be 4-byte aligned", name);
-    ActArgs p{};
-    p.a = (const uint4*)plane_a; p.b = (const uint4*)plane_b; p.n = (uint32_t)n;
-    p.L = (uint32_t)L; p.M = (uint32_t)M; p.weights = weights;
-    p.per_member = (uint32_t)(boards_per_member < n ? boards_per_member : n);     // anything above n is the single-policy case
-    p.action = action; p.score = score;
-    const dim3 grid((p.n + kBoardsPerBlock - 1) / kBoardsPerBlock), block(kActBlock);
-    hipLaunchKernelGGL(placement_act_kernel, grid, block, 0, (hipStream_t)stream, p);
-    TPL_LEARN_HIP(hipGetLastError());
-    return TPL_OK;
+    return launch_policy("tpl_placement_act", 1, plane_a, plane_b, n, L, M, weights, boards_per_member, action, nullptr, score, stream);
 }
 
 extern "C" int tpl_placement_search(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const float* weights,
                                     int64_t boards_per_member, uint8_t* action, uint8_t* second, float* score, void* stream) {
-    const char* name = "tpl_placement_search";
-    if (const int rc = check_planes(name, plane_a, plane_b, n, L, M)) return rc;
-    if (!weights || !action) return fail_msg(TPL_ERR_ARG, "%s: null pointer (weights and action are required)", name);
-    if (boards_per_member < 1) return fail_msg(TPL_ERR_ARG, "%s: boards_per_member must be positive", name);
-    if ((uintptr_t)weights & 15u) return fail_msg(TPL_ERR_ARG, "%s: weights must be 16-byte aligned", name);
-    if ((uintptr_t)score & 3u) return fail_msg(TPL_ERR_ARG, "%s: score must be 4-byte aligned", name);
-    SearchArgs p{};
-    p.a = (const uint4*)plane_a; p.b = (const uint4*)plane_b; p.n = (uint32_t)n;
-    p.L = (uint32_t)L; p.M = (uint32_t)M; p.weights = weights;
-    p.per_member = (uint32_t)(boards_per_member < n ? boards_per_member : n);     // anything above n is the single-policy case
-    p.action = action; p.second = second; p.score = score;
-    const dim3 grid((p.n + kBoardsPerBlock - 1) / kBoardsPerBlock), block(kActBlock);
-    hipLaunchKernelGGL(placement_search_kernel, grid, block, 0, (hipStream_t)stream, p);
-    TPL_LEARN_HIP(hipGetLastError());
-    return TPL_OK;
+    return launch_policy("tpl_placement_search", 2, plane_a, plane_b, n, L, M, weights, boards_per_member, action, second, score,
+                         stream);
 }

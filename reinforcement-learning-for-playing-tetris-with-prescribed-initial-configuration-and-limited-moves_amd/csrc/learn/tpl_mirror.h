@@ -8,8 +8,7 @@
 //
 // Every function takes `flip` and applies it with selects: a wave whose lanes disagree runs one straight-line path.
 //
-// canonical_action -- which of the 40 actions are one placement -- reads the same packed widths and lives here, shared by the
-// afterstate enumeration and the placement policy (afterstates.hip, heuristic.hip).
+// The packed widths and rotation masks below also serve canonical_action (tpl_placement.h).
 #pragma once
 
 #include "../tpl_device.h"
@@ -44,13 +43,6 @@ constexpr bool table_repeats_with_the_rotation_count() {
     return true;
 }
 static_assert(table_repeats_with_the_rotation_count(), "kRotations does not match the shape table");
-
-// canonical[a] = 10 (r mod nrot(cur)) + min(l, 10 - w(cur, r)) for a = 10 r + l, r < 4, l < 10
-__host__ __device__ __forceinline__ uint32_t canonical_action(uint32_t cur, uint32_t r, uint32_t l) {
-    const uint32_t right = 9u - ((uint32_t)(kWidthsLess1 >> (2u * (cur * 4u + r))) & 3u);      // 10 - w
-    const uint32_t rc = r & ((kRotationMasks >> (2u * cur)) & 3u);
-    return 10u * rc + (l < right ? l : right);
-}
 
 // a' = 10 ((4 - r) & 3) + (10 - w - min(l, 10 - w)) for a = 10 r' + l, r = r' & 3, w the width of entry [cur][r]; below 40
 __device__ __forceinline__ uint32_t mirror_action(uint32_t a, uint32_t cur, bool flip) {

@@ -24,7 +24,7 @@ import torch
 
 from . import _learn_lib
 from ._learn_lib import FEATURE_NAMES, NUM_ACTIONS, NUM_FEATURES, check
-from .lookahead import _MAX_BOARDS, _state_ptrs
+from .lookahead import _MAX_BOARDS, _ptr, _source_planes, _state_ptrs
 
 __all__ = ["FEATURE_NAMES", "placement_features", "HeuristicPolicy", "evaluate_heuristic", "tune_heuristic"]
 
@@ -34,29 +34,12 @@ def placement_features(env, states_a: Optional[torch.Tensor] = None, states_b: O
     [K, 4] plane pairs as env.expand_states takes them, under env.L and env.M.  Returns (features int16 [K, 40, 12], canonical
     uint8 [K, 40]); entry [i, a] belongs to action a = 10 r + l played from state i, a == canonical[i, a] marks the distinct
     placements, and a finished board's features are all zero."""
-    if (states_a is None) != (states_b is None):
-        raise ValueError("states_a and states_b go together")
-    if states_a is not None:
-        for t in (states_a, states_b):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != 4:
-                raise ValueError("states_a / states_b must be int32 [K, 4] tensors")
-        if states_a.shape != states_b.shape:
-            raise ValueError("states_a / states_b must be int32 [K, 4] tensors of equal shape")
-        k = int(states_a.shape[0])
-    else:
-        k = int(env.num_envs)
-    if not 1 <= k <= _MAX_BOARDS:
-        raise ValueError(f"placement_features takes 1 .. {_MAX_BOARDS} states (40 K must stay below 2^31)")
+    k, src_a, src_b = _source_planes(env, states_a, states_b, "placement_features")
     d = env.device
-    if states_a is not None:
-        states_a, states_b = states_a.to(d).contiguous(), states_b.to(d).contiguous()
-        src = (states_a.data_ptr(), states_b.data_ptr())
-    else:
-        src = _state_ptrs(env)
     features = torch.empty((k, NUM_ACTIONS, NUM_FEATURES), dtype=torch.int16, device=d)
     canonical = torch.empty((k, NUM_ACTIONS), dtype=torch.uint8, device=d)
     stream = torch._C._cuda_getCurrentRawStream(d.index)
-    check(_learn_lib.lib().tpl_placement_features(src[0], src[1], k, env.L, env.M, features.data_ptr(), canonical.data_ptr(), stream))
+    check(_learn_lib.lib().tpl_placement_features(_ptr(src_a), _ptr(src_b), k, env.L, env.M, features.data_ptr(), canonical.data_ptr(), stream))
     return features, canonical
 
 
@@ -150,15 +133,10 @@ class HeuristicPolicy:
         if second is not None:
             env._own(second, torch.uint8, "second")
         stream = torch._C._cuda_getCurrentRawStream(env.device.index)
-        if self.depth == 2:
-            check(_learn_lib.lib().tpl_placement_search(self._planes[0], self._planes[1], env.num_envs, env.L, env.M,
-                                                        self.weights.data_ptr(), self.boards_per_member, out.data_ptr(),
-                                                        None if second is None else second.data_ptr(),
-                                                        None if score is None else score.data_ptr(), stream))
-            return out
-        check(_learn_lib.lib().tpl_placement_act(self._planes[0], self._planes[1], env.num_envs, env.L, env.M,
-                                                 self.weights.data_ptr(), self.boards_per_member, out.data_ptr(),
-                                                 None if score is None else score.data_ptr(), stream))
+        lib = _learn_lib.lib()
+        entry, extra = (lib.tpl_placement_search, (_ptr(second),)) if self.depth == 2 else (lib.tpl_placement_act, ())
+        check(entry(self._planes[0], self._planes[1], env.num_envs, env.L, env.M, self.weights.data_ptr(), self.boards_per_member,
+                    out.data_ptr(), *extra, _ptr(score), stream))
         return out
 
 

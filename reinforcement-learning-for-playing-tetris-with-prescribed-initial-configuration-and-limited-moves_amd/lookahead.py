@@ -30,12 +30,40 @@ def _state_ptrs(env):
     return pa.value, pb.value
 
 
-def _enumerate(env, src_a: int, src_b: int, k: int, out_a, out_b, reward, done, cleared, canonical) -> None:
-    """tpl_afterstates of k states at device addresses (src_a, src_b) under env's L, M and reward parameters."""
-    ptr = lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr())
+def _ptr(t):
+    """The device address of a tensor; an address or None as it is."""
+    return t if t is None or isinstance(t, int) else t.data_ptr()
+
+
+def _source_planes(env, states_a, states_b, who: str, into=None):
+    """(K, plane_a, plane_b) of the states that `who` reads: int32 [K, 4] plane pairs as env.expand_states takes them, moved to
+    env.device, or env's resident boards (both None: K = env.num_envs, read in place).  A plane is a tensor where it was given
+    -- the caller holds it until its launch is enqueued -- and a device address where it is resident: _ptr takes either.
+    `into` (afterstates' destination environment) must hold 40 K boards: a condition on K, refused before the device is asked
+    for anything."""
+    if (states_a is None) != (states_b is None):
+        raise ValueError("states_a and states_b go together")
+    if states_a is not None:
+        for t in (states_a, states_b):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != 4:
+                raise ValueError("states_a / states_b must be int32 [K, 4] tensors")
+        if states_a.shape != states_b.shape:
+            raise ValueError("states_a / states_b must be int32 [K, 4] tensors of equal shape")
+    k = int(env.num_envs if states_a is None else states_a.shape[0])
+    if not 1 <= k <= _MAX_BOARDS:
+        raise ValueError(f"{who} takes 1 .. {_MAX_BOARDS} states (40 K must stay below 2^31)")
+    if into is not None and (into is env or into.num_envs != NUM_ACTIONS * k or into.device != env.device):
+        raise ValueError(f"into must be another environment of exactly {NUM_ACTIONS * k} boards on {env.device}")
+    if states_a is None:
+        return (k, *_state_ptrs(env))
+    return k, states_a.to(env.device).contiguous(), states_b.to(env.device).contiguous()
+
+
+def _enumerate(env, src_a, src_b, k: int, out_a, out_b, reward, done, cleared, canonical) -> None:
+    """tpl_afterstates of k states at (src_a, src_b) under env's L, M and reward parameters; tensors or device addresses."""
     stream = torch._C._cuda_getCurrentRawStream(env.device.index)
-    check(_learn_lib.lib().tpl_afterstates(src_a, src_b, k, env.L, env.M, *env.reward_params, ptr(out_a), ptr(out_b), ptr(reward),
-                                           ptr(done), ptr(cleared), ptr(canonical), stream))
+    check(_learn_lib.lib().tpl_afterstates(_ptr(src_a), _ptr(src_b), k, env.L, env.M, *env.reward_params, _ptr(out_a), _ptr(out_b),
+                                           _ptr(reward), _ptr(done), _ptr(cleared), _ptr(canonical), stream))
 
 
 def afterstates(env, states_a: Optional[torch.Tensor] = None, states_b: Optional[torch.Tensor] = None, with_states: bool = True,
@@ -47,27 +75,8 @@ def afterstates(env, states_a: Optional[torch.Tensor] = None, states_b: Optional
     [K, 40]; entry [i, a] belongs to action a = 10 r + l played from state i, and a == canonical[i, a] marks the distinct
     placements.  `into`: a BatchedTetris of exactly 40 K boards whose resident planes receive the afterstates (board 40 i + a;
     zero copy, its counters and step clock are not touched); the dict then holds no state tensors."""
-    if (states_a is None) != (states_b is None):
-        raise ValueError("states_a and states_b go together")
-    if states_a is not None:
-        for t in (states_a, states_b):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != 4:
-                raise ValueError("states_a / states_b must be int32 [K, 4] tensors")
-        if states_a.shape != states_b.shape:
-            raise ValueError("states_a / states_b must be int32 [K, 4] tensors of equal shape")
-        k = int(states_a.shape[0])
-    else:
-        k = int(env.num_envs)
-    if not 1 <= k <= _MAX_BOARDS:
-        raise ValueError(f"afterstates takes 1 .. {_MAX_BOARDS} states (40 K must stay below 2^31)")
-    if into is not None and (into is env or into.num_envs != NUM_ACTIONS * k or into.device != env.device):
-        raise ValueError(f"into must be another environment of exactly {NUM_ACTIONS * k} boards on {env.device}")
+    k, src_a, src_b = _source_planes(env, states_a, states_b, "afterstates", into)
     d = env.device
-    if states_a is not None:
-        states_a, states_b = states_a.to(d).contiguous(), states_b.to(d).contiguous()
-        src = (states_a.data_ptr(), states_b.data_ptr())
-    else:
-        src = _state_ptrs(env)
     out = dict(reward=torch.empty((k, NUM_ACTIONS), dtype=torch.float32, device=d))
     for name in ("done", "cleared", "canonical"):
         out[name] = torch.empty((k, NUM_ACTIONS), dtype=torch.uint8, device=d)
@@ -78,7 +87,7 @@ def afterstates(env, states_a: Optional[torch.Tensor] = None, states_b: Optional
         out["states_a"] = torch.empty((k, NUM_ACTIONS, 4), dtype=torch.int32, device=d)
         out["states_b"] = torch.empty((k, NUM_ACTIONS, 4), dtype=torch.int32, device=d)
         planes = (out["states_a"], out["states_b"])
-    _enumerate(env, src[0], src[1], k, planes[0], planes[1], out["reward"], out["done"], out["cleared"], out["canonical"])
+    _enumerate(env, src_a, src_b, k, planes[0], planes[1], out["reward"], out["done"], out["cleared"], out["canonical"])
     return out
 
 
