@@ -2,7 +2,7 @@
  * tpl_learn.h -- C ABI of the learner library (libtpl_learn.so): a packed replay ring on the device, its samplers (uniform,
  * prioritized, n-step, each optionally mirrored), device-side packing of a PolicyMLP's parameters into the three policy
  * images of libtetris_piclim.so, the enumeration of a board's 40 afterstates, and board features of every placement with a
- * linear placement policy on them.
+ * linear placement policy on them: one ply, two plies, or a beam over the known piece window.
  *
  * Conventions (as include/tetris_piclim.h)
  *   - every function returns 0 on success or a negative tpl_status (TPL_ERR_ARG, TPL_ERR_HIP, ...);
@@ -261,7 +261,8 @@ int tpl_placement_act(const void* plane_a, const void* plane_b, int64_t n, int32
                       int64_t boards_per_member, uint8_t* action, float* score, void* stream);
 
 /* Two plies with the known next piece.  Window entry 1 of a state is the piece after the current one, and an afterstate's window is
- * good for exactly these two entries (above), so two plies is the deepest search this library makes exactly without a pool.
+ * good for exactly these two entries (above), so two plies is the deepest search from an AFTERSTATE that is exact without a pool
+ * (tpl_placement_beam below goes deeper from environment states).
  * For a state s with weight row w[12], cur = window entry 0 of s, nxt = window entry 1:
  *   Finished board (state(s) != running): action 0, second 255, score = the score of twelve zeros -- the one-ply rule.
  *   Running board: for every distinct first placement a (a == canonical(cur, a)), move_board(s, a) exactly as tpl_afterstates makes
@@ -282,6 +283,47 @@ int tpl_placement_act(const void* plane_a, const void* plane_b, int64_t n, int32
  * not given is not written.  Refused before any HIP call: everything tpl_placement_act refuses. */
 int tpl_placement_search(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const float* weights,
                          int64_t boards_per_member, uint8_t* action, uint8_t* second, float* score, void* stream);
+
+/* Beam search over the known piece window.  An afterstate's window is good for two entries, but an ENVIRONMENT STATE carries more:
+ * at moves = m the first 12 - (m mod 10) entries of its window are the episode's true next pieces (the refill at a multiple of ten
+ * loads a word whose first two entries are the two that were left) -- never fewer than three, twelve right after a reset or a
+ * refill.  tpl_placement_beam searches them with a beam: exhaustive depth costs 34^D moves, a beam of width W 34 (1 + W (D - 1)).
+ *
+ * For a state s with weight row w[12], a depth D in [1, TPL_BEAM_MAX_DEPTH] and a width W in [1, TPL_BEAM_MAX_WIDTH]:
+ *   Finished board (state(s) != running): action 0, every plan entry 255, score = the score of twelve zeros -- the one-ply rule.
+ *   Running board: the effective depth is d = min(D, 12 - moves(s) mod 10), from the state's bits as they stand (pool or not).
+ *   A NODE is a board (its window popped once per move made, by next_window(s, false, 0) as tpl_afterstates does), the rows cleared
+ *   on the way c, the path of placements, and a value.  Beam_0 is the root alone (c = 0, empty path).
+ *   For ply j = 1 .. d the CANDIDATES are listed in order: over the nodes q = 0, 1, ... of Beam_{j-1} in their stored order,
+ *     a node whose state is not running gives one candidate, itself, value and path unchanged (index 0 within the node);
+ *     a running node gives one candidate per distinct placement b of its current piece (b == canonical(cur, b), cur = window entry 0
+ *     of the node; cur = 7 is what move_board and the shape table make of it: O's nine placements) in ascending b: the child is
+ *     move_board(node, b) exactly as tpl_afterstates makes it, then the pop; with n the rows it cleared,
+ *       psi = (c + n, won, lost, features 3..11 of the child's board)      -- feature 0 is at most 48 and converts exactly
+ *       value = the score rule above on psi: left to right in float32, every product and sum rounded once, never fused;
+ *     the child's c is c + n and its path the node's with b appended.
+ *   Candidates are ordered by (value descending, candidate index ascending); -0 and +0 tie.
+ *   Beam_j = the min(W, count) best candidates STORED IN CANDIDATE ORDER -- a stable compaction, not a sort -- so every beam is in
+ *   lexicographic order of its paths, and ties fall as in tpl_placement_act and tpl_placement_search.
+ *   Choice: the best node of Beam_d under the same order: action = the first placement of its path, score = its value,
+ *   plan[0 .. D) = its path padded with 255.
+ * Consequences:
+ *   D = 1, any W: action and score are tpl_placement_act's, bit for bit.
+ *   D = 2, W >= 34: action, plan[1] and score are tpl_placement_search's action, second and score, bit for bit, on every state.
+ *   Playing `plan` move by move on a non-auto-reset environment without a pool (no refill: the same pop) reaches a board whose psi
+ *   (rows cleared in total, won, lost, features 3..11) scores `score` under w, bit for bit.
+ * The weight rows of a population and THE FINITENESS CAVEAT are tpl_placement_act's.  Boards that different paths reach are not
+ * merged, and the pool is never read for pieces beyond the window. */
+#define TPL_BEAM_MAX_DEPTH 12
+#define TPL_BEAM_MAX_WIDTH 64
+
+/* One kernel, a workgroup per board, both beams and the candidate keys in LDS (csrc/learn/beam.hip): 32 bytes read per board,
+ * action u8 [n], plan u8 [n][depth] (optional), score f32 [n] (optional) written; an output that is not given is not written.
+ * Refused before any HIP call: everything tpl_placement_act refuses, depth outside [1, TPL_BEAM_MAX_DEPTH], width outside
+ * [1, TPL_BEAM_MAX_WIDTH]. */
+int tpl_placement_beam(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const float* weights,
+                       int64_t boards_per_member, int32_t depth, int32_t width, uint8_t* action, uint8_t* plan,
+                       float* score, void* stream);
 
 #ifdef __cplusplus
 }

@@ -21,7 +21,7 @@ from ._lib import TplError, _hipcc
 _LEARN_CSRC = os.path.join(_lib._CSRC, "learn")
 LEARN_LIB_PATH = os.path.join(_lib._LIBDIR, "libtpl_learn.so")
 _UNITS = [os.path.join(_LEARN_CSRC, f) for f in ("replay.hip", "pack.hip", "priority.hip", "afterstates.hip",
-                                                      "heuristic.hip")]
+                                                      "beam.hip", "heuristic.hip")]
 
 # entry points declared in include/tpl_learn.h (tests check that the .so exports every one of them)
 LEARN_SYMBOLS = [
@@ -29,9 +29,10 @@ LEARN_SYMBOLS = [
     "tpl_learn_image_bytes", "tpl_learn_pack", "tpl_priority_tree_bytes", "tpl_priority_init", "tpl_priority_push",
     "tpl_priority_update", "tpl_replay_sample_prioritized", "tpl_priority_target", "tpl_replay_sample_nstep",
     "tpl_replay_sample_mirror", "tpl_mirror_states", "tpl_afterstates", "tpl_canonical_action", "tpl_placement_features",
-    "tpl_placement_act", "tpl_placement_search",
+    "tpl_placement_act", "tpl_placement_search", "tpl_placement_beam",
 ]
 NSTEP_MAX = 16
+BEAM_MAX_DEPTH, BEAM_MAX_WIDTH = 12, 64
 MIRROR_MODES = {False: 0, True: 1, "always": 2}          # sample(mirror=...) -> tpl_mirror_mode
 
 IMAGE_KINDS = {"bf16": 0, "f32": 1, "split": 2}
@@ -133,10 +134,11 @@ def lib() -> C.CDLL:
     L.tpl_placement_features.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp]
     L.tpl_placement_act.argtypes = [vp, vp, i64, i32, i32, vp, i64, vp, vp, vp]
     L.tpl_placement_search.argtypes = [vp, vp, i64, i32, i32, vp, i64, vp, vp, vp, vp]
+    L.tpl_placement_beam.argtypes = [vp, vp, i64, i32, i32, vp, i64, i32, i32, vp, vp, vp, vp]
     for name in ("tpl_replay_push", "tpl_replay_sample", "tpl_learn_pack", "tpl_priority_init", "tpl_priority_push",
                  "tpl_priority_update", "tpl_replay_sample_prioritized", "tpl_replay_sample_nstep", "tpl_replay_sample_mirror",
                  "tpl_mirror_states", "tpl_afterstates", "tpl_placement_features", "tpl_placement_act",
-                 "tpl_placement_search"):
+                 "tpl_placement_search", "tpl_placement_beam"):
         getattr(L, name).restype = i32
     _handle = L
     return L
@@ -489,6 +491,19 @@ def search_choice(phi1, done1, distinct1, phi2, distinct2, weights):
     action = np.argmax(masked == masked.max(axis=1, keepdims=True), axis=1)
     at = np.arange(k)
     return action.astype(np.uint8), second[at, action].astype(np.uint8), value[at, action]
+
+
+def beam_select(values, width: int) -> np.ndarray:
+    """The one non-obvious step of the beam rule of include/tpl_learn.h (tpl_placement_beam): of candidates with float32
+    `values` [count], listed in candidate order, the indices of the min(width, count) best under (value descending, index
+    ascending; -0 and +0 tie), IN CANDIDATE ORDER (int64, ascending) -- a stable compaction, not a sort."""
+    v = np.asarray(values, dtype=np.float32)
+    if v.ndim != 1 or v.size < 1:
+        raise ValueError("values must be a non-empty vector")
+    if isinstance(width, bool) or int(width) != width or not 1 <= int(width) <= BEAM_MAX_WIDTH:
+        raise ValueError(f"width must be an integer in [1, {BEAM_MAX_WIDTH}]")
+    order = np.argsort(-(v + np.float32(0.0)), kind="stable")  # x + 0 makes -0 a +0; stable: the lower index first among equals
+    return np.sort(order[:int(width)]).astype(np.int64)
 
 
 # ------------------------------------------------------------------------------------------------ device packing

@@ -1,0 +1,295 @@
+// beam.hip -- a beam search over the known piece window with the linear placement policy's score: tpl_placement_beam
+// (include/tpl_learn.h states the rule).
+//
+// An environment state's window holds the episode's true next pieces, 12 - moves mod 10 of them, so a search from it may go
+// that deep.  Exhaustive depth costs 34^D moves; a beam of width W keeps the W best nodes of every ply and costs
+// 34 (1 + W (D - 1)).
+//
+// Mapping: ONE BOARD PER WORKGROUP of 256 threads (four waves).  Both beams (the parents of a ply and its children: packed
+// 32-byte boards, rows cleared so far, value, path) and the candidate keys live in LDS, 26 KB in all, so six groups share a
+// CU.  All nodes of ply j were popped j times from one root, so they have one current piece and one count S of distinct
+// placements (9, 17 or 34): candidate (node q, k-th distinct placement) is slot q S + k, slots in candidate order, and the
+// lanes take slots t, t + 256, ...  A ply is three phases:
+//   A  every lane moves, scores and keys its slots:  key = ordered_bits(value) << 32 | (4095 - slot)  -- the rule's total order
+//      (value descending, candidate index ascending) as one unsigned maximum, every key distinct and none zero.  A finished
+//      parent's slot 0 carries its own value; its other slots hold 0, below every key.
+//   B  selection: W rounds of a maximum, each taking the largest key not yet taken into sel[round]; after min(W, count) rounds
+//      sel[] holds the kept keys, best first.  Every lane caches the largest of its own slots and every wave the largest of
+//      its lanes (a shuffle reduction) in one LDS word; a round reads the four words, and only the wave whose key was taken --
+//      the keys are distinct, so it is one wave and one lane of it -- rescans its slots (one lane, up to nine LDS reads) and
+//      reduces again (six shuffle steps on 64 bits).  So a round is four broadcast reads and a barrier for three waves and that
+//      rescan and reduction for the fourth; no round is a pass of all lanes over the keys.  (The same rounds with an LDS
+//      atomicMax from every lane measured ten times the two-ply kernel at D = 2, W = 34 on an MI355X, where both make the same
+//      moves: 256 atomics on one address a round.  Counting every key against every other is count^2; a radix select is six
+//      passes of histogram atomics that all land in the few bins of the common exponent.)
+//   C  compaction in candidate order: lane e < kept owns sel[e]; its place in the new beam is the number of kept keys with a
+//      lower slot (at most 64 broadcast reads of the low words), it makes its move AGAIN (so no board but the parents' is
+//      kept for the 2,176 candidates), pops the window, packs the child and writes it there.  Lane 0 owns sel[0], the best.
+// After the last ply lane 0's node is the choice.  Nothing but the outputs goes to memory.
+#include "tpl_placement.h"
+
+namespace tpl_learn {
+namespace {
+
+constexpr int kMaxDepth = TPL_BEAM_MAX_DEPTH;
+constexpr int kMaxWidth = TPL_BEAM_MAX_WIDTH;
+constexpr int kMaxPlacements = 34;                            // distinct placements of L, J and T
+constexpr int kMaxCandidates = kMaxWidth * kMaxPlacements;    // 2,176
+constexpr int kBeamBlock = 256;
+constexpr uint32_t kNoMove = 255u;
+constexpr uint32_t kSlotTop = 4095u;                          // low key word = kSlotTop - slot, never 0
+static_assert(kMaxCandidates <= (int)kSlotTop, "a slot fits the low word's twelve bits");
+static_assert(kMaxDepth == tpl::kWindowEntries && kMaxDepth % 4 == 0, "a path is three words of four placements");
+
+struct BeamArgs {
+    const uint4* a;              // [n]
+    const uint4* b;
+    uint32_t n;                  // boards = workgroups
+    uint32_t L, M;
+    const float* weights;        // [P][12], P = ceil(n / per_member)
+    uint32_t per_member;         // boards per weight row, in [1, n]
+    uint32_t depth, width;       // D in [1, 12], W in [1, 64]
+    uint8_t* action;             // [n]
+    uint8_t* plan;               // [n][depth], optional
+    float* score;                // [n], optional
+};
+
+struct Beam {
+    uint4 a[kMaxWidth], b[kMaxWidth];                         // the node's board, popped once per move made
+    float value[kMaxWidth];
+    uint32_t cleared[kMaxWidth];                              // rows cleared on the way
+    uint32_t path[kMaxWidth][kMaxDepth / 4];                  // a placement a byte, kNoMove behind the last
+};
+
+// the k-th distinct placement of piece `cur` in ascending b = 10 r + l: rotation r has 10 - w(cur, r) + 1 of them
+__device__ __forceinline__ uint32_t nth_placement(uint32_t cur, uint32_t k, uint32_t& r, uint32_t& l) {
+    const uint32_t last_rot = (kRotationMasks >> (2u * cur)) & 3u;
+    r = 0u;
+    l = k;
+#pragma unroll
+    for (int step = 0; step < 3; ++step) {
+        const uint32_t count = 10u - ((uint32_t)(kWidthsLess1 >> (2u * (cur * 4u + r))) & 3u);
+        const bool over = l >= count && r < last_rot;
+        l -= over ? count : 0u;
+        r += over ? 1u : 0u;
+    }
+    return 10u * r + l;
+}
+
+__device__ __forceinline__ uint32_t placement_count(uint32_t cur) {
+    const uint32_t last_rot = (kRotationMasks >> (2u * cur)) & 3u;
+    uint32_t total = 0u;
+#pragma unroll
+    for (uint32_t r = 0; r < 4u; ++r)
+        total += r <= last_rot ? 10u - ((uint32_t)(kWidthsLess1 >> (2u * (cur * 4u + r))) & 3u) : 0u;
+    return total;
+}
+
+// Candidate k of running parent q: the board the move leaves (window not yet popped), the rows cleared with the parent's, and
+// the value of psi = (cleared, won, lost, features 3..11).  Phases A and C both come here, so a winner's second making of its
+// move gives the bits of the first.
+__device__ __forceinline__ float expand(const Beam& parent, uint32_t q, uint32_t k, const tpl::ShapeWord* shape, uint32_t L,
+                                        uint32_t M, const float (&w)[kFeatures], tpl::Board& s, uint32_t& cleared, uint32_t& b) {
+    const uint4 A = parent.a[q], B = parent.b[q];
+    uint32_t r, l, cur;
+    b = nth_placement(B.w & 7u, k, r, l);
+    bool running;                                             // the callers expand running parents only (Slot::finished)
+    cleared = parent.cleared[q] + first_move(A, B, shape, r, l, L, M, s, cur, running);
+    Features psi;
+    moved_features(s, cleared, true, psi);
+    return placement_score(w, psi);
+}
+
+// What slot q S + k stands for: parent q, its k-th distinct placement, and whether the parent is a finished game (then slot k = 0
+// carries it and its other slots are no candidates).  Phases A and C both decode a slot here.
+struct Slot { uint32_t q, k; bool finished; };
+__device__ __forceinline__ Slot slot_of(const Beam& parent, uint32_t slot, uint32_t stride) {
+    Slot c;
+    c.q = slot / stride;
+    c.k = slot - c.q * stride;
+    c.finished = tpl::packed_state(parent.b[c.q]) != tpl::ST_RUNNING;
+    return c;
+}
+
+// the largest of a wave's 64 values, in every lane
+__device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const unsigned long long other = __shfl_xor(v, off);
+        v = other > v ? other : v;
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(kBeamBlock) void placement_beam_kernel(const BeamArgs p) {
+    __shared__ tpl::ShapeWord s_shape[32];
+    __shared__ __attribute__((aligned(16))) float s_w[kFeatures];
+    __shared__ Beam s_beam[2];
+    __shared__ unsigned long long s_key[kMaxCandidates];
+    __shared__ unsigned long long s_sel[kMaxWidth];
+    __shared__ unsigned long long s_wave[2][kBeamBlock / 64];
+    __shared__ uint32_t s_best;
+    const uint32_t tid = threadIdx.x, i = blockIdx.x;          // the grid is n blocks
+    if (tid < 32) s_shape[tid] = tpl::kShapeTable[tid];
+    if (tid < kFeatures / 4) ((float4*)s_w)[tid] = ((const float4*)(p.weights + (size_t)(i / p.per_member) * kFeatures))[tid];
+    if (tid == 0) {                                            // Beam_0: the root alone
+        s_beam[0].a[0] = p.a[i];
+        s_beam[0].b[0] = p.b[i];
+        s_beam[0].value[0] = 0.0f;
+        s_beam[0].cleared[0] = 0u;
+#pragma unroll
+        for (int k = 0; k < kMaxDepth / 4; ++k) s_beam[0].path[0][k] = 0xFFFFFFFFu;
+        s_best = 0u;
+    }
+    __syncthreads();
+    float w[kFeatures];
+#pragma unroll
+    for (int q = 0; q < kFeatures / 4; ++q) {
+        const float4 v = ((const float4*)s_w)[q];
+        w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
+    }
+    const uint4 rootA = s_beam[0].a[0], rootB = s_beam[0].b[0];
+    const unsigned long long window = ((unsigned long long)(rootB.z >> 28) << 32) | rootB.w;
+    // the plies: none for a finished board, else as many as the window has true pieces
+    const uint32_t known = (uint32_t)tpl::kWindowEntries - tpl::packed_moves(rootA) % (uint32_t)tpl::kWindowStride;
+    const uint32_t plies = tpl::packed_state(rootB) != tpl::ST_RUNNING ? 0u : min(p.depth, known);
+    if (plies == 0u) {
+        Features zero;
+#pragma unroll
+        for (int k = 0; k < kFeatures; ++k) zero.f[k] = 0u;
+        if (tid == 0) s_beam[0].value[0] = placement_score(w, zero);
+        __syncthreads();
+    }
+
+    uint32_t nodes = 1u;
+#pragma unroll 1
+    for (uint32_t ply = 0; ply < plies; ++ply) {
+        const Beam& parent = s_beam[ply & 1u];
+        Beam& child = s_beam[(ply & 1u) ^ 1u];
+        const uint32_t cur = (uint32_t)(window >> (3u * ply)) & 7u;
+        const uint32_t stride = placement_count(cur);
+        const uint32_t total = nodes * stride;                 // at most 64 x 34 slots
+
+        // A: the keys
+#pragma unroll 1
+        for (uint32_t slot = tid; slot < total; slot += kBeamBlock) {
+            const Slot c = slot_of(parent, slot, stride);
+            unsigned long long key = 0ull;
+            if (c.finished) {
+                if (c.k == 0u) key = ((unsigned long long)ordered_bits(parent.value[c.q]) << 32) | (kSlotTop - slot);
+            } else {
+                tpl::Board s;
+                uint32_t cleared, b;
+                const float value = expand(parent, c.q, c.k, s_shape, p.L, p.M, w, s, cleared, b);
+                key = ((unsigned long long)ordered_bits(value) << 32) | (kSlotTop - slot);
+            }
+            s_key[slot] = key;
+        }
+        __syncthreads();
+
+        // B: the min(W, count) largest keys, best first.  s_wave[round & 1] holds the largest untaken key of each wave
+        unsigned long long mine = 0ull;
+#pragma unroll 1
+        for (uint32_t slot = tid; slot < total; slot += kBeamBlock) {
+            const unsigned long long key = s_key[slot];
+            mine = key > mine ? key : mine;
+        }
+        unsigned long long wave_best = wave_max(mine);
+        if ((tid & 63u) == 0u) s_wave[0][tid >> 6] = wave_best;
+        __syncthreads();
+        uint32_t kept = 0u;
+#pragma unroll 1
+        for (uint32_t round = 0; round < p.width; ++round) {
+            unsigned long long top = 0ull;
+#pragma unroll
+            for (int v = 0; v < kBeamBlock / 64; ++v) top = s_wave[round & 1u][v] > top ? s_wave[round & 1u][v] : top;
+            if (top == 0ull) break;                            // fewer candidates than W: the same words for every lane
+            if (tid == 0) s_sel[round] = top;
+            kept = round + 1u;
+            if (wave_best == top) {                            // this wave's key was taken: its owner looks for its next one
+                if (mine == top) {
+                    mine = 0ull;
+#pragma unroll 1
+                    for (uint32_t slot = tid; slot < total; slot += kBeamBlock) {
+                        const unsigned long long key = s_key[slot];
+                        mine = key < top && key > mine ? key : mine;
+                    }
+                }
+                wave_best = wave_max(mine);
+            }
+            if ((tid & 63u) == 0u) s_wave[(round & 1u) ^ 1u][tid >> 6] = wave_best;
+            __syncthreads();
+        }
+
+        // C: the kept candidates, in candidate order
+        if (tid < kept) {
+            const uint32_t low = (uint32_t)s_sel[tid];
+            uint32_t place = 0u;
+#pragma unroll 1
+            for (uint32_t e = 0; e < kept; ++e) place += (uint32_t)s_sel[e] > low ? 1u : 0u;
+            const Slot c = slot_of(parent, kSlotTop - low, stride);
+            const uint32_t q = c.q;
+            uint32_t path[kMaxDepth / 4];
+#pragma unroll
+            for (int j = 0; j < kMaxDepth / 4; ++j) path[j] = parent.path[q][j];
+            if (c.finished) {
+                child.a[place] = parent.a[q];
+                child.b[place] = parent.b[q];
+                child.value[place] = parent.value[q];
+                child.cleared[place] = parent.cleared[q];
+            } else {
+                tpl::Board s;
+                uint32_t cleared, b;
+                const float value = expand(parent, q, c.k, s_shape, p.L, p.M, w, s, cleared, b);
+                tpl::next_window(s, false, 0);                 // tpl_afterstates' pop
+                uint4 A, B;
+                tpl::pack_board(s, A, B);
+                child.a[place] = A;
+                child.b[place] = B;
+                child.value[place] = value;
+                child.cleared[place] = cleared;
+                // byte `ply` of the path: 0xFF -> b.  ply is the same for the whole block, the word is picked by selects
+                const uint32_t put = ~((kNoMove ^ b) << (8u * (ply & 3u)));
+#pragma unroll
+                for (int j = 0; j < kMaxDepth / 4; ++j) path[j] &= (ply >> 2) == (uint32_t)j ? put : 0xFFFFFFFFu;
+            }
+#pragma unroll
+            for (int j = 0; j < kMaxDepth / 4; ++j) child.path[place][j] = path[j];
+            if (tid == 0) s_best = place;
+        }
+        __syncthreads();
+        nodes = kept;
+    }
+
+    // the choice: the best node of the last beam
+    const Beam& last = s_beam[plies & 1u];
+    const uint32_t best = s_best;
+    if (tid == 0) {
+        p.action[i] = plies == 0u ? (uint8_t)0 : (uint8_t)(last.path[best][0] & 0xFFu);
+        if (p.score) p.score[i] = last.value[best];
+    }
+    if (p.plan && tid < p.depth) p.plan[(size_t)i * p.depth + tid] = (uint8_t)(last.path[best][tid >> 2] >> (8u * (tid & 3u)));
+}
+
+}  // namespace
+}  // namespace tpl_learn
+
+using namespace tpl_learn;
+
+extern "C" int tpl_placement_beam(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const float* weights,
+                                  int64_t boards_per_member, int32_t depth, int32_t width, uint8_t* action, uint8_t* plan,
+                                  float* score, void* stream) {
+    const char* name = "tpl_placement_beam";
+    if (const int rc = check_policy(name, plane_a, plane_b, n, L, M, weights, boards_per_member, action, score)) return rc;
+    if (depth < 1 || depth > kMaxDepth) return fail_msg(TPL_ERR_ARG, "%s: depth must be in [1, %d]", name, kMaxDepth);
+    if (width < 1 || width > kMaxWidth) return fail_msg(TPL_ERR_ARG, "%s: width must be in [1, %d]", name, kMaxWidth);
+    BeamArgs p{};
+    p.a = (const uint4*)plane_a; p.b = (const uint4*)plane_b; p.n = (uint32_t)n;
+    p.L = (uint32_t)L; p.M = (uint32_t)M; p.weights = weights;
+    p.per_member = (uint32_t)(boards_per_member < n ? boards_per_member : n);     // anything above n is the single-policy case
+    p.depth = (uint32_t)depth; p.width = (uint32_t)width;
+    p.action = action; p.plan = plan; p.score = score;
+    hipLaunchKernelGGL(placement_beam_kernel, dim3(p.n), dim3(kBeamBlock), 0, (hipStream_t)stream, p);
+    TPL_LEARN_HIP(hipGetLastError());
+    return TPL_OK;
+}

@@ -25,83 +25,10 @@
 namespace tpl_learn {
 namespace {
 
-constexpr int kFeatures = TPL_NUM_FEATURES;
 constexpr int kBoardsPerBlock = 8;
 constexpr int kActBlock = kBoardsPerBlock * kActions;        // 320 threads: five waves, eight whole boards
 constexpr int kFeatureBlock = 256;
 static_assert(kActBlock % 64 == 0, "a block is whole waves");
-
-struct Features { uint32_t f[kFeatures]; };
-
-// popcount(x) + acc: v_bcnt_u32_b32 adds its second operand
-__device__ __forceinline__ uint32_t bcnt(uint32_t x, uint32_t acc) { return (uint32_t)__builtin_popcount(x) + acc; }
-__device__ __forceinline__ uint32_t absdiff(uint32_t a, uint32_t b) { return max(a, b) - min(a, b); }
-
-// features 3..11 of a board given as its ten column words (bit r = row r, row 0 = top; bits 20.. clear)
-__device__ __forceinline__ void board_features(const uint32_t (&c)[tpl::kCols], Features& out) {
-    constexpr uint32_t kFloor = tpl::kSentinelBit;            // row 20: the floor, filled
-    uint32_t t[tpl::kCols];                                   // top of column x: row of its top-most filled cell, 20 if empty
-#pragma unroll
-    for (int x = 0; x < tpl::kCols; ++x) t[x] = (uint32_t)__builtin_ctz(c[x] | kFloor);
-
-    uint32_t top_sum = 0, top_min = tpl::kRows, filled = 0;
-    uint32_t col_trans = 0, hole_rows = 0, depth = 0;
-#pragma unroll
-    for (int x = 0; x < tpl::kCols; ++x) {
-        top_sum += t[x];
-        top_min = min(top_min, t[x]);
-        filled = bcnt(c[x], filled);
-        // rows r = 0..19 against r + 1 with the floor as row 20: pairs (r, r + 1), r < 19, and the floor term
-        const uint32_t cf = c[x] | kFloor;
-        col_trans = bcnt((cf ^ (cf >> 1)) & tpl::kColMask, col_trans);
-        // holes of the column: the empty cells below its top
-        hole_rows |= ~c[x] & (tpl::kColMask >> t[x] << t[x]);
-        // the run of filled cells from the top down; it ends at the column's top-most hole unless it reaches the floor
-        const uint32_t run = (uint32_t)__builtin_ctz(~(c[x] >> t[x]));
-        depth += t[x] + run < (uint32_t)tpl::kRows ? run : 0u;
-    }
-    const uint32_t height_sum = tpl::kRows * tpl::kCols - top_sum;
-
-    uint32_t bump = 0;
-#pragma unroll
-    for (int x = 0; x + 1 < tpl::kCols; ++x) bump += absdiff(t[x], t[x + 1]);
-
-    // per row: wall | x = 0..9 | wall, the walls filled
-    uint32_t row_trans = bcnt(~c[0] & tpl::kColMask, 0);
-#pragma unroll
-    for (int x = 0; x + 1 < tpl::kCols; ++x) row_trans = bcnt(c[x] ^ c[x + 1], row_trans);
-    row_trans = bcnt(~c[tpl::kCols - 1] & tpl::kColMask, row_trans);
-
-    // d_x = max(0, min(h_{x-1}, h_{x+1}) - h_x) = max(0, t_x - max(t_{x-1}, t_{x+1})), t = 0 beyond the walls (h = 20)
-    uint32_t wells = 0;
-#pragma unroll
-    for (int x = 0; x < tpl::kCols; ++x) {
-        const uint32_t left = x > 0 ? t[x - 1] : 0u, right = x + 1 < tpl::kCols ? t[x + 1] : 0u;
-        const uint32_t side = max(left, right);
-        const uint32_t d = t[x] > side ? t[x] - side : 0u;
-        wells += __umul24(d, d + 1u) >> 1;
-    }
-
-    out.f[3] = height_sum - filled;                            // holes: the cells below the tops that are not filled
-    out.f[4] = height_sum;
-    out.f[5] = tpl::kRows - top_min;
-    out.f[6] = bump;
-    out.f[7] = row_trans;
-    out.f[8] = col_trans;
-    out.f[9] = wells;
-    out.f[10] = (uint32_t)__builtin_popcount(hole_rows);
-    out.f[11] = depth;
-}
-
-// phi of the board `s` that a move (or two) left: rows cleared, won, lost and board_features; all zero where `live` is false
-__device__ __forceinline__ void moved_features(const tpl::Board& s, uint32_t n_clear, bool live, Features& out) {
-    board_features(s.c, out);
-    out.f[0] = n_clear;
-    out.f[1] = s.state == tpl::ST_WON ? 1u : 0u;
-    out.f[2] = s.state >= tpl::ST_LOST_LIMIT ? 1u : 0u;
-#pragma unroll
-    for (int k = 0; k < kFeatures; ++k) out.f[k] = live ? out.f[k] : 0u;
-}
 
 struct FeatureArgs {
     const uint4* a;              // [n]
@@ -132,22 +59,6 @@ __global__ __launch_bounds__(kFeatureBlock) void placement_features_kernel(const
     rec[1] = make_uint2(phi.f[4] | (phi.f[5] << 16), phi.f[6] | (phi.f[7] << 16));
     rec[2] = make_uint2(phi.f[8] | (phi.f[9] << 16), phi.f[10] | (phi.f[11] << 16));
     if (p.canonical) p.canonical[j] = (uint8_t)canonical_action(cur, r, l);
-}
-
-// w . phi left to right in float32: every product and every sum rounded once -- contraction off, as afterstate_reward
-__device__ __forceinline__ float placement_score(const float (&w)[kFeatures], const Features& phi) {
-#pragma clang fp contract(off)
-    float s = w[0] * (float)phi.f[0];
-#pragma unroll
-    for (int k = 1; k < kFeatures; ++k) s = s + w[k] * (float)phi.f[k];
-    return s;
-}
-
-// float32 -> uint32 with the order of the floats; -0 and +0 get one image, as they compare equal
-__device__ __forceinline__ uint32_t ordered_bits(float x) {
-    uint32_t u = __float_as_uint(x);
-    u = u == 0x80000000u ? 0u : u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
 constexpr uint32_t kNoSecond = 255u;
@@ -268,11 +179,7 @@ namespace {
 // what tpl_placement_act (plies = 1, second = null) and tpl_placement_search (plies = 2) share: the checks and the launch
 int launch_policy(const char* name, int plies, const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M,
                   const float* weights, int64_t boards_per_member, uint8_t* action, uint8_t* second, float* score, void* stream) {
-    if (const int rc = check_planes(name, plane_a, plane_b, n, L, M)) return rc;
-    if (!weights || !action) return fail_msg(TPL_ERR_ARG, "%s: null pointer (weights and action are required)", name);
-    if (boards_per_member < 1) return fail_msg(TPL_ERR_ARG, "%s: boards_per_member must be positive", name);
-    if ((uintptr_t)weights & 15u) return fail_msg(TPL_ERR_ARG, "%s: weights must be 16-byte aligned", name);
-    if ((uintptr_t)score & 3u) return fail_msg(TPL_ERR_ARG, "%s: score must be 4-byte aligned", name);
+    if (const int rc = check_policy(name, plane_a, plane_b, n, L, M, weights, boards_per_member, action, score)) return rc;
     PolicyArgs p{};
     p.a = (const uint4*)plane_a; p.b = (const uint4*)plane_b; p.n = (uint32_t)n;
     p.L = (uint32_t)L; p.M = (uint32_t)M; p.weights = weights;

@@ -1,6 +1,6 @@
-// tpl_placement.h -- what the placement family shares (afterstates.hip, heuristic.hip; include/tpl_learn.h states the rules):
-// which of the 40 actions are one placement, the first move of a (board, action) pair, and the argument checks of the entry
-// points that read a pair of state planes.
+// tpl_placement.h -- what the placement family shares (afterstates.hip, heuristic.hip, beam.hip; include/tpl_learn.h states the
+// rules): which of the 40 actions are one placement, the first move of a (board, action) pair, the board features, the score
+// and its ordered key, and the argument checks of the entry points that read a pair of state planes.
 #pragma once
 
 #include "tpl_learn_internal.h"
@@ -9,6 +9,7 @@
 namespace tpl_learn {
 
 constexpr int kActions = TPL_NUM_ACTIONS;
+constexpr int kFeatures = TPL_NUM_FEATURES;
 
 // canonical[a] = 10 (r mod nrot(cur)) + min(l, 10 - w(cur, r)) for a = 10 r + l, r < 4, l < 10; reads tpl_mirror.h's packed
 // widths and rotation masks instead of a dependent load of the shape table
@@ -31,6 +32,94 @@ __device__ __forceinline__ uint32_t first_move(const uint4& A, const uint4& B, c
     return tpl::move_board(s, shape, r, l, L, M, topout);
 }
 
+struct Features { uint32_t f[kFeatures]; };
+
+// popcount(x) + acc: v_bcnt_u32_b32 adds its second operand
+__device__ __forceinline__ uint32_t bcnt(uint32_t x, uint32_t acc) { return (uint32_t)__builtin_popcount(x) + acc; }
+__device__ __forceinline__ uint32_t absdiff(uint32_t a, uint32_t b) { return max(a, b) - min(a, b); }
+
+// features 3..11 of a board given as its ten column words (bit r = row r, row 0 = top; bits 20.. clear)
+__device__ __forceinline__ void board_features(const uint32_t (&c)[tpl::kCols], Features& out) {
+    constexpr uint32_t kFloor = tpl::kSentinelBit;            // row 20: the floor, filled
+    uint32_t t[tpl::kCols];                                   // top of column x: row of its top-most filled cell, 20 if empty
+#pragma unroll
+    for (int x = 0; x < tpl::kCols; ++x) t[x] = (uint32_t)__builtin_ctz(c[x] | kFloor);
+
+    uint32_t top_sum = 0, top_min = tpl::kRows, filled = 0;
+    uint32_t col_trans = 0, hole_rows = 0, depth = 0;
+#pragma unroll
+    for (int x = 0; x < tpl::kCols; ++x) {
+        top_sum += t[x];
+        top_min = min(top_min, t[x]);
+        filled = bcnt(c[x], filled);
+        // rows r = 0..19 against r + 1 with the floor as row 20: pairs (r, r + 1), r < 19, and the floor term
+        const uint32_t cf = c[x] | kFloor;
+        col_trans = bcnt((cf ^ (cf >> 1)) & tpl::kColMask, col_trans);
+        // holes of the column: the empty cells below its top
+        hole_rows |= ~c[x] & (tpl::kColMask >> t[x] << t[x]);
+        // the run of filled cells from the top down; it ends at the column's top-most hole unless it reaches the floor
+        const uint32_t run = (uint32_t)__builtin_ctz(~(c[x] >> t[x]));
+        depth += t[x] + run < (uint32_t)tpl::kRows ? run : 0u;
+    }
+    const uint32_t height_sum = tpl::kRows * tpl::kCols - top_sum;
+
+    uint32_t bump = 0;
+#pragma unroll
+    for (int x = 0; x + 1 < tpl::kCols; ++x) bump += absdiff(t[x], t[x + 1]);
+
+    // per row: wall | x = 0..9 | wall, the walls filled
+    uint32_t row_trans = bcnt(~c[0] & tpl::kColMask, 0);
+#pragma unroll
+    for (int x = 0; x + 1 < tpl::kCols; ++x) row_trans = bcnt(c[x] ^ c[x + 1], row_trans);
+    row_trans = bcnt(~c[tpl::kCols - 1] & tpl::kColMask, row_trans);
+
+    // d_x = max(0, min(h_{x-1}, h_{x+1}) - h_x) = max(0, t_x - max(t_{x-1}, t_{x+1})), t = 0 beyond the walls (h = 20)
+    uint32_t wells = 0;
+#pragma unroll
+    for (int x = 0; x < tpl::kCols; ++x) {
+        const uint32_t left = x > 0 ? t[x - 1] : 0u, right = x + 1 < tpl::kCols ? t[x + 1] : 0u;
+        const uint32_t side = max(left, right);
+        const uint32_t d = t[x] > side ? t[x] - side : 0u;
+        wells += __umul24(d, d + 1u) >> 1;
+    }
+
+    out.f[3] = height_sum - filled;                            // holes: the cells below the tops that are not filled
+    out.f[4] = height_sum;
+    out.f[5] = tpl::kRows - top_min;
+    out.f[6] = bump;
+    out.f[7] = row_trans;
+    out.f[8] = col_trans;
+    out.f[9] = wells;
+    out.f[10] = (uint32_t)__builtin_popcount(hole_rows);
+    out.f[11] = depth;
+}
+
+// phi of the board `s` that a move (or two) left: rows cleared, won, lost and board_features; all zero where `live` is false
+__device__ __forceinline__ void moved_features(const tpl::Board& s, uint32_t n_clear, bool live, Features& out) {
+    board_features(s.c, out);
+    out.f[0] = n_clear;
+    out.f[1] = s.state == tpl::ST_WON ? 1u : 0u;
+    out.f[2] = s.state >= tpl::ST_LOST_LIMIT ? 1u : 0u;
+#pragma unroll
+    for (int k = 0; k < kFeatures; ++k) out.f[k] = live ? out.f[k] : 0u;
+}
+
+// w . phi left to right in float32: every product and every sum rounded once -- contraction off, as afterstate_reward
+__device__ __forceinline__ float placement_score(const float (&w)[kFeatures], const Features& phi) {
+#pragma clang fp contract(off)
+    float s = w[0] * (float)phi.f[0];
+#pragma unroll
+    for (int k = 1; k < kFeatures; ++k) s = s + w[k] * (float)phi.f[k];
+    return s;
+}
+
+// float32 -> uint32 with the order of the floats; -0 and +0 get one image, as they compare equal
+__device__ __forceinline__ uint32_t ordered_bits(float x) {
+    uint32_t u = __float_as_uint(x);
+    u = u == 0x80000000u ? 0u : u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
 // the checks of every entry point that reads n states from a pair of planes; `name` leads the message
 inline int check_planes(const char* name, const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M) {
     if (!plane_a || !plane_b) return fail_msg(TPL_ERR_ARG, "%s: null pointer", name);
@@ -40,6 +129,17 @@ inline int check_planes(const char* name, const void* plane_a, const void* plane
     if (L < 1 || L > 255 || M < 1 || M > 255) return fail_msg(TPL_ERR_ARG, "%s: L and M must be in [1, 255]", name);
     if (((uintptr_t)plane_a & 15u) || ((uintptr_t)plane_b & 15u))
         return fail_msg(TPL_ERR_ARG, "%s: planes must be 16-byte aligned", name);
+    return TPL_OK;
+}
+
+// what every policy entry refuses besides check_planes (tpl_placement_act's list in include/tpl_learn.h)
+inline int check_policy(const char* name, const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M,
+                        const float* weights, int64_t boards_per_member, const uint8_t* action, const float* score) {
+    if (const int rc = check_planes(name, plane_a, plane_b, n, L, M)) return rc;
+    if (!weights || !action) return fail_msg(TPL_ERR_ARG, "%s: null pointer (weights and action are required)", name);
+    if (boards_per_member < 1) return fail_msg(TPL_ERR_ARG, "%s: boards_per_member must be positive", name);
+    if ((uintptr_t)weights & 15u) return fail_msg(TPL_ERR_ARG, "%s: weights must be 16-byte aligned", name);
+    if ((uintptr_t)score & 3u) return fail_msg(TPL_ERR_ARG, "%s: score must be 4-byte aligned", name);
     return TPL_OK;
 }
 

@@ -8,6 +8,9 @@
     HeuristicPolicy(env, weights, depth=2).act()
                                   two plies with the known next piece (window entry 1), still one launch: a first placement is
                                   worth the best placement of the next piece on the board it leaves
+    BeamPolicy(env, weights, depth, width).act()
+                                  a beam search over the pieces the state's window is known to hold (up to twelve), still one
+                                  launch: each ply keeps the `width` best nodes; act(plan=...) also gives the chosen path
     evaluate_heuristic(env, weights, boards_per_member, steps)
                                   episodes and wins of every member of a population on an auto-reset environment
     tune_heuristic(L, M, config_pool, ...)
@@ -23,10 +26,10 @@ import numpy as np
 import torch
 
 from . import _learn_lib
-from ._learn_lib import FEATURE_NAMES, NUM_ACTIONS, NUM_FEATURES, check
+from ._learn_lib import BEAM_MAX_DEPTH, BEAM_MAX_WIDTH, FEATURE_NAMES, NUM_ACTIONS, NUM_FEATURES, check
 from .lookahead import _MAX_BOARDS, _ptr, _source_planes, _state_ptrs
 
-__all__ = ["FEATURE_NAMES", "placement_features", "HeuristicPolicy", "evaluate_heuristic", "tune_heuristic"]
+__all__ = ["FEATURE_NAMES", "placement_features", "HeuristicPolicy", "BeamPolicy", "evaluate_heuristic", "tune_heuristic"]
 
 
 def placement_features(env, states_a: Optional[torch.Tensor] = None, states_b: Optional[torch.Tensor] = None):
@@ -65,6 +68,14 @@ def _depth(depth) -> int:
     if isinstance(depth, bool) or depth not in (1, 2):
         raise ValueError("depth must be 1 (the current piece) or 2 (the current and the known next piece)")
     return int(depth)
+
+
+def _beam_shape(depth, width):
+    """The validated (depth, width) of a beam search: integers, not bools, in range."""
+    for name, v, top in (("depth", depth, BEAM_MAX_DEPTH), ("width", width, BEAM_MAX_WIDTH)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= top:
+            raise ValueError(f"{name} must be an integer in [1, {top}], got {v!r}")
+    return int(depth), int(width)
 
 
 def _members(n: int, rows: int, boards_per_member) -> int:
@@ -140,6 +151,66 @@ class HeuristicPolicy:
         return out
 
 
+class BeamPolicy:
+    """A beam search with the linear placement score on the resident boards of `env` (tpl_placement_beam; the rule is in
+    include/tpl_learn.h).  At moves = m a state's window holds 12 - m mod 10 true next pieces; act() searches
+    min(depth, that many) plies: every ply expands each node of the beam by the distinct placements of its current piece,
+    scores the child on (rows cleared on the way, won, lost, the nine features of its board) and keeps the `width` best in
+    candidate order; the action is the first placement of the best leaf.  depth 1 is HeuristicPolicy; depth 2 with
+    width >= 34 is HeuristicPolicy(depth=2).  One launch, nothing written but the outputs.
+
+    weights, boards_per_member, members and set_weights() are HeuristicPolicy's."""
+
+    def __init__(self, env, weights, depth: int, width: int, boards_per_member: Optional[int] = None):
+        self.depth, self.width = _beam_shape(depth, width)
+        w = _weights(weights)
+        n = int(env.num_envs)
+        if not 1 <= n <= _MAX_BOARDS:
+            raise ValueError(f"BeamPolicy takes an environment of 1 .. {_MAX_BOARDS} boards (40 N must stay below 2^31)")
+        self.boards_per_member = _members(n, w.shape[0], boards_per_member)
+        self.env, self.members = env, int(w.shape[0])
+        self.weights = torch.from_numpy(w).to(env.device)
+        self._planes = None
+
+    set_weights = HeuristicPolicy.set_weights
+
+    @torch.no_grad()
+    def act(self, out: Optional[torch.Tensor] = None, score: Optional[torch.Tensor] = None,
+            plan: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """uint8 [N]: the action of every resident board; `score` (float32 [N], optional) receives the chosen leaf's value and
+        `plan` (uint8 [N, depth], optional) its path: plan[:, 0] is the action, 255 fills what was not searched (a finished
+        board, a game that ends on the way, a window with fewer known pieces).  No host sync, and no allocation when `out` is
+        given: capturable into a HIP graph."""
+        env = self.env
+        if out is None:
+            out = torch.empty(env.num_envs, dtype=torch.uint8, device=env.device)
+        env._own(out, torch.uint8, "out")
+        if score is not None:
+            env._own(score, torch.float32, "score")
+        if plan is not None:
+            env._own(plan, torch.uint8, "plan", (env.num_envs, self.depth))
+        if self._planes is None:
+            self._planes = _state_ptrs(env)                   # the resident planes live as long as the environment
+        stream = torch._C._cuda_getCurrentRawStream(env.device.index)
+        check(_learn_lib.lib().tpl_placement_beam(self._planes[0], self._planes[1], env.num_envs, env.L, env.M,
+                                                  self.weights.data_ptr(), self.boards_per_member, self.depth, self.width,
+                                                  out.data_ptr(), _ptr(plan), _ptr(score), stream))
+        return out
+
+
+def _player(depth, width):
+    """(class, depth, width) of the policy that plays `depth` plies: HeuristicPolicy without a width, else BeamPolicy."""
+    if width is None:
+        return HeuristicPolicy, _depth(depth), None
+    return (BeamPolicy,) + _beam_shape(depth, width)
+
+
+def _build_player(env, weights, boards_per_member, depth, width):
+    if width is None:
+        return HeuristicPolicy(env, weights, boards_per_member, depth=depth)
+    return BeamPolicy(env, weights, depth, width, boards_per_member)
+
+
 def _win_count_reward(env) -> None:
     if tuple(env.reward_params) != (0.0, 1.0, 0.0):
         raise ValueError("evaluate_heuristic counts wins as summed reward: the environment's reward must be (0, 1, 0), "
@@ -147,24 +218,30 @@ def _win_count_reward(env) -> None:
 
 
 @torch.no_grad()
-def evaluate_heuristic(env, weights, boards_per_member: Optional[int], steps: int, policy: Optional[HeuristicPolicy] = None,
-                       depth: int = 1) -> dict:
+def evaluate_heuristic(env, weights, boards_per_member: Optional[int], steps: int, policy=None, depth: int = 1,
+                       width: Optional[int] = None) -> dict:
     """Play `steps` steps of the population `weights` ([P, 12] or [12]) on `env` from a full reset: an auto-reset environment
     with a configuration pool and reward parameters (0, 1, 0), so that the summed reward is the number of wins.  Member p plays
     boards [p * boards_per_member, (p + 1) * boards_per_member).  Returns episodes and wins as int64 numpy arrays [P] and
     win_rate = wins / max(episodes, 1); the tallies are kept on the device, with one sync at the end.  `policy`: a
     HeuristicPolicy of this environment to reuse (its weights are replaced).  `depth`: 1 or 2 plies (HeuristicPolicy's); a
-    `policy` that is passed must have been built with it."""
-    depth = _depth(depth)
-    if policy is not None and policy.depth != depth:
-        raise ValueError(f"policy was built with depth {policy.depth}, not {depth}")
+    `policy` that is passed must have been built with it.  `width`: None, or a beam width -- then a BeamPolicy(depth, width)
+    plays, depth may be 1 .. 12, and a `policy` that is passed must be a BeamPolicy of that depth and width."""
+    kind, depth, width = _player(depth, width)
+    if policy is not None:
+        if isinstance(policy, BeamPolicy) != (kind is BeamPolicy):
+            raise ValueError(f"policy is a {type(policy).__name__}, but width={width} asks for a {kind.__name__}")
+        if policy.depth != depth:
+            raise ValueError(f"policy was built with depth {policy.depth}, not {depth}")
+        if width is not None and policy.width != width:
+            raise ValueError(f"policy was built with width {policy.width}, not {width}")
     _win_count_reward(env)
     if not env.auto_reset:
         raise ValueError("evaluate_heuristic needs an auto-reset environment")
     if isinstance(steps, bool) or int(steps) != steps or int(steps) < 1:
         raise ValueError("steps must be a positive integer")
     if policy is None:
-        policy = HeuristicPolicy(env, weights, boards_per_member, depth=depth)
+        policy = _build_player(env, weights, boards_per_member, depth, width)
     else:
         if policy.env is not env:
             raise ValueError("policy belongs to another environment")
@@ -191,18 +268,19 @@ def evaluate_heuristic(env, weights, boards_per_member: Optional[int], steps: in
 
 def tune_heuristic(L: int, M: int, config_pool, population: int = 64, boards_per_member: int = 4096, steps: Optional[int] = None,
                    generations: int = 20, elite_frac: float = 0.125, init_mean=None, init_std: float = 10.0, noise: float = 0.5,
-                   seed: int = 0, device="cuda:0", depth: int = 1) -> dict:
+                   seed: int = 0, device="cuda:0", depth: int = 1, width: Optional[int] = None) -> dict:
     """The noisy cross-entropy method on the twelve weights.  Each generation samples `population` weight rows from
     N(mean, diag std^2) with a CPU torch.Generator seeded by `seed`, plays them side by side (`boards_per_member` boards each,
     `steps` steps from a full reset, default 4 M: some four episodes a board) on ONE evaluation environment of
     population * boards_per_member boards over `config_pool` = (rows, pieces) with reward (0, 1, 0), takes fitness = wins /
     max(episodes, 1), and refits mean and std to the best ceil(elite_frac * population) rows, std^2 = var(elite) + noise (the
-    constant noise term that keeps the search from freezing early).  `depth`: the plies the members search (1 or 2).
+    constant noise term that keeps the search from freezing early).  `depth`: the plies the members search (1 or 2); with a
+    `width` the members are BeamPolicy(depth, width) and depth may be 1 .. 12.
 
     Returns mean (float32 [12], the final one), best (float32 [12], the best member seen) with best_fitness, and history: one
     dict of host floats per generation (population_mean, elite_mean, best).  Deterministic for a given seed."""
     from .env import BatchedTetris
-    depth = _depth(depth)
+    _, depth, width = _player(depth, width)
     for name, v in (("population", population), ("boards_per_member", boards_per_member), ("generations", generations)):
         if isinstance(v, bool) or int(v) != v or int(v) < 1:
             raise ValueError(f"{name} must be a positive integer")
@@ -225,8 +303,8 @@ def tune_heuristic(L: int, M: int, config_pool, population: int = 64, boards_per
             z = torch.randn((P, NUM_FEATURES), generator=gen, dtype=torch.float64).numpy()
             rows = (mean[None, :] + std[None, :] * z).astype(np.float32)
             if policy is None:
-                policy = HeuristicPolicy(env, rows, per, depth=depth)
-            fitness = evaluate_heuristic(env, rows, per, steps, policy=policy, depth=depth)["win_rate"]
+                policy = _build_player(env, rows, per, depth, width)
+            fitness = evaluate_heuristic(env, rows, per, steps, policy=policy, depth=depth, width=width)["win_rate"]
             order = np.argsort(-fitness, kind="stable")        # ties: the lower member first
             top = rows[order[:elite]].astype(np.float64)
             if fitness[order[0]] > best_fitness:

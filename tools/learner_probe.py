@@ -37,6 +37,11 @@ Parts:
               tpl_placement_act over its 40 x 16,384 boards, a torch max), alternated in one process; win rates at depth 1 and 2
               of the classical signs and of a tuned row on the L=2 / M=2 pool and an L=10 / M=40 carved pool (>= 10^6 episodes
               each, with standard errors)
+    beam         the beam search: BeamPolicy.act() at 2^16 and 2^20 boards (L=10 / M=40, mid-game) for (depth, width) in (2, 34),
+              (3, 8), (4, 16), (6, 16), (12, 64) beside tpl_placement_search on the same boards, alternated over three rounds;
+              the yardstick is the two-ply kernel of the same run and the prediction the moves per board of the two rules on these
+              boards (their windows' known pieces and placement counts); win rates of the classical signs at depth 1 and 2 and
+              at (3, 8), (4, 16) and (6, 16) on an L=10 / M=40 carved pool
 """
 import argparse
 import json
@@ -50,7 +55,7 @@ sys.path.insert(0, ROOT)
 
 HBM_ACHIEVABLE = 6.3e12
 PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600, "priority": 600, "nstep": 600, "mirror": 600, "afterstates": 600,
-         "heuristic": 600, "search": 900}
+         "heuristic": 600, "search": 900, "beam": 900}
 VALU_CYCLES, SIMDS, CLOCK_HZ = 3.3, 1024, 2.4e9           # the move's instruction mix, 256 CUs x 4, the clock
 
 
@@ -718,6 +723,87 @@ def part_search(rounds=5):
                   seconds=round(time.perf_counter() - t0, 2))
     out["l10_m40"] = dict(tune=dict(budget, best_fitness=round(tuned["best_fitness"], 5), best=[round(float(x), 4) for x in tuned["best"]]),
                           rates=_search_rates(10, 40, big, 1 << 18, 160, (("classical", classical), ("tuned", tuned["best"])), seed=11))
+    return out
+
+
+BEAM_SHAPES = ((2, 34), (3, 8), (4, 16), (6, 16), (12, 64))
+
+
+def _beam_model(a, b, depth, width):
+    """Moves per board the two rules make on the states (a, b) (uint32 [n, 4] planes), by the known pieces of every window and
+    the distinct placements of each: (beam at (depth, width), two-ply search), means over all boards (a finished board: 0)."""
+    import numpy as np
+    count = np.array([17, 34, 34, 34, 17, 17, 9, 9], np.int64)
+    running = ((b[:, 1] >> 28) & 3) == 0
+    moves = ((a[:, 1] >> 28) | ((a[:, 3] >> 28) << 4)).astype(np.int64)
+    window = b[:, 3].astype(np.uint64) | ((b[:, 2] >> 28).astype(np.uint64) << np.uint64(32))
+    plies = np.where(running, np.minimum(depth, 12 - moves % 10), 0)
+    nodes, total = np.ones(a.shape[0], np.int64), np.zeros(a.shape[0], np.int64)
+    for j in range(depth):
+        c = count[((window >> np.uint64(3 * j)) & np.uint64(7)).astype(np.int64)]
+        live = plies > j
+        total += np.where(live, nodes * c, 0)
+        nodes = np.where(live, np.minimum(width, nodes * c), nodes)
+    c0, c1 = count[(window & np.uint64(7)).astype(np.int64)], count[((window >> np.uint64(3)) & np.uint64(7)).astype(np.int64)]
+    return float(total.mean()), float(np.where(running, c0 * (1 + c1), 0).mean()), float(plies.mean())
+
+
+def part_beam(rounds=3):
+    import numpy as np
+    import torch
+    import tetris_piclim as T
+    classical = np.array([4, 100, -100, -8, -1, 0, -2, -3, -6, -3, -2, -1], np.float32) * np.float32(0.1)
+    out = dict(part="beam", model="34 (1 + W (D - 1)) moves per board against the two-ply search's 34^2",
+               nominal_ratio={f"{d}x{w}": round(34 * (1 + w * (d - 1)) / 34 ** 2, 3) for d, w in BEAM_SHAPES})
+    rows = []
+    for n in (1 << 16, 1 << 20):
+        env = T.BatchedTetris(10, 40, n, device="cuda:0", seed=1, auto_reset=True)
+        env.load_configs(*env.synthetic_configs(4096))
+        env.reset()
+        for t in range(6):                                       # mid-game boards
+            env.step(env.synthetic_actions(t), observe=False)
+        a, b = (x.cpu().numpy().view(np.uint32) for x in env.raw_planes())
+        action = torch.empty(n, dtype=torch.uint8, device="cuda:0")
+        two = T.HeuristicPolicy(env, classical, depth=2)
+        beams = {shape: T.BeamPolicy(env, classical, *shape) for shape in BEAM_SHAPES}
+        reps = 10 if n <= 1 << 16 else 3
+        times = {shape: [] for shape in BEAM_SHAPES}
+        times["search"] = []
+        for _ in range(rounds):                                  # alternate the kernels round by round
+            times["search"].append(_timed(lambda: two.act(out=action), reps, warmup=1))
+            for shape in BEAM_SHAPES:
+                times[shape].append(_timed(lambda: beams[shape].act(out=action), reps, warmup=1))
+        t_search = sorted(times["search"])[rounds // 2]
+        row = dict(boards=n, launches_per_timing=reps, rounds=rounds, search_us=_spread(times["search"]))
+        for shape in BEAM_SHAPES:
+            t = sorted(times[shape])[rounds // 2]
+            beam_moves, search_moves, plies = _beam_model(a, b, *shape)
+            row[f"{shape[0]}x{shape[1]}"] = dict(us=_spread(times[shape]), mean_plies=round(plies, 2), moves_per_board=round(beam_moves, 1),
+                                                 search_moves_per_board=round(search_moves, 1), measured_over_search=round(t / t_search, 3),
+                                                 predicted_over_search=round(beam_moves / search_moves, 3),
+                                                 measured_over_predicted=round(t / t_search / (beam_moves / search_moves), 3))
+        rows.append(row)
+        env.terminate()
+        torch.cuda.empty_cache()
+    out["act"] = rows
+    # play strength: the classical signs on an L = 10 / M = 40 carved pool
+    gen_env = T.BatchedTetris(10, 40, 64, device="cuda:0", seed=7)
+    big = gen_env.carved_configs(1 << 16, seed=7)
+    gen_env.terminate()
+    n, steps, seed = 1 << 16, 160, 11
+    env = T.BatchedTetris(10, 40, n, device="cuda:0", seed=seed, auto_reset=True, reward=(0.0, 1.0, 0.0), config_pool=big)
+    rates = dict(boards=n, steps=steps, seed=seed, pool=1 << 16, pool_seed=7)
+    for depth, width in ((1, None), (2, None), (3, 8), (4, 16), (6, 16)):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        got = T.evaluate_heuristic(env, classical, None, steps, depth=depth, width=width)
+        e, wins = int(got["episodes"][0]), int(got["wins"][0])
+        p = wins / max(e, 1)
+        rates[f"depth{depth}" + (f"_width{width}" if width else "")] = dict(
+            episodes=e, wins=wins, win_rate=round(p, 5), standard_error=round((p * (1 - p) / max(e, 1)) ** 0.5, 6),
+            seconds=round(time.perf_counter() - t0, 3))
+    env.terminate()
+    out["l10_m40"] = rates
     return out
 
 
