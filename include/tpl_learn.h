@@ -202,7 +202,8 @@ int tpl_mirror_states(int64_t count, const void* a, const void* b, void* out_a, 
 /* The 40 afterstates of each of `n` states: plane_a / plane_b [n] 16-byte words (read only) -> out_a / out_b [n][40] 16-byte
  * words (both or neither; e.g. the resident planes of a 40 n-board environment, tpl_state_ptrs), reward f32, done u8, cleared u8,
  * canonical u8 [n][40], each optional; at least one output.  Refused before any HIP call: n < 1, 40 n >= 2^31, a NULL or
- * misaligned (16 bytes) plane pointer, only one of out_a / out_b, no output at all, L or M outside [1, 255]. */
+ * misaligned (16 bytes) plane pointer, only one of out_a / out_b, no output at all, L outside [1, 250] or M outside
+ * [1, 254] (tpl_create's limits: lines + 4 must fit the eight bits of B.z that hold it). */
 int tpl_afterstates(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line, float r_win,
                     float r_lose, void* out_a, void* out_b, float* reward, uint8_t* done, uint8_t* cleared, uint8_t* canonical,
                     void* stream);
@@ -249,7 +250,7 @@ int32_t tpl_canonical_action(int32_t cur, int32_t action);
 /* phi of all 40 actions of each of `n` states: plane_a / plane_b [n] 16-byte words (read only) -> features i16 [n][40][12], one
  * contiguous 24-byte record per pair (8-byte aligned, written with 8-byte stores), and canonical u8 [n][40] (optional, as
  * tpl_afterstates').  Refused before any HIP call: n < 1, 40 n >= 2^31, a NULL or misaligned (16 bytes) plane pointer, features
- * NULL or not 8-byte aligned, L or M outside [1, 255]. */
+ * NULL or not 8-byte aligned, L outside [1, 250] or M outside [1, 254]. */
 int tpl_placement_features(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, int16_t* features,
                            uint8_t* canonical, void* stream);
 

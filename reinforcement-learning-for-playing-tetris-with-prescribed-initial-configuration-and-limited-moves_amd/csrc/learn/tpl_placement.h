@@ -120,13 +120,15 @@ __device__ __forceinline__ uint32_t ordered_bits(float x) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-// the checks of every entry point that reads n states from a pair of planes; `name` leads the message
+// the checks of every entry point that reads n states from a pair of planes; `name` leads the message.  L and M are the
+// environment's (tpl_create): move_board adds up to four rows to `lines` before pack_board writes it into eight bits
 inline int check_planes(const char* name, const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M) {
     if (!plane_a || !plane_b) return fail_msg(TPL_ERR_ARG, "%s: null pointer", name);
     if (n < 1) return fail_msg(TPL_ERR_ARG, "%s: n must be positive", name);
     if (n >= (((int64_t)1 << 31) + kActions - 1) / kActions)
         return fail_msg(TPL_ERR_ARG, "%s: n too large (40 n must stay below 2^31)", name);
-    if (L < 1 || L > 255 || M < 1 || M > 255) return fail_msg(TPL_ERR_ARG, "%s: L and M must be in [1, 255]", name);
+    if (L < 1 || L > 250 || M < 1 || M > 254)
+        return fail_msg(TPL_ERR_ARG, "%s: L and M must be in [1, 250] and [1, 254]", name);
     if (((uintptr_t)plane_a & 15u) || ((uintptr_t)plane_b & 15u))
         return fail_msg(TPL_ERR_ARG, "%s: planes must be 16-byte aligned", name);
     return TPL_OK;

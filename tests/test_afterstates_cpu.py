@@ -111,8 +111,10 @@ def test_every_refusal_comes_back_as_a_status_without_a_gpu():
     assert call(out_a=None) < 0 and b"go together" in err()
     assert call(out_b=None) < 0 and b"go together" in err()
     assert call(out_a=None, out_b=None, reward=None, done=None, cleared=None, canonical=None) < 0 and b"at least one output" in err()
-    for L, M in ((0, 2), (256, 2), (2, 0), (2, 256), (-1, -1)):
+    for L, M in ((0, 2), (256, 2), (2, 0), (2, 256), (-1, -1), (251, 2), (255, 2), (2, 255)):
         assert call(L=L, M=M) < 0 and b"L and M" in err(), (L, M)
+    # the environment's largest game is not refused for its size: the alignment check, which comes after L and M, speaks
+    assert call(L=250, M=254, a=fake + 8) < 0 and b"aligned" in err() and b"L and M" not in err()
     assert call(reward=fake + 2) < 0 and b"aligned" in err()
     assert b"tpl_afterstates" in err()
 

@@ -113,15 +113,17 @@ def _pool_fields(gen):
 class Pool:
     """The states, their planes and -- computed once -- what the oracle says of all 40 actions of every running one."""
 
-    def __init__(self, oracle):
-        gen = np.random.default_rng(1639)
-        f = self.fields = _pool_fields(gen)
+    def __init__(self, oracle, fields=None, L=L, M=M):
+        """Without `fields`: the POOL states of _pool_fields at L = 10 / M = 40 and their coverage condition; with them: those states
+        played at the game (L, M), the coverage left to the caller."""
+        own = fields is None
+        f = self.fields = _pool_fields(np.random.default_rng(1639)) if own else fields
         self.A, self.B = R.pack_state(f["rows"], f["lines"], f["moves"], f["state"], f["slot"], f["window"])
         self.B[:, 1] |= f["spare"] << np.uint32(31)
         back = R.decode_state(self.A, self.B)
         for k in ("rows", "lines", "moves", "state", "slot", "window"):
             assert np.array_equal(back[k].astype(np.int64), np.asarray(f[k]).astype(np.int64)), k
-        n = POOL
+        n = self.n = self.A.shape[0]
         self.rows = np.zeros((n, 40, 20), np.uint16)
         self.lines, self.moves = np.zeros((n, 40), np.int64), np.zeros((n, 40), np.int64)
         self.state, self.ret = np.zeros((n, 40), np.int64), np.zeros((n, 40), np.int64)
@@ -142,6 +144,8 @@ class Pool:
         self.won = (self.state == 1) & run[:, None]
         self.limit = (self.state == 2) & ~self.topout & run[:, None]
         self.done = np.where(run[:, None], self.state != 0, True)
+        if not own:
+            return
         # the coverage condition, on the oracle's own outcomes
         seen = {k: int(((self.cleared == k) & run[:, None]).sum()) for k in range(5)}
         ends = dict(win=int(self.won.sum()), limit=int(self.limit.sum()), topout=int(self.topout.sum()), frozen=int((~run).sum()),
@@ -152,7 +156,7 @@ class Pool:
         assert {8, 9, 18, 19} <= set(np.asarray(f["moves"])[run].tolist())
 
     def take(self, n, offset):
-        return (offset + np.arange(n)) % POOL
+        return (offset + np.arange(n)) % self.n
 
     def reward(self, idx, params):
         """float32 [n, 40]: one rounded multiply, at most one rounded add (numpy float32 operations round once each)."""
@@ -168,9 +172,9 @@ def pool(oracle):
     return Pool(oracle)
 
 
-def _run(A, B, params, skip=()):
-    """tpl_afterstates of host planes through canary-framed buffers; `skip` names the outputs passed as NULL ("states" = both
-    planes).  Returns host arrays of the outputs given."""
+def _run(A, B, params, skip=(), L=L, M=M):
+    """tpl_afterstates of host planes at the game (L, M) through canary-framed buffers; `skip` names the outputs passed as NULL
+    ("states" = both planes).  Returns host arrays of the outputs given."""
     n = A.shape[0]
     a, b = Framed(n * 16, 1), Framed(n * 16, 2)
     a.inner().copy_(torch.from_numpy(A.view(np.uint8).reshape(-1)))
@@ -321,7 +325,7 @@ def test_the_kernel_is_the_step_kernel_action_by_action(pool):
 
 
 # ------------------------------------------------------------------------------------------------ 3. zero copy, the policy
-def _resident(pool, n, offset, params):
+def _resident(pool, n, offset, params, L=L, M=M):
     env = T.BatchedTetris(L, M, n, device=DEV, seed=9, reward=params)
     idx = pool.take(n, offset)
     env.write_raw_planes(_i32(pool.A[idx]), _i32(pool.B[idx]))

@@ -99,8 +99,10 @@ def test_every_refusal_of_the_beam_entry_comes_back_as_a_status_without_a_gpu():
         assert beam(n=n) < 0 and b"2^31" in err() and name in err(), n
     for plane in ("a", "b"):
         assert beam(**{plane: fake + 8}) < 0 and b"aligned" in err() and name in err(), plane
-    for L, M in ((0, 2), (2, 256)):
+    for L, M in ((0, 2), (2, 256), (251, 2), (255, 2), (2, 255)):
         assert beam(L=L, M=M) < 0 and b"L and M" in err() and name in err(), (L, M)
+    # the environment's largest game is not refused for its size: the alignment check, which comes after L and M, speaks
+    assert beam(L=250, M=254, a=fake + 8) < 0 and b"aligned" in err() and b"L and M" not in err() and name in err()
     assert beam(weights=None) < 0 and b"null" in err() and name in err()
     assert beam(action=None) < 0 and b"null" in err() and name in err()
     assert beam(per=0) < 0 and b"boards_per_member" in err() and name in err()

@@ -42,8 +42,9 @@ def _m():
 class States:
     """The pool's states and planes (test_afterstates_gpu's generator and seed), without the oracle's outcomes."""
 
-    def __init__(self):
-        f = self.fields = _pool_fields(np.random.default_rng(1639))
+    def __init__(self, fields=None):
+        f = self.fields = _pool_fields(np.random.default_rng(1639)) if fields is None else fields
+        self.n = len(f["lines"])
         self.A, self.B = R.pack_state(f["rows"], f["lines"], f["moves"], f["state"], f["slot"], f["window"])
         self.B[:, 1] |= f["spare"] << np.uint32(31)
         self.running = np.asarray(f["state"]) == 0
@@ -51,7 +52,7 @@ class States:
         self.known = 12 - self.moves % 10                      # the true pieces a window holds
 
     def take(self, n, offset):
-        return (offset + np.arange(n)) % POOL
+        return (offset + np.arange(n)) % self.n
 
     def plies(self, idx, depth):
         return np.where(self.running[idx], np.minimum(depth, self.known[idx]), 0)
@@ -70,7 +71,7 @@ def env10():
     env.terminate()
 
 
-def _beam(a, b, n, weights, per, depth, width, skip=None):
+def _beam(a, b, n, weights, per, depth, width, skip=None, L=L, M=M):
     """tpl_placement_beam through canary-framed buffers; `skip` names the optional output passed as NULL."""
     w = np.ascontiguousarray(weights, np.float32).reshape(-1, NF)
     wf = Framed(w.size * 4, 5)
@@ -267,8 +268,8 @@ def test_a_population_searches_with_one_weight_row_per_member(states, env10, all
 
 
 # ------------------------------------------------------------------------------------------------ 3. the oracle
-def oracle_beam(O, f, i, plies, w, depth, width):
-    """The rule on state i with every move played by the C oracle: (action, plan, score)."""
+def oracle_beam(O, f, i, plies, w, depth, width, L=L, M=M):
+    """The rule on state i at the game (L, M) with every move played by the C oracle: (action, plan, score)."""
     m = _m()
     window = int(f["window"][i])
     pieces = [(window >> (3 * j)) & 7 for j in range(plies)]

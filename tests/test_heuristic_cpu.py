@@ -147,8 +147,10 @@ def test_every_refusal_of_both_entry_points_comes_back_as_a_status_without_a_gpu
         for plane in ("a", "b"):
             for off in (4, 8, 1):
                 assert call(**{plane: fake + off}) < 0 and b"aligned" in err(), (plane, off)
-        for L, M in ((0, 2), (256, 2), (2, 0), (2, 256), (-1, -1)):
-            assert call(L=L, M=M) < 0 and b"L and M" in err(), (L, M)
+        for L, M in ((0, 2), (256, 2), (2, 0), (2, 256), (-1, -1), (251, 2), (255, 2), (2, 255)):
+            assert call(L=L, M=M) < 0 and b"L and M" in err() and name in err(), (L, M)
+        # the environment's largest game is not refused for its size: the alignment check, which comes after L and M, speaks
+        assert call(L=250, M=254, a=fake + 8) < 0 and b"aligned" in err() and b"L and M" not in err()
         assert name in err()
     assert features(features=None) < 0 and b"null" in err()
     for off in (1, 2, 4):

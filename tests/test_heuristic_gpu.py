@@ -32,11 +32,13 @@ def _m():
 class Cases:
     """The pool and -- computed once -- phi of all 40 actions of every state as the oracle and the numpy mirror give it."""
 
-    def __init__(self, oracle):
-        p = self.pool = Pool(oracle)
+    def __init__(self, oracle, pool=None):
+        """Without `pool`: test_afterstates_gpu's own, and the coverage conditions of its 1,639 states; with one (a Pool of other
+        states, played at its own game): phi of those, the coverage left to the caller."""
+        p = self.pool = Pool(oracle) if pool is None else pool
         run = p.running[:, None]
-        board = _m().board_features(p.rows.reshape(-1, 20)).reshape(POOL, 40, 9)
-        phi = np.zeros((POOL, 40, NF), np.int64)
+        board = _m().board_features(p.rows.reshape(-1, 20)).reshape(p.n, 40, 9)
+        phi = np.zeros((p.n, 40, NF), np.int64)
         phi[:, :, 0] = p.cleared
         phi[:, :, 1] = p.won
         phi[:, :, 2] = p.limit | p.topout
@@ -45,6 +47,8 @@ class Cases:
         cur = (p.fields["window"] & np.uint64(7)).astype(np.int64)
         self.canonical = _m().canonical_actions(cur[:, None], np.arange(40)[None, :])
         self.distinct = self.canonical == np.arange(40)[None, :]
+        if pool is not None:
+            return
         # the coverage conditions, on the oracle's own outcomes
         values = {name: np.unique(self.phi[:, :, k]).size for k, name in enumerate(_m().FEATURE_NAMES)}
         clearing, topouts = int((self.phi[:, :, 0] > 0).sum()), int(p.topout.sum())
@@ -138,7 +142,7 @@ def _weight_sets():
     return sets
 
 
-def _act(a, b, n, weights, per, with_score=True):
+def _act(a, b, n, weights, per, with_score=True, L=L, M=M):
     w = np.ascontiguousarray(weights, np.float32).reshape(-1, NF)
     wf = Framed(w.size * 4, 5)
     wf.inner().copy_(torch.from_numpy(w.view(np.uint8).reshape(-1)))

@@ -157,8 +157,10 @@ def test_every_refusal_of_the_search_entry_comes_back_as_a_status_without_a_gpu(
     for plane in ("a", "b"):
         for off in (4, 8, 1):
             assert search(**{plane: fake + off}) < 0 and b"aligned" in err() and name in err(), (plane, off)
-    for L, M in ((0, 2), (256, 2), (2, 0), (2, 256), (-1, -1)):
+    for L, M in ((0, 2), (256, 2), (2, 0), (2, 256), (-1, -1), (251, 2), (255, 2), (2, 255)):
         assert search(L=L, M=M) < 0 and b"L and M" in err() and name in err(), (L, M)
+    # the environment's largest game is not refused for its size: the alignment check, which comes after L and M, speaks
+    assert search(L=250, M=254, a=fake + 8) < 0 and b"aligned" in err() and b"L and M" not in err() and name in err()
     assert search(weights=None) < 0 and b"null" in err() and name in err()
     assert search(action=None) < 0 and b"null" in err() and name in err()
     for per in (0, -1, -(1 << 40)):

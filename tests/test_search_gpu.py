@@ -37,13 +37,18 @@ def _m():
 class TwoPly:
     """test_heuristic_gpu's Cases and -- computed once -- psi(a, b) of every state the oracle can play two plies of."""
 
-    def __init__(self, oracle):
-        c = self.cases = Cases(oracle)
+    def __init__(self, oracle, cases=None, L=L, M=M, most=None):
+        """Without `cases`: test_heuristic_gpu's own at L = 10 / M = 40, and the coverage conditions; with them (Cases of another
+        pool, played at its game (L, M)): at most `most` of its states, evenly spread, the coverage left to the caller."""
+        own = cases is None
+        c = self.cases = Cases(oracle) if own else cases
         p = self.pool = c.pool
         f = p.fields
         cur = (f["window"] & np.uint64(7)).astype(np.int64)
         nxt = ((f["window"] >> np.uint64(3)) & np.uint64(7)).astype(np.int64)
         self.idx = np.flatnonzero(p.running & (nxt <= 6))      # the oracle has no piece 7
+        if most is not None and self.idx.size > most:
+            self.idx = self.idx[np.linspace(0, self.idx.size - 1, most).astype(np.int64)]
         K = self.idx.size
         self.done1 = p.done[self.idx]                          # [K, 40]: the first move ends the game
         self.distinct2 = _m().canonical_actions(nxt[self.idx][:, None], ARANGE[None, :]) == ARANGE[None, :]
@@ -73,15 +78,19 @@ class TwoPly:
                     count["both_clear"] += n1 > 0 and n2 > 0
                     if n1 + n2 <= 4:
                         count["cleared"][n1 + n2] += 1
-        where, rows2, head = np.array(where), np.array(rows2, np.uint16), np.array(head, np.int64)
-        self.pairs = where.shape[0]
-        board = np.concatenate([_m().board_features(rows2[at:at + 32768]) for at in range(0, self.pairs, 32768)])
+        self.pairs = len(where)
         self.phi2 = np.zeros((K, 40, 40, NF), np.int16)
-        self.phi2[where[:, 0], where[:, 1], where[:, 2], :3] = head
-        self.phi2[where[:, 0], where[:, 1], where[:, 2], 3:] = board
+        if self.pairs:                                         # none where every first move ends the game (M = 1)
+            where, rows2, head = np.array(where), np.array(rows2, np.uint16), np.array(head, np.int64)
+            board = np.concatenate([_m().board_features(rows2[at:at + 32768]) for at in range(0, self.pairs, 32768)])
+            self.phi2[where[:, 0], where[:, 1], where[:, 2], :3] = head
+            self.phi2[where[:, 0], where[:, 1], where[:, 2], 3:] = board
         self.phi1 = c.phi[self.idx]
         self.distinct1 = c.distinct[self.idx]
         print(f"{K} states, {self.pairs} (a, b) pairs; the oracle's outcomes: {count}")
+        self.count = count
+        if not own:
+            return
         # the coverage conditions, on the oracle's own outcomes
         assert K >= 1000 and set(nxt[self.idx].tolist()) == set(range(7))
         for name in ("first_move_ends", "win2", "limit2", "topout2", "both_clear"):
