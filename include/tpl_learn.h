@@ -2,7 +2,8 @@
  * tpl_learn.h -- C ABI of the learner library (libtpl_learn.so): a packed replay ring on the device, its samplers (uniform,
  * prioritized, n-step, each optionally mirrored), device-side packing of a PolicyMLP's parameters into the three policy
  * images of libtetris_piclim.so, the enumeration of a board's 40 afterstates, and board features of every placement with a
- * linear placement policy on them: one ply, two plies, or a beam over the known piece window.
+ * linear placement policy on them: one ply, two plies, or a beam over the known piece window; and a learned evaluation of the board a
+ * placement leaves: an n-tuple value function with its placement policy and its temporal-difference update.
  *
  * Conventions (as include/tetris_piclim.h)
  *   - every function returns 0 on success or a negative tpl_status (TPL_ERR_ARG, TPL_ERR_HIP, ...);
@@ -189,7 +190,9 @@ int tpl_mirror_states(int64_t count, const void* a, const void* b, void* out_a, 
  * canonical[a] = 10 * (r mod nrot(cur)) + min(l, 10 - w(cur, r)): cur = window entry 0 of s, nrot = TPL_PIECE_ROTATIONS,
  * w = the width of shape table entry [cur][r] as the table stands (so cur = 7 reads O's).  Two actions with one canonical value
  * are the same placement -- the right clamp and `rotations % len` alias 6 to 31 of the 40 -- and a == canonical[a] marks the
- * distinct ones: 17 for I, 34 for L, J and T, 17 for S and Z, 9 for O.  canonical is computed for finished boards too.
+ * distinct ones: 17 for I, 34 for L, J and T, 17 for S and Z, 9 for O.  canonical is computed for finished boards too.  (So a
+ * uniform draw over 0..39 is not uniform over placements: it plays the right-most location most often.  tpl_ntuple_act below
+ * explores uniformly over the DISTINCT placements.)
  *
  * Relation to the step: for a running board the afterstate is what a non-auto-reset tpl_step with the same reward parameters
  * leaves in the planes, and reward and done are the step's -- with ONE exception: on the move at which the environment refills
@@ -236,7 +239,7 @@ int32_t tpl_canonical_action(int32_t cur, int32_t action);
  * move_board keeps to itself.
  *
  * Score: with weights w[12] (float32), score = w_0 phi_0 + w_1 phi_1 + ... + w_11 phi_11 from left to right in float32: every
- * phi_f converts exactly, every product and every sum is rounded once, never fused (afterstate_reward's discipline).
+ * phi_f converts exactly, every product and every sum is rounded once, never fused (move_reward's discipline).
  * Choice: the arg-max of the score over the distinct placements (a == canonical[a]), the lowest a on ties (-0 and +0 tie).  A
  * finished board so gets action 0 and the score of twelve zeros.  THE WEIGHTS MUST BE FINITE (device memory cannot be checked
  * here), and of a size that no score overflows: the choice among scores that are not numbers is unspecified, though it is still
@@ -325,6 +328,58 @@ int tpl_placement_search(const void* plane_a, const void* plane_b, int64_t n, in
 int tpl_placement_beam(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const float* weights,
                        int64_t boards_per_member, int32_t depth, int32_t width, uint8_t* action, uint8_t* plan,
                        float* score, void* stream);
+
+/* An n-tuple afterstate value function, its placement policy and its temporal-difference update (csrc/learn/ntuple.hip).
+ *
+ * Table: TPL_NTUPLE_ENTRIES = 8 * 153 * 256 + 1024 = 314,368 int32 entries (1,257,472 bytes), 16-byte aligned, in units of 2^-16:
+ *   tuple[p][t][q] at index (p * 153 + t) * 256 + q      p in 0..7, t in 0..152, q in 0..255
+ *   counter[k]     at index 313,344 + k                   k in 0..1023
+ * Patterns of a state s with column words c_0 .. c_9 (bit r = row r, row 0 = top): a tuple is t = 17 x + y, x in 0..8, y in 0..16,
+ * and its pattern is  q(s, t) = ((c_x >> y) & 15) | (((c_{x+1} >> y) & 15) << 4)  -- two adjacent columns by four rows.  The piece
+ * index p is window entry 0 of s (0..7), and the counter index is  k = 64 min(max(L - lines, 0), 15) + min(max(M - moves, 0), 63).
+ * Value: V(s) = 0 for a state that is not running; otherwise
+ *   V(s) = float32( sum over the t with q(s, t) != 0 of tuple[p][t][q(s, t)]  +  counter[k] ) * 2^-16
+ * -- the sum exact in 64-bit integers, ONE rounding at the conversion, the scaling exact.  The all-empty pattern contributes nothing
+ * and is never updated: it is most of a typical board, and it would be the one address that every board adds to.
+ *
+ * Policy on a state s, with reward parameters (r_line, r_win, r_lose) and a discount gamma:
+ *   Finished board (state(s) != running): action 0, score 0; its afterstate is s itself, bit for bit, with value 0.
+ *   Running board: every distinct placement a (a == canonical(cur, a)) gives (s_a, r_a, done_a) exactly as tpl_afterstates makes
+ *   them;  score(a) = r_a if done_a, else r_a + gamma * V(s_a)  in float32: one rounded multiply and one rounded add, never fused.
+ *   The greedy action is the lowest a at the maximum of score (-0 and +0 tie).
+ * Exploration: h_i = position i + 1 of the splitmix64 stream keyed by (seed, step) -- the samplers' hash, with `step` where they
+ * have `update`.  A running board i explores iff (h_i >> 40) < (uint32)(epsilon * 2^24); it then plays the j-th distinct placement
+ * of its current piece in ascending order, j = ((h_i & 0xFFFFFFFF) * S) >> 32 with S the number of distinct placements (17, 34 or
+ * 9, above): uniform over placements, not over the 40 actions.  `score` is ALWAYS the greedy maximum -- it is the TD target --
+ * while `after` and `value` (V of `after`; 0 where the move ended the game) belong to the action that is played.
+ *
+ * Update, for each of n states with an error e_i: a state that is not running adds nothing; otherwise
+ *   d_i = (int32) rint(rate * e_i)   -- the product rounded once in float32, clamped to +-2^24, 0 for a NaN --
+ * is added to counter[k] and to tuple[p][t][q] of every tuple with a non-zero pattern.  The adds wrap as two's complement (the
+ * caller keeps entries small).  The kernel only adds and never reads the table, so the table that results is the same whatever
+ * order the adds arrive in: no float atomic, and two runs give the same bytes. */
+#define TPL_NTUPLE_ENTRIES 314368
+
+/* V of each of `n` states: plane_a / plane_b [n] 16-byte words (read only), table int32 [TPL_NTUPLE_ENTRIES] -> value f32 [n].
+ * Refused before any HIP call: n < 1, 40 n >= 2^31, a NULL or misaligned (16 bytes) plane pointer, L outside [1, 250] or M
+ * outside [1, 254] (tpl_afterstates' checks), table NULL or not 16-byte aligned, value NULL or not 4-byte aligned. */
+int tpl_ntuple_value(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const int32_t* table,
+                     float* value, void* stream);
+
+/* The policy above on each of `n` states in one kernel: 32 bytes read per board besides the table gathers (at most 153 per
+ * distinct placement that leaves the game running), and at most 1 + 4 + 32 + 4 bytes written: action u8 [n]; score f32 [n]
+ * (optional); after_a / after_b [n] 16-byte words (both or neither); value f32 [n] (optional).  An output that is not given is not
+ * written.  The afterstate comes out of the registers of the lane that made the chosen move.  Refused before any HIP call:
+ * tpl_ntuple_value's plane, n, L, M and table checks, action NULL, only one of after_a / after_b or either misaligned (16 bytes),
+ * score or value not 4-byte aligned, epsilon outside [0, 1] (a NaN included), gamma not finite. */
+int tpl_ntuple_act(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line, float r_win,
+                   float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed, uint64_t step, uint8_t* action,
+                   float* score, void* after_a, void* after_b, float* value, void* stream);
+
+/* The update above: error f32 [n], one per state of plane_a / plane_b.  Refused before any HIP call: tpl_ntuple_value's plane, n,
+ * L, M and table checks, error NULL or not 4-byte aligned, rate not finite. */
+int tpl_ntuple_update(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, int32_t* table,
+                      const float* error, float rate, void* stream);
 
 #ifdef __cplusplus
 }

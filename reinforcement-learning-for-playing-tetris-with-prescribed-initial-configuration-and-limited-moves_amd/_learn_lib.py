@@ -1,5 +1,5 @@
 """Build and bind the learner's C-ABI library (include/tpl_learn.h) with ctypes: the packed replay ring and the device-side
-policy packers (csrc/learn/).
+policy packers (csrc/learn/), and the numpy mirrors of their rules that the tests check the kernels against.
 
 A library of its own (<repo>/lib/libtpl_learn.so), so that the environment library and its measured sources stay as they
 are: it includes the environment's device headers read-only and links nothing of libtetris_piclim.so.  Built, stamped and
@@ -21,7 +21,7 @@ from ._lib import TplError, _hipcc
 _LEARN_CSRC = os.path.join(_lib._CSRC, "learn")
 LEARN_LIB_PATH = os.path.join(_lib._LIBDIR, "libtpl_learn.so")
 _UNITS = [os.path.join(_LEARN_CSRC, f) for f in ("replay.hip", "pack.hip", "priority.hip", "afterstates.hip",
-                                                      "beam.hip", "heuristic.hip")]
+                                                      "beam.hip", "ntuple.hip", "heuristic.hip")]
 
 # entry points declared in include/tpl_learn.h (tests check that the .so exports every one of them)
 LEARN_SYMBOLS = [
@@ -29,7 +29,7 @@ LEARN_SYMBOLS = [
     "tpl_learn_image_bytes", "tpl_learn_pack", "tpl_priority_tree_bytes", "tpl_priority_init", "tpl_priority_push",
     "tpl_priority_update", "tpl_replay_sample_prioritized", "tpl_priority_target", "tpl_replay_sample_nstep",
     "tpl_replay_sample_mirror", "tpl_mirror_states", "tpl_afterstates", "tpl_canonical_action", "tpl_placement_features",
-    "tpl_placement_act", "tpl_placement_search", "tpl_placement_beam",
+    "tpl_placement_act", "tpl_placement_search", "tpl_placement_beam", "tpl_ntuple_value", "tpl_ntuple_act", "tpl_ntuple_update",
 ]
 NSTEP_MAX = 16
 BEAM_MAX_DEPTH, BEAM_MAX_WIDTH = 12, 64
@@ -135,10 +135,14 @@ def lib() -> C.CDLL:
     L.tpl_placement_act.argtypes = [vp, vp, i64, i32, i32, vp, i64, vp, vp, vp]
     L.tpl_placement_search.argtypes = [vp, vp, i64, i32, i32, vp, i64, vp, vp, vp, vp]
     L.tpl_placement_beam.argtypes = [vp, vp, i64, i32, i32, vp, i64, i32, i32, vp, vp, vp, vp]
+    f32 = C.c_float
+    L.tpl_ntuple_value.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp]
+    L.tpl_ntuple_act.argtypes = [vp, vp, i64, i32, i32, f32, f32, f32, f32, vp, f32, u64, u64, vp, vp, vp, vp, vp, vp]
+    L.tpl_ntuple_update.argtypes = [vp, vp, i64, i32, i32, vp, vp, f32, vp]
     for name in ("tpl_replay_push", "tpl_replay_sample", "tpl_learn_pack", "tpl_priority_init", "tpl_priority_push",
                  "tpl_priority_update", "tpl_replay_sample_prioritized", "tpl_replay_sample_nstep", "tpl_replay_sample_mirror",
                  "tpl_mirror_states", "tpl_afterstates", "tpl_placement_features", "tpl_placement_act",
-                 "tpl_placement_search", "tpl_placement_beam"):
+                 "tpl_placement_search", "tpl_placement_beam", "tpl_ntuple_value", "tpl_ntuple_act", "tpl_ntuple_update"):
         getattr(L, name).restype = i32
     _handle = L
     return L
@@ -504,6 +508,87 @@ def beam_select(values, width: int) -> np.ndarray:
         raise ValueError(f"width must be an integer in [1, {BEAM_MAX_WIDTH}]")
     order = np.argsort(-(v + np.float32(0.0)), kind="stable")  # x + 0 makes -0 a +0; stable: the lower index first among equals
     return np.sort(order[:int(width)]).astype(np.int64)
+
+
+# ------------------------------------------------------------------------------------------------ the n-tuple value function
+# The table layout, the value and the update of include/tpl_learn.h on the host, from the ROW form of a board (uint16 [20], bit x =
+# column x): the device works on column words with two shifts and a mask (csrc/learn/ntuple.hip) -- the two share nothing.
+NTUPLE_PIECES, NTUPLE_TUPLES, NTUPLE_PATTERNS, NTUPLE_COUNTERS = 8, 153, 256, 1024
+NTUPLE_COUNTER_BASE = NTUPLE_PIECES * NTUPLE_TUPLES * NTUPLE_PATTERNS                   # 313,344
+NTUPLE_ENTRIES = NTUPLE_COUNTER_BASE + NTUPLE_COUNTERS                                   # 314,368
+NTUPLE_STEP_MAX = 1 << 24                                                               # |d| of one update is clamped to it
+PIECE_PLACEMENTS = (17, 34, 34, 34, 17, 17, 9, 9)        # S: the distinct placements of each piece id (7 reads O's entry)
+
+
+def ntuple_indices(rows, piece, L: int, M: int, lines, moves):
+    """Where the value of K boards lives in the table: (index int64 [K, 154], used bool [K, 154]).  Column t < 153 is tuple
+    t = 17 x + y -- cell (row y + j, column x) is bit j and cell (row y + j, column x + 1) bit 4 + j of its pattern q, j < 4 --
+    at index (piece * 153 + t) * 256 + q, used where q != 0; column 153 is the counter entry 313,344 + 64 min(max(L - lines, 0),
+    15) + min(max(M - moves, 0), 63), always used.  rows: uint16 [K, 20] or [20] row masks (bit x = column x, row 0 = top)."""
+    rows = np.asarray(rows)
+    if rows.ndim == 1:
+        rows = rows[None]
+    if rows.ndim != 2 or rows.shape[1] != 20:
+        raise ValueError("rows must be [K, 20] row masks")
+    k = rows.shape[0]
+    piece, lines, moves = (np.broadcast_to(np.asarray(v, dtype=np.int64), (k,)) for v in (piece, lines, moves))
+    if k and (piece.min() < 0 or piece.max() >= NTUPLE_PIECES):
+        raise ValueError("piece must be in 0..7")
+    cell = (rows.astype(np.int64)[:, :, None] >> np.arange(10)[None, None, :]) & 1              # [K, 20, 10]
+    index = np.zeros((k, NTUPLE_TUPLES + 1), dtype=np.int64)
+    used = np.ones((k, NTUPLE_TUPLES + 1), dtype=bool)
+    for x in range(9):
+        for y in range(17):
+            q = np.zeros(k, dtype=np.int64)
+            for j in range(4):
+                q |= (cell[:, y + j, x] << j) | (cell[:, y + j, x + 1] << (4 + j))
+            t = 17 * x + y
+            index[:, t] = (piece * NTUPLE_TUPLES + t) * NTUPLE_PATTERNS + q
+            used[:, t] = q != 0
+    index[:, NTUPLE_TUPLES] = (NTUPLE_COUNTER_BASE + 64 * np.clip(int(L) - lines, 0, 15) + np.clip(int(M) - moves, 0, 63))
+    return index, used
+
+
+def _ntuple_table(table) -> np.ndarray:
+    if not isinstance(table, np.ndarray) or table.dtype != np.int32 or table.shape != (NTUPLE_ENTRIES,):
+        raise ValueError(f"table must be an int32 array of {NTUPLE_ENTRIES} entries")
+    return table
+
+
+def ntuple_value(table, rows, piece, L: int, M: int, lines, moves, state) -> np.ndarray:
+    """V of K states (float32 [K]): 0 where state != 0, else the entries ntuple_indices names summed exactly (int64), rounded
+    once to float32 and scaled by 2^-16."""
+    index, used = ntuple_indices(rows, piece, L, M, lines, moves)
+    total = np.where(used, _ntuple_table(table)[index].astype(np.int64), 0).sum(axis=1)
+    running = np.broadcast_to(np.asarray(state), total.shape) == 0
+    return np.where(running, total.astype(np.float32) * np.float32(2.0 ** -16), np.float32(0.0)).astype(np.float32)
+
+
+def ntuple_steps(error, rate) -> np.ndarray:
+    """d = (int32) rint(rate * e): the float32 product rounded once, clamped to +-2^24, 0 for a NaN (int64 [K])."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        x = np.float32(rate) * np.asarray(error, dtype=np.float32)
+    x = np.where(np.isnan(x), np.float32(0.0), np.clip(x, -float(NTUPLE_STEP_MAX), float(NTUPLE_STEP_MAX)))
+    return np.rint(x).astype(np.int64)
+
+
+def ntuple_update(table, rows, piece, L: int, M: int, lines, moves, state, error, rate) -> np.ndarray:
+    """tpl_ntuple_update, in place: every running state adds its d to the entries ntuple_indices names; the adds wrap."""
+    index, used = ntuple_indices(rows, piece, L, M, lines, moves)
+    d = np.where(np.broadcast_to(np.asarray(state), index.shape[:1]) == 0, ntuple_steps(error, rate), 0)
+    used = used & (d != 0)[:, None]
+    np.add.at(_ntuple_table(table).view(np.uint32), index[used], np.broadcast_to(d[:, None], used.shape)[used].astype(np.uint32))
+    return table
+
+
+def ntuple_explore(seed: int, step: int, n: int, epsilon: float, placements):
+    """The exploration draw of tpl_ntuple_act for boards 0 .. n - 1: (explores bool [n], j int64 [n]) -- a RUNNING board i explores
+    iff (h_i >> 40) < (uint32)(epsilon * 2^24) and then plays the j-th of its `placements` (S, int [n] or a number) distinct
+    placements in ascending order, j = ((h_i & 0xFFFFFFFF) * S) >> 32; h = _draw_hashes(seed, step, n)."""
+    h = _draw_hashes(seed, step, n)
+    below = np.uint64(int(np.float32(epsilon) * np.float32(2.0 ** 24)))
+    s = np.broadcast_to(np.asarray(placements, dtype=np.uint64), (n,))
+    return (h >> np.uint64(40)) < below, (((h & _M32) * s) >> np.uint64(32)).astype(np.int64)
 
 
 # ------------------------------------------------------------------------------------------------ device packing

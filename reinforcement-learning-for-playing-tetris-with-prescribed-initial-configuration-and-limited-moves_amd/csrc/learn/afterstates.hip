@@ -34,16 +34,6 @@ struct AfterArgs {
     uint8_t* canonical;
 };
 
-// step_reward's rule (csrc/tpl_step.h): one rounded multiply, then at most one rounded add; contraction off, or the pair
-// becomes an FMA whose single rounding differs where r_line * n is not exact
-__device__ __forceinline__ float afterstate_reward(const AfterArgs& p, uint32_t n_clear, uint32_t state) {
-#pragma clang fp contract(off)
-    float reward = p.r_line * (float)n_clear;
-    if (state == tpl::ST_WON) reward = reward + p.r_win;
-    if (state >= tpl::ST_LOST_LIMIT) reward = reward + p.r_lose;
-    return reward;
-}
-
 __global__ __launch_bounds__(kAfterBlock) void afterstates_kernel(const AfterArgs p) {
     __shared__ tpl::ShapeWord s_shape[32];
     if (threadIdx.x < 32) s_shape[threadIdx.x] = tpl::kShapeTable[threadIdx.x];
@@ -58,7 +48,7 @@ __global__ __launch_bounds__(kAfterBlock) void afterstates_kernel(const AfterArg
     bool running;
     const uint32_t n_clear = first_move(A, B, s_shape, r, l, p.L, p.M, s, cur, running);
     tpl::next_window(s, false, 0);                                      // pieces.pop(0) without a refill: zeros enter
-    const float reward = afterstate_reward(p, n_clear, s.state);
+    const float reward = move_reward(p.r_line, p.r_win, p.r_lose, n_clear, s.state);
 
     // a finished board stays as it is, bit for bit, with reward 0, done 1, cleared 0 (a frozen board of tpl_step): selects
     if (p.out_a) {

@@ -1,0 +1,317 @@
+// ntuple.hip -- an n-tuple afterstate value function, its greedy / epsilon-greedy placement policy and its temporal-difference
+// update: tpl_ntuple_value, tpl_ntuple_act, tpl_ntuple_update (include/tpl_learn.h states the rule).
+//
+// The value of a board is a sum of table look-ups: 153 windows of two adjacent columns by four rows, each a 256-entry row of an
+// int32 table chosen by the piece that falls next, plus one entry for the lines and moves that are left.  In the column layout a
+// window's pattern is two shifts and two masks on column words that move_board leaves in registers, the sum is an exact integer,
+// and the update is integer adds -- so value, policy and update are bit-reproducible whatever order anything runs in.
+//
+// Lane mapping.  value and update: a lane per state; a lane's 153 gathers (or adds) go out nine at a time, one trip of a loop
+// over the window's top row y per nine column pairs, so nine are in flight per lane.  act: a lane per (board, action) PAIR in
+// placement_policy's frame (heuristic.hip: blocks of 320 threads = 8 boards x 40 actions, first_move, a 64-bit LDS maximum on
+// ordered score << 32 | 39 - a): the lanes of the distinct placements that leave the game running evaluate the board their move
+// left, the chosen lane packs that board from its own registers -- nothing is enumerated twice.  The mapping rejected for act
+// is a lane per board looping over the placements: it would have a fortieth of the gathers in flight, and the gathers, not the
+// moves, are what a pair costs (DESIGN.md section 9 has the counts).
+//
+// The all-empty pattern contributes nothing and is never updated: it is most of a board, and it would be the one address every
+// board adds to.  The look-up is still made (the address is in bounds, and the 64 lanes of a wave share it where their pieces
+// agree) and dropped by a select, so that the gathers stay straight-line code.  The counter entries -- 1,024, shared by every
+// board with the same lines and moves left, which boards in lockstep have -- are summed per block in LDS first and only the
+// non-zero sums go to memory.
+#include <cmath>
+
+#include "tpl_placement.h"
+
+namespace tpl_learn {
+namespace {
+
+constexpr int kTupleCols = tpl::kCols - 1;                    // x = 0..8: columns x and x + 1
+constexpr int kTupleRows = tpl::kRows - 3;                    // y = 0..16: rows y .. y + 3
+constexpr int kTuples = kTupleCols * kTupleRows;              // 153
+constexpr int kPatterns = 256;
+constexpr int kPieceStride = kTuples * kPatterns;
+constexpr int kCounterBase = 8 * kPieceStride;                // 313,344
+constexpr int kCounterLines = 16, kCounterMoves = 64;
+constexpr int kCounters = kCounterLines * kCounterMoves;      // 1,024
+static_assert(kCounterBase + kCounters == TPL_NTUPLE_ENTRIES, "the table layout of include/tpl_learn.h");
+
+constexpr int kStateBlock = 256;                              // value and update: a lane per state
+constexpr int kBoardsPerBlock = 8;
+constexpr int kActBlock = kBoardsPerBlock * kActions;         // act: 320 threads, five waves, eight whole boards
+static_assert(kActBlock % 64 == 0, "a block is whole waves");
+static_assert(kCounters % kStateBlock == 0, "the counter sums are zeroed and flushed in whole rounds of a block");
+
+// k = 64 min(max(L - lines, 0), 15) + min(max(M - moves, 0), 63)
+__device__ __forceinline__ uint32_t counter_index(uint32_t L, uint32_t M, uint32_t lines, uint32_t moves) {
+    const int left_l = min(max((int)L - (int)lines, 0), kCounterLines - 1);
+    const int left_m = min(max((int)M - (int)moves, 0), kCounterMoves - 1);
+    return (uint32_t)(left_l * kCounterMoves + left_m);
+}
+
+// the pattern of tuple (x, y) given the two columns' nibbles at row y
+__device__ __forceinline__ uint32_t pattern(uint32_t c_left, uint32_t c_right, uint32_t y) {
+    return ((c_left >> y) & 15u) | (((c_right >> y) & 15u) << 4);
+}
+
+// entry `index` of the table through a 32-bit byte offset from the (uniform) base: the whole table is 1.2 MB, and an index the
+// compiler has to widen costs a 64-bit shift and a 64-bit add per look-up
+template <typename T>
+__device__ __forceinline__ T* entry(T* table, uint32_t index) {
+    return (T*)((const char*)table + index * (uint32_t)sizeof(T));
+}
+
+// The integer value of a running board with column words c (bits 20.. clear), falling piece `piece` and counter entry k: the
+// sum over the tuples with a non-zero pattern plus the counter, exact in 64 bits.
+__device__ __forceinline__ long long ntuple_sum(const uint32_t (&c)[tpl::kCols], uint32_t piece, uint32_t k, const int32_t* table) {
+    const uint32_t base = piece * (uint32_t)kPieceStride;
+    long long sum = *entry(table, (uint32_t)kCounterBase + k);
+#pragma unroll 1
+    for (uint32_t y = 0; y < (uint32_t)kTupleRows; ++y) {
+        int32_t v[kTupleCols];
+#pragma unroll
+        for (int x = 0; x < kTupleCols; ++x) {
+            const uint32_t q = pattern(c[x], c[x + 1], y);
+            const int32_t e = *entry(table, base + ((uint32_t)(x * kTupleRows) + y) * (uint32_t)kPatterns + q);
+            v[x] = q ? e : 0;
+        }
+#pragma unroll
+        for (int x = 0; x < kTupleCols; ++x) sum += v[x];
+    }
+    return sum;
+}
+
+// V of a state that runs: one rounding from the 64-bit sum to float32, then an exact scaling by 2^-16
+__device__ __forceinline__ float ntuple_value(const tpl::Board& s, uint32_t L, uint32_t M, const int32_t* table) {
+    const long long sum = ntuple_sum(s.c, s.window & 7u, counter_index(L, M, s.lines, s.moves), table);
+    return (float)sum * 0x1p-16f;
+}
+
+struct ValueArgs {
+    const uint4* a;              // [n]
+    const uint4* b;
+    uint32_t n;
+    uint32_t L, M;
+    const int32_t* table;        // [TPL_NTUPLE_ENTRIES]
+    float* value;                // [n]
+};
+
+__global__ __launch_bounds__(kStateBlock) void ntuple_value_kernel(const ValueArgs p) {
+    const uint32_t i = blockIdx.x * kStateBlock + threadIdx.x;
+    if (i >= p.n) return;
+    tpl::Board s;
+    tpl::unpack_board(p.a[i], p.b[i], s);
+    float v = 0.0f;
+    if (s.state == tpl::ST_RUNNING) v = ntuple_value(s, p.L, p.M, p.table);
+    p.value[i] = v;
+}
+
+struct UpdateArgs {
+    const uint4* a;              // [n]
+    const uint4* b;
+    uint32_t n;
+    uint32_t L, M;
+    uint32_t* table;             // [TPL_NTUPLE_ENTRIES]: added to, never read; unsigned so that the adds wrap
+    const float* error;          // [n]
+    float rate;
+};
+
+// d = (int32) rint(rate * e): the product rounded once, clamped to +-2^24, 0 for a NaN
+__device__ __forceinline__ int32_t update_step(float rate, float e) {
+    const float x = rate * e;
+    if (x != x) return 0;
+    return (int32_t)rintf(fminf(fmaxf(x, -0x1p24f), 0x1p24f));
+}
+
+__global__ __launch_bounds__(kStateBlock) void ntuple_update_kernel(const UpdateArgs p) {
+    __shared__ uint32_t s_counter[kCounters];
+#pragma unroll
+    for (int t = threadIdx.x; t < kCounters; t += kStateBlock) s_counter[t] = 0u;
+    __syncthreads();
+    const uint32_t i = blockIdx.x * kStateBlock + threadIdx.x;
+    if (i < p.n) {
+        tpl::Board s;
+        tpl::unpack_board(p.a[i], p.b[i], s);
+        const uint32_t d = (uint32_t)update_step(p.rate, p.error[i]);
+        if (s.state == tpl::ST_RUNNING && d != 0u) {
+            atomicAdd(&s_counter[counter_index(p.L, p.M, s.lines, s.moves)], d);
+            const uint32_t base = (s.window & 7u) * (uint32_t)kPieceStride;
+#pragma unroll 1
+            for (uint32_t y = 0; y < (uint32_t)kTupleRows; ++y) {
+#pragma unroll
+                for (int x = 0; x < kTupleCols; ++x) {
+                    const uint32_t q = pattern(s.c[x], s.c[x + 1], y);
+                    if (q) atomicAdd(entry(p.table, base + ((uint32_t)(x * kTupleRows) + y) * (uint32_t)kPatterns + q), d);
+                }
+            }
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int t = threadIdx.x; t < kCounters; t += kStateBlock) {
+        const uint32_t sum = s_counter[t];
+        if (sum) atomicAdd(p.table + kCounterBase + t, sum);
+    }
+}
+
+struct ActArgs {
+    const uint4* a;              // [n]
+    const uint4* b;
+    uint32_t n;                  // boards; 40 n below 2^31
+    uint32_t L, M;
+    float r_line, r_win, r_lose, gamma;
+    const int32_t* table;
+    uint32_t explore_below;      // (uint32)(epsilon * 2^24): a board explores iff the top 24 bits of its hash are below
+    uint64_t key;                // replay_key(seed, step)
+    uint8_t* action;             // [n]
+    float* score;                // [n], optional: the greedy maximum
+    uint4* after_a;              // [n], with after_b or not at all: the chosen placement's afterstate
+    uint4* after_b;
+    float* value;                // [n], optional: V of that afterstate
+};
+
+constexpr uint32_t kGreedy = 0xFFFFFFFFu;
+
+// 10 - w(cur, r): the right-most location of rotation r
+__device__ __forceinline__ uint32_t right_most(uint32_t cur, uint32_t r) {
+    return 9u - ((uint32_t)(kWidthsLess1 >> (2u * (cur * 4u + r))) & 3u);
+}
+
+__global__ __launch_bounds__(kActBlock) void ntuple_act_kernel(const ActArgs p) {
+    __shared__ tpl::ShapeWord s_shape[32];
+    __shared__ unsigned long long s_best[kBoardsPerBlock];
+    __shared__ uint32_t s_pick[kBoardsPerBlock];                        // which distinct placement an exploring board plays
+    const uint32_t first = blockIdx.x * kBoardsPerBlock;                // the block's boards: first .. first + 7
+    if (threadIdx.x < 32) s_shape[threadIdx.x] = tpl::kShapeTable[threadIdx.x];
+    if (threadIdx.x < kBoardsPerBlock) {
+        s_best[threadIdx.x] = 0ull;                                     // below every key: a key's high word has a bit set
+        const uint32_t board = min(first + threadIdx.x, p.n - 1u);
+        const uint4 B = p.b[board];
+        const uint32_t cur = B.w & 7u, last_rot = (kRotationMasks >> (2u * cur)) & 3u;
+        uint32_t distinct = 0u;
+#pragma unroll
+        for (uint32_t r = 0; r < 4u; ++r) distinct += r <= last_rot ? right_most(cur, r) + 1u : 0u;
+        const uint64_t h = draw_hash(p.key, board);
+        const bool explores = tpl::packed_state(B) == tpl::ST_RUNNING && (uint32_t)(h >> 40) < p.explore_below;
+        s_pick[threadIdx.x] = explores ? __umulhi((uint32_t)h, distinct) : kGreedy;
+    }
+    __syncthreads();
+    const uint32_t slot = threadIdx.x / kActions, a = threadIdx.x - slot * kActions;
+    const uint32_t r = a / 10u, l = a - r * 10u;
+    const uint32_t i = first + slot;
+    const bool valid = i < p.n;                                         // whole boards: all 40 lanes of a board agree
+    const uint32_t src = valid ? i : p.n - 1u;                          // past the end: the last board again, never written
+
+    const uint4 A = p.a[src], B = p.b[src];
+    tpl::Board s1;
+    uint32_t cur;
+    bool running;
+    const uint32_t n1 = first_move(A, B, s_shape, r, l, p.L, p.M, s1, cur, running);
+    tpl::next_window(s1, false, 0);                                     // tpl_afterstates' pop: the next piece becomes current
+    const bool contends = valid && canonical_action(cur, r, l) == a;
+    const bool goes_on = running && s1.state == tpl::ST_RUNNING;
+    // the rank of a distinct placement among its piece's, in ascending a: the locations of the rotations before it, then l
+    uint32_t rank = l;
+#pragma unroll
+    for (uint32_t q = 0; q < 3u; ++q) rank += q < r ? right_most(cur, q) + 1u : 0u;
+
+    float v = 0.0f;                                                     // V of a state that does not run
+    if (contends && goes_on) v = ntuple_value(s1, p.L, p.M, p.table);
+    float score;
+    {
+#pragma clang fp contract(off)
+        const float reward = move_reward(p.r_line, p.r_win, p.r_lose, n1, s1.state);
+        const float later = p.gamma * v;
+        score = running ? (goes_on ? reward + later : reward) : 0.0f;
+    }
+    const unsigned long long key = ((unsigned long long)ordered_bits(score) << 32) | (uint32_t)(kActions - 1 - a);
+    if (contends) atomicMax(&s_best[slot], key);
+    __syncthreads();
+    const bool greedy = contends && s_best[slot] == key;                // one lane per board: the keys of a board are distinct
+    const uint32_t pick = s_pick[slot];
+    const bool chosen = pick == kGreedy ? greedy : contends && rank == pick;
+    if (greedy && p.score) p.score[i] = score;                          // the TD target, whatever is played
+    if (chosen) {
+        p.action[i] = (uint8_t)a;
+        if (p.value) p.value[i] = v;
+        if (p.after_a) {                                                // a finished board stays as it is, bit for bit
+            uint4 A2, B2;
+            tpl::pack_board(s1, A2, B2);
+            B2.y |= B.y & 0x80000000u;                                  // the spare bit (the slot travels in the Board)
+            p.after_a[i] = make_uint4(running ? A2.x : A.x, running ? A2.y : A.y, running ? A2.z : A.z, running ? A2.w : A.w);
+            p.after_b[i] = make_uint4(running ? B2.x : B.x, running ? B2.y : B.y, running ? B2.z : B.z, running ? B2.w : B.w);
+        }
+    }
+}
+
+// the checks the three entries share beyond check_planes
+int check_table(const char* name, const void* table) {
+    if (!table) return fail_msg(TPL_ERR_ARG, "%s: null pointer (table is required)", name);
+    if ((uintptr_t)table & 15u) return fail_msg(TPL_ERR_ARG, "%s: table must be 16-byte aligned", name);
+    return TPL_OK;
+}
+
+}  // namespace
+}  // namespace tpl_learn
+
+using namespace tpl_learn;
+
+extern "C" int tpl_ntuple_value(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const int32_t* table,
+                                float* value, void* stream) {
+    const char* name = "tpl_ntuple_value";
+    if (const int rc = check_planes(name, plane_a, plane_b, n, L, M)) return rc;
+    if (const int rc = check_table(name, table)) return rc;
+    if (!value) return fail_msg(TPL_ERR_ARG, "%s: null pointer (value is required)", name);
+    if ((uintptr_t)value & 3u) return fail_msg(TPL_ERR_ARG, "%s: value must be 4-byte aligned", name);
+    ValueArgs p{};
+    p.a = (const uint4*)plane_a; p.b = (const uint4*)plane_b; p.n = (uint32_t)n;
+    p.L = (uint32_t)L; p.M = (uint32_t)M; p.table = table; p.value = value;
+    const dim3 grid((p.n + kStateBlock - 1) / kStateBlock), block(kStateBlock);
+    hipLaunchKernelGGL(ntuple_value_kernel, grid, block, 0, (hipStream_t)stream, p);
+    TPL_LEARN_HIP(hipGetLastError());
+    return TPL_OK;
+}
+
+extern "C" int tpl_ntuple_act(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line, float r_win,
+                              float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed, uint64_t step,
+                              uint8_t* action, float* score, void* after_a, void* after_b, float* value, void* stream) {
+    const char* name = "tpl_ntuple_act";
+    if (const int rc = check_planes(name, plane_a, plane_b, n, L, M)) return rc;
+    if (const int rc = check_table(name, table)) return rc;
+    if (!action) return fail_msg(TPL_ERR_ARG, "%s: null pointer (action is required)", name);
+    if ((after_a == nullptr) != (after_b == nullptr)) return fail_msg(TPL_ERR_ARG, "%s: after_a and after_b go together", name);
+    if (((uintptr_t)after_a & 15u) || ((uintptr_t)after_b & 15u))
+        return fail_msg(TPL_ERR_ARG, "%s: after_a and after_b must be 16-byte aligned", name);
+    if (((uintptr_t)score & 3u) || ((uintptr_t)value & 3u))
+        return fail_msg(TPL_ERR_ARG, "%s: score and value must be 4-byte aligned", name);
+    if (!(epsilon >= 0.0f && epsilon <= 1.0f)) return fail_msg(TPL_ERR_ARG, "%s: epsilon must be in [0, 1]", name);
+    if (!std::isfinite(gamma)) return fail_msg(TPL_ERR_ARG, "%s: gamma must be finite", name);
+    ActArgs p{};
+    p.a = (const uint4*)plane_a; p.b = (const uint4*)plane_b; p.n = (uint32_t)n;
+    p.L = (uint32_t)L; p.M = (uint32_t)M; p.r_line = r_line; p.r_win = r_win; p.r_lose = r_lose; p.gamma = gamma;
+    p.table = table;
+    p.explore_below = (uint32_t)(epsilon * 0x1p24f);                    // exact: a power of two; 2^24 at epsilon = 1, above every hash
+    p.key = replay_key(seed, step);
+    p.action = action; p.score = score; p.after_a = (uint4*)after_a; p.after_b = (uint4*)after_b; p.value = value;
+    const dim3 grid((p.n + kBoardsPerBlock - 1) / kBoardsPerBlock), block(kActBlock);
+    hipLaunchKernelGGL(ntuple_act_kernel, grid, block, 0, (hipStream_t)stream, p);
+    TPL_LEARN_HIP(hipGetLastError());
+    return TPL_OK;
+}
+
+extern "C" int tpl_ntuple_update(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, int32_t* table,
+                                 const float* error, float rate, void* stream) {
+    const char* name = "tpl_ntuple_update";
+    if (const int rc = check_planes(name, plane_a, plane_b, n, L, M)) return rc;
+    if (const int rc = check_table(name, table)) return rc;
+    if (!error) return fail_msg(TPL_ERR_ARG, "%s: null pointer (error is required)", name);
+    if ((uintptr_t)error & 3u) return fail_msg(TPL_ERR_ARG, "%s: error must be 4-byte aligned", name);
+    if (!std::isfinite(rate)) return fail_msg(TPL_ERR_ARG, "%s: rate must be finite", name);
+    UpdateArgs p{};
+    p.a = (const uint4*)plane_a; p.b = (const uint4*)plane_b; p.n = (uint32_t)n;
+    p.L = (uint32_t)L; p.M = (uint32_t)M; p.table = (uint32_t*)table; p.error = error; p.rate = rate;
+    const dim3 grid((p.n + kStateBlock - 1) / kStateBlock), block(kStateBlock);
+    hipLaunchKernelGGL(ntuple_update_kernel, grid, block, 0, (hipStream_t)stream, p);
+    TPL_LEARN_HIP(hipGetLastError());
+    return TPL_OK;
+}

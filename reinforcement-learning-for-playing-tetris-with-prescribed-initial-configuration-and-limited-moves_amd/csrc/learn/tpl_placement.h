@@ -1,6 +1,6 @@
-// tpl_placement.h -- what the placement family shares (afterstates.hip, heuristic.hip, beam.hip; include/tpl_learn.h states the
-// rules): which of the 40 actions are one placement, the first move of a (board, action) pair, the board features, the score
-// and its ordered key, and the argument checks of the entry points that read a pair of state planes.
+// tpl_placement.h -- what the placement family shares (afterstates.hip, heuristic.hip, beam.hip, ntuple.hip; include/tpl_learn.h
+// states the rules): which of the 40 actions are one placement, the first move of a (board, action) pair and its reward, the
+// board features, the score and its ordered key, and the argument checks of the entry points that read a pair of state planes.
 #pragma once
 
 #include "tpl_learn_internal.h"
@@ -30,6 +30,16 @@ __device__ __forceinline__ uint32_t first_move(const uint4& A, const uint4& B, c
     running = s.state == tpl::ST_RUNNING;
     bool topout;
     return tpl::move_board(s, shape, r, l, L, M, topout);
+}
+
+// step_reward's rule (csrc/tpl_step.h) for a move that cleared n_clear rows and left `state`: one rounded multiply, then at most
+// one rounded add; contraction off, or the pair becomes an FMA whose single rounding differs where r_line * n is not exact
+__device__ __forceinline__ float move_reward(float r_line, float r_win, float r_lose, uint32_t n_clear, uint32_t state) {
+#pragma clang fp contract(off)
+    float reward = r_line * (float)n_clear;
+    if (state == tpl::ST_WON) reward = reward + r_win;
+    if (state >= tpl::ST_LOST_LIMIT) reward = reward + r_lose;
+    return reward;
 }
 
 struct Features { uint32_t f[kFeatures]; };
@@ -104,7 +114,7 @@ __device__ __forceinline__ void moved_features(const tpl::Board& s, uint32_t n_c
     for (int k = 0; k < kFeatures; ++k) out.f[k] = live ? out.f[k] : 0u;
 }
 
-// w . phi left to right in float32: every product and every sum rounded once -- contraction off, as afterstate_reward
+// w . phi left to right in float32: every product and every sum rounded once -- contraction off, as move_reward
 __device__ __forceinline__ float placement_score(const float (&w)[kFeatures], const Features& phi) {
 #pragma clang fp contract(off)
     float s = w[0] * (float)phi.f[0];

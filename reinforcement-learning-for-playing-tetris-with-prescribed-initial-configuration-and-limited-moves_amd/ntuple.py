@@ -1,0 +1,243 @@
+"""A learned evaluation of the board a placement leaves: an n-tuple network on afterstates, trained by temporal-difference
+learning on the device (the rule: include/tpl_learn.h; the kernels: csrc/learn/ntuple.hip).
+
+    ntuple_table(device)          a zeroed table: int32 [314,368], in units of 2^-16
+    ntuple_value(source, table)   V of every resident board of an environment, or of plane pairs
+    NTuplePolicy(env, table, gamma, epsilon, seed).act()
+                                  arg-max over the distinct placements of  r + gamma * V(afterstate)  in ONE launch; with epsilon a
+                                  board explores uniformly over its DISTINCT placements (not over the 40 actions, 6 to 31 of which
+                                  are aliases); act(score=, after=, value=) also gives the greedy score (the TD target), the
+                                  afterstate of the action played and its value
+    NTupleLearner(env, gamma, rate, epsilon, seed)
+                                  TD(0) on afterstates: train(steps), evaluate(steps); `table` is a plain tensor (torch.save it)
+
+The value is a sum of table entries, one per 2 x 4 window of the board that is not empty, chosen by the falling piece, plus one
+per (lines left, moves left); the update adds rint(rate * error) to the same entries.  Everything is integer, so two trainings
+with one seed give the same bytes.
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional
+
+import torch
+
+from . import _learn_lib
+from ._learn_lib import NTUPLE_ENTRIES, check
+from .lookahead import _MAX_BOARDS, _ptr, _state_ptrs
+
+__all__ = ["NTUPLE_ENTRIES", "ntuple_table", "ntuple_value", "NTuplePolicy", "NTupleLearner"]
+
+_STATE_WON = 1                                                 # bits 28..29 of B.y: 0 running, 1 won, 2 and 3 lost
+_FINISHED_B_Y = _STATE_WON << 28                               # B.y of a state that is finished and otherwise empty
+
+
+def ntuple_table(device="cuda:0") -> torch.Tensor:
+    """A zeroed n-tuple table on `device`: int32 [NTUPLE_ENTRIES]."""
+    return torch.zeros(NTUPLE_ENTRIES, dtype=torch.int32, device=device)
+
+
+def _table(table, device) -> torch.Tensor:
+    if (not isinstance(table, torch.Tensor) or table.dtype != torch.int32 or tuple(table.shape) != (NTUPLE_ENTRIES,)
+            or table.device != device or not table.is_contiguous()):
+        raise ValueError(f"table must be a contiguous int32 tensor of {NTUPLE_ENTRIES} entries on {device} (ntuple_table)")
+    return table
+
+
+def _unit(name: str, v) -> float:
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 <= float(v) <= 1.0:
+        raise ValueError(f"{name} must be a number in [0, 1], got {v!r}")
+    return float(v)
+
+
+def _finite(name: str, v) -> float:
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(float(v)):
+        raise ValueError(f"{name} must be a finite number, got {v!r}")
+    return float(v)
+
+
+def _count(name: str, v, least: int = 0) -> int:
+    if isinstance(v, bool) or not isinstance(v, int) or v < least:
+        raise ValueError(f"{name} must be an integer of at least {least}, got {v!r}")
+    return int(v)
+
+
+def _boards(env, who: str) -> int:
+    n = int(env.num_envs)
+    if not 1 <= n <= _MAX_BOARDS:
+        raise ValueError(f"{who} takes an environment of 1 .. {_MAX_BOARDS} boards (40 N must stay below 2^31)")
+    return n
+
+
+def _planes(pair, device, what: str):
+    """A pair of int32 [K, 4] planes on `device` (None: wherever the first one is), checked: (K, a, b)."""
+    if not isinstance(pair, (tuple, list)) or len(pair) != 2 or not isinstance(pair[0], torch.Tensor):
+        raise ValueError(f"{what} must be a pair of int32 [K, 4] tensors")
+    a, b = pair
+    device = a.device if device is None else device
+    for t in (a, b):
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != 4 or t.device != device
+                or not t.is_contiguous() or t.shape != a.shape):
+            raise ValueError(f"{what} must be a pair of contiguous int32 [K, 4] tensors of equal shape on {device}")
+    return int(a.shape[0]), a, b
+
+
+def _value(planes_a, planes_b, k: int, L: int, M: int, table, out, device) -> None:
+    stream = torch._C._cuda_getCurrentRawStream(device.index)
+    check(_learn_lib.lib().tpl_ntuple_value(_ptr(planes_a), _ptr(planes_b), k, L, M, table.data_ptr(), out.data_ptr(), stream))
+
+
+@torch.no_grad()
+def ntuple_value(source, table: torch.Tensor, L: Optional[int] = None, M: Optional[int] = None,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """float32 [K]: V of K states under `table`; 0 for a state that is not running.  `source` is an environment (its resident
+    boards, read in place, under its L and M) or a pair (states_a, states_b) of int32 [K, 4] planes on the table's device, for
+    which the game's L and M must be given.  No host sync, and no allocation when `out` is given."""
+    if hasattr(source, "num_envs"):
+        if L is not None or M is not None:
+            raise ValueError("an environment brings its own L and M")
+        k, device, L, M = _boards(source, "ntuple_value"), source.device, source.L, source.M
+        _table(table, device)
+        a, b = _state_ptrs(source)
+    else:
+        k, a, b = _planes(source, None, "source")
+        device = a.device
+        _table(table, device)
+        if L is None or M is None:
+            raise ValueError("planes need the game's L and M")
+        if not 1 <= k <= _MAX_BOARDS:
+            raise ValueError(f"ntuple_value takes 1 .. {_MAX_BOARDS} states")
+    if out is None:
+        out = torch.empty(k, dtype=torch.float32, device=device)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (k,) or out.device != device
+          or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous float32 tensor of shape ({k},) on {device}")
+    _value(a, b, k, int(L), int(M), table, out, device)
+    return out
+
+
+class NTuplePolicy:
+    """The greedy / epsilon-greedy placement policy of an n-tuple table on the resident boards of `env`: act() scores every
+    distinct placement a as  r_a  if it ends the game, else  r_a + gamma * V(afterstate)  (env.reward_params; float32, never
+    fused) and plays the lowest a at the maximum; a finished board gets action 0.  With epsilon > 0 a running board explores
+    with that probability, uniformly over its distinct placements, on the hash of (seed, step, board) -- deterministic.
+    One launch that leaves the environment as it is.  `table` is read at every act(): train it in place."""
+
+    def __init__(self, env, table: torch.Tensor, gamma: float = 0.99, epsilon: float = 0.0, seed: int = 0):
+        _boards(env, "NTuplePolicy")
+        self.env, self.table = env, _table(table, env.device)
+        self.gamma, self.epsilon, self.seed = _finite("gamma", gamma), _unit("epsilon", epsilon), _count("seed", seed)
+        self.step = 0                                          # the `step` of the next act() that is not given one
+        self._planes = None
+
+    @torch.no_grad()
+    def act(self, out: Optional[torch.Tensor] = None, score: Optional[torch.Tensor] = None, after=None,
+            value: Optional[torch.Tensor] = None, step: Optional[int] = None) -> torch.Tensor:
+        """uint8 [N]: the action of every resident board.  score (float32 [N], optional) receives the GREEDY maximum, whatever is
+        played; after (a pair of int32 [N, 4] planes, optional) the afterstate of the action played -- the board itself where it
+        is finished -- and value (float32 [N], optional) V of that afterstate.  step: the `step` of tpl_ntuple_act, which keys
+        the exploration draw; None takes the policy's own counter and advances it.  No host sync, and no allocation when `out`
+        is given: capturable into a HIP graph (which replays the step it was captured with)."""
+        env = self.env
+        if out is None:
+            out = torch.empty(env.num_envs, dtype=torch.uint8, device=env.device)
+        env._own(out, torch.uint8, "out")
+        if score is not None:
+            env._own(score, torch.float32, "score")
+        if value is not None:
+            env._own(value, torch.float32, "value")
+        after_a = after_b = None
+        if after is not None:
+            k, after_a, after_b = _planes(after, env.device, "after")
+            if k != env.num_envs:
+                raise ValueError(f"after must hold {env.num_envs} states")
+        if step is None:
+            step, self.step = self.step, self.step + 1
+        else:
+            step = _count("step", step)
+        if self._planes is None:
+            self._planes = _state_ptrs(env)                   # the resident planes live as long as the environment
+        stream = torch._C._cuda_getCurrentRawStream(env.device.index)
+        check(_learn_lib.lib().tpl_ntuple_act(self._planes[0], self._planes[1], env.num_envs, env.L, env.M, *env.reward_params,
+                                              self.gamma, self.table.data_ptr(), self.epsilon, self.seed % (1 << 64),
+                                              step % (1 << 64), out.data_ptr(), _ptr(score), _ptr(after_a), _ptr(after_b),
+                                              _ptr(value), stream))
+        return out
+
+
+class NTupleLearner:
+    """TD(0) on afterstates with an n-tuple table, entirely on the device.  `env`: an auto-reset environment with a
+    configuration pool.  Each step of train() is one loop body -- no host sync, nothing allocated:
+
+        1. act: the epsilon-greedy action, the greedy score and the afterstate of the action played (tpl_ntuple_act)
+        2. error = greedy score - V(the afterstate kept from the step before), V as the table stands now (tpl_ntuple_value)
+        3. the kept afterstates take  rint(rate * error)  on their table entries (tpl_ntuple_update)
+        4. the environment steps
+        5. the new afterstates are kept
+
+    The greedy score of a state is the TD target of the afterstate that led to it: the state IS that afterstate, up to window
+    entries the value does not read.  An afterstate that ended the game is not running, so it has value 0 and its update adds
+    nothing: a board that auto-resets drops out by the rule, without a mask.  `rate` is in table units per unit of error: the
+    step of V for one state alone is about rate * 2^-16 * (tuples in use + 1), and boards that share entries add up -- so it is
+    small for many boards in lockstep."""
+
+    def __init__(self, env, gamma: float = 0.99, rate: float = 8.0, epsilon: float = 0.1, seed: int = 0):
+        n = _boards(env, "NTupleLearner")
+        if not env.auto_reset:
+            raise ValueError("NTupleLearner needs an auto-reset environment")
+        self.env, self.rate = env, _finite("rate", rate)
+        _unit("epsilon", epsilon), _finite("gamma", gamma), _count("seed", seed)
+        d = env.device
+        self.table = ntuple_table(d)
+        self.policy = NTuplePolicy(env, self.table, gamma, epsilon, seed)
+        self.greedy = NTuplePolicy(env, self.table, gamma, 0.0, seed)
+        self.steps = 0                                         # train() steps so far: the `step` of the exploration draw
+        self._action = torch.empty(n, dtype=torch.uint8, device=d)
+        self._done = torch.empty(n, dtype=torch.uint8, device=d)
+        self._reward, self._score, self._kept_value, self._error = (torch.empty(n, dtype=torch.float32, device=d) for _ in range(4))
+        self._kept = tuple(torch.empty((n, 4), dtype=torch.int32, device=d) for _ in range(2))
+        self._next = tuple(torch.empty((n, 4), dtype=torch.int32, device=d) for _ in range(2))
+        self.forget()
+
+    def forget(self) -> None:
+        """Nothing is kept from the step before: the kept afterstates become finished states, which update nothing."""
+        self._kept[0].zero_()
+        self._kept[1].zero_()
+        self._kept[1][:, 1] = _FINISHED_B_Y
+
+    @torch.no_grad()
+    def train(self, steps: int) -> int:
+        """`steps` steps of the loop above from the environment as it stands.  Whatever else moves the environment between two
+        calls must be followed by forget(); evaluate() does it itself.  Returns the steps trained so far."""
+        steps = _count("steps", steps, 1)
+        env, n, lib = self.env, self.env.num_envs, _learn_lib.lib()
+        stream = torch._C._cuda_getCurrentRawStream(env.device.index)
+        for _ in range(steps):
+            self.policy.act(out=self._action, score=self._score, after=self._next, step=self.steps)
+            _value(self._kept[0], self._kept[1], n, env.L, env.M, self.table, self._kept_value, env.device)
+            torch.sub(self._score, self._kept_value, out=self._error)
+            check(lib.tpl_ntuple_update(self._kept[0].data_ptr(), self._kept[1].data_ptr(), n, env.L, env.M, self.table.data_ptr(),
+                                        self._error.data_ptr(), self.rate, stream))
+            env.step_into(self._action, self._reward, self._done)
+            self._kept, self._next = self._next, self._kept
+            self.steps += 1
+        return self.steps
+
+    @torch.no_grad()
+    def evaluate(self, steps: int) -> dict:
+        """Play `steps` greedy steps from a full reset and count: episodes (the steps' done flags), wins (the afterstates of the
+        moves played whose state is "won": every reward parameter counts the same wins) and win_rate = wins / max(episodes, 1).
+        The tallies stay on the device, with one sync at the end.  Training goes on from the boards this leaves, with nothing
+        kept."""
+        steps = _count("steps", steps, 1)
+        env, d = self.env, self.env.device
+        episodes = torch.zeros(env.num_envs, dtype=torch.int32, device=d)
+        wins = torch.zeros(env.num_envs, dtype=torch.int32, device=d)
+        env.reset()
+        for _ in range(steps):
+            env.step_into(self.greedy.act(out=self._action, after=self._next, step=0), self._reward, self._done)
+            episodes += self._done
+            wins += ((self._next[1][:, 1] >> 28) & 3) == _STATE_WON          # an auto-reset board runs whenever it is asked to act
+        self.forget()
+        ep, wn = int(episodes.sum(dtype=torch.int64)), int(wins.sum(dtype=torch.int64))
+        return dict(episodes=ep, wins=wn, win_rate=wn / max(ep, 1))

@@ -42,6 +42,12 @@ Parts:
               the yardstick is the two-ply kernel of the same run and the prediction the moves per board of the two rules on these
               boards (their windows' known pieces and placement counts); win rates of the classical signs at depth 1 and 2 and
               at (3, 8), (4, 16) and (6, 16) on an L=10 / M=40 carved pool
+    ntuple       the n-tuple value function: tpl_ntuple_act at 2^16, 2^18 and 2^20 boards (L=10 / M=40, mid-game, a random table)
+              beside tpl_placement_act and tpl_placement_search on the same boards, and tpl_ntuple_value and tpl_ntuple_update
+              against their gathered / added bytes (4 per tuple in use and the counter, counted on a sample of the boards) at the
+              scattered-atomic figure of 0.08 TB/s, everything alternated over five rounds of 20 launches after 3 warm-ups; the
+              win rate of NTupleLearner on the two-piece game and on an L=10 / M=40 carved pool (>= 10^6 episodes) beside the
+              zero table's and the classical weights' at one ply
 """
 import argparse
 import json
@@ -55,7 +61,8 @@ sys.path.insert(0, ROOT)
 
 HBM_ACHIEVABLE = 6.3e12
 PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600, "priority": 600, "nstep": 600, "mirror": 600, "afterstates": 600,
-         "heuristic": 600, "search": 900, "beam": 900}
+         "heuristic": 600, "search": 900, "beam": 900, "ntuple": 900}
+SCATTERED_ATOMICS = 0.08e12                                 # 64 lanes of a wave adding into 64 rows (float adds; integer adds unmeasured)
 VALU_CYCLES, SIMDS, CLOCK_HZ = 3.3, 1024, 2.4e9           # the move's instruction mix, 256 CUs x 4, the clock
 
 
@@ -804,6 +811,112 @@ def part_beam(rounds=3):
             seconds=round(time.perf_counter() - t0, 3))
     env.terminate()
     out["l10_m40"] = rates
+    return out
+
+
+NTUPLE_SMALL = dict(gamma=1.0, rate=8.0, epsilon=0.25)      # the two-piece game: tests/test_ntuple_gpu.py says why
+# L=10 / M=40: a win-only reward never pays before the first win, which exploration does not find (the zero table wins 0 of
+# 324,756 episodes and every TD error is 0), so the learner is trained on a shaped reward (r_line, r_win, r_lose) and judged on wins
+NTUPLE_LARGE_REWARD = (1.0, 10.0, -1.0)
+NTUPLE_LARGE = [dict(gamma=1.0, rate=rate, epsilon=0.05) for rate in (1.0, 4.0, 16.0)]
+
+
+def part_ntuple(rounds=5):
+    import ctypes as C
+    import numpy as np
+    import torch
+    import tetris_piclim as T
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import learn_ref as R
+    m = T._learn_lib
+    L, check = m.lib(), m.check
+    stream = torch._C._cuda_getCurrentRawStream(0)
+    lib_path = m.build_library()
+    valu = {k: _static_valu(k, lib_path) for k in ("ntuple_act_kernel", "ntuple_value_kernel", "ntuple_update_kernel")}
+    out = dict(part="ntuple", static_valu=valu, scattered_atomics_tb_per_s=SCATTERED_ATOMICS / 1e12)
+    classical = np.array([4, 100, -100, -8, -1, 0, -2, -3, -6, -3, -2, -1], np.float32) * np.float32(0.1)
+    weights = torch.from_numpy(classical).to("cuda:0")
+    host = np.random.default_rng(0).integers(-(1 << 20), (1 << 20) + 1, m.NTUPLE_ENTRIES).astype(np.int32)
+    rows = []
+    for n in (1 << 16, 1 << 18, 1 << 20):
+        env = T.BatchedTetris(10, 40, n, device="cuda:0", seed=1, auto_reset=True)
+        env.load_configs(*env.synthetic_configs(4096))
+        env.reset()
+        for t in range(6):                                       # mid-game boards
+            env.step(env.synthetic_actions(t), observe=False)
+        pa, pb = C.c_void_p(), C.c_void_p()
+        T._lib.check(env._lib.tpl_state_ptrs(env._h, C.byref(pa), C.byref(pb)))
+        a, b = (x[:4096].cpu().numpy().view(np.uint32) for x in env.raw_planes())
+        f = R.decode_state(a, b)
+        _, used = m.ntuple_indices(f["rows"], f["cur"], 10, 40, f["lines"].astype(np.int64), f["moves"].astype(np.int64))
+        in_use = float(used[f["state"] == 0].sum(axis=1).mean())   # entries per running board, the counter included
+        table = torch.from_numpy(host).to("cuda:0")
+        action = torch.empty(n, dtype=torch.uint8, device="cuda:0")
+        score, value, error = (torch.empty(n, dtype=torch.float32, device="cuda:0") for _ in range(3))
+        error.normal_()
+        after = [torch.empty((n, 4), dtype=torch.int32, device="cuda:0") for _ in range(2)]
+
+        def act(full):
+            check(L.tpl_ntuple_act(pa.value, pb.value, n, 10, 40, 0.0, 1.0, 0.0, 0.99, table.data_ptr(), 0.0, 0, 0, action.data_ptr(),
+                                   score.data_ptr() if full else None, after[0].data_ptr() if full else None,
+                                   after[1].data_ptr() if full else None, value.data_ptr() if full else None, stream))
+        variants = [
+            ("ntuple_act", lambda: act(False)), ("ntuple_act_all_outputs", lambda: act(True)),
+            ("placement_act", lambda: check(L.tpl_placement_act(pa.value, pb.value, n, 10, 40, weights.data_ptr(), n, action.data_ptr(),
+                                                                None, stream))),
+            ("placement_search", lambda: check(L.tpl_placement_search(pa.value, pb.value, n, 10, 40, weights.data_ptr(), n,
+                                                                      action.data_ptr(), None, None, stream))),
+            ("ntuple_value", lambda: check(L.tpl_ntuple_value(pa.value, pb.value, n, 10, 40, table.data_ptr(), value.data_ptr(), stream))),
+            ("ntuple_update", lambda: check(L.tpl_ntuple_update(pa.value, pb.value, n, 10, 40, table.data_ptr(), error.data_ptr(),
+                                                                100.0, stream))),
+        ]
+        times = {name: [] for name, _ in variants}
+        for _ in range(rounds):                                  # alternate the kernels round by round
+            for name, fn in variants:
+                times[name].append(_timed(fn, 20))
+        med = {name: sorted(ts)[rounds // 2] for name, ts in times.items()}
+        row = dict(boards=n, entries_in_use_per_board=round(in_use, 1), us={name: _spread(ts) for name, ts in times.items()},
+                   act_over_one_ply=round(med["ntuple_act"] / med["placement_act"], 2),
+                   act_over_two_ply=round(med["ntuple_act"] / med["placement_search"], 3))
+        for name in ("ntuple_value", "ntuple_update"):
+            nbytes = n * in_use * 4
+            row[name] = dict(bytes=round(nbytes), tb_per_s=round(nbytes / med[name] / 1e12, 3),
+                             over_scattered_atomics=round(nbytes / med[name] / SCATTERED_ATOMICS, 2))
+        rows.append(row)
+        env.terminate()
+        del table, after
+        torch.cuda.empty_cache()
+    out["kernel"] = dict(rounds=rounds, launches_per_timing=20, rows=rows)
+
+    def learn(L_, M_, pool, n, seed, train_steps, eval_steps, reward=(0.0, 1.0, 0.0), **kw):
+        env = T.BatchedTetris(L_, M_, n, device="cuda:0", seed=seed, auto_reset=True, reward=reward, config_pool=pool)
+        learner = T.NTupleLearner(env, seed=seed, **kw)
+        got = dict(kw, boards=n, seed=seed, reward=list(reward), zero_table=learner.evaluate(eval_steps), trained=[])
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for steps in train_steps:
+            learner.train(steps)
+            r = learner.evaluate(eval_steps)
+            p = r["win_rate"]
+            got["trained"].append(dict(r, steps=learner.steps, standard_error=round((p * (1 - p) / max(r["episodes"], 1)) ** 0.5, 6),
+                                       seconds=round(time.perf_counter() - t0, 2)))
+        got["entries_in_use"] = int((learner.table != 0).sum())
+        got["largest_entry"] = int(learner.table.abs().max())
+        env.terminate()
+        return got
+    out["l2_m2"] = learn(2, 2, T.generate_configs(2, 2, 64, seed=107), 4096, 3, (100, 200), 64, **NTUPLE_SMALL)
+    gen_env = T.BatchedTetris(10, 40, 64, device="cuda:0", seed=7)
+    big = gen_env.carved_configs(1 << 16, seed=7)
+    gen_env.terminate()
+    env = T.BatchedTetris(10, 40, 1 << 16, device="cuda:0", seed=11, auto_reset=True, reward=(0.0, 1.0, 0.0), config_pool=big)
+    got = T.evaluate_heuristic(env, classical, None, 640)
+    env.terminate()
+    out["l10_m40"] = dict(pool=1 << 16, pool_seed=7,
+                          classical_one_ply=dict(episodes=int(got["episodes"][0]), wins=int(got["wins"][0]),
+                                                 win_rate=round(float(got["win_rate"][0]), 5)),
+                          win_only_reward=learn(10, 40, big, 1 << 14, 11, (1500,), 160, gamma=1.0, rate=8.0, epsilon=0.05),
+                          shaped_reward=[learn(10, 40, big, 4096, 11, (10000, 30000), 12288, reward=NTUPLE_LARGE_REWARD, **kw)
+                                         for kw in NTUPLE_LARGE])
     return out
 
 
