@@ -376,6 +376,41 @@ int tpl_ntuple_act(const void* plane_a, const void* plane_b, int64_t n, int32_t 
                    float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed, uint64_t step, uint8_t* action,
                    float* score, void* after_a, void* after_b, float* value, void* stream);
 
+/* The policy two plies deep, with the known next piece.  In this game an afterstate knows the piece that falls next (window entry 1
+ * of the state it came from), so  max_b (r_b + gamma V(s_ab))  is the value of the afterstate s_a itself, not a heuristic
+ * extension: tpl_ntuple_act ranks placements by the table's approximation of that quantity, tpl_ntuple_search by the quantity, with
+ * the table one move further out.  An afterstate's window is good for exactly two entries (above), so this is the deepest search
+ * the table can make exactly.
+ * For a state s with cur = window entry 0, nxt = window entry 1, and every distinct first placement a (a == canonical(cur, a)):
+ *   move_board(s, a) and the pop give n1, state1, the board s1 and r1 = the reward of (n1, state1), exactly as tpl_ntuple_act
+ *   makes them.
+ *   Finished board (state(s) != running): action 0, score 0, second 255; its afterstate is s itself, bit for bit, with value 0.
+ *   state1 != running (the first move ends the game): Q(a) = r1 and second(a) = 255.
+ *   otherwise, for every distinct placement b of nxt (b == canonical(nxt, b)) in ascending b -- nxt = 7 ("none") is what move_board
+ *   and the shape table make of it, O's nine placements, as in tpl_placement_search --, move_board(s1, b) and the pop give n2,
+ *   state2, the board s2 and r2 = the reward of (n2, state2):
+ *     q(a, b) = r2 + gamma * V(s2) if state2 runs, else r2     -- V as tpl_ntuple_value gives it: the piece index of s2 is window
+ *                                                                 entry 2 of s, the counter index comes from s2's lines and moves;
+ *     W(a) = max over b of q(a, b); second(a) = the lowest b at that maximum (-0 and +0 tie);
+ *     Q(a) = r1 + gamma * W(a).
+ *   Every product and every sum is rounded once in float32 and never fused.
+ *   The greedy action is the lowest a at the maximum of Q (-0 and +0 tie).
+ * Exploration is tpl_ntuple_act's draw unchanged -- the same hash of (seed, step, board), uniform over the distinct FIRST placements
+ * -- so at equal (seed, step, epsilon) the same boards explore the same rank at both depths.  `score` is ALWAYS the greedy maximum
+ * of Q; `action`, `second` = second(action), `after` = the ONE-PLY afterstate s1 of the action and `value` = V(s1) (0 where the move
+ * ended the game) belong to the action that is played -- what tpl_ntuple_act gives for that action, so a TD(0) loop on afterstates
+ * needs nothing else, and its target becomes the two-ply score.
+ * After a non-auto-reset step with `action` on an environment without a pool, a board that still runs has a tpl_ntuple_act choice
+ * (epsilon 0) of `second`: the second ply is the one-ply rule on the board the step leaves.
+ *
+ * One kernel (ntuple_search_kernel, tpl_ntuple_act's frame with a loop over b in the lanes whose first move leaves the game
+ * running): 32 bytes read per board besides the table gathers, at most 1 + 1 + 4 + 32 + 4 bytes written: action u8 [n]; second u8
+ * [n] (optional, no alignment requirement); score, after_a / after_b and value as tpl_ntuple_act's.  An output that is not given is
+ * not written.  Refused before any HIP call: everything tpl_ntuple_act refuses. */
+int tpl_ntuple_search(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line, float r_win,
+                      float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed, uint64_t step, uint8_t* action,
+                      uint8_t* second, float* score, void* after_a, void* after_b, float* value, void* stream);
+
 /* The update above: error f32 [n], one per state of plane_a / plane_b.  Refused before any HIP call: tpl_ntuple_value's plane, n,
  * L, M and table checks, error NULL or not 4-byte aligned, rate not finite. */
 int tpl_ntuple_update(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, int32_t* table,

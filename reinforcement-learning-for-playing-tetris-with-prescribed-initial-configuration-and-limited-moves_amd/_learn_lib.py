@@ -30,6 +30,7 @@ LEARN_SYMBOLS = [
     "tpl_priority_update", "tpl_replay_sample_prioritized", "tpl_priority_target", "tpl_replay_sample_nstep",
     "tpl_replay_sample_mirror", "tpl_mirror_states", "tpl_afterstates", "tpl_canonical_action", "tpl_placement_features",
     "tpl_placement_act", "tpl_placement_search", "tpl_placement_beam", "tpl_ntuple_value", "tpl_ntuple_act", "tpl_ntuple_update",
+    "tpl_ntuple_search",
 ]
 NSTEP_MAX = 16
 BEAM_MAX_DEPTH, BEAM_MAX_WIDTH = 12, 64
@@ -139,10 +140,12 @@ def lib() -> C.CDLL:
     L.tpl_ntuple_value.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp]
     L.tpl_ntuple_act.argtypes = [vp, vp, i64, i32, i32, f32, f32, f32, f32, vp, f32, u64, u64, vp, vp, vp, vp, vp, vp]
     L.tpl_ntuple_update.argtypes = [vp, vp, i64, i32, i32, vp, vp, f32, vp]
+    L.tpl_ntuple_search.argtypes = [vp, vp, i64, i32, i32, f32, f32, f32, f32, vp, f32, u64, u64, vp, vp, vp, vp, vp, vp, vp]
     for name in ("tpl_replay_push", "tpl_replay_sample", "tpl_learn_pack", "tpl_priority_init", "tpl_priority_push",
                  "tpl_priority_update", "tpl_replay_sample_prioritized", "tpl_replay_sample_nstep", "tpl_replay_sample_mirror",
                  "tpl_mirror_states", "tpl_afterstates", "tpl_placement_features", "tpl_placement_act",
-                 "tpl_placement_search", "tpl_placement_beam", "tpl_ntuple_value", "tpl_ntuple_act", "tpl_ntuple_update"):
+                 "tpl_placement_search", "tpl_placement_beam", "tpl_ntuple_value", "tpl_ntuple_act", "tpl_ntuple_update",
+                 "tpl_ntuple_search"):
         getattr(L, name).restype = i32
     _handle = L
     return L
@@ -589,6 +592,49 @@ def ntuple_explore(seed: int, step: int, n: int, epsilon: float, placements):
     below = np.uint64(int(np.float32(epsilon) * np.float32(2.0 ** 24)))
     s = np.broadcast_to(np.asarray(placements, dtype=np.uint64), (n,))
     return (h >> np.uint64(40)) < below, (((h & _M32) * s) >> np.uint64(32)).astype(np.int64)
+
+
+def _lowest_at_max(x, axis):
+    """(the entry at the lowest index that holds the maximum along `axis` -- its own bits: -0 and +0 tie --, that index); -inf
+    marks what does not take part."""
+    x = np.asarray(x, dtype=np.float32)
+    at = np.argmax(x == x.max(axis=axis, keepdims=True), axis=axis)            # == : -0 and +0 are equal
+    return np.take_along_axis(x, np.expand_dims(at, axis), axis=axis).squeeze(axis), at
+
+
+def ntuple_search_choice(reward1, done1, distinct1, reward2, done2, value2, distinct2, gamma, running=None):
+    """The two-ply rule of include/tpl_learn.h (tpl_ntuple_search) on rewards and values that are given: reward1 f32 [K, 40] and
+    done1 [K, 40] of every first placement a; reward2 f32, done2 and value2 f32 [K, 40, 40] of every (a, b) -- read only where
+    done1 is not set; value2 = V(s_ab), read only where done2 is not set --; distinct1 [K, 40] where a is a distinct placement of
+    the current piece, distinct2 [K, 40] or [K, 40, 40] where b is one of the next piece; running [K] (default: all) where the
+    state is in play.  Returns (action u8 [K], second u8 [K], score f32 [K], Q f32 [K, 40], second of every a u8 [K, 40]):
+    q(a, b) = r2, or r2 + gamma * V where the game goes on; W(a) = the maximum over the distinct b, second(a) the lowest b at
+    it; Q(a) = r1 where done1 (second 255), else r1 + gamma * W(a); action = the lowest distinct a at the maximum of Q; a state
+    that is not running gets action 0, second 255, score 0 and Q = 0.  Float32 numpy operations: every product and every sum
+    rounded once; -0 and +0 tie."""
+    reward1, reward2, value2 = (np.asarray(x, dtype=np.float32) for x in (reward1, reward2, value2))
+    k = reward1.shape[0]
+    done1, distinct1, done2, distinct2 = (np.asarray(x).astype(bool) for x in (done1, distinct1, done2, distinct2))
+    if distinct2.ndim == 2:
+        distinct2 = np.broadcast_to(distinct2[:, None, :], (k, NUM_ACTIONS, NUM_ACTIONS))
+    pairs = (k, NUM_ACTIONS)
+    if reward1.shape != pairs or done1.shape != pairs or distinct1.shape != pairs:
+        raise ValueError("reward1, done1 and distinct1 must be [K, 40]")
+    if any(x.shape != pairs + (NUM_ACTIONS,) for x in (reward2, done2, value2, distinct2)):
+        raise ValueError("reward2, done2 and value2 must be [K, 40, 40] and distinct2 [K, 40] or [K, 40, 40]")
+    running = np.ones(k, dtype=bool) if running is None else np.asarray(running).astype(bool).reshape(k)
+    g = np.float32(gamma)
+    with np.errstate(invalid="ignore", over="ignore"):
+        q = np.where(done2, reward2, reward2 + g * value2)
+        w, second = _lowest_at_max(np.where(distinct2, q, -np.inf), axis=2)
+        w = np.where(done1, np.float32(0.0), w)                # not read there; keeps -inf out of the product
+        Q = np.where(done1, reward1, reward1 + g * w)
+    Q = np.where(running[:, None], Q, np.float32(0.0)).astype(np.float32)
+    second = np.where(done1 | ~running[:, None], NO_SECOND, second).astype(np.uint8)
+    score, action = _lowest_at_max(np.where(distinct1, Q, -np.inf), axis=1)
+    action = np.where(running, action, 0)
+    at = np.arange(k)
+    return action.astype(np.uint8), second[at, action], Q[at, action], Q, second
 
 
 # ------------------------------------------------------------------------------------------------ device packing

@@ -1,5 +1,5 @@
 // ntuple.hip -- an n-tuple afterstate value function, its greedy / epsilon-greedy placement policy and its temporal-difference
-// update: tpl_ntuple_value, tpl_ntuple_act, tpl_ntuple_update (include/tpl_learn.h states the rule).
+// update: tpl_ntuple_value, tpl_ntuple_act, tpl_ntuple_search, tpl_ntuple_update (include/tpl_learn.h states the rule).
 //
 // The value of a board is a sum of table look-ups: 153 windows of two adjacent columns by four rows, each a 256-entry row of an
 // int32 table chosen by the piece that falls next, plus one entry for the lines and moves that are left.  In the column layout a
@@ -13,6 +13,14 @@
 // left, the chosen lane packs that board from its own registers -- nothing is enumerated twice.  The mapping rejected for act
 // is a lane per board looping over the placements: it would have a fortieth of the gathers in flight, and the gathers, not the
 // moves, are what a pair costs (DESIGN.md section 9 has the counts).
+//
+// search is act two plies deep in the same frame (ntuple_policy<kDepth> is the one body of both kernels): a lane whose first move
+// leaves the game running holds that board in registers and loops over the distinct placements of the next piece -- 9, 17 or 34
+// trips, the same for the 40 lanes of a board -- each trip a copy, a move, the pop and the 153 gathers on the board in
+// registers.  A lane per (board, a, b) TRIPLE would have more gathers in flight, but 1,156 triples are no multiple of 64, the
+// first move's board would be handed through LDS and the arg-max would have two levels; act measured bound by instruction issue
+// and not by its gathers, so the loop is the form that is built.  What it leaves on the table first is the alias lanes, which
+// idle through the loop.
 //
 // The all-empty pattern contributes nothing and is never updated: it is most of a board, and it would be the one address every
 // board adds to.  The look-up is still made (the address is in bounds, and the 64 lanes of a wave share it where their pieces
@@ -177,7 +185,51 @@ __device__ __forceinline__ uint32_t right_most(uint32_t cur, uint32_t r) {
     return 9u - ((uint32_t)(kWidthsLess1 >> (2u * (cur * 4u + r))) & 3u);
 }
 
-__global__ __launch_bounds__(kActBlock) void ntuple_act_kernel(const ActArgs p) {
+constexpr uint32_t kNoSecond = 255u;
+
+// The second ply with the known next piece: W = the best  r2 + gamma V(s2)  (r2 alone where the second move ends the game) among
+// the distinct placements of s1's current piece on s1, the popped and still running board a first move left, and the placement
+// it belongs to.  heuristic.hip's second_ply with the table in place of the features: a copy of s1, the move, the pop, the sum
+// on the board in registers and the score, once per distinct placement in ascending b = 10 r2 + l2 -- 9, 17 or 34 trips, the
+// same for the 40 lanes of a board -- under a strict > on the ordered key, so the lowest b survives.  r2 and l2 are values out
+// of the packed widths, never register indices.
+__device__ __forceinline__ float second_ply(const tpl::Board& s1, const tpl::ShapeWord* shape, uint32_t L, uint32_t M, float r_line,
+                                            float r_win, float r_lose, float gamma, const int32_t* table, uint32_t& second) {
+    const uint32_t nxt = s1.window & 7u;
+    const uint32_t last_rot = (kRotationMasks >> (2u * nxt)) & 3u;
+    uint32_t best_key = 0u, r2 = 0u, l2 = 0u;
+    float best = 0.0f;
+#pragma unroll 1
+    while (r2 <= last_rot) {
+        tpl::Board s2 = s1;
+        bool topout;
+        const uint32_t n2 = tpl::move_board(s2, shape, r2, l2, L, M, topout);
+        tpl::next_window(s2, false, 0);                                 // the piece after the next: the original window entry 2
+        const bool goes_on = s2.state == tpl::ST_RUNNING;
+        float v = 0.0f;
+        if (goes_on) v = ntuple_value(s2, L, M, table);
+        float q;
+        {
+#pragma clang fp contract(off)
+            const float reward = move_reward(r_line, r_win, r_lose, n2, s2.state);
+            const float later = gamma * v;
+            q = goes_on ? reward + later : reward;
+        }
+        const uint32_t key = ordered_bits(q);                           // never 0, so the first trip is taken
+        if (key > best_key) { best_key = key; best = q; second = 10u * r2 + l2; }
+        const bool wrap = l2 >= right_most(nxt, r2);
+        l2 = wrap ? 0u : l2 + 1u;
+        r2 += wrap ? 1u : 0u;
+    }
+    return best;
+}
+
+// The policy of kDepth plies on the block's eight boards (the header comment has the frame).  What a first move that leaves the
+// game running is worth beyond its reward is the one thing that differs: V of the board it left at one ply, second_ply's W at
+// two.  At two plies V of the afterstate is not on the way to the score, so the one chosen lane of a board sums it afterwards,
+// and only where `value` is asked for.
+template <int kDepth>
+__device__ __forceinline__ void ntuple_policy(const ActArgs& p, uint8_t* second_out) {
     __shared__ tpl::ShapeWord s_shape[32];
     __shared__ unsigned long long s_best[kBoardsPerBlock];
     __shared__ uint32_t s_pick[kBoardsPerBlock];                        // which distinct placement an exploring board plays
@@ -216,7 +268,12 @@ __global__ __launch_bounds__(kActBlock) void ntuple_act_kernel(const ActArgs p) 
     for (uint32_t q = 0; q < 3u; ++q) rank += q < r ? right_most(cur, q) + 1u : 0u;
 
     float v = 0.0f;                                                     // V of a state that does not run
-    if (contends && goes_on) v = ntuple_value(s1, p.L, p.M, p.table);
+    uint32_t second = kNoSecond;
+    if constexpr (kDepth == 2) {
+        if (contends && goes_on) v = second_ply(s1, s_shape, p.L, p.M, p.r_line, p.r_win, p.r_lose, p.gamma, p.table, second);
+    } else {
+        if (contends && goes_on) v = ntuple_value(s1, p.L, p.M, p.table);
+    }
     float score;
     {
 #pragma clang fp contract(off)
@@ -231,8 +288,17 @@ __global__ __launch_bounds__(kActBlock) void ntuple_act_kernel(const ActArgs p) 
     const uint32_t pick = s_pick[slot];
     const bool chosen = pick == kGreedy ? greedy : contends && rank == pick;
     if (greedy && p.score) p.score[i] = score;                          // the TD target, whatever is played
+    if constexpr (kDepth == 2) {
+        if (p.value) {                                                  // uniform; v was W, the second ply's, until here
+            v = 0.0f;
+            if (chosen && goes_on) v = ntuple_value(s1, p.L, p.M, p.table);
+        }
+    }
     if (chosen) {
         p.action[i] = (uint8_t)a;
+        if constexpr (kDepth == 2) {
+            if (second_out) second_out[i] = (uint8_t)second;
+        }
         if (p.value) p.value[i] = v;
         if (p.after_a) {                                                // a finished board stays as it is, bit for bit
             uint4 A2, B2;
@@ -243,6 +309,14 @@ __global__ __launch_bounds__(kActBlock) void ntuple_act_kernel(const ActArgs p) 
         }
     }
 }
+
+struct SearchArgs {
+    ActArgs act;
+    uint8_t* second;             // [n], optional: the second placement behind the action played, 255 where there is none
+};
+
+__global__ __launch_bounds__(kActBlock) void ntuple_act_kernel(const ActArgs p) { ntuple_policy<1>(p, nullptr); }
+__global__ __launch_bounds__(kActBlock) void ntuple_search_kernel(const SearchArgs p) { ntuple_policy<2>(p.act, p.second); }
 
 // the checks the three entries share beyond check_planes
 int check_table(const char* name, const void* table) {
@@ -272,10 +346,13 @@ extern "C" int tpl_ntuple_value(const void* plane_a, const void* plane_b, int64_
     return TPL_OK;
 }
 
-extern "C" int tpl_ntuple_act(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line, float r_win,
-                              float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed, uint64_t step,
-                              uint8_t* action, float* score, void* after_a, void* after_b, float* value, void* stream) {
-    const char* name = "tpl_ntuple_act";
+namespace {
+
+// what tpl_ntuple_act (depth = 1, second = null) and tpl_ntuple_search (depth = 2) share: the checks and the launch
+int launch_ntuple_policy(const char* name, int depth, const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M,
+                         float r_line, float r_win, float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed,
+                         uint64_t step, uint8_t* action, uint8_t* second, float* score, void* after_a, void* after_b, float* value,
+                         void* stream) {
     if (const int rc = check_planes(name, plane_a, plane_b, n, L, M)) return rc;
     if (const int rc = check_table(name, table)) return rc;
     if (!action) return fail_msg(TPL_ERR_ARG, "%s: null pointer (action is required)", name);
@@ -294,9 +371,27 @@ extern "C" int tpl_ntuple_act(const void* plane_a, const void* plane_b, int64_t 
     p.key = replay_key(seed, step);
     p.action = action; p.score = score; p.after_a = (uint4*)after_a; p.after_b = (uint4*)after_b; p.value = value;
     const dim3 grid((p.n + kBoardsPerBlock - 1) / kBoardsPerBlock), block(kActBlock);
-    hipLaunchKernelGGL(ntuple_act_kernel, grid, block, 0, (hipStream_t)stream, p);
+    if (depth == 2) hipLaunchKernelGGL(ntuple_search_kernel, grid, block, 0, (hipStream_t)stream, SearchArgs{p, second});
+    else hipLaunchKernelGGL(ntuple_act_kernel, grid, block, 0, (hipStream_t)stream, p);
     TPL_LEARN_HIP(hipGetLastError());
     return TPL_OK;
+}
+
+}  // namespace
+
+extern "C" int tpl_ntuple_act(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line, float r_win,
+                              float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed, uint64_t step,
+                              uint8_t* action, float* score, void* after_a, void* after_b, float* value, void* stream) {
+    return launch_ntuple_policy("tpl_ntuple_act", 1, plane_a, plane_b, n, L, M, r_line, r_win, r_lose, gamma, table, epsilon, seed,
+                                step, action, nullptr, score, after_a, after_b, value, stream);
+}
+
+extern "C" int tpl_ntuple_search(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line,
+                                 float r_win, float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed,
+                                 uint64_t step, uint8_t* action, uint8_t* second, float* score, void* after_a, void* after_b,
+                                 float* value, void* stream) {
+    return launch_ntuple_policy("tpl_ntuple_search", 2, plane_a, plane_b, n, L, M, r_line, r_win, r_lose, gamma, table, epsilon,
+                                seed, step, action, second, score, after_a, after_b, value, stream);
 }
 
 extern "C" int tpl_ntuple_update(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, int32_t* table,

@@ -3,13 +3,16 @@ learning on the device (the rule: include/tpl_learn.h; the kernels: csrc/learn/n
 
     ntuple_table(device)          a zeroed table: int32 [314,368], in units of 2^-16
     ntuple_value(source, table)   V of every resident board of an environment, or of plane pairs
-    NTuplePolicy(env, table, gamma, epsilon, seed).act()
+    NTuplePolicy(env, table, gamma, epsilon, seed, depth=1).act()
                                   arg-max over the distinct placements of  r + gamma * V(afterstate)  in ONE launch; with epsilon a
                                   board explores uniformly over its DISTINCT placements (not over the 40 actions, 6 to 31 of which
                                   are aliases); act(score=, after=, value=) also gives the greedy score (the TD target), the
-                                  afterstate of the action played and its value
-    NTupleLearner(env, gamma, rate, epsilon, seed)
-                                  TD(0) on afterstates: train(steps), evaluate(steps); `table` is a plain tensor (torch.save it)
+                                  afterstate of the action played and its value.  depth=2 searches the known next piece as well,
+                                  still in one launch:  r + gamma * max_b (r_b + gamma * V)  -- the value of the afterstate itself,
+                                  with the table one move further out; act(second=) gives the placement planned for that piece
+    NTupleLearner(env, gamma, rate, epsilon, seed, depth=1)
+                                  TD(0) on afterstates: train(steps), evaluate(steps, depth=None); `table` is a plain tensor
+                                  (torch.save it); a table trained at one depth can be played at the other
 
 The value is a sum of table entries, one per 2 x 4 window of the board that is not empty, chosen by the falling piece, plus one
 per (lines left, moves left); the update adds rint(rate * error) to the same entries.  Everything is integer, so two trainings
@@ -60,6 +63,12 @@ def _count(name: str, v, least: int = 0) -> int:
     if isinstance(v, bool) or not isinstance(v, int) or v < least:
         raise ValueError(f"{name} must be an integer of at least {least}, got {v!r}")
     return int(v)
+
+
+def _depth(depth) -> int:
+    if isinstance(depth, bool) or depth not in (1, 2):
+        raise ValueError(f"depth must be 1 or 2 (an afterstate knows its next piece and no more), got {depth!r}")
+    return int(depth)
 
 
 def _boards(env, who: str) -> int:
@@ -121,24 +130,34 @@ class NTuplePolicy:
     distinct placement a as  r_a  if it ends the game, else  r_a + gamma * V(afterstate)  (env.reward_params; float32, never
     fused) and plays the lowest a at the maximum; a finished board gets action 0.  With epsilon > 0 a running board explores
     with that probability, uniformly over its distinct placements, on the hash of (seed, step, board) -- deterministic.
-    One launch that leaves the environment as it is.  `table` is read at every act(): train it in place."""
+    One launch that leaves the environment as it is.  `table` is read at every act(): train it in place.
 
-    def __init__(self, env, table: torch.Tensor, gamma: float = 0.99, epsilon: float = 0.0, seed: int = 0):
+    depth=2 (tpl_ntuple_search) looks at the known next piece too: where a placement leaves the game running, V(afterstate)
+    gives way to the best  r_b + gamma * V  (r_b alone where b ends the game) over the distinct placements b of the next piece
+    on that afterstate.  The draw, and what `after` and `value` mean, do not change with the depth."""
+
+    def __init__(self, env, table: torch.Tensor, gamma: float = 0.99, epsilon: float = 0.0, seed: int = 0, depth: int = 1):
         _boards(env, "NTuplePolicy")
-        self.env, self.table = env, _table(table, env.device)
+        self.env, self.table, self.depth = env, _table(table, env.device), _depth(depth)
         self.gamma, self.epsilon, self.seed = _finite("gamma", gamma), _unit("epsilon", epsilon), _count("seed", seed)
         self.step = 0                                          # the `step` of the next act() that is not given one
         self._planes = None
 
     @torch.no_grad()
     def act(self, out: Optional[torch.Tensor] = None, score: Optional[torch.Tensor] = None, after=None,
-            value: Optional[torch.Tensor] = None, step: Optional[int] = None) -> torch.Tensor:
+            value: Optional[torch.Tensor] = None, step: Optional[int] = None, second: Optional[torch.Tensor] = None) -> torch.Tensor:
         """uint8 [N]: the action of every resident board.  score (float32 [N], optional) receives the GREEDY maximum, whatever is
         played; after (a pair of int32 [N, 4] planes, optional) the afterstate of the action played -- the board itself where it
         is finished -- and value (float32 [N], optional) V of that afterstate.  step: the `step` of tpl_ntuple_act, which keys
-        the exploration draw; None takes the policy's own counter and advances it.  No host sync, and no allocation when `out`
-        is given: capturable into a HIP graph (which replays the step it was captured with)."""
+        the exploration draw; None takes the policy's own counter and advances it.  second (uint8 [N], optional, depth 2 only):
+        the placement planned for the next piece behind the action played, 255 where that action ends the game or the board is
+        finished.  No host sync, and no allocation when `out` is given: capturable into a HIP graph (which replays the step it
+        was captured with)."""
         env = self.env
+        if second is not None:
+            if self.depth != 2:
+                raise ValueError("second is an output of depth 2 only")
+            env._own(second, torch.uint8, "second")
         if out is None:
             out = torch.empty(env.num_envs, dtype=torch.uint8, device=env.device)
         env._own(out, torch.uint8, "out")
@@ -158,10 +177,11 @@ class NTuplePolicy:
         if self._planes is None:
             self._planes = _state_ptrs(env)                   # the resident planes live as long as the environment
         stream = torch._C._cuda_getCurrentRawStream(env.device.index)
-        check(_learn_lib.lib().tpl_ntuple_act(self._planes[0], self._planes[1], env.num_envs, env.L, env.M, *env.reward_params,
-                                              self.gamma, self.table.data_ptr(), self.epsilon, self.seed % (1 << 64),
-                                              step % (1 << 64), out.data_ptr(), _ptr(score), _ptr(after_a), _ptr(after_b),
-                                              _ptr(value), stream))
+        lib = _learn_lib.lib()
+        head = (self._planes[0], self._planes[1], env.num_envs, env.L, env.M, *env.reward_params, self.gamma, self.table.data_ptr(),
+                self.epsilon, self.seed % (1 << 64), step % (1 << 64), out.data_ptr())
+        tail = (_ptr(score), _ptr(after_a), _ptr(after_b), _ptr(value), stream)
+        check(lib.tpl_ntuple_search(*head, _ptr(second), *tail) if self.depth == 2 else lib.tpl_ntuple_act(*head, *tail))
         return out
 
 
@@ -169,7 +189,8 @@ class NTupleLearner:
     """TD(0) on afterstates with an n-tuple table, entirely on the device.  `env`: an auto-reset environment with a
     configuration pool.  Each step of train() is one loop body -- no host sync, nothing allocated:
 
-        1. act: the epsilon-greedy action, the greedy score and the afterstate of the action played (tpl_ntuple_act)
+        1. act: the epsilon-greedy action, the greedy score and the afterstate of the action played (tpl_ntuple_act; at
+           depth 2 tpl_ntuple_search, whose afterstate is the same one-ply afterstate and whose score is the two-ply one)
         2. error = greedy score - V(the afterstate kept from the step before), V as the table stands now (tpl_ntuple_value)
         3. the kept afterstates take  rint(rate * error)  on their table entries (tpl_ntuple_update)
         4. the environment steps
@@ -179,18 +200,20 @@ class NTupleLearner:
     entries the value does not read.  An afterstate that ended the game is not running, so it has value 0 and its update adds
     nothing: a board that auto-resets drops out by the rule, without a mask.  `rate` is in table units per unit of error: the
     step of V for one state alone is about rate * 2^-16 * (tuples in use + 1), and boards that share entries add up -- so it is
-    small for many boards in lockstep."""
+    small for many boards in lockstep.  At depth 2 `policy` and `greedy` search two plies, so the target of a kept afterstate
+    is the two-ply greedy score of the state it became; nothing else in the loop changes."""
 
-    def __init__(self, env, gamma: float = 0.99, rate: float = 8.0, epsilon: float = 0.1, seed: int = 0):
+    def __init__(self, env, gamma: float = 0.99, rate: float = 8.0, epsilon: float = 0.1, seed: int = 0, depth: int = 1):
         n = _boards(env, "NTupleLearner")
         if not env.auto_reset:
             raise ValueError("NTupleLearner needs an auto-reset environment")
         self.env, self.rate = env, _finite("rate", rate)
         _unit("epsilon", epsilon), _finite("gamma", gamma), _count("seed", seed)
         d = env.device
+        self.depth = _depth(depth)
         self.table = ntuple_table(d)
-        self.policy = NTuplePolicy(env, self.table, gamma, epsilon, seed)
-        self.greedy = NTuplePolicy(env, self.table, gamma, 0.0, seed)
+        self.policy = NTuplePolicy(env, self.table, gamma, epsilon, seed, self.depth)
+        self.greedy = NTuplePolicy(env, self.table, gamma, 0.0, seed, self.depth)
         self.steps = 0                                         # train() steps so far: the `step` of the exploration draw
         self._action = torch.empty(n, dtype=torch.uint8, device=d)
         self._done = torch.empty(n, dtype=torch.uint8, device=d)
@@ -224,18 +247,22 @@ class NTupleLearner:
         return self.steps
 
     @torch.no_grad()
-    def evaluate(self, steps: int) -> dict:
+    def evaluate(self, steps: int, depth: Optional[int] = None) -> dict:
         """Play `steps` greedy steps from a full reset and count: episodes (the steps' done flags), wins (the afterstates of the
         moves played whose state is "won": every reward parameter counts the same wins) and win_rate = wins / max(episodes, 1).
+        depth: how deep the greedy policy searches -- None: the learner's own; 1 or 2 plays the table as it stands at that depth.
         The tallies stay on the device, with one sync at the end.  Training goes on from the boards this leaves, with nothing
         kept."""
         steps = _count("steps", steps, 1)
         env, d = self.env, self.env.device
+        greedy = self.greedy
+        if depth is not None and _depth(depth) != self.depth:
+            greedy = NTuplePolicy(env, self.table, greedy.gamma, 0.0, greedy.seed, depth)
         episodes = torch.zeros(env.num_envs, dtype=torch.int32, device=d)
         wins = torch.zeros(env.num_envs, dtype=torch.int32, device=d)
         env.reset()
         for _ in range(steps):
-            env.step_into(self.greedy.act(out=self._action, after=self._next, step=0), self._reward, self._done)
+            env.step_into(greedy.act(out=self._action, after=self._next, step=0), self._reward, self._done)
             episodes += self._done
             wins += ((self._next[1][:, 1] >> 28) & 3) == _STATE_WON          # an auto-reset board runs whenever it is asked to act
         self.forget()

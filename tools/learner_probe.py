@@ -48,6 +48,14 @@ Parts:
               scattered-atomic figure of 0.08 TB/s, everything alternated over five rounds of 20 launches after 3 warm-ups; the
               win rate of NTupleLearner on the two-piece game and on an L=10 / M=40 carved pool (>= 10^6 episodes) beside the
               zero table's and the classical weights' at one ply
+    ntuple_search  the two-ply n-tuple policy: tpl_ntuple_search at 2^16, 2^18 and 2^20 boards (L=10 / M=40, mid-game, a random
+              table) beside tpl_ntuple_act and tpl_placement_search on the same boards, against its instruction price (per wave:
+              tpl_ntuple_act's vector instructions outside its gather loop once, and per trip of the wave's slowest board the
+              second-ply loop's outside its gather loop plus 17 times the gather loop's, all as built); NTuplePolicy(depth=2).act()
+              against the composition it replaces at 262,144 boards (per 16,384-board chunk: afterstates into a scratch
+              environment, tpl_ntuple_act over its 40 x 16,384 boards, a torch max), alternated in one process; on an L=10 / M=40
+              carved pool the win rates at depth 1 and 2 of a table trained at depth 1 and of one trained at depth 2 (the shaped
+              reward, 4,096 boards, 40,000 steps) beside the classical weights' at one and two plies
 """
 import argparse
 import json
@@ -61,7 +69,8 @@ sys.path.insert(0, ROOT)
 
 HBM_ACHIEVABLE = 6.3e12
 PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600, "priority": 600, "nstep": 600, "mirror": 600, "afterstates": 600,
-         "heuristic": 600, "search": 900, "beam": 900, "ntuple": 900}
+         "heuristic": 600, "search": 900, "beam": 900, "ntuple": 900,
+         "ntuple_search": 900}
 SCATTERED_ATOMICS = 0.08e12                                 # 64 lanes of a wave adding into 64 rows (float adds; integer adds unmeasured)
 VALU_CYCLES, SIMDS, CLOCK_HZ = 3.3, 1024, 2.4e9           # the move's instruction mix, 256 CUs x 4, the clock
 
@@ -917,6 +926,178 @@ def part_ntuple(rounds=5):
                           win_only_reward=learn(10, 40, big, 1 << 14, 11, (1500,), 160, gamma=1.0, rate=8.0, epsilon=0.05),
                           shaped_reward=[learn(10, 40, big, 4096, 11, (10000, 30000), 12288, reward=NTUPLE_LARGE_REWARD, **kw)
                                          for kw in NTUPLE_LARGE])
+    return out
+
+
+def _nested_loop_valu(kernel, lib_path):
+    """(vector ALU instructions of the kernel, of its outermost loop, of the gather loop inside that one): loops are backward
+    branches in the code as built (tools/dump_isa.sh), the outermost the one with the longest span, the gather loop the one inside
+    it with the most global loads (a backward branch to the outer loop's own head is a trip that ends early, not a loop)."""
+    import re
+    res = subprocess.run(["bash", os.path.join(ROOT, "tools", "dump_isa.sh"), kernel, lib_path], capture_output=True, text=True,
+                         cwd=ROOT, timeout=120)
+    code = []
+    for l in res.stdout.splitlines():
+        m = re.match(r"\s+(\S+)\s+(.*?)//\s*([0-9A-Fa-f]+):", l)
+        if m:
+            off = int(m.group(2).split()[0]) if m.group(1).startswith("s_cbranch") or m.group(1) == "s_branch" else None
+            code.append((int(m.group(3), 16), m.group(1), off))
+    spans = sorted(((addr + 4 + 4 * (off - 65536), addr) for addr, _, off in code if off is not None and off >= 32768),
+                   key=lambda s: s[0] - s[1])                    # the longest first
+    count = lambda span, prefix: sum(1 for addr, op, _ in code if op.startswith(prefix) and span[0] <= addr <= span[1])
+    outer = spans[0]
+    inside = [s for s in spans[1:] if outer[0] < s[0] and s[1] <= outer[1]]
+    gather = max(inside, key=lambda s: count(s, "global_load"))
+    return count((0, 1 << 62), "v_"), count(outer, "v_"), count(gather, "v_")
+
+
+def part_ntuple_search(rounds=5):
+    import ctypes as C
+    import numpy as np
+    import torch
+    import tetris_piclim as T
+    m = T._learn_lib
+    L, check = m.lib(), m.check
+    stream = torch._C._cuda_getCurrentRawStream(0)
+    lib_path = m.build_library()
+    total, loop, gather = _nested_loop_valu("ntuple_search_kernel", lib_path)
+    act_total, act_gather = _loop_valu("ntuple_act_kernel", lib_path)
+    trip = (loop - gather) + 17 * gather                         # one second placement: the move, the pop, the score and 17 gather trips
+    out = dict(part="ntuple_search", valu_cycles=VALU_CYCLES,
+               static_valu=dict(kernel=total, second_ply_loop=loop, gather_loop=gather, per_second_placement=trip,
+                                ntuple_act_kernel=act_total, ntuple_act_gather_loop=act_gather,
+                                ntuple_act_outside_its_loop=act_total - act_gather))
+    classical = np.array([4, 100, -100, -8, -1, 0, -2, -3, -6, -3, -2, -1], np.float32) * np.float32(0.1)
+    weights = torch.from_numpy(classical).to("cuda:0")
+    host = np.random.default_rng(0).integers(-(1 << 20), (1 << 20) + 1, m.NTUPLE_ENTRIES).astype(np.int32)
+    trips_of = np.array([17, 34, 34, 34, 17, 17, 9, 9])          # the distinct placements of each piece id
+    gamma = 0.99
+    rows = []
+    for n in (1 << 16, 1 << 18, 1 << 20):
+        env = T.BatchedTetris(10, 40, n, device="cuda:0", seed=1, auto_reset=True)
+        env.load_configs(*env.synthetic_configs(4096))
+        env.reset()
+        for t in range(6):                                       # mid-game boards
+            env.step(env.synthetic_actions(t), observe=False)
+        pa, pb = C.c_void_p(), C.c_void_p()
+        T._lib.check(env._lib.tpl_state_ptrs(env._h, C.byref(pa), C.byref(pb)))
+        table = torch.from_numpy(host).to("cuda:0")
+        action, second = (torch.empty(n, dtype=torch.uint8, device="cuda:0") for _ in range(2))
+        score, value = (torch.empty(n, dtype=torch.float32, device="cuda:0") for _ in range(2))
+        after = [torch.empty((n, 4), dtype=torch.int32, device="cuda:0") for _ in range(2)]
+        # the trips of every wave, as part_search counts them: a wave runs as long as its slowest board
+        b = env.raw_planes()[1].cpu().numpy().view(np.uint32)
+        running = ((b[:, 1] >> 28) & 3) == 0
+        trips = np.where(running, trips_of[(b[:, 3] >> 3) & 7], 0).reshape(-1, 8)
+        wave_trips = np.stack([trips[:, (64 * v) // 40:(64 * v + 63) // 40 + 1].max(axis=1) for v in range(5)], axis=1)
+        valu_per_wave = (act_total - act_gather) + trip * float(wave_trips.mean())
+        t_valu = (n * 40 / 64) * valu_per_wave * VALU_CYCLES / SIMDS / CLOCK_HZ
+
+        def search(full):
+            check(L.tpl_ntuple_search(pa.value, pb.value, n, 10, 40, 0.0, 1.0, 0.0, gamma, table.data_ptr(), 0.0, 0, 0,
+                                      action.data_ptr(), second.data_ptr() if full else None, score.data_ptr() if full else None,
+                                      after[0].data_ptr() if full else None, after[1].data_ptr() if full else None,
+                                      value.data_ptr() if full else None, stream))
+        variants = [
+            ("ntuple_search", lambda: search(False)), ("ntuple_search_all_outputs", lambda: search(True)),
+            ("ntuple_act", lambda: check(L.tpl_ntuple_act(pa.value, pb.value, n, 10, 40, 0.0, 1.0, 0.0, gamma, table.data_ptr(), 0.0, 0,
+                                                          0, action.data_ptr(), None, None, None, None, stream))),
+            ("placement_search", lambda: check(L.tpl_placement_search(pa.value, pb.value, n, 10, 40, weights.data_ptr(), n,
+                                                                      action.data_ptr(), None, None, stream))),
+        ]
+        times = {name: [] for name, _ in variants}
+        for _ in range(rounds):                                  # alternate the kernels round by round
+            for name, fn in variants:
+                times[name].append(_timed(fn, 20))
+        med = {name: sorted(ts)[rounds // 2] for name, ts in times.items()}
+        row = dict(boards=n, running=int(running.sum()), mean_trips_per_board=round(float(trips.mean()), 2),
+                   mean_trips_per_wave=round(float(wave_trips.mean()), 2), valu_per_wave=round(valu_per_wave),
+                   price_us=round(t_valu * 1e6, 1), us={name: _spread(ts) for name, ts in times.items()},
+                   price_over_measured=round(t_valu / med["ntuple_search"], 3),
+                   search_over_act=round(med["ntuple_search"] / med["ntuple_act"], 2),
+                   search_over_two_ply_heuristic=round(med["ntuple_search"] / med["placement_search"], 2))
+        if n == 1 << 18:                                         # against the composition of the one-ply pieces it replaces
+            chunk = 16384
+            fused = T.NTuplePolicy(env, table, gamma=gamma, depth=2)
+            scratch = T.BatchedTetris(10, 40, 40 * chunk, device="cuda:0", seed=1)
+            inner = T.NTuplePolicy(scratch, table, gamma=gamma)
+            inner_action = torch.empty(40 * chunk, dtype=torch.uint8, device="cuda:0")
+            inner_score = torch.empty(40 * chunk, dtype=torch.float32, device="cuda:0")
+            reward = torch.empty((chunk, 40), dtype=torch.float32, device="cuda:0")
+            done, cleared, canonical = (torch.empty((chunk, 40), dtype=torch.uint8, device="cuda:0") for _ in range(3))
+            ids = torch.arange(40, dtype=torch.int64, device="cuda:0")
+            sa, sb = T.lookahead._state_ptrs(scratch)
+
+            def composed():
+                for first in range(0, n, chunk):
+                    T.lookahead._enumerate(env, pa.value + 16 * first, pb.value + 16 * first, chunk, sa, sb, reward, done, cleared,
+                                           canonical)
+                    inner.act(out=inner_action, score=inner_score, step=0)
+                    q = torch.where(done != 0, reward, reward + gamma * inner_score.view(chunk, 40))
+                    q = torch.where(canonical == ids, q, float("-inf"))
+                    action[first:first + chunk] = q.max(dim=1).indices.to(torch.uint8)
+            fused_action = fused.act(step=0).clone()
+            composed()
+            torch.cuda.synchronize()
+            ts = dict(fused=[], composed=[])
+            for _ in range(rounds):
+                ts["fused"].append(_timed(lambda: fused.act(out=second, step=0), 20))
+                ts["composed"].append(_timed(composed, 20))
+            medp = {k: sorted(v)[rounds // 2] for k, v in ts.items()}
+            # torch's max takes a first index among equal maxima too; its product is rounded as the kernel's is
+            row["policy_act"] = dict(fused_us=_spread(ts["fused"]), composed_us=_spread(ts["composed"]), chunks=n // chunk,
+                                     composed_over_fused=round(medp["composed"] / medp["fused"], 3),
+                                     boards_where_the_actions_differ=int((fused_action != action).sum()))
+            scratch.terminate()
+        rows.append(row)
+        env.terminate()
+        del table, after
+        torch.cuda.empty_cache()
+    out["kernel"] = dict(rounds=rounds, launches_per_timing=20, gamma=gamma, rows=rows)
+
+    # play strength on the L=10 / M=40 carved pool of part_ntuple: one table trained at each depth, each played at both
+    gen_env = T.BatchedTetris(10, 40, 64, device="cuda:0", seed=7)
+    big = gen_env.carved_configs(1 << 16, seed=7)
+    gen_env.terminate()
+
+    def rate(r):
+        p = r["win_rate"]
+        return dict(r, win_rate=round(p, 5), standard_error=round((p * (1 - p) / max(r["episodes"], 1)) ** 0.5, 6))
+
+    kw = NTUPLE_LARGE[-1]
+    trained = []
+    for depth in (1, 2):
+        env = T.BatchedTetris(10, 40, 4096, device="cuda:0", seed=11, auto_reset=True, reward=NTUPLE_LARGE_REWARD, config_pool=big)
+        learner = T.NTupleLearner(env, seed=11, depth=depth, **kw)
+        # part_ntuple's sequence, so that the table trained at depth 1 is the one its log records: the zero table played (the
+        # full reset that training starts from), 10,000 steps, an evaluation, 30,000 steps
+        zero = rate(learner.evaluate(12288))
+        train_seconds = 0.0
+        for steps in (10000, 30000):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            learner.train(steps)
+            torch.cuda.synchronize()
+            train_seconds += time.perf_counter() - t0
+            if learner.steps == 10000:
+                early = rate(learner.evaluate(12288))
+        got = dict(kw, trained_at_depth=depth, boards=4096, seed=11, reward=list(NTUPLE_LARGE_REWARD), steps=learner.steps,
+                   train_seconds=round(train_seconds, 2), zero_table_at_its_depth=zero, after_10000_steps_at_its_depth=early)
+        for play in (1, 2):
+            t0 = time.perf_counter()
+            got[f"played_at_depth{play}"] = dict(rate(learner.evaluate(12288, depth=play)), seconds=round(time.perf_counter() - t0, 2))
+        got["entries_in_use"] = int((learner.table != 0).sum())
+        got["largest_entry"] = int(learner.table.abs().max())
+        trained.append(got)
+        env.terminate()
+    env = T.BatchedTetris(10, 40, 1 << 16, device="cuda:0", seed=11, auto_reset=True, reward=(0.0, 1.0, 0.0), config_pool=big)
+    heuristic = {}
+    for depth in (1, 2):
+        got = T.evaluate_heuristic(env, classical, None, 640, depth=depth)
+        e, wins = int(got["episodes"][0]), int(got["wins"][0])
+        heuristic[f"classical_depth{depth}"] = rate(dict(episodes=e, wins=wins, win_rate=wins / max(e, 1)))
+    env.terminate()
+    out["l10_m40"] = dict(pool=1 << 16, pool_seed=7, eval_steps=12288, tables=trained, **heuristic)
     return out
 
 
