@@ -416,6 +416,37 @@ int tpl_ntuple_search(const void* plane_a, const void* plane_b, int64_t n, int32
 int tpl_ntuple_update(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, int32_t* table,
                       const float* error, float rate, void* stream);
 
+/* The update with truncated TD(lambda) traces and, optionally, tied under the game's mirror symmetry (tpl_mirror.h).
+ *
+ * ring_a / ring_b: [slots][n] 16-byte words, slot-major, read only -- the last states of n boards.  The state of board i at age k
+ * is in slot (head - k) mod slots; age 0 is the newest.  error f32 [n], one per board.  For board i with error e:
+ *   weights  w_0 = 1.0f,  w_k = w_{k-1} * decay                      -- each product rounded once in float32
+ *   for k = 0 .. horizon - 1 in order, with s the state at age k: if s is not running, STOP -- older ages belong to an earlier
+ *   episode or were never filled.  Otherwise
+ *     d_k = (int32) rint((rate * w_k) * e)   -- two products, each rounded once in float32 and never fused, clamped to +-2^24, 0 for
+ *                                               a NaN: tpl_ntuple_update's step with rate * w_k as its rate, so d_0 is its d --
+ *   is added, wrapping as two's complement, to counter[k(s)] and to tuple[p][17 x + y][q] of every tuple of s with q != 0, exactly
+ *   as tpl_ntuple_update adds.
+ * With symmetric != 0, d_k is ALSO added to the entries of the reflected state: tuple[pi(p)][17 (8 - x) + y][swap(q)] for those same
+ * tuples, with pi = [0, 2, 1, 3, 5, 4, 6, 7] (L <-> J, S <-> Z) and swap(q) = (q >> 4) | ((q & 15) << 4).  The counter is added
+ * ONCE.  Both tuple adds are made even where the two indices coincide (p = pi(p), x = 4 and q = swap(q)): such an entry takes
+ * 2 d_k.  The kernel only adds and never reads the table, so the bytes that result do not depend on the order of the adds.
+ *
+ * Invariant.  Let sigma map the index of tuple[p][17 x + y][q] to that of tuple[pi(p)][17 (8 - x) + y][swap(q)] and fix the counter
+ * indices; sigma is an involution.  A table is MIRROR-SYMMETRIC when table[sigma(j)] == table[j] for all j.  The zero table is, and
+ * a symmetric update adds the same amount to j and to sigma(j), so it keeps a symmetric table symmetric.  The tuples of the
+ * reflected state are the sigma-images of the state's, so under a symmetric table V(s) == V(mirror s) exactly, and
+ * tpl_ntuple_value / tpl_ntuple_act / tpl_ntuple_search play it unchanged: symmetry is a property of the table's bytes.
+ *
+ * One kernel (ntuple_trace_kernel<symmetric>): a lane per (board, age), the age in the grid's y.  horizon = 1, decay anything,
+ * symmetric = 0 leaves tpl_ntuple_update's bytes on slot `head`.  Refused before any HIP call: everything tpl_ntuple_update
+ * refuses (ring_a / ring_b as its planes), slots outside [1, TPL_NTUPLE_TRACE_MAX + 1], head outside [0, slots), horizon outside
+ * [1, min(slots, TPL_NTUPLE_TRACE_MAX)], 40 * slots * n >= 2^31, decay outside [0, 1] (a NaN included). */
+#define TPL_NTUPLE_TRACE_MAX 16
+int tpl_ntuple_update_trace(const void* ring_a, const void* ring_b, int64_t n, int32_t slots, int32_t head, int32_t horizon,
+                            int32_t L, int32_t M, int32_t* table, const float* error, float rate, float decay,
+                            int32_t symmetric, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

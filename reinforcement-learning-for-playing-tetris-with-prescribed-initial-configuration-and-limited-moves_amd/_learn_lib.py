@@ -30,7 +30,7 @@ LEARN_SYMBOLS = [
     "tpl_priority_update", "tpl_replay_sample_prioritized", "tpl_priority_target", "tpl_replay_sample_nstep",
     "tpl_replay_sample_mirror", "tpl_mirror_states", "tpl_afterstates", "tpl_canonical_action", "tpl_placement_features",
     "tpl_placement_act", "tpl_placement_search", "tpl_placement_beam", "tpl_ntuple_value", "tpl_ntuple_act", "tpl_ntuple_update",
-    "tpl_ntuple_search",
+    "tpl_ntuple_search", "tpl_ntuple_update_trace",
 ]
 NSTEP_MAX = 16
 BEAM_MAX_DEPTH, BEAM_MAX_WIDTH = 12, 64
@@ -141,11 +141,12 @@ def lib() -> C.CDLL:
     L.tpl_ntuple_act.argtypes = [vp, vp, i64, i32, i32, f32, f32, f32, f32, vp, f32, u64, u64, vp, vp, vp, vp, vp, vp]
     L.tpl_ntuple_update.argtypes = [vp, vp, i64, i32, i32, vp, vp, f32, vp]
     L.tpl_ntuple_search.argtypes = [vp, vp, i64, i32, i32, f32, f32, f32, f32, vp, f32, u64, u64, vp, vp, vp, vp, vp, vp, vp]
+    L.tpl_ntuple_update_trace.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, vp, vp, f32, f32, i32, vp]
     for name in ("tpl_replay_push", "tpl_replay_sample", "tpl_learn_pack", "tpl_priority_init", "tpl_priority_push",
                  "tpl_priority_update", "tpl_replay_sample_prioritized", "tpl_replay_sample_nstep", "tpl_replay_sample_mirror",
                  "tpl_mirror_states", "tpl_afterstates", "tpl_placement_features", "tpl_placement_act",
                  "tpl_placement_search", "tpl_placement_beam", "tpl_ntuple_value", "tpl_ntuple_act", "tpl_ntuple_update",
-                 "tpl_ntuple_search"):
+                 "tpl_ntuple_search", "tpl_ntuple_update_trace"):
         getattr(L, name).restype = i32
     _handle = L
     return L
@@ -581,6 +582,56 @@ def ntuple_update(table, rows, piece, L: int, M: int, lines, moves, state, error
     d = np.where(np.broadcast_to(np.asarray(state), index.shape[:1]) == 0, ntuple_steps(error, rate), 0)
     used = used & (d != 0)[:, None]
     np.add.at(_ntuple_table(table).view(np.uint32), index[used], np.broadcast_to(d[:, None], used.shape)[used].astype(np.uint32))
+    return table
+
+
+NTUPLE_TRACE_MAX = 16                                    # the horizon of tpl_ntuple_update_trace is at most this
+
+
+def ntuple_mirror_permutation() -> np.ndarray:
+    """sigma (int64 [NTUPLE_ENTRIES]): the index of tuple[p][17 x + y][q] -> that of tuple[pi(p)][17 (8 - x) + y][swap(q)], with
+    pi = PIECE_MIRROR and swap(q) = (q >> 4) | ((q & 15) << 4); the counter indices stay.  A table is mirror-symmetric when
+    table[sigma] == table."""
+    sigma = np.arange(NTUPLE_ENTRIES, dtype=np.int64)
+    p, x, y, q = np.meshgrid(np.arange(NTUPLE_PIECES), np.arange(9), np.arange(17), np.arange(NTUPLE_PATTERNS), indexing="ij")
+    image = (np.array(PIECE_MIRROR)[p] * NTUPLE_TUPLES + 17 * (8 - x) + y) * NTUPLE_PATTERNS + ((q >> 4) | ((q & 15) << 4))
+    sigma[:NTUPLE_COUNTER_BASE] = image.reshape(-1)      # (p, x, y, q) in C order is the table's own order
+    return sigma
+
+
+def _reflected_rows(rows) -> np.ndarray:
+    """Row masks with their ten columns reversed: bit x -> bit 9 - x."""
+    rows = np.asarray(rows).astype(np.int64)
+    out = np.zeros_like(rows)
+    for x in range(10):
+        out |= ((rows >> x) & 1) << (9 - x)
+    return out.astype(np.uint16)
+
+
+def ntuple_update_trace(table, ages, L: int, M: int, error, rate, decay, symmetric) -> np.ndarray:
+    """tpl_ntuple_update_trace, in place.  `ages`: a list, newest first, of (rows, piece, lines, moves, state) -- the decoded
+    fields ntuple_update takes, K states each.  Board i takes d_k = ntuple_steps(e_i, float32(rate) * w_k), w_0 = 1 and w_k =
+    float32(w_{k-1} * decay), at age k as long as that state and every younger one run.  symmetric: the same d_k goes to the tuple
+    entries of the REFLECTED rows (columns reversed, piece through PIECE_MIRROR) as well -- not through sigma --; the counter is
+    added once."""
+    tab = _ntuple_table(table).view(np.uint32)
+    e = np.asarray(error, dtype=np.float32).reshape(-1)
+    open_ = np.ones(e.shape, dtype=bool)
+    w, decay = np.float32(1.0), np.float32(decay)
+    for age, (rows, piece, lines, moves, state) in enumerate(ages):
+        if age:
+            w = np.float32(w * decay)
+        open_ = open_ & (np.broadcast_to(np.asarray(state), e.shape) == 0)
+        d = np.where(open_, ntuple_steps(e, np.float32(rate) * w), 0)
+        index, used = ntuple_indices(rows, piece, L, M, lines, moves)
+        used = used & (d != 0)[:, None]
+        np.add.at(tab, index[used], np.broadcast_to(d[:, None], used.shape)[used].astype(np.uint32))
+        if symmetric:
+            piece = np.broadcast_to(np.asarray(piece, dtype=np.int64), e.shape)
+            index, used = ntuple_indices(_reflected_rows(rows), np.array(PIECE_MIRROR)[piece], L, M, lines, moves)
+            used = used & (d != 0)[:, None]
+            used[:, NTUPLE_TUPLES] = False               # the counter was added above, once
+            np.add.at(tab, index[used], np.broadcast_to(d[:, None], used.shape)[used].astype(np.uint32))
     return table
 
 

@@ -1,5 +1,6 @@
 // ntuple.hip -- an n-tuple afterstate value function, its greedy / epsilon-greedy placement policy and its temporal-difference
-// update: tpl_ntuple_value, tpl_ntuple_act, tpl_ntuple_search, tpl_ntuple_update (include/tpl_learn.h states the rule).
+// update: tpl_ntuple_value, tpl_ntuple_act, tpl_ntuple_search, tpl_ntuple_update, tpl_ntuple_update_trace (include/tpl_learn.h
+// states the rule).
 //
 // The value of a board is a sum of table look-ups: 153 windows of two adjacent columns by four rows, each a 256-entry row of an
 // int32 table chosen by the piece that falls next, plus one entry for the lines and moves that are left.  In the column layout a
@@ -27,6 +28,13 @@
 // agree) and dropped by a select, so that the gathers stay straight-line code.  The counter entries -- 1,024, shared by every
 // board with the same lines and moves left, which boards in lockstep have -- are summed per block in LDS first and only the
 // non-zero sums go to memory.
+//
+// update_trace is update over the last `horizon` states of every board, kept in a ring of slots: a lane per (board, age) PAIR,
+// the age in blockIdx.y, so that a wave's lanes read consecutive 16-byte words of one slot at every age and the decayed rate is
+// one value per block.  A lane first looks at the state field of the younger slots (a dword each, coalesced) and leaves where
+// one of them does not run: what lies behind belongs to an earlier episode.  With kSymmetric every add is made a second time,
+// at the entry of the reflected board (the piece through pi, tuple column 8 - x, the pattern's nibbles swapped), which keeps a
+// mirror-symmetric table mirror-symmetric.  Ages of one board add in any order: the adds are integers and nothing is read.
 #include <cmath>
 
 #include "tpl_placement.h"
@@ -150,6 +158,73 @@ __global__ __launch_bounds__(kStateBlock) void ntuple_update_kernel(const Update
                 for (int x = 0; x < kTupleCols; ++x) {
                     const uint32_t q = pattern(s.c[x], s.c[x + 1], y);
                     if (q) atomicAdd(entry(p.table, base + ((uint32_t)(x * kTupleRows) + y) * (uint32_t)kPatterns + q), d);
+                }
+            }
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int t = threadIdx.x; t < kCounters; t += kStateBlock) {
+        const uint32_t sum = s_counter[t];
+        if (sum) atomicAdd(p.table + kCounterBase + t, sum);
+    }
+}
+
+struct TraceArgs {
+    const uint4* a;              // [slots][n], slot-major: the state of board i at age k in slot (head - k) mod slots
+    const uint4* b;
+    uint32_t n, slots, head;     // slots * n below 2^31 / 40: every index and byte offset fits 32 bits
+    uint32_t L, M;
+    uint32_t* table;             // [TPL_NTUPLE_ENTRIES]: added to, never read
+    const float* error;          // [n]
+    float rate, decay;
+};
+
+constexpr uint32_t kPieceMirror = 0x76453120u;                // pi = [0, 2, 1, 3, 5, 4, 6, 7] (tpl_mirror.h), a nibble per piece
+
+// Age blockIdx.y of the boards blockIdx.x * 256 ..: d = update_step(rate * decay^age, e) on the state of that age, where it
+// and every younger state of the board run.  The weight is `age` rounded multiplies on a block-uniform value, as the rule has it.
+template <bool kSymmetric>
+__global__ __launch_bounds__(kStateBlock) void ntuple_trace_kernel(const TraceArgs p) {
+    __shared__ uint32_t s_counter[kCounters];
+#pragma unroll
+    for (int t = threadIdx.x; t < kCounters; t += kStateBlock) s_counter[t] = 0u;
+    __syncthreads();
+    const uint32_t age = blockIdx.y;                                    // below the horizon, which is at most `slots`
+    float w = 1.0f;
+    for (uint32_t k = 0; k < age; ++k) w = __fmul_rn(w, p.decay);
+    const float rate = __fmul_rn(p.rate, w);
+    const uint32_t i = blockIdx.x * kStateBlock + threadIdx.x;
+    if (i < p.n) {
+        bool open = true;
+        for (uint32_t k = 0; k < age; ++k) {                            // the younger states: only the word that holds the state
+            const uint32_t slot = p.head >= k ? p.head - k : p.head + p.slots - k;
+            open = open && ((p.b[slot * p.n + i].y >> 28) & 3u) == tpl::ST_RUNNING;
+        }
+        const uint32_t d = (uint32_t)update_step(rate, p.error[i]);
+        if (open && d != 0u) {
+            const uint32_t slot = p.head >= age ? p.head - age : p.head + p.slots - age;
+            tpl::Board s;
+            tpl::unpack_board(p.a[slot * p.n + i], p.b[slot * p.n + i], s);
+            if (s.state == tpl::ST_RUNNING) {
+                atomicAdd(&s_counter[counter_index(p.L, p.M, s.lines, s.moves)], d);      // once, symmetric or not
+                const uint32_t piece = s.window & 7u;
+                const uint32_t base = piece * (uint32_t)kPieceStride;
+                const uint32_t mirror_base = ((kPieceMirror >> (4u * piece)) & 7u) * (uint32_t)kPieceStride;
+#pragma unroll 1
+                for (uint32_t y = 0; y < (uint32_t)kTupleRows; ++y) {
+#pragma unroll
+                    for (int x = 0; x < kTupleCols; ++x) {
+                        const uint32_t q = pattern(s.c[x], s.c[x + 1], y);
+                        if (q) {
+                            atomicAdd(entry(p.table, base + ((uint32_t)(x * kTupleRows) + y) * (uint32_t)kPatterns + q), d);
+                            if constexpr (kSymmetric) {                 // both adds, also where the two entries are one
+                                const uint32_t swapped = (q >> 4) | ((q & 15u) << 4);
+                                atomicAdd(entry(p.table, mirror_base + ((uint32_t)((kTupleCols - 1 - x) * kTupleRows) + y) *
+                                                                           (uint32_t)kPatterns + swapped), d);
+                            }
+                        }
+                    }
                 }
             }
         }
@@ -394,19 +469,52 @@ extern "C" int tpl_ntuple_search(const void* plane_a, const void* plane_b, int64
                                 seed, step, action, second, score, after_a, after_b, value, stream);
 }
 
-extern "C" int tpl_ntuple_update(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, int32_t* table,
-                                 const float* error, float rate, void* stream) {
-    const char* name = "tpl_ntuple_update";
+namespace {
+
+// what tpl_ntuple_update and tpl_ntuple_update_trace refuse alike
+int check_update(const char* name, const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const int32_t* table,
+                 const float* error, float rate) {
     if (const int rc = check_planes(name, plane_a, plane_b, n, L, M)) return rc;
     if (const int rc = check_table(name, table)) return rc;
     if (!error) return fail_msg(TPL_ERR_ARG, "%s: null pointer (error is required)", name);
     if ((uintptr_t)error & 3u) return fail_msg(TPL_ERR_ARG, "%s: error must be 4-byte aligned", name);
     if (!std::isfinite(rate)) return fail_msg(TPL_ERR_ARG, "%s: rate must be finite", name);
+    return TPL_OK;
+}
+
+}  // namespace
+
+extern "C" int tpl_ntuple_update(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, int32_t* table,
+                                 const float* error, float rate, void* stream) {
+    if (const int rc = check_update("tpl_ntuple_update", plane_a, plane_b, n, L, M, table, error, rate)) return rc;
     UpdateArgs p{};
     p.a = (const uint4*)plane_a; p.b = (const uint4*)plane_b; p.n = (uint32_t)n;
     p.L = (uint32_t)L; p.M = (uint32_t)M; p.table = (uint32_t*)table; p.error = error; p.rate = rate;
     const dim3 grid((p.n + kStateBlock - 1) / kStateBlock), block(kStateBlock);
     hipLaunchKernelGGL(ntuple_update_kernel, grid, block, 0, (hipStream_t)stream, p);
+    TPL_LEARN_HIP(hipGetLastError());
+    return TPL_OK;
+}
+
+extern "C" int tpl_ntuple_update_trace(const void* ring_a, const void* ring_b, int64_t n, int32_t slots, int32_t head,
+                                       int32_t horizon, int32_t L, int32_t M, int32_t* table, const float* error, float rate,
+                                       float decay, int32_t symmetric, void* stream) {
+    const char* name = "tpl_ntuple_update_trace";
+    if (const int rc = check_update(name, ring_a, ring_b, n, L, M, table, error, rate)) return rc;
+    if (slots < 1 || slots > TPL_NTUPLE_TRACE_MAX + 1)
+        return fail_msg(TPL_ERR_ARG, "%s: slots must be in [1, %d]", name, TPL_NTUPLE_TRACE_MAX + 1);
+    if (head < 0 || head >= slots) return fail_msg(TPL_ERR_ARG, "%s: head must be in [0, slots)", name);
+    if (horizon < 1 || horizon > slots || horizon > TPL_NTUPLE_TRACE_MAX)
+        return fail_msg(TPL_ERR_ARG, "%s: horizon must be in [1, min(slots, %d)]", name, TPL_NTUPLE_TRACE_MAX);
+    if ((int64_t)slots * n >= (((int64_t)1 << 31) + kActions - 1) / kActions)
+        return fail_msg(TPL_ERR_ARG, "%s: 40 * slots * n must stay below 2^31", name);
+    if (!(decay >= 0.0f && decay <= 1.0f)) return fail_msg(TPL_ERR_ARG, "%s: decay must be in [0, 1]", name);
+    TraceArgs p{};
+    p.a = (const uint4*)ring_a; p.b = (const uint4*)ring_b; p.n = (uint32_t)n; p.slots = (uint32_t)slots; p.head = (uint32_t)head;
+    p.L = (uint32_t)L; p.M = (uint32_t)M; p.table = (uint32_t*)table; p.error = error; p.rate = rate; p.decay = decay;
+    const dim3 grid((p.n + kStateBlock - 1) / kStateBlock, (uint32_t)horizon), block(kStateBlock);
+    if (symmetric) hipLaunchKernelGGL(ntuple_trace_kernel<true>, grid, block, 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(ntuple_trace_kernel<false>, grid, block, 0, (hipStream_t)stream, p);
     TPL_LEARN_HIP(hipGetLastError());
     return TPL_OK;
 }

@@ -10,9 +10,13 @@ learning on the device (the rule: include/tpl_learn.h; the kernels: csrc/learn/n
                                   afterstate of the action played and its value.  depth=2 searches the known next piece as well,
                                   still in one launch:  r + gamma * max_b (r_b + gamma * V)  -- the value of the afterstate itself,
                                   with the table one move further out; act(second=) gives the placement planned for that piece
-    NTupleLearner(env, gamma, rate, epsilon, seed, depth=1)
+    NTupleLearner(env, gamma, rate, epsilon, seed, depth=1, lam=0.0, horizon=1, symmetric=False)
                                   TD(0) on afterstates: train(steps), evaluate(steps, depth=None); `table` is a plain tensor
-                                  (torch.save it); a table trained at one depth can be played at the other
+                                  (torch.save it); a table trained at one depth can be played at the other.  horizon > 1 adds
+                                  truncated TD(lambda) traces -- the error also goes, decayed by (gamma lam)^k, to the afterstates
+                                  k < horizon moves back in the same episode --, symmetric=True adds every update to the entries of
+                                  the reflected board as well, which keeps the table mirror-symmetric
+    ntuple_is_symmetric(table)    whether table[sigma] == table under the mirror permutation of the entries
 
 The value is a sum of table entries, one per 2 x 4 window of the board that is not empty, chosen by the falling piece, plus one
 per (lines left, moves left); the update adds rint(rate * error) to the same entries.  Everything is integer, so two trainings
@@ -26,10 +30,10 @@ from typing import Optional
 import torch
 
 from . import _learn_lib
-from ._learn_lib import NTUPLE_ENTRIES, check
+from ._learn_lib import NTUPLE_ENTRIES, NTUPLE_TRACE_MAX, check
 from .lookahead import _MAX_BOARDS, _ptr, _state_ptrs
 
-__all__ = ["NTUPLE_ENTRIES", "ntuple_table", "ntuple_value", "NTuplePolicy", "NTupleLearner"]
+__all__ = ["NTUPLE_ENTRIES", "ntuple_table", "ntuple_value", "ntuple_is_symmetric", "NTuplePolicy", "NTupleLearner"]
 
 _STATE_WON = 1                                                 # bits 28..29 of B.y: 0 running, 1 won, 2 and 3 lost
 _FINISHED_B_Y = _STATE_WON << 28                               # B.y of a state that is finished and otherwise empty
@@ -69,6 +73,12 @@ def _depth(depth) -> int:
     if isinstance(depth, bool) or depth not in (1, 2):
         raise ValueError(f"depth must be 1 or 2 (an afterstate knows its next piece and no more), got {depth!r}")
     return int(depth)
+
+
+def _horizon(horizon) -> int:
+    if isinstance(horizon, bool) or not isinstance(horizon, int) or not 1 <= horizon <= NTUPLE_TRACE_MAX:
+        raise ValueError(f"horizon must be an integer in 1 .. {NTUPLE_TRACE_MAX}, got {horizon!r}")
+    return int(horizon)
 
 
 def _boards(env, who: str) -> int:
@@ -123,6 +133,22 @@ def ntuple_value(source, table: torch.Tensor, L: Optional[int] = None, M: Option
         raise ValueError(f"out must be a contiguous float32 tensor of shape ({k},) on {device}")
     _value(a, b, k, int(L), int(M), table, out, device)
     return out
+
+
+_sigma = {}                                                    # the mirror permutation, once per device
+
+
+@torch.no_grad()
+def ntuple_is_symmetric(table: torch.Tensor) -> bool:
+    """Whether `table` is mirror-symmetric: table[sigma(j)] == table[j] for every j, sigma = _learn_lib.ntuple_mirror_permutation()
+    (include/tpl_learn.h states the invariant).  Under such a table a board and its reflection have the same value, bit for bit.
+    One gather and one comparison on the table's device; the answer is a host bool, so this syncs."""
+    if not isinstance(table, torch.Tensor):
+        raise ValueError(f"table must be a contiguous int32 tensor of {NTUPLE_ENTRIES} entries (ntuple_table)")
+    _table(table, table.device)
+    if table.device not in _sigma:
+        _sigma[table.device] = torch.from_numpy(_learn_lib.ntuple_mirror_permutation()).to(table.device)
+    return bool(torch.equal(table[_sigma[table.device]], table))
 
 
 class NTuplePolicy:
@@ -201,14 +227,34 @@ class NTupleLearner:
     nothing: a board that auto-resets drops out by the rule, without a mask.  `rate` is in table units per unit of error: the
     step of V for one state alone is about rate * 2^-16 * (tuples in use + 1), and boards that share entries add up -- so it is
     small for many boards in lockstep.  At depth 2 `policy` and `greedy` search two plies, so the target of a kept afterstate
-    is the two-ply greedy score of the state it became; nothing else in the loop changes."""
+    is the two-ply greedy score of the state it became; nothing else in the loop changes.
 
-    def __init__(self, env, gamma: float = 0.99, rate: float = 8.0, epsilon: float = 0.1, seed: int = 0, depth: int = 1):
+    Traces and symmetry (tpl_ntuple_update_trace; both off by default, which leaves the table bytes of the loop above).  The
+    afterstates of the last `horizon` steps stay in a ring of horizon + 1 slots, and step 3 adds  rint(rate * (gamma lam)^k *
+    error)  to the afterstate k steps back, k < horizon, as long as it and every younger one run -- an episode's end cuts the
+    trace by the same rule that drops a finished board.  Truncated TD(lambda): the effective step of V grows by about
+    sum_k (gamma lam)^k, so `rate` wants to shrink with it.  Traces are NOT cut on exploratory moves (the naive form): the error
+    of a step whose predecessor explored still reaches the older afterstates.  symmetric=True adds every update to the table
+    entries of the reflected board too (L <-> J, S <-> Z): the table stays mirror-symmetric (ntuple_is_symmetric), each board
+    teaches its reflection, and the step of V doubles once more.  Still five enqueues a step, no sync, nothing allocated."""
+
+    def __init__(self, env, gamma: float = 0.99, rate: float = 8.0, epsilon: float = 0.1, seed: int = 0, depth: int = 1,
+                 lam: float = 0.0, horizon: int = 1, symmetric: bool = False):
         n = _boards(env, "NTupleLearner")
         if not env.auto_reset:
             raise ValueError("NTupleLearner needs an auto-reset environment")
         self.env, self.rate = env, _finite("rate", rate)
         _unit("epsilon", epsilon), _finite("gamma", gamma), _count("seed", seed)
+        self.lam, self.horizon = _unit("lam", lam), _horizon(horizon)
+        if not isinstance(symmetric, bool):
+            raise ValueError(f"symmetric must be True or False, got {symmetric!r}")
+        self.symmetric = symmetric
+        self.decay = float(gamma) * self.lam                   # the C `decay`, passed as a float
+        if not 0.0 <= self.decay <= 1.0:
+            raise ValueError(f"gamma * lam must be in [0, 1] (it decays the trace), got {self.decay!r}")
+        self.slots = self.horizon + 1
+        if self.slots * n > _MAX_BOARDS:
+            raise ValueError(f"(horizon + 1) * boards must stay at or below {_MAX_BOARDS}")
         d = env.device
         self.depth = _depth(depth)
         self.table = ntuple_table(d)
@@ -218,15 +264,28 @@ class NTupleLearner:
         self._action = torch.empty(n, dtype=torch.uint8, device=d)
         self._done = torch.empty(n, dtype=torch.uint8, device=d)
         self._reward, self._score, self._kept_value, self._error = (torch.empty(n, dtype=torch.float32, device=d) for _ in range(4))
-        self._kept = tuple(torch.empty((n, 4), dtype=torch.int32, device=d) for _ in range(2))
-        self._next = tuple(torch.empty((n, 4), dtype=torch.int32, device=d) for _ in range(2))
+        # the afterstates of the last steps, slot-major: age k of the newest is slot (head - k) mod slots; act writes the next
+        # ones into slot head + 1, the one slot no age of the update reads
+        self._ring = tuple(torch.empty((self.slots, n, 4), dtype=torch.int32, device=d) for _ in range(2))
+        self._slot = [(self._ring[0][k], self._ring[1][k]) for k in range(self.slots)]
+        self._head = 0
         self.forget()
 
+    @property
+    def _kept(self):
+        """The newest kept afterstates: slot `head` of the ring."""
+        return self._slot[self._head]
+
+    @property
+    def _next(self):
+        """Where act writes the afterstates of the step being made: slot head + 1."""
+        return self._slot[(self._head + 1) % self.slots]
+
     def forget(self) -> None:
-        """Nothing is kept from the step before: the kept afterstates become finished states, which update nothing."""
-        self._kept[0].zero_()
-        self._kept[1].zero_()
-        self._kept[1][:, 1] = _FINISHED_B_Y
+        """Nothing is kept from the steps before: every slot becomes finished states, which update nothing."""
+        for ring in self._ring:
+            ring.zero_()
+        self._ring[1][:, :, 1] = _FINISHED_B_Y
 
     @torch.no_grad()
     def train(self, steps: int) -> int:
@@ -235,14 +294,17 @@ class NTupleLearner:
         steps = _count("steps", steps, 1)
         env, n, lib = self.env, self.env.num_envs, _learn_lib.lib()
         stream = torch._C._cuda_getCurrentRawStream(env.device.index)
+        ring_a, ring_b = self._ring[0].data_ptr(), self._ring[1].data_ptr()
         for _ in range(steps):
+            kept = self._kept
             self.policy.act(out=self._action, score=self._score, after=self._next, step=self.steps)
-            _value(self._kept[0], self._kept[1], n, env.L, env.M, self.table, self._kept_value, env.device)
+            _value(kept[0], kept[1], n, env.L, env.M, self.table, self._kept_value, env.device)
             torch.sub(self._score, self._kept_value, out=self._error)
-            check(lib.tpl_ntuple_update(self._kept[0].data_ptr(), self._kept[1].data_ptr(), n, env.L, env.M, self.table.data_ptr(),
-                                        self._error.data_ptr(), self.rate, stream))
+            check(lib.tpl_ntuple_update_trace(ring_a, ring_b, n, self.slots, self._head, self.horizon, env.L, env.M,
+                                              self.table.data_ptr(), self._error.data_ptr(), self.rate, self.decay,
+                                              int(self.symmetric), stream))
             env.step_into(self._action, self._reward, self._done)
-            self._kept, self._next = self._next, self._kept
+            self._head = (self._head + 1) % self.slots
             self.steps += 1
         return self.steps
 

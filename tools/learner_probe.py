@@ -56,6 +56,14 @@ Parts:
               environment, tpl_ntuple_act over its 40 x 16,384 boards, a torch max), alternated in one process; on an L=10 / M=40
               carved pool the win rates at depth 1 and 2 of a table trained at depth 1 and of one trained at depth 2 (the shaped
               reward, 4,096 boards, 40,000 steps) beside the classical weights' at one and two plies
+    ntuple_trace   the update with traces and mirror symmetry: tpl_ntuple_update_trace at 2^16, 2^18 and 2^20 boards for horizon 1, 4,
+              8 and 16, symmetric and not, decay 0.9 and errors of order 1, over a ring of 17 slots that holds the boards' last 17
+              states (L=10 / M=40, mid-game), alternated over five rounds with tpl_ntuple_update on the newest slot; the prediction
+              is tpl_ntuple_update's time of the same run times the (board, age) pairs that add (the trace is open and the step is
+              not 0) per board, times two where symmetric; bytes/s by the entries in use as part ntuple counts them
+    ntuple_trace_sweep  NTupleLearner on part ntuple's L=10 / M=40 carved pool (the shaped reward, 4,096 boards, epsilon 0.05, gamma
+              1, 40,000 steps, wins over 12,288 greedy steps): the TD(0) baseline at rate 16 re-run, then lambda in 0.5, 0.8, 0.9 x
+              horizon in 4, 8 x symmetric or not x rate in 4, 8, 16, and symmetry alone (horizon 1) at the three rates
 """
 import argparse
 import json
@@ -70,7 +78,7 @@ sys.path.insert(0, ROOT)
 HBM_ACHIEVABLE = 6.3e12
 PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600, "priority": 600, "nstep": 600, "mirror": 600, "afterstates": 600,
          "heuristic": 600, "search": 900, "beam": 900, "ntuple": 900,
-         "ntuple_search": 900}
+         "ntuple_search": 900, "ntuple_trace": 600, "ntuple_trace_sweep": 1100}
 SCATTERED_ATOMICS = 0.08e12                                 # 64 lanes of a wave adding into 64 rows (float adds; integer adds unmeasured)
 VALU_CYCLES, SIMDS, CLOCK_HZ = 3.3, 1024, 2.4e9           # the move's instruction mix, 256 CUs x 4, the clock
 
@@ -1099,6 +1107,111 @@ def part_ntuple_search(rounds=5):
     env.terminate()
     out["l10_m40"] = dict(pool=1 << 16, pool_seed=7, eval_steps=12288, tables=trained, **heuristic)
     return out
+
+
+def part_ntuple_trace(rounds=5, reps=10):
+    import numpy as np
+    import torch
+    import tetris_piclim as T
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import learn_ref as R
+    m = T._learn_lib
+    L, check = m.lib(), m.check
+    stream = torch._C._cuda_getCurrentRawStream(0)
+    slots, head, rate, decay = 17, 16, 100.0, 0.9
+    out = dict(part="ntuple_trace", slots=slots, head=head, rate=rate, decay=decay,
+               static_valu={k: _static_valu(k, m.build_library()) for k in ("ntuple_update_kernel", "ntuple_trace_kernelILb0", "ntuple_trace_kernelILb1")})
+    host = np.random.default_rng(0).integers(-(1 << 20), (1 << 20) + 1, m.NTUPLE_ENTRIES).astype(np.int32)
+    rows = []
+    for n in (1 << 16, 1 << 18, 1 << 20):
+        env = T.BatchedTetris(10, 40, n, device="cuda:0", seed=1, auto_reset=True)
+        env.load_configs(*env.synthetic_configs(4096))
+        env.reset()
+        ring = [torch.empty((slots, n, 4), dtype=torch.int32, device="cuda:0") for _ in range(2)]
+        for t in range(6 + slots):                               # mid-game boards: the last 17 states of every board, oldest first
+            env.step(env.synthetic_actions(t), observe=False)
+            if t >= 6:
+                a, b = env.raw_planes()
+                ring[0][t - 6].copy_(a)
+                ring[1][t - 6].copy_(b)
+        a, b = (x[head, :4096].cpu().numpy().view(np.uint32) for x in ring)
+        f = R.decode_state(a, b)
+        _, used = m.ntuple_indices(f["rows"], f["cur"], 10, 40, f["lines"].astype(np.int64), f["moves"].astype(np.int64))
+        in_use = float(used[f["state"] == 0].sum(axis=1).mean())   # entries per running board of the newest slot, the counter included
+        table = torch.from_numpy(host).to("cuda:0")
+        error = torch.empty(n, dtype=torch.float32, device="cuda:0").normal_()
+        # the (board, age) pairs that add: every state up to that age runs and rint(rate * decay^k * e) is not 0
+        running = ((ring[1][:, :, 1] >> 28) & 3) == 0
+        open_ = torch.cumprod(running.flip(0).to(torch.int32), dim=0).bool()         # [age, n]: slot head - age
+        w = torch.tensor([decay], dtype=torch.float32, device="cuda:0") ** torch.arange(slots, device="cuda:0", dtype=torch.float32)
+        adds = open_ & (torch.round(rate * w[:, None] * error[None, :]) != 0)
+        pairs = {h: float(adds[:h].sum()) / n for h in (1, 4, 8, 16)}
+        pa, pb = ring[0].data_ptr(), ring[1].data_ptr()
+
+        def trace(horizon, symmetric):
+            check(L.tpl_ntuple_update_trace(pa, pb, n, slots, head, horizon, 10, 40, table.data_ptr(), error.data_ptr(), rate, decay,
+                                            symmetric, stream))
+        variants = [("update", lambda: check(L.tpl_ntuple_update(ring[0][head].data_ptr(), ring[1][head].data_ptr(), n, 10, 40,
+                                                                 table.data_ptr(), error.data_ptr(), rate, stream)))]
+        variants += [(f"h{h}_s{sym}", (lambda h=h, sym=sym: trace(h, sym))) for h in (1, 4, 8, 16) for sym in (0, 1)]
+        times = {name: [] for name, _ in variants}
+        for _ in range(rounds):                                  # alternate the variants round by round
+            for name, fn in variants:
+                times[name].append(_timed(fn, reps))
+        med = {name: sorted(ts)[rounds // 2] for name, ts in times.items()}
+        row = dict(boards=n, entries_in_use_per_board=round(in_use, 1), running_share_of_the_newest_slot=round(float(running[head].float().mean()), 4),
+                   adding_pairs_per_board={f"h{h}": round(p, 3) for h, p in pairs.items()},
+                   update=dict(us=_spread(times["update"]), tb_per_s=round(n * pairs[1] * in_use * 4 / med["update"] / 1e12, 3)))
+        for h in (1, 4, 8, 16):
+            for sym in (0, 1):
+                name = f"h{h}_s{sym}"
+                predicted = med["update"] * pairs[h] / pairs[1] * (2 if sym else 1)
+                nbytes = n * pairs[h] * (in_use * (2 if sym else 1) - (1 if sym else 0)) * 4       # the counter: once
+                row[name] = dict(us=_spread(times[name]), over_update=round(med[name] / med["update"], 2),
+                                 predicted_over_update=round(predicted / med["update"], 2),
+                                 measured_over_predicted=round(med[name] / predicted, 3),
+                                 tb_per_s=round(nbytes / med[name] / 1e12, 3))
+        rows.append(row)
+        env.terminate()
+        del table, ring, running, open_, adds
+        torch.cuda.empty_cache()
+    out["kernel"] = dict(rounds=rounds, launches_per_timing=reps, rows=rows)
+    return out
+
+
+def part_ntuple_trace_sweep(eval_steps=12288):
+    import torch
+    import tetris_piclim as T
+    gen_env = T.BatchedTetris(10, 40, 64, device="cuda:0", seed=7)
+    big = gen_env.carved_configs(1 << 16, seed=7)
+    gen_env.terminate()
+
+    def learn(**kw):
+        """part_ntuple's sequence: the zero table played, 10,000 steps, an evaluation, 30,000 steps, an evaluation."""
+        env = T.BatchedTetris(10, 40, 4096, device="cuda:0", seed=11, auto_reset=True, reward=NTUPLE_LARGE_REWARD, config_pool=big)
+        learner = T.NTupleLearner(env, seed=11, gamma=1.0, epsilon=0.05, **kw)
+        learner.evaluate(eval_steps)
+        got = dict(kw, trained=[])
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for steps in (10000, 30000):
+            learner.train(steps)
+            r = learner.evaluate(eval_steps)
+            p = r["win_rate"]
+            got["trained"].append(dict(steps=learner.steps, episodes=r["episodes"], wins=r["wins"], win_rate=round(p, 5),
+                                       standard_error=round((p * (1 - p) / max(r["episodes"], 1)) ** 0.5, 6)))
+        got.update(seconds=round(time.perf_counter() - t0, 2), entries_in_use=int((learner.table != 0).sum()),
+                   largest_entry=int(learner.table.abs().max()), symmetric_table=T.ntuple_is_symmetric(learner.table))
+        env.terminate()
+        print(json.dumps(got), file=sys.stderr, flush=True)      # progress: a long part must not stay silent
+        return got
+    runs = [learn(rate=16.0)]
+    runs += [learn(rate=rate, symmetric=True) for rate in (4.0, 8.0, 16.0)]
+    runs += [learn(rate=rate, lam=lam, horizon=horizon, symmetric=symmetric) for lam in (0.5, 0.8, 0.9) for horizon in (4, 8)
+             for symmetric in (False, True) for rate in (4.0, 8.0, 16.0)]
+    best = max(runs, key=lambda r: r["trained"][-1]["win_rate"])
+    return dict(part="ntuple_trace_sweep", boards=4096, seed=11, pool=1 << 16, pool_seed=7, reward=list(NTUPLE_LARGE_REWARD), gamma=1.0,
+                epsilon=0.05, eval_steps=eval_steps, baseline=runs[0], best=best, runs=runs)
 
 
 def main():
