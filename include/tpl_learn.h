@@ -411,8 +411,10 @@ int tpl_ntuple_search(const void* plane_a, const void* plane_b, int64_t n, int32
                       float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed, uint64_t step, uint8_t* action,
                       uint8_t* second, float* score, void* after_a, void* after_b, float* value, void* stream);
 
-/* The update above: error f32 [n], one per state of plane_a / plane_b.  Refused before any HIP call: tpl_ntuple_value's plane, n,
- * L, M and table checks, error NULL or not 4-byte aligned, rate not finite. */
+/* The update above: error f32 [n], one per state of plane_a / plane_b.  It is tpl_ntuple_update_trace (below) on the planes as a
+ * ring of one slot, head 0, horizon 1, not symmetric, and it launches that entry's kernel (ntuple_trace_kernel<false>): age 0 has
+ * the weight w_0 = 1 whatever the decay, so d is rint(rate * e).  Refused before any HIP call, under its own name:
+ * tpl_ntuple_value's plane, n, L, M and table checks, error NULL or not 4-byte aligned, rate not finite. */
 int tpl_ntuple_update(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, int32_t* table,
                       const float* error, float rate, void* stream);
 

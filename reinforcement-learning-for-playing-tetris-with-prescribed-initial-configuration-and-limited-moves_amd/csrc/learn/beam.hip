@@ -61,28 +61,19 @@ struct Beam {
     uint32_t path[kMaxWidth][kMaxDepth / 4];                  // a placement a byte, kNoMove behind the last
 };
 
-// the k-th distinct placement of piece `cur` in ascending b = 10 r + l: rotation r has 10 - w(cur, r) + 1 of them
+// the k-th distinct placement of piece `cur` in ascending b = 10 r + l: rotation r has location_count(cur, r) of them
 __device__ __forceinline__ uint32_t nth_placement(uint32_t cur, uint32_t k, uint32_t& r, uint32_t& l) {
-    const uint32_t last_rot = (kRotationMasks >> (2u * cur)) & 3u;
+    const uint32_t last_rot = last_rotation(cur);
     r = 0u;
     l = k;
 #pragma unroll
     for (int step = 0; step < 3; ++step) {
-        const uint32_t count = 10u - ((uint32_t)(kWidthsLess1 >> (2u * (cur * 4u + r))) & 3u);
+        const uint32_t count = location_count(cur, r);
         const bool over = l >= count && r < last_rot;
         l -= over ? count : 0u;
         r += over ? 1u : 0u;
     }
     return 10u * r + l;
-}
-
-__device__ __forceinline__ uint32_t placement_count(uint32_t cur) {
-    const uint32_t last_rot = (kRotationMasks >> (2u * cur)) & 3u;
-    uint32_t total = 0u;
-#pragma unroll
-    for (uint32_t r = 0; r < 4u; ++r)
-        total += r <= last_rot ? 10u - ((uint32_t)(kWidthsLess1 >> (2u * (cur * 4u + r))) & 3u) : 0u;
-    return total;
 }
 
 // Candidate k of running parent q: the board the move leaves (window not yet popped), the rows cleared with the parent's, and

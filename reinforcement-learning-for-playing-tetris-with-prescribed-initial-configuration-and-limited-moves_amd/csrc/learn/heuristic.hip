@@ -19,7 +19,7 @@
 //
 // That frame -- block prologue, lane decode, first move, arg-max and the winner's stores -- is written once, in
 // placement_policy<kPlies>; placement_act_kernel and placement_search_kernel are its two instances.  What a lane's first move
-// is worth is the one thing that differs: its own score at one ply, the best second placement's (second_ply) at two.
+// is worth is the one thing that differs: its own score at one ply, the best second placement's (best_second) at two.
 #include "tpl_placement.h"
 
 namespace tpl_learn {
@@ -61,36 +61,6 @@ __global__ __launch_bounds__(kFeatureBlock) void placement_features_kernel(const
     if (p.canonical) p.canonical[j] = (uint8_t)canonical_action(cur, r, l);
 }
 
-constexpr uint32_t kNoSecond = 255u;
-
-// The second ply with the known next piece: the best score among the distinct placements of s1's current piece on s1, the
-// board a first move that cleared n1 rows left (popped, still running), and the placement it belongs to.  Copies s1, moves and
-// scores once per distinct placement in ascending b = 10 r2 + l2 -- r2 below nrot, l2 up to 10 - w: 9, 17 or 34 trips, the
-// same for the 40 lanes of a board -- and keeps a running best under a strict > on the ordered key, so the lowest b survives.
-__device__ __forceinline__ float second_ply(const tpl::Board& s1, uint32_t n1, const tpl::ShapeWord* shape, uint32_t L, uint32_t M,
-                                            const float (&w)[kFeatures], uint32_t& second) {
-    const uint32_t nxt = s1.window & 7u;
-    const uint32_t last_rot = (kRotationMasks >> (2u * nxt)) & 3u;
-    uint32_t best_key = 0u, r2 = 0u, l2 = 0u;
-    float value = 0.0f;
-#pragma unroll 1
-    while (r2 <= last_rot) {
-        tpl::Board s2 = s1;
-        bool topout;
-        const uint32_t n2 = tpl::move_board(s2, shape, r2, l2, L, M, topout);
-        Features psi;
-        moved_features(s2, n1 + n2, true, psi);
-        const float sc = placement_score(w, psi);
-        const uint32_t key = ordered_bits(sc);                          // never 0, so the first trip is taken
-        if (key > best_key) { best_key = key; value = sc; second = 10u * r2 + l2; }
-        const uint32_t right = 9u - ((uint32_t)(kWidthsLess1 >> (2u * (nxt * 4u + r2))) & 3u);      // 10 - w
-        const bool wrap = l2 >= right;
-        l2 = wrap ? 0u : l2 + 1u;
-        r2 += wrap ? 1u : 0u;
-    }
-    return value;
-}
-
 struct PolicyArgs {
     const uint4* a;              // [n]
     const uint4* b;
@@ -104,7 +74,7 @@ struct PolicyArgs {
 };
 
 // The policy of kPlies plies on the block's eight boards (the header comment has the frame).  A lane's value is the score of
-// what its first move leaves; at two plies, where that move leaves the game running, it is second_ply's instead.  Alias lanes
+// what its first move leaves; at two plies, where that move leaves the game running, it is best_second's instead.  Alias lanes
 // and lanes whose first move ended the game (or whose board is finished: all-zero features) keep the one-ply score.
 template <int kPlies>
 __device__ __forceinline__ void placement_policy(const PolicyArgs& p) {
@@ -150,7 +120,11 @@ __device__ __forceinline__ void placement_policy(const PolicyArgs& p) {
     float value;
     uint32_t second = kNoSecond;
     if (goes_on) {
-        value = second_ply(s1, n1, s_shape, p.L, p.M, w, second);
+        value = best_second(s1, s_shape, p.L, p.M, second, [&](const tpl::Board& s2, uint32_t n2) {
+            Features psi;
+            moved_features(s2, n1 + n2, true, psi);                     // the rows of both moves, the board of the second
+            return placement_score(w, psi);
+        });
     } else {
         Features phi;
         moved_features(s1, n1, running, phi);

@@ -31,7 +31,8 @@
 //
 // update_trace is update over the last `horizon` states of every board, kept in a ring of slots: a lane per (board, age) PAIR,
 // the age in blockIdx.y, so that a wave's lanes read consecutive 16-byte words of one slot at every age and the decayed rate is
-// one value per block.  A lane first looks at the state field of the younger slots (a dword each, coalesced) and leaves where
+// one value per block.  There is one update kernel, ntuple_trace_kernel: tpl_ntuple_update launches it on its planes as a ring of
+// one slot with a horizon of one, where age 0 has no younger slot to look at and a weight of exactly 1.  A lane first looks at the state field of the younger slots (a dword each, coalesced) and leaves where
 // one of them does not run: what lies behind belongs to an earlier episode.  With kSymmetric every add is made a second time,
 // at the entry of the reflected board (the piece through pi, tuple column 8 - x, the pattern's nibbles swapped), which keeps a
 // mirror-symmetric table mirror-symmetric.  Ages of one board add in any order: the adds are integers and nothing is read.
@@ -77,6 +78,14 @@ __device__ __forceinline__ T* entry(T* table, uint32_t index) {
     return (T*)((const char*)table + index * (uint32_t)sizeof(T));
 }
 
+// The index of pattern q of tuple (x, y) among the rows of the piece that start at `base`, a multiple of 256: the row, then q
+// in its low eight bits.  | q and not + q: the sum is the same, but as a function's + the compiler reassociates it and then
+// addresses the gathers with 64-bit adds (172 vector instructions for 156 in ntuple_value_kernel).
+static_assert(kPatterns == 256 && kPieceStride % kPatterns == 0, "a row's index has its low eight bits clear");
+__device__ __forceinline__ uint32_t tuple_entry(uint32_t base, int x, uint32_t y, uint32_t q) {
+    return (base + ((uint32_t)(x * kTupleRows) + y) * (uint32_t)kPatterns) | q;
+}
+
 // The integer value of a running board with column words c (bits 20.. clear), falling piece `piece` and counter entry k: the
 // sum over the tuples with a non-zero pattern plus the counter, exact in 64 bits.
 __device__ __forceinline__ long long ntuple_sum(const uint32_t (&c)[tpl::kCols], uint32_t piece, uint32_t k, const int32_t* table) {
@@ -88,7 +97,7 @@ __device__ __forceinline__ long long ntuple_sum(const uint32_t (&c)[tpl::kCols],
 #pragma unroll
         for (int x = 0; x < kTupleCols; ++x) {
             const uint32_t q = pattern(c[x], c[x + 1], y);
-            const int32_t e = *entry(table, base + ((uint32_t)(x * kTupleRows) + y) * (uint32_t)kPatterns + q);
+            const int32_t e = *entry(table, tuple_entry(base, x, y, q));
             v[x] = q ? e : 0;
         }
 #pragma unroll
@@ -122,52 +131,11 @@ __global__ __launch_bounds__(kStateBlock) void ntuple_value_kernel(const ValueAr
     p.value[i] = v;
 }
 
-struct UpdateArgs {
-    const uint4* a;              // [n]
-    const uint4* b;
-    uint32_t n;
-    uint32_t L, M;
-    uint32_t* table;             // [TPL_NTUPLE_ENTRIES]: added to, never read; unsigned so that the adds wrap
-    const float* error;          // [n]
-    float rate;
-};
-
 // d = (int32) rint(rate * e): the product rounded once, clamped to +-2^24, 0 for a NaN
 __device__ __forceinline__ int32_t update_step(float rate, float e) {
     const float x = rate * e;
     if (x != x) return 0;
     return (int32_t)rintf(fminf(fmaxf(x, -0x1p24f), 0x1p24f));
-}
-
-__global__ __launch_bounds__(kStateBlock) void ntuple_update_kernel(const UpdateArgs p) {
-    __shared__ uint32_t s_counter[kCounters];
-#pragma unroll
-    for (int t = threadIdx.x; t < kCounters; t += kStateBlock) s_counter[t] = 0u;
-    __syncthreads();
-    const uint32_t i = blockIdx.x * kStateBlock + threadIdx.x;
-    if (i < p.n) {
-        tpl::Board s;
-        tpl::unpack_board(p.a[i], p.b[i], s);
-        const uint32_t d = (uint32_t)update_step(p.rate, p.error[i]);
-        if (s.state == tpl::ST_RUNNING && d != 0u) {
-            atomicAdd(&s_counter[counter_index(p.L, p.M, s.lines, s.moves)], d);
-            const uint32_t base = (s.window & 7u) * (uint32_t)kPieceStride;
-#pragma unroll 1
-            for (uint32_t y = 0; y < (uint32_t)kTupleRows; ++y) {
-#pragma unroll
-                for (int x = 0; x < kTupleCols; ++x) {
-                    const uint32_t q = pattern(s.c[x], s.c[x + 1], y);
-                    if (q) atomicAdd(entry(p.table, base + ((uint32_t)(x * kTupleRows) + y) * (uint32_t)kPatterns + q), d);
-                }
-            }
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int t = threadIdx.x; t < kCounters; t += kStateBlock) {
-        const uint32_t sum = s_counter[t];
-        if (sum) atomicAdd(p.table + kCounterBase + t, sum);
-    }
 }
 
 struct TraceArgs {
@@ -217,11 +185,10 @@ __global__ __launch_bounds__(kStateBlock) void ntuple_trace_kernel(const TraceAr
                     for (int x = 0; x < kTupleCols; ++x) {
                         const uint32_t q = pattern(s.c[x], s.c[x + 1], y);
                         if (q) {
-                            atomicAdd(entry(p.table, base + ((uint32_t)(x * kTupleRows) + y) * (uint32_t)kPatterns + q), d);
+                            atomicAdd(entry(p.table, tuple_entry(base, x, y, q)), d);
                             if constexpr (kSymmetric) {                 // both adds, also where the two entries are one
                                 const uint32_t swapped = (q >> 4) | ((q & 15u) << 4);
-                                atomicAdd(entry(p.table, mirror_base + ((uint32_t)((kTupleCols - 1 - x) * kTupleRows) + y) *
-                                                                           (uint32_t)kPatterns + swapped), d);
+                                atomicAdd(entry(p.table, tuple_entry(mirror_base, kTupleCols - 1 - x, y, swapped)), d);
                             }
                         }
                     }
@@ -255,52 +222,8 @@ struct ActArgs {
 
 constexpr uint32_t kGreedy = 0xFFFFFFFFu;
 
-// 10 - w(cur, r): the right-most location of rotation r
-__device__ __forceinline__ uint32_t right_most(uint32_t cur, uint32_t r) {
-    return 9u - ((uint32_t)(kWidthsLess1 >> (2u * (cur * 4u + r))) & 3u);
-}
-
-constexpr uint32_t kNoSecond = 255u;
-
-// The second ply with the known next piece: W = the best  r2 + gamma V(s2)  (r2 alone where the second move ends the game) among
-// the distinct placements of s1's current piece on s1, the popped and still running board a first move left, and the placement
-// it belongs to.  heuristic.hip's second_ply with the table in place of the features: a copy of s1, the move, the pop, the sum
-// on the board in registers and the score, once per distinct placement in ascending b = 10 r2 + l2 -- 9, 17 or 34 trips, the
-// same for the 40 lanes of a board -- under a strict > on the ordered key, so the lowest b survives.  r2 and l2 are values out
-// of the packed widths, never register indices.
-__device__ __forceinline__ float second_ply(const tpl::Board& s1, const tpl::ShapeWord* shape, uint32_t L, uint32_t M, float r_line,
-                                            float r_win, float r_lose, float gamma, const int32_t* table, uint32_t& second) {
-    const uint32_t nxt = s1.window & 7u;
-    const uint32_t last_rot = (kRotationMasks >> (2u * nxt)) & 3u;
-    uint32_t best_key = 0u, r2 = 0u, l2 = 0u;
-    float best = 0.0f;
-#pragma unroll 1
-    while (r2 <= last_rot) {
-        tpl::Board s2 = s1;
-        bool topout;
-        const uint32_t n2 = tpl::move_board(s2, shape, r2, l2, L, M, topout);
-        tpl::next_window(s2, false, 0);                                 // the piece after the next: the original window entry 2
-        const bool goes_on = s2.state == tpl::ST_RUNNING;
-        float v = 0.0f;
-        if (goes_on) v = ntuple_value(s2, L, M, table);
-        float q;
-        {
-#pragma clang fp contract(off)
-            const float reward = move_reward(r_line, r_win, r_lose, n2, s2.state);
-            const float later = gamma * v;
-            q = goes_on ? reward + later : reward;
-        }
-        const uint32_t key = ordered_bits(q);                           // never 0, so the first trip is taken
-        if (key > best_key) { best_key = key; best = q; second = 10u * r2 + l2; }
-        const bool wrap = l2 >= right_most(nxt, r2);
-        l2 = wrap ? 0u : l2 + 1u;
-        r2 += wrap ? 1u : 0u;
-    }
-    return best;
-}
-
 // The policy of kDepth plies on the block's eight boards (the header comment has the frame).  What a first move that leaves the
-// game running is worth beyond its reward is the one thing that differs: V of the board it left at one ply, second_ply's W at
+// game running is worth beyond its reward is the one thing that differs: V of the board it left at one ply, best_second's W at
 // two.  At two plies V of the afterstate is not on the way to the score, so the one chosen lane of a board sums it afterwards,
 // and only where `value` is asked for.
 template <int kDepth>
@@ -314,13 +237,9 @@ __device__ __forceinline__ void ntuple_policy(const ActArgs& p, uint8_t* second_
         s_best[threadIdx.x] = 0ull;                                     // below every key: a key's high word has a bit set
         const uint32_t board = min(first + threadIdx.x, p.n - 1u);
         const uint4 B = p.b[board];
-        const uint32_t cur = B.w & 7u, last_rot = (kRotationMasks >> (2u * cur)) & 3u;
-        uint32_t distinct = 0u;
-#pragma unroll
-        for (uint32_t r = 0; r < 4u; ++r) distinct += r <= last_rot ? right_most(cur, r) + 1u : 0u;
         const uint64_t h = draw_hash(p.key, board);
         const bool explores = tpl::packed_state(B) == tpl::ST_RUNNING && (uint32_t)(h >> 40) < p.explore_below;
-        s_pick[threadIdx.x] = explores ? __umulhi((uint32_t)h, distinct) : kGreedy;
+        s_pick[threadIdx.x] = explores ? __umulhi((uint32_t)h, placement_count(B.w & 7u)) : kGreedy;
     }
     __syncthreads();
     const uint32_t slot = threadIdx.x / kActions, a = threadIdx.x - slot * kActions;
@@ -340,12 +259,23 @@ __device__ __forceinline__ void ntuple_policy(const ActArgs& p, uint8_t* second_
     // the rank of a distinct placement among its piece's, in ascending a: the locations of the rotations before it, then l
     uint32_t rank = l;
 #pragma unroll
-    for (uint32_t q = 0; q < 3u; ++q) rank += q < r ? right_most(cur, q) + 1u : 0u;
+    for (uint32_t q = 0; q < 3u; ++q) rank += q < r ? location_count(cur, q) : 0u;
 
     float v = 0.0f;                                                     // V of a state that does not run
     uint32_t second = kNoSecond;
     if constexpr (kDepth == 2) {
-        if (contends && goes_on) v = second_ply(s1, s_shape, p.L, p.M, p.r_line, p.r_win, p.r_lose, p.gamma, p.table, second);
+        // W = the best  r2 + gamma V(s2)  (r2 alone where the second move ends the game) of the next piece on s1
+        if (contends && goes_on)
+            v = best_second(s1, s_shape, p.L, p.M, second, [&](tpl::Board& s2, uint32_t n2) {
+#pragma clang fp contract(off)
+                tpl::next_window(s2, false, 0);                         // the piece after the next: the original window entry 2
+                const bool on = s2.state == tpl::ST_RUNNING;
+                float v2 = 0.0f;
+                if (on) v2 = ntuple_value(s2, p.L, p.M, p.table);
+                const float reward = move_reward(p.r_line, p.r_win, p.r_lose, n2, s2.state);
+                const float later = p.gamma * v2;
+                return on ? reward + later : reward;
+            });
     } else {
         if (contends && goes_on) v = ntuple_value(s1, p.L, p.M, p.table);
     }
@@ -482,18 +412,26 @@ int check_update(const char* name, const void* plane_a, const void* plane_b, int
     return TPL_OK;
 }
 
+// what the two updates share beyond check_update: the arguments and the launch, an age of the ring per grid row
+int launch_update(const void* ring_a, const void* ring_b, int64_t n, int32_t slots, int32_t head, int32_t horizon, int32_t L,
+                  int32_t M, int32_t* table, const float* error, float rate, float decay, bool symmetric, void* stream) {
+    TraceArgs p{};
+    p.a = (const uint4*)ring_a; p.b = (const uint4*)ring_b; p.n = (uint32_t)n; p.slots = (uint32_t)slots; p.head = (uint32_t)head;
+    p.L = (uint32_t)L; p.M = (uint32_t)M; p.table = (uint32_t*)table; p.error = error; p.rate = rate; p.decay = decay;
+    const dim3 grid((p.n + kStateBlock - 1) / kStateBlock, (uint32_t)horizon), block(kStateBlock);
+    if (symmetric) hipLaunchKernelGGL(ntuple_trace_kernel<true>, grid, block, 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(ntuple_trace_kernel<false>, grid, block, 0, (hipStream_t)stream, p);
+    TPL_LEARN_HIP(hipGetLastError());
+    return TPL_OK;
+}
+
 }  // namespace
 
+// the planes are a ring of one slot: age 0 alone, whose weight is decay^0 = 1 whatever the decay
 extern "C" int tpl_ntuple_update(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, int32_t* table,
                                  const float* error, float rate, void* stream) {
     if (const int rc = check_update("tpl_ntuple_update", plane_a, plane_b, n, L, M, table, error, rate)) return rc;
-    UpdateArgs p{};
-    p.a = (const uint4*)plane_a; p.b = (const uint4*)plane_b; p.n = (uint32_t)n;
-    p.L = (uint32_t)L; p.M = (uint32_t)M; p.table = (uint32_t*)table; p.error = error; p.rate = rate;
-    const dim3 grid((p.n + kStateBlock - 1) / kStateBlock), block(kStateBlock);
-    hipLaunchKernelGGL(ntuple_update_kernel, grid, block, 0, (hipStream_t)stream, p);
-    TPL_LEARN_HIP(hipGetLastError());
-    return TPL_OK;
+    return launch_update(plane_a, plane_b, n, 1, 0, 1, L, M, table, error, rate, 0.0f, false, stream);
 }
 
 extern "C" int tpl_ntuple_update_trace(const void* ring_a, const void* ring_b, int64_t n, int32_t slots, int32_t head,
@@ -509,12 +447,5 @@ extern "C" int tpl_ntuple_update_trace(const void* ring_a, const void* ring_b, i
     if ((int64_t)slots * n >= (((int64_t)1 << 31) + kActions - 1) / kActions)
         return fail_msg(TPL_ERR_ARG, "%s: 40 * slots * n must stay below 2^31", name);
     if (!(decay >= 0.0f && decay <= 1.0f)) return fail_msg(TPL_ERR_ARG, "%s: decay must be in [0, 1]", name);
-    TraceArgs p{};
-    p.a = (const uint4*)ring_a; p.b = (const uint4*)ring_b; p.n = (uint32_t)n; p.slots = (uint32_t)slots; p.head = (uint32_t)head;
-    p.L = (uint32_t)L; p.M = (uint32_t)M; p.table = (uint32_t*)table; p.error = error; p.rate = rate; p.decay = decay;
-    const dim3 grid((p.n + kStateBlock - 1) / kStateBlock, (uint32_t)horizon), block(kStateBlock);
-    if (symmetric) hipLaunchKernelGGL(ntuple_trace_kernel<true>, grid, block, 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(ntuple_trace_kernel<false>, grid, block, 0, (hipStream_t)stream, p);
-    TPL_LEARN_HIP(hipGetLastError());
-    return TPL_OK;
+    return launch_update(ring_a, ring_b, n, slots, head, horizon, L, M, table, error, rate, decay, symmetric != 0, stream);
 }

@@ -8,7 +8,8 @@
 //
 // Every function takes `flip` and applies it with selects: a wave whose lanes disagree runs one straight-line path.
 //
-// The packed widths and rotation masks below also serve canonical_action (tpl_placement.h).
+// The packed widths and rotation masks below, and what they say about a piece's distinct placements (right_most ..
+// next_placement), also serve the placement family (tpl_placement.h).
 #pragma once
 
 #include "../tpl_device.h"
@@ -44,10 +45,40 @@ constexpr bool table_repeats_with_the_rotation_count() {
 }
 static_assert(table_repeats_with_the_rotation_count(), "kRotations does not match the shape table");
 
+// The distinct placements of piece `cur`: rotations r = 0 .. last_rotation(cur), locations l = 0 .. right_most(cur, r).  These
+// are the only readers of the two literals.
+__host__ __device__ constexpr uint32_t width_less1(uint32_t cur, uint32_t r) {                 // w - 1 of entry [cur][r]
+    return (uint32_t)(kWidthsLess1 >> (2u * (cur * 4u + r))) & 3u;
+}
+__host__ __device__ constexpr uint32_t right_most(uint32_t cur, uint32_t r) { return 9u - width_less1(cur, r); }        // 10 - w
+__host__ __device__ constexpr uint32_t location_count(uint32_t cur, uint32_t r) { return 10u - width_less1(cur, r); }   // 11 - w
+__host__ __device__ constexpr uint32_t last_rotation(uint32_t cur) { return (kRotationMasks >> (2u * cur)) & 3u; }      // nrot - 1
+
+__host__ __device__ constexpr uint32_t placement_count(uint32_t cur) {
+    uint32_t total = 0u;
+#pragma unroll
+    for (uint32_t r = 0; r < 4u; ++r) total += r <= last_rotation(cur) ? location_count(cur, r) : 0u;
+    return total;
+}
+
+// one step of the walk over them in ascending 10 r + l, from (0, 0) until r > last_rotation(cur); selects, no branch
+__host__ __device__ constexpr void next_placement(uint32_t cur, uint32_t& r, uint32_t& l) {
+    const bool wrap = l >= right_most(cur, r);
+    l = wrap ? 0u : l + 1u;
+    r += wrap ? 1u : 0u;
+}
+
+constexpr bool placement_counts_are(const uint32_t (&want)[8]) {
+    for (uint32_t p = 0; p < 8u; ++p)
+        if (placement_count(p) != want[p]) return false;
+    return true;
+}
+static_assert(placement_counts_are({17, 34, 34, 34, 17, 17, 9, 9}), "the counts include/tpl_learn.h states");
+
 // a' = 10 ((4 - r) & 3) + (10 - w - min(l, 10 - w)) for a = 10 r' + l, r = r' & 3, w the width of entry [cur][r]; below 40
 __device__ __forceinline__ uint32_t mirror_action(uint32_t a, uint32_t cur, bool flip) {
     const uint32_t q = a / 10u, l = a - 10u * q, r = q & 3u;
-    const uint32_t right = 9u - ((uint32_t)(kWidthsLess1 >> (2u * (cur * 4u + r))) & 3u);     // 10 - w
+    const uint32_t right = right_most(cur, r);
     const uint32_t m = 10u * ((4u - r) & 3u) + (right - min(l, right));
     return flip ? m : a;
 }

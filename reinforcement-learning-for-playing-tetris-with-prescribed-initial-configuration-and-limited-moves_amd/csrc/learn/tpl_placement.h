@@ -1,6 +1,6 @@
 // tpl_placement.h -- what the placement family shares (afterstates.hip, heuristic.hip, beam.hip, ntuple.hip; include/tpl_learn.h
 // states the rules): which of the 40 actions are one placement, the first move of a (board, action) pair and its reward, the
-// board features, the score and its ordered key, and the argument checks of the entry points that read a pair of state planes.
+// board features, the score and its ordered key, the second ply's loop, and the argument checks of the entry points that read a pair of state planes.
 #pragma once
 
 #include "tpl_learn_internal.h"
@@ -13,11 +13,26 @@ constexpr int kFeatures = TPL_NUM_FEATURES;
 
 // canonical[a] = 10 (r mod nrot(cur)) + min(l, 10 - w(cur, r)) for a = 10 r + l, r < 4, l < 10; reads tpl_mirror.h's packed
 // widths and rotation masks instead of a dependent load of the shape table
-__host__ __device__ __forceinline__ uint32_t canonical_action(uint32_t cur, uint32_t r, uint32_t l) {
-    const uint32_t right = 9u - ((uint32_t)(kWidthsLess1 >> (2u * (cur * 4u + r))) & 3u);      // 10 - w
-    const uint32_t rc = r & ((kRotationMasks >> (2u * cur)) & 3u);
-    return 10u * rc + (l < right ? l : right);
+__host__ __device__ constexpr uint32_t canonical_action(uint32_t cur, uint32_t r, uint32_t l) {
+    const uint32_t right = right_most(cur, r);
+    return 10u * (r & last_rotation(cur)) + (l < right ? l : right);
 }
+
+// tpl_mirror.h's walk visits exactly the actions that are their own canonical form, in ascending order, placement_count of them
+constexpr bool walk_visits_the_canonical_actions() {
+    for (uint32_t p = 0; p < 8u; ++p) {
+        uint32_t r = 0u, l = 0u, steps = 0u;
+        for (uint32_t a = 0; a < (uint32_t)kActions; ++a) {
+            if (canonical_action(p, a / 10u, a % 10u) != a) continue;
+            if (r > last_rotation(p) || 10u * r + l != a) return false;
+            next_placement(p, r, l);
+            ++steps;
+        }
+        if (r <= last_rotation(p) || steps != placement_count(p)) return false;
+    }
+    return true;
+}
+static_assert(walk_visits_the_canonical_actions(), "next_placement and placement_count do not match canonical_action");
 
 // The first move of pair (state (A, B), action 10 r + l): `s` becomes the board the move leaves, its window not yet popped;
 // `cur` is the piece that was placed and `running` whether the state was still in play (a finished board's move means
@@ -128,6 +143,34 @@ __device__ __forceinline__ uint32_t ordered_bits(float x) {
     uint32_t u = __float_as_uint(x);
     u = u == 0x80000000u ? 0u : u;
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+constexpr uint32_t kNoSecond = 255u;
+
+// The second ply with the known next piece: the best  worth(s2, n2)  among the distinct placements of s1's current piece on s1,
+// the popped and still running board a first move left, and in `second` the placement it belongs to.  Copies s1, moves (s2 is
+// what the move leaves, its window not yet popped, n2 the rows it cleared; `worth` may change s2) and scores once per distinct
+// placement in ascending b = 10 r2 + l2 -- 9, 17 or 34 trips, the same for the 40 lanes of a board -- and keeps a running
+// best under a strict > on the ordered key, so the lowest b survives.  r2 and l2 are values out of the packed widths, never
+// register indices.  The one loop of tpl_placement_search and tpl_ntuple_search: they enumerate and tie-break alike by it.
+template <typename Worth>
+__device__ __forceinline__ float best_second(const tpl::Board& s1, const tpl::ShapeWord* shape, uint32_t L, uint32_t M,
+                                             uint32_t& second, Worth worth) {
+    const uint32_t nxt = s1.window & 7u;
+    const uint32_t last_rot = last_rotation(nxt);
+    uint32_t best_key = 0u, r2 = 0u, l2 = 0u;
+    float best = 0.0f;
+#pragma unroll 1
+    while (r2 <= last_rot) {
+        tpl::Board s2 = s1;
+        bool topout;
+        const uint32_t n2 = tpl::move_board(s2, shape, r2, l2, L, M, topout);
+        const float q = worth(s2, n2);
+        const uint32_t key = ordered_bits(q);                           // never 0, so the first trip is taken
+        if (key > best_key) { best_key = key; best = q; second = 10u * r2 + l2; }
+        next_placement(nxt, r2, l2);
+    }
+    return best;
 }
 
 // the checks of every entry point that reads n states from a pair of planes; `name` leads the message.  L and M are the

@@ -27,7 +27,7 @@ import torch
 
 from . import _learn_lib
 from ._learn_lib import BEAM_MAX_DEPTH, BEAM_MAX_WIDTH, FEATURE_NAMES, NUM_ACTIONS, NUM_FEATURES, check
-from .lookahead import _MAX_BOARDS, _ptr, _source_planes, _state_ptrs
+from .lookahead import _boards, _ptr, _source_planes, _state_ptrs
 
 __all__ = ["FEATURE_NAMES", "placement_features", "HeuristicPolicy", "BeamPolicy", "evaluate_heuristic", "tune_heuristic"]
 
@@ -92,7 +92,38 @@ def _members(n: int, rows: int, boards_per_member) -> int:
     return per
 
 
-class HeuristicPolicy:
+class _WeightedPolicy:
+    """What HeuristicPolicy and BeamPolicy share: the weight rows on the device and the outputs every act() takes."""
+
+    def _setup(self, env, weights, boards_per_member) -> None:
+        w = _weights(weights)
+        n = _boards(env, type(self).__name__)
+        self.boards_per_member = _members(n, w.shape[0], boards_per_member)
+        self.env, self.members = env, int(w.shape[0])
+        self.weights = torch.from_numpy(w).to(env.device)
+        self._planes = None
+
+    def set_weights(self, weights) -> None:
+        """Replace the weights (same shape) in the device buffer act() reads."""
+        w = _weights(weights)
+        if w.shape != tuple(self.weights.shape):
+            raise ValueError(f"weights must keep their shape {tuple(self.weights.shape)}")
+        self.weights.copy_(torch.from_numpy(w), non_blocking=False)
+
+    def _outputs(self, out, score) -> torch.Tensor:
+        """`out` (made where it is None) and `score` checked, and the resident planes at hand."""
+        env = self.env
+        if out is None:
+            out = torch.empty(env.num_envs, dtype=torch.uint8, device=env.device)
+        env._own(out, torch.uint8, "out")
+        if score is not None:
+            env._own(score, torch.float32, "score")
+        if self._planes is None:
+            self._planes = _state_ptrs(env)                   # the resident planes live as long as the environment
+        return out
+
+
+class HeuristicPolicy(_WeightedPolicy):
     """The linear placement policy on the resident boards of `env`: act() gives every board the arg-max over the distinct
     placements of w . phi(s, a) (left to right in float32; the lowest action on ties; action 0 for a finished board), in one
     launch that leaves the environment as it is.
@@ -108,21 +139,7 @@ class HeuristicPolicy:
 
     def __init__(self, env, weights, boards_per_member: Optional[int] = None, depth: int = 1):
         self.depth = _depth(depth)
-        w = _weights(weights)
-        n = int(env.num_envs)
-        if not 1 <= n <= _MAX_BOARDS:
-            raise ValueError(f"HeuristicPolicy takes an environment of 1 .. {_MAX_BOARDS} boards (40 N must stay below 2^31)")
-        self.boards_per_member = _members(n, w.shape[0], boards_per_member)
-        self.env, self.members = env, int(w.shape[0])
-        self.weights = torch.from_numpy(w).to(env.device)
-        self._planes = None
-
-    def set_weights(self, weights) -> None:
-        """Replace the weights (same shape) in the device buffer act() reads."""
-        w = _weights(weights)
-        if w.shape != tuple(self.weights.shape):
-            raise ValueError(f"weights must keep their shape {tuple(self.weights.shape)}")
-        self.weights.copy_(torch.from_numpy(w), non_blocking=False)
+        self._setup(env, weights, boards_per_member)
 
     @torch.no_grad()
     def act(self, out: Optional[torch.Tensor] = None, score: Optional[torch.Tensor] = None,
@@ -134,13 +151,7 @@ class HeuristicPolicy:
         env = self.env
         if second is not None and self.depth == 1:
             raise ValueError("second is the second ply's placement: this policy has depth 1")
-        if out is None:
-            out = torch.empty(env.num_envs, dtype=torch.uint8, device=env.device)
-        env._own(out, torch.uint8, "out")
-        if score is not None:
-            env._own(score, torch.float32, "score")
-        if self._planes is None:
-            self._planes = _state_ptrs(env)                   # the resident planes live as long as the environment
+        out = self._outputs(out, score)
         if second is not None:
             env._own(second, torch.uint8, "second")
         stream = torch._C._cuda_getCurrentRawStream(env.device.index)
@@ -151,7 +162,7 @@ class HeuristicPolicy:
         return out
 
 
-class BeamPolicy:
+class BeamPolicy(_WeightedPolicy):
     """A beam search with the linear placement score on the resident boards of `env` (tpl_placement_beam; the rule is in
     include/tpl_learn.h).  At moves = m a state's window holds 12 - m mod 10 true next pieces; act() searches
     min(depth, that many) plies: every ply expands each node of the beam by the distinct placements of its current piece,
@@ -163,16 +174,7 @@ class BeamPolicy:
 
     def __init__(self, env, weights, depth: int, width: int, boards_per_member: Optional[int] = None):
         self.depth, self.width = _beam_shape(depth, width)
-        w = _weights(weights)
-        n = int(env.num_envs)
-        if not 1 <= n <= _MAX_BOARDS:
-            raise ValueError(f"BeamPolicy takes an environment of 1 .. {_MAX_BOARDS} boards (40 N must stay below 2^31)")
-        self.boards_per_member = _members(n, w.shape[0], boards_per_member)
-        self.env, self.members = env, int(w.shape[0])
-        self.weights = torch.from_numpy(w).to(env.device)
-        self._planes = None
-
-    set_weights = HeuristicPolicy.set_weights
+        self._setup(env, weights, boards_per_member)
 
     @torch.no_grad()
     def act(self, out: Optional[torch.Tensor] = None, score: Optional[torch.Tensor] = None,
@@ -182,15 +184,9 @@ class BeamPolicy:
         board, a game that ends on the way, a window with fewer known pieces).  No host sync, and no allocation when `out` is
         given: capturable into a HIP graph."""
         env = self.env
-        if out is None:
-            out = torch.empty(env.num_envs, dtype=torch.uint8, device=env.device)
-        env._own(out, torch.uint8, "out")
-        if score is not None:
-            env._own(score, torch.float32, "score")
+        out = self._outputs(out, score)
         if plan is not None:
             env._own(plan, torch.uint8, "plan", (env.num_envs, self.depth))
-        if self._planes is None:
-            self._planes = _state_ptrs(env)                   # the resident planes live as long as the environment
         stream = torch._C._cuda_getCurrentRawStream(env.device.index)
         check(_learn_lib.lib().tpl_placement_beam(self._planes[0], self._planes[1], env.num_envs, env.L, env.M,
                                                   self.weights.data_ptr(), self.boards_per_member, self.depth, self.width,

@@ -23,6 +23,13 @@ from ._learn_lib import NUM_ACTIONS, check
 _MAX_BOARDS = ((1 << 31) - 1) // NUM_ACTIONS
 
 
+def _boards(env, who: str) -> int:
+    n = int(env.num_envs)
+    if not 1 <= n <= _MAX_BOARDS:
+        raise ValueError(f"{who} takes an environment of 1 .. {_MAX_BOARDS} boards (40 N must stay below 2^31)")
+    return n
+
+
 def _state_ptrs(env):
     from ._lib import check as env_check
     pa, pb = C.c_void_p(), C.c_void_p()

@@ -31,7 +31,7 @@ import torch
 
 from . import _learn_lib
 from ._learn_lib import NTUPLE_ENTRIES, NTUPLE_TRACE_MAX, check
-from .lookahead import _MAX_BOARDS, _ptr, _state_ptrs
+from .lookahead import _MAX_BOARDS, _boards, _ptr, _state_ptrs
 
 __all__ = ["NTUPLE_ENTRIES", "ntuple_table", "ntuple_value", "ntuple_is_symmetric", "NTuplePolicy", "NTupleLearner"]
 
@@ -79,13 +79,6 @@ def _horizon(horizon) -> int:
     if isinstance(horizon, bool) or not isinstance(horizon, int) or not 1 <= horizon <= NTUPLE_TRACE_MAX:
         raise ValueError(f"horizon must be an integer in 1 .. {NTUPLE_TRACE_MAX}, got {horizon!r}")
     return int(horizon)
-
-
-def _boards(env, who: str) -> int:
-    n = int(env.num_envs)
-    if not 1 <= n <= _MAX_BOARDS:
-        raise ValueError(f"{who} takes an environment of 1 .. {_MAX_BOARDS} boards (40 N must stay below 2^31)")
-    return n
 
 
 def _planes(pair, device, what: str):

@@ -126,7 +126,8 @@ def test_the_three_kernels_use_no_scratch_and_at_most_128_vgprs():
                          timeout=300, cwd=ROOT)
     assert res.returncode == 0, res.stderr
     rows = [l.split() for l in res.stdout.splitlines() if " scratch " in l]
-    for kernel in ("ntuple_value_kernel", "ntuple_act_kernel", "ntuple_update_kernel"):
+    # tpl_ntuple_update launches ntuple_trace_kernel<false>: the one update kernel, at age 0 of a ring of one slot
+    for kernel in ("ntuple_value_kernel", "ntuple_act_kernel", "ntuple_trace_kernelILb0"):
         mine = [r for r in rows if kernel in r[-1]]
         assert len(mine) == 1, (kernel, [r[-1] for r in rows])
         assert mine[0][mine[0].index("scratch") - 1] == "0", mine

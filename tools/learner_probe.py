@@ -849,7 +849,7 @@ def part_ntuple(rounds=5):
     L, check = m.lib(), m.check
     stream = torch._C._cuda_getCurrentRawStream(0)
     lib_path = m.build_library()
-    valu = {k: _static_valu(k, lib_path) for k in ("ntuple_act_kernel", "ntuple_value_kernel", "ntuple_update_kernel")}
+    valu = {k: _static_valu(k, lib_path) for k in ("ntuple_act_kernel", "ntuple_value_kernel", "ntuple_trace_kernelILb0")}
     out = dict(part="ntuple", static_valu=valu, scattered_atomics_tb_per_s=SCATTERED_ATOMICS / 1e12)
     classical = np.array([4, 100, -100, -8, -1, 0, -2, -3, -6, -3, -2, -1], np.float32) * np.float32(0.1)
     weights = torch.from_numpy(classical).to("cuda:0")
@@ -1120,7 +1120,7 @@ def part_ntuple_trace(rounds=5, reps=10):
     stream = torch._C._cuda_getCurrentRawStream(0)
     slots, head, rate, decay = 17, 16, 100.0, 0.9
     out = dict(part="ntuple_trace", slots=slots, head=head, rate=rate, decay=decay,
-               static_valu={k: _static_valu(k, m.build_library()) for k in ("ntuple_update_kernel", "ntuple_trace_kernelILb0", "ntuple_trace_kernelILb1")})
+               static_valu={k: _static_valu(k, m.build_library()) for k in ("ntuple_trace_kernelILb0", "ntuple_trace_kernelILb1")})
     host = np.random.default_rng(0).integers(-(1 << 20), (1 << 20) + 1, m.NTUPLE_ENTRIES).astype(np.int32)
     rows = []
     for n in (1 << 16, 1 << 18, 1 << 20):
