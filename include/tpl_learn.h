@@ -449,6 +449,42 @@ int tpl_ntuple_update_trace(const void* ring_a, const void* ring_b, int64_t n, i
                             int32_t L, int32_t M, int32_t* table, const float* error, float rate, float decay,
                             int32_t symmetric, void* stream);
 
+/* The update above with temporal-coherence step sizes (Beal & Smith): every table entry keeps the signed and the absolute sum of the
+ * steps it has been sent, and learns at their ratio -- at the full rate while its errors keep their sign, slower where they
+ * alternate, which is what an overshoot looks like.
+ *
+ * Coherence buffer: int64 [TPL_NTUPLE_ENTRIES][2] (5,029,888 bytes), 16-byte aligned: entry j holds the pair (E_j, A_j), the signed
+ * and the absolute sum of the steps sent to table entry j.  A zeroed buffer is the start.
+ * Step size of an entry:
+ *   alpha_j = 1.0f                                             if A_j <= 0,
+ *   alpha_j = fminf(__fdiv_rn((float) |E_j|, (float) A_j), 1.0f)  otherwise
+ * -- |E_j| the magnitude as an UNSIGNED 64-bit value (so INT64_MIN is defined), both conversions to nearest even, the quotient
+ * rounded once.
+ * The update.  For board i, age k < horizon, with error e: the ring, the ages, w_k, the stop at the first state that does not run and
+ *   d_k = (int32) rint((rate * w_k) * e)
+ * are exactly tpl_ntuple_update_trace's.  Where the trace is open and d_k != 0, for every entry j that tpl_ntuple_update_trace would
+ * add to -- the counter and every tuple with a non-zero pattern; with symmetric != 0 the sigma-images of the tuples as well, the
+ * counter ONCE, both tuple adds also where the two indices coincide --:
+ *   table[j] += s, wrapping, with  s = (int32) rint(((rate * w_k) * alpha_j) * e)   -- three products, each rounded once in float32
+ *                                                                                     and never fused, clamped to +-2^24, 0 for a NaN;
+ *   E_j += d_k  and  A_j += |d_k|, wrapping in 64 bits.
+ * Read before add: every alpha_j of a call is read from the coherence buffer AS IT STOOD BEFORE THE CALL.  A call has two phases, the
+ * step phase, which reads the coherence buffer and adds to the table, and the accumulate phase, which only adds to the coherence
+ * buffer.  Neither reads what it adds to, so the bytes of both buffers do not depend on the order of the adds, and two runs give the
+ * same bytes.
+ * Consequences.  With a zeroed coherence buffer every alpha is 1 and (r * 1.0f) * e is r * e: the table bytes are
+ * tpl_ntuple_update_trace's.  |s| <= |d_k|, and s is 0 where d_k is.  A coherence buffer is MIRROR-SYMMETRIC when its pairs at j and
+ * sigma(j) are equal; a symmetric call adds the same amounts at j and sigma(j) in both buffers, so a mirror-symmetric pair (table,
+ * coherence) stays mirror-symmetric.  An entry that is its own image takes 2 s, 2 d_k and 2 |d_k|.
+ *
+ * Two kernels on `stream`, one after the other (ntuple_coherent_step_kernel<symmetric>, ntuple_coherent_accumulate_kernel<symmetric>),
+ * each a lane per (board, age); no sync and nothing allocated, so a call can be captured into a graph.  Refused before any HIP call,
+ * under its own name: everything tpl_ntuple_update_trace refuses, in the same order, and, after the table checks, coherence NULL or
+ * not 16-byte aligned. */
+int tpl_ntuple_update_coherent(const void* ring_a, const void* ring_b, int64_t n, int32_t slots, int32_t head, int32_t horizon,
+                               int32_t L, int32_t M, int32_t* table, int64_t* coherence, const float* error, float rate,
+                               float decay, int32_t symmetric, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,7 +30,7 @@ LEARN_SYMBOLS = [
     "tpl_priority_update", "tpl_replay_sample_prioritized", "tpl_priority_target", "tpl_replay_sample_nstep",
     "tpl_replay_sample_mirror", "tpl_mirror_states", "tpl_afterstates", "tpl_canonical_action", "tpl_placement_features",
     "tpl_placement_act", "tpl_placement_search", "tpl_placement_beam", "tpl_ntuple_value", "tpl_ntuple_act", "tpl_ntuple_update",
-    "tpl_ntuple_search", "tpl_ntuple_update_trace",
+    "tpl_ntuple_search", "tpl_ntuple_update_trace", "tpl_ntuple_update_coherent",
 ]
 NSTEP_MAX = 16
 BEAM_MAX_DEPTH, BEAM_MAX_WIDTH = 12, 64
@@ -142,11 +142,12 @@ def lib() -> C.CDLL:
     L.tpl_ntuple_update.argtypes = [vp, vp, i64, i32, i32, vp, vp, f32, vp]
     L.tpl_ntuple_search.argtypes = [vp, vp, i64, i32, i32, f32, f32, f32, f32, vp, f32, u64, u64, vp, vp, vp, vp, vp, vp, vp]
     L.tpl_ntuple_update_trace.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, vp, vp, f32, f32, i32, vp]
+    L.tpl_ntuple_update_coherent.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, f32, f32, i32, vp]
     for name in ("tpl_replay_push", "tpl_replay_sample", "tpl_learn_pack", "tpl_priority_init", "tpl_priority_push",
                  "tpl_priority_update", "tpl_replay_sample_prioritized", "tpl_replay_sample_nstep", "tpl_replay_sample_mirror",
                  "tpl_mirror_states", "tpl_afterstates", "tpl_placement_features", "tpl_placement_act",
                  "tpl_placement_search", "tpl_placement_beam", "tpl_ntuple_value", "tpl_ntuple_act", "tpl_ntuple_update",
-                 "tpl_ntuple_search", "tpl_ntuple_update_trace"):
+                 "tpl_ntuple_search", "tpl_ntuple_update_trace", "tpl_ntuple_update_coherent"):
         getattr(L, name).restype = i32
     _handle = L
     return L
@@ -633,6 +634,63 @@ def ntuple_update_trace(table, ages, L: int, M: int, error, rate, decay, symmetr
             used[:, NTUPLE_TUPLES] = False               # the counter was added above, once
             np.add.at(tab, index[used], np.broadcast_to(d[:, None], used.shape)[used].astype(np.uint32))
     return table
+
+
+def _ntuple_coherence(coherence) -> np.ndarray:
+    if not isinstance(coherence, np.ndarray) or coherence.dtype != np.int64 or coherence.shape != (NTUPLE_ENTRIES, 2):
+        raise ValueError(f"coherence must be an int64 array of shape ({NTUPLE_ENTRIES}, 2)")
+    return coherence
+
+
+def ntuple_step_sizes(coherence) -> np.ndarray:
+    """alpha of every entry (float32 [NTUPLE_ENTRIES]) from its pair (E, A): 1 where A <= 0, else min(float32(|E|) / float32(A), 1)
+    -- |E| as an unsigned 64-bit value, both conversions to nearest even, the float32 quotient rounded once."""
+    c = _ntuple_coherence(coherence)
+    e, a = c[:, 0], c[:, 1]
+    mag = np.where(e < 0, np.uint64(0) - e.view(np.uint64), e.view(np.uint64)).astype(np.float32)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.minimum(mag / a.astype(np.float32), np.float32(1.0))
+    return np.where(a <= 0, np.float32(1.0), ratio).astype(np.float32)
+
+
+def ntuple_coherent_steps(error, rate, alpha) -> np.ndarray:
+    """s = (int32) rint((rate * alpha) * e) (int64, the shape of alpha against e): ntuple_steps with rate * alpha, a float32 product
+    rounded once, as its rate."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        x = (np.float32(rate) * np.asarray(alpha, dtype=np.float32)) * np.asarray(error, dtype=np.float32)
+    x = np.where(np.isnan(x), np.float32(0.0), np.clip(x, -float(NTUPLE_STEP_MAX), float(NTUPLE_STEP_MAX)))
+    return np.rint(x).astype(np.int64)
+
+
+def ntuple_update_coherent(table, coherence, ages, L: int, M: int, error, rate, decay, symmetric):
+    """tpl_ntuple_update_coherent, in place on both buffers: (table, coherence).  `ages` as ntuple_update_trace takes them.  Every
+    alpha is read from `coherence` as it stands at the call; entry j of a board at age k whose trace is open and whose d_k is not 0
+    takes s = ntuple_coherent_steps(e, float32(rate) * w_k, alpha_j) on the table, d_k on E_j and |d_k| on A_j, all wrapping."""
+    tab = _ntuple_table(table).view(np.uint32)
+    sums = _ntuple_coherence(coherence).view(np.uint64)
+    alpha = ntuple_step_sizes(coherence)                 # before any add of this call
+    e = np.asarray(error, dtype=np.float32).reshape(-1)
+    open_ = np.ones(e.shape, dtype=bool)
+    w, decay = np.float32(1.0), np.float32(decay)
+    for age, (rows, piece, lines, moves, state) in enumerate(ages):
+        if age:
+            w = np.float32(w * decay)
+        open_ = open_ & (np.broadcast_to(np.asarray(state), e.shape) == 0)
+        r = np.float32(rate) * w
+        d = np.where(open_, ntuple_steps(e, r), 0)
+        piece = np.broadcast_to(np.asarray(piece, dtype=np.int64), e.shape)
+        forms = [(rows, piece, True)] + ([(_reflected_rows(rows), np.array(PIECE_MIRROR)[piece], False)] if symmetric else [])
+        for form_rows, form_piece, counter in forms:
+            index, used = ntuple_indices(form_rows, form_piece, L, M, lines, moves)
+            used = used & (d != 0)[:, None]
+            used[:, NTUPLE_TUPLES] &= counter            # the counter is taken once, with the state's own entries
+            j = index[used]
+            d_j = np.broadcast_to(d[:, None], used.shape)[used]
+            s_j = ntuple_coherent_steps(np.broadcast_to(e[:, None], used.shape)[used], r, alpha[j])
+            np.add.at(tab, j, s_j.astype(np.uint32))
+            np.add.at(sums[:, 0], j, d_j.astype(np.uint64))
+            np.add.at(sums[:, 1], j, np.abs(d_j).astype(np.uint64))
+    return table, coherence
 
 
 def ntuple_explore(seed: int, step: int, n: int, epsilon: float, placements):

@@ -1,6 +1,6 @@
 // ntuple.hip -- an n-tuple afterstate value function, its greedy / epsilon-greedy placement policy and its temporal-difference
-// update: tpl_ntuple_value, tpl_ntuple_act, tpl_ntuple_search, tpl_ntuple_update, tpl_ntuple_update_trace (include/tpl_learn.h
-// states the rule).
+// update: tpl_ntuple_value, tpl_ntuple_act, tpl_ntuple_search, tpl_ntuple_update, tpl_ntuple_update_trace,
+// tpl_ntuple_update_coherent (include/tpl_learn.h states the rule).
 //
 // The value of a board is a sum of table look-ups: 153 windows of two adjacent columns by four rows, each a 256-entry row of an
 // int32 table chosen by the piece that falls next, plus one entry for the lines and moves that are left.  In the column layout a
@@ -36,6 +36,14 @@
 // one of them does not run: what lies behind belongs to an earlier episode.  With kSymmetric every add is made a second time,
 // at the entry of the reflected board (the piece through pi, tuple column 8 - x, the pattern's nibbles swapped), which keeps a
 // mirror-symmetric table mirror-symmetric.  Ages of one board add in any order: the adds are integers and nothing is read.
+//
+// update_coherent is update_trace with a step size per entry, alpha = |E| / A from the signed and the absolute sum of the steps
+// the entry was sent (a second buffer, 16 bytes an entry).  Two kernels in update_trace's frame, one after the other: the step
+// kernel gathers an entry's pair in one 16-byte load, nine (symmetric: eighteen) in flight per lane as in value, and adds
+// rint(rate * w * alpha * e) to the table; the accumulate kernel adds d and |d| to the pair with two 64-bit atomics.  Each reads
+// only what the other writes, so the bytes of both buffers are again the same in any order.  The two share walk_entries, the walk
+// over a state's entries with the per-entry action handed in; ntuple_trace_kernel keeps its own loop, since on the shared walk
+// its instructions came out in another order (profiles/learner/README.md).
 #include <cmath>
 
 #include "tpl_placement.h"
@@ -201,6 +209,151 @@ __global__ __launch_bounds__(kStateBlock) void ntuple_trace_kernel(const TraceAr
     for (int t = threadIdx.x; t < kCounters; t += kStateBlock) {
         const uint32_t sum = s_counter[t];
         if (sum) atomicAdd(p.table + kCounterBase + t, sum);
+    }
+}
+
+// ---- the coherent update: tpl_ntuple_update_coherent ----
+// Two kernels in ntuple_trace_kernel's frame (a lane per (board, age), the age in blockIdx.y): the step kernel reads the coherence
+// buffer and adds to the table, the accumulate kernel adds to the coherence buffer.  Neither reads what it adds to, so the bytes of
+// both buffers are the same whatever order the adds arrive in.
+
+struct CoherentArgs {
+    TraceArgs t;
+    longlong2* coherence;        // [TPL_NTUPLE_ENTRIES]: x = E, the signed sum; y = A, the absolute sum
+};
+
+// What a lane of either kernel does before its walk, ntuple_trace_kernel's lines: the decayed rate of the block's age, the younger
+// states' state words, the step and the state of that age.  True where the lane adds: `rate` is rate * w_age, `d` is not 0 and
+// `s` runs.
+__device__ __forceinline__ bool coherent_lane(const TraceArgs& p, float& rate, float& e, int32_t& d, tpl::Board& s) {
+    const uint32_t age = blockIdx.y;
+    float w = 1.0f;
+    for (uint32_t k = 0; k < age; ++k) w = __fmul_rn(w, p.decay);
+    rate = __fmul_rn(p.rate, w);
+    const uint32_t i = blockIdx.x * kStateBlock + threadIdx.x;
+    if (i >= p.n) return false;
+    bool open = true;
+    for (uint32_t k = 0; k < age; ++k) {
+        const uint32_t slot = p.head >= k ? p.head - k : p.head + p.slots - k;
+        open = open && ((p.b[slot * p.n + i].y >> 28) & 3u) == tpl::ST_RUNNING;
+    }
+    e = p.error[i];
+    d = update_step(rate, e);
+    if (!open || d == 0) return false;
+    const uint32_t slot = p.head >= age ? p.head - age : p.head + p.slots - age;
+    tpl::unpack_board(p.a[slot * p.n + i], p.b[slot * p.n + i], s);
+    return s.state == tpl::ST_RUNNING;
+}
+
+// The walk over the tuple entries of a running state: apply(j, gather(j)) for every tuple with a non-zero pattern and, with
+// kSymmetric, for its sigma-image as well -- both, also where the two are one entry.  gather(j) is made for all nine tuples of a
+// row before the first apply and also where the pattern is empty (the index is in bounds), so that what it loads is in flight
+// nine (eighteen) at a time and stays straight-line code; an action that loads nothing returns an empty struct.
+template <bool kSymmetric, typename Gather, typename Apply>
+__device__ __forceinline__ void walk_entries(const tpl::Board& s, Gather&& gather, Apply&& apply) {
+    const uint32_t piece = s.window & 7u;
+    const uint32_t base = piece * (uint32_t)kPieceStride;
+    const uint32_t mirror_base = ((kPieceMirror >> (4u * piece)) & 7u) * (uint32_t)kPieceStride;
+    using G = decltype(gather(0u));
+#pragma unroll 1
+    for (uint32_t y = 0; y < (uint32_t)kTupleRows; ++y) {
+        uint32_t j[kTupleCols], jm[kTupleCols];
+        G g[kTupleCols], gm[kTupleCols];
+#pragma unroll
+        for (int x = 0; x < kTupleCols; ++x) {
+            const uint32_t q = pattern(s.c[x], s.c[x + 1], y);
+            j[x] = tuple_entry(base, x, y, q);
+            g[x] = gather(j[x]);
+            if constexpr (kSymmetric) {
+                jm[x] = tuple_entry(mirror_base, kTupleCols - 1 - x, y, (q >> 4) | ((q & 15u) << 4));
+                gm[x] = gather(jm[x]);
+            }
+        }
+#pragma unroll
+        for (int x = 0; x < kTupleCols; ++x) {
+            if (j[x] & 255u) {                                          // the pattern, in the index's low eight bits
+                apply(j[x], g[x]);
+                if constexpr (kSymmetric) apply(jm[x], gm[x]);
+            }
+        }
+    }
+}
+
+// alpha of an entry with the pair c = (E, A): 1 where A <= 0, else min(|E| / A, 1) -- the magnitude as an unsigned value, both
+// conversions to nearest even, the quotient rounded once
+__device__ __forceinline__ float step_size(const longlong2 c) {
+    if (c.y <= 0) return 1.0f;
+    const unsigned long long mag = c.x < 0 ? 0ull - (unsigned long long)c.x : (unsigned long long)c.x;
+    return fminf(__fdiv_rn((float)mag, (float)c.y), 1.0f);
+}
+
+// s = (int32) rint(((rate * w_k) * alpha_j) * e), `rate` being rate * w_k
+__device__ __forceinline__ uint32_t coherent_step(float rate, const longlong2 c, float e) {
+    return (uint32_t)update_step(__fmul_rn(rate, step_size(c)), e);
+}
+
+// The step phase.  The counter entries are summed per block in LDS first, as in ntuple_trace_kernel; 32 bits are enough here,
+// since the table's own adds wrap in 32 bits.
+template <bool kSymmetric>
+__global__ __launch_bounds__(kStateBlock) void ntuple_coherent_step_kernel(const CoherentArgs p) {
+    __shared__ uint32_t s_counter[kCounters];
+#pragma unroll
+    for (int t = threadIdx.x; t < kCounters; t += kStateBlock) s_counter[t] = 0u;
+    __syncthreads();
+    tpl::Board s;
+    float rate, e;
+    int32_t d;
+    if (coherent_lane(p.t, rate, e, d, s)) {
+        const uint32_t k = counter_index(p.t.L, p.t.M, s.lines, s.moves);
+        atomicAdd(&s_counter[k], coherent_step(rate, *entry(p.coherence, (uint32_t)kCounterBase + k), e));
+        walk_entries<kSymmetric>(
+            s, [&](uint32_t j) { return *entry(p.coherence, j); },
+            [&](uint32_t j, const longlong2 c) {
+                const uint32_t step = coherent_step(rate, c, e);
+                if (step) atomicAdd(entry(p.t.table, j), step);
+            });
+    }
+    __syncthreads();
+#pragma unroll
+    for (int t = threadIdx.x; t < kCounters; t += kStateBlock) {
+        const uint32_t sum = s_counter[t];
+        if (sum) atomicAdd(p.t.table + kCounterBase + t, sum);
+    }
+}
+
+struct Nothing {};
+
+// The accumulate phase: E += d and A += |d|, wrapping in 64 bits.  The counters' sums are 64 bits wide in LDS as well: 256 lanes
+// of 2^24 each do not fit 32, and E and A do not wrap there.
+template <bool kSymmetric>
+__global__ __launch_bounds__(kStateBlock) void ntuple_coherent_accumulate_kernel(const CoherentArgs p) {
+    __shared__ unsigned long long s_signed[kCounters], s_absolute[kCounters];
+#pragma unroll
+    for (int t = threadIdx.x; t < kCounters; t += kStateBlock) s_signed[t] = s_absolute[t] = 0ull;
+    __syncthreads();
+    unsigned long long* const sums = (unsigned long long*)p.coherence;  // entry j: E at word 2 j, A at word 2 j + 1
+    tpl::Board s;
+    float rate, e;
+    int32_t d;
+    if (coherent_lane(p.t, rate, e, d, s)) {
+        const unsigned long long signed_d = (unsigned long long)(long long)d;
+        const unsigned long long absolute_d = (unsigned long long)(d < 0 ? -(long long)d : (long long)d);
+        const uint32_t k = counter_index(p.t.L, p.t.M, s.lines, s.moves);
+        atomicAdd(&s_signed[k], signed_d);
+        atomicAdd(&s_absolute[k], absolute_d);
+        walk_entries<kSymmetric>(
+            s, [](uint32_t) { return Nothing{}; },
+            [&](uint32_t j, Nothing) {
+                atomicAdd(entry(sums, 2u * j), signed_d);
+                atomicAdd(entry(sums, 2u * j + 1u), absolute_d);
+            });
+    }
+    __syncthreads();
+#pragma unroll
+    for (int t = threadIdx.x; t < kCounters; t += kStateBlock) {
+        const unsigned long long sum = s_signed[t], absolute = s_absolute[t];
+        if (sum) atomicAdd(sums + 2 * (kCounterBase + t), sum);
+        if (absolute) atomicAdd(sums + 2 * (kCounterBase + t) + 1, absolute);
     }
 }
 
@@ -401,27 +554,54 @@ extern "C" int tpl_ntuple_search(const void* plane_a, const void* plane_b, int64
 
 namespace {
 
-// what tpl_ntuple_update and tpl_ntuple_update_trace refuse alike
+// what the three updates refuse alike; `coherence`: where the entry takes a coherence buffer, the address of its pointer
 int check_update(const char* name, const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const int32_t* table,
-                 const float* error, float rate) {
+                 const float* error, float rate, const int64_t* const* coherence = nullptr) {
     if (const int rc = check_planes(name, plane_a, plane_b, n, L, M)) return rc;
     if (const int rc = check_table(name, table)) return rc;
+    if (coherence && !*coherence) return fail_msg(TPL_ERR_ARG, "%s: null pointer (coherence is required)", name);
+    if (coherence && ((uintptr_t)*coherence & 15u)) return fail_msg(TPL_ERR_ARG, "%s: coherence must be 16-byte aligned", name);
     if (!error) return fail_msg(TPL_ERR_ARG, "%s: null pointer (error is required)", name);
     if ((uintptr_t)error & 3u) return fail_msg(TPL_ERR_ARG, "%s: error must be 4-byte aligned", name);
     if (!std::isfinite(rate)) return fail_msg(TPL_ERR_ARG, "%s: rate must be finite", name);
     return TPL_OK;
 }
 
-// what the two updates share beyond check_update: the arguments and the launch, an age of the ring per grid row
+// what the three updates share beyond check_update: the arguments and the launch, an age of the ring per grid row
+// `coherence` null: ntuple_trace_kernel; otherwise the two phases of the coherent update, one after the other on the stream
 int launch_update(const void* ring_a, const void* ring_b, int64_t n, int32_t slots, int32_t head, int32_t horizon, int32_t L,
-                  int32_t M, int32_t* table, const float* error, float rate, float decay, bool symmetric, void* stream) {
+                  int32_t M, int32_t* table, const float* error, float rate, float decay, bool symmetric, void* stream,
+                  int64_t* coherence = nullptr) {
     TraceArgs p{};
     p.a = (const uint4*)ring_a; p.b = (const uint4*)ring_b; p.n = (uint32_t)n; p.slots = (uint32_t)slots; p.head = (uint32_t)head;
     p.L = (uint32_t)L; p.M = (uint32_t)M; p.table = (uint32_t*)table; p.error = error; p.rate = rate; p.decay = decay;
     const dim3 grid((p.n + kStateBlock - 1) / kStateBlock, (uint32_t)horizon), block(kStateBlock);
-    if (symmetric) hipLaunchKernelGGL(ntuple_trace_kernel<true>, grid, block, 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(ntuple_trace_kernel<false>, grid, block, 0, (hipStream_t)stream, p);
+    if (coherence) {
+        const CoherentArgs c{p, (longlong2*)coherence};
+        if (symmetric) hipLaunchKernelGGL(ntuple_coherent_step_kernel<true>, grid, block, 0, (hipStream_t)stream, c);
+        else hipLaunchKernelGGL(ntuple_coherent_step_kernel<false>, grid, block, 0, (hipStream_t)stream, c);
+        TPL_LEARN_HIP(hipGetLastError());
+        if (symmetric) hipLaunchKernelGGL(ntuple_coherent_accumulate_kernel<true>, grid, block, 0, (hipStream_t)stream, c);
+        else hipLaunchKernelGGL(ntuple_coherent_accumulate_kernel<false>, grid, block, 0, (hipStream_t)stream, c);
+    } else if (symmetric) {
+        hipLaunchKernelGGL(ntuple_trace_kernel<true>, grid, block, 0, (hipStream_t)stream, p);
+    } else {
+        hipLaunchKernelGGL(ntuple_trace_kernel<false>, grid, block, 0, (hipStream_t)stream, p);
+    }
     TPL_LEARN_HIP(hipGetLastError());
+    return TPL_OK;
+}
+
+// what the two ring updates refuse beyond check_update, in this order
+int check_ring(const char* name, int64_t n, int32_t slots, int32_t head, int32_t horizon, float decay) {
+    if (slots < 1 || slots > TPL_NTUPLE_TRACE_MAX + 1)
+        return fail_msg(TPL_ERR_ARG, "%s: slots must be in [1, %d]", name, TPL_NTUPLE_TRACE_MAX + 1);
+    if (head < 0 || head >= slots) return fail_msg(TPL_ERR_ARG, "%s: head must be in [0, slots)", name);
+    if (horizon < 1 || horizon > slots || horizon > TPL_NTUPLE_TRACE_MAX)
+        return fail_msg(TPL_ERR_ARG, "%s: horizon must be in [1, min(slots, %d)]", name, TPL_NTUPLE_TRACE_MAX);
+    if ((int64_t)slots * n >= (((int64_t)1 << 31) + kActions - 1) / kActions)
+        return fail_msg(TPL_ERR_ARG, "%s: 40 * slots * n must stay below 2^31", name);
+    if (!(decay >= 0.0f && decay <= 1.0f)) return fail_msg(TPL_ERR_ARG, "%s: decay must be in [0, 1]", name);
     return TPL_OK;
 }
 
@@ -439,13 +619,15 @@ extern "C" int tpl_ntuple_update_trace(const void* ring_a, const void* ring_b, i
                                        float decay, int32_t symmetric, void* stream) {
     const char* name = "tpl_ntuple_update_trace";
     if (const int rc = check_update(name, ring_a, ring_b, n, L, M, table, error, rate)) return rc;
-    if (slots < 1 || slots > TPL_NTUPLE_TRACE_MAX + 1)
-        return fail_msg(TPL_ERR_ARG, "%s: slots must be in [1, %d]", name, TPL_NTUPLE_TRACE_MAX + 1);
-    if (head < 0 || head >= slots) return fail_msg(TPL_ERR_ARG, "%s: head must be in [0, slots)", name);
-    if (horizon < 1 || horizon > slots || horizon > TPL_NTUPLE_TRACE_MAX)
-        return fail_msg(TPL_ERR_ARG, "%s: horizon must be in [1, min(slots, %d)]", name, TPL_NTUPLE_TRACE_MAX);
-    if ((int64_t)slots * n >= (((int64_t)1 << 31) + kActions - 1) / kActions)
-        return fail_msg(TPL_ERR_ARG, "%s: 40 * slots * n must stay below 2^31", name);
-    if (!(decay >= 0.0f && decay <= 1.0f)) return fail_msg(TPL_ERR_ARG, "%s: decay must be in [0, 1]", name);
+    if (const int rc = check_ring(name, n, slots, head, horizon, decay)) return rc;
     return launch_update(ring_a, ring_b, n, slots, head, horizon, L, M, table, error, rate, decay, symmetric != 0, stream);
+}
+
+extern "C" int tpl_ntuple_update_coherent(const void* ring_a, const void* ring_b, int64_t n, int32_t slots, int32_t head,
+                                          int32_t horizon, int32_t L, int32_t M, int32_t* table, int64_t* coherence,
+                                          const float* error, float rate, float decay, int32_t symmetric, void* stream) {
+    const char* name = "tpl_ntuple_update_coherent";
+    if (const int rc = check_update(name, ring_a, ring_b, n, L, M, table, error, rate, &coherence)) return rc;
+    if (const int rc = check_ring(name, n, slots, head, horizon, decay)) return rc;
+    return launch_update(ring_a, ring_b, n, slots, head, horizon, L, M, table, error, rate, decay, symmetric != 0, stream, coherence);
 }

@@ -10,13 +10,17 @@ learning on the device (the rule: include/tpl_learn.h; the kernels: csrc/learn/n
                                   afterstate of the action played and its value.  depth=2 searches the known next piece as well,
                                   still in one launch:  r + gamma * max_b (r_b + gamma * V)  -- the value of the afterstate itself,
                                   with the table one move further out; act(second=) gives the placement planned for that piece
-    NTupleLearner(env, gamma, rate, epsilon, seed, depth=1, lam=0.0, horizon=1, symmetric=False)
+    NTupleLearner(env, gamma, rate, epsilon, seed, depth=1, lam=0.0, horizon=1, symmetric=False, coherent=False)
                                   TD(0) on afterstates: train(steps), evaluate(steps, depth=None); `table` is a plain tensor
                                   (torch.save it); a table trained at one depth can be played at the other.  horizon > 1 adds
                                   truncated TD(lambda) traces -- the error also goes, decayed by (gamma lam)^k, to the afterstates
                                   k < horizon moves back in the same episode --, symmetric=True adds every update to the entries of
                                   the reflected board as well, which keeps the table mirror-symmetric
+                                  coherent=True gives every entry a step size of its own (temporal coherence): the ratio of the
+                                  signed to the absolute sum of the steps it was sent, kept in `coherence`
     ntuple_is_symmetric(table)    whether table[sigma] == table under the mirror permutation of the entries
+    ntuple_coherence(device)      a zeroed coherence buffer: int64 [314,368, 2], the pairs (E, A)
+    ntuple_step_sizes(coherence)  alpha of every entry: float32 [314,368]
 
 The value is a sum of table entries, one per 2 x 4 window of the board that is not empty, chosen by the falling piece, plus one
 per (lines left, moves left); the update adds rint(rate * error) to the same entries.  Everything is integer, so two trainings
@@ -33,7 +37,8 @@ from . import _learn_lib
 from ._learn_lib import NTUPLE_ENTRIES, NTUPLE_TRACE_MAX, check
 from .lookahead import _MAX_BOARDS, _boards, _ptr, _state_ptrs
 
-__all__ = ["NTUPLE_ENTRIES", "ntuple_table", "ntuple_value", "ntuple_is_symmetric", "NTuplePolicy", "NTupleLearner"]
+__all__ = ["NTUPLE_ENTRIES", "ntuple_table", "ntuple_value", "ntuple_is_symmetric", "ntuple_coherence", "ntuple_step_sizes",
+           "NTuplePolicy", "NTupleLearner"]
 
 _STATE_WON = 1                                                 # bits 28..29 of B.y: 0 running, 1 won, 2 and 3 lost
 _FINISHED_B_Y = _STATE_WON << 28                               # B.y of a state that is finished and otherwise empty
@@ -42,6 +47,28 @@ _FINISHED_B_Y = _STATE_WON << 28                               # B.y of a state 
 def ntuple_table(device="cuda:0") -> torch.Tensor:
     """A zeroed n-tuple table on `device`: int32 [NTUPLE_ENTRIES]."""
     return torch.zeros(NTUPLE_ENTRIES, dtype=torch.int32, device=device)
+
+
+def ntuple_coherence(device="cuda:0") -> torch.Tensor:
+    """A zeroed coherence buffer on `device`: int64 [NTUPLE_ENTRIES, 2], entry j the pair (E_j, A_j) of include/tpl_learn.h."""
+    return torch.zeros((NTUPLE_ENTRIES, 2), dtype=torch.int64, device=device)
+
+
+@torch.no_grad()
+def ntuple_step_sizes(coherence: torch.Tensor) -> torch.Tensor:
+    """float32 [NTUPLE_ENTRIES] on the buffer's device: alpha of every entry as tpl_ntuple_update_coherent would read it now -- 1
+    where A <= 0, else min(|E| / A, 1) in float32.  torch has no unsigned 64-bit conversion, so the one magnitude a signed
+    conversion gets wrong, |INT64_MIN| = 2^63, is put in by a select; the quotient of the two float32 values is taken in float64
+    and rounded to float32, which is the float32 quotient rounded once (53 >= 2 * 24 + 2 bits) whatever division torch's float32
+    kernels were built with.  No host sync."""
+    if (not isinstance(coherence, torch.Tensor) or coherence.dtype != torch.int64 or tuple(coherence.shape) != (NTUPLE_ENTRIES, 2)
+            or not coherence.is_contiguous()):
+        raise ValueError(f"coherence must be a contiguous int64 tensor of shape ({NTUPLE_ENTRIES}, 2) (ntuple_coherence)")
+    e, a = coherence[:, 0], coherence[:, 1]
+    lowest = e == torch.iinfo(torch.int64).min
+    mag = torch.where(lowest, 2.0 ** 63, e.masked_fill(lowest, 0).abs().to(torch.float32))
+    ratio = torch.clamp((mag.to(torch.float64) / a.to(torch.float32).to(torch.float64)).to(torch.float32), max=1.0)
+    return torch.where(a <= 0, 1.0, ratio).to(torch.float32)
 
 
 def _table(table, device) -> torch.Tensor:
@@ -229,10 +256,17 @@ class NTupleLearner:
     sum_k (gamma lam)^k, so `rate` wants to shrink with it.  Traces are NOT cut on exploratory moves (the naive form): the error
     of a step whose predecessor explored still reaches the older afterstates.  symmetric=True adds every update to the table
     entries of the reflected board too (L <-> J, S <-> Z): the table stays mirror-symmetric (ntuple_is_symmetric), each board
-    teaches its reflection, and the step of V doubles once more.  Still five enqueues a step, no sync, nothing allocated."""
+    teaches its reflection, and the step of V doubles once more.  Still five enqueues a step, no sync, nothing allocated.
+
+    Temporal coherence (tpl_ntuple_update_coherent; coherent=False by default, which leaves the table bytes of the loop above).
+    The learner owns `coherence` (ntuple_coherence), the signed and the absolute sum of the steps every entry was sent, and step 3
+    scales an entry's step by alpha = |E| / A as it stood before the step (ntuple_step_sizes): an entry whose errors keep their
+    sign learns at `rate`, one whose errors alternate -- an overshoot -- slows itself down.  A coherent step is never larger than
+    the plain one.  forget() leaves `coherence` alone; it is a plain tensor, and coherence.zero_() starts the step sizes over.
+    Still five enqueues a step (the entry launches two kernels), no sync, nothing allocated."""
 
     def __init__(self, env, gamma: float = 0.99, rate: float = 8.0, epsilon: float = 0.1, seed: int = 0, depth: int = 1,
-                 lam: float = 0.0, horizon: int = 1, symmetric: bool = False):
+                 lam: float = 0.0, horizon: int = 1, symmetric: bool = False, coherent: bool = False):
         n = _boards(env, "NTupleLearner")
         if not env.auto_reset:
             raise ValueError("NTupleLearner needs an auto-reset environment")
@@ -241,7 +275,9 @@ class NTupleLearner:
         self.lam, self.horizon = _unit("lam", lam), _horizon(horizon)
         if not isinstance(symmetric, bool):
             raise ValueError(f"symmetric must be True or False, got {symmetric!r}")
-        self.symmetric = symmetric
+        if not isinstance(coherent, bool):
+            raise ValueError(f"coherent must be True or False, got {coherent!r}")
+        self.symmetric, self.coherent = symmetric, coherent
         self.decay = float(gamma) * self.lam                   # the C `decay`, passed as a float
         if not 0.0 <= self.decay <= 1.0:
             raise ValueError(f"gamma * lam must be in [0, 1] (it decays the trace), got {self.decay!r}")
@@ -251,6 +287,7 @@ class NTupleLearner:
         d = env.device
         self.depth = _depth(depth)
         self.table = ntuple_table(d)
+        self.coherence = ntuple_coherence(d) if coherent else None
         self.policy = NTuplePolicy(env, self.table, gamma, epsilon, seed, self.depth)
         self.greedy = NTuplePolicy(env, self.table, gamma, 0.0, seed, self.depth)
         self.steps = 0                                         # train() steps so far: the `step` of the exploration draw
@@ -275,7 +312,8 @@ class NTupleLearner:
         return self._slot[(self._head + 1) % self.slots]
 
     def forget(self) -> None:
-        """Nothing is kept from the steps before: every slot becomes finished states, which update nothing."""
+        """Nothing is kept from the steps before: every slot becomes finished states, which update nothing.  The table and the
+        coherence buffer stay as they are."""
         for ring in self._ring:
             ring.zero_()
         self._ring[1][:, :, 1] = _FINISHED_B_Y
@@ -293,9 +331,10 @@ class NTupleLearner:
             self.policy.act(out=self._action, score=self._score, after=self._next, step=self.steps)
             _value(kept[0], kept[1], n, env.L, env.M, self.table, self._kept_value, env.device)
             torch.sub(self._score, self._kept_value, out=self._error)
-            check(lib.tpl_ntuple_update_trace(ring_a, ring_b, n, self.slots, self._head, self.horizon, env.L, env.M,
-                                              self.table.data_ptr(), self._error.data_ptr(), self.rate, self.decay,
-                                              int(self.symmetric), stream))
+            ring = (ring_a, ring_b, n, self.slots, self._head, self.horizon, env.L, env.M, self.table.data_ptr())
+            tail = (self._error.data_ptr(), self.rate, self.decay, int(self.symmetric), stream)
+            check(lib.tpl_ntuple_update_coherent(*ring, self.coherence.data_ptr(), *tail) if self.coherent
+                  else lib.tpl_ntuple_update_trace(*ring, *tail))
             env.step_into(self._action, self._reward, self._done)
             self._head = (self._head + 1) % self.slots
             self.steps += 1

@@ -64,6 +64,18 @@ Parts:
     ntuple_trace_sweep  NTupleLearner on part ntuple's L=10 / M=40 carved pool (the shaped reward, 4,096 boards, epsilon 0.05, gamma
               1, 40,000 steps, wins over 12,288 greedy steps): the TD(0) baseline at rate 16 re-run, then lambda in 0.5, 0.8, 0.9 x
               horizon in 4, 8 x symmetric or not x rate in 4, 8, 16, and symmetry alone (horizon 1) at the three rates
+    ntuple_coherent  temporal-coherence step sizes: tpl_ntuple_update_coherent beside tpl_ntuple_update_trace (and tpl_ntuple_update
+              on the newest slot) in the same alternated rounds, part ntuple_trace's ring, errors and method, at 2^16, 2^18 and
+              2^20 boards for horizon 1 and 4, symmetric and not, on a coherence buffer that three calls with other errors have
+              filled (most step sizes far below 1, so part of the steps round to 0 and their adds are skipped) and, as the other
+              end, with errors of one sign on a buffer of its own (every step size 1, every add made); the two phases' own times
+              from the kernel records of torch.profiler over five more calls; added bytes/s: 4 per entry and add for the step phase
+              (which also gathers 16), 16 for the accumulate phase
+    ntuple_coherent_sweep  part ntuple_trace_sweep's set-up unchanged (pool, seed, reward, epsilon, gamma, budget, evaluation) with
+              coherent on and off: TD(0), lambda 0.5 / horizon 8 and symmetric lambda 0.8 / horizon 4 at rates 4, 8, 16, 32 and 64
+              each (TD(0) at rate 16 without coherence is the baseline), and the two-piece game (4,096 boards, 300 steps) at rates
+              64, 256 and 1,024; win rates after 10,000 and 40,000 steps, the largest entry, and alpha over the entries that were
+              sent a step.  --chunk I/K runs every K-th cell from the I-th on, for a run in several processes
 """
 import argparse
 import json
@@ -78,7 +90,8 @@ sys.path.insert(0, ROOT)
 HBM_ACHIEVABLE = 6.3e12
 PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600, "priority": 600, "nstep": 600, "mirror": 600, "afterstates": 600,
          "heuristic": 600, "search": 900, "beam": 900, "ntuple": 900,
-         "ntuple_search": 900, "ntuple_trace": 600, "ntuple_trace_sweep": 1100}
+         "ntuple_search": 900, "ntuple_trace": 600, "ntuple_trace_sweep": 1100, "ntuple_coherent": 600,
+         "ntuple_coherent_sweep": 1700}
 SCATTERED_ATOMICS = 0.08e12                                 # 64 lanes of a wave adding into 64 rows (float adds; integer adds unmeasured)
 VALU_CYCLES, SIMDS, CLOCK_HZ = 3.3, 1024, 2.4e9           # the move's instruction mix, 256 CUs x 4, the clock
 
@@ -1214,12 +1227,205 @@ def part_ntuple_trace_sweep(eval_steps=12288):
                 epsilon=0.05, eval_steps=eval_steps, baseline=runs[0], best=best, runs=runs)
 
 
+def _kernel_us(fn, names, calls=5):
+    """The device time per call, in µs, of each kernel whose name holds one of `names`, from torch.profiler's kernel records over
+    `calls` calls of fn; a string that says why where there are none."""
+    import torch
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            for _ in range(calls):
+                fn()
+            torch.cuda.synchronize()
+        got = {}
+        for name in names:
+            ts = [e.device_time for e in prof.events() if name in e.name and e.device_time > 0]
+            got[name] = round(sum(ts) / calls, 2) if ts else "no kernel records"
+        return got
+    except Exception as exc:                                     # the profiler is a measuring aid; the timings above stand without it
+        return {name: f"profiler failed: {exc!r}"[:120] for name in names}
+
+
+def part_ntuple_coherent(rounds=5, reps=10):
+    import numpy as np
+    import torch
+    import tetris_piclim as T
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import learn_ref as R
+    m = T._learn_lib
+    L, check = m.lib(), m.check
+    stream = torch._C._cuda_getCurrentRawStream(0)
+    slots, head, rate, decay = 17, 16, 100.0, 0.9
+    kernels = ("ntuple_coherent_step_kernel", "ntuple_coherent_accumulate_kernel")
+    out = dict(part="ntuple_coherent", slots=slots, head=head, rate=rate, decay=decay,
+               static_valu={k: _static_valu(k, m.build_library()) for k in ("ntuple_trace_kernelILb0", "ntuple_trace_kernelILb1",
+                            "coherent_step_kernelILb0", "coherent_step_kernelILb1", "coherent_accumulate_kernelILb0",
+                            "coherent_accumulate_kernelILb1")})
+    host = np.random.default_rng(0).integers(-(1 << 20), (1 << 20) + 1, m.NTUPLE_ENTRIES).astype(np.int32)
+    rows = []
+    for n in (1 << 16, 1 << 18, 1 << 20):
+        env = T.BatchedTetris(10, 40, n, device="cuda:0", seed=1, auto_reset=True)
+        env.load_configs(*env.synthetic_configs(4096))
+        env.reset()
+        ring = [torch.empty((slots, n, 4), dtype=torch.int32, device="cuda:0") for _ in range(2)]
+        for t in range(6 + slots):                               # part ntuple_trace's ring: the last 17 states of every board
+            env.step(env.synthetic_actions(t), observe=False)
+            if t >= 6:
+                a, b = env.raw_planes()
+                ring[0][t - 6].copy_(a)
+                ring[1][t - 6].copy_(b)
+        a, b = (x[head, :4096].cpu().numpy().view(np.uint32) for x in ring)
+        f = R.decode_state(a, b)
+        _, used = m.ntuple_indices(f["rows"], f["cur"], 10, 40, f["lines"].astype(np.int64), f["moves"].astype(np.int64))
+        in_use = float(used[f["state"] == 0].sum(axis=1).mean())
+        table = torch.from_numpy(host).to("cuda:0")
+        coherence = T.ntuple_coherence("cuda:0")
+        error = torch.empty(n, dtype=torch.float32, device="cuda:0").normal_()
+        running = ((ring[1][:, :, 1] >> 28) & 3) == 0
+        open_ = torch.cumprod(running.flip(0).to(torch.int32), dim=0).bool()
+        w = torch.tensor([decay], dtype=torch.float32, device="cuda:0") ** torch.arange(slots, device="cuda:0", dtype=torch.float32)
+        adds = open_ & (torch.round(rate * w[:, None] * error[None, :]) != 0)
+        pairs = {h: float(adds[:h].sum()) / n for h in (1, 4)}
+        pa, pb = ring[0].data_ptr(), ring[1].data_ptr()
+
+        def trace(horizon, symmetric, e=error):
+            check(L.tpl_ntuple_update_trace(pa, pb, n, slots, head, horizon, 10, 40, table.data_ptr(), e.data_ptr(), rate, decay,
+                                            symmetric, stream))
+
+        def coherent(horizon, symmetric, e=error, c=coherence):
+            check(L.tpl_ntuple_update_coherent(pa, pb, n, slots, head, horizon, 10, 40, table.data_ptr(), c.data_ptr(),
+                                               e.data_ptr(), rate, decay, symmetric, stream))
+        one_sign, full = error.abs(), T.ntuple_coherence("cuda:0")   # E = A at every entry: alpha stays 1, no step rounds to 0
+        for _ in range(3):                                       # step sizes of every kind before anything is timed
+            coherent(4, 1, torch.empty_like(error).normal_())
+        alpha = T.ntuple_step_sizes(coherence)[coherence[:, 1] > 0]
+        steps = torch.round(rate * alpha.mean() * error)        # a rough share of the steps that round to 0 at the mean step size
+        variants = [("update", lambda: check(L.tpl_ntuple_update(ring[0][head].data_ptr(), ring[1][head].data_ptr(), n, 10, 40,
+                                                                 table.data_ptr(), error.data_ptr(), rate, stream)))]
+        for h in (1, 4):
+            for sym in (0, 1):
+                variants.append((f"trace_h{h}_s{sym}", (lambda h=h, sym=sym: trace(h, sym))))
+                variants.append((f"coherent_h{h}_s{sym}", (lambda h=h, sym=sym: coherent(h, sym))))
+                variants.append((f"alpha1_h{h}_s{sym}", (lambda h=h, sym=sym: coherent(h, sym, one_sign, full))))
+        times = {name: [] for name, _ in variants}
+        for _ in range(rounds):                                  # alternate the variants round by round
+            for name, fn in variants:
+                times[name].append(_timed(fn, reps))
+        med = {name: sorted(ts)[rounds // 2] for name, ts in times.items()}
+        row = dict(boards=n, entries_in_use_per_board=round(in_use, 1), adding_pairs_per_board={f"h{h}": round(p, 3) for h, p in pairs.items()},
+                   alpha_before_timing=dict(entries=int(alpha.numel()), mean=round(float(alpha.mean()), 3),
+                                            below_half=round(float((alpha < 0.5).float().mean()), 3),
+                                            steps_0_at_the_mean=round(float((steps == 0).float().mean()), 3)),
+                   update=dict(us=_spread(times["update"])))
+        for h in (1, 4):
+            for sym in (0, 1):
+                entries = n * pairs[h] * (in_use * (2 if sym else 1) - (1 if sym else 0))          # entry adds a call; the counter: once
+                t, c = med[f"trace_h{h}_s{sym}"], med[f"coherent_h{h}_s{sym}"]
+                phases = _kernel_us(lambda h=h, sym=sym: coherent(h, sym), kernels)
+                cell = dict(trace_us=_spread(times[f"trace_h{h}_s{sym}"]), coherent_us=_spread(times[f"coherent_h{h}_s{sym}"]),
+                            coherent_over_trace=round(c / t, 2), coherent_over_update=round(c / med["update"], 2),
+                            trace_tb_per_s=round(entries * 4 / t / 1e12, 3), phases_us=phases)
+                step, acc = phases[kernels[0]], phases[kernels[1]]
+                if isinstance(step, float) and isinstance(acc, float):
+                    cell.update(step_over_trace=round(step * 1e-6 / t, 2), accumulate_over_trace=round(acc * 1e-6 / t, 2),
+                                step_added_tb_per_s=round(entries * 4 / (step * 1e-6) / 1e12, 3),
+                                step_gathered_tb_per_s=round(entries * 16 / (step * 1e-6) / 1e12, 3),
+                                accumulate_added_tb_per_s=round(entries * 16 / (acc * 1e-6) / 1e12, 3),
+                                accumulate_atomics_per_s=round(entries * 2 / (acc * 1e-6) / 1e9, 2))
+                a1 = med[f"alpha1_h{h}_s{sym}"]
+                p1 = _kernel_us(lambda h=h, sym=sym: coherent(h, sym, one_sign, full), kernels)
+                cell["every_step_size_1"] = dict(coherent_us=_spread(times[f"alpha1_h{h}_s{sym}"]), coherent_over_trace=round(a1 / t, 2),
+                                                 coherent_over_update=round(a1 / med["update"], 2), phases_us=p1)
+                if isinstance(p1[kernels[0]], float):
+                    cell["every_step_size_1"].update(step_over_trace=round(p1[kernels[0]] * 1e-6 / t, 2),
+                                                     step_added_tb_per_s=round(entries * 4 / (p1[kernels[0]] * 1e-6) / 1e12, 3))
+                row[f"h{h}_s{sym}"] = cell
+        rows.append(row)
+        print(json.dumps(row), file=sys.stderr, flush=True)
+        env.terminate()
+        del table, coherence, full, ring, running, open_, adds
+        torch.cuda.empty_cache()
+    out["kernel"] = dict(rounds=rounds, launches_per_timing=reps, rows=rows)
+    return out
+
+
+def _alpha_summary(T, coherence):
+    import torch
+    alpha = T.ntuple_step_sizes(coherence)[coherence[:, 1] > 0]
+    if alpha.numel() == 0:
+        return dict(entries=0)
+    q = torch.quantile(alpha, torch.tensor([0.1, 0.5, 0.9], device=alpha.device))
+    return dict(entries=int(alpha.numel()), mean=round(float(alpha.mean()), 4), q10=round(float(q[0]), 4), q50=round(float(q[1]), 4),
+                q90=round(float(q[2]), 4), below_0_1=round(float((alpha < 0.1).float().mean()), 4),
+                below_0_5=round(float((alpha < 0.5).float().mean()), 4), at_1=round(float((alpha == 1.0).float().mean()), 4))
+
+
+def part_ntuple_coherent_sweep(eval_steps=12288, chunk=(0, 1)):
+    import torch
+    import tetris_piclim as T
+    cells = []
+    for form in (dict(), dict(lam=0.5, horizon=8), dict(lam=0.8, horizon=4, symmetric=True)):
+        for rate in (4.0, 8.0, 16.0, 32.0, 64.0):
+            for coherent in (False, True):
+                cells.append(dict(game="l10_m40", rate=rate, coherent=coherent, **form))
+    cells.sort(key=lambda c: (c != dict(game="l10_m40", rate=16.0, coherent=False)))               # the baseline first
+    cells += [dict(game="two_piece", rate=rate, coherent=coherent) for rate in (64.0, 256.0, 1024.0) for coherent in (False, True)]
+    mine = cells[chunk[0]::chunk[1]]
+    big = None
+    if any(c["game"] == "l10_m40" for c in mine):
+        gen_env = T.BatchedTetris(10, 40, 64, device="cuda:0", seed=7)
+        big = gen_env.carved_configs(1 << 16, seed=7)
+        gen_env.terminate()
+
+    def result(r):
+        p = r["win_rate"]
+        return dict(episodes=r["episodes"], wins=r["wins"], win_rate=round(p, 5),
+                    standard_error=round((p * (1 - p) / max(r["episodes"], 1)) ** 0.5, 6))
+
+    def learn(game, **kw):
+        if game == "two_piece":                                  # test_ntuple_gpu.py's game and budget
+            carved = T.generate_configs(2, 2, 64, seed=107)
+            env = T.BatchedTetris(2, 2, 4096, device="cuda:0", seed=3, auto_reset=True, reward=(0.0, 1.0, 0.0), config_pool=carved)
+            learner, budget, evaluation = T.NTupleLearner(env, seed=5, gamma=1.0, epsilon=0.25, **kw), (100, 200), 16
+        else:                                                    # part ntuple_trace_sweep's sequence
+            env = T.BatchedTetris(10, 40, 4096, device="cuda:0", seed=11, auto_reset=True, reward=NTUPLE_LARGE_REWARD, config_pool=big)
+            learner, budget, evaluation = T.NTupleLearner(env, seed=11, gamma=1.0, epsilon=0.05, **kw), (10000, 30000), eval_steps
+        got = dict(kw, game=game, zero_table=result(learner.evaluate(evaluation)), trained=[])
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for steps in budget:
+            learner.train(steps)
+            got["trained"].append(dict(steps=learner.steps, **result(learner.evaluate(evaluation))))
+        got.update(seconds=round(time.perf_counter() - t0, 2), entries_in_use=int((learner.table != 0).sum()),
+                   largest_entry=int(learner.table.abs().max()), symmetric_table=T.ntuple_is_symmetric(learner.table))
+        if learner.coherent:
+            got["alpha"] = _alpha_summary(T, learner.coherence)
+        env.terminate()
+        print(json.dumps(got), file=sys.stderr, flush=True)      # progress: a long part must not stay silent
+        return got
+    runs = [learn(**cell) for cell in mine]
+    large = [r for r in runs if r["game"] == "l10_m40"]
+    return dict(part="ntuple_coherent_sweep", chunk=list(chunk), boards=4096, seed=11, pool=1 << 16, pool_seed=7,
+                reward=list(NTUPLE_LARGE_REWARD), gamma=1.0, epsilon=0.05, eval_steps=eval_steps,
+                best=max(large, key=lambda r: r["trained"][-1]["win_rate"]) if large else None, runs=runs)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--part", choices=sorted(PARTS))
+    ap.add_argument("--chunk", default=None, help="I/K: of part ntuple_coherent_sweep, every K-th cell from the I-th on")
     args = ap.parse_args()
     if args.part:
-        print(json.dumps(globals()["part_" + args.part]()), flush=True)
+        kw = {}
+        if args.chunk:
+            if args.part != "ntuple_coherent_sweep":
+                ap.error("--chunk goes with --part ntuple_coherent_sweep")
+            i, k = (int(v) for v in args.chunk.split("/"))
+            if not 0 <= i < k:
+                ap.error("--chunk I/K needs 0 <= I < K")
+            kw["chunk"] = (i, k)
+        print(json.dumps(globals()["part_" + args.part](**kw)), flush=True)
         return 0
     for name, limit in PARTS.items():
         cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--part", name]
