@@ -485,6 +485,57 @@ int tpl_ntuple_update_coherent(const void* ring_a, const void* ring_b, int64_t n
                                int32_t L, int32_t M, int32_t* table, int64_t* coherence, const float* error, float rate,
                                float decay, int32_t symmetric, void* stream);
 
+/* Table shapes.  The geometry of the windows is a parameter of the table; everything else in the rule above is not.
+ *
+ * TPL_NTUPLE_SHAPE_2X4 = 0 is the rule as stated so far, unchanged in every byte: 153 windows of two adjacent columns by four rows.
+ * TPL_NTUPLE_SHAPE_3X3 = 1: a tuple is t = 18 x + y, x in 0..7, y in 0..17 -- 144 tuples --, the window of columns x, x + 1, x + 2 and
+ * rows y .. y + 2, and its pattern is
+ *   q(s, t) = ((c_x >> y) & 7) | (((c_{x+1} >> y) & 7) << 3) | (((c_{x+2} >> y) & 7) << 6)          -- 512 patterns.
+ * A 3 x 3 window holds a column together with BOTH of its neighbours, which no 2 x 4 window does: a well, or a notch under an
+ * overhang, is one pattern of it and not a sum of two half-views.
+ * Table: TPL_NTUPLE_ENTRIES_3X3 = 8 * 144 * 512 + 1024 = 590,848 int32 entries (2,363,392 bytes), 16-byte aligned, in units of 2^-16:
+ *   tuple[p][t][q] at index ((p * 144 + t) * 512) | q      p in 0..7, t in 0..143, q in 0..511
+ *   counter[k]     at index 589,824 + k                    k in 0..1023, the same k as above
+ * Unchanged: the piece index p and the counter index k; the all-empty pattern contributes nothing and is never updated; the sum is
+ * exact in 64-bit integers, rounded ONCE at the conversion and scaled by 2^-16; a state that is not running has V = 0; the policy,
+ * the exploration draw, d_k, the trace rule, the step size alpha_j and the read-before-add rule of the coherent update.
+ * Windows stay inside the board: no wall and no floor bits are added.  A wall column read as full would give every board with an
+ * empty edge column one shared non-empty entry -- the hot address that skipping the all-empty pattern avoids.
+ * Mirror image (symmetric != 0): d_k is also added to tuple[pi(p)][18 (7 - x) + y][swap(q)], where swap exchanges bits 0..2 of q with
+ * bits 6..8 and leaves bits 3..5:  swap(q) = (q >> 6) | (q & 0x38) | ((q & 7) << 6).  Both tuple adds are made, also where the two
+ * entries are one -- with eight window columns x never equals 7 - x, so in this shape no tuple entry is its own image; the rule is
+ * worded for both shapes.  sigma, the invariant and its consequences read as above with these indices.
+ * Coherence buffer: int64 [TPL_NTUPLE_ENTRIES_3X3][2] (9,453,568 bytes): of the shape's entry count, as the table.
+ *
+ * Each _shaped entry below is the entry of the same name with `shape` before `stream`; the entry without it is the _shaped one at
+ * TPL_NTUPLE_SHAPE_2X4, through the same argument check and the same kernels.  table (and coherence) must hold the shape's
+ * entries; device memory cannot be checked here.  Refused before anything else, and before any pointer is looked at: a shape that
+ * is neither of the two.  The 3 x 3 kernels (ntuple3_*_kernel) are the same device bodies compiled for the other geometry: the
+ * same lane mappings, eight (symmetric: sixteen) gathers or adds in flight per trip over y, 18 trips. */
+typedef enum { TPL_NTUPLE_SHAPE_2X4 = 0, TPL_NTUPLE_SHAPE_3X3 = 1 } tpl_ntuple_shape;
+#define TPL_NTUPLE_ENTRIES_3X3 590848
+
+/* The entries of a table of `shape`: TPL_NTUPLE_ENTRIES, TPL_NTUPLE_ENTRIES_3X3, or -1 for a shape that is not known. */
+int64_t tpl_ntuple_entries(int32_t shape);
+
+int tpl_ntuple_value_shaped(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const int32_t* table,
+                            float* value, int32_t shape, void* stream);
+int tpl_ntuple_act_shaped(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line, float r_win,
+                          float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed, uint64_t step,
+                          uint8_t* action, float* score, void* after_a, void* after_b, float* value, int32_t shape, void* stream);
+int tpl_ntuple_search_shaped(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line, float r_win,
+                             float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed, uint64_t step,
+                             uint8_t* action, uint8_t* second, float* score, void* after_a, void* after_b, float* value,
+                             int32_t shape, void* stream);
+int tpl_ntuple_update_shaped(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, int32_t* table,
+                             const float* error, float rate, int32_t shape, void* stream);
+int tpl_ntuple_update_trace_shaped(const void* ring_a, const void* ring_b, int64_t n, int32_t slots, int32_t head, int32_t horizon,
+                                   int32_t L, int32_t M, int32_t* table, const float* error, float rate, float decay,
+                                   int32_t symmetric, int32_t shape, void* stream);
+int tpl_ntuple_update_coherent_shaped(const void* ring_a, const void* ring_b, int64_t n, int32_t slots, int32_t head,
+                                      int32_t horizon, int32_t L, int32_t M, int32_t* table, int64_t* coherence, const float* error,
+                                      float rate, float decay, int32_t symmetric, int32_t shape, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,7 +30,9 @@ LEARN_SYMBOLS = [
     "tpl_priority_update", "tpl_replay_sample_prioritized", "tpl_priority_target", "tpl_replay_sample_nstep",
     "tpl_replay_sample_mirror", "tpl_mirror_states", "tpl_afterstates", "tpl_canonical_action", "tpl_placement_features",
     "tpl_placement_act", "tpl_placement_search", "tpl_placement_beam", "tpl_ntuple_value", "tpl_ntuple_act", "tpl_ntuple_update",
-    "tpl_ntuple_search", "tpl_ntuple_update_trace", "tpl_ntuple_update_coherent",
+    "tpl_ntuple_search", "tpl_ntuple_update_trace", "tpl_ntuple_update_coherent", "tpl_ntuple_entries",
+    "tpl_ntuple_value_shaped", "tpl_ntuple_act_shaped", "tpl_ntuple_search_shaped", "tpl_ntuple_update_shaped",
+    "tpl_ntuple_update_trace_shaped", "tpl_ntuple_update_coherent_shaped",
 ]
 NSTEP_MAX = 16
 BEAM_MAX_DEPTH, BEAM_MAX_WIDTH = 12, 64
@@ -143,6 +145,14 @@ def lib() -> C.CDLL:
     L.tpl_ntuple_search.argtypes = [vp, vp, i64, i32, i32, f32, f32, f32, f32, vp, f32, u64, u64, vp, vp, vp, vp, vp, vp, vp]
     L.tpl_ntuple_update_trace.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, vp, vp, f32, f32, i32, vp]
     L.tpl_ntuple_update_coherent.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, f32, f32, i32, vp]
+    L.tpl_ntuple_entries.restype = i64
+    L.tpl_ntuple_entries.argtypes = [i32]
+    shaped = ("tpl_ntuple_value", "tpl_ntuple_act", "tpl_ntuple_update", "tpl_ntuple_search", "tpl_ntuple_update_trace",
+              "tpl_ntuple_update_coherent")
+    for name in shaped:                                      # the twin's arguments with `shape` before `stream`
+        twin = getattr(L, name + "_shaped")
+        twin.argtypes = getattr(L, name).argtypes[:-1] + [i32, vp]
+        twin.restype = i32
     for name in ("tpl_replay_push", "tpl_replay_sample", "tpl_learn_pack", "tpl_priority_init", "tpl_priority_push",
                  "tpl_priority_update", "tpl_replay_sample_prioritized", "tpl_replay_sample_nstep", "tpl_replay_sample_mirror",
                  "tpl_mirror_states", "tpl_afterstates", "tpl_placement_features", "tpl_placement_act",
@@ -521,15 +531,37 @@ def beam_select(values, width: int) -> np.ndarray:
 NTUPLE_PIECES, NTUPLE_TUPLES, NTUPLE_PATTERNS, NTUPLE_COUNTERS = 8, 153, 256, 1024
 NTUPLE_COUNTER_BASE = NTUPLE_PIECES * NTUPLE_TUPLES * NTUPLE_PATTERNS                   # 313,344
 NTUPLE_ENTRIES = NTUPLE_COUNTER_BASE + NTUPLE_COUNTERS                                   # 314,368
+# the table shapes of include/tpl_learn.h: name -> (tuples, patterns, entries); NTUPLE_SHAPE_IDS gives the C `shape` of a name
+NTUPLE_SHAPES = {"2x4": (153, 256, 314368), "3x3": (144, 512, 590848)}
+NTUPLE_SHAPE_IDS = {"2x4": 0, "3x3": 1}
+_WINDOWS = {"2x4": (2, 4), "3x3": (3, 3)}                  # (columns, rows) of a window
 NTUPLE_STEP_MAX = 1 << 24                                                               # |d| of one update is clamped to it
 PIECE_PLACEMENTS = (17, 34, 34, 34, 17, 17, 9, 9)        # S: the distinct placements of each piece id (7 reads O's entry)
 
 
-def ntuple_indices(rows, piece, L: int, M: int, lines, moves):
+def _ntuple_shape(shape) -> str:
+    if not isinstance(shape, str) or shape not in NTUPLE_SHAPES:
+        raise ValueError(f"shape must be one of {sorted(NTUPLE_SHAPES)}, got {shape!r}")
+    return shape
+
+
+def ntuple_shape_of(entries: int) -> str:
+    """The shape whose table has `entries` entries; anything else is refused."""
+    for name, (_, _, count) in NTUPLE_SHAPES.items():
+        if entries == count:
+            return name
+    raise ValueError(f"no table shape has {entries} entries: {({k: v[2] for k, v in NTUPLE_SHAPES.items()})}")
+
+
+def ntuple_indices(rows, piece, L: int, M: int, lines, moves, shape: str = "2x4"):
     """Where the value of K boards lives in the table: (index int64 [K, 154], used bool [K, 154]).  Column t < 153 is tuple
     t = 17 x + y -- cell (row y + j, column x) is bit j and cell (row y + j, column x + 1) bit 4 + j of its pattern q, j < 4 --
     at index (piece * 153 + t) * 256 + q, used where q != 0; column 153 is the counter entry 313,344 + 64 min(max(L - lines, 0),
-    15) + min(max(M - moves, 0), 63), always used.  rows: uint16 [K, 20] or [20] row masks (bit x = column x, row 0 = top)."""
+    15) + min(max(M - moves, 0), 63), always used.  rows: uint16 [K, 20] or [20] row masks (bit x = column x, row 0 = top).
+    shape="3x3": [K, 145]; column t < 144 is tuple t = 18 x + y, x < 8 and y < 18 -- cell (row y + j, column x + i) is bit 3 i + j
+    of q, i and j < 3 -- at index (piece * 144 + t) * 512 + q; column 144 is the counter entry 589,824 + the same k."""
+    tuples, patterns, entries = NTUPLE_SHAPES[_ntuple_shape(shape)]
+    wide, high = _WINDOWS[shape]
     rows = np.asarray(rows)
     if rows.ndim == 1:
         rows = rows[None]
@@ -540,31 +572,39 @@ def ntuple_indices(rows, piece, L: int, M: int, lines, moves):
     if k and (piece.min() < 0 or piece.max() >= NTUPLE_PIECES):
         raise ValueError("piece must be in 0..7")
     cell = (rows.astype(np.int64)[:, :, None] >> np.arange(10)[None, None, :]) & 1              # [K, 20, 10]
-    index = np.zeros((k, NTUPLE_TUPLES + 1), dtype=np.int64)
-    used = np.ones((k, NTUPLE_TUPLES + 1), dtype=bool)
-    for x in range(9):
-        for y in range(17):
+    index = np.zeros((k, tuples + 1), dtype=np.int64)
+    used = np.ones((k, tuples + 1), dtype=bool)
+    ys = 20 - high + 1
+    for x in range(10 - wide + 1):
+        for y in range(ys):
             q = np.zeros(k, dtype=np.int64)
-            for j in range(4):
-                q |= (cell[:, y + j, x] << j) | (cell[:, y + j, x + 1] << (4 + j))
-            t = 17 * x + y
-            index[:, t] = (piece * NTUPLE_TUPLES + t) * NTUPLE_PATTERNS + q
+            for i in range(wide):
+                for j in range(high):
+                    q |= cell[:, y + j, x + i] << (high * i + j)
+            t = ys * x + y
+            index[:, t] = (piece * tuples + t) * patterns + q
             used[:, t] = q != 0
-    index[:, NTUPLE_TUPLES] = (NTUPLE_COUNTER_BASE + 64 * np.clip(int(L) - lines, 0, 15) + np.clip(int(M) - moves, 0, 63))
+    index[:, tuples] = (entries - NTUPLE_COUNTERS + 64 * np.clip(int(L) - lines, 0, 15) + np.clip(int(M) - moves, 0, 63))
     return index, used
 
 
 def _ntuple_table(table) -> np.ndarray:
-    if not isinstance(table, np.ndarray) or table.dtype != np.int32 or table.shape != (NTUPLE_ENTRIES,):
-        raise ValueError(f"table must be an int32 array of {NTUPLE_ENTRIES} entries")
+    if (not isinstance(table, np.ndarray) or table.dtype != np.int32 or table.ndim != 1
+            or table.shape[0] not in [v[2] for v in NTUPLE_SHAPES.values()]):
+        raise ValueError(f"table must be an int32 array of {NTUPLE_ENTRIES} entries (3x3: {NTUPLE_SHAPES['3x3'][2]})")
     return table
+
+
+def _table_shape(table) -> str:
+    """The shape of a table that _ntuple_table accepts."""
+    return ntuple_shape_of(_ntuple_table(table).shape[0])
 
 
 def ntuple_value(table, rows, piece, L: int, M: int, lines, moves, state) -> np.ndarray:
     """V of K states (float32 [K]): 0 where state != 0, else the entries ntuple_indices names summed exactly (int64), rounded
     once to float32 and scaled by 2^-16."""
-    index, used = ntuple_indices(rows, piece, L, M, lines, moves)
-    total = np.where(used, _ntuple_table(table)[index].astype(np.int64), 0).sum(axis=1)
+    index, used = ntuple_indices(rows, piece, L, M, lines, moves, _table_shape(table))
+    total = np.where(used, table[index].astype(np.int64), 0).sum(axis=1)
     running = np.broadcast_to(np.asarray(state), total.shape) == 0
     return np.where(running, total.astype(np.float32) * np.float32(2.0 ** -16), np.float32(0.0)).astype(np.float32)
 
@@ -579,7 +619,7 @@ def ntuple_steps(error, rate) -> np.ndarray:
 
 def ntuple_update(table, rows, piece, L: int, M: int, lines, moves, state, error, rate) -> np.ndarray:
     """tpl_ntuple_update, in place: every running state adds its d to the entries ntuple_indices names; the adds wrap."""
-    index, used = ntuple_indices(rows, piece, L, M, lines, moves)
+    index, used = ntuple_indices(rows, piece, L, M, lines, moves, _table_shape(table))
     d = np.where(np.broadcast_to(np.asarray(state), index.shape[:1]) == 0, ntuple_steps(error, rate), 0)
     used = used & (d != 0)[:, None]
     np.add.at(_ntuple_table(table).view(np.uint32), index[used], np.broadcast_to(d[:, None], used.shape)[used].astype(np.uint32))
@@ -587,17 +627,6 @@ def ntuple_update(table, rows, piece, L: int, M: int, lines, moves, state, error
 
 
 NTUPLE_TRACE_MAX = 16                                    # the horizon of tpl_ntuple_update_trace is at most this
-
-
-def ntuple_mirror_permutation() -> np.ndarray:
-    """sigma (int64 [NTUPLE_ENTRIES]): the index of tuple[p][17 x + y][q] -> that of tuple[pi(p)][17 (8 - x) + y][swap(q)], with
-    pi = PIECE_MIRROR and swap(q) = (q >> 4) | ((q & 15) << 4); the counter indices stay.  A table is mirror-symmetric when
-    table[sigma] == table."""
-    sigma = np.arange(NTUPLE_ENTRIES, dtype=np.int64)
-    p, x, y, q = np.meshgrid(np.arange(NTUPLE_PIECES), np.arange(9), np.arange(17), np.arange(NTUPLE_PATTERNS), indexing="ij")
-    image = (np.array(PIECE_MIRROR)[p] * NTUPLE_TUPLES + 17 * (8 - x) + y) * NTUPLE_PATTERNS + ((q >> 4) | ((q & 15) << 4))
-    sigma[:NTUPLE_COUNTER_BASE] = image.reshape(-1)      # (p, x, y, q) in C order is the table's own order
-    return sigma
 
 
 def _reflected_rows(rows) -> np.ndarray:
@@ -609,13 +638,47 @@ def _reflected_rows(rows) -> np.ndarray:
     return out.astype(np.uint16)
 
 
+_sigma_of = {}                                          # ntuple_mirror_permutation's results, one per shape
+
+
+def ntuple_mirror_permutation(shape: str = "2x4") -> np.ndarray:
+    """sigma (int64 [entries of the shape]): the index of tuple[p][17 x + y][q] -> that of tuple[pi(p)][17 (8 - x) + y][swap(q)],
+    with pi = PIECE_MIRROR and swap(q) = (q >> 4) | ((q & 15) << 4) (3x3: 18 (7 - x) + y, and swap exchanges bits 0..2 with bits
+    6..8); the counter indices stay.  A table is mirror-symmetric when table[sigma] == table.
+    Built from its definition, not from that closed form: every tuple entry (p, t, q) is put on a board as the cells of its
+    window, and its image is the index ntuple_indices gives the reflected rows under pi(p) at the reflected window."""
+    tuples, patterns, entries = NTUPLE_SHAPES[_ntuple_shape(shape)]
+    if shape in _sigma_of:
+        return _sigma_of[shape].copy()
+    wide, high = _WINDOWS[shape]
+    xs, ys = 10 - wide + 1, 20 - high + 1
+    sigma = np.arange(entries, dtype=np.int64)
+    q = np.arange(patterns, dtype=np.int64)
+    pi = np.array(PIECE_MIRROR)
+    for x in range(xs):
+        rows = np.zeros((ys, patterns, 20), dtype=np.int64)              # pattern q laid out in window (x, y) of an empty board
+        for y in range(ys):
+            for i in range(wide):
+                for j in range(high):
+                    rows[y, :, y + j] |= ((q >> (high * i + j)) & 1) << (x + i)
+        image, _ = ntuple_indices(_reflected_rows(rows.reshape(-1, 20)), 0, 1, 1, 0, 0, shape)
+        for y in range(ys):
+            t, image_t = ys * x + y, ys * (xs - 1 - x) + y
+            image_q = image[y * patterns:(y + 1) * patterns, image_t] - image_t * patterns    # piece 0: the tuple's row, then q
+            for p in range(NTUPLE_PIECES):
+                sigma[(p * tuples + t) * patterns + q] = (pi[p] * tuples + image_t) * patterns + image_q
+    _sigma_of[shape] = sigma.copy()
+    return sigma
+
+
 def ntuple_update_trace(table, ages, L: int, M: int, error, rate, decay, symmetric) -> np.ndarray:
     """tpl_ntuple_update_trace, in place.  `ages`: a list, newest first, of (rows, piece, lines, moves, state) -- the decoded
     fields ntuple_update takes, K states each.  Board i takes d_k = ntuple_steps(e_i, float32(rate) * w_k), w_0 = 1 and w_k =
     float32(w_{k-1} * decay), at age k as long as that state and every younger one run.  symmetric: the same d_k goes to the tuple
     entries of the REFLECTED rows (columns reversed, piece through PIECE_MIRROR) as well -- not through sigma --; the counter is
     added once."""
-    tab = _ntuple_table(table).view(np.uint32)
+    tab, shape = _ntuple_table(table).view(np.uint32), _table_shape(table)
+    tuples = NTUPLE_SHAPES[shape][0]
     e = np.asarray(error, dtype=np.float32).reshape(-1)
     open_ = np.ones(e.shape, dtype=bool)
     w, decay = np.float32(1.0), np.float32(decay)
@@ -624,26 +687,28 @@ def ntuple_update_trace(table, ages, L: int, M: int, error, rate, decay, symmetr
             w = np.float32(w * decay)
         open_ = open_ & (np.broadcast_to(np.asarray(state), e.shape) == 0)
         d = np.where(open_, ntuple_steps(e, np.float32(rate) * w), 0)
-        index, used = ntuple_indices(rows, piece, L, M, lines, moves)
+        index, used = ntuple_indices(rows, piece, L, M, lines, moves, shape)
         used = used & (d != 0)[:, None]
         np.add.at(tab, index[used], np.broadcast_to(d[:, None], used.shape)[used].astype(np.uint32))
         if symmetric:
             piece = np.broadcast_to(np.asarray(piece, dtype=np.int64), e.shape)
-            index, used = ntuple_indices(_reflected_rows(rows), np.array(PIECE_MIRROR)[piece], L, M, lines, moves)
+            index, used = ntuple_indices(_reflected_rows(rows), np.array(PIECE_MIRROR)[piece], L, M, lines, moves, shape)
             used = used & (d != 0)[:, None]
-            used[:, NTUPLE_TUPLES] = False               # the counter was added above, once
+            used[:, tuples] = False               # the counter was added above, once
             np.add.at(tab, index[used], np.broadcast_to(d[:, None], used.shape)[used].astype(np.uint32))
     return table
 
 
-def _ntuple_coherence(coherence) -> np.ndarray:
-    if not isinstance(coherence, np.ndarray) or coherence.dtype != np.int64 or coherence.shape != (NTUPLE_ENTRIES, 2):
-        raise ValueError(f"coherence must be an int64 array of shape ({NTUPLE_ENTRIES}, 2)")
+def _ntuple_coherence(coherence, entries=None) -> np.ndarray:
+    """An int64 [entries, 2] buffer of a shape's entry count -- of `entries`, where a table says which."""
+    if (not isinstance(coherence, np.ndarray) or coherence.dtype != np.int64 or coherence.ndim != 2 or coherence.shape[1] != 2
+            or coherence.shape[0] not in ([v[2] for v in NTUPLE_SHAPES.values()] if entries is None else [entries])):
+        raise ValueError(f"coherence must be an int64 array of shape ({NTUPLE_ENTRIES if entries is None else entries}, 2)")
     return coherence
 
 
 def ntuple_step_sizes(coherence) -> np.ndarray:
-    """alpha of every entry (float32 [NTUPLE_ENTRIES]) from its pair (E, A): 1 where A <= 0, else min(float32(|E|) / float32(A), 1)
+    """alpha of every entry (float32 [the buffer's entries]) from its pair (E, A): 1 where A <= 0, else min(float32(|E|) / float32(A), 1)
     -- |E| as an unsigned 64-bit value, both conversions to nearest even, the float32 quotient rounded once."""
     c = _ntuple_coherence(coherence)
     e, a = c[:, 0], c[:, 1]
@@ -666,8 +731,9 @@ def ntuple_update_coherent(table, coherence, ages, L: int, M: int, error, rate, 
     """tpl_ntuple_update_coherent, in place on both buffers: (table, coherence).  `ages` as ntuple_update_trace takes them.  Every
     alpha is read from `coherence` as it stands at the call; entry j of a board at age k whose trace is open and whose d_k is not 0
     takes s = ntuple_coherent_steps(e, float32(rate) * w_k, alpha_j) on the table, d_k on E_j and |d_k| on A_j, all wrapping."""
-    tab = _ntuple_table(table).view(np.uint32)
-    sums = _ntuple_coherence(coherence).view(np.uint64)
+    tab, shape = _ntuple_table(table).view(np.uint32), _table_shape(table)
+    tuples = NTUPLE_SHAPES[shape][0]
+    sums = _ntuple_coherence(coherence, table.shape[0]).view(np.uint64)
     alpha = ntuple_step_sizes(coherence)                 # before any add of this call
     e = np.asarray(error, dtype=np.float32).reshape(-1)
     open_ = np.ones(e.shape, dtype=bool)
@@ -681,9 +747,9 @@ def ntuple_update_coherent(table, coherence, ages, L: int, M: int, error, rate, 
         piece = np.broadcast_to(np.asarray(piece, dtype=np.int64), e.shape)
         forms = [(rows, piece, True)] + ([(_reflected_rows(rows), np.array(PIECE_MIRROR)[piece], False)] if symmetric else [])
         for form_rows, form_piece, counter in forms:
-            index, used = ntuple_indices(form_rows, form_piece, L, M, lines, moves)
+            index, used = ntuple_indices(form_rows, form_piece, L, M, lines, moves, shape)
             used = used & (d != 0)[:, None]
-            used[:, NTUPLE_TUPLES] &= counter            # the counter is taken once, with the state's own entries
+            used[:, tuples] &= counter            # the counter is taken once, with the state's own entries
             j = index[used]
             d_j = np.broadcast_to(d[:, None], used.shape)[used]
             s_j = ntuple_coherent_steps(np.broadcast_to(e[:, None], used.shape)[used], r, alpha[j])

@@ -44,6 +44,14 @@
 // only what the other writes, so the bytes of both buffers are again the same in any order.  The two share walk_entries, the walk
 // over a state's entries with the per-entry action handed in; ntuple_trace_kernel keeps its own loop, since on the shared walk
 // its instructions came out in another order (profiles/learner/README.md).
+//
+// Table shapes.  The geometry of the windows is a compile-time trait (Shape2x4, Shape3x3: the window, the tuple counts, the
+// patterns per tuple, the piece stride, the counter base, pattern(c, x, y) and mirrored(q)), and everything above is a __device__
+// template over it: ntuple_sum, tuple_entry, the trace kernel's loop, walk_entries, ntuple_policy.  Each __global__ kernel is a
+// name and a trait: ntuple_*_kernel with Shape2x4 -- the numbers in this comment are that shape's -- and ntuple3_*_kernel with
+// Shape3x3, 144 windows of three columns by three rows, eight (symmetric: sixteen) gathers or adds in flight per trip over 18
+// rows.  The update bodies take the kernel's argument struct BY VALUE: by reference those kernels came out 18 instructions longer.
+// The shape is an argument of the _shaped entries only; it picks the kernel on the host and is never seen on the device.
 #include <cmath>
 
 #include "tpl_placement.h"
@@ -51,15 +59,45 @@
 namespace tpl_learn {
 namespace {
 
-constexpr int kTupleCols = tpl::kCols - 1;                    // x = 0..8: columns x and x + 1
-constexpr int kTupleRows = tpl::kRows - 3;                    // y = 0..16: rows y .. y + 3
-constexpr int kTuples = kTupleCols * kTupleRows;              // 153
-constexpr int kPatterns = 256;
-constexpr int kPieceStride = kTuples * kPatterns;
-constexpr int kCounterBase = 8 * kPieceStride;                // 313,344
 constexpr int kCounterLines = 16, kCounterMoves = 64;
 constexpr int kCounters = kCounterLines * kCounterMoves;      // 1,024
-static_assert(kCounterBase + kCounters == TPL_NTUPLE_ENTRIES, "the table layout of include/tpl_learn.h");
+
+// The geometry of a table, one trait per TPL_NTUPLE_SHAPE_*: a window of kWindowCols adjacent columns by kWindowRows rows, its
+// top-left cell at column x < kTupleCols and row y < kTupleRows, so that every window lies inside the board.  The device bodies
+// below are templates over it; each __global__ kernel names its trait.
+struct Shape2x4 {
+    static constexpr int kWindowCols = 2, kWindowRows = 4;
+    static constexpr int kTupleCols = tpl::kCols - 1;         // x = 0..8: columns x and x + 1
+    static constexpr int kTupleRows = tpl::kRows - 3;         // y = 0..16: rows y .. y + 3
+    static constexpr int kTuples = kTupleCols * kTupleRows;   // 153
+    static constexpr int kPatterns = 256;
+    static constexpr int kPieceStride = kTuples * kPatterns;
+    static constexpr int kCounterBase = 8 * kPieceStride;     // 313,344
+    // the pattern of tuple (x, y): the two columns' nibbles at row y
+    static __device__ __forceinline__ uint32_t pattern(const uint32_t (&c)[tpl::kCols], int x, uint32_t y) {
+        return ((c[x] >> y) & 15u) | (((c[x + 1] >> y) & 15u) << 4);
+    }
+    // the pattern of the reflected window: the nibbles swapped
+    static __device__ __forceinline__ uint32_t mirrored(uint32_t q) { return (q >> 4) | ((q & 15u) << 4); }
+};
+static_assert(Shape2x4::kCounterBase + kCounters == TPL_NTUPLE_ENTRIES, "the table layout of include/tpl_learn.h");
+
+struct Shape3x3 {
+    static constexpr int kWindowCols = 3, kWindowRows = 3;
+    static constexpr int kTupleCols = tpl::kCols - 2;         // x = 0..7: columns x, x + 1 and x + 2
+    static constexpr int kTupleRows = tpl::kRows - 2;         // y = 0..17: rows y .. y + 2
+    static constexpr int kTuples = kTupleCols * kTupleRows;   // 144
+    static constexpr int kPatterns = 512;
+    static constexpr int kPieceStride = kTuples * kPatterns;
+    static constexpr int kCounterBase = 8 * kPieceStride;     // 589,824
+    // the pattern of tuple (x, y): the three columns' triplets at row y
+    static __device__ __forceinline__ uint32_t pattern(const uint32_t (&c)[tpl::kCols], int x, uint32_t y) {
+        return ((c[x] >> y) & 7u) | (((c[x + 1] >> y) & 7u) << 3) | (((c[x + 2] >> y) & 7u) << 6);
+    }
+    // the pattern of the reflected window: the outer triplets swapped, the middle one stays
+    static __device__ __forceinline__ uint32_t mirrored(uint32_t q) { return (q >> 6) | (q & 0x38u) | ((q & 7u) << 6); }
+};
+static_assert(Shape3x3::kCounterBase + kCounters == TPL_NTUPLE_ENTRIES_3X3, "the table layout of include/tpl_learn.h");
 
 constexpr int kStateBlock = 256;                              // value and update: a lane per state
 constexpr int kBoardsPerBlock = 8;
@@ -74,49 +112,49 @@ __device__ __forceinline__ uint32_t counter_index(uint32_t L, uint32_t M, uint32
     return (uint32_t)(left_l * kCounterMoves + left_m);
 }
 
-// the pattern of tuple (x, y) given the two columns' nibbles at row y
-__device__ __forceinline__ uint32_t pattern(uint32_t c_left, uint32_t c_right, uint32_t y) {
-    return ((c_left >> y) & 15u) | (((c_right >> y) & 15u) << 4);
-}
-
-// entry `index` of the table through a 32-bit byte offset from the (uniform) base: the whole table is 1.2 MB, and an index the
-// compiler has to widen costs a 64-bit shift and a 64-bit add per look-up
+// entry `index` of the table through a 32-bit byte offset from the (uniform) base: the largest buffer, a 3 x 3 coherence buffer, is 9.5 MB, and an
+// index the compiler has to widen costs a 64-bit shift and a 64-bit add per look-up
 template <typename T>
 __device__ __forceinline__ T* entry(T* table, uint32_t index) {
     return (T*)((const char*)table + index * (uint32_t)sizeof(T));
 }
 
-// The index of pattern q of tuple (x, y) among the rows of the piece that start at `base`, a multiple of 256: the row, then q
-// in its low eight bits.  | q and not + q: the sum is the same, but as a function's + the compiler reassociates it and then
+// The index of pattern q of tuple (x, y) among the rows of the piece that start at `base`, a multiple of kPatterns: the row,
+// then q in its low eight (3 x 3: nine) bits.  | q and not + q: the sum is the same, but as a function's + the compiler reassociates it and then
 // addresses the gathers with 64-bit adds (172 vector instructions for 156 in ntuple_value_kernel).
-static_assert(kPatterns == 256 && kPieceStride % kPatterns == 0, "a row's index has its low eight bits clear");
+template <typename S>
 __device__ __forceinline__ uint32_t tuple_entry(uint32_t base, int x, uint32_t y, uint32_t q) {
-    return (base + ((uint32_t)(x * kTupleRows) + y) * (uint32_t)kPatterns) | q;
+    static_assert((S::kPatterns & (S::kPatterns - 1)) == 0 && S::kPatterns == 1 << (S::kWindowCols * S::kWindowRows) &&
+                      S::kPieceStride % S::kPatterns == 0,
+                  "a row's index has the pattern's low bits clear");
+    return (base + ((uint32_t)(x * S::kTupleRows) + y) * (uint32_t)S::kPatterns) | q;
 }
 
 // The integer value of a running board with column words c (bits 20.. clear), falling piece `piece` and counter entry k: the
 // sum over the tuples with a non-zero pattern plus the counter, exact in 64 bits.
+template <typename S>
 __device__ __forceinline__ long long ntuple_sum(const uint32_t (&c)[tpl::kCols], uint32_t piece, uint32_t k, const int32_t* table) {
-    const uint32_t base = piece * (uint32_t)kPieceStride;
-    long long sum = *entry(table, (uint32_t)kCounterBase + k);
+    const uint32_t base = piece * (uint32_t)S::kPieceStride;
+    long long sum = *entry(table, (uint32_t)S::kCounterBase + k);
 #pragma unroll 1
-    for (uint32_t y = 0; y < (uint32_t)kTupleRows; ++y) {
-        int32_t v[kTupleCols];
+    for (uint32_t y = 0; y < (uint32_t)S::kTupleRows; ++y) {
+        int32_t v[S::kTupleCols];
 #pragma unroll
-        for (int x = 0; x < kTupleCols; ++x) {
-            const uint32_t q = pattern(c[x], c[x + 1], y);
-            const int32_t e = *entry(table, tuple_entry(base, x, y, q));
+        for (int x = 0; x < S::kTupleCols; ++x) {
+            const uint32_t q = S::pattern(c, x, y);
+            const int32_t e = *entry(table, tuple_entry<S>(base, x, y, q));
             v[x] = q ? e : 0;
         }
 #pragma unroll
-        for (int x = 0; x < kTupleCols; ++x) sum += v[x];
+        for (int x = 0; x < S::kTupleCols; ++x) sum += v[x];
     }
     return sum;
 }
 
 // V of a state that runs: one rounding from the 64-bit sum to float32, then an exact scaling by 2^-16
+template <typename S>
 __device__ __forceinline__ float ntuple_value(const tpl::Board& s, uint32_t L, uint32_t M, const int32_t* table) {
-    const long long sum = ntuple_sum(s.c, s.window & 7u, counter_index(L, M, s.lines, s.moves), table);
+    const long long sum = ntuple_sum<S>(s.c, s.window & 7u, counter_index(L, M, s.lines, s.moves), table);
     return (float)sum * 0x1p-16f;
 }
 
@@ -125,19 +163,23 @@ struct ValueArgs {
     const uint4* b;
     uint32_t n;
     uint32_t L, M;
-    const int32_t* table;        // [TPL_NTUPLE_ENTRIES]
+    const int32_t* table;        // [the shape's entries]
     float* value;                // [n]
 };
 
-__global__ __launch_bounds__(kStateBlock) void ntuple_value_kernel(const ValueArgs p) {
+template <typename S>
+__device__ __forceinline__ void value_lane(const ValueArgs& p) {
     const uint32_t i = blockIdx.x * kStateBlock + threadIdx.x;
     if (i >= p.n) return;
     tpl::Board s;
     tpl::unpack_board(p.a[i], p.b[i], s);
     float v = 0.0f;
-    if (s.state == tpl::ST_RUNNING) v = ntuple_value(s, p.L, p.M, p.table);
+    if (s.state == tpl::ST_RUNNING) v = ntuple_value<S>(s, p.L, p.M, p.table);
     p.value[i] = v;
 }
+
+__global__ __launch_bounds__(kStateBlock) void ntuple_value_kernel(const ValueArgs p) { value_lane<Shape2x4>(p); }
+__global__ __launch_bounds__(kStateBlock) void ntuple3_value_kernel(const ValueArgs p) { value_lane<Shape3x3>(p); }
 
 // d = (int32) rint(rate * e): the product rounded once, clamped to +-2^24, 0 for a NaN
 __device__ __forceinline__ int32_t update_step(float rate, float e) {
@@ -151,7 +193,7 @@ struct TraceArgs {
     const uint4* b;
     uint32_t n, slots, head;     // slots * n below 2^31 / 40: every index and byte offset fits 32 bits
     uint32_t L, M;
-    uint32_t* table;             // [TPL_NTUPLE_ENTRIES]: added to, never read
+    uint32_t* table;             // [the shape's entries]: added to, never read
     const float* error;          // [n]
     float rate, decay;
 };
@@ -160,8 +202,8 @@ constexpr uint32_t kPieceMirror = 0x76453120u;                // pi = [0, 2, 1, 
 
 // Age blockIdx.y of the boards blockIdx.x * 256 ..: d = update_step(rate * decay^age, e) on the state of that age, where it
 // and every younger state of the board run.  The weight is `age` rounded multiplies on a block-uniform value, as the rule has it.
-template <bool kSymmetric>
-__global__ __launch_bounds__(kStateBlock) void ntuple_trace_kernel(const TraceArgs p) {
+template <typename S, bool kSymmetric>
+__device__ __forceinline__ void trace_lane(const TraceArgs p) {
     __shared__ uint32_t s_counter[kCounters];
 #pragma unroll
     for (int t = threadIdx.x; t < kCounters; t += kStateBlock) s_counter[t] = 0u;
@@ -185,18 +227,18 @@ __global__ __launch_bounds__(kStateBlock) void ntuple_trace_kernel(const TraceAr
             if (s.state == tpl::ST_RUNNING) {
                 atomicAdd(&s_counter[counter_index(p.L, p.M, s.lines, s.moves)], d);      // once, symmetric or not
                 const uint32_t piece = s.window & 7u;
-                const uint32_t base = piece * (uint32_t)kPieceStride;
-                const uint32_t mirror_base = ((kPieceMirror >> (4u * piece)) & 7u) * (uint32_t)kPieceStride;
+                const uint32_t base = piece * (uint32_t)S::kPieceStride;
+                const uint32_t mirror_base = ((kPieceMirror >> (4u * piece)) & 7u) * (uint32_t)S::kPieceStride;
 #pragma unroll 1
-                for (uint32_t y = 0; y < (uint32_t)kTupleRows; ++y) {
+                for (uint32_t y = 0; y < (uint32_t)S::kTupleRows; ++y) {
 #pragma unroll
-                    for (int x = 0; x < kTupleCols; ++x) {
-                        const uint32_t q = pattern(s.c[x], s.c[x + 1], y);
+                    for (int x = 0; x < S::kTupleCols; ++x) {
+                        const uint32_t q = S::pattern(s.c, x, y);
                         if (q) {
-                            atomicAdd(entry(p.table, tuple_entry(base, x, y, q)), d);
+                            atomicAdd(entry(p.table, tuple_entry<S>(base, x, y, q)), d);
                             if constexpr (kSymmetric) {                 // both adds, also where the two entries are one
-                                const uint32_t swapped = (q >> 4) | ((q & 15u) << 4);
-                                atomicAdd(entry(p.table, tuple_entry(mirror_base, kTupleCols - 1 - x, y, swapped)), d);
+                                const uint32_t swapped = S::mirrored(q);
+                                atomicAdd(entry(p.table, tuple_entry<S>(mirror_base, S::kTupleCols - 1 - x, y, swapped)), d);
                             }
                         }
                     }
@@ -208,9 +250,14 @@ __global__ __launch_bounds__(kStateBlock) void ntuple_trace_kernel(const TraceAr
 #pragma unroll
     for (int t = threadIdx.x; t < kCounters; t += kStateBlock) {
         const uint32_t sum = s_counter[t];
-        if (sum) atomicAdd(p.table + kCounterBase + t, sum);
+        if (sum) atomicAdd(p.table + S::kCounterBase + t, sum);
     }
 }
+
+template <bool kSymmetric>
+__global__ __launch_bounds__(kStateBlock) void ntuple_trace_kernel(const TraceArgs p) { trace_lane<Shape2x4, kSymmetric>(p); }
+template <bool kSymmetric>
+__global__ __launch_bounds__(kStateBlock) void ntuple3_trace_kernel(const TraceArgs p) { trace_lane<Shape3x3, kSymmetric>(p); }
 
 // ---- the coherent update: tpl_ntuple_update_coherent ----
 // Two kernels in ntuple_trace_kernel's frame (a lane per (board, age), the age in blockIdx.y): the step kernel reads the coherence
@@ -219,7 +266,7 @@ __global__ __launch_bounds__(kStateBlock) void ntuple_trace_kernel(const TraceAr
 
 struct CoherentArgs {
     TraceArgs t;
-    longlong2* coherence;        // [TPL_NTUPLE_ENTRIES]: x = E, the signed sum; y = A, the absolute sum
+    longlong2* coherence;        // [the shape's entries]: x = E, the signed sum; y = A, the absolute sum
 };
 
 // What a lane of either kernel does before its walk, ntuple_trace_kernel's lines: the decayed rate of the block's age, the younger
@@ -246,32 +293,32 @@ __device__ __forceinline__ bool coherent_lane(const TraceArgs& p, float& rate, f
 }
 
 // The walk over the tuple entries of a running state: apply(j, gather(j)) for every tuple with a non-zero pattern and, with
-// kSymmetric, for its sigma-image as well -- both, also where the two are one entry.  gather(j) is made for all nine tuples of a
-// row before the first apply and also where the pattern is empty (the index is in bounds), so that what it loads is in flight
+// kSymmetric, for its sigma-image as well -- both, also where the two are one entry.  gather(j) is made for all nine (3 x 3: eight) tuples
+// of a row before the first apply and also where the pattern is empty (the index is in bounds), so that what it loads is in flight
 // nine (eighteen) at a time and stays straight-line code; an action that loads nothing returns an empty struct.
-template <bool kSymmetric, typename Gather, typename Apply>
+template <typename S, bool kSymmetric, typename Gather, typename Apply>
 __device__ __forceinline__ void walk_entries(const tpl::Board& s, Gather&& gather, Apply&& apply) {
     const uint32_t piece = s.window & 7u;
-    const uint32_t base = piece * (uint32_t)kPieceStride;
-    const uint32_t mirror_base = ((kPieceMirror >> (4u * piece)) & 7u) * (uint32_t)kPieceStride;
+    const uint32_t base = piece * (uint32_t)S::kPieceStride;
+    const uint32_t mirror_base = ((kPieceMirror >> (4u * piece)) & 7u) * (uint32_t)S::kPieceStride;
     using G = decltype(gather(0u));
 #pragma unroll 1
-    for (uint32_t y = 0; y < (uint32_t)kTupleRows; ++y) {
-        uint32_t j[kTupleCols], jm[kTupleCols];
-        G g[kTupleCols], gm[kTupleCols];
+    for (uint32_t y = 0; y < (uint32_t)S::kTupleRows; ++y) {
+        uint32_t j[S::kTupleCols], jm[S::kTupleCols];
+        G g[S::kTupleCols], gm[S::kTupleCols];
 #pragma unroll
-        for (int x = 0; x < kTupleCols; ++x) {
-            const uint32_t q = pattern(s.c[x], s.c[x + 1], y);
-            j[x] = tuple_entry(base, x, y, q);
+        for (int x = 0; x < S::kTupleCols; ++x) {
+            const uint32_t q = S::pattern(s.c, x, y);
+            j[x] = tuple_entry<S>(base, x, y, q);
             g[x] = gather(j[x]);
             if constexpr (kSymmetric) {
-                jm[x] = tuple_entry(mirror_base, kTupleCols - 1 - x, y, (q >> 4) | ((q & 15u) << 4));
+                jm[x] = tuple_entry<S>(mirror_base, S::kTupleCols - 1 - x, y, S::mirrored(q));
                 gm[x] = gather(jm[x]);
             }
         }
 #pragma unroll
-        for (int x = 0; x < kTupleCols; ++x) {
-            if (j[x] & 255u) {                                          // the pattern, in the index's low eight bits
+        for (int x = 0; x < S::kTupleCols; ++x) {
+            if (j[x] & (uint32_t)(S::kPatterns - 1)) {                  // the pattern, in the index's low bits
                 apply(j[x], g[x]);
                 if constexpr (kSymmetric) apply(jm[x], gm[x]);
             }
@@ -294,8 +341,8 @@ __device__ __forceinline__ uint32_t coherent_step(float rate, const longlong2 c,
 
 // The step phase.  The counter entries are summed per block in LDS first, as in ntuple_trace_kernel; 32 bits are enough here,
 // since the table's own adds wrap in 32 bits.
-template <bool kSymmetric>
-__global__ __launch_bounds__(kStateBlock) void ntuple_coherent_step_kernel(const CoherentArgs p) {
+template <typename S, bool kSymmetric>
+__device__ __forceinline__ void coherent_step_lane(const CoherentArgs p) {
     __shared__ uint32_t s_counter[kCounters];
 #pragma unroll
     for (int t = threadIdx.x; t < kCounters; t += kStateBlock) s_counter[t] = 0u;
@@ -305,8 +352,8 @@ __global__ __launch_bounds__(kStateBlock) void ntuple_coherent_step_kernel(const
     int32_t d;
     if (coherent_lane(p.t, rate, e, d, s)) {
         const uint32_t k = counter_index(p.t.L, p.t.M, s.lines, s.moves);
-        atomicAdd(&s_counter[k], coherent_step(rate, *entry(p.coherence, (uint32_t)kCounterBase + k), e));
-        walk_entries<kSymmetric>(
+        atomicAdd(&s_counter[k], coherent_step(rate, *entry(p.coherence, (uint32_t)S::kCounterBase + k), e));
+        walk_entries<S, kSymmetric>(
             s, [&](uint32_t j) { return *entry(p.coherence, j); },
             [&](uint32_t j, const longlong2 c) {
                 const uint32_t step = coherent_step(rate, c, e);
@@ -317,16 +364,25 @@ __global__ __launch_bounds__(kStateBlock) void ntuple_coherent_step_kernel(const
 #pragma unroll
     for (int t = threadIdx.x; t < kCounters; t += kStateBlock) {
         const uint32_t sum = s_counter[t];
-        if (sum) atomicAdd(p.t.table + kCounterBase + t, sum);
+        if (sum) atomicAdd(p.t.table + S::kCounterBase + t, sum);
     }
+}
+
+template <bool kSymmetric>
+__global__ __launch_bounds__(kStateBlock) void ntuple_coherent_step_kernel(const CoherentArgs p) {
+    coherent_step_lane<Shape2x4, kSymmetric>(p);
+}
+template <bool kSymmetric>
+__global__ __launch_bounds__(kStateBlock) void ntuple3_coherent_step_kernel(const CoherentArgs p) {
+    coherent_step_lane<Shape3x3, kSymmetric>(p);
 }
 
 struct Nothing {};
 
 // The accumulate phase: E += d and A += |d|, wrapping in 64 bits.  The counters' sums are 64 bits wide in LDS as well: 256 lanes
 // of 2^24 each do not fit 32, and E and A do not wrap there.
-template <bool kSymmetric>
-__global__ __launch_bounds__(kStateBlock) void ntuple_coherent_accumulate_kernel(const CoherentArgs p) {
+template <typename S, bool kSymmetric>
+__device__ __forceinline__ void coherent_accumulate_lane(const CoherentArgs p) {
     __shared__ unsigned long long s_signed[kCounters], s_absolute[kCounters];
 #pragma unroll
     for (int t = threadIdx.x; t < kCounters; t += kStateBlock) s_signed[t] = s_absolute[t] = 0ull;
@@ -341,7 +397,7 @@ __global__ __launch_bounds__(kStateBlock) void ntuple_coherent_accumulate_kernel
         const uint32_t k = counter_index(p.t.L, p.t.M, s.lines, s.moves);
         atomicAdd(&s_signed[k], signed_d);
         atomicAdd(&s_absolute[k], absolute_d);
-        walk_entries<kSymmetric>(
+        walk_entries<S, kSymmetric>(
             s, [](uint32_t) { return Nothing{}; },
             [&](uint32_t j, Nothing) {
                 atomicAdd(entry(sums, 2u * j), signed_d);
@@ -352,9 +408,18 @@ __global__ __launch_bounds__(kStateBlock) void ntuple_coherent_accumulate_kernel
 #pragma unroll
     for (int t = threadIdx.x; t < kCounters; t += kStateBlock) {
         const unsigned long long sum = s_signed[t], absolute = s_absolute[t];
-        if (sum) atomicAdd(sums + 2 * (kCounterBase + t), sum);
-        if (absolute) atomicAdd(sums + 2 * (kCounterBase + t) + 1, absolute);
+        if (sum) atomicAdd(sums + 2 * (S::kCounterBase + t), sum);
+        if (absolute) atomicAdd(sums + 2 * (S::kCounterBase + t) + 1, absolute);
     }
+}
+
+template <bool kSymmetric>
+__global__ __launch_bounds__(kStateBlock) void ntuple_coherent_accumulate_kernel(const CoherentArgs p) {
+    coherent_accumulate_lane<Shape2x4, kSymmetric>(p);
+}
+template <bool kSymmetric>
+__global__ __launch_bounds__(kStateBlock) void ntuple3_coherent_accumulate_kernel(const CoherentArgs p) {
+    coherent_accumulate_lane<Shape3x3, kSymmetric>(p);
 }
 
 struct ActArgs {
@@ -379,7 +444,7 @@ constexpr uint32_t kGreedy = 0xFFFFFFFFu;
 // game running is worth beyond its reward is the one thing that differs: V of the board it left at one ply, best_second's W at
 // two.  At two plies V of the afterstate is not on the way to the score, so the one chosen lane of a board sums it afterwards,
 // and only where `value` is asked for.
-template <int kDepth>
+template <typename S, int kDepth>
 __device__ __forceinline__ void ntuple_policy(const ActArgs& p, uint8_t* second_out) {
     __shared__ tpl::ShapeWord s_shape[32];
     __shared__ unsigned long long s_best[kBoardsPerBlock];
@@ -424,13 +489,13 @@ __device__ __forceinline__ void ntuple_policy(const ActArgs& p, uint8_t* second_
                 tpl::next_window(s2, false, 0);                         // the piece after the next: the original window entry 2
                 const bool on = s2.state == tpl::ST_RUNNING;
                 float v2 = 0.0f;
-                if (on) v2 = ntuple_value(s2, p.L, p.M, p.table);
+                if (on) v2 = ntuple_value<S>(s2, p.L, p.M, p.table);
                 const float reward = move_reward(p.r_line, p.r_win, p.r_lose, n2, s2.state);
                 const float later = p.gamma * v2;
                 return on ? reward + later : reward;
             });
     } else {
-        if (contends && goes_on) v = ntuple_value(s1, p.L, p.M, p.table);
+        if (contends && goes_on) v = ntuple_value<S>(s1, p.L, p.M, p.table);
     }
     float score;
     {
@@ -449,7 +514,7 @@ __device__ __forceinline__ void ntuple_policy(const ActArgs& p, uint8_t* second_
     if constexpr (kDepth == 2) {
         if (p.value) {                                                  // uniform; v was W, the second ply's, until here
             v = 0.0f;
-            if (chosen && goes_on) v = ntuple_value(s1, p.L, p.M, p.table);
+            if (chosen && goes_on) v = ntuple_value<S>(s1, p.L, p.M, p.table);
         }
     }
     if (chosen) {
@@ -473,8 +538,17 @@ struct SearchArgs {
     uint8_t* second;             // [n], optional: the second placement behind the action played, 255 where there is none
 };
 
-__global__ __launch_bounds__(kActBlock) void ntuple_act_kernel(const ActArgs p) { ntuple_policy<1>(p, nullptr); }
-__global__ __launch_bounds__(kActBlock) void ntuple_search_kernel(const SearchArgs p) { ntuple_policy<2>(p.act, p.second); }
+__global__ __launch_bounds__(kActBlock) void ntuple_act_kernel(const ActArgs p) { ntuple_policy<Shape2x4, 1>(p, nullptr); }
+__global__ __launch_bounds__(kActBlock) void ntuple_search_kernel(const SearchArgs p) { ntuple_policy<Shape2x4, 2>(p.act, p.second); }
+__global__ __launch_bounds__(kActBlock) void ntuple3_act_kernel(const ActArgs p) { ntuple_policy<Shape3x3, 1>(p, nullptr); }
+__global__ __launch_bounds__(kActBlock) void ntuple3_search_kernel(const SearchArgs p) { ntuple_policy<Shape3x3, 2>(p.act, p.second); }
+
+// a shape the library does not know is refused first, before any pointer is looked at
+int check_shape(const char* name, int32_t shape) {
+    if (shape != TPL_NTUPLE_SHAPE_2X4 && shape != TPL_NTUPLE_SHAPE_3X3)
+        return fail_msg(TPL_ERR_ARG, "%s: shape must be TPL_NTUPLE_SHAPE_2X4 (0) or TPL_NTUPLE_SHAPE_3X3 (1), got %d", name, (int)shape);
+    return TPL_OK;
+}
 
 // the checks the three entries share beyond check_planes
 int check_table(const char* name, const void* table) {
@@ -488,9 +562,18 @@ int check_table(const char* name, const void* table) {
 
 using namespace tpl_learn;
 
-extern "C" int tpl_ntuple_value(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const int32_t* table,
-                                float* value, void* stream) {
-    const char* name = "tpl_ntuple_value";
+extern "C" int64_t tpl_ntuple_entries(int32_t shape) {
+    if (shape == TPL_NTUPLE_SHAPE_2X4) return TPL_NTUPLE_ENTRIES;
+    if (shape == TPL_NTUPLE_SHAPE_3X3) return TPL_NTUPLE_ENTRIES_3X3;
+    return -1;
+}
+
+namespace {
+
+// what tpl_ntuple_value and tpl_ntuple_value_shaped share: the checks and the launch
+int launch_value(const char* name, const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const int32_t* table,
+                 float* value, int32_t shape, void* stream) {
+    if (const int rc = check_shape(name, shape)) return rc;
     if (const int rc = check_planes(name, plane_a, plane_b, n, L, M)) return rc;
     if (const int rc = check_table(name, table)) return rc;
     if (!value) return fail_msg(TPL_ERR_ARG, "%s: null pointer (value is required)", name);
@@ -499,18 +582,19 @@ extern "C" int tpl_ntuple_value(const void* plane_a, const void* plane_b, int64_
     p.a = (const uint4*)plane_a; p.b = (const uint4*)plane_b; p.n = (uint32_t)n;
     p.L = (uint32_t)L; p.M = (uint32_t)M; p.table = table; p.value = value;
     const dim3 grid((p.n + kStateBlock - 1) / kStateBlock), block(kStateBlock);
-    hipLaunchKernelGGL(ntuple_value_kernel, grid, block, 0, (hipStream_t)stream, p);
+    if (shape == TPL_NTUPLE_SHAPE_3X3) hipLaunchKernelGGL(ntuple3_value_kernel, grid, block, 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(ntuple_value_kernel, grid, block, 0, (hipStream_t)stream, p);
     TPL_LEARN_HIP(hipGetLastError());
     return TPL_OK;
 }
 
-namespace {
-
-// what tpl_ntuple_act (depth = 1, second = null) and tpl_ntuple_search (depth = 2) share: the checks and the launch
+// what tpl_ntuple_act (depth = 1, second = null) and tpl_ntuple_search (depth = 2) and their _shaped twins share: the checks
+// and the launch
 int launch_ntuple_policy(const char* name, int depth, const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M,
                          float r_line, float r_win, float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed,
                          uint64_t step, uint8_t* action, uint8_t* second, float* score, void* after_a, void* after_b, float* value,
-                         void* stream) {
+                         int32_t shape, void* stream) {
+    if (const int rc = check_shape(name, shape)) return rc;
     if (const int rc = check_planes(name, plane_a, plane_b, n, L, M)) return rc;
     if (const int rc = check_table(name, table)) return rc;
     if (!action) return fail_msg(TPL_ERR_ARG, "%s: null pointer (action is required)", name);
@@ -529,19 +613,45 @@ int launch_ntuple_policy(const char* name, int depth, const void* plane_a, const
     p.key = replay_key(seed, step);
     p.action = action; p.score = score; p.after_a = (uint4*)after_a; p.after_b = (uint4*)after_b; p.value = value;
     const dim3 grid((p.n + kBoardsPerBlock - 1) / kBoardsPerBlock), block(kActBlock);
-    if (depth == 2) hipLaunchKernelGGL(ntuple_search_kernel, grid, block, 0, (hipStream_t)stream, SearchArgs{p, second});
-    else hipLaunchKernelGGL(ntuple_act_kernel, grid, block, 0, (hipStream_t)stream, p);
+    const bool wide = shape == TPL_NTUPLE_SHAPE_3X3;
+    if (depth == 2) {
+        const SearchArgs q{p, second};
+        if (wide) hipLaunchKernelGGL(ntuple3_search_kernel, grid, block, 0, (hipStream_t)stream, q);
+        else hipLaunchKernelGGL(ntuple_search_kernel, grid, block, 0, (hipStream_t)stream, q);
+    } else if (wide) {
+        hipLaunchKernelGGL(ntuple3_act_kernel, grid, block, 0, (hipStream_t)stream, p);
+    } else {
+        hipLaunchKernelGGL(ntuple_act_kernel, grid, block, 0, (hipStream_t)stream, p);
+    }
     TPL_LEARN_HIP(hipGetLastError());
     return TPL_OK;
 }
 
 }  // namespace
 
+extern "C" int tpl_ntuple_value(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const int32_t* table,
+                                float* value, void* stream) {
+    return launch_value("tpl_ntuple_value", plane_a, plane_b, n, L, M, table, value, TPL_NTUPLE_SHAPE_2X4, stream);
+}
+
+extern "C" int tpl_ntuple_value_shaped(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M,
+                                       const int32_t* table, float* value, int32_t shape, void* stream) {
+    return launch_value("tpl_ntuple_value_shaped", plane_a, plane_b, n, L, M, table, value, shape, stream);
+}
+
 extern "C" int tpl_ntuple_act(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line, float r_win,
                               float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed, uint64_t step,
                               uint8_t* action, float* score, void* after_a, void* after_b, float* value, void* stream) {
     return launch_ntuple_policy("tpl_ntuple_act", 1, plane_a, plane_b, n, L, M, r_line, r_win, r_lose, gamma, table, epsilon, seed,
-                                step, action, nullptr, score, after_a, after_b, value, stream);
+                                step, action, nullptr, score, after_a, after_b, value, TPL_NTUPLE_SHAPE_2X4, stream);
+}
+
+extern "C" int tpl_ntuple_act_shaped(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line,
+                                     float r_win, float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed,
+                                     uint64_t step, uint8_t* action, float* score, void* after_a, void* after_b, float* value,
+                                     int32_t shape, void* stream) {
+    return launch_ntuple_policy("tpl_ntuple_act_shaped", 1, plane_a, plane_b, n, L, M, r_line, r_win, r_lose, gamma, table, epsilon,
+                                seed, step, action, nullptr, score, after_a, after_b, value, shape, stream);
 }
 
 extern "C" int tpl_ntuple_search(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line,
@@ -549,14 +659,23 @@ extern "C" int tpl_ntuple_search(const void* plane_a, const void* plane_b, int64
                                  uint64_t step, uint8_t* action, uint8_t* second, float* score, void* after_a, void* after_b,
                                  float* value, void* stream) {
     return launch_ntuple_policy("tpl_ntuple_search", 2, plane_a, plane_b, n, L, M, r_line, r_win, r_lose, gamma, table, epsilon,
-                                seed, step, action, second, score, after_a, after_b, value, stream);
+                                seed, step, action, second, score, after_a, after_b, value, TPL_NTUPLE_SHAPE_2X4, stream);
+}
+
+extern "C" int tpl_ntuple_search_shaped(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line,
+                                        float r_win, float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed,
+                                        uint64_t step, uint8_t* action, uint8_t* second, float* score, void* after_a, void* after_b,
+                                        float* value, int32_t shape, void* stream) {
+    return launch_ntuple_policy("tpl_ntuple_search_shaped", 2, plane_a, plane_b, n, L, M, r_line, r_win, r_lose, gamma, table,
+                                epsilon, seed, step, action, second, score, after_a, after_b, value, shape, stream);
 }
 
 namespace {
 
 // what the three updates refuse alike; `coherence`: where the entry takes a coherence buffer, the address of its pointer
-int check_update(const char* name, const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const int32_t* table,
-                 const float* error, float rate, const int64_t* const* coherence = nullptr) {
+int check_update(const char* name, int32_t shape, const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M,
+                 const int32_t* table, const float* error, float rate, const int64_t* const* coherence = nullptr) {
+    if (const int rc = check_shape(name, shape)) return rc;
     if (const int rc = check_planes(name, plane_a, plane_b, n, L, M)) return rc;
     if (const int rc = check_table(name, table)) return rc;
     if (coherence && !*coherence) return fail_msg(TPL_ERR_ARG, "%s: null pointer (coherence is required)", name);
@@ -568,25 +687,30 @@ int check_update(const char* name, const void* plane_a, const void* plane_b, int
 }
 
 // what the three updates share beyond check_update: the arguments and the launch, an age of the ring per grid row
-// `coherence` null: ntuple_trace_kernel; otherwise the two phases of the coherent update, one after the other on the stream
-int launch_update(const void* ring_a, const void* ring_b, int64_t n, int32_t slots, int32_t head, int32_t horizon, int32_t L,
-                  int32_t M, int32_t* table, const float* error, float rate, float decay, bool symmetric, void* stream,
+// `coherence` null: the trace kernel; otherwise the two phases of the coherent update, one after the other on the stream
+int launch_update(int32_t shape, const void* ring_a, const void* ring_b, int64_t n, int32_t slots, int32_t head, int32_t horizon,
+                  int32_t L, int32_t M, int32_t* table, const float* error, float rate, float decay, bool symmetric, void* stream,
                   int64_t* coherence = nullptr) {
     TraceArgs p{};
     p.a = (const uint4*)ring_a; p.b = (const uint4*)ring_b; p.n = (uint32_t)n; p.slots = (uint32_t)slots; p.head = (uint32_t)head;
     p.L = (uint32_t)L; p.M = (uint32_t)M; p.table = (uint32_t*)table; p.error = error; p.rate = rate; p.decay = decay;
     const dim3 grid((p.n + kStateBlock - 1) / kStateBlock, (uint32_t)horizon), block(kStateBlock);
+    const bool wide = shape == TPL_NTUPLE_SHAPE_3X3;
     if (coherence) {
         const CoherentArgs c{p, (longlong2*)coherence};
-        if (symmetric) hipLaunchKernelGGL(ntuple_coherent_step_kernel<true>, grid, block, 0, (hipStream_t)stream, c);
-        else hipLaunchKernelGGL(ntuple_coherent_step_kernel<false>, grid, block, 0, (hipStream_t)stream, c);
+        auto step = symmetric ? ntuple_coherent_step_kernel<true> : ntuple_coherent_step_kernel<false>;
+        auto accumulate = symmetric ? ntuple_coherent_accumulate_kernel<true> : ntuple_coherent_accumulate_kernel<false>;
+        if (wide) {
+            step = symmetric ? ntuple3_coherent_step_kernel<true> : ntuple3_coherent_step_kernel<false>;
+            accumulate = symmetric ? ntuple3_coherent_accumulate_kernel<true> : ntuple3_coherent_accumulate_kernel<false>;
+        }
+        hipLaunchKernelGGL(step, grid, block, 0, (hipStream_t)stream, c);
         TPL_LEARN_HIP(hipGetLastError());
-        if (symmetric) hipLaunchKernelGGL(ntuple_coherent_accumulate_kernel<true>, grid, block, 0, (hipStream_t)stream, c);
-        else hipLaunchKernelGGL(ntuple_coherent_accumulate_kernel<false>, grid, block, 0, (hipStream_t)stream, c);
-    } else if (symmetric) {
-        hipLaunchKernelGGL(ntuple_trace_kernel<true>, grid, block, 0, (hipStream_t)stream, p);
+        hipLaunchKernelGGL(accumulate, grid, block, 0, (hipStream_t)stream, c);
     } else {
-        hipLaunchKernelGGL(ntuple_trace_kernel<false>, grid, block, 0, (hipStream_t)stream, p);
+        auto trace = symmetric ? ntuple_trace_kernel<true> : ntuple_trace_kernel<false>;
+        if (wide) trace = symmetric ? ntuple3_trace_kernel<true> : ntuple3_trace_kernel<false>;
+        hipLaunchKernelGGL(trace, grid, block, 0, (hipStream_t)stream, p);
     }
     TPL_LEARN_HIP(hipGetLastError());
     return TPL_OK;
@@ -605,29 +729,61 @@ int check_ring(const char* name, int64_t n, int32_t slots, int32_t head, int32_t
     return TPL_OK;
 }
 
+// the planes are a ring of one slot: age 0 alone, whose weight is decay^0 = 1 whatever the decay
+int update_planes(const char* name, const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, int32_t* table,
+                  const float* error, float rate, int32_t shape, void* stream) {
+    if (const int rc = check_update(name, shape, plane_a, plane_b, n, L, M, table, error, rate)) return rc;
+    return launch_update(shape, plane_a, plane_b, n, 1, 0, 1, L, M, table, error, rate, 0.0f, false, stream);
+}
+
+int update_ring(const char* name, const void* ring_a, const void* ring_b, int64_t n, int32_t slots, int32_t head, int32_t horizon,
+                int32_t L, int32_t M, int32_t* table, const int64_t* const* coherence, const float* error, float rate, float decay,
+                int32_t symmetric, int32_t shape, void* stream) {
+    if (const int rc = check_update(name, shape, ring_a, ring_b, n, L, M, table, error, rate, coherence)) return rc;
+    if (const int rc = check_ring(name, n, slots, head, horizon, decay)) return rc;
+    return launch_update(shape, ring_a, ring_b, n, slots, head, horizon, L, M, table, error, rate, decay, symmetric != 0, stream,
+                         coherence ? (int64_t*)*coherence : nullptr);
+}
+
 }  // namespace
 
-// the planes are a ring of one slot: age 0 alone, whose weight is decay^0 = 1 whatever the decay
 extern "C" int tpl_ntuple_update(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, int32_t* table,
                                  const float* error, float rate, void* stream) {
-    if (const int rc = check_update("tpl_ntuple_update", plane_a, plane_b, n, L, M, table, error, rate)) return rc;
-    return launch_update(plane_a, plane_b, n, 1, 0, 1, L, M, table, error, rate, 0.0f, false, stream);
+    return update_planes("tpl_ntuple_update", plane_a, plane_b, n, L, M, table, error, rate, TPL_NTUPLE_SHAPE_2X4, stream);
+}
+
+extern "C" int tpl_ntuple_update_shaped(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, int32_t* table,
+                                        const float* error, float rate, int32_t shape, void* stream) {
+    return update_planes("tpl_ntuple_update_shaped", plane_a, plane_b, n, L, M, table, error, rate, shape, stream);
 }
 
 extern "C" int tpl_ntuple_update_trace(const void* ring_a, const void* ring_b, int64_t n, int32_t slots, int32_t head,
                                        int32_t horizon, int32_t L, int32_t M, int32_t* table, const float* error, float rate,
                                        float decay, int32_t symmetric, void* stream) {
-    const char* name = "tpl_ntuple_update_trace";
-    if (const int rc = check_update(name, ring_a, ring_b, n, L, M, table, error, rate)) return rc;
-    if (const int rc = check_ring(name, n, slots, head, horizon, decay)) return rc;
-    return launch_update(ring_a, ring_b, n, slots, head, horizon, L, M, table, error, rate, decay, symmetric != 0, stream);
+    return update_ring("tpl_ntuple_update_trace", ring_a, ring_b, n, slots, head, horizon, L, M, table, nullptr, error, rate, decay,
+                       symmetric, TPL_NTUPLE_SHAPE_2X4, stream);
+}
+
+extern "C" int tpl_ntuple_update_trace_shaped(const void* ring_a, const void* ring_b, int64_t n, int32_t slots, int32_t head,
+                                              int32_t horizon, int32_t L, int32_t M, int32_t* table, const float* error, float rate,
+                                              float decay, int32_t symmetric, int32_t shape, void* stream) {
+    return update_ring("tpl_ntuple_update_trace_shaped", ring_a, ring_b, n, slots, head, horizon, L, M, table, nullptr, error, rate,
+                       decay, symmetric, shape, stream);
 }
 
 extern "C" int tpl_ntuple_update_coherent(const void* ring_a, const void* ring_b, int64_t n, int32_t slots, int32_t head,
                                           int32_t horizon, int32_t L, int32_t M, int32_t* table, int64_t* coherence,
                                           const float* error, float rate, float decay, int32_t symmetric, void* stream) {
-    const char* name = "tpl_ntuple_update_coherent";
-    if (const int rc = check_update(name, ring_a, ring_b, n, L, M, table, error, rate, &coherence)) return rc;
-    if (const int rc = check_ring(name, n, slots, head, horizon, decay)) return rc;
-    return launch_update(ring_a, ring_b, n, slots, head, horizon, L, M, table, error, rate, decay, symmetric != 0, stream, coherence);
+    const int64_t* const given = coherence;
+    return update_ring("tpl_ntuple_update_coherent", ring_a, ring_b, n, slots, head, horizon, L, M, table, &given, error, rate,
+                       decay, symmetric, TPL_NTUPLE_SHAPE_2X4, stream);
+}
+
+extern "C" int tpl_ntuple_update_coherent_shaped(const void* ring_a, const void* ring_b, int64_t n, int32_t slots, int32_t head,
+                                                 int32_t horizon, int32_t L, int32_t M, int32_t* table, int64_t* coherence,
+                                                 const float* error, float rate, float decay, int32_t symmetric, int32_t shape,
+                                                 void* stream) {
+    const int64_t* const given = coherence;
+    return update_ring("tpl_ntuple_update_coherent_shaped", ring_a, ring_b, n, slots, head, horizon, L, M, table, &given, error,
+                       rate, decay, symmetric, shape, stream);
 }

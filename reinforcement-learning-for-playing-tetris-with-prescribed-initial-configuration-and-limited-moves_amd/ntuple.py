@@ -1,7 +1,9 @@
 """A learned evaluation of the board a placement leaves: an n-tuple network on afterstates, trained by temporal-difference
 learning on the device (the rule: include/tpl_learn.h; the kernels: csrc/learn/ntuple.hip).
 
-    ntuple_table(device)          a zeroed table: int32 [314,368], in units of 2^-16
+    ntuple_table(device, shape="2x4")
+                                  a zeroed table: int32 [314,368], in units of 2^-16; shape="3x3": int32 [590,848]
+    ntuple_shape(table)           "2x4" or "3x3", from the table's entry count
     ntuple_value(source, table)   V of every resident board of an environment, or of plane pairs
     NTuplePolicy(env, table, gamma, epsilon, seed, depth=1).act()
                                   arg-max over the distinct placements of  r + gamma * V(afterstate)  in ONE launch; with epsilon a
@@ -10,7 +12,7 @@ learning on the device (the rule: include/tpl_learn.h; the kernels: csrc/learn/n
                                   afterstate of the action played and its value.  depth=2 searches the known next piece as well,
                                   still in one launch:  r + gamma * max_b (r_b + gamma * V)  -- the value of the afterstate itself,
                                   with the table one move further out; act(second=) gives the placement planned for that piece
-    NTupleLearner(env, gamma, rate, epsilon, seed, depth=1, lam=0.0, horizon=1, symmetric=False, coherent=False)
+    NTupleLearner(env, gamma, rate, epsilon, seed, depth=1, lam=0.0, horizon=1, symmetric=False, coherent=False, shape="2x4")
                                   TD(0) on afterstates: train(steps), evaluate(steps, depth=None); `table` is a plain tensor
                                   (torch.save it); a table trained at one depth can be played at the other.  horizon > 1 adds
                                   truncated TD(lambda) traces -- the error also goes, decayed by (gamma lam)^k, to the afterstates
@@ -19,12 +21,15 @@ learning on the device (the rule: include/tpl_learn.h; the kernels: csrc/learn/n
                                   coherent=True gives every entry a step size of its own (temporal coherence): the ratio of the
                                   signed to the absolute sum of the steps it was sent, kept in `coherence`
     ntuple_is_symmetric(table)    whether table[sigma] == table under the mirror permutation of the entries
-    ntuple_coherence(device)      a zeroed coherence buffer: int64 [314,368, 2], the pairs (E, A)
-    ntuple_step_sizes(coherence)  alpha of every entry: float32 [314,368]
+    ntuple_coherence(device, shape="2x4")
+                                  a zeroed coherence buffer: int64 [entries of the shape, 2], the pairs (E, A)
+    ntuple_step_sizes(coherence)  alpha of every entry: float32 [entries]
 
 The value is a sum of table entries, one per 2 x 4 window of the board that is not empty, chosen by the falling piece, plus one
 per (lines left, moves left); the update adds rint(rate * error) to the same entries.  Everything is integer, so two trainings
-with one seed give the same bytes.
+with one seed give the same bytes.  The window is the table's SHAPE: "2x4", two adjacent columns by four rows, or "3x3", three by
+three -- a column with both of its neighbours.  Policy, value, the symmetry test and the step sizes take the shape from the table
+(or buffer) they are given; a table of one shape cannot be played as the other.
 """
 from __future__ import annotations
 
@@ -34,36 +39,51 @@ from typing import Optional
 import torch
 
 from . import _learn_lib
-from ._learn_lib import NTUPLE_ENTRIES, NTUPLE_TRACE_MAX, check
+from ._learn_lib import NTUPLE_ENTRIES, NTUPLE_SHAPE_IDS, NTUPLE_SHAPES, NTUPLE_TRACE_MAX, check
 from .lookahead import _MAX_BOARDS, _boards, _ptr, _state_ptrs
 
-__all__ = ["NTUPLE_ENTRIES", "ntuple_table", "ntuple_value", "ntuple_is_symmetric", "ntuple_coherence", "ntuple_step_sizes",
+__all__ = ["NTUPLE_ENTRIES", "NTUPLE_SHAPES", "ntuple_shape", "ntuple_table", "ntuple_value", "ntuple_is_symmetric", "ntuple_coherence", "ntuple_step_sizes",
            "NTuplePolicy", "NTupleLearner"]
 
 _STATE_WON = 1                                                 # bits 28..29 of B.y: 0 running, 1 won, 2 and 3 lost
 _FINISHED_B_Y = _STATE_WON << 28                               # B.y of a state that is finished and otherwise empty
 
 
-def ntuple_table(device="cuda:0") -> torch.Tensor:
-    """A zeroed n-tuple table on `device`: int32 [NTUPLE_ENTRIES]."""
-    return torch.zeros(NTUPLE_ENTRIES, dtype=torch.int32, device=device)
+def _entries(shape) -> int:
+    if not isinstance(shape, str) or shape not in NTUPLE_SHAPES:
+        raise ValueError(f"shape must be one of {sorted(NTUPLE_SHAPES)}, got {shape!r}")
+    return NTUPLE_SHAPES[shape][2]
 
 
-def ntuple_coherence(device="cuda:0") -> torch.Tensor:
-    """A zeroed coherence buffer on `device`: int64 [NTUPLE_ENTRIES, 2], entry j the pair (E_j, A_j) of include/tpl_learn.h."""
-    return torch.zeros((NTUPLE_ENTRIES, 2), dtype=torch.int64, device=device)
+def ntuple_table(device="cuda:0", shape: str = "2x4") -> torch.Tensor:
+    """A zeroed n-tuple table of `shape` on `device`: int32 [NTUPLE_SHAPES[shape] entries] (2x4: NTUPLE_ENTRIES)."""
+    return torch.zeros(_entries(shape), dtype=torch.int32, device=device)
+
+
+def ntuple_coherence(device="cuda:0", shape: str = "2x4") -> torch.Tensor:
+    """A zeroed coherence buffer of `shape` on `device`: int64 [entries, 2], entry j the pair (E_j, A_j) of include/tpl_learn.h."""
+    return torch.zeros((_entries(shape), 2), dtype=torch.int64, device=device)
+
+
+def ntuple_shape(table) -> str:
+    """"2x4" or "3x3": the shape of a table (or, by its first dimension, of a coherence buffer), from its entry count; a tensor
+    of any other size is refused."""
+    if isinstance(table, torch.Tensor) and table.dim() >= 1:
+        for name, (_, _, entries) in NTUPLE_SHAPES.items():
+            if table.shape[0] == entries:
+                return name
+    sizes = ", ".join(f"{v[2]} ({k})" for k, v in NTUPLE_SHAPES.items())
+    raise ValueError(f"table must be a tensor of {sizes} entries (ntuple_table)")
 
 
 @torch.no_grad()
 def ntuple_step_sizes(coherence: torch.Tensor) -> torch.Tensor:
-    """float32 [NTUPLE_ENTRIES] on the buffer's device: alpha of every entry as tpl_ntuple_update_coherent would read it now -- 1
+    """float32 [the buffer's entries] on the buffer's device: alpha of every entry as tpl_ntuple_update_coherent would read it now -- 1
     where A <= 0, else min(|E| / A, 1) in float32.  torch has no unsigned 64-bit conversion, so the one magnitude a signed
     conversion gets wrong, |INT64_MIN| = 2^63, is put in by a select; the quotient of the two float32 values is taken in float64
     and rounded to float32, which is the float32 quotient rounded once (53 >= 2 * 24 + 2 bits) whatever division torch's float32
     kernels were built with.  No host sync."""
-    if (not isinstance(coherence, torch.Tensor) or coherence.dtype != torch.int64 or tuple(coherence.shape) != (NTUPLE_ENTRIES, 2)
-            or not coherence.is_contiguous()):
-        raise ValueError(f"coherence must be a contiguous int64 tensor of shape ({NTUPLE_ENTRIES}, 2) (ntuple_coherence)")
+    _coherence(coherence)
     e, a = coherence[:, 0], coherence[:, 1]
     lowest = e == torch.iinfo(torch.int64).min
     mag = torch.where(lowest, 2.0 ** 63, e.masked_fill(lowest, 0).abs().to(torch.float32))
@@ -71,11 +91,32 @@ def ntuple_step_sizes(coherence: torch.Tensor) -> torch.Tensor:
     return torch.where(a <= 0, 1.0, ratio).to(torch.float32)
 
 
+def _sizes() -> str:
+    return " or ".join(f"{v[2]} ({k})" for k, v in NTUPLE_SHAPES.items())
+
+
+def _coherence(coherence, table=None) -> torch.Tensor:
+    """A coherence buffer of a shape's entry count -- of `table`'s, where one is given."""
+    counts = [v[2] for v in NTUPLE_SHAPES.values()] if table is None else [int(table.shape[0])]
+    if (not isinstance(coherence, torch.Tensor) or coherence.dtype != torch.int64 or coherence.dim() != 2
+            or coherence.shape[1] != 2 or coherence.shape[0] not in counts or not coherence.is_contiguous()
+            or (table is not None and coherence.device != table.device)):
+        want = _sizes() if table is None else f"{counts[0]}, the table's"
+        raise ValueError(f"coherence must be a contiguous int64 tensor of shape (entries, 2), entries = {want} (ntuple_coherence)")
+    return coherence
+
+
 def _table(table, device) -> torch.Tensor:
-    if (not isinstance(table, torch.Tensor) or table.dtype != torch.int32 or tuple(table.shape) != (NTUPLE_ENTRIES,)
-            or table.device != device or not table.is_contiguous()):
-        raise ValueError(f"table must be a contiguous int32 tensor of {NTUPLE_ENTRIES} entries on {device} (ntuple_table)")
+    if (not isinstance(table, torch.Tensor) or table.dtype != torch.int32 or table.dim() != 1
+            or table.shape[0] not in [v[2] for v in NTUPLE_SHAPES.values()] or table.device != device
+            or not table.is_contiguous()):
+        raise ValueError(f"table must be a contiguous int32 tensor of {_sizes()} entries on {device} (ntuple_table)")
     return table
+
+
+def _shape_id(table) -> int:
+    """The C `shape` of a table that _table accepts."""
+    return NTUPLE_SHAPE_IDS[ntuple_shape(table)]
 
 
 def _unit(name: str, v) -> float:
@@ -123,7 +164,8 @@ def _planes(pair, device, what: str):
 
 def _value(planes_a, planes_b, k: int, L: int, M: int, table, out, device) -> None:
     stream = torch._C._cuda_getCurrentRawStream(device.index)
-    check(_learn_lib.lib().tpl_ntuple_value(_ptr(planes_a), _ptr(planes_b), k, L, M, table.data_ptr(), out.data_ptr(), stream))
+    check(_learn_lib.lib().tpl_ntuple_value_shaped(_ptr(planes_a), _ptr(planes_b), k, L, M, table.data_ptr(), out.data_ptr(),
+                                                   _shape_id(table), stream))
 
 
 @torch.no_grad()
@@ -155,7 +197,7 @@ def ntuple_value(source, table: torch.Tensor, L: Optional[int] = None, M: Option
     return out
 
 
-_sigma = {}                                                    # the mirror permutation, once per device
+_sigma = {}                                                    # the mirror permutation, once per device and shape
 
 
 @torch.no_grad()
@@ -164,11 +206,12 @@ def ntuple_is_symmetric(table: torch.Tensor) -> bool:
     (include/tpl_learn.h states the invariant).  Under such a table a board and its reflection have the same value, bit for bit.
     One gather and one comparison on the table's device; the answer is a host bool, so this syncs."""
     if not isinstance(table, torch.Tensor):
-        raise ValueError(f"table must be a contiguous int32 tensor of {NTUPLE_ENTRIES} entries (ntuple_table)")
+        raise ValueError(f"table must be a contiguous int32 tensor of {_sizes()} entries (ntuple_table)")
     _table(table, table.device)
-    if table.device not in _sigma:
-        _sigma[table.device] = torch.from_numpy(_learn_lib.ntuple_mirror_permutation()).to(table.device)
-    return bool(torch.equal(table[_sigma[table.device]], table))
+    key = (table.device, ntuple_shape(table))
+    if key not in _sigma:
+        _sigma[key] = torch.from_numpy(_learn_lib.ntuple_mirror_permutation(key[1])).to(table.device)
+    return bool(torch.equal(table[_sigma[key]], table))
 
 
 class NTuplePolicy:
@@ -186,6 +229,7 @@ class NTuplePolicy:
         _boards(env, "NTuplePolicy")
         self.env, self.table, self.depth = env, _table(table, env.device), _depth(depth)
         self.gamma, self.epsilon, self.seed = _finite("gamma", gamma), _unit("epsilon", epsilon), _count("seed", seed)
+        self.shape = ntuple_shape(self.table)                  # "2x4" or "3x3": the table's, which picks the kernels
         self.step = 0                                          # the `step` of the next act() that is not given one
         self._planes = None
 
@@ -226,8 +270,9 @@ class NTuplePolicy:
         lib = _learn_lib.lib()
         head = (self._planes[0], self._planes[1], env.num_envs, env.L, env.M, *env.reward_params, self.gamma, self.table.data_ptr(),
                 self.epsilon, self.seed % (1 << 64), step % (1 << 64), out.data_ptr())
-        tail = (_ptr(score), _ptr(after_a), _ptr(after_b), _ptr(value), stream)
-        check(lib.tpl_ntuple_search(*head, _ptr(second), *tail) if self.depth == 2 else lib.tpl_ntuple_act(*head, *tail))
+        tail = (_ptr(score), _ptr(after_a), _ptr(after_b), _ptr(value), NTUPLE_SHAPE_IDS[self.shape], stream)
+        check(lib.tpl_ntuple_search_shaped(*head, _ptr(second), *tail) if self.depth == 2
+              else lib.tpl_ntuple_act_shaped(*head, *tail))
         return out
 
 
@@ -263,14 +308,19 @@ class NTupleLearner:
     scales an entry's step by alpha = |E| / A as it stood before the step (ntuple_step_sizes): an entry whose errors keep their
     sign learns at `rate`, one whose errors alternate -- an overshoot -- slows itself down.  A coherent step is never larger than
     the plain one.  forget() leaves `coherence` alone; it is a plain tensor, and coherence.zero_() starts the step sizes over.
-    Still five enqueues a step (the entry launches two kernels), no sync, nothing allocated."""
+    Still five enqueues a step (the entry launches two kernels), no sync, nothing allocated.
+
+    shape ("2x4" by default, which leaves everything above as it was; "3x3"): the windows of the table, and of the coherence buffer
+    if there is one.  Nothing else about the learner depends on it."""
 
     def __init__(self, env, gamma: float = 0.99, rate: float = 8.0, epsilon: float = 0.1, seed: int = 0, depth: int = 1,
-                 lam: float = 0.0, horizon: int = 1, symmetric: bool = False, coherent: bool = False):
+                 lam: float = 0.0, horizon: int = 1, symmetric: bool = False, coherent: bool = False, shape: str = "2x4"):
         n = _boards(env, "NTupleLearner")
         if not env.auto_reset:
             raise ValueError("NTupleLearner needs an auto-reset environment")
         self.env, self.rate = env, _finite("rate", rate)
+        _entries(shape)
+        self.shape = shape
         _unit("epsilon", epsilon), _finite("gamma", gamma), _count("seed", seed)
         self.lam, self.horizon = _unit("lam", lam), _horizon(horizon)
         if not isinstance(symmetric, bool):
@@ -286,8 +336,8 @@ class NTupleLearner:
             raise ValueError(f"(horizon + 1) * boards must stay at or below {_MAX_BOARDS}")
         d = env.device
         self.depth = _depth(depth)
-        self.table = ntuple_table(d)
-        self.coherence = ntuple_coherence(d) if coherent else None
+        self.table = ntuple_table(d, shape)
+        self.coherence = ntuple_coherence(d, shape) if coherent else None
         self.policy = NTuplePolicy(env, self.table, gamma, epsilon, seed, self.depth)
         self.greedy = NTuplePolicy(env, self.table, gamma, 0.0, seed, self.depth)
         self.steps = 0                                         # train() steps so far: the `step` of the exploration draw
@@ -326,15 +376,18 @@ class NTupleLearner:
         env, n, lib = self.env, self.env.num_envs, _learn_lib.lib()
         stream = torch._C._cuda_getCurrentRawStream(env.device.index)
         ring_a, ring_b = self._ring[0].data_ptr(), self._ring[1].data_ptr()
+        if self.coherent:
+            _coherence(self.coherence, _table(self.table, env.device))   # a buffer of the other shape would be overrun
+        shape = _shape_id(self.table)
         for _ in range(steps):
             kept = self._kept
             self.policy.act(out=self._action, score=self._score, after=self._next, step=self.steps)
             _value(kept[0], kept[1], n, env.L, env.M, self.table, self._kept_value, env.device)
             torch.sub(self._score, self._kept_value, out=self._error)
             ring = (ring_a, ring_b, n, self.slots, self._head, self.horizon, env.L, env.M, self.table.data_ptr())
-            tail = (self._error.data_ptr(), self.rate, self.decay, int(self.symmetric), stream)
-            check(lib.tpl_ntuple_update_coherent(*ring, self.coherence.data_ptr(), *tail) if self.coherent
-                  else lib.tpl_ntuple_update_trace(*ring, *tail))
+            tail = (self._error.data_ptr(), self.rate, self.decay, int(self.symmetric), shape, stream)
+            check(lib.tpl_ntuple_update_coherent_shaped(*ring, self.coherence.data_ptr(), *tail) if self.coherent
+                  else lib.tpl_ntuple_update_trace_shaped(*ring, *tail))
             env.step_into(self._action, self._reward, self._done)
             self._head = (self._head + 1) % self.slots
             self.steps += 1

@@ -76,6 +76,18 @@ Parts:
               each (TD(0) at rate 16 without coherence is the baseline), and the two-piece game (4,096 boards, 300 steps) at rates
               64, 256 and 1,024; win rates after 10,000 and 40,000 steps, the largest entry, and alpha over the entries that were
               sent a step.  --chunk I/K runs every K-th cell from the I-th on, for a run in several processes
+    ntuple_shape   the 3 x 3 table shape beside 2 x 4: on part ntuple_trace's ring (L=10 / M=40, mid-game, 17 slots) at 2^16, 2^18 and
+              2^20 boards every _shaped entry at shape 1 beside the same entry at shape 0 in the same alternated rounds -- value,
+              act, search, update, update_trace at horizon 4 plain and symmetric, update_coherent at horizon 4 --, each shape on a
+              random table of its own size; the entries in use per running board of both shapes, and the static vector instructions
+              of every kernel of both
+    ntuple_shape_sweep  part ntuple_trace_sweep's set-up unchanged (pool, seed, reward, epsilon, gamma, budget, evaluation): the 2 x 4
+              TD(0) baseline at rate 16 re-run, then shape 3 x 3 at rates 4, 8, 16 and 32 as TD(0), lambda 0.5 / horizon 8 and
+              symmetric lambda 0.8 / horizon 4; the best 3 x 3 table is also played at depth 2
+    ntuple_shape_ab  --parent LIB: the nine 2 x 4 n-tuple kernels of another build of the learner library against this tree's, both
+              loaded into one process: the outputs of the six entries compared byte for byte on the ring of part ntuple_shape
+              at 2^18 boards, then each entry timed in five rounds of the parent against itself and five of the parent against
+              this build; a new median passes within the parent's own min-max or at most 2 % above the parent's median
 """
 import argparse
 import json
@@ -91,7 +103,7 @@ HBM_ACHIEVABLE = 6.3e12
 PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600, "priority": 600, "nstep": 600, "mirror": 600, "afterstates": 600,
          "heuristic": 600, "search": 900, "beam": 900, "ntuple": 900,
          "ntuple_search": 900, "ntuple_trace": 600, "ntuple_trace_sweep": 1100, "ntuple_coherent": 600,
-         "ntuple_coherent_sweep": 1700}
+         "ntuple_coherent_sweep": 1700, "ntuple_shape": 600, "ntuple_shape_sweep": 1100}
 SCATTERED_ATOMICS = 0.08e12                                 # 64 lanes of a wave adding into 64 rows (float adds; integer adds unmeasured)
 VALU_CYCLES, SIMDS, CLOCK_HZ = 3.3, 1024, 2.4e9           # the move's instruction mix, 256 CUs x 4, the clock
 
@@ -1411,9 +1423,219 @@ def part_ntuple_coherent_sweep(eval_steps=12288, chunk=(0, 1)):
                 best=max(large, key=lambda r: r["trained"][-1]["win_rate"]) if large else None, runs=runs)
 
 
+def _shape_ring(T, n, slots=17):
+    """Part ntuple_trace's ring: the last `slots` states of n mid-game boards (L=10 / M=40), oldest first, and the environment."""
+    import torch
+    env = T.BatchedTetris(10, 40, n, device="cuda:0", seed=1, auto_reset=True)
+    env.load_configs(*env.synthetic_configs(4096))
+    env.reset()
+    ring = [torch.empty((slots, n, 4), dtype=torch.int32, device="cuda:0") for _ in range(2)]
+    for t in range(6 + slots):
+        env.step(env.synthetic_actions(t), observe=False)
+        if t >= 6:
+            a, b = env.raw_planes()
+            ring[0][t - 6].copy_(a)
+            ring[1][t - 6].copy_(b)
+    return env, ring
+
+
+def _shape_calls(L, check, ring, n, head, slots, tables, coherences, error, out, stream, twin=None):
+    """name -> call of the seven timed forms of the six entries, for table shape `s`: through the _shaped entries of library L, or,
+    with twin=True, through the entries without a shape (2 x 4 only)."""
+    pa, pb = ring[0].data_ptr(), ring[1].data_ptr()
+    na, nb = ring[0][head].data_ptr(), ring[1][head].data_ptr()
+    action, second, score, value, after_a, after_b = (t.data_ptr() for t in out)
+    rate, decay = 100.0, 0.9
+
+    def calls(s):
+        t, c, e = tables[s].data_ptr(), coherences[s].data_ptr(), error.data_ptr()
+        tail = (stream,) if twin else (s, stream)
+        f = (lambda name: getattr(L, name)) if twin else (lambda name: getattr(L, name + "_shaped"))
+        head_args = (na, nb, n, 10, 40, 1.0, 10.0, -1.0, 1.0, t, 0.05, 11, 3, action)
+        return {
+            "value": lambda: check(f("tpl_ntuple_value")(na, nb, n, 10, 40, t, value, *tail)),
+            "act": lambda: check(f("tpl_ntuple_act")(*head_args, score, after_a, after_b, value, *tail)),
+            "search": lambda: check(f("tpl_ntuple_search")(*head_args, second, score, after_a, after_b, value, *tail)),
+            "update": lambda: check(f("tpl_ntuple_update")(na, nb, n, 10, 40, t, e, rate, *tail)),
+            "trace_h4": lambda: check(f("tpl_ntuple_update_trace")(pa, pb, n, slots, head, 4, 10, 40, t, e, rate, decay, 0, *tail)),
+            "trace_h4_symmetric": lambda: check(f("tpl_ntuple_update_trace")(pa, pb, n, slots, head, 4, 10, 40, t, e, rate, decay, 1, *tail)),
+            "coherent_h4": lambda: check(f("tpl_ntuple_update_coherent")(pa, pb, n, slots, head, 4, 10, 40, t, c, e, rate, decay, 0, *tail)),
+        }
+    return calls
+
+
+def _shape_buffers(T, m, n):
+    import numpy as np
+    import torch
+    tables, coherences = {}, {}
+    for s, name in ((0, "2x4"), (1, "3x3")):
+        host = np.random.default_rng(s).integers(-(1 << 20), (1 << 20) + 1, m.NTUPLE_SHAPES[name][2]).astype(np.int32)
+        tables[s] = torch.from_numpy(host).to("cuda:0")
+        coherences[s] = T.ntuple_coherence("cuda:0", name)
+    error = torch.empty(n, dtype=torch.float32, device="cuda:0").normal_()
+    out = [torch.empty(n, dtype=torch.uint8, device="cuda:0"), torch.empty(n, dtype=torch.uint8, device="cuda:0"),
+           torch.empty(n, dtype=torch.float32, device="cuda:0"), torch.empty(n, dtype=torch.float32, device="cuda:0"),
+           torch.empty((n, 4), dtype=torch.int32, device="cuda:0"), torch.empty((n, 4), dtype=torch.int32, device="cuda:0")]
+    return tables, coherences, error, out
+
+
+def part_ntuple_shape(rounds=5, reps=10):
+    import numpy as np
+    import torch
+    import tetris_piclim as T
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import learn_ref as R
+    m = T._learn_lib
+    L, check = m.lib(), m.check
+    stream = torch._C._cuda_getCurrentRawStream(0)
+    slots, head = 17, 16
+    kernels = ("value_kernel", "act_kernel", "search_kernel", "trace_kernelILb0", "trace_kernelILb1", "coherent_step_kernelILb0",
+               "coherent_accumulate_kernelILb0")
+    out = dict(part="ntuple_shape", slots=slots, head=head, rate=100.0, decay=0.9,
+               static_valu={p + k: _static_valu(p + k, m.build_library()) for k in kernels for p in ("ntuple_", "ntuple3_")})
+    rows = []
+    for n in (1 << 16, 1 << 18, 1 << 20):
+        env, ring = _shape_ring(T, n, slots)
+        a, b = (x[head, :4096].cpu().numpy().view(np.uint32) for x in ring)
+        f = R.decode_state(a, b)
+        in_use = {}
+        for name in ("2x4", "3x3"):
+            _, used = m.ntuple_indices(f["rows"], f["cur"], 10, 40, f["lines"].astype(np.int64), f["moves"].astype(np.int64), shape=name)
+            in_use[name] = round(float(used[f["state"] == 0].sum(axis=1).mean()), 1)         # the counter included
+        tables, coherences, error, outputs = _shape_buffers(T, m, n)
+        calls = _shape_calls(L, check, ring, n, head, slots, tables, coherences, error, outputs, stream)
+        variants = [(f"{name}_{shape}", fn) for s, shape in ((0, "2x4"), (1, "3x3")) for name, fn in calls(s).items()]
+        variants.sort(key=lambda v: v[0])                        # each entry's two shapes next to each other in every round
+        for s in (0, 1):                                         # step sizes of every kind before anything is timed
+            for _ in range(2):
+                error.normal_()
+                calls(s)["coherent_h4"]()
+        times = {name: [] for name, _ in variants}
+        for _ in range(rounds):                                  # alternate the variants round by round
+            for name, fn in variants:
+                times[name].append(_timed(fn, reps if "search" not in name else max(reps // 3, 2)))
+        med = {name: sorted(ts)[rounds // 2] for name, ts in times.items()}
+        row = dict(boards=n, entries_in_use_per_board=in_use)
+        for name in calls(0):
+            row[name] = {"2x4_us": _spread(times[name + "_2x4"]), "3x3_us": _spread(times[name + "_3x3"]),
+                         "3x3_over_2x4": round(med[name + "_3x3"] / med[name + "_2x4"], 3)}
+        rows.append(row)
+        print(json.dumps(row), file=sys.stderr, flush=True)
+        env.terminate()
+        del tables, coherences, ring, outputs, error
+        torch.cuda.empty_cache()
+    out["kernel"] = dict(rounds=rounds, launches_per_timing=reps, search_launches_per_timing=max(reps // 3, 2), rows=rows)
+    return out
+
+
+def part_ntuple_shape_sweep(eval_steps=12288):
+    import torch
+    import tetris_piclim as T
+    gen_env = T.BatchedTetris(10, 40, 64, device="cuda:0", seed=7)
+    big = gen_env.carved_configs(1 << 16, seed=7)
+    gen_env.terminate()
+
+    def result(r):
+        p = r["win_rate"]
+        return dict(episodes=r["episodes"], wins=r["wins"], win_rate=round(p, 5),
+                    standard_error=round((p * (1 - p) / max(r["episodes"], 1)) ** 0.5, 6))
+
+    def learn(keep=False, **kw):
+        """part_ntuple_trace_sweep's sequence: the zero table played, 10,000 steps, an evaluation, 30,000 steps, an evaluation."""
+        env = T.BatchedTetris(10, 40, 4096, device="cuda:0", seed=11, auto_reset=True, reward=NTUPLE_LARGE_REWARD, config_pool=big)
+        learner = T.NTupleLearner(env, seed=11, gamma=1.0, epsilon=0.05, **kw)
+        got = dict(kw, zero_table=result(learner.evaluate(eval_steps)), trained=[])
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for steps in (10000, 30000):
+            learner.train(steps)
+            got["trained"].append(dict(steps=learner.steps, **result(learner.evaluate(eval_steps))))
+        got.update(seconds=round(time.perf_counter() - t0, 2), entries_in_use=int((learner.table != 0).sum()),
+                   largest_entry=int(learner.table.abs().max()), symmetric_table=T.ntuple_is_symmetric(learner.table))
+        table = learner.table.clone() if keep else None
+        env.terminate()
+        print(json.dumps(got), file=sys.stderr, flush=True)      # progress: a long part must not stay silent
+        return got, table
+    baseline, _ = learn(rate=16.0)
+    runs, tables = [], []
+    for form in (dict(), dict(lam=0.5, horizon=8), dict(lam=0.8, horizon=4, symmetric=True)):
+        for rate in (4.0, 8.0, 16.0, 32.0):
+            got, table = learn(keep=True, shape="3x3", rate=rate, **form)
+            runs.append(got)
+            tables.append(table)
+    at = max(range(len(runs)), key=lambda i: runs[i]["trained"][-1]["win_rate"])
+    env = T.BatchedTetris(10, 40, 4096, device="cuda:0", seed=11, auto_reset=True, reward=NTUPLE_LARGE_REWARD, config_pool=big)
+    player = T.NTupleLearner(env, seed=11, gamma=1.0, epsilon=0.05, shape="3x3")
+    player.table.copy_(tables[at])
+    deep = dict(depth_1=result(player.evaluate(eval_steps)), depth_2=result(player.evaluate(eval_steps, depth=2)))
+    env.terminate()
+    return dict(part="ntuple_shape_sweep", boards=4096, seed=11, pool=1 << 16, pool_seed=7, reward=list(NTUPLE_LARGE_REWARD), gamma=1.0,
+                epsilon=0.05, eval_steps=eval_steps, baseline=baseline, best=runs[at], best_played=deep, runs=runs)
+
+
+def part_ntuple_shape_ab(parent, rounds=5, reps=20, n=1 << 18):
+    import ctypes as C
+    import numpy as np
+    import torch
+    import tetris_piclim as T
+    m = T._learn_lib
+    new, check = m.lib(), m.check
+    old = C.CDLL(os.path.abspath(parent))
+    for name in ("tpl_ntuple_value", "tpl_ntuple_act", "tpl_ntuple_update", "tpl_ntuple_search", "tpl_ntuple_update_trace",
+                 "tpl_ntuple_update_coherent"):
+        getattr(old, name).argtypes, getattr(old, name).restype = getattr(new, name).argtypes, C.c_int32
+    stream = torch._C._cuda_getCurrentRawStream(0)
+    slots, head = 17, 16
+    env, ring = _shape_ring(T, n, slots)
+    tables, coherences, error, outputs = _shape_buffers(T, m, n)
+    start = tables[0].clone()
+    libs = {"parent": _shape_calls(old, check, ring, n, head, slots, tables, coherences, error, outputs, stream, twin=True)(0),
+            "new": _shape_calls(new, check, ring, n, head, slots, tables, coherences, error, outputs, stream, twin=True)(0)}
+    for _ in range(2):                                           # a coherence buffer with step sizes of every kind
+        error.normal_()
+        libs["parent"]["coherent_h4"]()
+    filled = coherences[0].clone()
+    error.normal_()
+    lines, equal = [], {}
+    for name in libs["new"]:                                     # byte for byte, from the same table and coherence buffer
+        left = {}
+        for which in ("parent", "new"):
+            tables[0].copy_(start)
+            coherences[0].copy_(filled)
+            for t in outputs:
+                t.zero_()
+            libs[which][name]()
+            torch.cuda.synchronize()
+            left[which] = [t.clone() for t in outputs] + [tables[0].clone(), coherences[0].clone()]
+        equal[name] = all(torch.equal(x, y) for x, y in zip(left["parent"], left["new"]))
+    tables[0].copy_(start)
+    lines.append(dict(boards=n, outputs_equal=equal, table_changed_by_the_updates=bool(int((left["new"][-2] != start).sum()) > 0)))
+    us = lambda t: round(t * 1e6, 2)
+    for name in libs["new"]:
+        fa, fb = libs["parent"][name], libs["new"][name]
+        k = max(reps // 4, 3) if name == "search" else reps
+        a, b, pa, nb = [], [], [], []
+        for _ in range(rounds):                                  # the parent against itself: the noise of the method
+            a.append(us(_timed(fa, k)))
+            b.append(us(_timed(fa, k)))
+        for _ in range(rounds):                                  # the parent against this build, alternated
+            pa.append(us(_timed(fa, k)))
+            nb.append(us(_timed(fb, k)))
+        lo, hi = min(a + b), max(a + b)
+        pm, nm = sorted(pa)[rounds // 2], sorted(nb)[rounds // 2]
+        bound = max(hi, round(1.02 * pm, 2))
+        lines.append(dict(boards=n, entry=name, parent_against_itself=dict(a=a, b=b, min=lo, max=hi), parent=pa, new=nb, parent_median=pm,
+                          new_median=nm, ratio=round(nm / pm, 4), bound_us=bound, within=bool(nm <= bound)))
+        print(json.dumps(lines[-1]), file=sys.stderr, flush=True)
+    env.terminate()
+    return dict(part="ntuple_shape_ab", rounds=rounds, launches_per_timing=reps, lines=lines,
+                every_output_equal=all(equal.values()), every_median_within=all(l["within"] for l in lines[1:]))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", choices=sorted(PARTS))
+    ap.add_argument("--part", choices=sorted(PARTS) + ["ntuple_shape_ab"])
+    ap.add_argument("--parent", default=None, help="of part ntuple_shape_ab: the learner library of the build to compare against")
     ap.add_argument("--chunk", default=None, help="I/K: of part ntuple_coherent_sweep, every K-th cell from the I-th on")
     args = ap.parse_args()
     if args.part:
@@ -1425,6 +1647,10 @@ def main():
             if not 0 <= i < k:
                 ap.error("--chunk I/K needs 0 <= I < K")
             kw["chunk"] = (i, k)
+        if args.part == "ntuple_shape_ab":
+            if not args.parent:
+                ap.error("--part ntuple_shape_ab needs --parent LIB")
+            kw["parent"] = args.parent
         print(json.dumps(globals()["part_" + args.part](**kw)), flush=True)
         return 0
     for name, limit in PARTS.items():
