@@ -536,6 +536,60 @@ int tpl_ntuple_update_coherent_shaped(const void* ring_a, const void* ring_b, in
                                       int32_t horizon, int32_t L, int32_t M, int32_t* table, int64_t* coherence, const float* error,
                                       float rate, float decay, int32_t symmetric, int32_t shape, void* stream);
 
+/* Beam search over the known piece window with an n-tuple table at the leaves.  tpl_ntuple_search stops at two plies because an
+ * AFTERSTATE knows its next piece and no more; an ENVIRONMENT STATE carries 12 - (moves mod 10) true pieces (tpl_placement_beam,
+ * above), and the policy is always asked about environment states.  tpl_placement_beam gives this rule its nodes, its candidates
+ * in order, the stable compaction and the ties; tpl_ntuple_search gives it the rewards and V.  There is no exploration: the policy
+ * is greedy.
+ *
+ * For a state s, a table of `shape`, reward parameters (r_line, r_win, r_lose), a discount gamma, a depth D in
+ * [1, TPL_NTUPLE_BEAM_MAX_DEPTH] and a width W in [1, TPL_BEAM_MAX_WIDTH]:
+ *   Finished board (state(s) != running): action 0, score 0, every plan entry 255; `after` is s itself, bit for bit.
+ *   Running board: the effective depth is d = min(D, 11 - moves(s) mod 10), from the state's bits as they stand (pool or not) -- ONE
+ *   LESS than tpl_placement_beam's: the value of a leaf is read under the piece that falls next, window entry d of the root, and
+ *   that entry must be a true piece.  11 - moves mod 10 is never below 2.
+ *   A NODE is a board (its window popped once per move made, by next_window(s, false, 0) as tpl_afterstates does), its path of
+ *   placements b_1 .. b_j, the rewards r_1 .. r_j of its moves -- each tpl_afterstates' reward of (rows cleared, state after) --
+ *   and a value.  Beam_0 is the root alone (empty path).
+ *   For ply j = 1 .. d the CANDIDATES are listed exactly as tpl_placement_beam lists them: over the nodes of Beam_{j-1} in their
+ *   stored order, a node that does not run gives one candidate, itself, value and path unchanged; a running node gives one child
+ *   per distinct placement b of its current piece in ascending b (piece 7 is O's nine placements): move_board(node, b), then the pop.
+ *   The value of a child at ply j is folded from the leaf inwards:
+ *       tail_j = r_j                       if the child does not run
+ *       tail_j = r_j + gamma * V(child)    otherwise
+ *       tail_k = r_k + gamma * tail_{k+1}  for k = j - 1 .. 1
+ *       value  = tail_1
+ *   -- V as tpl_ntuple_value_shaped gives it: the piece index is window entry 0 of the popped child (entry j of the root), the
+ *   counter index comes from the child's lines and moves.  Every product and every sum is rounded once in float32 and never fused.
+ *   (G + gamma^j * V, accumulated forwards, is other arithmetic and not this rule.)
+ *   Candidates are ordered by (value descending, candidate index ascending); -0 and +0 tie.  Beam_j = the min(W, count) best
+ *   candidates STORED IN CANDIDATE ORDER, each with its value as computed (a -0 stays a -0).
+ *   Choice: the best node of Beam_d under the same order: action = the first placement of its path, score = its value,
+ *   plan[0 .. D) = its path padded with 255.  after_a / after_b receive the ONE-PLY afterstate of `action`: row `action` of
+ *   tpl_afterstates, which is what tpl_ntuple_act writes for that action.
+ * Consequences:
+ *   D = 1, any W: action, score and after are tpl_ntuple_act_shaped's at epsilon 0, bit for bit.
+ *   D = 2, W >= 34, gamma >= 0: action and score are tpl_ntuple_search_shaped's, bit for bit.  x -> r1 + gamma * x is monotone under
+ *   rounding, so the best of the folded values is the fold of the best.  plan[1] is the lowest b whose FOLDED value equals score;
+ *   the search's `second` is the lowest b at the maximum of q; so plan[1] <= second, and they differ only where two different q round
+ *   to one Q.
+ *   Playing `plan` move by move on a non-auto-reset environment without a pool (no refill: the same pop) earns rewards and reaches a
+ *   final board whose fold under the table -- the rewards earned, and V of the final board where it still runs -- is `score`, bit
+ *   for bit.
+ * THE FINITENESS CAVEAT is tpl_placement_act's, here for the reward parameters and gamma times the table's values.  Boards that
+ * different paths reach are not merged, and the pool is never read for pieces beyond the window.
+ *
+ * One kernel per shape (ntuple_beam_kernel, ntuple_beam3_kernel: csrc/learn/ntuple_beam.hip), a workgroup per board in
+ * tpl_placement_beam's frame: 32 bytes read per board besides the table gathers, action u8 [n], plan u8 [n][depth] (optional),
+ * score f32 [n] (optional), after_a / after_b [n] 16-byte words (both or neither) written; an output that is not given is not
+ * written.  Refused before any HIP call, under the entry's own name: a shape that is neither of the two, before anything else;
+ * everything tpl_ntuple_act refuses for its planes, n, L, M, table, action, after, score and gamma, in that order; depth outside
+ * [1, TPL_NTUPLE_BEAM_MAX_DEPTH]; width outside [1, TPL_BEAM_MAX_WIDTH]. */
+#define TPL_NTUPLE_BEAM_MAX_DEPTH 11
+int tpl_ntuple_beam(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line, float r_win,
+                    float r_lose, float gamma, const int32_t* table, int32_t depth, int32_t width, uint8_t* action, uint8_t* plan,
+                    float* score, void* after_a, void* after_b, int32_t shape, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

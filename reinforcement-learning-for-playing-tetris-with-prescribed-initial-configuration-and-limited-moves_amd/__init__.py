@@ -13,7 +13,7 @@ from ._lib import (LIB_PATH, SYMBOLS, TplError, build_library, carve, forward_ge
 __all__ = ["BatchedTetris", "Tetris", "Snapshot", "OBS_DIM", "NUM_ACTIONS", "RUNNING", "WON", "LOST", "TplError",
            "RandomPieceGenerator", "get_tetromino", "piece_translations", "translate", "carve", "build_library", "shape_info", "generate_configs", "forward_generate", "pack_policy", "LIB_PATH", "SYMBOLS", "DQNLearner",
            "ReplayRing", "PrioritizedReplayRing", "LookaheadPolicy", "afterstates", "HeuristicPolicy", "placement_features",
-           "evaluate_heuristic", "tune_heuristic", "BeamPolicy", "NTuplePolicy", "NTupleLearner", "ntuple_table", "ntuple_value",
+           "evaluate_heuristic", "tune_heuristic", "BeamPolicy", "NTuplePolicy", "NTupleBeamPolicy", "NTupleLearner", "ntuple_table", "ntuple_value",
            "ntuple_is_symmetric", "ntuple_coherence", "ntuple_step_sizes", "ntuple_shape", "NTUPLE_SHAPES"]
 
 
@@ -38,7 +38,7 @@ def __getattr__(name):
         return getattr(importlib.import_module(__name__ + ".lookahead"), name)
     if name in ("HeuristicPolicy", "placement_features", "evaluate_heuristic", "tune_heuristic", "BeamPolicy"):
         return getattr(importlib.import_module(__name__ + ".heuristic"), name)
-    if name in ("NTuplePolicy", "NTupleLearner", "ntuple_table", "ntuple_value", "ntuple_is_symmetric", "ntuple_coherence",
+    if name in ("NTuplePolicy", "NTupleBeamPolicy", "NTupleLearner", "ntuple_table", "ntuple_value", "ntuple_is_symmetric", "ntuple_coherence",
                 "ntuple_step_sizes", "ntuple_shape", "NTUPLE_SHAPES"):
         return getattr(importlib.import_module(__name__ + ".ntuple"), name)
     if name in ("learn", "_learn_lib", "lookahead", "heuristic", "ntuple"):

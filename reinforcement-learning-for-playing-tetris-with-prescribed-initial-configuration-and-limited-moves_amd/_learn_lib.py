@@ -21,7 +21,7 @@ from ._lib import TplError, _hipcc
 _LEARN_CSRC = os.path.join(_lib._CSRC, "learn")
 LEARN_LIB_PATH = os.path.join(_lib._LIBDIR, "libtpl_learn.so")
 _UNITS = [os.path.join(_LEARN_CSRC, f) for f in ("replay.hip", "pack.hip", "priority.hip", "afterstates.hip",
-                                                      "beam.hip", "ntuple.hip", "heuristic.hip")]
+                                                      "beam.hip", "ntuple.hip", "ntuple_beam.hip", "heuristic.hip")]
 
 # entry points declared in include/tpl_learn.h (tests check that the .so exports every one of them)
 LEARN_SYMBOLS = [
@@ -32,10 +32,11 @@ LEARN_SYMBOLS = [
     "tpl_placement_act", "tpl_placement_search", "tpl_placement_beam", "tpl_ntuple_value", "tpl_ntuple_act", "tpl_ntuple_update",
     "tpl_ntuple_search", "tpl_ntuple_update_trace", "tpl_ntuple_update_coherent", "tpl_ntuple_entries",
     "tpl_ntuple_value_shaped", "tpl_ntuple_act_shaped", "tpl_ntuple_search_shaped", "tpl_ntuple_update_shaped",
-    "tpl_ntuple_update_trace_shaped", "tpl_ntuple_update_coherent_shaped",
+    "tpl_ntuple_update_trace_shaped", "tpl_ntuple_update_coherent_shaped", "tpl_ntuple_beam",
 ]
 NSTEP_MAX = 16
 BEAM_MAX_DEPTH, BEAM_MAX_WIDTH = 12, 64
+NTUPLE_BEAM_MAX_DEPTH = 11                               # one less: the leaf's piece must be a known one
 MIRROR_MODES = {False: 0, True: 1, "always": 2}          # sample(mirror=...) -> tpl_mirror_mode
 
 IMAGE_KINDS = {"bf16": 0, "f32": 1, "split": 2}
@@ -153,6 +154,8 @@ def lib() -> C.CDLL:
         twin = getattr(L, name + "_shaped")
         twin.argtypes = getattr(L, name).argtypes[:-1] + [i32, vp]
         twin.restype = i32
+    L.tpl_ntuple_beam.argtypes = [vp, vp, i64, i32, i32, f32, f32, f32, f32, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp]
+    L.tpl_ntuple_beam.restype = i32
     for name in ("tpl_replay_push", "tpl_replay_sample", "tpl_learn_pack", "tpl_priority_init", "tpl_priority_push",
                  "tpl_priority_update", "tpl_replay_sample_prioritized", "tpl_replay_sample_nstep", "tpl_replay_sample_mirror",
                  "tpl_mirror_states", "tpl_afterstates", "tpl_placement_features", "tpl_placement_act",
@@ -810,6 +813,74 @@ def ntuple_search_choice(reward1, done1, distinct1, reward2, done2, value2, dist
     action = np.where(running, action, 0)
     at = np.arange(k)
     return action.astype(np.uint8), second[at, action], Q[at, action], Q, second
+
+
+def ntuple_beam_values(rewards, ended, leaf_value, gamma) -> np.ndarray:
+    """The fold of include/tpl_learn.h (tpl_ntuple_beam) for K children at ply j: rewards f32 [K, j] = r_1 .. r_j of each path,
+    ended [K] where the child does not run, leaf_value f32 [K] = V(child), read only where it runs.  tail_j = r_j, or
+    r_j + gamma * V where the child runs; tail_k = r_k + gamma * tail_{k+1} for k = j - 1 .. 1; returns tail_1 (float32 [K]).
+    Float32 numpy operations from the leaf inwards: every product and every sum rounded once."""
+    r = np.asarray(rewards, dtype=np.float32)
+    if r.ndim != 2 or r.shape[1] < 1:
+        raise ValueError("rewards must be [K, j] with j >= 1")
+    ended = np.asarray(ended).astype(bool).reshape(r.shape[0])
+    v = np.asarray(leaf_value, dtype=np.float32).reshape(r.shape[0])
+    g = np.float32(gamma)
+    with np.errstate(invalid="ignore", over="ignore"):
+        tail = np.where(ended, r[:, -1], r[:, -1] + g * np.where(ended, np.float32(0.0), v)).astype(np.float32)
+        for k in range(r.shape[1] - 2, -1, -1):
+            tail = (r[:, k] + g * tail).astype(np.float32)
+    return tail
+
+
+def ntuple_beam_ply(node_value, node_running, child_value, distinct, width: int):
+    """The choice of one ply of the beam rule (tpl_placement_beam's candidates, tpl_ntuple_beam's values) on top of beam_select:
+    node_value f32 [Q] and node_running [Q] of the nodes of Beam_{j-1} in their stored order, child_value f32 [Q, 40] the folded
+    value of every placement of every running node, distinct [Q, 40] or [40] where a placement is a distinct one.  A node that does
+    not run is ONE candidate, itself, with its value unchanged; a running node gives its distinct placements in ascending b.
+    Returns (node int64 [kept], placement int64 [kept] -- 255 for a node carried --, value f32 [kept]) of Beam_j, in candidate
+    order; every value keeps its own bits."""
+    nv = np.asarray(node_value, dtype=np.float32).reshape(-1)
+    run = np.asarray(node_running).astype(bool).reshape(nv.shape[0])
+    cv = np.asarray(child_value, dtype=np.float32).reshape(nv.shape[0], NUM_ACTIONS)
+    d = np.broadcast_to(np.asarray(distinct).astype(bool), cv.shape)
+    cand = np.where(run[:, None], d, np.arange(NUM_ACTIONS)[None, :] == 0)
+    value = np.where(run[:, None], cv, nv[:, None])
+    at = np.flatnonzero(cand.reshape(-1))
+    keep = at[beam_select(value.reshape(-1)[at], width)]
+    q, b = keep // NUM_ACTIONS, keep % NUM_ACTIONS
+    return q, np.where(run[q], b, NO_SECOND), value[q, b]
+
+
+def ntuple_beam_choice(children, gamma, depth: int, width: int, running: bool = True):
+    """The rule of tpl_ntuple_beam for ONE state whose moves are given by a function: children(path) -> (reward f32 [40], ended
+    [40], value f32 [40], distinct [40]) of the node reached by the tuple of placements `path` -- the reward of every placement,
+    whether it ends the game, V of the child where it does not, and which placements are distinct.  `depth` is the EFFECTIVE depth.
+    Returns (action, plan -- a list of `depth` placements padded with 255 --, score f32).  A state that is not running: (0, all
+    255, 0)."""
+    if isinstance(depth, bool) or int(depth) != depth or not 1 <= int(depth) <= NTUPLE_BEAM_MAX_DEPTH:
+        raise ValueError(f"depth must be an integer in [1, {NTUPLE_BEAM_MAX_DEPTH}]")
+    if not running:
+        return 0, [NO_SECOND] * int(depth), np.float32(0.0)
+    nodes = [dict(path=(), rewards=[], value=np.float32(0.0), running=True)]
+    for _ in range(int(depth)):
+        child_value = np.zeros((len(nodes), NUM_ACTIONS), np.float32)
+        distinct = np.zeros((len(nodes), NUM_ACTIONS), bool)
+        made = {}
+        for q, node in enumerate(nodes):
+            if not node["running"]:
+                continue
+            reward, ended, value, distinct[q] = children(node["path"])
+            reward = np.asarray(reward, dtype=np.float32)
+            made[q] = (reward, np.asarray(ended).astype(bool))
+            before = np.broadcast_to(np.asarray(node["rewards"], np.float32), (NUM_ACTIONS, len(node["rewards"])))
+            child_value[q] = ntuple_beam_values(np.concatenate([before, reward[:, None]], axis=1), ended, value, gamma)
+        qs, bs, vs = ntuple_beam_ply([x["value"] for x in nodes], [x["running"] for x in nodes], child_value, distinct, width)
+        nodes = [nodes[q] if b == NO_SECOND else dict(path=nodes[q]["path"] + (int(b),), rewards=nodes[q]["rewards"] + [made[q][0][b]],
+                                                      value=v, running=not made[q][1][b]) for q, b, v in zip(qs, bs, vs)]
+    best = nodes[beam_select(np.array([x["value"] for x in nodes], np.float32), 1)[0]]
+    plan = list(best["path"]) + [NO_SECOND] * (int(depth) - len(best["path"]))
+    return plan[0], plan, np.float32(best["value"])
 
 
 # ------------------------------------------------------------------------------------------------ device packing

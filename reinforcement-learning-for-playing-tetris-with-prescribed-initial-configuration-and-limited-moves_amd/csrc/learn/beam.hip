@@ -26,20 +26,12 @@
 //      lower slot (at most 64 broadcast reads of the low words), it makes its move AGAIN (so no board but the parents' is
 //      kept for the 2,176 candidates), pops the window, packs the child and writes it there.  Lane 0 owns sel[0], the best.
 // After the last ply lane 0's node is the choice.  Nothing but the outputs goes to memory.
-#include "tpl_placement.h"
+// The frame -- the beam in LDS, slot decoding, phase B and the place of phase C -- is tpl_beam.h's, shared with the n-tuple beam
+// (ntuple_beam.hip); phase A's value and what a kept candidate stores are this kernel's.
+#include "tpl_beam.h"
 
 namespace tpl_learn {
 namespace {
-
-constexpr int kMaxDepth = TPL_BEAM_MAX_DEPTH;
-constexpr int kMaxWidth = TPL_BEAM_MAX_WIDTH;
-constexpr int kMaxPlacements = 34;                            // distinct placements of L, J and T
-constexpr int kMaxCandidates = kMaxWidth * kMaxPlacements;    // 2,176
-constexpr int kBeamBlock = 256;
-constexpr uint32_t kNoMove = 255u;
-constexpr uint32_t kSlotTop = 4095u;                          // low key word = kSlotTop - slot, never 0
-static_assert(kMaxCandidates <= (int)kSlotTop, "a slot fits the low word's twelve bits");
-static_assert(kMaxDepth == tpl::kWindowEntries && kMaxDepth % 4 == 0, "a path is three words of four placements");
 
 struct BeamArgs {
     const uint4* a;              // [n]
@@ -54,28 +46,6 @@ struct BeamArgs {
     float* score;                // [n], optional
 };
 
-struct Beam {
-    uint4 a[kMaxWidth], b[kMaxWidth];                         // the node's board, popped once per move made
-    float value[kMaxWidth];
-    uint32_t cleared[kMaxWidth];                              // rows cleared on the way
-    uint32_t path[kMaxWidth][kMaxDepth / 4];                  // a placement a byte, kNoMove behind the last
-};
-
-// the k-th distinct placement of piece `cur` in ascending b = 10 r + l: rotation r has location_count(cur, r) of them
-__device__ __forceinline__ uint32_t nth_placement(uint32_t cur, uint32_t k, uint32_t& r, uint32_t& l) {
-    const uint32_t last_rot = last_rotation(cur);
-    r = 0u;
-    l = k;
-#pragma unroll
-    for (int step = 0; step < 3; ++step) {
-        const uint32_t count = location_count(cur, r);
-        const bool over = l >= count && r < last_rot;
-        l -= over ? count : 0u;
-        r += over ? 1u : 0u;
-    }
-    return 10u * r + l;
-}
-
 // Candidate k of running parent q: the board the move leaves (window not yet popped), the rows cleared with the parent's, and
 // the value of psi = (cleared, won, lost, features 3..11).  Phases A and C both come here, so a winner's second making of its
 // move gives the bits of the first.
@@ -89,27 +59,6 @@ __device__ __forceinline__ float expand(const Beam& parent, uint32_t q, uint32_t
     Features psi;
     moved_features(s, cleared, true, psi);
     return placement_score(w, psi);
-}
-
-// What slot q S + k stands for: parent q, its k-th distinct placement, and whether the parent is a finished game (then slot k = 0
-// carries it and its other slots are no candidates).  Phases A and C both decode a slot here.
-struct Slot { uint32_t q, k; bool finished; };
-__device__ __forceinline__ Slot slot_of(const Beam& parent, uint32_t slot, uint32_t stride) {
-    Slot c;
-    c.q = slot / stride;
-    c.k = slot - c.q * stride;
-    c.finished = tpl::packed_state(parent.b[c.q]) != tpl::ST_RUNNING;
-    return c;
-}
-
-// the largest of a wave's 64 values, in every lane
-__device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const unsigned long long other = __shfl_xor(v, off);
-        v = other > v ? other : v;
-    }
-    return v;
 }
 
 __global__ __launch_bounds__(kBeamBlock) void placement_beam_kernel(const BeamArgs p) {
@@ -178,46 +127,13 @@ __global__ __launch_bounds__(kBeamBlock) void placement_beam_kernel(const BeamAr
         }
         __syncthreads();
 
-        // B: the min(W, count) largest keys, best first.  s_wave[round & 1] holds the largest untaken key of each wave
-        unsigned long long mine = 0ull;
-#pragma unroll 1
-        for (uint32_t slot = tid; slot < total; slot += kBeamBlock) {
-            const unsigned long long key = s_key[slot];
-            mine = key > mine ? key : mine;
-        }
-        unsigned long long wave_best = wave_max(mine);
-        if ((tid & 63u) == 0u) s_wave[0][tid >> 6] = wave_best;
-        __syncthreads();
-        uint32_t kept = 0u;
-#pragma unroll 1
-        for (uint32_t round = 0; round < p.width; ++round) {
-            unsigned long long top = 0ull;
-#pragma unroll
-            for (int v = 0; v < kBeamBlock / 64; ++v) top = s_wave[round & 1u][v] > top ? s_wave[round & 1u][v] : top;
-            if (top == 0ull) break;                            // fewer candidates than W: the same words for every lane
-            if (tid == 0) s_sel[round] = top;
-            kept = round + 1u;
-            if (wave_best == top) {                            // this wave's key was taken: its owner looks for its next one
-                if (mine == top) {
-                    mine = 0ull;
-#pragma unroll 1
-                    for (uint32_t slot = tid; slot < total; slot += kBeamBlock) {
-                        const unsigned long long key = s_key[slot];
-                        mine = key < top && key > mine ? key : mine;
-                    }
-                }
-                wave_best = wave_max(mine);
-            }
-            if ((tid & 63u) == 0u) s_wave[(round & 1u) ^ 1u][tid >> 6] = wave_best;
-            __syncthreads();
-        }
+        // B: the min(W, count) largest keys, best first
+        const uint32_t kept = select_keys(s_key, s_sel, s_wave, total, p.width, tid);
 
         // C: the kept candidates, in candidate order
         if (tid < kept) {
             const uint32_t low = (uint32_t)s_sel[tid];
-            uint32_t place = 0u;
-#pragma unroll 1
-            for (uint32_t e = 0; e < kept; ++e) place += (uint32_t)s_sel[e] > low ? 1u : 0u;
+            const uint32_t place = place_of(s_sel, kept, low);
             const Slot c = slot_of(parent, kSlotTop - low, stride);
             const uint32_t q = c.q;
             uint32_t path[kMaxDepth / 4];
@@ -239,10 +155,7 @@ __global__ __launch_bounds__(kBeamBlock) void placement_beam_kernel(const BeamAr
                 child.b[place] = B;
                 child.value[place] = value;
                 child.cleared[place] = cleared;
-                // byte `ply` of the path: 0xFF -> b.  ply is the same for the whole block, the word is picked by selects
-                const uint32_t put = ~((kNoMove ^ b) << (8u * (ply & 3u)));
-#pragma unroll
-                for (int j = 0; j < kMaxDepth / 4; ++j) path[j] &= (ply >> 2) == (uint32_t)j ? put : 0xFFFFFFFFu;
+                path_append(path, ply, b);
             }
 #pragma unroll
             for (int j = 0; j < kMaxDepth / 4; ++j) child.path[place][j] = path[j];

@@ -52,111 +52,19 @@
 // Shape3x3, 144 windows of three columns by three rows, eight (symmetric: sixteen) gathers or adds in flight per trip over 18
 // rows.  The update bodies take the kernel's argument struct BY VALUE: by reference those kernels came out 18 instructions longer.
 // The shape is an argument of the _shaped entries only; it picks the kernel on the host and is never seen on the device.
+// The traits, ntuple_sum and ntuple_value live in tpl_ntuple.h, which the n-tuple beam (ntuple_beam.hip) includes as well.
 #include <cmath>
 
-#include "tpl_placement.h"
+#include "tpl_ntuple.h"
 
 namespace tpl_learn {
 namespace {
-
-constexpr int kCounterLines = 16, kCounterMoves = 64;
-constexpr int kCounters = kCounterLines * kCounterMoves;      // 1,024
-
-// The geometry of a table, one trait per TPL_NTUPLE_SHAPE_*: a window of kWindowCols adjacent columns by kWindowRows rows, its
-// top-left cell at column x < kTupleCols and row y < kTupleRows, so that every window lies inside the board.  The device bodies
-// below are templates over it; each __global__ kernel names its trait.
-struct Shape2x4 {
-    static constexpr int kWindowCols = 2, kWindowRows = 4;
-    static constexpr int kTupleCols = tpl::kCols - 1;         // x = 0..8: columns x and x + 1
-    static constexpr int kTupleRows = tpl::kRows - 3;         // y = 0..16: rows y .. y + 3
-    static constexpr int kTuples = kTupleCols * kTupleRows;   // 153
-    static constexpr int kPatterns = 256;
-    static constexpr int kPieceStride = kTuples * kPatterns;
-    static constexpr int kCounterBase = 8 * kPieceStride;     // 313,344
-    // the pattern of tuple (x, y): the two columns' nibbles at row y
-    static __device__ __forceinline__ uint32_t pattern(const uint32_t (&c)[tpl::kCols], int x, uint32_t y) {
-        return ((c[x] >> y) & 15u) | (((c[x + 1] >> y) & 15u) << 4);
-    }
-    // the pattern of the reflected window: the nibbles swapped
-    static __device__ __forceinline__ uint32_t mirrored(uint32_t q) { return (q >> 4) | ((q & 15u) << 4); }
-};
-static_assert(Shape2x4::kCounterBase + kCounters == TPL_NTUPLE_ENTRIES, "the table layout of include/tpl_learn.h");
-
-struct Shape3x3 {
-    static constexpr int kWindowCols = 3, kWindowRows = 3;
-    static constexpr int kTupleCols = tpl::kCols - 2;         // x = 0..7: columns x, x + 1 and x + 2
-    static constexpr int kTupleRows = tpl::kRows - 2;         // y = 0..17: rows y .. y + 2
-    static constexpr int kTuples = kTupleCols * kTupleRows;   // 144
-    static constexpr int kPatterns = 512;
-    static constexpr int kPieceStride = kTuples * kPatterns;
-    static constexpr int kCounterBase = 8 * kPieceStride;     // 589,824
-    // the pattern of tuple (x, y): the three columns' triplets at row y
-    static __device__ __forceinline__ uint32_t pattern(const uint32_t (&c)[tpl::kCols], int x, uint32_t y) {
-        return ((c[x] >> y) & 7u) | (((c[x + 1] >> y) & 7u) << 3) | (((c[x + 2] >> y) & 7u) << 6);
-    }
-    // the pattern of the reflected window: the outer triplets swapped, the middle one stays
-    static __device__ __forceinline__ uint32_t mirrored(uint32_t q) { return (q >> 6) | (q & 0x38u) | ((q & 7u) << 6); }
-};
-static_assert(Shape3x3::kCounterBase + kCounters == TPL_NTUPLE_ENTRIES_3X3, "the table layout of include/tpl_learn.h");
 
 constexpr int kStateBlock = 256;                              // value and update: a lane per state
 constexpr int kBoardsPerBlock = 8;
 constexpr int kActBlock = kBoardsPerBlock * kActions;         // act: 320 threads, five waves, eight whole boards
 static_assert(kActBlock % 64 == 0, "a block is whole waves");
 static_assert(kCounters % kStateBlock == 0, "the counter sums are zeroed and flushed in whole rounds of a block");
-
-// k = 64 min(max(L - lines, 0), 15) + min(max(M - moves, 0), 63)
-__device__ __forceinline__ uint32_t counter_index(uint32_t L, uint32_t M, uint32_t lines, uint32_t moves) {
-    const int left_l = min(max((int)L - (int)lines, 0), kCounterLines - 1);
-    const int left_m = min(max((int)M - (int)moves, 0), kCounterMoves - 1);
-    return (uint32_t)(left_l * kCounterMoves + left_m);
-}
-
-// entry `index` of the table through a 32-bit byte offset from the (uniform) base: the largest buffer, a 3 x 3 coherence buffer, is 9.5 MB, and an
-// index the compiler has to widen costs a 64-bit shift and a 64-bit add per look-up
-template <typename T>
-__device__ __forceinline__ T* entry(T* table, uint32_t index) {
-    return (T*)((const char*)table + index * (uint32_t)sizeof(T));
-}
-
-// The index of pattern q of tuple (x, y) among the rows of the piece that start at `base`, a multiple of kPatterns: the row,
-// then q in its low eight (3 x 3: nine) bits.  | q and not + q: the sum is the same, but as a function's + the compiler reassociates it and then
-// addresses the gathers with 64-bit adds (172 vector instructions for 156 in ntuple_value_kernel).
-template <typename S>
-__device__ __forceinline__ uint32_t tuple_entry(uint32_t base, int x, uint32_t y, uint32_t q) {
-    static_assert((S::kPatterns & (S::kPatterns - 1)) == 0 && S::kPatterns == 1 << (S::kWindowCols * S::kWindowRows) &&
-                      S::kPieceStride % S::kPatterns == 0,
-                  "a row's index has the pattern's low bits clear");
-    return (base + ((uint32_t)(x * S::kTupleRows) + y) * (uint32_t)S::kPatterns) | q;
-}
-
-// The integer value of a running board with column words c (bits 20.. clear), falling piece `piece` and counter entry k: the
-// sum over the tuples with a non-zero pattern plus the counter, exact in 64 bits.
-template <typename S>
-__device__ __forceinline__ long long ntuple_sum(const uint32_t (&c)[tpl::kCols], uint32_t piece, uint32_t k, const int32_t* table) {
-    const uint32_t base = piece * (uint32_t)S::kPieceStride;
-    long long sum = *entry(table, (uint32_t)S::kCounterBase + k);
-#pragma unroll 1
-    for (uint32_t y = 0; y < (uint32_t)S::kTupleRows; ++y) {
-        int32_t v[S::kTupleCols];
-#pragma unroll
-        for (int x = 0; x < S::kTupleCols; ++x) {
-            const uint32_t q = S::pattern(c, x, y);
-            const int32_t e = *entry(table, tuple_entry<S>(base, x, y, q));
-            v[x] = q ? e : 0;
-        }
-#pragma unroll
-        for (int x = 0; x < S::kTupleCols; ++x) sum += v[x];
-    }
-    return sum;
-}
-
-// V of a state that runs: one rounding from the 64-bit sum to float32, then an exact scaling by 2^-16
-template <typename S>
-__device__ __forceinline__ float ntuple_value(const tpl::Board& s, uint32_t L, uint32_t M, const int32_t* table) {
-    const long long sum = ntuple_sum<S>(s.c, s.window & 7u, counter_index(L, M, s.lines, s.moves), table);
-    return (float)sum * 0x1p-16f;
-}
 
 struct ValueArgs {
     const uint4* a;              // [n]
@@ -542,20 +450,6 @@ __global__ __launch_bounds__(kActBlock) void ntuple_act_kernel(const ActArgs p) 
 __global__ __launch_bounds__(kActBlock) void ntuple_search_kernel(const SearchArgs p) { ntuple_policy<Shape2x4, 2>(p.act, p.second); }
 __global__ __launch_bounds__(kActBlock) void ntuple3_act_kernel(const ActArgs p) { ntuple_policy<Shape3x3, 1>(p, nullptr); }
 __global__ __launch_bounds__(kActBlock) void ntuple3_search_kernel(const SearchArgs p) { ntuple_policy<Shape3x3, 2>(p.act, p.second); }
-
-// a shape the library does not know is refused first, before any pointer is looked at
-int check_shape(const char* name, int32_t shape) {
-    if (shape != TPL_NTUPLE_SHAPE_2X4 && shape != TPL_NTUPLE_SHAPE_3X3)
-        return fail_msg(TPL_ERR_ARG, "%s: shape must be TPL_NTUPLE_SHAPE_2X4 (0) or TPL_NTUPLE_SHAPE_3X3 (1), got %d", name, (int)shape);
-    return TPL_OK;
-}
-
-// the checks the three entries share beyond check_planes
-int check_table(const char* name, const void* table) {
-    if (!table) return fail_msg(TPL_ERR_ARG, "%s: null pointer (table is required)", name);
-    if ((uintptr_t)table & 15u) return fail_msg(TPL_ERR_ARG, "%s: table must be 16-byte aligned", name);
-    return TPL_OK;
-}
 
 }  // namespace
 }  // namespace tpl_learn

@@ -12,8 +12,13 @@ learning on the device (the rule: include/tpl_learn.h; the kernels: csrc/learn/n
                                   afterstate of the action played and its value.  depth=2 searches the known next piece as well,
                                   still in one launch:  r + gamma * max_b (r_b + gamma * V)  -- the value of the afterstate itself,
                                   with the table one move further out; act(second=) gives the placement planned for that piece
+    NTupleBeamPolicy(env, table, depth, width, gamma=0.99).act()
+                                  a beam search over the pieces the window knows (up to 11 plies, up to 64 nodes a ply) with the
+                                  table at the leaves, in ONE launch: greedy, no exploration; act(score=, plan=, after=) also gives
+                                  the best leaf's folded value, its path and the one-ply afterstate of the action.  depth 1 is
+                                  NTuplePolicy's greedy choice, depth 2 with width >= 34 its depth=2
     NTupleLearner(env, gamma, rate, epsilon, seed, depth=1, lam=0.0, horizon=1, symmetric=False, coherent=False, shape="2x4")
-                                  TD(0) on afterstates: train(steps), evaluate(steps, depth=None); `table` is a plain tensor
+                                  TD(0) on afterstates: train(steps), evaluate(steps, depth=None, width=None); `table` is a plain tensor
                                   (torch.save it); a table trained at one depth can be played at the other.  horizon > 1 adds
                                   truncated TD(lambda) traces -- the error also goes, decayed by (gamma lam)^k, to the afterstates
                                   k < horizon moves back in the same episode --, symmetric=True adds every update to the entries of
@@ -39,11 +44,12 @@ from typing import Optional
 import torch
 
 from . import _learn_lib
-from ._learn_lib import NTUPLE_ENTRIES, NTUPLE_SHAPE_IDS, NTUPLE_SHAPES, NTUPLE_TRACE_MAX, check
+from ._learn_lib import (BEAM_MAX_WIDTH, NTUPLE_BEAM_MAX_DEPTH, NTUPLE_ENTRIES, NTUPLE_SHAPE_IDS, NTUPLE_SHAPES, NTUPLE_TRACE_MAX,
+                         check)
 from .lookahead import _MAX_BOARDS, _boards, _ptr, _state_ptrs
 
 __all__ = ["NTUPLE_ENTRIES", "NTUPLE_SHAPES", "ntuple_shape", "ntuple_table", "ntuple_value", "ntuple_is_symmetric", "ntuple_coherence", "ntuple_step_sizes",
-           "NTuplePolicy", "NTupleLearner"]
+           "NTuplePolicy", "NTupleBeamPolicy", "NTupleLearner"]
 
 _STATE_WON = 1                                                 # bits 28..29 of B.y: 0 running, 1 won, 2 and 3 lost
 _FINISHED_B_Y = _STATE_WON << 28                               # B.y of a state that is finished and otherwise empty
@@ -141,6 +147,15 @@ def _depth(depth) -> int:
     if isinstance(depth, bool) or depth not in (1, 2):
         raise ValueError(f"depth must be 1 or 2 (an afterstate knows its next piece and no more), got {depth!r}")
     return int(depth)
+
+
+def _beam_shape(depth, width):
+    """(depth, width) of an n-tuple beam: integers in 1 .. NTUPLE_BEAM_MAX_DEPTH and 1 .. BEAM_MAX_WIDTH."""
+    if isinstance(depth, bool) or not isinstance(depth, int) or not 1 <= depth <= NTUPLE_BEAM_MAX_DEPTH:
+        raise ValueError(f"depth must be an integer in 1 .. {NTUPLE_BEAM_MAX_DEPTH} (the leaf's piece must be a known one), got {depth!r}")
+    if isinstance(width, bool) or not isinstance(width, int) or not 1 <= width <= BEAM_MAX_WIDTH:
+        raise ValueError(f"width must be an integer in 1 .. {BEAM_MAX_WIDTH}, got {width!r}")
+    return int(depth), int(width)
 
 
 def _horizon(horizon) -> int:
@@ -276,6 +291,54 @@ class NTuplePolicy:
         return out
 
 
+class NTupleBeamPolicy:
+    """A beam search with an n-tuple table at the leaves on the resident boards of `env` (tpl_ntuple_beam; the rule is in
+    include/tpl_learn.h).  At moves = m a state's window holds 12 - m mod 10 true pieces; act() searches min(depth, one less than
+    that) plies -- the leaf is valued under the piece that falls next, which must be a known one.  Every ply expands each node of
+    the beam by the distinct placements of its current piece, values a child as the rewards on its path folded over  gamma * V
+    (env.reward_params; float32, never fused) and keeps the `width` best in candidate order; the action is the first placement of
+    the best leaf.  Greedy: there is no exploration.  depth 1 is NTuplePolicy at epsilon 0; depth 2 with width >= 34 is
+    NTuplePolicy(depth=2).  One launch that leaves the environment as it is; `table` is read at every act(), and its shape is the
+    table's."""
+
+    def __init__(self, env, table: torch.Tensor, depth: int, width: int, gamma: float = 0.99):
+        _boards(env, "NTupleBeamPolicy")
+        self.env, self.table = env, _table(table, env.device)
+        self.depth, self.width = _beam_shape(depth, width)
+        self.gamma = _finite("gamma", gamma)
+        self.shape = ntuple_shape(self.table)
+        self._planes = None
+
+    @torch.no_grad()
+    def act(self, out: Optional[torch.Tensor] = None, score: Optional[torch.Tensor] = None,
+            plan: Optional[torch.Tensor] = None, after=None) -> torch.Tensor:
+        """uint8 [N]: the action of every resident board; `score` (float32 [N], optional) receives the chosen leaf's value and
+        `plan` (uint8 [N, depth], optional) its path: plan[:, 0] is the action, 255 fills what was not searched (a finished
+        board, a game that ends on the way, a window with fewer known pieces); `after` (a pair of int32 [N, 4] planes, optional)
+        the ONE-PLY afterstate of the action -- the board itself where it is finished --, as NTuplePolicy.act gives it.  No host
+        sync, and no allocation when `out` is given: capturable into a HIP graph."""
+        env = self.env
+        if out is None:
+            out = torch.empty(env.num_envs, dtype=torch.uint8, device=env.device)
+        env._own(out, torch.uint8, "out")
+        if score is not None:
+            env._own(score, torch.float32, "score")
+        if plan is not None:
+            env._own(plan, torch.uint8, "plan", (env.num_envs, self.depth))
+        after_a = after_b = None
+        if after is not None:
+            k, after_a, after_b = _planes(after, env.device, "after")
+            if k != env.num_envs:
+                raise ValueError(f"after must hold {env.num_envs} states")
+        if self._planes is None:
+            self._planes = _state_ptrs(env)                   # the resident planes live as long as the environment
+        stream = torch._C._cuda_getCurrentRawStream(env.device.index)
+        check(_learn_lib.lib().tpl_ntuple_beam(self._planes[0], self._planes[1], env.num_envs, env.L, env.M, *env.reward_params,
+                                               self.gamma, self.table.data_ptr(), self.depth, self.width, out.data_ptr(), _ptr(plan),
+                                               _ptr(score), _ptr(after_a), _ptr(after_b), NTUPLE_SHAPE_IDS[self.shape], stream))
+        return out
+
+
 class NTupleLearner:
     """TD(0) on afterstates with an n-tuple table, entirely on the device.  `env`: an auto-reset environment with a
     configuration pool.  Each step of train() is one loop body -- no host sync, nothing allocated:
@@ -394,22 +457,30 @@ class NTupleLearner:
         return self.steps
 
     @torch.no_grad()
-    def evaluate(self, steps: int, depth: Optional[int] = None) -> dict:
+    def evaluate(self, steps: int, depth: Optional[int] = None, width: Optional[int] = None) -> dict:
         """Play `steps` greedy steps from a full reset and count: episodes (the steps' done flags), wins (the afterstates of the
         moves played whose state is "won": every reward parameter counts the same wins) and win_rate = wins / max(episodes, 1).
         depth: how deep the greedy policy searches -- None: the learner's own; 1 or 2 plays the table as it stands at that depth.
-        The tallies stay on the device, with one sync at the end.  Training goes on from the boards this leaves, with nothing
-        kept."""
+        width: None, or a beam width -- then NTupleBeamPolicy(depth, width) plays the table, `depth` must be given and may be
+        1 .. 11.  The tallies stay on the device, with one sync at the end.  Training goes on from the boards this leaves, with
+        nothing kept."""
         steps = _count("steps", steps, 1)
         env, d = self.env, self.env.device
         greedy = self.greedy
-        if depth is not None and _depth(depth) != self.depth:
-            greedy = NTuplePolicy(env, self.table, greedy.gamma, 0.0, greedy.seed, depth)
+        if width is not None:
+            if depth is None:
+                raise ValueError("evaluate(width=...) plays a beam: depth must be given with it (1 .. 11)")
+            beam = NTupleBeamPolicy(env, self.table, *_beam_shape(depth, width), gamma=greedy.gamma)
+            act = lambda: beam.act(out=self._action, after=self._next)
+        else:
+            if depth is not None and _depth(depth) != self.depth:
+                greedy = NTuplePolicy(env, self.table, greedy.gamma, 0.0, greedy.seed, depth)
+            act = lambda: greedy.act(out=self._action, after=self._next, step=0)
         episodes = torch.zeros(env.num_envs, dtype=torch.int32, device=d)
         wins = torch.zeros(env.num_envs, dtype=torch.int32, device=d)
         env.reset()
         for _ in range(steps):
-            env.step_into(greedy.act(out=self._action, after=self._next, step=0), self._reward, self._done)
+            env.step_into(act(), self._reward, self._done)
             episodes += self._done
             wins += ((self._next[1][:, 1] >> 28) & 3) == _STATE_WON          # an auto-reset board runs whenever it is asked to act
         self.forget()

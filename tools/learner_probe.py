@@ -84,6 +84,13 @@ Parts:
     ntuple_shape_sweep  part ntuple_trace_sweep's set-up unchanged (pool, seed, reward, epsilon, gamma, budget, evaluation): the 2 x 4
               TD(0) baseline at rate 16 re-run, then shape 3 x 3 at rates 4, 8, 16 and 32 as TD(0), lambda 0.5 / horizon 8 and
               symmetric lambda 0.8 / horizon 4; the best 3 x 3 table is also played at depth 2
+    ntuple_beam    the n-tuple beam search: tpl_ntuple_beam at 2^20 boards (L=10 / M=40, mid-game, a random table of each shape) for
+              (depth, width) in (1, 1), (2, 34), (3, 8), (4, 16), (6, 16), (11, 64) beside tpl_ntuple_act and tpl_ntuple_search on the
+              same boards and tpl_placement_beam at the same (depth, width), alternated over three rounds; the price is (tuples in
+              use) x (moves per board, by the windows' known pieces and placement counts) gathers at the rate act and search resolve
+              theirs in the same run; the ratio to tpl_ntuple_search at (2, 34), where both make the same moves and gathers; win
+              rates of part ntuple_shape_sweep's TD(0) tables (2 x 4 and 3 x 3, rate 16, one seed) on the L=10 / M=40 carved pool
+              at depth 1, at depth 2 and with beams (3, 8), (4, 16) and (6, 16)
     ntuple_shape_ab  --parent LIB: the nine 2 x 4 n-tuple kernels of another build of the learner library against this tree's, both
               loaded into one process: the outputs of the six entries compared byte for byte on the ring of part ntuple_shape
               at 2^18 boards, then each entry timed in five rounds of the parent against itself and five of the parent against
@@ -103,7 +110,7 @@ HBM_ACHIEVABLE = 6.3e12
 PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600, "priority": 600, "nstep": 600, "mirror": 600, "afterstates": 600,
          "heuristic": 600, "search": 900, "beam": 900, "ntuple": 900,
          "ntuple_search": 900, "ntuple_trace": 600, "ntuple_trace_sweep": 1100, "ntuple_coherent": 600,
-         "ntuple_coherent_sweep": 1700, "ntuple_shape": 600, "ntuple_shape_sweep": 1100}
+         "ntuple_coherent_sweep": 1700, "ntuple_shape": 600, "ntuple_shape_sweep": 1100, "ntuple_beam": 1100}
 SCATTERED_ATOMICS = 0.08e12                                 # 64 lanes of a wave adding into 64 rows (float adds; integer adds unmeasured)
 VALU_CYCLES, SIMDS, CLOCK_HZ = 3.3, 1024, 2.4e9           # the move's instruction mix, 256 CUs x 4, the clock
 
@@ -778,15 +785,16 @@ def part_search(rounds=5):
 BEAM_SHAPES = ((2, 34), (3, 8), (4, 16), (6, 16), (12, 64))
 
 
-def _beam_model(a, b, depth, width):
+def _beam_model(a, b, depth, width, known=12):
     """Moves per board the two rules make on the states (a, b) (uint32 [n, 4] planes), by the known pieces of every window and
-    the distinct placements of each: (beam at (depth, width), two-ply search), means over all boards (a finished board: 0)."""
+    the distinct placements of each: (beam at (depth, width), two-ply search), means over all boards (a finished board: 0).
+    known: the plies a fresh window allows -- 12 for the placement beam, 11 for the n-tuple beam, whose leaf reads one piece more."""
     import numpy as np
     count = np.array([17, 34, 34, 34, 17, 17, 9, 9], np.int64)
     running = ((b[:, 1] >> 28) & 3) == 0
     moves = ((a[:, 1] >> 28) | ((a[:, 3] >> 28) << 4)).astype(np.int64)
     window = b[:, 3].astype(np.uint64) | ((b[:, 2] >> 28).astype(np.uint64) << np.uint64(32))
-    plies = np.where(running, np.minimum(depth, 12 - moves % 10), 0)
+    plies = np.where(running, np.minimum(depth, known - moves % 10), 0)
     nodes, total = np.ones(a.shape[0], np.int64), np.zeros(a.shape[0], np.int64)
     for j in range(depth):
         c = count[((window >> np.uint64(3 * j)) & np.uint64(7)).astype(np.int64)]
@@ -1571,6 +1579,107 @@ def part_ntuple_shape_sweep(eval_steps=12288):
     env.terminate()
     return dict(part="ntuple_shape_sweep", boards=4096, seed=11, pool=1 << 16, pool_seed=7, reward=list(NTUPLE_LARGE_REWARD), gamma=1.0,
                 epsilon=0.05, eval_steps=eval_steps, baseline=baseline, best=runs[at], best_played=deep, runs=runs)
+
+
+NTUPLE_BEAM_SHAPES = ((1, 1), (2, 34), (3, 8), (4, 16), (6, 16), (11, 64))
+
+
+def part_ntuple_beam(rounds=3, n=1 << 20, eval_steps=12288):
+    import numpy as np
+    import torch
+    import tetris_piclim as T
+    m = T._learn_lib
+    classical = np.array([4, 100, -100, -8, -1, 0, -2, -3, -6, -3, -2, -1], np.float32) * np.float32(0.1)
+    gamma = 0.99
+    env = T.BatchedTetris(10, 40, n, device="cuda:0", seed=1, auto_reset=True)
+    env.load_configs(*env.synthetic_configs(4096))
+    env.reset()
+    for t in range(6):                                           # mid-game boards
+        env.step(env.synthetic_actions(t), observe=False)
+    a, b = (x.cpu().numpy().view(np.uint32) for x in env.raw_planes())
+    action = torch.empty(n, dtype=torch.uint8, device="cuda:0")
+    placement = {shape: T.BeamPolicy(env, classical, *shape) for shape in NTUPLE_BEAM_SHAPES}
+    sample = {k: v[:4096].cpu().numpy() for k, v in env.packed_state().items()}
+    count = np.array([17, 34, 34, 34, 17, 17, 9, 9], np.int64)
+    running = ((b[:, 1] >> 28) & 3) == 0
+    window = b[:, 3].astype(np.uint64) | ((b[:, 2] >> 28).astype(np.uint64) << np.uint64(32))
+    first = np.where(running, count[(window & np.uint64(7)).astype(np.int64)], 0)
+    out = dict(part="ntuple_beam", boards=n, rounds=rounds, gamma=gamma,
+               model="a ply costs (tuples in use) x (placements) x (nodes) gathers, at the rate act and search resolve theirs in this run")
+    shapes = []
+    for name in ("2x4", "3x3"):
+        entries = m.NTUPLE_SHAPES[name][2]
+        table = torch.from_numpy(np.random.default_rng(0).integers(-(1 << 20), (1 << 20) + 1, entries).astype(np.int32)).to("cuda:0")
+        _, used = m.ntuple_indices(sample["rows"].view(np.uint16), sample["cur"], 10, 40, sample["lines"], sample["moves"], name)
+        in_use = float(used.sum(axis=1).mean())                  # of the root boards: a child holds one piece more
+        act, search = T.NTuplePolicy(env, table, gamma=gamma), T.NTuplePolicy(env, table, gamma=gamma, depth=2)
+        beams = {shape: T.NTupleBeamPolicy(env, table, *shape, gamma=gamma) for shape in NTUPLE_BEAM_SHAPES}
+        reps = {shape: 10 if shape[0] <= 2 else 3 if shape[1] < 64 else 1 for shape in NTUPLE_BEAM_SHAPES}
+        times = {k: [] for k in ["act", "search"] + [("ntuple",) + s for s in NTUPLE_BEAM_SHAPES] + [("placement",) + s for s in NTUPLE_BEAM_SHAPES]}
+        for _ in range(rounds):                                  # alternate the kernels round by round
+            times["act"].append(_timed(lambda: act.act(out=action, step=0), 10, warmup=1))
+            times["search"].append(_timed(lambda: search.act(out=action, step=0), 10, warmup=1))
+            for shape in NTUPLE_BEAM_SHAPES:
+                times[("ntuple",) + shape].append(_timed(lambda: beams[shape].act(out=action), reps[shape], warmup=1))
+                times[("placement",) + shape].append(_timed(lambda: placement[shape].act(out=action), reps[shape], warmup=1))
+        med = {k: sorted(v)[rounds // 2] for k, v in times.items()}
+        act_moves = float(first.mean())
+        _, search_moves, _ = _beam_model(a, b, 2, 34, known=11)
+        rate_act = n * act_moves * in_use / med["act"]
+        rate_search = n * search_moves * in_use / med["search"]
+        row = dict(shape=name, tuples_in_use_per_board=round(in_use, 1), act_us=_spread(times["act"]), search_us=_spread(times["search"]),
+                   act_moves_per_board=round(act_moves, 1), search_moves_per_board=round(search_moves, 1),
+                   act_gathers_per_s=float(f"{rate_act:.3g}"), search_gathers_per_s=float(f"{rate_search:.3g}"))
+        for shape in NTUPLE_BEAM_SHAPES:
+            t = med[("ntuple",) + shape]
+            moves, _, plies = _beam_model(a, b, *shape, known=11)
+            gathers = n * moves * in_use
+            row[f"{shape[0]}x{shape[1]}"] = dict(
+                us=_spread(times[("ntuple",) + shape]), launches_per_timing=reps[shape], mean_plies=round(plies, 2),
+                moves_per_board=round(moves, 1), gathers_per_s=float(f"{gathers / t:.3g}"),
+                predicted_ms_at_act_rate=round(gathers / rate_act * 1e3, 2), predicted_ms_at_search_rate=round(gathers / rate_search * 1e3, 2),
+                measured_over_predicted_at_search_rate=round(t / (gathers / rate_search), 3),
+                over_ntuple_search=round(t / med["search"], 3), over_ntuple_act=round(t / med["act"], 3),
+                placement_beam_us=_spread(times[("placement",) + shape]),
+                over_placement_beam=round(t / med[("placement",) + shape], 3))
+        shapes.append(row)
+        print(json.dumps(row), file=sys.stderr, flush=True)      # progress: a long part must not stay silent
+        del table, beams
+    env.terminate()
+    torch.cuda.empty_cache()
+    out["act"] = shapes
+
+    # play strength: part ntuple_shape_sweep's TD(0) run at rate 16 (the zero table played, 10,000 steps, an evaluation, 30,000
+    # steps) for each shape, then the table played at every depth
+    gen_env = T.BatchedTetris(10, 40, 64, device="cuda:0", seed=7)
+    big = gen_env.carved_configs(1 << 16, seed=7)
+    gen_env.terminate()
+
+    def result(r, seconds):
+        p = r["win_rate"]
+        return dict(episodes=r["episodes"], wins=r["wins"], win_rate=round(p, 5),
+                    standard_error=round((p * (1 - p) / max(r["episodes"], 1)) ** 0.5, 6), seconds=round(seconds, 2))
+
+    played = []
+    for name in ("2x4", "3x3"):
+        env = T.BatchedTetris(10, 40, 4096, device="cuda:0", seed=11, auto_reset=True, reward=NTUPLE_LARGE_REWARD, config_pool=big)
+        learner = T.NTupleLearner(env, seed=11, gamma=1.0, epsilon=0.05, rate=16.0, shape=name)
+        learner.evaluate(eval_steps)
+        learner.train(10000)
+        learner.evaluate(eval_steps)
+        learner.train(30000)
+        got = dict(shape=name, rate=16.0, steps=learner.steps, entries_in_use=int((learner.table != 0).sum()))
+        for depth, width in ((1, None), (2, None), (3, 8), (4, 16), (6, 16)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            r = learner.evaluate(eval_steps, depth=depth, width=width)
+            got[f"depth{depth}" + (f"_width{width}" if width else "")] = result(r, time.perf_counter() - t0)
+            print(json.dumps({name: got}), file=sys.stderr, flush=True)
+        played.append(got)
+        env.terminate()
+    out["l10_m40"] = dict(boards=4096, seed=11, pool=1 << 16, pool_seed=7, reward=list(NTUPLE_LARGE_REWARD), gamma=1.0, epsilon=0.05,
+                          eval_steps=eval_steps, tables=played)
+    return out
 
 
 def part_ntuple_shape_ab(parent, rounds=5, reps=20, n=1 << 18):
