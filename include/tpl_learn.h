@@ -590,6 +590,50 @@ int tpl_ntuple_beam(const void* plane_a, const void* plane_b, int64_t n, int32_t
                     float r_lose, float gamma, const int32_t* table, int32_t depth, int32_t width, uint8_t* action, uint8_t* plan,
                     float* score, void* after_a, void* after_b, int32_t shape, void* stream);
 
+/* Two shapes summed in one value: the standard form of an n-tuple network, a 2 x 4 and a 3 x 3 table read for the same board.
+ *
+ * SUM TABLE: one int32 buffer of TPL_NTUPLE_ENTRIES_SUM = TPL_NTUPLE_ENTRIES + TPL_NTUPLE_ENTRIES_3X3 = 905,216 entries
+ * (3,620,864 bytes), 16-byte aligned, in units of 2^-16: a whole 2 x 4 table at entry 0, then a whole 3 x 3 table at entry
+ * 314,368 (byte 1,257,472, a multiple of 16), each with its own 1,024 counters.  Each part is by itself a valid table of its
+ * shape for every entry above.
+ * Value:   V(s) = float32(S_2x4 + S_3x3) * 2^-16   for a running s, 0 otherwise
+ *   -- each S the exact 64-bit sum of its part as stated above: the non-empty tuples of the part's windows under the falling
+ *   piece, plus the part's counter entry (the same k in both).  The two integers are added BEFORE the one rounding; this is not
+ *   float32(S_2x4) + float32(S_3x3), which rounds twice and differs from it on sums wider than 24 bits.
+ * Everything else is the rule of the entry of the same name with this V in place of the table's: the scores r + gamma V of
+ * tpl_ntuple_act, the two-ply Q of tpl_ntuple_search, the fold, the candidates, the ties and the effective depth of
+ * tpl_ntuple_beam; the epsilon draw, `second`, `plan`, `after` and `value`.  With one part all zero every output is, bit for bit,
+ * what the other part gives under the entry of its shape.
+ * Update: there is no new entry, and the layout is why.  The update kernels never read the table, so a TD error e of the summed
+ * value is applied by sending the same error array through the _shaped update entry once per part: TPL_NTUPLE_SHAPE_2X4 at the
+ * buffer's base, TPL_NTUPLE_SHAPE_3X3 at entry TPL_NTUPLE_ENTRIES.  This holds for tpl_ntuple_update_shaped, for
+ * tpl_ntuple_update_trace_shaped (with symmetric != 0 each part under its own sigma, so a sum table is mirror-symmetric when both
+ * parts are) and for tpl_ntuple_update_coherent_shaped, whose buffer is int64 [TPL_NTUPLE_ENTRIES_SUM][2] (14,483,456 bytes) laid
+ * out the same way: the second part at entry 314,368, byte 5,029,888, again a multiple of 16.  Every add is an integer add of a
+ * value that depends on no table entry, so the bytes of both buffers are the same whatever order the adds -- and the two calls'
+ * kernels -- arrive in.  A state adds to the entries of both parts, about twice as many as under one shape: the step of V per unit
+ * of rate roughly doubles, as it does under symmetry.
+ *
+ * Each _sum entry takes the arguments of the entry of the same name (tpl_ntuple_beam_sum: tpl_ntuple_beam's without `shape`), with
+ * `table` a sum table, and refuses what that entry refuses, in its order, under its own name, before any HIP call.  The sum is NOT
+ * a third tpl_ntuple_shape: tpl_ntuple_entries(2) stays -1 and the _shaped entries keep refusing it.  One kernel each
+ * (ntuple_sum_value_kernel, ntuple_sum_act_kernel, ntuple_sum_search_kernel: csrc/learn/ntuple.hip; ntuple_beam_sum_kernel:
+ * csrc/learn/ntuple_beam.hip) in the frames of their twins: the same device bodies under a composite geometry whose board sum is
+ * the two parts' gather loops one after the other, from one table pointer. */
+#define TPL_NTUPLE_ENTRIES_SUM (TPL_NTUPLE_ENTRIES + TPL_NTUPLE_ENTRIES_3X3)
+int tpl_ntuple_value_sum(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const int32_t* table,
+                         float* value, void* stream);
+int tpl_ntuple_act_sum(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line, float r_win,
+                       float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed, uint64_t step,
+                       uint8_t* action, float* score, void* after_a, void* after_b, float* value, void* stream);
+int tpl_ntuple_search_sum(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line, float r_win,
+                          float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed, uint64_t step,
+                          uint8_t* action, uint8_t* second, float* score, void* after_a, void* after_b, float* value,
+                          void* stream);
+int tpl_ntuple_beam_sum(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line, float r_win,
+                        float r_lose, float gamma, const int32_t* table, int32_t depth, int32_t width, uint8_t* action,
+                        uint8_t* plan, float* score, void* after_a, void* after_b, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,7 @@ LEARN_SYMBOLS = [
     "tpl_ntuple_search", "tpl_ntuple_update_trace", "tpl_ntuple_update_coherent", "tpl_ntuple_entries",
     "tpl_ntuple_value_shaped", "tpl_ntuple_act_shaped", "tpl_ntuple_search_shaped", "tpl_ntuple_update_shaped",
     "tpl_ntuple_update_trace_shaped", "tpl_ntuple_update_coherent_shaped", "tpl_ntuple_beam",
+    "tpl_ntuple_value_sum", "tpl_ntuple_act_sum", "tpl_ntuple_search_sum", "tpl_ntuple_beam_sum",
 ]
 NSTEP_MAX = 16
 BEAM_MAX_DEPTH, BEAM_MAX_WIDTH = 12, 64
@@ -156,6 +157,12 @@ def lib() -> C.CDLL:
         twin.restype = i32
     L.tpl_ntuple_beam.argtypes = [vp, vp, i64, i32, i32, f32, f32, f32, f32, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp]
     L.tpl_ntuple_beam.restype = i32
+    for name in ("tpl_ntuple_value", "tpl_ntuple_act", "tpl_ntuple_search"):      # a sum table: the unshaped twin's arguments
+        twin = getattr(L, name + "_sum")
+        twin.argtypes = getattr(L, name).argtypes
+        twin.restype = i32
+    L.tpl_ntuple_beam_sum.argtypes = L.tpl_ntuple_beam.argtypes[:-2] + [vp]      # tpl_ntuple_beam's without `shape`
+    L.tpl_ntuple_beam_sum.restype = i32
     for name in ("tpl_replay_push", "tpl_replay_sample", "tpl_learn_pack", "tpl_priority_init", "tpl_priority_push",
                  "tpl_priority_update", "tpl_replay_sample_prioritized", "tpl_replay_sample_nstep", "tpl_replay_sample_mirror",
                  "tpl_mirror_states", "tpl_afterstates", "tpl_placement_features", "tpl_placement_act",
@@ -538,22 +545,50 @@ NTUPLE_ENTRIES = NTUPLE_COUNTER_BASE + NTUPLE_COUNTERS                          
 NTUPLE_SHAPES = {"2x4": (153, 256, 314368), "3x3": (144, 512, 590848)}
 NTUPLE_SHAPE_IDS = {"2x4": 0, "3x3": 1}
 _WINDOWS = {"2x4": (2, 4), "3x3": (3, 3)}                  # (columns, rows) of a window
+# the sums of shapes in one value: name -> the shapes of its parts, whose tables lie one behind the other in a SUM TABLE; a sum is
+# no `shape` of the C interface (NTUPLE_SHAPE_IDS has none for it): the _sum entries read it, the updates take it part by part
+NTUPLE_SUMS = {"2x4+3x3": ("2x4", "3x3")}
+NTUPLE_ENTRIES_SUM = NTUPLE_SHAPES["2x4"][2] + NTUPLE_SHAPES["3x3"][2]                     # 905,216
 NTUPLE_STEP_MAX = 1 << 24                                                               # |d| of one update is clamped to it
 PIECE_PLACEMENTS = (17, 34, 34, 34, 17, 17, 9, 9)        # S: the distinct placements of each piece id (7 reads O's entry)
 
 
 def _ntuple_shape(shape) -> str:
-    if not isinstance(shape, str) or shape not in NTUPLE_SHAPES:
-        raise ValueError(f"shape must be one of {sorted(NTUPLE_SHAPES)}, got {shape!r}")
+    if not isinstance(shape, str) or (shape not in NTUPLE_SHAPES and shape not in NTUPLE_SUMS):
+        raise ValueError(f"shape must be one of {sorted(NTUPLE_SHAPES) + sorted(NTUPLE_SUMS)}, got {shape!r}")
     return shape
 
 
+def ntuple_parts_of(shape: str) -> tuple:
+    """The shapes whose tables a table of `shape` consists of, in the order they lie in it: the shape itself, or a sum's parts."""
+    return NTUPLE_SUMS.get(_ntuple_shape(shape), (shape,))
+
+
+def ntuple_entries_of(shape: str) -> int:
+    """The entries of a table of `shape`: a sum table holds its parts' tables whole, one behind the other."""
+    return sum(NTUPLE_SHAPES[part][2] for part in ntuple_parts_of(shape))
+
+
+def _ntuple_counts() -> dict:
+    """Entry count -> name, for every shape and every sum."""
+    return {ntuple_entries_of(name): name for name in list(NTUPLE_SHAPES) + list(NTUPLE_SUMS)}
+
+
 def ntuple_shape_of(entries: int) -> str:
-    """The shape whose table has `entries` entries; anything else is refused."""
-    for name, (_, _, count) in NTUPLE_SHAPES.items():
-        if entries == count:
-            return name
-    raise ValueError(f"no table shape has {entries} entries: {({k: v[2] for k, v in NTUPLE_SHAPES.items()})}")
+    """The shape (or sum of shapes) whose table has `entries` entries; anything else is refused."""
+    counts = _ntuple_counts()
+    if entries in counts:
+        return counts[entries]
+    raise ValueError(f"no table shape has {entries} entries: {({v: k for k, v in counts.items()})}")
+
+
+def _counter_columns(shape: str) -> list:
+    """The columns of ntuple_indices(shape=...) that hold a counter entry: the last one of every part."""
+    columns, at = [], 0
+    for part in ntuple_parts_of(shape):
+        at += NTUPLE_SHAPES[part][0] + 1
+        columns.append(at - 1)
+    return columns
 
 
 def ntuple_indices(rows, piece, L: int, M: int, lines, moves, shape: str = "2x4"):
@@ -562,8 +597,18 @@ def ntuple_indices(rows, piece, L: int, M: int, lines, moves, shape: str = "2x4"
     at index (piece * 153 + t) * 256 + q, used where q != 0; column 153 is the counter entry 313,344 + 64 min(max(L - lines, 0),
     15) + min(max(M - moves, 0), 63), always used.  rows: uint16 [K, 20] or [20] row masks (bit x = column x, row 0 = top).
     shape="3x3": [K, 145]; column t < 144 is tuple t = 18 x + y, x < 8 and y < 18 -- cell (row y + j, column x + i) is bit 3 i + j
-    of q, i and j < 3 -- at index (piece * 144 + t) * 512 + q; column 144 is the counter entry 589,824 + the same k."""
-    tuples, patterns, entries = NTUPLE_SHAPES[_ntuple_shape(shape)]
+    of q, i and j < 3 -- at index (piece * 144 + t) * 512 + q; column 144 is the counter entry 589,824 + the same k.
+    shape="2x4+3x3", a sum table: [K, 154 + 145] -- the 2 x 4 columns, then the 3 x 3 columns with 314,368, the entry where the second
+    part starts, added to every index; `used` likewise.  Both parts' counter columns are used."""
+    if _ntuple_shape(shape) in NTUPLE_SUMS:
+        index, used, at = [], [], 0
+        for part in NTUPLE_SUMS[shape]:
+            i, u = ntuple_indices(rows, piece, L, M, lines, moves, part)
+            index.append(i + at)
+            used.append(u)
+            at += NTUPLE_SHAPES[part][2]
+        return np.concatenate(index, axis=1), np.concatenate(used, axis=1)
+    tuples, patterns, entries = NTUPLE_SHAPES[shape]
     wide, high = _WINDOWS[shape]
     rows = np.asarray(rows)
     if rows.ndim == 1:
@@ -593,8 +638,9 @@ def ntuple_indices(rows, piece, L: int, M: int, lines, moves, shape: str = "2x4"
 
 def _ntuple_table(table) -> np.ndarray:
     if (not isinstance(table, np.ndarray) or table.dtype != np.int32 or table.ndim != 1
-            or table.shape[0] not in [v[2] for v in NTUPLE_SHAPES.values()]):
-        raise ValueError(f"table must be an int32 array of {NTUPLE_ENTRIES} entries (3x3: {NTUPLE_SHAPES['3x3'][2]})")
+            or table.shape[0] not in _ntuple_counts()):
+        raise ValueError(f"table must be an int32 array of {NTUPLE_ENTRIES} entries (3x3: {NTUPLE_SHAPES['3x3'][2]}, "
+                         f"2x4+3x3: {NTUPLE_ENTRIES_SUM})")
     return table
 
 
@@ -605,7 +651,7 @@ def _table_shape(table) -> str:
 
 def ntuple_value(table, rows, piece, L: int, M: int, lines, moves, state) -> np.ndarray:
     """V of K states (float32 [K]): 0 where state != 0, else the entries ntuple_indices names summed exactly (int64), rounded
-    once to float32 and scaled by 2^-16."""
+    once to float32 and scaled by 2^-16.  Under a sum table the entries of both parts are in that one sum: one rounding."""
     index, used = ntuple_indices(rows, piece, L, M, lines, moves, _table_shape(table))
     total = np.where(used, table[index].astype(np.int64), 0).sum(axis=1)
     running = np.broadcast_to(np.asarray(state), total.shape) == 0
@@ -621,7 +667,8 @@ def ntuple_steps(error, rate) -> np.ndarray:
 
 
 def ntuple_update(table, rows, piece, L: int, M: int, lines, moves, state, error, rate) -> np.ndarray:
-    """tpl_ntuple_update, in place: every running state adds its d to the entries ntuple_indices names; the adds wrap."""
+    """tpl_ntuple_update, in place: every running state adds its d to the entries ntuple_indices names; the adds wrap.  A sum
+    table takes d on the entries of both parts: tpl_ntuple_update_shaped once per part with the same errors."""
     index, used = ntuple_indices(rows, piece, L, M, lines, moves, _table_shape(table))
     d = np.where(np.broadcast_to(np.asarray(state), index.shape[:1]) == 0, ntuple_steps(error, rate), 0)
     used = used & (d != 0)[:, None]
@@ -645,12 +692,19 @@ _sigma_of = {}                                          # ntuple_mirror_permutat
 
 
 def ntuple_mirror_permutation(shape: str = "2x4") -> np.ndarray:
-    """sigma (int64 [entries of the shape]): the index of tuple[p][17 x + y][q] -> that of tuple[pi(p)][17 (8 - x) + y][swap(q)],
+    """shape="2x4+3x3": each part's sigma, the second offset by where its part starts.  Otherwise:
+    sigma (int64 [entries of the shape]): the index of tuple[p][17 x + y][q] -> that of tuple[pi(p)][17 (8 - x) + y][swap(q)],
     with pi = PIECE_MIRROR and swap(q) = (q >> 4) | ((q & 15) << 4) (3x3: 18 (7 - x) + y, and swap exchanges bits 0..2 with bits
     6..8); the counter indices stay.  A table is mirror-symmetric when table[sigma] == table.
     Built from its definition, not from that closed form: every tuple entry (p, t, q) is put on a board as the cells of its
     window, and its image is the index ntuple_indices gives the reflected rows under pi(p) at the reflected window."""
-    tuples, patterns, entries = NTUPLE_SHAPES[_ntuple_shape(shape)]
+    if _ntuple_shape(shape) in NTUPLE_SUMS:
+        parts, at = [], 0
+        for part in NTUPLE_SUMS[shape]:
+            parts.append(ntuple_mirror_permutation(part) + at)
+            at += NTUPLE_SHAPES[part][2]
+        return np.concatenate(parts)
+    tuples, patterns, entries = NTUPLE_SHAPES[shape]
     if shape in _sigma_of:
         return _sigma_of[shape].copy()
     wide, high = _WINDOWS[shape]
@@ -681,7 +735,7 @@ def ntuple_update_trace(table, ages, L: int, M: int, error, rate, decay, symmetr
     entries of the REFLECTED rows (columns reversed, piece through PIECE_MIRROR) as well -- not through sigma --; the counter is
     added once."""
     tab, shape = _ntuple_table(table).view(np.uint32), _table_shape(table)
-    tuples = NTUPLE_SHAPES[shape][0]
+    counters = _counter_columns(shape)
     e = np.asarray(error, dtype=np.float32).reshape(-1)
     open_ = np.ones(e.shape, dtype=bool)
     w, decay = np.float32(1.0), np.float32(decay)
@@ -697,7 +751,7 @@ def ntuple_update_trace(table, ages, L: int, M: int, error, rate, decay, symmetr
             piece = np.broadcast_to(np.asarray(piece, dtype=np.int64), e.shape)
             index, used = ntuple_indices(_reflected_rows(rows), np.array(PIECE_MIRROR)[piece], L, M, lines, moves, shape)
             used = used & (d != 0)[:, None]
-            used[:, tuples] = False               # the counter was added above, once
+            used[:, counters] = False             # the counter (of a sum table: each part's) was added above, once
             np.add.at(tab, index[used], np.broadcast_to(d[:, None], used.shape)[used].astype(np.uint32))
     return table
 
@@ -705,7 +759,7 @@ def ntuple_update_trace(table, ages, L: int, M: int, error, rate, decay, symmetr
 def _ntuple_coherence(coherence, entries=None) -> np.ndarray:
     """An int64 [entries, 2] buffer of a shape's entry count -- of `entries`, where a table says which."""
     if (not isinstance(coherence, np.ndarray) or coherence.dtype != np.int64 or coherence.ndim != 2 or coherence.shape[1] != 2
-            or coherence.shape[0] not in ([v[2] for v in NTUPLE_SHAPES.values()] if entries is None else [entries])):
+            or coherence.shape[0] not in (list(_ntuple_counts()) if entries is None else [entries])):
         raise ValueError(f"coherence must be an int64 array of shape ({NTUPLE_ENTRIES if entries is None else entries}, 2)")
     return coherence
 
@@ -735,7 +789,7 @@ def ntuple_update_coherent(table, coherence, ages, L: int, M: int, error, rate, 
     alpha is read from `coherence` as it stands at the call; entry j of a board at age k whose trace is open and whose d_k is not 0
     takes s = ntuple_coherent_steps(e, float32(rate) * w_k, alpha_j) on the table, d_k on E_j and |d_k| on A_j, all wrapping."""
     tab, shape = _ntuple_table(table).view(np.uint32), _table_shape(table)
-    tuples = NTUPLE_SHAPES[shape][0]
+    counters = _counter_columns(shape)
     sums = _ntuple_coherence(coherence, table.shape[0]).view(np.uint64)
     alpha = ntuple_step_sizes(coherence)                 # before any add of this call
     e = np.asarray(error, dtype=np.float32).reshape(-1)
@@ -752,7 +806,7 @@ def ntuple_update_coherent(table, coherence, ages, L: int, M: int, error, rate, 
         for form_rows, form_piece, counter in forms:
             index, used = ntuple_indices(form_rows, form_piece, L, M, lines, moves, shape)
             used = used & (d != 0)[:, None]
-            used[:, tuples] &= counter            # the counter is taken once, with the state's own entries
+            used[:, counters] &= counter          # the counter (each part's) is taken once, with the state's own entries
             j = index[used]
             d_j = np.broadcast_to(d[:, None], used.shape)[used]
             s_j = ntuple_coherent_steps(np.broadcast_to(e[:, None], used.shape)[used], r, alpha[j])

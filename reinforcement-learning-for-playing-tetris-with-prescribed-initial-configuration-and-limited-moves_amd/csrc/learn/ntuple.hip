@@ -1,6 +1,6 @@
 // ntuple.hip -- an n-tuple afterstate value function, its greedy / epsilon-greedy placement policy and its temporal-difference
 // update: tpl_ntuple_value, tpl_ntuple_act, tpl_ntuple_search, tpl_ntuple_update, tpl_ntuple_update_trace,
-// tpl_ntuple_update_coherent (include/tpl_learn.h states the rule).
+// tpl_ntuple_update_coherent, their _shaped twins and the _sum twins of the first three (include/tpl_learn.h states the rule).
 //
 // The value of a board is a sum of table look-ups: 153 windows of two adjacent columns by four rows, each a 256-entry row of an
 // int32 table chosen by the piece that falls next, plus one entry for the lines and moves that are left.  In the column layout a
@@ -53,6 +53,11 @@
 // rows.  The update bodies take the kernel's argument struct BY VALUE: by reference those kernels came out 18 instructions longer.
 // The shape is an argument of the _shaped entries only; it picks the kernel on the host and is never seen on the device.
 // The traits, ntuple_sum and ntuple_value live in tpl_ntuple.h, which the n-tuple beam (ntuple_beam.hip) includes as well.
+//
+// Two shapes summed (tpl_ntuple_value_sum, tpl_ntuple_act_sum, tpl_ntuple_search_sum).  ShapeSum is a composite trait: a 2 x 4
+// table and a 3 x 3 table behind one pointer, whose board sum is the two gather loops one after the other (tpl_ntuple.h).  The
+// three ntuple_sum_*_kernel are value_lane and ntuple_policy named with it, on the unchanged argument structs.  The updates have
+// no such kernel: they never read the table, so the host sends one error array through the existing kernels once per part.
 #include <cmath>
 
 #include "tpl_ntuple.h"
@@ -88,6 +93,7 @@ __device__ __forceinline__ void value_lane(const ValueArgs& p) {
 
 __global__ __launch_bounds__(kStateBlock) void ntuple_value_kernel(const ValueArgs p) { value_lane<Shape2x4>(p); }
 __global__ __launch_bounds__(kStateBlock) void ntuple3_value_kernel(const ValueArgs p) { value_lane<Shape3x3>(p); }
+__global__ __launch_bounds__(kStateBlock) void ntuple_sum_value_kernel(const ValueArgs p) { value_lane<ShapeSum>(p); }
 
 // d = (int32) rint(rate * e): the product rounded once, clamped to +-2^24, 0 for a NaN
 __device__ __forceinline__ int32_t update_step(float rate, float e) {
@@ -450,6 +456,8 @@ __global__ __launch_bounds__(kActBlock) void ntuple_act_kernel(const ActArgs p) 
 __global__ __launch_bounds__(kActBlock) void ntuple_search_kernel(const SearchArgs p) { ntuple_policy<Shape2x4, 2>(p.act, p.second); }
 __global__ __launch_bounds__(kActBlock) void ntuple3_act_kernel(const ActArgs p) { ntuple_policy<Shape3x3, 1>(p, nullptr); }
 __global__ __launch_bounds__(kActBlock) void ntuple3_search_kernel(const SearchArgs p) { ntuple_policy<Shape3x3, 2>(p.act, p.second); }
+__global__ __launch_bounds__(kActBlock) void ntuple_sum_act_kernel(const ActArgs p) { ntuple_policy<ShapeSum, 1>(p, nullptr); }
+__global__ __launch_bounds__(kActBlock) void ntuple_sum_search_kernel(const SearchArgs p) { ntuple_policy<ShapeSum, 2>(p.act, p.second); }
 
 }  // namespace
 }  // namespace tpl_learn
@@ -464,10 +472,10 @@ extern "C" int64_t tpl_ntuple_entries(int32_t shape) {
 
 namespace {
 
-// what tpl_ntuple_value and tpl_ntuple_value_shaped share: the checks and the launch
+// what tpl_ntuple_value, tpl_ntuple_value_shaped (its shape checked before it comes here) and tpl_ntuple_value_sum share: the
+// checks and the launch
 int launch_value(const char* name, const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const int32_t* table,
-                 float* value, int32_t shape, void* stream) {
-    if (const int rc = check_shape(name, shape)) return rc;
+                 float* value, Form form, void* stream) {
     if (const int rc = check_planes(name, plane_a, plane_b, n, L, M)) return rc;
     if (const int rc = check_table(name, table)) return rc;
     if (!value) return fail_msg(TPL_ERR_ARG, "%s: null pointer (value is required)", name);
@@ -476,19 +484,19 @@ int launch_value(const char* name, const void* plane_a, const void* plane_b, int
     p.a = (const uint4*)plane_a; p.b = (const uint4*)plane_b; p.n = (uint32_t)n;
     p.L = (uint32_t)L; p.M = (uint32_t)M; p.table = table; p.value = value;
     const dim3 grid((p.n + kStateBlock - 1) / kStateBlock), block(kStateBlock);
-    if (shape == TPL_NTUPLE_SHAPE_3X3) hipLaunchKernelGGL(ntuple3_value_kernel, grid, block, 0, (hipStream_t)stream, p);
+    if (form == Form::kSum) hipLaunchKernelGGL(ntuple_sum_value_kernel, grid, block, 0, (hipStream_t)stream, p);
+    else if (form == Form::k3x3) hipLaunchKernelGGL(ntuple3_value_kernel, grid, block, 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(ntuple_value_kernel, grid, block, 0, (hipStream_t)stream, p);
     TPL_LEARN_HIP(hipGetLastError());
     return TPL_OK;
 }
 
-// what tpl_ntuple_act (depth = 1, second = null) and tpl_ntuple_search (depth = 2) and their _shaped twins share: the checks
-// and the launch
+// what tpl_ntuple_act (depth = 1, second = null) and tpl_ntuple_search (depth = 2), their _shaped twins (the shape checked
+// before they come here) and their _sum twins share: the checks and the launch
 int launch_ntuple_policy(const char* name, int depth, const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M,
                          float r_line, float r_win, float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed,
                          uint64_t step, uint8_t* action, uint8_t* second, float* score, void* after_a, void* after_b, float* value,
-                         int32_t shape, void* stream) {
-    if (const int rc = check_shape(name, shape)) return rc;
+                         Form form, void* stream) {
     if (const int rc = check_planes(name, plane_a, plane_b, n, L, M)) return rc;
     if (const int rc = check_table(name, table)) return rc;
     if (!action) return fail_msg(TPL_ERR_ARG, "%s: null pointer (action is required)", name);
@@ -507,11 +515,14 @@ int launch_ntuple_policy(const char* name, int depth, const void* plane_a, const
     p.key = replay_key(seed, step);
     p.action = action; p.score = score; p.after_a = (uint4*)after_a; p.after_b = (uint4*)after_b; p.value = value;
     const dim3 grid((p.n + kBoardsPerBlock - 1) / kBoardsPerBlock), block(kActBlock);
-    const bool wide = shape == TPL_NTUPLE_SHAPE_3X3;
+    const bool wide = form == Form::k3x3;
     if (depth == 2) {
         const SearchArgs q{p, second};
-        if (wide) hipLaunchKernelGGL(ntuple3_search_kernel, grid, block, 0, (hipStream_t)stream, q);
+        if (form == Form::kSum) hipLaunchKernelGGL(ntuple_sum_search_kernel, grid, block, 0, (hipStream_t)stream, q);
+        else if (wide) hipLaunchKernelGGL(ntuple3_search_kernel, grid, block, 0, (hipStream_t)stream, q);
         else hipLaunchKernelGGL(ntuple_search_kernel, grid, block, 0, (hipStream_t)stream, q);
+    } else if (form == Form::kSum) {
+        hipLaunchKernelGGL(ntuple_sum_act_kernel, grid, block, 0, (hipStream_t)stream, p);
     } else if (wide) {
         hipLaunchKernelGGL(ntuple3_act_kernel, grid, block, 0, (hipStream_t)stream, p);
     } else {
@@ -525,27 +536,41 @@ int launch_ntuple_policy(const char* name, int depth, const void* plane_a, const
 
 extern "C" int tpl_ntuple_value(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const int32_t* table,
                                 float* value, void* stream) {
-    return launch_value("tpl_ntuple_value", plane_a, plane_b, n, L, M, table, value, TPL_NTUPLE_SHAPE_2X4, stream);
+    return launch_value("tpl_ntuple_value", plane_a, plane_b, n, L, M, table, value, Form::k2x4, stream);
 }
 
 extern "C" int tpl_ntuple_value_shaped(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M,
                                        const int32_t* table, float* value, int32_t shape, void* stream) {
-    return launch_value("tpl_ntuple_value_shaped", plane_a, plane_b, n, L, M, table, value, shape, stream);
+    if (const int rc = check_shape("tpl_ntuple_value_shaped", shape)) return rc;
+    return launch_value("tpl_ntuple_value_shaped", plane_a, plane_b, n, L, M, table, value, form_of(shape), stream);
+}
+
+extern "C" int tpl_ntuple_value_sum(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const int32_t* table,
+                                    float* value, void* stream) {
+    return launch_value("tpl_ntuple_value_sum", plane_a, plane_b, n, L, M, table, value, Form::kSum, stream);
 }
 
 extern "C" int tpl_ntuple_act(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line, float r_win,
                               float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed, uint64_t step,
                               uint8_t* action, float* score, void* after_a, void* after_b, float* value, void* stream) {
     return launch_ntuple_policy("tpl_ntuple_act", 1, plane_a, plane_b, n, L, M, r_line, r_win, r_lose, gamma, table, epsilon, seed,
-                                step, action, nullptr, score, after_a, after_b, value, TPL_NTUPLE_SHAPE_2X4, stream);
+                                step, action, nullptr, score, after_a, after_b, value, Form::k2x4, stream);
 }
 
 extern "C" int tpl_ntuple_act_shaped(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line,
                                      float r_win, float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed,
                                      uint64_t step, uint8_t* action, float* score, void* after_a, void* after_b, float* value,
                                      int32_t shape, void* stream) {
+    if (const int rc = check_shape("tpl_ntuple_act_shaped", shape)) return rc;
     return launch_ntuple_policy("tpl_ntuple_act_shaped", 1, plane_a, plane_b, n, L, M, r_line, r_win, r_lose, gamma, table, epsilon,
-                                seed, step, action, nullptr, score, after_a, after_b, value, shape, stream);
+                                seed, step, action, nullptr, score, after_a, after_b, value, form_of(shape), stream);
+}
+
+extern "C" int tpl_ntuple_act_sum(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line, float r_win,
+                                  float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed, uint64_t step,
+                                  uint8_t* action, float* score, void* after_a, void* after_b, float* value, void* stream) {
+    return launch_ntuple_policy("tpl_ntuple_act_sum", 1, plane_a, plane_b, n, L, M, r_line, r_win, r_lose, gamma, table, epsilon,
+                                seed, step, action, nullptr, score, after_a, after_b, value, Form::kSum, stream);
 }
 
 extern "C" int tpl_ntuple_search(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line,
@@ -553,15 +578,24 @@ extern "C" int tpl_ntuple_search(const void* plane_a, const void* plane_b, int64
                                  uint64_t step, uint8_t* action, uint8_t* second, float* score, void* after_a, void* after_b,
                                  float* value, void* stream) {
     return launch_ntuple_policy("tpl_ntuple_search", 2, plane_a, plane_b, n, L, M, r_line, r_win, r_lose, gamma, table, epsilon,
-                                seed, step, action, second, score, after_a, after_b, value, TPL_NTUPLE_SHAPE_2X4, stream);
+                                seed, step, action, second, score, after_a, after_b, value, Form::k2x4, stream);
 }
 
 extern "C" int tpl_ntuple_search_shaped(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line,
                                         float r_win, float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed,
                                         uint64_t step, uint8_t* action, uint8_t* second, float* score, void* after_a, void* after_b,
                                         float* value, int32_t shape, void* stream) {
+    if (const int rc = check_shape("tpl_ntuple_search_shaped", shape)) return rc;
     return launch_ntuple_policy("tpl_ntuple_search_shaped", 2, plane_a, plane_b, n, L, M, r_line, r_win, r_lose, gamma, table,
-                                epsilon, seed, step, action, second, score, after_a, after_b, value, shape, stream);
+                                epsilon, seed, step, action, second, score, after_a, after_b, value, form_of(shape), stream);
+}
+
+extern "C" int tpl_ntuple_search_sum(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line,
+                                     float r_win, float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed,
+                                     uint64_t step, uint8_t* action, uint8_t* second, float* score, void* after_a, void* after_b,
+                                     float* value, void* stream) {
+    return launch_ntuple_policy("tpl_ntuple_search_sum", 2, plane_a, plane_b, n, L, M, r_line, r_win, r_lose, gamma, table, epsilon,
+                                seed, step, action, second, score, after_a, after_b, value, Form::kSum, stream);
 }
 
 namespace {

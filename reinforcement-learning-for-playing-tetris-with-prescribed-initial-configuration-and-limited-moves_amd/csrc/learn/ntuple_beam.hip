@@ -1,5 +1,5 @@
-// ntuple_beam.hip -- a beam search over the known piece window with an n-tuple table at the leaves: tpl_ntuple_beam
-// (include/tpl_learn.h states the rule).
+// ntuple_beam.hip -- a beam search over the known piece window with an n-tuple table at the leaves: tpl_ntuple_beam and, with a
+// sum table there (ShapeSum of tpl_ntuple.h: ntuple_beam_sum_kernel), tpl_ntuple_beam_sum (include/tpl_learn.h states the rule).
 //
 // The frame is placement_beam_kernel's (tpl_beam.h; beam.hip's comment has the reasons): ONE BOARD PER WORKGROUP of 256 threads,
 // both beams and the candidate keys in LDS -- 25 KB in all, so six groups share a CU --, and a ply in three phases: A keys every
@@ -200,17 +200,19 @@ __device__ __forceinline__ void ntuple_beam(const NTupleBeamArgs& p) {
 
 __global__ __launch_bounds__(kBeamBlock) void ntuple_beam_kernel(const NTupleBeamArgs p) { ntuple_beam<Shape2x4>(p); }
 __global__ __launch_bounds__(kBeamBlock) void ntuple_beam3_kernel(const NTupleBeamArgs p) { ntuple_beam<Shape3x3>(p); }
+__global__ __launch_bounds__(kBeamBlock) void ntuple_beam_sum_kernel(const NTupleBeamArgs p) { ntuple_beam<ShapeSum>(p); }
 
 }  // namespace
 }  // namespace tpl_learn
 
 using namespace tpl_learn;
 
-extern "C" int tpl_ntuple_beam(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line, float r_win,
-                               float r_lose, float gamma, const int32_t* table, int32_t depth, int32_t width, uint8_t* action,
-                               uint8_t* plan, float* score, void* after_a, void* after_b, int32_t shape, void* stream) {
-    const char* name = "tpl_ntuple_beam";
-    if (const int rc = check_shape(name, shape)) return rc;
+namespace {
+
+// what tpl_ntuple_beam (its shape checked before it comes here) and tpl_ntuple_beam_sum share: the checks and the launch
+int launch_ntuple_beam(const char* name, const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line,
+                       float r_win, float r_lose, float gamma, const int32_t* table, int32_t depth, int32_t width, uint8_t* action,
+                       uint8_t* plan, float* score, void* after_a, void* after_b, Form form, void* stream) {
     if (const int rc = check_planes(name, plane_a, plane_b, n, L, M)) return rc;
     if (const int rc = check_table(name, table)) return rc;
     if (!action) return fail_msg(TPL_ERR_ARG, "%s: null pointer (action is required)", name);
@@ -226,8 +228,26 @@ extern "C" int tpl_ntuple_beam(const void* plane_a, const void* plane_b, int64_t
     p.L = (uint32_t)L; p.M = (uint32_t)M; p.r_line = r_line; p.r_win = r_win; p.r_lose = r_lose; p.gamma = gamma;
     p.table = table; p.depth = (uint32_t)depth; p.width = (uint32_t)width;
     p.action = action; p.plan = plan; p.score = score; p.after_a = (uint4*)after_a; p.after_b = (uint4*)after_b;
-    if (shape == TPL_NTUPLE_SHAPE_3X3) hipLaunchKernelGGL(ntuple_beam3_kernel, dim3(p.n), dim3(kBeamBlock), 0, (hipStream_t)stream, p);
+    if (form == Form::kSum) hipLaunchKernelGGL(ntuple_beam_sum_kernel, dim3(p.n), dim3(kBeamBlock), 0, (hipStream_t)stream, p);
+    else if (form == Form::k3x3) hipLaunchKernelGGL(ntuple_beam3_kernel, dim3(p.n), dim3(kBeamBlock), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(ntuple_beam_kernel, dim3(p.n), dim3(kBeamBlock), 0, (hipStream_t)stream, p);
     TPL_LEARN_HIP(hipGetLastError());
     return TPL_OK;
+}
+
+}  // namespace
+
+extern "C" int tpl_ntuple_beam(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line, float r_win,
+                               float r_lose, float gamma, const int32_t* table, int32_t depth, int32_t width, uint8_t* action,
+                               uint8_t* plan, float* score, void* after_a, void* after_b, int32_t shape, void* stream) {
+    if (const int rc = check_shape("tpl_ntuple_beam", shape)) return rc;
+    return launch_ntuple_beam("tpl_ntuple_beam", plane_a, plane_b, n, L, M, r_line, r_win, r_lose, gamma, table, depth, width, action,
+                              plan, score, after_a, after_b, form_of(shape), stream);
+}
+
+extern "C" int tpl_ntuple_beam_sum(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line,
+                                   float r_win, float r_lose, float gamma, const int32_t* table, int32_t depth, int32_t width,
+                                   uint8_t* action, uint8_t* plan, float* score, void* after_a, void* after_b, void* stream) {
+    return launch_ntuple_beam("tpl_ntuple_beam_sum", plane_a, plane_b, n, L, M, r_line, r_win, r_lose, gamma, table, depth, width,
+                              action, plan, score, after_a, after_b, Form::kSum, stream);
 }

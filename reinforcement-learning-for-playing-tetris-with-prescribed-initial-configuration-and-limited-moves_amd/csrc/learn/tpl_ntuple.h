@@ -1,6 +1,6 @@
 // tpl_ntuple.h -- what the units that read an n-tuple table share (ntuple.hip, ntuple_beam.hip; include/tpl_learn.h states the
-// rule): the geometry of the two table shapes, the counter index, the 32-bit addressing of an entry, the sum and the value of a
-// running board, and the shape and table checks of the entry points.
+// rule): the geometry of the two table shapes and of their sum, the counter index, the 32-bit addressing of an entry, the sum and
+// the value of a running board, and the shape and table checks of the entry points.
 #pragma once
 
 #include "tpl_placement.h"
@@ -93,12 +93,46 @@ __device__ __forceinline__ long long ntuple_sum(const uint32_t (&c)[tpl::kCols],
     return sum;
 }
 
+// The composite geometry of a SUM TABLE (include/tpl_learn.h): a whole table of shape First at the buffer's base, then a whole
+// table of shape Second, each with its own counters.  It has no windows of its own: the bodies that read a table (value_lane,
+// ntuple_policy, ntuple_beam) reach it through board_sum alone, so they stay written once.
+template <typename A, typename B, int kEntriesOfFirst>
+struct SumOf {
+    using First = A;
+    using Second = B;
+    static constexpr uint32_t kSecondAt = kEntriesOfFirst;    // the entry where the second part starts
+};
+using ShapeSum = SumOf<Shape2x4, Shape3x3, TPL_NTUPLE_ENTRIES>;
+static_assert(ShapeSum::kSecondAt + TPL_NTUPLE_ENTRIES_3X3 == TPL_NTUPLE_ENTRIES_SUM && (ShapeSum::kSecondAt * sizeof(int32_t)) % 16 == 0 &&
+                  (ShapeSum::kSecondAt * 2 * sizeof(int64_t)) % 16 == 0,
+              "the sum table's layout of include/tpl_learn.h: the second part is a 16-byte aligned table (and coherence buffer)");
+
+// The integer value of a running board under the table of geometry S.  A plain shape: ntuple_sum.  A sum of shapes: the two parts'
+// sums, integers added before the one rounding -- two gather loops one after the other from one (uniform) table pointer, each
+// part with its own counter base, so no more gathers are in flight than in the wider of the two.
+template <typename S>
+struct BoardSum {
+    static __device__ __forceinline__ long long of(const uint32_t (&c)[tpl::kCols], uint32_t piece, uint32_t k, const int32_t* table) {
+        return ntuple_sum<S>(c, piece, k, table);
+    }
+};
+template <typename A, typename B, int kEntriesOfFirst>
+struct BoardSum<SumOf<A, B, kEntriesOfFirst>> {
+    static __device__ __forceinline__ long long of(const uint32_t (&c)[tpl::kCols], uint32_t piece, uint32_t k, const int32_t* table) {
+        return ntuple_sum<A>(c, piece, k, table) + ntuple_sum<B>(c, piece, k, table + kEntriesOfFirst);
+    }
+};
+
 // V of a state that runs: one rounding from the 64-bit sum to float32, then an exact scaling by 2^-16
 template <typename S>
 __device__ __forceinline__ float ntuple_value(const tpl::Board& s, uint32_t L, uint32_t M, const int32_t* table) {
-    const long long sum = ntuple_sum<S>(s.c, s.window & 7u, counter_index(L, M, s.lines, s.moves), table);
+    const long long sum = BoardSum<S>::of(s.c, s.window & 7u, counter_index(L, M, s.lines, s.moves), table);
     return (float)sum * 0x1p-16f;
 }
+
+// Which kernels an entry launches: the two shapes of tpl_ntuple_shape, and their sum, which is no `shape` of the C interface.
+enum class Form { k2x4, k3x3, kSum };
+inline Form form_of(int32_t shape) { return shape == TPL_NTUPLE_SHAPE_3X3 ? Form::k3x3 : Form::k2x4; }   // after check_shape
 
 // a shape the library does not know is refused first, before any pointer is looked at
 inline int check_shape(const char* name, int32_t shape) {

@@ -3,7 +3,10 @@ learning on the device (the rule: include/tpl_learn.h; the kernels: csrc/learn/n
 
     ntuple_table(device, shape="2x4")
                                   a zeroed table: int32 [314,368], in units of 2^-16; shape="3x3": int32 [590,848]
-    ntuple_shape(table)           "2x4" or "3x3", from the table's entry count
+                                  shape="2x4+3x3": a SUM TABLE, int32 [905,216] -- a 2x4 table, then a 3x3 table, read together
+    ntuple_shape(table)           "2x4", "3x3" or "2x4+3x3", from the table's entry count
+    ntuple_parts(table)           the per-shape views of a table or a coherence buffer (one for a plain table, two for a sum):
+                                  they share its storage, and each is a valid table of its shape
     ntuple_value(source, table)   V of every resident board of an environment, or of plane pairs
     NTuplePolicy(env, table, gamma, epsilon, seed, depth=1).act()
                                   arg-max over the distinct placements of  r + gamma * V(afterstate)  in ONE launch; with epsilon a
@@ -35,6 +38,11 @@ per (lines left, moves left); the update adds rint(rate * error) to the same ent
 with one seed give the same bytes.  The window is the table's SHAPE: "2x4", two adjacent columns by four rows, or "3x3", three by
 three -- a column with both of its neighbours.  Policy, value, the symmetry test and the step sizes take the shape from the table
 (or buffer) they are given; a table of one shape cannot be played as the other.
+
+Two shapes summed ("2x4+3x3", the standard form of an n-tuple network): V = float32(S_2x4 + S_3x3) * 2^-16, the two parts' exact
+integer sums added before the one rounding.  The value, both policies and the beam read a sum table in one launch each (the _sum
+entries of include/tpl_learn.h); the update kernels never read the table, so the learner sends its errors through the existing
+update once per part.  Everything that takes a table takes a sum table, by its entry count.
 """
 from __future__ import annotations
 
@@ -44,42 +52,58 @@ from typing import Optional
 import torch
 
 from . import _learn_lib
-from ._learn_lib import (BEAM_MAX_WIDTH, NTUPLE_BEAM_MAX_DEPTH, NTUPLE_ENTRIES, NTUPLE_SHAPE_IDS, NTUPLE_SHAPES, NTUPLE_TRACE_MAX,
-                         check)
+from ._learn_lib import (BEAM_MAX_WIDTH, NTUPLE_BEAM_MAX_DEPTH, NTUPLE_ENTRIES, NTUPLE_ENTRIES_SUM, NTUPLE_SHAPE_IDS, NTUPLE_SHAPES,
+                         NTUPLE_SUMS, NTUPLE_TRACE_MAX, check)
 from .lookahead import _MAX_BOARDS, _boards, _ptr, _state_ptrs
 
-__all__ = ["NTUPLE_ENTRIES", "NTUPLE_SHAPES", "ntuple_shape", "ntuple_table", "ntuple_value", "ntuple_is_symmetric", "ntuple_coherence", "ntuple_step_sizes",
+__all__ = ["NTUPLE_ENTRIES", "NTUPLE_ENTRIES_SUM", "NTUPLE_SHAPES", "NTUPLE_SUMS", "ntuple_shape", "ntuple_parts", "ntuple_table", "ntuple_value", "ntuple_is_symmetric", "ntuple_coherence", "ntuple_step_sizes",
            "NTuplePolicy", "NTupleBeamPolicy", "NTupleLearner"]
 
 _STATE_WON = 1                                                 # bits 28..29 of B.y: 0 running, 1 won, 2 and 3 lost
 _FINISHED_B_Y = _STATE_WON << 28                               # B.y of a state that is finished and otherwise empty
 
 
+def _counts() -> dict:
+    """Entry count -> name, for every shape and every sum of shapes."""
+    return _learn_lib._ntuple_counts()
+
+
 def _entries(shape) -> int:
-    if not isinstance(shape, str) or shape not in NTUPLE_SHAPES:
-        raise ValueError(f"shape must be one of {sorted(NTUPLE_SHAPES)}, got {shape!r}")
-    return NTUPLE_SHAPES[shape][2]
+    if not isinstance(shape, str) or (shape not in NTUPLE_SHAPES and shape not in NTUPLE_SUMS):
+        raise ValueError(f"shape must be one of {sorted(NTUPLE_SHAPES) + sorted(NTUPLE_SUMS)}, got {shape!r}")
+    return _learn_lib.ntuple_entries_of(shape)
 
 
 def ntuple_table(device="cuda:0", shape: str = "2x4") -> torch.Tensor:
-    """A zeroed n-tuple table of `shape` on `device`: int32 [NTUPLE_SHAPES[shape] entries] (2x4: NTUPLE_ENTRIES)."""
+    """A zeroed n-tuple table of `shape` on `device`: int32 [NTUPLE_SHAPES[shape] entries] (2x4: NTUPLE_ENTRIES); "2x4+3x3": a sum
+    table, int32 [NTUPLE_ENTRIES_SUM] -- ntuple_parts gives its two tables."""
     return torch.zeros(_entries(shape), dtype=torch.int32, device=device)
 
 
 def ntuple_coherence(device="cuda:0", shape: str = "2x4") -> torch.Tensor:
-    """A zeroed coherence buffer of `shape` on `device`: int64 [entries, 2], entry j the pair (E_j, A_j) of include/tpl_learn.h."""
+    """A zeroed coherence buffer of `shape` on `device`: int64 [entries, 2], entry j the pair (E_j, A_j) of include/tpl_learn.h;
+    of a sum, laid out as the sum table is."""
     return torch.zeros((_entries(shape), 2), dtype=torch.int64, device=device)
 
 
 def ntuple_shape(table) -> str:
-    """"2x4" or "3x3": the shape of a table (or, by its first dimension, of a coherence buffer), from its entry count; a tensor
-    of any other size is refused."""
-    if isinstance(table, torch.Tensor) and table.dim() >= 1:
-        for name, (_, _, entries) in NTUPLE_SHAPES.items():
-            if table.shape[0] == entries:
-                return name
-    sizes = ", ".join(f"{v[2]} ({k})" for k, v in NTUPLE_SHAPES.items())
+    """"2x4", "3x3" or "2x4+3x3": the shape of a table (or, by its first dimension, of a coherence buffer), from its entry count; a
+    tensor of any other size is refused."""
+    if isinstance(table, torch.Tensor) and table.dim() >= 1 and table.shape[0] in _counts():
+        return _counts()[table.shape[0]]
+    sizes = ", ".join(f"{k} ({v})" for k, v in _counts().items())
     raise ValueError(f"table must be a tensor of {sizes} entries (ntuple_table)")
+
+
+def ntuple_parts(table) -> tuple:
+    """The per-shape views of a table or a coherence buffer, in the order they lie in it: (table,) for a plain one, (the 2x4 part,
+    the 3x3 part) for a sum.  Views, not copies: each is a valid, 16-byte aligned table (buffer) of its shape for everything that
+    takes one, and what is written through it is written to the whole."""
+    parts, at = [], 0
+    for part in _learn_lib.ntuple_parts_of(ntuple_shape(table)):
+        parts.append(table[at:at + NTUPLE_SHAPES[part][2]])
+        at += NTUPLE_SHAPES[part][2]
+    return tuple(parts)
 
 
 @torch.no_grad()
@@ -98,12 +122,12 @@ def ntuple_step_sizes(coherence: torch.Tensor) -> torch.Tensor:
 
 
 def _sizes() -> str:
-    return " or ".join(f"{v[2]} ({k})" for k, v in NTUPLE_SHAPES.items())
+    return " or ".join(f"{k} ({v})" for k, v in _counts().items())
 
 
 def _coherence(coherence, table=None) -> torch.Tensor:
     """A coherence buffer of a shape's entry count -- of `table`'s, where one is given."""
-    counts = [v[2] for v in NTUPLE_SHAPES.values()] if table is None else [int(table.shape[0])]
+    counts = list(_counts()) if table is None else [int(table.shape[0])]
     if (not isinstance(coherence, torch.Tensor) or coherence.dtype != torch.int64 or coherence.dim() != 2
             or coherence.shape[1] != 2 or coherence.shape[0] not in counts or not coherence.is_contiguous()
             or (table is not None and coherence.device != table.device)):
@@ -114,15 +138,18 @@ def _coherence(coherence, table=None) -> torch.Tensor:
 
 def _table(table, device) -> torch.Tensor:
     if (not isinstance(table, torch.Tensor) or table.dtype != torch.int32 or table.dim() != 1
-            or table.shape[0] not in [v[2] for v in NTUPLE_SHAPES.values()] or table.device != device
+            or table.shape[0] not in _counts() or table.device != device
             or not table.is_contiguous()):
         raise ValueError(f"table must be a contiguous int32 tensor of {_sizes()} entries on {device} (ntuple_table)")
     return table
 
 
-def _shape_id(table) -> int:
-    """The C `shape` of a table that _table accepts."""
-    return NTUPLE_SHAPE_IDS[ntuple_shape(table)]
+def _shaped(lib, entry: str, shape: str):
+    """How the library reads a table of `shape` through `entry` ("tpl_ntuple_value", ...): (function, trailing arguments before
+    `stream`) -- the _shaped twin with the C shape id, or for a sum of shapes the _sum twin, which takes none."""
+    if shape in NTUPLE_SUMS:
+        return getattr(lib, entry + "_sum"), ()
+    return getattr(lib, entry + "_shaped"), (NTUPLE_SHAPE_IDS[shape],)
 
 
 def _unit(name: str, v) -> float:
@@ -179,8 +206,8 @@ def _planes(pair, device, what: str):
 
 def _value(planes_a, planes_b, k: int, L: int, M: int, table, out, device) -> None:
     stream = torch._C._cuda_getCurrentRawStream(device.index)
-    check(_learn_lib.lib().tpl_ntuple_value_shaped(_ptr(planes_a), _ptr(planes_b), k, L, M, table.data_ptr(), out.data_ptr(),
-                                                   _shape_id(table), stream))
+    entry, shape = _shaped(_learn_lib.lib(), "tpl_ntuple_value", ntuple_shape(table))
+    check(entry(_ptr(planes_a), _ptr(planes_b), k, L, M, table.data_ptr(), out.data_ptr(), *shape, stream))
 
 
 @torch.no_grad()
@@ -218,7 +245,8 @@ _sigma = {}                                                    # the mirror perm
 @torch.no_grad()
 def ntuple_is_symmetric(table: torch.Tensor) -> bool:
     """Whether `table` is mirror-symmetric: table[sigma(j)] == table[j] for every j, sigma = _learn_lib.ntuple_mirror_permutation()
-    (include/tpl_learn.h states the invariant).  Under such a table a board and its reflection have the same value, bit for bit.
+    (include/tpl_learn.h states the invariant; of a sum table: of every part).  Under such a table a board and its reflection have
+    the same value, bit for bit.
     One gather and one comparison on the table's device; the answer is a host bool, so this syncs."""
     if not isinstance(table, torch.Tensor):
         raise ValueError(f"table must be a contiguous int32 tensor of {_sizes()} entries (ntuple_table)")
@@ -244,7 +272,7 @@ class NTuplePolicy:
         _boards(env, "NTuplePolicy")
         self.env, self.table, self.depth = env, _table(table, env.device), _depth(depth)
         self.gamma, self.epsilon, self.seed = _finite("gamma", gamma), _unit("epsilon", epsilon), _count("seed", seed)
-        self.shape = ntuple_shape(self.table)                  # "2x4" or "3x3": the table's, which picks the kernels
+        self.shape = ntuple_shape(self.table)                  # "2x4", "3x3" or "2x4+3x3": the table's, which picks the kernels
         self.step = 0                                          # the `step` of the next act() that is not given one
         self._planes = None
 
@@ -285,9 +313,9 @@ class NTuplePolicy:
         lib = _learn_lib.lib()
         head = (self._planes[0], self._planes[1], env.num_envs, env.L, env.M, *env.reward_params, self.gamma, self.table.data_ptr(),
                 self.epsilon, self.seed % (1 << 64), step % (1 << 64), out.data_ptr())
-        tail = (_ptr(score), _ptr(after_a), _ptr(after_b), _ptr(value), NTUPLE_SHAPE_IDS[self.shape], stream)
-        check(lib.tpl_ntuple_search_shaped(*head, _ptr(second), *tail) if self.depth == 2
-              else lib.tpl_ntuple_act_shaped(*head, *tail))
+        entry, shape = _shaped(lib, "tpl_ntuple_search" if self.depth == 2 else "tpl_ntuple_act", self.shape)
+        tail = (_ptr(score), _ptr(after_a), _ptr(after_b), _ptr(value), *shape, stream)
+        check(entry(*head, _ptr(second), *tail) if self.depth == 2 else entry(*head, *tail))
         return out
 
 
@@ -333,9 +361,11 @@ class NTupleBeamPolicy:
         if self._planes is None:
             self._planes = _state_ptrs(env)                   # the resident planes live as long as the environment
         stream = torch._C._cuda_getCurrentRawStream(env.device.index)
-        check(_learn_lib.lib().tpl_ntuple_beam(self._planes[0], self._planes[1], env.num_envs, env.L, env.M, *env.reward_params,
-                                               self.gamma, self.table.data_ptr(), self.depth, self.width, out.data_ptr(), _ptr(plan),
-                                               _ptr(score), _ptr(after_a), _ptr(after_b), NTUPLE_SHAPE_IDS[self.shape], stream))
+        lib = _learn_lib.lib()
+        entry, shape = (lib.tpl_ntuple_beam_sum, ()) if self.shape in NTUPLE_SUMS else (lib.tpl_ntuple_beam, (NTUPLE_SHAPE_IDS[self.shape],))
+        check(entry(self._planes[0], self._planes[1], env.num_envs, env.L, env.M, *env.reward_params, self.gamma,
+                    self.table.data_ptr(), self.depth, self.width, out.data_ptr(), _ptr(plan), _ptr(score), _ptr(after_a),
+                    _ptr(after_b), *shape, stream))
         return out
 
 
@@ -374,7 +404,15 @@ class NTupleLearner:
     Still five enqueues a step (the entry launches two kernels), no sync, nothing allocated.
 
     shape ("2x4" by default, which leaves everything above as it was; "3x3"): the windows of the table, and of the coherence buffer
-    if there is one.  Nothing else about the learner depends on it."""
+    if there is one.  Nothing else about the learner depends on it.
+
+    shape="2x4+3x3": a sum table, and a coherence buffer laid out the same way.  Steps 1 and 2 read it through the _sum entries; step
+    3 is the update above once per part with the same errors -- the 2x4 update on the first part, the 3x3 update on the second --,
+    which is the update of the summed value because no update kernel reads the table: five enqueues plus one more update call, no
+    sync, nothing allocated, and the same bytes in whatever order the adds arrive.  With symmetric=True each part is updated under
+    its own sigma; with coherent=True each part's entries keep their own step sizes.  A state now adds to about 222 entries (both
+    parts' non-empty windows and two counters) where it added to 107 to 115, so the step of V per unit of `rate` roughly DOUBLES,
+    as it does under symmetry: `rate` wants to be about half of what a single shape takes."""
 
     def __init__(self, env, gamma: float = 0.99, rate: float = 8.0, epsilon: float = 0.1, seed: int = 0, depth: int = 1,
                  lam: float = 0.0, horizon: int = 1, symmetric: bool = False, coherent: bool = False, shape: str = "2x4"):
@@ -441,16 +479,20 @@ class NTupleLearner:
         ring_a, ring_b = self._ring[0].data_ptr(), self._ring[1].data_ptr()
         if self.coherent:
             _coherence(self.coherence, _table(self.table, env.device))   # a buffer of the other shape would be overrun
-        shape = _shape_id(self.table)
+        # the update, part by part: (C shape id, the part's table pointer, its coherence pointer) -- one part unless the table is a sum
+        names = _learn_lib.ntuple_parts_of(ntuple_shape(self.table))
+        parts = list(zip((NTUPLE_SHAPE_IDS[name] for name in names), (t.data_ptr() for t in ntuple_parts(self.table)),
+                         (c.data_ptr() for c in ntuple_parts(self.coherence)) if self.coherent else (None,) * len(names)))
         for _ in range(steps):
             kept = self._kept
             self.policy.act(out=self._action, score=self._score, after=self._next, step=self.steps)
             _value(kept[0], kept[1], n, env.L, env.M, self.table, self._kept_value, env.device)
             torch.sub(self._score, self._kept_value, out=self._error)
-            ring = (ring_a, ring_b, n, self.slots, self._head, self.horizon, env.L, env.M, self.table.data_ptr())
-            tail = (self._error.data_ptr(), self.rate, self.decay, int(self.symmetric), shape, stream)
-            check(lib.tpl_ntuple_update_coherent_shaped(*ring, self.coherence.data_ptr(), *tail) if self.coherent
-                  else lib.tpl_ntuple_update_trace_shaped(*ring, *tail))
+            for shape, table, coherence in parts:
+                ring = (ring_a, ring_b, n, self.slots, self._head, self.horizon, env.L, env.M, table)
+                tail = (self._error.data_ptr(), self.rate, self.decay, int(self.symmetric), shape, stream)
+                check(lib.tpl_ntuple_update_coherent_shaped(*ring, coherence, *tail) if self.coherent
+                      else lib.tpl_ntuple_update_trace_shaped(*ring, *tail))
             env.step_into(self._action, self._reward, self._done)
             self._head = (self._head + 1) % self.slots
             self.steps += 1

@@ -91,6 +91,12 @@ Parts:
               theirs in the same run; the ratio to tpl_ntuple_search at (2, 34), where both make the same moves and gathers; win
               rates of part ntuple_shape_sweep's TD(0) tables (2 x 4 and 3 x 3, rate 16, one seed) on the L=10 / M=40 carved pool
               at depth 1, at depth 2 and with beams (3, 8), (4, 16) and (6, 16)
+    ntuple_sum     a sum table (2 x 4 and 3 x 3 summed in one value) beside its two twins, the tables that are its parts: on part
+              ntuple_shape's boards at 2^16, 2^18 and 2^20 the value, act, search, the beam at (3, 8) and (6, 16) and one learner step,
+              plain and coherent, of all three in the same alternated rounds, each as a ratio to the two twins' times added; the
+              entries in use per running board
+    ntuple_sum_sweep  part ntuple_shape_sweep's set-up unchanged: the 2 x 4 and 3 x 3 TD(0) runs at rate 16 again (they must reproduce
+              win for win), then a sum table as TD(0) at rates 2, 4, 8 and 16; the best one is also played at depth 2 and at beam (3, 8)
     ntuple_shape_ab  --parent LIB: the nine 2 x 4 n-tuple kernels of another build of the learner library against this tree's, both
               loaded into one process: the outputs of the six entries compared byte for byte on the ring of part ntuple_shape
               at 2^18 boards, then each entry timed in five rounds of the parent against itself and five of the parent against
@@ -110,7 +116,8 @@ HBM_ACHIEVABLE = 6.3e12
 PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600, "priority": 600, "nstep": 600, "mirror": 600, "afterstates": 600,
          "heuristic": 600, "search": 900, "beam": 900, "ntuple": 900,
          "ntuple_search": 900, "ntuple_trace": 600, "ntuple_trace_sweep": 1100, "ntuple_coherent": 600,
-         "ntuple_coherent_sweep": 1700, "ntuple_shape": 600, "ntuple_shape_sweep": 1100, "ntuple_beam": 1100}
+         "ntuple_coherent_sweep": 1700, "ntuple_shape": 600, "ntuple_shape_sweep": 1100, "ntuple_beam": 1100,
+         "ntuple_sum": 600, "ntuple_sum_sweep": 600}
 SCATTERED_ATOMICS = 0.08e12                                 # 64 lanes of a wave adding into 64 rows (float adds; integer adds unmeasured)
 VALU_CYCLES, SIMDS, CLOCK_HZ = 3.3, 1024, 2.4e9           # the move's instruction mix, 256 CUs x 4, the clock
 
@@ -1680,6 +1687,132 @@ def part_ntuple_beam(rounds=3, n=1 << 20, eval_steps=12288):
     out["l10_m40"] = dict(boards=4096, seed=11, pool=1 << 16, pool_seed=7, reward=list(NTUPLE_LARGE_REWARD), gamma=1.0, epsilon=0.05,
                           eval_steps=eval_steps, tables=played)
     return out
+
+
+NTUPLE_SUM = "2x4+3x3"
+
+
+def part_ntuple_sum(rounds=5, reps=10):
+    """A sum table beside its two twins -- the 2 x 4 and the 3 x 3 table that are its parts -- on part ntuple_shape's boards."""
+    import numpy as np
+    import torch
+    import tetris_piclim as T
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import learn_ref as R
+    m = T._learn_lib
+    slots, head = 17, 16
+    names = ("2x4", "3x3", NTUPLE_SUM)
+    kernels = ("ntuple_value_kernel", "ntuple3_value_kernel", "ntuple_sum_value_kernel", "ntuple_act_kernel", "ntuple3_act_kernel",
+               "ntuple_sum_act_kernel")
+    out = dict(part="ntuple_sum", gamma=1.0, epsilon=0.05, learner_rate=1.0,
+               static_valu={k: _static_valu(k, m.build_library()) for k in kernels})
+    rows = []
+    for n in (1 << 16, 1 << 18, 1 << 20):
+        env, ring = _shape_ring(T, n, slots)                     # the environment stands at the ring's newest slot
+        a, b = (x[head, :4096].cpu().numpy().view(np.uint32) for x in ring)
+        f = R.decode_state(a, b)
+        in_use = {}
+        for name in names:
+            _, used = m.ntuple_indices(f["rows"], f["cur"], 10, 40, f["lines"].astype(np.int64), f["moves"].astype(np.int64), shape=name)
+            in_use[name] = round(float(used[f["state"] == 0].sum(axis=1).mean()), 1)         # the counters included
+        del ring
+        whole = np.random.default_rng(0).integers(-(1 << 20), (1 << 20) + 1, m.NTUPLE_ENTRIES_SUM).astype(np.int32)
+        table = {NTUPLE_SUM: torch.from_numpy(whole).to("cuda:0")}
+        table["2x4"], table["3x3"] = (p.clone() for p in T.ntuple_parts(table[NTUPLE_SUM]))          # the twins: its parts, on their own
+        action, second = (torch.empty(n, dtype=torch.uint8, device="cuda:0") for _ in range(2))
+        score, value = (torch.empty(n, dtype=torch.float32, device="cuda:0") for _ in range(2))
+        after = tuple(torch.empty((n, 4), dtype=torch.int32, device="cuda:0") for _ in range(2))
+        variants = {}
+        for name in names:
+            act = T.NTuplePolicy(env, table[name], gamma=1.0, epsilon=0.05, seed=11)
+            search = T.NTuplePolicy(env, table[name], gamma=1.0, epsilon=0.05, seed=11, depth=2)
+            beams = {shape: T.NTupleBeamPolicy(env, table[name], *shape, gamma=1.0) for shape in ((3, 8), (6, 16))}
+            variants[("value", name)] = (lambda t=table[name]: T.ntuple_value(env, t, out=value), reps)
+            variants[("act", name)] = (lambda p=act: p.act(out=action, score=score, after=after, value=value, step=3), reps)
+            variants[("search", name)] = (lambda p=search: p.act(out=action, score=score, after=after, value=value, step=3,
+                                                                 second=second), max(reps // 3, 2))
+            variants[("beam_3x8", name)] = (lambda p=beams[(3, 8)]: p.act(out=action), 3)
+            variants[("beam_6x16", name)] = (lambda p=beams[(6, 16)]: p.act(out=action), 1)
+        order = sorted(variants)                                 # an entry's three tables next to each other in every round
+        times = {k: [] for k in order}
+        for _ in range(rounds):                                  # alternate the variants round by round
+            for k in order:
+                fn, count = variants[k]
+                times[k].append(_timed(fn, count, warmup=1))
+        # one learner step -- act, value, subtract, update (a sum table: two update calls), environment step -- plain and coherent; the
+        # learners step the environment, so they come last
+        for coherent in (False, True):
+            learners = {name: T.NTupleLearner(env, gamma=1.0, rate=1.0, epsilon=0.05, seed=11, shape=name, coherent=coherent) for name in names}
+            for name in names:
+                learners[name].table.copy_(table[name])          # the random table: gathers all over it, as in the kernels above
+                learners[name].train(3)                          # step sizes of every kind before anything is timed
+                times[("learner_step_coherent" if coherent else "learner_step", name)] = []
+            for _ in range(rounds):
+                for name in names:
+                    k = ("learner_step_coherent" if coherent else "learner_step", name)
+                    times[k].append(_timed(lambda l=learners[name]: l.train(1), reps, warmup=1))
+            del learners
+        med = {k: sorted(ts)[rounds // 2] for k, ts in times.items()}
+        row = dict(boards=n, entries_in_use_per_board=in_use)
+        for what in sorted({k[0] for k in times}):
+            row[what] = {name + "_us": _spread(times[(what, name)]) for name in names}
+            row[what]["sum_over_the_twins_together"] = round(med[(what, NTUPLE_SUM)] / (med[(what, "2x4")] + med[(what, "3x3")]), 3)
+        rows.append(row)
+        print(json.dumps(row), file=sys.stderr, flush=True)
+        env.terminate()
+        del table, variants, after
+        torch.cuda.empty_cache()
+    out["kernel"] = dict(rounds=rounds, launches_per_timing=reps, search_launches_per_timing=max(reps // 3, 2), beam_launches_per_timing=[3, 1],
+                         rows=rows)
+    return out
+
+
+def part_ntuple_sum_sweep(eval_steps=12288):
+    """Part ntuple_shape_sweep's set-up unchanged; its 2 x 4 and 3 x 3 TD(0) runs at rate 16 again, then a sum table as TD(0)."""
+    import torch
+    import tetris_piclim as T
+    gen_env = T.BatchedTetris(10, 40, 64, device="cuda:0", seed=7)
+    big = gen_env.carved_configs(1 << 16, seed=7)
+    gen_env.terminate()
+
+    def result(r):
+        p = r["win_rate"]
+        return dict(episodes=r["episodes"], wins=r["wins"], win_rate=round(p, 5),
+                    standard_error=round((p * (1 - p) / max(r["episodes"], 1)) ** 0.5, 6))
+
+    def learn(keep=False, **kw):
+        env = T.BatchedTetris(10, 40, 4096, device="cuda:0", seed=11, auto_reset=True, reward=NTUPLE_LARGE_REWARD, config_pool=big)
+        learner = T.NTupleLearner(env, seed=11, gamma=1.0, epsilon=0.05, **kw)
+        got = dict(kw, zero_table=result(learner.evaluate(eval_steps)), trained=[])
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for steps in (10000, 30000):
+            learner.train(steps)
+            got["trained"].append(dict(steps=learner.steps, **result(learner.evaluate(eval_steps))))
+        got.update(seconds=round(time.perf_counter() - t0, 2), entries_in_use=[int((p != 0).sum()) for p in T.ntuple_parts(learner.table)],
+                   largest_entry=int(learner.table.abs().max()))
+        table = learner.table.clone() if keep else None
+        env.terminate()
+        print(json.dumps(got), file=sys.stderr, flush=True)      # progress: a long part must not stay silent
+        return got, table
+    baselines = [learn(shape=shape, rate=16.0)[0] for shape in ("2x4", "3x3")]
+    expected = [(1473217, 1480033), (1467276, 1469796)]           # profiles/learner/sweep_ntuple_shape.log
+    reproduced = [(b["trained"][-1]["wins"], b["trained"][-1]["episodes"]) == e for b, e in zip(baselines, expected)]
+    runs, tables = [], []
+    for rate in (2.0, 4.0, 8.0, 16.0):
+        got, table = learn(keep=True, shape=NTUPLE_SUM, rate=rate)
+        runs.append(got)
+        tables.append(table)
+    at = max(range(len(runs)), key=lambda i: runs[i]["trained"][-1]["win_rate"])
+    env = T.BatchedTetris(10, 40, 4096, device="cuda:0", seed=11, auto_reset=True, reward=NTUPLE_LARGE_REWARD, config_pool=big)
+    player = T.NTupleLearner(env, seed=11, gamma=1.0, epsilon=0.05, shape=NTUPLE_SUM)
+    player.table.copy_(tables[at])
+    deep = dict(depth_1=result(player.evaluate(eval_steps)), depth_2=result(player.evaluate(eval_steps, depth=2)),
+                beam_3x8=result(player.evaluate(eval_steps, depth=3, width=8)))
+    env.terminate()
+    return dict(part="ntuple_sum_sweep", boards=4096, seed=11, pool=1 << 16, pool_seed=7, reward=list(NTUPLE_LARGE_REWARD), gamma=1.0,
+                epsilon=0.05, eval_steps=eval_steps, baselines=baselines, baselines_reproduced_win_for_win=reproduced, best=runs[at],
+                best_played=deep, runs=runs)
 
 
 def part_ntuple_shape_ab(parent, rounds=5, reps=20, n=1 << 18):
