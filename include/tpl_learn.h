@@ -634,6 +634,67 @@ int tpl_ntuple_beam_sum(const void* plane_a, const void* plane_b, int64_t n, int
                         float r_lose, float gamma, const int32_t* table, int32_t depth, int32_t width, uint8_t* action,
                         uint8_t* plan, float* score, void* after_a, void* after_b, void* stream);
 
+/* Staged tables: the weights split by game stage, the stage read from the lines and moves that are left.  In every table above the
+ * move budget enters the value additively, V = f(board, piece) + counter[k]; a staged table holds TPL_NTUPLE_STAGES = 8 whole tables
+ * and lets k choose which one is read, so that the same stack can be worth one thing with three moves left and another with thirty.
+ *
+ * STAGED TABLE of a FORM F -- TPL_NTUPLE_FORM_2X4 = 0, TPL_NTUPLE_FORM_3X3 = 1 (the two shapes) or TPL_NTUPLE_FORM_SUM = 2 (the sum
+ * table) -- with E_F = 314,368, 590,848 or 905,216 entries: one int32 buffer, 16-byte aligned, of 8 E_F + 1,024 entries --
+ *   TPL_NTUPLE_ENTRIES_STAGED     = 2,515,968   (10,063,872 bytes)
+ *   TPL_NTUPLE_ENTRIES_STAGED_3X3 = 4,727,808   (18,911,232 bytes)
+ *   TPL_NTUPLE_ENTRIES_STAGED_SUM = 7,242,752   (28,971,008 bytes)
+ * -- counts that no table and no coherence buffer above has, so a buffer's form still follows from its entry count:
+ *   block[g]  at entry g * E_F          g in 0..7: a whole table of form F, in units of 2^-16, with its own counters (a sum: both parts')
+ *   map[k]    at entry 8 * E_F + k      k in 0..1023, the counter index: the STAGE MAP
+ * E_F is a multiple of 512, so every block (and the second part of a sum's block) starts at a multiple of 16 bytes and of both
+ * shapes' pattern counts, and the first E_F entries are by themselves a valid plain table of the form.
+ * Stage:   g(s) = map[k(s)] & 7, k(s) the counter index of s under the game's L and M.  THE MASK IS PART OF THE RULE: a map that
+ *   holds anything at all, random words included, names a block of the buffer, and no kernel trusts device memory for a bound.
+ * Value:   V(s) is the value of form F stated above read from block[g(s)] -- the block's windows under the falling piece plus the
+ *   block's OWN counter entry (of a sum: both parts'), exact in 64 bits, ONE rounding, times 2^-16; 0 for a state that is not running.
+ * The stage is looked up wherever a table is read, state by state: the afterstates of tpl_ntuple_act, the second-ply boards of
+ * tpl_ntuple_search and every child of tpl_ntuple_beam are each valued in the block of THEIR OWN lines and moves left, which differ
+ * from the root's.  Everything else is the rule of the entry of the same name with this V: scores, Q, the fold, candidates, ties, the
+ * effective depth, the epsilon draw, `second`, `plan`, `after`, `value`.  With eight equal blocks every output is, bit for bit, what
+ * the block gives as a plain table under the entry of its form, whatever the map holds.  A map that uses two or four stages leaves
+ * the other blocks untouched: they cost memory only.
+ * Update (tpl_ntuple_update_trace_staged): tpl_ntuple_update_trace_shaped's rule -- d_k, the trace cut, the decay, the mirror image --
+ *   with every add of a state made in block[g(that state)]: the windows' entries and the counter entry, at g * E_F + the index above.
+ *   The reflected board has the state's lines and moves, hence its stage: a staged table whose blocks are each mirror-symmetric stays
+ *   so.  For TPL_NTUPLE_FORM_SUM both parts of the block take the same d_k, each under its own sigma.  The map is READ and never
+ *   written; the blocks are added to and never read, so the bytes are the same whatever order the adds arrive in.  The planes form
+ *   (tpl_ntuple_update) is a ring of one slot: slots = 1, head = 0, horizon = 1.  There is NO coherent update of a staged table.
+ *
+ * Each _staged entry takes the arguments of its _shaped twin (tpl_ntuple_beam_staged: tpl_ntuple_beam's) with `form` in the place of
+ * `shape` and `table` a staged table of that form, and refuses what the twin refuses, in its order, under its own name, before any
+ * HIP call; refused before anything else, and before any pointer is looked at: a form that is none of the three.  Kernels: the device
+ * bodies of the twins under a composite geometry (StagedOf: csrc/learn/tpl_ntuple.h) -- one extra dword gathered from the 4 KB map per
+ * board sum, the block's offset inside the 32-bit entry index, the table pointer uniform -- ntuple_staged_{value,act,search}_kernel,
+ * ntuple_staged3_*, ntuple_staged_sum_* (ntuple.hip) and ntuple_staged_beam_kernel, ntuple_staged_beam3_kernel,
+ * ntuple_staged_beam_sum_kernel (ntuple_beam.hip).  The update launches ntuple_staged_trace_kernel<symmetric> on the 2 x 4 part of
+ * every block, ntuple_staged3_trace_kernel<symmetric> on the 3 x 3 part, or both for a sum: a lane per (board, age), no sync and
+ * nothing allocated. */
+#define TPL_NTUPLE_STAGES 8
+typedef enum { TPL_NTUPLE_FORM_2X4 = 0, TPL_NTUPLE_FORM_3X3 = 1, TPL_NTUPLE_FORM_SUM = 2 } tpl_ntuple_form;
+#define TPL_NTUPLE_ENTRIES_STAGED (TPL_NTUPLE_STAGES * TPL_NTUPLE_ENTRIES + 1024)
+#define TPL_NTUPLE_ENTRIES_STAGED_3X3 (TPL_NTUPLE_STAGES * TPL_NTUPLE_ENTRIES_3X3 + 1024)
+#define TPL_NTUPLE_ENTRIES_STAGED_SUM (TPL_NTUPLE_STAGES * TPL_NTUPLE_ENTRIES_SUM + 1024)
+int tpl_ntuple_value_staged(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const int32_t* table,
+                            float* value, int32_t form, void* stream);
+int tpl_ntuple_act_staged(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line, float r_win,
+                          float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed, uint64_t step,
+                          uint8_t* action, float* score, void* after_a, void* after_b, float* value, int32_t form, void* stream);
+int tpl_ntuple_search_staged(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line, float r_win,
+                             float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed, uint64_t step,
+                             uint8_t* action, uint8_t* second, float* score, void* after_a, void* after_b, float* value,
+                             int32_t form, void* stream);
+int tpl_ntuple_beam_staged(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line, float r_win,
+                           float r_lose, float gamma, const int32_t* table, int32_t depth, int32_t width, uint8_t* action,
+                           uint8_t* plan, float* score, void* after_a, void* after_b, int32_t form, void* stream);
+int tpl_ntuple_update_trace_staged(const void* ring_a, const void* ring_b, int64_t n, int32_t slots, int32_t head, int32_t horizon,
+                                   int32_t L, int32_t M, int32_t* table, const float* error, float rate, float decay,
+                                   int32_t symmetric, int32_t form, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

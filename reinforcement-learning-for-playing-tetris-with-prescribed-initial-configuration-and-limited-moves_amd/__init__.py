@@ -14,7 +14,8 @@ __all__ = ["BatchedTetris", "Tetris", "Snapshot", "OBS_DIM", "NUM_ACTIONS", "RUN
            "RandomPieceGenerator", "get_tetromino", "piece_translations", "translate", "carve", "build_library", "shape_info", "generate_configs", "forward_generate", "pack_policy", "LIB_PATH", "SYMBOLS", "DQNLearner",
            "ReplayRing", "PrioritizedReplayRing", "LookaheadPolicy", "afterstates", "HeuristicPolicy", "placement_features",
            "evaluate_heuristic", "tune_heuristic", "BeamPolicy", "NTuplePolicy", "NTupleBeamPolicy", "NTupleLearner", "ntuple_table", "ntuple_value",
-           "ntuple_is_symmetric", "ntuple_coherence", "ntuple_step_sizes", "ntuple_shape", "NTUPLE_SHAPES", "ntuple_parts", "NTUPLE_SUMS", "NTUPLE_ENTRIES_SUM"]
+           "ntuple_is_symmetric", "ntuple_coherence", "ntuple_step_sizes", "ntuple_shape", "NTUPLE_SHAPES", "ntuple_parts", "NTUPLE_SUMS", "NTUPLE_ENTRIES_SUM",
+           "NTUPLE_STAGES", "ntuple_stage_map", "ntuple_staged", "ntuple_stages", "ntuple_map", "ntuple_is_staged"]
 
 
 def __getattr__(name):
@@ -39,7 +40,8 @@ def __getattr__(name):
     if name in ("HeuristicPolicy", "placement_features", "evaluate_heuristic", "tune_heuristic", "BeamPolicy"):
         return getattr(importlib.import_module(__name__ + ".heuristic"), name)
     if name in ("NTuplePolicy", "NTupleBeamPolicy", "NTupleLearner", "ntuple_table", "ntuple_value", "ntuple_is_symmetric", "ntuple_coherence",
-                "ntuple_step_sizes", "ntuple_shape", "NTUPLE_SHAPES", "ntuple_parts", "NTUPLE_SUMS", "NTUPLE_ENTRIES_SUM"):
+                "ntuple_step_sizes", "ntuple_shape", "NTUPLE_SHAPES", "ntuple_parts", "NTUPLE_SUMS", "NTUPLE_ENTRIES_SUM",
+                "NTUPLE_STAGES", "ntuple_stage_map", "ntuple_staged", "ntuple_stages", "ntuple_map", "ntuple_is_staged"):
         return getattr(importlib.import_module(__name__ + ".ntuple"), name)
     if name in ("learn", "_learn_lib", "lookahead", "heuristic", "ntuple"):
         return importlib.import_module(__name__ + "." + name)

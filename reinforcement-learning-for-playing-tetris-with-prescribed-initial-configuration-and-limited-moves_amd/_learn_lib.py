@@ -34,6 +34,8 @@ LEARN_SYMBOLS = [
     "tpl_ntuple_value_shaped", "tpl_ntuple_act_shaped", "tpl_ntuple_search_shaped", "tpl_ntuple_update_shaped",
     "tpl_ntuple_update_trace_shaped", "tpl_ntuple_update_coherent_shaped", "tpl_ntuple_beam",
     "tpl_ntuple_value_sum", "tpl_ntuple_act_sum", "tpl_ntuple_search_sum", "tpl_ntuple_beam_sum",
+    "tpl_ntuple_value_staged", "tpl_ntuple_act_staged", "tpl_ntuple_search_staged", "tpl_ntuple_beam_staged",
+    "tpl_ntuple_update_trace_staged",
 ]
 NSTEP_MAX = 16
 BEAM_MAX_DEPTH, BEAM_MAX_WIDTH = 12, 64
@@ -163,6 +165,12 @@ def lib() -> C.CDLL:
         twin.restype = i32
     L.tpl_ntuple_beam_sum.argtypes = L.tpl_ntuple_beam.argtypes[:-2] + [vp]      # tpl_ntuple_beam's without `shape`
     L.tpl_ntuple_beam_sum.restype = i32
+    for name in ("tpl_ntuple_value", "tpl_ntuple_act", "tpl_ntuple_search", "tpl_ntuple_update_trace"):   # a staged table: `form` for `shape`
+        twin = getattr(L, name + "_staged")
+        twin.argtypes = getattr(L, name + "_shaped").argtypes
+        twin.restype = i32
+    L.tpl_ntuple_beam_staged.argtypes = L.tpl_ntuple_beam.argtypes
+    L.tpl_ntuple_beam_staged.restype = i32
     for name in ("tpl_replay_push", "tpl_replay_sample", "tpl_learn_pack", "tpl_priority_init", "tpl_priority_push",
                  "tpl_priority_update", "tpl_replay_sample_prioritized", "tpl_replay_sample_nstep", "tpl_replay_sample_mirror",
                  "tpl_mirror_states", "tpl_afterstates", "tpl_placement_features", "tpl_placement_act",
@@ -591,6 +599,57 @@ def _counter_columns(shape: str) -> list:
     return columns
 
 
+# Staged tables (include/tpl_learn.h): NTUPLE_STAGES whole tables of a form -- a shape or a sum, NTUPLE_FORM_IDS gives the C `form` of
+# a name -- one behind the other, then the stage map, an int32 per counter index; the stage of a state is map[k] & 7
+NTUPLE_STAGES = 8
+NTUPLE_FORM_IDS = {"2x4": 0, "3x3": 1, "2x4+3x3": 2}
+
+
+def ntuple_staged_entries_of(shape: str) -> int:
+    """The entries of a staged table of the form `shape`: eight tables and the 1,024 entries of the map."""
+    return NTUPLE_STAGES * ntuple_entries_of(shape) + NTUPLE_COUNTERS
+
+
+def _ntuple_staged_counts() -> dict:
+    """Entry count -> the form's name, for the staged table of every shape and every sum."""
+    return {ntuple_staged_entries_of(name): name for name in list(NTUPLE_SHAPES) + list(NTUPLE_SUMS)}
+
+
+def ntuple_form_of(entries: int) -> tuple:
+    """(the form's name, whether the table is staged) of a table of `entries` entries; anything else is refused."""
+    staged = _ntuple_staged_counts()
+    return (staged[entries], True) if entries in staged else (ntuple_shape_of(entries), False)
+
+
+def ntuple_counter_index(L: int, M: int, lines, moves) -> np.ndarray:
+    """k = 64 min(max(L - lines, 0), 15) + min(max(M - moves, 0), 63) (int64, the shape of lines against moves)."""
+    lines, moves = np.asarray(lines, dtype=np.int64), np.asarray(moves, dtype=np.int64)
+    return 64 * np.clip(int(L) - lines, 0, 15) + np.clip(int(M) - moves, 0, 63)
+
+
+def ntuple_stage_map(L: int, M: int, lines: int = 1, moves: int = 4) -> np.ndarray:
+    """A stage map (int32 [1,024]) that cuts (lines left, moves left) into a grid of `lines` x `moves` <= 8 buckets of equal width:
+    entry k = 64 l + m, l < 16 and m < 64 the clamped counters, holds bl * moves + bm with bm = m * moves // (min(M, 63) + 1) and
+    bl = l * lines // (min(L, 15) + 1).  Counters above min(L, 15) or min(M, 63), which no state of the game has, fall in the top
+    bucket."""
+    for name, v in (("L", L), ("M", M), ("lines", lines), ("moves", moves)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError(f"{name} must be a positive integer, got {v!r}")
+    if lines * moves > NTUPLE_STAGES:
+        raise ValueError(f"lines * moves must be at most {NTUPLE_STAGES} stages, got {lines} x {moves}")
+    l, m = np.divmod(np.arange(NTUPLE_COUNTERS, dtype=np.int64), 64)
+    bl = np.minimum(l * lines // (min(int(L), 15) + 1), lines - 1)
+    bm = np.minimum(m * moves // (min(int(M), 63) + 1), moves - 1)
+    return (bl * moves + bm).astype(np.int32)
+
+
+def ntuple_stages_of(table, L: int, M: int, lines, moves) -> np.ndarray:
+    """The stage of K states under a staged table (or under a map of 1,024 entries alone): map[k] & 7 (int64 [K])."""
+    table = np.asarray(table)
+    stage_map = table[-NTUPLE_COUNTERS:]
+    return (stage_map[ntuple_counter_index(L, M, lines, moves)].astype(np.int64) & (NTUPLE_STAGES - 1)).reshape(-1)
+
+
 def ntuple_indices(rows, piece, L: int, M: int, lines, moves, shape: str = "2x4"):
     """Where the value of K boards lives in the table: (index int64 [K, 154], used bool [K, 154]).  Column t < 153 is tuple
     t = 17 x + y -- cell (row y + j, column x) is bit j and cell (row y + j, column x + 1) bit 4 + j of its pattern q, j < 4 --
@@ -636,23 +695,37 @@ def ntuple_indices(rows, piece, L: int, M: int, lines, moves, shape: str = "2x4"
     return index, used
 
 
-def _ntuple_table(table) -> np.ndarray:
+def _ntuple_table(table, staged: bool = True) -> np.ndarray:
+    """A table of a known entry count; staged=False: a plain one, for what has no staged form."""
     if (not isinstance(table, np.ndarray) or table.dtype != np.int32 or table.ndim != 1
-            or table.shape[0] not in _ntuple_counts()):
+            or (table.shape[0] not in _ntuple_counts() and not (staged and table.shape[0] in _ntuple_staged_counts()))):
         raise ValueError(f"table must be an int32 array of {NTUPLE_ENTRIES} entries (3x3: {NTUPLE_SHAPES['3x3'][2]}, "
-                         f"2x4+3x3: {NTUPLE_ENTRIES_SUM})")
+                         f"2x4+3x3: {NTUPLE_ENTRIES_SUM}" + (f"; staged: {list(_ntuple_staged_counts())})" if staged else
+                                                             "); a staged table has no coherent update"))
     return table
 
 
 def _table_shape(table) -> str:
-    """The shape of a table that _ntuple_table accepts."""
-    return ntuple_shape_of(_ntuple_table(table).shape[0])
+    """The shape of a PLAIN table."""
+    return ntuple_shape_of(_ntuple_table(table, staged=False).shape[0])
+
+
+def _table_indices(table, rows, piece, L: int, M: int, lines, moves):
+    """(index, used, the form's name) of K boards in `table`, plain or staged: ntuple_indices of the form, and under a staged table
+    every index of a board moved into the block of its stage, stage * (the form's entries) further on."""
+    shape, staged = ntuple_form_of(_ntuple_table(table).shape[0])
+    index, used = ntuple_indices(rows, piece, L, M, lines, moves, shape)
+    if staged:
+        stage = np.broadcast_to(ntuple_stages_of(table, L, M, lines, moves), index.shape[:1])
+        index = index + (stage * ntuple_entries_of(shape))[:, None]
+    return index, used, shape
 
 
 def ntuple_value(table, rows, piece, L: int, M: int, lines, moves, state) -> np.ndarray:
     """V of K states (float32 [K]): 0 where state != 0, else the entries ntuple_indices names summed exactly (int64), rounded
-    once to float32 and scaled by 2^-16.  Under a sum table the entries of both parts are in that one sum: one rounding."""
-    index, used = ntuple_indices(rows, piece, L, M, lines, moves, _table_shape(table))
+    once to float32 and scaled by 2^-16.  Under a sum table the entries of both parts are in that one sum: one rounding.  Under a
+    staged table: the same sum over the block of the state's stage, map[k] & 7."""
+    index, used, _ = _table_indices(table, rows, piece, L, M, lines, moves)
     total = np.where(used, table[index].astype(np.int64), 0).sum(axis=1)
     running = np.broadcast_to(np.asarray(state), total.shape) == 0
     return np.where(running, total.astype(np.float32) * np.float32(2.0 ** -16), np.float32(0.0)).astype(np.float32)
@@ -668,8 +741,9 @@ def ntuple_steps(error, rate) -> np.ndarray:
 
 def ntuple_update(table, rows, piece, L: int, M: int, lines, moves, state, error, rate) -> np.ndarray:
     """tpl_ntuple_update, in place: every running state adds its d to the entries ntuple_indices names; the adds wrap.  A sum
-    table takes d on the entries of both parts: tpl_ntuple_update_shaped once per part with the same errors."""
-    index, used = ntuple_indices(rows, piece, L, M, lines, moves, _table_shape(table))
+    table takes d on the entries of both parts: tpl_ntuple_update_shaped once per part with the same errors.  A staged table
+    takes d in the block of the state's stage (tpl_ntuple_update_trace_staged on a ring of one slot); its map is only read."""
+    index, used, _ = _table_indices(table, rows, piece, L, M, lines, moves)
     d = np.where(np.broadcast_to(np.asarray(state), index.shape[:1]) == 0, ntuple_steps(error, rate), 0)
     used = used & (d != 0)[:, None]
     np.add.at(_ntuple_table(table).view(np.uint32), index[used], np.broadcast_to(d[:, None], used.shape)[used].astype(np.uint32))
@@ -733,8 +807,9 @@ def ntuple_update_trace(table, ages, L: int, M: int, error, rate, decay, symmetr
     fields ntuple_update takes, K states each.  Board i takes d_k = ntuple_steps(e_i, float32(rate) * w_k), w_0 = 1 and w_k =
     float32(w_{k-1} * decay), at age k as long as that state and every younger one run.  symmetric: the same d_k goes to the tuple
     entries of the REFLECTED rows (columns reversed, piece through PIECE_MIRROR) as well -- not through sigma --; the counter is
-    added once."""
-    tab, shape = _ntuple_table(table).view(np.uint32), _table_shape(table)
+    added once.  A staged table (tpl_ntuple_update_trace_staged): every add of a state, the reflected board's included, goes to the
+    block of THAT state's stage; the map is read as it stands and never written."""
+    tab, shape = _ntuple_table(table).view(np.uint32), ntuple_form_of(table.shape[0])[0]
     counters = _counter_columns(shape)
     e = np.asarray(error, dtype=np.float32).reshape(-1)
     open_ = np.ones(e.shape, dtype=bool)
@@ -744,12 +819,12 @@ def ntuple_update_trace(table, ages, L: int, M: int, error, rate, decay, symmetr
             w = np.float32(w * decay)
         open_ = open_ & (np.broadcast_to(np.asarray(state), e.shape) == 0)
         d = np.where(open_, ntuple_steps(e, np.float32(rate) * w), 0)
-        index, used = ntuple_indices(rows, piece, L, M, lines, moves, shape)
+        index, used, _ = _table_indices(table, rows, piece, L, M, lines, moves)
         used = used & (d != 0)[:, None]
         np.add.at(tab, index[used], np.broadcast_to(d[:, None], used.shape)[used].astype(np.uint32))
         if symmetric:
             piece = np.broadcast_to(np.asarray(piece, dtype=np.int64), e.shape)
-            index, used = ntuple_indices(_reflected_rows(rows), np.array(PIECE_MIRROR)[piece], L, M, lines, moves, shape)
+            index, used, _ = _table_indices(table, _reflected_rows(rows), np.array(PIECE_MIRROR)[piece], L, M, lines, moves)
             used = used & (d != 0)[:, None]
             used[:, counters] = False             # the counter (of a sum table: each part's) was added above, once
             np.add.at(tab, index[used], np.broadcast_to(d[:, None], used.shape)[used].astype(np.uint32))

@@ -1,6 +1,7 @@
 // ntuple.hip -- an n-tuple afterstate value function, its greedy / epsilon-greedy placement policy and its temporal-difference
 // update: tpl_ntuple_value, tpl_ntuple_act, tpl_ntuple_search, tpl_ntuple_update, tpl_ntuple_update_trace,
-// tpl_ntuple_update_coherent, their _shaped twins and the _sum twins of the first three (include/tpl_learn.h states the rule).
+// tpl_ntuple_update_coherent, their _shaped twins, the _sum twins of the first three and the _staged twins of value, act, search
+// and update_trace (include/tpl_learn.h states the rule).
 //
 // The value of a board is a sum of table look-ups: 153 windows of two adjacent columns by four rows, each a 256-entry row of an
 // int32 table chosen by the piece that falls next, plus one entry for the lines and moves that are left.  In the column layout a
@@ -58,6 +59,12 @@
 // table and a 3 x 3 table behind one pointer, whose board sum is the two gather loops one after the other (tpl_ntuple.h).  The
 // three ntuple_sum_*_kernel are value_lane and ntuple_policy named with it, on the unchanged argument structs.  The updates have
 // no such kernel: they never read the table, so the host sends one error array through the existing kernels once per part.
+//
+// Staged tables (the _staged entries).  StagedOf<S> is a second composite trait: eight tables of the form S and a map from the
+// counter index to one of them (tpl_ntuple.h), so value_lane and ntuple_policy named with it are the nine ntuple_staged*_kernel,
+// and a leaf of the two-ply search reads the block of its OWN lines and moves left.  The update does get kernels of its own here:
+// where a state's adds go depends on its stage, so staged_trace_lane is trace_lane with the block's offset in every index.  It
+// reads the map, which nothing writes, and adds to the blocks, which it never reads.
 #include <cmath>
 
 #include "tpl_ntuple.h"
@@ -94,6 +101,9 @@ __device__ __forceinline__ void value_lane(const ValueArgs& p) {
 __global__ __launch_bounds__(kStateBlock) void ntuple_value_kernel(const ValueArgs p) { value_lane<Shape2x4>(p); }
 __global__ __launch_bounds__(kStateBlock) void ntuple3_value_kernel(const ValueArgs p) { value_lane<Shape3x3>(p); }
 __global__ __launch_bounds__(kStateBlock) void ntuple_sum_value_kernel(const ValueArgs p) { value_lane<ShapeSum>(p); }
+__global__ __launch_bounds__(kStateBlock) void ntuple_staged_value_kernel(const ValueArgs p) { value_lane<StagedOf<Shape2x4>>(p); }
+__global__ __launch_bounds__(kStateBlock) void ntuple_staged3_value_kernel(const ValueArgs p) { value_lane<StagedOf<Shape3x3>>(p); }
+__global__ __launch_bounds__(kStateBlock) void ntuple_staged_sum_value_kernel(const ValueArgs p) { value_lane<StagedOf<ShapeSum>>(p); }
 
 // d = (int32) rint(rate * e): the product rounded once, clamped to +-2^24, 0 for a NaN
 __device__ __forceinline__ int32_t update_step(float rate, float e) {
@@ -172,6 +182,79 @@ template <bool kSymmetric>
 __global__ __launch_bounds__(kStateBlock) void ntuple_trace_kernel(const TraceArgs p) { trace_lane<Shape2x4, kSymmetric>(p); }
 template <bool kSymmetric>
 __global__ __launch_bounds__(kStateBlock) void ntuple3_trace_kernel(const TraceArgs p) { trace_lane<Shape3x3, kSymmetric>(p); }
+
+// ---- the staged update: tpl_ntuple_update_trace_staged ----
+struct StagedTraceArgs {
+    TraceArgs t;                 // t.table: entry 0 of the part that is updated, in the block of stage 0
+    const int32_t* map;          // [1,024], read and never written: the stage of counter index k is map[k] & 7
+    uint32_t stride;             // entries from a stage's block to the next: the whole form's, a multiple of 512
+};
+
+// trace_lane on a staged table: the same lane, rate, trace cut and step, with every add at the block of the state's stage -- the
+// windows through the offset in `base`, the counter sums, still one per k and per block in LDS, through the offset of k's own stage
+// at the flush.  The reflected board has the state's lines and moves, so its adds go to the same block.
+template <typename S, bool kSymmetric>
+__device__ __forceinline__ void staged_trace_lane(const StagedTraceArgs p) {
+    __shared__ uint32_t s_counter[kCounters];
+#pragma unroll
+    for (int t = threadIdx.x; t < kCounters; t += kStateBlock) s_counter[t] = 0u;
+    __syncthreads();
+    const uint32_t age = blockIdx.y;
+    float w = 1.0f;
+    for (uint32_t k = 0; k < age; ++k) w = __fmul_rn(w, p.t.decay);
+    const float rate = __fmul_rn(p.t.rate, w);
+    const uint32_t i = blockIdx.x * kStateBlock + threadIdx.x;
+    if (i < p.t.n) {
+        bool open = true;
+        for (uint32_t k = 0; k < age; ++k) {
+            const uint32_t slot = p.t.head >= k ? p.t.head - k : p.t.head + p.t.slots - k;
+            open = open && ((p.t.b[slot * p.t.n + i].y >> 28) & 3u) == tpl::ST_RUNNING;
+        }
+        const uint32_t d = (uint32_t)update_step(rate, p.t.error[i]);
+        if (open && d != 0u) {
+            const uint32_t slot = p.t.head >= age ? p.t.head - age : p.t.head + p.t.slots - age;
+            tpl::Board s;
+            tpl::unpack_board(p.t.a[slot * p.t.n + i], p.t.b[slot * p.t.n + i], s);
+            if (s.state == tpl::ST_RUNNING) {
+                const uint32_t k = counter_index(p.t.L, p.t.M, s.lines, s.moves);
+                atomicAdd(&s_counter[k], d);
+                const uint32_t at = stage_offset(p.map, 0u, k, p.stride);
+                const uint32_t piece = s.window & 7u;
+                const uint32_t base = at + piece * (uint32_t)S::kPieceStride;
+                const uint32_t mirror_base = at + ((kPieceMirror >> (4u * piece)) & 7u) * (uint32_t)S::kPieceStride;
+#pragma unroll 1
+                for (uint32_t y = 0; y < (uint32_t)S::kTupleRows; ++y) {
+#pragma unroll
+                    for (int x = 0; x < S::kTupleCols; ++x) {
+                        const uint32_t q = S::pattern(s.c, x, y);
+                        if (q) {
+                            atomicAdd(entry(p.t.table, tuple_entry<S>(base, x, y, q)), d);
+                            if constexpr (kSymmetric) {
+                                const uint32_t swapped = S::mirrored(q);
+                                atomicAdd(entry(p.t.table, tuple_entry<S>(mirror_base, S::kTupleCols - 1 - x, y, swapped)), d);
+                            }
+                        }
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int t = threadIdx.x; t < kCounters; t += kStateBlock) {
+        const uint32_t sum = s_counter[t];
+        if (sum) atomicAdd(entry(p.t.table, stage_offset(p.map, 0u, (uint32_t)t, p.stride) + (uint32_t)S::kCounterBase + (uint32_t)t), sum);
+    }
+}
+
+template <bool kSymmetric>
+__global__ __launch_bounds__(kStateBlock) void ntuple_staged_trace_kernel(const StagedTraceArgs p) {
+    staged_trace_lane<Shape2x4, kSymmetric>(p);
+}
+template <bool kSymmetric>
+__global__ __launch_bounds__(kStateBlock) void ntuple_staged3_trace_kernel(const StagedTraceArgs p) {
+    staged_trace_lane<Shape3x3, kSymmetric>(p);
+}
 
 // ---- the coherent update: tpl_ntuple_update_coherent ----
 // Two kernels in ntuple_trace_kernel's frame (a lane per (board, age), the age in blockIdx.y): the step kernel reads the coherence
@@ -458,6 +541,21 @@ __global__ __launch_bounds__(kActBlock) void ntuple3_act_kernel(const ActArgs p)
 __global__ __launch_bounds__(kActBlock) void ntuple3_search_kernel(const SearchArgs p) { ntuple_policy<Shape3x3, 2>(p.act, p.second); }
 __global__ __launch_bounds__(kActBlock) void ntuple_sum_act_kernel(const ActArgs p) { ntuple_policy<ShapeSum, 1>(p, nullptr); }
 __global__ __launch_bounds__(kActBlock) void ntuple_sum_search_kernel(const SearchArgs p) { ntuple_policy<ShapeSum, 2>(p.act, p.second); }
+__global__ __launch_bounds__(kActBlock) void ntuple_staged_act_kernel(const ActArgs p) { ntuple_policy<StagedOf<Shape2x4>, 1>(p, nullptr); }
+__global__ __launch_bounds__(kActBlock) void ntuple_staged_search_kernel(const SearchArgs p) {
+    ntuple_policy<StagedOf<Shape2x4>, 2>(p.act, p.second);
+}
+__global__ __launch_bounds__(kActBlock) void ntuple_staged3_act_kernel(const ActArgs p) { ntuple_policy<StagedOf<Shape3x3>, 1>(p, nullptr); }
+__global__ __launch_bounds__(kActBlock) void ntuple_staged3_search_kernel(const SearchArgs p) {
+    ntuple_policy<StagedOf<Shape3x3>, 2>(p.act, p.second);
+}
+__global__ __launch_bounds__(kActBlock) void ntuple_staged_sum_act_kernel(const ActArgs p) { ntuple_policy<StagedOf<ShapeSum>, 1>(p, nullptr); }
+// Four waves a SIMD, 128 vector registers: at the default budget the compiler made room for the block's offset by issuing the second
+// ply's gathers one at a time, in both parts (1.63 times ntuple_sum_search_kernel with one stage live; 1.05 with nine in flight:
+// profiles/learner/README.md).  The other staged kernels keep their twins' loops at the default.
+__global__ __launch_bounds__(kActBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) void ntuple_staged_sum_search_kernel(const SearchArgs p) {
+    ntuple_policy<StagedOf<ShapeSum>, 2>(p.act, p.second);
+}
 
 }  // namespace
 }  // namespace tpl_learn
@@ -475,7 +573,7 @@ namespace {
 // what tpl_ntuple_value, tpl_ntuple_value_shaped (its shape checked before it comes here) and tpl_ntuple_value_sum share: the
 // checks and the launch
 int launch_value(const char* name, const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const int32_t* table,
-                 float* value, Form form, void* stream) {
+                 float* value, Form form, void* stream, bool staged = false) {
     if (const int rc = check_planes(name, plane_a, plane_b, n, L, M)) return rc;
     if (const int rc = check_table(name, table)) return rc;
     if (!value) return fail_msg(TPL_ERR_ARG, "%s: null pointer (value is required)", name);
@@ -484,7 +582,11 @@ int launch_value(const char* name, const void* plane_a, const void* plane_b, int
     p.a = (const uint4*)plane_a; p.b = (const uint4*)plane_b; p.n = (uint32_t)n;
     p.L = (uint32_t)L; p.M = (uint32_t)M; p.table = table; p.value = value;
     const dim3 grid((p.n + kStateBlock - 1) / kStateBlock), block(kStateBlock);
-    if (form == Form::kSum) hipLaunchKernelGGL(ntuple_sum_value_kernel, grid, block, 0, (hipStream_t)stream, p);
+    if (staged) {
+        const auto kernel = form == Form::kSum ? ntuple_staged_sum_value_kernel
+                                               : form == Form::k3x3 ? ntuple_staged3_value_kernel : ntuple_staged_value_kernel;
+        hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, p);
+    } else if (form == Form::kSum) hipLaunchKernelGGL(ntuple_sum_value_kernel, grid, block, 0, (hipStream_t)stream, p);
     else if (form == Form::k3x3) hipLaunchKernelGGL(ntuple3_value_kernel, grid, block, 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(ntuple_value_kernel, grid, block, 0, (hipStream_t)stream, p);
     TPL_LEARN_HIP(hipGetLastError());
@@ -496,7 +598,7 @@ int launch_value(const char* name, const void* plane_a, const void* plane_b, int
 int launch_ntuple_policy(const char* name, int depth, const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M,
                          float r_line, float r_win, float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed,
                          uint64_t step, uint8_t* action, uint8_t* second, float* score, void* after_a, void* after_b, float* value,
-                         Form form, void* stream) {
+                         Form form, void* stream, bool staged = false) {
     if (const int rc = check_planes(name, plane_a, plane_b, n, L, M)) return rc;
     if (const int rc = check_table(name, table)) return rc;
     if (!action) return fail_msg(TPL_ERR_ARG, "%s: null pointer (action is required)", name);
@@ -516,7 +618,14 @@ int launch_ntuple_policy(const char* name, int depth, const void* plane_a, const
     p.action = action; p.score = score; p.after_a = (uint4*)after_a; p.after_b = (uint4*)after_b; p.value = value;
     const dim3 grid((p.n + kBoardsPerBlock - 1) / kBoardsPerBlock), block(kActBlock);
     const bool wide = form == Form::k3x3;
-    if (depth == 2) {
+    if (staged && depth == 2) {
+        const SearchArgs q{p, second};
+        const auto kernel = form == Form::kSum ? ntuple_staged_sum_search_kernel : wide ? ntuple_staged3_search_kernel : ntuple_staged_search_kernel;
+        hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, q);
+    } else if (staged) {
+        const auto kernel = form == Form::kSum ? ntuple_staged_sum_act_kernel : wide ? ntuple_staged3_act_kernel : ntuple_staged_act_kernel;
+        hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, p);
+    } else if (depth == 2) {
         const SearchArgs q{p, second};
         if (form == Form::kSum) hipLaunchKernelGGL(ntuple_sum_search_kernel, grid, block, 0, (hipStream_t)stream, q);
         else if (wide) hipLaunchKernelGGL(ntuple3_search_kernel, grid, block, 0, (hipStream_t)stream, q);
@@ -598,12 +707,37 @@ extern "C" int tpl_ntuple_search_sum(const void* plane_a, const void* plane_b, i
                                 seed, step, action, second, score, after_a, after_b, value, Form::kSum, stream);
 }
 
+extern "C" int tpl_ntuple_value_staged(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M,
+                                       const int32_t* table, float* value, int32_t form, void* stream) {
+    if (const int rc = check_form("tpl_ntuple_value_staged", form)) return rc;
+    return launch_value("tpl_ntuple_value_staged", plane_a, plane_b, n, L, M, table, value, (Form)form, stream, true);
+}
+
+extern "C" int tpl_ntuple_act_staged(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line,
+                                     float r_win, float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed,
+                                     uint64_t step, uint8_t* action, float* score, void* after_a, void* after_b, float* value,
+                                     int32_t form, void* stream) {
+    if (const int rc = check_form("tpl_ntuple_act_staged", form)) return rc;
+    return launch_ntuple_policy("tpl_ntuple_act_staged", 1, plane_a, plane_b, n, L, M, r_line, r_win, r_lose, gamma, table, epsilon,
+                                seed, step, action, nullptr, score, after_a, after_b, value, (Form)form, stream, true);
+}
+
+extern "C" int tpl_ntuple_search_staged(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line,
+                                        float r_win, float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed,
+                                        uint64_t step, uint8_t* action, uint8_t* second, float* score, void* after_a, void* after_b,
+                                        float* value, int32_t form, void* stream) {
+    if (const int rc = check_form("tpl_ntuple_search_staged", form)) return rc;
+    return launch_ntuple_policy("tpl_ntuple_search_staged", 2, plane_a, plane_b, n, L, M, r_line, r_win, r_lose, gamma, table,
+                                epsilon, seed, step, action, second, score, after_a, after_b, value, (Form)form, stream, true);
+}
+
 namespace {
 
 // what the three updates refuse alike; `coherence`: where the entry takes a coherence buffer, the address of its pointer
 int check_update(const char* name, int32_t shape, const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M,
-                 const int32_t* table, const float* error, float rate, const int64_t* const* coherence = nullptr) {
-    if (const int rc = check_shape(name, shape)) return rc;
+                 const int32_t* table, const float* error, float rate, const int64_t* const* coherence = nullptr,
+                 bool staged = false) {
+    if (const int rc = staged ? check_form(name, shape) : check_shape(name, shape)) return rc;
     if (const int rc = check_planes(name, plane_a, plane_b, n, L, M)) return rc;
     if (const int rc = check_table(name, table)) return rc;
     if (coherence && !*coherence) return fail_msg(TPL_ERR_ARG, "%s: null pointer (coherence is required)", name);
@@ -697,6 +831,37 @@ extern "C" int tpl_ntuple_update_trace_shaped(const void* ring_a, const void* ri
                                               float decay, int32_t symmetric, int32_t shape, void* stream) {
     return update_ring("tpl_ntuple_update_trace_shaped", ring_a, ring_b, n, slots, head, horizon, L, M, table, nullptr, error, rate,
                        decay, symmetric, shape, stream);
+}
+
+// The staged update: the part updates of the form, each on its part of every block -- the part's entry 0 in stage 0 as the kernel's
+// table, the whole form's entries as the stride between blocks, the map behind the eighth block.
+extern "C" int tpl_ntuple_update_trace_staged(const void* ring_a, const void* ring_b, int64_t n, int32_t slots, int32_t head,
+                                              int32_t horizon, int32_t L, int32_t M, int32_t* table, const float* error, float rate,
+                                              float decay, int32_t symmetric, int32_t form, void* stream) {
+    const char* const name = "tpl_ntuple_update_trace_staged";
+    if (const int rc = check_update(name, form, ring_a, ring_b, n, L, M, table, error, rate, nullptr, true)) return rc;
+    if (const int rc = check_ring(name, n, slots, head, horizon, decay)) return rc;
+    const uint32_t stride = form == TPL_NTUPLE_FORM_SUM ? (uint32_t)ShapeSum::kEntries
+                                                        : form == TPL_NTUPLE_FORM_3X3 ? (uint32_t)Shape3x3::kEntries : (uint32_t)Shape2x4::kEntries;
+    StagedTraceArgs p{};
+    p.t.a = (const uint4*)ring_a; p.t.b = (const uint4*)ring_b; p.t.n = (uint32_t)n; p.t.slots = (uint32_t)slots;
+    p.t.head = (uint32_t)head; p.t.L = (uint32_t)L; p.t.M = (uint32_t)M; p.t.error = error; p.t.rate = rate; p.t.decay = decay;
+    p.map = table + (size_t)TPL_NTUPLE_STAGES * stride;
+    p.stride = stride;
+    const dim3 grid((p.t.n + kStateBlock - 1) / kStateBlock, (uint32_t)horizon), block(kStateBlock);
+    if (form != TPL_NTUPLE_FORM_3X3) {                                  // the 2 x 4 part, at the block's base
+        p.t.table = (uint32_t*)table;
+        hipLaunchKernelGGL(symmetric ? ntuple_staged_trace_kernel<true> : ntuple_staged_trace_kernel<false>, grid, block, 0,
+                           (hipStream_t)stream, p);
+        TPL_LEARN_HIP(hipGetLastError());
+    }
+    if (form != TPL_NTUPLE_FORM_2X4) {                                  // the 3 x 3 part: of a sum, behind the 2 x 4 part
+        p.t.table = (uint32_t*)table + (form == TPL_NTUPLE_FORM_SUM ? ShapeSum::kSecondAt : 0u);
+        hipLaunchKernelGGL(symmetric ? ntuple_staged3_trace_kernel<true> : ntuple_staged3_trace_kernel<false>, grid, block, 0,
+                           (hipStream_t)stream, p);
+        TPL_LEARN_HIP(hipGetLastError());
+    }
+    return TPL_OK;
 }
 
 extern "C" int tpl_ntuple_update_coherent(const void* ring_a, const void* ring_b, int64_t n, int32_t slots, int32_t head,

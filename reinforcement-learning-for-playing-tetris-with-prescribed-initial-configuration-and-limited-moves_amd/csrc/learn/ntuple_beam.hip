@@ -1,5 +1,7 @@
 // ntuple_beam.hip -- a beam search over the known piece window with an n-tuple table at the leaves: tpl_ntuple_beam and, with a
-// sum table there (ShapeSum of tpl_ntuple.h: ntuple_beam_sum_kernel), tpl_ntuple_beam_sum (include/tpl_learn.h states the rule).
+// sum table there (ShapeSum of tpl_ntuple.h: ntuple_beam_sum_kernel), tpl_ntuple_beam_sum; with a staged table of any form
+// (StagedOf: the three ntuple_staged_beam*_kernel), where every leaf reads the block of its own lines and moves left,
+// tpl_ntuple_beam_staged (include/tpl_learn.h states the rule).
 //
 // The frame is placement_beam_kernel's (tpl_beam.h; beam.hip's comment has the reasons): ONE BOARD PER WORKGROUP of 256 threads,
 // both beams and the candidate keys in LDS -- 25 KB in all, so six groups share a CU --, and a ply in three phases: A keys every
@@ -201,6 +203,11 @@ __device__ __forceinline__ void ntuple_beam(const NTupleBeamArgs& p) {
 __global__ __launch_bounds__(kBeamBlock) void ntuple_beam_kernel(const NTupleBeamArgs p) { ntuple_beam<Shape2x4>(p); }
 __global__ __launch_bounds__(kBeamBlock) void ntuple_beam3_kernel(const NTupleBeamArgs p) { ntuple_beam<Shape3x3>(p); }
 __global__ __launch_bounds__(kBeamBlock) void ntuple_beam_sum_kernel(const NTupleBeamArgs p) { ntuple_beam<ShapeSum>(p); }
+__global__ __launch_bounds__(kBeamBlock) void ntuple_staged_beam_kernel(const NTupleBeamArgs p) { ntuple_beam<StagedOf<Shape2x4>>(p); }
+__global__ __launch_bounds__(kBeamBlock) void ntuple_staged_beam3_kernel(const NTupleBeamArgs p) { ntuple_beam<StagedOf<Shape3x3>>(p); }
+// four waves a SIMD: as for ntuple_staged_sum_search_kernel (ntuple.hip), the gathers of a leaf go out nine and eight at a time
+// under this budget and one at a time under the default one (1.22 times ntuple_beam_sum_kernel with one stage live; 0.86 so)
+__global__ __launch_bounds__(kBeamBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) void ntuple_staged_beam_sum_kernel(const NTupleBeamArgs p) { ntuple_beam<StagedOf<ShapeSum>>(p); }
 
 }  // namespace
 }  // namespace tpl_learn
@@ -209,10 +216,11 @@ using namespace tpl_learn;
 
 namespace {
 
-// what tpl_ntuple_beam (its shape checked before it comes here) and tpl_ntuple_beam_sum share: the checks and the launch
+// what tpl_ntuple_beam (its shape checked before it comes here), tpl_ntuple_beam_sum and tpl_ntuple_beam_staged (its form checked
+// before) share: the checks and the launch
 int launch_ntuple_beam(const char* name, const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line,
                        float r_win, float r_lose, float gamma, const int32_t* table, int32_t depth, int32_t width, uint8_t* action,
-                       uint8_t* plan, float* score, void* after_a, void* after_b, Form form, void* stream) {
+                       uint8_t* plan, float* score, void* after_a, void* after_b, Form form, void* stream, bool staged = false) {
     if (const int rc = check_planes(name, plane_a, plane_b, n, L, M)) return rc;
     if (const int rc = check_table(name, table)) return rc;
     if (!action) return fail_msg(TPL_ERR_ARG, "%s: null pointer (action is required)", name);
@@ -228,7 +236,11 @@ int launch_ntuple_beam(const char* name, const void* plane_a, const void* plane_
     p.L = (uint32_t)L; p.M = (uint32_t)M; p.r_line = r_line; p.r_win = r_win; p.r_lose = r_lose; p.gamma = gamma;
     p.table = table; p.depth = (uint32_t)depth; p.width = (uint32_t)width;
     p.action = action; p.plan = plan; p.score = score; p.after_a = (uint4*)after_a; p.after_b = (uint4*)after_b;
-    if (form == Form::kSum) hipLaunchKernelGGL(ntuple_beam_sum_kernel, dim3(p.n), dim3(kBeamBlock), 0, (hipStream_t)stream, p);
+    if (staged) {
+        const auto kernel = form == Form::kSum ? ntuple_staged_beam_sum_kernel
+                                               : form == Form::k3x3 ? ntuple_staged_beam3_kernel : ntuple_staged_beam_kernel;
+        hipLaunchKernelGGL(kernel, dim3(p.n), dim3(kBeamBlock), 0, (hipStream_t)stream, p);
+    } else if (form == Form::kSum) hipLaunchKernelGGL(ntuple_beam_sum_kernel, dim3(p.n), dim3(kBeamBlock), 0, (hipStream_t)stream, p);
     else if (form == Form::k3x3) hipLaunchKernelGGL(ntuple_beam3_kernel, dim3(p.n), dim3(kBeamBlock), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(ntuple_beam_kernel, dim3(p.n), dim3(kBeamBlock), 0, (hipStream_t)stream, p);
     TPL_LEARN_HIP(hipGetLastError());
@@ -250,4 +262,13 @@ extern "C" int tpl_ntuple_beam_sum(const void* plane_a, const void* plane_b, int
                                    uint8_t* action, uint8_t* plan, float* score, void* after_a, void* after_b, void* stream) {
     return launch_ntuple_beam("tpl_ntuple_beam_sum", plane_a, plane_b, n, L, M, r_line, r_win, r_lose, gamma, table, depth, width,
                               action, plan, score, after_a, after_b, Form::kSum, stream);
+}
+
+extern "C" int tpl_ntuple_beam_staged(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line,
+                                      float r_win, float r_lose, float gamma, const int32_t* table, int32_t depth, int32_t width,
+                                      uint8_t* action, uint8_t* plan, float* score, void* after_a, void* after_b, int32_t form,
+                                      void* stream) {
+    if (const int rc = check_form("tpl_ntuple_beam_staged", form)) return rc;
+    return launch_ntuple_beam("tpl_ntuple_beam_staged", plane_a, plane_b, n, L, M, r_line, r_win, r_lose, gamma, table, depth, width,
+                              action, plan, score, after_a, after_b, (Form)form, stream, true);
 }

@@ -1,6 +1,6 @@
 // tpl_ntuple.h -- what the units that read an n-tuple table share (ntuple.hip, ntuple_beam.hip; include/tpl_learn.h states the
-// rule): the geometry of the two table shapes and of their sum, the counter index, the 32-bit addressing of an entry, the sum and
-// the value of a running board, and the shape and table checks of the entry points.
+// rule): the geometry of the two table shapes, of their sum and of a staged table of any of the three, the counter index, the
+// 32-bit addressing of an entry, the sum and the value of a running board, and the shape, form and table checks of the entry points.
 #pragma once
 
 #include "tpl_placement.h"
@@ -21,6 +21,7 @@ struct Shape2x4 {
     static constexpr int kPatterns = 256;
     static constexpr int kPieceStride = kTuples * kPatterns;
     static constexpr int kCounterBase = 8 * kPieceStride;     // 313,344
+    static constexpr int kEntries = kCounterBase + kCounters;
     // the pattern of tuple (x, y): the two columns' nibbles at row y
     static __device__ __forceinline__ uint32_t pattern(const uint32_t (&c)[tpl::kCols], int x, uint32_t y) {
         return ((c[x] >> y) & 15u) | (((c[x + 1] >> y) & 15u) << 4);
@@ -28,7 +29,7 @@ struct Shape2x4 {
     // the pattern of the reflected window: the nibbles swapped
     static __device__ __forceinline__ uint32_t mirrored(uint32_t q) { return (q >> 4) | ((q & 15u) << 4); }
 };
-static_assert(Shape2x4::kCounterBase + kCounters == TPL_NTUPLE_ENTRIES, "the table layout of include/tpl_learn.h");
+static_assert(Shape2x4::kEntries == TPL_NTUPLE_ENTRIES, "the table layout of include/tpl_learn.h");
 
 struct Shape3x3 {
     static constexpr int kWindowCols = 3, kWindowRows = 3;
@@ -38,6 +39,7 @@ struct Shape3x3 {
     static constexpr int kPatterns = 512;
     static constexpr int kPieceStride = kTuples * kPatterns;
     static constexpr int kCounterBase = 8 * kPieceStride;     // 589,824
+    static constexpr int kEntries = kCounterBase + kCounters;
     // the pattern of tuple (x, y): the three columns' triplets at row y
     static __device__ __forceinline__ uint32_t pattern(const uint32_t (&c)[tpl::kCols], int x, uint32_t y) {
         return ((c[x] >> y) & 7u) | (((c[x + 1] >> y) & 7u) << 3) | (((c[x + 2] >> y) & 7u) << 6);
@@ -45,7 +47,7 @@ struct Shape3x3 {
     // the pattern of the reflected window: the outer triplets swapped, the middle one stays
     static __device__ __forceinline__ uint32_t mirrored(uint32_t q) { return (q >> 6) | (q & 0x38u) | ((q & 7u) << 6); }
 };
-static_assert(Shape3x3::kCounterBase + kCounters == TPL_NTUPLE_ENTRIES_3X3, "the table layout of include/tpl_learn.h");
+static_assert(Shape3x3::kEntries == TPL_NTUPLE_ENTRIES_3X3, "the table layout of include/tpl_learn.h");
 
 // k = 64 min(max(L - lines, 0), 15) + min(max(M - moves, 0), 63)
 __device__ __forceinline__ uint32_t counter_index(uint32_t L, uint32_t M, uint32_t lines, uint32_t moves) {
@@ -54,7 +56,7 @@ __device__ __forceinline__ uint32_t counter_index(uint32_t L, uint32_t M, uint32
     return (uint32_t)(left_l * kCounterMoves + left_m);
 }
 
-// entry `index` of the table through a 32-bit byte offset from the (uniform) base: the largest buffer, a 3 x 3 coherence buffer, is 9.5 MB, and an
+// entry `index` of the table through a 32-bit byte offset from the (uniform) base: the largest buffer, a staged sum table, is 29 MB, and an
 // index the compiler has to widen costs a 64-bit shift and a 64-bit add per look-up
 template <typename T>
 __device__ __forceinline__ T* entry(T* table, uint32_t index) {
@@ -73,11 +75,14 @@ __device__ __forceinline__ uint32_t tuple_entry(uint32_t base, int x, uint32_t y
 }
 
 // The integer value of a running board with column words c (bits 20.. clear), falling piece `piece` and counter entry k: the
-// sum over the tuples with a non-zero pattern plus the counter, exact in 64 bits.
+// sum over the tuples with a non-zero pattern plus the counter, exact in 64 bits.  `at`: the entry of `table` where the table of
+// shape S starts, a multiple of kPatterns (tuple_entry) -- 0, or a stage's block of a staged table: a lane's own offset joins the
+// 32-bit index, and the pointer stays the wave's.
 template <typename S>
-__device__ __forceinline__ long long ntuple_sum(const uint32_t (&c)[tpl::kCols], uint32_t piece, uint32_t k, const int32_t* table) {
-    const uint32_t base = piece * (uint32_t)S::kPieceStride;
-    long long sum = *entry(table, (uint32_t)S::kCounterBase + k);
+__device__ __forceinline__ long long ntuple_sum(const uint32_t (&c)[tpl::kCols], uint32_t piece, uint32_t k, const int32_t* table,
+                                                uint32_t at = 0u) {
+    const uint32_t base = at + piece * (uint32_t)S::kPieceStride;
+    long long sum = *entry(table, at + (uint32_t)S::kCounterBase + k);
 #pragma unroll 1
     for (uint32_t y = 0; y < (uint32_t)S::kTupleRows; ++y) {
         int32_t v[S::kTupleCols];
@@ -101,6 +106,7 @@ struct SumOf {
     using First = A;
     using Second = B;
     static constexpr uint32_t kSecondAt = kEntriesOfFirst;    // the entry where the second part starts
+    static constexpr int kEntries = kEntriesOfFirst + B::kEntries;
 };
 using ShapeSum = SumOf<Shape2x4, Shape3x3, TPL_NTUPLE_ENTRIES>;
 static_assert(ShapeSum::kSecondAt + TPL_NTUPLE_ENTRIES_3X3 == TPL_NTUPLE_ENTRIES_SUM && (ShapeSum::kSecondAt * sizeof(int32_t)) % 16 == 0 &&
@@ -123,6 +129,49 @@ struct BoardSum<SumOf<A, B, kEntriesOfFirst>> {
     }
 };
 
+// The geometry of a STAGED TABLE of the form S (include/tpl_learn.h): TPL_NTUPLE_STAGES whole tables of S one behind the other, then
+// the stage map, an int32 per counter index.  Like SumOf it has no windows of its own and is reached through board_sum alone: the
+// state's k picks the block, one dword gathered from the 4 KB map, and the block's offset goes into ntuple_sum's 32-bit index.
+template <typename S>
+struct StagedOf {
+    using Stage = S;
+    static constexpr uint32_t kStride = S::kEntries;          // entries from a stage's block to the next
+    static constexpr uint32_t kMapAt = TPL_NTUPLE_STAGES * kStride;
+    static constexpr int kEntries = kMapAt + kCounters;
+};
+static_assert(StagedOf<Shape2x4>::kEntries == TPL_NTUPLE_ENTRIES_STAGED && StagedOf<Shape3x3>::kEntries == TPL_NTUPLE_ENTRIES_STAGED_3X3 &&
+                  StagedOf<ShapeSum>::kEntries == TPL_NTUPLE_ENTRIES_STAGED_SUM,
+              "the staged tables' layout of include/tpl_learn.h");
+static_assert(Shape2x4::kEntries % 512 == 0 && Shape3x3::kEntries % 512 == 0,
+              "every stage's block, and every part in it, starts at a multiple of both shapes' kPatterns (tuple_entry) and of 16 bytes");
+static_assert((unsigned long long)StagedOf<ShapeSum>::kEntries * sizeof(int32_t) < (1ull << 31), "byte offsets fit 32 bits");
+
+// The offset of the block of the stage that counter index k falls in: (map[k] & 7) * stride.  The mask is the rule, not a guard: a
+// map that holds anything addresses a block of the buffer.  `map_at`: the entry of `table` where the map starts.
+__device__ __forceinline__ uint32_t stage_offset(const int32_t* table, uint32_t map_at, uint32_t k, uint32_t stride) {
+    return ((uint32_t)*entry(table, map_at + k) & (uint32_t)(TPL_NTUPLE_STAGES - 1)) * stride;
+}
+
+// The board sum of the form S from the block that starts at entry `at`: ntuple_sum, or for a sum of shapes the two parts' sums.
+template <typename S>
+struct BlockSum {
+    static __device__ __forceinline__ long long of(const uint32_t (&c)[tpl::kCols], uint32_t piece, uint32_t k, const int32_t* table, uint32_t at) {
+        return ntuple_sum<S>(c, piece, k, table, at);
+    }
+};
+template <typename A, typename B, int kEntriesOfFirst>
+struct BlockSum<SumOf<A, B, kEntriesOfFirst>> {
+    static __device__ __forceinline__ long long of(const uint32_t (&c)[tpl::kCols], uint32_t piece, uint32_t k, const int32_t* table, uint32_t at) {
+        return ntuple_sum<A>(c, piece, k, table, at) + ntuple_sum<B>(c, piece, k, table, at + (uint32_t)kEntriesOfFirst);
+    }
+};
+template <typename S>
+struct BoardSum<StagedOf<S>> {
+    static __device__ __forceinline__ long long of(const uint32_t (&c)[tpl::kCols], uint32_t piece, uint32_t k, const int32_t* table) {
+        return BlockSum<S>::of(c, piece, k, table, stage_offset(table, StagedOf<S>::kMapAt, k, StagedOf<S>::kStride));
+    }
+};
+
 // V of a state that runs: one rounding from the 64-bit sum to float32, then an exact scaling by 2^-16
 template <typename S>
 __device__ __forceinline__ float ntuple_value(const tpl::Board& s, uint32_t L, uint32_t M, const int32_t* table) {
@@ -130,9 +179,20 @@ __device__ __forceinline__ float ntuple_value(const tpl::Board& s, uint32_t L, u
     return (float)sum * 0x1p-16f;
 }
 
-// Which kernels an entry launches: the two shapes of tpl_ntuple_shape, and their sum, which is no `shape` of the C interface.
+// Which kernels an entry launches: the two shapes of tpl_ntuple_shape, and their sum, which is no `shape` of the C interface.  The
+// _staged entries take all three as their `form` (tpl_ntuple_form has the enumerators' values).
 enum class Form { k2x4, k3x3, kSum };
 inline Form form_of(int32_t shape) { return shape == TPL_NTUPLE_SHAPE_3X3 ? Form::k3x3 : Form::k2x4; }   // after check_shape
+static_assert((int)Form::k2x4 == TPL_NTUPLE_FORM_2X4 && (int)Form::k3x3 == TPL_NTUPLE_FORM_3X3 && (int)Form::kSum == TPL_NTUPLE_FORM_SUM,
+              "a checked `form` converts to Form");
+
+// a form the library does not know is refused first, before any pointer is looked at
+inline int check_form(const char* name, int32_t form) {
+    if (form != TPL_NTUPLE_FORM_2X4 && form != TPL_NTUPLE_FORM_3X3 && form != TPL_NTUPLE_FORM_SUM)
+        return fail_msg(TPL_ERR_ARG, "%s: form must be TPL_NTUPLE_FORM_2X4 (0), TPL_NTUPLE_FORM_3X3 (1) or TPL_NTUPLE_FORM_SUM (2), got %d",
+                        name, (int)form);
+    return TPL_OK;
+}
 
 // a shape the library does not know is refused first, before any pointer is looked at
 inline int check_shape(const char* name, int32_t shape) {

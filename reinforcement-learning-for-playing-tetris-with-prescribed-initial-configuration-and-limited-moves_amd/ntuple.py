@@ -32,6 +32,14 @@ learning on the device (the rule: include/tpl_learn.h; the kernels: csrc/learn/n
     ntuple_coherence(device, shape="2x4")
                                   a zeroed coherence buffer: int64 [entries of the shape, 2], the pairs (E, A)
     ntuple_step_sizes(coherence)  alpha of every entry: float32 [entries]
+    ntuple_table(device, shape, staged=True)
+                                  a zeroed STAGED TABLE: NTUPLE_STAGES = 8 whole tables of the form and a stage map, one int32 buffer
+    ntuple_stage_map(L, M, lines=1, moves=4)
+                                  int32 [1,024]: a grid of lines x moves <= 8 buckets over (lines left, moves left)
+    ntuple_staged(table, stage_map)
+                                  weight promotion: a staged table whose eight blocks are each a copy of a plain table, with the map
+    ntuple_stages(table), ntuple_map(table), ntuple_is_staged(table)
+                                  the eight per-stage views (each a valid plain table of the form), the map view, the test
 
 The value is a sum of table entries, one per 2 x 4 window of the board that is not empty, chosen by the falling piece, plus one
 per (lines left, moves left); the update adds rint(rate * error) to the same entries.  Everything is integer, so two trainings
@@ -43,6 +51,14 @@ Two shapes summed ("2x4+3x3", the standard form of an n-tuple network): V = floa
 integer sums added before the one rounding.  The value, both policies and the beam read a sum table in one launch each (the _sum
 entries of include/tpl_learn.h); the update kernels never read the table, so the learner sends its errors through the existing
 update once per part.  Everything that takes a table takes a sum table, by its entry count.
+
+Staged tables.  In a plain table the move budget enters the value additively: V = f(board, piece) + counter[lines left, moves left].
+A staged table holds eight whole tables of one form ("2x4", "3x3" or "2x4+3x3") and a map from the counter index to one of them: the
+stage of a state is map[k] & 7, and V is the form's value read from that block -- so the same stack can be worth one thing with
+three moves left and another with thirty.  The stage is looked up wherever a table is read, ply by ply: a leaf of the two-ply search
+or of the beam is valued in the block of its own lines and moves left.  Value, both policies, the beam, the symmetry test and the
+learner (traces and symmetry; NOT temporal coherence) take a staged table by its entry count; a map that uses two or four stages
+leaves the other blocks untouched.  ntuple_staged(trained_table, map) starts every stage from a trained plain table.
 """
 from __future__ import annotations
 
@@ -52,12 +68,13 @@ from typing import Optional
 import torch
 
 from . import _learn_lib
-from ._learn_lib import (BEAM_MAX_WIDTH, NTUPLE_BEAM_MAX_DEPTH, NTUPLE_ENTRIES, NTUPLE_ENTRIES_SUM, NTUPLE_SHAPE_IDS, NTUPLE_SHAPES,
-                         NTUPLE_SUMS, NTUPLE_TRACE_MAX, check)
+from ._learn_lib import (BEAM_MAX_WIDTH, NTUPLE_BEAM_MAX_DEPTH, NTUPLE_COUNTERS, NTUPLE_ENTRIES, NTUPLE_ENTRIES_SUM, NTUPLE_FORM_IDS,
+                         NTUPLE_SHAPE_IDS, NTUPLE_SHAPES, NTUPLE_STAGES, NTUPLE_SUMS, NTUPLE_TRACE_MAX, check)
 from .lookahead import _MAX_BOARDS, _boards, _ptr, _state_ptrs
 
 __all__ = ["NTUPLE_ENTRIES", "NTUPLE_ENTRIES_SUM", "NTUPLE_SHAPES", "NTUPLE_SUMS", "ntuple_shape", "ntuple_parts", "ntuple_table", "ntuple_value", "ntuple_is_symmetric", "ntuple_coherence", "ntuple_step_sizes",
-           "NTuplePolicy", "NTupleBeamPolicy", "NTupleLearner"]
+           "NTuplePolicy", "NTupleBeamPolicy", "NTupleLearner", "NTUPLE_STAGES", "ntuple_stage_map", "ntuple_staged", "ntuple_stages",
+           "ntuple_map", "ntuple_is_staged"]
 
 _STATE_WON = 1                                                 # bits 28..29 of B.y: 0 running, 1 won, 2 and 3 lost
 _FINISHED_B_Y = _STATE_WON << 28                               # B.y of a state that is finished and otherwise empty
@@ -74,10 +91,73 @@ def _entries(shape) -> int:
     return _learn_lib.ntuple_entries_of(shape)
 
 
-def ntuple_table(device="cuda:0", shape: str = "2x4") -> torch.Tensor:
+def _staged_counts() -> dict:
+    """Entry count -> the form's name, for the staged table of every shape and every sum."""
+    return _learn_lib._ntuple_staged_counts()
+
+
+def ntuple_table(device="cuda:0", shape: str = "2x4", staged: bool = False) -> torch.Tensor:
     """A zeroed n-tuple table of `shape` on `device`: int32 [NTUPLE_SHAPES[shape] entries] (2x4: NTUPLE_ENTRIES); "2x4+3x3": a sum
-    table, int32 [NTUPLE_ENTRIES_SUM] -- ntuple_parts gives its two tables."""
-    return torch.zeros(_entries(shape), dtype=torch.int32, device=device)
+    table, int32 [NTUPLE_ENTRIES_SUM] -- ntuple_parts gives its two tables.  staged=True: a staged table of that form, int32
+    [NTUPLE_STAGES * entries + 1,024] -- ntuple_stages gives its eight tables, ntuple_map its map; the all-zero map sends every
+    state to stage 0."""
+    if not isinstance(staged, bool):
+        raise ValueError(f"staged must be True or False, got {staged!r}")
+    entries = _entries(shape)
+    return torch.zeros(NTUPLE_STAGES * entries + NTUPLE_COUNTERS if staged else entries, dtype=torch.int32, device=device)
+
+
+def ntuple_is_staged(table) -> bool:
+    """Whether `table` is a staged table, by its entry count (a tensor of no known count is refused, as ntuple_shape refuses it)."""
+    ntuple_shape(table)
+    return table.shape[0] in _staged_counts()
+
+
+def _staged(table) -> torch.Tensor:
+    if not (isinstance(table, torch.Tensor) and table.dim() == 1 and table.dtype == torch.int32 and table.shape[0] in _staged_counts()):
+        sizes = ", ".join(f"{k} ({v})" for k, v in _staged_counts().items())
+        raise ValueError(f"table must be a staged table: an int32 tensor of {sizes} entries (ntuple_table(staged=True), ntuple_staged)")
+    return table
+
+
+def ntuple_stages(table) -> tuple:
+    """The NTUPLE_STAGES per-stage views of a staged table, stage 0 first.  Views, not copies: each is a valid, 16-byte aligned plain
+    table of the form for everything that takes one, and what is written through it is written to the whole."""
+    entries = _entries(_staged_counts()[_staged(table).shape[0]])
+    return tuple(table[g * entries:(g + 1) * entries] for g in range(NTUPLE_STAGES))
+
+
+def ntuple_map(table) -> torch.Tensor:
+    """The stage map of a staged table: the view of its last 1,024 entries, one per counter index k; the stage of k is map[k] & 7."""
+    return _staged(table)[-NTUPLE_COUNTERS:]
+
+
+def ntuple_stage_map(L: int, M: int, lines: int = 1, moves: int = 4) -> torch.Tensor:
+    """int32 [1,024] on the host: a stage map that cuts (lines left, moves left) of an L / M game into lines x moves <= 8 buckets of
+    equal width -- entry 64 l + m holds bl * moves + bm, bm = m * moves // (min(M, 63) + 1) and bl = l * lines // (min(L, 15) + 1) on
+    the counters as the counter index clamps them.  Any other map is one the user writes: 1,024 integers, of which bits 0..2 count."""
+    return torch.from_numpy(_learn_lib.ntuple_stage_map(L, M, lines, moves))
+
+
+def _stage_map(stage_map, device) -> torch.Tensor:
+    if (not isinstance(stage_map, torch.Tensor) or stage_map.dtype != torch.int32 or tuple(stage_map.shape) != (NTUPLE_COUNTERS,)):
+        raise ValueError(f"stage_map must be an int32 tensor of {NTUPLE_COUNTERS} entries (ntuple_stage_map)")
+    return stage_map.to(device)
+
+
+@torch.no_grad()
+def ntuple_staged(table: torch.Tensor, stage_map: torch.Tensor) -> torch.Tensor:
+    """Weight promotion: a new staged table on `table`'s device whose eight blocks are each a copy of the PLAIN table `table` (of any
+    form), with `stage_map` (int32 [1,024]) as its map.  It values, and plays, exactly as `table` does, whatever the map holds, until
+    it is trained."""
+    if not isinstance(table, torch.Tensor) or ntuple_is_staged(table):
+        raise ValueError("ntuple_staged promotes a plain table (ntuple_stages gives the plain tables of a staged one)")
+    _table(table, table.device)
+    out = ntuple_table(table.device, ntuple_shape(table), staged=True)
+    for block in ntuple_stages(out):
+        block.copy_(table)
+    ntuple_map(out).copy_(_stage_map(stage_map, table.device))
+    return out
 
 
 def ntuple_coherence(device="cuda:0", shape: str = "2x4") -> torch.Tensor:
@@ -91,6 +171,8 @@ def ntuple_shape(table) -> str:
     tensor of any other size is refused."""
     if isinstance(table, torch.Tensor) and table.dim() >= 1 and table.shape[0] in _counts():
         return _counts()[table.shape[0]]
+    if isinstance(table, torch.Tensor) and table.dim() == 1 and table.shape[0] in _staged_counts():
+        return _staged_counts()[table.shape[0]]                # a staged table: the form of its blocks
     sizes = ", ".join(f"{k} ({v})" for k, v in _counts().items())
     raise ValueError(f"table must be a tensor of {sizes} entries (ntuple_table)")
 
@@ -98,7 +180,10 @@ def ntuple_shape(table) -> str:
 def ntuple_parts(table) -> tuple:
     """The per-shape views of a table or a coherence buffer, in the order they lie in it: (table,) for a plain one, (the 2x4 part,
     the 3x3 part) for a sum.  Views, not copies: each is a valid, 16-byte aligned table (buffer) of its shape for everything that
-    takes one, and what is written through it is written to the whole."""
+    takes one, and what is written through it is written to the whole.  A staged table is refused: ntuple_stages gives its eight
+    tables, each of which has parts."""
+    if isinstance(table, torch.Tensor) and table.dim() == 1 and table.shape[0] in _staged_counts():
+        raise ValueError("a staged table has no parts of its own: ntuple_stages(table) gives its eight tables, ntuple_parts of one its parts")
     parts, at = [], 0
     for part in _learn_lib.ntuple_parts_of(ntuple_shape(table)):
         parts.append(table[at:at + NTUPLE_SHAPES[part][2]])
@@ -138,15 +223,18 @@ def _coherence(coherence, table=None) -> torch.Tensor:
 
 def _table(table, device) -> torch.Tensor:
     if (not isinstance(table, torch.Tensor) or table.dtype != torch.int32 or table.dim() != 1
-            or table.shape[0] not in _counts() or table.device != device
+            or (table.shape[0] not in _counts() and table.shape[0] not in _staged_counts()) or table.device != device
             or not table.is_contiguous()):
-        raise ValueError(f"table must be a contiguous int32 tensor of {_sizes()} entries on {device} (ntuple_table)")
+        raise ValueError(f"table must be a contiguous int32 tensor of {_sizes()} entries, or a staged table, on {device} (ntuple_table)")
     return table
 
 
-def _shaped(lib, entry: str, shape: str):
+def _shaped(lib, entry: str, shape: str, staged: bool = False):
     """How the library reads a table of `shape` through `entry` ("tpl_ntuple_value", ...): (function, trailing arguments before
-    `stream`) -- the _shaped twin with the C shape id, or for a sum of shapes the _sum twin, which takes none."""
+    `stream`) -- the _shaped twin with the C shape id, or for a sum of shapes the _sum twin, which takes none; for a staged table of
+    any form the _staged twin with the C form id."""
+    if staged:
+        return getattr(lib, entry + "_staged"), (NTUPLE_FORM_IDS[shape],)
     if shape in NTUPLE_SUMS:
         return getattr(lib, entry + "_sum"), ()
     return getattr(lib, entry + "_shaped"), (NTUPLE_SHAPE_IDS[shape],)
@@ -206,7 +294,7 @@ def _planes(pair, device, what: str):
 
 def _value(planes_a, planes_b, k: int, L: int, M: int, table, out, device) -> None:
     stream = torch._C._cuda_getCurrentRawStream(device.index)
-    entry, shape = _shaped(_learn_lib.lib(), "tpl_ntuple_value", ntuple_shape(table))
+    entry, shape = _shaped(_learn_lib.lib(), "tpl_ntuple_value", ntuple_shape(table), ntuple_is_staged(table))
     check(entry(_ptr(planes_a), _ptr(planes_b), k, L, M, table.data_ptr(), out.data_ptr(), *shape, stream))
 
 
@@ -246,7 +334,7 @@ _sigma = {}                                                    # the mirror perm
 def ntuple_is_symmetric(table: torch.Tensor) -> bool:
     """Whether `table` is mirror-symmetric: table[sigma(j)] == table[j] for every j, sigma = _learn_lib.ntuple_mirror_permutation()
     (include/tpl_learn.h states the invariant; of a sum table: of every part).  Under such a table a board and its reflection have
-    the same value, bit for bit.
+    the same value, bit for bit.  A staged table: whether every one of its eight blocks is.
     One gather and one comparison on the table's device; the answer is a host bool, so this syncs."""
     if not isinstance(table, torch.Tensor):
         raise ValueError(f"table must be a contiguous int32 tensor of {_sizes()} entries (ntuple_table)")
@@ -254,7 +342,8 @@ def ntuple_is_symmetric(table: torch.Tensor) -> bool:
     key = (table.device, ntuple_shape(table))
     if key not in _sigma:
         _sigma[key] = torch.from_numpy(_learn_lib.ntuple_mirror_permutation(key[1])).to(table.device)
-    return bool(torch.equal(table[_sigma[key]], table))
+    blocks = ntuple_stages(table) if ntuple_is_staged(table) else (table,)
+    return all(bool(torch.equal(block[_sigma[key]], block)) for block in blocks)
 
 
 class NTuplePolicy:
@@ -273,6 +362,7 @@ class NTuplePolicy:
         self.env, self.table, self.depth = env, _table(table, env.device), _depth(depth)
         self.gamma, self.epsilon, self.seed = _finite("gamma", gamma), _unit("epsilon", epsilon), _count("seed", seed)
         self.shape = ntuple_shape(self.table)                  # "2x4", "3x3" or "2x4+3x3": the table's, which picks the kernels
+        self.staged = ntuple_is_staged(self.table)             # with the shape: the _staged entries
         self.step = 0                                          # the `step` of the next act() that is not given one
         self._planes = None
 
@@ -313,7 +403,7 @@ class NTuplePolicy:
         lib = _learn_lib.lib()
         head = (self._planes[0], self._planes[1], env.num_envs, env.L, env.M, *env.reward_params, self.gamma, self.table.data_ptr(),
                 self.epsilon, self.seed % (1 << 64), step % (1 << 64), out.data_ptr())
-        entry, shape = _shaped(lib, "tpl_ntuple_search" if self.depth == 2 else "tpl_ntuple_act", self.shape)
+        entry, shape = _shaped(lib, "tpl_ntuple_search" if self.depth == 2 else "tpl_ntuple_act", self.shape, self.staged)
         tail = (_ptr(score), _ptr(after_a), _ptr(after_b), _ptr(value), *shape, stream)
         check(entry(*head, _ptr(second), *tail) if self.depth == 2 else entry(*head, *tail))
         return out
@@ -334,7 +424,7 @@ class NTupleBeamPolicy:
         self.env, self.table = env, _table(table, env.device)
         self.depth, self.width = _beam_shape(depth, width)
         self.gamma = _finite("gamma", gamma)
-        self.shape = ntuple_shape(self.table)
+        self.shape, self.staged = ntuple_shape(self.table), ntuple_is_staged(self.table)
         self._planes = None
 
     @torch.no_grad()
@@ -362,7 +452,10 @@ class NTupleBeamPolicy:
             self._planes = _state_ptrs(env)                   # the resident planes live as long as the environment
         stream = torch._C._cuda_getCurrentRawStream(env.device.index)
         lib = _learn_lib.lib()
-        entry, shape = (lib.tpl_ntuple_beam_sum, ()) if self.shape in NTUPLE_SUMS else (lib.tpl_ntuple_beam, (NTUPLE_SHAPE_IDS[self.shape],))
+        if self.staged:
+            entry, shape = lib.tpl_ntuple_beam_staged, (NTUPLE_FORM_IDS[self.shape],)
+        else:
+            entry, shape = (lib.tpl_ntuple_beam_sum, ()) if self.shape in NTUPLE_SUMS else (lib.tpl_ntuple_beam, (NTUPLE_SHAPE_IDS[self.shape],))
         check(entry(self._planes[0], self._planes[1], env.num_envs, env.L, env.M, *env.reward_params, self.gamma,
                     self.table.data_ptr(), self.depth, self.width, out.data_ptr(), _ptr(plan), _ptr(score), _ptr(after_a),
                     _ptr(after_b), *shape, stream))
@@ -412,10 +505,19 @@ class NTupleLearner:
     sync, nothing allocated, and the same bytes in whatever order the adds arrive.  With symmetric=True each part is updated under
     its own sigma; with coherent=True each part's entries keep their own step sizes.  A state now adds to about 222 entries (both
     parts' non-empty windows and two counters) where it added to 107 to 115, so the step of V per unit of `rate` roughly DOUBLES,
-    as it does under symmetry: `rate` wants to be about half of what a single shape takes."""
+    as it does under symmetry: `rate` wants to be about half of what a single shape takes.
+
+    stage_map (None by default, which leaves everything above as it was; an int32 tensor of 1,024 entries: ntuple_stage_map): the
+    learner owns a STAGED table of `shape` with that map.  Steps 1 and 2 read it through the _staged entries, a state in the block of
+    its own lines and moves left; step 3 is tpl_ntuple_update_trace_staged, which adds in that block -- with traces and with symmetry
+    as above, in one call for every form.  A stage sees only the states that fall in it, so each block learns from a share of the
+    boards.  Temporal coherence has no staged form: coherent=True with a map is refused.
+    start (None, or a plain table of `shape`): the table starts as a copy of it -- with a stage_map every stage does, which is
+    weight promotion from a trained plain table."""
 
     def __init__(self, env, gamma: float = 0.99, rate: float = 8.0, epsilon: float = 0.1, seed: int = 0, depth: int = 1,
-                 lam: float = 0.0, horizon: int = 1, symmetric: bool = False, coherent: bool = False, shape: str = "2x4"):
+                 lam: float = 0.0, horizon: int = 1, symmetric: bool = False, coherent: bool = False, shape: str = "2x4",
+                 stage_map: Optional[torch.Tensor] = None, start: Optional[torch.Tensor] = None):
         n = _boards(env, "NTupleLearner")
         if not env.auto_reset:
             raise ValueError("NTupleLearner needs an auto-reset environment")
@@ -437,7 +539,19 @@ class NTupleLearner:
             raise ValueError(f"(horizon + 1) * boards must stay at or below {_MAX_BOARDS}")
         d = env.device
         self.depth = _depth(depth)
-        self.table = ntuple_table(d, shape)
+        if stage_map is not None and coherent:
+            raise ValueError("temporal coherence has no staged form (include/tpl_learn.h): coherent=True cannot go with a stage_map")
+        if start is not None and (not isinstance(start, torch.Tensor) or start.dim() != 1 or start.dtype != torch.int32
+                                  or start.shape[0] != _entries(shape)):
+            raise ValueError(f"start must be a plain int32 table of the learner's shape, {shape} ({_entries(shape)} entries)")
+        if stage_map is not None:
+            _stage_map(stage_map, d)
+        self.table = ntuple_table(d, shape, staged=stage_map is not None)
+        for block in (ntuple_stages(self.table) if stage_map is not None else (self.table,)):
+            if start is not None:
+                block.copy_(start)
+        if stage_map is not None:
+            ntuple_map(self.table).copy_(_stage_map(stage_map, d))
         self.coherence = ntuple_coherence(d, shape) if coherent else None
         self.policy = NTuplePolicy(env, self.table, gamma, epsilon, seed, self.depth)
         self.greedy = NTuplePolicy(env, self.table, gamma, 0.0, seed, self.depth)
@@ -480,14 +594,22 @@ class NTupleLearner:
         if self.coherent:
             _coherence(self.coherence, _table(self.table, env.device))   # a buffer of the other shape would be overrun
         # the update, part by part: (C shape id, the part's table pointer, its coherence pointer) -- one part unless the table is a sum
-        names = _learn_lib.ntuple_parts_of(ntuple_shape(self.table))
+        staged = ntuple_is_staged(_table(self.table, env.device))
+        if staged and self.coherent:
+            raise ValueError("temporal coherence has no staged form (include/tpl_learn.h)")
+        form = NTUPLE_FORM_IDS[ntuple_shape(self.table)]
+        names = () if staged else _learn_lib.ntuple_parts_of(ntuple_shape(self.table))
         parts = list(zip((NTUPLE_SHAPE_IDS[name] for name in names), (t.data_ptr() for t in ntuple_parts(self.table)),
-                         (c.data_ptr() for c in ntuple_parts(self.coherence)) if self.coherent else (None,) * len(names)))
+                         (c.data_ptr() for c in ntuple_parts(self.coherence)) if self.coherent else (None,) * len(names))) if names else []
         for _ in range(steps):
             kept = self._kept
             self.policy.act(out=self._action, score=self._score, after=self._next, step=self.steps)
             _value(kept[0], kept[1], n, env.L, env.M, self.table, self._kept_value, env.device)
             torch.sub(self._score, self._kept_value, out=self._error)
+            if staged:                                         # one call: the entry launches the part updates itself
+                check(lib.tpl_ntuple_update_trace_staged(ring_a, ring_b, n, self.slots, self._head, self.horizon, env.L, env.M,
+                                                         self.table.data_ptr(), self._error.data_ptr(), self.rate, self.decay,
+                                                         int(self.symmetric), form, stream))
             for shape, table, coherence in parts:
                 ring = (ring_a, ring_b, n, self.slots, self._head, self.horizon, env.L, env.M, table)
                 tail = (self._error.data_ptr(), self.rate, self.decay, int(self.symmetric), shape, stream)

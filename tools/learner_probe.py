@@ -97,6 +97,14 @@ Parts:
               entries in use per running board
     ntuple_sum_sweep  part ntuple_shape_sweep's set-up unchanged: the 2 x 4 and 3 x 3 TD(0) runs at rate 16 again (they must reproduce
               win for win), then a sum table as TD(0) at rates 2, 4, 8 and 16; the best one is also played at depth 2 and at beam (3, 8)
+    ntuple_stage   staged tables (eight tables of a form and a stage map) beside their plain twins: at 2^20 boards (L=10 / M=40,
+              part ntuple_shape's, played on for 200 steps so that they stand in several stages) the value, act, search, the beam at (3, 8) and one learner step for each of the three
+              forms -- the plain table, a staged one whose all-zero map keeps one stage live, and one under the four-stage moves=4 map,
+              eight distinct random blocks each -- in the same alternated rounds, each staged time as a ratio to its plain twin's
+    ntuple_stage_sweep  part ntuple_shape_sweep's set-up unchanged: the 3 x 3 TD(0) run at rate 16 again (it must reproduce win for
+              win), then a staged 3 x 3 table under the maps moves=2, moves=4 and lines=2 x moves=4, each trained from zero and each
+              promoted from the baseline's table and trained on for the same budget; every final table played at one ply, at depth 2
+              and at beam (3, 8)
     ntuple_shape_ab  --parent LIB: the nine 2 x 4 n-tuple kernels of another build of the learner library against this tree's, both
               loaded into one process: the outputs of the six entries compared byte for byte on the ring of part ntuple_shape
               at 2^18 boards, then each entry timed in five rounds of the parent against itself and five of the parent against
@@ -117,7 +125,7 @@ PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600, "priority": 600
          "heuristic": 600, "search": 900, "beam": 900, "ntuple": 900,
          "ntuple_search": 900, "ntuple_trace": 600, "ntuple_trace_sweep": 1100, "ntuple_coherent": 600,
          "ntuple_coherent_sweep": 1700, "ntuple_shape": 600, "ntuple_shape_sweep": 1100, "ntuple_beam": 1100,
-         "ntuple_sum": 600, "ntuple_sum_sweep": 600}
+         "ntuple_sum": 600, "ntuple_sum_sweep": 600, "ntuple_stage": 600, "ntuple_stage_sweep": 900}
 SCATTERED_ATOMICS = 0.08e12                                 # 64 lanes of a wave adding into 64 rows (float adds; integer adds unmeasured)
 VALU_CYCLES, SIMDS, CLOCK_HZ = 3.3, 1024, 2.4e9           # the move's instruction mix, 256 CUs x 4, the clock
 
@@ -1813,6 +1821,133 @@ def part_ntuple_sum_sweep(eval_steps=12288):
     return dict(part="ntuple_sum_sweep", boards=4096, seed=11, pool=1 << 16, pool_seed=7, reward=list(NTUPLE_LARGE_REWARD), gamma=1.0,
                 epsilon=0.05, eval_steps=eval_steps, baselines=baselines, baselines_reproduced_win_for_win=reproduced, best=runs[at],
                 best_played=deep, runs=runs)
+
+
+def part_ntuple_stage(rounds=5, reps=10, n=1 << 20):
+    """Staged tables beside their plain twins on part ntuple_shape's boards: one stage live, and four."""
+    import numpy as np
+    import torch
+    import tetris_piclim as T
+    m = T._learn_lib
+    names = ("2x4", "3x3", NTUPLE_SUM)
+    kinds = ("plain", "one_stage", "four_stages")
+    env, ring = _shape_ring(T, n, 2)                           # the environment stands at the ring's newest slot
+    del ring
+    for t in range(8, 208):                                    # boards in lockstep share one stage: play on until episodes have ended
+        env.step(env.synthetic_actions(t), observe=False)     # at different moves and the boards stand all over the game
+    four = T.ntuple_stage_map(10, 40, moves=4)
+
+    def stages():
+        """How many of the first 4,096 boards stand in each stage of the four-stage map, as the form's timings begin."""
+        k = m.ntuple_counter_index(10, 40, *(x.astype(np.int64) for x in _lines_and_moves(*env.raw_planes())))
+        return {int(g): int(c) for g, c in zip(*np.unique(four.numpy()[k], return_counts=True))}
+    out = dict(part="ntuple_stage", boards=n, gamma=1.0, epsilon=0.05, learner_rate=1.0, rounds=rounds, launches_per_timing=reps,
+               search_launches_per_timing=max(reps // 3, 2), beam_launches_per_timing=3)
+    action, second = (torch.empty(n, dtype=torch.uint8, device="cuda:0") for _ in range(2))
+    score, value = (torch.empty(n, dtype=torch.float32, device="cuda:0") for _ in range(2))
+    after = tuple(torch.empty((n, 4), dtype=torch.int32, device="cuda:0") for _ in range(2))
+    rows = []
+    for name in names:
+        entries = m.ntuple_entries_of(name)
+        spread = stages()
+        body = np.random.default_rng(0).integers(-(1 << 20), (1 << 20) + 1, 8 * entries).astype(np.int32)
+        table = {"plain": torch.from_numpy(body[:entries].copy()).to("cuda:0")}
+        for kind, stage_map in (("one_stage", torch.zeros(1024, dtype=torch.int32)), ("four_stages", four)):
+            table[kind] = torch.from_numpy(np.concatenate([body, stage_map.numpy()])).to("cuda:0")      # eight distinct blocks
+        variants = {}
+        for kind in kinds:
+            act = T.NTuplePolicy(env, table[kind], gamma=1.0, epsilon=0.05, seed=11)
+            search = T.NTuplePolicy(env, table[kind], gamma=1.0, epsilon=0.05, seed=11, depth=2)
+            beam = T.NTupleBeamPolicy(env, table[kind], 3, 8, gamma=1.0)
+            variants[("value", kind)] = (lambda t=table[kind]: T.ntuple_value(env, t, out=value), reps)
+            variants[("act", kind)] = (lambda p=act: p.act(out=action, score=score, after=after, value=value, step=3), reps)
+            variants[("search", kind)] = (lambda p=search: p.act(out=action, score=score, after=after, value=value, step=3,
+                                                                 second=second), max(reps // 3, 2))
+            variants[("beam_3x8", kind)] = (lambda p=beam: p.act(out=action), 3)
+        order = sorted(variants)                                 # an entry's three tables next to each other in every round
+        times = {key: [] for key in order}
+        for _ in range(rounds):                                  # alternate the variants round by round
+            for key in order:
+                fn, count = variants[key]
+                times[key].append(_timed(fn, count, warmup=1))
+        # one learner step -- act, value, subtract, update, environment step; the learners step the environment, so they come last
+        learners = {kind: T.NTupleLearner(env, gamma=1.0, rate=1.0, epsilon=0.05, seed=11, shape=name,
+                                          stage_map=None if kind == "plain" else T.ntuple_map(table[kind]).cpu()) for kind in kinds}
+        for kind in kinds:
+            learners[kind].table.copy_(table[kind])              # the random blocks: gathers all over them, as in the kernels above
+            learners[kind].train(3)
+            times[("learner_step", kind)] = []
+        for _ in range(rounds):
+            for kind in kinds:
+                times[("learner_step", kind)].append(_timed(lambda l=learners[kind]: l.train(1), reps, warmup=1))
+        del learners
+        med = {key: sorted(ts)[rounds // 2] for key, ts in times.items()}
+        row = dict(form=name, stages_of_the_first_4096_boards=spread, table_bytes={kind: int(table[kind].numel() * 4) for kind in kinds},
+                   bytes_in_use=dict(plain=4 * entries, one_stage=4 * entries + 4096, four_stages=16 * entries + 4096))
+        for what in sorted({key[0] for key in times}):
+            row[what] = {kind + "_us": _spread(times[(what, kind)]) for kind in kinds}
+            for kind in kinds[1:]:
+                row[what][kind + "_over_plain"] = round(med[(what, kind)] / med[(what, "plain")], 3)
+        rows.append(row)
+        print(json.dumps(row), file=sys.stderr, flush=True)
+        del table, variants
+        torch.cuda.empty_cache()
+    env.terminate()
+    out["rows"] = rows
+    return out
+
+
+def _lines_and_moves(pa, pb):
+    """(lines, moves) of packed states, through the tests' decoder."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import learn_ref as R
+    f = R.decode_state(pa[:4096].cpu().numpy().view(np.uint32), pb[:4096].cpu().numpy().view(np.uint32))
+    return f["lines"], f["moves"]
+
+
+def part_ntuple_stage_sweep(eval_steps=12288):
+    """Part ntuple_shape_sweep's set-up unchanged; its 3 x 3 TD(0) run at rate 16 again, then staged 3 x 3 tables under three maps, each
+    from zero and each promoted from that run's table."""
+    import torch
+    import tetris_piclim as T
+    gen_env = T.BatchedTetris(10, 40, 64, device="cuda:0", seed=7)
+    big = gen_env.carved_configs(1 << 16, seed=7)
+    gen_env.terminate()
+
+    def result(r):
+        p = r["win_rate"]
+        return dict(episodes=r["episodes"], wins=r["wins"], win_rate=round(p, 5),
+                    standard_error=round((p * (1 - p) / max(r["episodes"], 1)) ** 0.5, 6))
+
+    def learn(label, **kw):
+        env = T.BatchedTetris(10, 40, 4096, device="cuda:0", seed=11, auto_reset=True, reward=NTUPLE_LARGE_REWARD, config_pool=big)
+        learner = T.NTupleLearner(env, seed=11, gamma=1.0, epsilon=0.05, shape="3x3", rate=16.0, **kw)
+        got = dict(run=label, before_training=result(learner.evaluate(eval_steps)), trained=[])
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for steps in (10000, 30000):
+            learner.train(steps)
+            got["trained"].append(dict(steps=learner.steps, **result(learner.evaluate(eval_steps))))
+        blocks = T.ntuple_stages(learner.table) if T.ntuple_is_staged(learner.table) else (learner.table,)
+        got.update(seconds=round(time.perf_counter() - t0, 2), entries_in_use=[int((b != 0).sum()) for b in blocks],
+                   depth_2=result(learner.evaluate(eval_steps, depth=2)), beam_3x8=result(learner.evaluate(eval_steps, depth=3, width=8)))
+        table = learner.table.clone()
+        env.terminate()
+        print(json.dumps(got), file=sys.stderr, flush=True)      # progress: a long part must not stay silent
+        return got, table
+    baseline, trained = learn("3x3 plain")
+    expected = (1467276, 1469796)                                 # profiles/learner/sweep_ntuple_shape.log
+    reproduced = (baseline["trained"][-1]["wins"], baseline["trained"][-1]["episodes"]) == expected
+    carried, _ = learn("3x3 plain, trained on from the baseline", start=trained)   # the control of the promoted runs: the same second budget
+    runs = []
+    for label, grid in (("moves=2", dict(moves=2)), ("moves=4", dict(moves=4)), ("lines=2 x moves=4", dict(lines=2, moves=4))):
+        stage_map = T.ntuple_stage_map(10, 40, **grid)
+        runs.append(learn("staged " + label + ", from zero", stage_map=stage_map)[0])
+        runs.append(learn("staged " + label + ", promoted from the baseline", stage_map=stage_map, start=trained)[0])
+    return dict(part="ntuple_stage_sweep", boards=4096, seed=11, pool=1 << 16, pool_seed=7, reward=list(NTUPLE_LARGE_REWARD), gamma=1.0,
+                epsilon=0.05, rate=16.0, eval_steps=eval_steps, baseline=baseline, baseline_reproduced_win_for_win=reproduced,
+                baseline_trained_on=carried, hand_made_features_win_rate=0.99925, runs=runs)
 
 
 def part_ntuple_shape_ab(parent, rounds=5, reps=20, n=1 << 18):
