@@ -695,6 +695,68 @@ int tpl_ntuple_update_trace_staged(const void* ring_a, const void* ring_b, int64
                                    int32_t L, int32_t M, int32_t* table, const float* error, float rate, float decay,
                                    int32_t symmetric, int32_t form, void* stream);
 
+/* Feature tuples: n-tuple tables indexed by nine board features.  Every window above is local -- 2 x 4 or 3 x 3 cells --, and the
+ * quantities that carry the hand-made score of tpl_placement_act are global counts: no sum of local windows can express a threshold
+ * on them.  A feature tuple is a 256-entry row per (falling piece, feature), looked up at the feature's value: the
+ * piecewise-constant generalisation of that linear score, learned by the TD rule above.
+ *
+ * Features: phi_3 .. phi_11 of the board as stated for tpl_placement_features -- holes, aggregate_height, max_height, bumpiness,
+ *   row_transitions, column_transitions, wells, rows_with_holes, hole_depth --, numbered j = 0 .. 8 in that order.
+ * Bin:     q_j = min(phi_{3+j}, 255).  Only wells can pass 255 (950 on a comb board); THE CLAMP IS PART OF THE RULE.
+ * FEATURE TABLE: int32 [TPL_NTUPLE_ENTRIES_FEAT = 19,456] (77,824 bytes), 16-byte aligned, in units of 2^-16:
+ *   feature[p][j][q]  at index (p * 9 + j) * 256 + q    p in 0..7 the falling piece, j in 0..8, q in 0..255: 18,432 entries
+ *   counter[k]        at index 18,432 + k               k the counter index above
+ * All nine feature entries and the counter are ALWAYS used.  There is no "empty pattern" exception: a board with 0 holes reads bin 0.
+ * Value:   V(s) = float32(S) * 2^-16 for a running s, S the exact 64-bit sum of its ten entries, rounded once; 0 otherwise.
+ * The sum form (TPL_NTUPLE_FEATURE_FORM_3X3): int32 [TPL_NTUPLE_ENTRIES_3X3_FEAT = 610,304], a whole 3 x 3 table at entry 0 and behind
+ *   it, at entry 590,848 (byte 2,363,392, a multiple of 16), a whole feature table, each with its own counters.
+ *   V(s) = float32(S_3x3 + S_feat) * 2^-16: the two integers are added BEFORE the one rounding, as in "Two shapes summed".  With one
+ *   part all zero every output is, bit for bit, what the other part gives alone.
+ * Mirror image: all nine features are invariant under the left-right reflection of the board, so sigma moves only the piece through
+ *   pi (L <-> J, S <-> Z) and keeps j and q: sigma(feature[p][j][q]) = feature[pi(p)][j][q], the counters stay.
+ * Update (tpl_ntuple_update_trace_feature): tpl_ntuple_update_trace's rule -- d_k, the trace cut, the decay -- with d_k added to the
+ *   nine feature entries and the counter entry of every state that takes part.  With symmetric != 0 every feature add is made a
+ *   second time at (pi(p), j, q), also where the two entries are one (the pieces I, T, O and 7); the counter is added once.  It adds
+ *   to a feature table only: the 3 x 3 part of a sum form goes through tpl_ntuple_update_trace_shaped with the same errors, the
+ *   feature part, at entry 590,848, through this entry.  Nothing is read, every add is an integer add modulo 2^32: the bytes are
+ *   the same whatever order the adds arrive in.  A state adds to 10 entries where it adds to about 107 of a 3 x 3 table.
+ * There are no staged and no coherent feature tables: each would be eight more kernels, and neither raised a win rate in the record.
+ *
+ * tpl_ntuple_value_feature, _act_feature, _search_feature and _beam_feature take the arguments of tpl_ntuple_value_shaped, _act_shaped,
+ * _search_shaped and tpl_ntuple_beam with `form` (tpl_ntuple_feature_form) where those take `shape`, and keep their checks, in their
+ * order, under their own names, their outputs, their exploration draw and their ties; refused before anything else, and before any
+ * pointer is looked at: a form that is neither of the two.  tpl_ntuple_update_trace_feature takes tpl_ntuple_update_trace_shaped's
+ * arguments without `shape`.  tpl_ntuple_feature_bins writes the nine bins of every state, running or not, as uint8 [n][9]: the device
+ * feature code without the gathers, for tests and inspection -- NOT a hot-path entry (a lane's nine byte stores are not coalesced); it
+ * takes no L and M and refuses what the planes and n of the other entries are refused for.  Kernels: the device bodies of the twins under the geometries FeatureTable and SumOf<Shape3x3,
+ * FeatureTable> (csrc/learn/tpl_ntuple.h), whose board sum is board_features on the column words the lane holds, nine gathers and
+ * the counter -- ntuple_feature_{value,act,search}_kernel, ntuple_feature3_* (ntuple.hip), ntuple_feature_beam_kernel and
+ * ntuple_feature3_beam_kernel (ntuple_beam.hip); the update is ntuple_feature_trace_kernel<symmetric>, whose blocks sum
+ * their states' adds in an LDS image of the whole table (76 KB) and flush the non-zero sums with one atomic add each. */
+#define TPL_NTUPLE_FEATURES 9
+#define TPL_NTUPLE_FEATURE_BINS 256
+#define TPL_NTUPLE_ENTRIES_FEAT 19456
+#define TPL_NTUPLE_ENTRIES_3X3_FEAT 610304
+#define TPL_NTUPLE_FEATURE_FORM_ALONE 0
+#define TPL_NTUPLE_FEATURE_FORM_3X3 1
+typedef enum { TPL_NTUPLE_FEATURE_ALONE = TPL_NTUPLE_FEATURE_FORM_ALONE, TPL_NTUPLE_FEATURE_WITH_3X3 = TPL_NTUPLE_FEATURE_FORM_3X3 } tpl_ntuple_feature_form;
+int tpl_ntuple_value_feature(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const int32_t* table,
+                             float* value, int32_t form, void* stream);
+int tpl_ntuple_act_feature(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line, float r_win,
+                           float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed, uint64_t step,
+                           uint8_t* action, float* score, void* after_a, void* after_b, float* value, int32_t form, void* stream);
+int tpl_ntuple_search_feature(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line, float r_win,
+                              float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed, uint64_t step,
+                              uint8_t* action, uint8_t* second, float* score, void* after_a, void* after_b, float* value,
+                              int32_t form, void* stream);
+int tpl_ntuple_beam_feature(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line, float r_win,
+                            float r_lose, float gamma, const int32_t* table, int32_t depth, int32_t width, uint8_t* action,
+                            uint8_t* plan, float* score, void* after_a, void* after_b, int32_t form, void* stream);
+int tpl_ntuple_update_trace_feature(const void* ring_a, const void* ring_b, int64_t n, int32_t slots, int32_t head, int32_t horizon,
+                                    int32_t L, int32_t M, int32_t* table, const float* error, float rate, float decay,
+                                    int32_t symmetric, void* stream);
+int tpl_ntuple_feature_bins(const void* plane_a, const void* plane_b, int64_t n, uint8_t* bins, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

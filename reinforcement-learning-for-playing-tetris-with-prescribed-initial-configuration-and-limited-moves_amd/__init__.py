@@ -15,7 +15,8 @@ __all__ = ["BatchedTetris", "Tetris", "Snapshot", "OBS_DIM", "NUM_ACTIONS", "RUN
            "ReplayRing", "PrioritizedReplayRing", "LookaheadPolicy", "afterstates", "HeuristicPolicy", "placement_features",
            "evaluate_heuristic", "tune_heuristic", "BeamPolicy", "NTuplePolicy", "NTupleBeamPolicy", "NTupleLearner", "ntuple_table", "ntuple_value",
            "ntuple_is_symmetric", "ntuple_coherence", "ntuple_step_sizes", "ntuple_shape", "NTUPLE_SHAPES", "ntuple_parts", "NTUPLE_SUMS", "NTUPLE_ENTRIES_SUM",
-           "NTUPLE_STAGES", "ntuple_stage_map", "ntuple_staged", "ntuple_stages", "ntuple_map", "ntuple_is_staged"]
+           "NTUPLE_STAGES", "ntuple_stage_map", "ntuple_staged", "ntuple_stages", "ntuple_map", "ntuple_is_staged", "NTUPLE_FEATURE_FORMS",
+           "ntuple_feature_bins"]
 
 
 def __getattr__(name):
@@ -41,7 +42,8 @@ def __getattr__(name):
         return getattr(importlib.import_module(__name__ + ".heuristic"), name)
     if name in ("NTuplePolicy", "NTupleBeamPolicy", "NTupleLearner", "ntuple_table", "ntuple_value", "ntuple_is_symmetric", "ntuple_coherence",
                 "ntuple_step_sizes", "ntuple_shape", "NTUPLE_SHAPES", "ntuple_parts", "NTUPLE_SUMS", "NTUPLE_ENTRIES_SUM",
-                "NTUPLE_STAGES", "ntuple_stage_map", "ntuple_staged", "ntuple_stages", "ntuple_map", "ntuple_is_staged"):
+                "NTUPLE_STAGES", "ntuple_stage_map", "ntuple_staged", "ntuple_stages", "ntuple_map", "ntuple_is_staged", "NTUPLE_FEATURE_FORMS",
+                "ntuple_feature_bins"):
         return getattr(importlib.import_module(__name__ + ".ntuple"), name)
     if name in ("learn", "_learn_lib", "lookahead", "heuristic", "ntuple"):
         return importlib.import_module(__name__ + "." + name)

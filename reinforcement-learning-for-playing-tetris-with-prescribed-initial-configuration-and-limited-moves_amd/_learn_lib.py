@@ -36,6 +36,8 @@ LEARN_SYMBOLS = [
     "tpl_ntuple_value_sum", "tpl_ntuple_act_sum", "tpl_ntuple_search_sum", "tpl_ntuple_beam_sum",
     "tpl_ntuple_value_staged", "tpl_ntuple_act_staged", "tpl_ntuple_search_staged", "tpl_ntuple_beam_staged",
     "tpl_ntuple_update_trace_staged",
+    "tpl_ntuple_value_feature", "tpl_ntuple_act_feature", "tpl_ntuple_search_feature", "tpl_ntuple_beam_feature",
+    "tpl_ntuple_update_trace_feature", "tpl_ntuple_feature_bins",
 ]
 NSTEP_MAX = 16
 BEAM_MAX_DEPTH, BEAM_MAX_WIDTH = 12, 64
@@ -171,6 +173,16 @@ def lib() -> C.CDLL:
         twin.restype = i32
     L.tpl_ntuple_beam_staged.argtypes = L.tpl_ntuple_beam.argtypes
     L.tpl_ntuple_beam_staged.restype = i32
+    for name in ("tpl_ntuple_value", "tpl_ntuple_act", "tpl_ntuple_search"):      # a feature form: `form` for `shape`
+        twin = getattr(L, name + "_feature")
+        twin.argtypes = getattr(L, name + "_shaped").argtypes
+        twin.restype = i32
+    L.tpl_ntuple_beam_feature.argtypes = L.tpl_ntuple_beam.argtypes
+    L.tpl_ntuple_beam_feature.restype = i32
+    L.tpl_ntuple_update_trace_feature.argtypes = L.tpl_ntuple_update_trace.argtypes
+    L.tpl_ntuple_update_trace_feature.restype = i32
+    L.tpl_ntuple_feature_bins.argtypes = [vp, vp, i64, vp, vp]
+    L.tpl_ntuple_feature_bins.restype = i32
     for name in ("tpl_replay_push", "tpl_replay_sample", "tpl_learn_pack", "tpl_priority_init", "tpl_priority_push",
                  "tpl_priority_update", "tpl_replay_sample_prioritized", "tpl_replay_sample_nstep", "tpl_replay_sample_mirror",
                  "tpl_mirror_states", "tpl_afterstates", "tpl_placement_features", "tpl_placement_act",
@@ -561,20 +573,38 @@ NTUPLE_STEP_MAX = 1 << 24                                                       
 PIECE_PLACEMENTS = (17, 34, 34, 34, 17, 17, 9, 9)        # S: the distinct placements of each piece id (7 reads O's entry)
 
 
+# Feature tuples (include/tpl_learn.h): tables indexed by the nine board features, alone or behind a 3 x 3 table.  A registry of their
+# own -- name -> the C `form` of the _feature entries --, beside the shapes and sums above, which stay as they are
+NTUPLE_FEATURE_FORMS = {"feat": 0, "3x3+feat": 1}
+NTUPLE_FEATURES, NTUPLE_FEATURE_BINS = 9, 256
+NTUPLE_ENTRIES_FEAT = NTUPLE_PIECES * NTUPLE_FEATURES * NTUPLE_FEATURE_BINS + NTUPLE_COUNTERS    # 19,456
+_FEATURE_PARTS = {"feat": ("feat",), "3x3+feat": ("3x3", "feat")}
+_PART_ENTRIES = {"2x4": NTUPLE_SHAPES["2x4"][2], "3x3": NTUPLE_SHAPES["3x3"][2], "feat": NTUPLE_ENTRIES_FEAT}
+_PART_COLUMNS = {"2x4": 154, "3x3": 145, "feat": NTUPLE_FEATURES + 1}      # the columns of ntuple_indices, the counter's included
+NTUPLE_ENTRIES_3X3_FEAT = _PART_ENTRIES["3x3"] + NTUPLE_ENTRIES_FEAT                             # 610,304
+
+
 def _ntuple_shape(shape) -> str:
-    if not isinstance(shape, str) or (shape not in NTUPLE_SHAPES and shape not in NTUPLE_SUMS):
-        raise ValueError(f"shape must be one of {sorted(NTUPLE_SHAPES) + sorted(NTUPLE_SUMS)}, got {shape!r}")
+    if not isinstance(shape, str) or (shape not in NTUPLE_SHAPES and shape not in NTUPLE_SUMS and shape not in NTUPLE_FEATURE_FORMS):
+        raise ValueError(f"shape must be one of {sorted(NTUPLE_SHAPES) + sorted(NTUPLE_SUMS) + sorted(NTUPLE_FEATURE_FORMS)}, got {shape!r}")
     return shape
+
+
+def _ntuple_feature_counts() -> dict:
+    """Entry count -> name, for the feature forms."""
+    return {ntuple_entries_of(name): name for name in NTUPLE_FEATURE_FORMS}
 
 
 def ntuple_parts_of(shape: str) -> tuple:
     """The shapes whose tables a table of `shape` consists of, in the order they lie in it: the shape itself, or a sum's parts."""
-    return NTUPLE_SUMS.get(_ntuple_shape(shape), (shape,))
+    if _ntuple_shape(shape) in NTUPLE_FEATURE_FORMS:
+        return _FEATURE_PARTS[shape]
+    return NTUPLE_SUMS.get(shape, (shape,))
 
 
 def ntuple_entries_of(shape: str) -> int:
     """The entries of a table of `shape`: a sum table holds its parts' tables whole, one behind the other."""
-    return sum(NTUPLE_SHAPES[part][2] for part in ntuple_parts_of(shape))
+    return sum(_PART_ENTRIES[part] for part in ntuple_parts_of(shape))
 
 
 def _ntuple_counts() -> dict:
@@ -587,6 +617,9 @@ def ntuple_shape_of(entries: int) -> str:
     counts = _ntuple_counts()
     if entries in counts:
         return counts[entries]
+    if entries in _ntuple_feature_counts():
+        return _ntuple_feature_counts()[entries]
+    counts = {**counts, **_ntuple_feature_counts()}
     raise ValueError(f"no table shape has {entries} entries: {({v: k for k, v in counts.items()})}")
 
 
@@ -594,7 +627,7 @@ def _counter_columns(shape: str) -> list:
     """The columns of ntuple_indices(shape=...) that hold a counter entry: the last one of every part."""
     columns, at = [], 0
     for part in ntuple_parts_of(shape):
-        at += NTUPLE_SHAPES[part][0] + 1
+        at += _PART_COLUMNS[part]
         columns.append(at - 1)
     return columns
 
@@ -658,15 +691,33 @@ def ntuple_indices(rows, piece, L: int, M: int, lines, moves, shape: str = "2x4"
     shape="3x3": [K, 145]; column t < 144 is tuple t = 18 x + y, x < 8 and y < 18 -- cell (row y + j, column x + i) is bit 3 i + j
     of q, i and j < 3 -- at index (piece * 144 + t) * 512 + q; column 144 is the counter entry 589,824 + the same k.
     shape="2x4+3x3", a sum table: [K, 154 + 145] -- the 2 x 4 columns, then the 3 x 3 columns with 314,368, the entry where the second
-    part starts, added to every index; `used` likewise.  Both parts' counter columns are used."""
-    if _ntuple_shape(shape) in NTUPLE_SUMS:
+    part starts, added to every index; `used` likewise.  Both parts' counter columns are used.
+    shape="feat", a feature table: [K, 10]; column j < 9 is feature j of board_features(rows) -- holes .. hole_depth -- at index
+    (piece * 9 + j) * 256 + min(phi_j, 255); column 9 is the counter entry 18,432 + the same k; ALL ten are used.
+    shape="3x3+feat": [K, 145 + 10] -- the 3 x 3 columns, then the feature columns with 590,848 added to every index."""
+    if _ntuple_shape(shape) in NTUPLE_SUMS or shape == "3x3+feat":
         index, used, at = [], [], 0
-        for part in NTUPLE_SUMS[shape]:
+        for part in ntuple_parts_of(shape):
             i, u = ntuple_indices(rows, piece, L, M, lines, moves, part)
             index.append(i + at)
             used.append(u)
-            at += NTUPLE_SHAPES[part][2]
+            at += _PART_ENTRIES[part]
         return np.concatenate(index, axis=1), np.concatenate(used, axis=1)
+    if shape == "feat":
+        rows = np.asarray(rows)
+        if rows.ndim == 1:
+            rows = rows[None]
+        phi = board_features(rows)
+        k = rows.shape[0]
+        piece, lines, moves = (np.broadcast_to(np.asarray(v, dtype=np.int64), (k,)) for v in (piece, lines, moves))
+        if k and (piece.min() < 0 or piece.max() >= NTUPLE_PIECES):
+            raise ValueError("piece must be in 0..7")
+        index = np.zeros((k, NTUPLE_FEATURES + 1), dtype=np.int64)
+        index[:, :NTUPLE_FEATURES] = ((piece[:, None] * NTUPLE_FEATURES + np.arange(NTUPLE_FEATURES)[None, :]) * NTUPLE_FEATURE_BINS
+                                      + np.minimum(phi, NTUPLE_FEATURE_BINS - 1))
+        index[:, NTUPLE_FEATURES] = (NTUPLE_ENTRIES_FEAT - NTUPLE_COUNTERS + 64 * np.clip(int(L) - lines, 0, 15)
+                                     + np.clip(int(M) - moves, 0, 63))
+        return index, np.ones(index.shape, dtype=bool)
     tuples, patterns, entries = NTUPLE_SHAPES[shape]
     wide, high = _WINDOWS[shape]
     rows = np.asarray(rows)
@@ -698,9 +749,10 @@ def ntuple_indices(rows, piece, L: int, M: int, lines, moves, shape: str = "2x4"
 def _ntuple_table(table, staged: bool = True) -> np.ndarray:
     """A table of a known entry count; staged=False: a plain one, for what has no staged form."""
     if (not isinstance(table, np.ndarray) or table.dtype != np.int32 or table.ndim != 1
-            or (table.shape[0] not in _ntuple_counts() and not (staged and table.shape[0] in _ntuple_staged_counts()))):
+            or (table.shape[0] not in _ntuple_counts() and table.shape[0] not in _ntuple_feature_counts()
+                and not (staged and table.shape[0] in _ntuple_staged_counts()))):
         raise ValueError(f"table must be an int32 array of {NTUPLE_ENTRIES} entries (3x3: {NTUPLE_SHAPES['3x3'][2]}, "
-                         f"2x4+3x3: {NTUPLE_ENTRIES_SUM}" + (f"; staged: {list(_ntuple_staged_counts())})" if staged else
+                         f"2x4+3x3: {NTUPLE_ENTRIES_SUM}, feat: {NTUPLE_ENTRIES_FEAT}, 3x3+feat: {NTUPLE_ENTRIES_3X3_FEAT}" + (f"; staged: {list(_ntuple_staged_counts())})" if staged else
                                                              "); a staged table has no coherent update"))
     return table
 
@@ -771,13 +823,23 @@ def ntuple_mirror_permutation(shape: str = "2x4") -> np.ndarray:
     with pi = PIECE_MIRROR and swap(q) = (q >> 4) | ((q & 15) << 4) (3x3: 18 (7 - x) + y, and swap exchanges bits 0..2 with bits
     6..8); the counter indices stay.  A table is mirror-symmetric when table[sigma] == table.
     Built from its definition, not from that closed form: every tuple entry (p, t, q) is put on a board as the cells of its
-    window, and its image is the index ntuple_indices gives the reflected rows under pi(p) at the reflected window."""
-    if _ntuple_shape(shape) in NTUPLE_SUMS:
+    window, and its image is the index ntuple_indices gives the reflected rows under pi(p) at the reflected window.
+    shape="feat" (and the feature part of "3x3+feat") IS a closed form: feature[p][j][q] -> feature[pi(p)][j][q], the counters stay.
+    An entry of a feature table is no set of cells that could be laid on a board and reflected; that the image keeps j and q rests
+    on the nine features being invariant under reflection, which the tests check on the 8,192 boards of random_moves.npz, and the
+    closed form is held to the definition by the symmetric update, which goes through the reflected rows and not through sigma."""
+    if _ntuple_shape(shape) in NTUPLE_SUMS or shape == "3x3+feat":
         parts, at = [], 0
-        for part in NTUPLE_SUMS[shape]:
+        for part in ntuple_parts_of(shape):
             parts.append(ntuple_mirror_permutation(part) + at)
-            at += NTUPLE_SHAPES[part][2]
+            at += _PART_ENTRIES[part]
         return np.concatenate(parts)
+    if shape == "feat":                                       # the features are reflection-invariant: only the piece moves
+        sigma = np.arange(NTUPLE_ENTRIES_FEAT, dtype=np.int64)
+        stride = NTUPLE_FEATURES * NTUPLE_FEATURE_BINS
+        for p in range(NTUPLE_PIECES):
+            sigma[p * stride:(p + 1) * stride] = PIECE_MIRROR[p] * stride + np.arange(stride)
+        return sigma
     tuples, patterns, entries = NTUPLE_SHAPES[shape]
     if shape in _sigma_of:
         return _sigma_of[shape].copy()

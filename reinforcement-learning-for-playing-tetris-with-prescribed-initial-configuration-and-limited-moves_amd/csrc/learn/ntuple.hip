@@ -65,6 +65,13 @@
 // and a leaf of the two-ply search reads the block of its OWN lines and moves left.  The update does get kernels of its own here:
 // where a state's adds go depends on its stage, so staged_trace_lane is trace_lane with the block's offset in every index.  It
 // reads the map, which nothing writes, and adds to the blocks, which it never reads.
+//
+// Feature tuples (the _feature entries).  FeatureTable is a geometry without windows: nine rows of 256 bins per falling piece, row j
+// read at min(phi_{3 + j}, 255) of board_features on the column words the lane holds (tpl_ntuple.h).  value_lane and ntuple_policy named
+// with it, and with SumOf<Shape3x3, FeatureTable>, are the six ntuple_feature*_kernel.  The update is a kernel of its own,
+// ntuple_feature_trace_kernel: a state's ten adds fall on a table of 19,456 entries that fits LDS whole, so a block sums its states'
+// adds there and flushes what is not zero.  There is no staged and no coherent form.
+#include <algorithm>
 #include <cmath>
 
 #include "tpl_ntuple.h"
@@ -104,6 +111,27 @@ __global__ __launch_bounds__(kStateBlock) void ntuple_sum_value_kernel(const Val
 __global__ __launch_bounds__(kStateBlock) void ntuple_staged_value_kernel(const ValueArgs p) { value_lane<StagedOf<Shape2x4>>(p); }
 __global__ __launch_bounds__(kStateBlock) void ntuple_staged3_value_kernel(const ValueArgs p) { value_lane<StagedOf<Shape3x3>>(p); }
 __global__ __launch_bounds__(kStateBlock) void ntuple_staged_sum_value_kernel(const ValueArgs p) { value_lane<StagedOf<ShapeSum>>(p); }
+__global__ __launch_bounds__(kStateBlock) void ntuple_feature_value_kernel(const ValueArgs p) { value_lane<FeatureTable>(p); }
+__global__ __launch_bounds__(kStateBlock) void ntuple_feature3_value_kernel(const ValueArgs p) { value_lane<Shape3x3Feature>(p); }
+
+// ---- tpl_ntuple_feature_bins: the nine bins of every state, running or not ----
+struct BinsArgs {
+    const uint4* a;              // [n]
+    const uint4* b;
+    uint32_t n;
+    uint8_t* bins;               // [n][9]
+};
+
+__global__ __launch_bounds__(kStateBlock) void ntuple_feature_bins_kernel(const BinsArgs p) {
+    const uint32_t i = blockIdx.x * kStateBlock + threadIdx.x;
+    if (i >= p.n) return;
+    tpl::Board s;
+    tpl::unpack_board(p.a[i], p.b[i], s);
+    uint32_t q[FeatureTable::kFeatureRows];
+    feature_bins(s.c, q);
+#pragma unroll
+    for (int j = 0; j < FeatureTable::kFeatureRows; ++j) p.bins[i * (uint32_t)FeatureTable::kFeatureRows + j] = (uint8_t)q[j];
+}
 
 // d = (int32) rint(rate * e): the product rounded once, clamped to +-2^24, 0 for a NaN
 __device__ __forceinline__ int32_t update_step(float rate, float e) {
@@ -182,6 +210,74 @@ template <bool kSymmetric>
 __global__ __launch_bounds__(kStateBlock) void ntuple_trace_kernel(const TraceArgs p) { trace_lane<Shape2x4, kSymmetric>(p); }
 template <bool kSymmetric>
 __global__ __launch_bounds__(kStateBlock) void ntuple3_trace_kernel(const TraceArgs p) { trace_lane<Shape3x3, kSymmetric>(p); }
+
+// ---- the feature table's update: tpl_ntuple_update_trace_feature ----
+// What a lane does before its adds, trace_lane's lines for the state of board i at age `age`: the younger states'
+// state words, the step and the state of that age.  True where the lane adds: `d` is not 0 and `s` runs.
+__device__ __forceinline__ bool feature_trace_state(const TraceArgs& p, uint32_t i, uint32_t age, float rate, uint32_t& d, tpl::Board& s) {
+    bool open = true;
+    for (uint32_t k = 0; k < age; ++k) {
+        const uint32_t slot = p.head >= k ? p.head - k : p.head + p.slots - k;
+        open = open && ((p.b[slot * p.n + i].y >> 28) & 3u) == tpl::ST_RUNNING;
+    }
+    d = (uint32_t)update_step(rate, p.error[i]);
+    if (!open || d == 0u) return false;
+    const uint32_t slot = p.head >= age ? p.head - age : p.head + p.slots - age;
+    tpl::unpack_board(p.a[slot * p.n + i], p.b[slot * p.n + i], s);
+    return s.state == tpl::ST_RUNNING;
+}
+
+// rate * decay^age: `age` rounded multiplies on a block-uniform value, as the rule has it
+__device__ __forceinline__ float aged_rate(const TraceArgs& p, uint32_t age) {
+    float w = 1.0f;
+    for (uint32_t k = 0; k < age; ++k) w = __fmul_rn(w, p.decay);
+    return __fmul_rn(p.rate, w);
+}
+
+// The update kernel: a block holds an image of the WHOLE table in LDS (19,456 dwords, 76 KB of the 160 KB a gfx950 workgroup may
+// declare: two blocks a CU), walks the states i = blockIdx.x * 512 + tid, + 512 gridDim.x, ... of its age, adds every state's ten
+// entries (symmetric: nineteen) there with LDS atomics, and flushes the non-zero sums with one atomic add to memory each.  All adds are
+// integers modulo 2^32, so the bytes are those of an atomic add to memory per entry -- the form this one was measured against
+// (profiles/learner/ntuple_feature_update_forms.log): boards in lockstep send ten million adds to a few thousand addresses.
+constexpr int kCombineBlock = 512;
+// The blocks of one age, at the most: two blocks of 76 KB fit the 160 KB of a CU's LDS, and the MI355X this was measured on has 256
+// CUs -- one resident round of the device.  An ASSUMPTION about the device, not a bound: with more blocks each would zero and scan the
+// whole image for fewer states, with fewer CUs the blocks run in more than one round.  Other caps were not measured.
+constexpr uint32_t kCombineBlocksPerCU = 2, kCombineCUs = 256, kCombineMaxBlocks = kCombineBlocksPerCU * kCombineCUs;
+static_assert(FeatureTable::kEntries % kCombineBlock == 0, "the image is zeroed and flushed in whole rounds of a block");
+
+template <bool kSymmetric>
+__global__ __launch_bounds__(kCombineBlock) void ntuple_feature_trace_kernel(const TraceArgs p) {
+    __shared__ uint32_t s_sum[FeatureTable::kEntries];
+#pragma unroll 1
+    for (int t = threadIdx.x; t < FeatureTable::kEntries; t += kCombineBlock) s_sum[t] = 0u;
+    __syncthreads();
+    const uint32_t age = blockIdx.y;
+    const float rate = aged_rate(p, age);
+#pragma unroll 1
+    for (uint32_t i = blockIdx.x * kCombineBlock + threadIdx.x; i < p.n; i += gridDim.x * kCombineBlock) {
+        uint32_t d;
+        tpl::Board s;
+        if (!feature_trace_state(p, i, age, rate, d, s)) continue;
+        atomicAdd(&s_sum[(uint32_t)FeatureTable::kCounterBase + counter_index(p.L, p.M, s.lines, s.moves)], d);
+        uint32_t q[FeatureTable::kFeatureRows];
+        feature_bins(s.c, q);
+        const uint32_t piece = s.window & 7u;
+        const uint32_t base = piece * (uint32_t)FeatureTable::kPieceStride;
+        const uint32_t mirror_base = ((kPieceMirror >> (4u * piece)) & 7u) * (uint32_t)FeatureTable::kPieceStride;
+#pragma unroll
+        for (int j = 0; j < FeatureTable::kFeatureRows; ++j) {
+            atomicAdd(&s_sum[feature_entry(base, j, q[j])], d);
+            if constexpr (kSymmetric) atomicAdd(&s_sum[feature_entry(mirror_base, j, q[j])], d);
+        }
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int t = threadIdx.x; t < FeatureTable::kEntries; t += kCombineBlock) {
+        const uint32_t sum = s_sum[t];
+        if (sum) atomicAdd(p.table + t, sum);
+    }
+}
 
 // ---- the staged update: tpl_ntuple_update_trace_staged ----
 struct StagedTraceArgs {
@@ -557,6 +653,13 @@ __global__ __launch_bounds__(kActBlock) __attribute__((amdgpu_waves_per_eu(4, 4)
     ntuple_policy<StagedOf<ShapeSum>, 2>(p.act, p.second);
 }
 
+__global__ __launch_bounds__(kActBlock) void ntuple_feature_act_kernel(const ActArgs p) { ntuple_policy<FeatureTable, 1>(p, nullptr); }
+__global__ __launch_bounds__(kActBlock) void ntuple_feature_search_kernel(const SearchArgs p) { ntuple_policy<FeatureTable, 2>(p.act, p.second); }
+__global__ __launch_bounds__(kActBlock) void ntuple_feature3_act_kernel(const ActArgs p) { ntuple_policy<Shape3x3Feature, 1>(p, nullptr); }
+__global__ __launch_bounds__(kActBlock) void ntuple_feature3_search_kernel(const SearchArgs p) {
+    ntuple_policy<Shape3x3Feature, 2>(p.act, p.second);
+}
+
 }  // namespace
 }  // namespace tpl_learn
 
@@ -582,7 +685,10 @@ int launch_value(const char* name, const void* plane_a, const void* plane_b, int
     p.a = (const uint4*)plane_a; p.b = (const uint4*)plane_b; p.n = (uint32_t)n;
     p.L = (uint32_t)L; p.M = (uint32_t)M; p.table = table; p.value = value;
     const dim3 grid((p.n + kStateBlock - 1) / kStateBlock), block(kStateBlock);
-    if (staged) {
+    if (form == Form::kFeature || form == Form::k3x3Feature) {
+        const auto kernel = form == Form::kFeature ? ntuple_feature_value_kernel : ntuple_feature3_value_kernel;
+        hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, p);
+    } else if (staged) {
         const auto kernel = form == Form::kSum ? ntuple_staged_sum_value_kernel
                                                : form == Form::k3x3 ? ntuple_staged3_value_kernel : ntuple_staged_value_kernel;
         hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, p);
@@ -618,7 +724,16 @@ int launch_ntuple_policy(const char* name, int depth, const void* plane_a, const
     p.action = action; p.score = score; p.after_a = (uint4*)after_a; p.after_b = (uint4*)after_b; p.value = value;
     const dim3 grid((p.n + kBoardsPerBlock - 1) / kBoardsPerBlock), block(kActBlock);
     const bool wide = form == Form::k3x3;
-    if (staged && depth == 2) {
+    if (form == Form::kFeature || form == Form::k3x3Feature) {
+        if (depth == 2) {
+            const SearchArgs q{p, second};
+            const auto kernel = form == Form::kFeature ? ntuple_feature_search_kernel : ntuple_feature3_search_kernel;
+            hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, q);
+        } else {
+            const auto kernel = form == Form::kFeature ? ntuple_feature_act_kernel : ntuple_feature3_act_kernel;
+            hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, p);
+        }
+    } else if (staged && depth == 2) {
         const SearchArgs q{p, second};
         const auto kernel = form == Form::kSum ? ntuple_staged_sum_search_kernel : wide ? ntuple_staged3_search_kernel : ntuple_staged_search_kernel;
         hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, q);
@@ -879,4 +994,74 @@ extern "C" int tpl_ntuple_update_coherent_shaped(const void* ring_a, const void*
     const int64_t* const given = coherence;
     return update_ring("tpl_ntuple_update_coherent_shaped", ring_a, ring_b, n, slots, head, horizon, L, M, table, &given, error,
                        rate, decay, symmetric, shape, stream);
+}
+
+// ---- feature tuples: the _feature entries ----
+extern "C" int tpl_ntuple_value_feature(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const int32_t* table,
+                                        float* value, int32_t form, void* stream) {
+    if (const int rc = check_feature_form("tpl_ntuple_value_feature", form)) return rc;
+    return launch_value("tpl_ntuple_value_feature", plane_a, plane_b, n, L, M, table, value, feature_form_of(form), stream);
+}
+
+extern "C" int tpl_ntuple_act_feature(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line,
+                                      float r_win, float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed,
+                                      uint64_t step, uint8_t* action, float* score, void* after_a, void* after_b, float* value,
+                                      int32_t form, void* stream) {
+    if (const int rc = check_feature_form("tpl_ntuple_act_feature", form)) return rc;
+    return launch_ntuple_policy("tpl_ntuple_act_feature", 1, plane_a, plane_b, n, L, M, r_line, r_win, r_lose, gamma, table, epsilon,
+                                seed, step, action, nullptr, score, after_a, after_b, value, feature_form_of(form), stream);
+}
+
+extern "C" int tpl_ntuple_search_feature(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line,
+                                         float r_win, float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed,
+                                         uint64_t step, uint8_t* action, uint8_t* second, float* score, void* after_a, void* after_b,
+                                         float* value, int32_t form, void* stream) {
+    if (const int rc = check_feature_form("tpl_ntuple_search_feature", form)) return rc;
+    return launch_ntuple_policy("tpl_ntuple_search_feature", 2, plane_a, plane_b, n, L, M, r_line, r_win, r_lose, gamma, table,
+                                epsilon, seed, step, action, second, score, after_a, after_b, value, feature_form_of(form), stream);
+}
+
+extern "C" int tpl_ntuple_update_trace_feature(const void* ring_a, const void* ring_b, int64_t n, int32_t slots, int32_t head,
+                                               int32_t horizon, int32_t L, int32_t M, int32_t* table, const float* error, float rate,
+                                               float decay, int32_t symmetric, void* stream) {
+    const char* const name = "tpl_ntuple_update_trace_feature";
+    if (const int rc = check_planes(name, ring_a, ring_b, n, L, M)) return rc;
+    if (const int rc = check_table(name, table)) return rc;
+    if (!error) return fail_msg(TPL_ERR_ARG, "%s: null pointer (error is required)", name);
+    if ((uintptr_t)error & 3u) return fail_msg(TPL_ERR_ARG, "%s: error must be 4-byte aligned", name);
+    if (!std::isfinite(rate)) return fail_msg(TPL_ERR_ARG, "%s: rate must be finite", name);
+    if (const int rc = check_ring(name, n, slots, head, horizon, decay)) return rc;
+    TraceArgs p{};
+    p.a = (const uint4*)ring_a; p.b = (const uint4*)ring_b; p.n = (uint32_t)n; p.slots = (uint32_t)slots; p.head = (uint32_t)head;
+    p.L = (uint32_t)L; p.M = (uint32_t)M; p.table = (uint32_t*)table; p.error = error; p.rate = rate; p.decay = decay;
+    // at 2^20 boards a lane walks 2^20 / 512 / 512 = 4 states
+    const uint32_t blocks = std::min<uint32_t>((p.n + kCombineBlock - 1) / kCombineBlock, kCombineMaxBlocks);
+    hipLaunchKernelGGL(symmetric ? ntuple_feature_trace_kernel<true> : ntuple_feature_trace_kernel<false>,
+                       dim3(blocks, (uint32_t)horizon), dim3(kCombineBlock), 0, (hipStream_t)stream, p);
+    TPL_LEARN_HIP(hipGetLastError());
+    return TPL_OK;
+}
+
+// check_planes without a game: the bins read neither L nor M.  The same refusals in the same words, in its order.
+static int check_state_planes(const char* name, const void* plane_a, const void* plane_b, int64_t n) {
+    if (!plane_a || !plane_b) return fail_msg(TPL_ERR_ARG, "%s: null pointer", name);
+    if (n < 1) return fail_msg(TPL_ERR_ARG, "%s: n must be positive", name);
+    if (n >= (((int64_t)1 << 31) + kActions - 1) / kActions)
+        return fail_msg(TPL_ERR_ARG, "%s: n too large (40 n must stay below 2^31)", name);
+    if (((uintptr_t)plane_a & 15u) || ((uintptr_t)plane_b & 15u))
+        return fail_msg(TPL_ERR_ARG, "%s: planes must be 16-byte aligned", name);
+    return TPL_OK;
+}
+
+// Not a hot-path entry: it exists so that the device feature code can be held to the host mirror without the gathers, and a lane's
+// nine byte stores are not coalesced.
+extern "C" int tpl_ntuple_feature_bins(const void* plane_a, const void* plane_b, int64_t n, uint8_t* bins, void* stream) {
+    const char* const name = "tpl_ntuple_feature_bins";
+    if (const int rc = check_state_planes(name, plane_a, plane_b, n)) return rc;
+    if (!bins) return fail_msg(TPL_ERR_ARG, "%s: null pointer (bins is required)", name);
+    BinsArgs p{};
+    p.a = (const uint4*)plane_a; p.b = (const uint4*)plane_b; p.n = (uint32_t)n; p.bins = bins;
+    hipLaunchKernelGGL(ntuple_feature_bins_kernel, dim3((p.n + kStateBlock - 1) / kStateBlock), dim3(kStateBlock), 0, (hipStream_t)stream, p);
+    TPL_LEARN_HIP(hipGetLastError());
+    return TPL_OK;
 }

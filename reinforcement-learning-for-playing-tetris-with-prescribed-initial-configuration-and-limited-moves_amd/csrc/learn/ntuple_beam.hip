@@ -203,6 +203,8 @@ __device__ __forceinline__ void ntuple_beam(const NTupleBeamArgs& p) {
 __global__ __launch_bounds__(kBeamBlock) void ntuple_beam_kernel(const NTupleBeamArgs p) { ntuple_beam<Shape2x4>(p); }
 __global__ __launch_bounds__(kBeamBlock) void ntuple_beam3_kernel(const NTupleBeamArgs p) { ntuple_beam<Shape3x3>(p); }
 __global__ __launch_bounds__(kBeamBlock) void ntuple_beam_sum_kernel(const NTupleBeamArgs p) { ntuple_beam<ShapeSum>(p); }
+__global__ __launch_bounds__(kBeamBlock) void ntuple_feature_beam_kernel(const NTupleBeamArgs p) { ntuple_beam<FeatureTable>(p); }
+__global__ __launch_bounds__(kBeamBlock) void ntuple_feature3_beam_kernel(const NTupleBeamArgs p) { ntuple_beam<Shape3x3Feature>(p); }
 __global__ __launch_bounds__(kBeamBlock) void ntuple_staged_beam_kernel(const NTupleBeamArgs p) { ntuple_beam<StagedOf<Shape2x4>>(p); }
 __global__ __launch_bounds__(kBeamBlock) void ntuple_staged_beam3_kernel(const NTupleBeamArgs p) { ntuple_beam<StagedOf<Shape3x3>>(p); }
 // four waves a SIMD: as for ntuple_staged_sum_search_kernel (ntuple.hip), the gathers of a leaf go out nine and eight at a time
@@ -236,7 +238,10 @@ int launch_ntuple_beam(const char* name, const void* plane_a, const void* plane_
     p.L = (uint32_t)L; p.M = (uint32_t)M; p.r_line = r_line; p.r_win = r_win; p.r_lose = r_lose; p.gamma = gamma;
     p.table = table; p.depth = (uint32_t)depth; p.width = (uint32_t)width;
     p.action = action; p.plan = plan; p.score = score; p.after_a = (uint4*)after_a; p.after_b = (uint4*)after_b;
-    if (staged) {
+    if (form == Form::kFeature || form == Form::k3x3Feature) {
+        const auto kernel = form == Form::kFeature ? ntuple_feature_beam_kernel : ntuple_feature3_beam_kernel;
+        hipLaunchKernelGGL(kernel, dim3(p.n), dim3(kBeamBlock), 0, (hipStream_t)stream, p);
+    } else if (staged) {
         const auto kernel = form == Form::kSum ? ntuple_staged_beam_sum_kernel
                                                : form == Form::k3x3 ? ntuple_staged_beam3_kernel : ntuple_staged_beam_kernel;
         hipLaunchKernelGGL(kernel, dim3(p.n), dim3(kBeamBlock), 0, (hipStream_t)stream, p);
@@ -271,4 +276,13 @@ extern "C" int tpl_ntuple_beam_staged(const void* plane_a, const void* plane_b, 
     if (const int rc = check_form("tpl_ntuple_beam_staged", form)) return rc;
     return launch_ntuple_beam("tpl_ntuple_beam_staged", plane_a, plane_b, n, L, M, r_line, r_win, r_lose, gamma, table, depth, width,
                               action, plan, score, after_a, after_b, (Form)form, stream, true);
+}
+
+extern "C" int tpl_ntuple_beam_feature(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line,
+                                       float r_win, float r_lose, float gamma, const int32_t* table, int32_t depth, int32_t width,
+                                       uint8_t* action, uint8_t* plan, float* score, void* after_a, void* after_b, int32_t form,
+                                       void* stream) {
+    if (const int rc = check_feature_form("tpl_ntuple_beam_feature", form)) return rc;
+    return launch_ntuple_beam("tpl_ntuple_beam_feature", plane_a, plane_b, n, L, M, r_line, r_win, r_lose, gamma, table, depth, width,
+                              action, plan, score, after_a, after_b, feature_form_of(form), stream);
 }

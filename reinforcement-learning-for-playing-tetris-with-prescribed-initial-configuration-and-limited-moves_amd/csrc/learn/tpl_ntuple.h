@@ -1,5 +1,5 @@
 // tpl_ntuple.h -- what the units that read an n-tuple table share (ntuple.hip, ntuple_beam.hip; include/tpl_learn.h states the
-// rule): the geometry of the two table shapes, of their sum and of a staged table of any of the three, the counter index, the
+// rule): the geometry of the two table shapes, of their sum, of a staged table of any of the three and of a feature table, the counter index, the
 // 32-bit addressing of an entry, the sum and the value of a running board, and the shape, form and table checks of the entry points.
 #pragma once
 
@@ -172,6 +172,60 @@ struct BoardSum<StagedOf<S>> {
     }
 };
 
+// The geometry of a FEATURE TABLE (include/tpl_learn.h, "Feature tuples"): per falling piece nine rows of 256 bins, row j looked up
+// at min(phi_{3 + j}, 255) of the board, then the counters.  It has no windows: it is reached through BoardSum alone, like SumOf.
+struct FeatureTable {
+    static constexpr int kFeatureRows = TPL_NTUPLE_FEATURES, kBins = TPL_NTUPLE_FEATURE_BINS;
+    static constexpr int kPieceStride = kFeatureRows * kBins;  // 2,304
+    static constexpr int kCounterBase = 8 * kPieceStride;      // 18,432
+    static constexpr int kEntries = kCounterBase + kCounters;
+};
+static_assert(FeatureTable::kEntries == TPL_NTUPLE_ENTRIES_FEAT && FeatureTable::kFeatureRows == kFeatures - 3,
+              "the feature table's layout of include/tpl_learn.h: phi_3 .. phi_11");
+
+// the nine bins of a board: board_features on the column words, each clamped to the last bin (only wells can pass it)
+__device__ __forceinline__ void feature_bins(const uint32_t (&c)[tpl::kCols], uint32_t (&q)[FeatureTable::kFeatureRows]) {
+    Features phi;
+    board_features(c, phi);
+#pragma unroll
+    for (int j = 0; j < FeatureTable::kFeatureRows; ++j) q[j] = min(phi.f[3 + j], (uint32_t)(FeatureTable::kBins - 1));
+}
+
+// the index of bin q of feature j among the rows of the piece that start at `base`
+__device__ __forceinline__ uint32_t feature_entry(uint32_t base, int j, uint32_t q) { return base + (uint32_t)(j * FeatureTable::kBins) + q; }
+
+// The integer value of a running board under a feature table: the nine gathers, all in flight at once, and the counter.  Every one of
+// them is used: a board without holes reads bin 0.
+__device__ __forceinline__ long long feature_sum(const uint32_t (&c)[tpl::kCols], uint32_t piece, uint32_t k, const int32_t* table) {
+    uint32_t q[FeatureTable::kFeatureRows];
+    feature_bins(c, q);
+    const uint32_t base = piece * (uint32_t)FeatureTable::kPieceStride;
+    int32_t v[FeatureTable::kFeatureRows];
+#pragma unroll
+    for (int j = 0; j < FeatureTable::kFeatureRows; ++j) v[j] = *entry(table, feature_entry(base, j, q[j]));
+    long long sum = *entry(table, (uint32_t)FeatureTable::kCounterBase + k);
+#pragma unroll
+    for (int j = 0; j < FeatureTable::kFeatureRows; ++j) sum += v[j];
+    return sum;
+}
+
+template <>
+struct BoardSum<FeatureTable> {
+    static __device__ __forceinline__ long long of(const uint32_t (&c)[tpl::kCols], uint32_t piece, uint32_t k, const int32_t* table) {
+        return feature_sum(c, piece, k, table);
+    }
+};
+// a window table with a feature table behind it: the window part's gather loop, then the nine gathers, integers added before the one rounding
+template <typename A, int kEntriesOfFirst>
+struct BoardSum<SumOf<A, FeatureTable, kEntriesOfFirst>> {
+    static __device__ __forceinline__ long long of(const uint32_t (&c)[tpl::kCols], uint32_t piece, uint32_t k, const int32_t* table) {
+        return ntuple_sum<A>(c, piece, k, table) + feature_sum(c, piece, k, table + kEntriesOfFirst);
+    }
+};
+using Shape3x3Feature = SumOf<Shape3x3, FeatureTable, TPL_NTUPLE_ENTRIES_3X3>;
+static_assert(Shape3x3Feature::kEntries == TPL_NTUPLE_ENTRIES_3X3_FEAT && (Shape3x3Feature::kSecondAt * sizeof(int32_t)) % 16 == 0,
+              "the 3 x 3 + feature table's layout of include/tpl_learn.h: the feature part is a 16-byte aligned table");
+
 // V of a state that runs: one rounding from the 64-bit sum to float32, then an exact scaling by 2^-16
 template <typename S>
 __device__ __forceinline__ float ntuple_value(const tpl::Board& s, uint32_t L, uint32_t M, const int32_t* table) {
@@ -181,7 +235,17 @@ __device__ __forceinline__ float ntuple_value(const tpl::Board& s, uint32_t L, u
 
 // Which kernels an entry launches: the two shapes of tpl_ntuple_shape, and their sum, which is no `shape` of the C interface.  The
 // _staged entries take all three as their `form` (tpl_ntuple_form has the enumerators' values).
-enum class Form { k2x4, k3x3, kSum };
+// kFeature and k3x3Feature are the two tpl_ntuple_feature_form of the _feature entries, which no other entry takes.
+enum class Form { k2x4, k3x3, kSum, kFeature, k3x3Feature };
+inline Form feature_form_of(int32_t form) { return form == TPL_NTUPLE_FEATURE_FORM_3X3 ? Form::k3x3Feature : Form::kFeature; }   // after check_feature_form
+
+// a feature form the library does not know is refused first, before any pointer is looked at
+inline int check_feature_form(const char* name, int32_t form) {
+    if (form != TPL_NTUPLE_FEATURE_FORM_ALONE && form != TPL_NTUPLE_FEATURE_FORM_3X3)
+        return fail_msg(TPL_ERR_ARG, "%s: form must be TPL_NTUPLE_FEATURE_FORM_ALONE (0) or TPL_NTUPLE_FEATURE_FORM_3X3 (1), got %d", name,
+                        (int)form);
+    return TPL_OK;
+}
 inline Form form_of(int32_t shape) { return shape == TPL_NTUPLE_SHAPE_3X3 ? Form::k3x3 : Form::k2x4; }   // after check_shape
 static_assert((int)Form::k2x4 == TPL_NTUPLE_FORM_2X4 && (int)Form::k3x3 == TPL_NTUPLE_FORM_3X3 && (int)Form::kSum == TPL_NTUPLE_FORM_SUM,
               "a checked `form` converts to Form");

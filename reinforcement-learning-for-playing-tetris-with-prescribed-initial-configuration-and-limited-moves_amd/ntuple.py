@@ -40,6 +40,9 @@ learning on the device (the rule: include/tpl_learn.h; the kernels: csrc/learn/n
                                   weight promotion: a staged table whose eight blocks are each a copy of a plain table, with the map
     ntuple_stages(table), ntuple_map(table), ntuple_is_staged(table)
                                   the eight per-stage views (each a valid plain table of the form), the map view, the test
+    ntuple_table(device, "feat"), ntuple_table(device, "3x3+feat")
+                                  a zeroed FEATURE TABLE, int32 [19,456], and a 3x3 table with a feature table behind it, int32 [610,304]
+    ntuple_feature_bins(source)   uint8 [K, 9]: the nine bins a feature table is read at
 
 The value is a sum of table entries, one per 2 x 4 window of the board that is not empty, chosen by the falling piece, plus one
 per (lines left, moves left); the update adds rint(rate * error) to the same entries.  Everything is integer, so two trainings
@@ -59,6 +62,14 @@ three moves left and another with thirty.  The stage is looked up wherever a tab
 or of the beam is valued in the block of its own lines and moves left.  Value, both policies, the beam, the symmetry test and the
 learner (traces and symmetry; NOT temporal coherence) take a staged table by its entry count; a map that uses two or four stages
 leaves the other blocks untouched.  ntuple_staged(trained_table, map) starts every stage from a trained plain table.
+
+Feature tuples ("feat", "3x3+feat": NTUPLE_FEATURE_FORMS).  Every window is local; what carries HeuristicPolicy's hand-made score is
+global: holes, aggregate height, bumpiness, transitions, wells.  A feature table holds, per falling piece, a row of 256 entries for each
+of the nine board features, looked up at min(feature, 255) -- the piecewise-constant generalisation of that linear score, learned by the
+same TD rule -- and the counters; "3x3+feat" sums it with a 3x3 table as "2x4+3x3" sums two shapes, one rounding.  The features do not
+change under reflection, so the mirror image moves only the piece.  Value, both policies, the beam, the symmetry test and the learner
+with traces and symmetry take either form by name or by entry count.  There is no staged and no coherent form, and both are refused:
+each would be eight more kernels, and neither option raised a win rate in the record.
 """
 from __future__ import annotations
 
@@ -68,12 +79,12 @@ from typing import Optional
 import torch
 
 from . import _learn_lib
-from ._learn_lib import (BEAM_MAX_WIDTH, NTUPLE_BEAM_MAX_DEPTH, NTUPLE_COUNTERS, NTUPLE_ENTRIES, NTUPLE_ENTRIES_SUM, NTUPLE_FORM_IDS,
-                         NTUPLE_SHAPE_IDS, NTUPLE_SHAPES, NTUPLE_STAGES, NTUPLE_SUMS, NTUPLE_TRACE_MAX, check)
+from ._learn_lib import (BEAM_MAX_WIDTH, NTUPLE_BEAM_MAX_DEPTH, NTUPLE_COUNTERS, NTUPLE_ENTRIES, NTUPLE_ENTRIES_SUM, NTUPLE_FEATURE_FORMS,
+                         NTUPLE_FEATURES, NTUPLE_FORM_IDS, NTUPLE_SHAPE_IDS, NTUPLE_SHAPES, NTUPLE_STAGES, NTUPLE_SUMS, NTUPLE_TRACE_MAX, check)
 from .lookahead import _MAX_BOARDS, _boards, _ptr, _state_ptrs
 
 __all__ = ["NTUPLE_ENTRIES", "NTUPLE_ENTRIES_SUM", "NTUPLE_SHAPES", "NTUPLE_SUMS", "ntuple_shape", "ntuple_parts", "ntuple_table", "ntuple_value", "ntuple_is_symmetric", "ntuple_coherence", "ntuple_step_sizes",
-           "NTuplePolicy", "NTupleBeamPolicy", "NTupleLearner", "NTUPLE_STAGES", "ntuple_stage_map", "ntuple_staged", "ntuple_stages",
+           "NTuplePolicy", "NTupleBeamPolicy", "NTupleLearner", "NTUPLE_FEATURE_FORMS", "ntuple_feature_bins", "NTUPLE_STAGES", "ntuple_stage_map", "ntuple_staged", "ntuple_stages",
            "ntuple_map", "ntuple_is_staged"]
 
 _STATE_WON = 1                                                 # bits 28..29 of B.y: 0 running, 1 won, 2 and 3 lost
@@ -85,9 +96,22 @@ def _counts() -> dict:
     return _learn_lib._ntuple_counts()
 
 
-def _entries(shape) -> int:
-    if not isinstance(shape, str) or (shape not in NTUPLE_SHAPES and shape not in NTUPLE_SUMS):
-        raise ValueError(f"shape must be one of {sorted(NTUPLE_SHAPES) + sorted(NTUPLE_SUMS)}, got {shape!r}")
+def _table_counts() -> dict:
+    """Entry count -> name, for every plain table: the shapes, their sums and the feature forms."""
+    return {**_learn_lib._ntuple_counts(), **_learn_lib._ntuple_feature_counts()}
+
+
+_NO_FEATURE_FORM = ("a feature table ({shape!r}) has no {what}: each would be eight more kernels, and neither staging nor temporal "
+                    "coherence raised a win rate in the record (include/tpl_learn.h, \"Feature tuples\")")
+
+
+def _entries(shape, windows_only: str = "") -> int:
+    """The entries of a table of `shape`; windows_only: what a feature form is refused for, where it is."""
+    names = sorted(NTUPLE_SHAPES) + sorted(NTUPLE_SUMS) + sorted(NTUPLE_FEATURE_FORMS)
+    if not isinstance(shape, str) or shape not in names:
+        raise ValueError(f"shape must be one of {names}, got {shape!r}")
+    if windows_only and shape in NTUPLE_FEATURE_FORMS:
+        raise ValueError(_NO_FEATURE_FORM.format(shape=shape, what=windows_only))
     return _learn_lib.ntuple_entries_of(shape)
 
 
@@ -98,12 +122,13 @@ def _staged_counts() -> dict:
 
 def ntuple_table(device="cuda:0", shape: str = "2x4", staged: bool = False) -> torch.Tensor:
     """A zeroed n-tuple table of `shape` on `device`: int32 [NTUPLE_SHAPES[shape] entries] (2x4: NTUPLE_ENTRIES); "2x4+3x3": a sum
-    table, int32 [NTUPLE_ENTRIES_SUM] -- ntuple_parts gives its two tables.  staged=True: a staged table of that form, int32
+    table, int32 [NTUPLE_ENTRIES_SUM] -- ntuple_parts gives its two tables.  "feat": a feature table, int32 [19,456]; "3x3+feat":
+    int32 [610,304], a 3x3 table and a feature table (ntuple_parts); neither has a staged form.  staged=True: a staged table of that form, int32
     [NTUPLE_STAGES * entries + 1,024] -- ntuple_stages gives its eight tables, ntuple_map its map; the all-zero map sends every
     state to stage 0."""
     if not isinstance(staged, bool):
         raise ValueError(f"staged must be True or False, got {staged!r}")
-    entries = _entries(shape)
+    entries = _entries(shape, "staged form" if staged else "")
     return torch.zeros(NTUPLE_STAGES * entries + NTUPLE_COUNTERS if staged else entries, dtype=torch.int32, device=device)
 
 
@@ -153,6 +178,7 @@ def ntuple_staged(table: torch.Tensor, stage_map: torch.Tensor) -> torch.Tensor:
     if not isinstance(table, torch.Tensor) or ntuple_is_staged(table):
         raise ValueError("ntuple_staged promotes a plain table (ntuple_stages gives the plain tables of a staged one)")
     _table(table, table.device)
+    _entries(ntuple_shape(table), "staged form")
     out = ntuple_table(table.device, ntuple_shape(table), staged=True)
     for block in ntuple_stages(out):
         block.copy_(table)
@@ -163,7 +189,7 @@ def ntuple_staged(table: torch.Tensor, stage_map: torch.Tensor) -> torch.Tensor:
 def ntuple_coherence(device="cuda:0", shape: str = "2x4") -> torch.Tensor:
     """A zeroed coherence buffer of `shape` on `device`: int64 [entries, 2], entry j the pair (E_j, A_j) of include/tpl_learn.h;
     of a sum, laid out as the sum table is."""
-    return torch.zeros((_entries(shape), 2), dtype=torch.int64, device=device)
+    return torch.zeros((_entries(shape, "coherence buffer"), 2), dtype=torch.int64, device=device)
 
 
 def ntuple_shape(table) -> str:
@@ -171,9 +197,11 @@ def ntuple_shape(table) -> str:
     tensor of any other size is refused."""
     if isinstance(table, torch.Tensor) and table.dim() >= 1 and table.shape[0] in _counts():
         return _counts()[table.shape[0]]
+    if isinstance(table, torch.Tensor) and table.dim() == 1 and table.shape[0] in _table_counts():
+        return _table_counts()[table.shape[0]]                 # a feature form: "feat" or "3x3+feat"
     if isinstance(table, torch.Tensor) and table.dim() == 1 and table.shape[0] in _staged_counts():
         return _staged_counts()[table.shape[0]]                # a staged table: the form of its blocks
-    sizes = ", ".join(f"{k} ({v})" for k, v in _counts().items())
+    sizes = ", ".join(f"{k} ({v})" for k, v in _table_counts().items())
     raise ValueError(f"table must be a tensor of {sizes} entries (ntuple_table)")
 
 
@@ -186,8 +214,8 @@ def ntuple_parts(table) -> tuple:
         raise ValueError("a staged table has no parts of its own: ntuple_stages(table) gives its eight tables, ntuple_parts of one its parts")
     parts, at = [], 0
     for part in _learn_lib.ntuple_parts_of(ntuple_shape(table)):
-        parts.append(table[at:at + NTUPLE_SHAPES[part][2]])
-        at += NTUPLE_SHAPES[part][2]
+        parts.append(table[at:at + _learn_lib._PART_ENTRIES[part]])
+        at += _learn_lib._PART_ENTRIES[part]
     return tuple(parts)
 
 
@@ -207,7 +235,7 @@ def ntuple_step_sizes(coherence: torch.Tensor) -> torch.Tensor:
 
 
 def _sizes() -> str:
-    return " or ".join(f"{k} ({v})" for k, v in _counts().items())
+    return " or ".join(f"{k} ({v})" for k, v in _table_counts().items())
 
 
 def _coherence(coherence, table=None) -> torch.Tensor:
@@ -223,7 +251,7 @@ def _coherence(coherence, table=None) -> torch.Tensor:
 
 def _table(table, device) -> torch.Tensor:
     if (not isinstance(table, torch.Tensor) or table.dtype != torch.int32 or table.dim() != 1
-            or (table.shape[0] not in _counts() and table.shape[0] not in _staged_counts()) or table.device != device
+            or (table.shape[0] not in _table_counts() and table.shape[0] not in _staged_counts()) or table.device != device
             or not table.is_contiguous()):
         raise ValueError(f"table must be a contiguous int32 tensor of {_sizes()} entries, or a staged table, on {device} (ntuple_table)")
     return table
@@ -235,6 +263,8 @@ def _shaped(lib, entry: str, shape: str, staged: bool = False):
     any form the _staged twin with the C form id."""
     if staged:
         return getattr(lib, entry + "_staged"), (NTUPLE_FORM_IDS[shape],)
+    if shape in NTUPLE_FEATURE_FORMS:
+        return getattr(lib, entry + "_feature"), (NTUPLE_FEATURE_FORMS[shape],)
     if shape in NTUPLE_SUMS:
         return getattr(lib, entry + "_sum"), ()
     return getattr(lib, entry + "_shaped"), (NTUPLE_SHAPE_IDS[shape],)
@@ -324,6 +354,30 @@ def ntuple_value(source, table: torch.Tensor, L: Optional[int] = None, M: Option
           or not out.is_contiguous()):
         raise ValueError(f"out must be a contiguous float32 tensor of shape ({k},) on {device}")
     _value(a, b, k, int(L), int(M), table, out, device)
+    return out
+
+
+@torch.no_grad()
+def ntuple_feature_bins(source, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 [K, 9]: the nine bins a feature table is read at -- min(phi, 255) of holes, aggregate_height, max_height, bumpiness,
+    row_transitions, column_transitions, wells, rows_with_holes and hole_depth -- of K states, running or not
+    (tpl_ntuple_feature_bins).  `source` is an environment (its resident boards) or a pair (states_a, states_b) of int32 [K, 4]
+    planes on one GPU.  No host sync, and no allocation when `out` is given."""
+    if hasattr(source, "num_envs"):
+        k, device = _boards(source, "ntuple_feature_bins"), source.device
+        a, b = _state_ptrs(source)
+    else:
+        k, a, b = _planes(source, None, "source")
+        device = a.device
+        if not 1 <= k <= _MAX_BOARDS:
+            raise ValueError(f"ntuple_feature_bins takes 1 .. {_MAX_BOARDS} states")
+    if out is None:
+        out = torch.empty((k, NTUPLE_FEATURES), dtype=torch.uint8, device=device)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (k, NTUPLE_FEATURES) or out.device != device
+          or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous uint8 tensor of shape ({k}, {NTUPLE_FEATURES}) on {device}")
+    stream = torch._C._cuda_getCurrentRawStream(device.index)
+    check(_learn_lib.lib().tpl_ntuple_feature_bins(_ptr(a), _ptr(b), k, out.data_ptr(), stream))
     return out
 
 
@@ -454,6 +508,8 @@ class NTupleBeamPolicy:
         lib = _learn_lib.lib()
         if self.staged:
             entry, shape = lib.tpl_ntuple_beam_staged, (NTUPLE_FORM_IDS[self.shape],)
+        elif self.shape in NTUPLE_FEATURE_FORMS:
+            entry, shape = lib.tpl_ntuple_beam_feature, (NTUPLE_FEATURE_FORMS[self.shape],)
         else:
             entry, shape = (lib.tpl_ntuple_beam_sum, ()) if self.shape in NTUPLE_SUMS else (lib.tpl_ntuple_beam, (NTUPLE_SHAPE_IDS[self.shape],))
         check(entry(self._planes[0], self._planes[1], env.num_envs, env.L, env.M, *env.reward_params, self.gamma,
@@ -513,7 +569,14 @@ class NTupleLearner:
     as above, in one call for every form.  A stage sees only the states that fall in it, so each block learns from a share of the
     boards.  Temporal coherence has no staged form: coherent=True with a map is refused.
     start (None, or a plain table of `shape`): the table starts as a copy of it -- with a stage_map every stage does, which is
-    weight promotion from a trained plain table."""
+    weight promotion from a trained plain table.
+
+    shape="feat" or "3x3+feat": a feature table, alone or behind a 3x3 table (the module's docstring).  Steps 1 and 2 read it through
+    the _feature entries; step 3 is tpl_ntuple_update_trace_feature on the feature part and, for "3x3+feat", the 3x3 update on the
+    first part with the same errors.  Traces, symmetry and start= work as above; stage_map= and coherent=True are refused.  One `rate`
+    serves both parts of a sum.  A state adds to 10 entries of a feature table where it adds to about 107 of a 3x3 one, so the step of
+    V per unit of `rate` is about a tenth: alone, `rate` is EXPECTED to want roughly ten times a window table's.  That is arithmetic
+    on the step, not a measurement -- profiles/learner/README.md has what the sweep found."""
 
     def __init__(self, env, gamma: float = 0.99, rate: float = 8.0, epsilon: float = 0.1, seed: int = 0, depth: int = 1,
                  lam: float = 0.0, horizon: int = 1, symmetric: bool = False, coherent: bool = False, shape: str = "2x4",
@@ -523,6 +586,11 @@ class NTupleLearner:
             raise ValueError("NTupleLearner needs an auto-reset environment")
         self.env, self.rate = env, _finite("rate", rate)
         _entries(shape)
+        if shape in NTUPLE_FEATURE_FORMS:
+            if stage_map is not None:
+                raise ValueError(_NO_FEATURE_FORM.format(shape=shape, what="staged form (stage_map=)"))
+            if coherent is True:
+                raise ValueError(_NO_FEATURE_FORM.format(shape=shape, what="coherent update (coherent=True)"))
         self.shape = shape
         _unit("epsilon", epsilon), _finite("gamma", gamma), _count("seed", seed)
         self.lam, self.horizon = _unit("lam", lam), _horizon(horizon)
@@ -593,28 +661,44 @@ class NTupleLearner:
         ring_a, ring_b = self._ring[0].data_ptr(), self._ring[1].data_ptr()
         if self.coherent:
             _coherence(self.coherence, _table(self.table, env.device))   # a buffer of the other shape would be overrun
-        # the update, part by part: (C shape id, the part's table pointer, its coherence pointer) -- one part unless the table is a sum
+        # step 3 as a list of calls, each taking the ring's head: one per part of the table, each through the update entry of ITS kind --
+        # a window part the _shaped entry (coherent or not) with the part's C shape id, a feature part tpl_ntuple_update_trace_feature,
+        # which takes no shape; a staged table one call, whose entry launches the part updates itself
         staged = ntuple_is_staged(_table(self.table, env.device))
         if staged and self.coherent:
             raise ValueError("temporal coherence has no staged form (include/tpl_learn.h)")
-        form = NTUPLE_FORM_IDS[ntuple_shape(self.table)]
-        names = () if staged else _learn_lib.ntuple_parts_of(ntuple_shape(self.table))
-        parts = list(zip((NTUPLE_SHAPE_IDS[name] for name in names), (t.data_ptr() for t in ntuple_parts(self.table)),
-                         (c.data_ptr() for c in ntuple_parts(self.coherence)) if self.coherent else (None,) * len(names))) if names else []
+        form_name = ntuple_shape(self.table)
+        error, how = self._error.data_ptr(), (self.rate, self.decay, int(self.symmetric))
+
+        def ring(table_ptr, head):
+            return (ring_a, ring_b, n, self.slots, head, self.horizon, env.L, env.M, table_ptr)
+
+        updates = []
+        if staged:
+            whole, form = self.table.data_ptr(), NTUPLE_FORM_IDS[form_name]
+            updates.append(lambda head: lib.tpl_ntuple_update_trace_staged(*ring(whole, head), error, *how, form, stream))
+        else:
+            names = _learn_lib.ntuple_parts_of(form_name)
+            if self.coherent and "feat" in names:
+                raise ValueError(_NO_FEATURE_FORM.format(shape=form_name, what="coherent update"))
+            buffers = ntuple_parts(self.coherence) if self.coherent else (None,) * len(names)
+            for name, part, buffer in zip(names, ntuple_parts(self.table), buffers):
+                t = part.data_ptr()
+                if name == "feat":
+                    updates.append(lambda head, t=t: lib.tpl_ntuple_update_trace_feature(*ring(t, head), error, *how, stream))
+                elif self.coherent:
+                    updates.append(lambda head, t=t, c=buffer.data_ptr(), s=NTUPLE_SHAPE_IDS[name]:
+                                   lib.tpl_ntuple_update_coherent_shaped(*ring(t, head), c, error, *how, s, stream))
+                else:
+                    updates.append(lambda head, t=t, s=NTUPLE_SHAPE_IDS[name]:
+                                   lib.tpl_ntuple_update_trace_shaped(*ring(t, head), error, *how, s, stream))
         for _ in range(steps):
             kept = self._kept
             self.policy.act(out=self._action, score=self._score, after=self._next, step=self.steps)
             _value(kept[0], kept[1], n, env.L, env.M, self.table, self._kept_value, env.device)
             torch.sub(self._score, self._kept_value, out=self._error)
-            if staged:                                         # one call: the entry launches the part updates itself
-                check(lib.tpl_ntuple_update_trace_staged(ring_a, ring_b, n, self.slots, self._head, self.horizon, env.L, env.M,
-                                                         self.table.data_ptr(), self._error.data_ptr(), self.rate, self.decay,
-                                                         int(self.symmetric), form, stream))
-            for shape, table, coherence in parts:
-                ring = (ring_a, ring_b, n, self.slots, self._head, self.horizon, env.L, env.M, table)
-                tail = (self._error.data_ptr(), self.rate, self.decay, int(self.symmetric), shape, stream)
-                check(lib.tpl_ntuple_update_coherent_shaped(*ring, coherence, *tail) if self.coherent
-                      else lib.tpl_ntuple_update_trace_shaped(*ring, *tail))
+            for update in updates:
+                check(update(self._head))
             env.step_into(self._action, self._reward, self._done)
             self._head = (self._head + 1) % self.slots
             self.steps += 1

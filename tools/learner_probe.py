@@ -105,6 +105,13 @@ Parts:
               win), then a staged 3 x 3 table under the maps moves=2, moves=4 and lines=2 x moves=4, each trained from zero and each
               promoted from the baseline's table and trained on for the same budget; every final table played at one ply, at depth 2
               and at beam (3, 8)
+    ntuple_feature  feature tables ("feat", and "3x3+feat", a 3 x 3 table with a feature table behind it) beside the 3 x 3 table: at 2^20
+              boards (part ntuple_shape's) the value, act, search, the beam at (3, 8) and (6, 16) and one learner step of all three in the
+              same alternated rounds, "feat" as a ratio to the 3 x 3 twin and "3x3+feat" as a ratio to the two parts' times added; the
+              update kernel alone at horizons 1 and 4 beside the 3 x 3 update
+    ntuple_feature_sweep  part ntuple_shape_sweep's set-up unchanged: the 3 x 3 TD(0) run at rate 16 again (it must reproduce win for
+              win) and the classical weights at one ply; "feat" as TD(0) at rates 2 .. 512 and "3x3+feat" at rates 2 .. 16; the best of
+              each with symmetric updates; the best of each played at depth 2 and at beam (3, 8)
     ntuple_shape_ab  --parent LIB: the nine 2 x 4 n-tuple kernels of another build of the learner library against this tree's, both
               loaded into one process: the outputs of the six entries compared byte for byte on the ring of part ntuple_shape
               at 2^18 boards, then each entry timed in five rounds of the parent against itself and five of the parent against
@@ -125,7 +132,8 @@ PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600, "priority": 600
          "heuristic": 600, "search": 900, "beam": 900, "ntuple": 900,
          "ntuple_search": 900, "ntuple_trace": 600, "ntuple_trace_sweep": 1100, "ntuple_coherent": 600,
          "ntuple_coherent_sweep": 1700, "ntuple_shape": 600, "ntuple_shape_sweep": 1100, "ntuple_beam": 1100,
-         "ntuple_sum": 600, "ntuple_sum_sweep": 600, "ntuple_stage": 600, "ntuple_stage_sweep": 900}
+         "ntuple_sum": 600, "ntuple_sum_sweep": 600, "ntuple_stage": 600, "ntuple_stage_sweep": 900,
+         "ntuple_feature": 600, "ntuple_feature_sweep": 900}
 SCATTERED_ATOMICS = 0.08e12                                 # 64 lanes of a wave adding into 64 rows (float adds; integer adds unmeasured)
 VALU_CYCLES, SIMDS, CLOCK_HZ = 3.3, 1024, 2.4e9           # the move's instruction mix, 256 CUs x 4, the clock
 
@@ -1948,6 +1956,153 @@ def part_ntuple_stage_sweep(eval_steps=12288):
     return dict(part="ntuple_stage_sweep", boards=4096, seed=11, pool=1 << 16, pool_seed=7, reward=list(NTUPLE_LARGE_REWARD), gamma=1.0,
                 epsilon=0.05, rate=16.0, eval_steps=eval_steps, baseline=baseline, baseline_reproduced_win_for_win=reproduced,
                 baseline_trained_on=carried, hand_made_features_win_rate=0.99925, runs=runs)
+
+
+NTUPLE_FEATURE_FORMS = ("feat", "3x3+feat")
+
+
+def part_ntuple_feature(rounds=5, reps=10, n=1 << 20):
+    """Feature tables beside the 3 x 3 table on part ntuple_shape's boards."""
+    import numpy as np
+    import torch
+    import tetris_piclim as T
+    m = T._learn_lib
+    L, check = m.lib(), m.check
+    stream = torch._C._cuda_getCurrentRawStream(0)
+    slots, head = 17, 16
+    names = ("3x3",) + NTUPLE_FEATURE_FORMS
+    kernels = ("ntuple3_value_kernel", "ntuple_feature_value_kernel", "ntuple_feature3_value_kernel", "ntuple3_act_kernel",
+               "ntuple_feature_act_kernel", "ntuple_feature3_act_kernel")
+    out = dict(part="ntuple_feature", boards=n, gamma=1.0, epsilon=0.05, learner_rate=1.0,
+               static_valu={k: _static_valu(k, m.build_library()) for k in kernels})
+    env, ring = _shape_ring(T, n, slots)                         # the environment stands at the ring's newest slot
+    whole = np.random.default_rng(0).integers(-(1 << 20), (1 << 20) + 1, m.NTUPLE_ENTRIES_3X3_FEAT).astype(np.int32)
+    table = {"3x3+feat": torch.from_numpy(whole).to("cuda:0")}
+    table["3x3"], table["feat"] = (p.clone() for p in T.ntuple_parts(table["3x3+feat"]))             # the twins: its parts, on their own
+    bins = T.ntuple_feature_bins(env)[:4096].cpu().numpy()
+    out["distinct_bins_per_feature_of_4096_boards"] = [int(np.unique(bins[:, j]).size) for j in range(9)]
+    # the update kernel alone, beside the 3 x 3 update, on the ring
+    error = torch.empty(n, dtype=torch.float32, device="cuda:0").normal_()
+    ra, rb = ring[0].data_ptr(), ring[1].data_ptr()
+    scratch = {name: table[name].clone() for name in ("3x3", "feat")}
+    update = {}
+    for horizon in (1, 4):
+        for symmetric in (0, 1):
+            args = (ra, rb, n, slots, head, horizon, 10, 40)
+            tail = (error.data_ptr(), 100.0, 0.9, symmetric)
+            calls = {"feat": lambda a=args, t=tail: check(L.tpl_ntuple_update_trace_feature(*a, scratch["feat"].data_ptr(), *t, stream)),
+                     "3x3": lambda a=args, t=tail: check(L.tpl_ntuple_update_trace_shaped(*a, scratch["3x3"].data_ptr(), *t, 1, stream))}
+            times = {k: [] for k in calls}
+            for _ in range(rounds):
+                for k, fn in calls.items():
+                    times[k].append(_timed(fn, reps))
+            med = {k: sorted(ts)[rounds // 2] for k, ts in times.items()}
+            update[f"h{horizon}" + ("_symmetric" if symmetric else "")] = {
+                "feat_us": _spread(times["feat"]), "3x3_us": _spread(times["3x3"]), "feat_over_3x3": round(med["feat"] / med["3x3"], 4)}
+    out["update"] = update
+    del ring, scratch
+    action, second = (torch.empty(n, dtype=torch.uint8, device="cuda:0") for _ in range(2))
+    score, value = (torch.empty(n, dtype=torch.float32, device="cuda:0") for _ in range(2))
+    after = tuple(torch.empty((n, 4), dtype=torch.int32, device="cuda:0") for _ in range(2))
+    variants = {}
+    for name in names:
+        act = T.NTuplePolicy(env, table[name], gamma=1.0, epsilon=0.05, seed=11)
+        search = T.NTuplePolicy(env, table[name], gamma=1.0, epsilon=0.05, seed=11, depth=2)
+        beams = {shape: T.NTupleBeamPolicy(env, table[name], *shape, gamma=1.0) for shape in ((3, 8), (6, 16))}
+        variants[("value", name)] = (lambda t=table[name]: T.ntuple_value(env, t, out=value), reps)
+        variants[("act", name)] = (lambda p=act: p.act(out=action, score=score, after=after, value=value, step=3), reps)
+        variants[("search", name)] = (lambda p=search: p.act(out=action, score=score, after=after, value=value, step=3, second=second),
+                                      max(reps // 3, 2))
+        variants[("beam_3x8", name)] = (lambda p=beams[(3, 8)]: p.act(out=action), 3)
+        variants[("beam_6x16", name)] = (lambda p=beams[(6, 16)]: p.act(out=action), 1)
+    order = sorted(variants)                                     # an entry's three tables next to each other in every round
+    times = {k: [] for k in order}
+    for _ in range(rounds):                                      # alternate the variants round by round
+        for k in order:
+            fn, count = variants[k]
+            times[k].append(_timed(fn, count, warmup=1))
+    # one learner step -- act, value, subtract, update (a sum form: two update calls), environment step; the learners step the
+    # environment, so they come last
+    learners = {name: T.NTupleLearner(env, gamma=1.0, rate=1.0, epsilon=0.05, seed=11, shape=name) for name in names}
+    for name in names:
+        learners[name].table.copy_(table[name])
+        learners[name].train(3)
+        times[("learner_step", name)] = []
+    for _ in range(rounds):
+        for name in names:
+            times[("learner_step", name)].append(_timed(lambda l=learners[name]: l.train(1), reps, warmup=1))
+    med = {k: sorted(ts)[rounds // 2] for k, ts in times.items()}
+    row = {}
+    for what in sorted({k[0] for k in times}):
+        row[what] = {name + "_us": _spread(times[(what, name)]) for name in names}
+        row[what]["feat_over_3x3"] = round(med[(what, "feat")] / med[(what, "3x3")], 3)
+        row[what]["3x3+feat_over_the_parts_together"] = round(med[(what, "3x3+feat")] / (med[(what, "3x3")] + med[(what, "feat")]), 3)
+    env.terminate()
+    out["kernel"] = dict(rounds=rounds, launches_per_timing=reps, search_launches_per_timing=max(reps // 3, 2), beam_launches_per_timing=[3, 1],
+                         row=row)
+    return out
+
+
+def part_ntuple_feature_sweep(eval_steps=12288):
+    """Part ntuple_shape_sweep's set-up unchanged; its 3 x 3 TD(0) run at rate 16 again, the classical weights, then the feature forms."""
+    import numpy as np
+    import torch
+    import tetris_piclim as T
+    gen_env = T.BatchedTetris(10, 40, 64, device="cuda:0", seed=7)
+    big = gen_env.carved_configs(1 << 16, seed=7)
+    gen_env.terminate()
+
+    def result(r):
+        p = r["win_rate"]
+        return dict(episodes=r["episodes"], wins=r["wins"], win_rate=round(p, 5),
+                    standard_error=round((p * (1 - p) / max(r["episodes"], 1)) ** 0.5, 6))
+
+    def learn(keep=False, **kw):
+        env = T.BatchedTetris(10, 40, 4096, device="cuda:0", seed=11, auto_reset=True, reward=NTUPLE_LARGE_REWARD, config_pool=big)
+        learner = T.NTupleLearner(env, seed=11, gamma=1.0, epsilon=0.05, **kw)
+        got = dict(kw, zero_table=result(learner.evaluate(eval_steps)), trained=[])
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for steps in (10000, 30000):
+            learner.train(steps)
+            got["trained"].append(dict(steps=learner.steps, **result(learner.evaluate(eval_steps))))
+        got.update(seconds=round(time.perf_counter() - t0, 2), entries_in_use=[int((p != 0).sum()) for p in T.ntuple_parts(learner.table)],
+                   largest_entry=int(learner.table.abs().max()))
+        table = learner.table.clone() if keep else None
+        env.terminate()
+        print(json.dumps(got), file=sys.stderr, flush=True)      # progress: a long part must not stay silent
+        return got, table
+
+    baseline = learn(shape="3x3", rate=16.0)[0]
+    reproduced = (baseline["trained"][-1]["wins"], baseline["trained"][-1]["episodes"]) == (1467276, 1469796)   # sweep_ntuple_shape.log
+    classical = np.array([4, 100, -100, -8, -1, 0, -2, -3, -6, -3, -2, -1], np.float32) * np.float32(0.1)
+    env = T.BatchedTetris(10, 40, 1 << 16, device="cuda:0", seed=11, auto_reset=True, reward=(0.0, 1.0, 0.0), config_pool=big)
+    got = T.evaluate_heuristic(env, classical, None, 640)
+    e, wins = int(got["episodes"][0]), int(got["wins"][0])
+    hand = result(dict(episodes=e, wins=wins, win_rate=wins / max(e, 1)))
+    env.terminate()
+    out = dict(part="ntuple_feature_sweep", boards=4096, seed=11, pool=1 << 16, pool_seed=7, reward=list(NTUPLE_LARGE_REWARD), gamma=1.0,
+               epsilon=0.05, eval_steps=eval_steps, baseline=baseline, baseline_reproduced_win_for_win=reproduced,
+               classical_weights_one_ply=hand, forms={})
+    rates = {"feat": (2.0, 4.0, 8.0, 16.0, 32.0, 64.0, 128.0, 256.0, 512.0), "3x3+feat": (2.0, 4.0, 8.0, 16.0)}
+    for shape in NTUPLE_FEATURE_FORMS:
+        runs, tables = [], []
+        for rate in rates[shape]:
+            got, table = learn(keep=True, shape=shape, rate=rate)
+            runs.append(got)
+            tables.append(table)
+        at = max(range(len(runs)), key=lambda i: runs[i]["trained"][-1]["win_rate"])
+        symmetric, sym_table = learn(keep=True, shape=shape, rate=rates[shape][at] / 2, symmetric=True)
+        same_rate, _ = learn(shape=shape, rate=rates[shape][at], symmetric=True)
+        env = T.BatchedTetris(10, 40, 4096, device="cuda:0", seed=11, auto_reset=True, reward=NTUPLE_LARGE_REWARD, config_pool=big)
+        player = T.NTupleLearner(env, seed=11, gamma=1.0, epsilon=0.05, shape=shape)
+        player.table.copy_(tables[at])
+        deep = dict(depth_1=result(player.evaluate(eval_steps)), depth_2=result(player.evaluate(eval_steps, depth=2)),
+                    beam_3x8=result(player.evaluate(eval_steps, depth=3, width=8)))
+        env.terminate()
+        out["forms"][shape] = dict(best=runs[at], best_played=deep, best_symmetric_at_half_the_rate=symmetric,
+                                   best_symmetric_at_the_same_rate=same_rate, runs=runs)
+    return out
 
 
 def part_ntuple_shape_ab(parent, rounds=5, reps=20, n=1 << 18):
