@@ -106,8 +106,10 @@ __global__ __launch_bounds__(kThreads) void step_kernel(const StepArgs p) {
         const int64_t wave_first = (int64_t)blockIdx.x * (kThreads * kBpl) + (int64_t)k * kThreads +
                                    (int64_t)(__builtin_amdgcn_readfirstlane((int)threadIdx.x) & ~63);
         clock[k] = p.clock[wave_first >> kClockShift];
-        a0[k] = load_int(p.act0, p.int_shift, j);
-        a1[k] = kActionForm ? 0u : load_int(p.act1, p.int_shift, j);
+        // a streaming load: an action row is read once, and a run's rows together are many times the Infinity Cache, in
+        // which the boards and the pool records should stay (0.14 us on the launch at 2^20 boards, profiles/r07_step)
+        a0[k] = load_int<true>(p.act0, p.int_shift, j);
+        a1[k] = kActionForm ? 0u : load_int<true>(p.act1, p.int_shift, j);
     }
     if (threadIdx.x < 32) s_shape[threadIdx.x] = kShapeTable[threadIdx.x];
     if (threadIdx.x < 4) s_stat[threadIdx.x] = 0;
@@ -257,11 +259,28 @@ __global__ __launch_bounds__(kThreads) void step_kernel(const StepArgs p) {
     }
     // the groups' next step.  Every lane stores (the 32 lanes of a group write the same value to the same word: one
     // 16-byte write per wave): a branch on the lane index here would put a divergent region, and with it the
-    // compiler's full memory wait, between the state stores.
+    // compiler's full memory wait, between the state stores.  With an even number of boards per lane ONE store
+    // instruction carries the clocks of two of the lane's boards -- lanes 0-31 write the two groups of board k, lanes
+    // 32-63 those of board k + 1, the same words with the same values -- which halves the wave's clock stores
+    // (0.05 us on the launch at 2^20 boards, profiles/r07_step).
+    // (The pair's clocks are named by constant indices: `clock[k + (lane >> 5)]` in a loop makes the array an indexed one,
+    // which the compiler then keeps in LDS -- and the grid is no longer resident at once: 38 us per step.)
+    if constexpr (kBpl % 2 == 0) {
+        static_assert(kBpl == 2 || kBpl == 4, "one call of store_pair per two boards of a lane");
+        const int lane = threadIdx.x & 63;
+        const int64_t group_first = (int64_t)blockIdx.x * (kThreads * kBpl) + (threadIdx.x & ~63) + ((lane >> 4) & 1) * kClockGroup;
+        const auto store_pair = [&](int k, unsigned long long even, unsigned long long odd) {
+            const int64_t i = group_first + (int64_t)(k + (lane >> 5)) * kThreads;
+            p.clock[i >> kClockShift] = (lane >> 5 ? odd : even) + 1u;
+        };
+        store_pair(0, clock[0], clock[1]);
+        if constexpr (kBpl == 4) store_pair(2, clock[2], clock[3]);
+    } else {
 #pragma unroll
-    for (int k = 0; k < kBpl; ++k) {
-        const int64_t i = base + (int64_t)k * kThreads;
-        p.clock[i >> kClockShift] = clock[k] + 1u;
+        for (int k = 0; k < kBpl; ++k) {
+            const int64_t i = base + (int64_t)k * kThreads;
+            p.clock[i >> kClockShift] = clock[k] + 1u;
+        }
     }
 
     TPL_STAMP(4);

@@ -60,11 +60,13 @@ inline StepArgs make_args(const tpl_env* e) {
 // Element i of an array of 1-, 4- or 8-byte little-endian integers (1 << shift bytes each), as its low 32 bits,
 // without a branch on the width: the aligned word that holds the element's first byte is read and shifted.  (For
 // one-byte elements that word may reach up to three bytes past the end of the array -- never past the 4-byte unit
-// the last element is in.)
+// the last element is in.)  kStream marks the load as streaming (non-temporal): for a row that is read once and never
+// again, so that its lines do not push out of the caches what the next step reads again.
+template <bool kStream = false>
 __device__ __forceinline__ uint32_t load_int(const void* p, uint32_t shift, int64_t i) {
     const char* q = (const char*)p + (i << shift);
     const uint32_t skew = (uint32_t)((uintptr_t)q & 3u);
-    const uint32_t w = *(const uint32_t*)(q - skew);
+    const uint32_t w = kStream ? __builtin_nontemporal_load((const uint32_t*)(q - skew)) : *(const uint32_t*)(q - skew);
     const uint32_t v = w >> (8u * skew);
     return shift == 0u ? (v & 0xFFu) : v;
 }
