@@ -329,6 +329,51 @@ int tpl_placement_beam(const void* plane_a, const void* plane_b, int64_t n, int3
                        int64_t boards_per_member, int32_t depth, int32_t width, uint8_t* action, uint8_t* plan,
                        float* score, void* stream);
 
+/* A whole-game beam solver for prescribed configurations.  tpl_placement_beam plans from an environment state, which shows at most
+ * twelve pieces.  A prescribed CONFIGURATION is a board and the whole list of its pieces, so the same beam can run through all of a
+ * game: tpl_placement_solve does, stops at the first ply at which it sees a win, and returns the moves.
+ *
+ * For a configuration -- rows[20] (16-bit words, bit x = column x, row 0 = top) and pieces[M + 1] --, one weight row w[12] and a
+ * width W in [1, TPL_BEAM_MAX_WIDTH], in tpl_placement_beam's terms:
+ *   Beam_0 is the ROOT alone, c = 0, empty path: the state a full reset deals from the configuration -- 0 lines, 0 moves, running.
+ *   For ply j = 1 .. M: the current piece of every running node of Beam_{j-1} is pieces[j - 1] & 7, TAKEN FROM THE LIST (a popped
+ *     window is good for its twelve entries only; the features never read the entries behind the current piece, and they are no part
+ *     of this rule).  The CANDIDATES are listed exactly as tpl_placement_beam lists them: over the nodes in their stored order, a
+ *     finished node gives itself, a running node one child per distinct placement b of the current piece in ascending b, each
+ *     move_board(node, b) as tpl_afterstates makes it; with n the rows it cleared,
+ *       psi = (c + n, won, lost, features 3..11 of the child's board)      -- c + n is at most 253 and converts exactly
+ *       value = the score rule on psi: left to right in float32, every product and sum rounded once, never fused.
+ *     Candidates are ordered by (value descending, candidate index ascending); -0 and +0 tie.
+ *     best_value[j - 1] = the value of the candidate that comes first in that order.
+ *     STOP ON A WIN: if ANY candidate of ply j is won -- all candidates are looked at, BEFORE the cut, so a won candidate is never lost
+ *     to the cut and j is the first ply at which this beam sees a win -- the search ends: solved = 1, solution_len = j, and the
+ *     solution is the path of the won candidate that comes first in the order.
+ *     Otherwise Beam_j = the min(W, count) best candidates STORED IN CANDIDATE ORDER (the stable compaction).  If no node of Beam_j
+ *     runs, the search ends with solved = 0, solution_len = 0 and a path of 255s.
+ *   At ply M every child is finished (the move limit), so the search ends by then.
+ *   best_value is +0 beyond the plies that were run.
+ * solved = 0 MEANS THAT THIS BEAM, WITH THESE WEIGHTS AT THIS WIDTH, FOUND NO WIN.  IT DOES NOT MEAN THAT THE CONFIGURATION HAS NONE:
+ * nothing here proves a configuration unwinnable.
+ * Consequences:
+ *   1. Playing the solution move by move from the configuration ends won after exactly solution_len moves, on any correct
+ *      implementation of the game.
+ *   2. For j <= min(12, plies run) and an environment freshly reset to the configuration, best_value[j - 1] is the score of
+ *      tpl_placement_beam at depth j and width W, bit for bit: the same nodes, the same candidates, and the best candidate is always
+ *      kept.  Where the candidate that comes first at the winning ply j <= 12 is itself won, the beam's plan[0 .. j) is the solution.
+ *   3. At any fixed W the result is a function of the inputs alone; nothing is written but the outputs.
+ * THE FINITENESS CAVEAT of the weights is tpl_placement_act's.  The piece ids cannot be checked on the device: they are masked to
+ * three bits as move_board masks them (7 plays O's entry); the caller checks them where it can (load_configs' rule: 0..6).
+ *
+ * One kernel, a workgroup per configuration in tpl_placement_beam's frame (csrc/learn/solve.hip); the paths are kept as a tape of
+ * (parent, placement) per ply and node in LDS and walked back at the winning ply.  rows i16 [n][20] and pieces u8 [n][M + 1] are read;
+ * solved u8 [n], solution_len i32 [n], actions u8 [n][M] (the solution's placements b = 10 r + l, 255 behind the end) and best_value
+ * f32 [n][M] (optional; an output that is not given is not written) are written in full.
+ * Refused before any HIP call: n < 1, n >= 2^31 (the grid), a NULL rows, pieces, weights, solved, solution_len or actions, weights
+ * not 16-byte aligned, solution_len or best_value not 4-byte aligned, rows not 2-byte aligned, L outside [1, 250] or M outside
+ * [1, 254], width outside [1, TPL_BEAM_MAX_WIDTH]. */
+int tpl_placement_solve(const int16_t* rows, const uint8_t* pieces, int64_t n, int32_t L, int32_t M, const float* weights,
+                        int32_t width, uint8_t* solved, int32_t* solution_len, uint8_t* actions, float* best_value, void* stream);
+
 /* An n-tuple afterstate value function, its placement policy and its temporal-difference update (csrc/learn/ntuple.hip).
  *
  * Table: TPL_NTUPLE_ENTRIES = 8 * 153 * 256 + 1024 = 314,368 int32 entries (1,257,472 bytes), 16-byte aligned, in units of 2^-16:

@@ -21,7 +21,7 @@ from ._lib import TplError, _hipcc
 _LEARN_CSRC = os.path.join(_lib._CSRC, "learn")
 LEARN_LIB_PATH = os.path.join(_lib._LIBDIR, "libtpl_learn.so")
 _UNITS = [os.path.join(_LEARN_CSRC, f) for f in ("replay.hip", "pack.hip", "priority.hip", "afterstates.hip",
-                                                      "beam.hip", "ntuple.hip", "ntuple_beam.hip", "heuristic.hip")]
+                                                      "beam.hip", "solve.hip", "ntuple.hip", "ntuple_beam.hip", "heuristic.hip")]
 
 # entry points declared in include/tpl_learn.h (tests check that the .so exports every one of them)
 LEARN_SYMBOLS = [
@@ -37,7 +37,7 @@ LEARN_SYMBOLS = [
     "tpl_ntuple_value_staged", "tpl_ntuple_act_staged", "tpl_ntuple_search_staged", "tpl_ntuple_beam_staged",
     "tpl_ntuple_update_trace_staged",
     "tpl_ntuple_value_feature", "tpl_ntuple_act_feature", "tpl_ntuple_search_feature", "tpl_ntuple_beam_feature",
-    "tpl_ntuple_update_trace_feature", "tpl_ntuple_feature_bins",
+    "tpl_ntuple_update_trace_feature", "tpl_ntuple_feature_bins", "tpl_placement_solve",
 ]
 NSTEP_MAX = 16
 BEAM_MAX_DEPTH, BEAM_MAX_WIDTH = 12, 64
@@ -144,6 +144,8 @@ def lib() -> C.CDLL:
     L.tpl_placement_act.argtypes = [vp, vp, i64, i32, i32, vp, i64, vp, vp, vp]
     L.tpl_placement_search.argtypes = [vp, vp, i64, i32, i32, vp, i64, vp, vp, vp, vp]
     L.tpl_placement_beam.argtypes = [vp, vp, i64, i32, i32, vp, i64, i32, i32, vp, vp, vp, vp]
+    L.tpl_placement_solve.argtypes = [vp, vp, i64, i32, i32, vp, i32, vp, vp, vp, vp, vp]
+    L.tpl_placement_solve.restype = i32
     f32 = C.c_float
     L.tpl_ntuple_value.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp]
     L.tpl_ntuple_act.argtypes = [vp, vp, i64, i32, i32, f32, f32, f32, f32, vp, f32, u64, u64, vp, vp, vp, vp, vp, vp]
@@ -553,6 +555,178 @@ def beam_select(values, width: int) -> np.ndarray:
         raise ValueError(f"width must be an integer in [1, {BEAM_MAX_WIDTH}]")
     order = np.argsort(-(v + np.float32(0.0)), kind="stable")  # x + 0 makes -0 a +0; stable: the lower index first among equals
     return np.sort(order[:int(width)]).astype(np.int64)
+
+
+# ------------------------------------------------------------------------------------------------ the whole-game solver
+# The rule of tpl_placement_solve (include/tpl_learn.h) on the host, from the ROW form of a board: a move on row masks out of the
+# shape query's row patterns, board_features, placement_score and the order of beam_select.  The device works on column words
+# (csrc/learn/solve.hip, csrc/tpl_device.h) -- the two share nothing.
+SOLVE_MAX_MOVES = 254
+STATE_RUNNING, STATE_WON, STATE_LOST_LIMIT, STATE_LOST_TOPOUT = 0, 1, 2, 3
+_shape_tables = None
+
+
+def _solve_shape_tables():
+    """(height [8, 4], width [8, 4], row pattern [8, 4, 4], lowest cell of each piece column [8, 4, 4]) of shape table entry
+    [piece][rotations & 3], through the environment library's host shape query; row 7 ("none") is O's."""
+    global _shape_tables
+    if _shape_tables is None:
+        h, w = np.zeros((8, 4), np.int64), np.zeros((8, 4), np.int64)
+        mask, low = np.zeros((8, 4, 4), np.int64), np.zeros((8, 4, 4), np.int64)
+        for p in range(8):
+            for r in range(4):
+                hh, ww, masks, topo = _lib.shape_info(min(p, 6), r)
+                h[p, r], w[p, r] = hh, ww
+                mask[p, r, :hh], low[p, r, :ww] = masks, topo
+        _shape_tables = (h, w, mask, low)
+    return _shape_tables
+
+
+def host_moves(rows, piece, rotations, location, L: int, M: int, lines, moves):
+    """Tetris.move(rotations, location) with `piece` on K running boards in row form (uint16 [K, 20], bit x = column x, row 0 = top;
+    the rest [K]): the right clamp, the drop from the column tops under the piece, the top-out (board and moves stay), the lock, the
+    full-row test over the piece's rows, the compaction, then won (rows were cleared and lines >= L) before the move limit
+    (moves >= M).  Returns (rows uint16 [K, 20], cleared, lines, moves, state) -- state 0 running, 1 won, 2 lost at the limit,
+    3 topped out."""
+    H, W_, MASK, LOW = _solve_shape_tables()
+    rows = np.array(rows, dtype=np.uint16).reshape(-1, 20).astype(np.int64)
+    k = rows.shape[0]
+    piece, rot = np.broadcast_to(np.asarray(piece, np.int64) & 7, (k,)), np.broadcast_to(np.asarray(rotations, np.int64) & 3, (k,))
+    lines, moves = np.broadcast_to(np.asarray(lines, np.int64), (k,)).copy(), np.broadcast_to(np.asarray(moves, np.int64), (k,)).copy()
+    h, w = H[piece, rot], W_[piece, rot]
+    loc = np.minimum(np.broadcast_to(np.asarray(location, np.int64), (k,)), 10 - w)
+    at = np.arange(k)
+    cell = (rows[:, :, None] >> np.arange(10)) & 1
+    top = np.where(cell.any(axis=1), cell.argmax(axis=1), 20)                       # [K, 10]: the top-most filled row, 20 if none
+    delta = np.full(k, 1 << 20, np.int64)
+    for c in range(4):
+        d = top[at, np.minimum(loc + c, 9)] - LOW[piece, rot, c]
+        delta = np.where(c < w, np.minimum(delta, d), delta)
+    drop = delta - 1
+    ok = drop >= 0
+    cleared_row = np.zeros((k, 20), bool)
+    for i in range(4):
+        put = ok & (i < h)
+        r = np.where(put, drop + i, 0)
+        rows[at, r] |= np.where(put, MASK[piece, rot, i] << loc, 0)
+    for i in range(4):
+        put = ok & (i < h)
+        r = np.where(put, drop + i, 0)
+        full = put & (rows[at, r] == 0x3FF)
+        cleared_row[at[full], r[full]] = True
+    n = cleared_row.sum(axis=1)
+    order = np.argsort(~cleared_row, axis=1, kind="stable")                        # the cleared rows first, the others in order
+    rows = np.take_along_axis(rows, order, axis=1)
+    rows[np.arange(20)[None, :] < n[:, None]] = 0
+    moves += ok
+    lines += n
+    won = ok & (n > 0) & (lines >= L)
+    limit = ok & ~won & (moves >= M)
+    state = np.where(~ok, STATE_LOST_TOPOUT, np.where(won, STATE_WON, np.where(limit, STATE_LOST_LIMIT, STATE_RUNNING)))
+    return rows.astype(np.uint16), n, lines, moves, state
+
+
+def _first_in_order(values) -> int:
+    """The index of the candidate that comes first under (value descending, index ascending; -0 and +0 tie)."""
+    v = np.asarray(values, dtype=np.float32) + np.float32(0.0)
+    return int(np.argmax(v == v.max()))
+
+
+def placement_solve(rows, pieces, L: int, M: int, weights, width: int, max_width: int = BEAM_MAX_WIDTH, chunk: int = 1 << 14):
+    """The rule of tpl_placement_solve (include/tpl_learn.h) for n configurations: rows uint16 [n, 20] (bit x = column x), pieces
+    [n, M + 1] (masked to three bits), one weight row [12], a width in [1, max_width].  The placement beam run through the whole
+    piece list: ply j plays pieces[:, j - 1]; the search ends at the first ply at which ANY candidate is won, before the cut, with the
+    path of the won candidate that comes first in the rule's order, or unsolved once no node of the beam runs.  Returns
+    (solved uint8 [n], solution_len int32 [n], actions uint8 [n, M] padded with 255, best_value float32 [n, M], +0 beyond the
+    plies run) in the C layout.  solved = 0 means that this beam found no win, not that there is none.
+    `max_width` is for the test that compares a beam wide enough to keep everything with an exhaustive search; the kernel's limit
+    is BEAM_MAX_WIDTH.  `chunk` bounds how many candidates are moved and counted at once."""
+    L, M = int(L), int(M)
+    if not (1 <= L <= 250 and 1 <= M <= SOLVE_MAX_MOVES):
+        raise ValueError(f"L and M must be in [1, 250] and [1, {SOLVE_MAX_MOVES}]")
+    if isinstance(width, bool) or int(width) != width or not 1 <= int(width) <= int(max_width):
+        raise ValueError(f"width must be an integer in [1, {int(max_width)}]")
+    width = int(width)
+    rows = np.asarray(rows)
+    rows = (rows.view(np.uint16) if rows.dtype == np.int16 else rows.astype(np.uint16)).reshape(-1, 20)
+    n = rows.shape[0]
+    pieces = np.asarray(pieces).astype(np.int64) & 7
+    if n < 1 or pieces.shape != (n, M + 1):
+        raise ValueError(f"rows must be [n, 20] and pieces [n, {M + 1}] with n >= 1")
+    w = np.asarray(weights, dtype=np.float32).reshape(-1)
+    if w.shape != (NUM_FEATURES,):
+        raise ValueError("weights must be one row of 12")
+    placements = [np.flatnonzero(canonical_actions(p, np.arange(NUM_ACTIONS)) == np.arange(NUM_ACTIONS)) for p in range(8)]
+    solved, length = np.zeros(n, np.uint8), np.zeros(n, np.int32)
+    actions, best_value = np.full((n, M), NO_SECOND, np.uint8), np.zeros((n, M), np.float32)
+    # a beam: the nodes' rows, lines, moves, state and value in stored order; tape[j] = (parent's place, placement) of Beam_{j+1}
+    beams = [dict(rows=rows[s:s + 1].copy(), lines=np.zeros(1, np.int64), moves=np.zeros(1, np.int64),
+                  state=np.zeros(1, np.int64), value=np.zeros(1, np.float32), tape=[]) for s in range(n)]
+    active = list(range(n))
+    for ply in range(M):
+        # every child of every running node of every configuration still searched, in one batch
+        cfg, place, first, p_rows, p_lines, p_moves, total = [], [], {}, [], [], [], 0
+        for s in active:                                        # every active configuration has a running node
+            run = np.flatnonzero(beams[s]["state"] == STATE_RUNNING)
+            b = placements[pieces[s, ply]]
+            node = np.repeat(run, b.size)                       # node by node, ascending b: the candidates' order
+            first[s] = total
+            total += node.size
+            cfg.append(np.full(node.size, s)), place.append(np.tile(b, run.size))
+            p_rows.append(beams[s]["rows"][node]), p_lines.append(beams[s]["lines"][node]), p_moves.append(beams[s]["moves"][node])
+        cfg, place = np.concatenate(cfg), np.concatenate(place)
+        p_rows, p_lines, p_moves = np.concatenate(p_rows), np.concatenate(p_lines), np.concatenate(p_moves)
+        c_rows, c_lines, c_moves = np.zeros((total, 20), np.uint16), np.zeros(total, np.int64), np.zeros(total, np.int64)
+        c_state, c_value = np.zeros(total, np.int64), np.zeros(total, np.float32)
+        for lo in range(0, total, chunk):
+            hi = min(total, lo + chunk)
+            r2, _, l2, m2, s2 = host_moves(p_rows[lo:hi], pieces[cfg[lo:hi], ply], place[lo:hi] // 10, place[lo:hi] % 10, L, M,
+                                           p_lines[lo:hi], p_moves[lo:hi])
+            psi = np.concatenate([np.stack([l2, s2 == STATE_WON, s2 >= STATE_LOST_LIMIT], axis=1).astype(np.int64),
+                                  board_features(r2)], axis=1)
+            c_rows[lo:hi], c_lines[lo:hi], c_moves[lo:hi], c_state[lo:hi] = r2, l2, m2, s2
+            c_value[lo:hi] = placement_score(psi, w)
+        still = []
+        for s in active:
+            beam = beams[s]
+            run = beam["state"] == STATE_RUNNING
+            count = placements[pieces[s, ply]].size
+            sizes = np.where(run, count, 1)
+            cand = int(sizes.sum())
+            # the candidates in order: a finished node gives itself (child -1), a running node its children in ascending b
+            parent = np.repeat(np.arange(run.size), sizes)
+            child = np.full(cand, -1, np.int64)
+            mine = first[s] + np.arange(int(run.sum()) * count)
+            child[run[parent]] = mine
+            value = np.where(child >= 0, c_value[np.maximum(child, 0)], beam["value"][parent]).astype(np.float32)
+            best_value[s, ply] = value[_first_in_order(value)]
+            won = np.flatnonzero((child >= 0) & (c_state[np.maximum(child, 0)] == STATE_WON))
+            if won.size:                                        # the stop, before the cut
+                at = won[_first_in_order(value[won])]
+                path, q = [int(place[child[at]])], int(parent[at])
+                for back in reversed(beam["tape"]):
+                    path.append(int(back[1][q]))
+                    q = int(back[0][q])
+                solved[s], length[s] = 1, ply + 1
+                actions[s, :ply + 1] = path[::-1]
+                continue
+            order = np.argsort(-(value + np.float32(0.0)), kind="stable")       # beam_select's order, for any width
+            keep = np.sort(order[:width])
+            kc, kp = child[keep], parent[keep]
+            moved = kc >= 0
+            kc0 = np.maximum(kc, 0)
+            beam["tape"].append((kp, np.where(moved, place[kc0], NO_SECOND)))
+            beams[s] = dict(rows=np.where(moved[:, None], c_rows[kc0], beam["rows"][kp]),
+                            lines=np.where(moved, c_lines[kc0], beam["lines"][kp]),
+                            moves=np.where(moved, c_moves[kc0], beam["moves"][kp]),
+                            state=np.where(moved, c_state[kc0], beam["state"][kp]),
+                            value=value[keep], tape=beam["tape"])
+            if (beams[s]["state"] == STATE_RUNNING).any():
+                still.append(s)
+        active = still
+        if not active:
+            break
+    return solved, length, actions, best_value
 
 
 # ------------------------------------------------------------------------------------------------ the n-tuple value function

@@ -105,13 +105,28 @@ class ForwardGames:
     `translate(batch)` gives them the way the reference's `translate()` does (game/tetris.py:19-20): ONE random piece put in
     FRONT of the sequence, so that `pieces` has M + 1 entries -- which also means the game no longer starts with the piece its
     solver planned for: a translated game is not winnable by construction, in the reference either.  `lead=False` pads at the
-    END instead (the recorded solution still wins; the last piece is never played)."""
+    END instead (the recorded solution still wins; the last piece is never played).
 
-    def __init__(self, env, seeds=range(100), initial_height_max: int = 4, max_attempts: int = 1000):
+    `solver` says who decides which games are kept.  "reference" (the default) is the reference's greedy depth-first solver: the
+    games it marks winnable, with its solutions -- at L = 10 / M = 40 it finds none.  "beam" keeps the games `solve_configs` solves
+    (the whole-game placement beam under `weights`, None = CLASSICAL_WEIGHTS, at `width`) and records ITS solutions; it solves the
+    untranslated sequence, so, as with the reference's solver, a solution fits `translate(lead=False)` and not `lead=True`.  A
+    game the beam does not solve is dropped because this beam found no win, not because there is none."""
+
+    SOLVERS = ("reference", "beam")
+
+    def __init__(self, env, seeds=range(100), initial_height_max: int = 4, max_attempts: int = 1000, solver: str = "reference",
+                 weights=None, width: int = 16):
         import torch
+        if not isinstance(solver, str) or solver not in self.SOLVERS:
+            raise ValueError(f"solver must be one of {self.SOLVERS}, got {solver!r}")
         out = env.forward_configs(list(seeds), initial_height_max, max_attempts)
+        if solver == "beam":                                   # the generator's boards and sequences, the beam's verdicts
+            from .solve import solve_configs
+            found = solve_configs(out["rows"], out["sequence"], env.L, env.M, weights, width, device=env.device, validate=False)
+            out = dict(out, winnable=found["solved"], solution=found["solution"], solution_len=found["solution_len"])
         keep = out["winnable"]                                 # one host sync, at construction
-        self.device, self.M = env.device, env.M
+        self.device, self.M, self.solver = env.device, env.M, solver
         self.tried = int(keep.numel())
         self.rows = out["rows"][keep].contiguous()
         self.sequence = out["sequence"][keep].contiguous()
@@ -196,7 +211,8 @@ class PoolRefresher:
 
     def __init__(self, env, count: int = 0, seed: int = 0, first: int = 0, waves: int = 0, reserved_cus: int = 0,
                  low_priority: bool = False, cutoff: int = 0, strict: bool = False, max_capped_batches: int = 3,
-                 forward_seeds=None, forward_lead: bool = True, target_slowdown: float = 1.13):
+                 forward_seeds=None, forward_lead: bool = True, target_slowdown: float = 1.13, solver: str = "reference",
+                 weights=None, width: int = 16):
         """count: configurations per batch = the size of the pool the batch becomes (0 = as many as the environment has
         boards: with fewer, the generator idles between swaps -- a swap has to wait M + 1 steps for the boards still on the
         other buffer -- and the pool is re-dealt more often for the same cost).
@@ -213,7 +229,8 @@ class PoolRefresher:
         An (L, M, cutoff) under which NONE of the generator's pilot configurations finishes is refused HERE (TplError from the first start()).  A batch
         in which some configuration ran into all of its cut-offs is dropped: `strict` raises at once; otherwise a warning names
         (L, M, cutoff), and after `max_capped_batches` such batches IN A ROW the refresher stops (`stopped`; poll() returns
-        False from then on) instead of spending the generator's worst case beside the training loop for ever."""
+        False from then on) instead of spending the generator's worst case beside the training loop for ever.
+        solver, weights, width: who keeps the forward games of `forward_seeds`, passed to ForwardGames as they are."""
         import torch
         self.env, self.count, self.seed, self.next_first = env, int(count) or int(env.num_envs), int(seed), int(first)
         self.cutoff = int(cutoff)     # the restart rule's iteration cut-off (0 = by L), as generate_configs / carved_configs take it
@@ -231,7 +248,8 @@ class PoolRefresher:
         self.capped_batches = 0       # batches dropped because a configuration's attempts all ran into their cut-off
         self._capped_in_a_row = 0
         self.stopped = False
-        self.forward = ForwardGames(env, forward_seeds) if forward_seeds is not None else None
+        self.forward = (ForwardGames(env, forward_seeds, solver=solver, weights=weights, width=width)
+                        if forward_seeds is not None else None)
         self.forward_lead, self._batches = bool(forward_lead), 0
         self._stats_at_swap = None    # the environment's episode counters when the current pool came in (device tensor)
         self._pool_entries = 0

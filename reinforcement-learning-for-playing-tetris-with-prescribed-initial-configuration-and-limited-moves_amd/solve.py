@@ -1,0 +1,151 @@
+"""A whole-game beam solver for prescribed configurations (include/tpl_learn.h: tpl_placement_solve; csrc/learn/solve.hip).
+
+Every policy here plans from an environment state, which shows at most twelve pieces.  A prescribed configuration is a board and
+the WHOLE list of its M + 1 pieces; `solve_configs` runs the placement beam of `BeamPolicy` through that list, one workgroup per
+configuration, stops at the first ply at which it sees a win and returns the moves.  What it is for: deciding which forward-generated
+games to keep (`ForwardGames(solver="beam")`), checking pools from files for winnability on the device, and building pools with a
+tighter move budget from the solution lengths (`tighten_pool`).
+
+`solved = False` means that this beam, with these weights at this width, found no win.  It does NOT mean that there is none.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from ._learn_lib import BEAM_MAX_WIDTH, NUM_FEATURES, SOLVE_MAX_MOVES
+
+__all__ = ["CLASSICAL_WEIGHTS", "solve_configs", "tighten_pool"]
+
+# cleared, won, lost, holes, aggregate height, max height, bumpiness, row and column transitions, wells, rows with holes, hole depth:
+# the classical signs, a sensible default for the supply (0.99925 of a carved L = 10 / M = 40 pool at one ply)
+CLASSICAL_WEIGHTS = np.array([4, 100, -100, -8, -1, 0, -2, -3, -6, -3, -2, -1], np.float32) * np.float32(0.1)
+CLASSICAL_WEIGHTS.setflags(write=False)
+
+
+def _is_tensor(x) -> bool:
+    return type(x).__module__.split(".")[0] == "torch"
+
+
+def _game(L, M) -> tuple:
+    for name, v, hi in (("L", L, 250), ("M", M, SOLVE_MAX_MOVES)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= hi:
+            raise ValueError(f"{name} must be an integer in [1, {hi}], got {v!r}")
+    return int(L), int(M)
+
+
+def _width(width) -> int:
+    if isinstance(width, bool) or not isinstance(width, (int, np.integer)) or not 1 <= int(width) <= BEAM_MAX_WIDTH:
+        raise ValueError(f"width must be an integer in [1, {BEAM_MAX_WIDTH}], got {width!r}")
+    return int(width)
+
+
+def _weight_row(weights) -> np.ndarray:
+    """None -> CLASSICAL_WEIGHTS; anything array-like of twelve numbers -> a finite float32 [12]."""
+    if weights is None:
+        return CLASSICAL_WEIGHTS.copy()
+    if _is_tensor(weights):
+        weights = weights.detach().cpu().numpy()
+    w = np.asarray(weights)
+    if w.dtype == object or not (np.issubdtype(w.dtype, np.floating) or np.issubdtype(w.dtype, np.integer)):
+        raise ValueError(f"weights must be {NUM_FEATURES} numbers")
+    if w.shape not in ((NUM_FEATURES,), (1, NUM_FEATURES)):
+        raise ValueError(f"weights must be one row of shape [{NUM_FEATURES}], got {tuple(w.shape)}")
+    with np.errstate(over="ignore"):
+        w = np.ascontiguousarray(w.reshape(NUM_FEATURES), dtype=np.float32)
+    if not np.isfinite(w).all():
+        raise ValueError("weights must be finite (in float32)")
+    return w
+
+
+def _shapes(rows, pieces, M: int) -> int:
+    """The shapes solve_configs takes, checked before anything moves to the device; returns n."""
+    rs, ps = tuple(rows.shape), tuple(pieces.shape)
+    n = rs[0] if rs else 0
+    if not (rs == (n, 20) or rs == (n, 20, 10)) or ps not in ((n, M + 1), (n, M)):
+        raise ValueError(f"rows must be [n, 20] row masks or [n, 20, 10] cells and pieces [n, {M + 1}] or [n, {M}]; got {rs} {ps}")
+    if n < 1:
+        raise ValueError("at least one configuration is needed")
+    return n
+
+
+def solve_configs(rows, pieces, L: int, M: int, weights=None, width: int = 16, device="cuda:0", best_value: bool = False,
+                  validate: bool = True) -> dict:
+    """Search every configuration's whole game with the placement beam (the rule: include/tpl_learn.h, tpl_placement_solve).
+
+    rows: [n, 20] int16 / uint16 (bit x = column x) or [n, 20, 10] bool, converted as `load_configs` converts them; pieces:
+    [n, M + 1] uint8, or [n, M] (padded with piece 0: the piece behind the last move is never played); weights: one row of twelve
+    (None = CLASSICAL_WEIGHTS); width in [1, 64].  Tensors or arrays; everything is enqueued on the current stream of `device`.
+    Returns a dict of device tensors: solved bool [n], solution_len int32 [n], actions uint8 [n, M] (placements 10 r + l, 255
+    behind the end), solution uint8 [n, M, 2] as (rotations, location) -- the layout of carved_configs(with_solutions=True) and
+    forward_configs, zero behind the end -- and, with best_value=True, best_value float32 [n, M]: the value of the best candidate
+    of every ply run, +0 behind.
+
+    solved[i] = False means that THIS beam found no win for configuration i, not that there is none.
+    No host wait except the piece-id check (ids 0..6, as load_configs'), which validate=False skips."""
+    import torch
+    from . import _learn_lib
+    L, M = _game(L, M)
+    width = _width(width)
+    w = _weight_row(weights)
+    if not _is_tensor(rows):
+        rows = np.asarray(rows)
+    if not _is_tensor(pieces):
+        pieces = np.asarray(pieces)
+    n = _shapes(rows, pieces, M)
+    d = torch.device(device)
+    if not _is_tensor(rows):
+        if rows.ndim == 3:
+            rows = (rows.astype(np.uint16) << np.arange(10, dtype=np.uint16)).sum(-1).astype(np.uint16)
+        rows = torch.from_numpy(np.ascontiguousarray(rows.astype(np.uint16)).view(np.int16))
+    elif rows.dim() == 3:
+        rows = (rows.to(torch.int32) << torch.arange(10, device=rows.device, dtype=torch.int32)).sum(-1).to(torch.int16)
+    rows = rows.to(d).contiguous()
+    if rows.dtype not in (torch.int16, torch.uint16):
+        rows = rows.to(torch.int16)
+    if not _is_tensor(pieces):
+        pieces = torch.as_tensor(np.ascontiguousarray(pieces.astype(np.uint8)))
+    pieces = pieces.to(device=d, dtype=torch.uint8)
+    if pieces.shape[1] == M:
+        pieces = torch.cat([pieces, torch.zeros((n, 1), dtype=torch.uint8, device=d)], dim=1)
+    pieces = pieces.contiguous()
+    if validate and int(pieces.max()) > 6:
+        raise ValueError("piece ids must be in 0..6 (I L J T S Z O)")
+    wt = torch.from_numpy(w).to(d)
+    out = dict(solved=torch.empty(n, dtype=torch.uint8, device=d), solution_len=torch.empty(n, dtype=torch.int32, device=d),
+               actions=torch.empty((n, M), dtype=torch.uint8, device=d))
+    if best_value:
+        out["best_value"] = torch.empty((n, M), dtype=torch.float32, device=d)
+    stream = torch._C._cuda_getCurrentRawStream(d.index if d.index is not None else torch.cuda.current_device())
+    _learn_lib.check(_learn_lib.lib().tpl_placement_solve(rows.data_ptr(), pieces.data_ptr(), n, L, M, wt.data_ptr(), width,
+                                                          out["solved"].data_ptr(), out["solution_len"].data_ptr(),
+                                                          out["actions"].data_ptr(),
+                                                          out["best_value"].data_ptr() if best_value else None, stream))
+    out["solved"] = out["solved"].view(torch.bool)
+    played = out["actions"] != 255
+    a = torch.where(played, out["actions"], torch.zeros_like(out["actions"]))
+    out["solution"] = torch.stack([a // 10, a % 10], dim=2).to(torch.uint8)
+    return out
+
+
+def tighten_pool(rows, pieces, solved, solution_len, M_new: int):
+    """A pool with a tighter move budget: (rows, pieces[:, :M_new + 1]) of the configurations that are `solved` with
+    solution_len <= M_new -- a pool for BatchedTetris(L, M_new), every entry of it winnable within M_new moves by the solution
+    that was found.  Tensors (one host wait) or arrays; M is read off pieces [n, M + 1].  M_new outside [1, M] is refused, and so
+    is a result with nothing left."""
+    if len(pieces.shape) != 2 or pieces.shape[1] < 2:
+        raise ValueError("pieces must be [n, M + 1]")
+    n, M = int(pieces.shape[0]), int(pieces.shape[1]) - 1
+    if isinstance(M_new, bool) or not isinstance(M_new, (int, np.integer)) or not 1 <= int(M_new) <= M:
+        raise ValueError(f"M_new must be an integer in [1, {M}], got {M_new!r}")
+    M_new = int(M_new)
+    if tuple(rows.shape[:2]) != (n, 20) or tuple(solved.shape) != (n,) or tuple(solution_len.shape) != (n,):
+        raise ValueError(f"rows must be [{n}, 20] and solved and solution_len [{n}]")
+    if _is_tensor(rows):
+        keep = solved.to(device=rows.device).bool() & (solution_len.to(rows.device) <= M_new)
+        out = rows[keep], pieces.to(rows.device)[keep][:, :M_new + 1].contiguous()
+    else:
+        keep = np.asarray(solved).astype(bool) & (np.asarray(solution_len) <= M_new)
+        out = np.asarray(rows)[keep], np.ascontiguousarray(np.asarray(pieces)[keep][:, :M_new + 1])
+    if out[0].shape[0] == 0:
+        raise ValueError(f"no configuration is solved within {M_new} moves: nothing is left of the pool")
+    return out

@@ -116,6 +116,14 @@ Parts:
               loaded into one process: the outputs of the six entries compared byte for byte on the ring of part ntuple_shape
               at 2^18 boards, then each entry timed in five rounds of the parent against itself and five of the parent against
               this build; a new median passes within the parent's own min-max or at most 2 % above the parent's median
+    solve     the whole-game beam solver (tpl_placement_solve, solve_configs) under the classical weights: the share of forward seeds
+              0 .. 9,999 it solves at L=5 / M=20 and L=10 / M=40 at widths 1, 8, 16 and 64 beside the share the reference's solver marks
+              winnable in the same forward_configs call, and the share of the sweeps' carved pool (65,536, seed 7) it solves; the
+              histogram of its solution lengths there beside carving's; the pool tighten_pool makes at the median length and the win
+              rates on it of the classical weights at one ply, of the beam (3, 8) and of the rate-8 "feat" learner trained on it under the
+              sweeps' set-up; configurations a second at 2^16 and 2^20 configurations at widths 8, 16 and 64 (the median of five timings
+              after a warm-up) beside tpl_placement_beam at (12, W) on as many freshly reset boards, scaled by the mean plies run over
+              12, and beside the forward generator's games a second
 """
 import argparse
 import json
@@ -133,7 +141,7 @@ PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600, "priority": 600
          "ntuple_search": 900, "ntuple_trace": 600, "ntuple_trace_sweep": 1100, "ntuple_coherent": 600,
          "ntuple_coherent_sweep": 1700, "ntuple_shape": 600, "ntuple_shape_sweep": 1100, "ntuple_beam": 1100,
          "ntuple_sum": 600, "ntuple_sum_sweep": 600, "ntuple_stage": 600, "ntuple_stage_sweep": 900,
-         "ntuple_feature": 600, "ntuple_feature_sweep": 900}
+         "ntuple_feature": 600, "ntuple_feature_sweep": 900, "solve": 900}
 SCATTERED_ATOMICS = 0.08e12                                 # 64 lanes of a wave adding into 64 rows (float adds; integer adds unmeasured)
 VALU_CYCLES, SIMDS, CLOCK_HZ = 3.3, 1024, 2.4e9           # the move's instruction mix, 256 CUs x 4, the clock
 
@@ -2102,6 +2110,127 @@ def part_ntuple_feature_sweep(eval_steps=12288):
         env.terminate()
         out["forms"][shape] = dict(best=runs[at], best_played=deep, best_symmetric_at_half_the_rate=symmetric,
                                    best_symmetric_at_the_same_rate=same_rate, runs=runs)
+    return out
+
+
+def part_solve(rounds=5, eval_steps=12288):
+    import numpy as np
+    import torch
+    import tetris_piclim as T
+    dev = "cuda:0"
+    widths = (1, 8, 16, 64)
+    share = lambda x: round(float(x.float().mean()), 5)
+    out = dict(part="solve", weights="CLASSICAL_WEIGHTS", forward={}, carved={}, tight={}, time=[])
+
+    def progress(what):
+        print(json.dumps(what), file=sys.stderr, flush=True)     # a long part must not stay silent
+
+    # yield: the forward generator's games, kept by the reference's solver and by the beam
+    for L_, M_ in ((5, 20), (10, 40)):
+        env = T.BatchedTetris(L_, M_, 64, device=dev, seed=7)
+        fw = env.forward_configs(np.arange(10000))
+        got = dict(seeds=10000, reference_winnable=share(fw["winnable"]))
+        for W in widths:
+            found = T.solve_configs(fw["rows"], fw["sequence"], L_, M_, width=W, device=dev, validate=False)
+            got[f"beam_w{W}"] = share(found["solved"])
+            if W == 16:
+                got["reference_winnable_that_w16_solves"] = share(found["solved"][fw["winnable"]]) if bool(fw["winnable"].any()) else None
+                got["mean_solution_len_w16"] = round(float(found["solution_len"][found["solved"]].float().mean()), 2)
+        out["forward"][f"L{L_}_M{M_}"] = got
+        progress(got)
+        env.terminate()
+
+    # the sweeps' carved pool: winnable by construction, so everything short of 1 is the beam's miss rate
+    L_, M_, n = 10, 40, 1 << 16
+    env = T.BatchedTetris(L_, M_, 64, device=dev, seed=7)
+    rows, pieces, _, carved_len = env.carved_configs(n, seed=7, with_solutions=True)
+    env.terminate()
+    hist = lambda x: np.bincount(x.cpu().numpy().astype(np.int64), minlength=M_ + 1).tolist()
+    out["carved"] = dict(pool=n, pool_seed=7, L=L_, M=M_, carving_solution_len_histogram=hist(carved_len),
+                         carving_mean=round(float(carved_len.float().mean()), 2), widths={})
+    solved16 = None
+    for W in widths:
+        found = T.solve_configs(rows, pieces, L_, M_, width=W, device=dev, validate=False)
+        ok = found["solved"]
+        out["carved"]["widths"][f"w{W}"] = dict(solved=share(ok), mean_len=round(float(found["solution_len"][ok].float().mean()), 2),
+                                                solution_len_histogram=hist(found["solution_len"][ok]))
+        if W == 16:
+            solved16 = found
+    progress({k: v["solved"] for k, v in out["carved"]["widths"].items()})
+
+    # a tight pool: the median solution length of width 16 as the move budget
+    lens = solved16["solution_len"][solved16["solved"]]
+    M_new = int(lens.float().median())
+    t_rows, t_pieces = T.tighten_pool(rows, pieces, solved16["solved"], solved16["solution_len"], M_new)
+    tight = (t_rows, t_pieces)
+
+    def result(e, wins):
+        p = wins / max(e, 1)
+        return dict(episodes=int(e), wins=int(wins), win_rate=round(p, 5), standard_error=round((p * (1 - p) / max(e, 1)) ** 0.5, 6))
+
+    def hand(pool, M_pool, **kw):
+        env = T.BatchedTetris(L_, M_pool, 1 << 14, device=dev, seed=11, auto_reset=True, reward=(0.0, 1.0, 0.0), config_pool=pool)
+        got = T.evaluate_heuristic(env, T.CLASSICAL_WEIGHTS, None, 16 * (M_pool + 1), **kw)
+        env.terminate()
+        return result(int(got["episodes"][0]), int(got["wins"][0]))
+
+    def learned(pool, M_pool):
+        env = T.BatchedTetris(L_, M_pool, 4096, device=dev, seed=11, auto_reset=True, reward=NTUPLE_LARGE_REWARD, config_pool=pool)
+        learner = T.NTupleLearner(env, seed=11, gamma=1.0, epsilon=0.05, shape="feat", rate=8.0)
+        zero = learner.evaluate(eval_steps)
+        for steps in (10000, 30000):
+            learner.train(steps)
+        got = learner.evaluate(eval_steps)
+        env.terminate()
+        return dict(zero_table=result(zero["episodes"], zero["wins"]), trained_40000_steps=result(got["episodes"], got["wins"]))
+
+    out["tight"] = dict(M_new=M_new, from_width=16, size=int(t_rows.shape[0]), of=n,
+                        classical_one_ply=hand(tight, M_new), classical_beam_3x8=hand(tight, M_new, depth=3, width=8),
+                        feat_rate_8=learned(tight, M_new),
+                        the_full_pool_for_comparison=dict(classical_one_ply=hand((rows, pieces), M_), classical_beam_3x8=hand((rows, pieces), M_, depth=3, width=8)))
+    progress(out["tight"])
+
+    # time: the solver, the placement beam at (12, W) on as many freshly reset boards, the forward generator
+    median = lambda ts: sorted(ts)[len(ts) // 2]
+    for count in (1 << 16, 1 << 20):
+        env = T.BatchedTetris(L_, M_, count, device=dev, seed=7, auto_reset=False, assign="sequential")
+        rows, pieces = env.carved_configs(count, seed=7)
+        env.load_configs(rows, pieces, validate=False)
+        env.reset()
+        for W in (8, 16, 64):
+            found = T.solve_configs(rows, pieces, L_, M_, width=W, device=dev, validate=False)
+            plies = torch.where(found["solved"], found["solution_len"], torch.full_like(found["solution_len"], M_)).float().mean()
+            plies = float(plies)                                 # (an unsolved game counts as M plies: an upper bound)
+            w = torch.from_numpy(T.CLASSICAL_WEIGHTS.copy()).to(dev)
+            outs = (torch.empty(count, dtype=torch.uint8, device=dev), torch.empty(count, dtype=torch.int32, device=dev),
+                    torch.empty((count, M_), dtype=torch.uint8, device=dev))
+            lib, stream = T._learn_lib.lib(), torch._C._cuda_getCurrentRawStream(0)
+            solve = lambda: T._learn_lib.check(lib.tpl_placement_solve(rows.data_ptr(), pieces.data_ptr(), count, L_, M_, w.data_ptr(), W,
+                                                                        outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), None, stream))
+            beam = T.BeamPolicy(env, T.CLASSICAL_WEIGHTS, depth=12, width=W)
+            action = torch.empty(count, dtype=torch.uint8, device=dev)
+            reps = 3 if count == 1 << 16 else 1
+            ts, tb = [], []
+            for _ in range(rounds):                              # alternated
+                ts.append(_timed(solve, reps, warmup=1))
+                tb.append(_timed(lambda: beam.act(out=action), reps, warmup=1))
+            s_med, b_med = median(ts), median(tb)
+            line = dict(configurations=count, width=W, solved=share(found["solved"]), mean_plies_run=round(plies, 2),
+                        solve_ms=round(s_med * 1e3, 3), configurations_per_second=round(count / s_med),
+                        beam_12_ms=round(b_med * 1e3, 3), beam_scaled_by_plies_ms=round(b_med * plies / 12 * 1e3, 3),
+                        solve_over_scaled_beam=round(s_med / (b_med * plies / 12), 3))
+            out["time"].append(line)
+            progress(line)
+        env.terminate()
+    env = T.BatchedTetris(L_, M_, 64, device=dev, seed=7)
+    seeds = np.arange(10000)
+    tf = [_timed(lambda: env.forward_configs(seeds), 1, warmup=1) for _ in range(rounds)]
+    out["forward_generator"] = dict(games=10000, L=L_, M=M_, ms=round(median(tf) * 1e3, 3), games_per_second=round(10000 / median(tf)))
+    env.terminate()
+    res = subprocess.run(["bash", os.path.join(ROOT, "tools", "kernel_resources.sh"), T._learn_lib.build_library()],
+                         capture_output=True, text=True, cwd=ROOT)
+    out["kernel"] = [" ".join(l.split()) for l in res.stdout.splitlines() if "placement_solve_kernel" in l or "placement_beam_kernel" in l]
+    out["lds_note"] = "the solve kernel's dynamic tape of 2 W M bytes comes on top of its static lds"
     return out
 
 
