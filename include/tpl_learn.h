@@ -235,8 +235,8 @@ int32_t tpl_canonical_action(int32_t cur, int32_t action);
  *    9 wells               sum_x d_x (d_x + 1) / 2, d_x = max(0, min(h_{x-1}, h_{x+1}) - h_x) with h_{-1} = h_10 = 20
  *   10 rows_with_holes     rows that contain at least one hole
  *   11 hole_depth          over the columns that have a hole: the filled cells of the column above its top-most hole
- * Every value fits an int16.  Landing height and eroded cells are left out on purpose: both need the drop distance, which
- * move_board keeps to itself.
+ * Every value fits an int16.  These twelve describe the board a move leaves; the two features of the move itself, landing height and
+ * eroded cells, are features 12 and 13 of the 14-feature form below (tpl_placement_*_move).
  *
  * Score: with weights w[12] (float32), score = w_0 phi_0 + w_1 phi_1 + ... + w_11 phi_11 from left to right in float32: every
  * phi_f converts exactly, every product and every sum is rounded once, never fused (move_reward's discipline).
@@ -373,6 +373,57 @@ int tpl_placement_beam(const void* plane_a, const void* plane_b, int64_t n, int3
  * [1, 254], width outside [1, TPL_BEAM_MAX_WIDTH]. */
 int tpl_placement_solve(const int16_t* rows, const uint8_t* pieces, int64_t n, int32_t L, int32_t M, const float* weights,
                         int32_t width, uint8_t* solved, int32_t* solution_len, uint8_t* actions, float* best_value, void* stream);
+
+/* The 14-feature form: the twelve board features and the two features of the move itself -- the Dellacherie / BCTS controller's
+ * landing height and eroded piece cells.  A move budget rewards clearing rows soon and low down; these two measure that, and the
+ * twelve cannot: they see the board a move leaves, not how the piece came to lie in it.
+ *
+ * For a running state s and action a = 10 r + l, `drop` is move_board's drop: the row of the piece's top-most mask row after the fall,
+ * taken from the column tops under the piece (not a cell-by-cell slide: a piece never slips under an overhang), and h the height of
+ * shape table entry [cur][r].  A move that does not top out puts the piece's four cells into rows drop .. drop + h - 1; of those rows,
+ * the ones that are full after the lock are cleared, n of them (feature 0).
+ *   12 landing_height      39 - 2 drop - h: twice the height of the piece's centre above the floor, in half rows (0..38).  An I piece
+ *                          flat on an empty floor gives 0, an O piece on an empty floor 1.
+ *   13 eroded_cells        n x (the number of the piece's four cells that lay in cleared rows) (0..16).  A vertical I piece that
+ *                          clears four rows gives 16.
+ * Both are 0 for a top-out (the move is not made) and for a finished board, as the other twelve are.
+ * phi14(s, a) = features 0..11 as above, then these two: TPL_NUM_MOVE_FEATURES = 14 values.
+ * Weights: float32 [P][TPL_MOVE_WEIGHT_STRIDE = 16], 16-byte aligned; entries 14 and 15 of a row are never read.
+ * Score: the score rule carried two terms further: w_0 phi_0 + ... + w_13 phi_13 from left to right in float32, every product and
+ * every sum rounded once, never fused.  The arg-max, the ties, the rows of a population and THE FINITENESS CAVEAT are unchanged.
+ * With w_12 = w_13 = 0 (and finite scores) every choice is the 12-feature form's: the two added terms are +-0, and adding a zero
+ * changes no value but the sign of a zero, which the order does not see.
+ *
+ * Deeper than one ply both features ACCUMULATE ALONG THE PATH exactly as `cleared` does:
+ *   two plies   psi(a, b) = (n1 + n2, won2, lost2, features 3..11 of s2, land1 + land2, erod1 + erod2); where the first move ends
+ *               the game psi(a) = phi14(s, a).
+ *   beam, solve a node carries the sums of its path, a child's psi has its node's sums plus its move's; a finished node passes on
+ *               unchanged and a finished root scores fourteen zeros.  The landing sum is at most 254 * 38 and the eroded sum at most
+ *               4 (L + 3), so the kernels keep (cleared, landing, eroded) in 8 + 14 + 10 bits of the one word a node had for `cleared`.
+ * Everything else -- candidates, order, the stable compaction, the solver's stop at the first won candidate, the tape, best_value,
+ * the consequences listed with each rule -- is the 12-feature rule word for word, with `psi` read as above. */
+#define TPL_NUM_MOVE_FEATURES 14
+#define TPL_MOVE_WEIGHT_STRIDE 16
+
+/* tpl_placement_features in the 14-feature form: features i16 [n][40][16], one contiguous 32-byte record per pair (16-byte aligned,
+ * written with 16-byte stores), entries 14 and 15 zero; entries 0..11 and canonical are tpl_placement_features'.  Refused before any
+ * HIP call: what tpl_placement_features refuses, with features not 16-byte aligned in place of its 8. */
+int tpl_placement_features_move(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, int16_t* features,
+                                uint8_t* canonical, void* stream);
+
+/* tpl_placement_act, tpl_placement_search, tpl_placement_beam and tpl_placement_solve in the 14-feature form: the same arguments,
+ * outputs and checks, with weights f32 [P][16] (tpl_placement_solve_move: one row, [16], of which 14 are read).  Each is the same
+ * kernel body as its twin, instantiated on the other feature set (csrc/learn/tpl_placement.h: placed_move). */
+int tpl_placement_act_move(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const float* weights,
+                           int64_t boards_per_member, uint8_t* action, float* score, void* stream);
+int tpl_placement_search_move(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const float* weights,
+                              int64_t boards_per_member, uint8_t* action, uint8_t* second, float* score, void* stream);
+int tpl_placement_beam_move(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const float* weights,
+                            int64_t boards_per_member, int32_t depth, int32_t width, uint8_t* action, uint8_t* plan,
+                            float* score, void* stream);
+int tpl_placement_solve_move(const int16_t* rows, const uint8_t* pieces, int64_t n, int32_t L, int32_t M, const float* weights,
+                             int32_t width, uint8_t* solved, int32_t* solution_len, uint8_t* actions, float* best_value,
+                             void* stream);
 
 /* An n-tuple afterstate value function, its placement policy and its temporal-difference update (csrc/learn/ntuple.hip).
  *

@@ -16,7 +16,8 @@ __all__ = ["BatchedTetris", "Tetris", "Snapshot", "OBS_DIM", "NUM_ACTIONS", "RUN
            "evaluate_heuristic", "tune_heuristic", "BeamPolicy", "NTuplePolicy", "NTupleBeamPolicy", "NTupleLearner", "ntuple_table", "ntuple_value",
            "ntuple_is_symmetric", "ntuple_coherence", "ntuple_step_sizes", "ntuple_shape", "NTUPLE_SHAPES", "ntuple_parts", "NTUPLE_SUMS", "NTUPLE_ENTRIES_SUM",
            "NTUPLE_STAGES", "ntuple_stage_map", "ntuple_staged", "ntuple_stages", "ntuple_map", "ntuple_is_staged", "NTUPLE_FEATURE_FORMS",
-           "ntuple_feature_bins", "solve_configs", "tighten_pool", "CLASSICAL_WEIGHTS"]
+           "ntuple_feature_bins", "solve_configs", "tighten_pool", "CLASSICAL_WEIGHTS", "FEATURE_NAMES",
+           "MOVE_FEATURE_NAMES", "DELLACHERIE_WEIGHTS"]
 
 
 def __getattr__(name):
@@ -38,7 +39,8 @@ def __getattr__(name):
         return getattr(importlib.import_module(__name__ + ".learn"), name)
     if name in ("LookaheadPolicy", "afterstates"):
         return getattr(importlib.import_module(__name__ + ".lookahead"), name)
-    if name in ("HeuristicPolicy", "placement_features", "evaluate_heuristic", "tune_heuristic", "BeamPolicy"):
+    if name in ("HeuristicPolicy", "placement_features", "evaluate_heuristic", "tune_heuristic", "BeamPolicy", "FEATURE_NAMES",
+                "MOVE_FEATURE_NAMES", "DELLACHERIE_WEIGHTS"):
         return getattr(importlib.import_module(__name__ + ".heuristic"), name)
     if name in ("NTuplePolicy", "NTupleBeamPolicy", "NTupleLearner", "ntuple_table", "ntuple_value", "ntuple_is_symmetric", "ntuple_coherence",
                 "ntuple_step_sizes", "ntuple_shape", "NTUPLE_SHAPES", "ntuple_parts", "NTUPLE_SUMS", "NTUPLE_ENTRIES_SUM",

@@ -21,7 +21,8 @@ from ._lib import TplError, _hipcc
 _LEARN_CSRC = os.path.join(_lib._CSRC, "learn")
 LEARN_LIB_PATH = os.path.join(_lib._LIBDIR, "libtpl_learn.so")
 _UNITS = [os.path.join(_LEARN_CSRC, f) for f in ("replay.hip", "pack.hip", "priority.hip", "afterstates.hip",
-                                                      "beam.hip", "solve.hip", "ntuple.hip", "ntuple_beam.hip", "heuristic.hip")]
+                                                      "beam.hip", "solve.hip", "ntuple.hip", "ntuple_beam.hip", "heuristic_move.hip",
+                                                      "beam_move.hip", "solve_move.hip", "heuristic.hip")]
 
 # entry points declared in include/tpl_learn.h (tests check that the .so exports every one of them)
 LEARN_SYMBOLS = [
@@ -38,6 +39,8 @@ LEARN_SYMBOLS = [
     "tpl_ntuple_update_trace_staged",
     "tpl_ntuple_value_feature", "tpl_ntuple_act_feature", "tpl_ntuple_search_feature", "tpl_ntuple_beam_feature",
     "tpl_ntuple_update_trace_feature", "tpl_ntuple_feature_bins", "tpl_placement_solve",
+    "tpl_placement_features_move", "tpl_placement_act_move", "tpl_placement_search_move", "tpl_placement_beam_move",
+    "tpl_placement_solve_move",
 ]
 NSTEP_MAX = 16
 BEAM_MAX_DEPTH, BEAM_MAX_WIDTH = 12, 64
@@ -146,6 +149,10 @@ def lib() -> C.CDLL:
     L.tpl_placement_beam.argtypes = [vp, vp, i64, i32, i32, vp, i64, i32, i32, vp, vp, vp, vp]
     L.tpl_placement_solve.argtypes = [vp, vp, i64, i32, i32, vp, i32, vp, vp, vp, vp, vp]
     L.tpl_placement_solve.restype = i32
+    for name in ("features", "act", "search", "beam", "solve"):      # the 14-feature form: the twin's arguments
+        twin = getattr(L, f"tpl_placement_{name}_move")
+        twin.argtypes = getattr(L, f"tpl_placement_{name}").argtypes
+        twin.restype = i32
     f32 = C.c_float
     L.tpl_ntuple_value.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp]
     L.tpl_ntuple_act.argtypes = [vp, vp, i64, i32, i32, f32, f32, f32, f32, vp, f32, u64, u64, vp, vp, vp, vp, vp, vp]
@@ -463,6 +470,27 @@ def canonical_actions(cur, action) -> np.ndarray:
 NUM_FEATURES = 12
 FEATURE_NAMES = ("cleared", "won", "lost", "holes", "aggregate_height", "max_height", "bumpiness", "row_transitions",
                  "column_transitions", "wells", "rows_with_holes", "hole_depth")
+# the 14-feature form: the two features of the move itself behind the twelve of the board it leaves (host_move_features)
+NUM_MOVE_FEATURES = 14
+MOVE_WEIGHT_STRIDE = 16                                  # floats between two weight rows of the 14-feature kernels
+MOVE_FEATURE_NAMES = FEATURE_NAMES + ("landing_height", "eroded_cells")
+FEATURE_COUNTS = (NUM_FEATURES, NUM_MOVE_FEATURES)
+
+
+def entry(name: str, count: int):
+    """The entry point tpl_placement_<name> of the feature set with `count` features (12 or 14)."""
+    if count not in FEATURE_COUNTS:
+        raise ValueError(f"a weight row has {NUM_FEATURES} or {NUM_MOVE_FEATURES} entries, not {count}")
+    return getattr(lib(), f"tpl_placement_{name}" + ("_move" if count == NUM_MOVE_FEATURES else ""))
+
+
+def padded_weights(w: np.ndarray) -> np.ndarray:
+    """float32 [P, 12] as it is; [P, 14] -> [P, 16], the stride of the 14-feature kernels, zeros in entries 14 and 15."""
+    if w.shape[-1] == NUM_FEATURES:
+        return w
+    out = np.zeros(w.shape[:-1] + (MOVE_WEIGHT_STRIDE,), np.float32)
+    out[..., :NUM_MOVE_FEATURES] = w
+    return out
 
 
 def board_features(rows) -> np.ndarray:
@@ -497,14 +525,16 @@ def board_features(rows) -> np.ndarray:
 
 def placement_score(features, weights) -> np.ndarray:
     """score = w_0 phi_0 + w_1 phi_1 + ... + w_11 phi_11 from left to right in float32, every product and every sum rounded
-    once (numpy float32 operations; nothing fused): features [..., 12] integers, weights [12] or broadcastable [..., 12]."""
+    once (numpy float32 operations; nothing fused): features [..., 12] integers, weights [12] or broadcastable [..., 12].
+    The 14-feature form: both end in 14 and the sum runs two terms further."""
     f = np.asarray(features)
     w = np.asarray(weights, dtype=np.float32)
-    if f.shape[-1] != NUM_FEATURES or w.shape[-1] != NUM_FEATURES:
-        raise ValueError("features and weights must end in 12")
+    count = f.shape[-1]
+    if count not in FEATURE_COUNTS or w.shape[-1] != count:
+        raise ValueError("features and weights must both end in 12 or both in 14")
     f = f.astype(np.float32)                                  # exact: every feature is a small integer
     s = w[..., 0] * f[..., 0]
-    for k in range(1, NUM_FEATURES):
+    for k in range(1, count):
         s = s + w[..., k] * f[..., k]
     return np.asarray(s, dtype=np.float32)
 
@@ -519,19 +549,23 @@ def search_choice(phi1, done1, distinct1, phi2, distinct2, weights):
     done1 is not set), distinct2 [K, 40] or [K, 40, 40] where b is a distinct placement of the next piece; weights [12], or one
     row per board [K, 12].  Returns (action u8 [K], second u8 [K] -- 255 where the chosen first move ends the game --, score
     f32 [K]): V(a) = the one-ply score where done1, else the maximum over the distinct b of placement_score, the lowest index
-    at each maximum (-0 and +0 tie)."""
+    at each maximum (-0 and +0 tie).  The 14-feature form: phi1, phi2 and weights end in 14, phi2 holding the landing and eroded
+    sums of both moves."""
     phi1, phi2 = np.asarray(phi1), np.asarray(phi2)
-    k = phi1.shape[0]
-    if phi1.shape != (k, NUM_ACTIONS, NUM_FEATURES) or phi2.shape != (k, NUM_ACTIONS, NUM_ACTIONS, NUM_FEATURES):
-        raise ValueError("phi1 must be [K, 40, 12] and phi2 [K, 40, 40, 12]")
+    k, count = phi1.shape[0], phi1.shape[-1]
+    if count not in FEATURE_COUNTS or phi1.shape != (k, NUM_ACTIONS, count) or phi2.shape != (k, NUM_ACTIONS, NUM_ACTIONS, count):
+        raise ValueError("phi1 must be [K, 40, 12] and phi2 [K, 40, 40, 12], or both end in 14")
     done1, distinct1, distinct2 = (np.asarray(x).astype(bool) for x in (done1, distinct1, distinct2))
     if distinct2.ndim == 2:
         distinct2 = distinct2[:, None, :]
     if done1.shape != (k, NUM_ACTIONS) or distinct1.shape != (k, NUM_ACTIONS) or distinct2.shape[::2] != (k, NUM_ACTIONS):
         raise ValueError("done1 and distinct1 must be [K, 40] and distinct2 [K, 40] or [K, 40, 40]")
-    w = np.asarray(weights, dtype=np.float32).reshape(-1, NUM_FEATURES)
+    w = np.asarray(weights, dtype=np.float32)
+    if w.shape[-1] != count:
+        raise ValueError(f"weights must end in {count}, as the features do")
+    w = w.reshape(-1, count)
     if w.shape[0] not in (1, k):
-        raise ValueError("weights must be [12] or one row per board")
+        raise ValueError(f"weights must be [{count}] or one row per board")
     rows = np.arange(k)[:, None]
     first = np.arange(NUM_ACTIONS)[None, :]
     score2 = np.where(distinct2, placement_score(phi2, w[:, None, None, :]), -np.inf)
@@ -583,11 +617,25 @@ def _solve_shape_tables():
 
 
 def host_moves(rows, piece, rotations, location, L: int, M: int, lines, moves):
+    """host_moves_traced without the trace."""
+    return host_moves_traced(rows, piece, rotations, location, L, M, lines, moves)[:5]
+
+
+def host_move_features(rows, piece, rotations, location, L: int, M: int, lines, moves):
+    """Features 12 and 13 of include/tpl_learn.h for `piece` played on K running boards (host_moves' arguments): returns
+    (drop int64 [K], cleared_rows bool [K, 20], landing_height int64 [K], eroded_cells int64 [K]).  drop is the row of the piece's
+    top-most mask row after the fall (negative on a top-out), cleared_rows the rows that were full after the lock, in the
+    coordinates of the board BEFORE the compaction; landing_height = 39 - 2 drop - h and eroded_cells = (rows cleared) x (the
+    piece's cells in cleared rows), both 0 on a top-out."""
+    return host_moves_traced(rows, piece, rotations, location, L, M, lines, moves)[5:]
+
+
+def host_moves_traced(rows, piece, rotations, location, L: int, M: int, lines, moves):
     """Tetris.move(rotations, location) with `piece` on K running boards in row form (uint16 [K, 20], bit x = column x, row 0 = top;
     the rest [K]): the right clamp, the drop from the column tops under the piece, the top-out (board and moves stay), the lock, the
     full-row test over the piece's rows, the compaction, then won (rows were cleared and lines >= L) before the move limit
     (moves >= M).  Returns (rows uint16 [K, 20], cleared, lines, moves, state) -- state 0 running, 1 won, 2 lost at the limit,
-    3 topped out."""
+    3 topped out -- and behind them host_move_features' four."""
     H, W_, MASK, LOW = _solve_shape_tables()
     rows = np.array(rows, dtype=np.uint16).reshape(-1, 20).astype(np.int64)
     k = rows.shape[0]
@@ -615,6 +663,15 @@ def host_moves(rows, piece, rotations, location, L: int, M: int, lines, moves):
         full = put & (rows[at, r] == 0x3FF)
         cleared_row[at[full], r[full]] = True
     n = cleared_row.sum(axis=1)
+    # the move's own features: the piece's cells row by row, counted where the row was cleared
+    in_cleared = np.zeros(k, np.int64)
+    for i in range(4):
+        put = ok & (i < h)
+        cells = np.array([bin(m).count("1") for m in range(16)])[MASK[piece, rot, i]]
+        in_cleared += np.where(put & cleared_row[at, np.where(put, drop + i, 0)], cells, 0)
+    landing = np.where(ok, 39 - 2 * drop - h, 0)
+    eroded = n * in_cleared
+    trace = (drop, cleared_row.copy(), landing, eroded)
     order = np.argsort(~cleared_row, axis=1, kind="stable")                        # the cleared rows first, the others in order
     rows = np.take_along_axis(rows, order, axis=1)
     rows[np.arange(20)[None, :] < n[:, None]] = 0
@@ -623,7 +680,7 @@ def host_moves(rows, piece, rotations, location, L: int, M: int, lines, moves):
     won = ok & (n > 0) & (lines >= L)
     limit = ok & ~won & (moves >= M)
     state = np.where(~ok, STATE_LOST_TOPOUT, np.where(won, STATE_WON, np.where(limit, STATE_LOST_LIMIT, STATE_RUNNING)))
-    return rows.astype(np.uint16), n, lines, moves, state
+    return (rows.astype(np.uint16), n, lines, moves, state) + trace
 
 
 def _first_in_order(values) -> int:
@@ -634,7 +691,8 @@ def _first_in_order(values) -> int:
 
 def placement_solve(rows, pieces, L: int, M: int, weights, width: int, max_width: int = BEAM_MAX_WIDTH, chunk: int = 1 << 14):
     """The rule of tpl_placement_solve (include/tpl_learn.h) for n configurations: rows uint16 [n, 20] (bit x = column x), pieces
-    [n, M + 1] (masked to three bits), one weight row [12], a width in [1, max_width].  The placement beam run through the whole
+    [n, M + 1] (masked to three bits), one weight row [12] -- or [14], the 14-feature form, in which a node also carries the landing
+    and eroded sums of its path --, a width in [1, max_width].  The placement beam run through the whole
     piece list: ply j plays pieces[:, j - 1]; the search ends at the first ply at which ANY candidate is won, before the cut, with the
     path of the won candidate that comes first in the rule's order, or unsolved once no node of the beam runs.  Returns
     (solved uint8 [n], solution_len int32 [n], actions uint8 [n, M] padded with 255, best_value float32 [n, M], +0 beyond the
@@ -654,18 +712,20 @@ def placement_solve(rows, pieces, L: int, M: int, weights, width: int, max_width
     if n < 1 or pieces.shape != (n, M + 1):
         raise ValueError(f"rows must be [n, 20] and pieces [n, {M + 1}] with n >= 1")
     w = np.asarray(weights, dtype=np.float32).reshape(-1)
-    if w.shape != (NUM_FEATURES,):
-        raise ValueError("weights must be one row of 12")
+    if w.shape not in ((NUM_FEATURES,), (NUM_MOVE_FEATURES,)):
+        raise ValueError("weights must be one row of 12 or of 14")
+    move = w.shape[0] == NUM_MOVE_FEATURES
     placements = [np.flatnonzero(canonical_actions(p, np.arange(NUM_ACTIONS)) == np.arange(NUM_ACTIONS)) for p in range(8)]
     solved, length = np.zeros(n, np.uint8), np.zeros(n, np.int32)
     actions, best_value = np.full((n, M), NO_SECOND, np.uint8), np.zeros((n, M), np.float32)
     # a beam: the nodes' rows, lines, moves, state and value in stored order; tape[j] = (parent's place, placement) of Beam_{j+1}
     beams = [dict(rows=rows[s:s + 1].copy(), lines=np.zeros(1, np.int64), moves=np.zeros(1, np.int64),
-                  state=np.zeros(1, np.int64), value=np.zeros(1, np.float32), tape=[]) for s in range(n)]
+                  state=np.zeros(1, np.int64), value=np.zeros(1, np.float32), sums=np.zeros((1, 2), np.int64), tape=[])
+             for s in range(n)]
     active = list(range(n))
     for ply in range(M):
         # every child of every running node of every configuration still searched, in one batch
-        cfg, place, first, p_rows, p_lines, p_moves, total = [], [], {}, [], [], [], 0
+        cfg, place, first, p_rows, p_lines, p_moves, p_sums, total = [], [], {}, [], [], [], [], 0
         for s in active:                                        # every active configuration has a running node
             run = np.flatnonzero(beams[s]["state"] == STATE_RUNNING)
             b = placements[pieces[s, ply]]
@@ -674,16 +734,19 @@ def placement_solve(rows, pieces, L: int, M: int, weights, width: int, max_width
             total += node.size
             cfg.append(np.full(node.size, s)), place.append(np.tile(b, run.size))
             p_rows.append(beams[s]["rows"][node]), p_lines.append(beams[s]["lines"][node]), p_moves.append(beams[s]["moves"][node])
+            p_sums.append(beams[s]["sums"][node])
         cfg, place = np.concatenate(cfg), np.concatenate(place)
         p_rows, p_lines, p_moves = np.concatenate(p_rows), np.concatenate(p_lines), np.concatenate(p_moves)
+        p_sums, c_sums = np.concatenate(p_sums), np.zeros((total, 2), np.int64)
         c_rows, c_lines, c_moves = np.zeros((total, 20), np.uint16), np.zeros(total, np.int64), np.zeros(total, np.int64)
         c_state, c_value = np.zeros(total, np.int64), np.zeros(total, np.float32)
         for lo in range(0, total, chunk):
             hi = min(total, lo + chunk)
-            r2, _, l2, m2, s2 = host_moves(p_rows[lo:hi], pieces[cfg[lo:hi], ply], place[lo:hi] // 10, place[lo:hi] % 10, L, M,
-                                           p_lines[lo:hi], p_moves[lo:hi])
+            r2, _, l2, m2, s2, _, _, land, erod = host_moves_traced(p_rows[lo:hi], pieces[cfg[lo:hi], ply], place[lo:hi] // 10,
+                                                                    place[lo:hi] % 10, L, M, p_lines[lo:hi], p_moves[lo:hi])
+            c_sums[lo:hi] = p_sums[lo:hi] + np.stack([land, erod], axis=1)
             psi = np.concatenate([np.stack([l2, s2 == STATE_WON, s2 >= STATE_LOST_LIMIT], axis=1).astype(np.int64),
-                                  board_features(r2)], axis=1)
+                                  board_features(r2)] + ([c_sums[lo:hi]] if move else []), axis=1)
             c_rows[lo:hi], c_lines[lo:hi], c_moves[lo:hi], c_state[lo:hi] = r2, l2, m2, s2
             c_value[lo:hi] = placement_score(psi, w)
         still = []
@@ -720,6 +783,7 @@ def placement_solve(rows, pieces, L: int, M: int, weights, width: int, max_width
                             lines=np.where(moved, c_lines[kc0], beam["lines"][kp]),
                             moves=np.where(moved, c_moves[kc0], beam["moves"][kp]),
                             state=np.where(moved, c_state[kc0], beam["state"][kp]),
+                            sums=np.where(moved[:, None], c_sums[kc0], beam["sums"][kp]),
                             value=value[keep], tape=beam["tape"])
             if (beams[s]["state"] == STATE_RUNNING).any():
                 still.append(s)

@@ -28,17 +28,24 @@
 // After the last ply lane 0's node is the choice.  Nothing but the outputs goes to memory.
 // The frame -- the beam in LDS, slot decoding, phase B and the place of phase C -- is tpl_beam.h's, shared with the n-tuple beam
 // (ntuple_beam.hip); phase A's value and what a kept candidate stores are this kernel's.
+//
+// This unit is built twice (tpl_placement.h: kUnitFeatures): as it stands, placement_beam_kernel on the twelve board features, and
+// through beam_move.hip as placement_beam_move_kernel on the fourteen with landing height and eroded cells.  There a node's `cleared`
+// word is the carry of its path (tpl_placement.h): rows cleared, landing sum and eroded sum in 8 + 14 + 10 bits -- the beam in LDS is
+// the same size.
 #include "tpl_beam.h"
 
 namespace tpl_learn {
 namespace {
+
+constexpr int kF = kUnitFeatures;
 
 struct BeamArgs {
     const uint4* a;              // [n]
     const uint4* b;
     uint32_t n;                  // boards = workgroups
     uint32_t L, M;
-    const float* weights;        // [P][12], P = ceil(n / per_member)
+    const float* weights;        // [P][12] or, at 14 features, [P][16]; P = ceil(n / per_member)
     uint32_t per_member;         // boards per weight row, in [1, n]
     uint32_t depth, width;       // D in [1, 12], W in [1, 64]
     uint8_t* action;             // [n]
@@ -46,24 +53,32 @@ struct BeamArgs {
     float* score;                // [n], optional
 };
 
-// Candidate k of running parent q: the board the move leaves (window not yet popped), the rows cleared with the parent's, and
-// the value of psi = (cleared, won, lost, features 3..11).  Phases A and C both come here, so a winner's second making of its
+// Candidate k of running parent q: the board the move leaves (window not yet popped), the move's carry with the parent's (the rows
+// cleared at 12 features), and the value of psi = (cleared, won, lost, features 3..11[, landing sum, eroded sum]).  Phases A and C both come here, so a winner's second making of its
 // move gives the bits of the first.
 __device__ __forceinline__ float expand(const Beam& parent, uint32_t q, uint32_t k, const tpl::ShapeWord* shape, uint32_t L,
-                                        uint32_t M, const float (&w)[kFeatures], tpl::Board& s, uint32_t& cleared, uint32_t& b) {
+                                        uint32_t M, const float (&w)[kF], tpl::Board& s, uint32_t& cleared, uint32_t& b) {
     const uint4 A = parent.a[q], B = parent.b[q];
     uint32_t r, l, cur;
     b = nth_placement(B.w & 7u, k, r, l);
     bool running;                                             // the callers expand running parents only (Slot::finished)
-    cleared = parent.cleared[q] + first_move(A, B, shape, r, l, L, M, s, cur, running);
-    Features psi;
+    cleared = parent.cleared[q] + first_move<kF>(A, B, shape, r, l, L, M, s, cur, running);
+    FeatureSet<kF> psi;
     moved_features(s, cleared, true, psi);
     return placement_score(w, psi);
 }
 
-__global__ __launch_bounds__(kBeamBlock) void placement_beam_kernel(const BeamArgs p) {
+// The 12-feature kernel takes 95 VGPRs by itself: five workgroups a CU.  Left to itself the 14-feature one takes more than 128, which
+// is three; bound to the 96 of five it spills 20 bytes to scratch, so it is bound to four (tools/kernel_resources.sh).
+#ifdef TPL_PLACEMENT_MOVE_UNIT
+#define TPL_BEAM_BOUNDS __launch_bounds__(kBeamBlock, 4)
+#else
+#define TPL_BEAM_BOUNDS __launch_bounds__(kBeamBlock)
+#endif
+__global__ TPL_BEAM_BOUNDS void TPL_UNIT_KERNEL(placement_beam)(const BeamArgs p) {
+    constexpr int kStride = weight_stride<kF>();
     __shared__ tpl::ShapeWord s_shape[32];
-    __shared__ __attribute__((aligned(16))) float s_w[kFeatures];
+    __shared__ __attribute__((aligned(16))) float s_w[kStride];
     __shared__ Beam s_beam[2];
     __shared__ unsigned long long s_key[kMaxCandidates];
     __shared__ unsigned long long s_sel[kMaxWidth];
@@ -71,7 +86,10 @@ __global__ __launch_bounds__(kBeamBlock) void placement_beam_kernel(const BeamAr
     __shared__ uint32_t s_best;
     const uint32_t tid = threadIdx.x, i = blockIdx.x;          // the grid is n blocks
     if (tid < 32) s_shape[tid] = tpl::kShapeTable[tid];
-    if (tid < kFeatures / 4) ((float4*)s_w)[tid] = ((const float4*)(p.weights + (size_t)(i / p.per_member) * kFeatures))[tid];
+    if (tid < kFeatures / 4) ((float4*)s_w)[tid] = ((const float4*)(p.weights + (size_t)(i / p.per_member) * kStride))[tid];
+    if constexpr (kF == kMoveFeatures) {                       // entries 14 and 15 are not read
+        if (tid == kFeatures / 4) ((float2*)s_w)[6] = ((const float2*)(p.weights + (size_t)(i / p.per_member) * kStride))[6];
+    }
     if (tid == 0) {                                            // Beam_0: the root alone
         s_beam[0].a[0] = p.a[i];
         s_beam[0].b[0] = p.b[i];
@@ -82,11 +100,15 @@ __global__ __launch_bounds__(kBeamBlock) void placement_beam_kernel(const BeamAr
         s_best = 0u;
     }
     __syncthreads();
-    float w[kFeatures];
+    float w[kF];
 #pragma unroll
     for (int q = 0; q < kFeatures / 4; ++q) {
         const float4 v = ((const float4*)s_w)[q];
         w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
+    }
+    if constexpr (kF == kMoveFeatures) {
+        const float2 v = ((const float2*)s_w)[6];
+        w[kF - 2] = v.x; w[kF - 1] = v.y;
     }
     const uint4 rootA = s_beam[0].a[0], rootB = s_beam[0].b[0];
     const unsigned long long window = ((unsigned long long)(rootB.z >> 28) << 32) | rootB.w;
@@ -94,9 +116,9 @@ __global__ __launch_bounds__(kBeamBlock) void placement_beam_kernel(const BeamAr
     const uint32_t known = (uint32_t)tpl::kWindowEntries - tpl::packed_moves(rootA) % (uint32_t)tpl::kWindowStride;
     const uint32_t plies = tpl::packed_state(rootB) != tpl::ST_RUNNING ? 0u : min(p.depth, known);
     if (plies == 0u) {
-        Features zero;
+        FeatureSet<kF> zero;
 #pragma unroll
-        for (int k = 0; k < kFeatures; ++k) zero.f[k] = 0u;
+        for (int k = 0; k < kF; ++k) zero.f[k] = 0u;
         if (tid == 0) s_beam[0].value[0] = placement_score(w, zero);
         __syncthreads();
     }
@@ -180,10 +202,10 @@ __global__ __launch_bounds__(kBeamBlock) void placement_beam_kernel(const BeamAr
 
 using namespace tpl_learn;
 
-extern "C" int tpl_placement_beam(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const float* weights,
+extern "C" int TPL_UNIT_ENTRY(tpl_placement_beam)(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const float* weights,
                                   int64_t boards_per_member, int32_t depth, int32_t width, uint8_t* action, uint8_t* plan,
                                   float* score, void* stream) {
-    const char* name = "tpl_placement_beam";
+    const char* name = TPL_UNIT_ENTRY_NAME(tpl_placement_beam);
     if (const int rc = check_policy(name, plane_a, plane_b, n, L, M, weights, boards_per_member, action, score)) return rc;
     if (depth < 1 || depth > kMaxDepth) return fail_msg(TPL_ERR_ARG, "%s: depth must be in [1, %d]", name, kMaxDepth);
     if (width < 1 || width > kMaxWidth) return fail_msg(TPL_ERR_ARG, "%s: width must be in [1, %d]", name, kMaxWidth);
@@ -193,7 +215,7 @@ extern "C" int tpl_placement_beam(const void* plane_a, const void* plane_b, int6
     p.per_member = (uint32_t)(boards_per_member < n ? boards_per_member : n);     // anything above n is the single-policy case
     p.depth = (uint32_t)depth; p.width = (uint32_t)width;
     p.action = action; p.plan = plan; p.score = score;
-    hipLaunchKernelGGL(placement_beam_kernel, dim3(p.n), dim3(kBeamBlock), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(TPL_UNIT_KERNEL(placement_beam), dim3(p.n), dim3(kBeamBlock), 0, (hipStream_t)stream, p);
     TPL_LEARN_HIP(hipGetLastError());
     return TPL_OK;
 }

@@ -20,11 +20,17 @@
 // That frame -- block prologue, lane decode, first move, arg-max and the winner's stores -- is written once, in
 // placement_policy<kPlies>; placement_act_kernel and placement_search_kernel are its two instances.  What a lane's first move
 // is worth is the one thing that differs: its own score at one ply, the best second placement's (best_second) at two.
+//
+// This unit is built twice (tpl_placement.h: kUnitFeatures): as it stands on the twelve board features, and through heuristic_move.hip
+// on the fourteen that add landing height and eroded cells -- placement_features_move_kernel, placement_act_move_kernel,
+// placement_search_move_kernel and the tpl_placement_*_move entries.  What differs is the carry of a move (placed_move), the width of
+// a weight row and of a feature record.
 #include "tpl_placement.h"
 
 namespace tpl_learn {
 namespace {
 
+constexpr int kF = kUnitFeatures;
 constexpr int kBoardsPerBlock = 8;
 constexpr int kActBlock = kBoardsPerBlock * kActions;        // 320 threads: five waves, eight whole boards
 constexpr int kFeatureBlock = 256;
@@ -35,12 +41,12 @@ struct FeatureArgs {
     const uint4* b;
     uint32_t total;              // 40 n, below 2^31
     uint32_t L, M;
-    uint2* features;             // [n][40] records of 24 bytes = three 8-byte words
+    void* features;              // [n][40] records: 24 bytes = three 8-byte words at 12 features, 32 bytes = two 16-byte words at 14
     uint8_t* canonical;          // [n][40], optional
 };
 
-// phi(s, a) of every pair: the twelve features of what action a = 10 r + l leaves of state i; all zero for a finished board
-__global__ __launch_bounds__(kFeatureBlock) void placement_features_kernel(const FeatureArgs p) {
+// phi(s, a) of every pair: the kF features of what action a = 10 r + l leaves of state i; all zero for a finished board
+__global__ __launch_bounds__(kFeatureBlock) void TPL_UNIT_KERNEL(placement_features)(const FeatureArgs p) {
     __shared__ tpl::ShapeWord s_shape[32];
     if (threadIdx.x < 32) s_shape[threadIdx.x] = tpl::kShapeTable[threadIdx.x];
     __syncthreads();
@@ -51,13 +57,20 @@ __global__ __launch_bounds__(kFeatureBlock) void placement_features_kernel(const
     tpl::Board s;
     uint32_t cur;
     bool running;
-    const uint32_t n_clear = first_move(p.a[i], p.b[i], s_shape, r, l, p.L, p.M, s, cur, running);
-    Features phi;
+    const uint32_t n_clear = first_move<kF>(p.a[i], p.b[i], s_shape, r, l, p.L, p.M, s, cur, running);
+    FeatureSet<kF> phi;
     moved_features(s, n_clear, running, phi);
-    uint2* rec = p.features + 3u * (size_t)j;
-    rec[0] = make_uint2(phi.f[0] | (phi.f[1] << 16), phi.f[2] | (phi.f[3] << 16));
-    rec[1] = make_uint2(phi.f[4] | (phi.f[5] << 16), phi.f[6] | (phi.f[7] << 16));
-    rec[2] = make_uint2(phi.f[8] | (phi.f[9] << 16), phi.f[10] | (phi.f[11] << 16));
+    if constexpr (kF == kMoveFeatures) {
+        uint4* rec = (uint4*)p.features + 2u * (size_t)j;
+        rec[0] = make_uint4(phi.f[0] | (phi.f[1] << 16), phi.f[2] | (phi.f[3] << 16), phi.f[4] | (phi.f[5] << 16),
+                            phi.f[6] | (phi.f[7] << 16));
+        rec[1] = make_uint4(phi.f[8] | (phi.f[9] << 16), phi.f[10] | (phi.f[11] << 16), phi.f[kF - 2] | (phi.f[kF - 1] << 16), 0u);
+    } else {
+        uint2* rec = (uint2*)p.features + 3u * (size_t)j;
+        rec[0] = make_uint2(phi.f[0] | (phi.f[1] << 16), phi.f[2] | (phi.f[3] << 16));
+        rec[1] = make_uint2(phi.f[4] | (phi.f[5] << 16), phi.f[6] | (phi.f[7] << 16));
+        rec[2] = make_uint2(phi.f[8] | (phi.f[9] << 16), phi.f[10] | (phi.f[11] << 16));
+    }
     if (p.canonical) p.canonical[j] = (uint8_t)canonical_action(cur, r, l);
 }
 
@@ -66,7 +79,7 @@ struct PolicyArgs {
     const uint4* b;
     uint32_t n;                  // boards; 40 n below 2^31
     uint32_t L, M;
-    const float* weights;        // [P][12], P = ceil(n / per_member)
+    const float* weights;        // [P][12] or, at 14 features, [P][16]; P = ceil(n / per_member)
     uint32_t per_member;         // boards per weight row, in [1, n]
     uint8_t* action;             // [n]
     uint8_t* second;             // [n], optional; null at one ply
@@ -79,16 +92,18 @@ struct PolicyArgs {
 template <int kPlies>
 __device__ __forceinline__ void placement_policy(const PolicyArgs& p) {
     __shared__ tpl::ShapeWord s_shape[32];
-    __shared__ __attribute__((aligned(16))) float s_w[kBoardsPerBlock][kFeatures];
+    constexpr int kStride = weight_stride<kF>();
+    __shared__ __attribute__((aligned(16))) float s_w[kBoardsPerBlock][kStride];
     __shared__ unsigned long long s_best[kBoardsPerBlock];
     const uint32_t first = blockIdx.x * kBoardsPerBlock;                // the block's boards: first .. first + 7
     if (threadIdx.x < 32) s_shape[threadIdx.x] = tpl::kShapeTable[threadIdx.x];
     if (threadIdx.x < kBoardsPerBlock) {
         s_best[threadIdx.x] = 0ull;                                     // below every key: a key's high word has a bit set
         const uint32_t board = min(first + threadIdx.x, p.n - 1u);
-        const float4* row = (const float4*)(p.weights + (size_t)(board / p.per_member) * kFeatures);
+        const float4* row = (const float4*)(p.weights + (size_t)(board / p.per_member) * kStride);
         float4* dst = (float4*)s_w[threadIdx.x];
         dst[0] = row[0]; dst[1] = row[1]; dst[2] = row[2];
+        if constexpr (kF == kMoveFeatures) ((float2*)dst)[6] = ((const float2*)row)[6];       // entries 14 and 15 are not read
     }
     __syncthreads();
     const uint32_t slot = threadIdx.x / kActions, a = threadIdx.x - slot * kActions;
@@ -100,16 +115,20 @@ __device__ __forceinline__ void placement_policy(const PolicyArgs& p) {
     tpl::Board s1;
     uint32_t cur;
     bool running;
-    const uint32_t n1 = first_move(p.a[src], p.b[src], s_shape, r, l, p.L, p.M, s1, cur, running);
+    const uint32_t n1 = first_move<kF>(p.a[src], p.b[src], s_shape, r, l, p.L, p.M, s1, cur, running);
     const bool contends = valid && canonical_action(cur, r, l) == a;
     // the weight row, read back here and not ahead of the first move: there both kernels measured 2 % slower on an MI355X
     // at the same instruction counts (profiles/learner/README.md)
-    float w[kFeatures];
+    float w[kF];
     const float4* row = (const float4*)s_w[slot];
 #pragma unroll
     for (int q = 0; q < kFeatures / 4; ++q) {
         const float4 v = row[q];
         w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
+    }
+    if constexpr (kF == kMoveFeatures) {
+        const float2 v = ((const float2*)row)[6];
+        w[kF - 2] = v.x; w[kF - 1] = v.y;
     }
     bool goes_on = false;
     if constexpr (kPlies == 2) {
@@ -120,13 +139,13 @@ __device__ __forceinline__ void placement_policy(const PolicyArgs& p) {
     float value;
     uint32_t second = kNoSecond;
     if (goes_on) {
-        value = best_second(s1, s_shape, p.L, p.M, second, [&](const tpl::Board& s2, uint32_t n2) {
-            Features psi;
-            moved_features(s2, n1 + n2, true, psi);                     // the rows of both moves, the board of the second
+        value = best_second<kF>(s1, s_shape, p.L, p.M, second, [&](const tpl::Board& s2, uint32_t n2) {
+            FeatureSet<kF> psi;
+            moved_features(s2, n1 + n2, true, psi);                     // the carries of both moves, the board of the second
             return placement_score(w, psi);
         });
     } else {
-        Features phi;
+        FeatureSet<kF> phi;
         moved_features(s1, n1, running, phi);
         value = placement_score(w, phi);
     }
@@ -140,8 +159,8 @@ __device__ __forceinline__ void placement_policy(const PolicyArgs& p) {
     }
 }
 
-__global__ __launch_bounds__(kActBlock) void placement_act_kernel(const PolicyArgs p) { placement_policy<1>(p); }
-__global__ __launch_bounds__(kActBlock) void placement_search_kernel(const PolicyArgs p) { placement_policy<2>(p); }
+__global__ __launch_bounds__(kActBlock) void TPL_UNIT_KERNEL(placement_act)(const PolicyArgs p) { placement_policy<1>(p); }
+__global__ __launch_bounds__(kActBlock) void TPL_UNIT_KERNEL(placement_search)(const PolicyArgs p) { placement_policy<2>(p); }
 
 }  // namespace
 }  // namespace tpl_learn
@@ -160,35 +179,37 @@ int launch_policy(const char* name, int plies, const void* plane_a, const void* 
     p.per_member = (uint32_t)(boards_per_member < n ? boards_per_member : n);     // anything above n is the single-policy case
     p.action = action; p.second = second; p.score = score;
     const dim3 grid((p.n + kBoardsPerBlock - 1) / kBoardsPerBlock), block(kActBlock);
-    hipLaunchKernelGGL(plies == 2 ? placement_search_kernel : placement_act_kernel, grid, block, 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(plies == 2 ? TPL_UNIT_KERNEL(placement_search) : TPL_UNIT_KERNEL(placement_act), grid, block, 0,
+                       (hipStream_t)stream, p);
     TPL_LEARN_HIP(hipGetLastError());
     return TPL_OK;
 }
 
 }  // namespace
 
-extern "C" int tpl_placement_features(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M,
+extern "C" int TPL_UNIT_ENTRY(tpl_placement_features)(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M,
                                       int16_t* features, uint8_t* canonical, void* stream) {
-    const char* name = "tpl_placement_features";
+    const char* name = TPL_UNIT_ENTRY_NAME(tpl_placement_features);
+    constexpr unsigned align = kF == kMoveFeatures ? 16u : 8u;                       // the width of a record's stores
     if (const int rc = check_planes(name, plane_a, plane_b, n, L, M)) return rc;
     if (!features) return fail_msg(TPL_ERR_ARG, "%s: null pointer (features is required)", name);
-    if ((uintptr_t)features & 7u) return fail_msg(TPL_ERR_ARG, "%s: features must be 8-byte aligned", name);
+    if ((uintptr_t)features & (align - 1u)) return fail_msg(TPL_ERR_ARG, "%s: features must be %u-byte aligned", name, align);
     FeatureArgs p{};
     p.a = (const uint4*)plane_a; p.b = (const uint4*)plane_b; p.total = (uint32_t)(n * kActions);
-    p.L = (uint32_t)L; p.M = (uint32_t)M; p.features = (uint2*)features; p.canonical = canonical;
+    p.L = (uint32_t)L; p.M = (uint32_t)M; p.features = features; p.canonical = canonical;
     const dim3 grid((p.total + kFeatureBlock - 1) / kFeatureBlock), block(kFeatureBlock);
-    hipLaunchKernelGGL(placement_features_kernel, grid, block, 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(TPL_UNIT_KERNEL(placement_features), grid, block, 0, (hipStream_t)stream, p);
     TPL_LEARN_HIP(hipGetLastError());
     return TPL_OK;
 }
 
-extern "C" int tpl_placement_act(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const float* weights,
+extern "C" int TPL_UNIT_ENTRY(tpl_placement_act)(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const float* weights,
                                  int64_t boards_per_member, uint8_t* action, float* score, void* stream) {
-    return launch_policy("tpl_placement_act", 1, plane_a, plane_b, n, L, M, weights, boards_per_member, action, nullptr, score, stream);
+    return launch_policy(TPL_UNIT_ENTRY_NAME(tpl_placement_act), 1, plane_a, plane_b, n, L, M, weights, boards_per_member, action, nullptr, score, stream);
 }
 
-extern "C" int tpl_placement_search(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const float* weights,
+extern "C" int TPL_UNIT_ENTRY(tpl_placement_search)(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const float* weights,
                                     int64_t boards_per_member, uint8_t* action, uint8_t* second, float* score, void* stream) {
-    return launch_policy("tpl_placement_search", 2, plane_a, plane_b, n, L, M, weights, boards_per_member, action, second, score,
+    return launch_policy(TPL_UNIT_ENTRY_NAME(tpl_placement_search), 2, plane_a, plane_b, n, L, M, weights, boards_per_member, action, second, score,
                          stream);
 }

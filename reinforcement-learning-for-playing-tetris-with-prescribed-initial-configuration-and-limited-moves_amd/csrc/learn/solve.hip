@@ -22,11 +22,17 @@
 //               (Two beams of whole paths would be the same 32 KB at the limits and would copy up to 254 bytes per kept node and
 //               ply.)
 // Nothing but the outputs goes to memory.
+//
+// This unit is built twice (tpl_placement.h: kUnitFeatures): as it stands, placement_solve_kernel on the twelve board features, and
+// through solve_move.hip as placement_solve_move_kernel on the fourteen with landing height and eroded cells.  There a node's `cleared`
+// word is the carry of its path (tpl_placement.h): over the 254 moves of the longest game the landing sum is at most 254 * 38 = 9,652,
+// which fits its 14 bits.
 #include "tpl_beam.h"
 
 namespace tpl_learn {
 namespace {
 
+constexpr int kF = kUnitFeatures;
 constexpr int kSolveMaxMoves = 254;                           // M's limit (tpl_create's): a path fits kBeamBlock bytes
 static_assert(kSolveMaxMoves + 1 <= kBeamBlock, "one lane per piece of the list and per byte of the path");
 static_assert(kMaxWidth <= 256, "a parent's place fits the tape's low byte");
@@ -36,7 +42,7 @@ struct SolveArgs {
     const uint8_t* pieces;       // [n][M + 1]
     uint32_t n;                  // configurations = workgroups
     uint32_t L, M;
-    const float* weights;        // [12]
+    const float* weights;        // [12], or the first 14 of a row of 16
     uint32_t width;              // W in [1, 64]
     uint8_t* solved;             // [n]
     int32_t* solution_len;       // [n]
@@ -44,20 +50,19 @@ struct SolveArgs {
     float* best_value;           // [n][M], optional
 };
 
-// Candidate k of running parent q under the ply's piece `cur`: the board the move leaves, the rows cleared with the parent's, and
-// the value of psi = (cleared, won, lost, features 3..11).  Phases A and C and the winning ply all come here, so a candidate's
+// Candidate k of running parent q under the ply's piece `cur`: the board the move leaves, the move's carry with the parent's (the
+// rows cleared at 12 features), and the value of psi = (cleared, won, lost, features 3..11[, landing sum, eroded sum]).  Phases A and C and the winning ply all come here, so a candidate's
 // second making gives the bits of the first.
 __device__ __forceinline__ float expand(const Beam& parent, uint32_t q, uint32_t k, uint32_t cur, const tpl::ShapeWord* shape,
-                                        uint32_t L, uint32_t M, const float (&w)[kFeatures], tpl::Board& s, uint32_t& cleared,
+                                        uint32_t L, uint32_t M, const float (&w)[kF], tpl::Board& s, uint32_t& cleared,
                                         uint32_t& b) {
     uint32_t r, l;
     b = nth_placement(cur, k, r, l);
     tpl::unpack_board(parent.a[q], parent.b[q], s);
     s.window = cur;                                           // the list's piece; the entries behind it are not part of the rule
     s.window_hi = 0u;
-    bool topout;
-    cleared = parent.cleared[q] + tpl::move_board(s, shape, r, l, L, M, topout);
-    Features psi;
+    cleared = parent.cleared[q] + placed_move<kF>(s, shape, r, l, L, M);
+    FeatureSet<kF> psi;
     moved_features(s, cleared, true, psi);
     return placement_score(w, psi);
 }
@@ -71,7 +76,7 @@ __device__ __forceinline__ unsigned long long max4(const unsigned long long* v) 
 
 // Five waves a SIMD, five workgroups a CU, as placement_beam_kernel has: 95 VGPRs without scratch once the weight row sits in SGPRs
 // (tools/kernel_resources.sh; left to itself the allocator takes 105, which is four groups).
-__global__ __launch_bounds__(kBeamBlock, 5) void placement_solve_kernel(const SolveArgs p) {
+__global__ __launch_bounds__(kBeamBlock, 5) void TPL_UNIT_KERNEL(placement_solve)(const SolveArgs p) {
     extern __shared__ __attribute__((aligned(16))) uint16_t s_tape[];   // [M][W]: parent's place | placement << 8
     __shared__ tpl::ShapeWord s_shape[32];
     __shared__ Beam s_beam[2];
@@ -110,9 +115,9 @@ __global__ __launch_bounds__(kBeamBlock, 5) void placement_solve_kernel(const So
         s_beam[0].cleared[0] = 0u;
     }
     __syncthreads();
-    float w[kFeatures];                                        // one row for the whole grid: scalar loads, the weights stay in SGPRs
+    float w[kF];                                               // one row for the whole grid: scalar loads, the weights stay in SGPRs
 #pragma unroll
-    for (int q = 0; q < kFeatures; ++q) w[q] = p.weights[q];
+    for (int q = 0; q < kF; ++q) w[q] = p.weights[q];
     float* const best_value = p.best_value ? p.best_value + (size_t)i * M : nullptr;
 
     uint32_t nodes = 1u, plies = 0u, length = 0u;              // plies run; the winning ply, 0 while there is none
@@ -231,10 +236,10 @@ __global__ __launch_bounds__(kBeamBlock, 5) void placement_solve_kernel(const So
 
 using namespace tpl_learn;
 
-extern "C" int tpl_placement_solve(const int16_t* rows, const uint8_t* pieces, int64_t n, int32_t L, int32_t M,
+extern "C" int TPL_UNIT_ENTRY(tpl_placement_solve)(const int16_t* rows, const uint8_t* pieces, int64_t n, int32_t L, int32_t M,
                                    const float* weights, int32_t width, uint8_t* solved, int32_t* solution_len, uint8_t* actions,
                                    float* best_value, void* stream) {
-    const char* name = "tpl_placement_solve";
+    const char* name = TPL_UNIT_ENTRY_NAME(tpl_placement_solve);
     if (!rows || !pieces || !weights || !solved || !solution_len || !actions)
         return fail_msg(TPL_ERR_ARG, "%s: null pointer (only best_value is optional)", name);
     if (n < 1) return fail_msg(TPL_ERR_ARG, "%s: n must be positive", name);
@@ -251,7 +256,7 @@ extern "C" int tpl_placement_solve(const int16_t* rows, const uint8_t* pieces, i
     p.L = (uint32_t)L; p.M = (uint32_t)M; p.weights = weights; p.width = (uint32_t)width;
     p.solved = solved; p.solution_len = solution_len; p.actions = actions; p.best_value = best_value;
     const size_t tape = ((size_t)2 * p.width * p.M + 15u) & ~(size_t)15u;         // at most 32,512 bytes
-    hipLaunchKernelGGL(placement_solve_kernel, dim3(p.n), dim3(kBeamBlock), tape, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(TPL_UNIT_KERNEL(placement_solve), dim3(p.n), dim3(kBeamBlock), tape, (hipStream_t)stream, p);
     TPL_LEARN_HIP(hipGetLastError());
     return TPL_OK;
 }

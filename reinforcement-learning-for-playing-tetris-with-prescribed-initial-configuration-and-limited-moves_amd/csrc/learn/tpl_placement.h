@@ -1,6 +1,11 @@
 // tpl_placement.h -- what the placement family shares (afterstates.hip, heuristic.hip, beam.hip, ntuple.hip; include/tpl_learn.h
 // states the rules): which of the 40 actions are one placement, the first move of a (board, action) pair and its reward, the
 // board features, the score and its ordered key, the second ply's loop, and the argument checks of the entry points that read a pair of state planes.
+//
+// Two feature sets.  kFeatures = 12 describes the board a move leaves.  kMoveFeatures = 14 adds the two features of the move itself,
+// landing height and eroded cells; placed_move<14> is the one place they are made, from move_trace's drop and cleared-row mask.
+// What a path carries of its moves is one word, the CARRY: the rows cleared at 12, and at 14 the rows cleared, the landing sum and the
+// eroded sum in 8 + 14 + 10 bits, so that the carries of two moves add field by field with one add.
 #pragma once
 
 #include "tpl_learn_internal.h"
@@ -10,6 +15,33 @@ namespace tpl_learn {
 
 constexpr int kActions = TPL_NUM_ACTIONS;
 constexpr int kFeatures = TPL_NUM_FEATURES;
+constexpr int kMoveFeatures = TPL_NUM_MOVE_FEATURES;
+
+// A unit of the linear placement family (heuristic.hip, beam.hip, solve.hip) is written once and built twice: as it stands on the
+// twelve board features, and once more on the fourteen through its twin (heuristic_move.hip, ...), which defines
+// TPL_PLACEMENT_MOVE_UNIT and includes it.  Two units and not two instances in one: with both feature sets in one translation unit the
+// compiler orders a few instructions of the 12-feature kernels differently (profiles/learner/move_features_isa.log).  kUnitFeatures is
+// the unit's feature set; TPL_UNIT_KERNEL(placement_act) and TPL_UNIT_ENTRY(tpl_placement_act) are the names of a kernel and an entry
+// point in it: placement_act_kernel / tpl_placement_act, or placement_act_move_kernel / tpl_placement_act_move.
+#ifdef TPL_PLACEMENT_MOVE_UNIT
+constexpr int kUnitFeatures = kMoveFeatures;
+#define TPL_UNIT_KERNEL(stem) stem##_move_kernel
+#define TPL_UNIT_ENTRY(stem) stem##_move
+#define TPL_UNIT_ENTRY_NAME(stem) #stem "_move"
+#else
+constexpr int kUnitFeatures = kFeatures;
+#define TPL_UNIT_KERNEL(stem) stem##_kernel
+#define TPL_UNIT_ENTRY(stem) stem
+#define TPL_UNIT_ENTRY_NAME(stem) #stem
+#endif
+constexpr int kMoveWeightStride = TPL_MOVE_WEIGHT_STRIDE;
+// floats between two weight rows of feature set kF
+template <int kF> constexpr int weight_stride() { return kF == kMoveFeatures ? kMoveWeightStride : kF; }
+
+// the carry's fields at 14 features: a path clears at most 253 rows, lands at most 254 * 38 = 9,652 half rows and erodes at most
+// 4 (L + 3) <= 1,012 cells
+constexpr uint32_t kLandShift = 8u, kErodedShift = 22u;
+static_assert(254u * 38u < (1u << (kErodedShift - kLandShift)) && 4u * 253u < (1u << (32u - kErodedShift)), "the sums fit their fields");
 
 // canonical[a] = 10 (r mod nrot(cur)) + min(l, 10 - w(cur, r)) for a = 10 r + l, r < 4, l < 10; reads tpl_mirror.h's packed
 // widths and rotation masks instead of a dependent load of the shape table
@@ -34,17 +66,85 @@ constexpr bool walk_visits_the_canonical_actions() {
 }
 static_assert(walk_visits_the_canonical_actions(), "next_placement and placement_count do not match canonical_action");
 
+// What move_board (csrc/tpl_device.h) keeps to itself of the move it is about to make on `s`: the drop -- the row of the piece's top-most
+// mask row after the fall, from the column tops under the piece exactly as move_board takes it --, the rows that are full once the
+// piece is locked and that move_board will clear (bit r = row r), and the shape word with the piece's column nibbles and height.  A
+// top-out makes no move: drop and clear are 0.  Called on the board BEFORE the move.  The board itself is still made by move_board
+// alone: this only reads, so nothing it says can change a game, and the environment's header stays as it is (its digest names
+// the committed profiles).  The tops are move_board's own expressions, which the compiler shares between the two; the rest, some
+// eighty instructions a pair, is made twice.
+struct MoveTrace { uint32_t drop, clear, shape; };
+
+__device__ __forceinline__ MoveTrace move_trace(const tpl::Board& s, const tpl::ShapeWord* shape, uint32_t rot, uint32_t loc) {
+    const tpl::ShapeWord sh = shape[(s.window & 7u) * 4u + (rot & 3u)];
+    const uint32_t w = (sh.x >> 16) & 7u;
+    const uint32_t h = (sh.x >> 19) & 7u;
+    loc = min(loc, (uint32_t)tpl::kCols - w);
+    // the tops of the four columns under the piece as bytes, plus the table's per-column bias: drop = min - 4
+    uint32_t t[tpl::kCols];
+#pragma unroll
+    for (int k = 0; k < tpl::kCols; ++k) t[k] = (uint32_t)__builtin_ctz(s.c[k] | tpl::kSentinelBit);
+    const uint32_t p0 = t[0] | (t[1] << 8) | (t[2] << 16) | (t[3] << 24);
+    const uint32_t p1 = t[4] | (t[5] << 8) | (t[6] << 16) | (t[7] << 24);
+    const uint32_t p2 = t[8] | (t[9] << 8);
+    const uint32_t word = loc >> 2;
+    const uint32_t lo = word == 0u ? p0 : word == 1u ? p1 : p2;
+    const uint32_t hi = word == 0u ? p1 : word == 1u ? p2 : 0u;
+    const uint32_t sums = __builtin_amdgcn_alignbyte(hi, lo, loc & 3u) + sh.y;
+    const uint32_t best = min(min(sums & 0xFFu, (sums >> 8) & 0xFFu), min((sums >> 16) & 0xFFu, sums >> 24));
+    const bool topout = best < 4u;
+    const uint32_t drop = topout ? 0u : best - 4u;
+    // the rows that are full with the piece's column nibbles, shifted down by drop, in their columns
+    const uint64_t placed = (uint64_t)(sh.x & 0xFFFFu) << (4u * loc);
+    const uint32_t plo = (uint32_t)placed, phi = (uint32_t)(placed >> 32);
+    uint32_t full = 0xFFFFFFFFu;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) full &= s.c[k] | (((plo >> (4 * k)) & 0xFu) << drop);
+    full &= s.c[8] | ((phi & 0xFu) << drop);
+    full &= s.c[9] | (((phi >> 4) & 0xFu) << drop);
+    MoveTrace trace;
+    trace.drop = drop;
+    trace.clear = topout ? 0u : full & (((1u << h) - 1u) << drop);
+    trace.shape = sh.x;
+    return trace;
+}
+
+// move_board(s, r, l) and the carry of the move.  At 12 features that is the rows cleared and the code is move_board's.  At 14 it
+// is  n | landing_height << 8 | eroded_cells << 22  (include/tpl_learn.h, features 12 and 13): with drop the row of the piece's top
+// mask row and h the shape's height the piece lies in rows drop .. drop + h - 1, so landing_height = 39 - 2 drop - h; the piece's
+// cells in cleared rows are the bits of its four column nibbles at the cleared rows' offsets below drop, and eroded_cells is n times
+// their count.  A top-out makes no move: both are 0.
+template <int kF = kFeatures>
+__device__ __forceinline__ uint32_t placed_move(tpl::Board& s, const tpl::ShapeWord* shape, uint32_t r, uint32_t l, uint32_t L,
+                                                uint32_t M) {
+    bool topout;
+    if constexpr (kF == kMoveFeatures) {
+        // both features before the move, so that one word and not the trace lives across it
+        const MoveTrace trace = move_trace(s, shape, r, l);
+        const uint32_t h = (trace.shape >> 19) & 7u;
+        const uint32_t rows = (trace.clear >> trace.drop) & 0xFu;            // the cleared rows among the piece's, bit i = mask row i
+        const uint32_t cells = (uint32_t)__builtin_popcount(trace.shape & 0xFFFFu & (rows * 0x1111u));
+        const uint32_t eroded = __umul24((uint32_t)__builtin_popcount(rows), cells);
+        const uint32_t landing = 39u - 2u * trace.drop - h;
+        const uint32_t features = (landing << kLandShift) | (eroded << kErodedShift);
+        const uint32_t n = tpl::move_board(s, shape, r, l, L, M, topout);
+        return n | (topout ? 0u : features);
+    } else {
+        return tpl::move_board(s, shape, r, l, L, M, topout);
+    }
+}
+
 // The first move of pair (state (A, B), action 10 r + l): `s` becomes the board the move leaves, its window not yet popped;
 // `cur` is the piece that was placed and `running` whether the state was still in play (a finished board's move means
-// nothing: the callers select on `running`).  Returns the rows cleared.  r and l are values, never register indices
-// (move_board's comment says why).
+// nothing: the callers select on `running`).  Returns the move's carry: the rows cleared at 12 features.  r and l are values,
+// never register indices (move_board's comment says why).
+template <int kF = kFeatures>
 __device__ __forceinline__ uint32_t first_move(const uint4& A, const uint4& B, const tpl::ShapeWord* shape, uint32_t r, uint32_t l,
                                                uint32_t L, uint32_t M, tpl::Board& s, uint32_t& cur, bool& running) {
     tpl::unpack_board(A, B, s);
     cur = s.window & 7u;
     running = s.state == tpl::ST_RUNNING;
-    bool topout;
-    return tpl::move_board(s, shape, r, l, L, M, topout);
+    return placed_move<kF>(s, shape, r, l, L, M);
 }
 
 // step_reward's rule (csrc/tpl_step.h) for a move that cleared n_clear rows and left `state`: one rounded multiply, then at most
@@ -57,14 +157,16 @@ __device__ __forceinline__ float move_reward(float r_line, float r_win, float r_
     return reward;
 }
 
-struct Features { uint32_t f[kFeatures]; };
+template <int kF> struct FeatureSet { uint32_t f[kF]; };
+using Features = FeatureSet<kFeatures>;
 
 // popcount(x) + acc: v_bcnt_u32_b32 adds its second operand
 __device__ __forceinline__ uint32_t bcnt(uint32_t x, uint32_t acc) { return (uint32_t)__builtin_popcount(x) + acc; }
 __device__ __forceinline__ uint32_t absdiff(uint32_t a, uint32_t b) { return max(a, b) - min(a, b); }
 
 // features 3..11 of a board given as its ten column words (bit r = row r, row 0 = top; bits 20.. clear)
-__device__ __forceinline__ void board_features(const uint32_t (&c)[tpl::kCols], Features& out) {
+template <int kF>
+__device__ __forceinline__ void board_features(const uint32_t (&c)[tpl::kCols], FeatureSet<kF>& out) {
     constexpr uint32_t kFloor = tpl::kSentinelBit;            // row 20: the floor, filled
     uint32_t t[tpl::kCols];                                   // top of column x: row of its top-most filled cell, 20 if empty
 #pragma unroll
@@ -119,22 +221,31 @@ __device__ __forceinline__ void board_features(const uint32_t (&c)[tpl::kCols], 
     out.f[11] = depth;
 }
 
-// phi of the board `s` that a move (or two) left: rows cleared, won, lost and board_features; all zero where `live` is false
-__device__ __forceinline__ void moved_features(const tpl::Board& s, uint32_t n_clear, bool live, Features& out) {
+// phi of the board `s` that a move (or more) left, `carry` being the summed carries of the moves: rows cleared, won, lost and
+// board_features, at 14 features the landing and eroded sums behind them; all zero where `live` is false
+template <int kF>
+__device__ __forceinline__ void moved_features(const tpl::Board& s, uint32_t carry, bool live, FeatureSet<kF>& out) {
     board_features(s.c, out);
-    out.f[0] = n_clear;
+    if constexpr (kF == kMoveFeatures) {
+        out.f[0] = carry & ((1u << kLandShift) - 1u);
+        out.f[12] = (carry >> kLandShift) & ((1u << (kErodedShift - kLandShift)) - 1u);
+        out.f[13] = carry >> kErodedShift;
+    } else {
+        out.f[0] = carry;
+    }
     out.f[1] = s.state == tpl::ST_WON ? 1u : 0u;
     out.f[2] = s.state >= tpl::ST_LOST_LIMIT ? 1u : 0u;
 #pragma unroll
-    for (int k = 0; k < kFeatures; ++k) out.f[k] = live ? out.f[k] : 0u;
+    for (int k = 0; k < kF; ++k) out.f[k] = live ? out.f[k] : 0u;
 }
 
 // w . phi left to right in float32: every product and every sum rounded once -- contraction off, as move_reward
-__device__ __forceinline__ float placement_score(const float (&w)[kFeatures], const Features& phi) {
+template <int kF>
+__device__ __forceinline__ float placement_score(const float (&w)[kF], const FeatureSet<kF>& phi) {
 #pragma clang fp contract(off)
     float s = w[0] * (float)phi.f[0];
 #pragma unroll
-    for (int k = 1; k < kFeatures; ++k) s = s + w[k] * (float)phi.f[k];
+    for (int k = 1; k < kF; ++k) s = s + w[k] * (float)phi.f[k];
     return s;
 }
 
@@ -149,11 +260,11 @@ constexpr uint32_t kNoSecond = 255u;
 
 // The second ply with the known next piece: the best  worth(s2, n2)  among the distinct placements of s1's current piece on s1,
 // the popped and still running board a first move left, and in `second` the placement it belongs to.  Copies s1, moves (s2 is
-// what the move leaves, its window not yet popped, n2 the rows it cleared; `worth` may change s2) and scores once per distinct
+// what the move leaves, its window not yet popped, n2 the move's carry: the rows it cleared at 12 features; `worth` may change s2) and scores once per distinct
 // placement in ascending b = 10 r2 + l2 -- 9, 17 or 34 trips, the same for the 40 lanes of a board -- and keeps a running
 // best under a strict > on the ordered key, so the lowest b survives.  r2 and l2 are values out of the packed widths, never
 // register indices.  The one loop of tpl_placement_search and tpl_ntuple_search: they enumerate and tie-break alike by it.
-template <typename Worth>
+template <int kF = kFeatures, typename Worth>
 __device__ __forceinline__ float best_second(const tpl::Board& s1, const tpl::ShapeWord* shape, uint32_t L, uint32_t M,
                                              uint32_t& second, Worth worth) {
     const uint32_t nxt = s1.window & 7u;
@@ -163,8 +274,7 @@ __device__ __forceinline__ float best_second(const tpl::Board& s1, const tpl::Sh
 #pragma unroll 1
     while (r2 <= last_rot) {
         tpl::Board s2 = s1;
-        bool topout;
-        const uint32_t n2 = tpl::move_board(s2, shape, r2, l2, L, M, topout);
+        const uint32_t n2 = placed_move<kF>(s2, shape, r2, l2, L, M);
         const float q = worth(s2, n2);
         const uint32_t key = ordered_bits(q);                           // never 0, so the first trip is taken
         if (key > best_key) { best_key = key; best = q; second = 10u * r2 + l2; }

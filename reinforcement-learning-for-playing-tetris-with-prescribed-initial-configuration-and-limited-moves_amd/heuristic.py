@@ -17,6 +17,11 @@
                                   the weights by the noisy cross-entropy method (Szita & Lorincz 2006), fitness = win rate
 
 With weights (r_line, r_win, r_lose, 0, ..., 0) the policy is LookaheadPolicy(env, image=None): the best immediate reward.
+
+The 14-feature form.  Weights of 14 entries ([14] or [P, 14], MOVE_FEATURE_NAMES) select it everywhere above: the twelve features
+of the board a move leaves and the two of the move itself, landing_height and eroded_cells, which deeper than one ply add up along
+the path as `cleared` does.  placement_features(env, move=True) gives int16 [K, 40, 14].  DELLACHERIE_WEIGHTS is Dellacherie's
+published controller in this feature order, a named starting point with no win-rate claim attached.
 """
 from __future__ import annotations
 
@@ -26,37 +31,50 @@ import numpy as np
 import torch
 
 from . import _learn_lib
-from ._learn_lib import BEAM_MAX_DEPTH, BEAM_MAX_WIDTH, FEATURE_NAMES, NUM_ACTIONS, NUM_FEATURES, check
+from ._learn_lib import (BEAM_MAX_DEPTH, BEAM_MAX_WIDTH, FEATURE_COUNTS, FEATURE_NAMES, MOVE_FEATURE_NAMES, MOVE_WEIGHT_STRIDE,
+                         NUM_ACTIONS, NUM_FEATURES, NUM_MOVE_FEATURES, check)
 from .lookahead import _boards, _ptr, _source_planes, _state_ptrs
 
-__all__ = ["FEATURE_NAMES", "placement_features", "HeuristicPolicy", "BeamPolicy", "evaluate_heuristic", "tune_heuristic"]
+__all__ = ["FEATURE_NAMES", "MOVE_FEATURE_NAMES", "DELLACHERIE_WEIGHTS", "placement_features", "HeuristicPolicy", "BeamPolicy",
+           "evaluate_heuristic", "tune_heuristic"]
+
+# Dellacherie's controller in MOVE_FEATURE_NAMES' order and units: holes -4, row and column transitions -1, wells -1, landing height
+# -1 a row = -0.5 a half row, eroded cells +1; won and lost +-100 stand in for the end of the game, which his endless game has not
+DELLACHERIE_WEIGHTS = np.array([0, 100, -100, -4, 0, 0, 0, -1, -1, -1, 0, 0, -0.5, 1], np.float32)
+DELLACHERIE_WEIGHTS.setflags(write=False)
 
 
-def placement_features(env, states_a: Optional[torch.Tensor] = None, states_b: Optional[torch.Tensor] = None):
+def placement_features(env, states_a: Optional[torch.Tensor] = None, states_b: Optional[torch.Tensor] = None, move: bool = False):
     """phi(s, a) for K states and all 40 actions: the resident boards of `env` (K = env.num_envs, read in place), or int32
     [K, 4] plane pairs as env.expand_states takes them, under env.L and env.M.  Returns (features int16 [K, 40, 12], canonical
     uint8 [K, 40]); entry [i, a] belongs to action a = 10 r + l played from state i, a == canonical[i, a] marks the distinct
-    placements, and a finished board's features are all zero."""
+    placements, and a finished board's features are all zero.  move=True: the 14-feature form, int16 [K, 40, 14] (a view of the
+    kernel's 16-wide records), landing_height and eroded_cells behind the twelve."""
+    if not isinstance(move, (bool, np.bool_)):
+        raise ValueError("move must be True or False")
     k, src_a, src_b = _source_planes(env, states_a, states_b, "placement_features")
     d = env.device
-    features = torch.empty((k, NUM_ACTIONS, NUM_FEATURES), dtype=torch.int16, device=d)
+    count = NUM_MOVE_FEATURES if move else NUM_FEATURES
+    features = torch.empty((k, NUM_ACTIONS, MOVE_WEIGHT_STRIDE if move else NUM_FEATURES), dtype=torch.int16, device=d)
     canonical = torch.empty((k, NUM_ACTIONS), dtype=torch.uint8, device=d)
     stream = torch._C._cuda_getCurrentRawStream(d.index)
-    check(_learn_lib.lib().tpl_placement_features(_ptr(src_a), _ptr(src_b), k, env.L, env.M, features.data_ptr(), canonical.data_ptr(), stream))
-    return features, canonical
+    check(_learn_lib.entry("features", count)(_ptr(src_a), _ptr(src_b), k, env.L, env.M, features.data_ptr(), canonical.data_ptr(),
+                                              stream))
+    return features[:, :, :count], canonical
 
 
 def _weights(weights) -> np.ndarray:
-    """Anything array-like of shape [12] or [P, 12] -> finite float32 [P, 12]."""
+    """Anything array-like of shape [12] or [P, 12] -> finite float32 [P, 12]; [14] or [P, 14], the 14-feature form, likewise."""
     if isinstance(weights, torch.Tensor):
         weights = weights.detach().cpu().numpy()
     w = np.asarray(weights)
     if w.dtype == object or not (np.issubdtype(w.dtype, np.floating) or np.issubdtype(w.dtype, np.integer)):
-        raise ValueError(f"weights must be numbers of shape [{NUM_FEATURES}] or [P, {NUM_FEATURES}]")
+        raise ValueError(f"weights must be numbers of shape [{NUM_FEATURES}] or [P, {NUM_FEATURES}] (or {NUM_MOVE_FEATURES})")
     if w.ndim == 1:
         w = w[None]
-    if w.ndim != 2 or w.shape[1] != NUM_FEATURES or w.shape[0] < 1:
-        raise ValueError(f"weights must have shape [{NUM_FEATURES}] or [P, {NUM_FEATURES}], got {tuple(np.shape(weights))}")
+    if w.ndim != 2 or w.shape[1] not in FEATURE_COUNTS or w.shape[0] < 1:
+        raise ValueError(f"weights must have shape [{NUM_FEATURES}] or [P, {NUM_FEATURES}] (or {NUM_MOVE_FEATURES}: the 14-feature "
+                         f"form), got {tuple(np.shape(weights))}")
     with np.errstate(over="ignore"):
         w = np.ascontiguousarray(w, dtype=np.float32)
     if not np.isfinite(w).all():
@@ -99,8 +117,10 @@ class _WeightedPolicy:
         w = _weights(weights)
         n = _boards(env, type(self).__name__)
         self.boards_per_member = _members(n, w.shape[0], boards_per_member)
-        self.env, self.members = env, int(w.shape[0])
-        self.weights = torch.from_numpy(w).to(env.device)
+        self.env, self.members, self.features = env, int(w.shape[0]), int(w.shape[1])
+        # the device buffer act() reads: [P, 12], or [P, 16] with the fourteen in front; `weights` shows [P, 12] or [P, 14] of it
+        self._buffer = torch.from_numpy(_learn_lib.padded_weights(w)).to(env.device)
+        self.weights = self._buffer[:, :self.features]
         self._planes = None
 
     def set_weights(self, weights) -> None:
@@ -108,7 +128,7 @@ class _WeightedPolicy:
         w = _weights(weights)
         if w.shape != tuple(self.weights.shape):
             raise ValueError(f"weights must keep their shape {tuple(self.weights.shape)}")
-        self.weights.copy_(torch.from_numpy(w), non_blocking=False)
+        self._buffer.copy_(torch.from_numpy(_learn_lib.padded_weights(w)), non_blocking=False)
 
     def _outputs(self, out, score) -> torch.Tensor:
         """`out` (made where it is None) and `score` checked, and the resident planes at hand."""
@@ -129,7 +149,7 @@ class HeuristicPolicy(_WeightedPolicy):
     launch that leaves the environment as it is.
 
     weights: [12], or [P, 12] for a population -- board i plays row i // boards_per_member (the last member may be short;
-    None: the boards split evenly).  They are checked finite and uploaded once; set_weights() replaces them in place, so a
+    None: the boards split evenly) --, or [14] / [P, 14]: the 14-feature form with landing_height and eroded_cells.  They are checked finite and uploaded once; set_weights() replaces them in place, so a
     captured graph of act() plays the new ones.
 
     depth=2 searches two plies (tpl_placement_search): a first placement that does not end the game is worth the best score
@@ -155,10 +175,10 @@ class HeuristicPolicy(_WeightedPolicy):
         if second is not None:
             env._own(second, torch.uint8, "second")
         stream = torch._C._cuda_getCurrentRawStream(env.device.index)
-        lib = _learn_lib.lib()
-        entry, extra = (lib.tpl_placement_search, (_ptr(second),)) if self.depth == 2 else (lib.tpl_placement_act, ())
-        check(entry(self._planes[0], self._planes[1], env.num_envs, env.L, env.M, self.weights.data_ptr(), self.boards_per_member,
-                    out.data_ptr(), *extra, _ptr(score), stream))
+        name, extra = ("search", (_ptr(second),)) if self.depth == 2 else ("act", ())
+        check(_learn_lib.entry(name, self.features)(self._planes[0], self._planes[1], env.num_envs, env.L, env.M,
+                                                    self._buffer.data_ptr(), self.boards_per_member, out.data_ptr(), *extra,
+                                                    _ptr(score), stream))
         return out
 
 
@@ -188,9 +208,9 @@ class BeamPolicy(_WeightedPolicy):
         if plan is not None:
             env._own(plan, torch.uint8, "plan", (env.num_envs, self.depth))
         stream = torch._C._cuda_getCurrentRawStream(env.device.index)
-        check(_learn_lib.lib().tpl_placement_beam(self._planes[0], self._planes[1], env.num_envs, env.L, env.M,
-                                                  self.weights.data_ptr(), self.boards_per_member, self.depth, self.width,
-                                                  out.data_ptr(), _ptr(plan), _ptr(score), stream))
+        check(_learn_lib.entry("beam", self.features)(self._planes[0], self._planes[1], env.num_envs, env.L, env.M,
+                                                      self._buffer.data_ptr(), self.boards_per_member, self.depth, self.width,
+                                                      out.data_ptr(), _ptr(plan), _ptr(score), stream))
         return out
 
 
@@ -264,8 +284,9 @@ def evaluate_heuristic(env, weights, boards_per_member: Optional[int], steps: in
 
 def tune_heuristic(L: int, M: int, config_pool, population: int = 64, boards_per_member: int = 4096, steps: Optional[int] = None,
                    generations: int = 20, elite_frac: float = 0.125, init_mean=None, init_std: float = 10.0, noise: float = 0.5,
-                   seed: int = 0, device="cuda:0", depth: int = 1, width: Optional[int] = None) -> dict:
-    """The noisy cross-entropy method on the twelve weights.  Each generation samples `population` weight rows from
+                   seed: int = 0, device="cuda:0", depth: int = 1, width: Optional[int] = None, features: int = NUM_FEATURES) -> dict:
+    """The noisy cross-entropy method on the twelve weights, or with features=14 on the fourteen of the 14-feature form (`init_mean`
+    must have that length; at 12 the draws and the results are what they were before the argument existed).  Each generation samples `population` weight rows from
     N(mean, diag std^2) with a CPU torch.Generator seeded by `seed`, plays them side by side (`boards_per_member` boards each,
     `steps` steps from a full reset, default 4 M: some four episodes a board) on ONE evaluation environment of
     population * boards_per_member boards over `config_pool` = (rows, pieces) with reward (0, 1, 0), takes fitness = wins /
@@ -273,7 +294,7 @@ def tune_heuristic(L: int, M: int, config_pool, population: int = 64, boards_per
     constant noise term that keeps the search from freezing early).  `depth`: the plies the members search (1 or 2); with a
     `width` the members are BeamPolicy(depth, width) and depth may be 1 .. 12.
 
-    Returns mean (float32 [12], the final one), best (float32 [12], the best member seen) with best_fitness, and history: one
+    Returns mean (float32 [12] or [14], the final one), best (likewise, the best member seen) with best_fitness, and history: one
     dict of host floats per generation (population_mean, elite_mean, best).  Deterministic for a given seed."""
     from .env import BatchedTetris
     _, depth, width = _player(depth, width)
@@ -284,10 +305,22 @@ def tune_heuristic(L: int, M: int, config_pool, population: int = 64, boards_per
         raise ValueError("elite_frac must be in (0, 1]")
     if not (np.isfinite(init_std) and init_std > 0 and np.isfinite(noise) and noise >= 0):
         raise ValueError("init_std must be positive and noise non-negative")
+    if isinstance(features, bool) or features not in FEATURE_COUNTS:
+        raise ValueError(f"features must be {NUM_FEATURES} or {NUM_MOVE_FEATURES}, got {features!r}")
+    F = int(features)
     P, per = int(population), int(boards_per_member)
     steps = 4 * int(M) if steps is None else int(steps)
-    mean = np.zeros(NUM_FEATURES, np.float64) if init_mean is None else _weights(init_mean)[0].astype(np.float64)
-    std = np.full(NUM_FEATURES, float(init_std), np.float64)
+    if init_mean is None:
+        mean = np.zeros(F, np.float64)
+    else:
+        try:
+            start = _weights(init_mean)
+        except ValueError as e:
+            raise ValueError(f"init_mean: {e}") from None
+        if start.shape[1] != F:
+            raise ValueError(f"init_mean must be one row of {F} weights (features={F}), got shape {tuple(np.shape(init_mean))}")
+        mean = start[0].astype(np.float64)
+    std = np.full(F, float(init_std), np.float64)
     elite = max(1, int(np.ceil(float(elite_frac) * P)))
     env = BatchedTetris(L, M, P * per, device=device, seed=int(seed), auto_reset=True, reward=(0.0, 1.0, 0.0),
                         config_pool=config_pool)
@@ -296,7 +329,7 @@ def tune_heuristic(L: int, M: int, config_pool, population: int = 64, boards_per
     policy, best, best_fitness, history = None, mean.astype(np.float32), -1.0, []
     try:
         for _ in range(int(generations)):
-            z = torch.randn((P, NUM_FEATURES), generator=gen, dtype=torch.float64).numpy()
+            z = torch.randn((P, F), generator=gen, dtype=torch.float64).numpy()
             rows = (mean[None, :] + std[None, :] * z).astype(np.float32)
             if policy is None:
                 policy = _build_player(env, rows, per, depth, width)

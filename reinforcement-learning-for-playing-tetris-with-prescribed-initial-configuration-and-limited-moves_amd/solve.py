@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._learn_lib import BEAM_MAX_WIDTH, NUM_FEATURES, SOLVE_MAX_MOVES
+from ._learn_lib import BEAM_MAX_WIDTH, NUM_FEATURES, NUM_MOVE_FEATURES, SOLVE_MAX_MOVES
 
 __all__ = ["CLASSICAL_WEIGHTS", "solve_configs", "tighten_pool"]
 
@@ -40,18 +40,19 @@ def _width(width) -> int:
 
 
 def _weight_row(weights) -> np.ndarray:
-    """None -> CLASSICAL_WEIGHTS; anything array-like of twelve numbers -> a finite float32 [12]."""
+    """None -> CLASSICAL_WEIGHTS; anything array-like of twelve numbers -> a finite float32 [12]; of fourteen (the 14-feature form
+    with landing_height and eroded_cells) -> a finite float32 [14]."""
     if weights is None:
         return CLASSICAL_WEIGHTS.copy()
     if _is_tensor(weights):
         weights = weights.detach().cpu().numpy()
     w = np.asarray(weights)
     if w.dtype == object or not (np.issubdtype(w.dtype, np.floating) or np.issubdtype(w.dtype, np.integer)):
-        raise ValueError(f"weights must be {NUM_FEATURES} numbers")
-    if w.shape not in ((NUM_FEATURES,), (1, NUM_FEATURES)):
-        raise ValueError(f"weights must be one row of shape [{NUM_FEATURES}], got {tuple(w.shape)}")
+        raise ValueError(f"weights must be {NUM_FEATURES} numbers (or {NUM_MOVE_FEATURES})")
+    if w.shape not in ((NUM_FEATURES,), (1, NUM_FEATURES), (NUM_MOVE_FEATURES,), (1, NUM_MOVE_FEATURES)):
+        raise ValueError(f"weights must be one row of shape [{NUM_FEATURES}] or [{NUM_MOVE_FEATURES}], got {tuple(w.shape)}")
     with np.errstate(over="ignore"):
-        w = np.ascontiguousarray(w.reshape(NUM_FEATURES), dtype=np.float32)
+        w = np.ascontiguousarray(w.reshape(-1), dtype=np.float32)
     if not np.isfinite(w).all():
         raise ValueError("weights must be finite (in float32)")
     return w
@@ -74,7 +75,7 @@ def solve_configs(rows, pieces, L: int, M: int, weights=None, width: int = 16, d
 
     rows: [n, 20] int16 / uint16 (bit x = column x) or [n, 20, 10] bool, converted as `load_configs` converts them; pieces:
     [n, M + 1] uint8, or [n, M] (padded with piece 0: the piece behind the last move is never played); weights: one row of twelve
-    (None = CLASSICAL_WEIGHTS); width in [1, 64].  Tensors or arrays; everything is enqueued on the current stream of `device`.
+    (None = CLASSICAL_WEIGHTS) or of fourteen, which selects the 14-feature form; width in [1, 64].  Tensors or arrays; everything is enqueued on the current stream of `device`.
     Returns a dict of device tensors: solved bool [n], solution_len int32 [n], actions uint8 [n, M] (placements 10 r + l, 255
     behind the end), solution uint8 [n, M, 2] as (rotations, location) -- the layout of carved_configs(with_solutions=True) and
     forward_configs, zero behind the end -- and, with best_value=True, best_value float32 [n, M]: the value of the best candidate
@@ -110,16 +111,16 @@ def solve_configs(rows, pieces, L: int, M: int, weights=None, width: int = 16, d
     pieces = pieces.contiguous()
     if validate and int(pieces.max()) > 6:
         raise ValueError("piece ids must be in 0..6 (I L J T S Z O)")
-    wt = torch.from_numpy(w).to(d)
+    wt = torch.from_numpy(_learn_lib.padded_weights(w)).to(d)
     out = dict(solved=torch.empty(n, dtype=torch.uint8, device=d), solution_len=torch.empty(n, dtype=torch.int32, device=d),
                actions=torch.empty((n, M), dtype=torch.uint8, device=d))
     if best_value:
         out["best_value"] = torch.empty((n, M), dtype=torch.float32, device=d)
     stream = torch._C._cuda_getCurrentRawStream(d.index if d.index is not None else torch.cuda.current_device())
-    _learn_lib.check(_learn_lib.lib().tpl_placement_solve(rows.data_ptr(), pieces.data_ptr(), n, L, M, wt.data_ptr(), width,
-                                                          out["solved"].data_ptr(), out["solution_len"].data_ptr(),
-                                                          out["actions"].data_ptr(),
-                                                          out["best_value"].data_ptr() if best_value else None, stream))
+    _learn_lib.check(_learn_lib.entry("solve", w.shape[0])(rows.data_ptr(), pieces.data_ptr(), n, L, M, wt.data_ptr(), width,
+                                                           out["solved"].data_ptr(), out["solution_len"].data_ptr(),
+                                                           out["actions"].data_ptr(),
+                                                           out["best_value"].data_ptr() if best_value else None, stream))
     out["solved"] = out["solved"].view(torch.bool)
     played = out["actions"] != 255
     a = torch.where(played, out["actions"], torch.zeros_like(out["actions"]))

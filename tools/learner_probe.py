@@ -141,7 +141,7 @@ PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600, "priority": 600
          "ntuple_search": 900, "ntuple_trace": 600, "ntuple_trace_sweep": 1100, "ntuple_coherent": 600,
          "ntuple_coherent_sweep": 1700, "ntuple_shape": 600, "ntuple_shape_sweep": 1100, "ntuple_beam": 1100,
          "ntuple_sum": 600, "ntuple_sum_sweep": 600, "ntuple_stage": 600, "ntuple_stage_sweep": 900,
-         "ntuple_feature": 600, "ntuple_feature_sweep": 900, "solve": 900}
+         "ntuple_feature": 600, "ntuple_feature_sweep": 900, "solve": 900, "move_features": 1100}
 SCATTERED_ATOMICS = 0.08e12                                 # 64 lanes of a wave adding into 64 rows (float adds; integer adds unmeasured)
 VALU_CYCLES, SIMDS, CLOCK_HZ = 3.3, 1024, 2.4e9           # the move's instruction mix, 256 CUs x 4, the clock
 
@@ -2231,6 +2231,105 @@ def part_solve(rounds=5, eval_steps=12288):
                          capture_output=True, text=True, cwd=ROOT)
     out["kernel"] = [" ".join(l.split()) for l in res.stdout.splitlines() if "placement_solve_kernel" in l or "placement_beam_kernel" in l]
     out["lds_note"] = "the solve kernel's dynamic tape of 2 W M bytes comes on top of its static lds"
+    return out
+
+
+def part_move_features(rounds=5, generations=8, population=32, per=2048):
+    """The 14-feature form beside the 12: time of every kernel against its twin in the same run, and whether landing height and eroded
+    cells help on the tight pool of part_solve (carved L = 10 / M = 40, 65,536 configurations, seed 7, solved at width 16,
+    tighten_pool at the median solution length)."""
+    import numpy as np
+    import torch
+    import tetris_piclim as T
+    dev = "cuda:0"
+    L_, M_ = 10, 40
+    out = dict(part="move_features", time=[], tight={}, full={}, solver={})
+    median = lambda ts: sorted(ts)[len(ts) // 2]
+    classical14 = np.concatenate([T.CLASSICAL_WEIGHTS, np.zeros(2, np.float32)])
+
+    def progress(what):
+        print(json.dumps(what), file=sys.stderr, flush=True)
+
+    # time: 2^20 mid-game boards (carved configurations after twelve random steps), each kernel and its twin alternated
+    count = 1 << 20
+    env = T.BatchedTetris(L_, M_, count, device=dev, seed=7, auto_reset=True)
+    rows, pieces = env.carved_configs(1 << 16, seed=7)
+    env.load_configs(rows, pieces, validate=False)
+    env.reset()
+    for t in range(12):
+        env.step(env.synthetic_actions(t), observe=False)
+    action = torch.empty(count, dtype=torch.uint8, device=dev)
+    players = [("act", lambda w: T.HeuristicPolicy(env, w)), ("search", lambda w: T.HeuristicPolicy(env, w, depth=2)),
+               ("beam_3x8", lambda w: T.BeamPolicy(env, w, 3, 8)), ("beam_6x16", lambda w: T.BeamPolicy(env, w, 6, 16))]
+    for name, make in players:
+        p12, p14 = make(T.CLASSICAL_WEIGHTS), make(classical14)
+        same = bool(torch.equal(p12.act().clone(), p14.act()))
+        t12, t14 = [], []
+        for _ in range(rounds):
+            t12.append(_timed(lambda: p12.act(out=action), 3, warmup=1))
+            t14.append(_timed(lambda: p14.act(out=action), 3, warmup=1))
+        line = dict(kernel=name, boards=count, ms_12=round(median(t12) * 1e3, 3), ms_14=round(median(t14) * 1e3, 3),
+                    ratio=round(median(t14) / median(t12), 4), same_actions_with_zero_move_weights=same)
+        out["time"].append(line)
+        progress(line)
+    env.terminate()
+    for n in (1 << 16, 1 << 20):
+        env = T.BatchedTetris(L_, M_, 64, device=dev, seed=7)
+        rows_n, pieces_n = env.carved_configs(n, seed=7)
+        env.terminate()
+        t12, t14 = [], []
+        for _ in range(rounds):
+            t12.append(_timed(lambda: T.solve_configs(rows_n, pieces_n, L_, M_, T.CLASSICAL_WEIGHTS, 16, device=dev, validate=False), 1, warmup=1))
+            t14.append(_timed(lambda: T.solve_configs(rows_n, pieces_n, L_, M_, classical14, 16, device=dev, validate=False), 1, warmup=1))
+        line = dict(kernel="solve_w16", configurations=n, ms_12=round(median(t12) * 1e3, 3), ms_14=round(median(t14) * 1e3, 3),
+                    ratio=round(median(t14) / median(t12), 4))
+        out["time"].append(line)
+        progress(line)
+
+    # does it help: the record's tight pool, rebuilt
+    n = 1 << 16
+    env = T.BatchedTetris(L_, M_, 64, device=dev, seed=7)
+    rows, pieces = env.carved_configs(n, seed=7)
+    env.terminate()
+    solved16 = T.solve_configs(rows, pieces, L_, M_, width=16, device=dev, validate=False)
+    M_new = int(solved16["solution_len"][solved16["solved"]].float().median())
+    tight = T.tighten_pool(rows, pieces, solved16["solved"], solved16["solution_len"], M_new)
+
+    def result(e, wins):
+        p = wins / max(e, 1)
+        return dict(episodes=int(e), wins=int(wins), win_rate=round(p, 5), standard_error=round((p * (1 - p) / max(e, 1)) ** 0.5, 6))
+
+    def play(pool, M_pool, w, **kw):
+        env = T.BatchedTetris(L_, M_pool, 1 << 14, device=dev, seed=11, auto_reset=True, reward=(0.0, 1.0, 0.0), config_pool=pool)
+        got = T.evaluate_heuristic(env, w, None, 16 * (M_pool + 1), **kw)
+        env.terminate()
+        return result(int(got["episodes"][0]), int(got["wins"][0]))
+
+    both = lambda pool, M_pool, w: dict(one_ply=play(pool, M_pool, w), beam_3x8=play(pool, M_pool, w, depth=3, width=8))
+    out["tight"] = dict(M_new=M_new, size=int(tight[0].shape[0]), of=n, classical=both(tight, M_new, T.CLASSICAL_WEIGHTS))
+    progress(out["tight"])
+    tune = dict(population=population, boards_per_member=per, generations=generations, seed=5, device=dev, init_std=1.0, noise=0.05)
+    tuned12 = T.tune_heuristic(L_, M_new, tight, init_mean=T.CLASSICAL_WEIGHTS, **tune)
+    tuned14 = T.tune_heuristic(L_, M_new, tight, init_mean=classical14, features=14, **tune)
+    out["tune"] = dict(tune, device=None, tuned12=[round(float(x), 4) for x in tuned12["best"]], tuned12_fitness=tuned12["best_fitness"],
+                       tuned14=[round(float(x), 4) for x in tuned14["best"]], tuned14_fitness=tuned14["best_fitness"])
+    progress(out["tune"])
+    players = dict(dellacherie=T.DELLACHERIE_WEIGHTS, tuned12=tuned12["best"], tuned14=tuned14["best"])
+    for name, w in players.items():
+        out["tight"][name] = both(tight, M_new, w)
+        progress({name: out["tight"][name]})
+    for name, w in dict(players, classical=T.CLASSICAL_WEIGHTS).items():
+        out["full"][name] = both((rows, pieces), M_, w)
+        progress({"full_" + name: out["full"][name]})
+    share = lambda x: round(float(x.float().mean()), 5)
+    for W in (1, 8, 16):
+        line = {}
+        for name, w in (("classical", T.CLASSICAL_WEIGHTS), ("tuned14", tuned14["best"])):
+            found = T.solve_configs(rows, pieces, L_, M_, w, W, device=dev, validate=False)
+            line[name] = dict(solved=share(found["solved"]), mean_len=round(float(found["solution_len"][found["solved"]].float().mean()), 2))
+        out["solver"][f"w{W}"] = line
+    progress(out["solver"])
+    out["not_measured"] = "other seeds, other M_new, other tuning budgets"
     return out
 
 
