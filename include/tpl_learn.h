@@ -425,6 +425,70 @@ int tpl_placement_solve_move(const int16_t* rows, const uint8_t* pieces, int64_t
                              int32_t width, uint8_t* solved, int32_t* solution_len, uint8_t* actions, float* best_value,
                              void* stream);
 
+/* The move bound.  The game is named after its move limit; this is the one rule here that reasons about it.  For a board with
+ * l = L - lines > 0 lines still owed and m = M - moves moves left:
+ *   fill(r)   the number of filled cells of row r, r = 0 .. 19;
+ *   cost(r)   10 - fill(r) where fill(r) < 10, and 10 where fill(r) = 10: a full row that stands on the board can never be cleared -- a
+ *             piece has no cell in it, so it is never among the piece's rows -- and therefore costs what a fresh row costs;
+ *   cells     the sum of the l smallest costs, the twenty costs extended by as many 10s as l asks for (L goes up to 250);
+ *   need      ceil(cells / 4);
+ *   spare     4 m - cells.
+ * A running board is DEAD iff spare < 0, that is, need > m.  A finished board has cells = spare = 0 and is never dead.
+ * A DEAD BOARD HAS NO WINNING CONTINUATION, WHATEVER PIECES COME.  Proof: a row is cleared only when all ten of its cells are filled.
+ * Compaction keeps every surviving row's contents, and a fresh row enters empty.  Every move adds exactly four cells or tops out.  So
+ * if l lines are still owed, at least the l cheapest rows must be completed, and the cells missing from them cannot be supplied in
+ * fewer than a quarter as many moves.
+ * The bound never calls a winnable board lost.  It is blind to geometry: a board that is not dead may still have no win.
+ *
+ * tpl_move_bound reads n environment states, one lane a board: cells_out i32 [n] and spare_out i32 [n], both 0 for a finished board
+ * (a running state whose lines have reached L owes nothing: cells = 0).  Refused before any HIP call: what check_planes refuses for
+ * tpl_afterstates' planes (NULL or misaligned planes, n < 1, 40 n >= 2^31, L outside [1, 250], M outside [1, 254]), a NULL or
+ * misaligned (4 bytes) cells_out or spare_out.
+ * tpl_move_bound_rows reads n configurations, rows i16 [n][20] as tpl_placement_solve takes them, as the states a full reset deals
+ * (0 lines): cells_out i32 [n] = cells(board, L); ceil(cells / 4) is the least number of moves any solution can take.  Refused before
+ * any HIP call: a NULL rows or cells_out, n < 1, n >= 2^31, L outside [1, 250], rows not 2-byte or cells_out not 4-byte aligned. */
+int tpl_move_bound(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, int32_t* cells_out, int32_t* spare_out,
+                   void* stream);
+int tpl_move_bound_rows(const int16_t* rows, int64_t n, int32_t L, int32_t* cells_out, void* stream);
+
+/* THE BOUNDED FORM of a placement kernel is its unbounded twin with two changes, both made in one place after the move
+ * (csrc/learn/tpl_placement.h: bounded_move) and before psi is made:
+ *   1. A move that leaves a running, dead board leaves it LOST: its state becomes lost-at-the-limit.  Feature 2 then reads 1 and the
+ *      node is finished: it is not expanded, and it competes with its own value as any lost node does.
+ *   2. value = w . phi as before, then + spare_weight * float(spare): one rounded multiply and one rounded add, made last, never
+ *      fused.  spare is taken after change 1, so it is 0 for every finished node.  spare_weight is one finite float32 for the whole
+ *      launch, whatever the number of weight rows.
+ * With spare_weight = 0, on inputs where no child is dead, a bounded kernel writes the bytes of its twin (a value that is -0 in the
+ * twin comes out +0: the order does not see the difference).
+ *
+ * tpl_placement_solve_bound, tpl_placement_solve_move_bound: tpl_placement_solve[_move] in the bounded form, with spare_weight behind
+ * the width and two more outputs, both written in full:
+ *   bound i32 [n]      need(root): no solution of the configuration is shorter;
+ *   complete u8 [n]    1 iff at no ply run did the width cut drop a RUNNING candidate (dead children are lost, not running: dropping
+ *                      them loses nothing, because they cannot win).
+ * UNDER complete = 1, solved = 0 PROVES that no sequence of placements wins within M moves, and solved = 1 proves that solution_len is
+ * the shortest there is: every running candidate of every ply was kept, so the search was exhaustive up to the bound's prune.  Without
+ * complete, solved = 1 with solution_len == bound proves the same of that solution, and solved = 0 proves nothing.
+ * Refused before any HIP call: what tpl_placement_solve refuses, a NULL bound or complete, bound not 4-byte aligned, a spare_weight
+ * that is not finite.  The bounded kernels are bound to four workgroups a CU where their twin has five (csrc/learn/solve.hip).
+ *
+ * tpl_placement_beam_bound, tpl_placement_beam_move_bound: tpl_placement_beam[_move] in the bounded form, with spare_weight behind the
+ * width; L and M are the environment's, and lines and moves are read from the state's bits.  Depth 1, width 1 is the bounded
+ * one-ply player.  Consequence 2 of tpl_placement_solve holds between the bounded pair as it does between the unbounded one.
+ * Refused before any HIP call: what tpl_placement_beam refuses, a spare_weight that is not finite. */
+int tpl_placement_solve_bound(const int16_t* rows, const uint8_t* pieces, int64_t n, int32_t L, int32_t M, const float* weights,
+                              int32_t width, float spare_weight, uint8_t* solved, int32_t* solution_len, uint8_t* actions,
+                              float* best_value, int32_t* bound, uint8_t* complete, void* stream);
+int tpl_placement_solve_move_bound(const int16_t* rows, const uint8_t* pieces, int64_t n, int32_t L, int32_t M, const float* weights,
+                                   int32_t width, float spare_weight, uint8_t* solved, int32_t* solution_len, uint8_t* actions,
+                                   float* best_value, int32_t* bound, uint8_t* complete, void* stream);
+int tpl_placement_beam_bound(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const float* weights,
+                             int64_t boards_per_member, int32_t depth, int32_t width, float spare_weight, uint8_t* action,
+                             uint8_t* plan, float* score, void* stream);
+int tpl_placement_beam_move_bound(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const float* weights,
+                                  int64_t boards_per_member, int32_t depth, int32_t width, float spare_weight, uint8_t* action,
+                                  uint8_t* plan, float* score, void* stream);
+
 /* An n-tuple afterstate value function, its placement policy and its temporal-difference update (csrc/learn/ntuple.hip).
  *
  * Table: TPL_NTUPLE_ENTRIES = 8 * 153 * 256 + 1024 = 314,368 int32 entries (1,257,472 bytes), 16-byte aligned, in units of 2^-16:

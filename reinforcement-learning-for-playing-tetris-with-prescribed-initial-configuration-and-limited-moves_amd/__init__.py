@@ -17,7 +17,7 @@ __all__ = ["BatchedTetris", "Tetris", "Snapshot", "OBS_DIM", "NUM_ACTIONS", "RUN
            "ntuple_is_symmetric", "ntuple_coherence", "ntuple_step_sizes", "ntuple_shape", "NTUPLE_SHAPES", "ntuple_parts", "NTUPLE_SUMS", "NTUPLE_ENTRIES_SUM",
            "NTUPLE_STAGES", "ntuple_stage_map", "ntuple_staged", "ntuple_stages", "ntuple_map", "ntuple_is_staged", "NTUPLE_FEATURE_FORMS",
            "ntuple_feature_bins", "solve_configs", "tighten_pool", "CLASSICAL_WEIGHTS", "FEATURE_NAMES",
-           "MOVE_FEATURE_NAMES", "DELLACHERIE_WEIGHTS"]
+           "MOVE_FEATURE_NAMES", "DELLACHERIE_WEIGHTS", "move_bound", "config_bound"]
 
 
 def __getattr__(name):
@@ -40,14 +40,14 @@ def __getattr__(name):
     if name in ("LookaheadPolicy", "afterstates"):
         return getattr(importlib.import_module(__name__ + ".lookahead"), name)
     if name in ("HeuristicPolicy", "placement_features", "evaluate_heuristic", "tune_heuristic", "BeamPolicy", "FEATURE_NAMES",
-                "MOVE_FEATURE_NAMES", "DELLACHERIE_WEIGHTS"):
+                "MOVE_FEATURE_NAMES", "DELLACHERIE_WEIGHTS", "move_bound"):
         return getattr(importlib.import_module(__name__ + ".heuristic"), name)
     if name in ("NTuplePolicy", "NTupleBeamPolicy", "NTupleLearner", "ntuple_table", "ntuple_value", "ntuple_is_symmetric", "ntuple_coherence",
                 "ntuple_step_sizes", "ntuple_shape", "NTUPLE_SHAPES", "ntuple_parts", "NTUPLE_SUMS", "NTUPLE_ENTRIES_SUM",
                 "NTUPLE_STAGES", "ntuple_stage_map", "ntuple_staged", "ntuple_stages", "ntuple_map", "ntuple_is_staged", "NTUPLE_FEATURE_FORMS",
                 "ntuple_feature_bins"):
         return getattr(importlib.import_module(__name__ + ".ntuple"), name)
-    if name in ("solve_configs", "tighten_pool", "CLASSICAL_WEIGHTS"):
+    if name in ("solve_configs", "tighten_pool", "CLASSICAL_WEIGHTS", "config_bound"):
         return getattr(importlib.import_module(__name__ + ".solve"), name)
     if name in ("learn", "_learn_lib", "lookahead", "heuristic", "ntuple", "solve"):
         return importlib.import_module(__name__ + "." + name)

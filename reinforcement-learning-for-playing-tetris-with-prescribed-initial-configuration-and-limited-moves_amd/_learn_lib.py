@@ -22,7 +22,9 @@ _LEARN_CSRC = os.path.join(_lib._CSRC, "learn")
 LEARN_LIB_PATH = os.path.join(_lib._LIBDIR, "libtpl_learn.so")
 _UNITS = [os.path.join(_LEARN_CSRC, f) for f in ("replay.hip", "pack.hip", "priority.hip", "afterstates.hip",
                                                       "beam.hip", "solve.hip", "ntuple.hip", "ntuple_beam.hip", "heuristic_move.hip",
-                                                      "beam_move.hip", "solve_move.hip", "heuristic.hip")]
+                                                      "beam_move.hip", "solve_move.hip", "bound.hip", "beam_bound.hip",
+                                                      "solve_bound.hip", "beam_move_bound.hip", "solve_move_bound.hip",
+                                                      "heuristic.hip")]
 
 # entry points declared in include/tpl_learn.h (tests check that the .so exports every one of them)
 LEARN_SYMBOLS = [
@@ -41,6 +43,8 @@ LEARN_SYMBOLS = [
     "tpl_ntuple_update_trace_feature", "tpl_ntuple_feature_bins", "tpl_placement_solve",
     "tpl_placement_features_move", "tpl_placement_act_move", "tpl_placement_search_move", "tpl_placement_beam_move",
     "tpl_placement_solve_move",
+    "tpl_move_bound", "tpl_move_bound_rows", "tpl_placement_solve_bound", "tpl_placement_solve_move_bound",
+    "tpl_placement_beam_bound", "tpl_placement_beam_move_bound",
 ]
 NSTEP_MAX = 16
 BEAM_MAX_DEPTH, BEAM_MAX_WIDTH = 12, 64
@@ -154,6 +158,14 @@ def lib() -> C.CDLL:
         twin.argtypes = getattr(L, f"tpl_placement_{name}").argtypes
         twin.restype = i32
     f32 = C.c_float
+    L.tpl_move_bound.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp]
+    L.tpl_move_bound_rows.argtypes = [vp, i64, i32, vp, vp]
+    L.tpl_move_bound.restype = L.tpl_move_bound_rows.restype = i32
+    for form in ("", "_move"):                               # the bounded form: spare_weight behind the width, the solver's two outputs
+        beam, solve = getattr(L, f"tpl_placement_beam{form}_bound"), getattr(L, f"tpl_placement_solve{form}_bound")
+        beam.argtypes = [vp, vp, i64, i32, i32, vp, i64, i32, i32, f32, vp, vp, vp, vp]
+        solve.argtypes = [vp, vp, i64, i32, i32, vp, i32, f32, vp, vp, vp, vp, vp, vp, vp]
+        beam.restype = solve.restype = i32
     L.tpl_ntuple_value.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp]
     L.tpl_ntuple_act.argtypes = [vp, vp, i64, i32, i32, f32, f32, f32, f32, vp, f32, u64, u64, vp, vp, vp, vp, vp, vp]
     L.tpl_ntuple_update.argtypes = [vp, vp, i64, i32, i32, vp, vp, f32, vp]
@@ -477,11 +489,12 @@ MOVE_FEATURE_NAMES = FEATURE_NAMES + ("landing_height", "eroded_cells")
 FEATURE_COUNTS = (NUM_FEATURES, NUM_MOVE_FEATURES)
 
 
-def entry(name: str, count: int):
-    """The entry point tpl_placement_<name> of the feature set with `count` features (12 or 14)."""
+def entry(name: str, count: int, bound: bool = False):
+    """The entry point tpl_placement_<name> of the feature set with `count` features (12 or 14); bound=True: its bounded form
+    (beam and solve have one)."""
     if count not in FEATURE_COUNTS:
         raise ValueError(f"a weight row has {NUM_FEATURES} or {NUM_MOVE_FEATURES} entries, not {count}")
-    return getattr(lib(), f"tpl_placement_{name}" + ("_move" if count == NUM_MOVE_FEATURES else ""))
+    return getattr(lib(), f"tpl_placement_{name}" + ("_move" if count == NUM_MOVE_FEATURES else "") + ("_bound" if bound else ""))
 
 
 def padded_weights(w: np.ndarray) -> np.ndarray:
@@ -521,6 +534,41 @@ def board_features(rows) -> np.ndarray:
     depth = np.where(hole.any(axis=1), above_it, 0).sum(axis=1)
     return np.stack([hole.sum(axis=(1, 2)), height.sum(axis=1), height.max(axis=1), bump, row_trans, col_trans, wells,
                      hole.any(axis=2).sum(axis=1), depth], axis=1).astype(np.int64)
+
+
+def move_bound_cells(rows, lines_left) -> np.ndarray:
+    """The move bound's `cells` (include/tpl_learn.h) of boards given as row masks (uint16 [K, 20] or [20], bit x = column x) with
+    `lines_left` rows still owed ([K] or one number, each >= 0) -> int64 [K]: the sum of the lines_left smallest row costs, a row with
+    f < 10 filled cells costing 10 - f and a full row 10, the twenty costs extended by 10s.  Counted on the 0 / 1 cells, row by row
+    (the device adds the ten column words bit-sliced: csrc/learn/tpl_placement.h -- the two share nothing)."""
+    rows = np.asarray(rows)
+    if rows.ndim == 1:
+        rows = rows[None]
+    if rows.ndim != 2 or rows.shape[1] != 20:
+        raise ValueError("rows must be [K, 20] row masks")
+    k = rows.shape[0]
+    left = np.broadcast_to(np.asarray(lines_left, dtype=np.int64), (k,))
+    if left.size and left.min() < 0:
+        raise ValueError("lines_left must not be negative")
+    cell = (rows.astype(np.int64)[:, :, None] // (2 ** np.arange(10))[None, None, :]) % 2          # [K, 20, 10], 1 = filled
+    fill = cell.sum(axis=2)
+    cost = np.sort(np.where(fill < 10, 10 - fill, 10), axis=1)
+    upto = np.concatenate([np.zeros((k, 1), np.int64), np.cumsum(cost, axis=1)], axis=1)          # upto[:, j] = the j cheapest
+    return upto[np.arange(k), np.minimum(left, 20)] + 10 * np.maximum(left - 20, 0)
+
+
+def move_bound(rows, L: int, M: int, lines, moves, state) -> dict:
+    """The move bound of boards in row form under the game's L and M (include/tpl_learn.h): cells and spare = 4 (M - moves) - cells
+    for a running board (a running board whose lines have reached L owes nothing), both 0 for a finished one; need =
+    ceil(cells / 4); dead = spare < 0.  int64 [K] each, dead bool."""
+    rows = np.asarray(rows)
+    rows = rows[None] if rows.ndim == 1 else rows
+    k = rows.shape[0]
+    lines, moves, state = (np.broadcast_to(np.asarray(x, dtype=np.int64), (k,)) for x in (lines, moves, state))
+    running = state == STATE_RUNNING
+    cells = np.where(running, move_bound_cells(rows, np.maximum(int(L) - lines, 0)), 0)
+    spare = np.where(running, 4 * (int(M) - moves) - cells, 0)
+    return dict(cells=cells, spare=spare, need=(cells + 3) // 4, dead=spare < 0)
 
 
 def placement_score(features, weights) -> np.ndarray:
@@ -689,7 +737,8 @@ def _first_in_order(values) -> int:
     return int(np.argmax(v == v.max()))
 
 
-def placement_solve(rows, pieces, L: int, M: int, weights, width: int, max_width: int = BEAM_MAX_WIDTH, chunk: int = 1 << 14):
+def placement_solve(rows, pieces, L: int, M: int, weights, width: int, max_width: int = BEAM_MAX_WIDTH, chunk: int = 1 << 14,
+                    bound: bool = False, spare_weight: float = 0.0):
     """The rule of tpl_placement_solve (include/tpl_learn.h) for n configurations: rows uint16 [n, 20] (bit x = column x), pieces
     [n, M + 1] (masked to three bits), one weight row [12] -- or [14], the 14-feature form, in which a node also carries the landing
     and eroded sums of its path --, a width in [1, max_width].  The placement beam run through the whole
@@ -697,6 +746,11 @@ def placement_solve(rows, pieces, L: int, M: int, weights, width: int, max_width
     path of the won candidate that comes first in the rule's order, or unsolved once no node of the beam runs.  Returns
     (solved uint8 [n], solution_len int32 [n], actions uint8 [n, M] padded with 255, best_value float32 [n, M], +0 beyond the
     plies run) in the C layout.  solved = 0 means that this beam found no win, not that there is none.
+    bound=True is the bounded form (tpl_placement_solve_bound): a child that is left running and dead (move_bound) becomes lost at
+    the limit before psi is built, spare_weight * float32(spare) is added to the score last, in float32, and two more arrays are
+    returned behind the four: bound int32 [n] = need(root), and complete uint8 [n], 1 iff no cut dropped a running candidate -- under
+    which solved = 0 is a proof that there is no win and solved = 1 that solution_len is the shortest.  A spare_weight other than 0
+    needs bound=True.
     `max_width` is for the test that compares a beam wide enough to keep everything with an exhaustive search; the kernel's limit
     is BEAM_MAX_WIDTH.  `chunk` bounds how many candidates are moved and counted at once."""
     L, M = int(L), int(M)
@@ -715,6 +769,16 @@ def placement_solve(rows, pieces, L: int, M: int, weights, width: int, max_width
     if w.shape not in ((NUM_FEATURES,), (NUM_MOVE_FEATURES,)):
         raise ValueError("weights must be one row of 12 or of 14")
     move = w.shape[0] == NUM_MOVE_FEATURES
+    if not isinstance(bound, (bool, np.bool_)):
+        raise ValueError("bound must be True or False")
+    with np.errstate(over="ignore"):
+        spare_weight = np.float32(spare_weight)
+    if not np.isfinite(spare_weight):
+        raise ValueError("spare_weight must be finite (in float32)")
+    if spare_weight != 0 and not bound:
+        raise ValueError("spare_weight belongs to the bounded form: give bound=True")
+    root_need = move_bound(rows, L, M, 0, 0, STATE_RUNNING)["need"].astype(np.int32)
+    complete = np.ones(n, np.uint8)
     placements = [np.flatnonzero(canonical_actions(p, np.arange(NUM_ACTIONS)) == np.arange(NUM_ACTIONS)) for p in range(8)]
     solved, length = np.zeros(n, np.uint8), np.zeros(n, np.int32)
     actions, best_value = np.full((n, M), NO_SECOND, np.uint8), np.zeros((n, M), np.float32)
@@ -745,10 +809,17 @@ def placement_solve(rows, pieces, L: int, M: int, weights, width: int, max_width
             r2, _, l2, m2, s2, _, _, land, erod = host_moves_traced(p_rows[lo:hi], pieces[cfg[lo:hi], ply], place[lo:hi] // 10,
                                                                     place[lo:hi] % 10, L, M, p_lines[lo:hi], p_moves[lo:hi])
             c_sums[lo:hi] = p_sums[lo:hi] + np.stack([land, erod], axis=1)
+            spare = np.zeros(hi - lo, np.int64)
+            if bound:                                           # the one place where the bounded form parts from its twin
+                mb = move_bound(r2, L, M, l2, m2, s2)
+                s2 = np.where(mb["dead"], STATE_LOST_LIMIT, s2)
+                spare = np.where(mb["dead"], 0, mb["spare"])
             psi = np.concatenate([np.stack([l2, s2 == STATE_WON, s2 >= STATE_LOST_LIMIT], axis=1).astype(np.int64),
                                   board_features(r2)] + ([c_sums[lo:hi]] if move else []), axis=1)
             c_rows[lo:hi], c_lines[lo:hi], c_moves[lo:hi], c_state[lo:hi] = r2, l2, m2, s2
             c_value[lo:hi] = placement_score(psi, w)
+            if bound:                                           # one rounded multiply, one rounded add, made last
+                c_value[lo:hi] = c_value[lo:hi] + spare_weight * spare.astype(np.float32)
         still = []
         for s in active:
             beam = beams[s]
@@ -775,6 +846,9 @@ def placement_solve(rows, pieces, L: int, M: int, weights, width: int, max_width
                 continue
             order = np.argsort(-(value + np.float32(0.0)), kind="stable")       # beam_select's order, for any width
             keep = np.sort(order[:width])
+            cut = order[width:]
+            if (c_state[child[cut][child[cut] >= 0]] == STATE_RUNNING).any():
+                complete[s] = 0                                 # the cut dropped a running candidate
             kc, kp = child[keep], parent[keep]
             moved = kc >= 0
             kc0 = np.maximum(kc, 0)
@@ -790,6 +864,8 @@ def placement_solve(rows, pieces, L: int, M: int, weights, width: int, max_width
         active = still
         if not active:
             break
+    if bound:
+        return solved, length, actions, best_value, root_need, complete
     return solved, length, actions, best_value
 
 

@@ -33,6 +33,11 @@
 // through beam_move.hip as placement_beam_move_kernel on the fourteen with landing height and eroded cells.  There a node's `cleared`
 // word is the carry of its path (tpl_placement.h): rows cleared, landing sum and eroded sum in 8 + 14 + 10 bits -- the beam in LDS is
 // the same size.
+//
+// And twice more in the BOUNDED form (tpl_placement.h: kUnitBound; include/tpl_learn.h: the move bound), through beam_bound.hip and
+// beam_move_bound.hip: placement_beam_bound_kernel and placement_beam_move_bound_kernel.  expand() then turns a dead child into a lost one
+// and adds the spare term (bounded_move, bounded_value); nothing else differs, and the two unbounded kernels are what they were,
+// instruction for instruction (profiles/learner/bound_isa.log).
 #include "tpl_beam.h"
 
 namespace tpl_learn {
@@ -51,26 +56,42 @@ struct BeamArgs {
     uint8_t* action;             // [n]
     uint8_t* plan;               // [n][depth], optional
     float* score;                // [n], optional
+#ifdef TPL_PLACEMENT_BOUND_UNIT
+    float spare_weight;          // the bounded form's: the weight of a node's spare cells, one for the whole launch
+#endif
 };
+
+__device__ __forceinline__ float spare_weight_of(const BeamArgs& p) {
+#ifdef TPL_PLACEMENT_BOUND_UNIT
+    return p.spare_weight;
+#else
+    return 0.0f;
+#endif
+}
 
 // Candidate k of running parent q: the board the move leaves (window not yet popped), the move's carry with the parent's (the rows
 // cleared at 12 features), and the value of psi = (cleared, won, lost, features 3..11[, landing sum, eroded sum]).  Phases A and C both come here, so a winner's second making of its
-// move gives the bits of the first.
+// move gives the bits of the first.  In the bounded form a dead child is lost before psi is made, and its spare cells enter the value
+// last (tpl_placement.h: bounded_move).
 __device__ __forceinline__ float expand(const Beam& parent, uint32_t q, uint32_t k, const tpl::ShapeWord* shape, uint32_t L,
-                                        uint32_t M, const float (&w)[kF], tpl::Board& s, uint32_t& cleared, uint32_t& b) {
+                                        uint32_t M, const float (&w)[kF], float spare_weight, tpl::Board& s, uint32_t& cleared,
+                                        uint32_t& b) {
     const uint4 A = parent.a[q], B = parent.b[q];
     uint32_t r, l, cur;
     b = nth_placement(B.w & 7u, k, r, l);
     bool running;                                             // the callers expand running parents only (Slot::finished)
     cleared = parent.cleared[q] + first_move<kF>(A, B, shape, r, l, L, M, s, cur, running);
+    const int32_t spare = bounded_move(s, L, M);
     FeatureSet<kF> psi;
     moved_features(s, cleared, true, psi);
-    return placement_score(w, psi);
+    if constexpr (kUnitBound) return bounded_value(placement_score(w, psi), spare_weight, spare);
+    else return placement_score(w, psi);
 }
 
 // The 12-feature kernel takes 95 VGPRs by itself: five workgroups a CU.  Left to itself the 14-feature one takes more than 128, which
-// is three; bound to the 96 of five it spills 20 bytes to scratch, so it is bound to four (tools/kernel_resources.sh).
-#ifdef TPL_PLACEMENT_MOVE_UNIT
+// is three; bound to the 96 of five it spills 20 bytes to scratch, so it is bound to four (tools/kernel_resources.sh).  The bounded
+// forms carry the fill planes of move_bound_cells: left to itself the bounded 12-feature kernel takes 133, so both are bound to four.
+#if defined(TPL_PLACEMENT_MOVE_UNIT) || defined(TPL_PLACEMENT_BOUND_UNIT)
 #define TPL_BEAM_BOUNDS __launch_bounds__(kBeamBlock, 4)
 #else
 #define TPL_BEAM_BOUNDS __launch_bounds__(kBeamBlock)
@@ -110,6 +131,7 @@ __global__ TPL_BEAM_BOUNDS void TPL_UNIT_KERNEL(placement_beam)(const BeamArgs p
         const float2 v = ((const float2*)s_w)[6];
         w[kF - 2] = v.x; w[kF - 1] = v.y;
     }
+    const float spare_weight = spare_weight_of(p);
     const uint4 rootA = s_beam[0].a[0], rootB = s_beam[0].b[0];
     const unsigned long long window = ((unsigned long long)(rootB.z >> 28) << 32) | rootB.w;
     // the plies: none for a finished board, else as many as the window has true pieces
@@ -142,7 +164,7 @@ __global__ TPL_BEAM_BOUNDS void TPL_UNIT_KERNEL(placement_beam)(const BeamArgs p
             } else {
                 tpl::Board s;
                 uint32_t cleared, b;
-                const float value = expand(parent, c.q, c.k, s_shape, p.L, p.M, w, s, cleared, b);
+                const float value = expand(parent, c.q, c.k, s_shape, p.L, p.M, w, spare_weight, s, cleared, b);
                 key = ((unsigned long long)ordered_bits(value) << 32) | (kSlotTop - slot);
             }
             s_key[slot] = key;
@@ -169,7 +191,7 @@ __global__ TPL_BEAM_BOUNDS void TPL_UNIT_KERNEL(placement_beam)(const BeamArgs p
             } else {
                 tpl::Board s;
                 uint32_t cleared, b;
-                const float value = expand(parent, q, c.k, s_shape, p.L, p.M, w, s, cleared, b);
+                const float value = expand(parent, q, c.k, s_shape, p.L, p.M, w, spare_weight, s, cleared, b);
                 tpl::next_window(s, false, 0);                 // tpl_afterstates' pop
                 uint4 A, B;
                 tpl::pack_board(s, A, B);
@@ -202,9 +224,16 @@ __global__ TPL_BEAM_BOUNDS void TPL_UNIT_KERNEL(placement_beam)(const BeamArgs p
 
 using namespace tpl_learn;
 
+// the bounded entries take spare_weight behind the width (include/tpl_learn.h)
+#ifdef TPL_PLACEMENT_BOUND_UNIT
+#define TPL_BEAM_SPARE_PARAM float spare_weight,
+#else
+#define TPL_BEAM_SPARE_PARAM
+#endif
+
 extern "C" int TPL_UNIT_ENTRY(tpl_placement_beam)(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const float* weights,
-                                  int64_t boards_per_member, int32_t depth, int32_t width, uint8_t* action, uint8_t* plan,
-                                  float* score, void* stream) {
+                                  int64_t boards_per_member, int32_t depth, int32_t width, TPL_BEAM_SPARE_PARAM uint8_t* action,
+                                  uint8_t* plan, float* score, void* stream) {
     const char* name = TPL_UNIT_ENTRY_NAME(tpl_placement_beam);
     if (const int rc = check_policy(name, plane_a, plane_b, n, L, M, weights, boards_per_member, action, score)) return rc;
     if (depth < 1 || depth > kMaxDepth) return fail_msg(TPL_ERR_ARG, "%s: depth must be in [1, %d]", name, kMaxDepth);
@@ -215,6 +244,10 @@ extern "C" int TPL_UNIT_ENTRY(tpl_placement_beam)(const void* plane_a, const voi
     p.per_member = (uint32_t)(boards_per_member < n ? boards_per_member : n);     // anything above n is the single-policy case
     p.depth = (uint32_t)depth; p.width = (uint32_t)width;
     p.action = action; p.plan = plan; p.score = score;
+#ifdef TPL_PLACEMENT_BOUND_UNIT
+    if (!(spare_weight - spare_weight == 0.0f)) return fail_msg(TPL_ERR_ARG, "%s: spare_weight must be finite", name);
+    p.spare_weight = spare_weight;
+#endif
     hipLaunchKernelGGL(TPL_UNIT_KERNEL(placement_beam), dim3(p.n), dim3(kBeamBlock), 0, (hipStream_t)stream, p);
     TPL_LEARN_HIP(hipGetLastError());
     return TPL_OK;

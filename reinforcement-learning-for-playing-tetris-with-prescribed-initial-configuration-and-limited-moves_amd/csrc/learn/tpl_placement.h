@@ -17,7 +17,8 @@ constexpr int kActions = TPL_NUM_ACTIONS;
 constexpr int kFeatures = TPL_NUM_FEATURES;
 constexpr int kMoveFeatures = TPL_NUM_MOVE_FEATURES;
 
-// A unit of the linear placement family (heuristic.hip, beam.hip, solve.hip) is written once and built twice: as it stands on the
+// A unit of the linear placement family (heuristic.hip, beam.hip, solve.hip) is written once and built twice (beam.hip and solve.hip
+// four times: the bound switch below): as it stands on the
 // twelve board features, and once more on the fourteen through its twin (heuristic_move.hip, ...), which defines
 // TPL_PLACEMENT_MOVE_UNIT and includes it.  Two units and not two instances in one: with both feature sets in one translation unit the
 // compiler orders a few instructions of the 12-feature kernels differently (profiles/learner/move_features_isa.log).  kUnitFeatures is
@@ -25,15 +26,31 @@ constexpr int kMoveFeatures = TPL_NUM_MOVE_FEATURES;
 // point in it: placement_act_kernel / tpl_placement_act, or placement_act_move_kernel / tpl_placement_act_move.
 #ifdef TPL_PLACEMENT_MOVE_UNIT
 constexpr int kUnitFeatures = kMoveFeatures;
-#define TPL_UNIT_KERNEL(stem) stem##_move_kernel
-#define TPL_UNIT_ENTRY(stem) stem##_move
-#define TPL_UNIT_ENTRY_NAME(stem) #stem "_move"
+#define TPL_UNIT_FORM _move
+#define TPL_UNIT_FORM_NAME "_move"
 #else
 constexpr int kUnitFeatures = kFeatures;
-#define TPL_UNIT_KERNEL(stem) stem##_kernel
-#define TPL_UNIT_ENTRY(stem) stem
-#define TPL_UNIT_ENTRY_NAME(stem) #stem
+#define TPL_UNIT_FORM
+#define TPL_UNIT_FORM_NAME ""
 #endif
+// The bound switch stands beside the feature set: a unit that defines TPL_PLACEMENT_BOUND_UNIT before it includes its twin
+// (beam_bound.hip, solve_move_bound.hip, ...) is the BOUNDED form of that twin (include/tpl_learn.h: the move bound) --
+// placement_solve_bound_kernel / tpl_placement_solve_bound, placement_solve_move_bound_kernel / tpl_placement_solve_move_bound.
+// kUnitBound is the switch; bounded_move below is the one place where the two forms part.
+#ifdef TPL_PLACEMENT_BOUND_UNIT
+constexpr bool kUnitBound = true;
+#define TPL_UNIT_BOUND _bound
+#define TPL_UNIT_BOUND_NAME "_bound"
+#else
+constexpr bool kUnitBound = false;
+#define TPL_UNIT_BOUND
+#define TPL_UNIT_BOUND_NAME ""
+#endif
+#define TPL_UNIT_PASTE4_(a, b, c, d) a##b##c##d
+#define TPL_UNIT_PASTE4(a, b, c, d) TPL_UNIT_PASTE4_(a, b, c, d)
+#define TPL_UNIT_KERNEL(stem) TPL_UNIT_PASTE4(stem, TPL_UNIT_FORM, TPL_UNIT_BOUND, _kernel)
+#define TPL_UNIT_ENTRY(stem) TPL_UNIT_PASTE4(stem, TPL_UNIT_FORM, TPL_UNIT_BOUND, )
+#define TPL_UNIT_ENTRY_NAME(stem) #stem TPL_UNIT_FORM_NAME TPL_UNIT_BOUND_NAME
 constexpr int kMoveWeightStride = TPL_MOVE_WEIGHT_STRIDE;
 // floats between two weight rows of feature set kF
 template <int kF> constexpr int weight_stride() { return kF == kMoveFeatures ? kMoveWeightStride : kF; }
@@ -247,6 +264,75 @@ __device__ __forceinline__ float placement_score(const float (&w)[kF], const Fea
 #pragma unroll
     for (int k = 1; k < kF; ++k) s = s + w[k] * (float)phi.f[k];
     return s;
+}
+
+// The move bound (include/tpl_learn.h): the least number of cells that must still be added to a board given as its ten column
+// words (bits 20.. clear) before `lines_left` more rows can have been cleared -- the sum of the lines_left smallest row costs, a row
+// with f < 10 filled cells costing 10 - f and a full row or a fresh one 10.  Three steps, no register indexed by a value:
+//   the fills    a bit-sliced add of the ten words into four planes (bit r of p3 p2 p1 p0 = fill(r)): three carry-save adders on
+//                nine words, one on their sums, a half adder for the tenth, then the carries -- some thirty bitwise operations;
+//   the counts   h(f) = the rows with fill f, f = 1 .. 9: the planes or their complements under one mask, and a popcount;
+//   the sum      greedy from the cheapest: take min(h(f), left) rows at 10 - f for f = 9 .. 1, and what is left at 10 -- the rows with
+//                fill 0 or 10 and, past the twentieth, the fresh rows that L up to 250 asks for cost the same.
+__device__ __forceinline__ void carry_save(uint32_t a, uint32_t b, uint32_t c, uint32_t& sum, uint32_t& carry) {
+    const uint32_t ab = a ^ b;
+    sum = ab ^ c;
+    carry = (a & b) | (ab & c);
+}
+
+__device__ __forceinline__ uint32_t move_bound_cells(const uint32_t (&c)[tpl::kCols], uint32_t lines_left) {
+    static_assert(tpl::kCols == 10, "the adder tree is written for ten columns");
+    uint32_t s0, s1, s2, s3, k0, k1, k2, k3;
+    carry_save(c[0], c[1], c[2], s0, k0);
+    carry_save(c[3], c[4], c[5], s1, k1);
+    carry_save(c[6], c[7], c[8], s2, k2);
+    carry_save(s0, s1, s2, s3, k3);
+    const uint32_t p0 = s3 ^ c[9], k4 = s3 & c[9];            // the ones; k0 .. k4 are twos
+    uint32_t t0, m0, p1, m1;
+    carry_save(k0, k1, k2, t0, m0);
+    carry_save(t0, k3, k4, p1, m1);                            // m0 and m1 are fours; a fill is at most ten, so one eight at most
+    const uint32_t p2 = m0 ^ m1, p3 = m0 & m1;
+    uint32_t left = lines_left, cells = 0u;
+#pragma unroll
+    for (int f = 9; f >= 1; --f) {
+        const uint32_t rows = tpl::kColMask & ((f & 1) ? p0 : ~p0) & ((f & 2) ? p1 : ~p1) & ((f & 4) ? p2 : ~p2) & ((f & 8) ? p3 : ~p3);
+        const uint32_t take = min((uint32_t)__builtin_popcount(rows), left);
+        cells += __umul24(take, (uint32_t)(10 - f));
+        left -= take;
+    }
+    return cells + __umul24(left, 10u);                        // at most 2,500
+}
+
+// What a running board with `lines` rows cleared after `moves` moves still owes and still has under the game's L and M: cells as
+// above for the L - lines rows owed, spare = 4 (M - moves) - cells, both 0 for a finished board; spare < 0 is a DEAD board.
+struct MoveBound { uint32_t cells; int32_t spare; };
+__device__ __forceinline__ MoveBound move_bound(const tpl::Board& s, uint32_t L, uint32_t M) {
+    const bool running = s.state == tpl::ST_RUNNING;
+    MoveBound out;
+    out.cells = running ? move_bound_cells(s.c, L > s.lines ? L - s.lines : 0u) : 0u;
+    out.spare = running ? 4 * ((int32_t)M - (int32_t)s.moves) - (int32_t)out.cells : 0;
+    return out;
+}
+
+// The one place where a bounded kernel parts from its twin (include/tpl_learn.h, the bounded form), after the move and before psi:
+// a running board that is dead becomes lost at the limit, and the spare cells of the board as it then stands are returned for the
+// value's last term.  In an unbounded unit this is nothing and returns 0.
+__device__ __forceinline__ int32_t bounded_move(tpl::Board& s, uint32_t L, uint32_t M) {
+    if constexpr (kUnitBound) {
+        const MoveBound bound = move_bound(s, L, M);
+        const bool dead = bound.spare < 0;
+        s.state = dead ? (uint32_t)tpl::ST_LOST_LIMIT : s.state;
+        return dead ? 0 : bound.spare;
+    } else {
+        return 0;
+    }
+}
+
+// value = w . phi, then + spare_weight * float(spare): one rounded multiply and one rounded add, made last; contraction off
+__device__ __forceinline__ float bounded_value(float score, float spare_weight, int32_t spare) {
+#pragma clang fp contract(off)
+    const float term = spare_weight * (float)spare;
+    return score + term;
 }
 
 // float32 -> uint32 with the order of the floats; -0 and +0 get one image, as they compare equal

@@ -16,6 +16,12 @@
     tune_heuristic(L, M, config_pool, ...)
                                   the weights by the noisy cross-entropy method (Szita & Lorincz 2006), fitness = win rate
 
+    move_bound(env)               the move bound of every board (include/tpl_learn.h): the cells its owed rows still miss, the spare
+                                  cells its remaining moves leave, and whether it is dead -- provably lost whatever pieces come
+    BeamPolicy(..., bound=True, spare_weight=x)
+                                  the bounded form: a move that leaves a dead board leaves it lost, and x times a node's spare
+                                  cells is added to its value; depth 1, width 1 is the bounded one-ply player
+
 With weights (r_line, r_win, r_lose, 0, ..., 0) the policy is LookaheadPolicy(env, image=None): the best immediate reward.
 
 The 14-feature form.  Weights of 14 entries ([14] or [P, 14], MOVE_FEATURE_NAMES) select it everywhere above: the twelve features
@@ -36,7 +42,7 @@ from ._learn_lib import (BEAM_MAX_DEPTH, BEAM_MAX_WIDTH, FEATURE_COUNTS, FEATURE
 from .lookahead import _boards, _ptr, _source_planes, _state_ptrs
 
 __all__ = ["FEATURE_NAMES", "MOVE_FEATURE_NAMES", "DELLACHERIE_WEIGHTS", "placement_features", "HeuristicPolicy", "BeamPolicy",
-           "evaluate_heuristic", "tune_heuristic"]
+           "evaluate_heuristic", "tune_heuristic", "move_bound"]
 
 # Dellacherie's controller in MOVE_FEATURE_NAMES' order and units: holes -4, row and column transitions -1, wells -1, landing height
 # -1 a row = -0.5 a half row, eroded cells +1; won and lost +-100 stand in for the end of the game, which his endless game has not
@@ -61,6 +67,27 @@ def placement_features(env, states_a: Optional[torch.Tensor] = None, states_b: O
     check(_learn_lib.entry("features", count)(_ptr(src_a), _ptr(src_b), k, env.L, env.M, features.data_ptr(), canonical.data_ptr(),
                                               stream))
     return features[:, :, :count], canonical
+
+
+def move_bound(env, states_a: Optional[torch.Tensor] = None, states_b: Optional[torch.Tensor] = None) -> dict:
+    """The move bound of K states (include/tpl_learn.h; tpl_move_bound): the resident boards of `env` (read in place), or int32
+    [K, 4] plane pairs as env.expand_states takes them, under env.L and env.M.  Returns device tensors [K]: cells int32, the cells
+    missing from the cheapest rows still owed; spare int32 = 4 (moves left) - cells; need int32 = ceil(cells / 4), the least number
+    of moves in which the board can still be won; dead bool = spare < 0: no continuation wins, whatever pieces come.  A finished
+    board gives 0, 0, 0, False."""
+    k, src_a, src_b = _source_planes(env, states_a, states_b, "move_bound")
+    d = env.device
+    cells = torch.empty(k, dtype=torch.int32, device=d)
+    spare = torch.empty(k, dtype=torch.int32, device=d)
+    stream = torch._C._cuda_getCurrentRawStream(d.index)
+    check(_learn_lib.lib().tpl_move_bound(_ptr(src_a), _ptr(src_b), k, env.L, env.M, cells.data_ptr(), spare.data_ptr(), stream))
+    return dict(cells=cells, spare=spare, need=(cells + 3) // 4, dead=spare < 0)
+
+
+def _bounded(bound, spare_weight):
+    """The validated (bound, spare_weight) of a beam player: a bool, and one finite float32 that is 0 unless bound is set."""
+    from .solve import _spare_weight
+    return bool(bound), _spare_weight(spare_weight, bound)
 
 
 def _weights(weights) -> np.ndarray:
@@ -190,10 +217,16 @@ class BeamPolicy(_WeightedPolicy):
     candidate order; the action is the first placement of the best leaf.  depth 1 is HeuristicPolicy; depth 2 with
     width >= 34 is HeuristicPolicy(depth=2).  One launch, nothing written but the outputs.
 
-    weights, boards_per_member, members and set_weights() are HeuristicPolicy's."""
+    weights, boards_per_member, members and set_weights() are HeuristicPolicy's.
 
-    def __init__(self, env, weights, depth: int, width: int, boards_per_member: Optional[int] = None):
+    bound=True plays the bounded form (tpl_placement_beam_bound): a move that leaves a board which the move bound proves lost
+    leaves it lost, and spare_weight -- one finite number for all weight rows, refused without bound=True -- times a node's spare
+    cells is added to its value.  Depth 1 and width 1 make the bounded one-ply player."""
+
+    def __init__(self, env, weights, depth: int, width: int, boards_per_member: Optional[int] = None, bound: bool = False,
+                 spare_weight: float = 0.0):
         self.depth, self.width = _beam_shape(depth, width)
+        self.bound, self.spare_weight = _bounded(bound, spare_weight)
         self._setup(env, weights, boards_per_member)
 
     @torch.no_grad()
@@ -208,9 +241,11 @@ class BeamPolicy(_WeightedPolicy):
         if plan is not None:
             env._own(plan, torch.uint8, "plan", (env.num_envs, self.depth))
         stream = torch._C._cuda_getCurrentRawStream(env.device.index)
-        check(_learn_lib.entry("beam", self.features)(self._planes[0], self._planes[1], env.num_envs, env.L, env.M,
-                                                      self._buffer.data_ptr(), self.boards_per_member, self.depth, self.width,
-                                                      out.data_ptr(), _ptr(plan), _ptr(score), stream))
+        spare = (self.spare_weight,) if self.bound else ()
+        check(_learn_lib.entry("beam", self.features, self.bound)(self._planes[0], self._planes[1], env.num_envs, env.L, env.M,
+                                                                  self._buffer.data_ptr(), self.boards_per_member, self.depth,
+                                                                  self.width, *spare, out.data_ptr(), _ptr(plan), _ptr(score),
+                                                                  stream))
         return out
 
 
@@ -221,10 +256,18 @@ def _player(depth, width):
     return (BeamPolicy,) + _beam_shape(depth, width)
 
 
-def _build_player(env, weights, boards_per_member, depth, width):
+def _build_player(env, weights, boards_per_member, depth, width, bound=False, spare_weight=0.0):
     if width is None:
         return HeuristicPolicy(env, weights, boards_per_member, depth=depth)
-    return BeamPolicy(env, weights, depth, width, boards_per_member)
+    return BeamPolicy(env, weights, depth, width, boards_per_member, bound=bound, spare_weight=spare_weight)
+
+
+def _player_bound(width, bound, spare_weight):
+    """(bound, spare_weight) of evaluate_heuristic and tune_heuristic: the bounded form is the beam's, so it needs a width."""
+    bound, spare_weight = _bounded(bound, spare_weight)
+    if bound and width is None:
+        raise ValueError("bound=True plays the bounded beam: give a width (depth=1, width=1 is the bounded one-ply player)")
+    return bound, spare_weight
 
 
 def _win_count_reward(env) -> None:
@@ -235,15 +278,17 @@ def _win_count_reward(env) -> None:
 
 @torch.no_grad()
 def evaluate_heuristic(env, weights, boards_per_member: Optional[int], steps: int, policy=None, depth: int = 1,
-                       width: Optional[int] = None) -> dict:
+                       width: Optional[int] = None, bound: bool = False, spare_weight: float = 0.0) -> dict:
     """Play `steps` steps of the population `weights` ([P, 12] or [12]) on `env` from a full reset: an auto-reset environment
     with a configuration pool and reward parameters (0, 1, 0), so that the summed reward is the number of wins.  Member p plays
     boards [p * boards_per_member, (p + 1) * boards_per_member).  Returns episodes and wins as int64 numpy arrays [P] and
     win_rate = wins / max(episodes, 1); the tallies are kept on the device, with one sync at the end.  `policy`: a
     HeuristicPolicy of this environment to reuse (its weights are replaced).  `depth`: 1 or 2 plies (HeuristicPolicy's); a
     `policy` that is passed must have been built with it.  `width`: None, or a beam width -- then a BeamPolicy(depth, width)
-    plays, depth may be 1 .. 12, and a `policy` that is passed must be a BeamPolicy of that depth and width."""
+    plays, depth may be 1 .. 12, and a `policy` that is passed must be a BeamPolicy of that depth and width.  `bound` and
+    `spare_weight` are BeamPolicy's and need a `width`; a `policy` that is passed must have been built with them."""
     kind, depth, width = _player(depth, width)
+    bound, spare_weight = _player_bound(width, bound, spare_weight)
     if policy is not None:
         if isinstance(policy, BeamPolicy) != (kind is BeamPolicy):
             raise ValueError(f"policy is a {type(policy).__name__}, but width={width} asks for a {kind.__name__}")
@@ -251,13 +296,15 @@ def evaluate_heuristic(env, weights, boards_per_member: Optional[int], steps: in
             raise ValueError(f"policy was built with depth {policy.depth}, not {depth}")
         if width is not None and policy.width != width:
             raise ValueError(f"policy was built with width {policy.width}, not {width}")
+        if width is not None and (policy.bound, policy.spare_weight) != (bound, spare_weight):
+            raise ValueError(f"policy was built with bound={policy.bound}, spare_weight={policy.spare_weight}, not {bound}, {spare_weight}")
     _win_count_reward(env)
     if not env.auto_reset:
         raise ValueError("evaluate_heuristic needs an auto-reset environment")
     if isinstance(steps, bool) or int(steps) != steps or int(steps) < 1:
         raise ValueError("steps must be a positive integer")
     if policy is None:
-        policy = _build_player(env, weights, boards_per_member, depth, width)
+        policy = _build_player(env, weights, boards_per_member, depth, width, bound, spare_weight)
     else:
         if policy.env is not env:
             raise ValueError("policy belongs to another environment")
@@ -284,7 +331,8 @@ def evaluate_heuristic(env, weights, boards_per_member: Optional[int], steps: in
 
 def tune_heuristic(L: int, M: int, config_pool, population: int = 64, boards_per_member: int = 4096, steps: Optional[int] = None,
                    generations: int = 20, elite_frac: float = 0.125, init_mean=None, init_std: float = 10.0, noise: float = 0.5,
-                   seed: int = 0, device="cuda:0", depth: int = 1, width: Optional[int] = None, features: int = NUM_FEATURES) -> dict:
+                   seed: int = 0, device="cuda:0", depth: int = 1, width: Optional[int] = None, features: int = NUM_FEATURES,
+                   bound: bool = False, spare_weight: float = 0.0) -> dict:
     """The noisy cross-entropy method on the twelve weights, or with features=14 on the fourteen of the 14-feature form (`init_mean`
     must have that length; at 12 the draws and the results are what they were before the argument existed).  Each generation samples `population` weight rows from
     N(mean, diag std^2) with a CPU torch.Generator seeded by `seed`, plays them side by side (`boards_per_member` boards each,
@@ -292,12 +340,14 @@ def tune_heuristic(L: int, M: int, config_pool, population: int = 64, boards_per
     population * boards_per_member boards over `config_pool` = (rows, pieces) with reward (0, 1, 0), takes fitness = wins /
     max(episodes, 1), and refits mean and std to the best ceil(elite_frac * population) rows, std^2 = var(elite) + noise (the
     constant noise term that keeps the search from freezing early).  `depth`: the plies the members search (1 or 2); with a
-    `width` the members are BeamPolicy(depth, width) and depth may be 1 .. 12.
+    `width` the members are BeamPolicy(depth, width) and depth may be 1 .. 12; `bound` and `spare_weight` are then BeamPolicy's (one
+    spare_weight for the whole population: it is not tuned) and are refused without a width.
 
     Returns mean (float32 [12] or [14], the final one), best (likewise, the best member seen) with best_fitness, and history: one
     dict of host floats per generation (population_mean, elite_mean, best).  Deterministic for a given seed."""
     from .env import BatchedTetris
     _, depth, width = _player(depth, width)
+    bound, spare_weight = _player_bound(width, bound, spare_weight)
     for name, v in (("population", population), ("boards_per_member", boards_per_member), ("generations", generations)):
         if isinstance(v, bool) or int(v) != v or int(v) < 1:
             raise ValueError(f"{name} must be a positive integer")
@@ -332,8 +382,9 @@ def tune_heuristic(L: int, M: int, config_pool, population: int = 64, boards_per
             z = torch.randn((P, F), generator=gen, dtype=torch.float64).numpy()
             rows = (mean[None, :] + std[None, :] * z).astype(np.float32)
             if policy is None:
-                policy = _build_player(env, rows, per, depth, width)
-            fitness = evaluate_heuristic(env, rows, per, steps, policy=policy, depth=depth, width=width)["win_rate"]
+                policy = _build_player(env, rows, per, depth, width, bound, spare_weight)
+            fitness = evaluate_heuristic(env, rows, per, steps, policy=policy, depth=depth, width=width, bound=bound,
+                                         spare_weight=spare_weight)["win_rate"]
             order = np.argsort(-fitness, kind="stable")        # ties: the lower member first
             top = rows[order[:elite]].astype(np.float64)
             if fitness[order[0]] > best_fitness:

@@ -6,7 +6,10 @@ configuration, stops at the first ply at which it sees a win and returns the mov
 games to keep (`ForwardGames(solver="beam")`), checking pools from files for winnability on the device, and building pools with a
 tighter move budget from the solution lengths (`tighten_pool`).
 
-`solved = False` means that this beam, with these weights at this width, found no win.  It does NOT mean that there is none.
+`solved = False` means that this beam, with these weights at this width, found no win.  It does NOT mean that there is none --
+unless the search was the bounded one and `complete`: `solve_configs(bound=True)` prunes every board that the move bound
+(include/tpl_learn.h) proves lost, reports `bound`, the least number of moves any solution can take (`config_bound` gives it alone),
+and `complete`, under which `solved = False` IS a proof that there is no win and `solved = True` that the solution is the shortest.
 """
 from __future__ import annotations
 
@@ -14,7 +17,7 @@ import numpy as np
 
 from ._learn_lib import BEAM_MAX_WIDTH, NUM_FEATURES, NUM_MOVE_FEATURES, SOLVE_MAX_MOVES
 
-__all__ = ["CLASSICAL_WEIGHTS", "solve_configs", "tighten_pool"]
+__all__ = ["CLASSICAL_WEIGHTS", "solve_configs", "tighten_pool", "config_bound"]
 
 # cleared, won, lost, holes, aggregate height, max height, bumpiness, row and column transitions, wells, rows with holes, hole depth:
 # the classical signs, a sensible default for the supply (0.99925 of a carved L = 10 / M = 40 pool at one ply)
@@ -69,8 +72,62 @@ def _shapes(rows, pieces, M: int) -> int:
     return n
 
 
+def _spare_weight(spare_weight, bound) -> float:
+    """The validated spare_weight of a bounded search: one finite float32; anything but 0 needs bound=True."""
+    if not isinstance(bound, (bool, np.bool_)):
+        raise ValueError(f"bound must be True or False, got {bound!r}")
+    if isinstance(spare_weight, bool) or not isinstance(spare_weight, (int, float, np.integer, np.floating)):
+        raise ValueError(f"spare_weight must be a number, got {spare_weight!r}")
+    with np.errstate(over="ignore"):
+        value = np.float32(spare_weight)
+    if not np.isfinite(value):
+        raise ValueError("spare_weight must be finite (in float32)")
+    if value != 0 and not bound:
+        raise ValueError("spare_weight belongs to the bounded search: give bound=True")
+    return float(value)
+
+
+def _device_rows(rows, d):
+    """rows as solve_configs takes them -> a contiguous int16 / uint16 [n, 20] tensor on device d."""
+    import torch
+    if not _is_tensor(rows):
+        if rows.ndim == 3:
+            rows = (rows.astype(np.uint16) << np.arange(10, dtype=np.uint16)).sum(-1).astype(np.uint16)
+        rows = torch.from_numpy(np.ascontiguousarray(rows.astype(np.uint16)).view(np.int16))
+    elif rows.dim() == 3:
+        rows = (rows.to(torch.int32) << torch.arange(10, device=rows.device, dtype=torch.int32)).sum(-1).to(torch.int16)
+    rows = rows.to(d).contiguous()
+    if rows.dtype not in (torch.int16, torch.uint16):
+        rows = rows.to(torch.int16)
+    return rows
+
+
+def config_bound(rows, L: int, device="cuda:0"):
+    """The least number of moves any solution of each configuration can take (include/tpl_learn.h: the move bound;
+    tpl_move_bound_rows): int32 [n] on `device`, ceil(cells / 4) with cells the cells missing from the L cheapest rows.  rows as
+    solve_configs takes them: tensors or arrays, [n, 20] row masks or [n, 20, 10] cells.  A configuration whose budget M is below
+    this has no solution, whatever its pieces."""
+    import torch
+    from . import _learn_lib
+    L, _ = _game(L, 1)
+    if not _is_tensor(rows):
+        rows = np.asarray(rows)
+    rs = tuple(rows.shape)
+    n = rs[0] if rs else 0
+    if not (rs == (n, 20) or rs == (n, 20, 10)):
+        raise ValueError(f"rows must be [n, 20] row masks or [n, 20, 10] cells; got {rs}")
+    if n < 1:
+        raise ValueError("at least one configuration is needed")
+    d = torch.device(device)
+    rows = _device_rows(rows, d)
+    cells = torch.empty(n, dtype=torch.int32, device=d)
+    stream = torch._C._cuda_getCurrentRawStream(d.index if d.index is not None else torch.cuda.current_device())
+    _learn_lib.check(_learn_lib.lib().tpl_move_bound_rows(rows.data_ptr(), n, L, cells.data_ptr(), stream))
+    return (cells + 3) // 4
+
+
 def solve_configs(rows, pieces, L: int, M: int, weights=None, width: int = 16, device="cuda:0", best_value: bool = False,
-                  validate: bool = True) -> dict:
+                  validate: bool = True, bound: bool = False, spare_weight: float = 0.0) -> dict:
     """Search every configuration's whole game with the placement beam (the rule: include/tpl_learn.h, tpl_placement_solve).
 
     rows: [n, 20] int16 / uint16 (bit x = column x) or [n, 20, 10] bool, converted as `load_configs` converts them; pieces:
@@ -82,27 +139,28 @@ def solve_configs(rows, pieces, L: int, M: int, weights=None, width: int = 16, d
     of every ply run, +0 behind.
 
     solved[i] = False means that THIS beam found no win for configuration i, not that there is none.
+
+    bound=True searches in the bounded form (tpl_placement_solve_bound): a move that leaves a board which the move bound proves lost
+    -- the cells missing from the rows still owed cannot be supplied in the moves left -- leaves it lost, and spare_weight (one
+    finite number, 0 by default; refused without bound=True) times a node's spare cells is added to its value.  The dict then also
+    holds bound int32 [n], the least number of moves any solution can take; complete bool [n], set where no cut dropped a running
+    candidate; and optimal bool [n] = solved & ((solution_len == bound) | complete).  **With complete[i] set, solved[i] = False is a
+    proof that configuration i has no win within M moves, and solved[i] = True a proof that solution_len[i] is the shortest there
+    is; without it, solved[i] = False still proves nothing.**  bound=False launches the unbounded entry and returns its dict.
     No host wait except the piece-id check (ids 0..6, as load_configs'), which validate=False skips."""
     import torch
     from . import _learn_lib
     L, M = _game(L, M)
     width = _width(width)
     w = _weight_row(weights)
+    spare_weight = _spare_weight(spare_weight, bound)
     if not _is_tensor(rows):
         rows = np.asarray(rows)
     if not _is_tensor(pieces):
         pieces = np.asarray(pieces)
     n = _shapes(rows, pieces, M)
     d = torch.device(device)
-    if not _is_tensor(rows):
-        if rows.ndim == 3:
-            rows = (rows.astype(np.uint16) << np.arange(10, dtype=np.uint16)).sum(-1).astype(np.uint16)
-        rows = torch.from_numpy(np.ascontiguousarray(rows.astype(np.uint16)).view(np.int16))
-    elif rows.dim() == 3:
-        rows = (rows.to(torch.int32) << torch.arange(10, device=rows.device, dtype=torch.int32)).sum(-1).to(torch.int16)
-    rows = rows.to(d).contiguous()
-    if rows.dtype not in (torch.int16, torch.uint16):
-        rows = rows.to(torch.int16)
+    rows = _device_rows(rows, d)
     if not _is_tensor(pieces):
         pieces = torch.as_tensor(np.ascontiguousarray(pieces.astype(np.uint8)))
     pieces = pieces.to(device=d, dtype=torch.uint8)
@@ -117,22 +175,37 @@ def solve_configs(rows, pieces, L: int, M: int, weights=None, width: int = 16, d
     if best_value:
         out["best_value"] = torch.empty((n, M), dtype=torch.float32, device=d)
     stream = torch._C._cuda_getCurrentRawStream(d.index if d.index is not None else torch.cuda.current_device())
-    _learn_lib.check(_learn_lib.entry("solve", w.shape[0])(rows.data_ptr(), pieces.data_ptr(), n, L, M, wt.data_ptr(), width,
-                                                           out["solved"].data_ptr(), out["solution_len"].data_ptr(),
-                                                           out["actions"].data_ptr(),
-                                                           out["best_value"].data_ptr() if best_value else None, stream))
+    head = (rows.data_ptr(), pieces.data_ptr(), n, L, M, wt.data_ptr(), width)
+    outs = (out["solved"].data_ptr(), out["solution_len"].data_ptr(), out["actions"].data_ptr(),
+            out["best_value"].data_ptr() if best_value else None)
+    if bound:
+        out["bound"] = torch.empty(n, dtype=torch.int32, device=d)
+        out["complete"] = torch.empty(n, dtype=torch.uint8, device=d)
+        _learn_lib.check(_learn_lib.entry("solve", w.shape[0], bound=True)(*head, spare_weight, *outs, out["bound"].data_ptr(),
+                                                                          out["complete"].data_ptr(), stream))
+        out["complete"] = out["complete"].view(torch.bool)
+    else:
+        _learn_lib.check(_learn_lib.entry("solve", w.shape[0])(*head, *outs, stream))
     out["solved"] = out["solved"].view(torch.bool)
+    if bound:
+        out["optimal"] = out["solved"] & ((out["solution_len"] == out["bound"]) | out["complete"])
     played = out["actions"] != 255
     a = torch.where(played, out["actions"], torch.zeros_like(out["actions"]))
     out["solution"] = torch.stack([a // 10, a % 10], dim=2).to(torch.uint8)
     return out
 
 
-def tighten_pool(rows, pieces, solved, solution_len, M_new: int):
+def tighten_pool(rows, pieces, solved, solution_len, M_new: int, bound=None, slack=None):
     """A pool with a tighter move budget: (rows, pieces[:, :M_new + 1]) of the configurations that are `solved` with
     solution_len <= M_new -- a pool for BatchedTetris(L, M_new), every entry of it winnable within M_new moves by the solution
     that was found.  Tensors (one host wait) or arrays; M is read off pieces [n, M + 1].  M_new outside [1, M] is refused, and so
-    is a result with nothing left."""
+    is a result with nothing left.
+    `bound` ([n], config_bound's or solve_configs(bound=True)'s) and `slack` (an integer >= 0), given together, also require
+    bound >= M_new - slack: a pool whose budget is provably within `slack` moves of the least any solution can take."""
+    if (bound is None) != (slack is None):
+        raise ValueError("bound and slack go together")
+    if slack is not None and (isinstance(slack, bool) or not isinstance(slack, (int, np.integer)) or int(slack) < 0):
+        raise ValueError(f"slack must be an integer >= 0, got {slack!r}")
     if len(pieces.shape) != 2 or pieces.shape[1] < 2:
         raise ValueError("pieces must be [n, M + 1]")
     n, M = int(pieces.shape[0]), int(pieces.shape[1]) - 1
@@ -141,11 +214,18 @@ def tighten_pool(rows, pieces, solved, solution_len, M_new: int):
     M_new = int(M_new)
     if tuple(rows.shape[:2]) != (n, 20) or tuple(solved.shape) != (n,) or tuple(solution_len.shape) != (n,):
         raise ValueError(f"rows must be [{n}, 20] and solved and solution_len [{n}]")
+    if bound is not None and tuple(bound.shape) != (n,):
+        raise ValueError(f"bound must be [{n}]")
     if _is_tensor(rows):
         keep = solved.to(device=rows.device).bool() & (solution_len.to(rows.device) <= M_new)
+        if bound is not None:
+            import torch
+            keep = keep & (torch.as_tensor(bound).to(rows.device) >= M_new - int(slack))
         out = rows[keep], pieces.to(rows.device)[keep][:, :M_new + 1].contiguous()
     else:
         keep = np.asarray(solved).astype(bool) & (np.asarray(solution_len) <= M_new)
+        if bound is not None:
+            keep = keep & (np.asarray(bound.cpu() if _is_tensor(bound) else bound) >= M_new - int(slack))
         out = np.asarray(rows)[keep], np.ascontiguousarray(np.asarray(pieces)[keep][:, :M_new + 1])
     if out[0].shape[0] == 0:
         raise ValueError(f"no configuration is solved within {M_new} moves: nothing is left of the pool")

@@ -141,7 +141,7 @@ PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600, "priority": 600
          "ntuple_search": 900, "ntuple_trace": 600, "ntuple_trace_sweep": 1100, "ntuple_coherent": 600,
          "ntuple_coherent_sweep": 1700, "ntuple_shape": 600, "ntuple_shape_sweep": 1100, "ntuple_beam": 1100,
          "ntuple_sum": 600, "ntuple_sum_sweep": 600, "ntuple_stage": 600, "ntuple_stage_sweep": 900,
-         "ntuple_feature": 600, "ntuple_feature_sweep": 900, "solve": 900, "move_features": 1100}
+         "ntuple_feature": 600, "ntuple_feature_sweep": 900, "solve": 900, "move_features": 1100, "bound": 900}
 SCATTERED_ATOMICS = 0.08e12                                 # 64 lanes of a wave adding into 64 rows (float adds; integer adds unmeasured)
 VALU_CYCLES, SIMDS, CLOCK_HZ = 3.3, 1024, 2.4e9           # the move's instruction mix, 256 CUs x 4, the clock
 
@@ -2330,6 +2330,135 @@ def part_move_features(rounds=5, generations=8, population=32, per=2048):
         out["solver"][f"w{W}"] = line
     progress(out["solver"])
     out["not_measured"] = "other seeds, other M_new, other tuning budgets"
+    return out
+
+
+def part_bound(rounds=5):
+    """The move bound (include/tpl_learn.h): what the bounded kernels cost beside their twins in the same run, what the prune and the
+    spare term do for the players on the tight pool of part_solve (carved L = 10 / M = 40, 65,536 configurations, seed 7, solved at
+    width 16, tighten_pool(M_new=16)), and what the bounded solver proves on the carved pool at budgets of config_bound + s.  One seed
+    and one pool."""
+    import numpy as np
+    import torch
+    import tetris_piclim as T
+    dev = "cuda:0"
+    L_, M_ = 10, 40
+    share = lambda x: round(float(x.float().mean()), 5)
+    median = lambda ts: sorted(ts)[len(ts) // 2]
+    out = dict(part="bound", time=dict(solve=[], beam=[]), tight={}, solver=[])
+
+    def progress(what):
+        print(json.dumps(what), file=sys.stderr, flush=True)
+
+    classical = np.array(T.CLASSICAL_WEIGHTS)
+    # the tuned rows as profiles/learner/README.md prints them, to four decimals
+    tuned12 = np.array([0.7636, 9.9996, -10.2889, -2.1088, 0.0836, -1.2467, -0.65, -0.5988, -2.9422, -0.2366, -1.9736, -0.847], np.float32)
+    tuned14 = np.array([-0.2654, 10.3718, -11.7624, -2.251, -0.1728, 0.3929, 0.325, -1.3091, -1.6597, -0.9162, -1.5434, -1.832, -0.9158,
+                        0.2822], np.float32)
+    players = dict(classical=classical, dellacherie=np.array(T.DELLACHERIE_WEIGHTS), tuned12=tuned12, tuned14=tuned14)
+
+    # 1. the solver on the carved pool at M = config_bound + s and at M = 40, bounded and plain
+    n = 1 << 16
+    env = T.BatchedTetris(L_, M_, 64, device=dev, seed=7)
+    rows, pieces, _, carved_len = env.carved_configs(n, seed=7, with_solutions=True)
+    env.terminate()
+    need = T.config_bound(rows, L_, device=dev)
+    out["pool"] = dict(size=n, seed=7, L=L_, M=M_, config_bound_equals_carving_len=share(need == carved_len),
+                       config_bound_mean=round(float(need.float().mean()), 2))
+    for slack in (0, 1, 2, None):
+        budget = torch.full_like(need, M_) if slack is None else torch.clamp(need + slack, max=M_)
+        for W in (1, 8, 16, 64):
+            line = dict(budget="M = 40" if slack is None else f"config_bound + {slack}", width=W)
+            for form in ("plain", "bounded"):
+                solved, length, complete = (torch.zeros(n, dtype=torch.bool, device=dev), torch.zeros(n, dtype=torch.int32, device=dev),
+                                            torch.zeros(n, dtype=torch.bool, device=dev))
+                for b in torch.unique(budget).tolist():
+                    at = torch.nonzero(budget == b).flatten()
+                    got = T.solve_configs(rows[at], pieces[at][:, :b + 1].contiguous(), L_, b, width=W, device=dev, validate=False,
+                                          bound=form == "bounded")
+                    solved[at], length[at] = got["solved"], got["solution_len"]
+                    if form == "bounded":
+                        complete[at] = got["complete"]
+                line[form] = dict(solved=share(solved), mean_len=round(float(length[solved].float().mean()), 2) if bool(solved.any()) else None)
+                if form == "bounded":
+                    optimal = solved & ((length == need) | complete)
+                    line[form].update(complete=share(complete), optimal=share(optimal), proved_unwinnable=share(~solved & complete))
+            out["solver"].append(line)
+            progress(line)
+
+    # 2. the tight pool of the record, and the players on it
+    found = T.solve_configs(rows, pieces, L_, M_, width=16, device=dev, validate=False)
+    M_new = 16
+    tight = T.tighten_pool(rows, pieces, found["solved"], found["solution_len"], M_new)
+    tight_need = T.config_bound(tight[0], L_, device=dev)
+    out["tight"] = dict(M_new=M_new, size=int(tight[0].shape[0]), of=n, config_bound_mean=round(float(tight_need.float().mean()), 2),
+                        share_with_config_bound_16=share(tight_need == 16), players={})
+
+    def result(e, wins):
+        p = wins / max(e, 1)
+        return dict(episodes=int(e), wins=int(wins), win_rate=round(p, 5), standard_error=round((p * (1 - p) / max(e, 1)) ** 0.5, 6))
+
+    def play(w, depth, width, **kw):
+        env = T.BatchedTetris(L_, M_new, 1 << 14, device=dev, seed=11, auto_reset=True, reward=(0.0, 1.0, 0.0), config_pool=tight)
+        got = T.evaluate_heuristic(env, w, None, 16 * (M_new + 1), depth=depth, width=width, **kw)
+        env.terminate()
+        return result(int(got["episodes"][0]), int(got["wins"][0]))
+
+    out["tight"]["classical_one_ply_as_the_record_plays_it"] = play(classical, 1, None)
+    out["tight"]["classical_beam_3x8_as_the_record_plays_it"] = play(classical, 3, 8)
+    progress(out["tight"])
+    for name, w in players.items():
+        got = {}
+        for depth, width in ((1, 1), (3, 8)):
+            for label, kw in (("off", {}), ("on", dict(bound=True)), ("on_spare_0.25", dict(bound=True, spare_weight=0.25)),
+                              ("on_spare_1", dict(bound=True, spare_weight=1.0))):
+                got[f"beam_{depth}x{width}_{label}"] = play(w, depth, width, **kw)
+        out["tight"]["players"][name] = got
+        progress({name: {k: v["win_rate"] for k, v in got.items()}})
+
+    # 3. time: every bounded kernel against its own twin in the same run, alternated
+    count = 1 << 20
+    env = T.BatchedTetris(L_, M_, count, device=dev, seed=7, auto_reset=False, assign="sequential")
+    rows, pieces = env.carved_configs(count, seed=7)
+    env.load_configs(rows, pieces, validate=False)
+    env.reset()
+    lib, stream = T._learn_lib.lib(), torch._C._cuda_getCurrentRawStream(0)
+    outs = (torch.empty(count, dtype=torch.uint8, device=dev), torch.empty(count, dtype=torch.int32, device=dev),
+            torch.empty((count, M_), dtype=torch.uint8, device=dev), torch.empty(count, dtype=torch.int32, device=dev),
+            torch.empty(count, dtype=torch.uint8, device=dev))
+    for F, w in ((12, classical), (14, players["dellacherie"])):
+        wt = torch.from_numpy(T._learn_lib.padded_weights(w)).to(dev)
+        head = (rows.data_ptr(), pieces.data_ptr(), count, L_, M_, wt.data_ptr())
+        o = [x.data_ptr() for x in outs]
+        for W in (8, 16, 64):
+            twin = lambda: T._learn_lib.check(T._learn_lib.entry("solve", F)(*head, W, o[0], o[1], o[2], None, stream))
+            mine = lambda: T._learn_lib.check(T._learn_lib.entry("solve", F, True)(*head, W, 0.0, o[0], o[1], o[2], None, o[3], o[4], stream))
+            ta, tb = [], []
+            for _ in range(rounds):
+                ta.append(_timed(twin, 1, warmup=1))
+                tb.append(_timed(mine, 1, warmup=1))
+            line = dict(kernel="solve", features=F, width=W, configurations=count, M=M_, twin_ms=round(median(ta) * 1e3, 3),
+                        bounded_ms=round(median(tb) * 1e3, 3), ratio=round(median(tb) / median(ta), 4))
+            out["time"]["solve"].append(line)
+            progress(line)
+        action = torch.empty(count, dtype=torch.uint8, device=dev)
+        for depth, width in ((1, 1), (3, 8), (6, 16)):
+            twin, mine = T.BeamPolicy(env, w, depth, width), T.BeamPolicy(env, w, depth, width, bound=True)
+            ta, tb = [], []
+            for _ in range(rounds):
+                ta.append(_timed(lambda: twin.act(out=action), 2, warmup=1))
+                tb.append(_timed(lambda: mine.act(out=action), 2, warmup=1))
+            line = dict(kernel="beam", features=F, depth=depth, width=width, boards=count, twin_ms=round(median(ta) * 1e3, 3),
+                        bounded_ms=round(median(tb) * 1e3, 3), ratio=round(median(tb) / median(ta), 4))
+            out["time"]["beam"].append(line)
+            progress(line)
+    env.terminate()
+    res = subprocess.run(["bash", os.path.join(ROOT, "tools", "kernel_resources.sh"), T._learn_lib.build_library()],
+                         capture_output=True, text=True, cwd=ROOT)
+    out["kernel"] = [" ".join(l.split()) for l in res.stdout.splitlines()
+                     if any(k in l for k in ("placement_solve", "placement_beam", "move_bound"))]
+    out["scratch_bytes_over_every_kernel"] = sum(int(l.split()[l.split().index("scratch") - 1]) for l in res.stdout.splitlines() if " scratch " in l)
+    out["note"] = "fresh boards at M = 40 have no dead child for many plies: the time ratios are the cost of the bound, not the gain of the prune"
     return out
 
 
