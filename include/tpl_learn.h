@@ -917,6 +917,66 @@ int tpl_ntuple_update_trace_feature(const void* ring_a, const void* ring_b, int6
                                     int32_t symmetric, void* stream);
 int tpl_ntuple_feature_bins(const void* plane_a, const void* plane_b, int64_t n, uint8_t* bins, void* stream);
 
+/* The budget table: a feature table with a row for the spare cells of the move bound, and the dead-board prune.  A feature table sees
+ * the move budget only through one additive counter entry, clamped at 15 lines and 63 moves; it cannot see the one quantity the game
+ * is named after, the cells a board can still waste, and its policies keep valuing children that the move bound proves lost.
+ *
+ * BUDGET TABLE ("feat+spare"): int32 [TPL_NTUPLE_ENTRIES_BUDGET = 8 * 10 * 256 + 1,024 = 21,504] (86,016 bytes), 16-byte aligned, in
+ * units of 2^-16:
+ *   row[p][j][q]   at index (p * 10 + j) * 256 + q    p in 0..7 the falling piece, j in 0..9, q in 0..255: 20,480 entries
+ *   counter[k]     at index 20,480 + k                k the counter index above
+ * Rows j = 0 .. 8 are the feature table's, read at q_j = min(phi_{3+j}, 255).  Row 9 is read at
+ *   sbin = dead ? 0 : min(spare + 1, 255),   spare = 4 (M - moves) - cells,   cells = cells(board, max(L - lines, 0)),   dead = spare < 0
+ * -- exactly the move bound above (csrc/learn/tpl_placement.h: move_bound), from the board's OWN lines and moves under the game's L and
+ * M, never from the clamped counter index k: at L = 20, M = 100 a fresh empty board has spare 200 and reads bin 201.  BOTH CLAMPS ARE
+ * PART OF THE RULE, so no state addresses outside the buffer.  A finished board has spare 0 and is not dead: bin 1 (only
+ * tpl_ntuple_budget_bins shows it).  No other form has 21,504 entries.
+ * All ten row entries and the counter are ALWAYS used.
+ * Value:   V(s) = float32(S) * 2^-16 for a running s, S the exact 64-bit sum of its eleven entries, rounded once; 0 otherwise.
+ * Mirror image: the nine features and spare are invariant under the left-right reflection of the board (a row's fill is), so sigma
+ *   moves only the piece: sigma(row[p][j][q]) = row[pi(p)][j][q], the counters stay.
+ * Update (tpl_ntuple_update_trace_budget): tpl_ntuple_update_trace_feature's rule with eleven adds a state: d_k goes to the ten row
+ *   entries and the counter entry; with symmetric != 0 every row add is made a second time at (pi(p), j, q), also where the two
+ *   entries are one, and the counter is added once.  Nothing is read: the bytes are the same whatever order the adds arrive in.
+ * There are no staged, no coherent and no summed budget tables.
+ *
+ * THE PRUNE is a flag of the three policies, `prune`, 0 by default in every caller.  With prune != 0, wherever a move -- the first
+ * move, the second move of tpl_ntuple_search_budget, a move of any ply of tpl_ntuple_beam_budget -- leaves a RUNNING board that is
+ * dead, the move is scored as one that ends the game lost at the limit: its reward is move_reward with that state (r_line * rows +
+ * r_lose), there is no gamma * V term, and nothing is searched below it (in the beam the child is a finished node that competes with
+ * its own value).  The prune enters scores and the arg-max only: after_a / after_b and `value` stay the true, running afterstate of
+ * the action played and the table's value of it, because the environment plays on.  The exploration draw stays uniform over the
+ * distinct placements.  With prune = 0, and row 9 all zero, every output is what the _feature entries give for the feature table with
+ * the same nine rows and counters, bit for bit.
+ *
+ * tpl_ntuple_value_budget, _act_budget, _search_budget and _beam_budget take the arguments of their _feature twins without `form`; the
+ * three policies take one more int32 `prune` before `stream`.  They keep the twins' checks, in their order, under their own names,
+ * their outputs, their exploration draw and their ties.  tpl_ntuple_update_trace_budget takes tpl_ntuple_update_trace_feature's
+ * arguments and checks.  tpl_ntuple_budget_bins writes the ten bins of every state, running or not, as uint8 [n][10] -- for tests and
+ * inspection, NOT a hot-path entry --; it reads L and M and refuses what tpl_ntuple_value_budget refuses for the planes, n, L and M,
+ * and a NULL bins.  Kernels: the device bodies of the twins under the geometry BudgetTable (csrc/learn/tpl_ntuple.h), whose board sum
+ * is feature_bins and move_bound on the board the lane holds, ten gathers and the counter -- ntuple_budget_{value,act,search,bins}_kernel
+ * (ntuple.hip), ntuple_budget_beam_kernel (ntuple_beam.hip); the update is ntuple_budget_trace_kernel<symmetric>, whose blocks sum
+ * their states' adds in an LDS image of the whole table (84 KB: one block a CU) and flush the non-zero sums with one atomic add each. */
+#define TPL_NTUPLE_BUDGET_ROWS 10
+#define TPL_NTUPLE_ENTRIES_BUDGET 21504
+int tpl_ntuple_value_budget(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const int32_t* table,
+                            float* value, void* stream);
+int tpl_ntuple_act_budget(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line, float r_win,
+                          float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed, uint64_t step,
+                          uint8_t* action, float* score, void* after_a, void* after_b, float* value, int32_t prune, void* stream);
+int tpl_ntuple_search_budget(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line, float r_win,
+                             float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed, uint64_t step,
+                             uint8_t* action, uint8_t* second, float* score, void* after_a, void* after_b, float* value,
+                             int32_t prune, void* stream);
+int tpl_ntuple_beam_budget(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line, float r_win,
+                           float r_lose, float gamma, const int32_t* table, int32_t depth, int32_t width, uint8_t* action,
+                           uint8_t* plan, float* score, void* after_a, void* after_b, int32_t prune, void* stream);
+int tpl_ntuple_update_trace_budget(const void* ring_a, const void* ring_b, int64_t n, int32_t slots, int32_t head, int32_t horizon,
+                                   int32_t L, int32_t M, int32_t* table, const float* error, float rate, float decay,
+                                   int32_t symmetric, void* stream);
+int tpl_ntuple_budget_bins(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, uint8_t* bins, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,6 +45,8 @@ LEARN_SYMBOLS = [
     "tpl_placement_solve_move",
     "tpl_move_bound", "tpl_move_bound_rows", "tpl_placement_solve_bound", "tpl_placement_solve_move_bound",
     "tpl_placement_beam_bound", "tpl_placement_beam_move_bound",
+    "tpl_ntuple_value_budget", "tpl_ntuple_act_budget", "tpl_ntuple_search_budget", "tpl_ntuple_beam_budget",
+    "tpl_ntuple_update_trace_budget", "tpl_ntuple_budget_bins",
 ]
 NSTEP_MAX = 16
 BEAM_MAX_DEPTH, BEAM_MAX_WIDTH = 12, 64
@@ -204,6 +206,16 @@ def lib() -> C.CDLL:
     L.tpl_ntuple_update_trace_feature.restype = i32
     L.tpl_ntuple_feature_bins.argtypes = [vp, vp, i64, vp, vp]
     L.tpl_ntuple_feature_bins.restype = i32
+    # the budget table: the _feature twin's arguments without `form`, the policies with `prune` in its place
+    L.tpl_ntuple_value_budget.argtypes = L.tpl_ntuple_value.argtypes
+    L.tpl_ntuple_act_budget.argtypes = L.tpl_ntuple_act.argtypes[:-1] + [i32, vp]
+    L.tpl_ntuple_search_budget.argtypes = L.tpl_ntuple_search.argtypes[:-1] + [i32, vp]
+    L.tpl_ntuple_beam_budget.argtypes = L.tpl_ntuple_beam.argtypes
+    L.tpl_ntuple_update_trace_budget.argtypes = L.tpl_ntuple_update_trace.argtypes
+    L.tpl_ntuple_budget_bins.argtypes = [vp, vp, i64, i32, i32, vp, vp]
+    for name in ("value", "act", "search", "beam", "update_trace"):
+        getattr(L, f"tpl_ntuple_{name}_budget").restype = i32
+    L.tpl_ntuple_budget_bins.restype = i32
     for name in ("tpl_replay_push", "tpl_replay_sample", "tpl_learn_pack", "tpl_priority_init", "tpl_priority_push",
                  "tpl_priority_update", "tpl_replay_sample_prioritized", "tpl_replay_sample_nstep", "tpl_replay_sample_mirror",
                  "tpl_mirror_states", "tpl_afterstates", "tpl_placement_features", "tpl_placement_act",
@@ -897,10 +909,20 @@ _PART_ENTRIES = {"2x4": NTUPLE_SHAPES["2x4"][2], "3x3": NTUPLE_SHAPES["3x3"][2],
 _PART_COLUMNS = {"2x4": 154, "3x3": 145, "feat": NTUPLE_FEATURES + 1}      # the columns of ntuple_indices, the counter's included
 NTUPLE_ENTRIES_3X3_FEAT = _PART_ENTRIES["3x3"] + NTUPLE_ENTRIES_FEAT                             # 610,304
 
+# The budget table (include/tpl_learn.h): a feature table with a tenth row per piece, read at the spare cells of the move bound.  A
+# registry of its own again -- name -> the one form the _budget entries read --, beside the three above, which stay as they are
+NTUPLE_BUDGET_FORMS = {"feat+spare": 0}
+BUDGET = "feat+spare"
+NTUPLE_BUDGET_ROWS = NTUPLE_FEATURES + 1                                                         # the nine feature rows, then spare
+NTUPLE_ENTRIES_BUDGET = NTUPLE_PIECES * NTUPLE_BUDGET_ROWS * NTUPLE_FEATURE_BINS + NTUPLE_COUNTERS   # 21,504
+_PART_ENTRIES[BUDGET] = NTUPLE_ENTRIES_BUDGET
+_PART_COLUMNS[BUDGET] = NTUPLE_BUDGET_ROWS + 1
+
 
 def _ntuple_shape(shape) -> str:
-    if not isinstance(shape, str) or (shape not in NTUPLE_SHAPES and shape not in NTUPLE_SUMS and shape not in NTUPLE_FEATURE_FORMS):
-        raise ValueError(f"shape must be one of {sorted(NTUPLE_SHAPES) + sorted(NTUPLE_SUMS) + sorted(NTUPLE_FEATURE_FORMS)}, got {shape!r}")
+    known = (NTUPLE_SHAPES, NTUPLE_SUMS, NTUPLE_FEATURE_FORMS, NTUPLE_BUDGET_FORMS)
+    if not isinstance(shape, str) or not any(shape in names for names in known):
+        raise ValueError(f"shape must be one of {sum((sorted(names) for names in known), [])}, got {shape!r}")
     return shape
 
 
@@ -909,11 +931,33 @@ def _ntuple_feature_counts() -> dict:
     return {ntuple_entries_of(name): name for name in NTUPLE_FEATURE_FORMS}
 
 
+def _ntuple_budget_counts() -> dict:
+    """Entry count -> name, for the budget table."""
+    return {ntuple_entries_of(name): name for name in NTUPLE_BUDGET_FORMS}
+
+
 def ntuple_parts_of(shape: str) -> tuple:
     """The shapes whose tables a table of `shape` consists of, in the order they lie in it: the shape itself, or a sum's parts."""
     if _ntuple_shape(shape) in NTUPLE_FEATURE_FORMS:
         return _FEATURE_PARTS[shape]
     return NTUPLE_SUMS.get(shape, (shape,))
+
+
+def spare_bins(rows, L: int, M: int, lines, moves, state=0) -> np.ndarray:
+    """sbin of K boards in row form (int64 [K]), the bin row 9 of a budget table is read at: 0 where the board is dead, else
+    min(spare + 1, 255), dead and spare being move_bound's -- from the board's own lines and moves under the game's L and M.  A finished
+    board has spare 0 and is not dead: bin 1."""
+    bound = move_bound(rows, L, M, lines, moves, state)
+    return np.where(bound["dead"], 0, np.minimum(bound["spare"] + 1, NTUPLE_FEATURE_BINS - 1)).astype(np.int64)
+
+
+def ntuple_budget_bins(rows, L: int, M: int, lines, moves, state) -> np.ndarray:
+    """tpl_ntuple_budget_bins on the host (uint8 [K, 10]): min(phi_j, 255) of board_features, then spare_bins, of K states, running or
+    not."""
+    rows = np.asarray(rows)
+    rows = rows[None] if rows.ndim == 1 else rows
+    phi = np.minimum(board_features(rows), NTUPLE_FEATURE_BINS - 1)
+    return np.concatenate([phi, spare_bins(rows, L, M, lines, moves, state)[:, None]], axis=1).astype(np.uint8)
 
 
 def ntuple_entries_of(shape: str) -> int:
@@ -933,7 +977,9 @@ def ntuple_shape_of(entries: int) -> str:
         return counts[entries]
     if entries in _ntuple_feature_counts():
         return _ntuple_feature_counts()[entries]
-    counts = {**counts, **_ntuple_feature_counts()}
+    if entries in _ntuple_budget_counts():
+        return _ntuple_budget_counts()[entries]
+    counts = {**counts, **_ntuple_feature_counts(), **_ntuple_budget_counts()}
     raise ValueError(f"no table shape has {entries} entries: {({v: k for k, v in counts.items()})}")
 
 
@@ -1008,7 +1054,10 @@ def ntuple_indices(rows, piece, L: int, M: int, lines, moves, shape: str = "2x4"
     part starts, added to every index; `used` likewise.  Both parts' counter columns are used.
     shape="feat", a feature table: [K, 10]; column j < 9 is feature j of board_features(rows) -- holes .. hole_depth -- at index
     (piece * 9 + j) * 256 + min(phi_j, 255); column 9 is the counter entry 18,432 + the same k; ALL ten are used.
-    shape="3x3+feat": [K, 145 + 10] -- the 3 x 3 columns, then the feature columns with 590,848 added to every index."""
+    shape="3x3+feat": [K, 145 + 10] -- the 3 x 3 columns, then the feature columns with 590,848 added to every index.
+    shape="feat+spare", a budget table: [K, 11]; column j < 9 is feature j at index (piece * 10 + j) * 256 + min(phi_j, 255), column 9
+    the spare row at (piece * 10 + 9) * 256 + spare_bins(rows, L, M, lines, moves) -- of the board as a running one --, column 10 the
+    counter entry 20,480 + the same k; ALL eleven are used."""
     if _ntuple_shape(shape) in NTUPLE_SUMS or shape == "3x3+feat":
         index, used, at = [], [], 0
         for part in ntuple_parts_of(shape):
@@ -1017,6 +1066,21 @@ def ntuple_indices(rows, piece, L: int, M: int, lines, moves, shape: str = "2x4"
             used.append(u)
             at += _PART_ENTRIES[part]
         return np.concatenate(index, axis=1), np.concatenate(used, axis=1)
+    if shape == BUDGET:                                       # written from the row form: board_features and the move bound's mirror
+        rows = np.asarray(rows)
+        if rows.ndim == 1:
+            rows = rows[None]
+        phi = board_features(rows)
+        k = rows.shape[0]
+        piece, lines, moves = (np.broadcast_to(np.asarray(v, dtype=np.int64), (k,)) for v in (piece, lines, moves))
+        if k and (piece.min() < 0 or piece.max() >= NTUPLE_PIECES):
+            raise ValueError("piece must be in 0..7")
+        bins = np.concatenate([np.minimum(phi, NTUPLE_FEATURE_BINS - 1), spare_bins(rows, L, M, lines, moves)[:, None]], axis=1)
+        index = np.zeros((k, NTUPLE_BUDGET_ROWS + 1), dtype=np.int64)
+        index[:, :NTUPLE_BUDGET_ROWS] = ((piece[:, None] * NTUPLE_BUDGET_ROWS + np.arange(NTUPLE_BUDGET_ROWS)[None, :]) * NTUPLE_FEATURE_BINS
+                                         + bins)
+        index[:, NTUPLE_BUDGET_ROWS] = NTUPLE_ENTRIES_BUDGET - NTUPLE_COUNTERS + ntuple_counter_index(L, M, lines, moves)
+        return index, np.ones(index.shape, dtype=bool)
     if shape == "feat":
         rows = np.asarray(rows)
         if rows.ndim == 1:
@@ -1064,9 +1128,10 @@ def _ntuple_table(table, staged: bool = True) -> np.ndarray:
     """A table of a known entry count; staged=False: a plain one, for what has no staged form."""
     if (not isinstance(table, np.ndarray) or table.dtype != np.int32 or table.ndim != 1
             or (table.shape[0] not in _ntuple_counts() and table.shape[0] not in _ntuple_feature_counts()
+                and table.shape[0] not in _ntuple_budget_counts()
                 and not (staged and table.shape[0] in _ntuple_staged_counts()))):
         raise ValueError(f"table must be an int32 array of {NTUPLE_ENTRIES} entries (3x3: {NTUPLE_SHAPES['3x3'][2]}, "
-                         f"2x4+3x3: {NTUPLE_ENTRIES_SUM}, feat: {NTUPLE_ENTRIES_FEAT}, 3x3+feat: {NTUPLE_ENTRIES_3X3_FEAT}" + (f"; staged: {list(_ntuple_staged_counts())})" if staged else
+                         f"2x4+3x3: {NTUPLE_ENTRIES_SUM}, feat: {NTUPLE_ENTRIES_FEAT}, 3x3+feat: {NTUPLE_ENTRIES_3X3_FEAT}, feat+spare: {NTUPLE_ENTRIES_BUDGET}" + (f"; staged: {list(_ntuple_staged_counts())})" if staged else
                                                              "); a staged table has no coherent update"))
     return table
 
@@ -1141,16 +1206,17 @@ def ntuple_mirror_permutation(shape: str = "2x4") -> np.ndarray:
     shape="feat" (and the feature part of "3x3+feat") IS a closed form: feature[p][j][q] -> feature[pi(p)][j][q], the counters stay.
     An entry of a feature table is no set of cells that could be laid on a board and reflected; that the image keeps j and q rests
     on the nine features being invariant under reflection, which the tests check on the 8,192 boards of random_moves.npz, and the
-    closed form is held to the definition by the symmetric update, which goes through the reflected rows and not through sigma."""
+    closed form is held to the definition by the symmetric update, which goes through the reflected rows and not through sigma.
+    shape="feat+spare": the same closed form over ten rows a piece -- a row's fill, and with it spare, does not change under reflection."""
     if _ntuple_shape(shape) in NTUPLE_SUMS or shape == "3x3+feat":
         parts, at = [], 0
         for part in ntuple_parts_of(shape):
             parts.append(ntuple_mirror_permutation(part) + at)
             at += _PART_ENTRIES[part]
         return np.concatenate(parts)
-    if shape == "feat":                                       # the features are reflection-invariant: only the piece moves
-        sigma = np.arange(NTUPLE_ENTRIES_FEAT, dtype=np.int64)
-        stride = NTUPLE_FEATURES * NTUPLE_FEATURE_BINS
+    if shape in ("feat", BUDGET):                             # the features, and spare, are reflection-invariant: only the piece moves
+        sigma = np.arange(_PART_ENTRIES[shape], dtype=np.int64)
+        stride = (_PART_COLUMNS[shape] - 1) * NTUPLE_FEATURE_BINS
         for p in range(NTUPLE_PIECES):
             sigma[p * stride:(p + 1) * stride] = PIECE_MIRROR[p] * stride + np.arange(stride)
         return sigma

@@ -71,6 +71,12 @@
 // with it, and with SumOf<Shape3x3, FeatureTable>, are the six ntuple_feature*_kernel.  The update is a kernel of its own,
 // ntuple_feature_trace_kernel: a state's ten adds fall on a table of 19,456 entries that fits LDS whole, so a block sums its states'
 // adds there and flushes what is not zero.  There is no staged and no coherent form.
+//
+// The budget table (the _budget entries).  BudgetTable is FeatureTable with a tenth row read at the spare cells of the move bound
+// (tpl_ntuple.h).  That row needs the board's own lines and moves, which no BoardSum sees, so ntuple_value hands the board and the game to
+// budget_sum: value_lane and ntuple_policy named with it are ntuple_budget_{value,act,search}_kernel.  The policies take the prune flag
+// behind their argument struct; ntuple_policy reads it under `if constexpr` on the geometry, so every other instantiation is the code it
+// was.  The update is ntuple_budget_trace_kernel, the feature update with eleven adds a state on an 84 KB image.
 #include <algorithm>
 #include <cmath>
 
@@ -113,6 +119,7 @@ __global__ __launch_bounds__(kStateBlock) void ntuple_staged3_value_kernel(const
 __global__ __launch_bounds__(kStateBlock) void ntuple_staged_sum_value_kernel(const ValueArgs p) { value_lane<StagedOf<ShapeSum>>(p); }
 __global__ __launch_bounds__(kStateBlock) void ntuple_feature_value_kernel(const ValueArgs p) { value_lane<FeatureTable>(p); }
 __global__ __launch_bounds__(kStateBlock) void ntuple_feature3_value_kernel(const ValueArgs p) { value_lane<Shape3x3Feature>(p); }
+__global__ __launch_bounds__(kStateBlock) void ntuple_budget_value_kernel(const ValueArgs p) { value_lane<BudgetTable>(p); }
 
 // ---- tpl_ntuple_feature_bins: the nine bins of every state, running or not ----
 struct BinsArgs {
@@ -131,6 +138,26 @@ __global__ __launch_bounds__(kStateBlock) void ntuple_feature_bins_kernel(const 
     feature_bins(s.c, q);
 #pragma unroll
     for (int j = 0; j < FeatureTable::kFeatureRows; ++j) p.bins[i * (uint32_t)FeatureTable::kFeatureRows + j] = (uint8_t)q[j];
+}
+
+// ---- tpl_ntuple_budget_bins: the ten bins of every state, running or not ----
+struct BudgetBinsArgs {
+    const uint4* a;              // [n]
+    const uint4* b;
+    uint32_t n;
+    uint32_t L, M;
+    uint8_t* bins;               // [n][10]
+};
+
+__global__ __launch_bounds__(kStateBlock) void ntuple_budget_bins_kernel(const BudgetBinsArgs p) {
+    const uint32_t i = blockIdx.x * kStateBlock + threadIdx.x;
+    if (i >= p.n) return;
+    tpl::Board s;
+    tpl::unpack_board(p.a[i], p.b[i], s);
+    uint32_t q[BudgetTable::kRows];
+    budget_bins(s, p.L, p.M, q);
+#pragma unroll
+    for (int j = 0; j < BudgetTable::kRows; ++j) p.bins[i * (uint32_t)BudgetTable::kRows + j] = (uint8_t)q[j];
 }
 
 // d = (int32) rint(rate * e): the product rounded once, clamped to +-2^24, 0 for a NaN
@@ -274,6 +301,48 @@ __global__ __launch_bounds__(kCombineBlock) void ntuple_feature_trace_kernel(con
     __syncthreads();
 #pragma unroll 1
     for (int t = threadIdx.x; t < FeatureTable::kEntries; t += kCombineBlock) {
+        const uint32_t sum = s_sum[t];
+        if (sum) atomicAdd(p.table + t, sum);
+    }
+}
+
+// ---- the budget table's update: tpl_ntuple_update_trace_budget ----
+// ntuple_feature_trace_kernel on the budget table: the image is 21,504 dwords, 84 KB, so ONE block fits the 160 KB of a CU's LDS, and it
+// is a block of 1,024 threads -- the sixteen waves the two feature blocks of 512 bring to a CU between them.  A state's eleven entries
+// (symmetric: twenty-one) go to the image with LDS atomics; every index is below kEntries by the two clamps of the rule.
+constexpr int kBudgetBlock = 1024;
+constexpr uint32_t kBudgetMaxBlocks = kCombineCUs;            // one block a CU: one resident round of the device, as above an assumption
+static_assert(BudgetTable::kEntries % kBudgetBlock == 0, "the image is zeroed and flushed in whole rounds of a block");
+static_assert(BudgetTable::kEntries * sizeof(uint32_t) <= 160 * 1024, "the image fits the LDS a gfx950 workgroup may declare");
+
+template <bool kSymmetric>
+__global__ __launch_bounds__(kBudgetBlock) void ntuple_budget_trace_kernel(const TraceArgs p) {
+    __shared__ uint32_t s_sum[BudgetTable::kEntries];
+#pragma unroll 1
+    for (int t = threadIdx.x; t < BudgetTable::kEntries; t += kBudgetBlock) s_sum[t] = 0u;
+    __syncthreads();
+    const uint32_t age = blockIdx.y;
+    const float rate = aged_rate(p, age);
+#pragma unroll 1
+    for (uint32_t i = blockIdx.x * kBudgetBlock + threadIdx.x; i < p.n; i += gridDim.x * kBudgetBlock) {
+        uint32_t d;
+        tpl::Board s;
+        if (!feature_trace_state(p, i, age, rate, d, s)) continue;
+        atomicAdd(&s_sum[(uint32_t)BudgetTable::kCounterBase + counter_index(p.L, p.M, s.lines, s.moves)], d);
+        uint32_t q[BudgetTable::kRows];
+        budget_bins(s, p.L, p.M, q);
+        const uint32_t piece = s.window & 7u;
+        const uint32_t base = piece * (uint32_t)BudgetTable::kPieceStride;
+        const uint32_t mirror_base = ((kPieceMirror >> (4u * piece)) & 7u) * (uint32_t)BudgetTable::kPieceStride;
+#pragma unroll
+        for (int j = 0; j < BudgetTable::kRows; ++j) {
+            atomicAdd(&s_sum[budget_entry(base, j, q[j])], d);
+            if constexpr (kSymmetric) atomicAdd(&s_sum[budget_entry(mirror_base, j, q[j])], d);
+        }
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int t = threadIdx.x; t < BudgetTable::kEntries; t += kBudgetBlock) {
         const uint32_t sum = s_sum[t];
         if (sum) atomicAdd(p.table + t, sum);
     }
@@ -537,8 +606,11 @@ constexpr uint32_t kGreedy = 0xFFFFFFFFu;
 // game running is worth beyond its reward is the one thing that differs: V of the board it left at one ply, best_second's W at
 // two.  At two plies V of the afterstate is not on the way to the score, so the one chosen lane of a board sums it afterwards,
 // and only where `value` is asked for.
+// `prune` (the budget geometry alone reads it; tpl_ntuple.h: prune_dead): a move that leaves a running, dead board is scored as one
+// that ends lost at the limit, at either ply, and nothing is searched below it.  `goes_on`, s1 and the afterstate's V stay the true
+// board's: what is written to after_a / after_b and `value` is what the environment will hold.
 template <typename S, int kDepth>
-__device__ __forceinline__ void ntuple_policy(const ActArgs& p, uint8_t* second_out) {
+__device__ __forceinline__ void ntuple_policy(const ActArgs& p, uint8_t* second_out, uint32_t prune = 0u) {
     __shared__ tpl::ShapeWord s_shape[32];
     __shared__ unsigned long long s_best[kBoardsPerBlock];
     __shared__ uint32_t s_pick[kBoardsPerBlock];                        // which distinct placement an exploring board plays
@@ -572,14 +644,24 @@ __device__ __forceinline__ void ntuple_policy(const ActArgs& p, uint8_t* second_
 #pragma unroll
     for (uint32_t q = 0; q < 3u; ++q) rank += q < r ? location_count(cur, q) : 0u;
 
+    uint32_t scored = s1.state;                                         // the state the first move is scored with
+    bool searched = goes_on;                                            // goes_on, unless the prune ends the move
+    if constexpr (kBudgetGeometry<S>) {
+        tpl::Board pruned = s1;
+        prune_dead<S>(pruned, p.L, p.M, prune);
+        scored = pruned.state;
+        searched = running && scored == tpl::ST_RUNNING;
+    }
+
     float v = 0.0f;                                                     // V of a state that does not run
     uint32_t second = kNoSecond;
     if constexpr (kDepth == 2) {
         // W = the best  r2 + gamma V(s2)  (r2 alone where the second move ends the game) of the next piece on s1
-        if (contends && goes_on)
+        if (contends && searched)
             v = best_second(s1, s_shape, p.L, p.M, second, [&](tpl::Board& s2, uint32_t n2) {
 #pragma clang fp contract(off)
                 tpl::next_window(s2, false, 0);                         // the piece after the next: the original window entry 2
+                prune_dead<S>(s2, p.L, p.M, prune);
                 const bool on = s2.state == tpl::ST_RUNNING;
                 float v2 = 0.0f;
                 if (on) v2 = ntuple_value<S>(s2, p.L, p.M, p.table);
@@ -593,9 +675,9 @@ __device__ __forceinline__ void ntuple_policy(const ActArgs& p, uint8_t* second_
     float score;
     {
 #pragma clang fp contract(off)
-        const float reward = move_reward(p.r_line, p.r_win, p.r_lose, n1, s1.state);
+        const float reward = move_reward(p.r_line, p.r_win, p.r_lose, n1, scored);
         const float later = p.gamma * v;
-        score = running ? (goes_on ? reward + later : reward) : 0.0f;
+        score = running ? (searched ? reward + later : reward) : 0.0f;
     }
     const unsigned long long key = ((unsigned long long)ordered_bits(score) << 32) | (uint32_t)(kActions - 1 - a);
     if (contends) atomicMax(&s_best[slot], key);
@@ -660,6 +742,19 @@ __global__ __launch_bounds__(kActBlock) void ntuple_feature3_search_kernel(const
     ntuple_policy<Shape3x3Feature, 2>(p.act, p.second);
 }
 
+struct BudgetActArgs {
+    ActArgs act;
+    uint32_t prune;              // not 0: the dead-board prune
+};
+struct BudgetSearchArgs {
+    SearchArgs search;
+    uint32_t prune;
+};
+__global__ __launch_bounds__(kActBlock) void ntuple_budget_act_kernel(const BudgetActArgs p) { ntuple_policy<BudgetTable, 1>(p.act, nullptr, p.prune); }
+__global__ __launch_bounds__(kActBlock) void ntuple_budget_search_kernel(const BudgetSearchArgs p) {
+    ntuple_policy<BudgetTable, 2>(p.search.act, p.search.second, p.prune);
+}
+
 }  // namespace
 }  // namespace tpl_learn
 
@@ -685,7 +780,9 @@ int launch_value(const char* name, const void* plane_a, const void* plane_b, int
     p.a = (const uint4*)plane_a; p.b = (const uint4*)plane_b; p.n = (uint32_t)n;
     p.L = (uint32_t)L; p.M = (uint32_t)M; p.table = table; p.value = value;
     const dim3 grid((p.n + kStateBlock - 1) / kStateBlock), block(kStateBlock);
-    if (form == Form::kFeature || form == Form::k3x3Feature) {
+    if (form == Form::kBudget) {
+        hipLaunchKernelGGL(ntuple_budget_value_kernel, grid, block, 0, (hipStream_t)stream, p);
+    } else if (form == Form::kFeature || form == Form::k3x3Feature) {
         const auto kernel = form == Form::kFeature ? ntuple_feature_value_kernel : ntuple_feature3_value_kernel;
         hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, p);
     } else if (staged) {
@@ -704,7 +801,7 @@ int launch_value(const char* name, const void* plane_a, const void* plane_b, int
 int launch_ntuple_policy(const char* name, int depth, const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M,
                          float r_line, float r_win, float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed,
                          uint64_t step, uint8_t* action, uint8_t* second, float* score, void* after_a, void* after_b, float* value,
-                         Form form, void* stream, bool staged = false) {
+                         Form form, void* stream, bool staged = false, int32_t prune = 0) {
     if (const int rc = check_planes(name, plane_a, plane_b, n, L, M)) return rc;
     if (const int rc = check_table(name, table)) return rc;
     if (!action) return fail_msg(TPL_ERR_ARG, "%s: null pointer (action is required)", name);
@@ -724,7 +821,16 @@ int launch_ntuple_policy(const char* name, int depth, const void* plane_a, const
     p.action = action; p.score = score; p.after_a = (uint4*)after_a; p.after_b = (uint4*)after_b; p.value = value;
     const dim3 grid((p.n + kBoardsPerBlock - 1) / kBoardsPerBlock), block(kActBlock);
     const bool wide = form == Form::k3x3;
-    if (form == Form::kFeature || form == Form::k3x3Feature) {
+    if (form == Form::kBudget) {                                        // the one form that knows the prune
+        const uint32_t flag = prune != 0 ? 1u : 0u;
+        if (depth == 2) {
+            const BudgetSearchArgs q{{p, second}, flag};
+            hipLaunchKernelGGL(ntuple_budget_search_kernel, grid, block, 0, (hipStream_t)stream, q);
+        } else {
+            const BudgetActArgs q{p, flag};
+            hipLaunchKernelGGL(ntuple_budget_act_kernel, grid, block, 0, (hipStream_t)stream, q);
+        }
+    } else if (form == Form::kFeature || form == Form::k3x3Feature) {
         if (depth == 2) {
             const SearchArgs q{p, second};
             const auto kernel = form == Form::kFeature ? ntuple_feature_search_kernel : ntuple_feature3_search_kernel;
@@ -1021,10 +1127,11 @@ extern "C" int tpl_ntuple_search_feature(const void* plane_a, const void* plane_
                                 epsilon, seed, step, action, second, score, after_a, after_b, value, feature_form_of(form), stream);
 }
 
-extern "C" int tpl_ntuple_update_trace_feature(const void* ring_a, const void* ring_b, int64_t n, int32_t slots, int32_t head,
-                                               int32_t horizon, int32_t L, int32_t M, int32_t* table, const float* error, float rate,
-                                               float decay, int32_t symmetric, void* stream) {
-    const char* const name = "tpl_ntuple_update_trace_feature";
+// what tpl_ntuple_update_trace_feature and tpl_ntuple_update_trace_budget share: the checks and the launch of the kernel that holds
+// the whole table of `form` in LDS
+static int update_whole_table(const char* name, Form form, const void* ring_a, const void* ring_b, int64_t n, int32_t slots, int32_t head,
+                              int32_t horizon, int32_t L, int32_t M, int32_t* table, const float* error, float rate, float decay,
+                              int32_t symmetric, void* stream) {
     if (const int rc = check_planes(name, ring_a, ring_b, n, L, M)) return rc;
     if (const int rc = check_table(name, table)) return rc;
     if (!error) return fail_msg(TPL_ERR_ARG, "%s: null pointer (error is required)", name);
@@ -1034,12 +1141,24 @@ extern "C" int tpl_ntuple_update_trace_feature(const void* ring_a, const void* r
     TraceArgs p{};
     p.a = (const uint4*)ring_a; p.b = (const uint4*)ring_b; p.n = (uint32_t)n; p.slots = (uint32_t)slots; p.head = (uint32_t)head;
     p.L = (uint32_t)L; p.M = (uint32_t)M; p.table = (uint32_t*)table; p.error = error; p.rate = rate; p.decay = decay;
-    // at 2^20 boards a lane walks 2^20 / 512 / 512 = 4 states
-    const uint32_t blocks = std::min<uint32_t>((p.n + kCombineBlock - 1) / kCombineBlock, kCombineMaxBlocks);
-    hipLaunchKernelGGL(symmetric ? ntuple_feature_trace_kernel<true> : ntuple_feature_trace_kernel<false>,
-                       dim3(blocks, (uint32_t)horizon), dim3(kCombineBlock), 0, (hipStream_t)stream, p);
+    if (form == Form::kBudget) {                                        // at 2^20 boards a lane walks 2^20 / 1,024 / 256 = 4 states
+        const uint32_t blocks = std::min<uint32_t>((p.n + kBudgetBlock - 1) / kBudgetBlock, kBudgetMaxBlocks);
+        hipLaunchKernelGGL(symmetric ? ntuple_budget_trace_kernel<true> : ntuple_budget_trace_kernel<false>,
+                           dim3(blocks, (uint32_t)horizon), dim3(kBudgetBlock), 0, (hipStream_t)stream, p);
+    } else {                                                            // at 2^20 boards a lane walks 2^20 / 512 / 512 = 4 states
+        const uint32_t blocks = std::min<uint32_t>((p.n + kCombineBlock - 1) / kCombineBlock, kCombineMaxBlocks);
+        hipLaunchKernelGGL(symmetric ? ntuple_feature_trace_kernel<true> : ntuple_feature_trace_kernel<false>,
+                           dim3(blocks, (uint32_t)horizon), dim3(kCombineBlock), 0, (hipStream_t)stream, p);
+    }
     TPL_LEARN_HIP(hipGetLastError());
     return TPL_OK;
+}
+
+extern "C" int tpl_ntuple_update_trace_feature(const void* ring_a, const void* ring_b, int64_t n, int32_t slots, int32_t head,
+                                               int32_t horizon, int32_t L, int32_t M, int32_t* table, const float* error, float rate,
+                                               float decay, int32_t symmetric, void* stream) {
+    return update_whole_table("tpl_ntuple_update_trace_feature", Form::kFeature, ring_a, ring_b, n, slots, head, horizon, L, M, table,
+                              error, rate, decay, symmetric, stream);
 }
 
 // check_planes without a game: the bins read neither L nor M.  The same refusals in the same words, in its order.
@@ -1062,6 +1181,48 @@ extern "C" int tpl_ntuple_feature_bins(const void* plane_a, const void* plane_b,
     BinsArgs p{};
     p.a = (const uint4*)plane_a; p.b = (const uint4*)plane_b; p.n = (uint32_t)n; p.bins = bins;
     hipLaunchKernelGGL(ntuple_feature_bins_kernel, dim3((p.n + kStateBlock - 1) / kStateBlock), dim3(kStateBlock), 0, (hipStream_t)stream, p);
+    TPL_LEARN_HIP(hipGetLastError());
+    return TPL_OK;
+}
+
+// ---- the budget table: the _budget entries ----
+extern "C" int tpl_ntuple_value_budget(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const int32_t* table,
+                                       float* value, void* stream) {
+    return launch_value("tpl_ntuple_value_budget", plane_a, plane_b, n, L, M, table, value, Form::kBudget, stream);
+}
+
+extern "C" int tpl_ntuple_act_budget(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line,
+                                     float r_win, float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed,
+                                     uint64_t step, uint8_t* action, float* score, void* after_a, void* after_b, float* value,
+                                     int32_t prune, void* stream) {
+    return launch_ntuple_policy("tpl_ntuple_act_budget", 1, plane_a, plane_b, n, L, M, r_line, r_win, r_lose, gamma, table, epsilon,
+                                seed, step, action, nullptr, score, after_a, after_b, value, Form::kBudget, stream, false, prune);
+}
+
+extern "C" int tpl_ntuple_search_budget(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line,
+                                        float r_win, float r_lose, float gamma, const int32_t* table, float epsilon, uint64_t seed,
+                                        uint64_t step, uint8_t* action, uint8_t* second, float* score, void* after_a, void* after_b,
+                                        float* value, int32_t prune, void* stream) {
+    return launch_ntuple_policy("tpl_ntuple_search_budget", 2, plane_a, plane_b, n, L, M, r_line, r_win, r_lose, gamma, table, epsilon,
+                                seed, step, action, second, score, after_a, after_b, value, Form::kBudget, stream, false, prune);
+}
+
+extern "C" int tpl_ntuple_update_trace_budget(const void* ring_a, const void* ring_b, int64_t n, int32_t slots, int32_t head,
+                                              int32_t horizon, int32_t L, int32_t M, int32_t* table, const float* error, float rate,
+                                              float decay, int32_t symmetric, void* stream) {
+    return update_whole_table("tpl_ntuple_update_trace_budget", Form::kBudget, ring_a, ring_b, n, slots, head, horizon, L, M, table,
+                              error, rate, decay, symmetric, stream);
+}
+
+// Not a hot-path entry, as tpl_ntuple_feature_bins is none: a lane's ten byte stores are not coalesced.
+extern "C" int tpl_ntuple_budget_bins(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, uint8_t* bins,
+                                      void* stream) {
+    const char* const name = "tpl_ntuple_budget_bins";
+    if (const int rc = check_planes(name, plane_a, plane_b, n, L, M)) return rc;
+    if (!bins) return fail_msg(TPL_ERR_ARG, "%s: null pointer (bins is required)", name);
+    BudgetBinsArgs p{};
+    p.a = (const uint4*)plane_a; p.b = (const uint4*)plane_b; p.n = (uint32_t)n; p.L = (uint32_t)L; p.M = (uint32_t)M; p.bins = bins;
+    hipLaunchKernelGGL(ntuple_budget_bins_kernel, dim3((p.n + kStateBlock - 1) / kStateBlock), dim3(kStateBlock), 0, (hipStream_t)stream, p);
     TPL_LEARN_HIP(hipGetLastError());
     return TPL_OK;
 }

@@ -1,7 +1,8 @@
 // ntuple_beam.hip -- a beam search over the known piece window with an n-tuple table at the leaves: tpl_ntuple_beam and, with a
 // sum table there (ShapeSum of tpl_ntuple.h: ntuple_beam_sum_kernel), tpl_ntuple_beam_sum; with a staged table of any form
 // (StagedOf: the three ntuple_staged_beam*_kernel), where every leaf reads the block of its own lines and moves left,
-// tpl_ntuple_beam_staged (include/tpl_learn.h states the rule).
+// tpl_ntuple_beam_staged; with a budget table (BudgetTable: ntuple_budget_beam_kernel), and with it the dead-board prune,
+// tpl_ntuple_beam_budget (include/tpl_learn.h states the rule).
 //
 // The frame is placement_beam_kernel's (tpl_beam.h; beam.hip's comment has the reasons): ONE BOARD PER WORKGROUP of 256 threads,
 // both beams and the candidate keys in LDS -- 25 KB in all, so six groups share a CU --, and a ply in three phases: A keys every
@@ -16,6 +17,9 @@
 //   C  makes a kept candidate's move again for its board, but does NOT gather again: the value is the high word of the key, through
 //      the inverse of ordered_bits.  ordered_bits sends -0 to +0's key, so phase A notes a -0 in bit 0 of the key, BELOW the slot --
 //      slots are distinct, so the bit never decides an order -- and phase C gives the node the bits phase A computed.
+// The prune (the budget geometry alone; tpl_ntuple.h: prune_dead) is made where a child is made, behind expand in phases A and C: a
+// child that is left running and dead becomes lost at the limit there, so phase A folds it as a lost node and phase C packs a finished
+// node that no later ply expands.  The root's one-ply afterstate is made by first_move and not by expand: it stays the true board.
 // After the last ply lane 0 holds the choice and, where `after` is asked for, makes the root's move `action` once more: the one-ply
 // afterstate, as ntuple_act_kernel's chosen lane packs it.
 #include <cmath>
@@ -84,7 +88,7 @@ __device__ __forceinline__ float ordered_value(uint32_t key) {
 }
 
 template <typename S>
-__device__ __forceinline__ void ntuple_beam(const NTupleBeamArgs& p) {
+__device__ __forceinline__ void ntuple_beam(const NTupleBeamArgs& p, uint32_t prune = 0u) {
     __shared__ tpl::ShapeWord s_shape[32];
     __shared__ Beam s_beam[2];
     __shared__ unsigned long long s_key[kMaxCandidates];
@@ -130,6 +134,7 @@ __device__ __forceinline__ void ntuple_beam(const NTupleBeamArgs& p) {
                 tpl::Board s;
                 uint32_t b;
                 const uint32_t n = expand(parent, c.q, c.k, s_shape, p.L, p.M, s, b);
+                prune_dead<S>(s, p.L, p.M, prune);
                 const float value = folded_value<S>(p, s, n, parent.cleared[c.q], ply);
                 key = ((unsigned long long)ordered_bits(value) << 32) | low | (__float_as_uint(value) == 0x80000000u ? 1u : 0u);
             }
@@ -159,6 +164,7 @@ __device__ __forceinline__ void ntuple_beam(const NTupleBeamArgs& p) {
                 tpl::Board s;
                 uint32_t b;
                 const uint32_t n = expand(parent, q, c.k, s_shape, p.L, p.M, s, b);
+                prune_dead<S>(s, p.L, p.M, prune);
                 uint4 A, B;
                 tpl::pack_board(s, A, B);
                 child.a[place] = A;
@@ -205,6 +211,11 @@ __global__ __launch_bounds__(kBeamBlock) void ntuple_beam3_kernel(const NTupleBe
 __global__ __launch_bounds__(kBeamBlock) void ntuple_beam_sum_kernel(const NTupleBeamArgs p) { ntuple_beam<ShapeSum>(p); }
 __global__ __launch_bounds__(kBeamBlock) void ntuple_feature_beam_kernel(const NTupleBeamArgs p) { ntuple_beam<FeatureTable>(p); }
 __global__ __launch_bounds__(kBeamBlock) void ntuple_feature3_beam_kernel(const NTupleBeamArgs p) { ntuple_beam<Shape3x3Feature>(p); }
+struct BudgetBeamArgs {
+    NTupleBeamArgs beam;
+    uint32_t prune;              // not 0: the dead-board prune
+};
+__global__ __launch_bounds__(kBeamBlock) void ntuple_budget_beam_kernel(const BudgetBeamArgs p) { ntuple_beam<BudgetTable>(p.beam, p.prune); }
 __global__ __launch_bounds__(kBeamBlock) void ntuple_staged_beam_kernel(const NTupleBeamArgs p) { ntuple_beam<StagedOf<Shape2x4>>(p); }
 __global__ __launch_bounds__(kBeamBlock) void ntuple_staged_beam3_kernel(const NTupleBeamArgs p) { ntuple_beam<StagedOf<Shape3x3>>(p); }
 // four waves a SIMD: as for ntuple_staged_sum_search_kernel (ntuple.hip), the gathers of a leaf go out nine and eight at a time
@@ -222,7 +233,8 @@ namespace {
 // before) share: the checks and the launch
 int launch_ntuple_beam(const char* name, const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line,
                        float r_win, float r_lose, float gamma, const int32_t* table, int32_t depth, int32_t width, uint8_t* action,
-                       uint8_t* plan, float* score, void* after_a, void* after_b, Form form, void* stream, bool staged = false) {
+                       uint8_t* plan, float* score, void* after_a, void* after_b, Form form, void* stream, bool staged = false,
+                       int32_t prune = 0) {
     if (const int rc = check_planes(name, plane_a, plane_b, n, L, M)) return rc;
     if (const int rc = check_table(name, table)) return rc;
     if (!action) return fail_msg(TPL_ERR_ARG, "%s: null pointer (action is required)", name);
@@ -238,7 +250,10 @@ int launch_ntuple_beam(const char* name, const void* plane_a, const void* plane_
     p.L = (uint32_t)L; p.M = (uint32_t)M; p.r_line = r_line; p.r_win = r_win; p.r_lose = r_lose; p.gamma = gamma;
     p.table = table; p.depth = (uint32_t)depth; p.width = (uint32_t)width;
     p.action = action; p.plan = plan; p.score = score; p.after_a = (uint4*)after_a; p.after_b = (uint4*)after_b;
-    if (form == Form::kFeature || form == Form::k3x3Feature) {
+    if (form == Form::kBudget) {
+        const BudgetBeamArgs q{p, prune != 0 ? 1u : 0u};
+        hipLaunchKernelGGL(ntuple_budget_beam_kernel, dim3(p.n), dim3(kBeamBlock), 0, (hipStream_t)stream, q);
+    } else if (form == Form::kFeature || form == Form::k3x3Feature) {
         const auto kernel = form == Form::kFeature ? ntuple_feature_beam_kernel : ntuple_feature3_beam_kernel;
         hipLaunchKernelGGL(kernel, dim3(p.n), dim3(kBeamBlock), 0, (hipStream_t)stream, p);
     } else if (staged) {
@@ -285,4 +300,12 @@ extern "C" int tpl_ntuple_beam_feature(const void* plane_a, const void* plane_b,
     if (const int rc = check_feature_form("tpl_ntuple_beam_feature", form)) return rc;
     return launch_ntuple_beam("tpl_ntuple_beam_feature", plane_a, plane_b, n, L, M, r_line, r_win, r_lose, gamma, table, depth, width,
                               action, plan, score, after_a, after_b, feature_form_of(form), stream);
+}
+
+extern "C" int tpl_ntuple_beam_budget(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, float r_line,
+                                      float r_win, float r_lose, float gamma, const int32_t* table, int32_t depth, int32_t width,
+                                      uint8_t* action, uint8_t* plan, float* score, void* after_a, void* after_b, int32_t prune,
+                                      void* stream) {
+    return launch_ntuple_beam("tpl_ntuple_beam_budget", plane_a, plane_b, n, L, M, r_line, r_win, r_lose, gamma, table, depth, width,
+                              action, plan, score, after_a, after_b, Form::kBudget, stream, false, prune);
 }

@@ -1,5 +1,6 @@
 // tpl_ntuple.h -- what the units that read an n-tuple table share (ntuple.hip, ntuple_beam.hip; include/tpl_learn.h states the
-// rule): the geometry of the two table shapes, of their sum, of a staged table of any of the three and of a feature table, the counter index, the
+// rule): the geometry of the two table shapes, of their sum, of a staged table of any of the three, of a feature table and of a budget
+// table, the counter index, the
 // 32-bit addressing of an entry, the sum and the value of a running board, and the shape, form and table checks of the entry points.
 #pragma once
 
@@ -226,17 +227,82 @@ using Shape3x3Feature = SumOf<Shape3x3, FeatureTable, TPL_NTUPLE_ENTRIES_3X3>;
 static_assert(Shape3x3Feature::kEntries == TPL_NTUPLE_ENTRIES_3X3_FEAT && (Shape3x3Feature::kSecondAt * sizeof(int32_t)) % 16 == 0,
               "the 3 x 3 + feature table's layout of include/tpl_learn.h: the feature part is a 16-byte aligned table");
 
+// The geometry of a BUDGET TABLE (include/tpl_learn.h, "The budget table"): a feature table with a tenth row per falling piece, read
+// at the spare cells of the move bound.  That row is indexed by the board's own lines and moves under the game's L and M -- not by the
+// clamped counter index k --, so this geometry is not reached through BoardSum, which sees k alone: ntuple_value below hands the
+// board and the game to budget_sum, and every other geometry goes the way it went.
+struct BudgetTable {
+    static constexpr int kFeatureRows = TPL_NTUPLE_FEATURES, kBins = TPL_NTUPLE_FEATURE_BINS;
+    static constexpr int kRows = TPL_NTUPLE_BUDGET_ROWS;      // the nine feature rows, then the spare row
+    static constexpr int kSpareRow = kFeatureRows;
+    static constexpr int kPieceStride = kRows * kBins;        // 2,560
+    static constexpr int kCounterBase = 8 * kPieceStride;     // 20,480
+    static constexpr int kEntries = kCounterBase + kCounters;
+};
+static_assert(BudgetTable::kEntries == TPL_NTUPLE_ENTRIES_BUDGET && BudgetTable::kRows == BudgetTable::kFeatureRows + 1,
+              "the budget table's layout of include/tpl_learn.h");
+
+// sbin of a board: 0 where it is dead, else min(spare + 1, 255) of move_bound as it stands (a finished board has spare 0: bin 1)
+__device__ __forceinline__ uint32_t spare_bin(const tpl::Board& s, uint32_t L, uint32_t M) {
+    const MoveBound bound = move_bound(s, L, M);
+    return bound.spare < 0 ? 0u : (uint32_t)min(bound.spare + 1, BudgetTable::kBins - 1);
+}
+
+// the ten bins of a board: feature_bins, then sbin
+__device__ __forceinline__ void budget_bins(const tpl::Board& s, uint32_t L, uint32_t M, uint32_t (&q)[BudgetTable::kRows]) {
+    uint32_t f[FeatureTable::kFeatureRows];
+    feature_bins(s.c, f);
+#pragma unroll
+    for (int j = 0; j < BudgetTable::kFeatureRows; ++j) q[j] = f[j];
+    q[BudgetTable::kSpareRow] = spare_bin(s, L, M);
+}
+
+// the index of bin q of row j among the rows of the piece that start at `base`
+__device__ __forceinline__ uint32_t budget_entry(uint32_t base, int j, uint32_t q) { return base + (uint32_t)(j * BudgetTable::kBins) + q; }
+
+// The integer value of a running board under a budget table: the ten gathers, all in flight at once, and the counter
+__device__ __forceinline__ long long budget_sum(const tpl::Board& s, uint32_t L, uint32_t M, const int32_t* table) {
+    uint32_t q[BudgetTable::kRows];
+    budget_bins(s, L, M, q);
+    const uint32_t base = (s.window & 7u) * (uint32_t)BudgetTable::kPieceStride;
+    int32_t v[BudgetTable::kRows];
+#pragma unroll
+    for (int j = 0; j < BudgetTable::kRows; ++j) v[j] = *entry(table, budget_entry(base, j, q[j]));
+    long long sum = *entry(table, (uint32_t)BudgetTable::kCounterBase + counter_index(L, M, s.lines, s.moves));
+#pragma unroll
+    for (int j = 0; j < BudgetTable::kRows; ++j) sum += v[j];
+    return sum;
+}
+
+// whether a geometry's policies know the dead-board prune: the budget table's alone
+template <typename S> struct KnowsBudget { static constexpr bool value = false; };
+template <> struct KnowsBudget<BudgetTable> { static constexpr bool value = true; };
+template <typename S> constexpr bool kBudgetGeometry = KnowsBudget<S>::value;
+
+// The prune (include/tpl_learn.h): with `prune` set, a RUNNING board that is dead becomes lost at the limit, and the caller scores
+// and expands it as any board in that state.  Nothing, and no code, under any other geometry.
+template <typename S>
+__device__ __forceinline__ void prune_dead(tpl::Board& s, uint32_t L, uint32_t M, uint32_t prune) {
+    if constexpr (kBudgetGeometry<S>) {
+        const bool dead = prune != 0u && s.state == tpl::ST_RUNNING && move_bound(s, L, M).spare < 0;
+        s.state = dead ? (uint32_t)tpl::ST_LOST_LIMIT : s.state;
+    }
+}
+
 // V of a state that runs: one rounding from the 64-bit sum to float32, then an exact scaling by 2^-16
 template <typename S>
 __device__ __forceinline__ float ntuple_value(const tpl::Board& s, uint32_t L, uint32_t M, const int32_t* table) {
-    const long long sum = BoardSum<S>::of(s.c, s.window & 7u, counter_index(L, M, s.lines, s.moves), table);
+    long long sum;
+    if constexpr (kBudgetGeometry<S>) sum = budget_sum(s, L, M, table);
+    else sum = BoardSum<S>::of(s.c, s.window & 7u, counter_index(L, M, s.lines, s.moves), table);
     return (float)sum * 0x1p-16f;
 }
 
 // Which kernels an entry launches: the two shapes of tpl_ntuple_shape, and their sum, which is no `shape` of the C interface.  The
 // _staged entries take all three as their `form` (tpl_ntuple_form has the enumerators' values).
 // kFeature and k3x3Feature are the two tpl_ntuple_feature_form of the _feature entries, which no other entry takes.
-enum class Form { k2x4, k3x3, kSum, kFeature, k3x3Feature };
+// kBudget is the budget table of the _budget entries, which take no form: there is one.
+enum class Form { k2x4, k3x3, kSum, kFeature, k3x3Feature, kBudget };
 inline Form feature_form_of(int32_t form) { return form == TPL_NTUPLE_FEATURE_FORM_3X3 ? Form::k3x3Feature : Form::kFeature; }   // after check_feature_form
 
 // a feature form the library does not know is refused first, before any pointer is looked at

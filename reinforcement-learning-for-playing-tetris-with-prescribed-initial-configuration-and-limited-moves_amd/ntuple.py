@@ -4,7 +4,7 @@ learning on the device (the rule: include/tpl_learn.h; the kernels: csrc/learn/n
     ntuple_table(device, shape="2x4")
                                   a zeroed table: int32 [314,368], in units of 2^-16; shape="3x3": int32 [590,848]
                                   shape="2x4+3x3": a SUM TABLE, int32 [905,216] -- a 2x4 table, then a 3x3 table, read together
-    ntuple_shape(table)           "2x4", "3x3" or "2x4+3x3", from the table's entry count
+    ntuple_shape(table)           "2x4", "3x3", "2x4+3x3", "feat", "3x3+feat" or "feat+spare", from the table's entry count
     ntuple_parts(table)           the per-shape views of a table or a coherence buffer (one for a plain table, two for a sum):
                                   they share its storage, and each is a valid table of its shape
     ntuple_value(source, table)   V of every resident board of an environment, or of plane pairs
@@ -43,6 +43,12 @@ learning on the device (the rule: include/tpl_learn.h; the kernels: csrc/learn/n
     ntuple_table(device, "feat"), ntuple_table(device, "3x3+feat")
                                   a zeroed FEATURE TABLE, int32 [19,456], and a 3x3 table with a feature table behind it, int32 [610,304]
     ntuple_feature_bins(source)   uint8 [K, 9]: the nine bins a feature table is read at
+    ntuple_table(device, "feat+spare")
+                                  a zeroed BUDGET TABLE, int32 [21,504]: a feature table with a tenth row, read at the spare cells
+    ntuple_budget(feat_table)     a budget table whose nine feature rows and counters are a "feat" table's and whose row 9 is zero
+    ntuple_budget_bins(source)    uint8 [K, 10]: the ten bins a budget table is read at
+    NTuplePolicy(..., bound=True), NTupleBeamPolicy(..., bound=True), NTupleLearner(..., shape="feat+spare", bound=True)
+                                  the dead-board prune, for a budget table only
 
 The value is a sum of table entries, one per 2 x 4 window of the board that is not empty, chosen by the falling piece, plus one
 per (lines left, moves left); the update adds rint(rate * error) to the same entries.  Everything is integer, so two trainings
@@ -70,6 +76,15 @@ same TD rule -- and the counters; "3x3+feat" sums it with a 3x3 table as "2x4+3x
 change under reflection, so the mirror image moves only the piece.  Value, both policies, the beam, the symmetry test and the learner
 with traces and symmetry take either form by name or by entry count.  There is no staged and no coherent form, and both are refused:
 each would be eight more kernels, and neither option raised a win rate in the record.
+
+The budget table ("feat+spare": NTUPLE_BUDGET_FORMS).  A feature table sees the move budget only through one additive counter entry,
+clamped at 15 lines and 63 moves.  A budget table adds a tenth row per falling piece, read at sbin = 0 for a dead board and else
+min(spare + 1, 255), spare = 4 (M - moves) - cells being the move bound's (T.move_bound): what a board can still waste, from its own
+lines and moves.  The row is learned by the same TD rule where HeuristicPolicy's spare_weight is set by hand.  ntuple_budget(table)
+copies a trained "feat" table into one with row 9 zero, which plays as the source does, byte for byte.  bound=True on the policies is the
+dead-board prune: a move that leaves a running board the bound proves lost is scored as a loss at the limit -- no gamma * V, nothing
+searched below it --, while `after` and `value` stay the true afterstate's.  Only a budget table takes it; like "feat" it has no staged,
+coherent or summed form.
 """
 from __future__ import annotations
 
@@ -79,12 +94,14 @@ from typing import Optional
 import torch
 
 from . import _learn_lib
-from ._learn_lib import (BEAM_MAX_WIDTH, NTUPLE_BEAM_MAX_DEPTH, NTUPLE_COUNTERS, NTUPLE_ENTRIES, NTUPLE_ENTRIES_SUM, NTUPLE_FEATURE_FORMS,
+from ._learn_lib import (BEAM_MAX_WIDTH, NTUPLE_BEAM_MAX_DEPTH, NTUPLE_BUDGET_FORMS, NTUPLE_BUDGET_ROWS, NTUPLE_COUNTERS, NTUPLE_ENTRIES,
+                         NTUPLE_ENTRIES_SUM, NTUPLE_FEATURE_FORMS,
                          NTUPLE_FEATURES, NTUPLE_FORM_IDS, NTUPLE_SHAPE_IDS, NTUPLE_SHAPES, NTUPLE_STAGES, NTUPLE_SUMS, NTUPLE_TRACE_MAX, check)
 from .lookahead import _MAX_BOARDS, _boards, _ptr, _state_ptrs
 
 __all__ = ["NTUPLE_ENTRIES", "NTUPLE_ENTRIES_SUM", "NTUPLE_SHAPES", "NTUPLE_SUMS", "ntuple_shape", "ntuple_parts", "ntuple_table", "ntuple_value", "ntuple_is_symmetric", "ntuple_coherence", "ntuple_step_sizes",
-           "NTuplePolicy", "NTupleBeamPolicy", "NTupleLearner", "NTUPLE_FEATURE_FORMS", "ntuple_feature_bins", "NTUPLE_STAGES", "ntuple_stage_map", "ntuple_staged", "ntuple_stages",
+           "NTuplePolicy", "NTupleBeamPolicy", "NTupleLearner", "NTUPLE_FEATURE_FORMS", "ntuple_feature_bins", "NTUPLE_BUDGET_FORMS",
+           "ntuple_budget", "ntuple_budget_bins", "NTUPLE_STAGES", "ntuple_stage_map", "ntuple_staged", "ntuple_stages",
            "ntuple_map", "ntuple_is_staged"]
 
 _STATE_WON = 1                                                 # bits 28..29 of B.y: 0 running, 1 won, 2 and 3 lost
@@ -97,21 +114,29 @@ def _counts() -> dict:
 
 
 def _table_counts() -> dict:
-    """Entry count -> name, for every plain table: the shapes, their sums and the feature forms."""
-    return {**_learn_lib._ntuple_counts(), **_learn_lib._ntuple_feature_counts()}
+    """Entry count -> name, for every plain table: the shapes, their sums, the feature forms and the budget table."""
+    return {**_learn_lib._ntuple_counts(), **_learn_lib._ntuple_feature_counts(), **_learn_lib._ntuple_budget_counts()}
 
 
 _NO_FEATURE_FORM = ("a feature table ({shape!r}) has no {what}: each would be eight more kernels, and neither staging nor temporal "
                     "coherence raised a win rate in the record (include/tpl_learn.h, \"Feature tuples\")")
 
 
+_NO_BUDGET_FORM = ("a budget table ({shape!r}) has no {what}: like a feature table it has one plain form "
+                   "(include/tpl_learn.h, \"The budget table\")")
+_BOUND_NEEDS_BUDGET = ('bound=True is the dead-board prune of a budget table: the table must be of the form "feat+spare" '
+                       "(ntuple_table(device, \"feat+spare\"), ntuple_budget), not {shape!r}")
+
+
 def _entries(shape, windows_only: str = "") -> int:
-    """The entries of a table of `shape`; windows_only: what a feature form is refused for, where it is."""
-    names = sorted(NTUPLE_SHAPES) + sorted(NTUPLE_SUMS) + sorted(NTUPLE_FEATURE_FORMS)
+    """The entries of a table of `shape`; windows_only: what a feature form or the budget table is refused for, where it is."""
+    names = sorted(NTUPLE_SHAPES) + sorted(NTUPLE_SUMS) + sorted(NTUPLE_FEATURE_FORMS) + sorted(NTUPLE_BUDGET_FORMS)
     if not isinstance(shape, str) or shape not in names:
         raise ValueError(f"shape must be one of {names}, got {shape!r}")
     if windows_only and shape in NTUPLE_FEATURE_FORMS:
         raise ValueError(_NO_FEATURE_FORM.format(shape=shape, what=windows_only))
+    if windows_only and shape in NTUPLE_BUDGET_FORMS:
+        raise ValueError(_NO_BUDGET_FORM.format(shape=shape, what=windows_only))
     return _learn_lib.ntuple_entries_of(shape)
 
 
@@ -193,12 +218,12 @@ def ntuple_coherence(device="cuda:0", shape: str = "2x4") -> torch.Tensor:
 
 
 def ntuple_shape(table) -> str:
-    """"2x4", "3x3" or "2x4+3x3": the shape of a table (or, by its first dimension, of a coherence buffer), from its entry count; a
-    tensor of any other size is refused."""
+    """"2x4", "3x3" or "2x4+3x3": the shape of a table (or, by its first dimension, of a coherence buffer), from its entry count;
+    "feat", "3x3+feat" or "feat+spare" for a table of a feature form or a budget table; a tensor of any other size is refused."""
     if isinstance(table, torch.Tensor) and table.dim() >= 1 and table.shape[0] in _counts():
         return _counts()[table.shape[0]]
     if isinstance(table, torch.Tensor) and table.dim() == 1 and table.shape[0] in _table_counts():
-        return _table_counts()[table.shape[0]]                 # a feature form: "feat" or "3x3+feat"
+        return _table_counts()[table.shape[0]]                 # a feature form, "feat" or "3x3+feat", or the budget table
     if isinstance(table, torch.Tensor) and table.dim() == 1 and table.shape[0] in _staged_counts():
         return _staged_counts()[table.shape[0]]                # a staged table: the form of its blocks
     sizes = ", ".join(f"{k} ({v})" for k, v in _table_counts().items())
@@ -257,10 +282,22 @@ def _table(table, device) -> torch.Tensor:
     return table
 
 
-def _shaped(lib, entry: str, shape: str, staged: bool = False):
+def _bound(bound, shape: str, staged: bool = False) -> bool:
+    """The prune flag of a policy on a table of `shape`: a bool, and True for a budget table alone."""
+    if not isinstance(bound, bool):
+        raise ValueError(f"bound must be True or False, got {bound!r}")
+    if bound and (staged or shape not in NTUPLE_BUDGET_FORMS):
+        raise ValueError(_BOUND_NEEDS_BUDGET.format(shape=("staged " if staged else "") + shape))
+    return bound
+
+
+def _shaped(lib, entry: str, shape: str, staged: bool = False, prune=None):
     """How the library reads a table of `shape` through `entry` ("tpl_ntuple_value", ...): (function, trailing arguments before
     `stream`) -- the _shaped twin with the C shape id, or for a sum of shapes the _sum twin, which takes none; for a staged table of
-    any form the _staged twin with the C form id."""
+    any form the _staged twin with the C form id.  A budget table: the _budget twin, which takes no form, and for a policy
+    (prune given) the prune flag where the others take their id."""
+    if shape in NTUPLE_BUDGET_FORMS and not staged:
+        return getattr(lib, entry + "_budget"), (() if prune is None else (int(prune),))
     if staged:
         return getattr(lib, entry + "_staged"), (NTUPLE_FORM_IDS[shape],)
     if shape in NTUPLE_FEATURE_FORMS:
@@ -381,6 +418,48 @@ def ntuple_feature_bins(source, out: Optional[torch.Tensor] = None) -> torch.Ten
     return out
 
 
+@torch.no_grad()
+def ntuple_budget_bins(source, L: Optional[int] = None, M: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 [K, 10]: the ten bins a budget table is read at -- ntuple_feature_bins' nine, then sbin = 0 for a dead board and else
+    min(spare + 1, 255) of the move bound -- of K states, running or not (tpl_ntuple_budget_bins; a finished board has spare 0: bin 1).
+    `source` is an environment (its resident boards, under its L and M) or a pair (states_a, states_b) of int32 [K, 4] planes on one
+    GPU, for which the game's L and M must be given.  No host sync, and no allocation when `out` is given."""
+    if hasattr(source, "num_envs"):
+        if L is not None or M is not None:
+            raise ValueError("an environment brings its own L and M")
+        k, device, L, M = _boards(source, "ntuple_budget_bins"), source.device, source.L, source.M
+        a, b = _state_ptrs(source)
+    else:
+        k, a, b = _planes(source, None, "source")
+        device = a.device
+        if L is None or M is None:
+            raise ValueError("planes need the game's L and M")
+        if not 1 <= k <= _MAX_BOARDS:
+            raise ValueError(f"ntuple_budget_bins takes 1 .. {_MAX_BOARDS} states")
+    if out is None:
+        out = torch.empty((k, NTUPLE_BUDGET_ROWS), dtype=torch.uint8, device=device)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (k, NTUPLE_BUDGET_ROWS) or out.device != device
+          or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous uint8 tensor of shape ({k}, {NTUPLE_BUDGET_ROWS}) on {device}")
+    stream = torch._C._cuda_getCurrentRawStream(device.index)
+    check(_learn_lib.lib().tpl_ntuple_budget_bins(_ptr(a), _ptr(b), k, int(L), int(M), out.data_ptr(), stream))
+    return out
+
+
+@torch.no_grad()
+def ntuple_budget(table: torch.Tensor) -> torch.Tensor:
+    """Weight promotion: a new budget table ("feat+spare") on `table`'s device whose nine feature rows and counters are those of the
+    "feat" table `table` and whose row 9 is zero.  Without the prune it values, and plays, exactly as `table` does until it is trained."""
+    if not isinstance(table, torch.Tensor) or table.dim() != 1 or table.dtype != torch.int32 or ntuple_shape(table) != "feat":
+        raise ValueError('ntuple_budget promotes a "feat" table: an int32 tensor of 19,456 entries (ntuple_table(device, "feat"))')
+    out = ntuple_table(table.device, "feat+spare")
+    bins = _learn_lib.NTUPLE_FEATURE_BINS
+    rows = out[:-NTUPLE_COUNTERS].view(_learn_lib.NTUPLE_PIECES, NTUPLE_BUDGET_ROWS, bins)
+    rows[:, :NTUPLE_FEATURES].copy_(table[:-NTUPLE_COUNTERS].view(_learn_lib.NTUPLE_PIECES, NTUPLE_FEATURES, bins))
+    out[-NTUPLE_COUNTERS:].copy_(table[-NTUPLE_COUNTERS:])
+    return out
+
+
 _sigma = {}                                                    # the mirror permutation, once per device and shape
 
 
@@ -409,14 +488,21 @@ class NTuplePolicy:
 
     depth=2 (tpl_ntuple_search) looks at the known next piece too: where a placement leaves the game running, V(afterstate)
     gives way to the best  r_b + gamma * V  (r_b alone where b ends the game) over the distinct placements b of the next piece
-    on that afterstate.  The draw, and what `after` and `value` mean, do not change with the depth."""
+    on that afterstate.  The draw, and what `after` and `value` mean, do not change with the depth.
 
-    def __init__(self, env, table: torch.Tensor, gamma: float = 0.99, epsilon: float = 0.0, seed: int = 0, depth: int = 1):
+    bound=True (a "feat+spare" table only; anything else is refused): the dead-board prune.  A placement, at either ply, that leaves
+    a running board the move bound proves lost is scored as one that ends lost at the limit: its reward with r_lose, no gamma * V,
+    nothing searched below it.  Only scores and the arg-max change: `after` and `value` are still the true afterstate and its table
+    value, and exploration stays uniform over the distinct placements."""
+
+    def __init__(self, env, table: torch.Tensor, gamma: float = 0.99, epsilon: float = 0.0, seed: int = 0, depth: int = 1,
+                 bound: bool = False):
         _boards(env, "NTuplePolicy")
         self.env, self.table, self.depth = env, _table(table, env.device), _depth(depth)
         self.gamma, self.epsilon, self.seed = _finite("gamma", gamma), _unit("epsilon", epsilon), _count("seed", seed)
         self.shape = ntuple_shape(self.table)                  # "2x4", "3x3" or "2x4+3x3": the table's, which picks the kernels
         self.staged = ntuple_is_staged(self.table)             # with the shape: the _staged entries
+        self.bound = _bound(bound, self.shape, self.staged)    # the dead-board prune: a budget table's alone
         self.step = 0                                          # the `step` of the next act() that is not given one
         self._planes = None
 
@@ -457,7 +543,7 @@ class NTuplePolicy:
         lib = _learn_lib.lib()
         head = (self._planes[0], self._planes[1], env.num_envs, env.L, env.M, *env.reward_params, self.gamma, self.table.data_ptr(),
                 self.epsilon, self.seed % (1 << 64), step % (1 << 64), out.data_ptr())
-        entry, shape = _shaped(lib, "tpl_ntuple_search" if self.depth == 2 else "tpl_ntuple_act", self.shape, self.staged)
+        entry, shape = _shaped(lib, "tpl_ntuple_search" if self.depth == 2 else "tpl_ntuple_act", self.shape, self.staged, self.bound)
         tail = (_ptr(score), _ptr(after_a), _ptr(after_b), _ptr(value), *shape, stream)
         check(entry(*head, _ptr(second), *tail) if self.depth == 2 else entry(*head, *tail))
         return out
@@ -471,14 +557,16 @@ class NTupleBeamPolicy:
     (env.reward_params; float32, never fused) and keeps the `width` best in candidate order; the action is the first placement of
     the best leaf.  Greedy: there is no exploration.  depth 1 is NTuplePolicy at epsilon 0; depth 2 with width >= 34 is
     NTuplePolicy(depth=2).  One launch that leaves the environment as it is; `table` is read at every act(), and its shape is the
-    table's."""
+    table's.  bound=True (a "feat+spare" table only): the dead-board prune at every ply -- a child that is left running and dead is a
+    lost node, valued by its rewards alone and not expanded; `after` stays the true afterstate."""
 
-    def __init__(self, env, table: torch.Tensor, depth: int, width: int, gamma: float = 0.99):
+    def __init__(self, env, table: torch.Tensor, depth: int, width: int, gamma: float = 0.99, bound: bool = False):
         _boards(env, "NTupleBeamPolicy")
         self.env, self.table = env, _table(table, env.device)
         self.depth, self.width = _beam_shape(depth, width)
         self.gamma = _finite("gamma", gamma)
         self.shape, self.staged = ntuple_shape(self.table), ntuple_is_staged(self.table)
+        self.bound = _bound(bound, self.shape, self.staged)    # the dead-board prune: a budget table's alone
         self._planes = None
 
     @torch.no_grad()
@@ -508,6 +596,8 @@ class NTupleBeamPolicy:
         lib = _learn_lib.lib()
         if self.staged:
             entry, shape = lib.tpl_ntuple_beam_staged, (NTUPLE_FORM_IDS[self.shape],)
+        elif self.shape in NTUPLE_BUDGET_FORMS:
+            entry, shape = lib.tpl_ntuple_beam_budget, (int(self.bound),)
         elif self.shape in NTUPLE_FEATURE_FORMS:
             entry, shape = lib.tpl_ntuple_beam_feature, (NTUPLE_FEATURE_FORMS[self.shape],)
         else:
@@ -576,11 +666,17 @@ class NTupleLearner:
     first part with the same errors.  Traces, symmetry and start= work as above; stage_map= and coherent=True are refused.  One `rate`
     serves both parts of a sum.  A state adds to 10 entries of a feature table where it adds to about 107 of a 3x3 one, so the step of
     V per unit of `rate` is about a tenth: alone, `rate` is EXPECTED to want roughly ten times a window table's.  That is arithmetic
-    on the step, not a measurement -- profiles/learner/README.md has what the sweep found."""
+    on the step, not a measurement -- profiles/learner/README.md has what the sweep found.
+
+    shape="feat+spare": a budget table (the module's docstring).  Steps 1 and 2 read it through the _budget entries, step 3 is
+    tpl_ntuple_update_trace_budget: eleven adds a state.  Traces, symmetry and start= (a budget table: ntuple_budget promotes a "feat"
+    one) work as above; stage_map= and coherent=True are refused.  bound=True (this form only) is the dead-board prune of the
+    BEHAVIOUR policy and of the greedy target: the moves the learner plays and the scores it learns from skip what the move bound
+    proves lost.  evaluate(bound=) plays the table with or without it, whatever it was trained with."""
 
     def __init__(self, env, gamma: float = 0.99, rate: float = 8.0, epsilon: float = 0.1, seed: int = 0, depth: int = 1,
                  lam: float = 0.0, horizon: int = 1, symmetric: bool = False, coherent: bool = False, shape: str = "2x4",
-                 stage_map: Optional[torch.Tensor] = None, start: Optional[torch.Tensor] = None):
+                 stage_map: Optional[torch.Tensor] = None, start: Optional[torch.Tensor] = None, bound: bool = False):
         n = _boards(env, "NTupleLearner")
         if not env.auto_reset:
             raise ValueError("NTupleLearner needs an auto-reset environment")
@@ -591,7 +687,12 @@ class NTupleLearner:
                 raise ValueError(_NO_FEATURE_FORM.format(shape=shape, what="staged form (stage_map=)"))
             if coherent is True:
                 raise ValueError(_NO_FEATURE_FORM.format(shape=shape, what="coherent update (coherent=True)"))
-        self.shape = shape
+        if shape in NTUPLE_BUDGET_FORMS:
+            if stage_map is not None:
+                raise ValueError(_NO_BUDGET_FORM.format(shape=shape, what="staged form (stage_map=)"))
+            if coherent is True:
+                raise ValueError(_NO_BUDGET_FORM.format(shape=shape, what="coherent update (coherent=True)"))
+        self.shape, self.bound = shape, _bound(bound, shape, stage_map is not None)
         _unit("epsilon", epsilon), _finite("gamma", gamma), _count("seed", seed)
         self.lam, self.horizon = _unit("lam", lam), _horizon(horizon)
         if not isinstance(symmetric, bool):
@@ -621,8 +722,8 @@ class NTupleLearner:
         if stage_map is not None:
             ntuple_map(self.table).copy_(_stage_map(stage_map, d))
         self.coherence = ntuple_coherence(d, shape) if coherent else None
-        self.policy = NTuplePolicy(env, self.table, gamma, epsilon, seed, self.depth)
-        self.greedy = NTuplePolicy(env, self.table, gamma, 0.0, seed, self.depth)
+        self.policy = NTuplePolicy(env, self.table, gamma, epsilon, seed, self.depth, bound=self.bound)
+        self.greedy = NTuplePolicy(env, self.table, gamma, 0.0, seed, self.depth, bound=self.bound)
         self.steps = 0                                         # train() steps so far: the `step` of the exploration draw
         self._action = torch.empty(n, dtype=torch.uint8, device=d)
         self._done = torch.empty(n, dtype=torch.uint8, device=d)
@@ -684,7 +785,11 @@ class NTupleLearner:
             buffers = ntuple_parts(self.coherence) if self.coherent else (None,) * len(names)
             for name, part, buffer in zip(names, ntuple_parts(self.table), buffers):
                 t = part.data_ptr()
-                if name == "feat":
+                if name in NTUPLE_BUDGET_FORMS:
+                    if self.coherent:
+                        raise ValueError(_NO_BUDGET_FORM.format(shape=form_name, what="coherent update"))
+                    updates.append(lambda head, t=t: lib.tpl_ntuple_update_trace_budget(*ring(t, head), error, *how, stream))
+                elif name == "feat":
                     updates.append(lambda head, t=t: lib.tpl_ntuple_update_trace_feature(*ring(t, head), error, *how, stream))
                 elif self.coherent:
                     updates.append(lambda head, t=t, c=buffer.data_ptr(), s=NTUPLE_SHAPE_IDS[name]:
@@ -705,24 +810,26 @@ class NTupleLearner:
         return self.steps
 
     @torch.no_grad()
-    def evaluate(self, steps: int, depth: Optional[int] = None, width: Optional[int] = None) -> dict:
+    def evaluate(self, steps: int, depth: Optional[int] = None, width: Optional[int] = None, bound: Optional[bool] = None) -> dict:
         """Play `steps` greedy steps from a full reset and count: episodes (the steps' done flags), wins (the afterstates of the
         moves played whose state is "won": every reward parameter counts the same wins) and win_rate = wins / max(episodes, 1).
         depth: how deep the greedy policy searches -- None: the learner's own; 1 or 2 plays the table as it stands at that depth.
         width: None, or a beam width -- then NTupleBeamPolicy(depth, width) plays the table, `depth` must be given and may be
-        1 .. 11.  The tallies stay on the device, with one sync at the end.  Training goes on from the boards this leaves, with
+        1 .. 11.  bound: None -- the learner's own -- or whether the policy that plays prunes dead boards (a budget table only).
+        The tallies stay on the device, with one sync at the end.  Training goes on from the boards this leaves, with
         nothing kept."""
         steps = _count("steps", steps, 1)
         env, d = self.env, self.env.device
         greedy = self.greedy
+        bound = greedy.bound if bound is None else _bound(bound, greedy.shape, greedy.staged)
         if width is not None:
             if depth is None:
                 raise ValueError("evaluate(width=...) plays a beam: depth must be given with it (1 .. 11)")
-            beam = NTupleBeamPolicy(env, self.table, *_beam_shape(depth, width), gamma=greedy.gamma)
+            beam = NTupleBeamPolicy(env, self.table, *_beam_shape(depth, width), gamma=greedy.gamma, bound=bound)
             act = lambda: beam.act(out=self._action, after=self._next)
         else:
-            if depth is not None and _depth(depth) != self.depth:
-                greedy = NTuplePolicy(env, self.table, greedy.gamma, 0.0, greedy.seed, depth)
+            if (depth is not None and _depth(depth) != self.depth) or bound != greedy.bound:
+                greedy = NTuplePolicy(env, self.table, greedy.gamma, 0.0, greedy.seed, self.depth if depth is None else depth, bound=bound)
             act = lambda: greedy.act(out=self._action, after=self._next, step=0)
         episodes = torch.zeros(env.num_envs, dtype=torch.int32, device=d)
         wins = torch.zeros(env.num_envs, dtype=torch.int32, device=d)

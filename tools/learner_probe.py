@@ -112,6 +112,13 @@ Parts:
     ntuple_feature_sweep  part ntuple_shape_sweep's set-up unchanged: the 3 x 3 TD(0) run at rate 16 again (it must reproduce win for
               win) and the classical weights at one ply; "feat" as TD(0) at rates 2 .. 512 and "3x3+feat" at rates 2 .. 16; the best of
               each with symmetric updates; the best of each played at depth 2 and at beam (3, 8)
+    ntuple_budget  the budget table ("feat+spare") beside its "feat" twin at 2^20 boards (part ntuple_shape's): value, act, search, the
+              beam at (3, 8) and (6, 16) -- the policies with the prune off and on --, one learner step, and the update kernel alone
+              at horizons 1 and 4, each as a ratio to the twin's time in the same alternated rounds
+    ntuple_budget_sweep  the tight pool of the record (carved L=10 / M=40, 65,536 configurations, seed 7, solved at width 16,
+              tighten_pool(M_new=16)): the rate-8 "feat" learner again (it must reproduce win for win), then "feat+spare" from zero at
+              rates 2 .. 32 and from the promoted "feat" table, each trained with the prune off and on and played at one ply and at
+              beam (3, 8) with the prune off and on; the promoted table untrained is the prune alone; the loose pool once
     ntuple_shape_ab  --parent LIB: the nine 2 x 4 n-tuple kernels of another build of the learner library against this tree's, both
               loaded into one process: the outputs of the six entries compared byte for byte on the ring of part ntuple_shape
               at 2^18 boards, then each entry timed in five rounds of the parent against itself and five of the parent against
@@ -141,7 +148,8 @@ PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600, "priority": 600
          "ntuple_search": 900, "ntuple_trace": 600, "ntuple_trace_sweep": 1100, "ntuple_coherent": 600,
          "ntuple_coherent_sweep": 1700, "ntuple_shape": 600, "ntuple_shape_sweep": 1100, "ntuple_beam": 1100,
          "ntuple_sum": 600, "ntuple_sum_sweep": 600, "ntuple_stage": 600, "ntuple_stage_sweep": 900,
-         "ntuple_feature": 600, "ntuple_feature_sweep": 900, "solve": 900, "move_features": 1100, "bound": 900}
+         "ntuple_feature": 600, "ntuple_feature_sweep": 900, "solve": 900, "move_features": 1100, "bound": 900,
+         "ntuple_budget": 600, "ntuple_budget_sweep": 1100}
 SCATTERED_ATOMICS = 0.08e12                                 # 64 lanes of a wave adding into 64 rows (float adds; integer adds unmeasured)
 VALU_CYCLES, SIMDS, CLOCK_HZ = 3.3, 1024, 2.4e9           # the move's instruction mix, 256 CUs x 4, the clock
 
@@ -2110,6 +2118,160 @@ def part_ntuple_feature_sweep(eval_steps=12288):
         env.terminate()
         out["forms"][shape] = dict(best=runs[at], best_played=deep, best_symmetric_at_half_the_rate=symmetric,
                                    best_symmetric_at_the_same_rate=same_rate, runs=runs)
+    return out
+
+
+def part_ntuple_budget(rounds=5, reps=10, n=1 << 20):
+    """The budget table beside its "feat" twin on part ntuple_shape's boards: every time as a ratio to the twin's in the same rounds."""
+    import numpy as np
+    import torch
+    import tetris_piclim as T
+    m = T._learn_lib
+    L, check = m.lib(), m.check
+    stream = torch._C._cuda_getCurrentRawStream(0)
+    slots, head = 17, 16
+    kernels = ("ntuple_feature_value_kernel", "ntuple_budget_value_kernel", "ntuple_feature_act_kernel", "ntuple_budget_act_kernel",
+               "ntuple_feature_search_kernel", "ntuple_budget_search_kernel", "ntuple_feature_beam_kernel", "ntuple_budget_beam_kernel")
+    out = dict(part="ntuple_budget", boards=n, gamma=1.0, epsilon=0.05, learner_rate=1.0,
+               static_valu={k: _static_valu(k, m.build_library()) for k in kernels})
+    env, ring = _shape_ring(T, n, slots)                         # the environment stands at the ring's newest slot
+    feat = torch.from_numpy(np.random.default_rng(0).integers(-(1 << 20), (1 << 20) + 1, m.NTUPLE_ENTRIES_FEAT).astype(np.int32)).to("cuda:0")
+    table = {"feat": feat, "feat+spare": T.ntuple_budget(feat)}
+    table["feat+spare"][:-1024].view(8, 10, 256)[:, 9] = torch.randint(-(1 << 20), 1 << 20, (8, 256), dtype=torch.int32, device="cuda:0")
+    bins = T.ntuple_budget_bins(env)
+    out["spare_bin_of_the_boards"] = dict(dead=int((bins[:, 9] == 0).sum()), clamped=int((bins[:, 9] == 255).sum()),
+                                          distinct=int(torch.unique(bins[:, 9]).numel()))
+    error = torch.empty(n, dtype=torch.float32, device="cuda:0").normal_()
+    ra, rb = ring[0].data_ptr(), ring[1].data_ptr()
+    scratch = {name: table[name].clone() for name in table}
+    update = {}
+    for horizon in (1, 4):
+        for symmetric in (0, 1):
+            args = (ra, rb, n, slots, head, horizon, 10, 40)
+            tail = (error.data_ptr(), 100.0, 0.9, symmetric)
+            calls = {"feat": lambda a=args, t=tail: check(L.tpl_ntuple_update_trace_feature(*a, scratch["feat"].data_ptr(), *t, stream)),
+                     "feat+spare": lambda a=args, t=tail: check(L.tpl_ntuple_update_trace_budget(*a, scratch["feat+spare"].data_ptr(), *t, stream))}
+            times = {k: [] for k in calls}
+            for _ in range(rounds):
+                for k, fn in calls.items():
+                    times[k].append(_timed(fn, reps))
+            med = {k: sorted(ts)[rounds // 2] for k, ts in times.items()}
+            update[f"h{horizon}" + ("_symmetric" if symmetric else "")] = {
+                "feat_us": _spread(times["feat"]), "feat+spare_us": _spread(times["feat+spare"]),
+                "budget_over_feat": round(med["feat+spare"] / med["feat"], 4)}
+    out["update"] = update
+    del ring, scratch
+    action, second = (torch.empty(n, dtype=torch.uint8, device="cuda:0") for _ in range(2))
+    score, value = (torch.empty(n, dtype=torch.float32, device="cuda:0") for _ in range(2))
+    after = tuple(torch.empty((n, 4), dtype=torch.int32, device="cuda:0") for _ in range(2))
+    forms = (("feat", "feat", False), ("feat+spare", "feat+spare", False), ("feat+spare_pruned", "feat+spare", True))
+    variants = {}
+    for label, name, bound in forms:
+        act = T.NTuplePolicy(env, table[name], gamma=1.0, epsilon=0.05, seed=11, bound=bound)
+        search = T.NTuplePolicy(env, table[name], gamma=1.0, epsilon=0.05, seed=11, depth=2, bound=bound)
+        beams = {shape: T.NTupleBeamPolicy(env, table[name], *shape, gamma=1.0, bound=bound) for shape in ((3, 8), (6, 16))}
+        if not bound:
+            variants[("value", label)] = (lambda t=table[name]: T.ntuple_value(env, t, out=value), reps)
+        variants[("act", label)] = (lambda p=act: p.act(out=action, score=score, after=after, value=value, step=3), reps)
+        variants[("search", label)] = (lambda p=search: p.act(out=action, score=score, after=after, value=value, step=3, second=second),
+                                       max(reps // 3, 2))
+        variants[("beam_3x8", label)] = (lambda p=beams[(3, 8)]: p.act(out=action), 3)
+        variants[("beam_6x16", label)] = (lambda p=beams[(6, 16)]: p.act(out=action), 1)
+    order = sorted(variants)
+    times = {k: [] for k in order}
+    for _ in range(rounds):                                      # alternate the variants round by round
+        for k in order:
+            fn, count = variants[k]
+            times[k].append(_timed(fn, count, warmup=1))
+    learners = {label: T.NTupleLearner(env, gamma=1.0, rate=1.0, epsilon=0.05, seed=11, shape=name, bound=bound) for label, name, bound in forms}
+    for label, name, _ in forms:
+        learners[label].table.copy_(table[name])
+        learners[label].train(3)
+        times[("learner_step", label)] = []
+    for _ in range(rounds):
+        for label, _, _ in forms:
+            times[("learner_step", label)].append(_timed(lambda l=learners[label]: l.train(1), reps, warmup=1))
+    med = {k: sorted(ts)[rounds // 2] for k, ts in times.items()}
+    row = {}
+    for what in sorted({k[0] for k in times}):
+        labels = [label for label, _, _ in forms if (what, label) in times]
+        row[what] = {label + "_us": _spread(times[(what, label)]) for label in labels}
+        for label in labels[1:]:
+            row[what][label + "_over_feat"] = round(med[(what, label)] / med[(what, "feat")], 3)
+    env.terminate()
+    out["kernel"] = dict(rounds=rounds, launches_per_timing=reps, search_launches_per_timing=max(reps // 3, 2), beam_launches_per_timing=[3, 1],
+                         row=row)
+    res = subprocess.run(["bash", os.path.join(ROOT, "tools", "kernel_resources.sh"), m.build_library()], capture_output=True, text=True, cwd=ROOT)
+    out["resources"] = [" ".join(l.split()) for l in res.stdout.splitlines() if "ntuple_budget" in l or "ntuple_feature_" in l and "feature3" not in l]
+    return out
+
+
+def part_ntuple_budget_sweep(eval_steps=12288):
+    """The tight pool of the record (part_solve's and part_bound's): the rate-8 "feat" learner again, then the budget table."""
+    import torch
+    import tetris_piclim as T
+    dev = "cuda:0"
+    L_, M_, n = 10, 40, 1 << 16
+    env = T.BatchedTetris(L_, M_, 64, device=dev, seed=7)
+    rows, pieces = env.carved_configs(n, seed=7)
+    env.terminate()
+    found = T.solve_configs(rows, pieces, L_, M_, width=16, device=dev, validate=False)
+    M_new = 16
+    tight = T.tighten_pool(rows, pieces, found["solved"], found["solution_len"], M_new)
+    out = dict(part="ntuple_budget_sweep", boards=4096, seed=11, pool_seed=7, tight_pool=int(tight[0].shape[0]), M_new=M_new,
+               reward=list(NTUPLE_LARGE_REWARD), gamma=1.0, epsilon=0.05, eval_steps=eval_steps, train_steps=40000, runs=[])
+
+    def result(r):
+        p = r["win_rate"]
+        return dict(episodes=r["episodes"], wins=r["wins"], win_rate=round(p, 5), standard_error=round((p * (1 - p) / max(r["episodes"], 1)) ** 0.5, 6))
+
+    def played(learner):
+        """The table as it stands at one ply and at beam (3, 8), each without and with the prune (a "feat" table: without)."""
+        budget = learner.shape == "feat+spare"
+        got = {}
+        for name, kw in (("one_ply", {}), ("beam_3x8", dict(depth=3, width=8))):
+            for bound in ((False, True) if budget else (False,)):
+                got[name + ("_pruned" if bound else "")] = result(learner.evaluate(eval_steps, bound=bound, **kw))
+        return got
+
+    def learn(label, pool=tight, M_pool=M_new, train=True, keep=False, **kw):
+        env = T.BatchedTetris(L_, M_pool, 4096, device=dev, seed=11, auto_reset=True, reward=NTUPLE_LARGE_REWARD, config_pool=pool)
+        learner = T.NTupleLearner(env, seed=11, gamma=1.0, epsilon=0.05, **kw)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        before = None
+        if train:                                                # as the record's run: the start table is played first, then 40,000 steps
+            before = result(learner.evaluate(eval_steps))
+            for steps in (10000, 30000):
+                learner.train(steps)
+        got = dict(label=label, pool="tight" if pool is tight else "loose", trained=bool(train),
+                   **{k: v for k, v in kw.items() if k != "start"}, start_table=before, played=played(learner))
+        got["seconds"] = round(time.perf_counter() - t0, 2)
+        if learner.shape == "feat+spare":
+            row9 = learner.table[:-1024].view(8, 10, 256)[:, 9]
+            got["row_9"] = dict(entries_in_use=int((row9 != 0).sum()), bin_0_mean=round(float(row9[:, 0].float().mean()) / 65536, 4),
+                                live_bins_mean=round(float(row9[:, 1:][row9[:, 1:] != 0].float().mean()) / 65536, 4) if bool((row9[:, 1:] != 0).any()) else None)
+        table = learner.table.clone() if keep else None
+        env.terminate()
+        print(json.dumps(got), file=sys.stderr, flush=True)      # progress: a long part must not stay silent
+        out["runs"].append(got)
+        return got, table
+
+    baseline, feat = learn("feat rate 8, the record's run", keep=True, shape="feat", rate=8.0)
+    one = baseline["played"]["one_ply"]
+    out["baseline_reproduced_win_for_win"] = round(one["win_rate"], 5) == 0.51983
+    promoted = T.ntuple_budget(feat)
+    for bound in (False, True):                                  # the promoted table as it stands: with bound=True the prune alone
+        learn("promoted, untrained", train=False, shape="feat+spare", rate=8.0, start=promoted, bound=bound)
+    for rate in (2.0, 4.0, 8.0, 16.0, 32.0):
+        for bound in (False, True):
+            learn("from zero", shape="feat+spare", rate=rate, bound=bound)
+    for bound in (False, True):
+        learn("promoted, trained on", shape="feat+spare", rate=8.0, start=promoted, bound=bound)
+    loose = (rows, pieces)
+    learn("feat rate 8 on the loose pool", pool=loose, M_pool=M_, shape="feat", rate=8.0)
+    for bound in (False, True):
+        learn("from zero on the loose pool", pool=loose, M_pool=M_, shape="feat+spare", rate=8.0, bound=bound)
     return out
 
 
