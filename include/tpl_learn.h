@@ -489,6 +489,68 @@ int tpl_placement_beam_move_bound(const void* plane_a, const void* plane_b, int6
                                   int64_t boards_per_member, int32_t depth, int32_t width, float spare_weight, uint8_t* action,
                                   uint8_t* plan, float* score, void* stream);
 
+/* An exact depth-first solver for prescribed configurations.  What keeps tpl_placement_solve_bound from being a proof is its width
+ * cut.  A depth-first search has no width: within the move bound's prune it visits every running board, or it stops at a node budget
+ * and says so.  tpl_placement_exact searches the game of tpl_placement_solve_bound -- its configurations, its children, their values --
+ * depth first, and with `shortest` it deepens the move budget from the bound upwards, so that the first win it meets is a shortest one.
+ *
+ * For a configuration -- rows[20] and pieces[M + 1] as tpl_placement_solve takes them --, one weight row w[12], one finite spare_weight,
+ * max_nodes in [1, TPL_EXACT_MAX_NODES] and shortest = 0 or 1:
+ *   ONE ITERATION AT BUDGET B searches the game (L, B) depth first from the ROOT: 0 lines, 0 moves, running, carry c = 0.
+ *     Before a node at depth d is EXPANDED the node count is checked: if nodes == max_nodes THE WHOLE SEARCH ENDS with solved = 0,
+ *     proved = 0, solution_len = 0 and a path of 255s; otherwise nodes += 1.
+ *     To expand a node: its current piece is pieces[d] & 7, taken from the list; it has one child per distinct placement b of that piece
+ *     in ascending b, each made and valued exactly as tpl_placement_solve_bound makes and values a candidate, under (L, B): move_board
+ *     (node, b), whose move limit is B; a child left running and dead under (L, B) becomes LOST (the bounded form, change 1); with n the
+ *     rows the move cleared,
+ *       psi = (c + n, won, lost, features 3..11 of the child's board)
+ *       value = the score rule on psi, then + spare_weight * float(spare) (the bounded form, change 2).
+ *     The children are ordered by (value descending, b ascending); -0 and +0 tie.
+ *     If ANY child is won the iteration ends with a WIN of length d + 1: the solution is the path to the node, then the won child that
+ *     comes first in the order.
+ *     Otherwise the RUNNING children are descended into, one after the other, in that order -- each expanded as above at depth d + 1
+ *     with c + n for its carry --, and when they are used up the search returns to the node's parent.  A running child has made
+ *     d + 1 < B moves, so no path is longer than B.
+ *     The iteration ends WITHOUT A WIN when the root's children are used up.
+ *   THE BUDGETS.  bound = need(root) (the move bound) is written in every case.
+ *     shortest = 1: B = bound, bound + 1, .., M; the first iteration that wins ends the search with solved = 1, solution_len = B -- every
+ *                   smaller budget was searched out without a win and no solution is shorter than bound, so the win is of length B exactly.
+ *     shortest = 0: one iteration at B = M.
+ *     If bound > M there is no iteration: solved = 0, proved = 1, nodes = 0.
+ *     If no iteration wins: solved = 0, solution_len = 0, a path of 255s.
+ *     nodes counts the expansions of all iterations, and max_nodes caps that sum.
+ *   proved = 1 iff the search was not stopped by max_nodes.
+ * UNDER proved = 1, solved = 0 PROVES that no sequence of placements wins within M moves: the only boards left unexpanded are dead ones
+ * and finished ones, and a dead board has no winning continuation (the move bound's proof, above).  solved = 1 always comes with
+ * proved = 1, and with shortest = 1 solution_len is then THE SHORTEST THERE IS.  WITH proved = 0 NOTHING IS PROVED: NOT THAT THERE IS A
+ * WIN, AND NOT THAT THERE IS NONE.
+ * Consequences:
+ *   1. Playing the solution move by move from the configuration ends won after exactly solution_len moves, on any correct
+ *      implementation of the game.
+ *   2. Wherever tpl_placement_solve_bound reports complete = 1 for the same configuration, L, M, weights and spare_weight, this search
+ *      with proved = 1 agrees with it on solved, and with shortest = 1 on solution_len as well.
+ *   3. The result is a function of the inputs alone; nothing is written but the outputs.
+ * The weights order the children and so decide how soon a win is met and how many nodes that takes; they do not decide WHETHER a
+ * search that ends with proved = 1 finds one.  THE FINITENESS CAVEAT of the weights and the masking of the piece ids are
+ * tpl_placement_solve's.  tpl_placement_exact_move is the 14-feature form: weights f32 [16] of which 14 are read, a node's carry holding
+ * the landing and eroded sums of its path as the solver's does.
+ *
+ * One kernel, ONE CONFIGURATION PER WAVEFRONT (csrc/learn/exact.hip): lanes 0 .. 33 each make one child of the node being expanded, the
+ * order comes from 64-bit keys ranked across the wave, and the stack -- a record of 80 bytes a depth -- is LDS sized by M.  rows
+ * i16 [n][20] and pieces u8 [n][M + 1] are read; solved u8 [n], proved u8 [n], solution_len i32 [n], actions u8 [n][M] (the solution's
+ * placements b = 10 r + l, 255 behind the end), bound i32 [n] and nodes u32 [n] are each written in full.
+ * Refused before any HIP call: everything tpl_placement_solve_bound refuses of the arguments the two share (n < 1, n >= 2^31, a NULL
+ * rows, pieces, weights, solved, solution_len, actions or bound, weights not 16-byte aligned, solution_len or bound not 4-byte
+ * aligned, rows not 2-byte aligned, L outside [1, 250] or M outside [1, 254], a spare_weight that is not finite), a NULL proved or
+ * nodes, nodes not 4-byte aligned, max_nodes outside [1, TPL_EXACT_MAX_NODES], shortest other than 0 or 1. */
+#define TPL_EXACT_MAX_NODES (1 << 24)
+int tpl_placement_exact(const int16_t* rows, const uint8_t* pieces, int64_t n, int32_t L, int32_t M, const float* weights,
+                        float spare_weight, int32_t max_nodes, int32_t shortest, uint8_t* solved, uint8_t* proved,
+                        int32_t* solution_len, uint8_t* actions, int32_t* bound, uint32_t* nodes, void* stream);
+int tpl_placement_exact_move(const int16_t* rows, const uint8_t* pieces, int64_t n, int32_t L, int32_t M, const float* weights,
+                             float spare_weight, int32_t max_nodes, int32_t shortest, uint8_t* solved, uint8_t* proved,
+                             int32_t* solution_len, uint8_t* actions, int32_t* bound, uint32_t* nodes, void* stream);
+
 /* An n-tuple afterstate value function, its placement policy and its temporal-difference update (csrc/learn/ntuple.hip).
  *
  * Table: TPL_NTUPLE_ENTRIES = 8 * 153 * 256 + 1024 = 314,368 int32 entries (1,257,472 bytes), 16-byte aligned, in units of 2^-16:

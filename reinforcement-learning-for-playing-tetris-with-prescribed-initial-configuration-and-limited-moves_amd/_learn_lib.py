@@ -24,7 +24,7 @@ _UNITS = [os.path.join(_LEARN_CSRC, f) for f in ("replay.hip", "pack.hip", "prio
                                                       "beam.hip", "solve.hip", "ntuple.hip", "ntuple_beam.hip", "heuristic_move.hip",
                                                       "beam_move.hip", "solve_move.hip", "bound.hip", "beam_bound.hip",
                                                       "solve_bound.hip", "beam_move_bound.hip", "solve_move_bound.hip",
-                                                      "heuristic.hip")]
+                                                      "exact.hip", "exact_move.hip", "heuristic.hip")]
 
 # entry points declared in include/tpl_learn.h (tests check that the .so exports every one of them)
 LEARN_SYMBOLS = [
@@ -47,6 +47,7 @@ LEARN_SYMBOLS = [
     "tpl_placement_beam_bound", "tpl_placement_beam_move_bound",
     "tpl_ntuple_value_budget", "tpl_ntuple_act_budget", "tpl_ntuple_search_budget", "tpl_ntuple_beam_budget",
     "tpl_ntuple_update_trace_budget", "tpl_ntuple_budget_bins",
+    "tpl_placement_exact", "tpl_placement_exact_move",
 ]
 NSTEP_MAX = 16
 BEAM_MAX_DEPTH, BEAM_MAX_WIDTH = 12, 64
@@ -168,6 +169,9 @@ def lib() -> C.CDLL:
         beam.argtypes = [vp, vp, i64, i32, i32, vp, i64, i32, i32, f32, vp, vp, vp, vp]
         solve.argtypes = [vp, vp, i64, i32, i32, vp, i32, f32, vp, vp, vp, vp, vp, vp, vp]
         beam.restype = solve.restype = i32
+        exact = getattr(L, f"tpl_placement_exact{form}")     # the exact search: a node budget and a flag for a width
+        exact.argtypes = [vp, vp, i64, i32, i32, vp, f32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+        exact.restype = i32
     L.tpl_ntuple_value.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp]
     L.tpl_ntuple_act.argtypes = [vp, vp, i64, i32, i32, f32, f32, f32, f32, vp, f32, u64, u64, vp, vp, vp, vp, vp, vp]
     L.tpl_ntuple_update.argtypes = [vp, vp, i64, i32, i32, vp, vp, f32, vp]
@@ -503,7 +507,7 @@ FEATURE_COUNTS = (NUM_FEATURES, NUM_MOVE_FEATURES)
 
 def entry(name: str, count: int, bound: bool = False):
     """The entry point tpl_placement_<name> of the feature set with `count` features (12 or 14); bound=True: its bounded form
-    (beam and solve have one)."""
+    (beam and solve have one; exact is of the bounded form as it stands and has no other)."""
     if count not in FEATURE_COUNTS:
         raise ValueError(f"a weight row has {NUM_FEATURES} or {NUM_MOVE_FEATURES} entries, not {count}")
     return getattr(lib(), f"tpl_placement_{name}" + ("_move" if count == NUM_MOVE_FEATURES else "") + ("_bound" if bound else ""))
@@ -879,6 +883,117 @@ def placement_solve(rows, pieces, L: int, M: int, weights, width: int, max_width
     if bound:
         return solved, length, actions, best_value, root_need, complete
     return solved, length, actions, best_value
+
+
+# ------------------------------------------------------------------------------------------------ the exact search
+# The rule of tpl_placement_exact (include/tpl_learn.h) on the host, from the ROW form of a board again: host_moves_traced,
+# move_bound, board_features and placement_score.  The device keeps a stack of packed boards in LDS and ranks keys across a wave
+# (csrc/learn/exact.hip) -- the two share nothing.
+EXACT_MAX_NODES = 1 << 24
+
+
+def placement_exact(rows, pieces, L: int, M: int, weights, max_nodes: int, shortest: bool = True, spare_weight: float = 0.0):
+    """The rule of tpl_placement_exact (include/tpl_learn.h) for n configurations: rows uint16 [n, 20] (bit x = column x), pieces
+    [n, M + 1] (masked to three bits), one weight row [12] or [14], max_nodes in [1, 2^24], shortest True or False, one finite
+    spare_weight.  A depth-first search of the game (L, B) in the bounded form -- a child that the move bound proves lost under B is
+    lost --, children ordered by (value descending, placement ascending; -0 and +0 tie), the first won child of a node ending the
+    iteration; B runs over need(root) .. M (shortest) or is M alone; `nodes` counts the expansions of all iterations and the search
+    gives up, proving nothing, when it would pass max_nodes.  Returns (solved uint8 [n], proved uint8 [n], solution_len int32 [n],
+    actions uint8 [n, M] padded with 255, bound int32 [n], nodes uint32 [n]) in the C layout.
+    The configurations are searched in step, one expansion each a round, so that every round moves and counts the children of all of
+    them in one batch per budget."""
+    L, M = int(L), int(M)
+    if not (1 <= L <= 250 and 1 <= M <= SOLVE_MAX_MOVES):
+        raise ValueError(f"L and M must be in [1, 250] and [1, {SOLVE_MAX_MOVES}]")
+    if isinstance(max_nodes, bool) or not isinstance(max_nodes, (int, np.integer)) or not 1 <= int(max_nodes) <= EXACT_MAX_NODES:
+        raise ValueError(f"max_nodes must be an integer in [1, {EXACT_MAX_NODES}]")
+    max_nodes = int(max_nodes)
+    if not isinstance(shortest, (bool, np.bool_)):
+        raise ValueError("shortest must be True or False")
+    rows = np.asarray(rows)
+    rows = (rows.view(np.uint16) if rows.dtype == np.int16 else rows.astype(np.uint16)).reshape(-1, 20)
+    n = rows.shape[0]
+    pieces = np.asarray(pieces).astype(np.int64) & 7
+    if n < 1 or pieces.shape != (n, M + 1):
+        raise ValueError(f"rows must be [n, 20] and pieces [n, {M + 1}] with n >= 1")
+    w = np.asarray(weights, dtype=np.float32).reshape(-1)
+    if w.shape not in ((NUM_FEATURES,), (NUM_MOVE_FEATURES,)):
+        raise ValueError("weights must be one row of 12 or of 14")
+    move = w.shape[0] == NUM_MOVE_FEATURES
+    with np.errstate(over="ignore"):
+        spare_weight = np.float32(spare_weight)
+    if not np.isfinite(spare_weight):
+        raise ValueError("spare_weight must be finite (in float32)")
+    bound = move_bound(rows, L, M, 0, 0, STATE_RUNNING)["need"].astype(np.int32)
+    placements = [np.flatnonzero(canonical_actions(p, np.arange(NUM_ACTIONS)) == np.arange(NUM_ACTIONS)) for p in range(8)]
+    solved, proved, length = np.zeros(n, np.uint8), np.ones(n, np.uint8), np.zeros(n, np.int32)
+    actions, nodes = np.full((n, M), NO_SECOND, np.uint8), np.zeros(n, np.uint32)
+
+    def root(s):
+        return dict(rows=rows[s], lines=0, moves=0, sums=np.zeros(2, np.int64), kids=None, at=0)
+
+    # a stack per configuration still searched, its last frame the node to expand next; a frame's kids are its running children in
+    # the order of the descent -- (placement, rows, lines, moves, sums) each --, `at` the next of them
+    budget = {s: int(bound[s]) if shortest else M for s in range(n) if bound[s] <= M}
+    stacks = {s: [root(s)] for s in budget}
+    while stacks:
+        capped = [s for s in stacks if nodes[s] == max_nodes]
+        for s in capped:                                        # the cap: nothing is proved, nothing is reported
+            proved[s] = 0
+            del stacks[s]
+        if not stacks:
+            break
+        todo = sorted(stacks)
+        nodes[todo] += 1
+        found = {}
+        for B in sorted({budget[s] for s in todo}):             # the game (L, B): one batch per budget
+            group = [s for s in todo if budget[s] == B]
+            tops = [stacks[s][-1] for s in group]
+            place = [placements[pieces[s, len(stacks[s]) - 1]] for s in group]
+            sizes = [b.size for b in place]
+            b = np.concatenate(place)
+            rep = lambda key: np.repeat(np.array([t[key] for t in tops]), sizes, axis=0)
+            piece = np.repeat([pieces[s, len(stacks[s]) - 1] for s in group], sizes)
+            r2, _, l2, m2, s2, _, _, land, erod = host_moves_traced(rep("rows"), piece, b // 10, b % 10, L, B, rep("lines"), rep("moves"))
+            sums = rep("sums") + np.stack([land, erod], axis=1)
+            mb = move_bound(r2, L, B, l2, m2, s2)
+            s2 = np.where(mb["dead"], STATE_LOST_LIMIT, s2)
+            spare = np.where(mb["dead"], 0, mb["spare"])
+            psi = np.concatenate([np.stack([l2, s2 == STATE_WON, s2 >= STATE_LOST_LIMIT], axis=1).astype(np.int64),
+                                  board_features(r2)] + ([sums] if move else []), axis=1)
+            value = placement_score(psi, w)
+            value = value + spare_weight * spare.astype(np.float32)
+            lo = 0
+            for s, size in zip(group, sizes):
+                found[s] = (b[lo:lo + size], value[lo:lo + size], s2[lo:lo + size], r2[lo:lo + size], l2[lo:lo + size],
+                            m2[lo:lo + size], sums[lo:lo + size])
+                lo += size
+        for s in todo:
+            b, value, state, c_rows, c_lines, c_moves, c_sums = found[s]
+            stack = stacks[s]
+            order = np.argsort(-(value + np.float32(0.0)), kind="stable")
+            won = order[state[order] == STATE_WON]
+            if won.size:                                        # a win at this depth + 1: the path to here, then the won child
+                path = [f["kids"][f["at"] - 1][0] for f in stack[:-1]] + [int(b[won[0]])]
+                solved[s], length[s] = 1, len(path)
+                actions[s, :len(path)] = path
+                del stacks[s]
+                continue
+            run = order[state[order] == STATE_RUNNING]
+            stack[-1]["kids"] = [(int(b[k]), c_rows[k], int(c_lines[k]), int(c_moves[k]), c_sums[k]) for k in run]
+            while stack and stack[-1]["at"] == len(stack[-1]["kids"]):
+                stack.pop()                                     # used up: back to the parent
+            if stack:
+                top = stack[-1]
+                _, k_rows, k_lines, k_moves, k_sums = top["kids"][top["at"]]
+                top["at"] += 1
+                stack.append(dict(rows=k_rows, lines=k_lines, moves=k_moves, sums=k_sums, kids=None, at=0))
+            elif shortest and budget[s] < M:                    # searched out at this budget: the next one
+                budget[s] += 1
+                stack.append(root(s))
+            else:                                               # searched out: no sequence of placements wins within M moves
+                del stacks[s]
+    return solved, proved, length, actions, bound, nodes
 
 
 # ------------------------------------------------------------------------------------------------ the n-tuple value function

@@ -10,14 +10,18 @@ tighter move budget from the solution lengths (`tighten_pool`).
 unless the search was the bounded one and `complete`: `solve_configs(bound=True)` prunes every board that the move bound
 (include/tpl_learn.h) proves lost, reports `bound`, the least number of moves any solution can take (`config_bound` gives it alone),
 and `complete`, under which `solved = False` IS a proof that there is no win and `solved = True` that the solution is the shortest.
+
+`prove_configs` is the search that has no width to cut with: a depth-first search of the same game (tpl_placement_exact;
+csrc/learn/exact.hip), one wavefront per configuration, which within the move bound's prune visits every running board or stops at a
+node budget and says so (`proved`).
 """
 from __future__ import annotations
 
 import numpy as np
 
-from ._learn_lib import BEAM_MAX_WIDTH, NUM_FEATURES, NUM_MOVE_FEATURES, SOLVE_MAX_MOVES
+from ._learn_lib import BEAM_MAX_WIDTH, EXACT_MAX_NODES, NUM_FEATURES, NUM_MOVE_FEATURES, SOLVE_MAX_MOVES
 
-__all__ = ["CLASSICAL_WEIGHTS", "solve_configs", "tighten_pool", "config_bound"]
+__all__ = ["CLASSICAL_WEIGHTS", "solve_configs", "prove_configs", "tighten_pool", "config_bound"]
 
 # cleared, won, lost, holes, aggregate height, max height, bumpiness, row and column transitions, wells, rows with holes, hole depth:
 # the classical signs, a sensible default for the supply (0.99925 of a carved L = 10 / M = 40 pool at one ply)
@@ -102,6 +106,29 @@ def _device_rows(rows, d):
     return rows
 
 
+def _device_pieces(pieces, n: int, M: int, d, validate: bool):
+    """pieces as solve_configs takes them -> a contiguous uint8 [n, M + 1] tensor on device d, [n, M] padded with piece 0; the
+    piece-id check (one host wait) unless validate is False."""
+    import torch
+    if not _is_tensor(pieces):
+        pieces = torch.as_tensor(np.ascontiguousarray(pieces.astype(np.uint8)))
+    pieces = pieces.to(device=d, dtype=torch.uint8)
+    if pieces.shape[1] == M:
+        pieces = torch.cat([pieces, torch.zeros((n, 1), dtype=torch.uint8, device=d)], dim=1)
+    pieces = pieces.contiguous()
+    if validate and int(pieces.max()) > 6:
+        raise ValueError("piece ids must be in 0..6 (I L J T S Z O)")
+    return pieces
+
+
+def _solution(actions):
+    """actions uint8 [n, M] (255 behind the end) -> uint8 [n, M, 2] as (rotations, location), zero behind the end."""
+    import torch
+    played = actions != 255
+    a = torch.where(played, actions, torch.zeros_like(actions))
+    return torch.stack([a // 10, a % 10], dim=2).to(torch.uint8)
+
+
 def config_bound(rows, L: int, device="cuda:0"):
     """The least number of moves any solution of each configuration can take (include/tpl_learn.h: the move bound;
     tpl_move_bound_rows): int32 [n] on `device`, ceil(cells / 4) with cells the cells missing from the L cheapest rows.  rows as
@@ -161,14 +188,7 @@ def solve_configs(rows, pieces, L: int, M: int, weights=None, width: int = 16, d
     n = _shapes(rows, pieces, M)
     d = torch.device(device)
     rows = _device_rows(rows, d)
-    if not _is_tensor(pieces):
-        pieces = torch.as_tensor(np.ascontiguousarray(pieces.astype(np.uint8)))
-    pieces = pieces.to(device=d, dtype=torch.uint8)
-    if pieces.shape[1] == M:
-        pieces = torch.cat([pieces, torch.zeros((n, 1), dtype=torch.uint8, device=d)], dim=1)
-    pieces = pieces.contiguous()
-    if validate and int(pieces.max()) > 6:
-        raise ValueError("piece ids must be in 0..6 (I L J T S Z O)")
+    pieces = _device_pieces(pieces, n, M, d, validate)
     wt = torch.from_numpy(_learn_lib.padded_weights(w)).to(d)
     out = dict(solved=torch.empty(n, dtype=torch.uint8, device=d), solution_len=torch.empty(n, dtype=torch.int32, device=d),
                actions=torch.empty((n, M), dtype=torch.uint8, device=d))
@@ -189,9 +209,64 @@ def solve_configs(rows, pieces, L: int, M: int, weights=None, width: int = 16, d
     out["solved"] = out["solved"].view(torch.bool)
     if bound:
         out["optimal"] = out["solved"] & ((out["solution_len"] == out["bound"]) | out["complete"])
-    played = out["actions"] != 255
-    a = torch.where(played, out["actions"], torch.zeros_like(out["actions"]))
-    out["solution"] = torch.stack([a // 10, a % 10], dim=2).to(torch.uint8)
+    out["solution"] = _solution(out["actions"])
+    return out
+
+
+def _max_nodes(max_nodes) -> int:
+    if isinstance(max_nodes, bool) or not isinstance(max_nodes, (int, np.integer)) or not 1 <= int(max_nodes) <= EXACT_MAX_NODES:
+        raise ValueError(f"max_nodes must be an integer in [1, {EXACT_MAX_NODES}], got {max_nodes!r}")
+    return int(max_nodes)
+
+
+def prove_configs(rows, pieces, L: int, M: int, weights=None, max_nodes: int = 1 << 16, shortest: bool = True,
+                  spare_weight: float = 0.0, device="cuda:0", validate: bool = True) -> dict:
+    """Search every configuration's whole game depth first and exactly (the rule: include/tpl_learn.h, tpl_placement_exact;
+    csrc/learn/exact.hip), one wavefront per configuration.
+
+    rows, pieces, weights (None = CLASSICAL_WEIGHTS; fourteen select the 14-feature form), device and validate are solve_configs';
+    spare_weight is one finite number added, times a node's spare cells, to its value -- the search is always the bounded one, so it
+    needs no switch.  max_nodes in [1, 2^24] caps the nodes a configuration may expand, over all its iterations.  shortest=True
+    deepens the move budget from `bound` to M, so that the first win met is a shortest one; shortest=False searches at M alone and
+    takes the first win it meets.  The weights only order the children: they decide how many nodes a search takes, not what a search
+    that ends finds.
+    Returns a dict of device tensors: solved bool [n], proved bool [n], solution_len int32 [n], actions uint8 [n, M] (placements
+    10 r + l, 255 behind the end), solution uint8 [n, M, 2] in solve_configs' layout, bound int32 [n] (the least number of moves any
+    solution can take), nodes int32 [n] (the nodes expanded, at most 2^24), optimal bool [n] = solved & shortest and unwinnable bool [n] =
+    proved & ~solved.
+
+    **proved[i] is set iff the search of configuration i was not stopped by max_nodes.  With it, solved[i] = False IS a proof that no
+    sequence of placements wins within M moves, and with shortest=True solved[i] = True a proof that solution_len[i] is the shortest
+    there is.  solved[i] = True always comes with proved[i].  Without proved[i] NOTHING is proved, neither way.**
+    No host wait except the piece-id check, which validate=False skips."""
+    import torch
+    from . import _learn_lib
+    L, M = _game(L, M)
+    w = _weight_row(weights)
+    max_nodes = _max_nodes(max_nodes)
+    if not isinstance(shortest, (bool, np.bool_)):
+        raise ValueError(f"shortest must be True or False, got {shortest!r}")
+    spare_weight = _spare_weight(spare_weight, True)
+    if not _is_tensor(rows):
+        rows = np.asarray(rows)
+    if not _is_tensor(pieces):
+        pieces = np.asarray(pieces)
+    n = _shapes(rows, pieces, M)
+    d = torch.device(device)
+    rows = _device_rows(rows, d)
+    pieces = _device_pieces(pieces, n, M, d, validate)
+    wt = torch.from_numpy(_learn_lib.padded_weights(w)).to(d)
+    out = dict(solved=torch.empty(n, dtype=torch.uint8, device=d), proved=torch.empty(n, dtype=torch.uint8, device=d),
+               solution_len=torch.empty(n, dtype=torch.int32, device=d), actions=torch.empty((n, M), dtype=torch.uint8, device=d),
+               bound=torch.empty(n, dtype=torch.int32, device=d), nodes=torch.empty(n, dtype=torch.int32, device=d))
+    stream = torch._C._cuda_getCurrentRawStream(d.index if d.index is not None else torch.cuda.current_device())
+    _learn_lib.check(_learn_lib.entry("exact", w.shape[0])(
+        rows.data_ptr(), pieces.data_ptr(), n, L, M, wt.data_ptr(), spare_weight, max_nodes, int(bool(shortest)),
+        *(out[k].data_ptr() for k in ("solved", "proved", "solution_len", "actions", "bound", "nodes")), stream))
+    out["solved"], out["proved"] = out["solved"].view(torch.bool), out["proved"].view(torch.bool)
+    out["optimal"] = out["solved"] & bool(shortest)
+    out["unwinnable"] = out["proved"] & ~out["solved"]
+    out["solution"] = _solution(out["actions"])
     return out
 
 
@@ -201,7 +276,9 @@ def tighten_pool(rows, pieces, solved, solution_len, M_new: int, bound=None, sla
     that was found.  Tensors (one host wait) or arrays; M is read off pieces [n, M + 1].  M_new outside [1, M] is refused, and so
     is a result with nothing left.
     `bound` ([n], config_bound's or solve_configs(bound=True)'s) and `slack` (an integer >= 0), given together, also require
-    bound >= M_new - slack: a pool whose budget is provably within `slack` moves of the least any solution can take."""
+    bound >= M_new - slack: a pool whose budget is provably within `slack` moves of the least any solution can take.
+    With prove_configs' solved and solution_len (shortest=True) the kept pool's budget is exact: solution_len is then every
+    solved entry's shortest solution, so a proved entry is kept iff it can be won within M_new moves."""
     if (bound is None) != (slack is None):
         raise ValueError("bound and slack go together")
     if slack is not None and (isinstance(slack, bool) or not isinstance(slack, (int, np.integer)) or int(slack) < 0):

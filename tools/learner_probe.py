@@ -119,6 +119,10 @@ Parts:
               tighten_pool(M_new=16)): the rate-8 "feat" learner again (it must reproduce win for win), then "feat+spare" from zero at
               rates 2 .. 32 and from the promoted "feat" table, each trained with the prune off and on and played at one ply and at
               beam (3, 8) with the prune off and on; the promoted table untrained is the prune alone; the loose pool once
+    exact     the exact depth-first solver (tpl_placement_exact, prove_configs) on the record's pool (carved L=10 / M=40, 65,536
+              configurations, seed 7) at budgets of config_bound + 0, 1, 2 and max_nodes 2^12, 2^16 and 2^20: proved, solved and proved
+              unwinnable, mean and maximum nodes, seconds and nodes a second, the bounded beam at widths 16 and 64 beside it, and how
+              much of what width 64 leaves unsolved is then solved and proved shortest
     ntuple_shape_ab  --parent LIB: the nine 2 x 4 n-tuple kernels of another build of the learner library against this tree's, both
               loaded into one process: the outputs of the six entries compared byte for byte on the ring of part ntuple_shape
               at 2^18 boards, then each entry timed in five rounds of the parent against itself and five of the parent against
@@ -149,7 +153,7 @@ PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600, "priority": 600
          "ntuple_coherent_sweep": 1700, "ntuple_shape": 600, "ntuple_shape_sweep": 1100, "ntuple_beam": 1100,
          "ntuple_sum": 600, "ntuple_sum_sweep": 600, "ntuple_stage": 600, "ntuple_stage_sweep": 900,
          "ntuple_feature": 600, "ntuple_feature_sweep": 900, "solve": 900, "move_features": 1100, "bound": 900,
-         "ntuple_budget": 600, "ntuple_budget_sweep": 1100}
+         "ntuple_budget": 600, "ntuple_budget_sweep": 1100, "exact": 900}
 SCATTERED_ATOMICS = 0.08e12                                 # 64 lanes of a wave adding into 64 rows (float adds; integer adds unmeasured)
 VALU_CYCLES, SIMDS, CLOCK_HZ = 3.3, 1024, 2.4e9           # the move's instruction mix, 256 CUs x 4, the clock
 
@@ -2621,6 +2625,88 @@ def part_bound(rounds=5):
                      if any(k in l for k in ("placement_solve", "placement_beam", "move_bound"))]
     out["scratch_bytes_over_every_kernel"] = sum(int(l.split()[l.split().index("scratch") - 1]) for l in res.stdout.splitlines() if " scratch " in l)
     out["note"] = "fresh boards at M = 40 have no dead child for many plies: the time ratios are the cost of the bound, not the gain of the prune"
+    return out
+
+
+def part_exact(slice_size=4096, minute=60.0):
+    """The exact depth-first solver (include/tpl_learn.h: tpl_placement_exact) on the record's pool (carved L = 10 / M = 40, 65,536
+    configurations, seed 7) at budgets of config_bound + 0, 1, 2 and max_nodes 2^12, 2^16 and 2^20: the shares proved, solved and proved
+    unwinnable, the nodes, the time and the nodes a second, with the bounded beam at widths 16 and 64 beside it in the same run.  The
+    2^20 leg runs on the whole pool only if the 2^16 leg at the same budget says that it would take about a minute at most (sixteen
+    times as long at the worst); otherwise on the pool's first `slice_size` configurations.  One seed, one pool, one weight row."""
+    import numpy as np
+    import torch
+    import tetris_piclim as T
+    dev = "cuda:0"
+    L_, M_ = 10, 40
+    share = lambda x: round(float(x.float().mean()), 5)
+    out = dict(part="exact", exact=[], beam=[], of_what_width_64_left_unsolved=[])
+
+    def progress(what):
+        print(json.dumps(what), file=sys.stderr, flush=True)
+
+    n = 1 << 16
+    env = T.BatchedTetris(L_, M_, 64, device=dev, seed=7)
+    rows, pieces, _, carved_len = env.carved_configs(n, seed=7, with_solutions=True)
+    env.terminate()
+    need = T.config_bound(rows, L_, device=dev)
+    out["pool"] = dict(size=n, seed=7, L=L_, M=M_, weights="classical", config_bound_equals_carving_len=share(need == carved_len),
+                       config_bound_mean=round(float(need.float().mean()), 2))
+
+    def grouped(budget, count, search):
+        """`search` on the first `count` configurations, grouped by budget: its dict's entries gathered, and the seconds it took."""
+        got = {}
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for b in torch.unique(budget[:count]).tolist():
+            at = torch.nonzero(budget[:count] == b).flatten()
+            part = search(rows[at], pieces[at][:, :b + 1].contiguous(), b)
+            for k, v in part.items():
+                if v.dim() == 1:
+                    got.setdefault(k, torch.zeros(count, dtype=v.dtype, device=dev))[at] = v
+        torch.cuda.synchronize()
+        return got, time.perf_counter() - t0
+
+    beam_solved = {}
+    for slack in (0, 1, 2):
+        budget = torch.clamp(need + slack, max=M_)
+        for W in (16, 64):
+            got, seconds = grouped(budget, n, lambda r, p, b: T.solve_configs(r, p, L_, b, width=W, device=dev, validate=False, bound=True))
+            line = dict(budget=f"config_bound + {slack}", width=W, configurations=n, solved=share(got["solved"]),
+                        complete=share(got["complete"]), optimal=share(got["optimal"]),
+                        proved_unwinnable=share(~got["solved"] & got["complete"]), seconds=round(seconds, 3))
+            beam_solved[(slack, W)] = got["solved"]
+            out["beam"].append(line)
+            progress(line)
+        last = None
+        for log2 in (12, 16, 20):
+            count = n
+            if log2 == 20 and (last is None or last * 16 > minute):
+                count = slice_size
+            got, seconds = grouped(budget, count, lambda r, p, b: T.prove_configs(r, p, L_, b, max_nodes=1 << log2, device=dev,
+                                                                                  validate=False))
+            nodes = got["nodes"].double()
+            line = dict(budget=f"config_bound + {slack}", max_nodes=f"2^{log2}", configurations=count, proved=share(got["proved"]),
+                        solved=share(got["solved"]), unwinnable=share(got["unwinnable"]), nodes_mean=round(float(nodes.mean()), 1),
+                        nodes_max=int(nodes.max()), seconds=round(seconds, 3), nodes_per_second=round(float(nodes.sum()) / seconds, 1),
+                        solution_len_equals_config_bound=share(got["solution_len"][got["solved"]] == need[:count][got["solved"]])
+                        if bool(got["solved"].any()) else None)
+            last = seconds if log2 == 16 else last
+            out["exact"].append(line)
+            progress(line)
+            left = ~beam_solved[(slack, 64)][:count]
+            if bool(left.any()):
+                line = dict(budget=f"config_bound + {slack}", max_nodes=f"2^{log2}", configurations=count,
+                            unsolved_at_width_64=share(left), of_them_solved_and_proved_shortest=share(got["optimal"][left]),
+                            of_them_proved_unwinnable=share(got["unwinnable"][left]), of_them_not_proved=share(~got["proved"][left]))
+                out["of_what_width_64_left_unsolved"].append(line)
+                progress(line)
+    res = subprocess.run(["bash", os.path.join(ROOT, "tools", "kernel_resources.sh"), T._learn_lib.build_library()],
+                         capture_output=True, text=True, cwd=ROOT)
+    out["kernel"] = [" ".join(l.split()) for l in res.stdout.splitlines() if "placement_exact" in l]
+    out["not_measured"] = ("other weight rows and spare_weight other than 0; shortest=False; max_nodes above 2^20; pools other than this one; "
+                           "the kernel's time against a launch bound other than eight waves a SIMD; the idle lanes and a transposition table "
+                           "are not built")
     return out
 
 
