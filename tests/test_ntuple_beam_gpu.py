@@ -65,7 +65,7 @@ def effective(states, idx, depth):
     return np.where(states.running[idx], np.minimum(depth, 11 - states.moves[idx] % 10), 0)
 
 
-def _beam(A, B, table, depth, width, gamma=GAMMA, skip=(), params=PARAMS):
+def _beam(A, B, table, depth, width, gamma=GAMMA, skip=(), params=PARAMS, L=L, M=M):
     """tpl_ntuple_beam of host planes through canary-framed buffers; `skip` names the outputs passed as NULL ("after" = both)."""
     n = A.shape[0]
     shape = _m().NTUPLE_SHAPE_IDS[_m().ntuple_shape_of(table.shape[0])]
@@ -105,7 +105,7 @@ def _same(got, want, what):
 
 
 # ------------------------------------------------------------------------------------------------ 1. the parent's kernels
-def _folded_second(env, table, A, B, action, b2, gamma):
+def _folded_second(env, table, A, B, action, b2, gamma, L=L, M=M):
     """r1 + gamma * (r2 + gamma * V) of first placement `action` and second placement `b2` for every state, by T.afterstates and
     T.ntuple_value: what the beam calls the folded value of the path (action, b2)."""
     n = A.shape[0]
@@ -165,7 +165,7 @@ def _state_of(B):
     return (B[..., 1] >> np.uint32(28)) & np.uint32(3)
 
 
-def compose(env, table, A, B, plies, depth, width, gamma=GAMMA, mirror_value=False):
+def compose(env, table, A, B, plies, depth, width, gamma=GAMMA, mirror_value=False, L=L, M=M):
     """The rule without the kernel under test: every ply is T.afterstates on the beam's planes, V of the children from
     T.ntuple_value (mirror_value: from _learn_lib.ntuple_value on the decoded children), the numpy fold and ntuple_beam_ply.
     A, B uint32 [n, 4], plies [n] the effective depth of every state.  Returns action, plan, score and what the coverage counts."""
@@ -186,7 +186,7 @@ def compose(env, table, A, B, plies, depth, width, gamma=GAMMA, mirror_value=Fal
         after = T.afterstates(env, pa, pb)
         sa, sb = after["states_a"].view(-1, 4), after["states_b"].view(-1, 4)
         if mirror_value:
-            v = _mirror_value(table, _fields(_np(sa).view(np.uint32), _np(sb).view(np.uint32)))
+            v = _mirror_value(table, _fields(_np(sa).view(np.uint32), _np(sb).view(np.uint32)), L=L, M=M)
         else:
             v = _np(T.ntuple_value((sa, sb), dev_table, L, M))
         sa, sb = (_np(x).view(np.uint32).reshape(k, wc, 40, 4) for x in (sa, sb))

@@ -63,7 +63,7 @@ def _extra():
     return R.pack_state(rows, 1, 3, 0, 0, window)
 
 
-def _indices(f, form):
+def _indices(f, form, L=L, M=M):
     return _m().ntuple_indices(f["rows"], f["cur"], L, M, f["lines"], f["moves"], shape=form)
 
 
@@ -89,7 +89,7 @@ def whole(pool, after):
 
 
 # ------------------------------------------------------------------------------------------------ the entries, framed
-def _value(A, B, table, form):
+def _value(A, B, table, form, L=L, M=M):
     """form: a feature form's name, or "3x3": tpl_ntuple_value_shaped with shape 1."""
     n = A.shape[0]
     a, b, t, v = _framed(A, 1), _framed(B, 2), _framed(table, 3), Framed(4 * n, 4)
@@ -102,7 +102,7 @@ def _value(A, B, table, form):
     return v.host().view(np.float32).copy()
 
 
-def _policy(depth, A, B, table, form, gamma=GAMMA, epsilon=0.0, seed=0, step=0):
+def _policy(depth, A, B, table, form, gamma=GAMMA, epsilon=0.0, seed=0, step=0, L=L, M=M, params=PARAMS):
     n = A.shape[0]
     a, b, t = _framed(A, 1), _framed(B, 2), _framed(table, 3)
     sizes = dict(action=1, second=1, score=4, after_a=16, after_b=16, value=4)
@@ -110,7 +110,7 @@ def _policy(depth, A, B, table, form, gamma=GAMMA, epsilon=0.0, seed=0, step=0):
     for f in out.values():
         f.inner().fill_(0xCD)
     p = lambda k: out[k].ptr()
-    head = (a.ptr(), b.ptr(), n, L, M, *PARAMS, gamma, t.ptr(), epsilon, seed, step, p("action"))
+    head = (a.ptr(), b.ptr(), n, L, M, *params, gamma, t.ptr(), epsilon, seed, step, p("action"))
     tail = (p("score"), p("after_a"), p("after_b"), p("value"), FORMS[form], _stream())
     _check(_lib().tpl_ntuple_search_feature(*head, p("second"), *tail) if depth == 2 else _lib().tpl_ntuple_act_feature(*head, *tail))
     for k, f in list(out.items()) + [("a", a), ("b", b), ("table", t)]:
@@ -127,7 +127,7 @@ def _policy(depth, A, B, table, form, gamma=GAMMA, epsilon=0.0, seed=0, step=0):
     return host
 
 
-def _beam(A, B, table, depth, width, form, gamma=GAMMA):
+def _beam(A, B, table, depth, width, form, gamma=GAMMA, L=L, M=M, params=PARAMS):
     n = A.shape[0]
     a, b, t = _framed(A, 1), _framed(B, 2), _framed(table, 3)
     sizes = dict(action=1, plan=depth, score=4, after_a=16, after_b=16)
@@ -135,7 +135,7 @@ def _beam(A, B, table, depth, width, form, gamma=GAMMA):
     for f in out.values():
         f.inner().fill_(0xCD)
     p = lambda k: out[k].ptr()
-    _check(_lib().tpl_ntuple_beam_feature(a.ptr(), b.ptr(), n, L, M, *PARAMS, gamma, t.ptr(), depth, width, p("action"), p("plan"),
+    _check(_lib().tpl_ntuple_beam_feature(a.ptr(), b.ptr(), n, L, M, *params, gamma, t.ptr(), depth, width, p("action"), p("plan"),
                                           p("score"), p("after_a"), p("after_b"), FORMS[form], _stream()))
     for k, f in list(out.items()) + [("a", a), ("b", b), ("table", t)]:
         f.assert_canary((n, depth, width, form, k))
@@ -316,7 +316,7 @@ def env10():
     env.terminate()
 
 
-def _second_ply(env, dev_table, ply, idx):
+def _second_ply(env, dev_table, ply, idx, L=L, M=M):
     """The second ply of the states `idx`: T.afterstates on their 40 n first afterstates -- reward, done and distinct [n, 40, 40] --
     and V of the 1,600 n boards that leaves from T.ntuple_value, which the value tests hold to the mirror on the whole set."""
     n = idx.size
@@ -400,7 +400,7 @@ def test_beam_is_the_reference_composed_ply_by_ply(roots, env10, tables, form, d
 
 
 # ------------------------------------------------------------------------------------------------ UPDATE
-def _update(A, B, head, horizon, start, error, rate, decay, symmetric):
+def _update(A, B, head, horizon, start, error, rate, decay, symmetric, L=L, M=M):
     """tpl_ntuple_update_trace_feature of a host ring (uint32 [slots, n, 4] each) through canary-framed buffers: the table it leaves."""
     slots, n = A.shape[:2]
     a, b, t, e = _framed(A, 1), _framed(B, 2), _framed(start, 3), _framed(error, 4)

@@ -52,7 +52,7 @@ def _fields(A, B):
     return {k: (v if k in ("rows", "window") else v.astype(np.int64)) for k, v in d.items()}
 
 
-def _mirror_value(table, f):
+def _mirror_value(table, f, L=L, M=M):
     return _m().ntuple_value(table, f["rows"], f["cur"], L, M, f["lines"], f["moves"], f["state"])
 
 
@@ -71,7 +71,7 @@ def _random_table(seed, span=1 << 20):
 
 
 # ------------------------------------------------------------------------------------------------ 1. VALUE
-def _value(A, B, table):
+def _value(A, B, table, L=L, M=M):
     n = A.shape[0]
     a, b, t, v = _framed(A, 1), _framed(B, 2), _framed(table, 3), Framed(4 * n, 4)
     v.inner().fill_(0xCD)
@@ -113,9 +113,10 @@ class Expected:
     """What the rule says of tpl_ntuple_act on the pool's states, from the ORACLE's afterstates (Pool): per table, the score of
     every placement; per draw, the action played."""
 
-    def __init__(self, pool):
+    def __init__(self, pool, L=L, M=M):
         f = pool.fields
         self.pool, self.n, self._values = pool, pool.n, {}
+        self.L, self.M = L, M
         self.cur = (f["window"] & np.uint64(7)).astype(np.int64)
         self.nxt = ((f["window"] >> np.uint64(3)) & np.uint64(7)).astype(np.int64)
         self.distinct = _m().canonical_actions(self.cur[:, None], np.arange(40)[None, :]) == np.arange(40)[None, :]
@@ -135,7 +136,7 @@ class Expected:
         key = hash(table.tobytes())
         if key not in self._values:
             p = self.pool
-            v = _m().ntuple_value(table, p.rows.reshape(-1, 20), np.repeat(self.nxt, 40), L, M, p.lines.reshape(-1),
+            v = _m().ntuple_value(table, p.rows.reshape(-1, 20), np.repeat(self.nxt, 40), self.L, self.M, p.lines.reshape(-1),
                                   p.moves.reshape(-1), p.done.reshape(-1))
             self._values[key] = v.reshape(p.n, 40)
         return self._values[key]
@@ -163,7 +164,7 @@ def expected(pool):
     return Expected(pool)
 
 
-def _act(A, B, table, gamma=GAMMA, epsilon=0.0, seed=0, step=0, skip=()):
+def _act(A, B, table, gamma=GAMMA, epsilon=0.0, seed=0, step=0, skip=(), L=L, M=M, params=PARAMS):
     """tpl_ntuple_act of host planes through canary-framed buffers; `skip` names the outputs passed as NULL ("after" = both)."""
     n = A.shape[0]
     a, b, t = _framed(A, 1), _framed(B, 2), _framed(table, 3)
@@ -172,7 +173,7 @@ def _act(A, B, table, gamma=GAMMA, epsilon=0.0, seed=0, step=0, skip=()):
         f.inner().fill_(0xCD)
     given = {k: f for k, f in out.items() if k not in skip and not (k in ("after_a", "after_b") and "after" in skip)}
     p = lambda k: given[k].ptr() if k in given else None
-    _check(_lib().tpl_ntuple_act(a.ptr(), b.ptr(), n, L, M, *PARAMS, gamma, t.ptr(), epsilon, seed, step, p("action"), p("score"),
+    _check(_lib().tpl_ntuple_act(a.ptr(), b.ptr(), n, L, M, *params, gamma, t.ptr(), epsilon, seed, step, p("action"), p("score"),
                                  p("after_a"), p("after_b"), p("value"), _stream()))
     for k, f in list(out.items()) + [("a", a), ("b", b), ("table", t)]:
         f.assert_canary((n, epsilon, skip, k))
@@ -330,7 +331,7 @@ def test_act_explores_uniformly_over_the_distinct_placements_on_the_predicted_dr
 
 
 # ------------------------------------------------------------------------------------------------ 3. UPDATE
-def _update(A, B, start, error, rate, launches=1):
+def _update(A, B, start, error, rate, launches=1, L=L, M=M):
     n = A.shape[0]
     a, b, t, e = _framed(A, 1), _framed(B, 2), _framed(start, 3), _framed(error, 4)
     for _ in range(launches):
@@ -341,7 +342,7 @@ def _update(A, B, start, error, rate, launches=1):
     return t.host().view(np.int32).copy()
 
 
-def _mirror_update(start, f, error, rate):
+def _mirror_update(start, f, error, rate, L=L, M=M):
     return _m().ntuple_update(start.copy(), f["rows"], f["cur"], L, M, f["lines"], f["moves"], f["state"], error, rate)
 
 

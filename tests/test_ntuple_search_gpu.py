@@ -52,7 +52,7 @@ def _outputs(n):
     return out
 
 
-def _search(A, B, table, gamma=GAMMA, epsilon=0.0, seed=0, step=0, skip=(), params=PARAMS):
+def _search(A, B, table, gamma=GAMMA, epsilon=0.0, seed=0, step=0, skip=(), params=PARAMS, L=L, M=M):
     """tpl_ntuple_search of host planes through canary-framed buffers; `skip` names the outputs passed as NULL ("after" = both)."""
     n = A.shape[0]
     a, b, t = _framed(A, 1), _framed(B, 2), _framed(table, 3)
@@ -138,7 +138,7 @@ class Composed:
     """The rule put together from the parent's kernels for the states (A, B): tpl_afterstates, then tpl_ntuple_act (epsilon = 0)
     and tpl_ntuple_value over the 40 n afterstates -- Q and second of every first placement, its afterstate and V of it."""
 
-    def __init__(self, A, B, table, gamma, params=PARAMS):
+    def __init__(self, A, B, table, gamma, params=PARAMS, L=L, M=M):
         n = self.n = A.shape[0]
         a, b = _planes(A, B)
         out_a, out_b = Framed(n * 640, 3), Framed(n * 640, 4)
@@ -151,8 +151,8 @@ class Composed:
         self.done1 = done.host().reshape(n, 40) != 0
         self.distinct = canonical.host().reshape(n, 40) == ARANGE[None, :]
         assert params == PARAMS                                # test_ntuple_gpu's _act plays with them
-        ply = _act(self.A, self.B, table, gamma=gamma, skip=("after", "value"))
-        self.value = _value(self.A, self.B, table).reshape(n, 40)
+        ply = _act(self.A, self.B, table, gamma=gamma, skip=("after", "value"), L=L, M=M)
+        self.value = _value(self.A, self.B, table, L=L, M=M).reshape(n, 40)
         self.running = ((B[:, 1] >> np.uint32(28)) & np.uint32(3)) == 0
         with np.errstate(invalid="ignore", over="ignore"):
             self.Q = np.where(self.done1, r1, r1 + np.float32(gamma) * ply["score"].reshape(n, 40)).astype(np.float32)

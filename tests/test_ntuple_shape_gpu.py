@@ -58,7 +58,7 @@ def _bits(x):
 
 
 # ------------------------------------------------------------------------------------------------ the entries, framed
-def _value3(A, B, table, shape=1):
+def _value3(A, B, table, shape=1, L=L, M=M):
     n = A.shape[0]
     a, b, t, v = _framed(A, 1), _framed(B, 2), _framed(table, 3), Framed(4 * n, 4)
     v.inner().fill_(0xCD)
@@ -69,7 +69,7 @@ def _value3(A, B, table, shape=1):
     return v.host().view(np.float32).copy()
 
 
-def _policy3(depth, A, B, table, gamma=GAMMA, epsilon=0.0, seed=0, step=0, shape=1):
+def _policy3(depth, A, B, table, gamma=GAMMA, epsilon=0.0, seed=0, step=0, shape=1, L=L, M=M):
     """tpl_ntuple_act_shaped (depth 1) or tpl_ntuple_search_shaped (depth 2) of host planes through canary-framed buffers."""
     n = A.shape[0]
     a, b, t = _framed(A, 1), _framed(B, 2), _framed(table, 3)
@@ -98,7 +98,7 @@ def _policy3(depth, A, B, table, gamma=GAMMA, epsilon=0.0, seed=0, step=0, shape
     return host
 
 
-def _trace3(A, B, head, horizon, start, error, rate, decay, symmetric, shape=1, coherence=None, planes=False):
+def _trace3(A, B, head, horizon, start, error, rate, decay, symmetric, shape=1, coherence=None, planes=False, L=L, M=M):
     """tpl_ntuple_update_trace_shaped of a host ring (uint32 [slots, n, 4] each), tpl_ntuple_update_coherent_shaped where a
     coherence buffer is given, tpl_ntuple_update_shaped of planes [n, 4] with planes=True: the table (and the buffer) it leaves."""
     slots, n = (1, A.shape[0]) if planes else A.shape[:2]
@@ -227,7 +227,7 @@ class Composed:
     of tpl_afterstates: Q(a) = r1 + gamma * score'(s_a) and second(a) = action'(s_a), (score', action') the 3 x 3 one-ply policy on
     the afterstate -- held to the numpy rule by the act tests above --, V(s_a) from the numpy mirror."""
 
-    def __init__(self, A, B, table, gamma):
+    def __init__(self, A, B, table, gamma, L=L, M=M):
         n = self.n = A.shape[0]
         a, b = _planes(A, B)
         out_a, out_b = Framed(n * 640, 3), Framed(n * 640, 4)
@@ -239,7 +239,7 @@ class Composed:
         r1 = reward.host().view(np.float32).reshape(n, 40).copy()
         self.done1 = done.host().reshape(n, 40) != 0
         self.distinct = canonical.host().reshape(n, 40) == ARANGE[None, :]
-        ply = _policy3(1, self.A, self.B, table, gamma=gamma)
+        ply = _policy3(1, self.A, self.B, table, gamma=gamma, L=L, M=M)
         f = _fields(self.A, self.B)
         self.value = _m().ntuple_value(table, f["rows"], f["cur"], L, M, f["lines"], f["moves"], f["state"]).reshape(n, 40)
         with np.errstate(invalid="ignore", over="ignore"):

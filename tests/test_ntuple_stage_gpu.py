@@ -69,7 +69,7 @@ def _entry(base, form, staged):
 
 
 # ------------------------------------------------------------------------------------------------ the entries, framed
-def _value(A, B, table, form, staged=True):
+def _value(A, B, table, form, staged=True, L=L, M=M):
     n = A.shape[0]
     a, b, t, v = _framed(A, 1), _framed(B, 2), _framed(table, 3), Framed(4 * n, 4)
     v.inner().fill_(0xCD)
@@ -93,7 +93,7 @@ def _outputs(out, n, depth=None):
     return host
 
 
-def _policy(depth, A, B, table, form, staged=True, gamma=GAMMA, epsilon=0.0, seed=0, step=0):
+def _policy(depth, A, B, table, form, staged=True, gamma=GAMMA, epsilon=0.0, seed=0, step=0, L=L, M=M, params=PARAMS):
     n = A.shape[0]
     a, b, t = _framed(A, 1), _framed(B, 2), _framed(table, 3)
     sizes = dict(action=1, second=1, score=4, after_a=16, after_b=16, value=4)
@@ -102,7 +102,7 @@ def _policy(depth, A, B, table, form, staged=True, gamma=GAMMA, epsilon=0.0, see
         f.inner().fill_(0xCD)
     p = lambda k: out[k].ptr()
     entry, tail = _entry("tpl_ntuple_search" if depth == 2 else "tpl_ntuple_act", form, staged)
-    head = (a.ptr(), b.ptr(), n, L, M, *PARAMS, gamma, t.ptr(), epsilon, seed, step, p("action"))
+    head = (a.ptr(), b.ptr(), n, L, M, *params, gamma, t.ptr(), epsilon, seed, step, p("action"))
     rest = (p("score"), p("after_a"), p("after_b"), p("value"), *tail, _stream())
     _check(entry(*head, p("second"), *rest) if depth == 2 else entry(*head, *rest))
     for k, f in list(out.items()) + [("a", a), ("b", b), ("table", t)]:
@@ -113,7 +113,7 @@ def _policy(depth, A, B, table, form, staged=True, gamma=GAMMA, epsilon=0.0, see
     return _outputs(out, n)
 
 
-def _beam(A, B, table, depth, width, form, staged=True, gamma=GAMMA):
+def _beam(A, B, table, depth, width, form, staged=True, gamma=GAMMA, L=L, M=M, params=PARAMS):
     n = A.shape[0]
     a, b, t = _framed(A, 1), _framed(B, 2), _framed(table, 3)
     sizes = dict(action=1, plan=depth, score=4, after_a=16, after_b=16)
@@ -122,7 +122,7 @@ def _beam(A, B, table, depth, width, form, staged=True, gamma=GAMMA):
         f.inner().fill_(0xCD)
     p = lambda k: out[k].ptr()
     entry, tail = _entry("tpl_ntuple_beam", form, staged)
-    _check(entry(a.ptr(), b.ptr(), n, L, M, *PARAMS, gamma, t.ptr(), depth, width, p("action"), p("plan"), p("score"), p("after_a"),
+    _check(entry(a.ptr(), b.ptr(), n, L, M, *params, gamma, t.ptr(), depth, width, p("action"), p("plan"), p("score"), p("after_a"),
                  p("after_b"), *tail, _stream()))
     for k, f in list(out.items()) + [("a", a), ("b", b), ("table", t)]:
         f.assert_canary((n, depth, width, form, staged, k))
@@ -144,7 +144,7 @@ def _states(pool, n, offset):
     return idx, np.ascontiguousarray(pool.A[idx]), np.ascontiguousarray(pool.B[idx])
 
 
-def _mirror_value(table, f, idx):
+def _mirror_value(table, f, idx, L=L, M=M):
     return _m().ntuple_value(table, f["rows"][idx], f["cur"][idx], L, M, f["lines"][idx], f["moves"][idx], f["state"][idx])
 
 
@@ -203,7 +203,7 @@ def _state_of(B):
     return (B[..., 1] >> np.uint32(28)) & np.uint32(3)
 
 
-def _one_ply(env, dev_table, A, B):
+def _one_ply(env, dev_table, A, B, L=L, M=M):
     """T.afterstates of the states and the staged T.ntuple_value of their afterstates -- each in the block of ITS lines and moves."""
     n = A.shape[0]
     after = T.afterstates(env, _i32(A).to(DEV), _i32(B).to(DEV))
@@ -325,7 +325,7 @@ def test_playing_the_plan_of_a_staged_beam_reaches_its_score(pool, crossed, form
 
 
 # ------------------------------------------------------------------------------------------------ 4. UPDATE
-def _trace(A, B, head, horizon, start, error, rate, decay, symmetric, form, staged=True):
+def _trace(A, B, head, horizon, start, error, rate, decay, symmetric, form, staged=True, L=L, M=M):
     """The trace update of a host ring (uint32 [slots, n, 4] each) through canary-framed buffers: the table it leaves.  Staged: one
     tpl_ntuple_update_trace_staged; plain: tpl_ntuple_update_trace_shaped once per part."""
     slots, n = A.shape[:2]

@@ -62,7 +62,7 @@ def _tail(form):
     return () if form == "sum" else (form,)
 
 
-def _value(A, B, table, form="sum"):
+def _value(A, B, table, form="sum", L=L, M=M):
     n = A.shape[0]
     a, b, t, v = _framed(A, 1), _framed(B, 2), _framed(table, 3), Framed(4 * n, 4)
     v.inner().fill_(0xCD)
@@ -74,7 +74,7 @@ def _value(A, B, table, form="sum"):
     return v.host().view(np.float32).copy()
 
 
-def _policy(depth, A, B, table, form="sum", gamma=GAMMA, epsilon=0.0, seed=0, step=0):
+def _policy(depth, A, B, table, form="sum", gamma=GAMMA, epsilon=0.0, seed=0, step=0, L=L, M=M):
     n = A.shape[0]
     a, b, t = _framed(A, 1), _framed(B, 2), _framed(table, 3)
     sizes = dict(action=1, second=1, score=4, after_a=16, after_b=16, value=4)
@@ -100,7 +100,7 @@ def _policy(depth, A, B, table, form="sum", gamma=GAMMA, epsilon=0.0, seed=0, st
     return host
 
 
-def _beam(A, B, table, depth, width, form="sum", gamma=GAMMA):
+def _beam(A, B, table, depth, width, form="sum", gamma=GAMMA, L=L, M=M):
     n = A.shape[0]
     a, b, t = _framed(A, 1), _framed(B, 2), _framed(table, 3)
     sizes = dict(action=1, plan=depth, score=4, after_a=16, after_b=16)

@@ -182,7 +182,7 @@ def test_4096_copies_of_one_state_at_all_16_ages_where_every_add_collides(pool, 
 
 
 # ------------------------------------------------------------------------------------------------ 2. SYMMETRY
-def _device_value(A, B, table):
+def _device_value(A, B, table, L=L, M=M):
     n = A.shape[0]
     a, b, t, v = _framed(A, 1), _framed(B, 2), _framed(table, 3), Framed(4 * n, 4)
     _check(_lib().tpl_ntuple_value(a.ptr(), b.ptr(), n, L, M, t.ptr(), v.ptr(), _stream()))
