@@ -1039,6 +1039,51 @@ int tpl_ntuple_update_trace_budget(const void* ring_a, const void* ring_b, int64
                                    int32_t symmetric, void* stream);
 int tpl_ntuple_budget_bins(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, uint8_t* bins, void* stream);
 
+/* Per-configuration tallies and the resampled pool (csrc/learn/curriculum.hip).  Which pool entry a board plays is not stored anywhere:
+ * the environment derives it (csrc/tpl_device.h, tetris_piclim.h's tpl_create).  These three entries derive it the same way from the
+ * side and only READ the environment -- the planes (tpl_state_ptrs), the step clocks (tpl_clock_ptr: one uint64 per 32 boards) and the
+ * handle's global_offset, seed and assignment mode, all passed in by the caller: no entry of libtetris_piclim.so is involved.
+ *
+ * THE RULE.  A RUNNING board i made one move in every step of its episode, so the episode began at step  birth = clock[i / 32] -
+ * moves_used(i),  and its entry is that of the episode of global board g = global_offset + i beginning at `birth`, in the buffer its slot
+ * bit names (n_cfg0 entries for bit 0, n_cfg1 for bit 1):
+ *   TPL_ASSIGN_SEQUENTIAL   (g mod n_cfg + low32(birth) mod n_cfg) mod n_cfg
+ *   TPL_ASSIGN_HASH         x = (low32(g) + low32(birth) * 0x9E3779B1) ^ low32((g >> 32 & 0xFFFFFF) * 0x85EBCB)
+ *                               ^ low32((birth >> 32 & 0xFFFFFF) * 0xC2B2AF) ^ (splitmix64(seed) >> 32),  all in 32 bits;
+ *                           entry = (fmix32(x) * n_cfg) >> 32   (fmix32 = the murmur3 finaliser, splitmix64 = tpl_device.h's sm64)
+ * An n_cfg of 0 (no such buffer) gives entry 0.
+ *
+ * tpl_config_index writes index[i] (uint32) for every RUNNING board and slot[i] (the bit) for every board; either output may be NULL,
+ * not both.  A FINISHED, frozen board (auto_reset off) has no recoverable birth -- its clock runs on while moves_used stands still -- so
+ * its index[i] is LEFT AS THE CALLER HAS IT: called on one buffer before every step, a finished board keeps the entry of the episode
+ * it finished.  Refused: a null plane or clock, n outside [1, 2^31), planes not 16-byte or clock not 8-byte aligned, a negative
+ * global_offset, an assign_mode other than 0 / 1, an n_cfg outside [0, 2^32), both n_cfg 0, both outputs null, a misaligned index.
+ *
+ * tpl_pool_tally is called just before tpl_step with the same `action` array (`dtype` TPL_U8 / TPL_I32 / TPL_I64; the low 32 bits are
+ * the action, rot = action / 10 taken mod 4, loc = action mod 10, as tpl_step reads it).  For every RUNNING board it makes the move in
+ * registers (the afterstate kernel's body) and, where the move ends the episode, adds 1 to episodes_s[entry] of the board's buffer s
+ * and, where it ends won, 1 to wins_s[entry] (int32 [n_cfg_s] each).  Frozen boards add nothing; nothing of the environment is
+ * written.  A buffer's pair may be NULL (both or neither; not both buffers'): ends on that buffer are not counted, so one launch serves
+ * a pool in mid-swap.  No-return integer atomics, a wave's adds to one entry combined into one: the bytes do not depend on the order.
+ * Refused: what tpl_config_index refuses for the environment, L outside [1, 250], M outside [1, 254], a null or misaligned action, a
+ * bad dtype, a pair given by halves, no pair at all, a pair for a buffer of 0 entries, misaligned tallies.
+ *
+ * tpl_pool_resample gathers a reweighted pool.  rows uint16 [n_cfg][20], pieces uint8 [n_cfg][M + 1]; prefix int64 [n_cfg], the
+ * INCLUSIVE prefix sums of non-negative int64 weights whose total prefix[n_cfg - 1] is in [1, 2^62) (the caller's to ensure; the
+ * kernel stays inside the buffers whatever they hold).  Draw j < count:
+ *   h_j = mix64(key + 0x9E3779B97F4A7C15 * (j + 1)),  key = mix64(seed + 0x9E3779B97F4A7C15 * (round + 1))   (tpl_replay_sample's stream)
+ *   t_j = floor(h_j * total / 2^64);   source[j] = the first entry e with prefix[e] > t_j
+ * and rows_out[j], pieces_out[j] are the records of entry source[j] (int32 [count]).  An entry of weight 0 is never drawn.  Integers
+ * throughout: the outputs equal _learn_lib.pool_resample byte for byte.  Refused: a null pointer, n_cfg or count outside [1, 2^31), M
+ * outside [1, 254], rows / rows_out / prefix not 8-byte or source not 4-byte aligned, an output that is its input. */
+int tpl_config_index(const void* plane_a, const void* plane_b, const void* clock, int64_t n, int64_t global_offset, uint64_t seed,
+                     int32_t assign_mode, int64_t n_cfg0, int64_t n_cfg1, uint32_t* index, uint8_t* slot, void* stream);
+int tpl_pool_tally(const void* plane_a, const void* plane_b, const void* clock, int64_t n, int32_t L, int32_t M, const void* action,
+                   int32_t dtype, int64_t global_offset, uint64_t seed, int32_t assign_mode, int64_t n_cfg0, int64_t n_cfg1,
+                   int32_t* episodes0, int32_t* wins0, int32_t* episodes1, int32_t* wins1, void* stream);
+int tpl_pool_resample(const void* rows, const void* pieces, int64_t n_cfg, int32_t M, const int64_t* prefix, int64_t count,
+                      uint64_t seed, uint64_t round, void* rows_out, void* pieces_out, int32_t* source, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

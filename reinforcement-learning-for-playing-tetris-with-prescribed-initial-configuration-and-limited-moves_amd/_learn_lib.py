@@ -24,7 +24,7 @@ _UNITS = [os.path.join(_LEARN_CSRC, f) for f in ("replay.hip", "pack.hip", "prio
                                                       "beam.hip", "solve.hip", "ntuple.hip", "ntuple_beam.hip", "heuristic_move.hip",
                                                       "beam_move.hip", "solve_move.hip", "bound.hip", "beam_bound.hip",
                                                       "solve_bound.hip", "beam_move_bound.hip", "solve_move_bound.hip",
-                                                      "exact.hip", "exact_move.hip", "heuristic.hip")]
+                                                      "exact.hip", "exact_move.hip", "curriculum.hip", "heuristic.hip")]
 
 # entry points declared in include/tpl_learn.h (tests check that the .so exports every one of them)
 LEARN_SYMBOLS = [
@@ -48,6 +48,7 @@ LEARN_SYMBOLS = [
     "tpl_ntuple_value_budget", "tpl_ntuple_act_budget", "tpl_ntuple_search_budget", "tpl_ntuple_beam_budget",
     "tpl_ntuple_update_trace_budget", "tpl_ntuple_budget_bins",
     "tpl_placement_exact", "tpl_placement_exact_move",
+    "tpl_config_index", "tpl_pool_tally", "tpl_pool_resample",
 ]
 NSTEP_MAX = 16
 BEAM_MAX_DEPTH, BEAM_MAX_WIDTH = 12, 64
@@ -220,6 +221,11 @@ def lib() -> C.CDLL:
     for name in ("value", "act", "search", "beam", "update_trace"):
         getattr(L, f"tpl_ntuple_{name}_budget").restype = i32
     L.tpl_ntuple_budget_bins.restype = i32
+    # per-configuration tallies and the resampled pool (csrc/learn/curriculum.hip)
+    L.tpl_config_index.argtypes = [vp, vp, vp, i64, i64, u64, i32, i64, i64, vp, vp, vp]
+    L.tpl_pool_tally.argtypes = [vp, vp, vp, i64, i32, i32, vp, i32, i64, u64, i32, i64, i64, vp, vp, vp, vp, vp]
+    L.tpl_pool_resample.argtypes = [vp, vp, i64, i32, vp, i64, u64, u64, vp, vp, vp, vp]
+    L.tpl_config_index.restype = L.tpl_pool_tally.restype = L.tpl_pool_resample.restype = i32
     for name in ("tpl_replay_push", "tpl_replay_sample", "tpl_learn_pack", "tpl_priority_init", "tpl_priority_push",
                  "tpl_priority_update", "tpl_replay_sample_prioritized", "tpl_replay_sample_nstep", "tpl_replay_sample_mirror",
                  "tpl_mirror_states", "tpl_afterstates", "tpl_placement_features", "tpl_placement_act",
@@ -1603,3 +1609,91 @@ def pack_policy_device(params, kind: str = "split", out=None):
     stream = torch._C._cuda_getCurrentRawStream(dev.index)
     check(L.tpl_learn_pack(IMAGE_KINDS[kind], *[t.data_ptr() for t in params], out.data_ptr(), stream))
     return out
+
+
+# ------------------------------------------------------------------------------------------------ tallies and the resampled pool
+# numpy mirrors of csrc/learn/curriculum.hip, written from include/tpl_learn.h's rule ("Per-configuration tallies and the resampled
+# pool") and the interchange form of a pool (rows [n_cfg, 20], pieces [n_cfg, M + 1]).
+def _mulhi64(a, b):
+    """floor(a * b / 2^64) of uint64 arrays, from 32-bit halves (exact)."""
+    a, b = np.asarray(a, dtype=np.uint64), np.asarray(b, dtype=np.uint64)
+    s32 = np.uint64(32)
+    with np.errstate(over="ignore"):
+        a_hi, a_lo, b_hi, b_lo = a >> s32, a & _M32, b >> s32, b & _M32
+        mid = a_hi * b_lo + ((a_lo * b_lo) >> s32)              # below 2^64: (2^32 - 1)^2 + 2^32 - 1
+        mid2 = a_lo * b_hi + (mid & _M32)
+        return a_hi * b_hi + (mid >> s32) + (mid2 >> s32)
+
+
+def _fmix32(h):
+    h = np.asarray(h, dtype=np.uint64) & _M32
+    h ^= h >> np.uint64(16)
+    h = (h * np.uint64(0x85EBCA6B)) & _M32
+    h ^= h >> np.uint64(13)
+    h = (h * np.uint64(0xC2B2AE35)) & _M32
+    return h ^ (h >> np.uint64(16))
+
+
+def assign_entries(boards, births, seed: int, global_offset: int, n_cfg: int, mode: int) -> np.ndarray:
+    """The pool entry of the episode of board `boards[k]` (local index; global index global_offset + board) that begins at step
+    `births[k]`, in a buffer of n_cfg entries: int64, broadcast over the two arrays.  mode 0 = hash, 1 = sequential."""
+    if mode not in (0, 1):
+        raise ValueError("mode must be 0 (hash) or 1 (sequential)")
+    if not 1 <= int(n_cfg) < (1 << 32):
+        raise ValueError("n_cfg must be in [1, 2^32)")
+    if global_offset < 0:
+        raise ValueError("global_offset must not be negative")
+    g = np.asarray(boards, dtype=np.uint64) + np.uint64(global_offset)
+    birth = np.asarray(births, dtype=np.uint64)
+    n = np.uint64(n_cfg)
+    if mode == 1:
+        return ((g % n + (birth & _M32) % n) % n).astype(np.int64)
+    m24 = np.uint64(0xFFFFFF)
+    with np.errstate(over="ignore"):
+        seed_mix = _mix64(np.uint64(seed % (1 << 64)) + _GOLDEN) >> np.uint64(32)          # splitmix64(seed) >> 32
+        x = ((g & _M32) + (birth & _M32) * np.uint64(0x9E3779B1)) & _M32
+        x = x ^ ((((g >> np.uint64(32)) & m24) * np.uint64(0x85EBCB)) & _M32)
+        x = x ^ ((((birth >> np.uint64(32)) & m24) * np.uint64(0xC2B2AF)) & _M32) ^ seed_mix
+        return ((_fmix32(x) * n) >> np.uint64(32)).astype(np.int64)
+
+
+def check_pool_weights(weights) -> int:
+    """The total of int64 weights [n_cfg] that tpl_pool_resample's prefix sums may be made of: all non-negative, total in [1, 2^62)."""
+    w = np.asarray(weights)
+    if w.dtype != np.int64 or w.ndim != 1 or w.shape[0] < 1:
+        raise ValueError("weights must be int64 [n_cfg], n_cfg >= 1")
+    if int(w.min()) < 0:
+        raise ValueError("weights must not be negative")
+    total = int(w.astype(object).sum())                      # Python integers: the sum of int64 values may not fit one
+    if not 1 <= total < (1 << 62):
+        raise ValueError(f"the weights' total must be in [1, 2^62), got {total}")
+    return total
+
+
+def curriculum_weights(episodes, wins, floor: int = 1, gain: int = 8) -> np.ndarray:
+    """floor + gain * (episodes - wins) as int64: the losses so far, and a floor that keeps every configuration alive."""
+    for name, v in (("floor", floor), ("gain", gain)):
+        if isinstance(v, bool) or int(v) != v or int(v) < 0:
+            raise ValueError(f"{name} must be a non-negative integer, got {v!r}")
+    e, w = np.asarray(episodes), np.asarray(wins)
+    if e.shape != w.shape or e.ndim != 1 or e.dtype.kind not in "iu" or w.dtype.kind not in "iu":
+        raise ValueError("episodes and wins must be integer arrays of one shape [n_cfg]")
+    return np.int64(floor) + np.int64(gain) * (e.astype(np.int64) - w.astype(np.int64))
+
+
+def pool_resample(rows, pieces, weights, count: int, seed: int = 0, round: int = 0):
+    """tpl_pool_resample on the host: (rows' [count, 20], pieces' [count, M + 1], source int32 [count]).  Draw j takes the target
+    t_j = floor(h_j * total / 2^64), h = _draw_hashes(seed, round, count), and the first entry whose inclusive prefix sum is above it."""
+    rows, pieces = np.asarray(rows), np.asarray(pieces)
+    total = check_pool_weights(weights)
+    n_cfg = np.asarray(weights).shape[0]
+    if rows.ndim != 2 or rows.shape != (n_cfg, 20) or rows.dtype.itemsize != 2 or rows.dtype.kind not in "iu":
+        raise ValueError(f"rows must be 16-bit integers [{n_cfg}, 20]")
+    if pieces.ndim != 2 or pieces.shape[0] != n_cfg or pieces.dtype != np.uint8 or not 2 <= pieces.shape[1] <= 255:
+        raise ValueError(f"pieces must be uint8 [{n_cfg}, M + 1]")
+    if isinstance(count, bool) or int(count) != count or not 1 <= int(count) < (1 << 31):
+        raise ValueError("count must be in [1, 2^31)")
+    prefix = np.cumsum(np.asarray(weights, dtype=np.int64)).astype(np.uint64)
+    target = _mulhi64(_draw_hashes(seed, round, int(count)), np.uint64(total))
+    source = np.searchsorted(prefix, target, side="right").astype(np.int32)
+    return rows[source].copy(), pieces[source].copy(), source

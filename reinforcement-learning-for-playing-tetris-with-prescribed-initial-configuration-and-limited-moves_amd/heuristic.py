@@ -278,7 +278,7 @@ def _win_count_reward(env) -> None:
 
 @torch.no_grad()
 def evaluate_heuristic(env, weights, boards_per_member: Optional[int], steps: int, policy=None, depth: int = 1,
-                       width: Optional[int] = None, bound: bool = False, spare_weight: float = 0.0) -> dict:
+                       width: Optional[int] = None, bound: bool = False, spare_weight: float = 0.0, per_config: bool = False) -> dict:
     """Play `steps` steps of the population `weights` ([P, 12] or [12]) on `env` from a full reset: an auto-reset environment
     with a configuration pool and reward parameters (0, 1, 0), so that the summed reward is the number of wins.  Member p plays
     boards [p * boards_per_member, (p + 1) * boards_per_member).  Returns episodes and wins as int64 numpy arrays [P] and
@@ -286,7 +286,11 @@ def evaluate_heuristic(env, weights, boards_per_member: Optional[int], steps: in
     HeuristicPolicy of this environment to reuse (its weights are replaced).  `depth`: 1 or 2 plies (HeuristicPolicy's); a
     `policy` that is passed must have been built with it.  `width`: None, or a beam width -- then a BeamPolicy(depth, width)
     plays, depth may be 1 .. 12, and a `policy` that is passed must be a BeamPolicy of that depth and width.  `bound` and
-    `spare_weight` are BeamPolicy's and need a `width`; a `policy` that is passed must have been built with them."""
+    `spare_weight` are BeamPolicy's and need a `width`; a `policy` that is passed must have been built with them.
+    per_config=True: the dict gains episodes_by_config and wins_by_config, int32 device tensors over the loaded pool summed over the
+    members (a PoolTally observed before every step); the three other keys are what they are without it."""
+    if not isinstance(per_config, bool):
+        raise ValueError("per_config must be True or False")
     kind, depth, width = _player(depth, width)
     bound, spare_weight = _player_bound(width, bound, spare_weight)
     if policy is not None:
@@ -318,15 +322,25 @@ def evaluate_heuristic(env, weights, boards_per_member: Optional[int], steps: in
     episodes = torch.zeros(n, dtype=torch.int32, device=d)
     wins = torch.zeros(n, dtype=torch.float32, device=d)     # a board wins fewer than 2^24 times: the float sum is exact
     env.reset()
+    tally = None
+    if per_config:
+        from .curriculum import PoolTally
+        tally = PoolTally(env)
     for _ in range(int(steps)):
-        env.step_into(policy.act(out=action), reward, done)
+        policy.act(out=action)
+        if tally is not None:
+            tally.observe(action)
+        env.step_into(action, reward, done)
         episodes += done
         wins += reward
     member = torch.arange(n, device=d) // policy.boards_per_member
     zeros = torch.zeros(policy.members, dtype=torch.int64, device=d)
     ep = zeros.index_add(0, member, episodes.to(torch.int64)).cpu().numpy()
     wn = zeros.index_add(0, member, wins.to(torch.int64)).cpu().numpy()
-    return dict(episodes=ep, wins=wn, win_rate=wn / np.maximum(ep, 1))
+    result = dict(episodes=ep, wins=wn, win_rate=wn / np.maximum(ep, 1))
+    if tally is not None:
+        result.update(episodes_by_config=tally.episodes, wins_by_config=tally.wins)
+    return result
 
 
 def tune_heuristic(L: int, M: int, config_pool, population: int = 64, boards_per_member: int = 4096, steps: Optional[int] = None,

@@ -753,10 +753,18 @@ class NTupleLearner:
         self._ring[1][:, :, 1] = _FINISHED_B_Y
 
     @torch.no_grad()
-    def train(self, steps: int) -> int:
+    def train(self, steps: int, curriculum=None, refresh_every: int = 0) -> int:
         """`steps` steps of the loop above from the environment as it stands.  Whatever else moves the environment between two
-        calls must be followed by forget(); evaluate() does it itself.  Returns the steps trained so far."""
+        calls must be followed by forget(); evaluate() does it itself.  Returns the steps trained so far.
+        curriculum (None by default, which leaves the loop and the table bytes as they are; a PoolCurriculum of this environment):
+        its observe(action) is called before every step -- one more launch, which only reads the environment -- and, with
+        refresh_every > 0, its refresh() whenever the steps trained so far reach a multiple of refresh_every."""
         steps = _count("steps", steps, 1)
+        refresh_every = _count("refresh_every", refresh_every)
+        if curriculum is not None and getattr(curriculum, "env", None) is not self.env:
+            raise ValueError("curriculum belongs to another environment")
+        if curriculum is None and refresh_every:
+            raise ValueError("refresh_every needs a curriculum")
         env, n, lib = self.env, self.env.num_envs, _learn_lib.lib()
         stream = torch._C._cuda_getCurrentRawStream(env.device.index)
         ring_a, ring_b = self._ring[0].data_ptr(), self._ring[1].data_ptr()
@@ -804,20 +812,28 @@ class NTupleLearner:
             torch.sub(self._score, self._kept_value, out=self._error)
             for update in updates:
                 check(update(self._head))
+            if curriculum is not None:
+                curriculum.observe(self._action)
             env.step_into(self._action, self._reward, self._done)
             self._head = (self._head + 1) % self.slots
             self.steps += 1
+            if refresh_every and self.steps % refresh_every == 0:
+                curriculum.refresh()
         return self.steps
 
     @torch.no_grad()
-    def evaluate(self, steps: int, depth: Optional[int] = None, width: Optional[int] = None, bound: Optional[bool] = None) -> dict:
+    def evaluate(self, steps: int, depth: Optional[int] = None, width: Optional[int] = None, bound: Optional[bool] = None,
+                 per_config: bool = False) -> dict:
         """Play `steps` greedy steps from a full reset and count: episodes (the steps' done flags), wins (the afterstates of the
         moves played whose state is "won": every reward parameter counts the same wins) and win_rate = wins / max(episodes, 1).
         depth: how deep the greedy policy searches -- None: the learner's own; 1 or 2 plays the table as it stands at that depth.
         width: None, or a beam width -- then NTupleBeamPolicy(depth, width) plays the table, `depth` must be given and may be
         1 .. 11.  bound: None -- the learner's own -- or whether the policy that plays prunes dead boards (a budget table only).
         The tallies stay on the device, with one sync at the end.  Training goes on from the boards this leaves, with
-        nothing kept."""
+        nothing kept.  per_config=True: the dict gains episodes_by_config and wins_by_config, int32 device tensors over the loaded
+        pool (a PoolTally observed before every step); the three other keys are what they are without it."""
+        if not isinstance(per_config, bool):
+            raise ValueError("per_config must be True or False")
         steps = _count("steps", steps, 1)
         env, d = self.env, self.env.device
         greedy = self.greedy
@@ -834,10 +850,20 @@ class NTupleLearner:
         episodes = torch.zeros(env.num_envs, dtype=torch.int32, device=d)
         wins = torch.zeros(env.num_envs, dtype=torch.int32, device=d)
         env.reset()
+        tally = None
+        if per_config:
+            from .curriculum import PoolTally
+            tally = PoolTally(env)
         for _ in range(steps):
-            env.step_into(act(), self._reward, self._done)
+            action = act()
+            if tally is not None:
+                tally.observe(action)
+            env.step_into(action, self._reward, self._done)
             episodes += self._done
             wins += ((self._next[1][:, 1] >> 28) & 3) == _STATE_WON          # an auto-reset board runs whenever it is asked to act
         self.forget()
         ep, wn = int(episodes.sum(dtype=torch.int64)), int(wins.sum(dtype=torch.int64))
-        return dict(episodes=ep, wins=wn, win_rate=wn / max(ep, 1))
+        result = dict(episodes=ep, wins=wn, win_rate=wn / max(ep, 1))
+        if tally is not None:
+            result.update(episodes_by_config=tally.episodes, wins_by_config=tally.wins)
+        return result
