@@ -159,7 +159,6 @@ __global__ __launch_bounds__(kThreads) void step_kernel(const StepArgs p) {
     float reward[kBpl];
     uint32_t n_clear[kBpl];
     bool done[kBpl], reload[kBpl];
-    bool finished = false;
 #pragma unroll
     for (int k = 0; k < kBpl; ++k) {
         reward[k] = 0.0f;
@@ -194,7 +193,6 @@ __global__ __launch_bounds__(kThreads) void step_kernel(const StepArgs p) {
         done[k] = s.state != ST_RUNNING;
         if (done[k]) {
             // adds of a constant collapse to one popcount per wave; the line sum is rarely non-zero
-            finished = true;
             atomicAdd(&s_stat[0], 1u);
             if (s.lines) atomicAdd(&s_stat[1], s.lines);
             if (s.state == ST_WON) atomicAdd(&s_stat[2], 1u);
@@ -299,8 +297,12 @@ __global__ __launch_bounds__(kThreads) void step_kernel(const StepArgs p) {
         }
         if (count > 0) obs::store_span<Obs>(rows, lane, count, wave_base, lines_left, (Obs*)p.obs);
     }
-    // per-block statistics of the episodes that finished in this step -> one sharded 64-bit atomic per counter
-    if (__syncthreads_or(finished ? 1 : 0)) {
+    // per-block statistics of the episodes that finished in this step -> one sharded 64-bit atomic per counter.  s_stat[0]
+    // counts those episodes, so it says whether any lane of the block finished one: a plain barrier and that word, where
+    // __syncthreads_or(finished) cost every wave a cross-lane reduction, 256 bytes of LDS and three barriers
+    // (0.12 us on the launch at 2^20 boards, profiles/r08_step)
+    __syncthreads();
+    if (s_stat[0] != 0) {
         if (threadIdx.x < 4) {
             const uint32_t v = s_stat[threadIdx.x];
             if (v) atomicAdd(&p.stats[(size_t)(blockIdx.x % kStatShards) * kStatStride + threadIdx.x],
