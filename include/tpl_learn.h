@@ -1039,6 +1039,55 @@ int tpl_ntuple_update_trace_budget(const void* ring_a, const void* ring_b, int64
                                    int32_t symmetric, void* stream);
 int tpl_ntuple_budget_bins(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, uint8_t* bins, void* stream);
 
+/* The exact depth-first solver with its children ordered by an n-tuple table (csrc/learn/ntuple_exact.hip).  tpl_ntuple_exact IS
+ * tpl_placement_exact WITH ONE THING REPLACED: the value that orders a node's children.  Everything else is that search's, word for
+ * word: the iterations at budget B from bound = need(root) to M (shortest = 1) or at M alone (shortest = 0); the children of a node --
+ * the distinct placements of pieces[d] & 7 in ascending b, each made by move_board in the game (L, B), a child left running and dead
+ * under (L, B) turned LOST at the limit (the bounded form, change 1); the stop at the first ply with a won child, taking the first won
+ * child in the order; the descent into the running children in the order; nodes, the max_nodes cap checked before every expansion,
+ * proved, solved, solution_len, actions and bound; and the case bound > M, in which there is no iteration.
+ *
+ * THE VALUE of the child made at depth d (the node has made d moves, the child d + 1) is what the one-ply n-tuple policy with the
+ * dead-board prune scores a first move with, in the game (L, B) OF THE CURRENT ITERATION: with n the rows the move cleared and `state`
+ * the child's state after the bounded form's change 1,
+ *   reward = the reward rule (tpl_afterstates) on (r_line, r_win, r_lose, n, state)
+ *   value  = reward + gamma * V     if the child runs      (one rounded multiply, one rounded add, contraction off)
+ *   value  = reward                 otherwise
+ *   V      = the value of `table` on the child's board with pieces[d + 1] & 7 as the falling piece, its own lines and moves, under
+ *            (L, B) -- the sum exact in 64 bits, ONE rounding, the scaling by 2^-16 exact, as every n-tuple value here.
+ * pieces[d + 1] exists: d + 1 <= M and a list has M + 1 entries.  V IS READ AT B, NOT AT M: the counter index and, under a budget
+ * table, spare = 4 (B - moves) - cells are taken under the iteration's budget, so an iteration at the exact budget reads the low-spare
+ * bins that a table trained on a tight pool has filled.  The clamps of the tables -- min(phi, 255), sbin, the 16 x 64 counters -- are
+ * part of the rule, so no state addresses an entry outside the buffer.  The children are ordered by (value descending, b ascending);
+ * -0 and +0 tie.
+ *
+ * THE TABLE is one of the four plain forms, told apart by `entries`: TPL_NTUPLE_ENTRIES ("2x4"), TPL_NTUPLE_ENTRIES_3X3 ("3x3"),
+ * TPL_NTUPLE_ENTRIES_FEAT ("feat") or TPL_NTUPLE_ENTRIES_BUDGET ("feat+spare").  Any other count -- a sum table's and a staged
+ * table's among them -- is refused with a message that names the four.
+ *
+ * Two consequences, on which the tests rest:
+ *   1. UNDER proved = 1, solved, bound and (with shortest = 1) solution_len ARE INDEPENDENT OF THE TABLE and of the reward and gamma,
+ *      and equal tpl_placement_exact's under any weights: a finished search has visited every running board of its budgets or met a
+ *      win at the first budget that has one, in whatever order.
+ *   2. For a configuration PROVED UNWINNABLE, nodes is independent of the order too: every running board of every budget is expanded
+ *      once, whatever comes first.
+ * What the table decides is how many nodes a WIN takes -- how soon the first budget that has one meets it -- and so how many proofs fit
+ * in max_nodes.  WITH proved = 0 NOTHING IS PROVED, as there.  The result is a function of the inputs alone; nothing is written but
+ * the outputs.
+ *
+ * Four kernels, one per form, of tpl_placement_exact's frame: ONE CONFIGURATION PER WAVEFRONT, lanes 0 .. 33 a child each, the order
+ * from 64-bit keys ranked across the wave, the stack -- a record of 80 bytes a depth, without a carry -- in LDS sized by M.  The table
+ * is read from global memory: eleven gathers a running child under "feat+spare", ten under "feat", the non-empty windows and the
+ * counter under the window forms.  rows i16 [n][20], pieces u8 [n][M + 1] and table i32 [entries] are read; solved u8 [n], proved
+ * u8 [n], solution_len i32 [n], actions u8 [n][M], bound i32 [n] and nodes u32 [n] are each written in full.
+ * Refused before any HIP call: an `entries` that is none of the four, first; everything tpl_placement_exact refuses of the arguments
+ * the two share (a NULL rows, pieces, solved, proved, solution_len, actions, bound or nodes, n < 1, n >= 2^31, L outside [1, 250] or M
+ * outside [1, 254], max_nodes outside [1, TPL_EXACT_MAX_NODES], shortest other than 0 or 1, rows not 2-byte aligned, solution_len,
+ * bound or nodes not 4-byte aligned); a NULL table, a table not 4-byte aligned; an r_line, r_win, r_lose or gamma that is not finite. */
+int tpl_ntuple_exact(const int16_t* rows, const uint8_t* pieces, int64_t n, int32_t L, int32_t M, const int32_t* table, int64_t entries,
+                     float r_line, float r_win, float r_lose, float gamma, int32_t max_nodes, int32_t shortest, uint8_t* solved,
+                     uint8_t* proved, int32_t* solution_len, uint8_t* actions, int32_t* bound, uint32_t* nodes, void* stream);
+
 /* Per-configuration tallies and the resampled pool (csrc/learn/curriculum.hip).  Which pool entry a board plays is not stored anywhere:
  * the environment derives it (csrc/tpl_device.h, tetris_piclim.h's tpl_create).  These three entries derive it the same way from the
  * side and only READ the environment -- the planes (tpl_state_ptrs), the step clocks (tpl_clock_ptr: one uint64 per 32 boards) and the

@@ -24,7 +24,7 @@ _UNITS = [os.path.join(_LEARN_CSRC, f) for f in ("replay.hip", "pack.hip", "prio
                                                       "beam.hip", "solve.hip", "ntuple.hip", "ntuple_beam.hip", "heuristic_move.hip",
                                                       "beam_move.hip", "solve_move.hip", "bound.hip", "beam_bound.hip",
                                                       "solve_bound.hip", "beam_move_bound.hip", "solve_move_bound.hip",
-                                                      "exact.hip", "exact_move.hip", "curriculum.hip", "heuristic.hip")]
+                                                      "exact.hip", "exact_move.hip", "ntuple_exact.hip", "curriculum.hip", "heuristic.hip")]
 
 # entry points declared in include/tpl_learn.h (tests check that the .so exports every one of them)
 LEARN_SYMBOLS = [
@@ -47,7 +47,7 @@ LEARN_SYMBOLS = [
     "tpl_placement_beam_bound", "tpl_placement_beam_move_bound",
     "tpl_ntuple_value_budget", "tpl_ntuple_act_budget", "tpl_ntuple_search_budget", "tpl_ntuple_beam_budget",
     "tpl_ntuple_update_trace_budget", "tpl_ntuple_budget_bins",
-    "tpl_placement_exact", "tpl_placement_exact_move",
+    "tpl_placement_exact", "tpl_placement_exact_move", "tpl_ntuple_exact",
     "tpl_config_index", "tpl_pool_tally", "tpl_pool_resample",
 ]
 NSTEP_MAX = 16
@@ -221,6 +221,9 @@ def lib() -> C.CDLL:
     for name in ("value", "act", "search", "beam", "update_trace"):
         getattr(L, f"tpl_ntuple_{name}_budget").restype = i32
     L.tpl_ntuple_budget_bins.restype = i32
+    # the table-ordered exact search: the table and its entry count for the weights, the reward and gamma for spare_weight
+    L.tpl_ntuple_exact.argtypes = [vp, vp, i64, i32, i32, vp, i64, f32, f32, f32, f32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.tpl_ntuple_exact.restype = i32
     # per-configuration tallies and the resampled pool (csrc/learn/curriculum.hip)
     L.tpl_config_index.argtypes = [vp, vp, vp, i64, i64, u64, i32, i64, i64, vp, vp, vp]
     L.tpl_pool_tally.argtypes = [vp, vp, vp, i64, i32, i32, vp, i32, i64, u64, i32, i64, i64, vp, vp, vp, vp, vp]
@@ -1281,6 +1284,122 @@ def ntuple_value(table, rows, piece, L: int, M: int, lines, moves, state) -> np.
     total = np.where(used, table[index].astype(np.int64), 0).sum(axis=1)
     running = np.broadcast_to(np.asarray(state), total.shape) == 0
     return np.where(running, total.astype(np.float32) * np.float32(2.0 ** -16), np.float32(0.0)).astype(np.float32)
+
+
+# The rule of tpl_ntuple_exact (include/tpl_learn.h) on the host: placement_exact's search with the children valued by a table, from
+# the ROW form -- host_moves, move_bound and ntuple_value above.  The device ranks keys across a wave over packed boards in LDS and
+# gathers from column words (csrc/learn/ntuple_exact.hip) -- the two share nothing.
+NTUPLE_EXACT_FORMS = ("2x4", "3x3", "feat", "feat+spare")
+
+
+def _ntuple_exact_table(table) -> np.ndarray:
+    """A table of one of the four plain forms tpl_ntuple_exact reads; a sum or a staged table, or anything else, is refused."""
+    counts = {ntuple_entries_of(name): name for name in NTUPLE_EXACT_FORMS}
+    if not isinstance(table, np.ndarray) or table.dtype != np.int32 or table.ndim != 1 or table.shape[0] not in counts:
+        sizes = ", ".join(f"{k} ({v!r})" for k, v in counts.items())
+        raise ValueError(f"table must be an int32 array of {sizes} entries, one of the four plain forms: a sum or a staged table orders "
+                         "no search")
+    return table
+
+
+def ntuple_exact(rows, pieces, L: int, M: int, table, max_nodes: int, shortest: bool = True, gamma: float = 1.0,
+                 reward=(1.0, 0.0, 0.0)):
+    """The rule of tpl_ntuple_exact (include/tpl_learn.h) for n configurations: placement_exact's arguments with a table (int32, one of
+    NTUPLE_EXACT_FORMS by its entry count) for the weights and a finite gamma and reward = (r_line, r_win, r_lose) for spare_weight.  The
+    search is placement_exact's; the child made at depth d is worth reward, or reward + gamma * V where it runs, V being ntuple_value of
+    its board with pieces[d + 1] as the falling piece in the game (L, B) of the iteration -- float32 operations, each rounded once.
+    Returns placement_exact's six arrays.  The configurations are searched in step, as there."""
+    L, M = int(L), int(M)
+    if not (1 <= L <= 250 and 1 <= M <= SOLVE_MAX_MOVES):
+        raise ValueError(f"L and M must be in [1, 250] and [1, {SOLVE_MAX_MOVES}]")
+    if isinstance(max_nodes, bool) or not isinstance(max_nodes, (int, np.integer)) or not 1 <= int(max_nodes) <= EXACT_MAX_NODES:
+        raise ValueError(f"max_nodes must be an integer in [1, {EXACT_MAX_NODES}]")
+    max_nodes = int(max_nodes)
+    if not isinstance(shortest, (bool, np.bool_)):
+        raise ValueError("shortest must be True or False")
+    rows = np.asarray(rows)
+    rows = (rows.view(np.uint16) if rows.dtype == np.int16 else rows.astype(np.uint16)).reshape(-1, 20)
+    n = rows.shape[0]
+    pieces = np.asarray(pieces).astype(np.int64) & 7
+    if n < 1 or pieces.shape != (n, M + 1):
+        raise ValueError(f"rows must be [n, 20] and pieces [n, {M + 1}] with n >= 1")
+    table = _ntuple_exact_table(table)
+    try:
+        with np.errstate(over="ignore"):
+            g = np.float32(gamma)
+            r_line, r_win, r_lose = (np.float32(v) for v in reward)
+    except (TypeError, ValueError):
+        raise ValueError("gamma must be a number and reward three numbers (r_line, r_win, r_lose)") from None
+    if not all(np.isfinite(v) for v in (g, r_line, r_win, r_lose)):
+        raise ValueError("gamma and reward must be finite (in float32)")
+    bound = move_bound(rows, L, M, 0, 0, STATE_RUNNING)["need"].astype(np.int32)
+    placements = [np.flatnonzero(canonical_actions(p, np.arange(NUM_ACTIONS)) == np.arange(NUM_ACTIONS)) for p in range(8)]
+    solved, proved, length = np.zeros(n, np.uint8), np.ones(n, np.uint8), np.zeros(n, np.int32)
+    actions, nodes = np.full((n, M), NO_SECOND, np.uint8), np.zeros(n, np.uint32)
+
+    def root(s):
+        return dict(rows=rows[s], lines=0, moves=0, kids=None, at=0)
+
+    # placement_exact's stacks: a frame's kids are its running children in the order of the descent, `at` the next of them
+    budget = {s: int(bound[s]) if shortest else M for s in range(n) if bound[s] <= M}
+    stacks = {s: [root(s)] for s in budget}
+    while stacks:
+        for s in [s for s in stacks if nodes[s] == max_nodes]:  # the cap: nothing is proved, nothing is reported
+            proved[s] = 0
+            del stacks[s]
+        if not stacks:
+            break
+        todo = sorted(stacks)
+        nodes[todo] += 1
+        found = {}
+        for B in sorted({budget[s] for s in todo}):             # the game (L, B): one batch per budget
+            group = [s for s in todo if budget[s] == B]
+            tops = [stacks[s][-1] for s in group]
+            depth = [len(stacks[s]) - 1 for s in group]
+            place = [placements[pieces[s, d]] for s, d in zip(group, depth)]
+            sizes = [b.size for b in place]
+            b = np.concatenate(place)
+            rep = lambda key: np.repeat(np.array([t[key] for t in tops]), sizes, axis=0)
+            piece = np.repeat([pieces[s, d] for s, d in zip(group, depth)], sizes)
+            nxt = np.repeat([pieces[s, d + 1] for s, d in zip(group, depth)], sizes)
+            r2, cleared, l2, m2, s2 = host_moves(rep("rows"), piece, b // 10, b % 10, L, B, rep("lines"), rep("moves"))
+            s2 = np.where(move_bound(r2, L, B, l2, m2, s2)["dead"], STATE_LOST_LIMIT, s2)
+            with np.errstate(over="ignore", invalid="ignore"):
+                r = r_line * cleared.astype(np.float32)
+                r = np.where(s2 == STATE_WON, r + r_win, r)
+                r = np.where(s2 >= STATE_LOST_LIMIT, r + r_lose, r).astype(np.float32)
+                v = ntuple_value(table, r2, nxt, L, B, l2, m2, s2)
+                value = np.where(s2 == STATE_RUNNING, r + g * v, r).astype(np.float32)
+            lo = 0
+            for s, size in zip(group, sizes):
+                found[s] = (b[lo:lo + size], value[lo:lo + size], s2[lo:lo + size], r2[lo:lo + size], l2[lo:lo + size], m2[lo:lo + size])
+                lo += size
+        for s in todo:
+            b, value, state, c_rows, c_lines, c_moves = found[s]
+            stack = stacks[s]
+            order = np.argsort(-(value + np.float32(0.0)), kind="stable")
+            won = order[state[order] == STATE_WON]
+            if won.size:                                        # a win at this depth + 1: the path to here, then the won child
+                path = [f["kids"][f["at"] - 1][0] for f in stack[:-1]] + [int(b[won[0]])]
+                solved[s], length[s] = 1, len(path)
+                actions[s, :len(path)] = path
+                del stacks[s]
+                continue
+            run = order[state[order] == STATE_RUNNING]
+            stack[-1]["kids"] = [(int(b[k]), c_rows[k], int(c_lines[k]), int(c_moves[k])) for k in run]
+            while stack and stack[-1]["at"] == len(stack[-1]["kids"]):
+                stack.pop()                                     # used up: back to the parent
+            if stack:
+                top = stack[-1]
+                _, k_rows, k_lines, k_moves = top["kids"][top["at"]]
+                top["at"] += 1
+                stack.append(dict(rows=k_rows, lines=k_lines, moves=k_moves, kids=None, at=0))
+            elif shortest and budget[s] < M:                    # searched out at this budget: the next one
+                budget[s] += 1
+                stack.append(root(s))
+            else:                                               # searched out: no sequence of placements wins within M moves
+                del stacks[s]
+    return solved, proved, length, actions, bound, nodes
 
 
 def ntuple_steps(error, rate) -> np.ndarray:

@@ -13,7 +13,9 @@ and `complete`, under which `solved = False` IS a proof that there is no win and
 
 `prove_configs` is the search that has no width to cut with: a depth-first search of the same game (tpl_placement_exact;
 csrc/learn/exact.hip), one wavefront per configuration, which within the move bound's prune visits every running board or stops at a
-node budget and says so (`proved`).
+node budget and says so (`proved`).  Its weights do one thing, they order a node's children; `ntuple_prove_configs` is the same search
+with that order taken from an n-tuple table (tpl_ntuple_exact; csrc/learn/ntuple_exact.hip): a child is worth what the one-ply table
+policy scores a move with, read at the budget of the iteration.  Verdicts do not depend on the order; the nodes a proof takes do.
 """
 from __future__ import annotations
 
@@ -21,7 +23,7 @@ import numpy as np
 
 from ._learn_lib import BEAM_MAX_WIDTH, EXACT_MAX_NODES, NUM_FEATURES, NUM_MOVE_FEATURES, SOLVE_MAX_MOVES
 
-__all__ = ["CLASSICAL_WEIGHTS", "solve_configs", "prove_configs", "tighten_pool", "config_bound"]
+__all__ = ["CLASSICAL_WEIGHTS", "solve_configs", "prove_configs", "ntuple_prove_configs", "tighten_pool", "config_bound"]
 
 # cleared, won, lost, holes, aggregate height, max height, bumpiness, row and column transitions, wells, rows with holes, hole depth:
 # the classical signs, a sensible default for the supply (0.99925 of a carved L = 10 / M = 40 pool at one ply)
@@ -263,6 +265,85 @@ def prove_configs(rows, pieces, L: int, M: int, weights=None, max_nodes: int = 1
     _learn_lib.check(_learn_lib.entry("exact", w.shape[0])(
         rows.data_ptr(), pieces.data_ptr(), n, L, M, wt.data_ptr(), spare_weight, max_nodes, int(bool(shortest)),
         *(out[k].data_ptr() for k in ("solved", "proved", "solution_len", "actions", "bound", "nodes")), stream))
+    out["solved"], out["proved"] = out["solved"].view(torch.bool), out["proved"].view(torch.bool)
+    out["optimal"] = out["solved"] & bool(shortest)
+    out["unwinnable"] = out["proved"] & ~out["solved"]
+    out["solution"] = _solution(out["actions"])
+    return out
+
+
+def _number(name: str, v) -> float:
+    """One finite float32 given as a Python or numpy number."""
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise ValueError(f"{name} must be a number, got {v!r}")
+    with np.errstate(over="ignore"):
+        value = np.float32(v)
+    if not np.isfinite(value):
+        raise ValueError(f"{name} must be finite (in float32), got {v!r}")
+    return float(value)
+
+
+def _reward(reward) -> tuple:
+    if isinstance(reward, (str, bytes)) or not hasattr(reward, "__len__") or len(reward) != 3:
+        raise ValueError(f"reward must be three numbers (r_line, r_win, r_lose), got {reward!r}")
+    return tuple(_number(f"reward[{j}]", v) for j, v in enumerate(reward))
+
+
+def _exact_table(table, d):
+    """A table that orders an exact search: a contiguous int32 tensor of one of the four plain forms, moved to device d."""
+    from ._learn_lib import NTUPLE_EXACT_FORMS, ntuple_entries_of
+    counts = {ntuple_entries_of(name): name for name in NTUPLE_EXACT_FORMS}
+    sizes = ", ".join(f"{k} ({v!r})" for k, v in counts.items())
+    if not _is_tensor(table) or table.dim() != 1 or str(table.dtype) != "torch.int32":
+        raise ValueError(f"table must be an int32 tensor of {sizes} entries (ntuple_table)")
+    if int(table.shape[0]) not in counts:
+        raise ValueError(f"table must be of one of the four plain forms, {sizes} entries: a sum or a staged table orders no search; "
+                         f"got {int(table.shape[0])} entries")
+    return table.to(d).contiguous()
+
+
+def ntuple_prove_configs(rows, pieces, L: int, M: int, table, gamma: float = 1.0, reward=(1.0, 0.0, 0.0), max_nodes: int = 1 << 16,
+                         shortest: bool = True, device="cuda:0", validate: bool = True) -> dict:
+    """prove_configs with the children of a node ordered by an n-tuple table instead of a weight row (the rule: include/tpl_learn.h,
+    tpl_ntuple_exact; csrc/learn/ntuple_exact.hip), one wavefront per configuration.
+
+    rows, pieces, max_nodes, shortest, device and validate are prove_configs'.  table: an int32 tensor of one of the four plain forms
+    -- "2x4", "3x3", "feat" or "feat+spare" by its entry count (ntuple_table, NTupleLearner.table); a sum or a staged table is refused.
+    A child is worth reward, or reward + gamma * V(its board, the next piece of the list) where it runs, reward = (r_line, r_win,
+    r_lose) as an environment's -- what NTuplePolicy(bound=True) scores a move with --, and V is read in the game (L, B) of the
+    iteration: at the exact budget the low-spare bins of a table trained on a tight pool.  The table, gamma and the reward only order
+    the children: they decide how many nodes a search takes, not what a search that ends finds.
+    Returns prove_configs' dict of device tensors: solved, proved, solution_len, actions, solution, bound, nodes, optimal = solved &
+    shortest and unwinnable = proved & ~solved; it feeds tighten_pool unchanged.
+
+    **proved[i] is set iff the search of configuration i was not stopped by max_nodes.  With it, solved[i] = False IS a proof that no
+    sequence of placements wins within M moves, and with shortest=True solved[i] = True a proof that solution_len[i] is the shortest
+    there is.  solved[i] = True always comes with proved[i].  Without proved[i] NOTHING is proved, neither way.**
+    No host wait except the piece-id check, which validate=False skips."""
+    import torch
+    from . import _learn_lib
+    L, M = _game(L, M)
+    max_nodes = _max_nodes(max_nodes)
+    if not isinstance(shortest, (bool, np.bool_)):
+        raise ValueError(f"shortest must be True or False, got {shortest!r}")
+    gamma = _number("gamma", gamma)
+    r_line, r_win, r_lose = _reward(reward)
+    if not _is_tensor(rows):
+        rows = np.asarray(rows)
+    if not _is_tensor(pieces):
+        pieces = np.asarray(pieces)
+    n = _shapes(rows, pieces, M)
+    d = torch.device(device)
+    table = _exact_table(table, d)
+    rows = _device_rows(rows, d)
+    pieces = _device_pieces(pieces, n, M, d, validate)
+    out = dict(solved=torch.empty(n, dtype=torch.uint8, device=d), proved=torch.empty(n, dtype=torch.uint8, device=d),
+               solution_len=torch.empty(n, dtype=torch.int32, device=d), actions=torch.empty((n, M), dtype=torch.uint8, device=d),
+               bound=torch.empty(n, dtype=torch.int32, device=d), nodes=torch.empty(n, dtype=torch.int32, device=d))
+    stream = torch._C._cuda_getCurrentRawStream(d.index if d.index is not None else torch.cuda.current_device())
+    _learn_lib.check(_learn_lib.lib().tpl_ntuple_exact(
+        rows.data_ptr(), pieces.data_ptr(), n, L, M, table.data_ptr(), int(table.shape[0]), r_line, r_win, r_lose, gamma, max_nodes,
+        int(bool(shortest)), *(out[k].data_ptr() for k in ("solved", "proved", "solution_len", "actions", "bound", "nodes")), stream))
     out["solved"], out["proved"] = out["solved"].view(torch.bool), out["proved"].view(torch.bool)
     out["optimal"] = out["solved"] & bool(shortest)
     out["unwinnable"] = out["proved"] & ~out["solved"]

@@ -123,6 +123,12 @@ Parts:
               configurations, seed 7) at budgets of config_bound + 0, 1, 2 and max_nodes 2^12, 2^16 and 2^20: proved, solved and proved
               unwinnable, mean and maximum nodes, seconds and nodes a second, the bounded beam at widths 16 and 64 beside it, and how
               much of what width 64 leaves unsolved is then solved and proved shortest
+    ntuple_exact  the exact search with its children ordered by a table (tpl_ntuple_exact, ntuple_prove_configs) on part exact's pool at
+              the exact budget: the classical-weights rows of part exact at 2^12 and 2^16 nodes again (they must reproduce win for win),
+              then the same under the rate-8 "feat" table trained on the loose pool and the "feat+spare" tables trained on the tight
+              pool without and with the prune -- proved, mean nodes, seconds, the share of what the width-64 beam leaves unsolved that
+              each closes, and the 2 x 2 of which configurations each ordering proves; and the nodes a second of the four kernels as
+              a ratio to tpl_placement_exact's in five alternated rounds at 2^12 nodes
     ntuple_shape_ab  --parent LIB: the nine 2 x 4 n-tuple kernels of another build of the learner library against this tree's, both
               loaded into one process: the outputs of the six entries compared byte for byte on the ring of part ntuple_shape
               at 2^18 boards, then each entry timed in five rounds of the parent against itself and five of the parent against
@@ -153,7 +159,7 @@ PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600, "priority": 600
          "ntuple_coherent_sweep": 1700, "ntuple_shape": 600, "ntuple_shape_sweep": 1100, "ntuple_beam": 1100,
          "ntuple_sum": 600, "ntuple_sum_sweep": 600, "ntuple_stage": 600, "ntuple_stage_sweep": 900,
          "ntuple_feature": 600, "ntuple_feature_sweep": 900, "solve": 900, "move_features": 1100, "bound": 900,
-         "ntuple_budget": 600, "ntuple_budget_sweep": 1100, "exact": 900}
+         "ntuple_budget": 600, "ntuple_budget_sweep": 1100, "exact": 900, "ntuple_exact": 900}
 SCATTERED_ATOMICS = 0.08e12                                 # 64 lanes of a wave adding into 64 rows (float adds; integer adds unmeasured)
 VALU_CYCLES, SIMDS, CLOCK_HZ = 3.3, 1024, 2.4e9           # the move's instruction mix, 256 CUs x 4, the clock
 
@@ -2707,6 +2713,126 @@ def part_exact(slice_size=4096, minute=60.0):
     out["not_measured"] = ("other weight rows and spare_weight other than 0; shortest=False; max_nodes above 2^20; pools other than this one; "
                            "the kernel's time against a launch bound other than eight waves a SIMD; the idle lanes and a transposition table "
                            "are not built")
+    return out
+
+
+def part_ntuple_exact(rounds=5):
+    """The table-ordered exact search (include/tpl_learn.h: tpl_ntuple_exact) on part exact's pool, every configuration at its exact
+    budget (config_bound + 0), beside tpl_placement_exact under the classical weights in the same run.  One seed, one pool."""
+    import torch
+    import tetris_piclim as T
+    dev = "cuda:0"
+    L_, M_, n = 10, 40, 1 << 16
+    share = lambda x: round(float(x.float().mean()), 5)
+    out = dict(part="ntuple_exact", runs=[], two_by_two=[], kernel_cost=[])
+
+    def progress(what):
+        print(json.dumps(what), file=sys.stderr, flush=True)
+
+    env = T.BatchedTetris(L_, M_, 64, device=dev, seed=7)
+    rows, pieces = env.carved_configs(n, seed=7)
+    env.terminate()
+    need = T.config_bound(rows, L_, device=dev)
+    budget = torch.clamp(need, max=M_)
+    groups = [(b, torch.nonzero(budget == b).flatten()) for b in torch.unique(budget).tolist()]
+    groups = [(b, at, rows[at], pieces[at][:, :b + 1].contiguous()) for b, at in groups]
+
+    def grouped(search):
+        """`search` on the pool grouped by budget: its dict's entries gathered, and the seconds it took."""
+        got = {}
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for b, at, r, p in groups:
+            for k, v in search(r, p, b).items():
+                if v.dim() == 1:
+                    got.setdefault(k, torch.zeros(n, dtype=v.dtype, device=dev))[at] = v
+        torch.cuda.synchronize()
+        return got, time.perf_counter() - t0
+
+    beam, _ = grouped(lambda r, p, b: T.solve_configs(r, p, L_, b, width=64, device=dev, validate=False, bound=True))
+    left = ~beam["solved"]
+    out["pool"] = dict(size=n, seed=7, L=L_, M=M_, budget="config_bound + 0", config_bound_mean=round(float(need.float().mean()), 2),
+                       unsolved_at_width_64=share(left))
+
+    # the tables of the record: part ntuple_budget_sweep's runs, 40,000 steps each
+    found = T.solve_configs(rows, pieces, L_, M_, width=16, device=dev, validate=False)
+    tight = T.tighten_pool(rows, pieces, found["solved"], found["solution_len"], 16)
+
+    def learn(pool, M_pool, **kw):
+        env = T.BatchedTetris(L_, M_pool, 4096, device=dev, seed=11, auto_reset=True, reward=NTUPLE_LARGE_REWARD, config_pool=pool)
+        learner = T.NTupleLearner(env, seed=11, gamma=1.0, epsilon=0.05, rate=8.0, **kw)
+        for steps in (10000, 30000):
+            learner.train(steps)
+        one = learner.evaluate(12288, bound=kw.get("bound", False))
+        table = learner.table.clone()
+        env.terminate()
+        return table, round(one["win_rate"], 5)
+
+    tables = {}
+    for label, pool, M_pool, kw in (("feat, rate 8, loose pool", (rows, pieces), M_, dict(shape="feat")),
+                                    ("feat+spare, rate 8, tight pool", tight, 16, dict(shape="feat+spare", bound=False)),
+                                    ("feat+spare, rate 8, tight pool, trained with the prune", tight, 16, dict(shape="feat+spare", bound=True))):
+        tables[label], rate = learn(pool, M_pool, **kw)
+        progress(dict(table=label, one_ply_win_rate_on_its_pool=rate))
+        out.setdefault("tables", []).append(dict(table=label, one_ply_win_rate_on_its_pool=rate))
+
+    def line(label, log2, got, seconds):
+        nodes = got["nodes"].double()
+        return dict(ordering=label, max_nodes=f"2^{log2}", proved=share(got["proved"]), solved=share(got["solved"]),
+                    nodes_mean=round(float(nodes.mean()), 1), seconds=round(seconds, 3),
+                    nodes_per_second=round(float(nodes.sum()) / seconds, 1),
+                    of_unsolved_at_width_64_proved=share(got["proved"][left]), of_them_solved=share(got["solved"][left]))
+
+    record = {12: 0.350, 16: 0.650}
+    for log2 in (12, 16):
+        classical, seconds = grouped(lambda r, p, b: T.prove_configs(r, p, L_, b, max_nodes=1 << log2, device=dev, validate=False))
+        got = line("classical weights", log2, classical, seconds)
+        got["reproduces_the_record"] = round(got["proved"], 3) == record[log2]
+        out["runs"].append(got)
+        progress(got)
+        for label, table in tables.items():
+            mine, seconds = grouped(lambda r, p, b: T.ntuple_prove_configs(r, p, L_, b, table, gamma=1.0, reward=NTUPLE_LARGE_REWARD,
+                                                                           max_nodes=1 << log2, device=dev, validate=False))
+            got = line(label, log2, mine, seconds)
+            out["runs"].append(got)
+            progress(got)
+            a, b = classical["proved"], mine["proved"]
+            both = a & b
+            cell = dict(ordering=label, max_nodes=f"2^{log2}", both=int(both.sum()), classical_only=int((a & ~b).sum()),
+                        table_only=int((~a & b).sum()), neither=int((~a & ~b).sum()),
+                        verdicts_and_lengths_equal_where_both_prove=bool(torch.equal(classical["solved"][both], mine["solved"][both]) and
+                                                                         torch.equal(classical["solution_len"][both], mine["solution_len"][both])))
+            out["two_by_two"].append(cell)
+            progress(cell)
+
+    # the kernels: nodes a second at 2^12 nodes beside the twin, alternated; the window forms under random tables in +-2^18
+    gen = torch.Generator(device=dev).manual_seed(5)
+    forms = {"feat": tables["feat, rate 8, loose pool"], "feat+spare": tables["feat+spare, rate 8, tight pool"]}
+    for shape in ("2x4", "3x3"):
+        forms[shape] = torch.randint(-(1 << 18), (1 << 18) + 1, (T._learn_lib.ntuple_entries_of(shape),), generator=gen, device=dev,
+                                     dtype=torch.int32)
+    rate = lambda got, seconds: float(got["nodes"].double().sum()) / seconds
+    twin = lambda: grouped(lambda r, p, b: T.prove_configs(r, p, L_, b, max_nodes=1 << 12, device=dev, validate=False))
+    twin()
+    for shape, table in forms.items():
+        search = lambda: grouped(lambda r, p, b: T.ntuple_prove_configs(r, p, L_, b, table, gamma=1.0, reward=NTUPLE_LARGE_REWARD,
+                                                                        max_nodes=1 << 12, device=dev, validate=False))
+        search()
+        a, b = [], []
+        for _ in range(rounds):
+            a.append(rate(*twin()))
+            b.append(rate(*search()))
+        ma, mb = sorted(a)[rounds // 2], sorted(b)[rounds // 2]
+        got = dict(form=shape, twin_nodes_per_second=[round(x, 1) for x in a], nodes_per_second=[round(x, 1) for x in b],
+                   twin_median=round(ma, 1), median=round(mb, 1), ratio_to_the_twin=round(mb / ma, 4))
+        out["kernel_cost"].append(got)
+        progress(got)
+    res = subprocess.run(["bash", os.path.join(ROOT, "tools", "kernel_resources.sh"), T._learn_lib.build_library()],
+                         capture_output=True, text=True, cwd=ROOT)
+    out["kernel"] = [" ".join(l.split()) for l in res.stdout.splitlines() if "exact" in l]
+    out["not_measured"] = ("budgets above config_bound; max_nodes above 2^16; shortest=False; tables trained at other rates, other seeds and "
+                           "other pools; gamma and rewards other than the training's; trained window tables (the cost rows use random "
+                           "ones); a launch bound other than eight waves a SIMD")
     return out
 
 
