@@ -551,6 +551,67 @@ int tpl_placement_exact_move(const int16_t* rows, const uint8_t* pieces, int64_t
                              float spare_weight, int32_t max_nodes, int32_t shortest, uint8_t* solved, uint8_t* proved,
                              int32_t* solution_len, uint8_t* actions, int32_t* bound, uint32_t* nodes, void* stream);
 
+/* The exact search FROM A NODE, and the proved labels of a node's moves (csrc/learn/exact_nodes.hip).  tpl_placement_exact proves
+ * things about a configuration's root; these two prove them about any board of a prescribed game and about each move from it.
+ *
+ * A NODE of the game (L, M) is a board rows[20], the lines cleared and the moves made so far, and entry, the index of its
+ * configuration's list in a shared pieces u8 [n_cfg][M + 1]: the piece at depth d from the node is pieces[entry][moves + d] & 7.  The
+ * 34 children of a node and all nodes of one game name one list; nothing is copied.
+ * THE SHIFTED GAME.  For the exact search a node is the same thing as a fresh configuration with board rows, piece list
+ * pieces[entry][moves:] and the game (L - lines, M - moves): the move, the terminal tests (won: rows were cleared and lines >= L; lost
+ * at the limit: moves >= M), cells, spare = 4 (B - moves) - cells, the board features and the carry, which is 0 at the start, read
+ * nothing else, and every iteration's budget shifts by moves.
+ *
+ * tpl_placement_exact_nodes: for node i THE SEARCH IS tpl_placement_exact's, above, with the node for the root: running, carry 0,
+ * the budgets B = moves + need(node) .. M (shortest = 1) or M alone, need(node) the move bound's need of the board with L - lines
+ * rows owed; need(node) > M - moves is decided without expanding a node: solved = 0, proved = 1, nodes = 0.  THE SIX OUTPUTS ARE,
+ * BYTE FOR BYTE, WHAT tpl_placement_exact WRITES FOR THE SHIFTED CONFIGURATION in the game (L - lines, M - moves) with the same
+ * weights, spare_weight, max_nodes and shortest: solved, proved, solution_len and actions COUNTED FROM THE NODE, bound = need(node),
+ * nodes.  actions is u8 [n][M] for the launch's M: the shifted game's M - moves placements, then 255s.  With lines = moves = 0 and
+ * entry[i] = i it is tpl_placement_exact.  What proved = 1 and proved = 0 say is said there: WITH proved = 0 NOTHING IS PROVED.
+ * A node with lines >= L, moves >= M or entry >= n_cfg cannot be refused by the host without a copy; THE KERNEL TREATS IT AS
+ * FINISHED -- solved = 0, proved = 1, solution_len = 0, nodes = 0, bound = 0, a path of 255s -- AND READS NEITHER ITS BOARD NOR pieces
+ * FOR IT: no index ever falls outside pieces.
+ * One wavefront a node, the frame of tpl_placement_exact's kernel; the stack is indexed by the depth from the node and sized by M.
+ * Refused before any HIP call: everything tpl_placement_exact refuses of the arguments the two share, a NULL lines, moves or entry,
+ * entry not 4-byte aligned, n_cfg outside [1, 2^31).
+ *
+ * tpl_placement_exact_labels: for node i and every action b = 10 r + l < 40, label u8 [n][40], length i32 [n][40] and nodes u32
+ * [n][40], each written in full.  Placement b of the node's current piece is made exactly as the search makes a child -- move_board
+ * under (L, M) from the node's lines and moves, a child left running and dead becomes LOST (the bounded form, change 1) -- and then
+ *   TPL_LABEL_NONE 0   b is not a distinct placement of the piece (canonical(cur, b) != b), or the node is finished as above:
+ *                      length = 0, nodes = 0;
+ *   TPL_LABEL_WIN  1   PROVED WINNING: the child is won (length = 1, nodes = 0), or the search of tpl_placement_exact_nodes from the
+ *                      running child -- the node one move on, shortest = 1, max_nodes for this child alone -- ends solved:
+ *                      length = 1 + its solution_len, the fewest moves from the node in which a game through b can be won;
+ *   TPL_LABEL_LOSS 2   PROVED LOSING: the child is lost or dead (nodes = 0), or that search ends proved and not solved: no sequence of
+ *                      placements after b wins within M moves.  length = 0;
+ *   TPL_LABEL_OPEN 3   UNPROVED: that search was stopped by max_nodes.  length = 0.  LABEL 3 PROVES NOTHING: NOT THAT b WINS, AND NOT
+ *                      THAT IT LOSES.
+ * nodes is the child's search's.  By construction the labels of a node are tpl_placement_exact_nodes applied to its children.
+ * A grid of 40 n wavefronts, one a (node, action).  Refused before any HIP call: what tpl_placement_exact_nodes refuses of the
+ * arguments the two share, 40 n >= 2^31, a NULL label, length or nodes, length or nodes not 4-byte aligned.
+ * The _move entries are the 14-feature forms, as tpl_placement_exact_move is. */
+#define TPL_LABEL_NONE 0
+#define TPL_LABEL_WIN 1
+#define TPL_LABEL_LOSS 2
+#define TPL_LABEL_OPEN 3
+int tpl_placement_exact_nodes(const int16_t* rows, const uint8_t* lines, const uint8_t* moves, const uint32_t* entry,
+                              const uint8_t* pieces, int64_t n, int64_t n_cfg, int32_t L, int32_t M, const float* weights,
+                              float spare_weight, int32_t max_nodes, int32_t shortest, uint8_t* solved, uint8_t* proved,
+                              int32_t* solution_len, uint8_t* actions, int32_t* bound, uint32_t* nodes, void* stream);
+int tpl_placement_exact_nodes_move(const int16_t* rows, const uint8_t* lines, const uint8_t* moves, const uint32_t* entry,
+                                   const uint8_t* pieces, int64_t n, int64_t n_cfg, int32_t L, int32_t M, const float* weights,
+                                   float spare_weight, int32_t max_nodes, int32_t shortest, uint8_t* solved, uint8_t* proved,
+                                   int32_t* solution_len, uint8_t* actions, int32_t* bound, uint32_t* nodes, void* stream);
+int tpl_placement_exact_labels(const int16_t* rows, const uint8_t* lines, const uint8_t* moves, const uint32_t* entry,
+                               const uint8_t* pieces, int64_t n, int64_t n_cfg, int32_t L, int32_t M, const float* weights,
+                               float spare_weight, int32_t max_nodes, uint8_t* label, int32_t* length, uint32_t* nodes, void* stream);
+int tpl_placement_exact_labels_move(const int16_t* rows, const uint8_t* lines, const uint8_t* moves, const uint32_t* entry,
+                                    const uint8_t* pieces, int64_t n, int64_t n_cfg, int32_t L, int32_t M, const float* weights,
+                                    float spare_weight, int32_t max_nodes, uint8_t* label, int32_t* length, uint32_t* nodes,
+                                    void* stream);
+
 /* An n-tuple afterstate value function, its placement policy and its temporal-difference update (csrc/learn/ntuple.hip).
  *
  * Table: TPL_NTUPLE_ENTRIES = 8 * 153 * 256 + 1024 = 314,368 int32 entries (1,257,472 bytes), 16-byte aligned, in units of 2^-16:

@@ -18,7 +18,7 @@ __all__ = ["BatchedTetris", "Tetris", "Snapshot", "OBS_DIM", "NUM_ACTIONS", "RUN
            "NTUPLE_STAGES", "ntuple_stage_map", "ntuple_staged", "ntuple_stages", "ntuple_map", "ntuple_is_staged", "NTUPLE_FEATURE_FORMS",
            "ntuple_feature_bins", "NTUPLE_BUDGET_FORMS", "ntuple_budget", "ntuple_budget_bins", "solve_configs", "prove_configs", "ntuple_prove_configs", "tighten_pool", "CLASSICAL_WEIGHTS", "FEATURE_NAMES",
            "MOVE_FEATURE_NAMES", "DELLACHERIE_WEIGHTS", "move_bound", "config_bound", "config_index", "PoolTally", "resample_pool",
-           "curriculum_weights", "PoolCurriculum"]
+           "curriculum_weights", "PoolCurriculum", "prove_nodes", "label_moves", "label_states", "blunders"]
 
 
 def __getattr__(name):
@@ -48,7 +48,8 @@ def __getattr__(name):
                 "NTUPLE_STAGES", "ntuple_stage_map", "ntuple_staged", "ntuple_stages", "ntuple_map", "ntuple_is_staged", "NTUPLE_FEATURE_FORMS",
                 "ntuple_feature_bins", "NTUPLE_BUDGET_FORMS", "ntuple_budget", "ntuple_budget_bins"):
         return getattr(importlib.import_module(__name__ + ".ntuple"), name)
-    if name in ("solve_configs", "prove_configs", "ntuple_prove_configs", "tighten_pool", "CLASSICAL_WEIGHTS", "config_bound"):
+    if name in ("solve_configs", "prove_configs", "ntuple_prove_configs", "tighten_pool", "CLASSICAL_WEIGHTS", "config_bound", "prove_nodes",
+                "label_moves", "label_states", "blunders"):
         return getattr(importlib.import_module(__name__ + ".solve"), name)
     if name in ("config_index", "PoolTally", "resample_pool", "curriculum_weights", "PoolCurriculum"):
         return getattr(importlib.import_module(__name__ + ".curriculum"), name)

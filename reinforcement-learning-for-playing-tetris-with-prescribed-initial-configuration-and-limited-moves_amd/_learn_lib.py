@@ -24,7 +24,8 @@ _UNITS = [os.path.join(_LEARN_CSRC, f) for f in ("replay.hip", "pack.hip", "prio
                                                       "beam.hip", "solve.hip", "ntuple.hip", "ntuple_beam.hip", "heuristic_move.hip",
                                                       "beam_move.hip", "solve_move.hip", "bound.hip", "beam_bound.hip",
                                                       "solve_bound.hip", "beam_move_bound.hip", "solve_move_bound.hip",
-                                                      "exact.hip", "exact_move.hip", "ntuple_exact.hip", "curriculum.hip", "heuristic.hip")]
+                                                      "exact.hip", "exact_move.hip", "ntuple_exact.hip", "curriculum.hip", "exact_nodes.hip",
+                                                      "exact_nodes_move.hip", "heuristic.hip")]
 
 # entry points declared in include/tpl_learn.h (tests check that the .so exports every one of them)
 LEARN_SYMBOLS = [
@@ -49,6 +50,7 @@ LEARN_SYMBOLS = [
     "tpl_ntuple_update_trace_budget", "tpl_ntuple_budget_bins",
     "tpl_placement_exact", "tpl_placement_exact_move", "tpl_ntuple_exact",
     "tpl_config_index", "tpl_pool_tally", "tpl_pool_resample",
+    "tpl_placement_exact_nodes", "tpl_placement_exact_nodes_move", "tpl_placement_exact_labels", "tpl_placement_exact_labels_move",
 ]
 NSTEP_MAX = 16
 BEAM_MAX_DEPTH, BEAM_MAX_WIDTH = 12, 64
@@ -173,6 +175,11 @@ def lib() -> C.CDLL:
         exact = getattr(L, f"tpl_placement_exact{form}")     # the exact search: a node budget and a flag for a width
         exact.argtypes = [vp, vp, i64, i32, i32, vp, f32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
         exact.restype = i32
+        # the search from a node and the labels of its moves: lines, moves, entry and the shared lists for the configuration's own
+        nodes, labels = getattr(L, f"tpl_placement_exact_nodes{form}"), getattr(L, f"tpl_placement_exact_labels{form}")
+        nodes.argtypes = [vp, vp, vp, vp, vp, i64, i64, i32, i32, vp, f32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+        labels.argtypes = [vp, vp, vp, vp, vp, i64, i64, i32, i32, vp, f32, i32, vp, vp, vp, vp]
+        nodes.restype = labels.restype = i32
     L.tpl_ntuple_value.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp]
     L.tpl_ntuple_act.argtypes = [vp, vp, i64, i32, i32, f32, f32, f32, f32, vp, f32, u64, u64, vp, vp, vp, vp, vp, vp]
     L.tpl_ntuple_update.argtypes = [vp, vp, i64, i32, i32, vp, vp, f32, vp]
@@ -1003,6 +1010,119 @@ def placement_exact(rows, pieces, L: int, M: int, weights, max_nodes: int, short
             else:                                               # searched out: no sequence of placements wins within M moves
                 del stacks[s]
     return solved, proved, length, actions, bound, nodes
+
+
+# ------------------------------------------------------------------------------------------------ the exact search from a node
+# The rules of tpl_placement_exact_nodes and tpl_placement_exact_labels (include/tpl_learn.h) on the host, from the ROW form: the
+# nodes are grouped by (lines, moves), each group is handed to placement_exact as configurations of its SHIFTED game, and the one
+# move of a label is host_moves_traced and move_bound under the game's own (L, M).  The device shifts per wave and runs its own
+# copy of the search (csrc/learn/exact_nodes.hip) -- the two share nothing.
+LABEL_NONE, LABEL_WIN, LABEL_LOSS, LABEL_OPEN = 0, 1, 2, 3
+
+
+def _node_arrays(rows, lines, moves, entry, pieces, L: int, M: int):
+    """The node arguments of both mirrors, checked: rows uint16 [n, 20], lines / moves / entry int64 [n], pieces int64 [n_cfg, M + 1]
+    masked to three bits, and `live` [n], False where the kernel treats the node as finished."""
+    L, M = int(L), int(M)
+    if not (1 <= L <= 250 and 1 <= M <= SOLVE_MAX_MOVES):
+        raise ValueError(f"L and M must be in [1, 250] and [1, {SOLVE_MAX_MOVES}]")
+    rows = np.asarray(rows)
+    rows = (rows.view(np.uint16) if rows.dtype == np.int16 else rows.astype(np.uint16)).reshape(-1, 20)
+    n = rows.shape[0]
+    pieces = np.asarray(pieces)
+    if pieces.ndim != 2 or pieces.shape[0] < 1 or pieces.shape[1] != M + 1:
+        raise ValueError(f"pieces must be [n_cfg, {M + 1}] with n_cfg >= 1")
+    pieces = pieces.astype(np.int64) & 7
+    out = []
+    for name, x, top in (("lines", lines, 255), ("moves", moves, 255), ("entry", entry, (1 << 32) - 1)):
+        x = np.asarray(x)
+        if x.shape != (n,) or not np.issubdtype(x.dtype, np.integer):
+            raise ValueError(f"{name} must be {n} integers, one per node")
+        x = x.astype(np.int64)
+        if n and (x.min() < 0 or x.max() > top):
+            raise ValueError(f"{name} must be in [0, {top}]")
+        out.append(x)
+    if n < 1:
+        raise ValueError("rows must be [n, 20] with n >= 1")
+    lines, moves, entry = out
+    live = (lines < L) & (moves < M) & (entry < pieces.shape[0])
+    return rows, lines, moves, entry, pieces, live
+
+
+def _exact_arguments(weights, max_nodes, shortest, spare_weight) -> None:
+    """What placement_exact refuses of the arguments that are no arrays of nodes, for a call that may search nothing."""
+    if isinstance(max_nodes, bool) or not isinstance(max_nodes, (int, np.integer)) or not 1 <= int(max_nodes) <= EXACT_MAX_NODES:
+        raise ValueError(f"max_nodes must be an integer in [1, {EXACT_MAX_NODES}]")
+    if not isinstance(shortest, (bool, np.bool_)):
+        raise ValueError("shortest must be True or False")
+    if np.asarray(weights, dtype=np.float32).reshape(-1).shape not in ((NUM_FEATURES,), (NUM_MOVE_FEATURES,)):
+        raise ValueError("weights must be one row of 12 or of 14")
+    with np.errstate(over="ignore"):
+        if not np.isfinite(np.float32(spare_weight)):
+            raise ValueError("spare_weight must be finite (in float32)")
+
+
+def placement_exact_nodes(rows, lines, moves, entry, pieces, L: int, M: int, weights, max_nodes: int, shortest: bool = True,
+                          spare_weight: float = 0.0):
+    """The rule of tpl_placement_exact_nodes (include/tpl_learn.h) for n nodes of the game (L, M): rows uint16 [n, 20], lines, moves and
+    entry integers [n], pieces [n_cfg, M + 1] shared by the nodes, the rest placement_exact's.  Node i is searched as the configuration
+    (rows[i], pieces[entry[i], moves[i]:]) of the game (L - lines[i], M - moves[i]).  Returns placement_exact's six arrays with
+    solution_len and actions counted from the node, actions uint8 [n, M] padded with 255; a node with lines >= L, moves >= M or
+    entry >= n_cfg is finished: solved = 0, proved = 1, bound = 0, nodes = 0."""
+    rows, lines, moves, entry, pieces, live = _node_arrays(rows, lines, moves, entry, pieces, L, M)
+    L, M, n = int(L), int(M), rows.shape[0]
+    _exact_arguments(weights, max_nodes, shortest, spare_weight)
+    solved, proved, length = np.zeros(n, np.uint8), np.ones(n, np.uint8), np.zeros(n, np.int32)
+    actions, bound, nodes = np.full((n, M), NO_SECOND, np.uint8), np.zeros(n, np.int32), np.zeros(n, np.uint32)
+    for at_lines, at_moves in sorted({(int(a), int(b)) for a, b in zip(lines[live], moves[live])}):
+        idx = np.flatnonzero(live & (lines == at_lines) & (moves == at_moves))
+        got = placement_exact(rows[idx], pieces[entry[idx], at_moves:], L - at_lines, M - at_moves, weights, max_nodes, shortest,
+                              spare_weight)
+        solved[idx], proved[idx], length[idx], bound[idx], nodes[idx] = got[0], got[1], got[2], got[4], got[5]
+        actions[idx, :M - at_moves] = got[3]
+    return solved, proved, length, actions, bound, nodes
+
+
+def placement_exact_labels(rows, lines, moves, entry, pieces, L: int, M: int, weights, max_nodes: int, spare_weight: float = 0.0):
+    """The rule of tpl_placement_exact_labels (include/tpl_learn.h) for n nodes (placement_exact_nodes' arguments without `shortest`):
+    every distinct placement b of a node's piece is played under (L, M) from the node's lines and moves, a dead child turned lost; a won
+    child is LABEL_WIN at length 1, a lost one LABEL_LOSS, and a running one is what placement_exact_nodes (shortest, max_nodes for
+    the child alone) says of it: solved -> LABEL_WIN at 1 + solution_len, proved without a win -> LABEL_LOSS, stopped -> LABEL_OPEN,
+    which proves nothing.  Returns (label uint8 [n, 40], length int32 [n, 40], nodes uint32 [n, 40]); LABEL_NONE, 0, 0 where b is no
+    distinct placement and for every b of a finished node."""
+    rows, lines, moves, entry, pieces, live = _node_arrays(rows, lines, moves, entry, pieces, L, M)
+    L, M, n = int(L), int(M), rows.shape[0]
+    label, length = np.zeros((n, NUM_ACTIONS), np.uint8), np.zeros((n, NUM_ACTIONS), np.int32)
+    nodes = np.zeros((n, NUM_ACTIONS), np.uint32)
+    placements = [np.flatnonzero(canonical_actions(p, np.arange(NUM_ACTIONS)) == np.arange(NUM_ACTIONS)) for p in range(8)]
+    at = np.flatnonzero(live)
+    _exact_arguments(weights, max_nodes, True, spare_weight)
+    if at.size == 0:
+        return label, length, nodes
+    cur = pieces[entry[at], moves[at]]
+    sizes = [placements[p].size for p in cur]
+    node = np.repeat(at, sizes)
+    b = np.concatenate([placements[p] for p in cur])
+    r2, _, l2, m2, s2 = host_moves(rows[node], np.repeat(cur, sizes), b // 10, b % 10, L, M, lines[node], moves[node])
+    s2 = np.where(move_bound(r2, L, M, l2, m2, s2)["dead"], STATE_LOST_LIMIT, s2)
+    label[node, b] = np.where(s2 == STATE_WON, LABEL_WIN, np.where(s2 == STATE_RUNNING, LABEL_OPEN, LABEL_LOSS))
+    length[node, b] = s2 == STATE_WON
+    run = np.flatnonzero(s2 == STATE_RUNNING)
+    if run.size:
+        solved, proved, sol_len, _, _, count = placement_exact_nodes(r2[run], l2[run], m2[run], entry[node[run]], pieces, L, M, weights,
+                                                                     max_nodes, True, spare_weight)
+        label[node[run], b[run]] = np.where(solved == 1, LABEL_WIN, np.where(proved == 1, LABEL_LOSS, LABEL_OPEN))
+        length[node[run], b[run]] = np.where(solved == 1, 1 + sol_len, 0)
+        nodes[node[run], b[run]] = count
+    return label, length, nodes
+
+
+def best_labelled_move(label, length) -> np.ndarray:
+    """The lowest placement among the proved-winning ones of least length, uint8 [n]; 255 where no move is proved winning."""
+    label, length = np.asarray(label), np.asarray(length).astype(np.int64)
+    win = label == LABEL_WIN
+    key = np.where(win, length, np.iinfo(np.int64).max)
+    return np.where(win.any(axis=1), key.argmin(axis=1), NO_SECOND).astype(np.uint8)
 
 
 # ------------------------------------------------------------------------------------------------ the n-tuple value function

@@ -16,6 +16,12 @@ csrc/learn/exact.hip), one wavefront per configuration, which within the move bo
 node budget and says so (`proved`).  Its weights do one thing, they order a node's children; `ntuple_prove_configs` is the same search
 with that order taken from an n-tuple table (tpl_ntuple_exact; csrc/learn/ntuple_exact.hip): a child is worth what the one-ply table
 policy scores a move with, read at the budget of the iteration.  Verdicts do not depend on the order; the nodes a proof takes do.
+
+`prove_nodes` starts that search at any node of a game -- a board, its lines and moves, and the list of its configuration -- instead
+of at move 0 (tpl_placement_exact_nodes; csrc/learn/exact_nodes.hip): for the search a node is a fresh configuration of the game
+(L - lines, M - moves).  `label_moves` applies it to the children of a node and labels every move proved winning, proved losing
+or unproved (tpl_placement_exact_labels), `label_states` does so for the boards of an environment, and `blunders` marks where a
+proved-losing move was taken although a proved-winning one was there.
 """
 from __future__ import annotations
 
@@ -23,7 +29,8 @@ import numpy as np
 
 from ._learn_lib import BEAM_MAX_WIDTH, EXACT_MAX_NODES, NUM_FEATURES, NUM_MOVE_FEATURES, SOLVE_MAX_MOVES
 
-__all__ = ["CLASSICAL_WEIGHTS", "solve_configs", "prove_configs", "ntuple_prove_configs", "tighten_pool", "config_bound"]
+__all__ = ["CLASSICAL_WEIGHTS", "solve_configs", "prove_configs", "ntuple_prove_configs", "tighten_pool", "config_bound",
+           "prove_nodes", "label_moves", "label_states", "blunders"]
 
 # cleared, won, lost, holes, aggregate height, max height, bumpiness, row and column transitions, wells, rows with holes, hole depth:
 # the classical signs, a sensible default for the supply (0.99925 of a carved L = 10 / M = 40 pool at one ply)
@@ -270,6 +277,172 @@ def prove_configs(rows, pieces, L: int, M: int, weights=None, max_nodes: int = 1
     out["unwinnable"] = out["proved"] & ~out["solved"]
     out["solution"] = _solution(out["actions"])
     return out
+
+
+def _node_tensors(rows, lines, moves, entry, pieces, M: int, d, validate: bool):
+    """The node arguments of prove_nodes and label_moves, checked before anything moves to the device, as contiguous tensors on
+    d: rows int16 [n, 20], lines and moves uint8 [n], entry int32 [n] -- anything outside [0, n_cfg) becomes -1, which the kernels
+    read as an entry out of range --, pieces uint8 [n_cfg, M + 1]; and n, n_cfg."""
+    import torch
+    rows, lines, moves, entry, pieces = (x if _is_tensor(x) else np.asarray(x) for x in (rows, lines, moves, entry, pieces))
+    rs, ps = tuple(rows.shape), tuple(pieces.shape)
+    n = rs[0] if rs else 0
+    if not (rs == (n, 20) or rs == (n, 20, 10)):
+        raise ValueError(f"rows must be [n, 20] row masks or [n, 20, 10] cells; got {rs}")
+    if n < 1:
+        raise ValueError("at least one node is needed")
+    if len(ps) != 2 or ps[0] < 1 or ps[1] not in (M + 1, M):
+        raise ValueError(f"pieces must be [n_cfg, {M + 1}] or [n_cfg, {M}] with n_cfg >= 1, the lists the entries name; got {ps}")
+    n_cfg = ps[0]
+    plain = []
+    for name, x, top in (("lines", lines, 255), ("moves", moves, 255), ("entry", entry, None)):
+        kind = str(x.dtype)
+        if tuple(x.shape) != (n,) or "int" not in kind:
+            raise ValueError(f"{name} must be {n} integers, one per node; got {tuple(x.shape)} {kind}")
+        if not _is_tensor(x):
+            if top is not None and n and (x.min() < 0 or x.max() > top):
+                raise ValueError(f"{name} must be in [0, {top}]")
+            x = torch.from_numpy(np.ascontiguousarray(x.astype(np.int64)))
+        plain.append(x)
+    lines, moves = (x.to(d).to(torch.uint8).contiguous() for x in plain[:2])
+    entry = plain[2].to(d).to(torch.int64)
+    entry = torch.where((entry < 0) | (entry >= n_cfg), torch.full_like(entry, -1), entry).to(torch.int32).contiguous()
+    return _device_rows(rows, d), lines, moves, entry, _device_pieces(pieces, n_cfg, M, d, validate), n, n_cfg
+
+
+def prove_nodes(rows, lines, moves, entry, pieces, L: int, M: int, weights=None, max_nodes: int = 1 << 16, shortest: bool = True,
+                spare_weight: float = 0.0, device="cuda:0", validate: bool = True) -> dict:
+    """prove_configs from any node of a prescribed game (the rule: include/tpl_learn.h, tpl_placement_exact_nodes;
+    csrc/learn/exact_nodes.hip), one wavefront per node.
+
+    A node is a board rows[i] ([n, 20] row masks or [n, 20, 10] cells), the lines[i] cleared and the moves[i] made so far (integers
+    [n], 0..255), and entry[i] (integers [n]), the row of `pieces` ([n_cfg, M + 1] uint8, or [n_cfg, M]) that holds its
+    configuration's list: its next piece is pieces[entry[i], moves[i]].  Nodes of one game share a list; nothing is copied.  The rest
+    is prove_configs'.  For the search the node IS the configuration (rows[i], pieces[entry[i], moves[i]:]) of the game
+    (L - lines[i], M - moves[i]), and the result is that search's, byte for byte.
+    Returns prove_configs' dict: solved, proved, solution_len and actions [n, M] COUNTED FROM THE NODE, solution, bound (the least
+    number of further moves any win can take), nodes, optimal = solved & shortest, unwinnable = proved & ~solved.  A node with
+    lines >= L, moves >= M or an entry outside the lists is finished: proved, not solved, 0 nodes.
+
+    **proved[i] is set iff the search from node i was not stopped by max_nodes.  With it, solved[i] = False IS a proof that no sequence
+    of placements from the node wins within the M - moves[i] moves left.  Without proved[i] NOTHING is proved, neither way.**
+    No host wait except the piece-id check, which validate=False skips."""
+    import torch
+    from . import _learn_lib
+    L, M = _game(L, M)
+    w = _weight_row(weights)
+    max_nodes = _max_nodes(max_nodes)
+    if not isinstance(shortest, (bool, np.bool_)):
+        raise ValueError(f"shortest must be True or False, got {shortest!r}")
+    spare_weight = _spare_weight(spare_weight, True)
+    d = torch.device(device)
+    rows, lines, moves, entry, pieces, n, n_cfg = _node_tensors(rows, lines, moves, entry, pieces, M, d, validate)
+    wt = torch.from_numpy(_learn_lib.padded_weights(w)).to(d)
+    out = dict(solved=torch.empty(n, dtype=torch.uint8, device=d), proved=torch.empty(n, dtype=torch.uint8, device=d),
+               solution_len=torch.empty(n, dtype=torch.int32, device=d), actions=torch.empty((n, M), dtype=torch.uint8, device=d),
+               bound=torch.empty(n, dtype=torch.int32, device=d), nodes=torch.empty(n, dtype=torch.int32, device=d))
+    stream = torch._C._cuda_getCurrentRawStream(d.index if d.index is not None else torch.cuda.current_device())
+    _learn_lib.check(_learn_lib.entry("exact_nodes", w.shape[0])(
+        rows.data_ptr(), lines.data_ptr(), moves.data_ptr(), entry.data_ptr(), pieces.data_ptr(), n, n_cfg, L, M, wt.data_ptr(),
+        spare_weight, max_nodes, int(bool(shortest)),
+        *(out[k].data_ptr() for k in ("solved", "proved", "solution_len", "actions", "bound", "nodes")), stream))
+    out["solved"], out["proved"] = out["solved"].view(torch.bool), out["proved"].view(torch.bool)
+    out["optimal"] = out["solved"] & bool(shortest)
+    out["unwinnable"] = out["proved"] & ~out["solved"]
+    out["solution"] = _solution(out["actions"])
+    return out
+
+
+def _best_move(label, length):
+    """The lowest placement among the proved-winning ones of least length (uint8 [n]); 255 where none is proved."""
+    import torch
+    win = label == 1
+    key = torch.where(win, length.to(torch.int64), torch.full((), 1 << 40, dtype=torch.int64, device=label.device))
+    best = torch.argmin(key * 64 + torch.arange(40, device=label.device), dim=1)      # (length, b) in one word: b < 64
+    return torch.where(win.any(dim=1), best, torch.full_like(best, 255)).to(torch.uint8)
+
+
+def label_moves(rows, lines, moves, entry, pieces, L: int, M: int, weights=None, max_nodes: int = 1 << 12,
+                spare_weight: float = 0.0, device="cuda:0", validate: bool = True) -> dict:
+    """Every move of every node, proved (the rule: include/tpl_learn.h, tpl_placement_exact_labels; csrc/learn/exact_nodes.hip), one
+    wavefront per (node, placement).
+
+    The nodes are prove_nodes'.  Placement b = 10 r + l of node i's piece is made as the search makes a child, and
+      label[i, b] = 0   b is no distinct placement of the piece (its canonical form is another b), or the node is finished;
+                    1   PROVED WINNING: the move wins, or the shortest search from the board it leaves finds a win; length[i, b] is
+                        then the fewest moves from the node, b included, in which a game through b can be won;
+                    2   PROVED LOSING: the move ends the game lost or leaves a dead board, or the search from the board it leaves was
+                        searched out without a win;
+                    3   UNPROVED: that search was stopped by max_nodes, which caps each child on its own.
+    **Label 3 proves nothing, neither way: a larger max_nodes may turn it into 1 or into 2.  Labels 1 and 2 do not depend on
+    max_nodes or on the weights, which only order the search.**
+    Returns a dict of device tensors: label uint8 [n, 40], length int32 [n, 40] (0 unless the label is 1), nodes int32 [n, 40] (the
+    nodes the child's search expanded), winning bool [n, 40] = label == 1, and best uint8 [n]: the lowest placement among the
+    proved-winning ones of least length, 255 where none is proved.  No host wait except the piece-id check."""
+    import torch
+    from . import _learn_lib
+    L, M = _game(L, M)
+    w = _weight_row(weights)
+    max_nodes = _max_nodes(max_nodes)
+    spare_weight = _spare_weight(spare_weight, True)
+    d = torch.device(device)
+    rows, lines, moves, entry, pieces, n, n_cfg = _node_tensors(rows, lines, moves, entry, pieces, M, d, validate)
+    if 40 * n >= 1 << 31:
+        raise ValueError("too many nodes: 40 n must stay below 2^31")
+    wt = torch.from_numpy(_learn_lib.padded_weights(w)).to(d)
+    out = dict(label=torch.empty((n, 40), dtype=torch.uint8, device=d), length=torch.empty((n, 40), dtype=torch.int32, device=d),
+               nodes=torch.empty((n, 40), dtype=torch.int32, device=d))
+    stream = torch._C._cuda_getCurrentRawStream(d.index if d.index is not None else torch.cuda.current_device())
+    _learn_lib.check(_learn_lib.entry("exact_labels", w.shape[0])(
+        rows.data_ptr(), lines.data_ptr(), moves.data_ptr(), entry.data_ptr(), pieces.data_ptr(), n, n_cfg, L, M, wt.data_ptr(),
+        spare_weight, max_nodes, *(out[k].data_ptr() for k in ("label", "length", "nodes")), stream))
+    out["winning"] = out["label"] == 1
+    out["best"] = _best_move(out["label"], out["length"])
+    return out
+
+
+def label_states(env, pieces, weights=None, max_nodes: int = 1 << 12) -> dict:
+    """label_moves for every board of an environment that plays a pool: the boards, lines and moves come from env.packed_state(),
+    the entries from config_index(env), and `pieces` ([n_cfg, M + 1] uint8) is the piece lists of the pool the environment has
+    loaded -- the pieces that load_configs took.  A finished board has no move to label: label 0 throughout, best 255.
+    Returns label_moves' dict and, beside it, entry int32 [N] (config_index's, -1 for a finished board of an environment without
+    auto-reset) and running bool [N].  The environment is read, never written.  Refused: an environment without a pool, and a
+    `pieces` whose shape is not [n_cfg, M + 1] for the pool that is loaded.
+    **Label 3 proves nothing** (label_moves)."""
+    import torch
+    from .curriculum import config_index
+    info = env.pool_info()
+    if info["n_configs"] == 0:
+        raise ValueError("label_states needs an environment with a configuration pool (load_configs first)")
+    if not hasattr(pieces, "shape") or tuple(pieces.shape) != (info["n_configs"], env.M + 1):
+        raise ValueError(f"pieces must be the loaded pool's lists, [{info['n_configs']}, {env.M + 1}]; "
+                         f"got {tuple(getattr(pieces, 'shape', ()))}")
+    state = env.packed_state()
+    entry = config_index(env)
+    running = state["state"] == 0
+    lines = torch.where(running, state["lines"], torch.full_like(state["lines"], env.L))      # lines = L: finished for the kernel
+    out = label_moves(state["rows"], lines, state["moves"], entry, pieces, env.L, env.M, weights=weights, max_nodes=max_nodes,
+                      device=env.device)
+    out["entry"], out["running"] = entry, running
+    return out
+
+
+def blunders(label_before, action):
+    """Where a game was thrown away: uint8 [n], 1 where the node had a proved-winning move (a label 1 among label_before [n, 40])
+    and the action taken ([n], as the labels name it: the canonical placement 10 r + l) is labelled 2, proved losing.  An action
+    labelled 3 is no proved blunder.  Tensors give a tensor, arrays an array."""
+    if _is_tensor(label_before):
+        import torch
+        action = torch.as_tensor(action, device=label_before.device).to(torch.int64)
+        if label_before.dim() != 2 or label_before.shape[1] != 40 or tuple(action.shape) != (label_before.shape[0],):
+            raise ValueError("label_before must be [n, 40] and action [n]")
+        taken = torch.gather(label_before, 1, action.clamp(0, 39)[:, None])[:, 0]
+        return ((label_before == 1).any(dim=1) & (taken == 2) & (action >= 0) & (action < 40)).to(torch.uint8)
+    label_before, action = np.asarray(label_before), np.asarray(action).astype(np.int64)
+    if label_before.ndim != 2 or label_before.shape[1] != 40 or action.shape != (label_before.shape[0],):
+        raise ValueError("label_before must be [n, 40] and action [n]")
+    taken = label_before[np.arange(action.size), np.clip(action, 0, 39)]
+    return ((label_before == 1).any(axis=1) & (taken == 2) & (action >= 0) & (action < 40)).astype(np.uint8)
 
 
 def _number(name: str, v) -> float:

@@ -133,6 +133,12 @@ Parts:
               loaded into one process: the outputs of the six entries compared byte for byte on the ring of part ntuple_shape
               at 2^18 boards, then each entry timed in five rounds of the parent against itself and five of the parent against
               this build; a new median passes within the parent's own min-max or at most 2 % above the parent's median
+    labels    the proved move labels (tpl_placement_exact_labels, label_states) on the tight pool of the record (part bound's: carved
+              L=10 / M=40, 65,536 configurations, seed 7, solved at width 16, tighten_pool(M_new=16)): the classical weights at one ply
+              and at beam (3, 8) play one episode on 4,096 boards, label_states (max_nodes 2^12 a child) before every step -- per move
+              number the share of running boards whose every distinct move is proved and the blunder rate, the share of lost episodes
+              with a proved first blunder, the milliseconds of a label_states call, and the nodes a second beside prove_configs on the
+              same pool in the same run
     solve     the whole-game beam solver (tpl_placement_solve, solve_configs) under the classical weights: the share of forward seeds
               0 .. 9,999 it solves at L=5 / M=20 and L=10 / M=40 at widths 1, 8, 16 and 64 beside the share the reference's solver marks
               winnable in the same forward_configs call, and the share of the sweeps' carved pool (65,536, seed 7) it solves; the
@@ -159,7 +165,7 @@ PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600, "priority": 600
          "ntuple_coherent_sweep": 1700, "ntuple_shape": 600, "ntuple_shape_sweep": 1100, "ntuple_beam": 1100,
          "ntuple_sum": 600, "ntuple_sum_sweep": 600, "ntuple_stage": 600, "ntuple_stage_sweep": 900,
          "ntuple_feature": 600, "ntuple_feature_sweep": 900, "solve": 900, "move_features": 1100, "bound": 900,
-         "ntuple_budget": 600, "ntuple_budget_sweep": 1100, "exact": 900, "ntuple_exact": 900}
+         "ntuple_budget": 600, "ntuple_budget_sweep": 1100, "exact": 900, "ntuple_exact": 900, "labels": 900}
 SCATTERED_ATOMICS = 0.08e12                                 # 64 lanes of a wave adding into 64 rows (float adds; integer adds unmeasured)
 VALU_CYCLES, SIMDS, CLOCK_HZ = 3.3, 1024, 2.4e9           # the move's instruction mix, 256 CUs x 4, the clock
 
@@ -2713,6 +2719,92 @@ def part_exact(slice_size=4096, minute=60.0):
     out["not_measured"] = ("other weight rows and spare_weight other than 0; shortest=False; max_nodes above 2^20; pools other than this one; "
                            "the kernel's time against a launch bound other than eight waves a SIMD; the idle lanes and a transposition table "
                            "are not built")
+    return out
+
+
+def part_labels(boards=4096, log2_nodes=12):
+    """The proved move labels (include/tpl_learn.h: tpl_placement_exact_labels; T.label_states) on the tight pool of the record --
+    part_bound's: carved L = 10 / M = 40, 65,536 configurations, seed 7, solved at width 16, tighten_pool(M_new=16).  The classical
+    weights at one ply and at beam (3, 8) play one episode each on `boards` boards without auto-reset, label_states before every
+    step with max_nodes = 2^log2_nodes a child.  One seed, one pool, one weight row."""
+    import numpy as np
+    import torch
+    import tetris_piclim as T
+    dev = "cuda:0"
+    L_, M_, M_new = 10, 40, 16
+    share = lambda x: round(float(x.float().mean()), 5) if x.numel() else None
+    out = dict(part="labels", boards=boards, max_nodes=f"2^{log2_nodes}", players={})
+
+    def progress(what):
+        print(json.dumps(what), file=sys.stderr, flush=True)
+
+    n = 1 << 16
+    env = T.BatchedTetris(L_, M_, 64, device=dev, seed=7)
+    rows, pieces = env.carved_configs(n, seed=7)
+    env.terminate()
+    found = T.solve_configs(rows, pieces, L_, M_, width=16, device=dev, validate=False)
+    tight = T.tighten_pool(rows, pieces, found["solved"], found["solution_len"], M_new)
+    out["pool"] = dict(size=int(tight[0].shape[0]), of=n, seed=7, L=L_, M=M_new, weights="classical")
+    classical = np.array(T.CLASSICAL_WEIGHTS)
+    canon = torch.from_numpy(np.stack([T._learn_lib.canonical_actions(p, np.arange(40)) for p in range(8)]).astype(np.int64)).to(dev)
+
+    # the root search of the same pool in the same run: the rate the labels' searches stand beside
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    roots = T.prove_configs(tight[0], tight[1], L_, M_new, max_nodes=1 << log2_nodes, device=dev, validate=False)
+    torch.cuda.synchronize()
+    seconds = time.perf_counter() - t0
+    out["prove_configs"] = dict(configurations=int(tight[0].shape[0]), proved=share(roots["proved"]), solved=share(roots["solved"]),
+                                seconds=round(seconds, 3), nodes_per_second=round(float(roots["nodes"].double().sum()) / seconds, 1))
+    progress(out["prove_configs"])
+
+    for name, depth, width in (("one_ply", 1, 1), ("beam_3x8", 3, 8)):
+        env = T.BatchedTetris(L_, M_new, boards, device=dev, seed=11, auto_reset=False, reward=(0.0, 1.0, 0.0), config_pool=tight)
+        env.reset()
+        policy = T.BeamPolicy(env, classical, depth, width)
+        action = torch.empty(boards, dtype=torch.uint8, device=dev)
+        first = torch.full((boards,), -1, dtype=torch.int64, device=dev)          # the move number of a board's first proved blunder
+        open_before = torch.zeros(boards, dtype=torch.bool, device=dev)           # an unproved move met before it (or ever)
+        moves, nodes, spent = [], 0.0, 0.0
+        for t in range(M_new):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            lab = T.label_states(env, tight[1], weights=classical, max_nodes=1 << log2_nodes)
+            torch.cuda.synchronize()
+            ms = (time.perf_counter() - t0) * 1e3
+            running = lab["running"]
+            policy.act(out=action)
+            cur = env.packed_state()["cur"].to(torch.int64) & 7
+            taken = canon[cur, action.to(torch.int64).clamp(max=39)]
+            blunder = T.blunders(lab["label"], taken).bool() & running
+            proved_all = ~(lab["label"] == 3).any(dim=1)
+            first = torch.where((first < 0) & blunder, torch.full_like(first, t), first)
+            open_before |= running & ~proved_all & (first < 0)
+            count = float(lab["nodes"].double().sum())
+            nodes, spent = nodes + count, spent + ms * 1e-3
+            line = dict(move=t, running=int(running.sum()), every_move_proved=share(proved_all[running]),
+                        has_a_proved_winning_move=share(lab["winning"].any(dim=1)[running]), blunder_rate=share(blunder[running]),
+                        took_an_unproved_move=share((torch.gather(lab["label"], 1, taken[:, None])[:, 0] == 3)[running]),
+                        label_states_ms=round(ms, 2), nodes=int(count))
+            moves.append(line)
+            progress({name: line})
+            env.step(action, observe=False)
+        won = env.state == 1
+        lost = ~won
+        got = dict(per_move=moves, win_rate=share(won), lost_episodes=int(lost.sum()),
+                   lost_with_a_proved_first_blunder=share((first >= 0)[lost]),
+                   lost_with_a_proved_first_blunder_and_every_earlier_move_proved=share(((first >= 0) & ~open_before)[lost]),
+                   won_with_a_proved_blunder=share((first >= 0)[won]),
+                   first_blunder_move_histogram=torch.bincount(first[first >= 0], minlength=M_new).tolist(),
+                   label_states_ms_mean=round(spent * 1e3 / M_new, 2), nodes_per_second=round(nodes / spent, 1))
+        env.terminate()
+        out["players"][name] = got
+        progress({name: {k: v for k, v in got.items() if k != "per_move"}})
+    res = subprocess.run(["bash", os.path.join(ROOT, "tools", "kernel_resources.sh"), T._learn_lib.build_library()],
+                         capture_output=True, text=True, cwd=ROOT)
+    out["kernel"] = [" ".join(l.split()) for l in res.stdout.splitlines() if "placement_exact" in l]
+    out["not_measured"] = ("other weight rows, the fourteen features and spare_weight other than 0; max_nodes other than this one; other pools and "
+                           "seeds; learners; label_states' time includes the state export, config_index and the host's launch, not the kernel alone")
     return out
 
 
