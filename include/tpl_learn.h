@@ -1149,6 +1149,50 @@ int tpl_ntuple_exact(const int16_t* rows, const uint8_t* pieces, int64_t n, int3
                      float r_line, float r_win, float r_lose, float gamma, int32_t max_nodes, int32_t shortest, uint8_t* solved,
                      uint8_t* proved, int32_t* solution_len, uint8_t* actions, int32_t* bound, uint32_t* nodes, void* stream);
 
+/* The ranking update: what a proved move label teaches a table (csrc/learn/ntuple_rank.hip).  tpl_placement_exact_labels labels every
+ * placement of a board 1 (proved winning), 2 (proved losing) or 3 (unproved).  tpl_ntuple_rank reads such a row beside the board and a
+ * table and says whether the table's one-ply policy already prefers a proved win to every proved loss; where it does not, it names the
+ * hardest pair and the two afterstates to move.  It writes nothing but its outputs: THE TABLE IS READ ONLY.
+ *
+ * For a state s, its row label u8 [40], a table of one of the four plain forms (told apart by `entries` exactly as tpl_ntuple_exact
+ * tells them: "2x4", "3x3", "feat", "feat+spare"; any other count is refused with the message that names the four), reward parameters, a
+ * discount gamma, a margin and prune = 0 or 1:
+ *   SCORES.  score(a) of every distinct placement a (a == canonical(cur, a)) is tpl_ntuple_act's score, bit for bit: the move and the pop
+ *     of tpl_afterstates, reward = the reward rule on (rows cleared, state), score = reward where the move ends the game and
+ *     reward + gamma * V(afterstate) where it runs -- one product and one add, each rounded once, never fused.  A finished board scores 0.
+ *     prune is a flag of the budget form alone (prune = 1 with any other form is refused): with it a move into a RUNNING DEAD board is
+ *     scored as lost at the limit, reward with r_lose and no gamma * V, as tpl_ntuple_act_budget scores it.
+ *   SETS.  W = the distinct a with label[a] == 1, X = the distinct a with label[a] == 2.  Labels 0 and 3 take part in nothing, and
+ *     neither does any other byte value, nor any label on an action that is not distinct: the row is not trusted to be well formed.
+ *     LABEL 3 PROVES NOTHING AND TEACHES NOTHING.
+ *   THE PAIR.  win = the lowest a at the maximum of score over W, loss = the lowest a at the maximum of score over X, greedy = the lowest
+ *     a at the maximum over all distinct placements -- tpl_ntuple_act's action at epsilon 0; -0 and +0 tie (ordered_bits), as everywhere.
+ *     A finished state, an empty W or an empty X is UNDECIDED: win = loss = 255, gap = 0, violated = 0, both errors 0, and both
+ *     afterstates are the state itself, bit for bit (tpl_ntuple_act's convention).  greedy is still written, 0 for a finished board.
+ *   THE VIOLATION.  gap = score(win) - score(loss), one float32 subtraction on the scores' own bits; violated = (gap <= margin).  A tie
+ *     violates at margin 0 -- under the zero table every score ties and every decided node must teach.  A NaN gap does not violate.
+ *   WHAT IS TAUGHT, a perceptron step on the hardest pair: err_win = +1.0f if violated AND score(win) held a gamma * V term (the child
+ *     runs and the prune did not end it), else 0; err_loss = -1.0f under the same condition for loss, else 0.  A side that ended the game
+ *     has no value to move and teaches nothing; the node can still be violated and is reported so.
+ *     win_a / win_b and loss_a / loss_b are the two afterstates after the pop exactly as tpl_ntuple_act writes `after`: the true board,
+ *     the spare bit kept, also under the prune.
+ * TEACHING is two calls of the existing update entry of the table's form (tpl_ntuple_update_trace_shaped, _feature or _budget) on a ring
+ * of one slot (slots = 1, head = 0, horizon = 1): the win planes with err_win, then the loss planes with err_loss; each adds
+ * rint(rate * err) to the entries of its afterstate, with `symmetric` as given.  This entry never writes the table and the update never
+ * reads it, so one step leaves the same bytes in any order of arrival, and two runs give the same table.
+ *
+ * One kernel per form (ntuple_rank_kernel, ntuple_rank3_kernel, ntuple_rank_feature_kernel, ntuple_rank_budget_kernel) in
+ * tpl_ntuple_act's frame: eight boards a block, 40 lanes a board, three LDS maxima a board where the policy has one, no exploration
+ * draw, no scratch.  Read: 32 + 40 bytes a board and the table gathers.  Written, each in full: win, loss, greedy, violated u8 [n];
+ * gap, err_win, err_loss f32 [n]; win_a, win_b, loss_a, loss_b [n] 16-byte words.
+ * Refused before any HIP call, under the entry's own name: an `entries` that is none of the four, first; then tpl_ntuple_act's plane, n,
+ * L, M and table checks; a NULL label; any NULL output; a misaligned (16 bytes) afterstate plane or (4 bytes) float output; a margin,
+ * gamma or reward parameter that is not finite; prune other than 0 or 1, or prune = 1 outside the budget form. */
+int tpl_ntuple_rank(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const int32_t* table, int64_t entries,
+                    const uint8_t* label, float r_line, float r_win, float r_lose, float gamma, float margin, int32_t prune,
+                    uint8_t* win, uint8_t* loss, uint8_t* greedy, uint8_t* violated, float* gap, float* err_win, float* err_loss,
+                    void* win_a, void* win_b, void* loss_a, void* loss_b, void* stream);
+
 /* Per-configuration tallies and the resampled pool (csrc/learn/curriculum.hip).  Which pool entry a board plays is not stored anywhere:
  * the environment derives it (csrc/tpl_device.h, tetris_piclim.h's tpl_create).  These three entries derive it the same way from the
  * side and only READ the environment -- the planes (tpl_state_ptrs), the step clocks (tpl_clock_ptr: one uint64 per 32 boards) and the

@@ -18,7 +18,8 @@ __all__ = ["BatchedTetris", "Tetris", "Snapshot", "OBS_DIM", "NUM_ACTIONS", "RUN
            "NTUPLE_STAGES", "ntuple_stage_map", "ntuple_staged", "ntuple_stages", "ntuple_map", "ntuple_is_staged", "NTUPLE_FEATURE_FORMS",
            "ntuple_feature_bins", "NTUPLE_BUDGET_FORMS", "ntuple_budget", "ntuple_budget_bins", "solve_configs", "prove_configs", "ntuple_prove_configs", "tighten_pool", "CLASSICAL_WEIGHTS", "FEATURE_NAMES",
            "MOVE_FEATURE_NAMES", "DELLACHERIE_WEIGHTS", "move_bound", "config_bound", "config_index", "PoolTally", "resample_pool",
-           "curriculum_weights", "PoolCurriculum", "prove_nodes", "label_moves", "label_states", "blunders"]
+           "curriculum_weights", "PoolCurriculum", "prove_nodes", "label_moves", "label_states", "blunders",
+           "NTupleRanker", "LabelSet", "collect_labels", "label_agreement"]
 
 
 def __getattr__(name):
@@ -46,10 +47,10 @@ def __getattr__(name):
     if name in ("NTuplePolicy", "NTupleBeamPolicy", "NTupleLearner", "ntuple_table", "ntuple_value", "ntuple_is_symmetric", "ntuple_coherence",
                 "ntuple_step_sizes", "ntuple_shape", "NTUPLE_SHAPES", "ntuple_parts", "NTUPLE_SUMS", "NTUPLE_ENTRIES_SUM",
                 "NTUPLE_STAGES", "ntuple_stage_map", "ntuple_staged", "ntuple_stages", "ntuple_map", "ntuple_is_staged", "NTUPLE_FEATURE_FORMS",
-                "ntuple_feature_bins", "NTUPLE_BUDGET_FORMS", "ntuple_budget", "ntuple_budget_bins"):
+                "ntuple_feature_bins", "NTUPLE_BUDGET_FORMS", "ntuple_budget", "ntuple_budget_bins", "NTupleRanker"):
         return getattr(importlib.import_module(__name__ + ".ntuple"), name)
     if name in ("solve_configs", "prove_configs", "ntuple_prove_configs", "tighten_pool", "CLASSICAL_WEIGHTS", "config_bound", "prove_nodes",
-                "label_moves", "label_states", "blunders"):
+                "label_moves", "label_states", "blunders", "LabelSet", "collect_labels", "label_agreement"):
         return getattr(importlib.import_module(__name__ + ".solve"), name)
     if name in ("config_index", "PoolTally", "resample_pool", "curriculum_weights", "PoolCurriculum"):
         return getattr(importlib.import_module(__name__ + ".curriculum"), name)

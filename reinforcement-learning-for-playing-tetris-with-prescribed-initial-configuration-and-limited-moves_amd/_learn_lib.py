@@ -25,7 +25,7 @@ _UNITS = [os.path.join(_LEARN_CSRC, f) for f in ("replay.hip", "pack.hip", "prio
                                                       "beam_move.hip", "solve_move.hip", "bound.hip", "beam_bound.hip",
                                                       "solve_bound.hip", "beam_move_bound.hip", "solve_move_bound.hip",
                                                       "exact.hip", "exact_move.hip", "ntuple_exact.hip", "curriculum.hip", "exact_nodes.hip",
-                                                      "exact_nodes_move.hip", "heuristic.hip")]
+                                                      "exact_nodes_move.hip", "ntuple_rank.hip", "heuristic.hip")]
 
 # entry points declared in include/tpl_learn.h (tests check that the .so exports every one of them)
 LEARN_SYMBOLS = [
@@ -51,6 +51,7 @@ LEARN_SYMBOLS = [
     "tpl_placement_exact", "tpl_placement_exact_move", "tpl_ntuple_exact",
     "tpl_config_index", "tpl_pool_tally", "tpl_pool_resample",
     "tpl_placement_exact_nodes", "tpl_placement_exact_nodes_move", "tpl_placement_exact_labels", "tpl_placement_exact_labels_move",
+    "tpl_ntuple_rank",
 ]
 NSTEP_MAX = 16
 BEAM_MAX_DEPTH, BEAM_MAX_WIDTH = 12, 64
@@ -231,6 +232,9 @@ def lib() -> C.CDLL:
     # the table-ordered exact search: the table and its entry count for the weights, the reward and gamma for spare_weight
     L.tpl_ntuple_exact.argtypes = [vp, vp, i64, i32, i32, vp, i64, f32, f32, f32, f32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.tpl_ntuple_exact.restype = i32
+    # the ranking update's chooser: the planes, the table and its entry count, the label rows, then the eleven outputs
+    L.tpl_ntuple_rank.argtypes = [vp, vp, i64, i32, i32, vp, i64, vp, f32, f32, f32, f32, f32, i32] + [vp] * 12
+    L.tpl_ntuple_rank.restype = i32
     # per-configuration tallies and the resampled pool (csrc/learn/curriculum.hip)
     L.tpl_config_index.argtypes = [vp, vp, vp, i64, i64, u64, i32, i64, i64, vp, vp, vp]
     L.tpl_pool_tally.argtypes = [vp, vp, vp, i64, i32, i32, vp, i32, i64, u64, i32, i64, i64, vp, vp, vp, vp, vp]
@@ -1709,6 +1713,145 @@ def _lowest_at_max(x, axis):
     x = np.asarray(x, dtype=np.float32)
     at = np.argmax(x == x.max(axis=axis, keepdims=True), axis=axis)            # == : -0 and +0 are equal
     return np.take_along_axis(x, np.expand_dims(at, axis), axis=axis).squeeze(axis), at
+
+
+# The rule of tpl_ntuple_rank (include/tpl_learn.h) on the host, from the ROW form: host_moves, canonical_actions, move_bound and
+# ntuple_value above, the arg-max by _lowest_at_max.  The device scores a (board, action) pair a lane and takes three 64-bit maxima in
+# LDS (csrc/learn/ntuple_rank.hip) -- the two share nothing.
+NTUPLE_RANK_FORMS = NTUPLE_EXACT_FORMS
+RANK_UNDECIDED = 255
+RANK_OUTPUTS = ("win", "loss", "greedy", "violated", "gap", "err_win", "err_loss", "win_rows", "win_fields", "loss_rows", "loss_fields")
+
+
+def _rank_table(table) -> np.ndarray:
+    """A table of one of the four plain forms tpl_ntuple_rank reads; a sum or a staged table, or anything else, is refused."""
+    counts = {ntuple_entries_of(name): name for name in NTUPLE_RANK_FORMS}
+    if not isinstance(table, np.ndarray) or table.dtype != np.int32 or table.ndim != 1 or table.shape[0] not in counts:
+        sizes = ", ".join(f"{k} ({v!r})" for k, v in counts.items())
+        raise ValueError(f"table must be an int32 array of {sizes} entries, one of the four plain forms: a sum or a staged table is "
+                         "taught no ranking")
+    return table
+
+
+def _rank_numbers(gamma, reward, margin, prune, table):
+    try:
+        with np.errstate(over="ignore"):
+            g, m = np.float32(gamma), np.float32(margin)
+            r_line, r_win, r_lose = (np.float32(v) for v in reward)
+    except (TypeError, ValueError):
+        raise ValueError("gamma and margin must be numbers and reward three numbers (r_line, r_win, r_lose)") from None
+    if not all(np.isfinite(v) for v in (g, m, r_line, r_win, r_lose)):
+        raise ValueError("gamma, margin and reward must be finite (in float32)")
+    if not isinstance(prune, (bool, np.bool_)):
+        raise ValueError("prune must be True or False")
+    if prune and table.shape[0] != NTUPLE_ENTRIES_BUDGET:
+        raise ValueError('prune=True is the dead-board prune of a budget table ("feat+spare") alone')
+    return g, m, (r_line, r_win, r_lose)
+
+
+def ntuple_rank(table, rows, piece, L: int, M: int, lines, moves, state, label, gamma, reward, margin, prune) -> dict:
+    """The rule of tpl_ntuple_rank (include/tpl_learn.h) for K states in row form: rows uint16 [K, 20], piece int [K, 2] -- the falling
+    piece and the one behind it, window entries 0 and 1 --, lines, moves and state [K], label uint8 [K, 40]; table an int32 array of one
+    of NTUPLE_RANK_FORMS; gamma, margin and reward = (r_line, r_win, r_lose) finite; prune a bool, True under a "feat+spare" table only.
+    Returns a dict of RANK_OUTPUTS: win, loss, greedy, violated uint8 [K]; gap, err_win, err_loss float32 [K]; and the two afterstates
+    in row form, win_rows / loss_rows uint16 [K, 20] and win_fields / loss_fields int64 [K, 3] = (lines, moves, state) -- the state itself
+    where the node is undecided; the falling piece of a decided afterstate is piece[:, 1]."""
+    table = _rank_table(table)
+    L, M = int(L), int(M)
+    if not (1 <= L <= 250 and 1 <= M <= 254):
+        raise ValueError("L and M must be in [1, 250] and [1, 254]")
+    g, margin, (r_line, r_win, r_lose) = _rank_numbers(gamma, reward, margin, prune, table)
+    rows = np.asarray(rows)
+    rows = (rows.view(np.uint16) if rows.dtype == np.int16 else rows.astype(np.uint16)).reshape(-1, 20)
+    k = rows.shape[0]
+    piece = np.asarray(piece).astype(np.int64) & 7
+    label = np.asarray(label)
+    if k < 1 or piece.shape != (k, 2) or label.shape != (k, NUM_ACTIONS) or label.dtype != np.uint8:
+        raise ValueError("rows must be [K, 20], piece [K, 2] and label uint8 [K, 40] with K >= 1")
+    lines, moves, state = (np.broadcast_to(np.asarray(x).astype(np.int64), (k,)) for x in (lines, moves, state))
+    running = state == STATE_RUNNING
+    acts = np.arange(NUM_ACTIONS)
+    distinct = canonical_actions(piece[:, :1], acts[None, :]) == acts[None, :]
+    # every distinct placement of every running board, played once
+    node, a = np.nonzero(distinct & running[:, None])
+    score = np.zeros((k, NUM_ACTIONS), np.float32)                          # a finished board scores 0
+    valued = np.zeros((k, NUM_ACTIONS), bool)
+    child_rows = np.repeat(rows[:, None, :], NUM_ACTIONS, axis=1)
+    child = np.repeat(np.stack([lines, moves, state], axis=1)[:, None, :], NUM_ACTIONS, axis=1)
+    if node.size:
+        r2, cleared, l2, m2, s2 = host_moves(rows[node], piece[node, 0], a // 10, a % 10, L, M, lines[node], moves[node])
+        scored = np.where(move_bound(r2, L, M, l2, m2, s2)["dead"], STATE_LOST_LIMIT, s2) if prune else s2
+        with np.errstate(over="ignore", invalid="ignore"):
+            r = r_line * cleared.astype(np.float32)
+            r = np.where(scored == STATE_WON, r + r_win, r)
+            r = np.where(scored >= STATE_LOST_LIMIT, r + r_lose, r).astype(np.float32)
+            v = ntuple_value(table, r2, piece[node, 1], L, M, l2, m2, scored)
+            score[node, a] = np.where(scored == STATE_RUNNING, r + g * v, r).astype(np.float32)
+        valued[node, a] = scored == STATE_RUNNING
+        child_rows[node, a] = r2
+        child[node, a] = np.stack([l2, m2, s2], axis=1)                     # the true board, also under the prune
+    wins = distinct & running[:, None] & (label == 1)
+    losses = distinct & running[:, None] & (label == 2)
+    decided = wins.any(axis=1) & losses.any(axis=1)
+    at = np.arange(k)
+    masked = lambda m: np.where(m, score, -np.inf).astype(np.float32)
+    _, greedy = _lowest_at_max(masked(distinct), 1)
+    s_win, win = _lowest_at_max(masked(wins), 1)
+    s_loss, loss = _lowest_at_max(masked(losses), 1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        zero = np.float32(0.0)
+        gap = (np.where(decided, s_win, zero).astype(np.float32) - np.where(decided, s_loss, zero).astype(np.float32)).astype(np.float32)
+        violated = decided & (gap <= margin)
+    out = dict(win=np.where(decided, win, RANK_UNDECIDED).astype(np.uint8), loss=np.where(decided, loss, RANK_UNDECIDED).astype(np.uint8),
+               greedy=greedy.astype(np.uint8), violated=violated.astype(np.uint8), gap=gap,
+               err_win=np.where(violated & valued[at, win], np.float32(1.0), np.float32(0.0)).astype(np.float32),
+               err_loss=np.where(violated & valued[at, loss], np.float32(-1.0), np.float32(0.0)).astype(np.float32))
+    own = np.stack([lines, moves, state], axis=1)
+    for side, b in (("win", win), ("loss", loss)):
+        out[side + "_rows"] = np.where(decided[:, None], child_rows[at, b], rows).astype(np.uint16)
+        out[side + "_fields"] = np.where(decided[:, None], child[at, b], own).astype(np.int64)
+    return out
+
+
+def ntuple_rank_step(table, rows, piece, L: int, M: int, lines, moves, state, label, gamma, reward, margin, prune, rate,
+                     symmetric: bool = False) -> dict:
+    """One teaching step, in place on `table`: ntuple_rank, then ntuple_update_trace twice on a ring of one slot -- the win afterstates
+    with err_win, then the loss afterstates with err_loss, each adding rint(rate * err) to its entries (symmetric: to the reflected
+    board's as well).  Returns ntuple_rank's dict, taken BEFORE the adds."""
+    out = ntuple_rank(table, rows, piece, L, M, lines, moves, state, label, gamma, reward, margin, prune)
+    piece = np.asarray(piece).astype(np.int64) & 7
+    falling = np.where(out["win"] == RANK_UNDECIDED, piece[:, 0], piece[:, 1])      # an undecided node's afterstate is the state itself
+    for side in ("win", "loss"):
+        f = out[side + "_fields"]
+        ntuple_update_trace(table, [(out[side + "_rows"], falling, f[:, 0], f[:, 1], f[:, 2])], L, M, out["err_" + side], rate, 1.0,
+                            symmetric)
+    return out
+
+
+def rank_fit_order(count: int, epochs: int, seed: int) -> np.ndarray:
+    """The order in which `fit` visits `count` nodes: int64 [epochs, count], one permutation an epoch from numpy's default generator
+    seeded with `seed` -- the one order of NTupleRanker.fit and of its mirror below."""
+    gen = np.random.default_rng(int(seed))
+    return np.stack([gen.permutation(int(count)) for _ in range(int(epochs))]).astype(np.int64).reshape(int(epochs), int(count))
+
+
+def ntuple_rank_fit(table, rows, piece, L: int, M: int, lines, moves, state, label, gamma, reward, margin, prune, rate,
+                    symmetric: bool, epochs: int, batch: int, seed: int = 0) -> list:
+    """NTupleRanker.fit on the host, in place on `table`: every epoch walks the nodes in rank_fit_order's permutation, `batch` at a time
+    (the last minibatch may be short), one ntuple_rank_step each; returns the violated count of every epoch -- each node counted when
+    its minibatch was ranked, before that minibatch's adds."""
+    rows, piece, label = np.asarray(rows), np.asarray(piece), np.asarray(label)
+    lines, moves, state = (np.asarray(x) for x in (lines, moves, state))
+    counts = []
+    for order in rank_fit_order(rows.shape[0], epochs, seed):
+        total = 0
+        for lo in range(0, order.size, int(batch)):
+            pick = order[lo:lo + int(batch)]
+            out = ntuple_rank_step(table, rows[pick], piece[pick], L, M, lines[pick], moves[pick], state[pick], label[pick], gamma, reward,
+                                   margin, prune, rate, symmetric)
+            total += int(out["violated"].sum())
+        counts.append(total)
+    return counts
 
 
 def ntuple_search_choice(reward1, done1, distinct1, reward2, done2, value2, distinct2, gamma, running=None):

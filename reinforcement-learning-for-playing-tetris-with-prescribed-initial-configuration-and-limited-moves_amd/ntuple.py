@@ -49,6 +49,12 @@ learning on the device (the rule: include/tpl_learn.h; the kernels: csrc/learn/n
     ntuple_budget_bins(source)    uint8 [K, 10]: the ten bins a budget table is read at
     NTuplePolicy(..., bound=True), NTupleBeamPolicy(..., bound=True), NTupleLearner(..., shape="feat+spare", bound=True)
                                   the dead-board prune, for a budget table only
+    NTupleRanker(table, L, M, gamma, reward, rate, margin, bound, symmetric)
+                                  a supervised ranking update from proved move labels (T.label_moves): rank(planes, label) names the
+                                  best-scored proved win, the best-scored proved loss and the greedy move of every state in ONE
+                                  launch; step() then adds rint(rate) on the win's afterstate and subtracts it on the loss's through
+                                  the update kernels above; fit(labelset, epochs, batch, seed).  One of the four plain forms, taught in
+                                  place; label 3 proves nothing and teaches nothing
 
 The value is a sum of table entries, one per 2 x 4 window of the board that is not empty, chosen by the falling piece, plus one
 per (lines left, moves left); the update adds rint(rate * error) to the same entries.  Everything is integer, so two trainings
@@ -102,7 +108,7 @@ from .lookahead import _MAX_BOARDS, _boards, _ptr, _state_ptrs
 __all__ = ["NTUPLE_ENTRIES", "NTUPLE_ENTRIES_SUM", "NTUPLE_SHAPES", "NTUPLE_SUMS", "ntuple_shape", "ntuple_parts", "ntuple_table", "ntuple_value", "ntuple_is_symmetric", "ntuple_coherence", "ntuple_step_sizes",
            "NTuplePolicy", "NTupleBeamPolicy", "NTupleLearner", "NTUPLE_FEATURE_FORMS", "ntuple_feature_bins", "NTUPLE_BUDGET_FORMS",
            "ntuple_budget", "ntuple_budget_bins", "NTUPLE_STAGES", "ntuple_stage_map", "ntuple_staged", "ntuple_stages",
-           "ntuple_map", "ntuple_is_staged"]
+           "ntuple_map", "ntuple_is_staged", "NTupleRanker"]
 
 _STATE_WON = 1                                                 # bits 28..29 of B.y: 0 running, 1 won, 2 and 3 lost
 _FINISHED_B_Y = _STATE_WON << 28                               # B.y of a state that is finished and otherwise empty
@@ -867,3 +873,145 @@ class NTupleLearner:
         if tally is not None:
             result.update(episodes_by_config=tally.episodes, wins_by_config=tally.wins)
         return result
+
+
+RANK_OUTPUTS = ("win", "loss", "greedy", "violated", "gap", "err_win", "err_loss", "win_a", "win_b", "loss_a", "loss_b")
+
+
+def _rank_table(table) -> torch.Tensor:
+    """A table the ranking update teaches: a contiguous int32 tensor of one of the four plain forms on a GPU."""
+    counts = {_learn_lib.ntuple_entries_of(name): name for name in _learn_lib.NTUPLE_RANK_FORMS}
+    sizes = ", ".join(f"{k} ({v!r})" for k, v in counts.items())
+    if not isinstance(table, torch.Tensor) or table.dim() != 1 or table.dtype != torch.int32 or not table.is_contiguous():
+        raise ValueError(f"table must be a contiguous int32 tensor of {sizes} entries (ntuple_table)")
+    if int(table.shape[0]) not in counts:
+        raise ValueError(f"table must be of one of the four plain forms, {sizes} entries: a sum or a staged table is taught no ranking; "
+                         f"got {int(table.shape[0])} entries")
+    if table.device.type != "cuda":
+        raise ValueError(f"table must be on a GPU (cuda:N), not on {table.device}: the ranking update has no CPU path")
+    return table
+
+
+class NTupleRanker:
+    """A supervised ranking update of an n-tuple table from proved move labels (the rule: include/tpl_learn.h, tpl_ntuple_rank; the
+    kernel: csrc/learn/ntuple_rank.hip).  A label row (T.label_moves, T.label_states) says which placements of a board are proved
+    winning (1) and which proved losing (2); **label 3 proves nothing and teaches nothing**.  rank() scores every distinct placement as
+    NTuplePolicy does, names the best-scored proved win, the best-scored proved loss and the greedy choice, and says whether the table
+    prefers the win by more than `margin`; step() then adds rint(rate) to the entries of the win's afterstate and subtracts it from the
+    loss's, through the update kernels the learner uses -- a perceptron step on the hardest pair.  The table is read by one kernel and
+    only added to by the others, so a step leaves the same bytes in any order and two runs give the same table.
+
+    `table` is one of the four plain forms ("2x4", "3x3", "feat", "feat+spare") on a GPU and is TAUGHT IN PLACE, as the policies read it
+    in place.  L and M are the game's; reward = (r_line, r_win, r_lose) as an environment's.  bound=True (a "feat+spare" table only) is
+    the dead-board prune of NTuplePolicy(bound=True); symmetric=True adds every update to the reflected board's entries as well."""
+
+    def __init__(self, table: torch.Tensor, L: int, M: int, gamma: float = 0.99, reward=(1.0, 0.0, 0.0), rate: float = 8.0,
+                 margin: float = 0.0, bound: bool = False, symmetric: bool = False):
+        self.table = _rank_table(table)
+        self.shape = ntuple_shape(self.table)
+        if isinstance(L, bool) or not isinstance(L, int) or not 1 <= L <= 250:
+            raise ValueError(f"L must be an integer in [1, 250], got {L!r}")
+        if isinstance(M, bool) or not isinstance(M, int) or not 1 <= M <= 254:
+            raise ValueError(f"M must be an integer in [1, 254], got {M!r}")
+        self.L, self.M = int(L), int(M)
+        self.gamma, self.rate, self.margin = _finite("gamma", gamma), _finite("rate", rate), _finite("margin", margin)
+        if isinstance(reward, (str, bytes)) or not hasattr(reward, "__len__") or len(reward) != 3:
+            raise ValueError(f"reward must be three numbers (r_line, r_win, r_lose), got {reward!r}")
+        self.reward = tuple(_finite(f"reward[{j}]", v) for j, v in enumerate(reward))
+        self.bound = _bound(bound, self.shape)
+        if not isinstance(symmetric, bool):
+            raise ValueError(f"symmetric must be True or False, got {symmetric!r}")
+        self.symmetric = symmetric
+        self.device = self.table.device
+
+    def buffers(self, k: int) -> dict:
+        """The eleven outputs of rank() for k states, uninitialised, on the table's device: pass them as out= to allocate nothing."""
+        d, k = self.device, _count("k", k, 1)
+        out = {name: torch.empty(k, dtype=torch.uint8, device=d) for name in RANK_OUTPUTS[:4]}
+        out.update({name: torch.empty(k, dtype=torch.float32, device=d) for name in RANK_OUTPUTS[4:7]})
+        out.update({name: torch.empty((k, 4), dtype=torch.int32, device=d) for name in RANK_OUTPUTS[7:]})
+        return out
+
+    def _inputs(self, planes, label, out):
+        k, a, b = _planes(planes, self.device, "planes")
+        if not 1 <= k <= _MAX_BOARDS:
+            raise ValueError(f"rank takes 1 .. {_MAX_BOARDS} states")
+        if (not isinstance(label, torch.Tensor) or label.dtype != torch.uint8 or tuple(label.shape) != (k, 40) or label.device != self.device
+                or not label.is_contiguous()):
+            raise ValueError(f"label must be a contiguous uint8 tensor of shape ({k}, 40) on {self.device}")
+        if out is None:
+            out = self.buffers(k)
+        else:
+            if not isinstance(out, dict) or set(out) != set(RANK_OUTPUTS):
+                raise ValueError(f"out must be a dict of {RANK_OUTPUTS} (NTupleRanker.buffers)")
+            for j, name in enumerate(RANK_OUTPUTS):
+                dtype = torch.uint8 if j < 4 else torch.float32 if j < 7 else torch.int32
+                shape = (k,) if j < 7 else (k, 4)
+                t = out[name]
+                if (not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or t.device != self.device
+                        or not t.is_contiguous()):
+                    raise ValueError(f"out[{name!r}] must be a contiguous {dtype} tensor of shape {shape} on {self.device}")
+        return k, a, b, out
+
+    @torch.no_grad()
+    def rank(self, planes, label: torch.Tensor, out: Optional[dict] = None) -> dict:
+        """tpl_ntuple_rank on K states: planes a pair of int32 [K, 4] tensors, label uint8 [K, 40], both on the table's device.
+        Returns a dict of device tensors: win, loss, greedy, violated uint8 [K] (win = loss = 255 where the node is undecided: a
+        finished board, or no distinct placement labelled 1, or none labelled 2); gap, err_win, err_loss float32 [K]; win_a, win_b,
+        loss_a, loss_b int32 [K, 4], the two afterstates.  The table is only read.  One launch, no host sync, and no allocation when
+        out= (buffers(K)) is given."""
+        k, a, b, out = self._inputs(planes, label, out)
+        stream = torch._C._cuda_getCurrentRawStream(self.device.index)
+        check(_learn_lib.lib().tpl_ntuple_rank(a.data_ptr(), b.data_ptr(), k, self.L, self.M, self.table.data_ptr(), int(self.table.shape[0]),
+                                               label.data_ptr(), *self.reward, self.gamma, self.margin, int(self.bound),
+                                               *(out[name].data_ptr() for name in RANK_OUTPUTS), stream))
+        return out
+
+    def _update(self, k: int, a: torch.Tensor, b: torch.Tensor, error: torch.Tensor, stream) -> None:
+        """rint(rate * error) on the entries of k afterstates: the update entry of the table's form on a ring of one slot."""
+        lib = _learn_lib.lib()
+        head = (a.data_ptr(), b.data_ptr(), k, 1, 0, 1, self.L, self.M, self.table.data_ptr(), error.data_ptr(), self.rate, 1.0,
+                int(self.symmetric))
+        if self.shape in NTUPLE_BUDGET_FORMS:
+            check(lib.tpl_ntuple_update_trace_budget(*head, stream))
+        elif self.shape in NTUPLE_FEATURE_FORMS:
+            check(lib.tpl_ntuple_update_trace_feature(*head, stream))
+        else:
+            check(lib.tpl_ntuple_update_trace_shaped(*head, NTUPLE_SHAPE_IDS[self.shape], stream))
+
+    @torch.no_grad()
+    def step(self, planes, label: torch.Tensor, out: Optional[dict] = None) -> dict:
+        """One teaching step: rank(), then the update of the win afterstates with err_win and of the loss afterstates with err_loss.
+        Three enqueues, no host sync.  Returns rank()'s dict, which describes the table BEFORE the adds."""
+        out = self.rank(planes, label, out)
+        k = int(label.shape[0])
+        stream = torch._C._cuda_getCurrentRawStream(self.device.index)
+        self._update(k, out["win_a"], out["win_b"], out["err_win"], stream)
+        self._update(k, out["loss_a"], out["loss_b"], out["err_loss"], stream)
+        return out
+
+    @torch.no_grad()
+    def fit(self, labelset, epochs: int, batch: int, seed: int = 0) -> list:
+        """`epochs` passes over a LabelSet (anything with planes_a, planes_b int32 [K, 4] and label uint8 [K, 40] on the table's device),
+        `batch` nodes a step in the order of a permutation seeded by `seed` (_learn_lib.rank_fit_order; the last minibatch of an epoch
+        may be short).  Returns the violated count of every epoch -- each node counted when its minibatch was ranked, before that
+        minibatch's adds -- with one host read an epoch."""
+        epochs, batch, seed = _count("epochs", epochs, 1), _count("batch", batch, 1), _count("seed", seed)
+        k, a, b = _planes((labelset.planes_a, labelset.planes_b), self.device, "labelset planes")
+        label = labelset.label
+        if k < 1 or not isinstance(label, torch.Tensor) or label.dtype != torch.uint8 or tuple(label.shape) != (k, 40) or label.device != self.device:
+            raise ValueError(f"labelset must hold at least one node, with label a uint8 tensor of shape ({k}, 40) on {self.device}")
+        order = torch.from_numpy(_learn_lib.rank_fit_order(k, epochs, seed)).to(self.device)
+        buffers = {}
+        counts = []
+        for e in range(epochs):
+            total = torch.zeros((), dtype=torch.int64, device=self.device)
+            for lo in range(0, k, batch):
+                pick = order[e, lo:lo + batch]
+                size = int(pick.shape[0])
+                if size not in buffers:
+                    buffers[size] = self.buffers(size)
+                out = self.step((a[pick], b[pick]), label[pick], buffers[size])
+                total += out["violated"].sum(dtype=torch.int64)
+            counts.append(int(total))
+        return counts

@@ -22,6 +22,10 @@ of at move 0 (tpl_placement_exact_nodes; csrc/learn/exact_nodes.hip): for the se
 (L - lines, M - moves).  `label_moves` applies it to the children of a node and labels every move proved winning, proved losing
 or unproved (tpl_placement_exact_labels), `label_states` does so for the boards of an environment, and `blunders` marks where a
 proved-losing move was taken although a proved-winning one was there.
+
+`collect_labels` plays a policy on an environment with a pool and keeps the boards the labels decide -- a proved win and a proved loss
+among their moves -- in a `LabelSet`, the input of `NTupleRanker.fit` (ntuple.py); `label_agreement` counts how often a table's greedy
+move is labelled 1, 2 and 3 on such nodes.
 """
 from __future__ import annotations
 
@@ -30,7 +34,7 @@ import numpy as np
 from ._learn_lib import BEAM_MAX_WIDTH, EXACT_MAX_NODES, NUM_FEATURES, NUM_MOVE_FEATURES, SOLVE_MAX_MOVES
 
 __all__ = ["CLASSICAL_WEIGHTS", "solve_configs", "prove_configs", "ntuple_prove_configs", "tighten_pool", "config_bound",
-           "prove_nodes", "label_moves", "label_states", "blunders"]
+           "prove_nodes", "label_moves", "label_states", "blunders", "LabelSet", "collect_labels", "label_agreement"]
 
 # cleared, won, lost, holes, aggregate height, max height, bumpiness, row and column transitions, wells, rows with holes, hole depth:
 # the classical signs, a sensible default for the supply (0.99925 of a carved L = 10 / M = 40 pool at one ply)
@@ -443,6 +447,109 @@ def blunders(label_before, action):
         raise ValueError("label_before must be [n, 40] and action [n]")
     taken = label_before[np.arange(action.size), np.clip(action, 0, 39)]
     return ((label_before == 1).any(axis=1) & (taken == 2) & (action >= 0) & (action < 40)).astype(np.uint8)
+
+
+class LabelSet:
+    """Labelled nodes for NTupleRanker.fit, as device tensors: planes_a, planes_b int32 [K, 4] (the 32-byte states), label uint8
+    [K, 40] (label_moves' rows) and entry int32 [K] (the pool entry a node's game began from; -1 where none is known).  It starts
+    empty; append() adds nodes, split() cuts it in two by pool entry, so that no configuration has nodes on both sides."""
+
+    def __init__(self, device="cuda:0"):
+        import torch
+        self.device = torch.device(device)
+        self.planes_a = torch.empty((0, 4), dtype=torch.int32, device=self.device)
+        self.planes_b = torch.empty((0, 4), dtype=torch.int32, device=self.device)
+        self.label = torch.empty((0, 40), dtype=torch.uint8, device=self.device)
+        self.entry = torch.empty((0,), dtype=torch.int32, device=self.device)
+
+    def __len__(self) -> int:
+        return int(self.label.shape[0])
+
+    def append(self, planes_a, planes_b, label, entry=None) -> "LabelSet":
+        """k more nodes: planes int32 [k, 4] each, label uint8 [k, 40], entry [k] integers (None: -1).  Copies are kept."""
+        import torch
+        for name, t, dtype, tail in (("planes_a", planes_a, torch.int32, (4,)), ("planes_b", planes_b, torch.int32, (4,)),
+                                     ("label", label, torch.uint8, (40,))):
+            if not _is_tensor(t) or t.dtype != dtype or t.dim() != 2 or tuple(t.shape[1:]) != tail:
+                raise ValueError(f"{name} must be a {dtype} tensor of shape [k, {tail[0]}]")
+        k = int(label.shape[0])
+        if int(planes_a.shape[0]) != k or int(planes_b.shape[0]) != k:
+            raise ValueError("planes_a, planes_b and label must hold the same number of nodes")
+        if entry is None:
+            entry = torch.full((k,), -1, dtype=torch.int32, device=self.device)
+        if not _is_tensor(entry) or tuple(entry.shape) != (k,) or entry.dtype.is_floating_point:
+            raise ValueError(f"entry must be an integer tensor of shape [{k}]")
+        d = self.device
+        self.planes_a = torch.cat([self.planes_a, planes_a.to(d)]).contiguous()
+        self.planes_b = torch.cat([self.planes_b, planes_b.to(d)]).contiguous()
+        self.label = torch.cat([self.label, label.to(d)]).contiguous()
+        self.entry = torch.cat([self.entry, entry.to(device=d, dtype=torch.int32)]).contiguous()
+        return self
+
+    def select(self, keep) -> "LabelSet":
+        """The nodes where `keep` (bool [K]) is set, as a new set."""
+        out = LabelSet(self.device)
+        return out.append(self.planes_a[keep], self.planes_b[keep], self.label[keep], self.entry[keep])
+
+    def split(self, fraction: float = 0.5, by: str = "entry"):
+        """(first, second): by="entry" puts the nodes of the lowest ceil(fraction * E) of the E distinct pool entries into the first set
+        and the rest into the second -- no entry has nodes in both --; by="node" cuts the nodes themselves in the order they were
+        appended.  One host read."""
+        import math
+        import torch
+        if isinstance(fraction, bool) or not isinstance(fraction, (int, float)) or not 0.0 <= float(fraction) <= 1.0:
+            raise ValueError(f"fraction must be a number in [0, 1], got {fraction!r}")
+        if by not in ("entry", "node"):
+            raise ValueError(f'by must be "entry" or "node", got {by!r}')
+        if by == "node":
+            cut = math.ceil(float(fraction) * len(self))
+            first = torch.arange(len(self), device=self.device) < cut
+        else:
+            entries = torch.unique(self.entry)                 # sorted
+            cut = math.ceil(float(fraction) * int(entries.shape[0]))
+            first = torch.isin(self.entry, entries[:cut])
+        return self.select(first), self.select(~first)
+
+
+def collect_labels(env, pieces, policy, steps: int, max_nodes: int = 1 << 12, weights=None) -> LabelSet:
+    """Play `steps` steps of policy.act() on an environment that plays a pool and keep what the proofs decide.  Before every step the
+    boards are labelled (label_states, max_nodes a child), and every DECIDED running board -- at least one placement labelled 1 and at
+    least one labelled 2 -- goes into the returned LabelSet: a copy of its planes, its label row and its pool entry.  **Label 3 proves
+    nothing**: a board whose only labels are 3 and 0, or that has no proved win or no proved loss, is not kept.
+    The environment is read as label_states reads it and written only through env.step: it ends where `steps` plain steps of the same
+    actions leave it.  One host wait a step (the piece-id check of label_moves and the selection)."""
+    import torch
+    if isinstance(steps, bool) or not isinstance(steps, int) or steps < 1:
+        raise ValueError(f"steps must be an integer of at least 1, got {steps!r}")
+    if not hasattr(policy, "act"):
+        raise ValueError("policy must have an act() that returns the action of every board (NTuplePolicy, HeuristicPolicy, ...)")
+    out = LabelSet(env.device)
+    for _ in range(steps):
+        labels = label_states(env, pieces, weights=weights, max_nodes=max_nodes)
+        row = labels["label"]
+        decided = labels["running"] & (row == 1).any(dim=1) & (row == 2).any(dim=1)
+        a, b = env.raw_planes()
+        out.append(a[decided], b[decided], row[decided], labels["entry"][decided])
+        env.step(policy.act(), observe=False)
+    return out
+
+
+def label_agreement(table, planes, label, L: int, M: int, gamma: float = 0.99, reward=(1.0, 0.0, 0.0), margin: float = 0.0,
+                    bound: bool = False) -> dict:
+    """How a table's one-ply choice sits with the proofs, over the DECIDED nodes of (planes, label) -- running boards with a placement
+    labelled 1 and one labelled 2: decided (their number), greedy_win, greedy_loss and greedy_open (how often the table's greedy
+    placement, NTuplePolicy's at epsilon 0, is labelled 1, 2 and 3), violated (nodes whose best-scored proved win does not beat their
+    best-scored proved loss by more than `margin`) and nodes (all that were given).  This is what NTupleRanker optimises; a greedy move
+    labelled 3 is neither right nor wrong, **label 3 proves nothing**.  planes: a pair of int32 [K, 4] tensors; label uint8 [K, 40];
+    the other arguments are NTupleRanker's.  One launch and one host read; the table is only read."""
+    import torch
+    from .ntuple import NTupleRanker
+    out = NTupleRanker(table, L, M, gamma=gamma, reward=reward, margin=margin, bound=bound).rank(planes, label)
+    decided = out["win"] != 255
+    chosen = torch.gather(label, 1, out["greedy"].to(torch.int64)[:, None])[:, 0]
+    counts = torch.stack([decided.sum(), (decided & (chosen == 1)).sum(), (decided & (chosen == 2)).sum(), (decided & (chosen == 3)).sum(),
+                          out["violated"].sum(dtype=torch.int64)]).tolist()
+    return dict(zip(("decided", "greedy_win", "greedy_loss", "greedy_open", "violated"), (int(c) for c in counts)), nodes=int(label.shape[0]))
 
 
 def _number(name: str, v) -> float:

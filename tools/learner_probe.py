@@ -139,6 +139,11 @@ Parts:
               number the share of running boards whose every distinct move is proved and the blunder rate, the share of lost episodes
               with a proved first blunder, the milliseconds of a label_states call, and the nodes a second beside prove_configs on the
               same pool in the same run
+    rank      the ranking update from proved move labels (tpl_ntuple_rank, NTupleRanker, collect_labels, label_agreement): rank() of
+              each of the four forms beside NTuplePolicy.act() and a whole step() beside a learner step, alternated, at 2^20 boards;
+              then on the tight pool of the record split by pool entry: labels collected under the rate-8 "feat+spare" TD table, fit()
+              from that table and from zero, and on the held-out half label_agreement, the one-ply and the beam (3, 8) win rate before
+              and after, with one sweep over rate and margin
     solve     the whole-game beam solver (tpl_placement_solve, solve_configs) under the classical weights: the share of forward seeds
               0 .. 9,999 it solves at L=5 / M=20 and L=10 / M=40 at widths 1, 8, 16 and 64 beside the share the reference's solver marks
               winnable in the same forward_configs call, and the share of the sweeps' carved pool (65,536, seed 7) it solves; the
@@ -165,7 +170,8 @@ PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600, "priority": 600
          "ntuple_coherent_sweep": 1700, "ntuple_shape": 600, "ntuple_shape_sweep": 1100, "ntuple_beam": 1100,
          "ntuple_sum": 600, "ntuple_sum_sweep": 600, "ntuple_stage": 600, "ntuple_stage_sweep": 900,
          "ntuple_feature": 600, "ntuple_feature_sweep": 900, "solve": 900, "move_features": 1100, "bound": 900,
-         "ntuple_budget": 600, "ntuple_budget_sweep": 1100, "exact": 900, "ntuple_exact": 900, "labels": 900}
+         "ntuple_budget": 600, "ntuple_budget_sweep": 1100, "exact": 900, "ntuple_exact": 900, "labels": 900,
+         "rank": 1100}
 SCATTERED_ATOMICS = 0.08e12                                 # 64 lanes of a wave adding into 64 rows (float adds; integer adds unmeasured)
 VALU_CYCLES, SIMDS, CLOCK_HZ = 3.3, 1024, 2.4e9           # the move's instruction mix, 256 CUs x 4, the clock
 
@@ -2925,6 +2931,160 @@ def part_ntuple_exact(rounds=5):
     out["not_measured"] = ("budgets above config_bound; max_nodes above 2^16; shortest=False; tables trained at other rates, other seeds and "
                            "other pools; gamma and rewards other than the training's; trained window tables (the cost rows use random "
                            "ones); a launch bound other than eight waves a SIMD")
+    return out
+
+
+def part_rank(rounds=5, reps=10, n=1 << 20, boards=4096, eval_boards=16384, log2_nodes=12, epochs=4, batch=1024):
+    """The ranking update from proved move labels (include/tpl_learn.h: tpl_ntuple_rank; T.NTupleRanker, T.collect_labels,
+    T.label_agreement).  One seed, one pool.
+      time   rank() for each of the four forms beside NTuplePolicy.act() with every output, alternated, on part ntuple_shape's 2^20
+             mid-game boards with label rows drawn from 0 .. 3; a whole step() beside one NTupleLearner step of the form.
+      buys   the tight pool of the record (part labels'), split by pool entry into a training and a held-out half.  The rate-8
+             "feat+spare" TD table of part ntuple_exact plays one episode on each half under collect_labels; fit() on the training
+             half's nodes from that table and from zero; on the held-out half label_agreement, the one-ply win rate and the beam (3, 8)
+             win rate before and after, and a sweep over rate and margin from the TD table."""
+    import numpy as np
+    import torch
+    import tetris_piclim as T
+    m = T._learn_lib
+    dev = "cuda:0"
+    out = dict(part="rank", time=dict(boards=n, rounds=rounds, launches_per_timing=reps, forms={}), buys={})
+
+    def progress(what):
+        print(json.dumps(what), file=sys.stderr, flush=True)
+
+    # ---- time
+    env, ring = _shape_ring(T, n, 2)
+    del ring
+    a, b = env.raw_planes()
+    label = torch.randint(0, 4, (n, 40), dtype=torch.uint8, device=dev, generator=torch.Generator(device=dev).manual_seed(3))
+    action = torch.empty(n, dtype=torch.uint8, device=dev)
+    score, value = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(2))
+    after = tuple(torch.empty((n, 4), dtype=torch.int32, device=dev) for _ in range(2))
+    for form in m.NTUPLE_RANK_FORMS:
+        host = np.random.default_rng(1).integers(-(1 << 20), (1 << 20) + 1, m.ntuple_entries_of(form)).astype(np.int32)
+        table = torch.from_numpy(host).to(dev)
+        policy = T.NTuplePolicy(env, table, gamma=1.0, epsilon=0.0, seed=11)
+        ranker = T.NTupleRanker(table.clone(), 10, 40, gamma=1.0, reward=env.reward_params, rate=1.0)
+        buffers = ranker.buffers(n)
+        learner = T.NTupleLearner(env, gamma=1.0, rate=1.0, epsilon=0.05, seed=11, shape=form)
+        learner.table.copy_(table)
+        learner.train(3)
+        decided = ranker.rank((a, b), label, buffers)["win"] != 255
+        calls = {"act": lambda: policy.act(out=action, score=score, after=after, value=value, step=3),
+                 "rank": lambda: ranker.rank((a, b), label, buffers),
+                 "learner_step": lambda: learner.train(1),
+                 "rank_step": lambda: ranker.step((a, b), label, buffers)}
+        times = {k: [] for k in calls}
+        for pair in (("act", "rank"), ("learner_step", "rank_step")):   # alternated round by round; the learner moves the boards, so it comes last
+            for _ in range(rounds):
+                for k in pair:
+                    times[k].append(_timed(calls[k], reps, warmup=1))
+        med = {k: sorted(ts)[rounds // 2] for k, ts in times.items()}
+        got = {k + "_us": _spread(ts) for k, ts in times.items()}
+        got.update(decided_share=round(float(decided.float().mean()), 4), rank_over_act=round(med["rank"] / med["act"], 4),
+                   step_over_learner_step=round(med["rank_step"] / med["learner_step"], 4))
+        out["time"]["forms"][form] = got
+        progress({form: got})
+        del learner, ranker, buffers, policy
+    env.terminate()
+    del a, b, label, action, score, value, after
+    torch.cuda.empty_cache()
+
+    # ---- what it buys
+    L_, M_, M_new, count = 10, 40, 16, 1 << 16
+    env = T.BatchedTetris(L_, M_, 64, device=dev, seed=7)
+    rows, pieces = env.carved_configs(count, seed=7)
+    env.terminate()
+    found = T.solve_configs(rows, pieces, L_, M_, width=16, device=dev, validate=False)
+    tight = T.tighten_pool(rows, pieces, found["solved"], found["solution_len"], M_new)
+    size = int(tight[0].shape[0])
+    half = size // 2
+    halves = {"train": (tight[0][:half].contiguous(), tight[1][:half].contiguous()),
+              "held_out": (tight[0][half:].contiguous(), tight[1][half:].contiguous())}
+    buys = out["buys"]
+    buys["pool"] = dict(size=size, of=count, seed=7, L=L_, M=M_new, train_entries=half, held_out_entries=size - half,
+                        label_boards=boards, episode_boards=eval_boards)
+
+    env = T.BatchedTetris(L_, M_new, 4096, device=dev, seed=11, auto_reset=True, reward=NTUPLE_LARGE_REWARD, config_pool=tight)
+    learner = T.NTupleLearner(env, seed=11, gamma=1.0, epsilon=0.05, rate=8.0, shape="feat+spare", bound=False)
+    for steps in (10000, 30000):
+        learner.train(steps)
+    buys["td_table"] = dict(form="feat+spare", rate=8.0, steps=40000, pool="the whole tight pool",
+                            one_ply_win_rate_on_its_pool=round(learner.evaluate(12288)["win_rate"], 5), record=0.56785)
+    td = learner.table.clone()
+    env.terminate()
+    progress(buys["td_table"])
+
+    def episode(table, pool, beam=None):
+        """One episode on `eval_boards` boards of `pool` without auto-reset: the share won."""
+        env = T.BatchedTetris(L_, M_new, eval_boards, device=dev, seed=11, auto_reset=False, reward=NTUPLE_LARGE_REWARD, config_pool=pool)
+        env.reset()
+        policy = T.NTupleBeamPolicy(env, table, *beam, gamma=1.0) if beam else T.NTuplePolicy(env, table, gamma=1.0, epsilon=0.0)
+        for _ in range(M_new):
+            env.step(policy.act(), observe=False)
+        won = round(float((env.state == 1).float().mean()), 5)
+        env.terminate()
+        return won
+
+    def collect(pool):
+        env = T.BatchedTetris(L_, M_new, boards, device=dev, seed=11, auto_reset=False, reward=NTUPLE_LARGE_REWARD, config_pool=pool)
+        env.reset()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        got = T.collect_labels(env, pool[1], T.NTuplePolicy(env, td, gamma=1.0, epsilon=0.0), M_new, max_nodes=1 << log2_nodes)
+        torch.cuda.synchronize()
+        seconds = time.perf_counter() - t0
+        env.terminate()
+        return got, seconds
+
+    sets = {}
+    for name, pool in halves.items():
+        sets[name], seconds = collect(pool)
+        moves = ((sets[name].planes_a[:, 1] >> 28) & 15) | (((sets[name].planes_a[:, 3] >> 28) & 15) << 4)
+        buys.setdefault("labels", {})[name] = dict(nodes=len(sets[name]), boards=boards, steps=M_new, max_nodes=f"2^{log2_nodes}",
+                                                   seconds=round(seconds, 2), by_move=torch.bincount(moves.to(torch.int64), minlength=M_new).tolist())
+        progress({name: buys["labels"][name]})
+    held = sets["held_out"]
+    kw = dict(gamma=1.0, reward=NTUPLE_LARGE_REWARD)
+
+    def measure(table, beam=True):
+        got = dict(agreement=T.label_agreement(table, (held.planes_a, held.planes_b), held.label, L_, M_new, **kw),
+                   one_ply=episode(table, halves["held_out"]))
+        if beam:
+            got["beam_3x8"] = episode(table, halves["held_out"], (3, 8))
+        return got
+
+    def fit(start, rate, margin, epochs=epochs):
+        table = start.clone()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        counts = T.NTupleRanker(table, L_, M_new, rate=rate, margin=margin, **kw).fit(sets["train"], epochs, batch, seed=0)
+        torch.cuda.synchronize()
+        return table, counts, round(time.perf_counter() - t0, 3)
+
+    buys["held_out"] = {"td_table": measure(td)}
+    progress(buys["held_out"])
+    for name, start in (("fit_from_the_td_table", td), ("fit_from_zero", torch.zeros_like(td))):
+        table, counts, seconds = fit(start, 8.0, 0.0)
+        buys["held_out"][name] = dict(rate=8.0, margin=0.0, epochs=epochs, batch=batch, violated_per_epoch=counts, fit_seconds=seconds,
+                                      train_nodes=len(sets["train"]), **measure(table))
+        progress({name: buys["held_out"][name]})
+    buys["sweep_from_the_td_table"] = []
+    cells = [(rate, margin, epochs) for rate in (1.0, 8.0, 64.0, 512.0, 4096.0) for margin in (0.0, 1.0, 4.0)]
+    cells += [(rate, 1.0, 4 * epochs) for rate in (64.0, 512.0)]
+    for rate, margin, passes in cells:
+        table, counts, _ = fit(td, rate, margin, passes)
+        line = dict(rate=rate, margin=margin, epochs=passes, violated_first_and_last_epoch=[counts[0], counts[-1]],
+                    **measure(table, beam=passes != epochs))
+        buys["sweep_from_the_td_table"].append(line)
+        progress(line)
+    buys["one_ply_standard_error"] = round(0.5 / eval_boards ** 0.5, 4)
+    res = subprocess.run(["bash", os.path.join(ROOT, "tools", "kernel_resources.sh"), m.build_library()], capture_output=True, text=True, cwd=ROOT)
+    out["kernel"] = [" ".join(l.split()) for l in res.stdout.splitlines() if "ntuple_rank" in l]
+    out["not_measured"] = ("other seeds and pools; more epochs, other batch sizes; bound=True; symmetric=True; the window forms as learners; "
+                           "labels collected under other policies or at other max_nodes; teaching through two plies or the beam; mixing "
+                           "ranking steps into TD training; the time of rank() on real label rows (the timed rows are drawn from 0 .. 3)")
     return out
 
 
