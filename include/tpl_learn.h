@@ -612,6 +612,51 @@ int tpl_placement_exact_labels_move(const int16_t* rows, const uint8_t* lines, c
                                     float spare_weight, int32_t max_nodes, uint8_t* label, int32_t* length, uint32_t* nodes,
                                     void* stream);
 
+/* The exact search OVER THE PIECES A STATE'S WINDOW SHOWS (csrc/learn/exact_window.hip).  The searches above read a configuration's
+ * whole piece list, which an agent that plays from states does not have.  A state does carry pieces: its 36-bit window holds
+ * known = 12 - moves % 10 true ones, the falling one first (tpl_placement_beam, above).  This entry proves what those pieces decide.
+ *
+ * tpl_placement_window_prove: n states in the two packed planes the beam entries take.  Take a RUNNING board of the game (L, M) with
+ * `lines`, `moves` and window entries q[0..11], entry j at bits 3 j of window | window_hi << 32, masked & 7 as move_board masks them, and
+ *   known = 12 - moves % 10,   rem = M - moves,   H = min(known, rem), the HORIZON.
+ * THE SEARCH IS tpl_placement_exact_nodes' WITH shortest = 1: the root is the board, the game is (L - lines, H), the piece at depth d
+ * is q[d]; there is no new search rule.  Equivalently, and this is what the tests hold it to: THE OUTPUTS ARE, BYTE FOR BYTE, WHAT
+ * tpl_placement_exact_nodes WRITES for the node (rows, lines, M - H, entry i) over a list pieces'[i] with pieces'[i][M - H + d] = q[d]
+ * for d < H -- solved, proved, solution_len, actions[0..H), bound and nodes.
+ * Outputs per board, each written in full: solved u8, proved u8, solution_len i32, plan u8 [n][TPL_WINDOW_PLAN] (placements
+ * b = 10 r + l, 255 behind the end), bound i32 (need(board) with L - lines rows owed), nodes u32, horizon u8 (H), and verdict u8:
+ *   TPL_WINDOW_NONE 0   the board is finished or was skipped (below);
+ *   TPL_WINDOW_WIN  1   solved: the plan wins THE REAL GAME in solution_len moves, and no shorter win exists, because a shorter win
+ *                       would lie inside the horizon too;
+ *   TPL_WINDOW_LOSS 2   proved, not solved, and H == rem: no sequence of placements wins -- the move bound's proof, as
+ *                       tpl_placement_exact's;
+ *   TPL_WINDOW_OPEN 3   everything else: max_nodes stopped the search, or it was searched out with H < rem, which says only that no
+ *                       win lies within the known pieces.  VERDICT 3 PROVES NOTHING ABOUT THE GAME.
+ * A board that is not running -- or whose lines >= L or moves >= M, which no environment of the game holds -- is FINISHED: verdict 0,
+ * solved = 0, proved = 1, solution_len = 0, a plan of 255s, bound = 0, nodes = 0, horizon = 0, as tpl_placement_exact_nodes finishes
+ * the node with moves = M.
+ * skip (may be NULL) is a mask u8 [n]: a board with skip[i] != 0 is NOT SEARCHED and gets verdict 0, solved = 0, proved = 0,
+ * solution_len = 0, a plan of 255s and nodes = 0; bound and horizon are still written.
+ * weights is one row (12 floats, or in the _move form the first 14 of a row of 16), spare_weight and max_nodes are
+ * tpl_placement_exact's: they order the children and cap the expansions, and decide no verdict but between 3 and the two others.
+ * One wavefront a board, the frame of tpl_placement_exact's kernel with a stack of twelve records in static LDS.
+ * Refused before any HIP call: everything tpl_placement_exact_nodes refuses of the arguments the two share (n outside [1, 2^31), L
+ * or M out of range, max_nodes outside [1, TPL_EXACT_MAX_NODES], a spare_weight that is not finite, weights NULL or not 16-byte
+ * aligned), a NULL plane or output, planes not 16-byte aligned, solution_len, bound or nodes not 4-byte aligned. */
+#define TPL_WINDOW_PLAN 12
+#define TPL_WINDOW_NONE 0
+#define TPL_WINDOW_WIN 1
+#define TPL_WINDOW_LOSS 2
+#define TPL_WINDOW_OPEN 3
+int tpl_placement_window_prove(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const float* weights,
+                               float spare_weight, int32_t max_nodes, const uint8_t* skip, uint8_t* solved, uint8_t* proved,
+                               int32_t* solution_len, uint8_t* plan, int32_t* bound, uint32_t* nodes, uint8_t* horizon,
+                               uint8_t* verdict, void* stream);
+int tpl_placement_window_prove_move(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const float* weights,
+                                    float spare_weight, int32_t max_nodes, const uint8_t* skip, uint8_t* solved, uint8_t* proved,
+                                    int32_t* solution_len, uint8_t* plan, int32_t* bound, uint32_t* nodes, uint8_t* horizon,
+                                    uint8_t* verdict, void* stream);
+
 /* An n-tuple afterstate value function, its placement policy and its temporal-difference update (csrc/learn/ntuple.hip).
  *
  * Table: TPL_NTUPLE_ENTRIES = 8 * 153 * 256 + 1024 = 314,368 int32 entries (1,257,472 bytes), 16-byte aligned, in units of 2^-16:

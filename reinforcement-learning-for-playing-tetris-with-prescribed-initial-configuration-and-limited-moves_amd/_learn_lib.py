@@ -25,7 +25,8 @@ _UNITS = [os.path.join(_LEARN_CSRC, f) for f in ("replay.hip", "pack.hip", "prio
                                                       "beam_move.hip", "solve_move.hip", "bound.hip", "beam_bound.hip",
                                                       "solve_bound.hip", "beam_move_bound.hip", "solve_move_bound.hip",
                                                       "exact.hip", "exact_move.hip", "ntuple_exact.hip", "curriculum.hip", "exact_nodes.hip",
-                                                      "exact_nodes_move.hip", "ntuple_rank.hip", "heuristic.hip")]
+                                                      "exact_nodes_move.hip", "exact_window.hip", "exact_window_move.hip",
+                                                      "ntuple_rank.hip", "heuristic.hip")]
 
 # entry points declared in include/tpl_learn.h (tests check that the .so exports every one of them)
 LEARN_SYMBOLS = [
@@ -52,6 +53,7 @@ LEARN_SYMBOLS = [
     "tpl_config_index", "tpl_pool_tally", "tpl_pool_resample",
     "tpl_placement_exact_nodes", "tpl_placement_exact_nodes_move", "tpl_placement_exact_labels", "tpl_placement_exact_labels_move",
     "tpl_ntuple_rank",
+    "tpl_placement_window_prove", "tpl_placement_window_prove_move",
 ]
 NSTEP_MAX = 16
 BEAM_MAX_DEPTH, BEAM_MAX_WIDTH = 12, 64
@@ -181,6 +183,10 @@ def lib() -> C.CDLL:
         nodes.argtypes = [vp, vp, vp, vp, vp, i64, i64, i32, i32, vp, f32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
         labels.argtypes = [vp, vp, vp, vp, vp, i64, i64, i32, i32, vp, f32, i32, vp, vp, vp, vp]
         nodes.restype = labels.restype = i32
+        # the search over a state's window: the planes, one weight row, the optional skip mask, then the eight outputs
+        window = getattr(L, f"tpl_placement_window_prove{form}")
+        window.argtypes = [vp, vp, i64, i32, i32, vp, f32, i32, vp] + [vp] * 8 + [vp]
+        window.restype = i32
     L.tpl_ntuple_value.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp]
     L.tpl_ntuple_act.argtypes = [vp, vp, i64, i32, i32, f32, f32, f32, f32, vp, f32, u64, u64, vp, vp, vp, vp, vp, vp]
     L.tpl_ntuple_update.argtypes = [vp, vp, i64, i32, i32, vp, vp, f32, vp]
@@ -527,7 +533,8 @@ FEATURE_COUNTS = (NUM_FEATURES, NUM_MOVE_FEATURES)
 
 def entry(name: str, count: int, bound: bool = False):
     """The entry point tpl_placement_<name> of the feature set with `count` features (12 or 14); bound=True: its bounded form
-    (beam and solve have one; exact is of the bounded form as it stands and has no other)."""
+    (beam and solve have one; exact, exact_nodes, exact_labels and window_prove are of the bounded form as they stand and have no
+    other)."""
     if count not in FEATURE_COUNTS:
         raise ValueError(f"a weight row has {NUM_FEATURES} or {NUM_MOVE_FEATURES} entries, not {count}")
     return getattr(lib(), f"tpl_placement_{name}" + ("_move" if count == NUM_MOVE_FEATURES else "") + ("_bound" if bound else ""))
@@ -1127,6 +1134,79 @@ def best_labelled_move(label, length) -> np.ndarray:
     win = label == LABEL_WIN
     key = np.where(win, length, np.iinfo(np.int64).max)
     return np.where(win.any(axis=1), key.argmin(axis=1), NO_SECOND).astype(np.uint8)
+
+
+# ------------------------------------------------------------------------------------------------ the exact search over a window
+# The rule of tpl_placement_window_prove (include/tpl_learn.h) on the host, from the ROW form: the window is decoded, the boards are
+# grouped by (lines, H), and each group is handed to placement_exact as configurations of the SHIFTED game (L - lines, H) whose lists
+# are the window's first H entries; the verdict is derived from what comes back.  The device unpacks the planes and runs its own copy
+# of the search (csrc/learn/exact_window.hip) -- the two share nothing.
+WINDOW_PLAN = 12                                         # the plan's width: the window's twelve entries
+WINDOW_NONE, WINDOW_WIN, WINDOW_LOSS, WINDOW_OPEN = 0, 1, 2, 3
+
+
+def window_entries(window) -> np.ndarray:
+    """The twelve 3-bit entries of 36-bit piece windows (window | window_hi << 32, entry j at bits 3 j): int64 [n, 12]."""
+    window = np.asarray(window).astype(np.uint64).reshape(-1)
+    return ((window[:, None] >> (np.uint64(3) * np.arange(WINDOW_PLAN, dtype=np.uint64))) & np.uint64(7)).astype(np.int64)
+
+
+def placement_window_prove(rows, lines, moves, state, window, L: int, M: int, weights, max_nodes: int, spare_weight: float = 0.0,
+                           skip=None) -> dict:
+    """The rule of tpl_placement_window_prove (include/tpl_learn.h) for n states of the game (L, M) given by their fields: rows uint16
+    [n, 20] (bit x = column x), lines, moves and state integers [n] (state 0 = running), window uint64 [n] (36 bits); one weight row
+    [12] or [14], max_nodes in [1, 2^24], one finite spare_weight, skip None or [n] (nonzero: not searched).
+    A running board with lines < L and moves < M has known = 12 - moves % 10, rem = M - moves and the horizon H = min(known, rem), and is
+    searched as the configuration (rows, window entries 0 .. H - 1) of the game (L - lines, H), shortest; anything else is finished.
+    Returns a dict in the C layout: solved, proved uint8 [n], solution_len int32 [n], plan uint8 [n, 12] padded with 255, bound int32
+    [n], nodes uint32 [n], horizon uint8 [n], verdict uint8 [n] (WINDOW_NONE / WIN / LOSS / OPEN), and known uint8 [n]."""
+    L, M = int(L), int(M)
+    if not (1 <= L <= 250 and 1 <= M <= SOLVE_MAX_MOVES):
+        raise ValueError(f"L and M must be in [1, 250] and [1, {SOLVE_MAX_MOVES}]")
+    _exact_arguments(weights, max_nodes, True, spare_weight)
+    rows = np.asarray(rows)
+    rows = (rows.view(np.uint16) if rows.dtype == np.int16 else rows.astype(np.uint16)).reshape(-1, 20)
+    n = rows.shape[0]
+    if n < 1:
+        raise ValueError("rows must be [n, 20] with n >= 1")
+    fields = []
+    for name, x, top in (("lines", lines, 255), ("moves", moves, 255), ("state", state, 3), ("window", window, (1 << 36) - 1)):
+        x = np.asarray(x)
+        if x.shape != (n,) or not np.issubdtype(x.dtype, np.integer):
+            raise ValueError(f"{name} must be {n} integers, one per state")
+        if x.min() < 0 or int(x.max()) > top:
+            raise ValueError(f"{name} must be in [0, {top}]")
+        fields.append(x.astype(np.uint64 if name == "window" else np.int64))
+    lines, moves, state, window = fields
+    if skip is None:
+        skip = np.zeros(n, bool)
+    else:
+        skip = np.asarray(skip)
+        if skip.shape != (n,):
+            raise ValueError(f"skip must be None or {n} flags, one per state")
+        skip = skip != 0
+    q = window_entries(window)
+    live = (state == STATE_RUNNING) & (lines < L) & (moves < M)
+    known = (WINDOW_PLAN - moves % 10).astype(np.int64)
+    rem = np.where(live, M - moves, 0)
+    H = np.minimum(known, rem)
+    out = dict(solved=np.zeros(n, np.uint8), proved=np.where(skip, 0, 1).astype(np.uint8), solution_len=np.zeros(n, np.int32),
+               plan=np.full((n, WINDOW_PLAN), NO_SECOND, np.uint8), bound=np.zeros(n, np.int32), nodes=np.zeros(n, np.uint32),
+               horizon=H.astype(np.uint8), verdict=np.zeros(n, np.uint8), known=known.astype(np.uint8))
+    if live.any():
+        at = np.flatnonzero(live)
+        out["bound"][at] = move_bound(rows[at], L, M, lines[at], 0, STATE_RUNNING)["need"]
+    todo = live & ~skip
+    for at_lines, at_H in sorted({(int(a), int(b)) for a, b in zip(lines[todo], H[todo])}):
+        idx = np.flatnonzero(todo & (lines == at_lines) & (H == at_H))
+        lists = np.concatenate([q[idx, :at_H], np.zeros((idx.size, 1), np.int64)], axis=1)      # [k, H + 1]: the last is never placed
+        solved, proved, length, actions, _, nodes = placement_exact(rows[idx], lists, L - at_lines, at_H, weights, max_nodes, True,
+                                                                    spare_weight)
+        out["solved"][idx], out["proved"][idx], out["solution_len"][idx], out["nodes"][idx] = solved, proved, length, nodes
+        out["plan"][idx, :at_H] = actions
+        out["verdict"][idx] = np.where(solved == 1, WINDOW_WIN,
+                                       np.where((proved == 1) & (at_H == rem[idx]), WINDOW_LOSS, WINDOW_OPEN))
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ the n-tuple value function

@@ -278,7 +278,8 @@ def _win_count_reward(env) -> None:
 
 @torch.no_grad()
 def evaluate_heuristic(env, weights, boards_per_member: Optional[int], steps: int, policy=None, depth: int = 1,
-                       width: Optional[int] = None, bound: bool = False, spare_weight: float = 0.0, per_config: bool = False) -> dict:
+                       width: Optional[int] = None, bound: bool = False, spare_weight: float = 0.0, per_config: bool = False,
+                       proof: Optional[int] = None) -> dict:
     """Play `steps` steps of the population `weights` ([P, 12] or [12]) on `env` from a full reset: an auto-reset environment
     with a configuration pool and reward parameters (0, 1, 0), so that the summed reward is the number of wins.  Member p plays
     boards [p * boards_per_member, (p + 1) * boards_per_member).  Returns episodes and wins as int64 numpy arrays [P] and
@@ -288,9 +289,15 @@ def evaluate_heuristic(env, weights, boards_per_member: Optional[int], steps: in
     plays, depth may be 1 .. 12, and a `policy` that is passed must be a BeamPolicy of that depth and width.  `bound` and
     `spare_weight` are BeamPolicy's and need a `width`; a `policy` that is passed must have been built with them.
     per_config=True: the dict gains episodes_by_config and wins_by_config, int32 device tensors over the loaded pool summed over the
-    members (a PoolTally observed before every step); the three other keys are what they are without it."""
+    members (a PoolTally observed before every step); the three other keys are what they are without it.
+    proof: None, or a node budget -- then the policy plays inside a ProofPolicy(env, policy, max_nodes=proof) (solve.py): the first
+    move of a plan that the exact search over the state's window proves winning, the policy's own move elsewhere; the dict gains
+    proof, that policy's stats().  None leaves every result as it is."""
     if not isinstance(per_config, bool):
         raise ValueError("per_config must be True or False")
+    if proof is not None:
+        from .solve import _max_nodes
+        proof = _max_nodes(proof)
     kind, depth, width = _player(depth, width)
     bound, spare_weight = _player_bound(width, bound, spare_weight)
     if policy is not None:
@@ -315,6 +322,10 @@ def evaluate_heuristic(env, weights, boards_per_member: Optional[int], steps: in
         policy.set_weights(weights)
         if boards_per_member is not None and int(boards_per_member) != policy.boards_per_member:
             raise ValueError("policy was built with another boards_per_member")
+    player = policy
+    if proof is not None:
+        from .solve import ProofPolicy
+        player = ProofPolicy(env, policy, max_nodes=proof)
     n, d = env.num_envs, env.device
     action = torch.empty(n, dtype=torch.uint8, device=d)
     reward = torch.empty(n, dtype=torch.float32, device=d)
@@ -327,7 +338,7 @@ def evaluate_heuristic(env, weights, boards_per_member: Optional[int], steps: in
         from .curriculum import PoolTally
         tally = PoolTally(env)
     for _ in range(int(steps)):
-        policy.act(out=action)
+        player.act(out=action)
         if tally is not None:
             tally.observe(action)
         env.step_into(action, reward, done)
@@ -340,6 +351,8 @@ def evaluate_heuristic(env, weights, boards_per_member: Optional[int], steps: in
     result = dict(episodes=ep, wins=wn, win_rate=wn / np.maximum(ep, 1))
     if tally is not None:
         result.update(episodes_by_config=tally.episodes, wins_by_config=tally.wins)
+    if proof is not None:
+        result["proof"] = player.stats()
     return result
 
 

@@ -829,7 +829,7 @@ class NTupleLearner:
 
     @torch.no_grad()
     def evaluate(self, steps: int, depth: Optional[int] = None, width: Optional[int] = None, bound: Optional[bool] = None,
-                 per_config: bool = False) -> dict:
+                 per_config: bool = False, proof: Optional[int] = None) -> dict:
         """Play `steps` greedy steps from a full reset and count: episodes (the steps' done flags), wins (the afterstates of the
         moves played whose state is "won": every reward parameter counts the same wins) and win_rate = wins / max(episodes, 1).
         depth: how deep the greedy policy searches -- None: the learner's own; 1 or 2 plays the table as it stands at that depth.
@@ -837,9 +837,16 @@ class NTupleLearner:
         1 .. 11.  bound: None -- the learner's own -- or whether the policy that plays prunes dead boards (a budget table only).
         The tallies stay on the device, with one sync at the end.  Training goes on from the boards this leaves, with
         nothing kept.  per_config=True: the dict gains episodes_by_config and wins_by_config, int32 device tensors over the loaded
-        pool (a PoolTally observed before every step); the three other keys are what they are without it."""
+        pool (a PoolTally observed before every step); the three other keys are what they are without it.
+        proof: None, or a node budget -- then the policy plays inside a ProofPolicy(env, policy, max_nodes=proof) (solve.py): the
+        first move of a plan that the exact search over the state's window proves winning, the table's move elsewhere; a plan's
+        move wins exactly where it is the plan's last.  The dict gains proof, that policy's stats().  None leaves every result as
+        it is."""
         if not isinstance(per_config, bool):
             raise ValueError("per_config must be True or False")
+        if proof is not None:
+            from .solve import ProofPolicy, _max_nodes
+            proof = _max_nodes(proof)
         steps = _count("steps", steps, 1)
         env, d = self.env, self.env.device
         greedy = self.greedy
@@ -848,11 +855,13 @@ class NTupleLearner:
             if depth is None:
                 raise ValueError("evaluate(width=...) plays a beam: depth must be given with it (1 .. 11)")
             beam = NTupleBeamPolicy(env, self.table, *_beam_shape(depth, width), gamma=greedy.gamma, bound=bound)
-            act = lambda: beam.act(out=self._action, after=self._next)
+            player, arguments = beam, dict(after=self._next)
         else:
             if (depth is not None and _depth(depth) != self.depth) or bound != greedy.bound:
                 greedy = NTuplePolicy(env, self.table, greedy.gamma, 0.0, greedy.seed, self.depth if depth is None else depth, bound=bound)
-            act = lambda: greedy.act(out=self._action, after=self._next, step=0)
+            player, arguments = greedy, dict(after=self._next, step=0)
+        prover = None if proof is None else ProofPolicy(env, player, max_nodes=proof)
+        act = lambda: (player if prover is None else prover).act(out=self._action, **arguments)
         episodes = torch.zeros(env.num_envs, dtype=torch.int32, device=d)
         wins = torch.zeros(env.num_envs, dtype=torch.int32, device=d)
         env.reset()
@@ -866,12 +875,15 @@ class NTupleLearner:
                 tally.observe(action)
             env.step_into(action, self._reward, self._done)
             episodes += self._done
-            wins += ((self._next[1][:, 1] >> 28) & 3) == _STATE_WON          # an auto-reset board runs whenever it is asked to act
+            won = ((self._next[1][:, 1] >> 28) & 3) == _STATE_WON             # an auto-reset board runs whenever it is asked to act
+            wins += won if prover is None else torch.where(prover.played, prover.finishing, won)
         self.forget()
         ep, wn = int(episodes.sum(dtype=torch.int64)), int(wins.sum(dtype=torch.int64))
         result = dict(episodes=ep, wins=wn, win_rate=wn / max(ep, 1))
         if tally is not None:
             result.update(episodes_by_config=tally.episodes, wins_by_config=tally.wins)
+        if prover is not None:
+            result["proof"] = prover.stats()
         return result
 
 

@@ -23,6 +23,11 @@ of at move 0 (tpl_placement_exact_nodes; csrc/learn/exact_nodes.hip): for the se
 or unproved (tpl_placement_exact_labels), `label_states` does so for the boards of an environment, and `blunders` marks where a
 proved-losing move was taken although a proved-winning one was there.
 
+`window_prove` is the exact search an honest agent can run: it searches over the pieces a state's own window shows, known =
+12 - moves mod 10 of them, instead of a configuration's list (tpl_placement_window_prove; csrc/learn/exact_window.hip).  A win it
+finds is a win of the real game; no win proves a loss only where the window reaches the end of the game, and otherwise proves
+nothing.  `ProofPolicy` wraps any policy with it: a proved plan's move where there is one, the base policy's move elsewhere.
+
 `collect_labels` plays a policy on an environment with a pool and keeps the boards the labels decide -- a proved win and a proved loss
 among their moves -- in a `LabelSet`, the input of `NTupleRanker.fit` (ntuple.py); `label_agreement` counts how often a table's greedy
 move is labelled 1, 2 and 3 on such nodes.
@@ -34,7 +39,8 @@ import numpy as np
 from ._learn_lib import BEAM_MAX_WIDTH, EXACT_MAX_NODES, NUM_FEATURES, NUM_MOVE_FEATURES, SOLVE_MAX_MOVES
 
 __all__ = ["CLASSICAL_WEIGHTS", "solve_configs", "prove_configs", "ntuple_prove_configs", "tighten_pool", "config_bound",
-           "prove_nodes", "label_moves", "label_states", "blunders", "LabelSet", "collect_labels", "label_agreement"]
+           "prove_nodes", "label_moves", "label_states", "blunders", "LabelSet", "collect_labels", "label_agreement", "window_prove",
+           "ProofPolicy"]
 
 # cleared, won, lost, holes, aggregate height, max height, bumpiness, row and column transitions, wells, rows with holes, hole depth:
 # the classical signs, a sensible default for the supply (0.99925 of a carved L = 10 / M = 40 pool at one ply)
@@ -355,6 +361,201 @@ def prove_nodes(rows, lines, moves, entry, pieces, L: int, M: int, weights=None,
     out["unwinnable"] = out["proved"] & ~out["solved"]
     out["solution"] = _solution(out["actions"])
     return out
+
+
+
+# ------------------------------------------------------------------------------------------------ the search over a state's window
+WINDOW_OUTPUTS = ("solved", "proved", "solution_len", "plan", "bound", "nodes", "horizon", "verdict")
+
+
+def _resident_planes(env):
+    """The two resident state planes of `env` as int32 [N, 4] VIEWS of its workspace (env.raw_planes() returns copies of them)."""
+    import torch
+    from .lookahead import _state_ptrs
+    n, base = env.num_envs, env._workspace.data_ptr()
+    return tuple(env._workspace[p - base: p - base + n * 16].view(torch.int32).view(n, 4) for p in _state_ptrs(env))
+
+
+def _plane_fields(a, b):
+    """moves, state and lines (int32 [N] each) of int32 [N, 4] planes (the layout: DESIGN.md section 2)."""
+    moves = ((a[:, 1] >> 28) & 15) | (((a[:, 3] >> 28) & 15) << 4)
+    return moves, (b[:, 1] >> 28) & 3, (b[:, 2] >> 20) & 255
+
+
+def _window_buffers(n: int, d) -> dict:
+    import torch
+    kinds = dict(solved=torch.uint8, proved=torch.uint8, solution_len=torch.int32, bound=torch.int32, nodes=torch.int32,
+                 horizon=torch.uint8, verdict=torch.uint8)
+    out = {k: torch.empty(n, dtype=t, device=d) for k, t in kinds.items()}
+    out["plan"] = torch.empty((n, 12), dtype=torch.uint8, device=d)
+    return out
+
+
+def _window_launch(env, planes, features: int, wt, spare_weight: float, max_nodes: int, skip, out: dict) -> None:
+    """tpl_placement_window_prove[_move] on the resident boards of `env` into the buffers of _window_buffers."""
+    import torch
+    from . import _learn_lib
+    stream = torch._C._cuda_getCurrentRawStream(env.device.index)
+    _learn_lib.check(_learn_lib.entry("window_prove", features)(
+        planes[0], planes[1], env.num_envs, env.L, env.M, wt.data_ptr(), spare_weight, max_nodes,
+        None if skip is None else skip.data_ptr(), *(out[k].data_ptr() for k in WINDOW_OUTPUTS), stream))
+
+
+def _skip_mask(env, skip):
+    """None, or a contiguous uint8 [N] on the environment's device: nonzero = do not search that board."""
+    import torch
+    if skip is None:
+        return None
+    if not _is_tensor(skip):
+        skip = torch.from_numpy(np.ascontiguousarray(np.asarray(skip) != 0).view(np.uint8))
+    if tuple(skip.shape) != (env.num_envs,) or skip.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"skip must be None or {env.num_envs} flags (bool or uint8), one per board")
+    skip = skip.to(env.device)
+    return (skip.view(torch.uint8) if skip.dtype == torch.bool else skip).contiguous()
+
+
+def window_prove(env, weights=None, max_nodes: int = 1 << 12, spare_weight: float = 0.0, skip=None) -> dict:
+    """The exact search over the pieces each resident board's window shows (the rule: include/tpl_learn.h,
+    tpl_placement_window_prove; csrc/learn/exact_window.hip), one wavefront per board.  Nothing but the state is read: no pool, no
+    piece list.
+
+    A running board at moves = m knows known = 12 - m mod 10 true pieces, the falling one first, and has rem = M - m moves left; the
+    search is prove_nodes' shortest search of the game (L - lines, H) with the HORIZON H = min(known, rem), its pieces the window's.
+    weights (None = CLASSICAL_WEIGHTS; fourteen select the 14-feature form), spare_weight and max_nodes are prove_configs': they
+    order the children and cap the nodes of a board, and decide no verdict but between 3 and the two others.  skip: None, or [N] flags
+    (bool or uint8) -- a flagged board is not searched: verdict 0, nothing solved or proved, 0 nodes; bound and horizon still stand.
+    Returns a dict of device tensors [N]: solved bool, proved bool, solution_len int32, plan uint8 [N, 12] (placements 10 r + l, 255
+    behind the end), bound int32 (the least number of moves any win takes), nodes int32, horizon uint8, known uint8,
+    action uint8 = plan[:, 0], and verdict uint8:
+      0  the board is finished, or was skipped;
+      1  WIN: the plan wins the real game in solution_len moves, and no shorter win exists;
+      2  LOSS: searched out with the window reaching the end of the game (H == rem): no sequence of placements wins;
+      3  OPEN: the node budget stopped the search, or it was searched out with H < rem, which says only that no win lies within the
+         known pieces.
+    **Verdict 3 proves nothing about the game, neither way.**  Verdicts 1 and 2 do not depend on max_nodes or on the weights.
+    The environment is read, never written; no host wait."""
+    import torch
+    from . import _learn_lib
+    from .lookahead import _boards, _state_ptrs
+    _boards(env, "window_prove")
+    w = _weight_row(weights)
+    max_nodes = _max_nodes(max_nodes)
+    spare_weight = _spare_weight(spare_weight, True)
+    skip = _skip_mask(env, skip)
+    wt = torch.from_numpy(_learn_lib.padded_weights(w)).to(env.device)
+    out = _window_buffers(env.num_envs, env.device)
+    _window_launch(env, _state_ptrs(env), w.shape[0], wt, spare_weight, max_nodes, skip, out)
+    out["solved"], out["proved"] = out["solved"].view(torch.bool), out["proved"].view(torch.bool)
+    moves, _, _ = _plane_fields(*_resident_planes(env))
+    out["known"] = (12 - moves % 10).to(torch.uint8)
+    out["action"] = out["plan"][:, 0]
+    return out
+
+
+class ProofPolicy:
+    """A base policy with proofs on top: act() runs window_prove on the resident boards and plays the first move of the proved plan
+    where the verdict is 1 (WIN), and base.act()'s move everywhere else.  `base` is any policy of this environment with act(out=...):
+    HeuristicPolicy, BeamPolicy, NTuplePolicy, NTupleBeamPolicy.  weights (None = CLASSICAL_WEIGHTS, or fourteen), max_nodes and
+    spare_weight are window_prove's and only order and cap the search.
+
+    **A verdict 1 is a proof: following the plan wins the game in solution_len moves.  Verdicts 2 and 3 change nothing -- the base
+    plays --, and 3 proves nothing.**
+
+    A proved plan is KEPT per board and stays live while the board is running, its `moves` is the move the plan expects next AND its
+    cells are those the plan's last move was to leave (one afterstate enumeration per act()); anything else -- a reset, a caller
+    that stepped with another action -- drops the plan.  Where a later search gives no verdict 1 -- the node budget can stop the
+    search from the board one move on although it did not stop the first: the children's values carry the rows cleared on the path,
+    and float rounding breaks their many ties differently from another root -- the live plan is followed: a proof once held is not
+    thrown away.  reuse=False (the default) searches every board at every act() and takes a new proof over the kept one;
+    reuse=True passes the boards that hold a live plan to the kernel as `skip` and follows their plans without searching them again.
+
+    After an act(): `verdict` uint8 [N] (the kernel's; 0 where a board was skipped), `played` bool [N] (the action is a plan's
+    move) and `finishing` bool [N] (it is the plan's last move: it wins), `nodes` int32 [N] (0 where nothing was searched).
+    stats() counts since construction, on the device.  No host wait in act()."""
+
+    def __init__(self, env, base, weights=None, max_nodes: int = 1 << 12, spare_weight: float = 0.0, reuse: bool = False):
+        import torch
+        from . import _learn_lib
+        from .lookahead import _boards, _state_ptrs
+        n = _boards(env, "ProofPolicy")
+        if not callable(getattr(base, "act", None)):
+            raise ValueError("base must be a policy with act(out=...): HeuristicPolicy, BeamPolicy, NTuplePolicy or NTupleBeamPolicy")
+        if getattr(base, "env", env) is not env:
+            raise ValueError("base belongs to another environment")
+        if not isinstance(reuse, (bool, np.bool_)):
+            raise ValueError(f"reuse must be True or False, got {reuse!r}")
+        w = _weight_row(weights)
+        self.env, self.base, self.reuse = env, base, bool(reuse)
+        self.features, self.max_nodes = int(w.shape[0]), _max_nodes(max_nodes)
+        self.spare_weight = _spare_weight(spare_weight, True)
+        d = env.device
+        self._weights = torch.from_numpy(_learn_lib.padded_weights(w)).to(d)
+        self._ptrs, self._planes = _state_ptrs(env), _resident_planes(env)
+        self._out = _window_buffers(n, d)
+        self._index = torch.arange(n, device=d)
+        self._counts = torch.zeros(4, dtype=torch.int64, device=d)              # verdicts 1, 2, 3; plan moves played
+        # the plans kept: the plan, its length, the next move's index, the `moves` it expects and the cells it is to find
+        self._plan = torch.full((n, 12), 255, dtype=torch.uint8, device=d)
+        self._length = torch.zeros(n, dtype=torch.int32, device=d)
+        self._at = torch.zeros(n, dtype=torch.int32, device=d)
+        self._expect = torch.full((n,), -1, dtype=torch.int32, device=d)
+        self._cells = torch.zeros((n, 7), dtype=torch.int32, device=d)
+        self._holds = torch.zeros(n, dtype=torch.bool, device=d)
+        self.verdict, self.nodes = self._out["verdict"], self._out["nodes"]
+        self.played = torch.zeros(n, dtype=torch.bool, device=d)
+        self.finishing = torch.zeros(n, dtype=torch.bool, device=d)
+
+    @staticmethod
+    def _cells_of(a, b):
+        """The seven words of a plane pair that hold its cells alone: moves, state, slot, lines and the window masked out."""
+        import torch
+        return torch.stack([a[..., 0], a[..., 1] & 0x0FFFFFFF, a[..., 2], a[..., 3] & 0x0FFFFFFF, b[..., 0], b[..., 1] & 0x0FFFFFFF,
+                            b[..., 2] & 0xFFFFF], dim=-1)
+
+    def act(self, out=None, verdict=None, **base_arguments):
+        """uint8 [N]: the proved plan's move where this call's verdict is 1 or a live plan is held, base.act(out=out,
+        **base_arguments)'s move elsewhere.  `verdict` (uint8 [N], optional) receives the kernel's verdicts.  No host wait."""
+        import torch
+        from .lookahead import afterstates
+        env, n = self.env, self.env.num_envs
+        if out is None:
+            out = torch.empty(n, dtype=torch.uint8, device=env.device)
+        env._own(out, torch.uint8, "out")
+        if verdict is not None:
+            env._own(verdict, torch.uint8, "verdict")
+        with torch.no_grad():
+            self.base.act(out=out, **base_arguments)
+            moves, state, _ = _plane_fields(*self._planes)
+            same = (self._cells == self._cells_of(*self._planes)).all(dim=1)
+            self._holds &= (state == 0) & (moves == self._expect) & same
+            skip = self._holds.view(torch.uint8) if self.reuse else None
+            _window_launch(env, self._ptrs, self.features, self._weights, self.spare_weight, self.max_nodes, skip, self._out)
+            found = self._out["verdict"] == 1
+            if verdict is not None:
+                verdict.copy_(self._out["verdict"])
+            self._counts[:3] += torch.stack([(self._out["verdict"] == k).sum() for k in (1, 2, 3)])
+            self._plan.copy_(torch.where(found[:, None], self._out["plan"], self._plan))
+            self._length.copy_(torch.where(found, self._out["solution_len"], self._length))
+            self._at.copy_(torch.where(found, torch.zeros_like(self._at), self._at))
+            self._holds |= found
+            move = self._plan[self._index, self._at.clamp(0, 11).to(torch.int64)]
+            out.copy_(torch.where(self._holds, move, out))
+            # what the move is to leave: the cells of its afterstate (the window and the counters are the environment's own)
+            after = afterstates(env)
+            pick = out.to(torch.int64).clamp(0, 39)
+            self._cells.copy_(self._cells_of(after["states_a"][self._index, pick], after["states_b"][self._index, pick]))
+            self.played = self._holds.clone()
+            self._at += self._holds.to(torch.int32)
+            self._expect.copy_(moves + 1)
+            self.finishing = self.played & (self._at == self._length)
+            self._holds &= self._at < self._length
+            self._counts[3] += self.played.sum()
+        return out
+
+    def stats(self) -> dict:
+        """Counts since construction (one host read): the verdicts 1, 2 and 3 the kernel gave, and the plan moves played."""
+        win, loss, open_, played = (int(v) for v in self._counts.cpu())
+        return dict(win=win, loss=loss, open=open_, plan_moves=played)
 
 
 def _best_move(label, length):

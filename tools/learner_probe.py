@@ -144,6 +144,13 @@ Parts:
               then on the tight pool of the record split by pool entry: labels collected under the rate-8 "feat+spare" TD table, fit()
               from that table and from zero, and on the held-out half label_agreement, the one-ply and the beam (3, 8) win rate before
               and after, with one sweep over rate and margin
+    window    the exact search over a state's piece window and the proof policy (tpl_placement_window_prove, window_prove,
+              ProofPolicy) on the tight pool of the record (part bound's): the record's two classical rows again (they must reproduce
+              win for win), then on 4,096 boards the classical one-ply player and the beam (3, 8), each alone and inside a ProofPolicy
+              at max_nodes 2^8, 2^12 and 2^16 -- win rate with its standard error, the verdicts 1, 2 and 3 per move number as shares of
+              the running boards, the episodes that held a verdict 1 and did not end won (which must be 0), the milliseconds of a
+              played step with reuse off and on beside the base's in alternated rounds, and the nodes a second of window_prove beside
+              prove_nodes on the same boards; the loose pool once.  --sections and --budgets choose what one call runs
     solve     the whole-game beam solver (tpl_placement_solve, solve_configs) under the classical weights: the share of forward seeds
               0 .. 9,999 it solves at L=5 / M=20 and L=10 / M=40 at widths 1, 8, 16 and 64 beside the share the reference's solver marks
               winnable in the same forward_configs call, and the share of the sweeps' carved pool (65,536, seed 7) it solves; the
@@ -171,7 +178,7 @@ PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600, "priority": 600
          "ntuple_sum": 600, "ntuple_sum_sweep": 600, "ntuple_stage": 600, "ntuple_stage_sweep": 900,
          "ntuple_feature": 600, "ntuple_feature_sweep": 900, "solve": 900, "move_features": 1100, "bound": 900,
          "ntuple_budget": 600, "ntuple_budget_sweep": 1100, "exact": 900, "ntuple_exact": 900, "labels": 900,
-         "rank": 1100}
+         "rank": 1100, "window": 1100}
 SCATTERED_ATOMICS = 0.08e12                                 # 64 lanes of a wave adding into 64 rows (float adds; integer adds unmeasured)
 VALU_CYCLES, SIMDS, CLOCK_HZ = 3.3, 1024, 2.4e9           # the move's instruction mix, 256 CUs x 4, the clock
 
@@ -3088,6 +3095,182 @@ def part_rank(rounds=5, reps=10, n=1 << 20, boards=4096, eval_boards=16384, log2
     return out
 
 
+def part_window(sections=("record", "rates", "verdicts", "time", "loose"), budgets=(8, 12, 16), boards=4096, rounds=5):
+    """The exact search over a state's window and the proof policy (include/tpl_learn.h: tpl_placement_window_prove; T.window_prove,
+    T.ProofPolicy) on the tight pool of the record -- part_bound's: carved L = 10 / M = 40, 65,536 configurations, seed 7, solved at
+    width 16, tighten_pool(M_new=16) -- and once on the loose pool.  One seed, one pool, the classical weight row."""
+    import numpy as np
+    import torch
+    import tetris_piclim as T
+    _plane_fields, _resident_planes = T.solve._plane_fields, T.solve._resident_planes
+    dev = "cuda:0"
+    L_, M_, M_new = 10, 40, 16
+    out = dict(part="window", sections=list(sections), budgets=[f"2^{b}" for b in budgets], boards=boards)
+
+    def progress(what):
+        print(json.dumps(what), file=sys.stderr, flush=True)
+
+    n = 1 << 16
+    env = T.BatchedTetris(L_, M_, 64, device=dev, seed=7)
+    rows, pieces = env.carved_configs(n, seed=7)
+    env.terminate()
+    found = T.solve_configs(rows, pieces, L_, M_, width=16, device=dev, validate=False)
+    tight = T.tighten_pool(rows, pieces, found["solved"], found["solution_len"], M_new)
+    out["pool"] = dict(size=int(tight[0].shape[0]), of=n, seed=7, L=L_, M=M_new, weights="classical")
+    classical = np.array(T.CLASSICAL_WEIGHTS)
+    bases = (("one_ply", 1, None), ("beam_3x8", 3, 8))
+
+    def result(e, wins):
+        p = wins / max(e, 1)
+        return dict(episodes=int(e), wins=int(wins), win_rate=round(p, 5), standard_error=round((p * (1 - p) / max(e, 1)) ** 0.5, 6))
+
+    def make(game_M, pool, depth, width, log2, reuse, count=boards):
+        env = T.BatchedTetris(L_, game_M, count, device=dev, seed=11, auto_reset=True, reward=(0.0, 1.0, 0.0), config_pool=pool)
+        env.reset()
+        base = T.HeuristicPolicy(env, classical, depth=depth) if width is None else T.BeamPolicy(env, classical, depth, width)
+        return env, base if log2 is None else T.ProofPolicy(env, base, max_nodes=1 << log2, reuse=reuse)
+
+    def play(env, player, steps, game_M):
+        """`steps` steps from the reset: episodes, wins, the episodes that held a verdict 1 and did not end won, the verdicts per move
+        number (column 0: a live plan was followed, or nothing was searched), and the seconds."""
+        count = env.num_envs
+        action = torch.empty(count, dtype=torch.uint8, device=dev)
+        reward = torch.empty(count, dtype=torch.float32, device=dev)
+        done = torch.empty(count, dtype=torch.uint8, device=dev)
+        tallies = torch.zeros(4, dtype=torch.int64, device=dev)           # episodes, wins, episodes with a proof, broken proofs
+        per_move = torch.zeros(game_M * 4, dtype=torch.int64, device=dev)
+        held = torch.zeros(count, dtype=torch.bool, device=dev)
+        proof = isinstance(player, T.ProofPolicy)
+        planes = _resident_planes(env)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            if proof:
+                moves = _plane_fields(*planes)[0].to(torch.int64)
+            player.act(out=action)
+            if proof:
+                per_move += torch.bincount(moves * 4 + player.verdict.to(torch.int64), minlength=game_M * 4)[:game_M * 4]
+                held |= player.played
+            env.step_into(action, reward, done)
+            over, won = done.bool(), reward == 1.0
+            tallies += torch.stack([over.sum(), (over & won).sum(), (over & held).sum(), (over & held & ~won).sum()])
+            held &= ~over
+        torch.cuda.synchronize()
+        seconds = time.perf_counter() - t0
+        e, w, with_proof, broken = tallies.tolist()
+        got = dict(result(e, w), steps=steps, seconds=round(seconds, 2), ms_per_step=round(seconds * 1e3 / steps, 3))
+        if proof:
+            got.update(episodes_that_held_a_verdict_1=with_proof, of_them_not_won=broken, stats=player.stats())
+            got["per_move"] = per_move.view(game_M, 4).tolist()
+        return got
+
+    if "record" in sections:                                   # the record's rows as the record plays them: they must reproduce
+        out["record"] = {}
+        for name, depth, width in bases:
+            env = T.BatchedTetris(L_, M_new, 1 << 14, device=dev, seed=11, auto_reset=True, reward=(0.0, 1.0, 0.0), config_pool=tight)
+            got = T.evaluate_heuristic(env, classical, None, 16 * (M_new + 1), depth=depth, width=width)
+            env.terminate()
+            out["record"][name] = result(int(got["episodes"][0]), int(got["wins"][0]))
+        progress(out["record"])
+
+    steps = 16 * (M_new + 1) * (1 << 14) // boards               # the record's episode budget on fewer boards
+    if "rates" in sections:
+        out["rates"] = {}
+        for name, depth, width in bases:
+            got = {}
+            for log2 in (None,) + tuple(budgets):
+                env, player = make(M_new, tight, depth, width, log2, True)
+                got["base" if log2 is None else f"proof_2^{log2}"] = play(env, player, steps, M_new)
+                env.terminate()
+                progress({name: {k: {x: y for x, y in v.items() if x != "per_move"} for k, v in got.items()}})
+            out["rates"][name] = got
+        out["rates"]["feat+spare_rate_8_table"] = "skipped: no table file is kept in the repository"
+
+    if "verdicts" in sections:                                 # reuse off: every running board is searched at every move
+        out["verdicts"] = {}
+        for log2 in budgets:
+            env, player = make(M_new, tight, 1, None, log2, False)
+            got = play(env, player, 8 * (M_new + 1), M_new)
+            env.terminate()
+            table = []
+            for move, (none, win, loss, open_) in enumerate(got.pop("per_move")):
+                total = max(none + win + loss + open_, 1)
+                table.append(dict(move=move, running=total, win=round(win / total, 5), loss=round(loss / total, 5),
+                                  open=round(open_ / total, 5)))
+            out["verdicts"][f"2^{log2}"] = dict(got, per_move=table)
+            progress({f"2^{log2}": out["verdicts"][f"2^{log2}"]})
+
+    if "time" in sections:
+        out["time"] = dict(steps=[], search=[])
+        median = lambda ts: sorted(ts)[len(ts) // 2]
+        for name, depth, width in bases:
+            for log2 in budgets:
+                arms = {}
+                for arm, (b, reuse) in (("base", (None, False)), ("reuse_off", (log2, False)), ("reuse_on", (log2, True))):
+                    arms[arm] = make(M_new, tight, depth, width, b, reuse)
+                times = {arm: [] for arm in arms}
+                for _ in range(rounds):                        # alternated: each arm plays 64 steps on from where it stands
+                    for arm, (env, player) in arms.items():
+                        times[arm].append(play(env, player, 64, M_new)["ms_per_step"])
+                for env, _ in arms.values():
+                    env.terminate()
+                line = dict(base=name, max_nodes=f"2^{log2}", boards=boards, ms_per_step={a: median(t) for a, t in times.items()},
+                            min={a: min(t) for a, t in times.items()})
+                line["ratio_to_base"] = {a: round(line["ms_per_step"][a] / line["ms_per_step"]["base"], 3) for a in ("reuse_off", "reuse_on")}
+                out["time"]["steps"].append(line)
+                progress(line)
+        # nodes a second: window_prove beside prove_nodes on the same boards, mid-game, alternated
+        env, player = make(M_new, tight, 1, None, None, False)
+        play(env, player, 40, M_new)
+        state = env.packed_state()
+        for log2 in budgets:
+            mine = T.window_prove(env, max_nodes=1 << log2)
+            H = mine["horizon"].to(torch.int64)
+            lists = torch.full((boards, M_new + 1), 7, dtype=torch.uint8, device=dev)
+            planes = _resident_planes(env)
+            window = (planes[1][:, 3].to(torch.int64) & 0xFFFFFFFF) | (((planes[1][:, 2] >> 28) & 15).to(torch.int64) << 32)
+            d = torch.arange(12, device=dev)
+            entries = ((window[:, None] >> (3 * d)) & 7).to(torch.uint8)
+            at = (M_new - H)[:, None] + d
+            keep = d[None, :] < H[:, None]
+            lists[torch.arange(boards, device=dev)[:, None].expand(-1, 12)[keep], at[keep]] = entries[keep]
+            args = (state["rows"], state["lines"], (M_new - H).to(torch.uint8), torch.arange(boards, device=dev, dtype=torch.int32), lists,
+                    L_, M_new)
+            ref = T.prove_nodes(*args, max_nodes=1 << log2, device=dev, validate=False)
+            same = all(torch.equal(mine[k], ref[k]) for k in ("solved", "proved", "solution_len", "bound", "nodes"))
+            total = float(mine["nodes"].double().sum())
+            ta, tb = [], []
+            for _ in range(rounds):
+                ta.append(_timed(lambda: T.prove_nodes(*args, max_nodes=1 << log2, device=dev, validate=False), 1, warmup=0))
+                tb.append(_timed(lambda: T.window_prove(env, max_nodes=1 << log2), 1, warmup=0))
+            line = dict(max_nodes=f"2^{log2}", boards=boards, nodes=int(total), outputs_equal=bool(same),
+                        prove_nodes_ms=round(median(ta) * 1e3, 3), window_prove_ms=round(median(tb) * 1e3, 3),
+                        prove_nodes_nodes_per_second=round(total / median(ta), 1), window_prove_nodes_per_second=round(total / median(tb), 1),
+                        ratio=round(median(ta) / median(tb), 4))
+            out["time"]["search"].append(line)
+            progress(line)
+        env.terminate()
+
+    if "loose" in sections:                                    # the loose pool: every policy wins about 0.999 there
+        loose = (rows, pieces)
+        got = {}
+        for log2 in (None, 12):
+            env, player = make(M_, loose, 1, None, log2, True)
+            got["base" if log2 is None else f"proof_2^{log2}"] = play(env, player, 16 * (M_ + 1), M_)
+            env.terminate()
+        for v in got.values():
+            v.pop("per_move", None)
+        out["loose"] = got
+        progress(got)
+    res = subprocess.run(["bash", os.path.join(ROOT, "tools", "kernel_resources.sh"), T._learn_lib.build_library()],
+                         capture_output=True, text=True, cwd=ROOT)
+    out["kernel"] = [" ".join(l.split()) for l in res.stdout.splitlines() if "window_prove" in l or "placement_exact_nodes" in l]
+    out["not_measured"] = ("other weight rows, the fourteen features and spare_weight other than 0; other pools and seeds; learners and "
+                           "table policies as bases; a step's milliseconds include the base's act(), the state reads, under reuse the "
+                           "afterstate enumeration, and the environment's step")
+    return out
+
+
 def part_ntuple_shape_ab(parent, rounds=5, reps=20, n=1 << 18):
     import ctypes as C
     import numpy as np
@@ -3152,6 +3335,8 @@ def main():
     ap.add_argument("--part", choices=sorted(PARTS) + ["ntuple_shape_ab"])
     ap.add_argument("--parent", default=None, help="of part ntuple_shape_ab: the learner library of the build to compare against")
     ap.add_argument("--chunk", default=None, help="I/K: of part ntuple_coherent_sweep, every K-th cell from the I-th on")
+    ap.add_argument("--sections", default=None, help="of part window: which of record,rates,verdicts,time,loose to run (all)")
+    ap.add_argument("--budgets", default=None, help="of part window: the log2 of the node budgets, e.g. 8,12 (8,12,16)")
     args = ap.parse_args()
     if args.part:
         kw = {}
@@ -3162,6 +3347,13 @@ def main():
             if not 0 <= i < k:
                 ap.error("--chunk I/K needs 0 <= I < K")
             kw["chunk"] = (i, k)
+        if args.sections or args.budgets:
+            if args.part != "window":
+                ap.error("--sections and --budgets go with --part window")
+            if args.sections:
+                kw["sections"] = tuple(args.sections.split(","))
+            if args.budgets:
+                kw["budgets"] = tuple(int(v) for v in args.budgets.split(","))
         if args.part == "ntuple_shape_ab":
             if not args.parent:
                 ap.error("--part ntuple_shape_ab needs --parent LIB")
