@@ -1194,6 +1194,45 @@ int tpl_ntuple_exact(const int16_t* rows, const uint8_t* pieces, int64_t n, int3
                      float r_line, float r_win, float r_lose, float gamma, int32_t max_nodes, int32_t shortest, uint8_t* solved,
                      uint8_t* proved, int32_t* solution_len, uint8_t* actions, int32_t* bound, uint32_t* nodes, void* stream);
 
+/* The exact search over a state's window with its children ordered by an n-tuple table (csrc/learn/ntuple_window.hip).
+ * tpl_ntuple_window_prove IS tpl_placement_window_prove WITH ONE THING REPLACED, exactly as tpl_ntuple_exact is tpl_placement_exact
+ * with one thing replaced: the value that orders a node's children.  Everything of the window frame is unchanged: the two packed
+ * planes; which board is running, finished or skipped; known = 12 - moves % 10, rem = M - moves, H = min(known, rem); the outputs
+ * solved, proved, solution_len, plan [TPL_WINDOW_PLAN], bound, nodes, horizon and verdict; what is written for a finished board and
+ * for a skipped board (NOT SEARCHED; bound and horizon are still written); the verdicts TPL_WINDOW_NONE / WIN / LOSS / OPEN and
+ * what they mean.  VERDICT 3 PROVES NOTHING ABOUT THE GAME.
+ *
+ * THE SEARCH of a running, unskipped board IS tpl_ntuple_exact's WITH shortest = 1, run on the configuration whose rows are the
+ * board's and whose list is q[0], ..., q[H - 1], 0 -- q the window's entries, the falling piece first -- in the game (L - lines, H).
+ * solved, proved, solution_len, actions[0 .. H), bound and nodes are BYTE FOR BYTE what tpl_ntuple_exact writes for that
+ * configuration; plan is actions padded with 255 to twelve entries.  Two things follow:
+ *   - V IS READ AT THE ITERATION'S BUDGET B, under (L - lines, B): the counter index is that of the shifted game at the child's own
+ *     lines' and moves', and under a budget table spare = 4 (B - moves') - cells.  An iteration below the horizon therefore reads
+ *     the low-spare bins, as tpl_ntuple_exact does.
+ *   - NOTHING DEPENDS ON THE ABSOLUTE lines OR moves, only on what is left: the search starts from a fresh root of the shifted game.
+ *
+ * KNOWN PIECES.  The child made at depth d is valued with q[d + 1] as its falling piece.  A child that runs has
+ * d + 1 < B <= H <= known, so q[d + 1] is a TRUE piece of the episode: NO VALUE IS EVER READ UNDER A PIECE THE AGENT DOES NOT KNOW.
+ * List entry H (index 12 where H = 12) is a defined 0; it is never used for a value.
+ *
+ * THE TABLE is one of the four plain forms, told apart by `entries` as tpl_ntuple_exact tells them apart; any other count is refused
+ * first, with tpl_ntuple_exact's message.
+ *
+ * Two consequences, inherited from the two parents, on which the tests rest:
+ *   1. UNDER proved = 1, solved, solution_len, bound and verdict ARE INDEPENDENT OF THE TABLE, gamma and the reward, and equal
+ *      tpl_placement_window_prove's on the same board wherever that one is proved too.
+ *   2. For a board searched out without a win, nodes is independent of the order as well.
+ *
+ * Four kernels, one per form, of tpl_placement_window_prove's frame: ONE BOARD PER WAVEFRONT, the stack -- twelve records of 80
+ * bytes, without a carry --, the shape table and sixteen bytes of pieces in static LDS, the table in global memory.
+ * Refused before any HIP call: an `entries` that is none of the four, first; then whatever tpl_ntuple_exact refuses of table, r_line,
+ * r_win, r_lose and gamma (a NULL table, a table not 4-byte aligned, a value that is not finite) and whatever
+ * tpl_placement_window_prove refuses of the planes, n, L, M, max_nodes, skip and the outputs. */
+int tpl_ntuple_window_prove(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const int32_t* table,
+                            int64_t entries, float r_line, float r_win, float r_lose, float gamma, int32_t max_nodes,
+                            const uint8_t* skip, uint8_t* solved, uint8_t* proved, int32_t* solution_len, uint8_t* plan,
+                            int32_t* bound, uint32_t* nodes, uint8_t* horizon, uint8_t* verdict, void* stream);
+
 /* The ranking update: what a proved move label teaches a table (csrc/learn/ntuple_rank.hip).  tpl_placement_exact_labels labels every
  * placement of a board 1 (proved winning), 2 (proved losing) or 3 (unproved).  tpl_ntuple_rank reads such a row beside the board and a
  * table and says whether the table's one-ply policy already prefers a proved win to every proved loss; where it does not, it names the

@@ -19,7 +19,8 @@ __all__ = ["BatchedTetris", "Tetris", "Snapshot", "OBS_DIM", "NUM_ACTIONS", "RUN
            "ntuple_feature_bins", "NTUPLE_BUDGET_FORMS", "ntuple_budget", "ntuple_budget_bins", "solve_configs", "prove_configs", "ntuple_prove_configs", "tighten_pool", "CLASSICAL_WEIGHTS", "FEATURE_NAMES",
            "MOVE_FEATURE_NAMES", "DELLACHERIE_WEIGHTS", "move_bound", "config_bound", "config_index", "PoolTally", "resample_pool",
            "curriculum_weights", "PoolCurriculum", "prove_nodes", "label_moves", "label_states", "blunders",
-           "NTupleRanker", "LabelSet", "collect_labels", "label_agreement", "window_prove", "ProofPolicy"]
+           "NTupleRanker", "LabelSet", "collect_labels", "label_agreement", "window_prove", "ProofPolicy",
+           "ntuple_window_prove", "TableProofPolicy"]
 
 
 def __getattr__(name):
@@ -50,7 +51,8 @@ def __getattr__(name):
                 "ntuple_feature_bins", "NTUPLE_BUDGET_FORMS", "ntuple_budget", "ntuple_budget_bins", "NTupleRanker"):
         return getattr(importlib.import_module(__name__ + ".ntuple"), name)
     if name in ("solve_configs", "prove_configs", "ntuple_prove_configs", "tighten_pool", "CLASSICAL_WEIGHTS", "config_bound", "prove_nodes",
-                "label_moves", "label_states", "blunders", "LabelSet", "collect_labels", "label_agreement", "window_prove", "ProofPolicy"):
+                "label_moves", "label_states", "blunders", "LabelSet", "collect_labels", "label_agreement", "window_prove", "ProofPolicy",
+                "ntuple_window_prove", "TableProofPolicy"):
         return getattr(importlib.import_module(__name__ + ".solve"), name)
     if name in ("config_index", "PoolTally", "resample_pool", "curriculum_weights", "PoolCurriculum"):
         return getattr(importlib.import_module(__name__ + ".curriculum"), name)

@@ -26,7 +26,7 @@ _UNITS = [os.path.join(_LEARN_CSRC, f) for f in ("replay.hip", "pack.hip", "prio
                                                       "solve_bound.hip", "beam_move_bound.hip", "solve_move_bound.hip",
                                                       "exact.hip", "exact_move.hip", "ntuple_exact.hip", "curriculum.hip", "exact_nodes.hip",
                                                       "exact_nodes_move.hip", "exact_window.hip", "exact_window_move.hip",
-                                                      "ntuple_rank.hip", "heuristic.hip")]
+                                                      "ntuple_window.hip", "ntuple_rank.hip", "heuristic.hip")]
 
 # entry points declared in include/tpl_learn.h (tests check that the .so exports every one of them)
 LEARN_SYMBOLS = [
@@ -53,7 +53,7 @@ LEARN_SYMBOLS = [
     "tpl_config_index", "tpl_pool_tally", "tpl_pool_resample",
     "tpl_placement_exact_nodes", "tpl_placement_exact_nodes_move", "tpl_placement_exact_labels", "tpl_placement_exact_labels_move",
     "tpl_ntuple_rank",
-    "tpl_placement_window_prove", "tpl_placement_window_prove_move",
+    "tpl_placement_window_prove", "tpl_placement_window_prove_move", "tpl_ntuple_window_prove",
 ]
 NSTEP_MAX = 16
 BEAM_MAX_DEPTH, BEAM_MAX_WIDTH = 12, 64
@@ -238,6 +238,9 @@ def lib() -> C.CDLL:
     # the table-ordered exact search: the table and its entry count for the weights, the reward and gamma for spare_weight
     L.tpl_ntuple_exact.argtypes = [vp, vp, i64, i32, i32, vp, i64, f32, f32, f32, f32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.tpl_ntuple_exact.restype = i32
+    # the table-ordered window search: tpl_placement_window_prove's arguments with tpl_ntuple_exact's table, reward and gamma
+    L.tpl_ntuple_window_prove.argtypes = [vp, vp, i64, i32, i32, vp, i64, f32, f32, f32, f32, i32, vp] + [vp] * 8 + [vp]
+    L.tpl_ntuple_window_prove.restype = i32
     # the ranking update's chooser: the planes, the table and its entry count, the label rows, then the eleven outputs
     L.tpl_ntuple_rank.argtypes = [vp, vp, i64, i32, i32, vp, i64, vp, f32, f32, f32, f32, f32, i32] + [vp] * 12
     L.tpl_ntuple_rank.restype = i32
@@ -1151,19 +1154,10 @@ def window_entries(window) -> np.ndarray:
     return ((window[:, None] >> (np.uint64(3) * np.arange(WINDOW_PLAN, dtype=np.uint64))) & np.uint64(7)).astype(np.int64)
 
 
-def placement_window_prove(rows, lines, moves, state, window, L: int, M: int, weights, max_nodes: int, spare_weight: float = 0.0,
-                           skip=None) -> dict:
-    """The rule of tpl_placement_window_prove (include/tpl_learn.h) for n states of the game (L, M) given by their fields: rows uint16
-    [n, 20] (bit x = column x), lines, moves and state integers [n] (state 0 = running), window uint64 [n] (36 bits); one weight row
-    [12] or [14], max_nodes in [1, 2^24], one finite spare_weight, skip None or [n] (nonzero: not searched).
-    A running board with lines < L and moves < M has known = 12 - moves % 10, rem = M - moves and the horizon H = min(known, rem), and is
-    searched as the configuration (rows, window entries 0 .. H - 1) of the game (L - lines, H), shortest; anything else is finished.
-    Returns a dict in the C layout: solved, proved uint8 [n], solution_len int32 [n], plan uint8 [n, 12] padded with 255, bound int32
-    [n], nodes uint32 [n], horizon uint8 [n], verdict uint8 [n] (WINDOW_NONE / WIN / LOSS / OPEN), and known uint8 [n]."""
-    L, M = int(L), int(M)
-    if not (1 <= L <= 250 and 1 <= M <= SOLVE_MAX_MOVES):
-        raise ValueError(f"L and M must be in [1, 250] and [1, {SOLVE_MAX_MOVES}]")
-    _exact_arguments(weights, max_nodes, True, spare_weight)
+def _window_frame(rows, lines, moves, state, window, L: int, M: int, skip, search) -> dict:
+    """The framing the two window mirrors share: the fields checked, live / known / rem / H, the dict in the C layout, the boards grouped
+    by (lines, H), and the verdicts.  search(rows [k, 20], lists [k, H + 1], L - lines, H) -> the six arrays of an exact mirror for the
+    group's configurations, shortest."""
     rows = np.asarray(rows)
     rows = (rows.view(np.uint16) if rows.dtype == np.int16 else rows.astype(np.uint16)).reshape(-1, 20)
     n = rows.shape[0]
@@ -1200,13 +1194,29 @@ def placement_window_prove(rows, lines, moves, state, window, L: int, M: int, we
     for at_lines, at_H in sorted({(int(a), int(b)) for a, b in zip(lines[todo], H[todo])}):
         idx = np.flatnonzero(todo & (lines == at_lines) & (H == at_H))
         lists = np.concatenate([q[idx, :at_H], np.zeros((idx.size, 1), np.int64)], axis=1)      # [k, H + 1]: the last is never placed
-        solved, proved, length, actions, _, nodes = placement_exact(rows[idx], lists, L - at_lines, at_H, weights, max_nodes, True,
-                                                                    spare_weight)
+        solved, proved, length, actions, _, nodes = search(rows[idx], lists, L - at_lines, at_H)
         out["solved"][idx], out["proved"][idx], out["solution_len"][idx], out["nodes"][idx] = solved, proved, length, nodes
         out["plan"][idx, :at_H] = actions
         out["verdict"][idx] = np.where(solved == 1, WINDOW_WIN,
                                        np.where((proved == 1) & (at_H == rem[idx]), WINDOW_LOSS, WINDOW_OPEN))
     return out
+
+
+def placement_window_prove(rows, lines, moves, state, window, L: int, M: int, weights, max_nodes: int, spare_weight: float = 0.0,
+                           skip=None) -> dict:
+    """The rule of tpl_placement_window_prove (include/tpl_learn.h) for n states of the game (L, M) given by their fields: rows uint16
+    [n, 20] (bit x = column x), lines, moves and state integers [n] (state 0 = running), window uint64 [n] (36 bits); one weight row
+    [12] or [14], max_nodes in [1, 2^24], one finite spare_weight, skip None or [n] (nonzero: not searched).
+    A running board with lines < L and moves < M has known = 12 - moves % 10, rem = M - moves and the horizon H = min(known, rem), and is
+    searched as the configuration (rows, window entries 0 .. H - 1) of the game (L - lines, H), shortest; anything else is finished.
+    Returns a dict in the C layout: solved, proved uint8 [n], solution_len int32 [n], plan uint8 [n, 12] padded with 255, bound int32
+    [n], nodes uint32 [n], horizon uint8 [n], verdict uint8 [n] (WINDOW_NONE / WIN / LOSS / OPEN), and known uint8 [n]."""
+    L, M = int(L), int(M)
+    if not (1 <= L <= 250 and 1 <= M <= SOLVE_MAX_MOVES):
+        raise ValueError(f"L and M must be in [1, 250] and [1, {SOLVE_MAX_MOVES}]")
+    _exact_arguments(weights, max_nodes, True, spare_weight)
+    return _window_frame(rows, lines, moves, state, window, L, M, skip,
+                         lambda r, p, game_L, H: placement_exact(r, p, game_L, H, weights, max_nodes, True, spare_weight))
 
 
 # ------------------------------------------------------------------------------------------------ the n-tuple value function
@@ -1604,6 +1614,34 @@ def ntuple_exact(rows, pieces, L: int, M: int, table, max_nodes: int, shortest: 
             else:                                               # searched out: no sequence of placements wins within M moves
                 del stacks[s]
     return solved, proved, length, actions, bound, nodes
+
+
+# The rule of tpl_ntuple_window_prove (include/tpl_learn.h) on the host: placement_window_prove's framing (_window_frame, shared) with
+# ntuple_exact for placement_exact, from the ROW form.  The device unpacks the planes and runs its own copy of the search
+# (csrc/learn/ntuple_window.hip) -- the two share nothing.
+def ntuple_window_prove(rows, lines, moves, state, window, L: int, M: int, table, max_nodes: int, gamma: float = 1.0,
+                        reward=(1.0, 0.0, 0.0), skip=None) -> dict:
+    """The rule of tpl_ntuple_window_prove (include/tpl_learn.h) for n states of the game (L, M): placement_window_prove's fields and
+    skip mask, with ntuple_exact's table (int32, one of NTUPLE_EXACT_FORMS by its entry count), gamma and reward = (r_line, r_win,
+    r_lose) for the weights and spare_weight.  A running board with lines < L and moves < M is searched as the configuration (rows,
+    [window entries 0 .. H - 1, 0]) of the game (L - lines, H) by ntuple_exact, shortest; anything else is finished.
+    Returns placement_window_prove's dict, `known` included."""
+    L, M = int(L), int(M)
+    if not (1 <= L <= 250 and 1 <= M <= SOLVE_MAX_MOVES):
+        raise ValueError(f"L and M must be in [1, 250] and [1, {SOLVE_MAX_MOVES}]")
+    if isinstance(max_nodes, bool) or not isinstance(max_nodes, (int, np.integer)) or not 1 <= int(max_nodes) <= EXACT_MAX_NODES:
+        raise ValueError(f"max_nodes must be an integer in [1, {EXACT_MAX_NODES}]")
+    max_nodes = int(max_nodes)
+    table = _ntuple_exact_table(table)
+    try:
+        with np.errstate(over="ignore"):
+            values = [np.float32(gamma)] + [np.float32(v) for v in reward]
+    except (TypeError, ValueError):
+        raise ValueError("gamma must be a number and reward three numbers (r_line, r_win, r_lose)") from None
+    if len(values) != 4 or not all(np.isfinite(v) for v in values):
+        raise ValueError("gamma and reward = (r_line, r_win, r_lose) must be finite (in float32)")
+    return _window_frame(rows, lines, moves, state, window, L, M, skip,
+                         lambda r, p, game_L, H: ntuple_exact(r, p, game_L, H, table, max_nodes, True, gamma, reward))
 
 
 def ntuple_steps(error, rate) -> np.ndarray:

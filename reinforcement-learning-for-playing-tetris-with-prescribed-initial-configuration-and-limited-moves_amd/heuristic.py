@@ -279,7 +279,7 @@ def _win_count_reward(env) -> None:
 @torch.no_grad()
 def evaluate_heuristic(env, weights, boards_per_member: Optional[int], steps: int, policy=None, depth: int = 1,
                        width: Optional[int] = None, bound: bool = False, spare_weight: float = 0.0, per_config: bool = False,
-                       proof: Optional[int] = None) -> dict:
+                       proof: Optional[int] = None, proof_table=None) -> dict:
     """Play `steps` steps of the population `weights` ([P, 12] or [12]) on `env` from a full reset: an auto-reset environment
     with a configuration pool and reward parameters (0, 1, 0), so that the summed reward is the number of wins.  Member p plays
     boards [p * boards_per_member, (p + 1) * boards_per_member).  Returns episodes and wins as int64 numpy arrays [P] and
@@ -292,9 +292,15 @@ def evaluate_heuristic(env, weights, boards_per_member: Optional[int], steps: in
     members (a PoolTally observed before every step); the three other keys are what they are without it.
     proof: None, or a node budget -- then the policy plays inside a ProofPolicy(env, policy, max_nodes=proof) (solve.py): the first
     move of a plan that the exact search over the state's window proves winning, the policy's own move elsewhere; the dict gains
-    proof, that policy's stats().  None leaves every result as it is."""
+    proof, that policy's stats().  None leaves every result as it is.
+    proof_table: None or False, or with `proof` an n-tuple table of one of the four plain forms (solve.ntuple_window_prove's): the proofs are
+    then ordered by it (gamma 1, reward (1, 0, 0)) instead of the classical weights.  It only orders the search."""
     if not isinstance(per_config, bool):
         raise ValueError("per_config must be True or False")
+    if proof_table is False:                                   # NTupleLearner.evaluate's default: the classical order
+        proof_table = None
+    if proof is None and proof_table is not None:
+        raise ValueError("proof_table orders the proofs: it needs proof, a node budget")
     if proof is not None:
         from .solve import _max_nodes
         proof = _max_nodes(proof)
@@ -325,7 +331,8 @@ def evaluate_heuristic(env, weights, boards_per_member: Optional[int], steps: in
     player = policy
     if proof is not None:
         from .solve import ProofPolicy
-        player = ProofPolicy(env, policy, max_nodes=proof)
+        player = ProofPolicy(env, policy, max_nodes=proof) if proof_table is None else \
+            ProofPolicy(env, policy, max_nodes=proof, table=proof_table)
     n, d = env.num_envs, env.device
     action = torch.empty(n, dtype=torch.uint8, device=d)
     reward = torch.empty(n, dtype=torch.float32, device=d)

@@ -829,7 +829,7 @@ class NTupleLearner:
 
     @torch.no_grad()
     def evaluate(self, steps: int, depth: Optional[int] = None, width: Optional[int] = None, bound: Optional[bool] = None,
-                 per_config: bool = False, proof: Optional[int] = None) -> dict:
+                 per_config: bool = False, proof: Optional[int] = None, proof_table=False) -> dict:
         """Play `steps` greedy steps from a full reset and count: episodes (the steps' done flags), wins (the afterstates of the
         moves played whose state is "won": every reward parameter counts the same wins) and win_rate = wins / max(episodes, 1).
         depth: how deep the greedy policy searches -- None: the learner's own; 1 or 2 plays the table as it stands at that depth.
@@ -841,9 +841,26 @@ class NTupleLearner:
         proof: None, or a node budget -- then the policy plays inside a ProofPolicy(env, policy, max_nodes=proof) (solve.py): the
         first move of a plan that the exact search over the state's window proves winning, the table's move elsewhere; a plan's
         move wins exactly where it is the plan's last.  The dict gains proof, that policy's stats().  None leaves every result as
-        it is."""
+        it is.
+        proof_table: False or None -- the proofs are ordered by the classical weights --, True -- by the learner's own table as it
+        stands, with the learner's gamma and the environment's reward; refused where the table is not of one of the four plain forms
+        "2x4", "3x3", "feat", "feat+spare" --, or a table of one of those forms, used as given with gamma 1 and reward (1, 0, 0)
+        (solve.ntuple_window_prove).  It only orders the search, and needs `proof`."""
         if not isinstance(per_config, bool):
             raise ValueError("per_config must be True or False")
+        ordered = proof_table is not None and proof_table is not False
+        if proof is None and ordered:
+            raise ValueError("proof_table orders the proofs: it needs proof, a node budget")
+        order = {}
+        if ordered and proof_table is True:
+            from ._learn_lib import NTUPLE_EXACT_FORMS
+            if self.greedy.staged or self.greedy.shape not in NTUPLE_EXACT_FORMS:
+                raise ValueError(f"proof_table=True orders the proofs by the learner's table, which must be of one of the four plain "
+                                 f"forms {', '.join(map(repr, NTUPLE_EXACT_FORMS))}; this learner's is "
+                                 f"{'staged ' if self.greedy.staged else ''}{self.greedy.shape!r}")
+            order = dict(table=self.table, gamma=self.greedy.gamma, reward=tuple(float(v) for v in self.env.reward_params))
+        elif ordered:
+            order = dict(table=proof_table)
         if proof is not None:
             from .solve import ProofPolicy, _max_nodes
             proof = _max_nodes(proof)
@@ -860,7 +877,7 @@ class NTupleLearner:
             if (depth is not None and _depth(depth) != self.depth) or bound != greedy.bound:
                 greedy = NTuplePolicy(env, self.table, greedy.gamma, 0.0, greedy.seed, self.depth if depth is None else depth, bound=bound)
             player, arguments = greedy, dict(after=self._next, step=0)
-        prover = None if proof is None else ProofPolicy(env, player, max_nodes=proof)
+        prover = None if proof is None else ProofPolicy(env, player, max_nodes=proof, **order)
         act = lambda: (player if prover is None else prover).act(out=self._action, **arguments)
         episodes = torch.zeros(env.num_envs, dtype=torch.int32, device=d)
         wins = torch.zeros(env.num_envs, dtype=torch.int32, device=d)

@@ -27,6 +27,8 @@ proved-losing move was taken although a proved-winning one was there.
 12 - moves mod 10 of them, instead of a configuration's list (tpl_placement_window_prove; csrc/learn/exact_window.hip).  A win it
 finds is a win of the real game; no win proves a loss only where the window reaches the end of the game, and otherwise proves
 nothing.  `ProofPolicy` wraps any policy with it: a proved plan's move where there is one, the base policy's move elsewhere.
+`ntuple_window_prove` is that search with its children ordered by an n-tuple table, as `ntuple_prove_configs` is `prove_configs`'
+(tpl_ntuple_window_prove; csrc/learn/ntuple_window.hip), and `ProofPolicy(table=...)` plays with it.
 
 `collect_labels` plays a policy on an environment with a pool and keeps the boards the labels decide -- a proved win and a proved loss
 among their moves -- in a `LabelSet`, the input of `NTupleRanker.fit` (ntuple.py); `label_agreement` counts how often a table's greedy
@@ -40,7 +42,7 @@ from ._learn_lib import BEAM_MAX_WIDTH, EXACT_MAX_NODES, NUM_FEATURES, NUM_MOVE_
 
 __all__ = ["CLASSICAL_WEIGHTS", "solve_configs", "prove_configs", "ntuple_prove_configs", "tighten_pool", "config_bound",
            "prove_nodes", "label_moves", "label_states", "blunders", "LabelSet", "collect_labels", "label_agreement", "window_prove",
-           "ProofPolicy"]
+           "ProofPolicy", "ntuple_window_prove", "TableProofPolicy"]
 
 # cleared, won, lost, holes, aggregate height, max height, bumpiness, row and column transitions, wells, rows with holes, hole depth:
 # the classical signs, a sensible default for the supply (0.99925 of a carved L = 10 / M = 40 pool at one ply)
@@ -452,6 +454,53 @@ def window_prove(env, weights=None, max_nodes: int = 1 << 12, spare_weight: floa
     return out
 
 
+def _window_table(table, d):
+    """A table that orders the window search: _exact_table's, a numpy int32 array uploaded first.  A tensor that already lies
+    contiguous on device d is returned as it is, not copied.  d None: checked and left where it is."""
+    import torch
+    if isinstance(table, np.ndarray) and table.dtype == np.int32 and table.ndim == 1:
+        table = torch.from_numpy(np.array(table, np.int32))    # a copy: the array may be read-only
+    return _exact_table(table, table.device if d is None and _is_tensor(table) else d)
+
+
+def _ntuple_window_launch(env, planes, table, reward, gamma: float, max_nodes: int, skip, out: dict) -> None:
+    """tpl_ntuple_window_prove on the resident boards of `env` into the buffers of _window_buffers."""
+    import torch
+    from . import _learn_lib
+    stream = torch._C._cuda_getCurrentRawStream(env.device.index)
+    _learn_lib.check(_learn_lib.lib().tpl_ntuple_window_prove(
+        planes[0], planes[1], env.num_envs, env.L, env.M, table.data_ptr(), int(table.shape[0]), reward[0], reward[1], reward[2], gamma,
+        max_nodes, None if skip is None else skip.data_ptr(), *(out[k].data_ptr() for k in WINDOW_OUTPUTS), stream))
+
+
+def ntuple_window_prove(env, table, gamma: float = 1.0, reward=(1.0, 0.0, 0.0), max_nodes: int = 1 << 12, skip=None) -> dict:
+    """window_prove with the children of a node ordered by an n-tuple table instead of a weight row (the rule: include/tpl_learn.h,
+    tpl_ntuple_window_prove; csrc/learn/ntuple_window.hip), one wavefront per board.
+
+    table: an int32 tensor on the environment's device (a numpy int32 array is uploaded) of one of the four plain forms -- "2x4",
+    "3x3", "feat" or "feat+spare" by its entry count; a sum, a staged or a "3x3+feat" table is refused.  gamma and reward = (r_line,
+    r_win, r_lose) are ntuple_prove_configs': a child is worth reward, or reward + gamma * V(its board, the next KNOWN piece) where it
+    runs, V read in the game (L - lines, B) of the iteration.  They and the table only order the children: they decide how many nodes
+    a search takes, and no verdict but between 3 and the two others.  max_nodes and skip are window_prove's.
+    Returns window_prove's dict with the same keys and dtypes.  **Verdict 3 proves nothing about the game, neither way.**
+    The environment is read, never written; no host wait."""
+    import torch
+    from .lookahead import _boards, _state_ptrs
+    _boards(env, "ntuple_window_prove")
+    max_nodes = _max_nodes(max_nodes)
+    gamma = _number("gamma", gamma)
+    reward = _reward(reward)
+    table = _window_table(table, env.device)
+    skip = _skip_mask(env, skip)
+    out = _window_buffers(env.num_envs, env.device)
+    _ntuple_window_launch(env, _state_ptrs(env), table, reward, gamma, max_nodes, skip, out)
+    out["solved"], out["proved"] = out["solved"].view(torch.bool), out["proved"].view(torch.bool)
+    moves, _, _ = _plane_fields(*_resident_planes(env))
+    out["known"] = (12 - moves % 10).to(torch.uint8)
+    out["action"] = out["plan"][:, 0]
+    return out
+
+
 class ProofPolicy:
     """A base policy with proofs on top: act() runs window_prove on the resident boards and plays the first move of the proved plan
     where the verdict is 1 (WIN), and base.act()'s move everywhere else.  `base` is any policy of this environment with act(out=...):
@@ -471,7 +520,18 @@ class ProofPolicy:
 
     After an act(): `verdict` uint8 [N] (the kernel's; 0 where a board was skipped), `played` bool [N] (the action is a plan's
     move) and `finishing` bool [N] (it is the plan's last move: it wins), `nodes` int32 [N] (0 where nothing was searched).
-    stats() counts since construction, on the device.  No host wait in act()."""
+    stats() counts since construction, on the device.  No host wait in act().
+
+    ProofPolicy(env, base, ..., table=None, gamma=1.0, reward=(1.0, 0.0, 0.0)) -- the three given by keyword -- makes a
+    TableProofPolicy, whose search is ordered by an n-tuple table (below); without them this class is all there is.  Only
+    ProofPolicy itself is switched: a subclass of ProofPolicy that wants the table order derives from TableProofPolicy, and one that
+    does not is refused `table=` by its own __init__ (a TypeError), as any unknown argument is."""
+
+    def __new__(cls, *args, **named):
+        # the table-ordered policy is a subclass with three more arguments; ProofPolicy(..., table=...) makes one
+        if cls is ProofPolicy and any(k in named for k in ("table", "gamma", "reward")):
+            cls = TableProofPolicy
+        return object.__new__(cls)
 
     def __init__(self, env, base, weights=None, max_nodes: int = 1 << 12, spare_weight: float = 0.0, reuse: bool = False):
         import torch
@@ -512,6 +572,10 @@ class ProofPolicy:
         return torch.stack([a[..., 0], a[..., 1] & 0x0FFFFFFF, a[..., 2], a[..., 3] & 0x0FFFFFFF, b[..., 0], b[..., 1] & 0x0FFFFFFF,
                             b[..., 2] & 0xFFFFF], dim=-1)
 
+    def _search(self, skip) -> None:
+        """The window search of the resident boards into self._out."""
+        _window_launch(self.env, self._ptrs, self.features, self._weights, self.spare_weight, self.max_nodes, skip, self._out)
+
     def act(self, out=None, verdict=None, **base_arguments):
         """uint8 [N]: the proved plan's move where this call's verdict is 1 or a live plan is held, base.act(out=out,
         **base_arguments)'s move elsewhere.  `verdict` (uint8 [N], optional) receives the kernel's verdicts.  No host wait."""
@@ -529,7 +593,7 @@ class ProofPolicy:
             same = (self._cells == self._cells_of(*self._planes)).all(dim=1)
             self._holds &= (state == 0) & (moves == self._expect) & same
             skip = self._holds.view(torch.uint8) if self.reuse else None
-            _window_launch(env, self._ptrs, self.features, self._weights, self.spare_weight, self.max_nodes, skip, self._out)
+            self._search(skip)
             found = self._out["verdict"] == 1
             if verdict is not None:
                 verdict.copy_(self._out["verdict"])
@@ -556,6 +620,39 @@ class ProofPolicy:
         """Counts since construction (one host read): the verdicts 1, 2 and 3 the kernel gave, and the plan moves played."""
         win, loss, open_, played = (int(v) for v in self._counts.cpu())
         return dict(win=win, loss=loss, open=open_, plan_moves=played)
+
+
+class TableProofPolicy(ProofPolicy):
+    """ProofPolicy with the search of every act() ordered by an n-tuple table: ntuple_window_prove for window_prove (the rule:
+    include/tpl_learn.h, tpl_ntuple_window_prove).  ProofPolicy(env, base, table=...) makes one.  table, gamma and reward are
+    ntuple_window_prove's; they only order the search, so everything a verdict 1 promises stands as it does there.
+
+    **The table tensor is HELD, not copied: a tensor that lies contiguous on the environment's device is read as it stands at each
+    act(), so a learner's table orders the proofs with whatever it has learnt by then.**  (A numpy table, or one on another device, is
+    uploaded once.)  table together with weights or a non-zero spare_weight is refused: a search has one order.  table=None is
+    ProofPolicy as it stands, weights and spare_weight included; a gamma or reward other than the defaults is then refused, since
+    nothing would read it.  The kept plans, reuse, stats(), verdict, played, finishing and nodes
+    are ProofPolicy's, untouched."""
+
+    def __init__(self, env, base, weights=None, max_nodes: int = 1 << 12, spare_weight: float = 0.0, reuse: bool = False, table=None,
+                 gamma: float = 1.0, reward=(1.0, 0.0, 0.0)):
+        if table is None:
+            if (_number("gamma", gamma), _reward(reward)) != (1.0, (1.0, 0.0, 0.0)):
+                raise ValueError("gamma and reward order the search through a table: without table= they are refused, not ignored")
+            super().__init__(env, base, weights, max_nodes, spare_weight, reuse)
+            self.table = None
+            return
+        if weights is not None or _spare_weight(spare_weight, True) != 0.0:
+            raise ValueError("table orders the search in place of weights and spare_weight: give the table, or those two")
+        self.gamma, self.reward = _number("gamma", gamma), _reward(reward)
+        table = _window_table(table, None)                     # the form, before anything of the environment is touched
+        super().__init__(env, base, None, max_nodes, 0.0, reuse)
+        self.table = _window_table(table, env.device)
+
+    def _search(self, skip) -> None:
+        if self.table is None:
+            return super()._search(skip)
+        _ntuple_window_launch(self.env, self._ptrs, self.table, self.reward, self.gamma, self.max_nodes, skip, self._out)
 
 
 def _best_move(label, length):

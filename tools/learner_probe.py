@@ -178,7 +178,7 @@ PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600, "priority": 600
          "ntuple_sum": 600, "ntuple_sum_sweep": 600, "ntuple_stage": 600, "ntuple_stage_sweep": 900,
          "ntuple_feature": 600, "ntuple_feature_sweep": 900, "solve": 900, "move_features": 1100, "bound": 900,
          "ntuple_budget": 600, "ntuple_budget_sweep": 1100, "exact": 900, "ntuple_exact": 900, "labels": 900,
-         "rank": 1100, "window": 1100}
+         "rank": 1100, "window": 1100, "ntuple_window": 1100}
 SCATTERED_ATOMICS = 0.08e12                                 # 64 lanes of a wave adding into 64 rows (float adds; integer adds unmeasured)
 VALU_CYCLES, SIMDS, CLOCK_HZ = 3.3, 1024, 2.4e9           # the move's instruction mix, 256 CUs x 4, the clock
 
@@ -3268,6 +3268,146 @@ def part_window(sections=("record", "rates", "verdicts", "time", "loose"), budge
     out["not_measured"] = ("other weight rows, the fourteen features and spare_weight other than 0; other pools and seeds; learners and "
                            "table policies as bases; a step's milliseconds include the base's act(), the state reads, under reuse the "
                            "afterstate enumeration, and the environment's step")
+    return out
+
+
+# part window's rates on 4,096 boards (profiles/learner/probe_window.log): base -> (episodes, wins) alone and at 2^8 and 2^12 nodes
+WINDOW_RECORD = {"one_ply": {None: (290486, 121962), 8: (305761, 188687), 12: (319886, 236021)},
+                 "beam_3x8": {None: (309968, 247253), 8: (326378, 282375), 12: (333769, 303791)}}
+
+
+def part_ntuple_window(budgets=(8, 12), boards=4096, rounds=5):
+    """The window proof search ordered by an n-tuple table (include/tpl_learn.h: tpl_ntuple_window_prove; T.ntuple_window_prove,
+    T.ProofPolicy(table=)) beside the classical order, on part window's set-up: the tight pool of the record, 4,096 boards, one seed,
+    reuse on.  The table is part ntuple_exact's "feat+spare, rate 8, tight pool", made by its recipe."""
+    import numpy as np
+    import torch
+    import tetris_piclim as T
+    _plane_fields, _resident_planes = T.solve._plane_fields, T.solve._resident_planes
+    dev = "cuda:0"
+    L_, M_, M_new = 10, 40, 16
+    out = dict(part="ntuple_window", budgets=[f"2^{b}" for b in budgets], boards=boards, rates={}, verdict_1_share_per_move={}, search=[])
+
+    def progress(what):
+        print(json.dumps(what), file=sys.stderr, flush=True)
+
+    n = 1 << 16
+    env = T.BatchedTetris(L_, M_, 64, device=dev, seed=7)
+    rows, pieces = env.carved_configs(n, seed=7)
+    env.terminate()
+    found = T.solve_configs(rows, pieces, L_, M_, width=16, device=dev, validate=False)
+    tight = T.tighten_pool(rows, pieces, found["solved"], found["solution_len"], M_new)
+    out["pool"] = dict(size=int(tight[0].shape[0]), of=n, seed=7, L=L_, M=M_new)
+    classical = np.array(T.CLASSICAL_WEIGHTS)
+
+    env = T.BatchedTetris(L_, M_new, 4096, device=dev, seed=11, auto_reset=True, reward=NTUPLE_LARGE_REWARD, config_pool=tight)
+    learner = T.NTupleLearner(env, seed=11, gamma=1.0, epsilon=0.05, rate=8.0, shape="feat+spare", bound=False)
+    for steps in (10000, 30000):
+        learner.train(steps)
+    one = learner.evaluate(12288, bound=False)
+    table = learner.table.clone()
+    env.terminate()
+    out["table"] = dict(table="feat+spare, rate 8, tight pool", one_ply_win_rate_on_its_pool=round(one["win_rate"], 5),
+                        order="gamma 1, reward (1, 10, -1): the training's")
+    progress(out["table"])
+    order = dict(table=table, gamma=1.0, reward=NTUPLE_LARGE_REWARD)
+
+    def make(depth, width, log2, ordered):
+        env = T.BatchedTetris(L_, M_new, boards, device=dev, seed=11, auto_reset=True, reward=(0.0, 1.0, 0.0), config_pool=tight)
+        env.reset()
+        base = T.HeuristicPolicy(env, classical, depth=depth) if width is None else T.BeamPolicy(env, classical, depth, width)
+        if log2 is None:
+            return env, base
+        return env, T.ProofPolicy(env, base, max_nodes=1 << log2, reuse=True, **(order if ordered else {}))
+
+    def play(env, player, steps):
+        """part window's play: episodes, wins, the episodes that held a verdict 1 and did not end won, the verdicts per move number."""
+        action = torch.empty(boards, dtype=torch.uint8, device=dev)
+        reward = torch.empty(boards, dtype=torch.float32, device=dev)
+        done = torch.empty(boards, dtype=torch.uint8, device=dev)
+        tallies = torch.zeros(4, dtype=torch.int64, device=dev)
+        per_move = torch.zeros(M_new * 4, dtype=torch.int64, device=dev)
+        held = torch.zeros(boards, dtype=torch.bool, device=dev)
+        proof = isinstance(player, T.ProofPolicy)
+        planes = _resident_planes(env)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            if proof:
+                moves = _plane_fields(*planes)[0].to(torch.int64)
+            player.act(out=action)
+            if proof:
+                per_move += torch.bincount(moves * 4 + player.verdict.to(torch.int64), minlength=M_new * 4)[:M_new * 4]
+                held |= player.played
+            env.step_into(action, reward, done)
+            over, won = done.bool(), reward == 1.0
+            tallies += torch.stack([over.sum(), (over & won).sum(), (over & held).sum(), (over & held & ~won).sum()])
+            held &= ~over
+        torch.cuda.synchronize()
+        seconds = time.perf_counter() - t0
+        e, w, with_proof, broken = tallies.tolist()
+        p = w / max(e, 1)
+        got = dict(episodes=int(e), wins=int(w), win_rate=round(p, 5), standard_error=round((p * (1 - p) / max(e, 1)) ** 0.5, 6),
+                   steps=steps, seconds=round(seconds, 2), ms_per_step=round(seconds * 1e3 / steps, 3))
+        if proof:
+            got.update(episodes_that_held_a_verdict_1=with_proof, of_them_not_won=broken, stats=player.stats())
+            got["per_move"] = per_move.view(M_new, 4).tolist()
+        return got
+
+    steps = 16 * (M_new + 1) * (1 << 14) // boards               # the record's episode budget on fewer boards
+    broken = 0
+    for name, depth, width in (("one_ply", 1, None), ("beam_3x8", 3, 8)):
+        got = {}
+        for log2 in (None,) + tuple(budgets):
+            for ordered in ((False,) if log2 is None else (False, True)):
+                env, player = make(depth, width, log2, ordered)
+                key = "base" if log2 is None else f"proof_2^{log2}_{'table' if ordered else 'classical'}"
+                got[key] = play(env, player, steps)
+                env.terminate()
+                if not ordered and log2 in WINDOW_RECORD[name]:    # part window's rows, win for win
+                    got[key]["reproduces_part_window"] = (got[key]["episodes"], got[key]["wins"]) == WINDOW_RECORD[name][log2]
+                    if not got[key]["reproduces_part_window"]:     # another set-up: nothing measured on it is comparable
+                        raise RuntimeError(f"{name} {key}: {got[key]['episodes']} episodes and {got[key]['wins']} wins, part window has "
+                                           f"{WINDOW_RECORD[name][log2]}: the set-up is not the record's, so the probe stops here")
+                if log2 is not None:
+                    broken += got[key]["of_them_not_won"]
+                    shares = [dict(move=m, searched_or_followed=sum(v), verdict_1=round(v[1] / max(sum(v[1:]), 1), 5))
+                              for m, v in enumerate(got[key].pop("per_move"))]
+                    out["verdict_1_share_per_move"][f"{name}_{key}"] = shares      # of the boards searched at that move counter
+                progress({name: {key: got[key]}})
+        out["rates"][name] = got
+    out["episodes_that_held_a_verdict_1_and_did_not_end_won"] = broken
+
+    # nodes a second beside tpl_placement_window_prove on the same boards, mid-game, alternated rounds
+    median = lambda ts: sorted(ts)[len(ts) // 2]
+    env, player = make(1, None, None, False)
+    play(env, player, 40)
+    for log2 in budgets:
+        theirs = T.window_prove(env, max_nodes=1 << log2)
+        mine = T.ntuple_window_prove(env, max_nodes=1 << log2, **order)
+        both = theirs["proved"] & mine["proved"]
+        same = all(torch.equal(theirs[k][both], mine[k][both]) for k in ("solved", "solution_len", "verdict", "bound"))
+        ta, tb = [], []
+        for _ in range(rounds):
+            ta.append(_timed(lambda: T.window_prove(env, max_nodes=1 << log2), 1, warmup=0))
+            tb.append(_timed(lambda: T.ntuple_window_prove(env, max_nodes=1 << log2, **order), 1, warmup=0))
+        na, nb = float(theirs["nodes"].double().sum()), float(mine["nodes"].double().sum())
+        line = dict(max_nodes=f"2^{log2}", boards=boards, classical=dict(nodes=int(na), proved=int(theirs["proved"].sum()),
+                                                                        verdict_1=int((theirs["verdict"] == 1).sum()),
+                                                                        ms=round(median(ta) * 1e3, 3), nodes_per_second=round(na / median(ta), 1)),
+                    table=dict(nodes=int(nb), proved=int(mine["proved"].sum()), verdict_1=int((mine["verdict"] == 1).sum()),
+                               ms=round(median(tb) * 1e3, 3), nodes_per_second=round(nb / median(tb), 1)),
+                    both_proved=int(both.sum()), verdicts_and_lengths_equal_where_both_prove=bool(same),
+                    nodes_per_second_ratio=round((nb / median(tb)) / (na / median(ta)), 4))
+        out["search"].append(line)
+        progress(line)
+    env.terminate()
+    res = subprocess.run(["bash", os.path.join(ROOT, "tools", "kernel_resources.sh"), T._learn_lib.build_library()],
+                         capture_output=True, text=True, cwd=ROOT)
+    out["kernel"] = [" ".join(l.split()) for l in res.stdout.splitlines() if "window" in l]
+    out["not_measured"] = ("2^16 nodes; reuse off; other tables, seeds, pools, gammas and rewards; the window forms as an order; table "
+                           "policies as bases; the loose pool; a step's milliseconds include the base's act(), the state reads, the "
+                           "afterstate enumeration and the environment's step")
     return out
 
 
