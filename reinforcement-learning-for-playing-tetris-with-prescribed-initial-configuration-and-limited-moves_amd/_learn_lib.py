@@ -922,53 +922,48 @@ def placement_solve(rows, pieces, L: int, M: int, weights, width: int, max_width
 EXACT_MAX_NODES = 1 << 24
 
 
-def placement_exact(rows, pieces, L: int, M: int, weights, max_nodes: int, shortest: bool = True, spare_weight: float = 0.0):
-    """The rule of tpl_placement_exact (include/tpl_learn.h) for n configurations: rows uint16 [n, 20] (bit x = column x), pieces
-    [n, M + 1] (masked to three bits), one weight row [12] or [14], max_nodes in [1, 2^24], shortest True or False, one finite
-    spare_weight.  A depth-first search of the game (L, B) in the bounded form -- a child that the move bound proves lost under B is
-    lost --, children ordered by (value descending, placement ascending; -0 and +0 tie), the first won child of a node ending the
-    iteration; B runs over need(root) .. M (shortest) or is M alone; `nodes` counts the expansions of all iterations and the search
-    gives up, proving nothing, when it would pass max_nodes.  Returns (solved uint8 [n], proved uint8 [n], solution_len int32 [n],
-    actions uint8 [n, M] padded with 255, bound int32 [n], nodes uint32 [n]) in the C layout.
-    The configurations are searched in step, one expansion each a round, so that every round moves and counts the children of all of
-    them in one batch per budget."""
+def _exact_arrays(rows, pieces, L: int, M: int, max_nodes, shortest):
+    """What placement_exact and ntuple_exact refuse alike, and their arrays: (L, M, max_nodes, rows uint16 [n, 20], pieces int64
+    [n, M + 1] masked to three bits)."""
     L, M = int(L), int(M)
     if not (1 <= L <= 250 and 1 <= M <= SOLVE_MAX_MOVES):
         raise ValueError(f"L and M must be in [1, 250] and [1, {SOLVE_MAX_MOVES}]")
     if isinstance(max_nodes, bool) or not isinstance(max_nodes, (int, np.integer)) or not 1 <= int(max_nodes) <= EXACT_MAX_NODES:
         raise ValueError(f"max_nodes must be an integer in [1, {EXACT_MAX_NODES}]")
-    max_nodes = int(max_nodes)
     if not isinstance(shortest, (bool, np.bool_)):
         raise ValueError("shortest must be True or False")
     rows = np.asarray(rows)
     rows = (rows.view(np.uint16) if rows.dtype == np.int16 else rows.astype(np.uint16)).reshape(-1, 20)
-    n = rows.shape[0]
     pieces = np.asarray(pieces).astype(np.int64) & 7
-    if n < 1 or pieces.shape != (n, M + 1):
+    if rows.shape[0] < 1 or pieces.shape != (rows.shape[0], M + 1):
         raise ValueError(f"rows must be [n, 20] and pieces [n, {M + 1}] with n >= 1")
-    w = np.asarray(weights, dtype=np.float32).reshape(-1)
-    if w.shape not in ((NUM_FEATURES,), (NUM_MOVE_FEATURES,)):
-        raise ValueError("weights must be one row of 12 or of 14")
-    move = w.shape[0] == NUM_MOVE_FEATURES
-    with np.errstate(over="ignore"):
-        spare_weight = np.float32(spare_weight)
-    if not np.isfinite(spare_weight):
-        raise ValueError("spare_weight must be finite (in float32)")
+    return L, M, int(max_nodes), rows, pieces
+
+
+def _exact_search(rows, pieces, L: int, M: int, max_nodes: int, shortest: bool, children):
+    """The depth-first search of placement_exact and ntuple_exact on checked arguments: the budgets, the cap, the stop at the first won
+    child in the order (value descending, placement ascending; -0 and +0 tie), the descent and the return.  What a node's children are
+    worth is the caller's: children(tops, piece, nxt, b, L, B) takes a batch of children of the game (L, B), one a row -- tops holds
+    the parent's rows, lines, moves and extra (None where no parent has any: a root carries nothing), piece the piece placed, nxt the
+    one behind it in the list, b the placement -- and returns their (value, state, rows, lines, moves, extra), extra being whatever
+    the order keeps along a path, or None.  Returns placement_exact's six arrays.
+    The configurations are searched in step, one expansion each a round, so that every round moves and counts the children of all of
+    them in one batch per budget."""
+    n = rows.shape[0]
     bound = move_bound(rows, L, M, 0, 0, STATE_RUNNING)["need"].astype(np.int32)
     placements = [np.flatnonzero(canonical_actions(p, np.arange(NUM_ACTIONS)) == np.arange(NUM_ACTIONS)) for p in range(8)]
     solved, proved, length = np.zeros(n, np.uint8), np.ones(n, np.uint8), np.zeros(n, np.int32)
     actions, nodes = np.full((n, M), NO_SECOND, np.uint8), np.zeros(n, np.uint32)
 
     def root(s):
-        return dict(rows=rows[s], lines=0, moves=0, sums=np.zeros(2, np.int64), kids=None, at=0)
+        return dict(rows=rows[s], lines=0, moves=0, extra=None, kids=None, at=0)
 
     # a stack per configuration still searched, its last frame the node to expand next; a frame's kids are its running children in
-    # the order of the descent -- (placement, rows, lines, moves, sums) each --, `at` the next of them
+    # the order of the descent -- (placement, rows, lines, moves, extra) each --, `at` the next of them
     budget = {s: int(bound[s]) if shortest else M for s in range(n) if bound[s] <= M}
     stacks = {s: [root(s)] for s in budget}
     while stacks:
-        capped = [s for s in stacks if nodes[s] == max_nodes]
-        for s in capped:                                        # the cap: nothing is proved, nothing is reported
+        for s in [s for s in stacks if nodes[s] == max_nodes]:  # the cap: nothing is proved, nothing is reported
             proved[s] = 0
             del stacks[s]
         if not stacks:
@@ -979,27 +974,21 @@ def placement_exact(rows, pieces, L: int, M: int, weights, max_nodes: int, short
         for B in sorted({budget[s] for s in todo}):             # the game (L, B): one batch per budget
             group = [s for s in todo if budget[s] == B]
             tops = [stacks[s][-1] for s in group]
-            place = [placements[pieces[s, len(stacks[s]) - 1]] for s in group]
+            depth = [len(stacks[s]) - 1 for s in group]
+            place = [placements[pieces[s, d]] for s, d in zip(group, depth)]
             sizes = [b.size for b in place]
-            b = np.concatenate(place)
-            rep = lambda key: np.repeat(np.array([t[key] for t in tops]), sizes, axis=0)
-            piece = np.repeat([pieces[s, len(stacks[s]) - 1] for s in group], sizes)
-            r2, _, l2, m2, s2, _, _, land, erod = host_moves_traced(rep("rows"), piece, b // 10, b % 10, L, B, rep("lines"), rep("moves"))
-            sums = rep("sums") + np.stack([land, erod], axis=1)
-            mb = move_bound(r2, L, B, l2, m2, s2)
-            s2 = np.where(mb["dead"], STATE_LOST_LIMIT, s2)
-            spare = np.where(mb["dead"], 0, mb["spare"])
-            psi = np.concatenate([np.stack([l2, s2 == STATE_WON, s2 >= STATE_LOST_LIMIT], axis=1).astype(np.int64),
-                                  board_features(r2)] + ([sums] if move else []), axis=1)
-            value = placement_score(psi, w)
-            value = value + spare_weight * spare.astype(np.float32)
+            rep = lambda per_top: np.repeat(np.array(per_top), sizes, axis=0)
+            carried = next((t["extra"] for t in tops if t["extra"] is not None), None)
+            batch = dict(rows=rep([t["rows"] for t in tops]), lines=rep([t["lines"] for t in tops]), moves=rep([t["moves"] for t in tops]),
+                         extra=None if carried is None else rep([np.zeros_like(carried) if t["extra"] is None else t["extra"] for t in tops]))
+            out = children(batch, rep([pieces[s, d] for s, d in zip(group, depth)]), rep([pieces[s, d + 1] for s, d in zip(group, depth)]),
+                           np.concatenate(place), L, B)
             lo = 0
-            for s, size in zip(group, sizes):
-                found[s] = (b[lo:lo + size], value[lo:lo + size], s2[lo:lo + size], r2[lo:lo + size], l2[lo:lo + size],
-                            m2[lo:lo + size], sums[lo:lo + size])
+            for s, b, size in zip(group, place, sizes):
+                found[s] = (b,) + tuple(None if x is None else x[lo:lo + size] for x in out)
                 lo += size
         for s in todo:
-            b, value, state, c_rows, c_lines, c_moves, c_sums = found[s]
+            b, value, state, c_rows, c_lines, c_moves, c_extra = found[s]
             stack = stacks[s]
             order = np.argsort(-(value + np.float32(0.0)), kind="stable")
             won = order[state[order] == STATE_WON]
@@ -1010,20 +999,52 @@ def placement_exact(rows, pieces, L: int, M: int, weights, max_nodes: int, short
                 del stacks[s]
                 continue
             run = order[state[order] == STATE_RUNNING]
-            stack[-1]["kids"] = [(int(b[k]), c_rows[k], int(c_lines[k]), int(c_moves[k]), c_sums[k]) for k in run]
+            stack[-1]["kids"] = [(int(b[k]), c_rows[k], int(c_lines[k]), int(c_moves[k]), None if c_extra is None else c_extra[k]) for k in run]
             while stack and stack[-1]["at"] == len(stack[-1]["kids"]):
                 stack.pop()                                     # used up: back to the parent
             if stack:
                 top = stack[-1]
-                _, k_rows, k_lines, k_moves, k_sums = top["kids"][top["at"]]
+                _, k_rows, k_lines, k_moves, k_extra = top["kids"][top["at"]]
                 top["at"] += 1
-                stack.append(dict(rows=k_rows, lines=k_lines, moves=k_moves, sums=k_sums, kids=None, at=0))
+                stack.append(dict(rows=k_rows, lines=k_lines, moves=k_moves, extra=k_extra, kids=None, at=0))
             elif shortest and budget[s] < M:                    # searched out at this budget: the next one
                 budget[s] += 1
                 stack.append(root(s))
             else:                                               # searched out: no sequence of placements wins within M moves
                 del stacks[s]
     return solved, proved, length, actions, bound, nodes
+
+
+def placement_exact(rows, pieces, L: int, M: int, weights, max_nodes: int, shortest: bool = True, spare_weight: float = 0.0):
+    """The rule of tpl_placement_exact (include/tpl_learn.h) for n configurations: rows uint16 [n, 20] (bit x = column x), pieces
+    [n, M + 1] (masked to three bits), one weight row [12] or [14], max_nodes in [1, 2^24], shortest True or False, one finite
+    spare_weight.  A depth-first search of the game (L, B) in the bounded form -- a child that the move bound proves lost under B is
+    lost --, children ordered by (value descending, placement ascending; -0 and +0 tie), the first won child of a node ending the
+    iteration; B runs over need(root) .. M (shortest) or is M alone; `nodes` counts the expansions of all iterations and the search
+    gives up, proving nothing, when it would pass max_nodes.  Returns (solved uint8 [n], proved uint8 [n], solution_len int32 [n],
+    actions uint8 [n, M] padded with 255, bound int32 [n], nodes uint32 [n]) in the C layout (_exact_search)."""
+    L, M, max_nodes, rows, pieces = _exact_arrays(rows, pieces, L, M, max_nodes, shortest)
+    w = np.asarray(weights, dtype=np.float32).reshape(-1)
+    if w.shape not in ((NUM_FEATURES,), (NUM_MOVE_FEATURES,)):
+        raise ValueError("weights must be one row of 12 or of 14")
+    move = w.shape[0] == NUM_MOVE_FEATURES
+    with np.errstate(over="ignore"):
+        spare_weight = np.float32(spare_weight)
+    if not np.isfinite(spare_weight):
+        raise ValueError("spare_weight must be finite (in float32)")
+
+    def children(tops, piece, nxt, b, L, B):                    # the linear order; extra: the path's landing and eroded sums
+        r2, _, l2, m2, s2, _, _, land, erod = host_moves_traced(tops["rows"], piece, b // 10, b % 10, L, B, tops["lines"], tops["moves"])
+        sums = np.stack([land, erod], axis=1) + (0 if tops["extra"] is None else tops["extra"])
+        mb = move_bound(r2, L, B, l2, m2, s2)
+        s2 = np.where(mb["dead"], STATE_LOST_LIMIT, s2)
+        spare = np.where(mb["dead"], 0, mb["spare"])
+        psi = np.concatenate([np.stack([l2, s2 == STATE_WON, s2 >= STATE_LOST_LIMIT], axis=1).astype(np.int64),
+                              board_features(r2)] + ([sums] if move else []), axis=1)
+        value = placement_score(psi, w)
+        return value + spare_weight * spare.astype(np.float32), s2, r2, l2, m2, sums
+
+    return _exact_search(rows, pieces, L, M, max_nodes, bool(shortest), children)
 
 
 # ------------------------------------------------------------------------------------------------ the exact search from a node
@@ -1520,23 +1541,10 @@ def ntuple_exact(rows, pieces, L: int, M: int, table, max_nodes: int, shortest: 
                  reward=(1.0, 0.0, 0.0)):
     """The rule of tpl_ntuple_exact (include/tpl_learn.h) for n configurations: placement_exact's arguments with a table (int32, one of
     NTUPLE_EXACT_FORMS by its entry count) for the weights and a finite gamma and reward = (r_line, r_win, r_lose) for spare_weight.  The
-    search is placement_exact's; the child made at depth d is worth reward, or reward + gamma * V where it runs, V being ntuple_value of
-    its board with pieces[d + 1] as the falling piece in the game (L, B) of the iteration -- float32 operations, each rounded once.
-    Returns placement_exact's six arrays.  The configurations are searched in step, as there."""
-    L, M = int(L), int(M)
-    if not (1 <= L <= 250 and 1 <= M <= SOLVE_MAX_MOVES):
-        raise ValueError(f"L and M must be in [1, 250] and [1, {SOLVE_MAX_MOVES}]")
-    if isinstance(max_nodes, bool) or not isinstance(max_nodes, (int, np.integer)) or not 1 <= int(max_nodes) <= EXACT_MAX_NODES:
-        raise ValueError(f"max_nodes must be an integer in [1, {EXACT_MAX_NODES}]")
-    max_nodes = int(max_nodes)
-    if not isinstance(shortest, (bool, np.bool_)):
-        raise ValueError("shortest must be True or False")
-    rows = np.asarray(rows)
-    rows = (rows.view(np.uint16) if rows.dtype == np.int16 else rows.astype(np.uint16)).reshape(-1, 20)
-    n = rows.shape[0]
-    pieces = np.asarray(pieces).astype(np.int64) & 7
-    if n < 1 or pieces.shape != (n, M + 1):
-        raise ValueError(f"rows must be [n, 20] and pieces [n, {M + 1}] with n >= 1")
+    search is placement_exact's (_exact_search); the child made at depth d is worth reward, or reward + gamma * V where it runs, V being
+    ntuple_value of its board with pieces[d + 1] as the falling piece in the game (L, B) of the iteration -- float32 operations, each
+    rounded once.  Returns placement_exact's six arrays."""
+    L, M, max_nodes, rows, pieces = _exact_arrays(rows, pieces, L, M, max_nodes, shortest)
     table = _ntuple_exact_table(table)
     try:
         with np.errstate(over="ignore"):
@@ -1546,74 +1554,19 @@ def ntuple_exact(rows, pieces, L: int, M: int, table, max_nodes: int, shortest: 
         raise ValueError("gamma must be a number and reward three numbers (r_line, r_win, r_lose)") from None
     if not all(np.isfinite(v) for v in (g, r_line, r_win, r_lose)):
         raise ValueError("gamma and reward must be finite (in float32)")
-    bound = move_bound(rows, L, M, 0, 0, STATE_RUNNING)["need"].astype(np.int32)
-    placements = [np.flatnonzero(canonical_actions(p, np.arange(NUM_ACTIONS)) == np.arange(NUM_ACTIONS)) for p in range(8)]
-    solved, proved, length = np.zeros(n, np.uint8), np.ones(n, np.uint8), np.zeros(n, np.int32)
-    actions, nodes = np.full((n, M), NO_SECOND, np.uint8), np.zeros(n, np.uint32)
 
-    def root(s):
-        return dict(rows=rows[s], lines=0, moves=0, kids=None, at=0)
+    def children(tops, piece, nxt, b, L, B):                    # the table's order; nothing is kept along a path
+        r2, cleared, l2, m2, s2 = host_moves(tops["rows"], piece, b // 10, b % 10, L, B, tops["lines"], tops["moves"])
+        s2 = np.where(move_bound(r2, L, B, l2, m2, s2)["dead"], STATE_LOST_LIMIT, s2)
+        with np.errstate(over="ignore", invalid="ignore"):
+            r = r_line * cleared.astype(np.float32)
+            r = np.where(s2 == STATE_WON, r + r_win, r)
+            r = np.where(s2 >= STATE_LOST_LIMIT, r + r_lose, r).astype(np.float32)
+            v = ntuple_value(table, r2, nxt, L, B, l2, m2, s2)
+            value = np.where(s2 == STATE_RUNNING, r + g * v, r).astype(np.float32)
+        return value, s2, r2, l2, m2, None
 
-    # placement_exact's stacks: a frame's kids are its running children in the order of the descent, `at` the next of them
-    budget = {s: int(bound[s]) if shortest else M for s in range(n) if bound[s] <= M}
-    stacks = {s: [root(s)] for s in budget}
-    while stacks:
-        for s in [s for s in stacks if nodes[s] == max_nodes]:  # the cap: nothing is proved, nothing is reported
-            proved[s] = 0
-            del stacks[s]
-        if not stacks:
-            break
-        todo = sorted(stacks)
-        nodes[todo] += 1
-        found = {}
-        for B in sorted({budget[s] for s in todo}):             # the game (L, B): one batch per budget
-            group = [s for s in todo if budget[s] == B]
-            tops = [stacks[s][-1] for s in group]
-            depth = [len(stacks[s]) - 1 for s in group]
-            place = [placements[pieces[s, d]] for s, d in zip(group, depth)]
-            sizes = [b.size for b in place]
-            b = np.concatenate(place)
-            rep = lambda key: np.repeat(np.array([t[key] for t in tops]), sizes, axis=0)
-            piece = np.repeat([pieces[s, d] for s, d in zip(group, depth)], sizes)
-            nxt = np.repeat([pieces[s, d + 1] for s, d in zip(group, depth)], sizes)
-            r2, cleared, l2, m2, s2 = host_moves(rep("rows"), piece, b // 10, b % 10, L, B, rep("lines"), rep("moves"))
-            s2 = np.where(move_bound(r2, L, B, l2, m2, s2)["dead"], STATE_LOST_LIMIT, s2)
-            with np.errstate(over="ignore", invalid="ignore"):
-                r = r_line * cleared.astype(np.float32)
-                r = np.where(s2 == STATE_WON, r + r_win, r)
-                r = np.where(s2 >= STATE_LOST_LIMIT, r + r_lose, r).astype(np.float32)
-                v = ntuple_value(table, r2, nxt, L, B, l2, m2, s2)
-                value = np.where(s2 == STATE_RUNNING, r + g * v, r).astype(np.float32)
-            lo = 0
-            for s, size in zip(group, sizes):
-                found[s] = (b[lo:lo + size], value[lo:lo + size], s2[lo:lo + size], r2[lo:lo + size], l2[lo:lo + size], m2[lo:lo + size])
-                lo += size
-        for s in todo:
-            b, value, state, c_rows, c_lines, c_moves = found[s]
-            stack = stacks[s]
-            order = np.argsort(-(value + np.float32(0.0)), kind="stable")
-            won = order[state[order] == STATE_WON]
-            if won.size:                                        # a win at this depth + 1: the path to here, then the won child
-                path = [f["kids"][f["at"] - 1][0] for f in stack[:-1]] + [int(b[won[0]])]
-                solved[s], length[s] = 1, len(path)
-                actions[s, :len(path)] = path
-                del stacks[s]
-                continue
-            run = order[state[order] == STATE_RUNNING]
-            stack[-1]["kids"] = [(int(b[k]), c_rows[k], int(c_lines[k]), int(c_moves[k])) for k in run]
-            while stack and stack[-1]["at"] == len(stack[-1]["kids"]):
-                stack.pop()                                     # used up: back to the parent
-            if stack:
-                top = stack[-1]
-                _, k_rows, k_lines, k_moves = top["kids"][top["at"]]
-                top["at"] += 1
-                stack.append(dict(rows=k_rows, lines=k_lines, moves=k_moves, kids=None, at=0))
-            elif shortest and budget[s] < M:                    # searched out at this budget: the next one
-                budget[s] += 1
-                stack.append(root(s))
-            else:                                               # searched out: no sequence of placements wins within M moves
-                del stacks[s]
-    return solved, proved, length, actions, bound, nodes
+    return _exact_search(rows, pieces, L, M, max_nodes, bool(shortest), children)
 
 
 # The rule of tpl_ntuple_window_prove (include/tpl_learn.h) on the host: placement_window_prove's framing (_window_frame, shared) with

@@ -10,30 +10,24 @@
 //
 // A child made at depth d carries list entry d + 1 as its falling piece, the piece it will play.  A child that runs has
 // d + 1 < B <= H <= known, so that entry is a true piece of the episode: no value is read under a piece the agent does not know.
-// The frame reads the entry before it knows the child's state, so entry H -- index 12 where H = 12 -- is a defined 0 in LDS.
+// The order reads the entry before it knows the child's state, so entry H -- index 12 where H = 12 -- is a defined 0 in LDS.
 //
-// Mapping: exact_window.hip's.  ONE BOARD PER WAVEFRONT, one wavefront a workgroup, no barrier; lanes 0 .. 33 a child each, 64-bit
-// keys ranked across the wave; STATIC LDS: twelve stack records of 80 bytes (ntuple_exact.hip's, without a carry), the shape table and
-// sixteen bytes of pieces.  The table stays in global memory, as in ntuple_exact.hip and for its reason.  The body is a template over
-// the geometry of tpl_ntuple.h and each __global__ kernel names its geometry.
-//
-// The search loop is ntuple_exact.hip's, duplicated once more: that unit, exact.hip, exact_nodes.hip and exact_window.hip stay as they
-// are, with their instructions (profiles/learner/ntuple_window_isa.log).
+// The search, its mapping and its stack record are tpl_exact.h's.  ONE BOARD PER WAVEFRONT; STATIC LDS: twelve stack records of 80 bytes,
+// the shape table and sixteen bytes of pieces.  The table stays in global memory, as in ntuple_exact.hip and for its reason.  The order
+// is a template over the geometry of tpl_ntuple.h and each __global__ kernel names its geometry.
 #ifndef TPL_PLACEMENT_BOUND_UNIT
 #define TPL_PLACEMENT_BOUND_UNIT
 #endif
 #include "tpl_beam.h"
+#include "tpl_exact.h"
 #include "tpl_ntuple.h"
 
 namespace tpl_learn {
 namespace {
 
-constexpr int kWindowWave = 64;
+constexpr int kWindowWave = kExactWave;
 constexpr int kWindowDepth = tpl::kWindowEntries;             // 12: the longest horizon, and the plan's width
 constexpr int kWindowList = 16;                               // the list in LDS: entries 0 .. H - 1 of the window, 0 behind them
-constexpr int kWindowMaxNodes = TPL_EXACT_MAX_NODES;
-static_assert(kUnitBound, "the exact search is a unit of the bounded form");
-static_assert(kMaxPlacements <= kWindowWave, "a lane per child");
 static_assert(kWindowDepth == TPL_WINDOW_PLAN, "the plan is as wide as the window");
 static_assert(kWindowDepth < kWindowList, "entry 12 of the list exists");
 
@@ -56,38 +50,6 @@ struct NTupleWindowArgs {
     uint8_t* verdict;            // [n]
 };
 
-// one depth of the stack (ntuple_exact.hip's record)
-struct alignas(16) Frame {
-    uint4 a, b;                  // the node's board; its window is not part of the rule
-    uint32_t count;              // its running children
-    uint32_t cursor;             // how many of them have been descended into
-    uint8_t kids[36];            // their placements b = 10 r + l in the order of the descent, kMaxPlacements at most
-};
-static_assert(sizeof(Frame) == 80, "a record is 80 bytes");
-
-// LDS written by one lane, read by another of the same wave: the accesses of a wave reach LDS in order, so this only keeps the
-// compiler from moving them across and waits for the write
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ uint32_t uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-
-// The child of `node` by placement (r, l) of piece `cur` in the game (L, B): the board the move leaves, dead turned lost, with `nxt`,
-// the piece the child will play, as its falling piece.  Returns the rows the move cleared (ntuple_exact.hip's).
-__device__ __forceinline__ uint32_t make_child(const Frame& node, uint32_t cur, uint32_t nxt, uint32_t r, uint32_t l,
-                                               const tpl::ShapeWord* shape, uint32_t L, uint32_t B, tpl::Board& s) {
-    tpl::unpack_board(node.a, node.b, s);
-    s.window = cur;
-    s.window_hi = 0u;
-    const uint32_t n_clear = placed_move<kFeatures>(s, shape, r, l, L, B);
-    bounded_move(s, L, B);
-    s.window = nxt;
-    return n_clear;
-}
-
 // what the one-ply policy scores the move with: reward, or reward + gamma V where the child runs; every product and sum rounded once
 template <typename S>
 __device__ __forceinline__ float child_value(const tpl::Board& s, uint32_t n_clear, uint32_t L, uint32_t B, const NTupleWindowArgs& p) {
@@ -100,117 +62,28 @@ __device__ __forceinline__ float child_value(const tpl::Board& s, uint32_t n_cle
     return on ? reward + later : reward;
 }
 
-__device__ __forceinline__ void store_frame(Frame& f, const tpl::Board& s) {
-    uint4 A, B;
-    tpl::pack_board(s, A, B);
-    f.a = A;
-    f.b = B;
-}
-
-struct Found {
-    uint32_t nodes, length, last;                              // expansions; the winning length, 0 if none, and its last move
-    bool capped;
-};
-
-// ntuple_exact.hip's search, shortest, of the game (L, H), H <= 12, from `root` -- the same in every lane, 0 lines, 0 moves -- whose
-// piece at depth d is s_pieces[d]; `need` is need(root), and need > H is decided without a node.  The caller has filled s_shape and
-// s_pieces, entry H of which is 0.  On return the path of a win is in the stack: the child in hand at every depth, then `last`.
+// The table's order, as ntuple_exact.hip has it: the board the move leaves, dead turned lost, with the piece the child will play as its
+// falling piece, worth what the one-ply policy scores the move with.  The table, the rewards and gamma are kernel arguments: SGPRs.
 template <typename S>
-__device__ __forceinline__ Found search(Frame* stack, const uint8_t* s_pieces, const tpl::ShapeWord* s_shape, const tpl::Board& root,
-                                        uint32_t need, uint32_t L, uint32_t H, const NTupleWindowArgs& p, uint32_t lane) {
-    const uint32_t max_nodes = p.max_nodes;
-    uint32_t nodes = 0u, length = 0u, last = kNoMove;
-    bool capped = false;
-#pragma unroll 1
-    for (uint32_t B = need; B <= H && length == 0u && !capped; ++B) {
-        wave_sync();                                           // the last iteration's reads of record 0 (and, the first time, the tables)
-        if (lane == 0) store_frame(stack[0], root);
-        wave_sync();
-        uint32_t d = 0u;
-#pragma unroll 1
-        for (;;) {
-            // expand the node at depth d
-            if (nodes == max_nodes) { capped = true; break; }
-            ++nodes;
-            const uint32_t cur = uniform(s_pieces[d]), nxt = uniform(s_pieces[d + 1u]);      // d + 1 <= H <= 12: the list has 16 entries
-            const uint32_t stride = placement_count(cur);
-            const bool mine = lane < stride;
-            const uint32_t k = mine ? lane : 0u;
-            uint32_t r, l;
-            const uint32_t b = nth_placement(cur, k, r, l);
-            tpl::Board s;
-            const uint32_t n_clear = make_child(stack[d], cur, nxt, r, l, s_shape, L, B, s);
-            const float value = child_value<S>(s, n_clear, L, B, p);
-            const uint32_t key_hi = ordered_bits(value), key_lo = kSlotTop - k;
-            const bool won = mine && s.state == tpl::ST_WON, running = mine && s.state == tpl::ST_RUNNING;
-
-            // the stop: the won child that comes first in the order
-            if (__ballot(won) != 0ull) {
-                const unsigned long long top = wave_max(won ? ((unsigned long long)key_hi << 32) | key_lo : 0ull);
-                uint32_t r2, l2;
-                last = nth_placement(cur, kSlotTop - uniform((uint32_t)top), r2, l2);
-                length = d + 1u;
-                break;
-            }
-
-            // the order of the running children: a child's rank is the number of running children with a larger key
-            const uint32_t run_hi = running ? key_hi : 0u, run_lo = running ? key_lo : 0u;
-            const unsigned long long run_key = ((unsigned long long)run_hi << 32) | run_lo;
-            uint32_t rank = 0u;
-#pragma unroll
-            for (int j = 0; j < kMaxPlacements; ++j) {
-                const unsigned long long other = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)run_hi, j) << 32) |
-                                                 (uint32_t)__builtin_amdgcn_readlane((int)run_lo, j);
-                rank += other > run_key ? 1u : 0u;
-            }
-            const uint32_t count = (uint32_t)__builtin_popcountll(__ballot(running));
-            if (running) {
-                stack[d].kids[rank] = (uint8_t)b;
-                if (rank == 0u && d + 1u < H) store_frame(stack[d + 1u], s);      // descended into at once (d + 1 < B <= H <= 12)
-            }
-            if (lane == 0) {
-                stack[d].count = count;
-                stack[d].cursor = count != 0u ? 1u : 0u;
-            }
-            wave_sync();
-            if (count != 0u) { ++d; continue; }
-
-            // no running child: back to the nearest node that has one left, and into it
-            bool more = false;
-#pragma unroll 1
-            while (d > 0u) {
-                --d;
-                const uint32_t at = uniform(stack[d].cursor);
-                if (at < uniform(stack[d].count)) {
-                    const uint32_t b2 = uniform(stack[d].kids[at]);
-                    tpl::Board s2;
-                    make_child(stack[d], uniform(s_pieces[d]), uniform(s_pieces[d + 1u]), b2 / 10u, b2 % 10u, s_shape, L, B, s2);
-                    wave_sync();
-                    if (lane == 0 && d + 1u < H) {
-                        stack[d].cursor = at + 1u;
-                        store_frame(stack[d + 1u], s2);
-                    }
-                    wave_sync();
-                    ++d;
-                    more = true;
-                    break;
-                }
-            }
-            if (!more) break;                                  // the root's children are used up: no win at this budget
-        }
+struct TableOrder {
+    using Carry = NoCarry;       // a table's value reads the board alone
+    const NTupleWindowArgs& p;
+    __device__ __forceinline__ float child(const Frame<Carry>& node, uint32_t cur, const uint8_t* later, uint32_t r, uint32_t l,
+                                           const tpl::ShapeWord* shape, uint32_t L, uint32_t B, tpl::Board& s, Carry&) const {
+        tpl::unpack_board(node.a, node.b, s);
+        s.window = cur;
+        s.window_hi = 0u;
+        const uint32_t n_clear = placed_move<kFeatures>(s, shape, r, l, L, B);
+        bounded_move(s, L, B);
+        s.window = uniform(later[0]);                          // depth d + 1 <= H <= 12: the list has 16 entries
+        return child_value<S>(s, n_clear, L, B, p);
     }
-    wave_sync();
-    Found out;
-    out.nodes = nodes;
-    out.length = capped ? 0u : length;
-    out.last = last;
-    out.capped = capped;
-    return out;
-}
+};
+using Stack = Frame<NoCarry>;
 
 template <typename S>
 __device__ __forceinline__ void ntuple_window(const NTupleWindowArgs& p) {
-    __shared__ Frame stack[kWindowDepth];
+    __shared__ Stack stack[kWindowDepth];
     __shared__ tpl::ShapeWord s_shape[32];
     __shared__ uint8_t s_pieces[kWindowList];
     const uint32_t lane = threadIdx.x, i = blockIdx.x;         // the grid is n blocks of one wave
@@ -229,9 +102,8 @@ __device__ __forceinline__ void ntuple_window(const NTupleWindowArgs& p) {
     tpl::Board root;                                           // the board as the root of its shifted game: the same in every lane
 #pragma unroll
     for (int x = 0; x < tpl::kCols; ++x) root.c[x] = uniform(at.c[x]);
-    root.window = 0u; root.window_hi = 0u;
-    root.state = tpl::ST_RUNNING; root.lines = 0u; root.moves = 0u; root.slot = 0u;
-    const uint32_t need = live ? (move_bound_cells(root.c, L) + 3u) >> 2 : 0u;      // need(board): no win is shorter
+    fresh_root(root);
+    const uint32_t need = live ? need_of(root, L) : 0u;        // need(board): no win is shorter
 
     const bool last_known = H == rem;                          // the window reaches the end of the game
     if (lane == 0) {                                           // what the search does not decide, before it
@@ -246,7 +118,8 @@ __device__ __forceinline__ void ntuple_window(const NTupleWindowArgs& p) {
         // list entry `lane`: the window's, masked as move_board masks it, below the horizon and 0 from it on
         const unsigned long long window = ((unsigned long long)at.window_hi << 32) | at.window;
         if (lane < (uint32_t)kWindowList) s_pieces[lane] = lane < H ? (uint8_t)((uint32_t)(window >> (3u * lane)) & 7u) : (uint8_t)0;
-        f = search<S>(stack, s_pieces, s_shape, root, need, L, H, p, lane);
+        const TableOrder<S> order{p};
+        f = search(order, stack, s_pieces, s_shape, root, need, L, H, p.max_nodes, 1u, lane);      // the game (L, H), shortest
     }
     const bool solved = f.length != 0u, proved = !skipped && !f.capped;
     if (lane == 0) {
@@ -259,18 +132,10 @@ __device__ __forceinline__ void ntuple_window(const NTupleWindowArgs& p) {
                        : proved && last_known ? (uint8_t)TPL_WINDOW_LOSS
                                               : (uint8_t)TPL_WINDOW_OPEN;
     }
-    // the plan: the child in hand at every depth of the path, then the won one; 255 behind the end
-    if (lane < (uint32_t)kWindowDepth) {
-        uint32_t a = kNoMove;
-        if (lane + 1u < f.length) a = stack[lane].kids[stack[lane].cursor - 1u];
-        else if (lane + 1u == f.length) a = f.last;
-        p.plan[(size_t)i * kWindowDepth + lane] = (uint8_t)a;
-    }
+    write_path(stack, f, p.plan + (size_t)i * kWindowDepth, (uint32_t)kWindowDepth, lane);      // the plan
 }
 
-// One wave a workgroup, each kernel bound to eight waves a SIMD as ntuple_exact.hip's and exact_window.hip's are and for their reason: a
-// wave's search is one dependent chain with a trip to L2 in every link, and what hides it is other waves (tools/kernel_resources.sh;
-// profiles/learner/ntuple_window_isa.log).
+// one wave a workgroup, each kernel bound to eight waves a SIMD (tpl_exact.h says why; here a trip to L2 is part of every link)
 __global__ __launch_bounds__(kWindowWave, 8) void ntuple_window_kernel(const NTupleWindowArgs p) { ntuple_window<Shape2x4>(p); }
 __global__ __launch_bounds__(kWindowWave, 8) void ntuple_window3_kernel(const NTupleWindowArgs p) { ntuple_window<Shape3x3>(p); }
 __global__ __launch_bounds__(kWindowWave, 8) void ntuple_window_feature_kernel(const NTupleWindowArgs p) { ntuple_window<FeatureTable>(p); }
@@ -299,17 +164,11 @@ extern "C" int tpl_ntuple_window_prove(const void* plane_a, const void* plane_b,
     if (!(r_line - r_line == 0.0f) || !(r_win - r_win == 0.0f) || !(r_lose - r_lose == 0.0f))
         return fail_msg(TPL_ERR_ARG, "%s: r_line, r_win and r_lose must be finite", name);
     if (!(gamma - gamma == 0.0f)) return fail_msg(TPL_ERR_ARG, "%s: gamma must be finite", name);
-    if (n < 1) return fail_msg(TPL_ERR_ARG, "%s: n must be positive", name);
-    if (n >= ((int64_t)1 << 31)) return fail_msg(TPL_ERR_ARG, "%s: n too large (a workgroup per board: n must stay below 2^31)", name);
-    if (L < 1 || L > 250 || M < 1 || M > 254) return fail_msg(TPL_ERR_ARG, "%s: L and M must be in [1, 250] and [1, 254]", name);
-    if (max_nodes < 1 || max_nodes > kWindowMaxNodes)
-        return fail_msg(TPL_ERR_ARG, "%s: max_nodes must be in [1, %d]", name, kWindowMaxNodes);
+    if (const int rc = check_search(name, n, 1, "a workgroup per board: n must stay below 2^31", 1, L, M, max_nodes)) return rc;
     if (((uintptr_t)plane_a & 15u) || ((uintptr_t)plane_b & 15u))
         return fail_msg(TPL_ERR_ARG, "%s: planes must be 16-byte aligned", name);
     if ((uintptr_t)table & 3u) return fail_msg(TPL_ERR_ARG, "%s: table must be 4-byte aligned", name);
-    if ((uintptr_t)solution_len & 3u) return fail_msg(TPL_ERR_ARG, "%s: solution_len must be 4-byte aligned", name);
-    if ((uintptr_t)bound & 3u) return fail_msg(TPL_ERR_ARG, "%s: bound must be 4-byte aligned", name);
-    if ((uintptr_t)nodes & 3u) return fail_msg(TPL_ERR_ARG, "%s: nodes must be 4-byte aligned", name);
+    if (const int rc = check_counts(name, solution_len, bound, nodes)) return rc;
     NTupleWindowArgs p{};
     p.a = (const uint4*)plane_a; p.b = (const uint4*)plane_b; p.n = (uint32_t)n;
     p.L = (uint32_t)L; p.M = (uint32_t)M; p.table = table;

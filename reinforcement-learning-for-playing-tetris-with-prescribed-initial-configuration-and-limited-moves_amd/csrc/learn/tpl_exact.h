@@ -1,0 +1,256 @@
+// tpl_exact.h -- the exact depth-first search the five proof units share (exact.hip, exact_nodes.hip, exact_window.hip,
+// ntuple_exact.hip, ntuple_window.hip; include/tpl_learn.h states their rules): the stack record, the search, the write-out of a
+// win's path and the argument checks the entries have in common.  What a unit keeps is its frame -- where the root, the piece list
+// and the game (L, M) come from, and what the result means -- and its ORDER: what a node's child is worth.
+//
+// The search is of the game (L, M) from a root with 0 lines and 0 moves, in the bounded form (tpl_placement.h: kUnitBound): the move
+// bound's prune is what makes it finite in practice and its proof is the bound's.  Within the prune it visits every running board,
+// or it stops at a node budget and says so.  With `shortest` it deepens the budget B from need(root) to M, so the first win it meets
+// is a shortest one.
+//
+// Mapping: ONE SEARCH PER WAVEFRONT, one wavefront a workgroup, so the data-dependent loop holds no barrier at all; what one lane
+// writes to LDS for the others is ordered by wave_sync(), which emits no instruction but the wait for the write.
+//   the node    being expanded is read from its stack record by every lane; lane k < 34 makes child k, the k-th distinct placement of
+//               the ply's piece in ascending b, and its 64-bit key (ordered_bits(value) << 32 | kSlotTop - k), so a larger key comes
+//               first in the rule's order.  The other lanes idle: the search is divergent by nature.
+//   the stop    a ballot over the won children; if any is set the largest won key names the child the solution ends with.
+//   the order   the running children are ranked by their keys: 34 lane reads of a key, a compare and an add each.  A running
+//               child writes its placement to place `rank` of the record's list; the one of rank 0 also writes the next record, since
+//               it is descended into at once.
+//   the stack   LDS, one 80-byte record a depth: the node's packed board (two uint4), what the order carries along the path, the
+//               number of its running children, a cursor, and the list.  A running child at depth d + 1 has made d + 1 < B <= M
+//               moves, so M records hold every path: 3,200 bytes at M = 40, 20,320 at M = 254, 960 for the twelve of a window.
+//   the return  a later child is made again from its parent's record and the list's placement when the search comes back to it, as
+//               the beam makes a kept candidate again in its phase C.
+// Nothing but the outputs goes to memory.  A wave's search is one long dependent chain -- a record read from LDS, a move, the child's
+// value, a rank, a record written -- so what hides its latency is other waves: every kernel is bound to eight waves a SIMD, 64 VGPRs
+// without scratch, since everything the 34 children share sits in SGPRs (tools/kernel_resources.sh;
+// profiles/learner/exact_refactor_isa.log).
+//
+// An ORDER is a small struct of the unit's, the same in every lane:
+//   Carry        what a record keeps of the path for the order: the linear weights' carry word, or NoCarry (a table's value reads the
+//                board alone), which takes no room in the record;
+//   child(...)   the child of a record by placement (r, l) of piece `cur` in the game (L, B) -- the board the move leaves, dead turned
+//                lost (placed_move, bounded_move) -- its Carry, and its value.  `later` points at the list behind `cur`: its first
+//                entry is the piece the child will play.  The expansion and the return both come here, so a child's second making
+//                gives the board of the first; the return drops the value.
+#pragma once
+
+#include "tpl_beam.h"
+
+namespace tpl_learn {
+
+constexpr int kExactWave = 64;
+constexpr int kExactMaxMoves = 254;                           // M's limit (tpl_create's)
+constexpr int kExactMaxNodes = TPL_EXACT_MAX_NODES;
+static_assert(kUnitBound, "the exact search is a unit of the bounded form");
+static_assert(kMaxPlacements <= kExactWave, "a lane per child");
+
+// one depth of the stack
+template <typename Carry>
+struct alignas(16) Frame {
+    uint4 a, b;                  // the node's board; its window is not part of the rule
+    [[no_unique_address]] Carry carry;                         // of the path to the node, for the order
+    uint32_t count;              // its running children
+    uint32_t cursor;             // how many of them have been descended into
+    uint8_t kids[36];            // their placements b = 10 r + l in the order of the descent, kMaxPlacements at most
+};
+struct NoCarry {};               // of an order whose value reads the board alone: no room in the record
+static_assert(sizeof(Frame<uint32_t>) == 80 && sizeof(Frame<NoCarry>) == 80, "a record is 80 bytes");
+
+// LDS written by one lane, read by another of the same wave: the accesses of a wave reach LDS in order, so this only keeps the
+// compiler from moving them across and waits for the write
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ uint32_t uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+
+template <typename Carry>
+__device__ __forceinline__ void store_frame(Frame<Carry>& f, const tpl::Board& s, Carry carry) {
+    uint4 A, B;
+    tpl::pack_board(s, A, B);
+    f.a = A;
+    f.b = B;
+    f.carry = carry;
+}
+
+// a fresh root of a game: 0 lines, 0 moves, running; the columns are left to the caller
+__device__ __forceinline__ void fresh_root(tpl::Board& root) {
+    root.window = 0u; root.window_hi = 0u;
+    root.state = tpl::ST_RUNNING; root.lines = 0u; root.moves = 0u; root.slot = 0u;
+}
+
+// need(root): no solution of the game with L lines owed is shorter
+__device__ __forceinline__ uint32_t need_of(const tpl::Board& root, uint32_t L) { return (move_bound_cells(root.c, L) + 3u) >> 2; }
+
+// the M + 1 entries of a piece list from pieces[first] on into LDS, masked as move_board masks them
+__device__ __forceinline__ void load_pieces(uint8_t* s_pieces, const uint8_t* pieces, size_t first, uint32_t M, uint32_t lane) {
+    for (uint32_t t = lane; t <= M; t += kExactWave) s_pieces[t] = pieces[first + t] & 7u;
+}
+
+// The LINEAR order of exact.hip, exact_nodes.hip and exact_window.hip on the unit's F board features: a child exactly as solve.hip's
+// expand() makes a bounded candidate -- the board the move leaves, dead turned lost, the carry of the path with the move's, and the
+// value of psi under the weights.  One row of weights for the whole grid: scalar loads, and they stay in SGPRs.
+template <int F>
+struct LinearOrder {
+    using Carry = uint32_t;      // of the path to the node (tpl_placement.h)
+    float w[F];
+    float spare_weight;
+    __device__ __forceinline__ LinearOrder(const float* weights, float spare) : spare_weight(spare) {
+#pragma unroll
+        for (int q = 0; q < F; ++q) w[q] = weights[q];
+    }
+    __device__ __forceinline__ float child(const Frame<Carry>& node, uint32_t cur, const uint8_t*, uint32_t r, uint32_t l,
+                                           const tpl::ShapeWord* shape, uint32_t L, uint32_t B, tpl::Board& s, Carry& carry) const {
+        tpl::unpack_board(node.a, node.b, s);
+        s.window = cur;
+        s.window_hi = 0u;
+        carry = node.carry + placed_move<F>(s, shape, r, l, L, B);
+        const int32_t spare = bounded_move(s, L, B);
+        FeatureSet<F> psi;
+        moved_features(s, carry, true, psi);
+        return bounded_value(placement_score(w, psi), spare_weight, spare);
+    }
+};
+
+struct Found {
+    uint32_t nodes, length, last;                             // expansions, all iterations; the winning length, 0 if none, and its last move
+    bool capped;
+};
+
+// The search of the game (L, M) from `root` -- 0 lines, 0 moves -- whose piece at depth d is s_pieces[d]; every argument is the same
+// in every lane.  `need` is need(root), and need > M is decided without a node.  The caller has filled s_shape and s_pieces, entries
+// 0 .. M.  On return the path of a win is in the stack: the child in hand at every depth, then `last`.
+template <typename Order>
+__device__ __forceinline__ Found search(const Order& order, Frame<typename Order::Carry>* stack, const uint8_t* s_pieces,
+                                        const tpl::ShapeWord* s_shape, const tpl::Board& root, uint32_t need, uint32_t L, uint32_t M,
+                                        uint32_t max_nodes, uint32_t shortest, uint32_t lane) {
+    using Carry = typename Order::Carry;
+    uint32_t nodes = 0u, length = 0u, last = kNoMove;
+    bool capped = false;
+    if (need <= M) {
+#pragma unroll 1
+        for (uint32_t B = shortest ? need : M; B <= M && length == 0u && !capped; ++B) {
+            wave_sync();                                       // the last iteration's reads of record 0 (and, the first time, the tables)
+            if (lane == 0) store_frame(stack[0], root, Carry{});
+            wave_sync();
+            uint32_t d = 0u;
+#pragma unroll 1
+            for (;;) {
+                // expand the node at depth d
+                if (nodes == max_nodes) { capped = true; break; }
+                ++nodes;
+                const uint32_t cur = uniform(s_pieces[d]);
+                const uint32_t stride = placement_count(cur);
+                const bool mine = lane < stride;
+                const uint32_t k = mine ? lane : 0u;
+                uint32_t r, l;
+                const uint32_t b = nth_placement(cur, k, r, l);
+                tpl::Board s;
+                Carry carry;
+                const float value = order.child(stack[d], cur, s_pieces + d + 1u, r, l, s_shape, L, B, s, carry);
+                const uint32_t key_hi = ordered_bits(value), key_lo = kSlotTop - k;
+                const bool won = mine && s.state == tpl::ST_WON, running = mine && s.state == tpl::ST_RUNNING;
+
+                // the stop: the won child that comes first in the order
+                if (__ballot(won) != 0ull) {
+                    const unsigned long long top = wave_max(won ? ((unsigned long long)key_hi << 32) | key_lo : 0ull);
+                    uint32_t r2, l2;
+                    last = nth_placement(cur, kSlotTop - uniform((uint32_t)top), r2, l2);
+                    length = d + 1u;
+                    break;
+                }
+
+                // the order of the running children: a child's rank is the number of running children with a larger key
+                const uint32_t run_hi = running ? key_hi : 0u, run_lo = running ? key_lo : 0u;
+                const unsigned long long run_key = ((unsigned long long)run_hi << 32) | run_lo;
+                uint32_t rank = 0u;
+#pragma unroll
+                for (int j = 0; j < kMaxPlacements; ++j) {
+                    const unsigned long long other = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)run_hi, j) << 32) |
+                                                     (uint32_t)__builtin_amdgcn_readlane((int)run_lo, j);
+                    rank += other > run_key ? 1u : 0u;
+                }
+                const uint32_t count = (uint32_t)__builtin_popcountll(__ballot(running));
+                if (running) {
+                    stack[d].kids[rank] = (uint8_t)b;
+                    if (rank == 0u && d + 1u < M) store_frame(stack[d + 1u], s, carry);      // descended into at once (d + 1 < B <= M)
+                }
+                if (lane == 0) {
+                    stack[d].count = count;
+                    stack[d].cursor = count != 0u ? 1u : 0u;
+                }
+                wave_sync();
+                if (count != 0u) { ++d; continue; }
+
+                // no running child: back to the nearest node that has one left, and into it
+                bool more = false;
+#pragma unroll 1
+                while (d > 0u) {
+                    --d;
+                    const uint32_t at = uniform(stack[d].cursor);
+                    if (at < uniform(stack[d].count)) {
+                        const uint32_t b2 = uniform(stack[d].kids[at]);
+                        tpl::Board s2;
+                        Carry carry2;
+                        order.child(stack[d], uniform(s_pieces[d]), s_pieces + d + 1u, b2 / 10u, b2 % 10u, s_shape, L, B, s2, carry2);
+                        wave_sync();
+                        if (lane == 0 && d + 1u < M) {
+                            stack[d].cursor = at + 1u;
+                            store_frame(stack[d + 1u], s2, carry2);
+                        }
+                        wave_sync();
+                        ++d;
+                        more = true;
+                        break;
+                    }
+                }
+                if (!more) break;                              // the root's children are used up: no win at this budget
+            }
+        }
+    }
+    wave_sync();
+    Found out;
+    out.nodes = nodes;
+    out.length = capped ? 0u : length;
+    out.last = last;
+    out.capped = capped;
+    return out;
+}
+
+// the path of a win from the stack: the child in hand at every depth, then the won one; 255 behind the end, up to `width`
+template <typename Carry>
+__device__ __forceinline__ void write_path(const Frame<Carry>* stack, const Found& f, uint8_t* out, uint32_t width, uint32_t lane) {
+    for (uint32_t t = lane; t < width; t += kExactWave) {
+        uint32_t a = kNoMove;
+        if (t + 1u < f.length) a = stack[t].kids[stack[t].cursor - 1u];
+        else if (t + 1u == f.length) a = f.last;
+        out[t] = (uint8_t)a;
+    }
+}
+
+// What every entry of the five units refuses of n, the game and the node budget, in the order they all test them; `name` leads the
+// message.  A launch is `waves_each` workgroups for each of n, and `each` says so in the refusal; n_cfg is 1 where there is no pool.
+inline int check_search(const char* name, int64_t n, int64_t waves_each, const char* each, int64_t n_cfg, int32_t L, int32_t M,
+                        int32_t max_nodes) {
+    if (n < 1) return fail_msg(TPL_ERR_ARG, "%s: n must be positive", name);
+    if (n >= (((int64_t)1 << 31) + waves_each - 1) / waves_each) return fail_msg(TPL_ERR_ARG, "%s: n too large (%s)", name, each);
+    if (n_cfg < 1 || n_cfg >= ((int64_t)1 << 31)) return fail_msg(TPL_ERR_ARG, "%s: n_cfg must be in [1, 2^31)", name);
+    if (L < 1 || L > 250 || M < 1 || M > kExactMaxMoves)
+        return fail_msg(TPL_ERR_ARG, "%s: L and M must be in [1, 250] and [1, %d]", name, kExactMaxMoves);
+    if (max_nodes < 1 || max_nodes > kExactMaxNodes) return fail_msg(TPL_ERR_ARG, "%s: max_nodes must be in [1, %d]", name, kExactMaxNodes);
+    return TPL_OK;
+}
+
+// the three int32 outputs of a search: the last of every entry's checks
+inline int check_counts(const char* name, const int32_t* solution_len, const int32_t* bound, const uint32_t* nodes) {
+    if ((uintptr_t)solution_len & 3u) return fail_msg(TPL_ERR_ARG, "%s: solution_len must be 4-byte aligned", name);
+    if ((uintptr_t)bound & 3u) return fail_msg(TPL_ERR_ARG, "%s: bound must be 4-byte aligned", name);
+    if ((uintptr_t)nodes & 3u) return fail_msg(TPL_ERR_ARG, "%s: nodes must be 4-byte aligned", name);
+    return TPL_OK;
+}
+
+}  // namespace tpl_learn

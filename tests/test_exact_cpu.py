@@ -281,6 +281,23 @@ def test_the_header_states_the_rule_and_the_library_exports_both_entries():
     assert any(p.endswith(os.path.join("learn", "exact.hip")) for p in m._sources())
 
 
+def test_the_five_exact_units_share_one_search_and_the_mirrors_one_stack_machine():
+    m = _m()
+    assert any(p.endswith(os.path.join("learn", "tpl_exact.h")) for p in m._sources())     # so the library's digest covers it
+    here = os.path.dirname(m._UNITS[-1])
+    loop = ("kids[rank]", "__builtin_amdgcn_readlane", "struct alignas(16) Frame")
+    header = open(os.path.join(here, "tpl_exact.h")).read()
+    assert all(words in header for words in loop)
+    for unit in ("exact.hip", "exact_nodes.hip", "exact_window.hip", "ntuple_exact.hip", "ntuple_window.hip"):
+        body = open(os.path.join(here, unit)).read()
+        assert '#include "tpl_exact.h"' in body, unit
+        assert body.index('#include "tpl_beam.h"') < body.index('#include "tpl_exact.h"'), unit
+        for words in loop:
+            assert words not in body, (unit, words)
+    mirrors = open(m.__file__).read()
+    assert mirrors.count("while stacks:") == 1 and mirrors.count("def _exact_search(") == 1
+
+
 def test_the_exact_kernels_use_no_scratch_and_fill_a_simd_with_waves():
     path = _m().build_library()
     res = subprocess.run(["bash", os.path.join(ROOT, "tools", "kernel_resources.sh"), path], capture_output=True, text=True,

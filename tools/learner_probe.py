@@ -133,6 +133,11 @@ Parts:
               loaded into one process: the outputs of the six entries compared byte for byte on the ring of part ntuple_shape
               at 2^18 boards, then each entry timed in five rounds of the parent against itself and five of the parent against
               this build; a new median passes within the parent's own min-max or at most 2 % above the parent's median
+    exact_ab  --parent LIB: the ten entries of the five exact-search units (exact, exact_nodes, exact_window, ntuple_exact,
+              ntuple_window) of another build of the learner library against this tree's, both loaded into one process: carved
+              L=10 / M=40, 4,096 roots, and 4,096 nodes and resident boards ten moves on, max_nodes 2^12, the table entries under each
+              of the four plain forms; every output compared byte for byte, then each call timed by ntuple_shape_ab's protocol
+              (--no-timing: the comparison alone)
     labels    the proved move labels (tpl_placement_exact_labels, label_states) on the tight pool of the record (part bound's: carved
               L=10 / M=40, 65,536 configurations, seed 7, solved at width 16, tighten_pool(M_new=16)): the classical weights at one ply
               and at beam (3, 8) play one episode on 4,096 boards, label_states (max_nodes 2^12 a child) before every step -- per move
@@ -3470,10 +3475,101 @@ def part_ntuple_shape_ab(parent, rounds=5, reps=20, n=1 << 18):
                 every_output_equal=all(equal.values()), every_median_within=all(l["within"] for l in lines[1:]))
 
 
+def part_exact_ab(parent, rounds=5, reps=3, boards=4096, log2_nodes=12, timing=True):
+    """The ten entries of the five exact-search units of another build of the learner library against this tree's, both loaded into
+    one process and reached through the package's own wrappers (the library handle is swapped under them): carved L = 10 / M = 40,
+    seed 7, `boards` configurations as roots, and as nodes and resident boards after ten moves of the classical one-ply player;
+    max_nodes 2^log2_nodes; the two table entries under each of the four plain forms (random tables: an order is an order).  Every
+    output is compared byte for byte; then (timing) each call is timed by ntuple_shape_ab's protocol."""
+    import ctypes as C
+    import numpy as np
+    import torch
+    import tetris_piclim as T
+    m = T._learn_lib
+    libs = {"new": m.lib(), "parent": C.CDLL(os.path.abspath(parent))}
+    for name in m.LEARN_SYMBOLS:
+        f, g = getattr(libs["new"], name), getattr(libs["parent"], name)
+        g.argtypes, g.restype = f.argtypes, f.restype
+    dev, L_, M_, cap = "cuda:0", 10, 40, 1 << log2_nodes
+    env = T.BatchedTetris(L_, M_, 64, device=dev, seed=7)
+    rows, pieces = env.carved_configs(boards, seed=7)
+    env.terminate()
+    env = T.BatchedTetris(L_, M_, boards, device=dev, seed=11, auto_reset=False, reward=(0.0, 1.0, 0.0), config_pool=(rows, pieces))
+    env.reset()
+    player, action = T.HeuristicPolicy(env, np.array(T.CLASSICAL_WEIGHTS), depth=1), torch.empty(boards, dtype=torch.uint8, device=dev)
+    for _ in range(10):                                          # moves = 10: the window shows its twelve pieces again
+        player.act(out=action)
+        env.step(action, observe=False)
+    state, entry = env.packed_state(), T.config_index(env)
+    running = state["state"] == 0
+    lines = torch.where(running, state["lines"], torch.full_like(state["lines"], L_))
+    node = (state["rows"], lines, state["moves"], entry, pieces, L_, M_)
+    rows12 = np.array(T.CLASSICAL_WEIGHTS)
+    weights = {"": rows12, "_move": np.concatenate([rows12, np.array([-0.4, 0.3], np.float32)])}
+    gen = torch.Generator(device="cpu").manual_seed(7)
+    tables = {form: torch.randint(-(1 << 16), 1 << 16, (m.ntuple_entries_of(form),), generator=gen, dtype=torch.int32).to(dev)
+              for form in m.NTUPLE_EXACT_FORMS}
+    order = dict(gamma=0.99, reward=NTUPLE_LARGE_REWARD)
+    calls = {}
+    for form, w in weights.items():
+        calls["tpl_placement_exact" + form] = lambda w=w: T.prove_configs(rows, pieces, L_, M_, weights=w, max_nodes=cap, device=dev,
+                                                                        validate=False)
+        calls["tpl_placement_exact_nodes" + form] = lambda w=w: T.prove_nodes(*node, weights=w, max_nodes=cap, device=dev, validate=False)
+        calls["tpl_placement_exact_labels" + form] = lambda w=w: T.label_moves(*node, weights=w, max_nodes=cap, device=dev, validate=False)
+        calls["tpl_placement_window_prove" + form] = lambda w=w: T.window_prove(env, weights=w, max_nodes=cap)
+    for form, table in tables.items():
+        calls[f"tpl_ntuple_exact {form}"] = lambda t=table: T.ntuple_prove_configs(rows, pieces, L_, M_, t, max_nodes=cap, device=dev,
+                                                                                  validate=False, **order)
+        calls[f"tpl_ntuple_window_prove {form}"] = lambda t=table: T.ntuple_window_prove(env, t, max_nodes=cap, **order)
+
+    def run(which, name):
+        m._handle = libs[which]
+        try:
+            return calls[name]()
+        finally:
+            m._handle = libs["new"]
+
+    lines_, equal = [], {}
+    for name in calls:                                           # byte for byte, every tensor the wrapper returns
+        got = {}
+        for which in ("parent", "new"):
+            got[which] = run(which, name)
+            torch.cuda.synchronize()
+        equal[name] = set(got["parent"]) == set(got["new"]) and all(torch.equal(got["parent"][k], got["new"][k]) for k in got["new"])
+        nodes = got["new"]["nodes"].double()
+        lines_.append(dict(entry=name, outputs_equal=equal[name], searches=int(nodes.numel()), nodes=int(nodes.sum()),
+                           capped=int((nodes == cap).sum())))
+        print(json.dumps(lines_[-1]), file=sys.stderr, flush=True)
+    out = dict(part="exact_ab", boards=boards, max_nodes=f"2^{log2_nodes}", running_nodes=int(running.sum()), lines=lines_,
+               every_output_equal=all(equal.values()))
+    if timing:
+        ms = lambda t: round(t * 1e3, 3)
+        for name in calls:
+            fa, fb = (lambda: run("parent", name)), (lambda: run("new", name))
+            k = 1 if "labels" in name else reps                  # forty searches a node: one launch is long enough
+            a, b, pa, nb = [], [], [], []
+            for _ in range(rounds):                              # the parent against itself: the noise of the method
+                a.append(ms(_timed(fa, k, warmup=1)))
+                b.append(ms(_timed(fa, k, warmup=1)))
+            for _ in range(rounds):                              # the parent against this build, alternated
+                pa.append(ms(_timed(fa, k, warmup=1)))
+                nb.append(ms(_timed(fb, k, warmup=1)))
+            lo, hi = min(a + b), max(a + b)
+            pm, nm = sorted(pa)[rounds // 2], sorted(nb)[rounds // 2]
+            bound = max(hi, round(1.02 * pm, 3))
+            lines_.append(dict(entry=name, parent_against_itself=dict(a=a, b=b, min=lo, max=hi), parent=pa, new=nb, parent_median_ms=pm,
+                               new_median_ms=nm, ratio=round(nm / pm, 4), bound_ms=bound, within=bool(nm <= bound), launches_per_timing=k))
+            print(json.dumps(lines_[-1]), file=sys.stderr, flush=True)
+        out.update(rounds=rounds, launches_per_timing=reps, every_median_within=all(l["within"] for l in lines_ if "within" in l))
+    env.terminate()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", choices=sorted(PARTS) + ["ntuple_shape_ab"])
-    ap.add_argument("--parent", default=None, help="of part ntuple_shape_ab: the learner library of the build to compare against")
+    ap.add_argument("--part", choices=sorted(PARTS) + ["ntuple_shape_ab", "exact_ab"])
+    ap.add_argument("--parent", default=None, help="of parts ntuple_shape_ab and exact_ab: the learner library of the build to compare against")
+    ap.add_argument("--no-timing", action="store_true", help="of part exact_ab: compare the outputs only")
     ap.add_argument("--chunk", default=None, help="I/K: of part ntuple_coherent_sweep, every K-th cell from the I-th on")
     ap.add_argument("--sections", default=None, help="of part window: which of record,rates,verdicts,time,loose to run (all)")
     ap.add_argument("--budgets", default=None, help="of part window: the log2 of the node budgets, e.g. 8,12 (8,12,16)")
@@ -3494,10 +3590,14 @@ def main():
                 kw["sections"] = tuple(args.sections.split(","))
             if args.budgets:
                 kw["budgets"] = tuple(int(v) for v in args.budgets.split(","))
-        if args.part == "ntuple_shape_ab":
+        if args.part in ("ntuple_shape_ab", "exact_ab"):
             if not args.parent:
-                ap.error("--part ntuple_shape_ab needs --parent LIB")
+                ap.error(f"--part {args.part} needs --parent LIB")
             kw["parent"] = args.parent
+        if args.no_timing:
+            if args.part != "exact_ab":
+                ap.error("--no-timing goes with --part exact_ab")
+            kw["timing"] = False
         print(json.dumps(globals()["part_" + args.part](**kw)), flush=True)
         return 0
     for name, limit in PARTS.items():
