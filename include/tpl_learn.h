@@ -1233,6 +1233,77 @@ int tpl_ntuple_window_prove(const void* plane_a, const void* plane_b, int64_t n,
                             const uint8_t* skip, uint8_t* solved, uint8_t* proved, int32_t* solution_len, uint8_t* plan,
                             int32_t* bound, uint32_t* nodes, uint8_t* horizon, uint8_t* verdict, void* stream);
 
+/* The exact searches in LIMITED-DISCREPANCY ORDER (Harvey and Ginsberg; csrc/learn/tpl_exact.h: search<Order, Limited = true>).  A proof
+ * fits max_nodes or it does not, and on a winnable board the node count is a matter of child order alone.  Plain depth-first search
+ * spends a budget badly when the order is good but not perfect: one wrong choice near the root, and the whole subtree below it is
+ * searched out before the second child is tried.  The limited search tries the paths that follow the order everywhere first, then
+ * those that leave it once, then twice, and so on until an iteration cuts nothing.
+ *
+ * Each _limited entry is its twin -- tpl_placement_exact[_move], tpl_placement_window_prove[_move], tpl_ntuple_exact,
+ * tpl_ntuple_window_prove -- with three more arguments: int32 first_limit in [0, 65535] and int32 growth in {0, 1} behind max_nodes and
+ * shortest, and the output limit i32 [n] behind nodes.  The children, their values, their order, the stop, the node cap, the budgets,
+ * the frames and the verdicts are the twin's.  THE RULE is the twin's search with one more loop and one more number at a node:
+ *   AN ITERATION is (B, K): the game (L, B) as before, searched under the discrepancy limit K.  The root is given rem = K.
+ *   A node with rem is EXPANDED exactly as in the plain search: the node count is checked and counted, every distinct placement of its
+ *     piece is made, and a dead child is lost.
+ *   If ANY child is won the iteration ends with the won child that comes first in the order, WHATEVER ITS RANK.
+ *   Otherwise the running children are ranked as in the plain search (value descending, placement ascending), rank 0 first.
+ *     Only the children of rank <= rem are kept: the node has min(count, rem + 1) children to descend into.
+ *     If a running child was dropped, the iteration's flag `cut` is set.
+ *     The kept child of rank j is searched with rem - j.
+ *   When the root's children are used up:
+ *     cut is set:   the next iteration is (B, K'), from a fresh root, with cut cleared;
+ *     cut is clear: nothing was dropped, so the iteration visited every running board the plain iteration at B visits.  The game
+ *                   (L, B) is searched out, and the search goes on to B + 1 with K back at first_limit, or ends, as the plain one.
+ *   K' = K + 1 with growth = 0 ("add"), K' = max(1, 2 K) with growth = 1 ("double"); K' is clamped at 65,535 either way.  A path has
+ *     at most 253 nodes above the one expanded and a rank is at most 33, so a K >= 8,382 never cuts.
+ *   nodes counts the expansions of ALL iterations (B, K); nodes == max_nodes ends the whole search and proves nothing, as in the twin.
+ *   limit is the K of the last iteration begun, and 0 where there was no iteration (bound > M; a finished or skipped board).
+ * Consequences:
+ *   1. VERDICTS DO NOT CHANGE.  Under proved = 1, solved, solution_len, bound and unwinnable (solved = 0) are the plain search's, for
+ *      any first_limit and growth, because the last iteration at every budget cut nothing.  The window entries' verdicts (1 WIN,
+ *      2 LOSS, 3 OPEN) are defined from solved, proved and the horizon as in the twin: VERDICT 3 STILL PROVES NOTHING ABOUT THE GAME.
+ *   2. THE SOLUTION MAY DIFFER.  actions (plan) may name a different win of the same length.  It is still a shortest win, and it
+ *      replays to a win in exactly solution_len moves.
+ *   3. first_limit >= 8,382 gives the plain search's outputs BYTE FOR BYTE: all six (eight) outputs, the path as well.
+ *   4. THE WORST CASE for a budget with no win is bounded.  If the plain search takes T nodes to search that budget out, the limited
+ *      search takes at most 15 T under "double" -- the K values are 0, 1, 2, 4, .., 8,192 -- and up to 8,383 T under "add".  "add"
+ *      found more wins at equal node budgets where it was measured; "double" is the choice where budgets below the shortest length must
+ *      be exhausted.
+ * With proved = 0 nothing is proved, as in the twin.  What limited-discrepancy order buys is proofs within max_nodes: whatever the plain
+ * search proves within max_nodes under first_limit >= 8,382 it proves too; under a small first_limit a search may be capped that the
+ * plain one finishes, and the other way round.
+ * Kernels of the twins' frames with their own names and argument records: one wavefront a configuration or board, the same LDS, a
+ * stack record of the same 80 bytes -- a node's rem is the upper half of its child count's word --, rem, K and cut in scalar
+ * registers.  Refused before any HIP call: everything the twin refuses, first_limit outside [0, 65535], growth other than 0 or 1, a
+ * NULL limit, limit not 4-byte aligned. */
+int tpl_placement_exact_limited(const int16_t* rows, const uint8_t* pieces, int64_t n, int32_t L, int32_t M, const float* weights,
+                                float spare_weight, int32_t max_nodes, int32_t shortest, int32_t first_limit, int32_t growth,
+                                uint8_t* solved, uint8_t* proved, int32_t* solution_len, uint8_t* actions, int32_t* bound,
+                                uint32_t* nodes, int32_t* limit, void* stream);
+int tpl_placement_exact_limited_move(const int16_t* rows, const uint8_t* pieces, int64_t n, int32_t L, int32_t M, const float* weights,
+                                     float spare_weight, int32_t max_nodes, int32_t shortest, int32_t first_limit, int32_t growth,
+                                     uint8_t* solved, uint8_t* proved, int32_t* solution_len, uint8_t* actions, int32_t* bound,
+                                     uint32_t* nodes, int32_t* limit, void* stream);
+int tpl_placement_window_prove_limited(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const float* weights,
+                                       float spare_weight, int32_t max_nodes, int32_t first_limit, int32_t growth, const uint8_t* skip,
+                                       uint8_t* solved, uint8_t* proved, int32_t* solution_len, uint8_t* plan, int32_t* bound,
+                                       uint32_t* nodes, int32_t* limit, uint8_t* horizon, uint8_t* verdict, void* stream);
+int tpl_placement_window_prove_limited_move(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M,
+                                            const float* weights, float spare_weight, int32_t max_nodes, int32_t first_limit,
+                                            int32_t growth, const uint8_t* skip, uint8_t* solved, uint8_t* proved, int32_t* solution_len,
+                                            uint8_t* plan, int32_t* bound, uint32_t* nodes, int32_t* limit, uint8_t* horizon,
+                                            uint8_t* verdict, void* stream);
+int tpl_ntuple_exact_limited(const int16_t* rows, const uint8_t* pieces, int64_t n, int32_t L, int32_t M, const int32_t* table,
+                             int64_t entries, float r_line, float r_win, float r_lose, float gamma, int32_t max_nodes, int32_t shortest,
+                             int32_t first_limit, int32_t growth, uint8_t* solved, uint8_t* proved, int32_t* solution_len,
+                             uint8_t* actions, int32_t* bound, uint32_t* nodes, int32_t* limit, void* stream);
+int tpl_ntuple_window_prove_limited(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const int32_t* table,
+                                    int64_t entries, float r_line, float r_win, float r_lose, float gamma, int32_t max_nodes,
+                                    int32_t first_limit, int32_t growth, const uint8_t* skip, uint8_t* solved, uint8_t* proved,
+                                    int32_t* solution_len, uint8_t* plan, int32_t* bound, uint32_t* nodes, int32_t* limit,
+                                    uint8_t* horizon, uint8_t* verdict, void* stream);
+
 /* The ranking update: what a proved move label teaches a table (csrc/learn/ntuple_rank.hip).  tpl_placement_exact_labels labels every
  * placement of a board 1 (proved winning), 2 (proved losing) or 3 (unproved).  tpl_ntuple_rank reads such a row beside the board and a
  * table and says whether the table's one-ply policy already prefers a proved win to every proved loss; where it does not, it names the

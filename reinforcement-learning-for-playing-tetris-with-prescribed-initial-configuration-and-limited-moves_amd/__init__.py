@@ -20,7 +20,8 @@ __all__ = ["BatchedTetris", "Tetris", "Snapshot", "OBS_DIM", "NUM_ACTIONS", "RUN
            "MOVE_FEATURE_NAMES", "DELLACHERIE_WEIGHTS", "move_bound", "config_bound", "config_index", "PoolTally", "resample_pool",
            "curriculum_weights", "PoolCurriculum", "prove_nodes", "label_moves", "label_states", "blunders",
            "NTupleRanker", "LabelSet", "collect_labels", "label_agreement", "window_prove", "ProofPolicy",
-           "ntuple_window_prove", "TableProofPolicy"]
+           "ntuple_window_prove", "TableProofPolicy", "prove_configs_limited", "ntuple_prove_configs_limited",
+           "window_prove_limited", "ntuple_window_prove_limited", "LimitedProofPolicy"]
 
 
 def __getattr__(name):
@@ -52,7 +53,8 @@ def __getattr__(name):
         return getattr(importlib.import_module(__name__ + ".ntuple"), name)
     if name in ("solve_configs", "prove_configs", "ntuple_prove_configs", "tighten_pool", "CLASSICAL_WEIGHTS", "config_bound", "prove_nodes",
                 "label_moves", "label_states", "blunders", "LabelSet", "collect_labels", "label_agreement", "window_prove", "ProofPolicy",
-                "ntuple_window_prove", "TableProofPolicy"):
+                "ntuple_window_prove", "TableProofPolicy", "prove_configs_limited", "ntuple_prove_configs_limited",
+                "window_prove_limited", "ntuple_window_prove_limited", "LimitedProofPolicy"):
         return getattr(importlib.import_module(__name__ + ".solve"), name)
     if name in ("config_index", "PoolTally", "resample_pool", "curriculum_weights", "PoolCurriculum"):
         return getattr(importlib.import_module(__name__ + ".curriculum"), name)

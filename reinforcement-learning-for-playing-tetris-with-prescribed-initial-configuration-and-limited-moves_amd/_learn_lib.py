@@ -26,7 +26,9 @@ _UNITS = [os.path.join(_LEARN_CSRC, f) for f in ("replay.hip", "pack.hip", "prio
                                                       "solve_bound.hip", "beam_move_bound.hip", "solve_move_bound.hip",
                                                       "exact.hip", "exact_move.hip", "ntuple_exact.hip", "curriculum.hip", "exact_nodes.hip",
                                                       "exact_nodes_move.hip", "exact_window.hip", "exact_window_move.hip",
-                                                      "ntuple_window.hip", "ntuple_rank.hip", "heuristic.hip")]
+                                                      "ntuple_window.hip", "ntuple_rank.hip", "exact_limited.hip", "exact_limited_move.hip",
+                                                      "exact_window_limited.hip", "exact_window_limited_move.hip",
+                                                      "ntuple_exact_limited.hip", "ntuple_window_limited.hip", "heuristic.hip")]
 
 # entry points declared in include/tpl_learn.h (tests check that the .so exports every one of them)
 LEARN_SYMBOLS = [
@@ -54,6 +56,8 @@ LEARN_SYMBOLS = [
     "tpl_placement_exact_nodes", "tpl_placement_exact_nodes_move", "tpl_placement_exact_labels", "tpl_placement_exact_labels_move",
     "tpl_ntuple_rank",
     "tpl_placement_window_prove", "tpl_placement_window_prove_move", "tpl_ntuple_window_prove",
+    "tpl_placement_exact_limited", "tpl_placement_exact_limited_move", "tpl_placement_window_prove_limited",
+    "tpl_placement_window_prove_limited_move", "tpl_ntuple_exact_limited", "tpl_ntuple_window_prove_limited",
 ]
 NSTEP_MAX = 16
 BEAM_MAX_DEPTH, BEAM_MAX_WIDTH = 12, 64
@@ -187,6 +191,13 @@ def lib() -> C.CDLL:
         window = getattr(L, f"tpl_placement_window_prove{form}")
         window.argtypes = [vp, vp, i64, i32, i32, vp, f32, i32, vp] + [vp] * 8 + [vp]
         window.restype = i32
+        # the limited searches: first_limit and growth behind max_nodes and shortest, limit behind nodes
+        limited = getattr(L, f"tpl_placement_exact_limited{form}")
+        limited.argtypes = exact.argtypes[:9] + [i32, i32] + exact.argtypes[9:15] + [vp, vp]
+        limited.restype = i32
+        limited = getattr(L, f"tpl_placement_window_prove_limited{form}")
+        limited.argtypes = window.argtypes[:8] + [i32, i32] + window.argtypes[8:15] + [vp] + window.argtypes[15:]
+        limited.restype = i32
     L.tpl_ntuple_value.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp]
     L.tpl_ntuple_act.argtypes = [vp, vp, i64, i32, i32, f32, f32, f32, f32, vp, f32, u64, u64, vp, vp, vp, vp, vp, vp]
     L.tpl_ntuple_update.argtypes = [vp, vp, i64, i32, i32, vp, vp, f32, vp]
@@ -241,6 +252,12 @@ def lib() -> C.CDLL:
     # the table-ordered window search: tpl_placement_window_prove's arguments with tpl_ntuple_exact's table, reward and gamma
     L.tpl_ntuple_window_prove.argtypes = [vp, vp, i64, i32, i32, vp, i64, f32, f32, f32, f32, i32, vp] + [vp] * 8 + [vp]
     L.tpl_ntuple_window_prove.restype = i32
+    # their limited forms: first_limit and growth behind max_nodes and shortest, limit behind nodes
+    L.tpl_ntuple_exact_limited.argtypes = L.tpl_ntuple_exact.argtypes[:13] + [i32, i32] + L.tpl_ntuple_exact.argtypes[13:19] + [vp, vp]
+    L.tpl_ntuple_window_prove_limited.argtypes = (L.tpl_ntuple_window_prove.argtypes[:12] + [i32, i32] +
+                                                  L.tpl_ntuple_window_prove.argtypes[12:19] + [vp] +
+                                                  L.tpl_ntuple_window_prove.argtypes[19:])
+    L.tpl_ntuple_exact_limited.restype = L.tpl_ntuple_window_prove_limited.restype = i32
     # the ranking update's chooser: the planes, the table and its entry count, the label rows, then the eleven outputs
     L.tpl_ntuple_rank.argtypes = [vp, vp, i64, i32, i32, vp, i64, vp, f32, f32, f32, f32, f32, i32] + [vp] * 12
     L.tpl_ntuple_rank.restype = i32
@@ -940,13 +957,32 @@ def _exact_arrays(rows, pieces, L: int, M: int, max_nodes, shortest):
     return L, M, int(max_nodes), rows, pieces
 
 
-def _exact_search(rows, pieces, L: int, M: int, max_nodes: int, shortest: bool, children):
+LIMIT_TOP = 65535                                        # the clamp of a discrepancy limit K, and first_limit's largest value
+LIMIT_NEVER_CUTS = 8382                                  # a K from here on never cuts: 253 nodes above the one expanded, ranks <= 33
+DISCREPANCY_GROWTH = {"add": 0, "double": 1}             # discrepancy= of the Python surface -> the C `growth`
+
+
+def _limit_arguments(first_limit, growth) -> None:
+    """What every limited mirror refuses of its two arguments (first_limit None is the plain rule and takes any growth of the two)."""
+    if first_limit is not None and (isinstance(first_limit, bool) or not isinstance(first_limit, (int, np.integer))
+                                    or not 0 <= int(first_limit) <= LIMIT_TOP):
+        raise ValueError(f"first_limit must be None or an integer in [0, {LIMIT_TOP}]")
+    if isinstance(growth, bool) or not isinstance(growth, (int, np.integer)) or int(growth) not in (0, 1):
+        raise ValueError("growth must be 0 (add) or 1 (double)")
+
+
+def _exact_search(rows, pieces, L: int, M: int, max_nodes: int, shortest: bool, children, first_limit=None, growth: int = 0):
     """The depth-first search of placement_exact and ntuple_exact on checked arguments: the budgets, the cap, the stop at the first won
     child in the order (value descending, placement ascending; -0 and +0 tie), the descent and the return.  What a node's children are
     worth is the caller's: children(tops, piece, nxt, b, L, B) takes a batch of children of the game (L, B), one a row -- tops holds
     the parent's rows, lines, moves and extra (None where no parent has any: a root carries nothing), piece the piece placed, nxt the
     one behind it in the list, b the placement -- and returns their (value, state, rows, lines, moves, extra), extra being whatever
     the order keeps along a path, or None.  Returns placement_exact's six arrays.
+    first_limit None is the plain rule.  An integer is the LIMITED rule of tpl_placement_exact_limited: an iteration is (B, K), K from
+    first_limit; a node holds rem, what is left of K on its path; of its running children those of rank <= rem are kept, the one of
+    rank j with rem - j, and a dropped child sets the iteration's cut; a budget searched out with cut set starts again from a fresh
+    root under K + 1 (growth 0) or max(1, 2 K) (growth 1), clamped at 65,535, and only one that cut nothing ends the budget.  Then a
+    seventh array is returned: limit int32 [n], the K of the last iteration begun.
     The configurations are searched in step, one expansion each a round, so that every round moves and counts the children of all of
     them in one batch per budget."""
     n = rows.shape[0]
@@ -955,12 +991,17 @@ def _exact_search(rows, pieces, L: int, M: int, max_nodes: int, shortest: bool, 
     solved, proved, length = np.zeros(n, np.uint8), np.ones(n, np.uint8), np.zeros(n, np.int32)
     actions, nodes = np.full((n, M), NO_SECOND, np.uint8), np.zeros(n, np.uint32)
 
+    limited = first_limit is not None
+    limit, cut = np.zeros(n, np.int32), np.zeros(n, bool)
+
     def root(s):
-        return dict(rows=rows[s], lines=0, moves=0, extra=None, kids=None, at=0)
+        return dict(rows=rows[s], lines=0, moves=0, extra=None, kids=None, at=0, rem=int(limit[s]))
 
     # a stack per configuration still searched, its last frame the node to expand next; a frame's kids are its running children in
     # the order of the descent -- (placement, rows, lines, moves, extra) each --, `at` the next of them
     budget = {s: int(bound[s]) if shortest else M for s in range(n) if bound[s] <= M}
+    if limited:
+        limit[sorted(budget)] = int(first_limit)
     stacks = {s: [root(s)] for s in budget}
     while stacks:
         for s in [s for s in stacks if nodes[s] == max_nodes]:  # the cap: nothing is proved, nothing is reported
@@ -999,20 +1040,27 @@ def _exact_search(rows, pieces, L: int, M: int, max_nodes: int, shortest: bool, 
                 del stacks[s]
                 continue
             run = order[state[order] == STATE_RUNNING]
+            if limited and run.size > stack[-1]["rem"] + 1:     # the children of rank <= rem are kept; a dropped one is a cut
+                run, cut[s] = run[:stack[-1]["rem"] + 1], True
             stack[-1]["kids"] = [(int(b[k]), c_rows[k], int(c_lines[k]), int(c_moves[k]), None if c_extra is None else c_extra[k]) for k in run]
             while stack and stack[-1]["at"] == len(stack[-1]["kids"]):
                 stack.pop()                                     # used up: back to the parent
             if stack:
                 top = stack[-1]
                 _, k_rows, k_lines, k_moves, k_extra = top["kids"][top["at"]]
+                stack.append(dict(rows=k_rows, lines=k_lines, moves=k_moves, extra=k_extra, kids=None, at=0, rem=top["rem"] - top["at"]))
                 top["at"] += 1
-                stack.append(dict(rows=k_rows, lines=k_lines, moves=k_moves, extra=k_extra, kids=None, at=0))
+            elif cut[s]:                                        # something was dropped: the same budget under the next limit
+                limit[s], cut[s] = min(max(1, 2 * int(limit[s])) if growth else int(limit[s]) + 1, LIMIT_TOP), False
+                stack.append(root(s))
             elif shortest and budget[s] < M:                    # searched out at this budget: the next one
                 budget[s] += 1
+                if limited:
+                    limit[s] = int(first_limit)
                 stack.append(root(s))
             else:                                               # searched out: no sequence of placements wins within M moves
                 del stacks[s]
-    return solved, proved, length, actions, bound, nodes
+    return (solved, proved, length, actions, bound, nodes) + ((limit,) if limited else ())
 
 
 def placement_exact(rows, pieces, L: int, M: int, weights, max_nodes: int, shortest: bool = True, spare_weight: float = 0.0):
@@ -1023,7 +1071,21 @@ def placement_exact(rows, pieces, L: int, M: int, weights, max_nodes: int, short
     iteration; B runs over need(root) .. M (shortest) or is M alone; `nodes` counts the expansions of all iterations and the search
     gives up, proving nothing, when it would pass max_nodes.  Returns (solved uint8 [n], proved uint8 [n], solution_len int32 [n],
     actions uint8 [n, M] padded with 255, bound int32 [n], nodes uint32 [n]) in the C layout (_exact_search)."""
+    return _placement_exact(rows, pieces, L, M, weights, max_nodes, shortest, spare_weight, None, 0)
+
+
+def placement_exact_limited(rows, pieces, L: int, M: int, weights, max_nodes: int, first_limit: int = 0, growth: int = 0,
+                            shortest: bool = True, spare_weight: float = 0.0):
+    """The rule of tpl_placement_exact_limited (include/tpl_learn.h): placement_exact in limited-discrepancy order, with first_limit an
+    integer in [0, 65535] and growth 0 ("add") or 1 ("double") (_exact_search says what they do).  Under proved the verdicts are
+    placement_exact's; first_limit >= 8,382 gives its outputs byte for byte.  Returns its six arrays and limit int32 [n], the K of the
+    last iteration begun.  first_limit None is placement_exact itself, six arrays."""
+    return _placement_exact(rows, pieces, L, M, weights, max_nodes, shortest, spare_weight, first_limit, growth)
+
+
+def _placement_exact(rows, pieces, L, M, weights, max_nodes, shortest, spare_weight, first_limit, growth):
     L, M, max_nodes, rows, pieces = _exact_arrays(rows, pieces, L, M, max_nodes, shortest)
+    _limit_arguments(first_limit, growth)
     w = np.asarray(weights, dtype=np.float32).reshape(-1)
     if w.shape not in ((NUM_FEATURES,), (NUM_MOVE_FEATURES,)):
         raise ValueError("weights must be one row of 12 or of 14")
@@ -1044,7 +1106,7 @@ def placement_exact(rows, pieces, L: int, M: int, weights, max_nodes: int, short
         value = placement_score(psi, w)
         return value + spare_weight * spare.astype(np.float32), s2, r2, l2, m2, sums
 
-    return _exact_search(rows, pieces, L, M, max_nodes, bool(shortest), children)
+    return _exact_search(rows, pieces, L, M, max_nodes, bool(shortest), children, first_limit, int(growth))
 
 
 # ------------------------------------------------------------------------------------------------ the exact search from a node
@@ -1178,7 +1240,8 @@ def window_entries(window) -> np.ndarray:
 def _window_frame(rows, lines, moves, state, window, L: int, M: int, skip, search) -> dict:
     """The framing the two window mirrors share: the fields checked, live / known / rem / H, the dict in the C layout, the boards grouped
     by (lines, H), and the verdicts.  search(rows [k, 20], lists [k, H + 1], L - lines, H) -> the six arrays of an exact mirror for the
-    group's configurations, shortest."""
+    group's configurations, shortest -- or the seven of a limited one, and then the dict holds limit int32 [n], 0 where nothing was
+    searched."""
     rows = np.asarray(rows)
     rows = (rows.view(np.uint16) if rows.dtype == np.int16 else rows.astype(np.uint16)).reshape(-1, 20)
     n = rows.shape[0]
@@ -1215,7 +1278,9 @@ def _window_frame(rows, lines, moves, state, window, L: int, M: int, skip, searc
     for at_lines, at_H in sorted({(int(a), int(b)) for a, b in zip(lines[todo], H[todo])}):
         idx = np.flatnonzero(todo & (lines == at_lines) & (H == at_H))
         lists = np.concatenate([q[idx, :at_H], np.zeros((idx.size, 1), np.int64)], axis=1)      # [k, H + 1]: the last is never placed
-        solved, proved, length, actions, _, nodes = search(rows[idx], lists, L - at_lines, at_H)
+        solved, proved, length, actions, _, nodes, *limit = search(rows[idx], lists, L - at_lines, at_H)
+        if limit:
+            out.setdefault("limit", np.zeros(n, np.int32))[idx] = limit[0]
         out["solved"][idx], out["proved"][idx], out["solution_len"][idx], out["nodes"][idx] = solved, proved, length, nodes
         out["plan"][idx, :at_H] = actions
         out["verdict"][idx] = np.where(solved == 1, WINDOW_WIN,
@@ -1232,12 +1297,28 @@ def placement_window_prove(rows, lines, moves, state, window, L: int, M: int, we
     searched as the configuration (rows, window entries 0 .. H - 1) of the game (L - lines, H), shortest; anything else is finished.
     Returns a dict in the C layout: solved, proved uint8 [n], solution_len int32 [n], plan uint8 [n, 12] padded with 255, bound int32
     [n], nodes uint32 [n], horizon uint8 [n], verdict uint8 [n] (WINDOW_NONE / WIN / LOSS / OPEN), and known uint8 [n]."""
+    return _placement_window_prove(rows, lines, moves, state, window, L, M, weights, max_nodes, spare_weight, skip, None, 0)
+
+
+def placement_window_prove_limited(rows, lines, moves, state, window, L: int, M: int, weights, max_nodes: int, first_limit: int = 0,
+                                   growth: int = 0, spare_weight: float = 0.0, skip=None) -> dict:
+    """The rule of tpl_placement_window_prove_limited (include/tpl_learn.h): placement_window_prove with the search of every board
+    placement_exact_limited's.  Returns its dict with limit int32 [n], 0 where nothing was searched."""
+    return _placement_window_prove(rows, lines, moves, state, window, L, M, weights, max_nodes, spare_weight, skip, first_limit, growth)
+
+
+def _placement_window_prove(rows, lines, moves, state, window, L, M, weights, max_nodes, spare_weight, skip, first_limit, growth) -> dict:
     L, M = int(L), int(M)
     if not (1 <= L <= 250 and 1 <= M <= SOLVE_MAX_MOVES):
         raise ValueError(f"L and M must be in [1, 250] and [1, {SOLVE_MAX_MOVES}]")
     _exact_arguments(weights, max_nodes, True, spare_weight)
-    return _window_frame(rows, lines, moves, state, window, L, M, skip,
-                         lambda r, p, game_L, H: placement_exact(r, p, game_L, H, weights, max_nodes, True, spare_weight))
+    _limit_arguments(first_limit, growth)
+    out = _window_frame(rows, lines, moves, state, window, L, M, skip,
+                        lambda r, p, game_L, H: _placement_exact(r, p, game_L, H, weights, max_nodes, True, spare_weight, first_limit,
+                                                                 growth))
+    if first_limit is not None:
+        out.setdefault("limit", np.zeros(out["solved"].shape[0], np.int32))
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ the n-tuple value function
@@ -1544,7 +1625,19 @@ def ntuple_exact(rows, pieces, L: int, M: int, table, max_nodes: int, shortest: 
     search is placement_exact's (_exact_search); the child made at depth d is worth reward, or reward + gamma * V where it runs, V being
     ntuple_value of its board with pieces[d + 1] as the falling piece in the game (L, B) of the iteration -- float32 operations, each
     rounded once.  Returns placement_exact's six arrays."""
+    return _ntuple_exact(rows, pieces, L, M, table, max_nodes, shortest, gamma, reward, None, 0)
+
+
+def ntuple_exact_limited(rows, pieces, L: int, M: int, table, max_nodes: int, first_limit: int = 0, growth: int = 0,
+                         shortest: bool = True, gamma: float = 1.0, reward=(1.0, 0.0, 0.0)):
+    """The rule of tpl_ntuple_exact_limited (include/tpl_learn.h): ntuple_exact in limited-discrepancy order, first_limit and growth
+    placement_exact_limited's.  Returns its seven arrays."""
+    return _ntuple_exact(rows, pieces, L, M, table, max_nodes, shortest, gamma, reward, first_limit, growth)
+
+
+def _ntuple_exact(rows, pieces, L, M, table, max_nodes, shortest, gamma, reward, first_limit, growth):
     L, M, max_nodes, rows, pieces = _exact_arrays(rows, pieces, L, M, max_nodes, shortest)
+    _limit_arguments(first_limit, growth)
     table = _ntuple_exact_table(table)
     try:
         with np.errstate(over="ignore"):
@@ -1566,7 +1659,7 @@ def ntuple_exact(rows, pieces, L: int, M: int, table, max_nodes: int, shortest: 
             value = np.where(s2 == STATE_RUNNING, r + g * v, r).astype(np.float32)
         return value, s2, r2, l2, m2, None
 
-    return _exact_search(rows, pieces, L, M, max_nodes, bool(shortest), children)
+    return _exact_search(rows, pieces, L, M, max_nodes, bool(shortest), children, first_limit, int(growth))
 
 
 # The rule of tpl_ntuple_window_prove (include/tpl_learn.h) on the host: placement_window_prove's framing (_window_frame, shared) with
@@ -1579,6 +1672,17 @@ def ntuple_window_prove(rows, lines, moves, state, window, L: int, M: int, table
     r_lose) for the weights and spare_weight.  A running board with lines < L and moves < M is searched as the configuration (rows,
     [window entries 0 .. H - 1, 0]) of the game (L - lines, H) by ntuple_exact, shortest; anything else is finished.
     Returns placement_window_prove's dict, `known` included."""
+    return _ntuple_window_prove(rows, lines, moves, state, window, L, M, table, max_nodes, gamma, reward, skip, None, 0)
+
+
+def ntuple_window_prove_limited(rows, lines, moves, state, window, L: int, M: int, table, max_nodes: int, first_limit: int = 0,
+                                growth: int = 0, gamma: float = 1.0, reward=(1.0, 0.0, 0.0), skip=None) -> dict:
+    """The rule of tpl_ntuple_window_prove_limited (include/tpl_learn.h): ntuple_window_prove with the search of every board
+    ntuple_exact_limited's.  Returns its dict with limit int32 [n], 0 where nothing was searched."""
+    return _ntuple_window_prove(rows, lines, moves, state, window, L, M, table, max_nodes, gamma, reward, skip, first_limit, growth)
+
+
+def _ntuple_window_prove(rows, lines, moves, state, window, L, M, table, max_nodes, gamma, reward, skip, first_limit, growth) -> dict:
     L, M = int(L), int(M)
     if not (1 <= L <= 250 and 1 <= M <= SOLVE_MAX_MOVES):
         raise ValueError(f"L and M must be in [1, 250] and [1, {SOLVE_MAX_MOVES}]")
@@ -1593,8 +1697,12 @@ def ntuple_window_prove(rows, lines, moves, state, window, L: int, M: int, table
         raise ValueError("gamma must be a number and reward three numbers (r_line, r_win, r_lose)") from None
     if len(values) != 4 or not all(np.isfinite(v) for v in values):
         raise ValueError("gamma and reward = (r_line, r_win, r_lose) must be finite (in float32)")
-    return _window_frame(rows, lines, moves, state, window, L, M, skip,
-                         lambda r, p, game_L, H: ntuple_exact(r, p, game_L, H, table, max_nodes, True, gamma, reward))
+    _limit_arguments(first_limit, growth)
+    out = _window_frame(rows, lines, moves, state, window, L, M, skip,
+                        lambda r, p, game_L, H: _ntuple_exact(r, p, game_L, H, table, max_nodes, True, gamma, reward, first_limit, growth))
+    if first_limit is not None:
+        out.setdefault("limit", np.zeros(out["solved"].shape[0], np.int32))
+    return out
 
 
 def ntuple_steps(error, rate) -> np.ndarray:

@@ -14,7 +14,9 @@
 // path is longer than the twelve window entries, so the stack is twelve records, 960 bytes of STATIC LDS, beside the twelve pieces of
 // the window, a byte each.  The wave unpacks its board from the two packed planes the beam kernels take.
 //
-// Built twice, as exact.hip is: as it stands on the twelve board features and through exact_window_move.hip on the fourteen.
+// Built twice, as exact.hip is: as it stands on the twelve board features and through exact_window_move.hip on the fourteen.  And
+// twice more with TPL_EXACT_LIMITED_UNIT (exact_window_limited.hip, exact_window_limited_move.hip), as exact.hip is and for its reason:
+// the same frame around the LIMITED search, placement_window_prove_limited[_move]_kernel behind tpl_placement_window_prove_limited[_move].
 #ifndef TPL_PLACEMENT_BOUND_UNIT
 #define TPL_PLACEMENT_BOUND_UNIT
 #endif
@@ -29,9 +31,15 @@ constexpr int kWindowWave = kExactWave;
 constexpr int kWindowDepth = tpl::kWindowEntries;             // 12: the longest horizon, and the plan's width
 static_assert(kWindowDepth == TPL_WINDOW_PLAN, "the plan is as wide as the window");
 
+#ifdef TPL_EXACT_LIMITED_UNIT
+#define TPL_WINDOW_KERNEL TPL_UNIT_PASTE4(placement_window_prove_limited, TPL_UNIT_FORM, , _kernel)
+#define TPL_WINDOW_ENTRY TPL_UNIT_PASTE4(tpl_placement_window_prove_limited, TPL_UNIT_FORM, , )
+#define TPL_WINDOW_ENTRY_NAME "tpl_placement_window_prove_limited" TPL_UNIT_FORM_NAME
+#else
 #define TPL_WINDOW_KERNEL TPL_UNIT_PASTE4(placement_window_prove, TPL_UNIT_FORM, , _kernel)
 #define TPL_WINDOW_ENTRY TPL_UNIT_PASTE4(tpl_placement_window_prove, TPL_UNIT_FORM, , )
 #define TPL_WINDOW_ENTRY_NAME "tpl_placement_window_prove" TPL_UNIT_FORM_NAME
+#endif
 
 struct WindowArgs {
     const uint4* a;              // [n]: the packed planes
@@ -51,12 +59,23 @@ struct WindowArgs {
     uint8_t* horizon;            // [n]: H
     uint8_t* verdict;            // [n]
 };
+#ifdef TPL_EXACT_LIMITED_UNIT
+// the limited entry's own record: the twin's, the two numbers of the limited search and its ninth output
+struct WindowLimitedArgs : WindowArgs {
+    uint32_t first_limit;        // in [0, 65535]: the K every budget starts with
+    uint32_t growth;             // 0: K + 1 ("add"); 1: max(1, 2 K) ("double")
+    int32_t* limit;              // [n]: the K of the last iteration begun, 0 where nothing was searched
+};
+using KernelArgs = WindowLimitedArgs;
+#else
+using KernelArgs = WindowArgs;
+#endif
 
 using Order = LinearOrder<kF>;
 using Stack = Frame<Order::Carry>;
 
 // one wave a workgroup, bound to eight waves a SIMD (tpl_exact.h says why)
-__global__ __launch_bounds__(kWindowWave, 8) void TPL_WINDOW_KERNEL(const WindowArgs p) {
+__global__ __launch_bounds__(kWindowWave, 8) void TPL_WINDOW_KERNEL(const KernelArgs p) {
     __shared__ Stack stack[kWindowDepth];
     __shared__ tpl::ShapeWord s_shape[32];
     __shared__ uint8_t s_pieces[16];
@@ -86,14 +105,19 @@ __global__ __launch_bounds__(kWindowWave, 8) void TPL_WINDOW_KERNEL(const Window
     }
 
     Found f;
-    f.nodes = 0u; f.length = 0u; f.last = kNoMove; f.capped = false;
+    f.nodes = 0u; f.length = 0u; f.last = kNoMove; f.capped = false; f.limit = 0u;
     if (live && !skipped) {
         if (lane < 32) s_shape[lane] = tpl::kShapeTable[lane];
         // window entry `lane`, masked as move_board masks it
         const unsigned long long window = ((unsigned long long)at.window_hi << 32) | at.window;
         if (lane < (uint32_t)kWindowDepth) s_pieces[lane] = (uint8_t)((uint32_t)(window >> (3u * lane)) & 7u);
         const Order order(p.weights, p.spare_weight);
+#ifdef TPL_EXACT_LIMITED_UNIT
+        f = search<Order, true>(order, stack, s_pieces, s_shape, root, need, L, H, p.max_nodes, 1u, lane,
+                                Discrepancy{p.first_limit, p.growth});                             // the game (L, H), shortest
+#else
         f = search(order, stack, s_pieces, s_shape, root, need, L, H, p.max_nodes, 1u, lane);      // the game (L, H), shortest
+#endif
     }
     const bool solved = f.length != 0u, proved = !skipped && !f.capped;
     if (lane == 0) {
@@ -105,6 +129,9 @@ __global__ __launch_bounds__(kWindowWave, 8) void TPL_WINDOW_KERNEL(const Window
                        : solved               ? (uint8_t)TPL_WINDOW_WIN
                        : proved && last_known ? (uint8_t)TPL_WINDOW_LOSS
                                               : (uint8_t)TPL_WINDOW_OPEN;
+#ifdef TPL_EXACT_LIMITED_UNIT
+        p.limit[i] = (int32_t)f.limit;
+#endif
     }
     write_path(stack, f, p.plan + (size_t)i * kWindowDepth, (uint32_t)kWindowDepth, lane);      // the plan
 }
@@ -115,9 +142,16 @@ __global__ __launch_bounds__(kWindowWave, 8) void TPL_WINDOW_KERNEL(const Window
 using namespace tpl_learn;
 
 extern "C" int TPL_WINDOW_ENTRY(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const float* weights,
-                                float spare_weight, int32_t max_nodes, const uint8_t* skip, uint8_t* solved, uint8_t* proved,
-                                int32_t* solution_len, uint8_t* plan, int32_t* bound, uint32_t* nodes, uint8_t* horizon,
-                                uint8_t* verdict, void* stream) {
+                                float spare_weight, int32_t max_nodes,
+#ifdef TPL_EXACT_LIMITED_UNIT
+                                int32_t first_limit, int32_t growth,
+#endif
+                                const uint8_t* skip, uint8_t* solved, uint8_t* proved, int32_t* solution_len, uint8_t* plan, int32_t* bound,
+                                uint32_t* nodes,
+#ifdef TPL_EXACT_LIMITED_UNIT
+                                int32_t* limit,
+#endif
+                                uint8_t* horizon, uint8_t* verdict, void* stream) {
     const char* name = TPL_WINDOW_ENTRY_NAME;
     if (!plane_a || !plane_b || !weights || !solved || !proved || !solution_len || !plan || !bound || !nodes || !horizon || !verdict)
         return fail_msg(TPL_ERR_ARG, "%s: null pointer (every argument but skip and the stream is required)", name);
@@ -127,7 +161,11 @@ extern "C" int TPL_WINDOW_ENTRY(const void* plane_a, const void* plane_b, int64_
         return fail_msg(TPL_ERR_ARG, "%s: planes must be 16-byte aligned", name);
     if ((uintptr_t)weights & 15u) return fail_msg(TPL_ERR_ARG, "%s: weights must be 16-byte aligned", name);
     if (const int rc = check_counts(name, solution_len, bound, nodes)) return rc;
-    WindowArgs p{};
+    KernelArgs p{};
+#ifdef TPL_EXACT_LIMITED_UNIT
+    if (const int rc = check_discrepancy(name, first_limit, growth, limit)) return rc;
+    p.first_limit = (uint32_t)first_limit; p.growth = (uint32_t)growth; p.limit = limit;
+#endif
     p.a = (const uint4*)plane_a; p.b = (const uint4*)plane_b; p.n = (uint32_t)n;
     p.L = (uint32_t)L; p.M = (uint32_t)M; p.weights = weights; p.spare_weight = spare_weight; p.max_nodes = (uint32_t)max_nodes;
     p.skip = skip;

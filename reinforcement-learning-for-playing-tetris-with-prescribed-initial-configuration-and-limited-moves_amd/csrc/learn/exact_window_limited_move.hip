@@ -1,0 +1,5 @@
+// exact_window_limited_move.hip -- exact_window_limited.hip on the fourteen features: tpl_placement_window_prove_limited_move.
+#define TPL_PLACEMENT_MOVE_UNIT
+#define TPL_PLACEMENT_BOUND_UNIT
+#define TPL_EXACT_LIMITED_UNIT
+#include "exact_window.hip"

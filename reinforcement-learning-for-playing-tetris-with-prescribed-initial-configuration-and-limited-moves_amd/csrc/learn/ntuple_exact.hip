@@ -16,6 +16,9 @@
 // a workgroup cannot afford a copy in LDS.  The order is a template over the geometry of tpl_ntuple.h, reached through ntuple_value<S>,
 // and each __global__ kernel names its geometry, as ntuple.hip's do.  The budget geometry hands ntuple_value the board and (L, B);
 // prune_dead is not called: bounded_move has already turned a dead child lost.
+//
+// Built once more with TPL_EXACT_LIMITED_UNIT (ntuple_exact_limited.hip), as exact.hip is and for its reason: the same frame around the
+// LIMITED search of tpl_exact.h, four kernels ntuple_exact*_limited_kernel behind tpl_ntuple_exact_limited.
 #ifndef TPL_PLACEMENT_BOUND_UNIT
 #define TPL_PLACEMENT_BOUND_UNIT
 #endif
@@ -42,6 +45,23 @@ struct NTupleExactArgs {
     int32_t* bound;              // [n]: need(root)
     uint32_t* nodes;             // [n]: expansions, all iterations
 };
+#ifdef TPL_EXACT_LIMITED_UNIT
+// the limited entry's own record: the twin's, the two numbers of the limited search and its seventh output
+struct NTupleExactLimitedArgs : NTupleExactArgs {
+    uint32_t first_limit;        // in [0, 65535]: the K every budget starts with
+    uint32_t growth;             // 0: K + 1 ("add"); 1: max(1, 2 K) ("double")
+    int32_t* limit;              // [n]: the K of the last iteration begun
+};
+using KernelArgs = NTupleExactLimitedArgs;
+#define TPL_KERNEL(stem) stem##_limited_kernel
+#define TPL_NTUPLE_EXACT_ENTRY tpl_ntuple_exact_limited
+#define TPL_NTUPLE_EXACT_ENTRY_NAME "tpl_ntuple_exact_limited"
+#else
+using KernelArgs = NTupleExactArgs;
+#define TPL_KERNEL(stem) stem##_kernel
+#define TPL_NTUPLE_EXACT_ENTRY tpl_ntuple_exact
+#define TPL_NTUPLE_EXACT_ENTRY_NAME "tpl_ntuple_exact"
+#endif
 
 // what the one-ply policy scores the move with: reward, or reward + gamma V where the child runs; every product and sum rounded once
 template <typename S>
@@ -77,7 +97,7 @@ using Stack = Frame<NoCarry>;
 // A wave's search is one long dependent chain, and here a trip to L2 or beyond is part of every link -- the table's gathers --, so what
 // hides it is other waves.
 template <typename S>
-__device__ __forceinline__ void ntuple_exact(const NTupleExactArgs& p) {
+__device__ __forceinline__ void ntuple_exact(const KernelArgs& p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
     Stack* const stack = reinterpret_cast<Stack*>(s_raw);      // [M]
     __shared__ tpl::ShapeWord s_shape[32];
@@ -93,13 +113,21 @@ __device__ __forceinline__ void ntuple_exact(const NTupleExactArgs& p) {
     const uint32_t bound = need_of(root, L);
 
     const TableOrder<S> order{p};
+#ifdef TPL_EXACT_LIMITED_UNIT
+    const Found f = search<TableOrder<S>, true>(order, stack, s_pieces, s_shape, root, bound, L, M, p.max_nodes, p.shortest, lane,
+                                                Discrepancy{p.first_limit, p.growth});
+#else
     const Found f = search(order, stack, s_pieces, s_shape, root, bound, L, M, p.max_nodes, p.shortest, lane);
+#endif
     if (lane == 0) {
         p.solved[i] = f.length != 0u ? (uint8_t)1 : (uint8_t)0;
         p.proved[i] = f.capped ? (uint8_t)0 : (uint8_t)1;
         p.solution_len[i] = (int32_t)f.length;
         p.bound[i] = (int32_t)bound;
         p.nodes[i] = f.nodes;
+#ifdef TPL_EXACT_LIMITED_UNIT
+        p.limit[i] = (int32_t)f.limit;
+#endif
     }
     write_path(stack, f, p.actions + (size_t)i * M, M, lane);
 }
@@ -107,21 +135,29 @@ __device__ __forceinline__ void ntuple_exact(const NTupleExactArgs& p) {
 // One wave a workgroup, each kernel bound to eight waves a SIMD, which every geometry fits without scratch: 55 VGPRs ("2x4"), 52
 // ("3x3"), 59 ("feat") and 60 ("feat+spare") of the 64 the bound allows, 78 SGPRs (tools/kernel_resources.sh;
 // profiles/learner/ntuple_exact_isa.log).
-__global__ __launch_bounds__(kExactWave, 8) void ntuple_exact_kernel(const NTupleExactArgs p) { ntuple_exact<Shape2x4>(p); }
-__global__ __launch_bounds__(kExactWave, 8) void ntuple_exact3_kernel(const NTupleExactArgs p) { ntuple_exact<Shape3x3>(p); }
-__global__ __launch_bounds__(kExactWave, 8) void ntuple_exact_feature_kernel(const NTupleExactArgs p) { ntuple_exact<FeatureTable>(p); }
-__global__ __launch_bounds__(kExactWave, 8) void ntuple_exact_budget_kernel(const NTupleExactArgs p) { ntuple_exact<BudgetTable>(p); }
+__global__ __launch_bounds__(kExactWave, 8) void TPL_KERNEL(ntuple_exact)(const KernelArgs p) { ntuple_exact<Shape2x4>(p); }
+__global__ __launch_bounds__(kExactWave, 8) void TPL_KERNEL(ntuple_exact3)(const KernelArgs p) { ntuple_exact<Shape3x3>(p); }
+__global__ __launch_bounds__(kExactWave, 8) void TPL_KERNEL(ntuple_exact_feature)(const KernelArgs p) { ntuple_exact<FeatureTable>(p); }
+__global__ __launch_bounds__(kExactWave, 8) void TPL_KERNEL(ntuple_exact_budget)(const KernelArgs p) { ntuple_exact<BudgetTable>(p); }
 
 }  // namespace
 }  // namespace tpl_learn
 
 using namespace tpl_learn;
 
-extern "C" int tpl_ntuple_exact(const int16_t* rows, const uint8_t* pieces, int64_t n, int32_t L, int32_t M, const int32_t* table,
-                                int64_t entries, float r_line, float r_win, float r_lose, float gamma, int32_t max_nodes,
-                                int32_t shortest, uint8_t* solved, uint8_t* proved, int32_t* solution_len, uint8_t* actions,
-                                int32_t* bound, uint32_t* nodes, void* stream) {
-    const char* name = "tpl_ntuple_exact";
+extern "C" int TPL_NTUPLE_EXACT_ENTRY(const int16_t* rows, const uint8_t* pieces, int64_t n, int32_t L, int32_t M, const int32_t* table,
+                                      int64_t entries, float r_line, float r_win, float r_lose, float gamma, int32_t max_nodes,
+                                      int32_t shortest,
+#ifdef TPL_EXACT_LIMITED_UNIT
+                                      int32_t first_limit, int32_t growth,
+#endif
+                                      uint8_t* solved, uint8_t* proved, int32_t* solution_len, uint8_t* actions, int32_t* bound,
+                                      uint32_t* nodes,
+#ifdef TPL_EXACT_LIMITED_UNIT
+                                      int32_t* limit,
+#endif
+                                      void* stream) {
+    const char* name = TPL_NTUPLE_EXACT_ENTRY_NAME;
     // a table of any other entry count is refused first, before any pointer is looked at
     if (entries != TPL_NTUPLE_ENTRIES && entries != TPL_NTUPLE_ENTRIES_3X3 && entries != TPL_NTUPLE_ENTRIES_FEAT &&
         entries != TPL_NTUPLE_ENTRIES_BUDGET)
@@ -140,7 +176,11 @@ extern "C" int tpl_ntuple_exact(const int16_t* rows, const uint8_t* pieces, int6
     if ((uintptr_t)rows & 1u) return fail_msg(TPL_ERR_ARG, "%s: rows must be 2-byte aligned", name);
     if ((uintptr_t)table & 3u) return fail_msg(TPL_ERR_ARG, "%s: table must be 4-byte aligned", name);
     if (const int rc = check_counts(name, solution_len, bound, nodes)) return rc;
-    NTupleExactArgs p{};
+    KernelArgs p{};
+#ifdef TPL_EXACT_LIMITED_UNIT
+    if (const int rc = check_discrepancy(name, first_limit, growth, limit)) return rc;
+    p.first_limit = (uint32_t)first_limit; p.growth = (uint32_t)growth; p.limit = limit;
+#endif
     p.rows = (const uint16_t*)rows; p.pieces = pieces; p.n = (uint32_t)n;
     p.L = (uint32_t)L; p.M = (uint32_t)M; p.table = table;
     p.r_line = r_line; p.r_win = r_win; p.r_lose = r_lose; p.gamma = gamma;
@@ -148,10 +188,11 @@ extern "C" int tpl_ntuple_exact(const int16_t* rows, const uint8_t* pieces, int6
     p.solved = solved; p.proved = proved; p.solution_len = solution_len; p.actions = actions; p.bound = bound; p.nodes = nodes;
     const size_t stack = sizeof(Stack) * (size_t)p.M;          // at most 20,320 bytes
     const dim3 grid(p.n), block(kExactWave);
-    if (entries == TPL_NTUPLE_ENTRIES) hipLaunchKernelGGL(ntuple_exact_kernel, grid, block, stack, (hipStream_t)stream, p);
-    else if (entries == TPL_NTUPLE_ENTRIES_3X3) hipLaunchKernelGGL(ntuple_exact3_kernel, grid, block, stack, (hipStream_t)stream, p);
-    else if (entries == TPL_NTUPLE_ENTRIES_FEAT) hipLaunchKernelGGL(ntuple_exact_feature_kernel, grid, block, stack, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(ntuple_exact_budget_kernel, grid, block, stack, (hipStream_t)stream, p);
+    if (entries == TPL_NTUPLE_ENTRIES) hipLaunchKernelGGL(TPL_KERNEL(ntuple_exact), grid, block, stack, (hipStream_t)stream, p);
+    else if (entries == TPL_NTUPLE_ENTRIES_3X3) hipLaunchKernelGGL(TPL_KERNEL(ntuple_exact3), grid, block, stack, (hipStream_t)stream, p);
+    else if (entries == TPL_NTUPLE_ENTRIES_FEAT)
+        hipLaunchKernelGGL(TPL_KERNEL(ntuple_exact_feature), grid, block, stack, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(TPL_KERNEL(ntuple_exact_budget), grid, block, stack, (hipStream_t)stream, p);
     TPL_LEARN_HIP(hipGetLastError());
     return TPL_OK;
 }

@@ -15,6 +15,9 @@
 // The search, its mapping and its stack record are tpl_exact.h's.  ONE BOARD PER WAVEFRONT; STATIC LDS: twelve stack records of 80 bytes,
 // the shape table and sixteen bytes of pieces.  The table stays in global memory, as in ntuple_exact.hip and for its reason.  The order
 // is a template over the geometry of tpl_ntuple.h and each __global__ kernel names its geometry.
+//
+// Built once more with TPL_EXACT_LIMITED_UNIT (ntuple_window_limited.hip), as exact.hip is and for its reason: the same frame around the
+// LIMITED search of tpl_exact.h, four kernels ntuple_window*_limited_kernel behind tpl_ntuple_window_prove_limited.
 #ifndef TPL_PLACEMENT_BOUND_UNIT
 #define TPL_PLACEMENT_BOUND_UNIT
 #endif
@@ -49,6 +52,23 @@ struct NTupleWindowArgs {
     uint8_t* horizon;            // [n]: H
     uint8_t* verdict;            // [n]
 };
+#ifdef TPL_EXACT_LIMITED_UNIT
+// the limited entry's own record: the twin's, the two numbers of the limited search and its ninth output
+struct NTupleWindowLimitedArgs : NTupleWindowArgs {
+    uint32_t first_limit;        // in [0, 65535]: the K every budget starts with
+    uint32_t growth;             // 0: K + 1 ("add"); 1: max(1, 2 K) ("double")
+    int32_t* limit;              // [n]: the K of the last iteration begun, 0 where nothing was searched
+};
+using KernelArgs = NTupleWindowLimitedArgs;
+#define TPL_KERNEL(stem) stem##_limited_kernel
+#define TPL_NTUPLE_WINDOW_ENTRY tpl_ntuple_window_prove_limited
+#define TPL_NTUPLE_WINDOW_ENTRY_NAME "tpl_ntuple_window_prove_limited"
+#else
+using KernelArgs = NTupleWindowArgs;
+#define TPL_KERNEL(stem) stem##_kernel
+#define TPL_NTUPLE_WINDOW_ENTRY tpl_ntuple_window_prove
+#define TPL_NTUPLE_WINDOW_ENTRY_NAME "tpl_ntuple_window_prove"
+#endif
 
 // what the one-ply policy scores the move with: reward, or reward + gamma V where the child runs; every product and sum rounded once
 template <typename S>
@@ -82,7 +102,7 @@ struct TableOrder {
 using Stack = Frame<NoCarry>;
 
 template <typename S>
-__device__ __forceinline__ void ntuple_window(const NTupleWindowArgs& p) {
+__device__ __forceinline__ void ntuple_window(const KernelArgs& p) {
     __shared__ Stack stack[kWindowDepth];
     __shared__ tpl::ShapeWord s_shape[32];
     __shared__ uint8_t s_pieces[kWindowList];
@@ -112,14 +132,19 @@ __device__ __forceinline__ void ntuple_window(const NTupleWindowArgs& p) {
     }
 
     Found f;
-    f.nodes = 0u; f.length = 0u; f.last = kNoMove; f.capped = false;
+    f.nodes = 0u; f.length = 0u; f.last = kNoMove; f.capped = false; f.limit = 0u;
     if (live && !skipped) {
         if (lane < 32) s_shape[lane] = tpl::kShapeTable[lane];
         // list entry `lane`: the window's, masked as move_board masks it, below the horizon and 0 from it on
         const unsigned long long window = ((unsigned long long)at.window_hi << 32) | at.window;
         if (lane < (uint32_t)kWindowList) s_pieces[lane] = lane < H ? (uint8_t)((uint32_t)(window >> (3u * lane)) & 7u) : (uint8_t)0;
         const TableOrder<S> order{p};
+#ifdef TPL_EXACT_LIMITED_UNIT
+        f = search<TableOrder<S>, true>(order, stack, s_pieces, s_shape, root, need, L, H, p.max_nodes, 1u, lane,
+                                        Discrepancy{p.first_limit, p.growth});                     // the game (L, H), shortest
+#else
         f = search(order, stack, s_pieces, s_shape, root, need, L, H, p.max_nodes, 1u, lane);      // the game (L, H), shortest
+#endif
     }
     const bool solved = f.length != 0u, proved = !skipped && !f.capped;
     if (lane == 0) {
@@ -131,26 +156,36 @@ __device__ __forceinline__ void ntuple_window(const NTupleWindowArgs& p) {
                        : solved               ? (uint8_t)TPL_WINDOW_WIN
                        : proved && last_known ? (uint8_t)TPL_WINDOW_LOSS
                                               : (uint8_t)TPL_WINDOW_OPEN;
+#ifdef TPL_EXACT_LIMITED_UNIT
+        p.limit[i] = (int32_t)f.limit;
+#endif
     }
     write_path(stack, f, p.plan + (size_t)i * kWindowDepth, (uint32_t)kWindowDepth, lane);      // the plan
 }
 
 // one wave a workgroup, each kernel bound to eight waves a SIMD (tpl_exact.h says why; here a trip to L2 is part of every link)
-__global__ __launch_bounds__(kWindowWave, 8) void ntuple_window_kernel(const NTupleWindowArgs p) { ntuple_window<Shape2x4>(p); }
-__global__ __launch_bounds__(kWindowWave, 8) void ntuple_window3_kernel(const NTupleWindowArgs p) { ntuple_window<Shape3x3>(p); }
-__global__ __launch_bounds__(kWindowWave, 8) void ntuple_window_feature_kernel(const NTupleWindowArgs p) { ntuple_window<FeatureTable>(p); }
-__global__ __launch_bounds__(kWindowWave, 8) void ntuple_window_budget_kernel(const NTupleWindowArgs p) { ntuple_window<BudgetTable>(p); }
+__global__ __launch_bounds__(kWindowWave, 8) void TPL_KERNEL(ntuple_window)(const KernelArgs p) { ntuple_window<Shape2x4>(p); }
+__global__ __launch_bounds__(kWindowWave, 8) void TPL_KERNEL(ntuple_window3)(const KernelArgs p) { ntuple_window<Shape3x3>(p); }
+__global__ __launch_bounds__(kWindowWave, 8) void TPL_KERNEL(ntuple_window_feature)(const KernelArgs p) { ntuple_window<FeatureTable>(p); }
+__global__ __launch_bounds__(kWindowWave, 8) void TPL_KERNEL(ntuple_window_budget)(const KernelArgs p) { ntuple_window<BudgetTable>(p); }
 
 }  // namespace
 }  // namespace tpl_learn
 
 using namespace tpl_learn;
 
-extern "C" int tpl_ntuple_window_prove(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const int32_t* table,
+extern "C" int TPL_NTUPLE_WINDOW_ENTRY(const void* plane_a, const void* plane_b, int64_t n, int32_t L, int32_t M, const int32_t* table,
                                        int64_t entries, float r_line, float r_win, float r_lose, float gamma, int32_t max_nodes,
+#ifdef TPL_EXACT_LIMITED_UNIT
+                                       int32_t first_limit, int32_t growth,
+#endif
                                        const uint8_t* skip, uint8_t* solved, uint8_t* proved, int32_t* solution_len, uint8_t* plan,
-                                       int32_t* bound, uint32_t* nodes, uint8_t* horizon, uint8_t* verdict, void* stream) {
-    const char* name = "tpl_ntuple_window_prove";
+                                       int32_t* bound, uint32_t* nodes,
+#ifdef TPL_EXACT_LIMITED_UNIT
+                                       int32_t* limit,
+#endif
+                                       uint8_t* horizon, uint8_t* verdict, void* stream) {
+    const char* name = TPL_NTUPLE_WINDOW_ENTRY_NAME;
     // a table of any other entry count is refused first, before any pointer is looked at (tpl_ntuple_exact's message)
     if (entries != TPL_NTUPLE_ENTRIES && entries != TPL_NTUPLE_ENTRIES_3X3 && entries != TPL_NTUPLE_ENTRIES_FEAT &&
         entries != TPL_NTUPLE_ENTRIES_BUDGET)
@@ -169,7 +204,11 @@ extern "C" int tpl_ntuple_window_prove(const void* plane_a, const void* plane_b,
         return fail_msg(TPL_ERR_ARG, "%s: planes must be 16-byte aligned", name);
     if ((uintptr_t)table & 3u) return fail_msg(TPL_ERR_ARG, "%s: table must be 4-byte aligned", name);
     if (const int rc = check_counts(name, solution_len, bound, nodes)) return rc;
-    NTupleWindowArgs p{};
+    KernelArgs p{};
+#ifdef TPL_EXACT_LIMITED_UNIT
+    if (const int rc = check_discrepancy(name, first_limit, growth, limit)) return rc;
+    p.first_limit = (uint32_t)first_limit; p.growth = (uint32_t)growth; p.limit = limit;
+#endif
     p.a = (const uint4*)plane_a; p.b = (const uint4*)plane_b; p.n = (uint32_t)n;
     p.L = (uint32_t)L; p.M = (uint32_t)M; p.table = table;
     p.r_line = r_line; p.r_win = r_win; p.r_lose = r_lose; p.gamma = gamma;
@@ -177,10 +216,11 @@ extern "C" int tpl_ntuple_window_prove(const void* plane_a, const void* plane_b,
     p.solved = solved; p.proved = proved; p.solution_len = solution_len; p.plan = plan; p.bound = bound; p.nodes = nodes;
     p.horizon = horizon; p.verdict = verdict;
     const dim3 grid(p.n), block(kWindowWave);
-    if (entries == TPL_NTUPLE_ENTRIES) hipLaunchKernelGGL(ntuple_window_kernel, grid, block, 0, (hipStream_t)stream, p);
-    else if (entries == TPL_NTUPLE_ENTRIES_3X3) hipLaunchKernelGGL(ntuple_window3_kernel, grid, block, 0, (hipStream_t)stream, p);
-    else if (entries == TPL_NTUPLE_ENTRIES_FEAT) hipLaunchKernelGGL(ntuple_window_feature_kernel, grid, block, 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(ntuple_window_budget_kernel, grid, block, 0, (hipStream_t)stream, p);
+    if (entries == TPL_NTUPLE_ENTRIES) hipLaunchKernelGGL(TPL_KERNEL(ntuple_window), grid, block, 0, (hipStream_t)stream, p);
+    else if (entries == TPL_NTUPLE_ENTRIES_3X3) hipLaunchKernelGGL(TPL_KERNEL(ntuple_window3), grid, block, 0, (hipStream_t)stream, p);
+    else if (entries == TPL_NTUPLE_ENTRIES_FEAT)
+        hipLaunchKernelGGL(TPL_KERNEL(ntuple_window_feature), grid, block, 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(TPL_KERNEL(ntuple_window_budget), grid, block, 0, (hipStream_t)stream, p);
     TPL_LEARN_HIP(hipGetLastError());
     return TPL_OK;
 }

@@ -1,0 +1,4 @@
+// ntuple_window_limited.hip -- ntuple_window.hip once more, around the limited-discrepancy search: tpl_ntuple_window_prove_limited
+// (include/tpl_learn.h states the rule; exact.hip says why this is a unit of its own).
+#define TPL_EXACT_LIMITED_UNIT
+#include "ntuple_window.hip"

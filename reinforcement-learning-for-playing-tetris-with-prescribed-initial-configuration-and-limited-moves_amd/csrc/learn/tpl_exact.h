@@ -119,96 +119,128 @@ struct LinearOrder {
 struct Found {
     uint32_t nodes, length, last;                             // expansions, all iterations; the winning length, 0 if none, and its last move
     bool capped;
+    uint32_t limit;                                           // the limited search alone: the K of the last iteration begun, 0 if none
 };
+
+// The LIMITED search's two numbers (include/tpl_learn.h: tpl_placement_exact_limited): the first discrepancy limit of every budget and
+// how the limit grows, 0 by one ("add"), 1 by doubling ("double").  The plain search takes none.
+struct Discrepancy {
+    uint32_t first, growth;
+};
+constexpr uint32_t kLimitTop = 65535u;                        // K's clamp; a K >= 8,382 never cuts, so the clamp ends nothing
 
 // The search of the game (L, M) from `root` -- 0 lines, 0 moves -- whose piece at depth d is s_pieces[d]; every argument is the same
 // in every lane.  `need` is need(root), and need > M is decided without a node.  The caller has filled s_shape and s_pieces, entries
 // 0 .. M.  On return the path of a win is in the stack: the child in hand at every depth, then `last`.
-template <typename Order>
+//
+// Limited = true is the limited-discrepancy order: an iteration is (B, K), the game (L, B) searched with at most K steps off the
+// order on a path.  A node holds `rem`, what is left of K on the path to it: of its running children those of rank <= rem are kept,
+// the one of rank j is searched with rem - j, and a dropped child sets `cut`.  A budget's iterations go on from a fresh root with the
+// next K until one cuts nothing -- that one has visited what the plain iteration visits.  rem, K and cut are the same in every lane
+// and stay in SGPRs; a record keeps its rem in the upper half of `count`, which is 34 at most, so a record stays 80 bytes.
+template <typename Order, bool Limited = false>
 __device__ __forceinline__ Found search(const Order& order, Frame<typename Order::Carry>* stack, const uint8_t* s_pieces,
                                         const tpl::ShapeWord* s_shape, const tpl::Board& root, uint32_t need, uint32_t L, uint32_t M,
-                                        uint32_t max_nodes, uint32_t shortest, uint32_t lane) {
+                                        uint32_t max_nodes, uint32_t shortest, uint32_t lane, Discrepancy disc = Discrepancy{0u, 0u}) {
     using Carry = typename Order::Carry;
     uint32_t nodes = 0u, length = 0u, last = kNoMove;
     bool capped = false;
+    uint32_t limit = 0u;
     if (need <= M) {
 #pragma unroll 1
         for (uint32_t B = shortest ? need : M; B <= M && length == 0u && !capped; ++B) {
-            wave_sync();                                       // the last iteration's reads of record 0 (and, the first time, the tables)
-            if (lane == 0) store_frame(stack[0], root, Carry{});
-            wave_sync();
-            uint32_t d = 0u;
+            uint32_t K = disc.first;                           // Limited: every budget starts at the first limit
 #pragma unroll 1
-            for (;;) {
-                // expand the node at depth d
-                if (nodes == max_nodes) { capped = true; break; }
-                ++nodes;
-                const uint32_t cur = uniform(s_pieces[d]);
-                const uint32_t stride = placement_count(cur);
-                const bool mine = lane < stride;
-                const uint32_t k = mine ? lane : 0u;
-                uint32_t r, l;
-                const uint32_t b = nth_placement(cur, k, r, l);
-                tpl::Board s;
-                Carry carry;
-                const float value = order.child(stack[d], cur, s_pieces + d + 1u, r, l, s_shape, L, B, s, carry);
-                const uint32_t key_hi = ordered_bits(value), key_lo = kSlotTop - k;
-                const bool won = mine && s.state == tpl::ST_WON, running = mine && s.state == tpl::ST_RUNNING;
-
-                // the stop: the won child that comes first in the order
-                if (__ballot(won) != 0ull) {
-                    const unsigned long long top = wave_max(won ? ((unsigned long long)key_hi << 32) | key_lo : 0ull);
-                    uint32_t r2, l2;
-                    last = nth_placement(cur, kSlotTop - uniform((uint32_t)top), r2, l2);
-                    length = d + 1u;
-                    break;
-                }
-
-                // the order of the running children: a child's rank is the number of running children with a larger key
-                const uint32_t run_hi = running ? key_hi : 0u, run_lo = running ? key_lo : 0u;
-                const unsigned long long run_key = ((unsigned long long)run_hi << 32) | run_lo;
-                uint32_t rank = 0u;
-#pragma unroll
-                for (int j = 0; j < kMaxPlacements; ++j) {
-                    const unsigned long long other = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)run_hi, j) << 32) |
-                                                     (uint32_t)__builtin_amdgcn_readlane((int)run_lo, j);
-                    rank += other > run_key ? 1u : 0u;
-                }
-                const uint32_t count = (uint32_t)__builtin_popcountll(__ballot(running));
-                if (running) {
-                    stack[d].kids[rank] = (uint8_t)b;
-                    if (rank == 0u && d + 1u < M) store_frame(stack[d + 1u], s, carry);      // descended into at once (d + 1 < B <= M)
-                }
-                if (lane == 0) {
-                    stack[d].count = count;
-                    stack[d].cursor = count != 0u ? 1u : 0u;
-                }
+            for (;;) {                                         // Limited: the iterations (B, K) of one budget; the plain search has one
+                bool cut = false;
+                uint32_t rem = K;                              // of the node at depth d
+                if constexpr (Limited) limit = K;
+                wave_sync();                                   // the last iteration's reads of record 0 (and, the first time, the tables)
+                if (lane == 0) store_frame(stack[0], root, Carry{});
                 wave_sync();
-                if (count != 0u) { ++d; continue; }
-
-                // no running child: back to the nearest node that has one left, and into it
-                bool more = false;
+                uint32_t d = 0u;
 #pragma unroll 1
-                while (d > 0u) {
-                    --d;
-                    const uint32_t at = uniform(stack[d].cursor);
-                    if (at < uniform(stack[d].count)) {
-                        const uint32_t b2 = uniform(stack[d].kids[at]);
-                        tpl::Board s2;
-                        Carry carry2;
-                        order.child(stack[d], uniform(s_pieces[d]), s_pieces + d + 1u, b2 / 10u, b2 % 10u, s_shape, L, B, s2, carry2);
-                        wave_sync();
-                        if (lane == 0 && d + 1u < M) {
-                            stack[d].cursor = at + 1u;
-                            store_frame(stack[d + 1u], s2, carry2);
-                        }
-                        wave_sync();
-                        ++d;
-                        more = true;
+                for (;;) {
+                    // expand the node at depth d
+                    if (nodes == max_nodes) { capped = true; break; }
+                    ++nodes;
+                    const uint32_t cur = uniform(s_pieces[d]);
+                    const uint32_t stride = placement_count(cur);
+                    const bool mine = lane < stride;
+                    const uint32_t k = mine ? lane : 0u;
+                    uint32_t r, l;
+                    const uint32_t b = nth_placement(cur, k, r, l);
+                    tpl::Board s;
+                    Carry carry;
+                    const float value = order.child(stack[d], cur, s_pieces + d + 1u, r, l, s_shape, L, B, s, carry);
+                    const uint32_t key_hi = ordered_bits(value), key_lo = kSlotTop - k;
+                    const bool won = mine && s.state == tpl::ST_WON, running = mine && s.state == tpl::ST_RUNNING;
+
+                    // the stop: the won child that comes first in the order
+                    if (__ballot(won) != 0ull) {
+                        const unsigned long long top = wave_max(won ? ((unsigned long long)key_hi << 32) | key_lo : 0ull);
+                        uint32_t r2, l2;
+                        last = nth_placement(cur, kSlotTop - uniform((uint32_t)top), r2, l2);
+                        length = d + 1u;
                         break;
                     }
+
+                    // the order of the running children: a child's rank is the number of running children with a larger key
+                    const uint32_t run_hi = running ? key_hi : 0u, run_lo = running ? key_lo : 0u;
+                    const unsigned long long run_key = ((unsigned long long)run_hi << 32) | run_lo;
+                    uint32_t rank = 0u;
+#pragma unroll
+                    for (int j = 0; j < kMaxPlacements; ++j) {
+                        const unsigned long long other = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)run_hi, j) << 32) |
+                                                         (uint32_t)__builtin_amdgcn_readlane((int)run_lo, j);
+                        rank += other > run_key ? 1u : 0u;
+                    }
+                    uint32_t count = (uint32_t)__builtin_popcountll(__ballot(running));
+                    if constexpr (Limited) {                   // the children of rank <= rem are kept; a dropped one is a cut
+                        if (count > rem + 1u) { count = rem + 1u; cut = true; }
+                    }
+                    if (running && (!Limited || rank < count)) {
+                        stack[d].kids[rank] = (uint8_t)b;
+                        if (rank == 0u && d + 1u < M) store_frame(stack[d + 1u], s, carry);  // descended into at once (d + 1 < B <= M)
+                    }
+                    if (lane == 0) {
+                        stack[d].count = Limited ? count | (rem << 16) : count;
+                        stack[d].cursor = count != 0u ? 1u : 0u;
+                    }
+                    wave_sync();
+                    if (count != 0u) { ++d; continue; }        // Limited: the child of rank 0 keeps the node's rem
+
+                    // no running child: back to the nearest node that has one left, and into it
+                    bool more = false;
+#pragma unroll 1
+                    while (d > 0u) {
+                        --d;
+                        const uint32_t at = uniform(stack[d].cursor);
+                        const uint32_t word = uniform(stack[d].count);
+                        if (at < (Limited ? word & 0xFFFFu : word)) {
+                            if constexpr (Limited) rem = (word >> 16) - at;  // the child of rank `at`: at < count <= rem + 1
+                            const uint32_t b2 = uniform(stack[d].kids[at]);
+                            tpl::Board s2;
+                            Carry carry2;
+                            order.child(stack[d], uniform(s_pieces[d]), s_pieces + d + 1u, b2 / 10u, b2 % 10u, s_shape, L, B, s2, carry2);
+                            wave_sync();
+                            if (lane == 0 && d + 1u < M) {
+                                stack[d].cursor = at + 1u;
+                                store_frame(stack[d + 1u], s2, carry2);
+                            }
+                            wave_sync();
+                            ++d;
+                            more = true;
+                            break;
+                        }
+                    }
+                    if (!more) break;                          // the root's children are used up: no win at this budget
                 }
-                if (!more) break;                              // the root's children are used up: no win at this budget
+                if constexpr (!Limited) break;
+                else {
+                    if (!cut || capped || length != 0u) break;     // nothing dropped: (L, B) is searched out -- or the search is over
+                    K = min(disc.growth != 0u ? max(1u, 2u * K) : K + 1u, kLimitTop);
+                }
             }
         }
     }
@@ -218,6 +250,7 @@ __device__ __forceinline__ Found search(const Order& order, Frame<typename Order
     out.length = capped ? 0u : length;
     out.last = last;
     out.capped = capped;
+    out.limit = limit;
     return out;
 }
 
@@ -250,6 +283,16 @@ inline int check_counts(const char* name, const int32_t* solution_len, const int
     if ((uintptr_t)solution_len & 3u) return fail_msg(TPL_ERR_ARG, "%s: solution_len must be 4-byte aligned", name);
     if ((uintptr_t)bound & 3u) return fail_msg(TPL_ERR_ARG, "%s: bound must be 4-byte aligned", name);
     if ((uintptr_t)nodes & 3u) return fail_msg(TPL_ERR_ARG, "%s: nodes must be 4-byte aligned", name);
+    return TPL_OK;
+}
+
+// what every limited entry refuses of its own three arguments, after its twin's checks of n, the game and the node budget
+inline int check_discrepancy(const char* name, int32_t first_limit, int32_t growth, const int32_t* limit) {
+    if (first_limit < 0 || first_limit > (int32_t)kLimitTop)
+        return fail_msg(TPL_ERR_ARG, "%s: first_limit must be in [0, %d]", name, (int)kLimitTop);
+    if (growth != 0 && growth != 1) return fail_msg(TPL_ERR_ARG, "%s: growth must be 0 (add) or 1 (double)", name);
+    if (!limit) return fail_msg(TPL_ERR_ARG, "%s: null pointer (limit is required)", name);
+    if ((uintptr_t)limit & 3u) return fail_msg(TPL_ERR_ARG, "%s: limit must be 4-byte aligned", name);
     return TPL_OK;
 }
 

@@ -279,7 +279,7 @@ def _win_count_reward(env) -> None:
 @torch.no_grad()
 def evaluate_heuristic(env, weights, boards_per_member: Optional[int], steps: int, policy=None, depth: int = 1,
                        width: Optional[int] = None, bound: bool = False, spare_weight: float = 0.0, per_config: bool = False,
-                       proof: Optional[int] = None, proof_table=None) -> dict:
+                       proof: Optional[int] = None, proof_table=None, proof_discrepancy=None) -> dict:
     """Play `steps` steps of the population `weights` ([P, 12] or [12]) on `env` from a full reset: an auto-reset environment
     with a configuration pool and reward parameters (0, 1, 0), so that the summed reward is the number of wins.  Member p plays
     boards [p * boards_per_member, (p + 1) * boards_per_member).  Returns episodes and wins as int64 numpy arrays [P] and
@@ -294,16 +294,21 @@ def evaluate_heuristic(env, weights, boards_per_member: Optional[int], steps: in
     move of a plan that the exact search over the state's window proves winning, the policy's own move elsewhere; the dict gains
     proof, that policy's stats().  None leaves every result as it is.
     proof_table: None or False, or with `proof` an n-tuple table of one of the four plain forms (solve.ntuple_window_prove's): the proofs are
-    then ordered by it (gamma 1, reward (1, 0, 0)) instead of the classical weights.  It only orders the search."""
+    then ordered by it (gamma 1, reward (1, 0, 0)) instead of the classical weights.  It only orders the search.
+    proof_discrepancy: None, or with `proof` "add" or "double" -- ProofPolicy's discrepancy: the proofs are searched in
+    limited-discrepancy order from first_limit 0.  It changes which proofs fit the node budget, and nothing a proof promises."""
     if not isinstance(per_config, bool):
         raise ValueError("per_config must be True or False")
     if proof_table is False:                                   # NTupleLearner.evaluate's default: the classical order
         proof_table = None
     if proof is None and proof_table is not None:
         raise ValueError("proof_table orders the proofs: it needs proof, a node budget")
+    if proof is None and proof_discrepancy is not None:
+        raise ValueError("proof_discrepancy orders the proofs: it needs proof, a node budget")
     if proof is not None:
-        from .solve import _max_nodes
+        from .solve import _discrepancy, _max_nodes
         proof = _max_nodes(proof)
+        _discrepancy(proof_discrepancy, 0)
     kind, depth, width = _player(depth, width)
     bound, spare_weight = _player_bound(width, bound, spare_weight)
     if policy is not None:
@@ -331,8 +336,10 @@ def evaluate_heuristic(env, weights, boards_per_member: Optional[int], steps: in
     player = policy
     if proof is not None:
         from .solve import ProofPolicy
-        player = ProofPolicy(env, policy, max_nodes=proof) if proof_table is None else \
-            ProofPolicy(env, policy, max_nodes=proof, table=proof_table)
+        order = {} if proof_table is None else dict(table=proof_table)
+        if proof_discrepancy is not None:                      # only then a LimitedProofPolicy
+            order["discrepancy"] = proof_discrepancy
+        player = ProofPolicy(env, policy, max_nodes=proof, **order)
     n, d = env.num_envs, env.device
     action = torch.empty(n, dtype=torch.uint8, device=d)
     reward = torch.empty(n, dtype=torch.float32, device=d)

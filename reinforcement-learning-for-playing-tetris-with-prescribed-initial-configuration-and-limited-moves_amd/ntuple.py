@@ -829,7 +829,7 @@ class NTupleLearner:
 
     @torch.no_grad()
     def evaluate(self, steps: int, depth: Optional[int] = None, width: Optional[int] = None, bound: Optional[bool] = None,
-                 per_config: bool = False, proof: Optional[int] = None, proof_table=False) -> dict:
+                 per_config: bool = False, proof: Optional[int] = None, proof_table=False, proof_discrepancy=None) -> dict:
         """Play `steps` greedy steps from a full reset and count: episodes (the steps' done flags), wins (the afterstates of the
         moves played whose state is "won": every reward parameter counts the same wins) and win_rate = wins / max(episodes, 1).
         depth: how deep the greedy policy searches -- None: the learner's own; 1 or 2 plays the table as it stands at that depth.
@@ -845,7 +845,9 @@ class NTupleLearner:
         proof_table: False or None -- the proofs are ordered by the classical weights --, True -- by the learner's own table as it
         stands, with the learner's gamma and the environment's reward; refused where the table is not of one of the four plain forms
         "2x4", "3x3", "feat", "feat+spare" --, or a table of one of those forms, used as given with gamma 1 and reward (1, 0, 0)
-        (solve.ntuple_window_prove).  It only orders the search, and needs `proof`."""
+        (solve.ntuple_window_prove).  It only orders the search, and needs `proof`.
+        proof_discrepancy: None, or with `proof` "add" or "double" -- ProofPolicy's discrepancy: the proofs are searched in
+        limited-discrepancy order from first_limit 0.  It changes which proofs fit the node budget, and nothing a proof promises."""
         if not isinstance(per_config, bool):
             raise ValueError("per_config must be True or False")
         ordered = proof_table is not None and proof_table is not False
@@ -861,9 +863,14 @@ class NTupleLearner:
             order = dict(table=self.table, gamma=self.greedy.gamma, reward=tuple(float(v) for v in self.env.reward_params))
         elif ordered:
             order = dict(table=proof_table)
+        if proof is None and proof_discrepancy is not None:
+            raise ValueError("proof_discrepancy orders the proofs: it needs proof, a node budget")
         if proof is not None:
-            from .solve import ProofPolicy, _max_nodes
+            from .solve import ProofPolicy, _discrepancy, _max_nodes
             proof = _max_nodes(proof)
+            _discrepancy(proof_discrepancy, 0)
+            if proof_discrepancy is not None:                  # only then a LimitedProofPolicy
+                order["discrepancy"] = proof_discrepancy
         steps = _count("steps", steps, 1)
         env, d = self.env, self.env.device
         greedy = self.greedy

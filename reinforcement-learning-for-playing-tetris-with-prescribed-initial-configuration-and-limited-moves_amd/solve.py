@@ -42,7 +42,8 @@ from ._learn_lib import BEAM_MAX_WIDTH, EXACT_MAX_NODES, NUM_FEATURES, NUM_MOVE_
 
 __all__ = ["CLASSICAL_WEIGHTS", "solve_configs", "prove_configs", "ntuple_prove_configs", "tighten_pool", "config_bound",
            "prove_nodes", "label_moves", "label_states", "blunders", "LabelSet", "collect_labels", "label_agreement", "window_prove",
-           "ProofPolicy", "ntuple_window_prove", "TableProofPolicy"]
+           "ProofPolicy", "ntuple_window_prove", "TableProofPolicy", "prove_configs_limited", "ntuple_prove_configs_limited",
+           "window_prove_limited", "ntuple_window_prove_limited", "LimitedProofPolicy"]
 
 # cleared, won, lost, holes, aggregate height, max height, bumpiness, row and column transitions, wells, rows with holes, hole depth:
 # the classical signs, a sensible default for the supply (0.99925 of a carved L = 10 / M = 40 pool at one ply)
@@ -240,6 +241,17 @@ def _max_nodes(max_nodes) -> int:
     return int(max_nodes)
 
 
+def _discrepancy(discrepancy, first_limit):
+    """(growth, first_limit) of a limited search, or None for discrepancy=None, the plain one.  discrepancy is None, "add" or
+    "double"; first_limit an integer in [0, 65535], looked at in every case."""
+    from ._learn_lib import DISCREPANCY_GROWTH, LIMIT_TOP
+    if discrepancy is not None and (not isinstance(discrepancy, str) or discrepancy not in DISCREPANCY_GROWTH):
+        raise ValueError(f'discrepancy must be None, "add" or "double", got {discrepancy!r}')
+    if isinstance(first_limit, bool) or not isinstance(first_limit, (int, np.integer)) or not 0 <= int(first_limit) <= LIMIT_TOP:
+        raise ValueError(f"first_limit must be an integer in [0, {LIMIT_TOP}], got {first_limit!r}")
+    return None if discrepancy is None else (DISCREPANCY_GROWTH[discrepancy], int(first_limit))
+
+
 def prove_configs(rows, pieces, L: int, M: int, weights=None, max_nodes: int = 1 << 16, shortest: bool = True,
                   spare_weight: float = 0.0, device="cuda:0", validate: bool = True) -> dict:
     """Search every configuration's whole game depth first and exactly (the rule: include/tpl_learn.h, tpl_placement_exact;
@@ -260,6 +272,26 @@ def prove_configs(rows, pieces, L: int, M: int, weights=None, max_nodes: int = 1
     sequence of placements wins within M moves, and with shortest=True solved[i] = True a proof that solution_len[i] is the shortest
     there is.  solved[i] = True always comes with proved[i].  Without proved[i] NOTHING is proved, neither way.**
     No host wait except the piece-id check, which validate=False skips."""
+    return _prove_configs(rows, pieces, L, M, weights, max_nodes, shortest, spare_weight, device, validate, None, 0)
+
+
+def prove_configs_limited(rows, pieces, L: int, M: int, discrepancy="add", first_limit: int = 0, **arguments) -> dict:
+    """prove_configs in LIMITED-DISCREPANCY ORDER (the rule: include/tpl_learn.h, tpl_placement_exact_limited): the same search, its
+    children, stop, budgets and node cap, with the paths that follow the children's order searched first.  The arguments are
+    prove_configs', by keyword; the dict is prove_configs' with limit int32 [n], the K of the last iteration begun.
+    discrepancy: "add" or "double" -- every budget is searched under a limit K on the steps a path may take off the children's order:
+    K = first_limit (an integer in [0, 65535]) first, then K + 1 ("add") or max(1, 2 K) ("double"), until an iteration drops no
+    child; `nodes` counts them all.  None is the plain search: the result of prove_configs as it stands, without `limit`.
+    **Verdicts do not change: under proved, solved, solution_len, bound and unwinnable are the plain search's.  The solution may
+    differ: actions may name another win of the same length, still a shortest one.  first_limit >= 8,382 gives the plain search's
+    outputs byte for byte.  Searching out a budget that holds no win takes at most 15 times the plain search's nodes under "double"
+    and up to 8,383 times under "add".**  What it buys is proofs within max_nodes where the order is good but not perfect."""
+    return _prove_configs(rows, pieces, L, M, **arguments, discrepancy=discrepancy, first_limit=first_limit)
+
+
+def _prove_configs(rows, pieces, L: int, M: int, weights=None, max_nodes: int = 1 << 16, shortest: bool = True,
+                  spare_weight: float = 0.0, device="cuda:0", validate: bool = True, discrepancy=None, first_limit: int = 0) -> dict:
+    """prove_configs and prove_configs_limited on their arguments; discrepancy None is the plain search."""
     import torch
     from . import _learn_lib
     L, M = _game(L, M)
@@ -268,6 +300,7 @@ def prove_configs(rows, pieces, L: int, M: int, weights=None, max_nodes: int = 1
     if not isinstance(shortest, (bool, np.bool_)):
         raise ValueError(f"shortest must be True or False, got {shortest!r}")
     spare_weight = _spare_weight(spare_weight, True)
+    limited = _discrepancy(discrepancy, first_limit)
     if not _is_tensor(rows):
         rows = np.asarray(rows)
     if not _is_tensor(pieces):
@@ -281,9 +314,15 @@ def prove_configs(rows, pieces, L: int, M: int, weights=None, max_nodes: int = 1
                solution_len=torch.empty(n, dtype=torch.int32, device=d), actions=torch.empty((n, M), dtype=torch.uint8, device=d),
                bound=torch.empty(n, dtype=torch.int32, device=d), nodes=torch.empty(n, dtype=torch.int32, device=d))
     stream = torch._C._cuda_getCurrentRawStream(d.index if d.index is not None else torch.cuda.current_device())
-    _learn_lib.check(_learn_lib.entry("exact", w.shape[0])(
-        rows.data_ptr(), pieces.data_ptr(), n, L, M, wt.data_ptr(), spare_weight, max_nodes, int(bool(shortest)),
-        *(out[k].data_ptr() for k in ("solved", "proved", "solution_len", "actions", "bound", "nodes")), stream))
+    if limited is None:
+        _learn_lib.check(_learn_lib.entry("exact", w.shape[0])(
+            rows.data_ptr(), pieces.data_ptr(), n, L, M, wt.data_ptr(), spare_weight, max_nodes, int(bool(shortest)),
+            *(out[k].data_ptr() for k in ("solved", "proved", "solution_len", "actions", "bound", "nodes")), stream))
+    else:
+        out["limit"] = torch.empty(n, dtype=torch.int32, device=d)
+        _learn_lib.check(_learn_lib.entry("exact_limited", w.shape[0])(
+            rows.data_ptr(), pieces.data_ptr(), n, L, M, wt.data_ptr(), spare_weight, max_nodes, int(bool(shortest)), limited[1],
+            limited[0], *(out[k].data_ptr() for k in ("solved", "proved", "solution_len", "actions", "bound", "nodes", "limit")), stream))
     out["solved"], out["proved"] = out["solved"].view(torch.bool), out["proved"].view(torch.bool)
     out["optimal"] = out["solved"] & bool(shortest)
     out["unwinnable"] = out["proved"] & ~out["solved"]
@@ -368,6 +407,7 @@ def prove_nodes(rows, lines, moves, entry, pieces, L: int, M: int, weights=None,
 
 # ------------------------------------------------------------------------------------------------ the search over a state's window
 WINDOW_OUTPUTS = ("solved", "proved", "solution_len", "plan", "bound", "nodes", "horizon", "verdict")
+WINDOW_LIMITED_OUTPUTS = WINDOW_OUTPUTS[:6] + ("limit",) + WINDOW_OUTPUTS[6:]
 
 
 def _resident_planes(env):
@@ -384,23 +424,31 @@ def _plane_fields(a, b):
     return moves, (b[:, 1] >> 28) & 3, (b[:, 2] >> 20) & 255
 
 
-def _window_buffers(n: int, d) -> dict:
+def _window_buffers(n: int, d, limited=None) -> dict:
     import torch
     kinds = dict(solved=torch.uint8, proved=torch.uint8, solution_len=torch.int32, bound=torch.int32, nodes=torch.int32,
                  horizon=torch.uint8, verdict=torch.uint8)
+    if limited is not None:
+        kinds["limit"] = torch.int32
     out = {k: torch.empty(n, dtype=t, device=d) for k, t in kinds.items()}
     out["plan"] = torch.empty((n, 12), dtype=torch.uint8, device=d)
     return out
 
 
-def _window_launch(env, planes, features: int, wt, spare_weight: float, max_nodes: int, skip, out: dict) -> None:
-    """tpl_placement_window_prove[_move] on the resident boards of `env` into the buffers of _window_buffers."""
+def _window_launch(env, planes, features: int, wt, spare_weight: float, max_nodes: int, skip, out: dict, limited=None) -> None:
+    """tpl_placement_window_prove[_move] on the resident boards of `env` into the buffers of _window_buffers; with limited =
+    (growth, first_limit) the _limited entry, which also fills out["limit"]."""
     import torch
     from . import _learn_lib
     stream = torch._C._cuda_getCurrentRawStream(env.device.index)
-    _learn_lib.check(_learn_lib.entry("window_prove", features)(
-        planes[0], planes[1], env.num_envs, env.L, env.M, wt.data_ptr(), spare_weight, max_nodes,
-        None if skip is None else skip.data_ptr(), *(out[k].data_ptr() for k in WINDOW_OUTPUTS), stream))
+    if limited is None:
+        _learn_lib.check(_learn_lib.entry("window_prove", features)(
+            planes[0], planes[1], env.num_envs, env.L, env.M, wt.data_ptr(), spare_weight, max_nodes,
+            None if skip is None else skip.data_ptr(), *(out[k].data_ptr() for k in WINDOW_OUTPUTS), stream))
+    else:
+        _learn_lib.check(_learn_lib.entry("window_prove_limited", features)(
+            planes[0], planes[1], env.num_envs, env.L, env.M, wt.data_ptr(), spare_weight, max_nodes, limited[1], limited[0],
+            None if skip is None else skip.data_ptr(), *(out[k].data_ptr() for k in WINDOW_LIMITED_OUTPUTS), stream))
 
 
 def _skip_mask(env, skip):
@@ -436,6 +484,26 @@ def window_prove(env, weights=None, max_nodes: int = 1 << 12, spare_weight: floa
          known pieces.
     **Verdict 3 proves nothing about the game, neither way.**  Verdicts 1 and 2 do not depend on max_nodes or on the weights.
     The environment is read, never written; no host wait."""
+    return _window_prove(env, weights, max_nodes, spare_weight, skip, None, 0)
+
+
+def window_prove_limited(env, discrepancy="add", first_limit: int = 0, **arguments) -> dict:
+    """window_prove in LIMITED-DISCREPANCY ORDER (the rule: include/tpl_learn.h, tpl_placement_window_prove_limited).  The arguments
+    are window_prove's, by keyword; the dict is window_prove's with limit int32 [N], the K of the last iteration begun and 0 where
+    nothing was searched.  **Verdict 3 still proves nothing about the game.**
+    discrepancy: "add" or "double" -- every budget is searched under a limit K on the steps a path may take off the children's order:
+    K = first_limit (an integer in [0, 65535]) first, then K + 1 ("add") or max(1, 2 K) ("double"), until an iteration drops no
+    child; `nodes` counts them all.  None is the plain search: the result of window_prove as it stands, without `limit`.
+    **Verdicts do not change: under proved, solved, solution_len, bound and the verdicts 1 and 2 are the plain search's.  The solution may
+    differ: plan may name another win of the same length, still a shortest one.  first_limit >= 8,382 gives the plain search's
+    outputs byte for byte.  Searching out a budget that holds no win takes at most 15 times the plain search's nodes under "double"
+    and up to 8,383 times under "add".**  What it buys is proofs within max_nodes where the order is good but not perfect."""
+    return _window_prove(env, **arguments, discrepancy=discrepancy, first_limit=first_limit)
+
+
+def _window_prove(env, weights=None, max_nodes: int = 1 << 12, spare_weight: float = 0.0, skip=None, discrepancy=None,
+                 first_limit: int = 0) -> dict:
+    """window_prove and window_prove_limited on their arguments; discrepancy None is the plain search."""
     import torch
     from . import _learn_lib
     from .lookahead import _boards, _state_ptrs
@@ -443,10 +511,11 @@ def window_prove(env, weights=None, max_nodes: int = 1 << 12, spare_weight: floa
     w = _weight_row(weights)
     max_nodes = _max_nodes(max_nodes)
     spare_weight = _spare_weight(spare_weight, True)
+    limited = _discrepancy(discrepancy, first_limit)
     skip = _skip_mask(env, skip)
     wt = torch.from_numpy(_learn_lib.padded_weights(w)).to(env.device)
-    out = _window_buffers(env.num_envs, env.device)
-    _window_launch(env, _state_ptrs(env), w.shape[0], wt, spare_weight, max_nodes, skip, out)
+    out = _window_buffers(env.num_envs, env.device, limited)
+    _window_launch(env, _state_ptrs(env), w.shape[0], wt, spare_weight, max_nodes, skip, out, limited)
     out["solved"], out["proved"] = out["solved"].view(torch.bool), out["proved"].view(torch.bool)
     moves, _, _ = _plane_fields(*_resident_planes(env))
     out["known"] = (12 - moves % 10).to(torch.uint8)
@@ -463,14 +532,21 @@ def _window_table(table, d):
     return _exact_table(table, table.device if d is None and _is_tensor(table) else d)
 
 
-def _ntuple_window_launch(env, planes, table, reward, gamma: float, max_nodes: int, skip, out: dict) -> None:
-    """tpl_ntuple_window_prove on the resident boards of `env` into the buffers of _window_buffers."""
+def _ntuple_window_launch(env, planes, table, reward, gamma: float, max_nodes: int, skip, out: dict, limited=None) -> None:
+    """tpl_ntuple_window_prove on the resident boards of `env` into the buffers of _window_buffers; with limited = (growth,
+    first_limit) the _limited entry, which also fills out["limit"]."""
     import torch
     from . import _learn_lib
     stream = torch._C._cuda_getCurrentRawStream(env.device.index)
-    _learn_lib.check(_learn_lib.lib().tpl_ntuple_window_prove(
-        planes[0], planes[1], env.num_envs, env.L, env.M, table.data_ptr(), int(table.shape[0]), reward[0], reward[1], reward[2], gamma,
-        max_nodes, None if skip is None else skip.data_ptr(), *(out[k].data_ptr() for k in WINDOW_OUTPUTS), stream))
+    if limited is None:
+        _learn_lib.check(_learn_lib.lib().tpl_ntuple_window_prove(
+            planes[0], planes[1], env.num_envs, env.L, env.M, table.data_ptr(), int(table.shape[0]), reward[0], reward[1], reward[2],
+            gamma, max_nodes, None if skip is None else skip.data_ptr(), *(out[k].data_ptr() for k in WINDOW_OUTPUTS), stream))
+    else:
+        _learn_lib.check(_learn_lib.lib().tpl_ntuple_window_prove_limited(
+            planes[0], planes[1], env.num_envs, env.L, env.M, table.data_ptr(), int(table.shape[0]), reward[0], reward[1], reward[2],
+            gamma, max_nodes, limited[1], limited[0], None if skip is None else skip.data_ptr(),
+            *(out[k].data_ptr() for k in WINDOW_LIMITED_OUTPUTS), stream))
 
 
 def ntuple_window_prove(env, table, gamma: float = 1.0, reward=(1.0, 0.0, 0.0), max_nodes: int = 1 << 12, skip=None) -> dict:
@@ -484,16 +560,37 @@ def ntuple_window_prove(env, table, gamma: float = 1.0, reward=(1.0, 0.0, 0.0), 
     a search takes, and no verdict but between 3 and the two others.  max_nodes and skip are window_prove's.
     Returns window_prove's dict with the same keys and dtypes.  **Verdict 3 proves nothing about the game, neither way.**
     The environment is read, never written; no host wait."""
+    return _ntuple_window_prove(env, table, gamma, reward, max_nodes, skip, None, 0)
+
+
+def ntuple_window_prove_limited(env, table, discrepancy="add", first_limit: int = 0, **arguments) -> dict:
+    """ntuple_window_prove in LIMITED-DISCREPANCY ORDER (the rule: include/tpl_learn.h, tpl_ntuple_window_prove_limited).  The arguments
+    are ntuple_window_prove's, by keyword; the dict is its dict with limit int32 [N], the K of the last iteration begun and 0 where
+    nothing was searched.  **Verdict 3 still proves nothing about the game.**
+    discrepancy: "add" or "double" -- every budget is searched under a limit K on the steps a path may take off the children's order:
+    K = first_limit (an integer in [0, 65535]) first, then K + 1 ("add") or max(1, 2 K) ("double"), until an iteration drops no
+    child; `nodes` counts them all.  None is the plain search: the result of ntuple_window_prove as it stands, without `limit`.
+    **Verdicts do not change: under proved, solved, solution_len, bound and the verdicts 1 and 2 are the plain search's.  The solution may
+    differ: plan may name another win of the same length, still a shortest one.  first_limit >= 8,382 gives the plain search's
+    outputs byte for byte.  Searching out a budget that holds no win takes at most 15 times the plain search's nodes under "double"
+    and up to 8,383 times under "add".**  What it buys is proofs within max_nodes where the order is good but not perfect."""
+    return _ntuple_window_prove(env, table, **arguments, discrepancy=discrepancy, first_limit=first_limit)
+
+
+def _ntuple_window_prove(env, table, gamma: float = 1.0, reward=(1.0, 0.0, 0.0), max_nodes: int = 1 << 12, skip=None,
+                        discrepancy=None, first_limit: int = 0) -> dict:
+    """ntuple_window_prove and ntuple_window_prove_limited on their arguments; discrepancy None is the plain search."""
     import torch
     from .lookahead import _boards, _state_ptrs
     _boards(env, "ntuple_window_prove")
     max_nodes = _max_nodes(max_nodes)
     gamma = _number("gamma", gamma)
     reward = _reward(reward)
+    limited = _discrepancy(discrepancy, first_limit)
     table = _window_table(table, env.device)
     skip = _skip_mask(env, skip)
-    out = _window_buffers(env.num_envs, env.device)
-    _ntuple_window_launch(env, _state_ptrs(env), table, reward, gamma, max_nodes, skip, out)
+    out = _window_buffers(env.num_envs, env.device, limited)
+    _ntuple_window_launch(env, _state_ptrs(env), table, reward, gamma, max_nodes, skip, out, limited)
     out["solved"], out["proved"] = out["solved"].view(torch.bool), out["proved"].view(torch.bool)
     moves, _, _ = _plane_fields(*_resident_planes(env))
     out["known"] = (12 - moves % 10).to(torch.uint8)
@@ -522,15 +619,23 @@ class ProofPolicy:
     move) and `finishing` bool [N] (it is the plan's last move: it wins), `nodes` int32 [N] (0 where nothing was searched).
     stats() counts since construction, on the device.  No host wait in act().
 
+    ProofPolicy(env, base, ..., discrepancy="add", first_limit=0) -- the two given by keyword, with or without the three of a table
+    below -- makes a LimitedProofPolicy, whose searches run in limited-discrepancy order.
+
     ProofPolicy(env, base, ..., table=None, gamma=1.0, reward=(1.0, 0.0, 0.0)) -- the three given by keyword -- makes a
     TableProofPolicy, whose search is ordered by an n-tuple table (below); without them this class is all there is.  Only
     ProofPolicy itself is switched: a subclass of ProofPolicy that wants the table order derives from TableProofPolicy, and one that
     does not is refused `table=` by its own __init__ (a TypeError), as any unknown argument is."""
 
+    _limited = None                                            # (growth, first_limit) in a LimitedProofPolicy: the plain search here
+
     def __new__(cls, *args, **named):
         # the table-ordered policy is a subclass with three more arguments; ProofPolicy(..., table=...) makes one
         if cls is ProofPolicy and any(k in named for k in ("table", "gamma", "reward")):
             cls = TableProofPolicy
+        # and the limited order is a subclass of that one with two more
+        if cls in (ProofPolicy, TableProofPolicy) and any(k in named for k in ("discrepancy", "first_limit")):
+            cls = LimitedProofPolicy
         return object.__new__(cls)
 
     def __init__(self, env, base, weights=None, max_nodes: int = 1 << 12, spare_weight: float = 0.0, reuse: bool = False):
@@ -551,7 +656,9 @@ class ProofPolicy:
         d = env.device
         self._weights = torch.from_numpy(_learn_lib.padded_weights(w)).to(d)
         self._ptrs, self._planes = _state_ptrs(env), _resident_planes(env)
-        self._out = _window_buffers(n, d)
+        self._out = _window_buffers(n, d, self._limited)
+        if self._limited is not None:
+            self.limit = self._out["limit"]
         self._index = torch.arange(n, device=d)
         self._counts = torch.zeros(4, dtype=torch.int64, device=d)              # verdicts 1, 2, 3; plan moves played
         # the plans kept: the plan, its length, the next move's index, the `moves` it expects and the cells it is to find
@@ -574,7 +681,8 @@ class ProofPolicy:
 
     def _search(self, skip) -> None:
         """The window search of the resident boards into self._out."""
-        _window_launch(self.env, self._ptrs, self.features, self._weights, self.spare_weight, self.max_nodes, skip, self._out)
+        _window_launch(self.env, self._ptrs, self.features, self._weights, self.spare_weight, self.max_nodes, skip, self._out,
+                       self._limited)
 
     def act(self, out=None, verdict=None, **base_arguments):
         """uint8 [N]: the proved plan's move where this call's verdict is 1 or a live plan is held, base.act(out=out,
@@ -652,7 +760,23 @@ class TableProofPolicy(ProofPolicy):
     def _search(self, skip) -> None:
         if self.table is None:
             return super()._search(skip)
-        _ntuple_window_launch(self.env, self._ptrs, self.table, self.reward, self.gamma, self.max_nodes, skip, self._out)
+        _ntuple_window_launch(self.env, self._ptrs, self.table, self.reward, self.gamma, self.max_nodes, skip, self._out,
+                              self._limited)
+
+
+class LimitedProofPolicy(TableProofPolicy):
+    """ProofPolicy, or with table= TableProofPolicy, with the search of every act() in LIMITED-DISCREPANCY ORDER:
+    window_prove_limited for window_prove and ntuple_window_prove_limited for ntuple_window_prove (the rule: include/tpl_learn.h,
+    tpl_placement_window_prove_limited).  ProofPolicy(env, base, discrepancy="add") makes one.  discrepancy -- "add", "double", or
+    None for the plain search -- and first_limit are window_prove_limited's.  They change which proofs fit max_nodes and nothing a
+    verdict 1 promises: following the plan wins the game in solution_len moves.  **Verdict 3 still proves nothing.**
+    The kept plans, reuse, stats(), verdict, played, finishing and nodes are ProofPolicy's, untouched; after an act() `limit` int32
+    [N] holds the kernel's limits (with a discrepancy)."""
+
+    def __init__(self, env, base, weights=None, max_nodes: int = 1 << 12, spare_weight: float = 0.0, reuse: bool = False, table=None,
+                 gamma: float = 1.0, reward=(1.0, 0.0, 0.0), discrepancy="add", first_limit: int = 0):
+        self._limited = _discrepancy(discrepancy, first_limit)
+        super().__init__(env, base, weights, max_nodes, spare_weight, reuse, table, gamma, reward)
 
 
 def _best_move(label, length):
@@ -898,6 +1022,26 @@ def ntuple_prove_configs(rows, pieces, L: int, M: int, table, gamma: float = 1.0
     sequence of placements wins within M moves, and with shortest=True solved[i] = True a proof that solution_len[i] is the shortest
     there is.  solved[i] = True always comes with proved[i].  Without proved[i] NOTHING is proved, neither way.**
     No host wait except the piece-id check, which validate=False skips."""
+    return _ntuple_prove_configs(rows, pieces, L, M, table, gamma, reward, max_nodes, shortest, device, validate, None, 0)
+
+
+def ntuple_prove_configs_limited(rows, pieces, L: int, M: int, table, discrepancy="add", first_limit: int = 0, **arguments) -> dict:
+    """ntuple_prove_configs in LIMITED-DISCREPANCY ORDER (the rule: include/tpl_learn.h, tpl_ntuple_exact_limited): prove_configs_limited
+    with the children ordered by an n-tuple table.  The arguments are ntuple_prove_configs', by keyword; the dict is its dict with
+    limit int32 [n], the K of the last iteration begun.
+    discrepancy: "add" or "double" -- every budget is searched under a limit K on the steps a path may take off the children's order:
+    K = first_limit (an integer in [0, 65535]) first, then K + 1 ("add") or max(1, 2 K) ("double"), until an iteration drops no
+    child; `nodes` counts them all.  None is the plain search: the result of ntuple_prove_configs as it stands, without `limit`.
+    **Verdicts do not change: under proved, solved, solution_len, bound and unwinnable are the plain search's.  The solution may
+    differ: actions may name another win of the same length, still a shortest one.  first_limit >= 8,382 gives the plain search's
+    outputs byte for byte.  Searching out a budget that holds no win takes at most 15 times the plain search's nodes under "double"
+    and up to 8,383 times under "add".**  What it buys is proofs within max_nodes where the order is good but not perfect."""
+    return _ntuple_prove_configs(rows, pieces, L, M, table, **arguments, discrepancy=discrepancy, first_limit=first_limit)
+
+
+def _ntuple_prove_configs(rows, pieces, L: int, M: int, table, gamma: float = 1.0, reward=(1.0, 0.0, 0.0), max_nodes: int = 1 << 16,
+                         shortest: bool = True, device="cuda:0", validate: bool = True, discrepancy=None, first_limit: int = 0) -> dict:
+    """ntuple_prove_configs and ntuple_prove_configs_limited on their arguments; discrepancy None is the plain search."""
     import torch
     from . import _learn_lib
     L, M = _game(L, M)
@@ -906,6 +1050,7 @@ def ntuple_prove_configs(rows, pieces, L: int, M: int, table, gamma: float = 1.0
         raise ValueError(f"shortest must be True or False, got {shortest!r}")
     gamma = _number("gamma", gamma)
     r_line, r_win, r_lose = _reward(reward)
+    limited = _discrepancy(discrepancy, first_limit)
     if not _is_tensor(rows):
         rows = np.asarray(rows)
     if not _is_tensor(pieces):
@@ -919,9 +1064,16 @@ def ntuple_prove_configs(rows, pieces, L: int, M: int, table, gamma: float = 1.0
                solution_len=torch.empty(n, dtype=torch.int32, device=d), actions=torch.empty((n, M), dtype=torch.uint8, device=d),
                bound=torch.empty(n, dtype=torch.int32, device=d), nodes=torch.empty(n, dtype=torch.int32, device=d))
     stream = torch._C._cuda_getCurrentRawStream(d.index if d.index is not None else torch.cuda.current_device())
-    _learn_lib.check(_learn_lib.lib().tpl_ntuple_exact(
-        rows.data_ptr(), pieces.data_ptr(), n, L, M, table.data_ptr(), int(table.shape[0]), r_line, r_win, r_lose, gamma, max_nodes,
-        int(bool(shortest)), *(out[k].data_ptr() for k in ("solved", "proved", "solution_len", "actions", "bound", "nodes")), stream))
+    if limited is None:
+        _learn_lib.check(_learn_lib.lib().tpl_ntuple_exact(
+            rows.data_ptr(), pieces.data_ptr(), n, L, M, table.data_ptr(), int(table.shape[0]), r_line, r_win, r_lose, gamma, max_nodes,
+            int(bool(shortest)), *(out[k].data_ptr() for k in ("solved", "proved", "solution_len", "actions", "bound", "nodes")), stream))
+    else:
+        out["limit"] = torch.empty(n, dtype=torch.int32, device=d)
+        _learn_lib.check(_learn_lib.lib().tpl_ntuple_exact_limited(
+            rows.data_ptr(), pieces.data_ptr(), n, L, M, table.data_ptr(), int(table.shape[0]), r_line, r_win, r_lose, gamma, max_nodes,
+            int(bool(shortest)), limited[1], limited[0],
+            *(out[k].data_ptr() for k in ("solved", "proved", "solution_len", "actions", "bound", "nodes", "limit")), stream))
     out["solved"], out["proved"] = out["solved"].view(torch.bool), out["proved"].view(torch.bool)
     out["optimal"] = out["solved"] & bool(shortest)
     out["unwinnable"] = out["proved"] & ~out["solved"]

@@ -156,6 +156,14 @@ Parts:
               the running boards, the episodes that held a verdict 1 and did not end won (which must be 0), the milliseconds of a
               played step with reuse off and on beside the base's in alternated rounds, and the nodes a second of window_prove beside
               prove_nodes on the same boards; the loose pool once.  --sections and --budgets choose what one call runs
+    limited   the exact searches in limited-discrepancy order (tpl_placement_exact_limited and its five kin; prove_configs_limited,
+              ProofPolicy(discrepancy=)) beside the plain kernels IN THE SAME RUN, the legs alternated: the share of part exact's pool
+              proved at its exact budget at 2^12 and 2^16 nodes under the plain order, "add" and "double", and what each closes of what
+              the width-64 beam leaves unsolved; the nodes a second of each limited kernel at first_limit 65,535 -- the plain kernel's
+              work -- as a ratio to its twin, and at first_limit 0; the nodes both growths take to search out budgets that hold no win,
+              over the plain search's; on part window's tight pool the one-ply player and the beam (3, 8) inside a ProofPolicy at 2^8 and
+              2^12 nodes, plain against "add".  Under the classical weights and under part ntuple_exact's "feat+spare" table, made here
+              by its recipe.  --sections chooses what one call runs.  One seed, one pool
     solve     the whole-game beam solver (tpl_placement_solve, solve_configs) under the classical weights: the share of forward seeds
               0 .. 9,999 it solves at L=5 / M=20 and L=10 / M=40 at widths 1, 8, 16 and 64 beside the share the reference's solver marks
               winnable in the same forward_configs call, and the share of the sweeps' carved pool (65,536, seed 7) it solves; the
@@ -183,7 +191,7 @@ PARTS = {"sample": 300, "push": 300, "update": 300, "loop": 600, "priority": 600
          "ntuple_sum": 600, "ntuple_sum_sweep": 600, "ntuple_stage": 600, "ntuple_stage_sweep": 900,
          "ntuple_feature": 600, "ntuple_feature_sweep": 900, "solve": 900, "move_features": 1100, "bound": 900,
          "ntuple_budget": 600, "ntuple_budget_sweep": 1100, "exact": 900, "ntuple_exact": 900, "labels": 900,
-         "rank": 1100, "window": 1100, "ntuple_window": 1100}
+         "rank": 1100, "window": 1100, "ntuple_window": 1100, "limited": 1100}
 SCATTERED_ATOMICS = 0.08e12                                 # 64 lanes of a wave adding into 64 rows (float adds; integer adds unmeasured)
 VALU_CYCLES, SIMDS, CLOCK_HZ = 3.3, 1024, 2.4e9           # the move's instruction mix, 256 CUs x 4, the clock
 
@@ -2740,6 +2748,233 @@ def part_exact(slice_size=4096, minute=60.0):
     return out
 
 
+def part_limited(sections=("proofs", "cost", "searching_out", "wins"), rounds=3, boards=4096):
+    """The exact searches in limited-discrepancy order (include/tpl_learn.h: tpl_placement_exact_limited) beside the plain kernels in
+    the same run, under the classical weights and under part ntuple_exact's "feat+spare, rate 8, tight pool" table, made here by its
+    recipe.  Sections: proofs (part exact's pool at config_bound + 0, 2^12 and 2^16 nodes), cost (nodes a second of every limited
+    kernel against its twin, alternated rounds), searching_out (budgets that hold no win) and wins (part window's tight pool, 4,096
+    boards, 1,088 steps).  One seed, one pool."""
+    import numpy as np
+    import torch
+    import tetris_piclim as T
+    dev = "cuda:0"
+    L_, M_, M_new = 10, 40, 16
+    share = lambda x: round(float(x.float().mean()), 5)
+    out = dict(part="limited", sections=list(sections))
+
+    def progress(what):
+        print(json.dumps(what), file=sys.stderr, flush=True)
+
+    n = 1 << 16
+    env = T.BatchedTetris(L_, M_, 64, device=dev, seed=7)
+    rows, pieces = env.carved_configs(n, seed=7)
+    env.terminate()
+    need = T.config_bound(rows, L_, device=dev)
+    budget = torch.clamp(need, max=M_)
+    groups = [(b, torch.nonzero(budget == b).flatten()) for b in torch.unique(budget).tolist()]
+    groups = [(b, at, rows[at], pieces[at][:, :b + 1].contiguous()) for b, at in groups]
+    found = T.solve_configs(rows, pieces, L_, M_, width=16, device=dev, validate=False)
+    tight = T.tighten_pool(rows, pieces, found["solved"], found["solution_len"], M_new)
+    classical = np.array(T.CLASSICAL_WEIGHTS)
+
+    # the table of the record: part ntuple_exact's "feat+spare, rate 8, tight pool", by its recipe
+    env = T.BatchedTetris(L_, M_new, 4096, device=dev, seed=11, auto_reset=True, reward=NTUPLE_LARGE_REWARD, config_pool=tight)
+    learner = T.NTupleLearner(env, seed=11, gamma=1.0, epsilon=0.05, rate=8.0, shape="feat+spare", bound=False)
+    for steps in (10000, 30000):
+        learner.train(steps)
+    one = learner.evaluate(12288, bound=False)
+    table = learner.table.clone()
+    env.terminate()
+    out["table"] = dict(table="feat+spare, rate 8, tight pool", one_ply_win_rate_on_its_pool=round(one["win_rate"], 5),
+                        order="gamma 1, reward (1, 10, -1): the training's")
+    progress(out["table"])
+    ordered = dict(gamma=1.0, reward=NTUPLE_LARGE_REWARD)
+
+    def grouped(search, count=n):
+        got = {}
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for b, at, r, p in groups:
+            keep = at < count
+            if not bool(keep.any()):
+                continue
+            for k, v in search(r[keep], p[keep], b).items():
+                if v.dim() == 1:
+                    got.setdefault(k, torch.zeros(n, dtype=v.dtype, device=dev))[at[keep]] = v
+        torch.cuda.synchronize()
+        return {k: v[:count] for k, v in got.items()}, time.perf_counter() - t0
+
+    def prove(rule, log2, first=0, **kw):
+        """A root search of the pool under a weight row: plain (rule None) or limited."""
+        if rule is None:
+            return lambda r, p, b: T.prove_configs(r, p, L_, b, max_nodes=1 << log2, device=dev, validate=False, **kw)
+        return lambda r, p, b: T.prove_configs_limited(r, p, L_, b, rule, first, max_nodes=1 << log2, device=dev, validate=False, **kw)
+
+    def prove_tabled(tab, rule, log2, first=0):
+        if rule is None:
+            return lambda r, p, b: T.ntuple_prove_configs(r, p, L_, b, tab, max_nodes=1 << log2, device=dev, validate=False, **ordered)
+        return lambda r, p, b: T.ntuple_prove_configs_limited(r, p, L_, b, tab, rule, first, max_nodes=1 << log2, device=dev,
+                                                              validate=False, **ordered)
+
+    if "proofs" in sections:
+        beam, _ = grouped(lambda r, p, b: T.solve_configs(r, p, L_, b, width=64, device=dev, validate=False, bound=True))
+        left = ~beam["solved"]
+        out["pool"] = dict(size=n, seed=7, L=L_, M=M_, budget="config_bound + 0", unsolved_at_width_64=share(left))
+        out["proofs"] = []
+        record = {("classical weights", 12): 0.350, ("classical weights", 16): 0.650, ("feat+spare table", 12): 0.453,
+                  ("feat+spare table", 16): 0.750}
+        for label, make in (("classical weights", prove), ("feat+spare table", lambda rule, log2: prove_tabled(table, rule, log2))):
+            for log2 in (12, 16):
+                base = None
+                for rule in (None, "add", "double"):
+                    got, seconds = grouped(make(rule, log2))
+                    nodes = got["nodes"].double()
+                    line = dict(ordering=label, order=rule or "plain", max_nodes=f"2^{log2}", proved=share(got["proved"]),
+                                solved=share(got["solved"]), unwinnable=share(got["unwinnable"]),
+                                of_what_width_64_left_unsolved_closed=share(got["optimal"][left]),
+                                nodes_mean=round(float(nodes.mean()), 1), seconds=round(seconds, 3),
+                                nodes_per_second=round(float(nodes.sum()) / seconds, 1))
+                    if rule is None:
+                        base = got
+                        line["reproduces_the_record"] = round(line["proved"], 3) == record[(label, log2)]
+                    else:
+                        both = base["proved"] & got["proved"]
+                        line.update(plain_proofs_kept=share(got["proved"][base["proved"]]), limit_max=int(got["limit"].max()),
+                                    limit_mean_of_proved=round(float(got["limit"][got["proved"]].float().mean()), 2),
+                                    same_length_where_both_proved=bool((base["solution_len"][both] == got["solution_len"][both]).all()))
+                    out["proofs"].append(line)
+                    progress(line)
+
+    if "cost" in sections:
+        # nodes a second of every limited kernel beside its twin at 2^12 nodes, the legs alternated, the median of the rounds after a
+        # warm-up round: the root kernels on the pool's first 16,384, the window kernels on 4,096 boards of the tight pool in mid-game
+        count, log2 = 1 << 14, 12
+        w14 = np.array(T.DELLACHERIE_WEIGHTS)
+        zero = {form: torch.zeros(T._learn_lib.ntuple_entries_of(form), dtype=torch.int32, device=dev) for form in ("2x4", "3x3", "feat")}
+        tables = dict(zero, **{"feat+spare": table})
+        env = T.BatchedTetris(L_, M_new, boards, device=dev, seed=11, auto_reset=True, reward=(0.0, 1.0, 0.0), config_pool=tight)
+        env.reset()
+        player = T.HeuristicPolicy(env, classical)
+        for _ in range(40):
+            env.step(player.act(), observe=False)
+
+        def window(rule, first, **kw):
+            if rule is None:
+                return lambda: T.window_prove(env, max_nodes=1 << log2, **kw)
+            return lambda: T.window_prove_limited(env, rule, first, max_nodes=1 << log2, **kw)
+
+        def window_tabled(tab, rule, first):
+            if rule is None:
+                return lambda: T.ntuple_window_prove(env, tab, max_nodes=1 << log2, **ordered)
+            return lambda: T.ntuple_window_prove_limited(env, tab, rule, first, max_nodes=1 << log2, **ordered)
+
+        def once(search):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            got = search()
+            torch.cuda.synchronize()
+            return got, time.perf_counter() - t0
+
+        root = lambda make: (lambda rule, first: (lambda s=make(rule, first): grouped(s, count)))
+        flat = lambda make: (lambda rule, first: (lambda s=make(rule, first): once(s)))
+        kernels = {"tpl_placement_exact": root(lambda rule, first: prove(rule, log2, first)),
+                   "tpl_placement_exact_move": root(lambda rule, first: prove(rule, log2, first, weights=w14))}
+        for form, tab in tables.items():
+            kernels[f"tpl_ntuple_exact, {form!r}"] = root(lambda rule, first, tab=tab: prove_tabled(tab, rule, log2, first))
+        kernels["tpl_placement_window_prove"] = flat(lambda rule, first: window(rule, first))
+        kernels["tpl_placement_window_prove_move"] = flat(lambda rule, first: window(rule, first, weights=w14))
+        for form, tab in tables.items():
+            kernels[f"tpl_ntuple_window_prove, {form!r}"] = flat(lambda rule, first, tab=tab: window_tabled(tab, rule, first))
+        out["cost"] = dict(max_nodes=f"2^{log2}", rounds=rounds, root_configurations=count, window_boards=boards,
+                           tables='"feat+spare": the trained table; the three other forms: zero tables, whose order is the reward alone', rows=[])
+        for name, make in kernels.items():
+            legs = {"plain": make(None, 0), "limited_65535": make("add", 65535), "limited_0_add": make("add", 0),
+                    "limited_0_double": make("double", 0)}
+            rate = {k: [] for k in legs}
+            for _ in range(rounds + 1):
+                for k, run in legs.items():
+                    got, seconds = run()
+                    rate[k].append(float(got["nodes"].double().sum()) / seconds)
+            med = {k: float(np.median(v[1:])) for k, v in rate.items()}
+            line = dict(kernel=name, nodes_per_second={k: round(v, 1) for k, v in med.items()},
+                        limited_65535_over_plain=round(med["limited_65535"] / med["plain"], 4),
+                        limited_0_add_over_plain=round(med["limited_0_add"] / med["plain"], 4))
+            out["cost"]["rows"].append(line)
+            progress(line)
+        env.terminate()
+
+    if "searching_out" in sections:
+        # The record's pool is carved, so at config_bound + 0 the first budget searched is the shortest length: it has no budget without a
+        # win.  generate_configs(3, 8) boards searched for four lines in six moves have.
+        g_rows, g_pieces = T.generate_configs(3, 8, 4096, seed=7)
+        g_pieces = np.ascontiguousarray(g_pieces[:, :7])
+        base = T.prove_configs(g_rows, g_pieces, 4, 6, max_nodes=1 << 20, device=dev)
+        at = base["unwinnable"] & (base["nodes"] > 0)
+        out["searching_out"] = dict(record_pool="none: carved configurations at their exact budget are all winnable, and the first budget "
+                                    "searched is the shortest length", boards="generate_configs(3, 8, 4096, seed 7) searched for 4 lines in 6 moves",
+                                    max_nodes="2^20", proved_without_a_win=int(at.sum()),
+                                    plain_nodes_mean=round(float(base["nodes"][at].double().mean()), 1))
+        for rule in ("add", "double"):
+            got = T.prove_configs_limited(g_rows, g_pieces, 4, 6, rule, 0, max_nodes=1 << 20, device=dev)
+            ratio = got["nodes"][at].double() / base["nodes"][at].double()
+            total = float(got["nodes"][at].double().sum() / base["nodes"][at].double().sum())
+            out["searching_out"][rule] = dict(still_proved_without_a_win=share(got["unwinnable"][at]), nodes_over_plain_total=round(total, 3),
+                                              nodes_over_plain_max=round(float(ratio.max()), 2), limit_max=int(got["limit"][at].max()))
+        progress(out["searching_out"])
+
+    if "wins" in sections:                                     # part window's and part ntuple_window's set-up
+        steps = 16 * (M_new + 1) * (1 << 14) // boards
+        out["wins"] = dict(pool=dict(size=int(tight[0].shape[0]), L=L_, M=M_new), boards=boards, steps=steps, reuse=True, rows=[])
+        record = {("classical weights", "one_ply", 8): 0.617, ("classical weights", "one_ply", 12): 0.738,
+                  ("classical weights", "beam_3x8", 8): 0.865, ("classical weights", "beam_3x8", 12): 0.910,
+                  ("feat+spare table", "one_ply", 8): 0.673, ("feat+spare table", "one_ply", 12): 0.774}
+        for label, order in (("classical weights", {}), ("feat+spare table", dict(ordered, table=table))):
+            for name, depth, width in (("one_ply", 1, None), ("beam_3x8", 3, 8)):
+                for log2 in (8, 12):
+                    for rule in (None, "add"):
+                        env = T.BatchedTetris(L_, M_new, boards, device=dev, seed=11, auto_reset=True, reward=(0.0, 1.0, 0.0), config_pool=tight)
+                        env.reset()
+                        base_policy = T.HeuristicPolicy(env, classical, depth=depth) if width is None else \
+                            T.BeamPolicy(env, classical, depth, width)
+                        limited = {} if rule is None else dict(discrepancy=rule)
+                        player = T.ProofPolicy(env, base_policy, max_nodes=1 << log2, reuse=True, **order, **limited)
+                        action = torch.empty(boards, dtype=torch.uint8, device=dev)
+                        reward = torch.empty(boards, dtype=torch.float32, device=dev)
+                        done = torch.empty(boards, dtype=torch.uint8, device=dev)
+                        tallies = torch.zeros(4, dtype=torch.int64, device=dev)   # episodes, wins, episodes with a proof, broken proofs
+                        held = torch.zeros(boards, dtype=torch.bool, device=dev)
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        for _ in range(steps):
+                            player.act(out=action)
+                            held |= player.played
+                            env.step_into(action, reward, done)
+                            over, won = done.bool(), reward == 1.0
+                            tallies += torch.stack([over.sum(), (over & won).sum(), (over & held).sum(), (over & held & ~won).sum()])
+                            held &= ~over
+                        torch.cuda.synchronize()
+                        seconds = time.perf_counter() - t0
+                        e, w, with_proof, broken = tallies.tolist()
+                        env.terminate()
+                        rate = w / max(e, 1)
+                        line = dict(ordering=label, base=name, max_nodes=f"2^{log2}", order=rule or "plain", episodes=e, wins=w,
+                                    win_rate=round(rate, 5), standard_error=round((rate * (1 - rate) / max(e, 1)) ** 0.5, 6),
+                                    episodes_that_held_a_verdict_1=with_proof, of_them_not_won=broken,
+                                    ms_per_step=round(seconds * 1e3 / steps, 3), stats=player.stats())
+                        if rule is None and (label, name, log2) in record:
+                            line["reproduces_the_record"] = round(rate, 3) == record[(label, name, log2)]
+                        out["wins"]["rows"].append(line)
+                        progress(line)
+                        if broken:                              # a bug to fix before anything is recorded
+                            raise RuntimeError(f"{broken} episodes held a verdict 1 and did not end won: {line}")
+    res = subprocess.run(["bash", os.path.join(ROOT, "tools", "kernel_resources.sh"), T._learn_lib.build_library()],
+                         capture_output=True, text=True, cwd=ROOT)
+    out["kernel"] = [" ".join(l.split()) for l in res.stdout.splitlines() if "_limited_kernel" in l]
+    out["not_measured"] = ("first limits other than 0 and 65,535; trained tables of the forms other than \"feat+spare\"; \"double\" in play; "
+                           "pools other than this one; more than one seed")
+    return out
+
+
 def part_labels(boards=4096, log2_nodes=12):
     """The proved move labels (include/tpl_learn.h: tpl_placement_exact_labels; T.label_states) on the tight pool of the record --
     part_bound's: carved L = 10 / M = 40, 65,536 configurations, seed 7, solved at width 16, tighten_pool(M_new=16).  The classical
@@ -3571,7 +3806,8 @@ def main():
     ap.add_argument("--parent", default=None, help="of parts ntuple_shape_ab and exact_ab: the learner library of the build to compare against")
     ap.add_argument("--no-timing", action="store_true", help="of part exact_ab: compare the outputs only")
     ap.add_argument("--chunk", default=None, help="I/K: of part ntuple_coherent_sweep, every K-th cell from the I-th on")
-    ap.add_argument("--sections", default=None, help="of part window: which of record,rates,verdicts,time,loose to run (all)")
+    ap.add_argument("--sections", default=None, help="of part window: which of record,rates,verdicts,time,loose to run (all); "
+                    "of part limited: which of proofs,cost,searching_out,wins")
     ap.add_argument("--budgets", default=None, help="of part window: the log2 of the node budgets, e.g. 8,12 (8,12,16)")
     args = ap.parse_args()
     if args.part:
@@ -3584,8 +3820,8 @@ def main():
                 ap.error("--chunk I/K needs 0 <= I < K")
             kw["chunk"] = (i, k)
         if args.sections or args.budgets:
-            if args.part != "window":
-                ap.error("--sections and --budgets go with --part window")
+            if args.part not in ("window", "limited") or (args.budgets and args.part != "window"):
+                ap.error("--sections goes with --part window or limited, --budgets with --part window")
             if args.sections:
                 kw["sections"] = tuple(args.sections.split(","))
             if args.budgets:
