@@ -51,10 +51,11 @@ static inline size_t record_stride(int M) { return (size_t)1 << record_stride_sh
 // phases so that a wave makes as few dependent trips to memory as the rules allow -- the whole grid is resident at
 // once, so the time of a launch is the length of one wave's chain, not a sum over rounds of waves:
 //   0  every board's state words and actions are requested
-//   1  the piece-word gathers of the boards whose window runs out with this move are requested
-//   2  the moves are computed (registers and LDS only)
+//   1  the boards whose window runs out with this move are noted (a test on the move counter, nothing is requested)
+//   2  the moves are computed (registers and LDS only); the window is popped
 //   3  reward / done / cleared are written
-//   4  the pool records of the boards that finished are requested (auto-reset)
+//   4  one record per board that needs one is requested: the pool record of a board that finished (auto-reset), or else
+//      the piece word of a board whose window ran out; a board never needs both
 //   5  the state words are written
 #ifdef TPL_DIAG_CLOCK
 // diagnostic build only (tools/step_timeline.py): every wave stamps the 100 MHz real-time counter
@@ -116,15 +117,14 @@ __global__ __launch_bounds__(kThreads) void step_kernel(const StepArgs p) {
     __syncthreads();
 
     // phase 1.  pieces.pop(0) (:356) moves the cursor to moves_used + 1 whatever the move does.  When that is a
-    // multiple of ten the window is down to its last two entries and piece word cursor/10 replaces it.
-    uint64_t word[kBpl];
-    uint32_t moves[kBpl], refill_word[kBpl];
+    // multiple of ten the window is down to its last two entries and piece word cursor/10 replaces it -- in phase 4,
+    // behind the move: here the board is only noted.
+    uint32_t moves[kBpl];
     bool live[kBpl], refill[kBpl];
 #pragma unroll
     for (int k = 0; k < kBpl; ++k) {
-        // an empty statement that needs every phase-0 result: it pins the one wait for phase 0 here, ahead of all
-        // the gathers (left alone, the compiler waits for board k only after the gather of board k-1 has left,
-        // which then has to be waited for as well)
+        // an empty statement that needs every phase-0 result: it pins the one wait for phase 0 here, ahead of the
+        // first move
         asm volatile("" ::"v"(A[k].x), "v"(B[k].x), "v"(a0[k]), "v"(a1[k]), "s"(clock[k]));
     }
     TPL_STAMP(1);
@@ -138,34 +138,15 @@ __global__ __launch_bounds__(kThreads) void step_kernel(const StepArgs p) {
 #pragma unroll
     for (int k = 0; k < kBpl; ++k) {
         moves[k] = packed_moves(A[k]);
-        const uint32_t tenth = tenths(moves[k] + 1u);
-        refill_word[k] = window_word(tenth);
         live[k] = packed_state(B[k]) == ST_RUNNING;
-        refill[k] = live[k] && window_runs_out(tenth) && (p.n_cfg[0] | p.n_cfg[1]) != 0u;
-    }
-#pragma unroll
-    for (int k = 0; k < kBpl; ++k) {
-        const int64_t i = base + (int64_t)k * kThreads;
-        word[k] = 0;
-        if (refill[k]) {
-            // the board's episode began at step clock - moves_used, in the pool buffer the board carries
-            const uint32_t slot = packed_slot(B[k]);
-            const uint32_t cfg = config_of(p, (uint32_t)i, clock[k] - moves[k], slot);
-            word[k] = piece_word_at(pool_record(p, slot, cfg), refill_word[k]);
-        }
+        refill[k] = live[k] && window_runs_out(tenths(moves[k] + 1u)) && (p.n_cfg[0] | p.n_cfg[1]) != 0u;
     }
 
     // phase 2
     float reward[kBpl];
     uint32_t n_clear[kBpl];
     bool done[kBpl], reload[kBpl];
-#pragma unroll
-    for (int k = 0; k < kBpl; ++k) {
-        reward[k] = 0.0f;
-        n_clear[k] = 0;
-        done[k] = true;
-        reload[k] = false;
-        if (!live[k]) continue;                               // frozen: reward 0, done, state untouched
+    const auto move_one = [&](int k) {
         uint32_t rot, loc;
         if (kActionForm) {
             split_action(a0[k], rot, loc);
@@ -187,7 +168,7 @@ __global__ __launch_bounds__(kThreads) void step_kernel(const StepArgs p) {
         }
         n_clear[k] = move_board_lds(s, cols, s_shape, rot, loc, p.L, p.M, topout);
         lds_load_cols(cols, s.c);
-        next_window(s, refill[k], word[k]);                    // the falling piece is consumed even on a top-out
+        pop_window(s);                                         // the falling piece is consumed even on a top-out
 
         reward[k] = step_reward(p, n_clear[k], s.state);
         done[k] = s.state != ST_RUNNING;
@@ -200,6 +181,14 @@ __global__ __launch_bounds__(kThreads) void step_kernel(const StepArgs p) {
         }
         reload[k] = kAutoReset && done[k];
         pack_board<true>(s, A[k], B[k]);
+    };
+#pragma unroll
+    for (int k = 0; k < kBpl; ++k) {
+        reward[k] = 0.0f;
+        n_clear[k] = 0;
+        done[k] = true;
+        reload[k] = false;
+        if (live[k]) move_one(k);                             // else frozen: reward 0, done, state untouched
     }
 
     TPL_STAMP(2);
@@ -213,30 +202,53 @@ __global__ __launch_bounds__(kThreads) void step_kernel(const StepArgs p) {
         if (p.cleared) p.cleared[i] = (uint8_t)n_clear[k];
     }
 
-    // phase 4: reset()/load_warm_reset() (:438-449) of the boards that finished.  One divergent region for all of
-    // a lane's boards, with the records landing in fresh registers: every request leaves before the first wait.
-    // (A lane in the region for one board only reads record 0 for its others and drops it.)
-    if (kAutoReset) {
-        bool any = false;
+    // phase 4: reset()/load_warm_reset() (:438-449) of the boards that finished, and the piece word of the boards that go
+    // on with a window that ran out.  A board that finished takes its whole state from its new record, so no board needs
+    // both, and both are "hash (board, birth) -> record address -> load": ONE hash per board, its inputs selected by what
+    // the board needs.  One divergent region for all of a lane's boards, and every request of it leaves before its one
+    // wait; a lane in the region for one board only hashes for its others and loads nothing for them.  Without auto-reset
+    // the region serves refills only, and a board that finished on its refill move keeps the refilled window, as the rules
+    // leave it.
+    {
+        bool patch[kBpl], any = false;
 #pragma unroll
-        for (int k = 0; k < kBpl; ++k) any = any || reload[k];
+        for (int k = 0; k < kBpl; ++k) {
+            patch[k] = refill[k] && !reload[k];
+            any = any || reload[k] || patch[k];
+        }
         if (any) {
-            uint4 RA[kBpl], RB[kBpl];
+            uint64_t word[kBpl];
 #pragma unroll
             for (int k = 0; k < kBpl; ++k) {
                 const int64_t i = base + (int64_t)k * kThreads;
-                // the new episode's first move is the next step: birth = clock + 1, from the current pool buffer
-                const uint32_t cfg = config_of(p, (uint32_t)i, clock[k] + 1u, p.cur_slot);
-                const uint4* rec = (const uint4*)pool_record(p, p.cur_slot, reload[k] ? cfg : 0u);
-                RA[k] = rec[0];
-                RB[k] = rec[1];
+                // a window is refilled from the episode the board is in: it began at step clock - moves_used, in the pool
+                // buffer the board carries.  A new episode's first move is the next step: birth = clock + 1, from the
+                // current pool buffer.
+                const uint32_t slot = patch[k] ? packed_slot(B[k]) : p.cur_slot;
+                const uint64_t birth = clock[k] + (patch[k] ? 0ull - (uint64_t)moves[k] : 1ull);
+                const uint8_t* rec = pool_record(p, slot, config_of(p, (uint32_t)i, birth, slot));
+                // (read only on the lanes that load it: any value elsewhere, said as an empty statement that leaves one.  Left
+                // undefined the word lands in a register of its own and is copied, behind a wait, inside the branch; zeroed,
+                // the zero is moved into the other branch and waits there for the load it would overwrite)
+                asm volatile("" : "=v"(word[k]));
+                if (reload[k]) {
+                    // the record lands in the registers the state is stored from
+                    A[k] = ((const uint4*)rec)[0];
+                    B[k] = ((const uint4*)rec)[1];
+                } else if (patch[k]) {
+                    word[k] = piece_word_at(rec, window_word(tenths(moves[k] + 1u)));
+                }
             }
+            // an empty statement that needs every load of the region: it pins the region's one wait here, behind the last
+            // request (left alone, the compiler moves a board's patch up into the branch that loads its word, and the
+            // wait with it: the next board's hash and requests then start only after that trip)
+#pragma unroll
+            for (int k = 0; k < kBpl; ++k) asm volatile("" ::"v"(word[k]), "v"(A[k].x), "v"(B[k].x));
 #pragma unroll
             for (int k = 0; k < kBpl; ++k) {
-                if (!reload[k]) continue;
-                A[k] = RA[k];
+                if (patch[k]) patch_window(B[k], word[k]);
                 // the record carries slot 0: stamp the current one (as load_config does)
-                B[k] = make_uint4(RB[k].x, RB[k].y | (p.cur_slot << 30), RB[k].z, RB[k].w);
+                if (reload[k]) B[k].y |= p.cur_slot << 30;
             }
         }
     }

@@ -69,6 +69,12 @@ __device__ __forceinline__ void next_window(Board& s, bool refill, uint64_t word
     s.window = refill ? (uint32_t)word : lo;
     s.window_hi = refill ? ((uint32_t)(word >> 32) & 0xFu) : hi;
 }
+// the pop alone, for a kernel that fetches the piece word of a window that has run out after the move and patches it into
+// the packed state (patch_window below): the step kernel, whose move then waits for no gather
+__device__ __forceinline__ void pop_window(Board& s) {
+    s.window = __builtin_amdgcn_alignbit(s.window_hi, s.window, 3);
+    s.window_hi >>= 3;
+}
 // cursor / 10 and cursor % 10 == 0 for cursor < 256 from one 24-bit multiply (full rate): cursor * 205 = 2048 * (cursor / 10)
 // + a remainder that is below 205 exactly when cursor is a multiple of ten (checked exhaustively in tests/test_boundary.py)
 __device__ __forceinline__ uint32_t tenths(uint32_t cursor) { return __umul24(cursor, 205u); }
@@ -202,6 +208,12 @@ __device__ __forceinline__ void pack_board(const Board& s, uint4& A, uint4& B) {
     B.y |= (s.state << 28) | (s.slot << 30);
     B.z = c[9] | (s.lines << 20) | (s.window_hi << 28);
     B.w = s.window;
+}
+// next_window(refill) on the packed state: piece word `word` becomes the window (its low 32 bits are B.w, its bits 32..35
+// are B.z[31:28])
+__device__ __forceinline__ void patch_window(uint4& B, uint64_t word) {
+    B.w = (uint32_t)word;
+    B.z = (B.z & 0x0FFFFFFFu) | ((uint32_t)(word >> 32) << 28);
 }
 
 // rows (interchange, u16[20], bit x = column x) <-> columns
