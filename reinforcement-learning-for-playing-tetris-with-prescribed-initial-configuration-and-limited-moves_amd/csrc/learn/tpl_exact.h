@@ -1,7 +1,10 @@
-// tpl_exact.h -- the exact depth-first search the five proof units share (exact.hip, exact_nodes.hip, exact_window.hip,
-// ntuple_exact.hip, ntuple_window.hip; include/tpl_learn.h states their rules): the stack record, the search, the write-out of a
-// win's path and the argument checks the entries have in common.  What a unit keeps is its frame -- where the root, the piece list
-// and the game (L, M) come from, and what the result means -- and its ORDER: what a node's child is worth.
+// tpl_exact.h -- what the five proof units share (exact.hip, exact_nodes.hip, exact_window.hip, ntuple_exact.hip, ntuple_window.hip;
+// include/tpl_learn.h states their rules): the stack record, the exact depth-first search, the write-out of a win's path, the two
+// FRAMES a search stands in -- prove_root around a configuration's whole game, prove_window around the pieces a state's window shows
+// --, the limited units' argument record and the argument checks the entries have in common.  What a unit keeps is its argument
+// record, its entry and its ORDER: what a node's child is worth.  The linear order is here (LinearOrder); the table's is
+// tpl_exact_table.h's, so that the linear units do not parse the table geometry.  exact_nodes.hip has a frame of its own: a finished
+// node's exit, a game per node and a stride over the launch.
 //
 // The search is of the game (L, M) from a root with 0 lines and 0 moves, in the bounded form (tpl_placement.h: kUnitBound): the move
 // bound's prune is what makes it finite in practice and its proof is the bound's.  Within the prune it visits every running board,
@@ -27,7 +30,9 @@
 // without scratch, since everything the 34 children share sits in SGPRs (tools/kernel_resources.sh;
 // profiles/learner/exact_refactor_isa.log).
 //
-// An ORDER is a small struct of the unit's, the same in every lane:
+// An ORDER is a small struct the unit's kernel names, the same in every lane:
+//   Order(p)     a frame builds it from the unit's argument record just ahead of the search -- a window frame only for a board it
+//                searches --, so what the order reads of the record is loaded there;
 //   Carry        what a record keeps of the path for the order: the linear weights' carry word, or NoCarry (a table's value reads the
 //                board alone), which takes no room in the record;
 //   child(...)   the child of a record by placement (r, l) of piece `cur` in the game (L, B) -- the board the move leaves, dead turned
@@ -45,6 +50,21 @@ constexpr int kExactMaxMoves = 254;                           // M's limit (tpl_
 constexpr int kExactMaxNodes = TPL_EXACT_MAX_NODES;
 static_assert(kUnitBound, "the exact search is a unit of the bounded form");
 static_assert(kMaxPlacements <= kExactWave, "a lane per child");
+
+// A unit built with TPL_EXACT_LIMITED_UNIT (the *_limited*.hip files) is its twin's text around the LIMITED search.  The macro chooses
+// here, once: kLimitedUnit, which the unit hands its frame; the _limited in its kernels' and its entry's names; and TPL_LIMITED(...),
+// the text only the limited entry has -- its three extra parameters.  Everything else is `if constexpr` on the constant.
+#ifdef TPL_EXACT_LIMITED_UNIT
+constexpr bool kLimitedUnit = true;
+#define TPL_EXACT_LIMITED _limited
+#define TPL_EXACT_LIMITED_NAME "_limited"
+#define TPL_LIMITED(...) __VA_ARGS__
+#else
+constexpr bool kLimitedUnit = false;
+#define TPL_EXACT_LIMITED
+#define TPL_EXACT_LIMITED_NAME ""
+#define TPL_LIMITED(...)
+#endif
 
 // one depth of the stack
 template <typename Carry>
@@ -103,6 +123,8 @@ struct LinearOrder {
 #pragma unroll
         for (int q = 0; q < F; ++q) w[q] = weights[q];
     }
+    template <typename Args>     // of a frame's argument record
+    __device__ __forceinline__ explicit LinearOrder(const Args& p) : LinearOrder(p.weights, p.spare_weight) {}
     __device__ __forceinline__ float child(const Frame<Carry>& node, uint32_t cur, const uint8_t*, uint32_t r, uint32_t l,
                                            const tpl::ShapeWord* shape, uint32_t L, uint32_t B, tpl::Board& s, Carry& carry) const {
         tpl::unpack_board(node.a, node.b, s);
@@ -116,10 +138,10 @@ struct LinearOrder {
     }
 };
 
-struct Found {
-    uint32_t nodes, length, last;                             // expansions, all iterations; the winning length, 0 if none, and its last move
-    bool capped;
-    uint32_t limit;                                           // the limited search alone: the K of the last iteration begun, 0 if none
+struct Found {                   // as declared: the result of no search at all
+    uint32_t nodes = 0u, length = 0u, last = kNoMove;         // expansions, all iterations; the winning length, 0 if none, and its last move
+    bool capped = false;
+    uint32_t limit = 0u;                                      // the limited search alone: the K of the last iteration begun, 0 if none
 };
 
 // The LIMITED search's two numbers (include/tpl_learn.h: tpl_placement_exact_limited): the first discrepancy limit of every budget and
@@ -128,6 +150,20 @@ struct Discrepancy {
     uint32_t first, growth;
 };
 constexpr uint32_t kLimitTop = 65535u;                        // K's clamp; a K >= 8,382 never cuts, so the clamp ends nothing
+
+// a limited entry's argument record: its twin's, the two numbers of the limited search and one more output
+template <typename Twin>
+struct LimitedArgs : Twin {
+    uint32_t first_limit;        // in [0, 65535]: the K every budget starts with
+    uint32_t growth;             // 0: K + 1 ("add"); 1: max(1, 2 K) ("double")
+    int32_t* limit;              // [n]: the K of the last iteration begun, 0 where nothing was searched
+};
+// what a frame hands the search of a record's two numbers; a plain record has none, and the plain search reads none
+template <bool Limited, typename Args>
+__device__ __forceinline__ Discrepancy discrepancy_of(const Args& p) {
+    if constexpr (Limited) return Discrepancy{p.first_limit, p.growth};
+    else return Discrepancy{0u, 0u};
+}
 
 // The search of the game (L, M) from `root` -- 0 lines, 0 moves -- whose piece at depth d is s_pieces[d]; every argument is the same
 // in every lane.  `need` is need(root), and need > M is decided without a node.  The caller has filled s_shape and s_pieces, entries
@@ -265,6 +301,112 @@ __device__ __forceinline__ void write_path(const Frame<Carry>* stack, const Foun
     }
 }
 
+// The ROOT FRAME (exact.hip, ntuple_exact.hip): configuration blockIdx.x of the record `p` -- its rows as a full reset deals them, its
+// whole piece list, the game (L, M) -- searched under `order`, and what the search found written out.  The stack is the launch's
+// dynamic LDS, M records of 80 bytes; the shape table and the list are static.  A limited unit's record is LimitedArgs of its twin's.
+template <typename Order, bool Limited, typename Args>
+__device__ __forceinline__ void prove_root(const Args& p) {
+    using Stack = Frame<typename Order::Carry>;
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+    Stack* const stack = reinterpret_cast<Stack*>(s_raw);      // [M]
+    __shared__ tpl::ShapeWord s_shape[32];
+    __shared__ uint8_t s_pieces[kExactMaxMoves + 2];
+    const uint32_t lane = threadIdx.x, i = blockIdx.x;         // the grid is n blocks of one wave
+    const uint32_t L = p.L, M = p.M;
+    if (lane < 32) s_shape[lane] = tpl::kShapeTable[lane];
+    load_pieces(s_pieces, p.pieces, (size_t)i * (M + 1u), M, lane);
+
+    tpl::Board root;                                           // the root, as a full reset deals it: the same in every lane
+    tpl::rows_to_cols(p.rows + (size_t)i * tpl::kRows, root.c);
+    fresh_root(root);
+    const uint32_t bound = need_of(root, L);
+
+    const Order order(p);
+    const Found f = search<Order, Limited>(order, stack, s_pieces, s_shape, root, bound, L, M, p.max_nodes, p.shortest, lane,
+                                           discrepancy_of<Limited>(p));
+    if (lane == 0) {
+        p.solved[i] = f.length != 0u ? (uint8_t)1 : (uint8_t)0;
+        p.proved[i] = f.capped ? (uint8_t)0 : (uint8_t)1;
+        p.solution_len[i] = (int32_t)f.length;
+        p.bound[i] = (int32_t)bound;
+        p.nodes[i] = f.nodes;
+        if constexpr (Limited) p.limit[i] = (int32_t)f.limit;
+    }
+    write_path(stack, f, p.actions + (size_t)i * M, M, lane);
+}
+
+constexpr int kWindowWave = kExactWave;
+constexpr int kWindowDepth = tpl::kWindowEntries;             // 12: the longest horizon, and the plan's width
+constexpr int kWindowList = 16;                               // the list in LDS: entries 0 .. H - 1 of the window, 0 behind them
+static_assert(kWindowDepth == TPL_WINDOW_PLAN, "the plan is as wide as the window");
+static_assert(kWindowDepth < kWindowList, "entry 12 of the list exists");
+
+// The WINDOW FRAME (exact_window.hip, ntuple_window.hip): board blockIdx.x of the packed planes, a running board of the game
+// (p.L, p.M) with `lines` cleared after `moves` moves.  It has rem = M - moves moves left and its window shows known = 12 - moves mod
+// 10 true pieces, so H = min(known, rem) moves have their piece known: the HORIZON.  The board is searched as a fresh root of the
+// shifted game (L - lines, H) with shortest = 1, its list window entries 0 .. H - 1, and the verdict says what the result means.  No
+// path is longer than twelve entries: the stack is twelve records of STATIC LDS beside the shape table and the list.
+//
+// One list rule for every order: sixteen entries, the window's below H and 0 from H on.  An order that values a child under the
+// piece it will play (TableOrder) reads list entry d + 1 before it knows whether the child runs; a child that runs has
+// d + 1 < B <= H, a true piece of the episode, and any other child's value is its reward alone.  So the read reaches entry H at most
+// -- index 12 where H = 12 -- and that entry is a defined 0, never a piece the agent does not know and never stale LDS.  The linear
+// order reads nothing behind `cur`.
+template <typename Order, bool Limited, typename Args>
+__device__ __forceinline__ void prove_window(const Args& p) {
+    __shared__ Frame<typename Order::Carry> stack[kWindowDepth];
+    __shared__ tpl::ShapeWord s_shape[32];
+    __shared__ uint8_t s_pieces[kWindowList];
+    const uint32_t lane = threadIdx.x, i = blockIdx.x;         // the grid is n blocks of one wave
+    const uint4 A = p.a[i], B = p.b[i];                        // one address for the wave
+    tpl::Board at;
+    tpl::unpack_board(A, B, at);
+    const uint32_t lines = uniform(at.lines), moves = uniform(at.moves), state = uniform(at.state);
+    const bool skipped = p.skip != nullptr && uniform(p.skip[i]) != 0u;
+    // a board that is not running -- or that no environment of this game holds -- is finished: nothing to search
+    const bool live = state == tpl::ST_RUNNING && lines < p.L && moves < p.M;
+    const uint32_t known = (uint32_t)tpl::kWindowEntries - moves % (uint32_t)tpl::kWindowStride;
+    const uint32_t rem = live ? p.M - moves : 0u;
+    const uint32_t H = min(known, rem);                       // 0 for a finished board
+    const uint32_t L = live ? p.L - lines : 1u;                // of the shifted game (L - lines, H)
+
+    tpl::Board root;                                           // the board as the root of its shifted game: the same in every lane
+#pragma unroll
+    for (int x = 0; x < tpl::kCols; ++x) root.c[x] = uniform(at.c[x]);
+    fresh_root(root);
+    const uint32_t need = live ? need_of(root, L) : 0u;        // need(board): no win is shorter
+
+    const bool last_known = H == rem;                          // the window reaches the end of the game
+    if (lane == 0) {                                           // what the search does not decide, before it
+        p.bound[i] = (int32_t)need;
+        p.horizon[i] = (uint8_t)H;
+    }
+
+    Found f;
+    if (live && !skipped) {
+        if (lane < 32) s_shape[lane] = tpl::kShapeTable[lane];
+        // list entry `lane`: the window's, masked as move_board masks it, below the horizon and 0 from it on
+        const unsigned long long window = ((unsigned long long)at.window_hi << 32) | at.window;
+        if (lane < (uint32_t)kWindowList) s_pieces[lane] = lane < H ? (uint8_t)((uint32_t)(window >> (3u * lane)) & 7u) : (uint8_t)0;
+        const Order order(p);
+        f = search<Order, Limited>(order, stack, s_pieces, s_shape, root, need, L, H, p.max_nodes, 1u, lane,
+                                   discrepancy_of<Limited>(p));                                    // the game (L, H), shortest
+    }
+    const bool solved = f.length != 0u, proved = !skipped && !f.capped;
+    if (lane == 0) {
+        p.solved[i] = solved ? (uint8_t)1 : (uint8_t)0;
+        p.proved[i] = proved ? (uint8_t)1 : (uint8_t)0;
+        p.solution_len[i] = (int32_t)f.length;
+        p.nodes[i] = f.nodes;
+        p.verdict[i] = !live || skipped ? (uint8_t)TPL_WINDOW_NONE
+                       : solved               ? (uint8_t)TPL_WINDOW_WIN
+                       : proved && last_known ? (uint8_t)TPL_WINDOW_LOSS
+                                              : (uint8_t)TPL_WINDOW_OPEN;
+        if constexpr (Limited) p.limit[i] = (int32_t)f.limit;
+    }
+    write_path(stack, f, p.plan + (size_t)i * kWindowDepth, (uint32_t)kWindowDepth, lane);      // the plan
+}
+
 // What every entry of the five units refuses of n, the game and the node budget, in the order they all test them; `name` leads the
 // message.  A launch is `waves_each` workgroups for each of n, and `each` says so in the refusal; n_cfg is 1 where there is no pool.
 inline int check_search(const char* name, int64_t n, int64_t waves_each, const char* each, int64_t n_cfg, int32_t L, int32_t M,
@@ -286,6 +428,24 @@ inline int check_counts(const char* name, const int32_t* solution_len, const int
     return TPL_OK;
 }
 
+// what the two table entries refuse of a table's entry count, first of all, and of the rewards and gamma
+inline int check_table_form(const char* name, int64_t entries) {
+    if (entries != TPL_NTUPLE_ENTRIES && entries != TPL_NTUPLE_ENTRIES_3X3 && entries != TPL_NTUPLE_ENTRIES_FEAT &&
+        entries != TPL_NTUPLE_ENTRIES_BUDGET)
+        return fail_msg(TPL_ERR_ARG,
+                        "%s: entries must be %d (\"2x4\"), %d (\"3x3\"), %d (\"feat\") or %d (\"feat+spare\"), the four plain forms -- a sum "
+                        "or a staged table orders no search --, got %lld",
+                        name, (int)TPL_NTUPLE_ENTRIES, (int)TPL_NTUPLE_ENTRIES_3X3, (int)TPL_NTUPLE_ENTRIES_FEAT,
+                        (int)TPL_NTUPLE_ENTRIES_BUDGET, (long long)entries);
+    return TPL_OK;
+}
+inline int check_table_numbers(const char* name, float r_line, float r_win, float r_lose, float gamma) {
+    if (!(r_line - r_line == 0.0f) || !(r_win - r_win == 0.0f) || !(r_lose - r_lose == 0.0f))
+        return fail_msg(TPL_ERR_ARG, "%s: r_line, r_win and r_lose must be finite", name);
+    if (!(gamma - gamma == 0.0f)) return fail_msg(TPL_ERR_ARG, "%s: gamma must be finite", name);
+    return TPL_OK;
+}
+
 // what every limited entry refuses of its own three arguments, after its twin's checks of n, the game and the node budget
 inline int check_discrepancy(const char* name, int32_t first_limit, int32_t growth, const int32_t* limit) {
     if (first_limit < 0 || first_limit > (int32_t)kLimitTop)
@@ -295,5 +455,15 @@ inline int check_discrepancy(const char* name, int32_t first_limit, int32_t grow
     if ((uintptr_t)limit & 3u) return fail_msg(TPL_ERR_ARG, "%s: limit must be 4-byte aligned", name);
     return TPL_OK;
 }
+
+// the last of an entry's checks: a limited record takes its three arguments, checked; a plain one has none to take
+template <typename Twin>
+inline int take_limited(const char* name, LimitedArgs<Twin>& p, int32_t first_limit, int32_t growth, int32_t* limit) {
+    if (const int rc = check_discrepancy(name, first_limit, growth, limit)) return rc;
+    p.first_limit = (uint32_t)first_limit; p.growth = (uint32_t)growth; p.limit = limit;
+    return TPL_OK;
+}
+template <typename Args>
+inline int take_limited(const char*, Args&) { return TPL_OK; }
 
 }  // namespace tpl_learn

@@ -252,6 +252,39 @@ def _discrepancy(discrepancy, first_limit):
     return None if discrepancy is None else (DISCREPANCY_GROWTH[discrepancy], int(first_limit))
 
 
+def _limited_parts(limited, names: tuple) -> tuple:
+    """What a launch splices in for limited = (growth, first_limit): the entry name's suffix, the arguments first_limit and growth, which
+    stand ahead of the entry's outputs, and the output names with `limit` behind `nodes`.  For limited = None, the plain entry:
+    no suffix, no arguments, the names as they are."""
+    if limited is None:
+        return "", (), names
+    at = names.index("nodes") + 1
+    return "_limited", (limited[1], limited[0]), names[:at] + ("limit",) + names[at:]
+
+
+ROOT_OUTPUTS = ("solved", "proved", "solution_len", "actions", "bound", "nodes")
+
+
+def _root_buffers(n: int, M: int, d, limited=None) -> dict:
+    """The outputs of a search from n roots of the game (L, M), uninitialised on d; `limit` with them for a limited search."""
+    import torch
+    kinds = dict(solved=torch.uint8, proved=torch.uint8, solution_len=torch.int32, actions=torch.uint8, bound=torch.int32,
+                 nodes=torch.int32)
+    if limited is not None:
+        kinds["limit"] = torch.int32
+    return {k: torch.empty((n, M) if k == "actions" else n, dtype=t, device=d) for k, t in kinds.items()}
+
+
+def _root_result(out: dict, shortest) -> dict:
+    """The filled buffers of _root_buffers as prove_configs' dict: the flags as bool, optimal, unwinnable and solution."""
+    import torch
+    out["solved"], out["proved"] = out["solved"].view(torch.bool), out["proved"].view(torch.bool)
+    out["optimal"] = out["solved"] & bool(shortest)
+    out["unwinnable"] = out["proved"] & ~out["solved"]
+    out["solution"] = _solution(out["actions"])
+    return out
+
+
 def prove_configs(rows, pieces, L: int, M: int, weights=None, max_nodes: int = 1 << 16, shortest: bool = True,
                   spare_weight: float = 0.0, device="cuda:0", validate: bool = True) -> dict:
     """Search every configuration's whole game depth first and exactly (the rule: include/tpl_learn.h, tpl_placement_exact;
@@ -310,24 +343,13 @@ def _prove_configs(rows, pieces, L: int, M: int, weights=None, max_nodes: int = 
     rows = _device_rows(rows, d)
     pieces = _device_pieces(pieces, n, M, d, validate)
     wt = torch.from_numpy(_learn_lib.padded_weights(w)).to(d)
-    out = dict(solved=torch.empty(n, dtype=torch.uint8, device=d), proved=torch.empty(n, dtype=torch.uint8, device=d),
-               solution_len=torch.empty(n, dtype=torch.int32, device=d), actions=torch.empty((n, M), dtype=torch.uint8, device=d),
-               bound=torch.empty(n, dtype=torch.int32, device=d), nodes=torch.empty(n, dtype=torch.int32, device=d))
+    out = _root_buffers(n, M, d, limited)
     stream = torch._C._cuda_getCurrentRawStream(d.index if d.index is not None else torch.cuda.current_device())
-    if limited is None:
-        _learn_lib.check(_learn_lib.entry("exact", w.shape[0])(
-            rows.data_ptr(), pieces.data_ptr(), n, L, M, wt.data_ptr(), spare_weight, max_nodes, int(bool(shortest)),
-            *(out[k].data_ptr() for k in ("solved", "proved", "solution_len", "actions", "bound", "nodes")), stream))
-    else:
-        out["limit"] = torch.empty(n, dtype=torch.int32, device=d)
-        _learn_lib.check(_learn_lib.entry("exact_limited", w.shape[0])(
-            rows.data_ptr(), pieces.data_ptr(), n, L, M, wt.data_ptr(), spare_weight, max_nodes, int(bool(shortest)), limited[1],
-            limited[0], *(out[k].data_ptr() for k in ("solved", "proved", "solution_len", "actions", "bound", "nodes", "limit")), stream))
-    out["solved"], out["proved"] = out["solved"].view(torch.bool), out["proved"].view(torch.bool)
-    out["optimal"] = out["solved"] & bool(shortest)
-    out["unwinnable"] = out["proved"] & ~out["solved"]
-    out["solution"] = _solution(out["actions"])
-    return out
+    suffix, limits, names = _limited_parts(limited, ROOT_OUTPUTS)
+    _learn_lib.check(_learn_lib.entry("exact" + suffix, w.shape[0])(
+        rows.data_ptr(), pieces.data_ptr(), n, L, M, wt.data_ptr(), spare_weight, max_nodes, int(bool(shortest)), *limits,
+        *(out[k].data_ptr() for k in names), stream))
+    return _root_result(out, shortest)
 
 
 def _node_tensors(rows, lines, moves, entry, pieces, M: int, d, validate: bool):
@@ -389,25 +411,16 @@ def prove_nodes(rows, lines, moves, entry, pieces, L: int, M: int, weights=None,
     d = torch.device(device)
     rows, lines, moves, entry, pieces, n, n_cfg = _node_tensors(rows, lines, moves, entry, pieces, M, d, validate)
     wt = torch.from_numpy(_learn_lib.padded_weights(w)).to(d)
-    out = dict(solved=torch.empty(n, dtype=torch.uint8, device=d), proved=torch.empty(n, dtype=torch.uint8, device=d),
-               solution_len=torch.empty(n, dtype=torch.int32, device=d), actions=torch.empty((n, M), dtype=torch.uint8, device=d),
-               bound=torch.empty(n, dtype=torch.int32, device=d), nodes=torch.empty(n, dtype=torch.int32, device=d))
+    out = _root_buffers(n, M, d)
     stream = torch._C._cuda_getCurrentRawStream(d.index if d.index is not None else torch.cuda.current_device())
     _learn_lib.check(_learn_lib.entry("exact_nodes", w.shape[0])(
         rows.data_ptr(), lines.data_ptr(), moves.data_ptr(), entry.data_ptr(), pieces.data_ptr(), n, n_cfg, L, M, wt.data_ptr(),
-        spare_weight, max_nodes, int(bool(shortest)),
-        *(out[k].data_ptr() for k in ("solved", "proved", "solution_len", "actions", "bound", "nodes")), stream))
-    out["solved"], out["proved"] = out["solved"].view(torch.bool), out["proved"].view(torch.bool)
-    out["optimal"] = out["solved"] & bool(shortest)
-    out["unwinnable"] = out["proved"] & ~out["solved"]
-    out["solution"] = _solution(out["actions"])
-    return out
-
+        spare_weight, max_nodes, int(bool(shortest)), *(out[k].data_ptr() for k in ROOT_OUTPUTS), stream))
+    return _root_result(out, shortest)
 
 
 # ------------------------------------------------------------------------------------------------ the search over a state's window
 WINDOW_OUTPUTS = ("solved", "proved", "solution_len", "plan", "bound", "nodes", "horizon", "verdict")
-WINDOW_LIMITED_OUTPUTS = WINDOW_OUTPUTS[:6] + ("limit",) + WINDOW_OUTPUTS[6:]
 
 
 def _resident_planes(env):
@@ -441,14 +454,20 @@ def _window_launch(env, planes, features: int, wt, spare_weight: float, max_node
     import torch
     from . import _learn_lib
     stream = torch._C._cuda_getCurrentRawStream(env.device.index)
-    if limited is None:
-        _learn_lib.check(_learn_lib.entry("window_prove", features)(
-            planes[0], planes[1], env.num_envs, env.L, env.M, wt.data_ptr(), spare_weight, max_nodes,
-            None if skip is None else skip.data_ptr(), *(out[k].data_ptr() for k in WINDOW_OUTPUTS), stream))
-    else:
-        _learn_lib.check(_learn_lib.entry("window_prove_limited", features)(
-            planes[0], planes[1], env.num_envs, env.L, env.M, wt.data_ptr(), spare_weight, max_nodes, limited[1], limited[0],
-            None if skip is None else skip.data_ptr(), *(out[k].data_ptr() for k in WINDOW_LIMITED_OUTPUTS), stream))
+    suffix, limits, names = _limited_parts(limited, WINDOW_OUTPUTS)
+    _learn_lib.check(_learn_lib.entry("window_prove" + suffix, features)(
+        planes[0], planes[1], env.num_envs, env.L, env.M, wt.data_ptr(), spare_weight, max_nodes, *limits,
+        None if skip is None else skip.data_ptr(), *(out[k].data_ptr() for k in names), stream))
+
+
+def _window_result(env, out: dict) -> dict:
+    """The filled buffers of _window_buffers as window_prove's dict: the flags as bool, known and action."""
+    import torch
+    out["solved"], out["proved"] = out["solved"].view(torch.bool), out["proved"].view(torch.bool)
+    moves, _, _ = _plane_fields(*_resident_planes(env))
+    out["known"] = (12 - moves % 10).to(torch.uint8)
+    out["action"] = out["plan"][:, 0]
+    return out
 
 
 def _skip_mask(env, skip):
@@ -516,11 +535,7 @@ def _window_prove(env, weights=None, max_nodes: int = 1 << 12, spare_weight: flo
     wt = torch.from_numpy(_learn_lib.padded_weights(w)).to(env.device)
     out = _window_buffers(env.num_envs, env.device, limited)
     _window_launch(env, _state_ptrs(env), w.shape[0], wt, spare_weight, max_nodes, skip, out, limited)
-    out["solved"], out["proved"] = out["solved"].view(torch.bool), out["proved"].view(torch.bool)
-    moves, _, _ = _plane_fields(*_resident_planes(env))
-    out["known"] = (12 - moves % 10).to(torch.uint8)
-    out["action"] = out["plan"][:, 0]
-    return out
+    return _window_result(env, out)
 
 
 def _window_table(table, d):
@@ -538,15 +553,10 @@ def _ntuple_window_launch(env, planes, table, reward, gamma: float, max_nodes: i
     import torch
     from . import _learn_lib
     stream = torch._C._cuda_getCurrentRawStream(env.device.index)
-    if limited is None:
-        _learn_lib.check(_learn_lib.lib().tpl_ntuple_window_prove(
-            planes[0], planes[1], env.num_envs, env.L, env.M, table.data_ptr(), int(table.shape[0]), reward[0], reward[1], reward[2],
-            gamma, max_nodes, None if skip is None else skip.data_ptr(), *(out[k].data_ptr() for k in WINDOW_OUTPUTS), stream))
-    else:
-        _learn_lib.check(_learn_lib.lib().tpl_ntuple_window_prove_limited(
-            planes[0], planes[1], env.num_envs, env.L, env.M, table.data_ptr(), int(table.shape[0]), reward[0], reward[1], reward[2],
-            gamma, max_nodes, limited[1], limited[0], None if skip is None else skip.data_ptr(),
-            *(out[k].data_ptr() for k in WINDOW_LIMITED_OUTPUTS), stream))
+    suffix, limits, names = _limited_parts(limited, WINDOW_OUTPUTS)
+    _learn_lib.check(getattr(_learn_lib.lib(), "tpl_ntuple_window_prove" + suffix)(
+        planes[0], planes[1], env.num_envs, env.L, env.M, table.data_ptr(), int(table.shape[0]), *reward, gamma, max_nodes, *limits,
+        None if skip is None else skip.data_ptr(), *(out[k].data_ptr() for k in names), stream))
 
 
 def ntuple_window_prove(env, table, gamma: float = 1.0, reward=(1.0, 0.0, 0.0), max_nodes: int = 1 << 12, skip=None) -> dict:
@@ -580,7 +590,6 @@ def ntuple_window_prove_limited(env, table, discrepancy="add", first_limit: int 
 def _ntuple_window_prove(env, table, gamma: float = 1.0, reward=(1.0, 0.0, 0.0), max_nodes: int = 1 << 12, skip=None,
                         discrepancy=None, first_limit: int = 0) -> dict:
     """ntuple_window_prove and ntuple_window_prove_limited on their arguments; discrepancy None is the plain search."""
-    import torch
     from .lookahead import _boards, _state_ptrs
     _boards(env, "ntuple_window_prove")
     max_nodes = _max_nodes(max_nodes)
@@ -591,11 +600,7 @@ def _ntuple_window_prove(env, table, gamma: float = 1.0, reward=(1.0, 0.0, 0.0),
     skip = _skip_mask(env, skip)
     out = _window_buffers(env.num_envs, env.device, limited)
     _ntuple_window_launch(env, _state_ptrs(env), table, reward, gamma, max_nodes, skip, out, limited)
-    out["solved"], out["proved"] = out["solved"].view(torch.bool), out["proved"].view(torch.bool)
-    moves, _, _ = _plane_fields(*_resident_planes(env))
-    out["known"] = (12 - moves % 10).to(torch.uint8)
-    out["action"] = out["plan"][:, 0]
-    return out
+    return _window_result(env, out)
 
 
 class ProofPolicy:
@@ -1060,25 +1065,13 @@ def _ntuple_prove_configs(rows, pieces, L: int, M: int, table, gamma: float = 1.
     table = _exact_table(table, d)
     rows = _device_rows(rows, d)
     pieces = _device_pieces(pieces, n, M, d, validate)
-    out = dict(solved=torch.empty(n, dtype=torch.uint8, device=d), proved=torch.empty(n, dtype=torch.uint8, device=d),
-               solution_len=torch.empty(n, dtype=torch.int32, device=d), actions=torch.empty((n, M), dtype=torch.uint8, device=d),
-               bound=torch.empty(n, dtype=torch.int32, device=d), nodes=torch.empty(n, dtype=torch.int32, device=d))
+    out = _root_buffers(n, M, d, limited)
     stream = torch._C._cuda_getCurrentRawStream(d.index if d.index is not None else torch.cuda.current_device())
-    if limited is None:
-        _learn_lib.check(_learn_lib.lib().tpl_ntuple_exact(
-            rows.data_ptr(), pieces.data_ptr(), n, L, M, table.data_ptr(), int(table.shape[0]), r_line, r_win, r_lose, gamma, max_nodes,
-            int(bool(shortest)), *(out[k].data_ptr() for k in ("solved", "proved", "solution_len", "actions", "bound", "nodes")), stream))
-    else:
-        out["limit"] = torch.empty(n, dtype=torch.int32, device=d)
-        _learn_lib.check(_learn_lib.lib().tpl_ntuple_exact_limited(
-            rows.data_ptr(), pieces.data_ptr(), n, L, M, table.data_ptr(), int(table.shape[0]), r_line, r_win, r_lose, gamma, max_nodes,
-            int(bool(shortest)), limited[1], limited[0],
-            *(out[k].data_ptr() for k in ("solved", "proved", "solution_len", "actions", "bound", "nodes", "limit")), stream))
-    out["solved"], out["proved"] = out["solved"].view(torch.bool), out["proved"].view(torch.bool)
-    out["optimal"] = out["solved"] & bool(shortest)
-    out["unwinnable"] = out["proved"] & ~out["solved"]
-    out["solution"] = _solution(out["actions"])
-    return out
+    suffix, limits, names = _limited_parts(limited, ROOT_OUTPUTS)
+    _learn_lib.check(getattr(_learn_lib.lib(), "tpl_ntuple_exact" + suffix)(
+        rows.data_ptr(), pieces.data_ptr(), n, L, M, table.data_ptr(), int(table.shape[0]), r_line, r_win, r_lose, gamma, max_nodes,
+        int(bool(shortest)), *limits, *(out[k].data_ptr() for k in names), stream))
+    return _root_result(out, shortest)
 
 
 def tighten_pool(rows, pieces, solved, solution_len, M_new: int, bound=None, slack=None):

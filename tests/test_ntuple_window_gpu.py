@@ -149,15 +149,17 @@ def test_the_kernel_is_the_mirror_byte_for_byte(keys, n):
 
 
 def test_the_launches_cover_every_verdict_every_table_form_and_every_cap():
-    seen, forms, caps, sizes = set(), set(), set(), set()
+    seen, forms, caps, sizes, whole_window = set(), set(), set(), set(), False
     for keys, n in LAUNCHES:
         _, _, _, want = boards(keys)
         pick = (np.arange(n) * 37 + 5) % want["verdict"].shape[0]
         seen |= set(want["verdict"][pick].tolist())
+        whole_window |= bool(((want["horizon"][pick] == 12) & (want["nodes"][pick] > 0)).any())
         forms.add(G.TABLES[G.CASES[keys[0]]["table"]])
         caps.add((G.TABLES[G.CASES[keys[0]]["table"]][0], G.CASES[keys[0]]["max_nodes"]))
         sizes.add(n)
     assert seen == {0, 1, 2, 3} and sizes == {1, 63, 64, 65, 203}
+    assert whole_window                                        # a searched board with H = 12: the table order reads list entry 12, the 0
     assert {f for f, _ in forms} == {"2x4", "3x3", "feat", "feat+spare"} and {k for _, k in forms} == {"hashed", "linear", "zero", "huge"}
     assert {("feat", c) for c in (1, 64, 1024)} | {("feat+spare", c) for c in (1, 64, 1024)} | {("2x4", 1), ("2x4", 64), ("3x3", 1), ("3x3", 64)} <= caps
 

@@ -133,11 +133,12 @@ Parts:
               loaded into one process: the outputs of the six entries compared byte for byte on the ring of part ntuple_shape
               at 2^18 boards, then each entry timed in five rounds of the parent against itself and five of the parent against
               this build; a new median passes within the parent's own min-max or at most 2 % above the parent's median
-    exact_ab  --parent LIB: the ten entries of the five exact-search units (exact, exact_nodes, exact_window, ntuple_exact,
-              ntuple_window) of another build of the learner library against this tree's, both loaded into one process: carved
-              L=10 / M=40, 4,096 roots, and 4,096 nodes and resident boards ten moves on, max_nodes 2^12, the table entries under each
-              of the four plain forms; every output compared byte for byte, then each call timed by ntuple_shape_ab's protocol
-              (--no-timing: the comparison alone)
+    exact_ab  --parent LIB: the ten plain and the six limited entries of the five exact-search units (exact, exact_nodes,
+              exact_window, ntuple_exact, ntuple_window) of another build of the learner library against this tree's, both loaded
+              into one process: carved L=10 / M=40, 4,096 roots, and 4,096 nodes and resident boards ten moves on, max_nodes 2^12,
+              the table entries under each of the four plain forms, the limited ones at first_limit 0; every output compared byte
+              for byte (the limited under "add" and "double"), then each call timed by ntuple_shape_ab's protocol (the limited
+              under "add"; --no-timing: the comparison alone)
     labels    the proved move labels (tpl_placement_exact_labels, label_states) on the tight pool of the record (part bound's: carved
               L=10 / M=40, 65,536 configurations, seed 7, solved at width 16, tighten_pool(M_new=16)): the classical weights at one ply
               and at beam (3, 8) play one episode on 4,096 boards, label_states (max_nodes 2^12 a child) before every step -- per move
@@ -3711,11 +3712,13 @@ def part_ntuple_shape_ab(parent, rounds=5, reps=20, n=1 << 18):
 
 
 def part_exact_ab(parent, rounds=5, reps=3, boards=4096, log2_nodes=12, timing=True):
-    """The ten entries of the five exact-search units of another build of the learner library against this tree's, both loaded into
-    one process and reached through the package's own wrappers (the library handle is swapped under them): carved L = 10 / M = 40,
-    seed 7, `boards` configurations as roots, and as nodes and resident boards after ten moves of the classical one-ply player;
-    max_nodes 2^log2_nodes; the two table entries under each of the four plain forms (random tables: an order is an order).  Every
-    output is compared byte for byte; then (timing) each call is timed by ntuple_shape_ab's protocol."""
+    """The ten plain and the six limited entries of the five exact-search units of another build of the learner library against
+    this tree's, both loaded into one process and reached through the package's own wrappers (the library handle is swapped under
+    them): carved L = 10 / M = 40, seed 7, `boards` configurations as roots, and as nodes and resident boards after ten moves of the
+    classical one-ply player; max_nodes 2^log2_nodes; the table entries under each of the four plain forms (random tables: an order
+    is an order); the limited entries through the four *_limited wrappers at first_limit = 0.  Every output is compared byte for
+    byte, a limited entry's under "add" and under "double"; then (timing) each call is timed by ntuple_shape_ab's protocol, a
+    limited one under "add"."""
     import ctypes as C
     import numpy as np
     import torch
@@ -3756,24 +3759,40 @@ def part_exact_ab(parent, rounds=5, reps=3, boards=4096, log2_nodes=12, timing=T
         calls[f"tpl_ntuple_exact {form}"] = lambda t=table: T.ntuple_prove_configs(rows, pieces, L_, M_, t, max_nodes=cap, device=dev,
                                                                                   validate=False, **order)
         calls[f"tpl_ntuple_window_prove {form}"] = lambda t=table: T.ntuple_window_prove(env, t, max_nodes=cap, **order)
+    limited = {}                                                 # the limited entries: a call takes the growth rule, "add" unless told
+    for form, w in weights.items():
+        limited["tpl_placement_exact_limited" + form] = lambda rule, w=w: T.prove_configs_limited(
+            rows, pieces, L_, M_, discrepancy=rule, first_limit=0, weights=w, max_nodes=cap, device=dev, validate=False)
+        limited["tpl_placement_window_prove_limited" + form] = lambda rule, w=w: T.window_prove_limited(
+            env, discrepancy=rule, first_limit=0, weights=w, max_nodes=cap)
+    for form, table in tables.items():
+        limited[f"tpl_ntuple_exact_limited {form}"] = lambda rule, t=table: T.ntuple_prove_configs_limited(
+            rows, pieces, L_, M_, t, discrepancy=rule, first_limit=0, max_nodes=cap, device=dev, validate=False, **order)
+        limited[f"tpl_ntuple_window_prove_limited {form}"] = lambda rule, t=table: T.ntuple_window_prove_limited(
+            env, t, discrepancy=rule, first_limit=0, max_nodes=cap, **order)
+    for name, call in limited.items():
+        calls[name] = lambda rule="add", call=call: call(rule)
 
-    def run(which, name):
+    def run(which, name, *rule):
         m._handle = libs[which]
         try:
-            return calls[name]()
+            return calls[name](*rule)
         finally:
             m._handle = libs["new"]
 
     lines_, equal = [], {}
     for name in calls:                                           # byte for byte, every tensor the wrapper returns
-        got = {}
-        for which in ("parent", "new"):
-            got[which] = run(which, name)
-            torch.cuda.synchronize()
-        equal[name] = set(got["parent"]) == set(got["new"]) and all(torch.equal(got["parent"][k], got["new"][k]) for k in got["new"])
-        nodes = got["new"]["nodes"].double()
+        rules = [("double",), ("add",)] if name in limited else [()]
+        equal[name] = True
+        for rule in rules:
+            got = {}
+            for which in ("parent", "new"):
+                got[which] = run(which, name, *rule)
+                torch.cuda.synchronize()
+            equal[name] &= set(got["parent"]) == set(got["new"]) and all(torch.equal(got["parent"][k], got["new"][k]) for k in got["new"])
+        nodes = got["new"]["nodes"].double()                     # of the last rule: "add", the one timed
         lines_.append(dict(entry=name, outputs_equal=equal[name], searches=int(nodes.numel()), nodes=int(nodes.sum()),
-                           capped=int((nodes == cap).sum())))
+                           capped=int((nodes == cap).sum()), **(dict(compared_under=["double", "add"]) if name in limited else {})))
         print(json.dumps(lines_[-1]), file=sys.stderr, flush=True)
     out = dict(part="exact_ab", boards=boards, max_nodes=f"2^{log2_nodes}", running_nodes=int(running.sum()), lines=lines_,
                every_output_equal=all(equal.values()))
