@@ -53,7 +53,7 @@ static inline size_t record_stride(int M) { return (size_t)1 << record_stride_sh
 //   0  every board's state words and actions are requested
 //   1  the boards whose window runs out with this move are noted (a test on the move counter, nothing is requested)
 //   2  the moves are computed (registers and LDS only); the window is popped
-//   3  reward / done / cleared are written
+//   3  reward / done / cleared are written; the block's tally of finished episodes leaves with the last wave to get here
 //   4  one record per board that needs one is requested: the pool record of a board that finished (auto-reset), or else
 //      the piece word of a board whose window ran out; a board never needs both
 //   5  the state words are written
@@ -202,6 +202,31 @@ __global__ __launch_bounds__(kThreads) void step_kernel(const StepArgs p) {
         if (p.cleared) p.cleared[i] = (uint8_t)n_clear[k];
     }
 
+    // The block's statistics of the episodes that finished in this step -> one sharded 64-bit atomic per counter that is not
+    // zero.  They leave as soon as they are complete, not behind the block's last state store: a wave whose moves are over has
+    // made all its adds to s_stat and counts itself in, and the wave that finds all the others counted holds the block's sums
+    // and sends them, ahead of its record region and its state stores.  No barrier at the end of the kernel: that barrier,
+    // then s_stat, then atomics that travel past the XCD's L2 were the tail of the block's last wave (profiles/NOTES.md,
+    // round 10).  LDS operations of a wave are performed in the order it issues them; the fences
+    // say so to the compiler, at workgroup scope and for LDS only (they wait for no store).
+    // The count of waves shares s_stat[0] with the count of episodes: a block finishes at most 512 * 4 of them, the waves count
+    // in units of 2^16 above that (a word of its own would be the block's only LDS past 13,584 bytes at 256 threads).
+    {
+        constexpr uint32_t kArrival = 1u << 16;
+        static_assert(kThreads * kBpl < (int)kArrival, "the block's episodes stay below the waves' unit");
+        const uint32_t lane = threadIdx.x & 63;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+        uint32_t arrived = 0;
+        if (lane == 0) arrived = __hip_atomic_fetch_add(&s_stat[0], kArrival, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (__builtin_amdgcn_readfirstlane(arrived) / kArrival == kThreads / 64 - 1) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+            if (lane < 4) {
+                const uint32_t v = s_stat[lane] & (lane == 0 ? kArrival - 1u : ~0u);
+                if (v) atomicAdd(&p.stats[(size_t)(blockIdx.x % kStatShards) * kStatStride + lane], (unsigned long long)v);
+            }
+        }
+    }
+
     // phase 4: reset()/load_warm_reset() (:438-449) of the boards that finished, and the piece word of the boards that go
     // on with a window that ran out.  A board that finished takes its whole state from its new record, so no board needs
     // both, and both are "hash (board, birth) -> record address -> load": ONE hash per board, its inputs selected by what
@@ -309,18 +334,7 @@ __global__ __launch_bounds__(kThreads) void step_kernel(const StepArgs p) {
         }
         if (count > 0) obs::store_span<Obs>(rows, lane, count, wave_base, lines_left, (Obs*)p.obs);
     }
-    // per-block statistics of the episodes that finished in this step -> one sharded 64-bit atomic per counter.  s_stat[0]
-    // counts those episodes, so it says whether any lane of the block finished one: a plain barrier and that word, where
-    // __syncthreads_or(finished) cost every wave a cross-lane reduction, 256 bytes of LDS and three barriers
-    // (0.12 us on the launch at 2^20 boards, profiles/r08_step)
-    __syncthreads();
-    if (s_stat[0] != 0) {
-        if (threadIdx.x < 4) {
-            const uint32_t v = s_stat[threadIdx.x];
-            if (v) atomicAdd(&p.stats[(size_t)(blockIdx.x % kStatShards) * kStatStride + threadIdx.x],
-                             (unsigned long long)v);
-        }
-    }
+    // (the block's statistics left behind phase 3: nothing of the block waits here)
 #ifdef TPL_DIAG_CLOCK
     __builtin_amdgcn_s_waitcnt(0);           // the stores have been acknowledged
     TPL_STAMP(5);
